@@ -9,11 +9,13 @@ batch through lsm2d_align_batch with the clouds already resident in HBM and NEW 
 step with identical poses every time, which the library answers from what it kept, is the labelled
 `same_poses_every_step` block).  With N GPUs every rank aligns its own 1000 scans (weak scaling) against
 the map broadcast from rank 0 over RCCL; there is no data-path collective.
-Blocks beside the headline on the default N=1 line: same_poses_every_step, sum_order_1 (the reference's
-order of summation: bitwise the sequential fp32 oracle), pipelined (two batches in flight), streamed
-(ranges in, poses out), also (configs[4], configs[3]), cpu_baseline (+ all_cores).
+A plain run sets up, warms up, times the K steps and prints the headline line (with its pose gate and the
+roofline block, which take no runs of their own).  Blocks beside the headline on the N=1 line, with --full:
+same_poses_every_step, sum_order_1 (the reference's order of summation: bitwise the sequential fp32 oracle),
+pipelined (two batches in flight), streamed (ranges in, poses out), also (configs[4], configs[3]),
+cpu_baseline (+ all_cores).  --dump-outputs DIR writes the last timed step's results as .npy files.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 The roofline block: the map (0.8 MB of coordinates at 1e5 points) is served from every XCD's L2, so
@@ -245,6 +247,25 @@ def build_roofline(role, finder, scans, map_points, iterations, beams, cauchy, n
         roof["warning"] = warn
         print("bench.py: " + warn, file=sys.stderr)
     return roof
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir: str, res, seed: int = 0) -> None:
+    """--dump-outputs: the arrays the timed call hands its caller (BatchResult pose [n, 3], information [n, 3, 3], status [n], iterations [n]) as float32 .npy
+    files.  Beyond DUMP_LIMIT_BYTES in all, the same seeded sample of rows of every array (its row numbers in sample_index.npy, float64)."""
+    arrays = {"pose": res.pose, "information": res.information, "status": res.status, "iterations": res.iterations}
+    arrays = {k: np.asarray(v).astype(np.float32) for k, v in arrays.items()}
+    n = len(arrays["pose"])
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        np.save(os.path.join(out_dir, "sample_index.npy"), keep.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def measure_pipelined(ctx, prep_a, prep_b, x0_sets, want_sets, args, roof) -> dict:
@@ -490,7 +511,13 @@ def main() -> None:
     ap.add_argument("--stream-batches", type=int, default=4, help="--stream: distinct range batches cycled through (each has its own truth; every step is gated)")
     ap.add_argument("--no-streamed", action="store_true", help="skip the `streamed` block (the --stream pipeline in short, after the timed region)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the `pipelined` block (the same resident step with two batches in flight, after the timed region)")
-    ap.add_argument("--no-also", action="store_true", help="the default N=1 line carries an `also` block -- BASELINE configs[4] (1000 scans vs a 1M-point map, 3 steps) and "
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline (N=1): the same_poses_every_step, sum_order_1, pipelined, streamed and also blocks and the cpu_baseline leg; "
+                         "a plain run (the default) sets up, warms up, times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pose, information, status, iterations) as DIR/<name>.npy in float32 "
+                         "(rank 0's alignments; a seeded sample of rows, with sample_index.npy, beyond 64 MB)")
+    ap.add_argument("--no-also", action="store_true", help="the --full N=1 line carries an `also` block -- BASELINE configs[4] (1000 scans vs a 1M-point map, 3 steps) and "
                                                               "configs[3] (65 536 candidates over 2 048 scans, Cauchy 0.05, 1 step), each with its own parity gate, kernel ms, clock and roofline; this skips it")
     ap.add_argument("--pose-sets", type=int, default=8,
                     help="distinct sets of start poses the timed steps cycle through (same scans, new initial guesses of the same spread): every step uploads its start poses and "
@@ -616,6 +643,8 @@ def main() -> None:
     robust = api.RobustifierCauchy(args.cauchy) if args.cauchy > 0 else None
     aligner.param_slice_processors.append(api.AlignerSliceProcessorLaser2D(finder, min_num_correspondences=10, robustifier=robust))
     if args.stream:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the resident-input step only (not --stream)")
         if world != 1 or args.role != "A" or args.finder != "projective" or strong:
             raise SystemExit("--stream: one GPU, role A, projective finder")
         run_stream(ctx, api, synth, torch, world_geom, map_set, map_dev, aligner, args, side)
@@ -706,6 +735,10 @@ def main() -> None:
     t_spin = time.perf_counter()
     while time.perf_counter() - t_spin < args.spinup_s:
         step(); spinup_steps += 1
+    # ... finishing the rotation of pose sets, so that the warm-up starts at set 0 whatever the spin-up's length: the timed steps see the same start poses
+    # from run to run (--dump-outputs compares the last one's results between builds), and no step repeats the poses of the step before it
+    while step_state["i"] % n_sets:
+        step(); spinup_steps += 1
     for _ in range(args.warmup):
         res = step()
     torch.cuda.synchronize()
@@ -750,6 +783,8 @@ def main() -> None:
     rank_note("timed_done", ms_per_step=elapsed / args.steps * 1e3, steps=args.steps)
     if gc_was_on:
         gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, args.seed)      # (before anything else runs `prepared`: its result arrays are shared between runs)
     if gather_pad:
         assert gathered is not None and gathered.shape == (gather_pad * world, 3)
     per_rank_ms = None
@@ -839,7 +874,7 @@ def main() -> None:
             return {"value": args.scans * args.steps / dt, "unit": "alignments/s", "ms_per_step": dt / args.steps * 1e3, "steps": args.steps, "kernel_ms": float(np.mean(km)),
                     "estimate_launched_in_last_step": bool(ctx.get_option("last_cull_estimate")),
                     "note": "what no consumer submits (identical start poses step after step); kept beside the headline because rounds 4-5 reported it as the headline"}
-        # The extras of the default line (profiler passes run --no-also).  None of them may cost the headline its line: a failure inside one is reported IN its block.
+        # The extras of the --full line (profiler passes run without --full, or with --no-also).  None of them may cost the headline its line: a failure inside one is reported IN its block.
         def extra(name, fn):
             try:
                 out[name] = fn()
@@ -849,9 +884,9 @@ def main() -> None:
                     ctx.synchronize()
                 except Exception:
                     pass
-        if world == 1 and n_sets > 1 and not args.no_also and not options_set:
+        if args.full and world == 1 and n_sets > 1 and not args.no_also and not options_set:
             extra("same_poses_every_step", same_poses_block)
-        if world == 1 and default_cfg and not args.no_also and not options_set:
+        if args.full and world == 1 and default_cfg and not args.no_also and not options_set:
             def sum_order_block():
                 # the reference's order of summation ("sum_order" 1: pair after pair, bitwise the sequential fp32 oracle -- checked in the cpu_baseline leg below): its price
                 ctx.set_option("sum_order", 1)
@@ -875,10 +910,10 @@ def main() -> None:
                         "kernel": "k_align_seq<1,0,0,0,5>", "over_default_order": (dt / args.steps * 1e3) / (elapsed / args.steps * 1e3), "parity_ok": True, "_first16": keep,
                         "note": "lsm2d_set_option(\"sum_order\", 1): H, b and chi^2 added pair after pair in the reference's order (nicp_post.m:69-90) instead of in trees"}
             extra("sum_order_1", sum_order_block)
-        if world == 1 and default_cfg and not args.no_also and not args.no_pipelined and not options_set:
+        if args.full and world == 1 and default_cfg and not args.no_also and not args.no_pipelined and not options_set:
             extra("pipelined", lambda: measure_pipelined(ctx, prepared, make_prepared(), x0_sets, want_sets, args, roof))
-        if world == 1 and default_cfg and not args.no_also and not args.no_streamed and not options_set:
-            # the streamed pipeline of `--stream` in short (fresh ranges every step, 300 steps): so that the default line -- the one the round-end driver records -- has timed it
+        if args.full and world == 1 and default_cfg and not args.no_also and not args.no_streamed and not options_set:
+            # the streamed pipeline of `--stream` in short (fresh ranges every step, 300 steps): so that the --full line has timed it
             import copy
             a2 = copy.copy(args); a2.steps, a2.warmup, a2.spinup_s = 300, 5, 0.1
             kt = ctx.get_option("kernel_timing")
@@ -893,7 +928,7 @@ def main() -> None:
                         "h2d_GBs_sustained": so["stream"]["h2d_GBs_sustained"], "steps_checked_bitwise_against_the_synchronous_calls": so["steps_checked_bitwise_against_the_synchronous_calls"],
                         "steps_that_differed": so["steps_that_differed"], "parity_ok": so["parity_ok"], "parity_gate": so["parity_gate"]}
             extra("streamed", streamed_block)
-        if world == 1 and default_cfg and not args.no_also and not options_set:
+        if args.full and world == 1 and default_cfg and not args.no_also and not options_set:
             extra("also", lambda: measure_also(ctx, api, synth, world_geom, wl, scan_set, args, x0_sets))
         if cross:
             out["cross_rank_check"] = cross
@@ -907,7 +942,7 @@ def main() -> None:
             out["sharding"] = shard_info
         if gather_pad:
             out["strong_scaling_gather"] = "all_gather of %d x 12 B per rank inside every timed step" % gather_pad
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import pyoracle as po       # the checker, timed as the CPU baseline ("port")
             ns = min(args.cpu_sample, n_unique)
             offs = wl.scan_offsets[: ns + 1]

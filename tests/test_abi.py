@@ -123,6 +123,27 @@ def test_srrg_adapter_sources_compile_against_the_stand_in_headers(tmp_path):
 
 
 # ---- the adapters' and the compile shim's PARAMs against the reference's own headers ------------------------------------------
+# (the reference's side is tests/golden/reference_params.json, read out of its headers and sources by tests/golden/make_reference_params.py)
+REFERENCE_CLASSES = [("registration/correspondence_finder_projective_2d.h", "CorrespondenceFinderProjective2f"),
+                     ("registration/correspondence_finder_kd_tree_2d.h", "CorrespondenceFinderKDTree2D"),
+                     ("registration/correspondence_finder_nn_2d.h", "CorrespondenceFinderNN2D"),
+                     ("mapping/scene_clipper_projective_2d.h", "SceneClipperProjective2D"),
+                     ("mapping/merger_projective_2d.h", "MergerProjective2D"),
+                     ("sensor_processing/raw_data_preprocessor_projective_2d.h", "RawDataPreprocessorProjective2D")]
+
+
+def _reference():
+    import json
+    from conftest import golden_path
+    return json.load(open(golden_path("reference_params.json")))
+
+
+def _reference_params(header, class_name):
+    ent = _reference()["params"][class_name]
+    assert ent["header"] == header, (class_name, ent["header"], header)
+    return {name: tuple(v) for name, v in ent["params"].items()}
+
+
 def _params_of(text, class_name):
     """(type, name, default) of every PARAM(...) inside `class class_name`; nesting-aware split, `srrg2_core::` stripped."""
     import re
@@ -162,12 +183,9 @@ def _params_of(text, class_name):
 
 
 def test_adapter_and_shim_params_match_the_reference_headers():
-    """Where the reference tree is present (this container, not the GPU box): every PARAM the reference declares for the classes the
-    adapters replace or recognise exists, with the same property type and default, in (a) the stand-in headers the adapters are
-    compile-checked against and (b) the adapters' own sibling classes -- a configuration written for the reference loads unchanged."""
-    ref = "/root/reference/srrg2_laser_slam_2d/src/srrg2_laser_slam_2d"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
+    """Every PARAM the reference declares for the classes the adapters replace or recognise (tests/golden/reference_params.json) exists,
+    with the same property type and default, in (a) the stand-in headers the adapters are compile-checked against and (b) the adapters'
+    own sibling classes -- a configuration written for the reference loads unchanged."""
     rd = lambda *p: open(os.path.join(*p)).read()
     shim = rd(ROOT, "tests", "cpp", "adapter_shim", "srrg_shim.h")
     fh = rd(ROOT, "adapters", "srrg", "correspondence_finder_hip_2d.h"); mh = rd(ROOT, "adapters", "srrg", "mapping_hip_2d.h")
@@ -179,7 +197,7 @@ def test_adapter_and_shim_params_match_the_reference_headers():
              ("sensor_processing/raw_data_preprocessor_projective_2d.h", "RawDataPreprocessorProjective2D", None,
               rd(ROOT, "adapters", "srrg", "raw_data_preprocessor_hip_2d.h"), "RawDataPreprocessorHIP2D")]
     for header, cls, shim_text, adapter_text, adapter_cls in cases:
-        want = _params_of(rd(ref, header), cls)
+        want = _reference_params(header, cls)
         assert want, (header, cls)
         for where, text, name in (("shim", shim_text, cls), ("adapter", adapter_text, adapter_cls)):
             if text is None:
@@ -195,13 +213,9 @@ def test_adapter_and_shim_params_match_the_reference_headers():
 
 def test_python_mirror_defaults_match_the_reference_headers():
     """The Python mirror of the reference classes (srrg2_laser_slam_2d_amd/api.py) takes the reference's PARAM names as keyword arguments:
-    where the reference tree is present, every numeric default must be the reference's."""
+    every numeric default must be the reference's (tests/golden/reference_params.json)."""
     import inspect
-    ref = "/root/reference/srrg2_laser_slam_2d/src/srrg2_laser_slam_2d"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
     from srrg2_laser_slam_2d_amd import api
-    rd = lambda *p: open(os.path.join(*p)).read()
     cases = [("registration/correspondence_finder_projective_2d.h", "CorrespondenceFinderProjective2f", api.CorrespondenceFinderProjective2f),
              ("registration/correspondence_finder_kd_tree_2d.h", "CorrespondenceFinderKDTree2D", api.CorrespondenceFinderKDTree2D),
              ("registration/correspondence_finder_nn_2d.h", "CorrespondenceFinderNN2D", api.CorrespondenceFinderNN2D),
@@ -210,7 +224,7 @@ def test_python_mirror_defaults_match_the_reference_headers():
              ("sensor_processing/raw_data_preprocessor_projective_2d.h", "RawDataPreprocessorProjective2D", api.RawDataPreprocessorProjective2D)]
     checked = 0
     for header, cls, mirror in cases:
-        want = _params_of(rd(ref, header), cls)
+        want = _reference_params(header, cls)
         sig = inspect.signature(mirror.__init__).parameters
         for pname, (typ, default) in want.items():
             if default == "expr" or typ == "PropertyString":
@@ -223,17 +237,10 @@ def test_python_mirror_defaults_match_the_reference_headers():
 
 def test_adapters_touch_only_base_class_members_the_reference_uses():
     """The adapters derive from upstream base classes this image does not have; the members they read and write there (`_fixed`,
-    `_full_scene`, `_meas`, ...) are the ones the reference's own implementations of the same classes use.  Where the reference tree is
-    present: every underscore-member an adapter touches is either declared by the adapter itself, used somewhere in the reference's
-    sources, or one of the names isolated (and tagged UPSTREAM) in adapters/srrg/upstream_access.h / multi_aligner_hip_2d.cpp."""
-    import glob
-    ref = "/root/reference/srrg2_laser_slam_2d"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
-    ref_ids = set()
-    for p in glob.glob(ref + "/**/*", recursive=True):
-        if os.path.isfile(p) and p.endswith((".h", ".hpp", ".cpp")):
-            ref_ids |= set(re.findall(r"\b_[a-z][a-zA-Z_0-9]*\b", open(p, errors="ignore").read()))
+    `_full_scene`, `_meas`, ...) are the ones the reference's own implementations of the same classes use: every underscore-member an
+    adapter touches is either declared by the adapter itself, used somewhere in the reference's sources (tests/golden/reference_params.json,
+    member_ids), or one of the names isolated (and tagged UPSTREAM) in adapters/srrg/upstream_access.h / multi_aligner_hip_2d.cpp."""
+    ref_ids = set(_reference()["member_ids"])
     upstream_tagged = {"_fixed_slice", "_moving_slice", "_information_matrix", "_iteration_stats"}     # upstream_access.h:58-68, multi_aligner_hip_2d.cpp (_writeBack)
     ad = os.path.join(ROOT, "adapters", "srrg")
     texts = {f: re.sub(r"//.*", "", open(os.path.join(ad, f)).read()) for f in sorted(os.listdir(ad))}

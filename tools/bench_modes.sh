@@ -3,7 +3,7 @@
 # usage on the GPU box: bash tools/bench_modes.sh <tag>
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; tag=${1:-round}; O=$R/gpurun_out/$tag; mkdir -p $O; cd $R
 : > $O/bench_modes.jsonl
-run() { timeout -k 10 400 python bench.py "$@" 2>> $O/bench_modes.err | tail -1 >> $O/bench_modes.jsonl; echo "mode [$*] rc=$?"; }
+run() { timeout -k 10 400 python bench.py --full "$@" 2>> $O/bench_modes.err | tail -1 >> $O/bench_modes.jsonl; echo "mode [$*] rc=$?"; }
 run                                                                  # configs[1], role A / projective (the headline line)
 run --role B --finder nn --cpu-sample 200                            # configs[1], role B / NN
 run --role B --finder kdtree --cpu-sample 200                        # configs[1], role B / the reference's own KD-tree (BASELINE's wording: tree over the map, scans as queries)
