@@ -35,13 +35,11 @@ namespace srrg2_laser_slam_2d {
     }
     lsm2d_slice_params sp{};
     fillSliceParams(&sp); // throws on a missing projector / bad parameters, before anything touches the device
-    if (!_ctx) {
-      if (param_context.value()) {
-        _ctx = param_context.value()->handle(who);
-      } else {
-        _shared = lsm2d_srrg::sharedContext(param_device_id.value(), who);
-        _ctx    = _shared->ctx;
-      }
+    if (param_context.value()) {
+      _ctx = param_context.value()->handle(who); // every call: handle() applies a changed sum_order (the device clouds follow a re-created context)
+    } else if (!_ctx) {
+      _shared = lsm2d_srrg::sharedContext(param_device_id.value(), who);
+      _ctx    = _shared->ctx;
     }
     // fixed: behind the base class's dirty flag, like the reference's cached canvas / tree (:37-44; kd_tree_2d.cpp:6-9)
     if (_fixed_changed_flag || !_fixed_dev.set() || _fixed_dev.host() != _fixed) {

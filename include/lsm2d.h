@@ -184,7 +184,11 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   lsm2d_linearize equal the sequential fp32 oracle (oracle/: lsmo_align_f, lsmo_linearize_f) BIT FOR BIT.  Cost: the pairs' terms go through LDS (14 KB
  *   more per workgroup) and one wave adds them one after the other (a quad of lanes per quantity): configs[1] (1000 scans vs a 100k-point map) takes
  *   about 1.2 x the default order's step (1.03 M against 1.24 M alignments/s: DESIGN.md section 5; the point-query finders in the tracker's wiring, whose 100 000
- *   queries per iteration all pass a barrier per 512, 3 - 5 x).  Calls the latency kernel would take (align_path 3) run on k_align instead: "last_align_path" reads 1.
+ *   queries per iteration all pass a barrier per 512, 3 - 5 x).  The latency kernel has a reference-order form too (k_align_pair<true>: both slices' pairs
+ *   added at once, one wave per slice): with "sum_order" 1 it takes every SINGLE-alignment call with one or two projective slices (the live tracker's and the
+ *   standalone aligner's call) and every call with align_path 3, whenever its LDS layout fits ("last_align_path" reads 3); batches of two and more alignments
+ *   take k_align_seq by themselves (one workgroup per alignment).  The tracker's step (two 721-column slices + prior): 0.114 ms asynchronous against 0.204 on
+ *   k_align_seq and 0.059 in the tree order.
  * "align_width": the launch form of a culled projective batch (k_align): 0 = automatic (default: workgroups of 512 threads; of 256 -- six alignments per CU round instead
  *   of four -- for batches just above a multiple of 1024 alignments, where the last few would otherwise run a round of their own on an empty chip; PACKED -- one round
  *   of 1024 workgroups, the lightest alignments two to a workgroup, one after the other -- for 1025 .. 1048 and 1537 .. 2047 alignments, and for up to 32 more than 2048 or 3072; with "sum_order" 1, which has no narrow form: 1025 .. 1600), 512 / 256 = always that
@@ -192,7 +196,8 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   sums, a packed workgroup runs the same kernel body twice: bit-identical results (get: "last_align_width": 512, 256, or 1024 for a packed launch).
  * "align_path": 0 = automatic (default), 1 = always one workgroup per alignment (k_align), 2 = always the split path (k_split_project +
  *   k_split_finish per iteration; projective slices only), 3 = the latency kernel whenever the batch has one or two projective slices
- *   (k_align_pair: 512 threads per slice, two slices' passes side by side in one workgroup; automatic for <= 256 alignments).  All paths return
+ *   (k_align_pair: 512 threads per slice, two slices' passes side by side in one workgroup; automatic for <= 256 alignments -- with "sum_order" 1 for
+ *   single alignments only, see there).  All paths return
  *   bit-identical results; the split path is for a handful of alignments against a large cloud, the latency kernel for calls that cannot fill
  *   the chip (the live tracker).
  * "kernel_timing": 1 records HIP events around the hot-path launches so that lsm2d_last_kernel_ms can report them; 0 (default) does not -- the

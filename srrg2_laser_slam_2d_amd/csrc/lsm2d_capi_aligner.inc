@@ -182,6 +182,13 @@ int AlignBatch::validate_and_lay_out_scratch() {
   return LSM2D_SUCCESS;
 }
 
+// Which calls the latency kernel may take, as far as the order of summation goes: every one in the tree order; with "sum_order" 1 (k_align_pair<true>)
+// an explicit align_path 3, and -- automatically -- a single alignment (the live tracker's and the standalone aligner's call: DESIGN section 5, the
+// tracker step in the reference's order).  Batches of two and more keep k_align_seq, one workgroup per alignment.
+static bool pair_order_ok(const lsm2d_context* ctx, int n) {
+  return !ctx->sum_order || ctx->align_path == 3 || (ctx->align_path == 0 && n == 1);
+}
+
 int AlignBatch::choose_path() {
   // ---- which path: few alignments against a big cloud are spread over many workgroups each (projective slices only)
   has_proj = false, has_nn = false, has_dist = false, has_kd = false;
@@ -277,7 +284,7 @@ int AlignBatch::prepare_slices() {
     if (sp.finder == LSM2D_FINDER_PROJECTIVE) { const int lrc = ensure_lane_layout(ctx, m); if (lrc) return lrc; }
     // k_align's bin walk gathers both z-buffer winners as 16-byte rows of the sets' AoS copies (not for the calls the latency kernel or the split
     // path will take: the live tracker's sets change every step)
-    const bool pair_candidate = !ctx->sum_order && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
+    const bool pair_candidate = pair_order_ok(ctx, n) && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
     if (sp.finder == LSM2D_FINDER_PROJECTIVE && !use_split && !pair_candidate && !defer_unpack) {
       int arc = ensure_aos(ctx, f); if (arc) return arc;
       arc = ensure_aos(ctx, m); if (arc) return arc;
@@ -410,6 +417,8 @@ int AlignBatch::lay_out_lds() {
   // the moving clouds themselves (kPairMovCap points of 16 bytes per slice)
   lds_pair0 = sizeof(float4) * (size_t) fcan_total + sizeof(u64) * (size_t) fcan_total +
                            (size_t) ns * (sizeof(u64) * (size_t) cols_max + sizeof(float) * kPairRedStride * (kAlignBlock / 64));
+  // ("sum_order" 1, k_align_pair<true>: a buffer of pair records per slice behind the canvases -- counted before the clouds, which are staged only if there is room)
+  if (ctx->sum_order) lds_pair0 += (size_t) ns * kSeqLdsBytes;
   lds_mov = (size_t) ns * kPairMovCap * sizeof(float4);
   A.pair_mov_cap = (int) (lds_pair0 + lds_mov) + 512 <= ctx->max_dyn_lds ? kPairMovCap : 0;
   // ... and the fixed clouds (sizes the host knows, or upper bounds of sizes only the device knows: the kernel compares the real ones)
@@ -419,8 +428,8 @@ int AlignBatch::lay_out_lds() {
   lds_fix = (size_t) ns * (size_t) max_fixed_rows * sizeof(float4);
   A.pair_fix_cap = max_fixed_rows <= 4096 && (int) (lds_pair0 + (A.pair_mov_cap ? lds_mov : 0) + lds_fix) + 512 <= ctx->max_dyn_lds ? max_fixed_rows : 0;
   lds_pair = lds_pair0 + (A.pair_mov_cap ? lds_mov : 0) + (A.pair_fix_cap ? lds_fix : 0);
-  // ("sum_order" 1: the latency kernel keeps the tree order -- such calls take k_align_seq, one workgroup per alignment)
-  use_pair = !ctx->sum_order && !use_split && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd &&
+  // ("sum_order" 1: the latency kernel's reference-order form, k_align_pair<true>, for the calls pair_order_ok admits; the others take k_align_seq)
+  use_pair = pair_order_ok(ctx, n) && !use_split && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd &&
                         (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0 && (int) lds_pair + 512 <= ctx->max_dyn_lds;
   return LSM2D_SUCCESS;
 }
@@ -693,7 +702,7 @@ int AlignBatch::launch() {
     }
   } else {
     const dim3 grid((unsigned) n), block(kAlignBlock);
-    if (use_pair) hipLaunchKernelGGL(k_align_pair, grid, dim3((unsigned) (kAlignBlock * ns)), lds_pair, ks, A);
+    if (use_pair) hipLaunchKernelGGL(ctx->sum_order ? k_align_pair<true> : k_align_pair<false>, grid, dim3((unsigned) (kAlignBlock * ns)), lds_pair, ks, A);
     else {
       // which instantiation: the finders the batch's slices use, and -- for a batch of ONE finder kind -- the form of its inner loop the host could prove
       // serves every alignment (kNNMode of align_body).  One table (round 5; a 12-way ladder before); the mixed instantiations take whatever is left.

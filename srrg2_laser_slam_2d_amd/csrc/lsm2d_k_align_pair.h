@@ -28,8 +28,20 @@ static constexpr int kPairRedStride = 16;               // words per (slice, wav
 // all threads of a slice call; afterwards red[wave][0..13] holds the wave's totals.  count_bits: bits a thread's counts can occupy
 // (a thread accumulates at most ceil(cols / 512) pairs).  A slice without robustifier has chi_out == +0 and n_in == n_corr in
 // every lane: nothing to add up.
+// kCountsOnly ("sum_order" 1): the eleven sums come from the walks of the pair records; only the three counts go into the wave's row (words 11-13)
+template <bool kCountsOnly = false>
 LSM2D_DEV void pair_wave_sums(const Accum& A, float* red, int tid, bool cauchy, int count_bits) {
   const int lane = tid & 63, wave = tid >> 6;
+  if constexpr (kCountsOnly) {
+    int nc = 0, ni = 0;
+    for (int b = 0; b < count_bits; ++b) {
+      nc += __builtin_popcountll(__ballot((A.n_corr >> b) & 1)) << b;
+      ni += __builtin_popcountll(__ballot((A.n_in >> b) & 1)) << b;
+    }
+    if (!cauchy) ni = nc;
+    if (lane == 63) { float* r = red + wave * kPairRedStride; r[11] = (float) ni; r[12] = (float) (nc - ni); r[13] = (float) nc; }
+    return;
+  }
   float f[11] = {A.h00, A.h01, A.h02, A.h11, A.h12, A.h22, A.b0, A.b1, A.b2, A.chi_in, A.chi_out};
   int nc = 0, ni = 0;
   if (cauchy) {
@@ -95,6 +107,10 @@ LSM2D_DEV bool solve_flat(float h00, float h01, float h02, float h11, float h12,
 #define LSM2D_PAIR_READ_FIRST false      // z-buffer updates of the on-chip moving cloud: fire-and-forget (neighbouring lanes hold neighbouring columns' points)
 #endif
 
+// kSeq ("sum_order" 1): H, b and the chi^2 sums pair after pair in the reference's order -- k_align_seq's bits (pose, H, status, iterations, statistics,
+// pair digest) for one or two projective slices, both slices' records walked at once (see "the reference's order" below); its LDS is k_align_pair<false>'s
+// plus kSeqLdsBytes of records per slice behind the canvases.  kSeq = false: the tree order described above.
+template <bool kSeq>
 __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int nwaves = kAlignBlock / 64;
@@ -236,6 +252,11 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
   const bool want_dig = A.out_stats != nullptr;
   const uint32_t salt = (uint32_t) half * 0x632BE5ABu;
   const int it_cap = A.inlier_runs ? 2 * A.max_it : A.max_it;
+  int seq_trips = 0;      // kSeq: trips of 512 columns per iteration, the wider slice's (both slices take part in every trip's barriers)
+  if constexpr (kSeq) {
+    const int cols_w = A.s[0].proj.cols > A.s[n_slices - 1].proj.cols ? A.s[0].proj.cols : A.s[n_slices - 1].proj.cols;
+    seq_trips = __builtin_amdgcn_readfirstlane((cols_w + kAlignBlock - 1) / kAlignBlock);
+  }
   __syncthreads();
   LSM2D_PC(0);
 
@@ -245,6 +266,7 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
     const Iso T = s_iso[half];
     const bool inl_only = A.inlier_runs && __builtin_amdgcn_readfirstlane(s_inl) != 0;
     Accum acc; accum_zero(acc);
+    if constexpr (!kSeq) {
     if (on_chip) {
       // both clouds in LDS (the tracker's case): one point's z-buffer update per thread, then the walk one column at a time -- every gather is
       // an LDS row, so there is no latency worth a second column in flight, and a wave without a second column does not walk through one
@@ -319,6 +341,90 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
     LSM2D_PC(6);                 // thread 0's wave: bin walk
     pair_wave_sums(acc, red, tid, cauchy, count_bits);
     LSM2D_PC(7);                 // its wave sums
+    } else {
+      // ---- the reference's order (k_align_seq's, lsm2d_device.h "sum_order" 1): every matched pair becomes a record of its terms, the records of a slice are
+      // added in ascending canvas column, trip after trip (512 columns), from +0.  Both slices at once: slice 0's records are walked by its wave 0, slice 1's by
+      // its wave 1 (another SIMD), each in its own kSeqHalf-record buffer.  A trip's pairs are compacted per slice in column order (a column without a pair
+      // would add fma(+0, +0, h) == h: leaving it out changes no bit) and appended to the slice's buffer; both buffers are walked whenever one of them is full
+      // and once more at the end.  Every count that steers a barrier is known to all 1024 threads (both slices' wave counts sit in red2), so all sixteen
+      // waves meet every barrier -- also when the two canvases need different numbers of trips (the narrower slice's extra trips hold no records).
+      if (S.moving.lane_xy) project_cloud_lanes(S.moving.lane_xy + S.moving.lane_start[mc], S.moving.lane_T[mc], T, S.proj, mcan, tid, kAlignBlock);
+      else if (m_on_chip) {
+        if (tid < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p0.x, p0.y, tid, mcan);
+        if (j1 < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p1.x, p1.y, j1, mcan);
+      }
+      else project_cloud(mp, m_count, T, S.proj, mcan, tid, kAlignBlock);
+      __syncthreads();
+      LSM2D_PC(1);
+      float* rec = reinterpret_cast<float*>(fcan + A.fcan_total) + half * (kSeqHalf * kSeqFields);      // this slice's records (behind the canvases)
+      int* wcnt = reinterpret_cast<int*>(red2);      // a trip's pairs per wave: words 14 / 15 (trip parity) of the wave's row, both slices' rows read by all
+      const int wave_l = __builtin_amdgcn_readfirstlane(tid >> 6);
+      const bool walker = wave_l == half;
+      float seq_acc = 0.0f;          // the walker's lanes: the slice's eleven running sums (seq_walk's quads)
+      int fill0 = 0, fill1 = 0;      // records waiting in each slice's buffer (the same in every thread)
+      auto walk_both = [&]() {
+        const int mine = half ? fill1 : fill0;
+        if (tid < ((mine + 7) & ~7) - mine) { float z[kSeqFields]; seq_zero(z); seq_store(rec, mine + tid, z); }      // seq_walk takes eight at a time
+        __syncthreads();
+        if (walker) seq_acc = seq_walk(rec, mine, lane, seq_acc);
+        __syncthreads();
+        fill0 = 0; fill1 = 0;
+      };
+      for (int trip = 0; trip < seq_trips; ++trip) {
+        const int col = trip * kAlignBlock + tid;
+        float t[kSeqFields]; seq_zero(t);      // (pair_terms writes fields 0-11; the constants 1, 0 of fields 12, 13 come from here)
+        bool have = false;
+        if (col < Pk.cols) {
+          const u64 fk = fcs[col], mk = mcan[col];
+          mcan[col] = kEmptyCell;
+          const uint32_t fdb = (uint32_t) (fk >> 32), mdb = (uint32_t) (mk >> 32);       // an empty cell's depth bits are all ones, no depth's are
+          if (fdb != 0xFFFFFFFFu && mdb != 0xFFFFFFFFu && !(__builtin_fabsf(__uint_as_float(fdb) - __uint_as_float(mdb)) > k_pd)) {
+            const int mi = (int) (uint32_t) mk, fi = (int) (uint32_t) fk;
+            float4 m;
+            if (m_on_chip) m = mwin[mi];
+            else { const float2 pm = mp[mi], nm = mn[mi]; m = make_float4(pm.x, pm.y, nm.x, nm.y); }
+            const float4 f = f_on_chip ? fall[fi] : fws[col];
+            float nqx, nqy; xf_normal(T, m.z, m.w, nqx, nqy);
+            if (!(__builtin_fmaf(nqx, f.z, nqy * f.w) < k_ncos)) {
+              if (want_dig) digest_add(&s_dig, salt, fi, mi);
+              bool inl;
+              pair_terms(T, make_float2(f.x, f.y), make_float2(f.z, f.w), make_float2(m.x, m.y), make_float2(m.z, m.w), cauchy, k_tau, inl_only, t, inl);
+              ++acc.n_corr; acc.n_in += inl ? 1 : 0;
+              have = true;
+            }
+          }
+        }
+        const u64 bal = __ballot(have);
+        const int parity = trip & 1;
+        if (lane == 0) wcnt[(gtid >> 6) * kPairRedStride + 14 + parity] = __popcll(bal);
+        __syncthreads();
+        int before = 0, n0 = 0, n1 = 0;
+#pragma unroll
+        for (int w = 0; w < nwaves; ++w) {
+          const int c0 = wcnt[w * kPairRedStride + 14 + parity], c1 = two_slices ? wcnt[(nwaves + w) * kPairRedStride + 14 + parity] : 0;
+          n0 += c0; n1 += c1; before += w < wave_l ? (half ? c1 : c0) : 0;
+        }
+        n0 = __builtin_amdgcn_readfirstlane(n0); n1 = __builtin_amdgcn_readfirstlane(n1);
+        const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+        int done0 = 0, done1 = 0;
+        while (done0 < n0 || done1 < n1) {      // this trip's records into the buffers, as far as they have room; a full buffer is walked (both are)
+          const int take0 = n0 - done0 < kSeqHalf - fill0 ? n0 - done0 : kSeqHalf - fill0;
+          const int take1 = n1 - done1 < kSeqHalf - fill1 ? n1 - done1 : kSeqHalf - fill1;
+          const int done = half ? done1 : done0, take = half ? take1 : take0, fill = half ? fill1 : fill0;
+          if (have && pos >= done && pos < done + take) seq_store(rec, fill + pos - done, t);
+          fill0 += take0; fill1 += take1; done0 += take0; done1 += take1;
+          if (fill0 == kSeqHalf || fill1 == kSeqHalf) walk_both();
+        }
+      }
+      if (fill0 > 0 || fill1 > 0) walk_both();
+      LSM2D_PC(6);
+      pair_wave_sums<true>(acc, red, tid, cauchy, count_bits);
+      if (walker) {      // the slice's eleven totals -> words 0-10 of the slice's first row (the counts are in words 11-13 of every row)
+        const float v = seq_total(seq_acc, lane);
+        if (lane < 11) red[lane] = v;
+      }
+      LSM2D_PC(7);
+    }
     // what depends on the pose alone, computed by wave 0 HERE, where it would otherwise wait for the slowest of the sixteen: each
     // lane's entry of the prior's terms, and the rotation of the update X <- X * v2t(dx)
     float P = 0.0f, sp = 0.0f, cp = 1.0f;
@@ -332,12 +438,24 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
     if (w0) {
       // gather: this lane's quantity over the waves (wave order, from +0 -- block_reduce_gather's sums), both slices
       float v0 = 0.0f, v1 = 0.0f;
+      const bool two = two_slices;
+      if constexpr (kSeq) {      // the sums: the walks' totals; the counts over the waves as below
+        if (q < 11) { v0 = red2[q]; if (two) v1 = red2[nwaves * kPairRedStride + q]; }
+        else {
+#pragma unroll
+          for (int w = 0; w < nwaves; ++w) v0 += red2[w * kPairRedStride + q];
+          if (two) {
+#pragma unroll
+            for (int w = 0; w < nwaves; ++w) v1 += red2[(nwaves + w) * kPairRedStride + q];
+          }
+        }
+      } else {
 #pragma unroll
       for (int w = 0; w < nwaves; ++w) v0 += red2[w * kPairRedStride + q];
-      const bool two = two_slices;
       if (two) {
 #pragma unroll
         for (int w = 0; w < nwaves; ++w) v1 += red2[(nwaves + w) * kPairRedStride + q];
+      }
       }
       LSM2D_PC(3);
       // k_align's per-slice accumulation (zeroed sums, then slice 0, then slice 1; the pair count of every slice, the rest of active ones)
