@@ -194,6 +194,7 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   of 1024 workgroups, the lightest alignments two to a workgroup, one after the other -- for 1025 .. 1048 and 1537 .. 2047 alignments, and for up to 32 more than 2048 or 3072; with "sum_order" 1, which has no narrow form: 1025 .. 1600), 512 / 256 = always that
  *   width, 1024 = packed whenever the batch has more than 1024 and fewer than 4096 alignments and is not a multiple of 1024.  The narrow workgroups keep the wide kernel's 512 virtual threads in the bin walk and the
  *   sums, a packed workgroup runs the same kernel body twice: bit-identical results (get: "last_align_width": 512, 256, or 1024 for a packed launch).
+ *   Only 0, 256, 512 and 1024 are accepted; any other value is LSM2D_BAD_ARGUMENT and leaves the option as it was.
  * "align_path": 0 = automatic (default), 1 = always one workgroup per alignment (k_align), 2 = always the split path (k_split_project +
  *   k_split_finish per iteration; projective slices only), 3 = the latency kernel whenever the batch has one or two projective slices
  *   (k_align_pair: 512 threads per slice, two slices' passes side by side in one workgroup; automatic for <= 256 alignments -- with "sum_order" 1 for

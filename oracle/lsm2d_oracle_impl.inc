@@ -17,6 +17,7 @@ static inline SFX(iso) SFX(v2t)(const REAL v[3]) {
 }
 
 static inline REAL SFX(wrap_angle)(REAL a) {
+  if (!(fabs((double) a) < 3.0e7)) return (REAL) NAN;      /* not a number, or beyond where 2 pi changes it: the loops below would never end (the device's wrap_angle) */
   while (a > R_PI) a -= R_TWO_PI;
   while (a <= -R_PI) a += R_TWO_PI;
   return a;

@@ -545,6 +545,8 @@ extern "C" int lsm2d_set_option(lsm2d_context* ctx, const char* key, int64_t val
       char buf[160]; snprintf(buf, sizeof buf, "set_option: %s must be %sin %lld .. %lld", o.key, (o.flags & kOptEven) ? "even and " : "", o.lo, o.hi);
       return fail(ctx, LSM2D_BAD_ARGUMENT, buf);
     }
+    if (o.field == &lsm2d_context::align_width && value != 0 && value != 256 && value != 512 && value != 1024)      // (any other value used to act as 0)
+      return fail(ctx, LSM2D_BAD_ARGUMENT, "set_option: align_width must be 0, 256, 512 or 1024");
     ctx->*(o.field) = (int) value;
     if (o.flags & kOptResetsNotes) ctx->wg_place_shape = 0;
     if (o.field == &lsm2d_context::kernel_timing && !value) ctx->have_timing = false;

@@ -516,6 +516,7 @@ static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float ma
 
 static Iso make_iso(const float pose[3]) { Iso T; sincos_fixed(pose[2], T.s, T.c); T.tx = pose[0]; T.ty = pose[1]; return T; }
 static float wrap_host(float a) {
+  if (!(fabsf(a) < 3.0e7f)) return NAN;      // (wrap_angle: the loops below would never end)
   while (a > 3.14159274101257324f) a -= 6.28318548202514648f;
   while (a <= -3.14159274101257324f) a += 6.28318548202514648f;
   return a;

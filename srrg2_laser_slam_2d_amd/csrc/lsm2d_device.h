@@ -82,6 +82,9 @@ LSM2D_DEV void xf_normal(const Iso& T, float nx, float ny, float& ox, float& oy)
 }
 
 LSM2D_DEV float wrap_angle(float a) {
+  // (an angle that is not a number, or so large that 2 pi no longer changes it -- an infinite start pose composed with a sensor offset -- would never
+  // leave the loops below: NaN, and its alignment fails like any other start pose that is not a number)
+  if (!(__builtin_fabsf(a) < 3.0e7f)) return __builtin_nanf("");
   while (a > 3.14159274101257324f) a -= 6.28318548202514648f;
   while (a <= -3.14159274101257324f) a += 6.28318548202514648f;
   return a;

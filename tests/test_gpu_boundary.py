@@ -294,6 +294,17 @@ def test_abi_error_paths_and_limits(ctx, small_workload):
         al.compute_batch([s], [m], wl.x0[:3])                  # 6 clouds, 3 alignments, no index array
     with pytest.raises(api.Lsm2dError):
         al.compute_batch([s], [m], wl.x0, fixed_index=np.full((1, len(wl.x0)), 77, np.int32))
+    # "align_width": only the launch forms it names; a typo must not quietly act as "automatic"
+    for bad in (300, 1, 255, 768, 1023):
+        with pytest.raises(api.Lsm2dError) as ei:
+            ctx.set_option("align_width", bad)
+        assert ei.value.code == _capi.BAD_ARGUMENT and ctx.get_option("align_width") == 0, bad
+    try:
+        for w in (256, 512, 1024, 0):
+            ctx.set_option("align_width", w); assert ctx.get_option("align_width") == w
+    finally:
+        ctx.set_option("align_width", 0)
+    assert np.all(al.compute_batch([s], [m], wl.x0).status == 0)      # the context still works
     sp = api.make_slice_params(finder=7)
     n = C.c_int32(0); out = np.zeros((10, 2), np.int32)
     rc = lib.lsm2d_find_correspondences(ctx.handle, C.byref(sp), s.handle, 0, m.handle, 0, np.zeros(3, np.float32).ctypes.data_as(C.c_void_p),
