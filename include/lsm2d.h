@@ -45,7 +45,9 @@ extern "C" {
                                     (fresh scans into an existing set: no allocation, nothing waits); the option keys below are the WHOLE public set (the A/B
                                     knobs of rounds 1-4 exist only in a -DLSM2D_EXPERIMENTS build); read-only keys "uploads", "last_cull_estimate", "experiments";
                              0.6.0: + option "sum_order" (1: H, b and the chi^2 statistics are added pair after pair in the reference's order -- the ONE option
-                                    results depend on: with it the aligner is bitwise the sequential fp32 restatement of nicp_post.m:69-90) */
+                                    results depend on: with it the aligner is bitwise the sequential fp32 restatement of nicp_post.m:69-90);
+                             (0.7.0, number unchanged: additions only) + lsm2d_cloudset_create_reserved_many / lsm2d_cloudset_clear_clouds, lsm2d_clip_scene_batch,
+                                    lsm2d_merge_scene_batch (N independent trackers per call: one workgroup per tracker, the single-tracker calls' bits) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -247,6 +249,16 @@ int  lsm2d_cloudset_create_from_device(lsm2d_context* ctx, const void* d_points_
                                        int32_t n_clouds, int64_t total_points, lsm2d_cloudset** out_set);
 /* a single growable cloud (count 0) with room for capacity_points: the device-resident local map / clipped scene */
 int  lsm2d_cloudset_create_reserved(lsm2d_context* ctx, int64_t capacity_points, lsm2d_cloudset** out_set);
+/* n_clouds growable clouds (count 0 each), each with room for capacity_per_cloud points: the local maps of N trackers, or their clipped
+ * scenes (lsm2d_clip_scene_batch / lsm2d_merge_scene_batch).  Cloud i occupies the fixed slot that starts at point i * capacity_per_cloud,
+ * rounded up to an even point.  Sizes written by the batched calls stay on the device until asked for (lsm2d_cloudset_cloud_sizes: one
+ * wait for all of them).  lsm2d_align_batch, lsm2d_find_correspondences, lsm2d_project and lsm2d_cloudset_download read such a set
+ * like any multi-cloud set; the single-cloud calls (lsm2d_cloudset_upload, lsm2d_clip_scene[_voxelized], lsm2d_merge_scene[s],
+ * lsm2d_preprocess_scan_into, lsm2d_preprocess_scans_refill) refuse it (LSM2D_BAD_ARGUMENT), even with n_clouds = 1. */
+int  lsm2d_cloudset_create_reserved_many(lsm2d_context* ctx, int32_t n_clouds, int64_t capacity_per_cloud, lsm2d_cloudset** out_set);
+/* empties clouds cloud_index[0 .. n) of a set of lsm2d_cloudset_create_reserved_many (cloud_index NULL: every cloud, n is not read) --
+ * a tracker that starts a new local map.  Asynchronous: queued on the context's stream, nothing waits. */
+int  lsm2d_cloudset_clear_clouds(lsm2d_cloudset* set, int32_t n, const int32_t* cloud_index);
 /* refill an existing SINGLE-cloud set in place (no allocation); LSM2D_CAPACITY_EXCEEDED when it does not fit.  The points are
  * copied into the set's pinned staging buffer before the call returns and travel asynchronously on the context's stream:
  * for scan-sized sets (<= 16 384 points) whoever reads the set first queues their unpacking, and a single-alignment projective
@@ -341,6 +353,26 @@ int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* projector, lsm2
 int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* projector, lsm2d_cloudset* scene, int32_t n_measurements,
                        const lsm2d_cloudset* const* measurements, const int32_t* meas_index, const float* measurement_in_scene,
                        float merge_threshold, int32_t* out_size, int32_t* out_counts);
+
+/* ---- N independent trackers per call (one robot model: one projector and one sensor_in_robot for all of them) ----------------------
+ * Each tracker's result is the bits the single-tracker call gives for it; one workgroup per tracker, no workgroup waits for another.
+ * lsm2d_clip_scene for n_trackers at once (voxelize_resolution 0): tracker i clips cloud scene_index[i] (NULL: i) of `scenes` at
+ * robot_in_local_map[i] * sensor_in_robot into cloud i of `clipped`, a set of lsm2d_cloudset_create_reserved_many with >= n_trackers
+ * clouds of >= canvas_cols points.  Any scene size, sizes known to the device only included, is clipped without a wait.
+ * out_n_points [n_trackers] or NULL (ASYNCHRONOUS: nothing waits, the sizes stay on the device). */
+int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector* projector, const lsm2d_cloudset* scenes, int32_t n_trackers,
+                           const int32_t* scene_index, const float* robot_in_local_map /* [n_trackers][3] */, const float sensor_in_robot[3],
+                           lsm2d_cloudset* clipped, int32_t* out_n_points);
+/* lsm2d_merge_scenes for n_trackers at once: cloud scene_index[i] (NULL: i) of `scenes` (a set of lsm2d_cloudset_create_reserved_many;
+ * no index twice) gets cloud meas_index[k * n_trackers + i] (NULL: i) of measurements[k], k = 0 .. n_measurements - 1 (1 .. 4), merged
+ * one after the other at measurement_in_scene[i][k] ([n_trackers][n_measurements][3]).  All or nothing: when a scene may lack room for
+ * n_measurements * canvas_cols more points by the host's upper bounds, the sizes are fetched (one wait); a scene that really lacks it is
+ * LSM2D_CAPACITY_EXCEEDED (lsm2d_last_error names the tracker) and nothing is launched.  out_sizes [n_trackers] and
+ * out_counts [n_trackers][n_measurements][3] (new, merged, replaced) or NULL (then both: ASYNCHRONOUS). */
+int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector* projector, lsm2d_cloudset* scenes, int32_t n_trackers,
+                            const int32_t* scene_index, int32_t n_measurements, const lsm2d_cloudset* const* measurements,
+                            const int32_t* meas_index, const float* measurement_in_scene, float merge_threshold,
+                            int32_t* out_sizes, int32_t* out_counts);
 
 /* ---- plugin interface #1: CorrespondenceFinder_::compute ---------------------------------------
  * Replaces compute() of the three finders (registration/correspondence_finder_projective_2d.cpp:18-77,

@@ -117,6 +117,10 @@ SYMBOLS = [
     ("lsm2d_align_batch_begin", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.c_int32, C.POINTER(_P)]),
     ("lsm2d_align_batch_wait", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("lsm2d_preprocess_scans_refill", C.c_int, [_P, C.POINTER(Preprocessor), _P, C.c_int32, _P]),
+    ("lsm2d_cloudset_create_reserved_many", C.c_int, [_P, C.c_int32, C.c_int64, C.POINTER(_P)]),
+    ("lsm2d_cloudset_clear_clouds", C.c_int, [_P, C.c_int32, _P]),
+    ("lsm2d_clip_scene_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("lsm2d_merge_scene_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_float, _P, _P]),
 ]
 
 _lib = None

@@ -139,6 +139,29 @@ class CloudSet:
         ctx._sets.add(self)
         return self
 
+    @classmethod
+    def reserved_many(cls, ctx: Context, n_clouds: int, capacity: int) -> "CloudSet":
+        """``n_clouds`` growable device clouds, each with room for ``capacity`` points (the local maps of N trackers, or their clipped
+        scenes: lsm2d_cloudset_create_reserved_many).  The single-cloud calls refuse such a set; the batched clipper / merger fill it."""
+        self = cls.__new__(cls)
+        self._ctx, self._lib = ctx, ctx._lib
+        h = C.c_void_p()
+        check(ctx._lib.lsm2d_cloudset_create_reserved_many(ctx.handle, int(n_clouds), int(capacity), C.byref(h)),
+              "lsm2d_cloudset_create_reserved_many", ctx.handle)
+        self._h, self.n_clouds, self.n_points, self.counts, self.capacity = h, int(n_clouds), 0, np.zeros(int(n_clouds), np.int64), int(capacity)
+        self._many = True
+        ctx._sets.add(self)
+        return self
+
+    def clear(self, indices=None):
+        """Empties clouds ``indices`` (None: all) of a ``reserved_many`` set, asynchronously (lsm2d_cloudset_clear_clouds)."""
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
+        check(self._lib.lsm2d_cloudset_clear_clouds(self._h, 0 if idx is None else len(idx), None if idx is None else idx.ctypes.data_as(C.c_void_p)),
+              "lsm2d_cloudset_clear_clouds", self._ctx.handle)
+        if not getattr(self, "_pending", False):
+            c = self._counts.copy(); c[slice(None) if idx is None else idx] = 0
+            self._counts = c; self._n_points = int(c.sum())
+
     # n_points / counts of a reserved set can be "known to the device only" after an asynchronous clip / merge
     # (SceneClipperProjective2D / MergerProjective2D with asynchronous=True): reading them then asks the library, which
     # synchronises once.
@@ -161,7 +184,12 @@ class CloudSet:
         self._counts = v
 
     def _resolve(self):
-        if getattr(self, "_pending", False):
+        if getattr(self, "_pending", False) and self.n_clouds > 1:      # all sizes of a multi-cloud set with one wait
+            c = np.empty(self.n_clouds, np.int32)
+            check(min(self._lib.lsm2d_cloudset_cloud_sizes(self._h, c.ctypes.data_as(C.c_void_p), self.n_clouds), 0), "lsm2d_cloudset_cloud_sizes", self._ctx.handle)
+            self._pending = False
+            self._n_points = int(c.sum()); self._counts = c.astype(np.int64)
+        elif getattr(self, "_pending", False):
             n = int(self._lib.lsm2d_cloudset_cloud_size(self._h, 0))
             self._pending = False
             self._n_points = n; self._counts = np.array([n], np.int64)
@@ -775,6 +803,25 @@ class SceneClipperProjective2D:
         self.source_indices = src[: n.value].copy() if not vox > 0 else np.zeros(0, np.int32)
         return self._clipped
 
+    def compute_batch(self, scenes: CloudSet, robot_in_local_map, clipped: CloudSet, scene_index=None):
+        """compute() for N trackers at once (lsm2d_clip_scene_batch, voxelize_resolution 0 only): tracker i clips cloud
+        ``scene_index[i]`` (None: i) of ``scenes`` at ``robot_in_local_map[i]`` * the sensor offset into cloud i of ``clipped`` (a
+        ``CloudSet.reserved_many`` of >= N clouds of >= canvas_cols points).  Returns the N sizes, or None when asynchronous."""
+        if self.param_projector is None:
+            raise RuntimeError("SceneClipperProjective2D::compute| Missing Projector")
+        if float(self.param_voxelize_resolution) > 0:
+            raise ValueError("the batched clipper has no voxelised form (voxelize_resolution must be 0)")
+        poses = np.ascontiguousarray(robot_in_local_map, np.float32).reshape(-1, 3)
+        n = len(poses)
+        idx = None if scene_index is None else np.ascontiguousarray(scene_index, np.int32).ravel()
+        pr = self.param_projector.struct()
+        out = None if self.asynchronous else np.empty(n, np.int32)
+        check(self._ctx._lib.lsm2d_clip_scene_batch(self._ctx.handle, C.byref(pr), scenes.handle, n, None if idx is None else idx.ctypes.data_as(C.c_void_p),
+                                                    poses.ctypes.data_as(C.c_void_p), self._sensor_in_robot.ctypes.data_as(C.c_void_p), clipped.handle,
+                                                    None if out is None else out.ctypes.data_as(C.c_void_p)), "lsm2d_clip_scene_batch", self._ctx.handle)
+        clipped._set_pending()
+        return out
+
 
 class MergerProjective2D:
     """mapping/merger_projective_2d.{h,cpp}: folds a measurement into the device-resident scene, in place."""
@@ -849,6 +896,29 @@ class MergerProjective2D:
         self._scene._set_count(size.value)
         self.counts = [tuple(counts[3 * k:3 * k + 3]) for k in range(n)]
         return size.value
+
+    def compute_batch(self, scenes: CloudSet, measurements: Sequence[CloudSet], poses, scene_index=None, meas_index=None):
+        """compute_all() for N trackers at once (lsm2d_merge_scene_batch): cloud ``scene_index[i]`` (None: i) of the ``reserved_many``
+        set ``scenes`` gets cloud ``meas_index[k][i]`` (None: i) of ``measurements[k]``, k = 0 .. K-1 (K <= 4), in order, at ``poses[i][k]``.
+        Returns the N new sizes (``counts``: [N][K][3] new, merged, replaced), or None when asynchronous."""
+        if self.param_projector is None:
+            raise RuntimeError("MergerProjective2D::compute| Missing Projector")
+        k = len(measurements)
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, k, 3)
+        n = len(p)
+        handles = (C.c_void_p * max(k, 1))(*[m.handle.value for m in measurements])
+        sidx = None if scene_index is None else np.ascontiguousarray(scene_index, np.int32).ravel()
+        midx = None if meas_index is None else np.ascontiguousarray(meas_index, np.int32).reshape(k, n)
+        pr = self.param_projector.struct()
+        sizes = None if self.asynchronous else np.empty(n, np.int32)
+        counts = None if self.asynchronous else np.empty((n, k, 3), np.int32)
+        check(self._ctx._lib.lsm2d_merge_scene_batch(self._ctx.handle, C.byref(pr), scenes.handle, n, None if sidx is None else sidx.ctypes.data_as(C.c_void_p),
+                                                     k, handles, None if midx is None else midx.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
+                                                     float(self.param_merge_threshold), None if sizes is None else sizes.ctypes.data_as(C.c_void_p),
+                                                     None if counts is None else counts.ctypes.data_as(C.c_void_p)), "lsm2d_merge_scene_batch", self._ctx.handle)
+        scenes._set_pending()
+        self.counts = counts
+        return sizes
 
 
 def _data_pointer(a):
@@ -939,3 +1009,78 @@ class RawDataPreprocessorProjective2D:
         out._set_pending()
         self._meas = out
         return out
+
+
+class TrackerBatch:
+    """N independent live trackers stepped together, one robot model for all of them: the reference's tracker step (clip the local map
+    around the odometry guess, align the front and the rear scan with the odometry prior, merge both scans at the corrected pose;
+    MULTI.json:464-482) as ONE call of each batched kernel per step.  Every tracker's result is what the single-tracker calls give for it.
+
+    ``aligner`` carries two projective ``AlignerSliceProcessorLaser2DWithSensor`` slices (front, rear); their sensor offsets place the scans,
+    the first one the clip.  The pose composition is float64 per tracker, as a single tracker's host side does it.  One wait per step:
+    the aligner's poses."""
+
+    def __init__(self, ctx: Context, n_trackers: int, projector: PointNormal2fProjectorPolar, preprocessor: RawDataPreprocessorProjective2D,
+                 aligner: MultiAligner2D, angle_min: float, angle_max: float, range_min: float = 0.0, range_max: float = float("inf"),
+                 merge_threshold: float = 0.2, prior_omega=None, map_capacity: int = 50000):
+        from . import synth
+        if len(aligner.param_slice_processors) != 2:
+            raise ValueError("TrackerBatch: the aligner needs two slices (front and rear scan)")
+        self._ctx, self.n = ctx, int(n_trackers)
+        self._synth = synth
+        self.projector, self.preprocessor, self.aligner = projector, preprocessor, aligner
+        self._msg = (float(angle_min), float(angle_max), float(range_min), float(range_max))
+        self.sensor_in_robot = [np.asarray(getattr(s, "sensor_in_robot", (0.0, 0.0, 0.0)), np.float32).reshape(3)
+                                for s in aligner.param_slice_processors]
+        self.maps = CloudSet.reserved_many(ctx, self.n, map_capacity)
+        self.clipped = CloudSet.reserved_many(ctx, self.n, projector.param_canvas_cols)
+        self.scans = [None, None]            # the two scan sets (lsm2d_preprocess_scans once, refilled every step)
+        self.clipper = SceneClipperProjective2D(ctx, projector, voxelize_resolution=0.0, asynchronous=True)
+        self.clipper.setSensorInRobot(self.sensor_in_robot[0])
+        self.merger = MergerProjective2D(ctx, projector, merge_threshold, asynchronous=True)
+        om = np.diag([100.0, 100.0, 100.0]) if prior_omega is None else prior_omega
+        self._priors = [(np.zeros(3, np.float32), np.asarray(om, np.float32).reshape(3, 3))] * self.n
+        self.estimate = np.zeros((self.n, 3), np.float64)      # robot in local map, per tracker
+        self.guess = np.zeros((self.n, 3), np.float32)
+
+    def _sensor_poses(self, poses):
+        c, s_ = self._synth.compose_poses, self.sensor_in_robot
+        return np.array([[np.float32(c(np.asarray(p, np.float64)[None, :], s.astype(np.float64)[None, :])[0]) for s in s_] for p in poses], np.float32)
+
+    def _fill(self, k: int, ranges):
+        a0, a1, r0, r1 = self._msg
+        self.preprocessor.setRawData(np.ascontiguousarray(ranges, np.float32).reshape(self.n, -1), a0, a1, r0, r1)
+        if self.scans[k] is None:
+            self.scans[k] = self.preprocessor.compute()
+        else:
+            self.preprocessor.refill(self.scans[k])
+            self.scans[k]._set_pending()      # (the sizes are the device's until asked for)
+
+    def reset(self, indices, ranges_front, ranges_rear, poses):
+        """Trackers ``indices`` start a new local map at ``poses`` [len(indices)][3] (robot in local map) from the two scans given
+        [len(indices)][beams]: their maps are emptied and both scans merged, as a single tracker starts."""
+        idx = np.ascontiguousarray(indices, np.int32).ravel()
+        p = np.asarray(poses, np.float64).reshape(len(idx), 3)
+        a0, a1, r0, r1 = self._msg
+        meas = []
+        for r in (ranges_front, ranges_rear):
+            self.preprocessor.setRawData(np.ascontiguousarray(r, np.float32).reshape(len(idx), -1), a0, a1, r0, r1)
+            meas.append(self.preprocessor.compute())
+        self.maps.clear(idx)
+        self.merger.compute_batch(self.maps, meas, self._sensor_poses(p), scene_index=idx)
+        self.estimate[idx] = p
+        self._reset_meas = meas      # (read by the merge launch: kept until the next reset)
+
+    def step(self, ranges_front, ranges_rear, odometry):
+        """One tracker step of all N trackers: returns (pose [N][3] float32 -- the aligner's moving-in-fixed --, status [N], information [N][3][3]).
+        ``estimate`` then holds every tracker's corrected pose, float64."""
+        c, inv = self._synth.compose_poses, self._synth.invert_poses
+        odo = np.asarray(odometry, np.float64).reshape(self.n, 3)
+        self._fill(0, ranges_front); self._fill(1, ranges_rear)
+        self.guess = np.array([c(self.estimate[i][None, :], odo[i][None, :])[0] for i in range(self.n)], np.float32)
+        self.clipper.compute_batch(self.maps, self.guess, self.clipped)
+        r = self.aligner.compute_batch(self.scans, [self.clipped, self.clipped], np.zeros((self.n, 3), np.float32), priors=self._priors)
+        x = r.pose
+        self.estimate = np.array([c(self.guess[i][None, :].astype(np.float64), inv(x[i][None, :].astype(np.float64)))[0] for i in range(self.n)], np.float64)
+        self.merger.compute_batch(self.maps, self.scans, self._sensor_poses(self.estimate))
+        return x, r.status, r.information

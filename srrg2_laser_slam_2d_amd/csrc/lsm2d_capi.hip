@@ -273,7 +273,8 @@ struct lsm2d_cloudset {
   int32_t n_clouds = 0;
   mutable int64_t total = 0;  // logical points
   int64_t padded_total = 0;   // device points incl. even-alignment padding
-  int64_t capacity = 0;       // > 0: a reserved single growable cloud (lsm2d_cloudset_create_reserved)
+  int64_t capacity = 0;       // > 0: a reserved single growable cloud (lsm2d_cloudset_create_reserved) -- or, with `many`, the room of every cloud
+  bool many = false;          // lsm2d_cloudset_create_reserved_many: n_clouds growable clouds in fixed slots; never taken for a single reserved cloud
   float2* d_xy = nullptr; float2* d_nrm = nullptr;
   int32_t* d_start = nullptr; int32_t* d_count = nullptr;
   float* d_ranges = nullptr;      // lsm2d_preprocess_scans_refill: the device copy of the ranges the set was last refilled from
@@ -413,6 +414,8 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   (void) hipFuncSetAttribute((const void*) k_clip_small, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_merge_small, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_merge_multi, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+  (void) hipFuncSetAttribute((const void*) k_clip_batch, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+  (void) hipFuncSetAttribute((const void*) k_merge_batch, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_split_project<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_split_project<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipGetLastError();

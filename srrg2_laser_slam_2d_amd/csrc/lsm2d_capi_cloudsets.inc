@@ -220,6 +220,46 @@ extern "C" int lsm2d_cloudset_create_reserved(lsm2d_context* ctx, int64_t capaci
   return LSM2D_SUCCESS;
 }
 
+extern "C" int lsm2d_cloudset_create_reserved_many(lsm2d_context* ctx, int32_t n_clouds, int64_t capacity, lsm2d_cloudset** out) {
+  if (!ctx || !out || n_clouds < 1 || capacity < 1 || capacity > 0x7ffffff0) return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_create_reserved_many: bad argument");
+  *out = nullptr;
+  const int64_t stride = capacity + (capacity & 1);      // every slot starts on an even point (16-byte aligned xy), as cloudset_layout lays them out
+  if (stride * n_clouds > 0x7ffffff0) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "cloudset_create_reserved_many: too many points");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  lsm2d_cloudset* cs = new (std::nothrow) lsm2d_cloudset;
+  if (!cs) return LSM2D_OUT_OF_MEMORY;
+  cs->ctx = ctx; ctx->live_sets.push_back(cs); cs->n_clouds = n_clouds; cs->total = 0; cs->capacity = capacity; cs->many = true;
+  cs->padded_total = stride * n_clouds + 2;
+  cs->h_start.resize(n_clouds); cs->h_count.assign(n_clouds, 0);
+  for (int32_t c = 0; c < n_clouds; ++c) cs->h_start[c] = (int32_t) (stride * c);
+  int rc = cloudset_alloc(ctx, cs);
+  if (rc == LSM2D_SUCCESS) { hipError_t e = stream_sync(ctx); if (e != hipSuccess) rc = LSM2D_DEVICE_ERROR; }
+  if (rc != LSM2D_SUCCESS) { lsm2d_cloudset_destroy(cs); return rc; }
+  *out = cs;
+  return LSM2D_SUCCESS;
+}
+
+// asynchronous: the device-side sizes of the named clouds are zeroed on the context's stream (contiguous runs of indices: one memset each)
+extern "C" int lsm2d_cloudset_clear_clouds(lsm2d_cloudset* cs, int32_t n, const int32_t* idx) {
+  lsm2d_context* ctx = cs ? cs->ctx : nullptr;
+  if (!cs || !ctx || !cs->many || (idx && n < 0)) return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_clear_clouds: bad argument");
+  const int32_t m = idx ? n : cs->n_clouds;
+  for (int32_t k = 0; k < m; ++k) if (idx && (idx[k] < 0 || idx[k] >= cs->n_clouds)) return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_clear_clouds: cloud index out of range");
+  if (m == 0) return LSM2D_SUCCESS;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
+  cloudset_drop_grids(cs);
+  for (int32_t k = 0; k < m;) {
+    const int32_t c0 = idx ? idx[k] : k;
+    int32_t len = 1;
+    while (k + len < m && (idx ? idx[k + len] : k + len) == c0 + len) ++len;
+    HIPCHK(ctx, hipMemsetAsync(cs->d_count + c0, 0, sizeof(int32_t) * (size_t) len, ctx->stream));
+    for (int32_t c = c0; c < c0 + len; ++c) { cs->total -= cs->h_count[c]; cs->h_count[c] = 0; }      // exact zeros (the others stay what they were: sizes or bounds)
+    k += len;
+  }
+  return LSM2D_SUCCESS;
+}
+
 static int set_single_count(lsm2d_context* ctx, lsm2d_cloudset* cs, int32_t n) {
   cs->h_count[0] = n; cs->total = n;
   HIPCHK(ctx, hipMemcpyAsync(cs->d_count, cs->h_count.data(), sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -236,7 +276,7 @@ static int acquire_upload_stage(lsm2d_cloudset* cs, size_t need) {
   if (cs->stage_on_side) { HIPCHK(ctx, hipEventSynchronize(cs->ev_stage)); cs->stage_on_side = false; }
   if (need > cs->h_upload_bytes) {
     if (cs->h_upload) { HIPCHK(ctx, hipHostFree(cs->h_upload)); cs->h_upload = nullptr; cs->h_upload_bytes = 0; }
-    const size_t want = cs->capacity > 0 ? sizeof(float) * 4 * (size_t) cs->capacity + 16 : need;
+    const size_t want = cs->capacity > 0 && !cs->many ? sizeof(float) * 4 * (size_t) cs->capacity + 16 : need;      // (a set of many clouds stages the batched calls' per-tracker arguments only)
     HIPCHK(ctx, hipHostMalloc(&cs->h_upload, want > need ? want : need, hipHostMallocCoherent | hipHostMallocMapped));
     HIPCHK(ctx, hipHostGetDevicePointer(&cs->h_upload_dev, cs->h_upload, 0));
     cs->h_upload_bytes = want > need ? want : need;
@@ -245,7 +285,7 @@ static int acquire_upload_stage(lsm2d_cloudset* cs, size_t need) {
 }
 
 extern "C" int lsm2d_cloudset_upload(lsm2d_cloudset* cs, const float* pts, int64_t n) {
-  if (!cs || !cs->ctx || cs->n_clouds != 1 || n < 0 || (n > 0 && !pts)) return fail(cs ? cs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "cloudset_upload: bad argument");
+  if (!cs || !cs->ctx || cs->n_clouds != 1 || cs->many || n < 0 || (n > 0 && !pts)) return fail(cs ? cs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "cloudset_upload: bad argument");
   lsm2d_context* ctx = cs->ctx;
   const int64_t cap = cs->capacity > 0 ? cs->capacity : cs->padded_total - 2;
   if (n > cap) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "cloudset_upload: does not fit the allocation");

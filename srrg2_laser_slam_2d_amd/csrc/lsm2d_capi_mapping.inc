@@ -131,7 +131,7 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
 
 // the live tracker's form: ONE scan into an existing reserved set, no allocation, no wait (size pending on the device)
 extern "C" int lsm2d_preprocess_scan_into(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const float* ranges, lsm2d_cloudset* out) {
-  if (!ctx || !pp || !ranges || !out || out->ctx != ctx || out->n_clouds != 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scan_into: bad argument");
+  if (!ctx || !pp || !ranges || !out || out->ctx != ctx || out->n_clouds != 1 || out->many) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scan_into: bad argument");
   const int nb = pp->n_beams;
   if (nb < 1 || nb > kPrepMaxBeams) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scan_into: n_beams must be in [1, 2048]");
   if (!(pp->angle_max > pp->angle_min) || pp->normal_min_points < 1 || !(pp->normal_point_distance >= 0.0f))
@@ -186,7 +186,7 @@ static int clip_scene_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const 
                            const float robot_in_local_map[3], const float sensor_in_robot[3], float vox_res, lsm2d_cloudset* clipped,
                            int32_t* out_n, int32_t* out_src) {
   if (!ctx || !pr || !robot_in_local_map || !sensor_in_robot || !clipped || !valid_cloud_index(scene, si) || clipped->n_clouds != 1 ||
-      clipped == scene || (!out_n && out_src))
+      clipped == scene || clipped->many || scene->many || (!out_n && out_src))
     return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene: bad argument");
   const bool vox = vox_res > 0.0f;
   if (vox && out_src) return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene: a voxelised cloud has no source indices");
@@ -267,7 +267,7 @@ extern "C" int lsm2d_clip_scene_voxelized(lsm2d_context* ctx, const lsm2d_projec
 extern "C" int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* pr, lsm2d_cloudset* scene, const lsm2d_cloudset* meas,
                                  int32_t mi, const float measurement_in_scene[3], float merge_threshold, int32_t* out_size,
                                  int32_t* out_counts) {
-  if (!ctx || !pr || !scene || !measurement_in_scene || !valid_cloud_index(meas, mi) || scene->n_clouds != 1 || scene == meas || (!out_size && out_counts))
+  if (!ctx || !pr || !scene || !measurement_in_scene || !valid_cloud_index(meas, mi) || scene->n_clouds != 1 || scene->many || scene == meas || (!out_size && out_counts))
     return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene: bad argument");
   ProjK P;
   if (!make_projk(*pr, &P)) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene: bad projector");
@@ -347,7 +347,7 @@ extern "C" int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* pr, 
 extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr, lsm2d_cloudset* scene, int32_t n_measurements,
                                   const lsm2d_cloudset* const* meas, const int32_t* meas_index, const float* measurement_in_scene,
                                   float merge_threshold, int32_t* out_size, int32_t* out_counts) {
-  if (!ctx || !pr || !scene || !meas || !measurement_in_scene || n_measurements < 1 || scene->n_clouds != 1 || (!out_size && out_counts))
+  if (!ctx || !pr || !scene || !meas || !measurement_in_scene || n_measurements < 1 || scene->n_clouds != 1 || scene->many || (!out_size && out_counts))
     return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scenes: bad argument");
   for (int k = 0; k < n_measurements; ++k)
     if (!valid_cloud_index(meas[k], meas_index ? meas_index[k] : 0) || meas[k] == scene) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scenes: bad measurement");
@@ -403,6 +403,159 @@ extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr,
   const int32_t* h = (const int32_t*) ((char*) ctx->h_stage + o_out);
   scene->h_count[0] = h[4 * (n - 1)]; scene->total = scene->h_count[0]; scene->count_pending = false; *out_size = scene->h_count[0];
   if (out_counts) for (int k = 0; k < n; ++k) { out_counts[3 * k] = h[4 * k + 1]; out_counts[3 * k + 1] = h[4 * k + 2]; out_counts[3 * k + 2] = h[4 * k + 3]; }
+  return LSM2D_SUCCESS;
+}
+
+// ---- N independent trackers per call: batched clipper and merger ------------------------------------------------------------------
+// The per-tracker arguments go to the OUTPUT set's own pinned buffer (acquire_upload_stage: it waits only when the set's previous batch has not
+// been waited for since -- in a tracker step the aligner's wait comes in between), which the kernel reads directly: nothing else is staged, so
+// an asynchronous call leaves nothing behind in the context's staging buffer that a later call could overwrite under it.
+extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector* pr, const lsm2d_cloudset* scenes, int32_t n,
+                                      const int32_t* scene_index, const float* robot_in_local_map, const float sensor_in_robot[3],
+                                      lsm2d_cloudset* clipped, int32_t* out_n) {
+  if (!ctx || !pr || !scenes || !robot_in_local_map || !sensor_in_robot || !clipped || n < 1 || scenes == clipped ||
+      scenes->ctx != ctx || clipped->ctx != ctx || !clipped->many || clipped->n_clouds < n)
+    return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: bad argument (clipped: a reserved-many set of >= n_trackers clouds, not the scenes' set)");
+  for (int i = 0; i < n; ++i)
+    if (!valid_cloud_index(scenes, scene_index ? scene_index[i] : i)) return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: scene index out of range");
+  ProjK P;
+  if (!make_projk(*pr, &P)) return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: bad projector");
+  if (clipped->capacity < P.cols) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: clipped clouds smaller than canvas_cols");
+  if ((int) (sizeof(u64) * (size_t) P.cols) + 512 > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: canvas does not fit LDS");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  { const int rc0 = flush_pending(scenes); if (rc0) return rc0; }
+  HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
+  int rc = acquire_upload_stage(clipped, sizeof(ClipBatchItem) * (size_t) n + 16); if (rc) return rc;
+  if (out_n) { rc = ensure_stage(ctx, sizeof(int32_t) * (size_t) n + 16); if (rc) return rc; }
+  cloudset_drop_grids(clipped);
+  ClipBatchItem* items = (ClipBatchItem*) clipped->h_upload;
+  for (int i = 0; i < n; ++i) {      // the single call's transform (clip_scene_impl), per tracker
+    const int si = scene_index ? scene_index[i] : i;
+    float cam[3], cam_inv[3];
+    compose_host(robot_in_local_map + 3 * i, sensor_in_robot, cam); inverse_host(cam, cam_inv);
+    items[i].T = make_iso(cam_inv); items[i].start = scenes->h_start[si]; items[i].n = scenes->count_pending ? -1 : scenes->h_count[si]; items[i].si = si; items[i].pad = 0;
+  }
+  ClipBatchArgs A;
+  A.xy = scenes->d_xy; A.nrm = scenes->d_nrm; A.scene_count_dev = scenes->d_count; A.items = (const ClipBatchItem*) clipped->h_upload_dev;
+  A.proj = P; A.S = make_iso(sensor_in_robot);
+  A.s_identity = sensor_in_robot[0] == 0.0f && sensor_in_robot[1] == 0.0f && sensor_in_robot[2] == 0.0f;
+  A.out_xy = clipped->d_xy; A.out_nrm = clipped->d_nrm; A.out_stride = clipped->n_clouds > 1 ? clipped->h_start[1] : 0; A.out_count_dev = clipped->d_count;
+  A.host_polls = out_n != nullptr; A.out_count = nullptr;
+  int32_t* h_out = (int32_t*) ctx->h_stage;
+  if (out_n) {
+    char* dvo = nullptr; rc = stage_device_view(ctx, &dvo); if (rc) return rc;
+    A.out_count = (int32_t*) dvo;
+    for (int i = 0; i < n; ++i) h_out[i] = kStatusNotWritten;
+  }
+  hipLaunchKernelGGL(k_clip_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * (size_t) P.cols, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  clipped->staged_epoch = ctx->sync_epoch;
+  ctx->have_timing = false;
+  if (!out_n) {                               // at most one point per column
+    for (int i = 0; i < n; ++i) { clipped->total += (int64_t) P.cols - clipped->h_count[i]; clipped->h_count[i] = P.cols; }
+    clipped->count_pending = true;
+    return LSM2D_SUCCESS;
+  }
+  HIPCHK(ctx, wait_for_statuses(ctx, h_out, n));      // every workgroup writes its count last
+  // (exact sizes now for clouds 0 .. n; a set whose other clouds' sizes were pending stays pending: their numbers are still upper bounds)
+  for (int i = 0; i < n; ++i) { clipped->total += (int64_t) h_out[i] - clipped->h_count[i]; clipped->h_count[i] = h_out[i]; out_n[i] = h_out[i]; }
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector* pr, lsm2d_cloudset* scenes, int32_t n,
+                                       const int32_t* scene_index, int32_t n_measurements, const lsm2d_cloudset* const* meas,
+                                       const int32_t* meas_index, const float* measurement_in_scene, float merge_threshold,
+                                       int32_t* out_sizes, int32_t* out_counts) {
+  if (!ctx || !pr || !scenes || !meas || !measurement_in_scene || n < 1 || n_measurements < 1 || n_measurements > kMergeMulti ||
+      scenes->ctx != ctx || !scenes->many || (!out_sizes && out_counts))
+    return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: bad argument (scenes: a reserved-many set; 1 <= n_measurements <= 4)");
+  const int nm = n_measurements;
+  for (int k = 0; k < nm; ++k) {
+    if (!meas[k] || meas[k] == scenes || meas[k]->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: bad measurement set");
+    for (int i = 0; i < n; ++i)
+      if (!valid_cloud_index(meas[k], meas_index ? meas_index[(size_t) k * n + i] : i)) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: measurement index out of range");
+  }
+  {   // every scene once
+    std::vector<char> seen((size_t) scenes->n_clouds, 0);
+    for (int i = 0; i < n; ++i) {
+      const int si = scene_index ? scene_index[i] : i;
+      if (!valid_cloud_index(scenes, si)) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: scene index out of range");
+      if (seen[(size_t) si]) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: a scene index appears twice");
+      seen[(size_t) si] = 1;
+    }
+  }
+  ProjK P;
+  if (!make_projk(*pr, &P)) return fail(ctx, LSM2D_BAD_ARGUMENT, "merge_scene_batch: bad projector");
+  if ((int) (sizeof(u64) * 2 * (size_t) P.cols) + 512 > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "merge_scene_batch: canvases do not fit LDS");
+  // all or nothing: upper bounds first, the real sizes (one wait) only when a bound does not settle it
+  const int64_t cap = scenes->capacity, grow = (int64_t) nm * P.cols;
+  for (int pass = 0; pass < 2; ++pass) {
+    int short_of_room = -1;
+    for (int i = 0; i < n && short_of_room < 0; ++i) if ((int64_t) scenes->h_count[scene_index ? scene_index[i] : i] + grow > cap) short_of_room = i;
+    if (short_of_room < 0) break;
+    if (pass == 0 && scenes->count_pending) { const int rc0 = resolve_count(scenes); if (rc0) return rc0; continue; }
+    char msg[160];
+    snprintf(msg, sizeof msg, "merge_scene_batch: the scene of tracker %d (cloud %d) has no room for n_measurements * canvas_cols more points", short_of_room,
+             scene_index ? scene_index[short_of_room] : short_of_room);
+    return fail(ctx, LSM2D_CAPACITY_EXCEEDED, msg);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  for (int k = 0; k < nm; ++k) { const int rc0 = flush_pending(meas[k]); if (rc0) return rc0; }
+  HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
+  const size_t o_items = ((sizeof(int4) * (size_t) n) + 15) & ~(size_t) 15;
+  int rc = acquire_upload_stage(scenes, o_items + sizeof(MergeBatchItem) * (size_t) n * nm + 16); if (rc) return rc;
+  const size_t out_bytes = sizeof(int32_t) * 4 * (size_t) n * nm;
+  rc = ensure_scratch(ctx, out_bytes + 16); if (rc) return rc;
+  if (out_sizes) { rc = ensure_stage(ctx, out_bytes + 16); if (rc) return rc; }
+  cloudset_drop_grids(scenes);
+  int4* hs = (int4*) scenes->h_upload;
+  MergeBatchItem* items = (MergeBatchItem*) ((char*) scenes->h_upload + o_items);
+  for (int i = 0; i < n; ++i) {
+    const int si = scene_index ? scene_index[i] : i;
+    hs[i] = make_int4(scenes->h_start[si], scenes->count_pending ? -1 : scenes->h_count[si], si, 0);
+    for (int k = 0; k < nm; ++k) {      // lsm2d_merge_scenes' transforms, per tracker and measurement
+      const lsm2d_cloudset* ms = meas[k]; const int mi = meas_index ? meas_index[(size_t) k * n + i] : i;
+      const float* mis = measurement_in_scene + 3 * ((size_t) i * nm + k);
+      float cam_inv[3]; inverse_host(mis, cam_inv);
+      MergeBatchItem& it = items[(size_t) i * nm + k];
+      it.Tinv = make_iso(cam_inv); it.M = make_iso(mis); it.mstart = ms->h_start[mi]; it.n_meas = ms->count_pending ? -1 : ms->h_count[mi]; it.mc = mi; it.pad = 0;
+    }
+  }
+  MergeBatchArgs A;
+  A.sxy = scenes->d_xy; A.snrm = scenes->d_nrm; A.scene_count_dev = scenes->d_count;
+  A.scenes = (const int4*) scenes->h_upload_dev; A.items = (const MergeBatchItem*) ((char*) scenes->h_upload_dev + o_items);
+  for (int k = 0; k < kMergeMulti; ++k) {
+    const lsm2d_cloudset* ms = meas[k < nm ? k : 0];
+    A.mxy[k] = ms->d_xy; A.mnrm[k] = ms->d_nrm; A.mcount_dev[k] = ms->d_count;
+  }
+  A.proj = P; A.far_limit = 0.9f * pr->range_max; A.merge_threshold = merge_threshold; A.n_meas = nm;
+  A.host_polls = out_sizes != nullptr;
+  const int32_t* h_out = (const int32_t*) ctx->h_stage;
+  if (out_sizes) {
+    char* dvo = nullptr; rc = stage_device_view(ctx, &dvo); if (rc) return rc;
+    A.out = (int32_t*) dvo;
+    for (int i = 0; i < n; ++i) ((int32_t*) ctx->h_stage)[4 * ((size_t) i * nm + nm - 1)] = kStatusNotWritten;
+  } else {
+    A.out = (int32_t*) ctx->d_scratch;
+  }
+  hipLaunchKernelGGL(k_merge_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * 2 * (size_t) P.cols, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  scenes->staged_epoch = ctx->sync_epoch;
+  ctx->have_timing = false;
+  if (!out_sizes) {                           // every merge appends at most one point per column
+    for (int i = 0; i < n; ++i) { const int si = scene_index ? scene_index[i] : i; scenes->h_count[si] += (int32_t) grow; scenes->total += grow; }
+    scenes->count_pending = true;
+    return LSM2D_SUCCESS;
+  }
+  // every tracker's last new size, each written last by its workgroup: polled one after the other (a stride of n_measurements counters)
+  for (int i = 0; i < n; ++i) HIPCHK(ctx, wait_for_statuses(ctx, h_out + 4 * ((size_t) i * nm + nm - 1), 1));
+  // (exact sizes now for the scenes merged into; a set whose other clouds' sizes were pending stays pending)
+  for (int i = 0; i < n; ++i) {
+    const int si = scene_index ? scene_index[i] : i;
+    const int32_t* h = h_out + 4 * ((size_t) i * nm);
+    scenes->total += (int64_t) h[4 * (nm - 1)] - scenes->h_count[si]; scenes->h_count[si] = h[4 * (nm - 1)]; out_sizes[i] = h[4 * (nm - 1)];
+    if (out_counts) for (int k = 0; k < nm; ++k) { out_counts[3 * ((size_t) i * nm + k)] = h[4 * k + 1]; out_counts[3 * ((size_t) i * nm + k) + 1] = h[4 * k + 2]; out_counts[3 * ((size_t) i * nm + k) + 2] = h[4 * k + 3]; }
+  }
   return LSM2D_SUCCESS;
 }
 

@@ -514,3 +514,86 @@ __global__ __launch_bounds__(kPrepSmallBlock) void k_preprocess_scans_small(cons
 static constexpr int kPrepMulti = 4;
 struct PrepMultiArgs { PrepArgs a[kPrepMulti]; };
 __global__ __launch_bounds__(kPrepBlock) void k_preprocess_multi(const PrepMultiArgs M) { preprocess_scan_body<kPrepBlock, kPrepMaxBeams>(M.a[blockIdx.x], 0); }
+
+// ---- N independent trackers per launch (lsm2d_clip_scene_batch / lsm2d_merge_scene_batch): one workgroup per tracker, each running the
+// single-tracker kernel's passes on its own clouds -- the same device bodies, so the same bits.  No workgroup waits for another.  The
+// per-tracker transforms are the host's (compose_host / inverse_host / make_iso, as the single calls compute them), read from a pinned
+// array of the output set's; sizes only the device knows are read from the sets' device-side counts.
+struct ClipBatchItem { Iso T; int32_t start, n, si, pad; };      // sensor_in_local_map^-1; the scene cloud's first point, size (-1: d_count[si])
+struct ClipBatchArgs {
+  const float2* xy; const float2* nrm; const int32_t* scene_count_dev;      // the scenes' set
+  const ClipBatchItem* items;                                              // [n_trackers]
+  ProjK proj; Iso S; int32_t s_identity;
+  float2* out_xy; float2* out_nrm; int32_t out_stride; int32_t* out_count_dev;      // tracker t writes cloud t of the clipped set (slot t * out_stride)
+  int32_t* out_count; int32_t host_polls;                                  // [n_trackers] in pinned memory, polled by the host (synchronous form), or nullptr
+};
+// any scene size in one workgroup: the canvas cells are atomicMin of the same 64-bit keys as the split path's, so the order of the updates does not matter
+__global__ __launch_bounds__(kFindBlock) void k_clip_batch(const ClipBatchArgs A) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  u64* can = reinterpret_cast<u64*>(smem);
+  __shared__ int s_tot[2 * (kFindBlock / 64)];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  const ClipBatchItem it = A.items[t];
+  for (int i = tid; i < A.proj.cols; i += kFindBlock) can[i] = kEmptyCell;
+  __syncthreads();
+  const int n = it.n >= 0 ? it.n : A.scene_count_dev[it.si];
+  project_cloud(A.xy + it.start, n, it.T, A.proj, can, tid, kFindBlock);
+  __syncthreads();
+  ClipEmitArgs E;
+  E.gcanvas = nullptr; E.cols = A.proj.cols; E.xy = A.xy + it.start; E.nrm = A.nrm + it.start;
+  E.T = it.T; E.S = A.S; E.s_identity = A.s_identity;
+  E.out_xy = A.out_xy + (size_t) t * A.out_stride; E.out_nrm = A.out_nrm + (size_t) t * A.out_stride; E.out_src = nullptr;
+  E.out_count_dev = A.out_count_dev + t; E.out_count = A.host_polls ? A.out_count + t : A.out_count_dev + t; E.host_polls = A.host_polls;
+  clip_emit_body(E, can, s_tot, tid);
+}
+
+// per (tracker, measurement): measurement_in_scene^-1 and measurement_in_scene; the measurement cloud's first point and size (-1: its set's d_count[mc])
+struct MergeBatchItem { Iso Tinv, M; int32_t mstart, n_meas, mc, pad; };
+struct MergeBatchArgs {
+  float2* sxy; float2* snrm; int32_t* scene_count_dev;                     // the scenes' set (a reserved-many set)
+  const int4* scenes;                                                      // [n_trackers]: (first point, size or -1, cloud index, -)
+  const MergeBatchItem* items;                                             // [n_trackers][n_meas]
+  const float2* mxy[kMergeMulti]; const float2* mnrm[kMergeMulti]; const int32_t* mcount_dev[kMergeMulti];      // the measurement sets
+  ProjK proj; float far_limit, merge_threshold; int32_t n_meas;
+  int32_t* out;                                                            // [n_trackers][n_meas][4]: new size, new, merged, replaced
+  int32_t host_polls;                                                      // out is pinned memory; the host polls every tracker's last new size
+};
+// k_merge_multi's loop per workgroup: the scene's new size is carried from one measurement to the next inside the workgroup
+__global__ __launch_bounds__(kFindBlock) void k_merge_batch(const MergeBatchArgs A) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  u64* scan = reinterpret_cast<u64*>(smem);
+  u64* mcan = scan + A.proj.cols;
+  __shared__ int s_tot[2 * (kFindBlock / 64)];
+  __shared__ int s_cnt[4];
+  __shared__ MergeBatchItem s_items[kMergeMulti];
+  const int tid = threadIdx.x, t = blockIdx.x, nm = A.n_meas;
+  // the pinned arguments in one round trip (every measurement's together), then the sizes only the device knows, their loads in flight together
+  const int4 sc = A.scenes[t];
+  if (tid < nm * (int) (sizeof(MergeBatchItem) / 4)) reinterpret_cast<int32_t*>(s_items)[tid] = reinterpret_cast<const int32_t*>(A.items + (size_t) t * nm)[tid];
+  __syncthreads();
+  int n_scene = sc.y >= 0 ? sc.y : A.scene_count_dev[sc.z];
+  int n_meas_of[kMergeMulti];
+#pragma unroll
+  for (int k = 0; k < kMergeMulti; ++k) n_meas_of[k] = k < nm ? (s_items[k].n_meas >= 0 ? s_items[k].n_meas : A.mcount_dev[k][s_items[k].mc]) : 0;
+  for (int k = 0; k < nm; ++k) {
+    const Iso Tinv = s_items[k].Tinv, M = s_items[k].M;
+    const int mstart = s_items[k].mstart;
+    for (int i = tid; i < A.proj.cols; i += kFindBlock) { scan[i] = kEmptyCell; mcan[i] = kEmptyCell; }
+    if (tid < 4) s_cnt[tid] = 0;
+    __syncthreads();
+    MergeArgs m;
+    m.scanvas = nullptr; m.mcanvas = nullptr; m.cols = A.proj.cols; m.sxy = A.sxy + sc.x; m.snrm = A.snrm + sc.x; m.n_scene = n_scene;
+    m.mxy = A.mxy[k] + mstart; m.mnrm = A.mnrm[k] + mstart; m.far_limit = A.far_limit; m.merge_threshold = A.merge_threshold;
+    m.out = A.out + 4 * ((size_t) t * nm + k); m.count_dev = A.scene_count_dev + sc.z; m.host_polls = A.host_polls && k == nm - 1;
+    const int n_meas = k == 0 ? n_meas_of[0] : (k == 1 ? n_meas_of[1] : (k == 2 ? n_meas_of[2] : n_meas_of[3]));
+    project_cloud(m.sxy, m.n_scene, Tinv, A.proj, scan, tid, kFindBlock);
+    for (int i = tid; i < n_meas; i += kFindBlock) {
+      const float2 p = m.mxy[i];
+      float x, y; xf_point(M, p.x, p.y, x, y);
+      project_point(Tinv, A.proj, x, y, i, mcan);
+    }
+    __syncthreads();
+    n_scene = m.n_scene + merge_apply_body(m, scan, mcan, &M, s_tot, s_cnt, tid);
+    __syncthreads();
+  }
+}

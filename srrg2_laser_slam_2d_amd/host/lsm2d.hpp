@@ -9,6 +9,8 @@
 //       iterationStats / status
 //   LaserMessageBatchStream            batches of fresh LaserMessages through preprocessor + aligner, pipelined over three scan sets
 //       (lsm2d_preprocess_scans_refill, lsm2d_align_batch_begin / _wait)
+//   TrackerBatch                       N independent live trackers stepped together: one batched clip, align and merge per step
+//       (lsm2d_clip_scene_batch, lsm2d_align_batch, lsm2d_merge_scene_batch), each tracker's bits those of the single-tracker calls
 // This header depends on nothing but the C ABI and the standard library, so it compiles with plain g++;
 // the SRRG-side adapter (adapters/srrg/) is the same code expressed with srrg2_core types.
 #pragma once
@@ -464,6 +466,92 @@ class LoopClosureSweep {
     if (rc < 0) throw std::runtime_error(std::string("LoopClosureSweep::") + where + "| " + lsm2d_status_string(rc) + ": " + lsm2d_sweep_last_error(_sw));
   }
   lsm2d_sweep* _sw = nullptr;
+};
+
+// N independent live trackers with one robot model (MULTI.json:464-482 for each of them): clip the local map around the odometry guess, align the
+// front and the rear scan (two projective slices with their sensor offsets) with the odometry prior, merge both scans at the corrected pose --
+// one call of each batched entry point per step, ONE wait (the aligner's poses).  Poses compose in double on the host, per tracker.
+class TrackerBatch {
+ public:
+  struct Params {
+    lsm2d_projector projector{721, -(float) M_PI, (float) M_PI, 0.3f, 20.0f, 0.0f};
+    lsm2d_preprocessor preprocessor{721, -2.34747f, 2.35619f, 0.3f, 20.0f, 0.3f, 5, 0.02f};
+    std::array<lsm2d_slice_params, 2> slices{};          // front, rear: projective, sensor_in_robot set (the first one's is also the clip's)
+    lsm2d_aligner_params aligner{10, 10, 0.0f, 0.0f, 0, 0};
+    std::array<float, 9> prior_omega{{100, 0, 0, 0, 100, 0, 0, 0, 100}};
+    float merge_threshold = 0.2f;
+    int64_t map_capacity = 50000;
+  };
+  TrackerBatch(Context& ctx, int32_t n_trackers, const Params& p) : _ctx(ctx), _n(n_trackers), _p(p), _est((size_t) n_trackers * 3, 0.0),
+                                                                       _prior((size_t) n_trackers), _x((size_t) n_trackers * 3), _H((size_t) n_trackers * 9),
+                                                                       _status((size_t) n_trackers) {
+    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.map_capacity, &_maps), "lsm2d_cloudset_create_reserved_many", ctx.get());
+    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.projector.canvas_cols, &_clipped), "lsm2d_cloudset_create_reserved_many", ctx.get());
+    for (auto& q : _prior) { for (float& z : q.z) z = 0.0f; for (int k = 0; k < 9; ++k) q.omega[k] = p.prior_omega[(size_t) k]; }
+  }
+  ~TrackerBatch() { for (lsm2d_cloudset* s : {_maps, _clipped, _scans[0], _scans[1]}) lsm2d_cloudset_destroy(s); }
+  TrackerBatch(const TrackerBatch&) = delete; TrackerBatch& operator=(const TrackerBatch&) = delete;
+  int32_t size() const { return _n; }
+  // trackers idx[0 .. m) start a new local map at robot pose poses[m][3] from their scans front / rear [m][n_beams]
+  void reset(int32_t m, const int32_t* idx, const float* front, const float* rear, const double* poses) {
+    lsm2d_cloudset* meas[2] = {nullptr, nullptr};
+    const float* r[2] = {front, rear};
+    for (int s = 0; s < 2; ++s) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], m, &meas[s]), "lsm2d_preprocess_scans", _ctx.get());
+    std::vector<float> mis((size_t) m * 6);
+    for (int32_t i = 0; i < m; ++i) { std::copy(poses + 3 * i, poses + 3 * i + 3, &_est[(size_t) idx[i] * 3]); sensorPoses(idx[i], &mis[(size_t) i * 6]); }
+    int rc = lsm2d_cloudset_clear_clouds(_maps, m, idx);
+    const lsm2d_cloudset* ms[2] = {meas[0], meas[1]};
+    if (rc == LSM2D_SUCCESS) rc = lsm2d_merge_scene_batch(_ctx.get(), &_p.projector, _maps, m, idx, 2, ms, nullptr, mis.data(), _p.merge_threshold, nullptr, nullptr);
+    if (rc == LSM2D_SUCCESS) rc = lsm2d_synchronize(_ctx.get());      // (the scan sets go: the merge has read them)
+    lsm2d_cloudset_destroy(meas[0]); lsm2d_cloudset_destroy(meas[1]);
+    check(rc, "TrackerBatch::reset", _ctx.get());
+  }
+  // one step of every tracker: front / rear [N][n_beams] raw ranges (kept untouched until step() returns), odometry [N][3]
+  void step(const float* front, const float* rear, const double* odometry) {
+    const float* r[2] = {front, rear};
+    for (int s = 0; s < 2; ++s) {
+      if (!_scans[s]) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], _n, &_scans[s]), "lsm2d_preprocess_scans", _ctx.get());
+      else check(lsm2d_preprocess_scans_refill(_ctx.get(), &_p.preprocessor, r[s], _n, _scans[s]), "lsm2d_preprocess_scans_refill", _ctx.get());
+    }
+    std::vector<float> guess((size_t) _n * 3), x0((size_t) _n * 3, 0.0f), mis((size_t) _n * 6);
+    for (int32_t i = 0; i < _n; ++i) { double g[3]; compose(&_est[(size_t) i * 3], odometry + 3 * i, g); for (int c = 0; c < 3; ++c) guess[(size_t) i * 3 + c] = (float) g[c]; }
+    check(lsm2d_clip_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, guess.data(), _p.slices[0].sensor_in_robot, _clipped, nullptr), "lsm2d_clip_scene_batch", _ctx.get());
+    const lsm2d_cloudset* fixed[2] = {_scans[0], _scans[1]}; const lsm2d_cloudset* moving[2] = {_clipped, _clipped};
+    lsm2d_batch b{};
+    b.n_alignments = _n; b.n_slices = 2; b.slices = _p.slices.data(); b.fixed = fixed; b.moving = moving; b.init_pose = x0.data(); b.prior = _prior.data();
+    check(lsm2d_align_batch(_ctx.get(), &_p.aligner, &b, _x.data(), _H.data(), _status.data(), nullptr, nullptr), "lsm2d_align_batch", _ctx.get());
+    for (int32_t i = 0; i < _n; ++i) {          // estimate = guess * x^-1, then both scans at the corrected pose
+      const double xd[3] = {_x[(size_t) i * 3], _x[(size_t) i * 3 + 1], _x[(size_t) i * 3 + 2]}, gd[3] = {guess[(size_t) i * 3], guess[(size_t) i * 3 + 1], guess[(size_t) i * 3 + 2]};
+      double xi[3]; inverse(xd, xi); compose(gd, xi, &_est[(size_t) i * 3]); sensorPoses(i, &mis[(size_t) i * 6]);
+    }
+    const lsm2d_cloudset* ms[2] = {_scans[0], _scans[1]};
+    check(lsm2d_merge_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, 2, ms, nullptr, mis.data(), _p.merge_threshold, nullptr, nullptr), "lsm2d_merge_scene_batch", _ctx.get());
+  }
+  const std::vector<float>& movingInFixed() const { return _x; }         // [N][3]: the aligner's result of the last step
+  const std::vector<float>& informationMatrix() const { return _H; }     // [N][9]
+  const std::vector<int32_t>& status() const { return _status; }         // [N]
+  const std::vector<double>& robotInLocalMap() const { return _est; }    // [N][3]: every tracker's corrected pose
+  lsm2d_cloudset* localMaps() const { return _maps; }
+  lsm2d_cloudset* clippedScenes() const { return _clipped; }
+ private:
+  static void compose(const double a[3], const double b[3], double o[3]) {
+    const double c = std::cos(a[2]), s = std::sin(a[2]);
+    o[0] = a[0] + c * b[0] - s * b[1]; o[1] = a[1] + s * b[0] + c * b[1]; o[2] = a[2] + b[2];
+  }
+  static void inverse(const double a[3], double o[3]) {
+    const double c = std::cos(a[2]), s = std::sin(a[2]);
+    o[0] = -(c * a[0] + s * a[1]); o[1] = -(-s * a[0] + c * a[1]); o[2] = -a[2];
+  }
+  void sensorPoses(int32_t i, float* out) const {
+    for (int s = 0; s < 2; ++s) {
+      const double S[3] = {_p.slices[(size_t) s].sensor_in_robot[0], _p.slices[(size_t) s].sensor_in_robot[1], _p.slices[(size_t) s].sensor_in_robot[2]};
+      double m[3]; compose(&_est[(size_t) i * 3], S, m); for (int c = 0; c < 3; ++c) out[3 * s + c] = (float) m[c];
+    }
+  }
+  Context& _ctx; int32_t _n; Params _p;
+  std::vector<double> _est; std::vector<lsm2d_prior> _prior;
+  std::vector<float> _x, _H; std::vector<int32_t> _status;
+  lsm2d_cloudset *_maps = nullptr, *_clipped = nullptr, *_scans[2] = {nullptr, nullptr};
 };
 
 }  // namespace lsm2d_host
