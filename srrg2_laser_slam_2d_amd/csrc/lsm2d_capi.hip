@@ -24,17 +24,41 @@ using namespace lsm2d;
 
 static thread_local std::string g_last_error;
 
+// ---- batches in flight (lsm2d_align_batch_begin / _wait, round 5).  Everything a batch keeps between its launch and its results -- the pinned staging buffer its
+// results land in, the device scratch its arguments and statistics live in, the placement the estimate made for it, its timing events, the stream it launches
+// on -- forms a LANE.  The context has two (lsm2d_context::lanes) and an index, `cur`: every entry point works on lanes[cur] (lane()); begin() marks that lane
+// busy and flips the index, so whatever is called next (the refill and the begin of the FOLLOWING batch) finds a free lane; wait() frees the lane its batch
+// was begun on (lsm2d_pending::lane).  At most two batches are in flight.
+struct Lane {
+  // pinned host staging + device scratch, grown on demand (ensure_stage / ensure_scratch)
+  void* h_stage = nullptr; size_t h_stage_bytes = 0; void* h_stage_dev = nullptr;
+  void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
+  int32_t* d_order = nullptr;                                                // [4096] the placement the latest estimate made: kept for the next run of the SAME batch (order_valid / order_key / order_poses)
+  bool order_valid = false; unsigned long long order_key = 0; std::vector<float> order_poses;      // the placement d_order holds: which batch it was made for
+  // what the lane's device scratch holds as a batch's INPUT block (start poses, index arrays), byte for byte, while nothing else has used the scratch since: a batch
+  // that comes again with the same inputs needs no upload either (ensure_scratch invalidates it: every other user of the scratch comes through there)
+  std::vector<unsigned char> inputs_shadow; bool inputs_valid = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around the lane's latest timed launch (lsm2d_last_kernel_ms)
+  hipEvent_t ev_done = nullptr;                 // "this lane's batch's last operation has run"
+  bool busy = false;                            // a batch begun on this lane has not been waited for
+  // a batch begun asynchronously launches on ITS LANE's stream: two batches in flight are two streams, and the second one's workgroups fill the slots the first
+  // one's tail leaves free instead of waiting for its last workgroup (lane_stream; created on first use)
+  hipStream_t k_stream = nullptr;
+};
+// A side stream of the streamed pipeline with the event that orders other streams behind it, created on first use (make_side_stream)
+struct SideStream {
+  hipStream_t st = nullptr; hipEvent_t ev = nullptr;
+  bool dirty = false;         // something was queued here that the next aligner call has to wait for (join_pre_stream / join_refill_stream)
+  bool recorded = false;      // ev has been recorded at least once
+};
+
 struct lsm2d_context {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t last_ev0 = nullptr, last_ev1 = nullptr;      // the events lsm2d_last_kernel_ms reads: the current lane's, or those of the batch most recently waited for
   bool have_timing = false;
+  int timed_lane = -1;         // the lane whose ev0 / ev1 lsm2d_last_kernel_ms reads: the one that recorded the latest timed launch (note_timed), or whose batch was most recently waited for; -1: the current one
   std::string last_error;
-  // pinned host staging + device scratch, grown on demand
-  void* h_stage = nullptr; size_t h_stage_bytes = 0; void* h_stage_dev = nullptr;
-  void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
   void* d_split = nullptr; size_t d_split_bytes = 0;      // workspace of the split aligner path
   void* d_kd_work = nullptr; size_t d_kd_work_bytes = 0;  // working set of the KD-tree build (ping-pong copies, queues, counters): kept, grown on demand
   void* h_flag = nullptr;                                 // 256 pinned bytes of its own for small read-backs inside a call (the KD-tree build's level counts)
@@ -60,7 +84,6 @@ struct lsm2d_context {
   int balance_notes = 1;       // ... group the workgroup ids by the CU the previous launch of the same shape ran them on (0: assume b, b + n_cu, ...; A/B knob)
   int32_t* d_wg_place = nullptr; unsigned long long wg_place_shape = 0;      // the notes (one int per workgroup) and the launch shape they belong to
   uint32_t* d_xcd = nullptr; size_t d_xcd_bytes = 0;                         // the XCD window's counters (AlignArgs::xcd_sync), cleared per launch
-  int32_t* d_order = nullptr;                                                // [4096] the placement the latest estimate made: kept for the next run of the SAME batch (order_valid / order_key / order_poses)
   int proj_modes = 1;          // projective batches against map-sized clouds: the instantiation with the culled stream only (0: the shared one; A/B knob)
   int kd_modes = 1;            // KD-tree batches: the instantiations with one form of the descent only (0: the shared one; A/B knob)
   int nn_lds_only = 1;         // grid NN with every alignment's tables staged in LDS: the instantiation without the search in global memory (0: the shared one; A/B knob)
@@ -99,67 +122,45 @@ struct lsm2d_context {
   int estimate_reuse = 1;      // a prepared batch run again with unchanged start poses keeps its placement (no k_cull_estimate launch); experiments build: 0 switches that off
   int last_xcd_lockstep = 0;   // what the latest aligner call ran with (0: free-running)
   int last_cull_estimate = 0;  // what the latest aligner call did about the placement's estimate ("last_cull_estimate")
-  bool order_valid = false; unsigned long long order_key = 0; std::vector<float> order_poses;      // the placement d_order holds: which batch it was made for
   int last_query_cull = 0;     // the latest aligner call ran its point-query finder with the exact culling of the queries (k_align, tiles of 64 moving points)
   long long last_kd_levels = 0, last_kd_nodes = 0;      // shape of the most recently built KD-tree set (levels of the deepest tree, nodes in all of them)
   std::vector<lsm2d_cloudset*> live_sets;      // lsm2d_destroy orphans what is left (a set destroyed after its context must not touch it)
-  // ---- batches in flight (lsm2d_align_batch_begin / _wait, round 5).  Everything a batch keeps between its launch and its results -- the pinned staging buffer its
-  // results land in, the device scratch its arguments and statistics live in, the placement the estimate made for it, its timing events -- forms a LANE; the
-  // context has two: the members above (h_stage, d_scratch, d_order, order_*, ev0, ev1) are the CURRENT lane's, `parked` holds the other one's.  begin() works
-  // on the current lane, marks it busy and swaps: whatever is called next (the refill and the begin of the FOLLOWING batch) finds a free lane; wait() frees
-  // the lane its batch was begun on.  At most two batches are in flight.
-  struct Lane {
-    void* h_stage = nullptr; size_t h_stage_bytes = 0; void* h_stage_dev = nullptr; void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
-    int32_t* d_order = nullptr; bool order_valid = false; unsigned long long order_key = 0; std::vector<float> order_poses;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr; bool busy = false; int id = 1;
-    std::vector<unsigned char> inputs_shadow; bool inputs_valid = false;
-  } parked;
-  int lane_id = 0; bool lane_busy = false; hipEvent_t ev_done = nullptr;      // the current lane's id / busy flag / "this batch's last operation has run"
-  // what the lane's device scratch holds as a batch's INPUT block (start poses, index arrays), byte for byte, while nothing else has used the scratch since: a batch
-  // that comes again with the same inputs needs no upload either (ensure_scratch invalidates it: every other user of the scratch comes through there)
-  std::vector<unsigned char> inputs_shadow; bool inputs_valid = false;
+  Lane lanes[2]; int cur = 0;            // the two lanes and which one is current (lane()): see struct Lane
   int inflight = 0;                        // batches begun and not yet waited for
   // the SECOND stream: while a batch is in flight, what the next one needs ahead of its k_align -- its scans' preprocessing (lsm2d_preprocess_scans_refill), its
   // start poses' upload, its placement's estimate -- is queued here, so the chip runs it in the slots the launch in flight leaves free (its tail), and k_align
   // on the first stream waits for an event behind it
-  hipStream_t stream_b = nullptr; hipEvent_t ev_b = nullptr, ev_a_est = nullptr; bool b_dirty = false, a_est_recorded = false, b_recorded = false;
-  hipStream_t stream_c = nullptr; hipEvent_t ev_c = nullptr; bool c_dirty = false;      // lsm2d_preprocess_scans_refill while a batch is in flight: a stream of its own (refill_stream)
-  hipStream_t stream_h = nullptr; hipEvent_t ev_h = nullptr;                            // ... and one for its host-to-device copy (the copy engine's; nothing it waits for)
-  // a batch begun asynchronously launches on ITS LANE's stream: two batches in flight are two streams, and the second one's workgroups fill the slots the first
-  // one's tail leaves free instead of waiting for its last workgroup (lane_stream)
-  hipStream_t k_stream[2] = {nullptr, nullptr}; hipEvent_t ev_main = nullptr;
+  SideStream side_pre;         // (pre_stream; `recorded`: an estimate queued there may still be running)
+  hipEvent_t ev_a_est = nullptr; bool a_est_recorded = false;      // ... and behind the latest estimate queued on the context's own stream: the two share ONE ticket counter (make_placement)
+  SideStream side_refill;      // lsm2d_preprocess_scans_refill while a batch is in flight: a stream of its own (refill_stream)
+  SideStream side_copy;        // ... and one for its host-to-device copy (the copy engine's; nothing it waits for)
+  hipEvent_t ev_main = nullptr;      // orders the lanes' streams (and the pre-kernels' stream) behind what the context's own stream holds (lane_stream)
 };
-static void swap_lanes(lsm2d_context* c) {
-  lsm2d_context::Lane& p = c->parked;
-  std::swap(c->h_stage, p.h_stage); std::swap(c->h_stage_bytes, p.h_stage_bytes); std::swap(c->h_stage_dev, p.h_stage_dev);
-  std::swap(c->d_scratch, p.d_scratch); std::swap(c->d_scratch_bytes, p.d_scratch_bytes);
-  std::swap(c->d_order, p.d_order); std::swap(c->order_valid, p.order_valid); std::swap(c->order_key, p.order_key); c->order_poses.swap(p.order_poses);
-  std::swap(c->ev0, p.ev0); std::swap(c->ev1, p.ev1); std::swap(c->ev_done, p.ev_done); std::swap(c->lane_busy, p.busy); std::swap(c->lane_id, p.id);
-  c->inputs_shadow.swap(p.inputs_shadow); std::swap(c->inputs_valid, p.inputs_valid);
-}
+static inline Lane& lane(lsm2d_context* ctx) { return ctx->lanes[ctx->cur]; }
 // Side streams, created on first use with the highest priority the device has: what they carry is short, and the launch in flight holds every wave slot of the
 // chip -- the slots that come free at its end should go to the next batches' pre-kernels first, not to the 1000 long-lived workgroups of the launch queued behind it.
-static bool make_side_stream(hipStream_t* st, hipEvent_t* ev) {
+static bool make_side_stream(SideStream& s) {
+  if (s.st) return true;
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void) hipGetLastError(); prio_greatest = 0; }
-  if (hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_greatest) != hipSuccess) { (void) hipGetLastError(); *st = nullptr; return false; }
-  if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); (void) hipStreamDestroy(*st); *st = nullptr; *ev = nullptr; return false; }
+  if (hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, prio_greatest) != hipSuccess) { (void) hipGetLastError(); s.st = nullptr; return false; }
+  if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); (void) hipStreamDestroy(s.st); s.st = nullptr; s.ev = nullptr; return false; }
   return true;
 }
 // the stream a batch's PRE-kernels go to (its start poses, its estimate): the second one while another batch is in flight, else the context's own
 static hipStream_t pre_stream(lsm2d_context* ctx) {
   if (ctx->inflight <= 0) return ctx->stream;
-  if (!ctx->stream_b && !make_side_stream(&ctx->stream_b, &ctx->ev_b)) return ctx->stream;
-  ctx->b_dirty = true;
-  return ctx->stream_b;
+  if (!make_side_stream(ctx->side_pre)) return ctx->stream;
+  ctx->side_pre.dirty = true;
+  return ctx->side_pre.st;
 }
 // ... and the stream lsm2d_preprocess_scans_refill goes to while a batch is in flight: a THIRD one.  On the second stream a refill queued a step ahead of its
 // batch would sit between two estimates, and every estimate behind a preprocessing launch that the launch in flight starves of wave slots: the chain
 // preprocessing -> estimate -> k_align ran in the gap between two launches however early the host queued it (rocprofv3 trace).
 static hipStream_t refill_stream(lsm2d_context* ctx) {
   if (ctx->inflight <= 0) return ctx->stream;
-  if (!ctx->stream_c && !make_side_stream(&ctx->stream_c, &ctx->ev_c)) return ctx->stream;
-  return ctx->stream_c;
+  if (!make_side_stream(ctx->side_refill)) return ctx->stream;
+  return ctx->side_refill.st;
 }
 // The refill's host-to-device copy depends on nothing the device does (the batch that read the set's previous contents has been waited for: the caller's side of
 // the contract), but in order on the refill stream it sat BETWEEN two preprocessing launches: 82 us of copy after the previous launch had ended, the next one
@@ -170,8 +171,8 @@ static hipStream_t refill_stream(lsm2d_context* ctx) {
 // fully serial step -- 0.81 against 0.75 ms per step from C++, stream_ab_r05.txt.)
 static hipStream_t refill_copy_stream(lsm2d_context* ctx, hipStream_t refill) {
   if (refill == ctx->stream || ctx->inflight < 2) return refill;
-  if (!ctx->stream_h && !make_side_stream(&ctx->stream_h, &ctx->ev_h)) return refill;
-  return ctx->stream_h;
+  if (!make_side_stream(ctx->side_copy)) return refill;
+  return ctx->side_copy.st;
 }
 // The stream an asynchronously begun batch's OWN operations go to (its memsets, k_align, its results' copies, its events): one per lane.  In order on the
 // context's stream the younger batch's 1000 workgroups waited for the older launch's LAST workgroup while a tenth of the chip's slot-time stood empty in its tail
@@ -179,25 +180,27 @@ static hipStream_t refill_copy_stream(lsm2d_context* ctx, hipStream_t refill) {
 // everything that prepares sets; an event recorded on it at begin() orders the lane's stream (and the pre-kernels' stream) behind what it holds.
 static hipStream_t lane_stream(lsm2d_context* ctx) {
   if (!ctx->lane_streams) return ctx->stream;
-  hipStream_t& st = ctx->k_stream[ctx->lane_id & 1];
+  hipStream_t& st = lane(ctx).k_stream;
   if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void) hipGetLastError(); st = nullptr; return ctx->stream; }
   if (!ctx->ev_main && hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); ctx->ev_main = nullptr; return ctx->stream; }
   return st;
 }
 // what was queued on the refill stream comes before whatever `st` (and the context's own stream) is given next
 static hipError_t join_refill_stream(lsm2d_context* ctx, hipStream_t st) {
-  if (!ctx->c_dirty || !ctx->stream_c) return hipSuccess;
-  hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_c, 0);
-  if (e == hipSuccess && st != ctx->stream) e = hipStreamWaitEvent(st, ctx->ev_c, 0);
-  ctx->c_dirty = false;
+  SideStream& s = ctx->side_refill;
+  if (!s.dirty || !s.st) return hipSuccess;
+  hipError_t e = hipStreamWaitEvent(ctx->stream, s.ev, 0);
+  if (e == hipSuccess && st != ctx->stream) e = hipStreamWaitEvent(st, s.ev, 0);
+  s.dirty = false;
   return e;
 }
 // k_align (first stream) must see what the second stream was given for it
 static hipError_t join_pre_stream(lsm2d_context* ctx, hipStream_t ks) {
-  if (!ctx->b_dirty || !ctx->stream_b) return hipSuccess;
-  hipError_t e = hipEventRecord(ctx->ev_b, ctx->stream_b);
-  if (e == hipSuccess) { ctx->b_recorded = true; e = hipStreamWaitEvent(ks, ctx->ev_b, 0); }
-  ctx->b_dirty = false;
+  SideStream& s = ctx->side_pre;
+  if (!s.dirty || !s.st) return hipSuccess;
+  hipError_t e = hipEventRecord(s.ev, s.st);
+  if (e == hipSuccess) { s.recorded = true; e = hipStreamWaitEvent(ks, s.ev, 0); }
+  s.dirty = false;
   return e;
 }
 
@@ -206,6 +209,17 @@ static hipError_t join_pre_stream(lsm2d_context* ctx, hipStream_t ks) {
 static hipError_t stream_sync(lsm2d_context* ctx) {
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   ++ctx->sync_epoch;
+  return e;
+}
+// Every stream the context created besides its own, in ONE place: the side streams and -- with_lanes -- the lanes' streams
+template <class F> static void for_each_extra_stream(lsm2d_context* ctx, bool with_lanes, F f) {
+  for (SideStream* s : {&ctx->side_pre, &ctx->side_copy, &ctx->side_refill}) if (s->st) f(s->st);
+  if (with_lanes) for (Lane& L : ctx->lanes) if (L.k_stream) f(L.k_stream);
+}
+// ... and the wait for the context's own stream and for them: every one is waited for, the first error is the answer
+static hipError_t sync_streams(lsm2d_context* ctx, bool with_lanes) {
+  hipError_t e = stream_sync(ctx);
+  for_each_extra_stream(ctx, with_lanes, [&e](hipStream_t st) { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; });
   return e;
 }
 
@@ -374,12 +388,11 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   hipError_t e = hipSetDevice(device_id);
   if (e == hipSuccess && hip_stream) { c->stream = (hipStream_t) hip_stream; c->owns_stream = false; }
   else if (e == hipSuccess) { e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking); c->owns_stream = true; }
-  if (e == hipSuccess) e = hipEventCreate(&c->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-  if (e == hipSuccess) e = hipEventCreate(&c->parked.ev0);
-  if (e == hipSuccess) e = hipEventCreate(&c->parked.ev1);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->parked.ev_done, hipEventDisableTiming);
+  for (Lane& L : c->lanes) {
+    if (e == hipSuccess) e = hipEventCreate(&L.ev0);
+    if (e == hipSuccess) e = hipEventCreate(&L.ev1);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming);
+  }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_a_est, hipEventDisableTiming);
   if (e == hipSuccess) e = hipHostMalloc(&c->h_flag, 256, hipHostMallocDefault);
   if (e != hipSuccess) { g_last_error = hipGetErrorString(e); delete c; return LSM2D_DEVICE_ERROR; }
@@ -428,31 +441,22 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
   (void) hipSetDevice(c->device);
   // every stream the context ever launched on comes to rest BEFORE anything is freed (batches may still be in flight on the lanes' streams; a lsm2d_pending
   // that has not been waited for is the caller's to delete -- include/lsm2d.h: wait for every begun batch before lsm2d_destroy)
-  (void) hipStreamSynchronize(c->stream); ++c->sync_epoch;
-  if (c->stream_b) (void) hipStreamSynchronize(c->stream_b);
-  if (c->stream_c) (void) hipStreamSynchronize(c->stream_c);
-  if (c->stream_h) (void) hipStreamSynchronize(c->stream_h);
-  for (hipStream_t st : c->k_stream) if (st) (void) hipStreamSynchronize(st);
+  (void) sync_streams(c, true);
   for (lsm2d_cloudset* cs : c->live_sets) cs->ctx = nullptr;        // still owned by the caller: destroy them any time, use them no more
-  if (c->h_stage) (void) hipHostFree(c->h_stage);
+  for (Lane& L : c->lanes) {
+    if (L.h_stage) (void) hipHostFree(L.h_stage);
+    if (L.d_scratch) (void) hipFree(L.d_scratch);
+    if (L.d_order) (void) hipFree(L.d_order);
+    for (hipEvent_t e : {L.ev0, L.ev1, L.ev_done}) if (e) (void) hipEventDestroy(e);
+  }
   if (c->h_flag) (void) hipHostFree(c->h_flag);
-  if (c->d_scratch) (void) hipFree(c->d_scratch);
   if (c->d_split) (void) hipFree(c->d_split);
   if (c->d_kd_work) (void) hipFree(c->d_kd_work);
   if (c->d_wg_place) (void) hipFree(c->d_wg_place);
-  if (c->d_order) (void) hipFree(c->d_order);
-  if (c->parked.h_stage) (void) hipHostFree(c->parked.h_stage);
-  if (c->parked.d_scratch) (void) hipFree(c->parked.d_scratch);
-  if (c->parked.d_order) (void) hipFree(c->parked.d_order);
-  for (hipEvent_t e : {c->parked.ev0, c->parked.ev1, c->parked.ev_done, c->ev_done, c->ev_b, c->ev_c, c->ev_h, c->ev_main, c->ev_a_est}) if (e) (void) hipEventDestroy(e);
-  if (c->stream_b) (void) hipStreamDestroy(c->stream_b);
-  if (c->stream_c) (void) hipStreamDestroy(c->stream_c);
-  if (c->stream_h) (void) hipStreamDestroy(c->stream_h);
-  for (hipStream_t st : c->k_stream) if (st) (void) hipStreamDestroy(st);
+  for (hipEvent_t e : {c->side_pre.ev, c->side_refill.ev, c->side_copy.ev, c->ev_main, c->ev_a_est}) if (e) (void) hipEventDestroy(e);
+  for_each_extra_stream(c, true, [](hipStream_t st) { (void) hipStreamDestroy(st); });
   if (c->d_xcd) (void) hipFree(c->d_xcd);
   for (auto& bd : c->beam_dirs) if (bd.d_dir) (void) hipFree(bd.d_dir);
-  if (c->ev0) (void) hipEventDestroy(c->ev0);
-  if (c->ev1) (void) hipEventDestroy(c->ev1);
   if (c->owns_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -460,11 +464,7 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
 extern "C" int lsm2d_synchronize(lsm2d_context* ctx) {
   if (!ctx) return LSM2D_BAD_ARGUMENT;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, stream_sync(ctx));
-  if (ctx->stream_b) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_b));      // (the side streams of the streamed pipeline: "everything" includes them)
-  if (ctx->stream_h) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_h));
-  if (ctx->stream_c) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_c));
-  for (hipStream_t st : ctx->k_stream) if (st) HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, sync_streams(ctx, true));      // (the side streams of the streamed pipeline and the lanes' streams: "everything" includes them)
   return LSM2D_SUCCESS;
 }
 
@@ -553,7 +553,7 @@ extern "C" int lsm2d_set_option(lsm2d_context* ctx, const char* key, int64_t val
     ctx->*(o.field) = (int) value;
     if (o.flags & kOptResetsNotes) ctx->wg_place_shape = 0;
     if (o.field == &lsm2d_context::kernel_timing && !value) ctx->have_timing = false;
-    ctx->order_valid = false;      // whatever changed may change what a batch launches: the next call makes its placement afresh
+    lane(ctx).order_valid = false;      // (the CURRENT lane's only, as ever) whatever changed may change what a batch launches: the next call makes its placement afresh
     return LSM2D_SUCCESS;
   }
   return fail(ctx, LSM2D_BAD_ARGUMENT, "unknown option");
@@ -569,15 +569,15 @@ extern "C" int lsm2d_get_option(lsm2d_context* ctx, const char* key, int64_t* ou
 extern "C" int lsm2d_last_kernel_ms(lsm2d_context* ctx, float* out_ms) {
   if (!ctx || !out_ms) return LSM2D_BAD_ARGUMENT;
   if (!ctx->have_timing) return fail(ctx, LSM2D_BAD_ARGUMENT, "no timed launch yet");
-  hipEvent_t e0 = ctx->last_ev0 ? ctx->last_ev0 : ctx->ev0, e1 = ctx->last_ev1 ? ctx->last_ev1 : ctx->ev1;
-  HIPCHK(ctx, hipEventSynchronize(e1));
-  HIPCHK(ctx, hipEventElapsedTime(out_ms, e0, e1));
+  const Lane& L = ctx->lanes[ctx->timed_lane < 0 ? ctx->cur : ctx->timed_lane];
+  HIPCHK(ctx, hipEventSynchronize(L.ev1));
+  HIPCHK(ctx, hipEventElapsedTime(out_ms, L.ev0, L.ev1));
   return LSM2D_SUCCESS;
 }
 
 // a timed launch outside the batch entry points recorded the CURRENT lane's events: they are what lsm2d_last_kernel_ms reads next (round-5 advisor: after an
-// asynchronous begin had swapped lanes the call kept answering with the old batch's events)
-static void note_timed(lsm2d_context* ctx, bool timed) { ctx->have_timing = timed; ctx->last_ev0 = ctx->ev0; ctx->last_ev1 = ctx->ev1; }
+// asynchronous begin had moved on to the other lane the call kept answering with the old batch's events)
+static void note_timed(lsm2d_context* ctx, bool timed) { ctx->have_timing = timed; ctx->timed_lane = ctx->cur; }
 
 static bool valid_cloud_index_fwd(const lsm2d_cloudset* cs, int32_t i);
 // what a caller's buffer is to the runtime (entry points that take bulk input accept all three)
@@ -595,32 +595,30 @@ static PtrKind pointer_kind(const void* p, int* device = nullptr) {
 // anything comes through here and fails loudly instead of writing over them; lsm2d_align_batch_begin says the same before it gets here)
 static const char* const kBothLanesBusy = "two batches are in flight on this context and its staging buffers are theirs: wait for the older one first (lsm2d_align_batch_wait)";
 static int ensure_stage(lsm2d_context* ctx, size_t bytes) {
-  if (ctx->lane_busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  if (bytes <= ctx->h_stage_bytes) return LSM2D_SUCCESS;
-  if (ctx->h_stage) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipHostFree(ctx->h_stage)); ctx->h_stage = nullptr; ctx->h_stage_bytes = 0; }
+  Lane& L = lane(ctx);
+  if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  if (bytes <= L.h_stage_bytes) return LSM2D_SUCCESS;
+  if (L.h_stage) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipHostFree(L.h_stage)); L.h_stage = nullptr; L.h_stage_bytes = 0; }
   size_t cap = bytes + bytes / 2 + 4096;
-  HIPCHK(ctx, hipHostMalloc(&ctx->h_stage, cap, hipHostMallocCoherent | hipHostMallocMapped));
-  HIPCHK(ctx, hipHostGetDevicePointer(&ctx->h_stage_dev, ctx->h_stage, 0));      // looked up once: kernels read / write the buffer directly
-  ctx->h_stage_bytes = cap;
-  return LSM2D_SUCCESS;
-}
-// device-side address of the pinned staging buffer: kernels with small outputs write them there directly (no device-to-host copy)
-static int stage_device_view(lsm2d_context* ctx, char** out) {
-  *out = (char*) ctx->h_stage_dev;
+  HIPCHK(ctx, hipHostMalloc(&L.h_stage, cap, hipHostMallocCoherent | hipHostMallocMapped));
+  // the buffer's device-side address, looked up once: kernels with small outputs write them there directly (no device-to-host copy)
+  HIPCHK(ctx, hipHostGetDevicePointer(&L.h_stage_dev, L.h_stage, 0));
+  L.h_stage_bytes = cap;
   return LSM2D_SUCCESS;
 }
 
 static int ensure_scratch(lsm2d_context* ctx, size_t bytes) {
-  if (ctx->lane_busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  ctx->inputs_valid = false;      // (whoever asks is about to write the scratch; lsm2d_align_batch looks at the flag before it asks)
-  if (bytes <= ctx->d_scratch_bytes) return LSM2D_SUCCESS;
+  Lane& L = lane(ctx);
+  if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  L.inputs_valid = false;      // (whoever asks is about to write the scratch; lsm2d_align_batch looks at the flag before it asks)
+  if (bytes <= L.d_scratch_bytes) return LSM2D_SUCCESS;
   // (a NEW allocation holds nobody's input block: the shadow goes with the old one -- round-5 advisor: a batch run again with more outputs, e.g. statistics,
   // grew the scratch, compared equal against the shadow and skipped the upload into memory that had never seen it)
-  ctx->inputs_shadow.clear();
-  if (ctx->d_scratch) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(ctx->d_scratch)); ctx->d_scratch = nullptr; ctx->d_scratch_bytes = 0; }
+  L.inputs_shadow.clear();
+  if (L.d_scratch) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(L.d_scratch)); L.d_scratch = nullptr; L.d_scratch_bytes = 0; }
   size_t cap = bytes + bytes / 2 + 4096;
-  HIPCHK(ctx, hipMalloc(&ctx->d_scratch, cap));
-  ctx->d_scratch_bytes = cap;
+  HIPCHK(ctx, hipMalloc(&L.d_scratch, cap));
+  L.d_scratch_bytes = cap;
   return LSM2D_SUCCESS;
 }
 

@@ -28,8 +28,7 @@ extern "C" int32_t lsm2d_stats_capacity(const lsm2d_aligner_params* ap) {
 // What a batch that has been LAUNCHED keeps until its results are asked for (lsm2d_align_batch_begin / _wait; the synchronous calls go through the same two halves)
 struct lsm2d_pending {
   lsm2d_context* ctx = nullptr;
-  int lane_id = 0; hipEvent_t ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  char* hs = nullptr;                       // the lane's pinned staging buffer: where the results are (or are copied to)
+  Lane* lane = nullptr;                     // the lane the batch was launched on: its pinned staging buffer is where the results are (or are copied to), its ev_done what a wait waits for
   size_t o_pose = 0, o_H = 0, o_status = 0, o_its = 0, o_stats = 0, o_last_pose = 0, o_clock = 0;
   int n = 0, stats_stride = 0, n_clock = 0, clock_stride = 0;
   bool zero_copy = false, want_stats = false, want_last_pose = false, stamps = false, timed = false, async = false;
@@ -100,6 +99,7 @@ static bool pack_two_for(const lsm2d_context* ctx, int n, size_t lds) {
 struct AlignBatch {
   // ---- the call
   lsm2d_context* ctx; const lsm2d_aligner_params* ap; const lsm2d_batch* b;
+  Lane* L;      // the lane the call works on: the context's current one when it began (hand_over moves the context on to the other lane, not this)
   float* out_pose; float* out_H; int32_t* out_status; int32_t* out_its; lsm2d_iteration_stats* out_stats; float* out_last_pose; int32_t* out_work; lsm2d_pending* pend;
   bool async; hipStream_t pre, ks;      // begun asynchronously; the stream of what goes AHEAD of k_align (start poses, estimate); the stream of the batch's own operations
   int n, ns, stats_stride, it_cap;
@@ -175,10 +175,10 @@ int AlignBatch::validate_and_lay_out_scratch() {
   o_order = take(sizeof(int32_t) * (size_t) n), o_resume = take(sizeof(ResumeDev) * (size_t) n);
 #endif
   total_bytes = off;
-  had_inputs = ctx->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
+  had_inputs = L->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
   int rc = ensure_scratch(ctx, total_bytes); if (rc) return rc;
   rc = ensure_stage(ctx, total_bytes); if (rc) return rc;
-  hs = (char*) ctx->h_stage; ds = (char*) ctx->d_scratch;
+  hs = (char*) L->h_stage; ds = (char*) L->d_scratch;
   return LSM2D_SUCCESS;
 }
 
@@ -211,7 +211,7 @@ int AlignBatch::choose_path() {
   // against 1.467 with the three small transfers; tools/zero_copy_ab.py.)
   // ("zero_copy_max" bounds every batch, so the A/B knob works below 256 too; batches that carry index arrays stay on the transfers above 256)
   zero_copy = !out_work && !use_split && n <= ctx->zero_copy_max && (n <= 256 || (!b->fixed_index && !b->moving_index));
-  if (zero_copy) ds = (char*) ctx->h_stage_dev;
+  if (zero_copy) ds = (char*) L->h_stage_dev;
   return LSM2D_SUCCESS;
 }
 
@@ -460,13 +460,13 @@ int AlignBatch::stage_inputs() {
   // Round 5: a batch that comes again with the SAME input block (start poses, index arrays; no priors) while nothing else has touched the lane's scratch needs no
   // upload: the blit and the wait behind it are 8 us of a 0.77 ms step (kernel trace: copy 2.4 us + 5.6 us until k_align starts).  Compared byte for byte against a
   // host-side shadow of what was uploaded last -- up to 64 KB; a sweep's index arrays beyond that are uploaded as before.
-  same_inputs = !zero_copy && !out_work && !b->prior && had_inputs && in_bytes <= (64u << 10) && ctx->inputs_shadow.size() == in_bytes &&
-                           !memcmp(ctx->inputs_shadow.data(), hs, in_bytes);
+  same_inputs = !zero_copy && !out_work && !b->prior && had_inputs && in_bytes <= (64u << 10) && L->inputs_shadow.size() == in_bytes &&
+                           !memcmp(L->inputs_shadow.data(), hs, in_bytes);
   if (!zero_copy && !same_inputs) {
     HIPCHK(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, pre));
-    if (!out_work && !b->prior && in_bytes <= (64u << 10)) ctx->inputs_shadow.assign((const unsigned char*) hs, (const unsigned char*) hs + in_bytes); else ctx->inputs_shadow.clear();
+    if (!out_work && !b->prior && in_bytes <= (64u << 10)) L->inputs_shadow.assign((const unsigned char*) hs, (const unsigned char*) hs + in_bytes); else L->inputs_shadow.clear();
   }
-  ctx->inputs_valid = !zero_copy && !ctx->inputs_shadow.empty();
+  L->inputs_valid = !zero_copy && !L->inputs_shadow.empty();
   A.init_pose = (const float*) (ds + o_pose_in);
   if (xcd_on && !use_split && !use_pair && !zero_copy) {
     const size_t xb = sizeof(uint32_t) * 16 * (size_t) A.xcd_stride;
@@ -482,14 +482,14 @@ int AlignBatch::stage_inputs() {
   // staging buffer: the device-to-host copy behind the launch -- a hand-over to the copy engine, 9 us of gap + 6 us of copy on the timeline of a
   // 1000-alignment step -- is gone, the stream wait ends with the kernel.  The statistics (28 bytes per iteration and alignment) stay on the device and are copied.
   host_results = !zero_copy && !use_split && ctx->results_to_host && n > 0;
-  char* const ro = host_results ? (char*) ctx->h_stage_dev : ds;
+  char* const ro = host_results ? (char*) L->h_stage_dev : ds;
   A.out_pose = (float*) (ro + o_pose); A.out_H = (float*) (ro + o_H); A.out_status = (int32_t*) (ro + o_status); A.out_its = (int32_t*) (ro + o_its);
   A.out_stats = out_stats ? (StatsDev*) (ds + o_stats) : nullptr;
   A.out_last_pose = out_last_pose ? (float*) (ro + o_last_pose) : nullptr;
 
   ctx->last_clock_khz = 0; ctx->last_wg_lifetime_ns = 0;
   stamps = ctx->kernel_timing && !use_split && !use_pair;
-  if (stamps) { A.clock_out = (unsigned long long*) ((host_results ? (char*) ctx->h_stage_dev : ds) + o_clock); A.clock_stride = clock_stride; }
+  if (stamps) { A.clock_out = (unsigned long long*) ((host_results ? (char*) L->h_stage_dev : ds) + o_clock); A.clock_stride = clock_stride; }
   A.host_polls = zero_copy;
   if (zero_copy) {
     memset(hs + o_pose, 0, out_bytes);
@@ -515,7 +515,7 @@ int AlignBatch::estimate_only() {      // lsm2d_estimate_work: the chunks of the
   int bs = -1;
   for (int s = 0; s < ns && bs < 0; ++s) if (A.s[s].finder == LSM2D_FINDER_PROJECTIVE && A.s[s].moving.lane_xy && A.s[s].moving.lane_bounds && A.cull) bs = s;
   if (bs < 0) { for (int i = 0; i < n; ++i) out_work[i] = 1; return LSM2D_SUCCESS; }
-  int32_t* d_work = (int32_t*) ((char*) ctx->d_scratch + o_work);
+  int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work);
   hipLaunchKernelGGL(k_cull_estimate, dim3((unsigned) n), dim3(kAlignBlock), sizeof(u64) * (size_t) A.s[bs].proj.cols, ctx->stream, A, bs, d_work, (int32_t*) nullptr, (const int32_t*) nullptr, ctx->n_cu, (unsigned int*) nullptr);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(hs + o_work, d_work, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, ctx->stream));
@@ -535,14 +535,14 @@ int AlignBatch::make_placement() {
   const bool two_stage = !use_split && !use_pair && !zero_copy && A.cull && ctx->balance && ctx->two_stage && n > 256 && n <= 1024 && proj_culled_for_all &&
                          has_proj && !has_nn && !has_dist && !has_kd && ap->max_iterations >= 4;
   if (two_stage) {
-    int32_t* d_work = (int32_t*) ((char*) ctx->d_scratch + o_work); int32_t* d_order = (int32_t*) ((char*) ctx->d_scratch + o_order);
+    int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work); int32_t* d_order = (int32_t*) ((char*) L->d_scratch + o_order);
     const unsigned long long shape = ((unsigned long long) (unsigned) n << 32) ^ ((unsigned long long) lds << 8) ^ 6ull;
     if (!ctx->d_wg_place) {
       HIPCHK(ctx, hipMalloc(&ctx->d_wg_place, sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
       HIPCHK(ctx, hipMemsetAsync(ctx->d_wg_place, 0, sizeof(int32_t) * 1025, ctx->stream));
     }
     const bool notes = ctx->balance_notes && ctx->wg_place_shape == shape;
-    A.stage = 1; A.stage_split = 1; A.resume = (ResumeDev*) ((char*) ctx->d_scratch + o_resume); A.stage_work = d_work;
+    A.stage = 1; A.stage_split = 1; A.resume = (ResumeDev*) ((char*) L->d_scratch + o_resume); A.stage_work = d_work;
     hipLaunchKernelGGL(k_first_iteration, dim3((unsigned) n), dim3(kAlignBlock), lds, ctx->stream, A);
     hipLaunchKernelGGL(k_balance_only, dim3(1), dim3(kAlignBlock), sizeof(BalanceLds), ctx->stream, (const int32_t*) d_work, n, ctx->n_cu, d_order,
                        notes ? (const int32_t*) ctx->d_wg_place : (const int32_t*) nullptr);
@@ -584,10 +584,10 @@ int AlignBatch::make_placement() {
     std::vector<int32_t> ord((size_t) n, -1); const int per = (n + K - 1) / K; std::vector<int32_t> spill;
     for (int p = 0; p < n; ++p) { const int id = p / per + K * (p % per); if (id < n) ord[id] = by_cluster[p]; else spill.push_back(by_cluster[p]); }
     for (int id = 0, q = 0; id < n; ++id) if (ord[id] < 0) ord[id] = spill[q++];
-    if (!ctx->d_order) { HIPCHK(ctx, hipMalloc(&ctx->d_order, sizeof(int32_t) * kOrderInts)); }
-    HIPCHK(ctx, hipMemcpy(ctx->d_order, ord.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));      // (synchronous: an experiment's upload)
-    ctx->order_valid = false;
-    A.order = ctx->d_order;
+    if (!L->d_order) { HIPCHK(ctx, hipMalloc(&L->d_order, sizeof(int32_t) * kOrderInts)); }
+    HIPCHK(ctx, hipMemcpy(L->d_order, ord.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));      // (synchronous: an experiment's upload)
+    L->order_valid = false;
+    A.order = L->d_order;
   }
   else
 #endif
@@ -595,7 +595,7 @@ int AlignBatch::make_placement() {
     int bs = -1;
     for (int s = 0; s < ns && bs < 0; ++s) if (A.s[s].finder == LSM2D_FINDER_PROJECTIVE && A.s[s].moving.lane_xy && A.s[s].moving.lane_bounds) bs = s;
     if (bs >= 0) {
-      int32_t* d_work = (int32_t*) ((char*) ctx->d_scratch + o_work);
+      int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work);
       // the workgroups of the previous launch of the same shape noted the CU they ran on (AlignArgs::wg_place): the placement groups by those notes
       // (round 6) packed: one dispatch round of 4 n_cu workgroups, the lightest alignments two to a workgroup (pack_two_for; the pairs are made by balance_order)
       const bool packed = proj_culled_for_all && !(kExperiments && ctx->two_stage) && pack_two_for(ctx, n, lds);
@@ -604,7 +604,7 @@ int AlignBatch::make_placement() {
         HIPCHK(ctx, hipMalloc(&ctx->d_wg_place, sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
         HIPCHK(ctx, hipMemsetAsync(ctx->d_wg_place, 0, sizeof(int32_t) * 1025, pre));      // (on the stream the estimate that reads the ticket is queued on)
       }
-      if (!ctx->d_order) { HIPCHK(ctx, hipMalloc(&ctx->d_order, sizeof(int32_t) * kOrderInts)); ctx->order_valid = false; }
+      if (!L->d_order) { HIPCHK(ctx, hipMalloc(&L->d_order, sizeof(int32_t) * kOrderInts)); L->order_valid = false; }
       const bool notes = ctx->balance_notes && ctx->wg_place_shape == shape;
       // Round 5: the order lives in a buffer of its own and is KEPT.  A caller that runs the same batch again -- the same sets (uid and version), index arrays,
       // slice parameters, launch shape and START POSES: a candidate sweep re-scored, bench.py's resident step -- gets the placement made for it the first time
@@ -618,36 +618,36 @@ int AlignBatch::make_placement() {
         if (b->fixed_index) mix(b->fixed_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
         if (b->moving_index) mix(b->moving_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
       }
-      const bool reuse = ctx->estimate_reuse && notes && ctx->order_valid && ctx->order_key == key && ctx->order_poses.size() == 3 * (size_t) n &&
-                         !memcmp(ctx->order_poses.data(), b->init_pose, sizeof(float) * 3 * (size_t) n);
+      const bool reuse = ctx->estimate_reuse && notes && L->order_valid && L->order_key == key && L->order_poses.size() == 3 * (size_t) n &&
+                         !memcmp(L->order_poses.data(), b->init_pose, sizeof(float) * 3 * (size_t) n);
       // A batch begun while another one is in flight starts on the slots that one's tail leaves free -- wherever they are: the launch balances itself as a batch
       // of many dispatch rounds does, and what is left of the placement's gain (2 % with a kept order) is less than the estimate's own chip time when it has to be made
       // afresh (streamed pipeline 0.685 against 0.696 ms per step): no estimate then, workgroup b = alignment b.  A kept order is still used -- and a batch this
       // lane has seen before (same sets, versions, parameters: a caller that runs it again and again) gets its estimate once, to be kept from then on.
       const bool joins_a_batch_in_flight = ks != ctx->stream && ctx->inflight >= 1 && ctx->lane_streams;
-      if (!reuse && joins_a_batch_in_flight && !(ctx->estimate_reuse && ctx->order_key == key)) { ctx->order_valid = false; ctx->order_key = key; }
+      if (!reuse && joins_a_batch_in_flight && !(ctx->estimate_reuse && L->order_key == key)) { L->order_valid = false; L->order_key = key; }
       else {
       if (!reuse) {
         size_t est_lds = sizeof(u64) * (size_t) A.s[bs].proj.cols; if (est_lds < sizeof(BalanceLds)) est_lds = sizeof(BalanceLds);
         // (estimates share ONE ticket counter: one queued on the second stream waits for the latest one queued on the first)
         if (pre != ctx->stream && ctx->a_est_recorded) HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->ev_a_est, 0));
-        if (pre == ctx->stream && ctx->b_recorded) HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->ev_b, 0));      // (... and the other way round: a synchronous call while a begun batch's estimate may still be running)
-        hipLaunchKernelGGL(k_cull_estimate, dim3((unsigned) n), dim3(kAlignBlock), est_lds, pre, A, bs, d_work, ctx->d_order,
+        if (pre == ctx->stream && ctx->side_pre.recorded) HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->side_pre.ev, 0));      // (... and the other way round: a synchronous call while a begun batch's estimate may still be running)
+        hipLaunchKernelGGL(k_cull_estimate, dim3((unsigned) n), dim3(kAlignBlock), est_lds, pre, A, bs, d_work, L->d_order,
                            notes ? (const int32_t*) ctx->d_wg_place : (const int32_t*) nullptr, ctx->n_cu, (unsigned int*) (ctx->d_wg_place + 1024),
-                           packed ? ctx->d_order + kPackOrder2At : (int32_t*) nullptr);
+                           packed ? L->d_order + kPackOrder2At : (int32_t*) nullptr);
         const hipError_t le = hipGetLastError();
         if (le == hipSuccess && pre == ctx->stream) { HIPCHK(ctx, hipEventRecord(ctx->ev_a_est, ctx->stream)); ctx->a_est_recorded = true; }
         if (le != hipSuccess) {      // (round-4 advisor) a launch that failed may have left the ticket counter mid-count: the next call must not start mis-counted
-          (void) hipMemsetAsync(ctx->d_wg_place + 1024, 0, sizeof(int32_t), ctx->stream); ctx->order_valid = false;
+          (void) hipMemsetAsync(ctx->d_wg_place + 1024, 0, sizeof(int32_t), ctx->stream); L->order_valid = false;
           HIPCHK(ctx, le);
         }
         ctx->last_cull_estimate = 1;
         // (kept only once it was made WITH notes: the first call of a shape orders by the round-3 assumption, the second by what the first really did)
-        ctx->order_valid = notes; ctx->order_key = key;
-        if (notes) ctx->order_poses.assign(b->init_pose, b->init_pose + 3 * (size_t) n);
+        L->order_valid = notes; L->order_key = key;
+        if (notes) L->order_poses.assign(b->init_pose, b->init_pose + 3 * (size_t) n);
       }
-      A.order = ctx->d_order;
-      if (packed) A.order2 = ctx->d_order + kPackOrder2At;      // (kept with the order: a batch that comes again with the same start poses finds both)
+      A.order = L->d_order;
+      if (packed) A.order2 = L->d_order + kPackOrder2At;      // (kept with the order: a batch that comes again with the same start poses finds both)
       if (ctx->balance_notes && ((packed && n < 2048) || n <= 1024)) { A.wg_place = ctx->d_wg_place; ctx->wg_place_shape = shape; }      // (one note per workgroup of a launch of at most 1024)
       }
     }
@@ -661,7 +661,7 @@ int AlignBatch::launch() {
     HIPCHK(ctx, hipStreamWaitEvent(ks, ctx->ev_main, 0));
   }
   HIPCHK(ctx, join_pre_stream(ctx, ks));      // whatever the second stream holds for this batch (its start poses, its estimate) comes first
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ks));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L->ev0, ks));
   if (use_split) {
     // workspace: global canvases + running pose / flags, grown on demand and kept by the context
     const size_t can_bytes = sizeof(u64) * 2 * (size_t) fcan_total * (size_t) n;
@@ -733,7 +733,7 @@ int AlignBatch::launch() {
   HIPCHK(ctx, hipGetLastError());
   for (int s = 0; s < ns; ++s)                  // sets the kernel's prologue unpacks (SliceDev::unpack_src)
     if (A.s[s].unpack_src) { b->fixed[s]->unpack_pending = false; b->fixed[s]->staged_epoch = ctx->sync_epoch; }
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ks));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L->ev1, ks));
   ctx->have_timing = ctx->kernel_timing;
   if (host_results) { if (out_stats) HIPCHK(ctx, hipMemcpyAsync(hs + o_stats, ds + o_stats, sizeof(StatsDev) * (size_t) n * (size_t) stats_stride, hipMemcpyDeviceToHost, ks)); }
   else if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(hs + o_pose, ds + o_pose, out_bytes, hipMemcpyDeviceToHost, ks));
@@ -743,15 +743,15 @@ int AlignBatch::launch() {
 int AlignBatch::hand_over() {
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
-  P.ctx = ctx; P.lane_id = ctx->lane_id; P.ev_done = ctx->ev_done; P.ev0 = ctx->ev0; P.ev1 = ctx->ev1; P.hs = hs;
+  P.ctx = ctx; P.lane = L;
   P.o_pose = o_pose; P.o_H = o_H; P.o_status = o_status; P.o_its = o_its; P.o_stats = o_stats; P.o_last_pose = o_last_pose; P.o_clock = o_clock;
   P.n = n; P.stats_stride = stats_stride; P.n_clock = n_clock; P.clock_stride = clock_stride;
   P.zero_copy = zero_copy; P.want_stats = out_stats != nullptr; P.want_last_pose = out_last_pose != nullptr; P.stamps = stamps; P.timed = ctx->kernel_timing != 0; P.async = async;
   P.xcd_sync = A.xcd_sync; P.xcd_stride = A.xcd_stride; P.xcd_window = A.xcd_window; P.xcd_positions = A.xcd_positions;
   if (async) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_done, ks));      // (zero-copy batches too: what their wait falls back to when the statuses do not arrive within the spin budget)
-    ctx->lane_busy = true; ++ctx->inflight;
-    swap_lanes(ctx);      // whatever is called next works on the other lane
+    HIPCHK(ctx, hipEventRecord(L->ev_done, ks));      // (zero-copy batches too: what their wait falls back to when the statuses do not arrive within the spin budget)
+    L->busy = true; ++ctx->inflight;
+    ctx->cur ^= 1;      // whatever is called next works on the other lane (L stays this batch's)
     return LSM2D_SUCCESS;
   }
   return align_batch_finish(P, out_pose, out_H, out_status, out_its, out_stats, out_last_pose);
@@ -761,9 +761,9 @@ static int align_batch_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, 
                             float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats, float* out_last_pose,
                             int32_t* out_work = nullptr, lsm2d_pending* pend = nullptr) {
   if (!ctx || !ap || !b || ((!out_pose || !out_status) && !out_work)) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: null argument");
-  if (ctx->lane_busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
+  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
   AlignBatch B;
-  B.ctx = ctx; B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = out_status; B.out_its = out_its; B.out_stats = out_stats;
+  B.ctx = ctx; B.L = &lane(ctx); B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = out_status; B.out_its = out_its; B.out_stats = out_stats;
   B.out_last_pose = out_last_pose; B.out_work = out_work; B.pend = pend;
   int rc = B.validate_and_lay_out_scratch();
   if (rc == kEmptyBatch) return LSM2D_SUCCESS;
@@ -780,8 +780,8 @@ static int align_batch_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, 
 
 // the second half: wait for the batch, check that every alignment reported, hand the results over
 static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats, float* out_last_pose) {
-  lsm2d_context* ctx = P.ctx;
-  char* hs = P.hs; const int n = P.n;
+  lsm2d_context* ctx = P.ctx; Lane& L = *P.lane;
+  char* hs = (char*) L.h_stage; const int n = P.n;
   const size_t o_pose = P.o_pose, o_H = P.o_H, o_status = P.o_status, o_its = P.o_its, o_stats = P.o_stats, o_last_pose = P.o_last_pose, o_clock = P.o_clock;
   const int stats_stride = P.stats_stride, n_clock = P.n_clock, clock_stride = P.clock_stride;
   const bool zero_copy = P.zero_copy, stamps = P.stamps;
@@ -789,19 +789,19 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
     // (an event of the batch's own, not a wait for the stream: the NEXT batch may be queued behind it already.  The stream's epoch does not move: work queued
     // after this batch has not necessarily run)
     hipError_t we = hipSuccess;
-    if (zero_copy) { const unsigned long long epoch = ctx->sync_epoch; we = wait_for_statuses(ctx, (const int32_t*) (hs + o_status), n, P.ev_done); ctx->sync_epoch = epoch; }
-    else we = hipEventSynchronize(P.ev_done);
-    if (ctx->lane_id == P.lane_id) ctx->lane_busy = false; else if (ctx->parked.id == P.lane_id) ctx->parked.busy = false;
+    if (zero_copy) { const unsigned long long epoch = ctx->sync_epoch; we = wait_for_statuses(ctx, (const int32_t*) (hs + o_status), n, L.ev_done); ctx->sync_epoch = epoch; }
+    else we = hipEventSynchronize(L.ev_done);
+    L.busy = false;
     if (ctx->inflight > 0) --ctx->inflight;
     HIPCHK(ctx, we);
   }
   else if (zero_copy) HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) (hs + o_status), n));
   else HIPCHK(ctx, stream_sync(ctx));
-  ctx->last_ev0 = P.ev0; ctx->last_ev1 = P.ev1; ctx->have_timing = P.timed;
+  ctx->timed_lane = (int) (&L - ctx->lanes); ctx->have_timing = P.timed;
   {
     static_assert(kStatusNotWritten == -1, "the memsets above write 0xFF bytes");
     const int32_t* st = (const int32_t*) (hs + o_status);
-    for (int i = 0; i < n; ++i) if (st[i] == kStatusNotWritten) { ctx->order_valid = false; ctx->parked.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
+    for (int i = 0; i < n; ++i) if (st[i] == kStatusNotWritten) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
   }
   memcpy(out_pose, hs + o_pose, sizeof(float) * 3 * (size_t) n);
   if (out_H) memcpy(out_H, hs + o_H, sizeof(float) * 9 * (size_t) n);

@@ -114,10 +114,7 @@ static int resolve_count(const lsm2d_cloudset* cs) {
   { const int rc0 = flush_pending(cs); if (rc0) return rc0; }      // a preprocessing launch still pending: its result is the count asked for
   lsm2d_context* ctx = cs->ctx;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, stream_sync(ctx));
-  if (ctx->stream_b) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_b));
-  if (ctx->stream_h) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_h));
-  if (ctx->stream_c) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_c));      // (a refill queued on the refill stream)
+  HIPCHK(ctx, sync_streams(ctx, false));      // (the side streams: a refill queued on the refill stream; not the lanes' streams: a batch in flight changes no set's size)
   if (cs->n_clouds > 1) {      // a refilled set of scans (lsm2d_preprocess_scans_refill): every cloud's size
     HIPCHK(ctx, hipMemcpy(cs->h_count.data(), cs->d_count, sizeof(int32_t) * (size_t) cs->n_clouds, hipMemcpyDeviceToHost));
     cs->total = 0; for (int c = 0; c < cs->n_clouds; ++c) cs->total += cs->h_count[c];
@@ -334,12 +331,13 @@ extern "C" int lsm2d_cloudset_download(const lsm2d_cloudset* cs, int32_t ci, flo
   const size_t bytes = sizeof(float4) * (size_t) n;
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
+  Lane& L = lane(ctx);
   const int base = cs->h_start[ci];
   hipLaunchKernelGGL(k_pack_aos, dim3((unsigned) ((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     (const float2*) (cs->d_xy + base), (const float2*) (cs->d_nrm + base), (int) n, (float4*) ctx->d_scratch);
+                     (const float2*) (cs->d_xy + base), (const float2*) (cs->d_nrm + base), (int) n, (float4*) L.d_scratch);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(L.h_stage, L.d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, stream_sync(ctx));
-  memcpy(out, ctx->h_stage, bytes);
+  memcpy(out, L.h_stage, bytes);
   return LSM2D_SUCCESS;
 }

@@ -31,12 +31,12 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
     const size_t o_match = (bytes + 255) & ~(size_t) 255, o_cnt = o_match + ((nm * 4 + 255) & ~(size_t) 255);
     rc = ensure_scratch(ctx, multi ? o_cnt + 4 * (size_t) n_blocks : bytes); if (rc) return rc;
     rc = ensure_stage(ctx, bytes); if (rc) return rc;
+    Lane& L = lane(ctx);
     const bool direct = bytes <= (1u << 16);             // up to 8k pairs: written straight to pinned host memory
-    char* dv = (char*) ctx->d_scratch;
-    if (direct) { rc = stage_device_view(ctx, &dv); if (rc) return rc; }
+    char* dv = (char*) (direct ? L.h_stage_dev : L.d_scratch);
     N.out_count = (int32_t*) dv; N.out_pairs = (int32_t*) (dv + 16);
-    N.match = (int32_t*) ((char*) ctx->d_scratch + o_match); N.block_count = (int32_t*) ((char*) ctx->d_scratch + o_cnt);
-    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    N.match = (int32_t*) ((char*) L.d_scratch + o_match); N.block_count = (int32_t*) ((char*) L.d_scratch + o_cnt);
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
     if (multi) {
       hipLaunchKernelGGL(k_find_nn_multi<0>, dim3((unsigned) n_blocks), dim3(kFindBlock), 0, ctx->stream, N);
       hipLaunchKernelGGL(k_find_nn_multi<1>, dim3((unsigned) n_blocks), dim3(kFindBlock), 0, ctx->stream, N);
@@ -44,14 +44,14 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
       hipLaunchKernelGGL(k_find_nn, dim3(1), dim3(kFindBlock), 0, ctx->stream, N);
     }
     HIPCHK(ctx, hipGetLastError());
-    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
     note_timed(ctx, ctx->kernel_timing);
-    if (!direct) HIPCHK(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (!direct) HIPCHK(ctx, hipMemcpyAsync(L.h_stage, L.d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, stream_sync(ctx));
-    const int32_t n = *(const int32_t*) ctx->h_stage;
+    const int32_t n = *(const int32_t*) L.h_stage;
     *out_n = n;
     if (n > capacity) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "find_correspondences: out_pairs too small");
-    memcpy(out_pairs, (char*) ctx->h_stage + 16, sizeof(lsm2d_correspondence) * (size_t) n);
+    memcpy(out_pairs, (char*) L.h_stage + 16, sizeof(lsm2d_correspondence) * (size_t) n);
     return LSM2D_SUCCESS;
   }
   if (sp->finder != LSM2D_FINDER_PROJECTIVE) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences: finder not supported yet");
@@ -66,31 +66,32 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
   const size_t o_can = (bytes + 255) & ~(size_t) 255;
   int rc = ensure_scratch(ctx, o_can + 2 * cols * sizeof(u64)); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
+  Lane& L = lane(ctx);
   A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr); A.fc = fi; A.mc = mi;
   A.point_distance = sp->point_distance; A.normal_cos = sp->normal_cos; A.T = make_iso(pose); A.inl_tau = inl_tau;
-  char* dv = nullptr; rc = stage_device_view(ctx, &dv); if (rc) return rc;       // <= one pair per column: written straight to pinned host memory
+  char* dv = (char*) L.h_stage_dev;       // <= one pair per column: written straight to pinned host memory
   A.out_count = (int32_t*) dv; A.out_pairs = (int32_t*) (dv + 16);
   A.fcan_global = nullptr; A.mcan_global = nullptr;
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
   if (big_f) {
-    u64* g = (u64*) ((char*) ctx->d_scratch + o_can); const Iso ident = {1.0f, 0.0f, 0.0f, 0.0f};
+    u64* g = (u64*) ((char*) L.d_scratch + o_can); const Iso ident = {1.0f, 0.0f, 0.0f, 0.0f};
     rc = project_split(ctx, fixed->d_xy + fixed->h_start[fi], fixed->h_count[fi], ident, A.proj, g); if (rc) return rc;
     A.fcan_global = g;
   }
   if (big_m) {
-    u64* g = (u64*) ((char*) ctx->d_scratch + o_can) + cols;
+    u64* g = (u64*) ((char*) L.d_scratch + o_can) + cols;
     rc = project_split(ctx, moving->d_xy + moving->h_start[mi], moving->h_count[mi], A.T, A.proj, g); if (rc) return rc;
     A.mcan_global = g;
   }
   hipLaunchKernelGGL(k_find_projective, dim3(1), dim3(kFindBlock), lds, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
   HIPCHK(ctx, stream_sync(ctx));
-  const int32_t n = *(const int32_t*) ctx->h_stage;
+  const int32_t n = *(const int32_t*) L.h_stage;
   *out_n = n;
   if (n > capacity) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "find_correspondences: out_pairs too small");
-  memcpy(out_pairs, (char*) ctx->h_stage + 16, sizeof(lsm2d_correspondence) * (size_t) n);
+  memcpy(out_pairs, (char*) L.h_stage + 16, sizeof(lsm2d_correspondence) * (size_t) n);
   return LSM2D_SUCCESS;
 }
 
@@ -121,30 +122,30 @@ extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp,
   const size_t bytes = dig_off + sizeof(unsigned long long);
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
-  if (n_pairs) memcpy(ctx->h_stage, pairs, pair_bytes);
+  Lane& L = lane(ctx);
+  if (n_pairs) memcpy(L.h_stage, pairs, pair_bytes);
   // up to 8k pairs (a canvas worth): the kernels read the pairs from, and write the sums to, the pinned staging buffer directly
   const bool direct = n_pairs <= 8192;
-  char* dv = (char*) ctx->d_scratch;
-  if (direct) { rc = stage_device_view(ctx, &dv); if (rc) return rc; }
-  else if (n_pairs) HIPCHK(ctx, hipMemcpyAsync(ctx->d_scratch, ctx->h_stage, pair_bytes, hipMemcpyHostToDevice, ctx->stream));
+  char* dv = (char*) (direct ? L.h_stage_dev : L.d_scratch);
+  if (!direct && n_pairs) HIPCHK(ctx, hipMemcpyAsync(L.d_scratch, L.h_stage, pair_bytes, hipMemcpyHostToDevice, ctx->stream));
   LinArgs A;
   A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr); A.fc = fi; A.mc = mi;
   A.pairs = (const int32_t*) dv; A.n_pairs = n_pairs; A.T = make_iso(pose);
   A.cauchy = sp->robustifier == LSM2D_ROBUST_CAUCHY; A.tau = sp->chi_threshold;
-  A.partial = (float*) ((char*) ctx->d_scratch + part_off); A.out = (float*) (dv + out_off);
+  A.partial = (float*) ((char*) L.d_scratch + part_off); A.out = (float*) (dv + out_off);
   A.dig = (unsigned long long*) (dv + dig_off);
-  if (direct) *(unsigned long long*) ((char*) ctx->h_stage + dig_off) = 0ull;
+  if (direct) *(unsigned long long*) ((char*) L.h_stage + dig_off) = 0ull;
   else HIPCHK(ctx, hipMemsetAsync(A.dig, 0, sizeof(unsigned long long), ctx->stream));
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
   if (ctx->sum_order) hipLaunchKernelGGL(k_linearize_seq, dim3(1), dim3(kAlignBlock), 0, ctx->stream, A);      // pair after pair, the order of the vector
   else {
     hipLaunchKernelGGL(k_linearize_partial, dim3(blocks), dim3(256), 0, ctx->stream, A);
     hipLaunchKernelGGL(k_linearize_final, dim3(1), dim3(64), 0, ctx->stream, (const float*) A.partial, blocks, A.out);
   }
   HIPCHK(ctx, hipGetLastError());
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
-  float* h = (float*) ((char*) ctx->h_stage + out_off);
+  float* h = (float*) ((char*) L.h_stage + out_off);
   if (!direct) HIPCHK(ctx, hipMemcpyAsync(h, A.out, sizeof(float) * kAccumWords + sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, stream_sync(ctx));
   out_H[0] = h[0]; out_H[1] = h[1]; out_H[2] = h[2]; out_H[3] = h[1]; out_H[4] = h[3]; out_H[5] = h[4]; out_H[6] = h[2]; out_H[7] = h[4]; out_H[8] = h[5];
@@ -152,7 +153,7 @@ extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp,
   if (st) {
     int32_t iv[3]; memcpy(iv, h + 11, sizeof iv);
     st->n_inliers = iv[0]; st->n_outliers = iv[1]; st->n_correspondences = iv[2]; st->chi_inliers = h[9]; st->chi_outliers = h[10];
-    unsigned long long dg; memcpy(&dg, (char*) ctx->h_stage + dig_off, sizeof dg);
+    unsigned long long dg; memcpy(&dg, (char*) L.h_stage + dig_off, sizeof dg);
     st->pair_digest_lo = (uint32_t) dg; st->pair_digest_hi = (uint32_t) (dg >> 32);
   }
   return LSM2D_SUCCESS;

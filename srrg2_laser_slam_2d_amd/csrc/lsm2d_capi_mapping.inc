@@ -4,15 +4,49 @@ static void launch_preprocess_scans(const PrepArgs& A, int n_scans, hipStream_t 
   if (n_scans >= 8 && A.n_beams <= kPrepSmallBeams) hipLaunchKernelGGL(k_preprocess_scans_small, dim3((unsigned) n_scans), dim3(kPrepSmallBlock), 0, st, A);
   else hipLaunchKernelGGL(k_preprocess_scans, dim3((unsigned) n_scans), dim3(kPrepBlock), 0, st, A);
 }
+// the preprocessor's parameters, checked the same way by every entry point (`who`: its name, as the messages carry it)
+static int check_preprocessor(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const char* who) {
+  char msg[96];
+  if (pp->n_beams < 1 || pp->n_beams > kPrepMaxBeams) { snprintf(msg, sizeof msg, "%s: n_beams must be in [1, 2048]", who); return fail(ctx, LSM2D_CAPACITY_EXCEEDED, msg); }
+  if (!(pp->angle_max > pp->angle_min) || pp->normal_min_points < 1 || !(pp->normal_point_distance >= 0.0f)) { snprintf(msg, sizeof msg, "%s: bad parameters", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
+  return LSM2D_SUCCESS;
+}
+// beam directions with the host libm (the oracle does the same): angle = (c - n/2) * sensor_res
+static void beam_dirs_host(const lsm2d_preprocessor* pp, float2* hd) {
+  const int nb = pp->n_beams;
+  const float sensor_res = (pp->angle_max - pp->angle_min) / (float) nb, k01 = (float) nb * 0.5f;
+  for (int c = 0; c < nb; ++c) { const float a = ((float) c - k01) * sensor_res; hd[c] = make_float2(cosf(a), sinf(a)); }
+}
+// ... on the device, once per sensor geometry (lsm2d_context::beam_dirs)
+static int beam_dirs_device(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const float2** out) {
+  const int nb = pp->n_beams;
+  for (const auto& bd : ctx->beam_dirs) if (bd.n_beams == nb && bd.angle_min == pp->angle_min && bd.angle_max == pp->angle_max) { *out = bd.d_dir; return LSM2D_SUCCESS; }
+  std::vector<float2> hd((size_t) nb);
+  beam_dirs_host(pp, hd.data());
+  float2* d = nullptr;
+  HIPCHK(ctx, hipMalloc((void**) &d, sizeof(float2) * (size_t) nb));
+  hipError_t e = hipMemcpy(d, hd.data(), sizeof(float2) * (size_t) nb, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void) hipFree(d); HIPCHK(ctx, e); }
+  ctx->beam_dirs.push_back({nb, pp->angle_min, pp->angle_max, d}); *out = d;
+  return LSM2D_SUCCESS;
+}
+// the preprocessing kernels' arguments: the scans' ranges and beam directions in, the clouds of `out` out (a stride of n_beams, made even, per cloud)
+static PrepArgs make_prep_args(const lsm2d_preprocessor* pp, const float* ranges, const float2* beam_dir, const lsm2d_cloudset* out) {
+  PrepArgs A;
+  A.ranges = ranges; A.beam_dir = beam_dir;
+  A.n_beams = pp->n_beams; A.stride = pp->n_beams + (pp->n_beams & 1); A.rmin = pp->range_min; A.rmax = pp->range_max;
+  A.d2max = pp->normal_point_distance * pp->normal_point_distance; A.min_points = pp->normal_min_points;
+  A.inv_res = pp->voxelize_resolution > 0.0f ? 1.0f / pp->voxelize_resolution : 0.0f;
+  A.out_xy = out->d_xy; A.out_nrm = out->d_nrm; A.out_count = out->d_count;
+  return A;
+}
 // ---- RawDataPreprocessorProjective2D, batched -------------------------------------------------------------------
 extern "C" int lsm2d_preprocess_scans(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const float* ranges, int32_t n_scans,
                                       lsm2d_cloudset** out) {
   if (!ctx || !pp || !out || n_scans < 1 || !ranges) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans: bad argument");
   *out = nullptr;
+  { const int rc0 = check_preprocessor(ctx, pp, "preprocess_scans"); if (rc0) return rc0; }
   const int nb = pp->n_beams;
-  if (nb < 1 || nb > kPrepMaxBeams) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scans: n_beams must be in [1, 2048]");
-  if (!(pp->angle_max > pp->angle_min) || pp->normal_min_points < 1 || !(pp->normal_point_distance >= 0.0f))
-    return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans: bad parameters");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int stride = nb + (nb & 1);
   if ((int64_t) stride * n_scans > 0x7ffffff0) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scans: too many points");
@@ -28,26 +62,20 @@ extern "C" int lsm2d_preprocess_scans(lsm2d_context* ctx, const lsm2d_preprocess
   int rdev = -1;
   const PtrKind kind = pointer_kind(ranges, &rdev);
   if (kind == PtrKind::device && rdev != ctx->device) { lsm2d_cloudset_destroy(cs); return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans: device-resident ranges must live on the context's device"); }
-  // beam directions with the host libm (the oracle does the same): angle = (c - n/2) * sensor_res
+  // (the beam directions travel in the staging buffer on every call here)
   const size_t rbytes = sizeof(float) * (size_t) nb * (size_t) n_scans, dbytes = sizeof(float2) * (size_t) nb;
   const size_t o_rng = (dbytes + 255) & ~(size_t) 255;
   rc = ensure_scratch(ctx, o_rng + (kind == PtrKind::device ? 0 : rbytes)); if (rc) { lsm2d_cloudset_destroy(cs); return rc; }
   rc = ensure_stage(ctx, o_rng + (kind == PtrKind::pageable ? rbytes : 0)); if (rc) { lsm2d_cloudset_destroy(cs); return rc; }
-  if (kind == PtrKind::pageable) memcpy((char*) ctx->h_stage + o_rng, ranges, rbytes);
-  float2* hd = (float2*) ctx->h_stage;
-  const float sensor_res = (pp->angle_max - pp->angle_min) / (float) nb, k01 = (float) nb * 0.5f;
-  for (int c = 0; c < nb; ++c) { const float a = ((float) c - k01) * sensor_res; hd[c] = make_float2(cosf(a), sinf(a)); }
-  PrepArgs A;
-  A.ranges = kind == PtrKind::device ? ranges : (const float*) ((char*) ctx->d_scratch + o_rng); A.beam_dir = (const float2*) ctx->d_scratch;
-  A.n_beams = nb; A.stride = stride; A.rmin = pp->range_min; A.rmax = pp->range_max;
-  A.d2max = pp->normal_point_distance * pp->normal_point_distance; A.min_points = pp->normal_min_points;
-  A.inv_res = pp->voxelize_resolution > 0.0f ? 1.0f / pp->voxelize_resolution : 0.0f;
-  A.out_xy = cs->d_xy; A.out_nrm = cs->d_nrm; A.out_count = cs->d_count;
-  hipError_t e = hipMemcpyAsync(ctx->d_scratch, ctx->h_stage, kind == PtrKind::pageable ? o_rng + rbytes : dbytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && kind == PtrKind::pinned) e = hipMemcpyAsync((char*) ctx->d_scratch + o_rng, ranges, rbytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(ctx->ev0, ctx->stream);
+  Lane& L = lane(ctx);
+  if (kind == PtrKind::pageable) memcpy((char*) L.h_stage + o_rng, ranges, rbytes);
+  beam_dirs_host(pp, (float2*) L.h_stage);
+  const PrepArgs A = make_prep_args(pp, kind == PtrKind::device ? ranges : (const float*) ((char*) L.d_scratch + o_rng), (const float2*) L.d_scratch, cs);
+  hipError_t e = hipMemcpyAsync(L.d_scratch, L.h_stage, kind == PtrKind::pageable ? o_rng + rbytes : dbytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && kind == PtrKind::pinned) e = hipMemcpyAsync((char*) L.d_scratch + o_rng, ranges, rbytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(L.ev0, ctx->stream);
   if (e == hipSuccess) { launch_preprocess_scans(A, n_scans, ctx->stream); e = hipGetLastError(); }
-  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(ctx->ev1, ctx->stream);
+  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(L.ev1, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(cs->h_count.data(), cs->d_count, sizeof(int32_t) * (size_t) n_scans, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = stream_sync(ctx);
   if (e != hipSuccess) { lsm2d_cloudset_destroy(cs); HIPCHK(ctx, e); }
@@ -64,10 +92,8 @@ extern "C" int lsm2d_preprocess_scans(lsm2d_context* ctx, const lsm2d_preprocess
 // somebody asks; the set's AoS rows, if it has them, are rewritten by the same launch.
 extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const float* ranges, int32_t n_scans, lsm2d_cloudset* set) {
   if (!ctx || !pp || !ranges || !set || set->ctx != ctx || n_scans < 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans_refill: bad argument");
+  { const int rc0 = check_preprocessor(ctx, pp, "preprocess_scans_refill"); if (rc0) return rc0; }
   const int nb = pp->n_beams;
-  if (nb < 1 || nb > kPrepMaxBeams) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scans_refill: n_beams must be in [1, 2048]");
-  if (!(pp->angle_max > pp->angle_min) || pp->normal_min_points < 1 || !(pp->normal_point_distance >= 0.0f))
-    return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans_refill: bad parameters");
   const int stride = nb + (nb & 1);
   if (set->n_clouds != n_scans || set->capacity > 0 || set->padded_total != (int64_t) stride * n_scans + 2 || (n_scans > 1 && set->h_start[1] != stride))
     return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans_refill: the set must come from lsm2d_preprocess_scans with the same number of scans and beams");
@@ -81,19 +107,8 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
   cloudset_drop_grids(set);
   set->d_aos = keep_aos;
   if (kind != PtrKind::device && !set->d_ranges) HIPCHK(ctx, hipMalloc((void**) &set->d_ranges, rbytes));
-  // beam directions with the host libm (the oracle does the same), once per sensor geometry
   const float2* d_dir = nullptr;
-  for (const auto& bd : ctx->beam_dirs) if (bd.n_beams == nb && bd.angle_min == pp->angle_min && bd.angle_max == pp->angle_max) d_dir = bd.d_dir;
-  if (!d_dir) {
-    std::vector<float2> hd((size_t) nb);
-    const float sensor_res = (pp->angle_max - pp->angle_min) / (float) nb, k01 = (float) nb * 0.5f;
-    for (int c = 0; c < nb; ++c) { const float a = ((float) c - k01) * sensor_res; hd[c] = make_float2(cosf(a), sinf(a)); }
-    float2* d = nullptr;
-    HIPCHK(ctx, hipMalloc((void**) &d, sizeof(float2) * (size_t) nb));
-    hipError_t e = hipMemcpy(d, hd.data(), sizeof(float2) * (size_t) nb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void) hipFree(d); HIPCHK(ctx, e); }
-    ctx->beam_dirs.push_back({nb, pp->angle_min, pp->angle_max, d}); d_dir = d;
-  }
+  { const int rc0 = beam_dirs_device(ctx, pp, &d_dir); if (rc0) return rc0; }
   const hipStream_t pre = refill_stream(ctx), cpy = refill_copy_stream(ctx, pre);
   if (set->ev_prep) HIPCHK(ctx, hipStreamWaitEvent(cpy, set->ev_prep, 0));      // (the same set refilled twice in a row: its previous launch, on the refill stream, may still read d_ranges and write the clouds)
   if (kind == PtrKind::pageable) {
@@ -108,18 +123,14 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
     }
   }
   else if (kind == PtrKind::pinned) HIPCHK(ctx, hipMemcpyAsync(set->d_ranges, ranges, rbytes, hipMemcpyHostToDevice, cpy));
-  if (cpy != pre && kind != PtrKind::device) { HIPCHK(ctx, hipEventRecord(ctx->ev_h, cpy)); HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->ev_h, 0)); }
+  if (cpy != pre && kind != PtrKind::device) { HIPCHK(ctx, hipEventRecord(ctx->side_copy.ev, cpy)); HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->side_copy.ev, 0)); }
   ++ctx->uploads; ctx->last_h2d_bytes = kind == PtrKind::device ? 0 : (long long) rbytes;
-  PrepArgs A;
-  A.ranges = kind == PtrKind::device ? ranges : (const float*) set->d_ranges; A.beam_dir = d_dir;
-  A.n_beams = nb; A.stride = stride; A.rmin = pp->range_min; A.rmax = pp->range_max;
-  A.d2max = pp->normal_point_distance * pp->normal_point_distance; A.min_points = pp->normal_min_points;
-  A.inv_res = pp->voxelize_resolution > 0.0f ? 1.0f / pp->voxelize_resolution : 0.0f;
-  A.out_xy = set->d_xy; A.out_nrm = set->d_nrm; A.out_count = set->d_count; A.out_aos = set->d_aos;
+  PrepArgs A = make_prep_args(pp, kind == PtrKind::device ? ranges : (const float*) set->d_ranges, d_dir, set);
+  A.out_aos = set->d_aos;
   launch_preprocess_scans(A, n_scans, pre);
   HIPCHK(ctx, hipGetLastError());
   if (pre != ctx->stream) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_c, pre)); ctx->c_dirty = true;      // the next aligner call waits for it (join_refill_stream)
+    HIPCHK(ctx, hipEventRecord(ctx->side_refill.ev, pre)); ctx->side_refill.dirty = true;      // the next aligner call waits for it (join_refill_stream)
     if (!set->ev_prep && hipEventCreateWithFlags(&set->ev_prep, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); set->ev_prep = nullptr; }
     if (set->ev_prep) HIPCHK(ctx, hipEventRecord(set->ev_prep, pre));
     else HIPCHK(ctx, hipStreamSynchronize(pre));      // (no event to be had: the only safe order left)
@@ -132,48 +143,30 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
 // the live tracker's form: ONE scan into an existing reserved set, no allocation, no wait (size pending on the device)
 extern "C" int lsm2d_preprocess_scan_into(lsm2d_context* ctx, const lsm2d_preprocessor* pp, const float* ranges, lsm2d_cloudset* out) {
   if (!ctx || !pp || !ranges || !out || out->ctx != ctx || out->n_clouds != 1 || out->many) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scan_into: bad argument");
+  { const int rc0 = check_preprocessor(ctx, pp, "preprocess_scan_into"); if (rc0) return rc0; }
   const int nb = pp->n_beams;
-  if (nb < 1 || nb > kPrepMaxBeams) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scan_into: n_beams must be in [1, 2048]");
-  if (!(pp->angle_max > pp->angle_min) || pp->normal_min_points < 1 || !(pp->normal_point_distance >= 0.0f))
-    return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scan_into: bad parameters");
   const int64_t cap = out->capacity > 0 ? out->capacity : out->padded_total - 2;
   if (cap < nb) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scan_into: the set must have room for n_beams points");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   cloudset_drop_grids(out);
-  // beam directions with the host libm (the oracle does the same), once per sensor geometry
   const float2* d_dir = nullptr;
-  for (const auto& bd : ctx->beam_dirs) if (bd.n_beams == nb && bd.angle_min == pp->angle_min && bd.angle_max == pp->angle_max) d_dir = bd.d_dir;
-  if (!d_dir) {
-    std::vector<float2> hd((size_t) nb);
-    const float sensor_res = (pp->angle_max - pp->angle_min) / (float) nb, k01 = (float) nb * 0.5f;
-    for (int c = 0; c < nb; ++c) { const float a = ((float) c - k01) * sensor_res; hd[c] = make_float2(cosf(a), sinf(a)); }
-    float2* d = nullptr;
-    HIPCHK(ctx, hipMalloc((void**) &d, sizeof(float2) * (size_t) nb));
-    hipError_t e = hipMemcpy(d, hd.data(), sizeof(float2) * (size_t) nb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void) hipFree(d); HIPCHK(ctx, e); }
-    ctx->beam_dirs.push_back({nb, pp->angle_min, pp->angle_max, d}); d_dir = d;
-  }
+  { const int rc0 = beam_dirs_device(ctx, pp, &d_dir); if (rc0) return rc0; }
   const size_t rbytes = sizeof(float) * (size_t) nb;
   out->unpack_pending = false;                  // an upload nobody read is simply replaced
   int rc = acquire_upload_stage(out, rbytes + 16); if (rc) return rc;
   memcpy(out->h_upload, ranges, rbytes);
-  void* dev_view = out->h_upload_dev;          // the kernel reads the ranges straight from the pinned buffer: no copy, no extra launch
-  PrepArgs A;
-  A.ranges = (const float*) dev_view; A.beam_dir = d_dir;
-  A.n_beams = nb; A.stride = nb + (nb & 1); A.rmin = pp->range_min; A.rmax = pp->range_max;
-  A.d2max = pp->normal_point_distance * pp->normal_point_distance; A.min_points = pp->normal_min_points;
-  A.inv_res = pp->voxelize_resolution > 0.0f ? 1.0f / pp->voxelize_resolution : 0.0f;
-  A.out_xy = out->d_xy; A.out_nrm = out->d_nrm; A.out_count = out->d_count;
+  const PrepArgs A = make_prep_args(pp, (const float*) out->h_upload_dev, d_dir, out);      // the kernel reads the ranges straight from the pinned buffer: no copy, no extra launch
   out->h_count[0] = nb; out->total = nb; out->count_pending = true;          // at most one point per beam
   if (!ctx->kernel_timing) {                    // the launch is queued by the set's first reader (flush_pending / flush_preprocessing_together)
     out->prep_pending = true; out->prep_args = A;
     return LSM2D_SUCCESS;
   }
   out->prep_pending = false;
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  Lane& L = lane(ctx);
+  HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
   hipLaunchKernelGGL(k_preprocess_scans, dim3(1), dim3(kPrepBlock), 0, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   out->staged_epoch = ctx->sync_epoch;                    // the staging buffer is free again once the kernel has run
   note_timed(ctx, true);
   return LSM2D_SUCCESS;
@@ -205,11 +198,12 @@ static int clip_scene_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const 
   const size_t cols = (size_t) P.cols, o_src = cols * 8, o_cnt = o_src + cols * 4, bytes = o_cnt + 16;
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
+  Lane& L = lane(ctx);
   float cam[3], cam_inv[3];
   compose_host(robot_in_local_map, sensor_in_robot, cam); inverse_host(cam, cam_inv);
   const Iso T = make_iso(cam_inv);
-  u64* d_canvas = (u64*) ctx->d_scratch;
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  u64* d_canvas = (u64*) L.d_scratch;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
   const bool small = scene->h_count[si] <= 32768;            // one workgroup, LDS canvas, one launch
   if (!small) { rc = project_split(ctx, scene->d_xy + scene->h_start[si], scene->h_count[si], T, P, d_canvas); if (rc) return rc; }
   ClipEmitArgs A;
@@ -218,10 +212,10 @@ static int clip_scene_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const 
   const bool s_ident = sensor_in_robot[0] == 0.0f && sensor_in_robot[1] == 0.0f && sensor_in_robot[2] == 0.0f;
   A.s_identity = s_ident || vox;                  // voxelisation happens in the sensor frame
   // synchronous form: source indices and the count go straight to the pinned staging buffer (no device-to-host copy)
-  char* dvo = (char*) ctx->d_scratch;
-  if (out_n) { rc = stage_device_view(ctx, &dvo); if (rc) return rc; *(int32_t*) ((char*) ctx->h_stage + o_cnt) = kStatusNotWritten; }
+  char* dvo = (char*) (out_n ? L.h_stage_dev : L.d_scratch);
+  if (out_n) *(int32_t*) ((char*) L.h_stage + o_cnt) = kStatusNotWritten;
   A.out_xy = clipped->d_xy; A.out_nrm = clipped->d_nrm; A.out_src = (int32_t*) (dvo + o_src);
-  A.out_count = vox ? (int32_t*) ((char*) ctx->d_scratch + o_cnt) : (int32_t*) (dvo + o_cnt);      // with voxelisation the final count is k_voxelize_clipped's
+  A.out_count = vox ? (int32_t*) ((char*) L.d_scratch + o_cnt) : (int32_t*) (dvo + o_cnt);      // with voxelisation the final count is k_voxelize_clipped's
   A.out_count_dev = clipped->d_count; A.host_polls = out_n != nullptr && !vox;
   if (small) {
     ClipSmallArgs CS; CS.xy = A.xy; CS.nrm = A.nrm; CS.n = scene->h_count[si]; CS.n_dev = scene->count_pending ? scene->d_count : nullptr; CS.proj = P; CS.emit = A;
@@ -239,16 +233,16 @@ static int clip_scene_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const 
     hipLaunchKernelGGL(k_voxelize_clipped, dim3(1), dim3(kVoxBlock), 0, ctx->stream, V);
     HIPCHK(ctx, hipGetLastError());
   }
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
   if (!out_n) {                               // at most one point per column
     clipped->h_count[0] = P.cols; clipped->total = P.cols; clipped->count_pending = true;
     return LSM2D_SUCCESS;
   }
-  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) ctx->h_stage + o_cnt), 1));      // the kernel writes the count last
-  const int32_t n = *(const int32_t*) ((char*) ctx->h_stage + o_cnt);
+  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) L.h_stage + o_cnt), 1));      // the kernel writes the count last
+  const int32_t n = *(const int32_t*) ((char*) L.h_stage + o_cnt);
   clipped->h_count[0] = n; clipped->total = n; clipped->count_pending = false; *out_n = n;
-  if (out_src) memcpy(out_src, (char*) ctx->h_stage + o_src, sizeof(int32_t) * (size_t) n);
+  if (out_src) memcpy(out_src, (char*) L.h_stage + o_src, sizeof(int32_t) * (size_t) n);
   return LSM2D_SUCCESS;
 }
 
@@ -294,14 +288,15 @@ extern "C" int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* pr, 
   const size_t o_mcan = cols * 8, o_out = o_mcan + cols * 8, o_txy = o_out + 64, o_tn = o_txy + ((nm * 8 + 15) & ~(size_t) 15) + 16, bytes = o_tn + nm * 8 + 16;
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, o_out + 64); if (rc) return rc;
+  Lane& L = lane(ctx);
   float cam_inv[3]; inverse_host(measurement_in_scene, cam_inv);
   const Iso Tinv = make_iso(cam_inv), M = make_iso(measurement_in_scene);
-  char* ds = (char*) ctx->d_scratch;
-  char* dvo = ds;                                  // synchronous form: the four counters go straight to the pinned staging buffer
-  if (out_size) { rc = stage_device_view(ctx, &dvo); if (rc) return rc; *(int32_t*) ((char*) ctx->h_stage + o_out) = kStatusNotWritten; }
+  char* ds = (char*) L.d_scratch;
+  char* dvo = out_size ? (char*) L.h_stage_dev : ds;      // synchronous form: the four counters go straight to the pinned staging buffer
+  if (out_size) *(int32_t*) ((char*) L.h_stage + o_out) = kStatusNotWritten;
   u64* d_scan = (u64*) ds; u64* d_mcan = (u64*) (ds + o_mcan);
   float2* d_txy = (float2*) (ds + o_txy); float2* d_tn = (float2*) (ds + o_tn);
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
   const bool small = n_scene <= 32768 && n_meas <= 32768 && (int) (sizeof(u64) * 2 * (size_t) P.cols) <= ctx->max_dyn_lds;
   if (small) {                                               // one workgroup does the transform, both z-buffers and the column walk
     MergeSmallArgs MS;
@@ -328,14 +323,14 @@ extern "C" int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* pr, 
   hipLaunchKernelGGL(k_merge_apply, dim3(1), dim3(kFindBlock), 0, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
   }
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
   if (!out_size) {                            // a merge appends at most one point per column
     scene->h_count[0] = n_scene + P.cols; scene->total = scene->h_count[0]; scene->count_pending = true;
     return LSM2D_SUCCESS;
   }
-  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) ctx->h_stage + o_out), 1));      // the kernel writes the new size last
-  const int32_t* h = (const int32_t*) ((char*) ctx->h_stage + o_out);
+  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) L.h_stage + o_out), 1));      // the kernel writes the new size last
+  const int32_t* h = (const int32_t*) ((char*) L.h_stage + o_out);
   scene->h_count[0] = h[0]; scene->total = h[0]; scene->count_pending = false; *out_size = h[0];
   if (out_counts) { out_counts[0] = h[1]; out_counts[1] = h[2]; out_counts[2] = h[3]; }
   return LSM2D_SUCCESS;
@@ -376,8 +371,9 @@ extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr,
   const size_t cols = (size_t) P.cols, o_out = 0, bytes = 16 * (size_t) n + 64;
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
-  char* dvo = (char*) ctx->d_scratch;         // synchronous form: the counters go straight to the pinned staging buffer, the last size last
-  if (out_size) { rc = stage_device_view(ctx, &dvo); if (rc) return rc; *(int32_t*) ((char*) ctx->h_stage + o_out + 16 * (size_t) (n - 1)) = kStatusNotWritten; }
+  Lane& L = lane(ctx);
+  char* dvo = (char*) (out_size ? L.h_stage_dev : L.d_scratch);         // synchronous form: the counters go straight to the pinned staging buffer, the last size last
+  if (out_size) { *(int32_t*) ((char*) L.h_stage + o_out + 16 * (size_t) (n - 1)) = kStatusNotWritten; }
   MergeMultiArgs MM; MM.n = n;
   for (int k = 0; k < n; ++k) {
     const lsm2d_cloudset* ms = meas[k]; const int mi = meas_index ? meas_index[k] : 0;
@@ -399,8 +395,8 @@ extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr,
     scene->h_count[0] = scene->h_count[0] + n * P.cols; scene->total = scene->h_count[0]; scene->count_pending = true;
     return LSM2D_SUCCESS;
   }
-  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) ctx->h_stage + o_out + 16 * (size_t) (n - 1)), 1));
-  const int32_t* h = (const int32_t*) ((char*) ctx->h_stage + o_out);
+  HIPCHK(ctx, wait_for_statuses(ctx, (const int32_t*) ((char*) L.h_stage + o_out + 16 * (size_t) (n - 1)), 1));
+  const int32_t* h = (const int32_t*) ((char*) L.h_stage + o_out);
   scene->h_count[0] = h[4 * (n - 1)]; scene->total = scene->h_count[0]; scene->count_pending = false; *out_size = scene->h_count[0];
   if (out_counts) for (int k = 0; k < n; ++k) { out_counts[3 * k] = h[4 * k + 1]; out_counts[3 * k + 1] = h[4 * k + 2]; out_counts[3 * k + 2] = h[4 * k + 3]; }
   return LSM2D_SUCCESS;
@@ -441,10 +437,10 @@ extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector*
   A.s_identity = sensor_in_robot[0] == 0.0f && sensor_in_robot[1] == 0.0f && sensor_in_robot[2] == 0.0f;
   A.out_xy = clipped->d_xy; A.out_nrm = clipped->d_nrm; A.out_stride = clipped->n_clouds > 1 ? clipped->h_start[1] : 0; A.out_count_dev = clipped->d_count;
   A.host_polls = out_n != nullptr; A.out_count = nullptr;
-  int32_t* h_out = (int32_t*) ctx->h_stage;
+  Lane& L = lane(ctx);
+  int32_t* h_out = (int32_t*) L.h_stage;
   if (out_n) {
-    char* dvo = nullptr; rc = stage_device_view(ctx, &dvo); if (rc) return rc;
-    A.out_count = (int32_t*) dvo;
+    A.out_count = (int32_t*) L.h_stage_dev;
     for (int i = 0; i < n; ++i) h_out[i] = kStatusNotWritten;
   }
   hipLaunchKernelGGL(k_clip_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * (size_t) P.cols, ctx->stream, A);
@@ -530,13 +526,13 @@ extern "C" int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector
   }
   A.proj = P; A.far_limit = 0.9f * pr->range_max; A.merge_threshold = merge_threshold; A.n_meas = nm;
   A.host_polls = out_sizes != nullptr;
-  const int32_t* h_out = (const int32_t*) ctx->h_stage;
+  Lane& L = lane(ctx);
+  const int32_t* h_out = (const int32_t*) L.h_stage;
   if (out_sizes) {
-    char* dvo = nullptr; rc = stage_device_view(ctx, &dvo); if (rc) return rc;
-    A.out = (int32_t*) dvo;
-    for (int i = 0; i < n; ++i) ((int32_t*) ctx->h_stage)[4 * ((size_t) i * nm + nm - 1)] = kStatusNotWritten;
+    A.out = (int32_t*) L.h_stage_dev;
+    for (int i = 0; i < n; ++i) ((int32_t*) L.h_stage)[4 * ((size_t) i * nm + nm - 1)] = kStatusNotWritten;
   } else {
-    A.out = (int32_t*) ctx->d_scratch;
+    A.out = (int32_t*) L.d_scratch;
   }
   hipLaunchKernelGGL(k_merge_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * 2 * (size_t) P.cols, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
@@ -572,16 +568,17 @@ extern "C" int lsm2d_project(lsm2d_context* ctx, const lsm2d_projector* pr, cons
   const size_t cols = (size_t) A.proj.cols, bytes = cols * (4 + 4 + 16);
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
+  Lane& L = lane(ctx);
   A.cloud = cloud_dev(cloud, nullptr); A.ci = ci; A.T = make_iso(pose);
-  char* dv = nullptr; rc = stage_device_view(ctx, &dv); if (rc) return rc;       // the canvas rows go straight to pinned host memory
+  char* dv = (char*) L.h_stage_dev;       // the canvas rows go straight to pinned host memory
   A.out_xynn = (float4*) dv;
   A.out_src = (int32_t*) (dv + cols * 16);
   A.out_depth = (float*) (dv + cols * 20);
   hipLaunchKernelGGL(k_project_canvas, dim3(1), dim3(kFindBlock), lds, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));
-  if (out_xynn) memcpy(out_xynn, ctx->h_stage, cols * 16);
-  if (out_src) memcpy(out_src, (char*) ctx->h_stage + cols * 16, cols * 4);
-  if (out_depth) memcpy(out_depth, (char*) ctx->h_stage + cols * 20, cols * 4);
+  if (out_xynn) memcpy(out_xynn, L.h_stage, cols * 16);
+  if (out_src) memcpy(out_src, (char*) L.h_stage + cols * 16, cols * 4);
+  if (out_depth) memcpy(out_depth, (char*) L.h_stage + cols * 20, cols * 4);
   return LSM2D_SUCCESS;
 }
