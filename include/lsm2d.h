@@ -47,7 +47,9 @@ extern "C" {
                              0.6.0: + option "sum_order" (1: H, b and the chi^2 statistics are added pair after pair in the reference's order -- the ONE option
                                     results depend on: with it the aligner is bitwise the sequential fp32 restatement of nicp_post.m:69-90);
                              (0.7.0, number unchanged: additions only) + lsm2d_cloudset_create_reserved_many / lsm2d_cloudset_clear_clouds, lsm2d_clip_scene_batch,
-                                    lsm2d_merge_scene_batch (N independent trackers per call: one workgroup per tracker, the single-tracker calls' bits) */
+                                    lsm2d_merge_scene_batch (N independent trackers per call: one workgroup per tracker, the single-tracker calls' bits);
+                             (0.7.1, number unchanged: an addition only) + lsm2d_find_correspondences_batch (plugin interface #1 for n_items triples in one
+                                    launch, the single call's bits); lsm2d_align_batch_pairs of more than one alignment derives its pairs through it */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -384,6 +386,24 @@ int lsm2d_find_correspondences(lsm2d_context* ctx, const lsm2d_slice_params* sli
                                const lsm2d_cloudset* moving, int32_t moving_index,
                                const float local_map_in_sensor[3],
                                lsm2d_correspondence* out_pairs, int32_t capacity, int32_t* out_n_pairs);
+/* CorrespondenceFinder_::compute for n_items independent (fixed, moving, pose) triples in ONE launch: item i matches cloud
+ * fixed_index[i] of `fixed` against cloud moving_index[i] of `moving` under local_map_in_sensor[i].  All four finder kinds; per item the
+ * pairs and their order are those of lsm2d_find_correspondences, bit for bit (one workgroup per item runs the single call's device
+ * functions; a cloud of any size is z-buffered by the item's own workgroup).
+ * Indices: the rule of lsm2d_batch -- NULL means cloud i, or cloud 0 of a set that holds one cloud (the set must then hold 1 or n_items
+ * clouds); indices may repeat.  Sets in any state (sizes known to the device only, unpacking / preprocessing pending) are read: counts are
+ * resolved and pending work is flushed once for the whole batch, and the set's search structure is built or reused once.
+ * pair_capacity must hold the largest possible vector -- canvas_cols for the projective finder, the largest cloud of `moving` otherwise --
+ * or the call returns LSM2D_CAPACITY_EXCEEDED before anything is launched and writes nothing.  n_items == 0 is a successful no-op.
+ * The pairs pass through a device buffer of fixed size (2^21 pairs): a batch whose n_items x pair_capacity exceeds it runs as several
+ * launches over consecutive items.  The call waits once per launch.  With one batch in flight (lsm2d_align_batch_begin) it works; with
+ * two it is refused (LSM2D_BAD_ARGUMENT), like every call that moves data. */
+int lsm2d_find_correspondences_batch(lsm2d_context* ctx, const lsm2d_slice_params* slice,
+                                     const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                     const lsm2d_cloudset* moving, const int32_t* moving_index,
+                                     int32_t n_items, const float* local_map_in_sensor /* [n_items][3] */,
+                                     lsm2d_correspondence* out_pairs /* [n_items][pair_capacity] */,
+                                     int32_t pair_capacity, int32_t* out_n_pairs /* [n_items] */);
 
 /* ---- factor: SE2Plane2PlaneErrorFactor over a correspondence vector ----------------------------
  * Replaces the per-correspondence errorAndJacobian + robustifier + H/b accumulation of the
@@ -453,8 +473,10 @@ int lsm2d_align_batch_wait(lsm2d_pending* pending, float* out_pose, float* out_H
  * order (ascending column / ascending moving index) -- with keep_only_inlier_correspondences only those whose factor was an inlier in that
  * iteration.  out_pairs: [n][n_slices][pair_capacity]; out_n_pairs: [n][n_slices].  pair_capacity must hold a slice's largest possible vector
  * (canvas_cols of a projective slice, the largest moving cloud of a point-query slice) or the call returns LSM2D_CAPACITY_EXCEEDED.  The
- * pairs are re-derived after the aligner kernel from the pose its last iteration started at (one finder pass per alignment and slice, same
- * arithmetic, hence the same pairs: tests compare their digest with the in-kernel one); out_pairs == NULL is lsm2d_align_batch. */
+ * pairs are re-derived after the aligner kernel from the pose its last iteration started at: ONE batched finder pass per slice over the
+ * alignments that started an iteration (lsm2d_find_correspondences_batch's kernels: a workgroup per alignment, one wait per launch; a call
+ * with a single alignment keeps one lsm2d_find_correspondences pass per slice) -- the same arithmetic, hence the same pairs: tests compare
+ * their digest with the in-kernel one.  out_pairs == NULL is lsm2d_align_batch. */
 int lsm2d_align_batch_pairs(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, const lsm2d_batch* batch,
                             float* out_pose, float* out_H, int32_t* out_status, int32_t* out_iterations, lsm2d_iteration_stats* out_stats,
                             lsm2d_correspondence* out_pairs, int32_t pair_capacity, int32_t* out_n_pairs);

@@ -317,6 +317,30 @@ class _FinderBase:
         self._correspondences = out[:n.value].copy()
         return self._correspondences
 
+    def compute_batch(self, fixed, moving, poses, fixed_index=None, moving_index=None) -> list:
+        """compute() for ``len(poses)`` independent (fixed, moving, pose) triples in one launch (lsm2d_find_correspondences_batch): item ``i``
+        matches cloud ``fixed_index[i]`` of the set ``fixed`` against cloud ``moving_index[i]`` of the set ``moving`` under ``poses[i]``
+        (None: cloud ``i``, or the only cloud of a one-cloud set).  Returns a list of int32 ``[k, 2]`` arrays (fixed_idx, moving_idx): per
+        item what ``compute()`` returns, in the same order."""
+        ctx, lib = self._ctx, self._ctx._lib
+        fixed = _as_cloudset(ctx, fixed); moving = _as_cloudset(ctx, moving)
+        x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+        n = len(x)
+        sp = self.slice_params()
+        fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
+        mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
+        if sp.finder == FINDER_PROJECTIVE:
+            cap = int(sp.projector.canvas_cols)
+        else:
+            cap = int(max(moving.counts)) if len(moving.counts) else 0
+        cap = max(cap, 1)
+        out = np.empty((max(n, 1), cap, 2), np.int32); cnt = np.zeros(max(n, 1), np.int32)
+        check(lib.lsm2d_find_correspondences_batch(ctx.handle, C.byref(sp), fixed.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
+                                                   moving.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n,
+                                                   x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)),
+              "lsm2d_find_correspondences_batch", ctx.handle)
+        return [out[i, : cnt[i]].copy() for i in range(n)]
+
 
 class CorrespondenceFinderProjective2f(_FinderBase):
     """registration/correspondence_finder_projective_2d.{h,cpp}"""
@@ -562,7 +586,8 @@ class MultiAligner2D:
                       fixed_index=None, moving_index=None, want_stats: bool = False, want_pairs: bool = False) -> BatchResult:
         """``fixed[s]`` / ``moving[s]``: cloud set of slice ``s`` (one cloud = shared by the batch, else one per
         alignment or chosen through ``*_index[s][i]``).  ``init_poses``: [n, 3].  want_pairs: also the correspondences the aligner
-        leaves in its slices (lsm2d_align_batch_pairs: one finder pass per alignment and slice after the aligner kernel)."""
+        leaves in its slices (lsm2d_align_batch_pairs: after the aligner kernel ONE batched finder pass per slice over the alignments that started an
+        iteration -- a workgroup per alignment, one wait per launch; a single alignment keeps one single-call pass per slice)."""
         ctx, lib = self._ctx, self._ctx._lib
         slices = self.param_slice_processors
         ns = len(slices)

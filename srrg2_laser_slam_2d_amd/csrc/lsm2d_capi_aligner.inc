@@ -889,8 +889,21 @@ extern "C" int lsm2d_estimate_work(lsm2d_context* ctx, const lsm2d_batch* b, int
 
 // MultiAligner2D::compute + what it leaves in the slices' correspondence vectors (apps/visual_test_aligner_2d.cpp:129-143).  The aligner kernels keep
 // no pair lists (their pairs live for one bin walk / one query); the vectors are re-derived from the pose the last started iteration began at by
-// the finder-level kernels -- the same arithmetic, hence the same pairs (tests: their digest equals the in-kernel one) -- one finder pass per
-// alignment and slice: an observability surface (40-90 us per pass), not a throughput path.
+// the finder-level kernels -- the same arithmetic, hence the same pairs (tests: their digest equals the in-kernel one).  A batch takes ONE batched finder
+// pass per slice over the alignments that started an iteration (k_find_*_batch: a workgroup per alignment, one wait per launch), so the pairs of a thousand
+// alignments cost a launch and a copy, not a thousand waits.
+// Routing: a call with ONE alignment keeps the single calls, one per slice (lsm2d_find_correspondences: pairs written straight to pinned host memory, no
+// argument upload, no result copy) -- for one slice by definition, for the tracker's two slices because it is the faster of the two: the batched pass is a
+// launch and a wait per slice as well and adds an upload and a copy to each.  Measured on the MI355X (tests/bench/pairs_batch_bench.py part c: one alignment, two
+// 721-column slices, a prior, with pairs; medians of 300 calls, three runs each, alternated in one job; profiles/r10/pairs_ab_r10.jsonl): single calls 83.2 / 84.1 /
+// 91.5 us per call (the parent commit: 84.2 / 84.2 / 84.3), the batched pass (a build with -DLSM2D_PAIRS_BATCH_MIN=1) 106.6 / 108.2 / 108.5.  From two alignments on
+// the batched pass: at n = 1000 it costs 0.53 - 0.65 ms where 1000 single calls cost 31.3 - 31.6 ms.
+static constexpr int kPairsBatchMinAlignments =
+#ifdef LSM2D_PAIRS_BATCH_MIN
+    LSM2D_PAIRS_BATCH_MIN;      // (A/B builds of tests/bench/pairs_batch_bench.py only)
+#else
+    2;
+#endif
 extern "C" int lsm2d_align_batch_pairs(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, float* out_pose, float* out_H,
                                        int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats,
                                        lsm2d_correspondence* out_pairs, int32_t pair_capacity, int32_t* out_n_pairs) {
@@ -912,10 +925,18 @@ extern "C" int lsm2d_align_batch_pairs(lsm2d_context* ctx, const lsm2d_aligner_p
   if (!its) { its_local.assign((size_t) (n > 0 ? n : 1), 0); its = its_local.data(); }
   int rc = align_batch_impl(ctx, ap, b, out_pose, out_H, out_status, its, out_stats, last_pose.data());
   if (rc) return rc;
-  for (int i = 0; i < n; ++i)
-    for (int s = 0; s < ns; ++s) {
-      const lsm2d_slice_params& sp = b->slices[s];
-      const lsm2d_cloudset* f = b->fixed[s]; const lsm2d_cloudset* m = b->moving[s];
+  const bool batched = n >= kPairsBatchMinAlignments;
+  std::vector<int32_t> slots, fcs, mcs; std::vector<float> poses;
+  if (batched) { slots.reserve((size_t) n); fcs.reserve((size_t) n); mcs.reserve((size_t) n); poses.reserve((size_t) 3 * (size_t) n); }
+  for (int s = 0; s < ns; ++s) {
+    const lsm2d_slice_params& sp = b->slices[s];
+    const lsm2d_cloudset* f = b->fixed[s]; const lsm2d_cloudset* m = b->moving[s];
+    const bool has_sensor = !(sp.sensor_in_robot[0] == 0.0f && sp.sensor_in_robot[1] == 0.0f && sp.sensor_in_robot[2] == 0.0f);
+    const float inl_tau = (ap->keep_only_inlier_correspondences && sp.robustifier == LSM2D_ROBUST_CAUCHY) ? sp.chi_threshold : 0.0f;
+    float Sinv[3] = {0.0f, 0.0f, 0.0f};
+    if (has_sensor) inverse_host(sp.sensor_in_robot, Sinv);
+    slots.clear(); fcs.clear(); mcs.clear(); poses.clear();
+    for (int i = 0; i < n; ++i) {
       int32_t* cnt = out_n_pairs + (size_t) i * ns + s;
       lsm2d_correspondence* dst = out_pairs + ((size_t) i * ns + s) * (size_t) pair_capacity;
       *cnt = 0;
@@ -923,11 +944,19 @@ extern "C" int lsm2d_align_batch_pairs(lsm2d_context* ctx, const lsm2d_aligner_p
       const int fc = b->fixed_index ? b->fixed_index[(size_t) s * n + i] : (f->n_clouds == 1 ? 0 : i);
       const int mc = b->moving_index ? b->moving_index[(size_t) s * n + i] : (m->n_clouds == 1 ? 0 : i);
       float Xe[3] = {last_pose[3 * (size_t) i], last_pose[3 * (size_t) i + 1], last_pose[3 * (size_t) i + 2]};
-      const bool has_sensor = !(sp.sensor_in_robot[0] == 0.0f && sp.sensor_in_robot[1] == 0.0f && sp.sensor_in_robot[2] == 0.0f);
-      if (has_sensor) { float Sinv[3], X[3] = {Xe[0], Xe[1], Xe[2]}; inverse_host(sp.sensor_in_robot, Sinv); compose_host(Sinv, X, Xe); }      // X_eff = S^-1 X, the kernels' operations
-      const float inl_tau = (ap->keep_only_inlier_correspondences && sp.robustifier == LSM2D_ROBUST_CAUCHY) ? sp.chi_threshold : 0.0f;
-      rc = find_correspondences_impl(ctx, &sp, f, fc, m, mc, Xe, dst, pair_capacity, cnt, inl_tau);
+      if (has_sensor) { float X[3] = {Xe[0], Xe[1], Xe[2]}; compose_host(Sinv, X, Xe); }      // X_eff = S^-1 X, the kernels' operations
+      if (!batched) {
+        rc = find_correspondences_impl(ctx, &sp, f, fc, m, mc, Xe, dst, pair_capacity, cnt, inl_tau);
+        if (rc) return rc;
+        continue;
+      }
+      slots.push_back(i); fcs.push_back(fc); mcs.push_back(mc); poses.push_back(Xe[0]); poses.push_back(Xe[1]); poses.push_back(Xe[2]);
+    }
+    if (batched && !slots.empty()) {      // the slice's pass: destination strided into [n][n_slices][pair_capacity]
+      rc = find_batch_impl(ctx, &sp, f, fcs.data(), m, mcs.data(), (int32_t) slots.size(), poses.data(), inl_tau, out_pairs + (size_t) s * (size_t) pair_capacity,
+                           pair_capacity, out_n_pairs + s, slots.data(), (size_t) ns * (size_t) pair_capacity, (size_t) ns);
       if (rc) return rc;
     }
+  }
   return LSM2D_SUCCESS;
 }

@@ -101,6 +101,119 @@ extern "C" int lsm2d_find_correspondences(lsm2d_context* ctx, const lsm2d_slice_
   return find_correspondences_impl(ctx, sp, fixed, fi, moving, mi, pose, out_pairs, capacity, out_n, 0.0f);
 }
 
+// ---- plugin interface #1 for a whole batch ------------------------------------------------------------------------
+// The device room for the pairs of ONE launch of the batched finder, in pairs (8 bytes each: 16 MiB, and as much pinned staging behind it).  Every item owns
+// pair_capacity slots of it whatever it finds, so a launch takes kFindBatchPairBudget / pair_capacity items (at least one); a batch beyond that runs as several
+// launches over consecutive items, each with its own wait -- same results.  1000 scans against a 1081-column canvas (8.6 MB) are one launch; point-query items of
+// a 100 000-point moving cloud go 20 to a launch.
+static constexpr size_t kFindBatchPairBudget = (size_t) 2 << 20;
+
+// n items, item k = (cloud fc[k] of `fixed`, cloud mc[k] of `moving`, poses[k]); its pairs go to out_pairs + slot * pair_stride and its count to
+// out_n + slot * count_stride, slot = slots ? slots[k] : k.  The callers have checked the pointers, the indices and the capacity rule.
+static int find_batch_impl(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fc, const lsm2d_cloudset* moving,
+                           const int32_t* mc, int32_t n, const float* poses, float inl_tau, lsm2d_correspondence* out_pairs, int32_t capacity,
+                           int32_t* out_n, const int32_t* slots, size_t pair_stride, size_t count_stride) {
+  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  // sizes only the device knows, pending unpacking / preprocessing: once for the whole batch
+  { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
+  { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
+  const bool point_query = sp->finder == LSM2D_FINDER_NN || sp->finder == LSM2D_FINDER_DISTMAP || sp->finder == LSM2D_FINDER_KDTREE;
+  if (!point_query && sp->finder != LSM2D_FINDER_PROJECTIVE) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: finder not supported");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  FindBatchArgs A; FindNNBatchArgs N;
+  size_t lds = 0;
+  if (point_query) {
+    if (sp->finder != LSM2D_FINDER_DISTMAP && !(sp->max_distance > 0.0f)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: max_distance must be > 0");
+    N.fixed = cloud_dev(fixed, nullptr); N.moving = cloud_dev(moving, nullptr);
+    N.use_distmap = sp->finder == LSM2D_FINDER_DISTMAP; N.use_kd = sp->finder == LSM2D_FINDER_KDTREE;
+    // the set's search structure covers every cloud of it: built (or found) once
+    const int rc = N.use_distmap ? ensure_distmap(ctx, fixed, sp->max_distance, sp->resolution, &N.fixed.dist)
+                 : N.use_kd      ? ensure_kdtree(ctx, fixed, sp->kd_max_leaf_range, sp->kd_min_leaf_points, &N.fixed.kd)
+                                 : ensure_grid(ctx, fixed, sp->max_distance, &N.fixed.grid);
+    if (rc) return rc;
+    N.max_distance = sp->max_distance; N.normal_cos = sp->normal_cos; N.inl_tau = inl_tau; N.pair_capacity = capacity;
+  } else {
+    if (!make_projk(sp->projector, &A.proj)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: bad projector");
+    lds = sizeof(u64) * 2 * (size_t) A.proj.cols;
+    if ((int) lds > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "find_correspondences_batch: canvases do not fit LDS");
+    A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr);
+    A.point_distance = sp->point_distance; A.normal_cos = sp->normal_cos; A.inl_tau = inl_tau; A.pair_capacity = capacity;
+  }
+  size_t per_launch = kFindBatchPairBudget / (size_t) (capacity > 0 ? capacity : 1);
+  if (per_launch < 1) per_launch = 1;
+  if (per_launch > (size_t) n) per_launch = (size_t) n;
+  // one layout for the lane's device scratch and its pinned staging: the items' arguments (up), then counts and pairs (down, ONE copy)
+  const size_t o_cnt = (sizeof(FindItem) * per_launch + 255) & ~(size_t) 255, o_pairs = (o_cnt + sizeof(int32_t) * per_launch + 255) & ~(size_t) 255;
+  const size_t bytes = o_pairs + sizeof(lsm2d_correspondence) * per_launch * (size_t) capacity;
+  { int rc = ensure_scratch(ctx, bytes); if (rc) return rc; rc = ensure_stage(ctx, bytes); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  for (size_t k0 = 0; k0 < (size_t) n; k0 += per_launch) {
+    const size_t cnt = (size_t) n - k0 < per_launch ? (size_t) n - k0 : per_launch;
+    FindItem* items = (FindItem*) hs;
+    for (size_t k = 0; k < cnt; ++k) {
+      FindItem& it = items[k];
+      it.fc = fc[k0 + k]; it.mc = mc[k0 + k]; it.T = make_iso(poses + 3 * (k0 + k)); it.pad = 0;
+      it.nn_group = fixed->h_count[it.fc] >= 4 * (int64_t) moving->h_count[it.mc] ? kNNGroup : 1;      // dense fixed cloud: cooperative search, item by item
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(FindItem) * cnt, hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+    if (point_query) {
+      N.items = (const FindItem*) ds; N.out_count = (int32_t*) (ds + o_cnt); N.out_pairs = (int32_t*) (ds + o_pairs);
+      hipLaunchKernelGGL(k_find_nn_batch, dim3((unsigned) cnt), dim3(kFindBlock), 0, ctx->stream, N);
+    } else {
+      A.items = (const FindItem*) ds; A.out_count = (int32_t*) (ds + o_cnt); A.out_pairs = (int32_t*) (ds + o_pairs);
+      hipLaunchKernelGGL(k_find_projective_batch, dim3((unsigned) cnt), dim3(kFindBlock), lds, ctx->stream, A);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+    note_timed(ctx, ctx->kernel_timing);
+    const size_t down = o_pairs - o_cnt + sizeof(lsm2d_correspondence) * cnt * (size_t) capacity;
+    HIPCHK(ctx, hipMemcpyAsync(hs + o_cnt, ds + o_cnt, down, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_sync(ctx));      // the one wait of this launch
+    const int32_t* h_cnt = (const int32_t*) (hs + o_cnt);
+    for (size_t k = 0; k < cnt; ++k) {
+      const size_t slot = slots ? (size_t) slots[k0 + k] : k0 + k;
+      const int32_t np = h_cnt[k];
+      if (np < 0 || np > capacity) return fail(ctx, LSM2D_DEVICE_ERROR, "find_correspondences_batch: an item reported more pairs than its slot holds");
+      out_n[slot * count_stride] = np;
+      if (np) memcpy(out_pairs + slot * pair_stride, hs + o_pairs + sizeof(lsm2d_correspondence) * k * (size_t) capacity, sizeof(lsm2d_correspondence) * (size_t) np);
+    }
+  }
+  return LSM2D_SUCCESS;
+}
+
+// a slice's largest possible correspondence vector: one pair per column, or per point of the largest moving cloud
+static int find_batch_need(const lsm2d_slice_params* sp, const lsm2d_cloudset* moving, long long* need) {
+  *need = 0;
+  if (sp->finder == LSM2D_FINDER_PROJECTIVE) { *need = sp->projector.canvas_cols; return LSM2D_SUCCESS; }
+  const int rc0 = resolve_count(moving); if (rc0) return rc0;
+  for (int c = 0; c < moving->n_clouds; ++c) if (moving->h_count[c] > *need) *need = moving->h_count[c];
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_find_correspondences_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                                const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses,
+                                                lsm2d_correspondence* out_pairs, int32_t pair_capacity, int32_t* out_n_pairs) {
+  if (!ctx || !sp || !fixed || !moving || n_items < 0 || pair_capacity < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: bad argument");
+  if (fixed->ctx != ctx || moving->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: cloud set from another (or a destroyed) context");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  if (n_items == 0) return LSM2D_SUCCESS;
+  if (!poses || !out_n_pairs || (pair_capacity > 0 && !out_pairs)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: null argument");
+  if (!fixed_index && fixed->n_clouds != 1 && fixed->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: fixed set must hold 1 or n_items clouds");
+  if (!moving_index && moving->n_clouds != 1 && moving->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: moving set must hold 1 or n_items clouds");
+  std::vector<int32_t> fc((size_t) n_items), mc((size_t) n_items);
+  for (int32_t i = 0; i < n_items; ++i) {
+    fc[(size_t) i] = fixed_index ? fixed_index[i] : (fixed->n_clouds == 1 ? 0 : i);
+    mc[(size_t) i] = moving_index ? moving_index[i] : (moving->n_clouds == 1 ? 0 : i);
+    if (!valid_cloud_index(fixed, fc[(size_t) i]) || !valid_cloud_index(moving, mc[(size_t) i])) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: cloud index out of range");
+  }
+  long long need = 0;
+  { const int rc0 = find_batch_need(sp, moving, &need); if (rc0) return rc0; }
+  if (need > pair_capacity) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "find_correspondences_batch: pair_capacity below the largest possible correspondence vector");
+  return find_batch_impl(ctx, sp, fixed, fc.data(), moving, mc.data(), n_items, poses, 0.0f, out_pairs, pair_capacity, out_n_pairs, nullptr, (size_t) pair_capacity, 1);
+}
+
 // ---- factor ---------------------------------------------------------------------------------------------------
 extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, int32_t fi,
                                const lsm2d_cloudset* moving, int32_t mi, const lsm2d_correspondence* pairs, int32_t n_pairs,

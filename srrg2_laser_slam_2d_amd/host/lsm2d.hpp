@@ -81,6 +81,32 @@ struct PointNormal2fProjectorPolar {
 };
 using PointNormal2fProjectorPolarPtr = std::shared_ptr<PointNormal2fProjectorPolar>;
 
+// compute() of a finder for poses.size() independent (fixed, moving, pose) triples in one launch (lsm2d_find_correspondences_batch): item i matches cloud
+// fixed_index[i] of `fixed` against cloud moving_index[i] of `moving` (an empty index vector: cloud i, or the only cloud of a one-cloud set) under poses[i];
+// per item the vector compute() fills, in the same order
+inline std::vector<CorrespondenceVector> findCorrespondencesBatch(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving,
+                                                                  const std::vector<Vector3f>& poses, const std::vector<int32_t>& fixed_index,
+                                                                  const std::vector<int32_t>& moving_index) {
+  const size_t n = poses.size();
+  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
+    throw std::runtime_error("findCorrespondencesBatch| an index vector is empty or holds one entry per pose");
+  size_t cap = 0;
+  if (sp.finder == LSM2D_FINDER_PROJECTIVE) cap = (size_t) (sp.projector.canvas_cols > 0 ? sp.projector.canvas_cols : 0);
+  else {      // one pair per point of the largest moving cloud
+    std::vector<int32_t> sizes((size_t) moving.numClouds(), 0);
+    check(std::min(lsm2d_cloudset_cloud_sizes(moving.get(), sizes.data(), (int32_t) sizes.size()), 0), "lsm2d_cloudset_cloud_sizes", ctx.get());
+    for (int32_t v : sizes) cap = std::max(cap, (size_t) v);
+  }
+  std::vector<Correspondence> buf(std::max<size_t>(cap * n, 1)); std::vector<int32_t> cnt(std::max<size_t>(n, 1), 0);
+  check(lsm2d_find_correspondences_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
+                                         moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, buf.data(),
+                                         (int32_t) cap, cnt.data()),
+        "lsm2d_find_correspondences_batch", ctx.get());
+  std::vector<CorrespondenceVector> out(n);
+  for (size_t i = 0; i < n; ++i) out[i].assign(buf.begin() + (ptrdiff_t) (i * cap), buf.begin() + (ptrdiff_t) (i * cap + (size_t) cnt[i]));
+  return out;
+}
+
 class CorrespondenceFinderProjective2f {
  public:
   explicit CorrespondenceFinderProjective2f(Context& ctx) : _ctx(ctx) {}
@@ -113,6 +139,12 @@ class CorrespondenceFinderProjective2f {
                                      _correspondences->data(), (int32_t) _correspondences->size(), &k),
           "lsm2d_find_correspondences", _ctx.get());
     _correspondences->resize((size_t) k);                                 // .cpp:76
+  }
+  // compute() for a whole batch of (fixed, moving, pose) triples in one launch: see findCorrespondencesBatch
+  std::vector<CorrespondenceVector> computeBatch(const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
+                                                 const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
+    if (!param_projector) throw std::runtime_error("CorrespondenceFinderProjective2f::computeBatch| Missing Projector");
+    return findCorrespondencesBatch(_ctx, sliceParams(), fixed, moving, poses, fixed_index, moving_index);
   }
  private:
   Context& _ctx;
@@ -152,6 +184,12 @@ class CorrespondenceFinderPointQuery {
                                      _correspondences->data(), (int32_t) _correspondences->size(), &k),
           "lsm2d_find_correspondences", _ctx.get());
     _correspondences->resize((size_t) k);
+  }
+  // compute() for a whole batch of (fixed, moving, pose) triples in one launch: see findCorrespondencesBatch
+  std::vector<CorrespondenceVector> computeBatch(const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
+                                                 const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
+    if (_finder == LSM2D_FINDER_DISTMAP && !(param_resolution > 0.f)) throw std::runtime_error("resolution must be > 0");
+    return findCorrespondencesBatch(_ctx, sliceParams(), fixed, moving, poses, fixed_index, moving_index);
   }
  protected:
   Context& _ctx; int _finder;

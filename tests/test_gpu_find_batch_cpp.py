@@ -1,0 +1,43 @@
+"""computeBatch of the C++ host mirror's finders (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU: the batches equal the
+mirror's own single compute() calls item by item (checked inside the driver) and the CPU oracle (checked here), bit for bit."""
+import json
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from srrg2_laser_slam_2d_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+
+def test_cpp_compute_batch(po, tmp_path):
+    exe = str(tmp_path / "find_batch_driver")
+    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
+                    os.path.join(ROOT, "tests", "cpp", "find_batch_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    world = synth.make_world(4)
+    m = synth.make_map(world, 6000, seed=2)
+    robots = synth.sample_poses(world, 6, seed=8)
+    pts, offs = synth.make_scans(world, robots, n_beams=1081, noise_sigma=0.01, seed=5)
+    x0 = synth.invert_poses(synth.compose_poses(robots, np.array([[0.12, -0.08, 0.04]] * 6))).astype(np.float32)
+    x0[5] = np.float32([500.0, 500.0, 1.0])
+    pts.tofile(tmp_path / "scans.bin"); offs.astype(np.int32).tofile(tmp_path / "offsets.bin"); m.tofile(tmp_path / "map.bin"); x0.tofile(tmp_path / "poses.bin")
+    out = subprocess.run([exe] + [str(tmp_path / f) for f in ("scans.bin", "offsets.bin", "map.bin", "poses.bin")] + ["1081", "0.4"],
+                         check=True, capture_output=True, text=True, timeout=120).stdout
+    r = json.loads(out)
+    assert r["n"] == 6 and r["equal_single"] == 1 and r["equal_reversed"] == 1 and r["n_empty"] == 0
+    osp = po.slice_params(canvas_cols=1081, range_max=25.0)
+    onn = po.slice_params(finder=po.FINDER_NN, max_distance=0.4, normal_cos=0.7)
+    counts = []
+    for i in range(6):
+        scan = pts[offs[i]:offs[i + 1]]
+        got = np.array(r["projective"][i], np.int32).reshape(-1, 2)
+        assert np.array_equal(got, po.find(osp, scan, m, x0[i])), i
+        counts.append(len(got))
+        inv = np.float32(r["inv"][i])      # the driver's own host-side inverse, as printed
+        assert np.array_equal(np.array(r["nn"][i], np.int32).reshape(-1, 2), po.find(onn, m, scan, inv)), i
+    assert counts == [404, 516, 404, 430, 466, 0]
