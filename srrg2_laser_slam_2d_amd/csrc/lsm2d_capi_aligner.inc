@@ -112,7 +112,8 @@ struct AlignBatch {
   int clock_stride, n_clock;
   bool had_inputs; char* hs; char* ds;
   // ---- which path
-  bool has_proj, has_nn, has_dist, has_kd, split_ok, use_split, zero_copy, use_pair;
+  bool has_proj, has_nn, has_dist, has_kd, proj_only /* projective slices and no others */, split_ok, use_split, zero_copy;
+  bool pair_eligible /* the latency kernel may take the call, its LDS and the split path aside */, use_pair;
   int max_moving;
   // ---- slices, LDS
   int cols_max, fcan_total, max_fixed_rows; const KdCache* kd_cache0;
@@ -197,9 +198,10 @@ int AlignBatch::choose_path() {
     const int fd = b->slices[s].finder;
     if (fd == LSM2D_FINDER_PROJECTIVE) has_proj = true; else if (fd == LSM2D_FINDER_NN) has_nn = true; else if (fd == LSM2D_FINDER_KDTREE) has_kd = true; else has_dist = true;
     const lsm2d_cloudset* m = b->moving[s];
-    if (m) for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] > max_moving) max_moving = m->h_count[c];
+    if (m) max_moving = std::max(max_moving, max_cloud_count(m));
   }
-  split_ok = has_proj && !has_nn && !has_dist && !has_kd && ap->max_iterations > 0 && n <= 32768;
+  proj_only = has_proj && !has_nn && !has_dist && !has_kd;
+  split_ok = proj_only && ap->max_iterations > 0 && n <= 32768;
   // measured (tools/small_batch_bench.py, profiles/r01/small_batch*.jsonl): the split path costs two launches per iteration per
   // alignment call and wins whenever one workgroup per alignment would leave most of the chip idle for long enough
   use_split = split_ok && (ctx->align_path == 2 ||
@@ -211,6 +213,7 @@ int AlignBatch::choose_path() {
   // against 1.467 with the three small transfers; tools/zero_copy_ab.py.)
   // ("zero_copy_max" bounds every batch, so the A/B knob works below 256 too; batches that carry index arrays stay on the transfers above 256)
   zero_copy = !out_work && !use_split && n <= ctx->zero_copy_max && (n <= 256 || (!b->fixed_index && !b->moving_index));
+  pair_eligible = pair_order_ok(ctx, n) && ctx->align_path != 1 && (ns == 1 || ns == 2) && proj_only && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
   if (zero_copy) ds = (char*) L->h_stage_dev;
   return LSM2D_SUCCESS;
 }
@@ -278,14 +281,13 @@ int AlignBatch::prepare_slices() {
     }
     // a fixed set whose upload still sits in its pinned buffer: single-alignment projective calls unpack it in the kernel's prologue
     // (decided once the kernel is known, below); every other reader gets it unpacked by a launch of its own, here
-    const bool defer_unpack = f->unpack_pending && n == 1 && !use_split && has_proj && !has_nn && !has_dist && !has_kd && f != m;
+    const bool defer_unpack = f->unpack_pending && n == 1 && !use_split && proj_only && f != m;
     if (!defer_unpack) { const int urc = flush_pending(f); if (urc) return urc; }
     { const int urc = flush_pending(m); if (urc) return urc; }
     if (sp.finder == LSM2D_FINDER_PROJECTIVE) { const int lrc = ensure_lane_layout(ctx, m); if (lrc) return lrc; }
     // k_align's bin walk gathers both z-buffer winners as 16-byte rows of the sets' AoS copies (not for the calls the latency kernel or the split
     // path will take: the live tracker's sets change every step)
-    const bool pair_candidate = pair_order_ok(ctx, n) && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
-    if (sp.finder == LSM2D_FINDER_PROJECTIVE && !use_split && !pair_candidate && !defer_unpack) {
+    if (sp.finder == LSM2D_FINDER_PROJECTIVE && !use_split && !pair_eligible && !defer_unpack) {
       int arc = ensure_aos(ctx, f); if (arc) return arc;
       arc = ensure_aos(ctx, m); if (arc) return arc;
     }
@@ -295,9 +297,7 @@ int AlignBatch::prepare_slices() {
     if (sp.finder == LSM2D_FINDER_DISTMAP) { const int grc = ensure_distmap(ctx, f, sp.max_distance, sp.resolution, &S.fixed.dist); if (grc) return grc; }
     if (sp.finder == LSM2D_FINDER_KDTREE) { const int grc = ensure_kdtree(ctx, f, sp.kd_max_leaf_range, sp.kd_min_leaf_points, &S.fixed.kd, &kd_cache0); if (grc) return grc; }
     {   // cooperative NN search pays when the fixed cloud is much denser than the queries (map as fixed, scans as queries)
-      int64_t mf = 0, mm = 1;
-      for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > mf) mf = f->h_count[c];
-      for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] > mm) mm = m->h_count[c];
+      const int64_t mf = max_cloud_count(f), mm = std::max(1, max_cloud_count(m));
       S.nn_group = mf >= 4 * mm ? kNNGroup : 1;
     }
     S.finder = sp.finder; S.point_distance = sp.point_distance; S.normal_cos = sp.normal_cos; S.max_distance = sp.max_distance;
@@ -327,9 +327,7 @@ int AlignBatch::lay_out_lds() {
   if (ns == 1 && ctx->cull && (b->slices[0].finder == LSM2D_FINDER_NN || b->slices[0].finder == LSM2D_FINDER_KDTREE || b->slices[0].finder == LSM2D_FINDER_DISTMAP) &&
       !b->moving[0]->count_pending) {
     const lsm2d_cloudset* f = b->fixed[0]; const lsm2d_cloudset* m = b->moving[0];
-    int mf = 0, mm = 0;
-    for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > mf) mf = f->h_count[c];
-    for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] > mm) mm = m->h_count[c];
+    const int mf = max_cloud_count(f), mm = max_cloud_count(m);
     const int keep_words = (((mm + 63) / 64 + kAlignBlock - 1) / kAlignBlock) * (kAlignBlock / 64);
     if (mf <= 16384 && mm >= 4096 && mm > 2 * mf && keep_words <= 512) {
       const int trc = ensure_tile_bounds(ctx, m); if (trc) return trc;
@@ -340,7 +338,7 @@ int AlignBatch::lay_out_lds() {
   A.nn_lds_points = 0; A.nn_lds_cells = 0;
   if (ns == 1 && b->slices[0].finder == LSM2D_FINDER_NN && A.s[0].nn_group == 1) {
     const lsm2d_cloudset* f = b->fixed[0];
-    int mf = 0; for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > mf) mf = f->h_count[c];
+    const int mf = max_cloud_count(f);
     int cap = (int) ceil((mf >= 16384 ? 6.0 : 3.0) * sqrt((double) (mf > 0 ? mf : 1))); cap = cap < 16 ? 16 : cap;      // ensure_grid's rule
     const size_t need = sizeof(float2) * (size_t) mf + sizeof(uint16_t) * ((size_t) cap * cap + 4) + sizeof(uint16_t) * ((size_t) mf + 2);
     if (mf > 0 && mf <= 65535 && lds + need <= lds_budget) { A.nn_lds_points = mf; A.nn_lds_cells = cap * cap + 1; lds += need + 16; }
@@ -350,7 +348,7 @@ int AlignBatch::lay_out_lds() {
   A.nn_qcache = 0;
   if (ns == 1 && b->slices[0].finder == LSM2D_FINDER_NN && A.nn_lds_points == 0 && ctx->nn_qcache) {
     const lsm2d_cloudset* m = b->moving[0];
-    int mm = 0; for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] > mm) mm = m->h_count[c];
+    const int mm = max_cloud_count(m);
     lds = (lds + 15) & ~(size_t) 15;
     if (mm > 0 && lds + 32 * (size_t) mm + 16 <= lds_budget) { A.nn_qcache = mm; lds += 32 * (size_t) mm + 16; }
   }
@@ -363,7 +361,7 @@ int AlignBatch::lay_out_lds() {
     if (k > 0) { A.kd_lds_nodes = k; lds += (size_t) k * (sizeof(float4) + sizeof(int2)) + 16; }
     // scan-sized fixed clouds whose whole tree fits: the leaf arrays too (coordinates and normals: 16 bytes per point)
     const lsm2d_cloudset* f = b->fixed[0];
-    int mf = 0; for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > mf) mf = f->h_count[c];
+    const int mf = max_cloud_count(f);
     const size_t need = (size_t) (mf + 2) * (sizeof(float2) + sizeof(float2)) + 32;
     if (k > 0 && k == kd_cache0->max_nodes_per_cloud && mf > 0 && mf <= 65535 && lds + need <= lds_budget) { A.kd_lds_points = mf; lds += need; }
   }
@@ -372,7 +370,7 @@ int AlignBatch::lay_out_lds() {
   // the projective instantiation with the culled stream only: every slice's moving set has its lane-chunked copy and chunk circles, and culling is on
   // (its unit lists -- kCullBlocks x 512 16-bit entries per slice, kept across iterations -- sit behind everything else in dynamic LDS; "cull_block" is the
   // round-3 stream's tuning knob: a batch that sets it runs the shared instantiation)
-  proj_culled_for_all = has_proj && !has_nn && !has_dist && !has_kd && A.cull == 1 && ctx->proj_modes && ctx->cull_block == 0;
+  proj_culled_for_all = proj_only && A.cull == 1 && ctx->proj_modes && ctx->cull_block == 0;
   for (int s = 0; s < ns && proj_culled_for_all; ++s)
     proj_culled_for_all = A.s[s].moving.lane_xy != nullptr && A.s[s].moving.lane_bounds != nullptr && A.s[s].moving.block_bounds != nullptr;
   A.units_off = 0; A.cull_keep = ctx->cull_keep;
@@ -403,8 +401,7 @@ int AlignBatch::lay_out_lds() {
   nn_lds_for_all = false;
   if (A.nn_lds_points > 0 && ctx->nn_lds_only && !b->moving[0]->count_pending && !b->fixed[0]->count_pending) {
     const lsm2d_cloudset* f = b->fixed[0]; const lsm2d_cloudset* m = b->moving[0];
-    long long mf = 0, mn = 0x7fffffff;
-    for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > mf) mf = f->h_count[c];
+    const long long mf = max_cloud_count(f); long long mn = 0x7fffffff;
     for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] < mn) mn = m->h_count[c];
     nn_lds_for_all = m->n_clouds > 0 && mf < 4 * mn;
   }
@@ -423,14 +420,13 @@ int AlignBatch::lay_out_lds() {
   A.pair_mov_cap = (int) (lds_pair0 + lds_mov) + 512 <= ctx->max_dyn_lds ? kPairMovCap : 0;
   // ... and the fixed clouds (sizes the host knows, or upper bounds of sizes only the device knows: the kernel compares the real ones)
   max_fixed_rows = 0;
-  for (int s = 0; s < ns; ++s) { const lsm2d_cloudset* f = b->fixed[s]; for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > max_fixed_rows) max_fixed_rows = f->h_count[c]; }
+  for (int s = 0; s < ns; ++s) max_fixed_rows = std::max(max_fixed_rows, max_cloud_count(b->fixed[s]));
   max_fixed_rows = (max_fixed_rows + 63) & ~63;
   lds_fix = (size_t) ns * (size_t) max_fixed_rows * sizeof(float4);
   A.pair_fix_cap = max_fixed_rows <= 4096 && (int) (lds_pair0 + (A.pair_mov_cap ? lds_mov : 0) + lds_fix) + 512 <= ctx->max_dyn_lds ? max_fixed_rows : 0;
   lds_pair = lds_pair0 + (A.pair_mov_cap ? lds_mov : 0) + (A.pair_fix_cap ? lds_fix : 0);
   // ("sum_order" 1: the latency kernel's reference-order form, k_align_pair<true>, for the calls pair_order_ok admits; the others take k_align_seq)
-  use_pair = pair_order_ok(ctx, n) && !use_split && ctx->align_path != 1 && (ns == 1 || ns == 2) && has_proj && !has_nn && !has_dist && !has_kd &&
-                        (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0 && (int) lds_pair + 512 <= ctx->max_dyn_lds;
+  use_pair = pair_eligible && !use_split && (int) lds_pair + 512 <= ctx->max_dyn_lds;
   return LSM2D_SUCCESS;
 }
 
@@ -533,7 +529,7 @@ int AlignBatch::make_placement() {
   // a culled batch of about one dispatch round, two launches: iteration 0 anywhere (k_first_iteration), then the rest placed by what iteration 1's lists hold
 #ifdef LSM2D_EXPERIMENTS
   const bool two_stage = !use_split && !use_pair && !zero_copy && A.cull && ctx->balance && ctx->two_stage && n > 256 && n <= 1024 && proj_culled_for_all &&
-                         has_proj && !has_nn && !has_dist && !has_kd && ap->max_iterations >= 4;
+                         proj_only && ap->max_iterations >= 4;
   if (two_stage) {
     int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work); int32_t* d_order = (int32_t*) ((char*) L->d_scratch + o_order);
     const unsigned long long shape = ((unsigned long long) (unsigned) n << 32) ^ ((unsigned long long) lds << 8) ^ 6ull;
@@ -683,7 +679,7 @@ int AlignBatch::launch() {
     HIPCHK(ctx, hipMemsetAsync(SA.phase, 0, sizeof(int32_t) * 3 * (size_t) n, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(SA.pose, A.init_pose, sizeof(float) * 3 * (size_t) n, hipMemcpyDeviceToDevice, ctx->stream));
     int max_fixed = 0;
-    for (int s = 0; s < ns; ++s) { const lsm2d_cloudset* f = b->fixed[s]; for (int c = 0; c < f->n_clouds; ++c) if (f->h_count[c] > max_fixed) max_fixed = f->h_count[c]; }
+    for (int s = 0; s < ns; ++s) max_fixed = std::max(max_fixed, max_cloud_count(b->fixed[s]));
     auto chunks_for = [&](int max_points) {
       int c = (max_points / 2 + 2047) / 2048;                 // >= 4 pairs per thread and chunk
       const int budget = 2048 / (n * ns) > 1 ? 2048 / (n * ns) : 1;
@@ -915,8 +911,7 @@ extern "C" int lsm2d_align_batch_pairs(lsm2d_context* ctx, const lsm2d_aligner_p
     const lsm2d_cloudset* m = b->moving[s];
     if (!m || !b->fixed[s]) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch_pairs: cloud set missing");
     long long need = 0;
-    if (b->slices[s].finder == LSM2D_FINDER_PROJECTIVE) need = b->slices[s].projector.canvas_cols;
-    else { const int rc0 = resolve_count(m); if (rc0) return rc0; for (int c = 0; c < m->n_clouds; ++c) if (m->h_count[c] > need) need = m->h_count[c]; }
+    { const int rc0 = find_batch_need(&b->slices[s], m, &need); if (rc0) return rc0; }
     if (need > pair_capacity) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "align_batch_pairs: pair_capacity below a slice's largest possible correspondence vector");
   }
   std::vector<float> last_pose((size_t) 3 * (size_t) (n > 0 ? n : 1));

@@ -1,6 +1,17 @@
 // lsm2d_capi_finder.inc -- plugin interface #1 (CorrespondenceFinder_::compute for the four finder kinds) and the factor over a correspondence vector.
 // Part of lsm2d_capi.hip (included there); not a translation unit of its own.
 // ---- plugin interface #1 ---------------------------------------------------------------------------------
+static bool is_point_query(int finder) { return finder == LSM2D_FINDER_NN || finder == LSM2D_FINDER_DISTMAP || finder == LSM2D_FINDER_KDTREE; }
+
+// A point-query finder's reach checked and the fixed set's search structure built (or found) for it: it covers every cloud of the set.  `fixed_dev`: the
+// set's device view, which gets the structure.  `bad_distance`: the caller's message for a reach that is not > 0.
+static int prepare_point_query(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, CloudDev& fixed_dev, const char* bad_distance) {
+  if (sp->finder != LSM2D_FINDER_DISTMAP && !(sp->max_distance > 0.0f)) return fail(ctx, LSM2D_BAD_ARGUMENT, bad_distance);
+  return sp->finder == LSM2D_FINDER_DISTMAP ? ensure_distmap(ctx, fixed, sp->max_distance, sp->resolution, &fixed_dev.dist)
+       : sp->finder == LSM2D_FINDER_KDTREE  ? ensure_kdtree(ctx, fixed, sp->kd_max_leaf_range, sp->kd_min_leaf_points, &fixed_dev.kd)
+                                            : ensure_grid(ctx, fixed, sp->max_distance, &fixed_dev.grid);
+}
+
 // inl_tau > 0: only the pairs whose factor is an inlier under a Cauchy robustifier of that threshold (FindArgs::inl_tau)
 static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed,
                                      int32_t fi, const lsm2d_cloudset* moving, int32_t mi, const float pose[3],
@@ -11,16 +22,12 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
   { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
   { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
   *out_n = 0;
-  if (sp->finder == LSM2D_FINDER_NN || sp->finder == LSM2D_FINDER_DISTMAP || sp->finder == LSM2D_FINDER_KDTREE) {
-    if (sp->finder != LSM2D_FINDER_DISTMAP && !(sp->max_distance > 0.0f)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences: max_distance must be > 0");
+  if (is_point_query(sp->finder)) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     FindNNArgs N;
     N.fixed = cloud_dev(fixed, nullptr); N.moving = cloud_dev(moving, nullptr); N.fc = fi; N.mc = mi;
     N.use_distmap = sp->finder == LSM2D_FINDER_DISTMAP; N.use_kd = sp->finder == LSM2D_FINDER_KDTREE;
-    int rc = N.use_distmap ? ensure_distmap(ctx, fixed, sp->max_distance, sp->resolution, &N.fixed.dist)
-           : N.use_kd      ? ensure_kdtree(ctx, fixed, sp->kd_max_leaf_range, sp->kd_min_leaf_points, &N.fixed.kd)
-                           : ensure_grid(ctx, fixed, sp->max_distance, &N.fixed.grid);
-    if (rc) return rc;
+    int rc = prepare_point_query(ctx, sp, fixed, N.fixed, "find_correspondences: max_distance must be > 0"); if (rc) return rc;
     const size_t nm = (size_t) moving->h_count[mi], bytes = nm * 8 + 16;
     N.max_distance = sp->max_distance; N.normal_cos = sp->normal_cos; N.T = make_iso(pose); N.inl_tau = inl_tau;
     N.nn_group = fixed->h_count[fi] >= 4 * (int64_t) moving->h_count[mi] ? kNNGroup : 1;     // dense fixed cloud: cooperative search
@@ -117,20 +124,15 @@ static int find_batch_impl(lsm2d_context* ctx, const lsm2d_slice_params* sp, con
   // sizes only the device knows, pending unpacking / preprocessing: once for the whole batch
   { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
   { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
-  const bool point_query = sp->finder == LSM2D_FINDER_NN || sp->finder == LSM2D_FINDER_DISTMAP || sp->finder == LSM2D_FINDER_KDTREE;
+  const bool point_query = is_point_query(sp->finder);
   if (!point_query && sp->finder != LSM2D_FINDER_PROJECTIVE) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: finder not supported");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   FindBatchArgs A; FindNNBatchArgs N;
   size_t lds = 0;
   if (point_query) {
-    if (sp->finder != LSM2D_FINDER_DISTMAP && !(sp->max_distance > 0.0f)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: max_distance must be > 0");
     N.fixed = cloud_dev(fixed, nullptr); N.moving = cloud_dev(moving, nullptr);
     N.use_distmap = sp->finder == LSM2D_FINDER_DISTMAP; N.use_kd = sp->finder == LSM2D_FINDER_KDTREE;
-    // the set's search structure covers every cloud of it: built (or found) once
-    const int rc = N.use_distmap ? ensure_distmap(ctx, fixed, sp->max_distance, sp->resolution, &N.fixed.dist)
-                 : N.use_kd      ? ensure_kdtree(ctx, fixed, sp->kd_max_leaf_range, sp->kd_min_leaf_points, &N.fixed.kd)
-                                 : ensure_grid(ctx, fixed, sp->max_distance, &N.fixed.grid);
-    if (rc) return rc;
+    const int rc = prepare_point_query(ctx, sp, fixed, N.fixed, "find_correspondences_batch: max_distance must be > 0"); if (rc) return rc;
     N.max_distance = sp->max_distance; N.normal_cos = sp->normal_cos; N.inl_tau = inl_tau; N.pair_capacity = capacity;
   } else {
     if (!make_projk(sp->projector, &A.proj)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: bad projector");
@@ -188,7 +190,7 @@ static int find_batch_need(const lsm2d_slice_params* sp, const lsm2d_cloudset* m
   *need = 0;
   if (sp->finder == LSM2D_FINDER_PROJECTIVE) { *need = sp->projector.canvas_cols; return LSM2D_SUCCESS; }
   const int rc0 = resolve_count(moving); if (rc0) return rc0;
-  for (int c = 0; c < moving->n_clouds; ++c) if (moving->h_count[c] > *need) *need = moving->h_count[c];
+  *need = max_cloud_count(moving);
   return LSM2D_SUCCESS;
 }
 

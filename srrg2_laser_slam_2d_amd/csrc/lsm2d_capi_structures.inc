@@ -1,5 +1,13 @@
 // lsm2d_capi_structures.inc -- parameter packing and what a set caches per finder: the NN grid, the KD-tree (level loop, one-launch and LDS forms), the lane-chunked copy with its circles, AoS rows, tile bounds, the distance map.
 // Part of lsm2d_capi.hip (included there); not a translation unit of its own.
+static bool valid_cloud_index(const lsm2d_cloudset* cs, int32_t i) { return cs && i >= 0 && i < cs->n_clouds; }
+static bool valid_cloud_index_fwd(const lsm2d_cloudset* cs, int32_t i) { return valid_cloud_index(cs, i); }
+// the set's largest cloud, in points (sizes the host knows, or upper bounds of sizes only the device knows); 0 for a set without clouds
+static int max_cloud_count(const lsm2d_cloudset* cs) {
+  int mx = 0;
+  for (int c = 0; c < cs->n_clouds; ++c) if (cs->h_count[c] > mx) mx = cs->h_count[c];
+  return mx;
+}
 // ---- parameter packing -------------------------------------------------------------------------------
 // Depths are compared through r2: sqrtf is correctly rounded and monotone, so
 //   rmin <= sqrtf(r2)  <=>  r2 >= r2lo,  r2lo = smallest float whose sqrtf reaches rmin   (same for rmax).
@@ -471,7 +479,7 @@ static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float ma
     if (total > (1ll << 33)) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "distmap: more than 8 Gi pixels in one set");
   }
   // scatter build (every point stamps its disc, k_distmap_stamp) whenever (d2, index) packs into 31 bits; else the gather build
-  int max_pts = 1; for (int c = 0; c < nc; ++c) if (cs->h_count[c] > max_pts) max_pts = cs->h_count[c];
+  const int max_pts = std::max(1, max_cloud_count(cs));
   int gbits = 1; while (gbits < 31 && (1ll << gbits) < (long long) max_pts) ++gbits;
   const bool scatter = ctx->distmap_build != 1 && R <= 511 && (((long long) R * R + 1) << gbits) <= (1ll << 31);
   for (auto& m : meta) { m.gbits = scatter ? gbits : 31; m.gmask = scatter ? (int32_t) ((1u << gbits) - 1u) : 0x7fffffff; }
@@ -527,8 +535,6 @@ static void inverse_host(const float a[3], float out[3]) {   // (R,t)^-1 = (R^T,
   out[1] = -(fmaf(-s, a[0], c * a[1]));
   out[2] = wrap_host(-a[2]);
 }
-static bool valid_cloud_index(const lsm2d_cloudset* cs, int32_t i) { return cs && i >= 0 && i < cs->n_clouds; }
-static bool valid_cloud_index_fwd(const lsm2d_cloudset* cs, int32_t i) { return valid_cloud_index(cs, i); }
 static void compose_host(const float a[3], const float b[3], float out[3]) {   // v2t(a) * v2t(b)
   float s, c; sincos_fixed(a[2], s, c);
   out[0] = fmaf(c, b[0], fmaf(-s, b[1], a[0]));

@@ -187,8 +187,6 @@ LSM2D_DEV void add_prior_inline(const PriorDev& Pz, const float pose[3], float H
 // k_align (64 VGPRs) and the split path call it: rarely taken, and out of the register allocation of their loops
 __device__ __noinline__ void add_prior(const PriorDev& Pz, const float pose[3], float H[9], float b[3]) { add_prior_inline(Pz, pose, H, b); }
 
-LSM2D_DEV int block_compact_pos(bool flag, int* s_tot, int parity, int& base, int tid, int nwaves);      // (defined with the mapping kernels below)
-
 // kHasProj / kHasNN: which finders the batch's slices use -- the unused one is compiled out so the
 // projective hot loop does not carry the NN path's register pressure (and vice versa).
 // kHasDist: a slice uses the distance-map finder (compiled out otherwise so the NN search keeps its registers).

@@ -28,39 +28,6 @@ __global__ __launch_bounds__(512) void k_project_split(const ProjectSplitArgs A)
   for (int i = tid; i < P.cols; i += 512) { const u64 k = can[i]; if (k != kEmptyCell) atomicMin(&A.gcanvas[i], k); }
 }
 
-LSM2D_DEV int block_compact_offset(bool flag, int* s_wave_tot, int* s_base, int tid, int nwaves) {
-  // order-preserving position of this thread's element among the flagged ones (all threads must call)
-  const int lane = tid & 63, wave = tid >> 6;
-  const u64 bal = __ballot(flag);
-  const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) s_wave_tot[wave] = __popcll(bal);
-  __syncthreads();
-  int before = *s_base, total = 0;
-  for (int w = 0; w < nwaves; ++w) { const int t = s_wave_tot[w]; if (w < wave) before += t; total += t; }
-  __syncthreads();
-  if (tid == 0) *s_base += total;
-  __syncthreads();
-  return before + prefix;
-}
-
-// the same with ONE barrier per call: the per-wave totals alternate between two buffers (`parity`: 0, 1, 0, ... from call to call; the
-// barrier of call i + 1 separates the reads of call i from the writes of call i + 2), and every thread keeps the running base itself
-// (`base`, the same value in all threads; in: flagged elements so far, out: including this call's)
-LSM2D_DEV int block_compact_pos(bool flag, int* s_tot /* [2][nwaves] */, int parity, int& base, int tid, int nwaves) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const u64 bal = __ballot(flag);
-  const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
-  int* t = s_tot + parity * nwaves;
-  if (lane == 0) t[wave] = __popcll(bal);
-  __syncthreads();
-  int before = base, total = 0;
-  for (int w = 0; w < nwaves; ++w) { const int v = t[w]; if (w < wave) before += v; total += v; }
-  // the running base is the same in every lane: say so (a count that came out of LDS reads is a per-lane value to the compiler, and loops
-  // bounded by it compile to per-lane forms -- the preprocessor's window walks ran 58 % slower over a batch before this line)
-  base = __builtin_amdgcn_readfirstlane(base + total);
-  return before + prefix;
-}
-
 // SceneClipperProjective2D::compute tail (mapping/scene_clipper_projective_2d.cpp:53-63): filled cells in ascending
 // column -> transformed point (sensor frame), then moved to the robot frame by sensor_in_robot
 struct ClipEmitArgs {

@@ -1,4 +1,4 @@
-// lsm2d_k_split_finder.h -- the split aligner path (k_split_project / k_split_finish), the finder-level kernels (CorrespondenceFinder_::compute), the projector and the factor over a correspondence vector.
+// lsm2d_k_split_finder.h -- the split aligner path (k_split_project / k_split_finish), the projector and the factor over a correspondence vector (the finder-level kernels: lsm2d_k_finder.h).
 // Part of lsm2d_kernels.h (included there, inside namespace lsm2d, in this order); not a translation unit of its own.
 // ---- split path: the same alignment spread over many workgroups -------------------------------------------------
 // For a handful of alignments against a big cloud one workgroup per alignment leaves the chip empty, so each iteration
@@ -172,180 +172,6 @@ __global__ __launch_bounds__(kAlignBlock) void k_split_finish(const SplitArgs S)
       if (A.out_H) for (int k = 0; k < 9; ++k) A.out_H[9 * a + k] = S.it == 0 && !s_active ? 0.0f : S.H_last[9 * a + k];
       if (A.out_its) A.out_its[a] = S.it + 1;
     }
-  }
-}
-
-// ---- finder-level: one (fixed, moving, pose) -> pairs in ascending column ------------------------
-struct FindArgs {
-  CloudDev fixed, moving; int32_t fc, mc;
-  ProjK proj; float point_distance, normal_cos;
-  Iso T;
-  int32_t* out_pairs;  // [cols][2]
-  int32_t* out_count;
-  const u64* fcan_global; const u64* mcan_global;      // a map-sized cloud's canvas, projected over many workgroups beforehand (k_project_split), or nullptr
-  float inl_tau;         // > 0: only pairs whose factor is an inlier under a Cauchy robustifier of this threshold (chi^2 < tau) are emitted -- the aligner's
-                         // keep_only_inlier_correspondences (lsm2d_align_batch_pairs); 0: every pair
-};
-
-__global__ __launch_bounds__(kFindBlock) void k_find_projective(const FindArgs A) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  u64* mcan = reinterpret_cast<u64*>(smem);
-  u64* fcan = mcan + A.proj.cols;
-  __shared__ int s_wave_tot[kFindBlock / 64];
-  __shared__ int s_base;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < A.proj.cols; i += kFindBlock) { mcan[i] = kEmptyCell; fcan[i] = kEmptyCell; }
-  if (tid == 0) s_base = 0;
-  __syncthreads();
-  const Iso ident = {1.0f, 0.0f, 0.0f, 0.0f};
-  const int fbase = A.fixed.start[A.fc], mbase = A.moving.start[A.mc];
-  if (A.fcan_global) { for (int i = tid; i < A.proj.cols; i += kFindBlock) fcan[i] = A.fcan_global[i]; }
-  else project_cloud(A.fixed.xy + fbase, A.fixed.count[A.fc], ident, A.proj, fcan, tid, kFindBlock);
-  if (A.mcan_global) { for (int i = tid; i < A.proj.cols; i += kFindBlock) mcan[i] = A.mcan_global[i]; }
-  else project_cloud(A.moving.xy + mbase, A.moving.count[A.mc], A.T, A.proj, mcan, tid, kFindBlock);
-  __syncthreads();
-  SliceDev S; S.point_distance = A.point_distance; S.normal_cos = A.normal_cos;
-  const int lane = tid & 63, wave = tid >> 6;
-  for (int c0 = 0; c0 < A.proj.cols; c0 += kFindBlock) {
-    const int col = c0 + tid;
-    int fi = -1, mi = -1; float2 nf, nm; bool ok = false;
-    if (col < A.proj.cols) ok = match_bin(fcan[col], mcan[col], S, A.T, A.fixed.nrm + fbase, A.moving.nrm + mbase, fi, mi, nf, nm);
-    if (ok && A.inl_tau > 0.0f) ok = pair_chi(A.T, A.fixed.xy[fbase + fi], nf, A.moving.xy[mbase + mi], nm) < A.inl_tau;
-    // order-preserving compaction: ballot prefix inside the wave, wave totals through LDS
-    const u64 bal = __ballot(ok);
-    const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int before = s_base, total = 0;
-    for (int w = 0; w < kFindBlock / 64; ++w) { const int t = s_wave_tot[w]; if (w < wave) before += t; total += t; }
-    if (ok) { A.out_pairs[2 * (before + prefix)] = fi; A.out_pairs[2 * (before + prefix) + 1] = mi; }
-    __syncthreads();
-    if (tid == 0) s_base += total;
-    __syncthreads();
-  }
-  if (tid == 0) *A.out_count = s_base;
-}
-
-// ---- finder-level NN: pairs in ascending moving index (correspondence_finder_kd_tree_2d.cpp:12-27) ------
-struct FindNNArgs {
-  CloudDev fixed, moving; int32_t fc, mc; int32_t use_distmap; int32_t use_kd;      // at most one of the two set; neither: the exact grid search
-  float max_distance, normal_cos; Iso T; int32_t nn_group;
-  int32_t* out_pairs; int32_t* out_count;
-  int32_t* match; int32_t* block_count;      // k_find_nn_multi: per query the matched fixed index or -1; pairs per workgroup
-  float inl_tau;                              // as FindArgs::inl_tau
-};
-
-__global__ __launch_bounds__(kFindBlock) void k_find_nn(const FindNNArgs A) {
-  __shared__ int s_wave_tot[kFindBlock / 64];
-  __shared__ int s_base;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_base = 0;
-  __syncthreads();
-  const int fbase = A.fixed.start[A.fc], mbase = A.moving.start[A.mc], n = A.moving.count[A.mc];
-  GridMeta g; DistMeta dm;
-  const int32_t* cst = nullptr; const int32_t* sidx = nullptr; const float2* sxy = nullptr;
-  const KdNode* knd = nullptr;
-  if (A.use_distmap) dm = A.fixed.dist.meta[A.fc];
-  else if (A.use_kd) { knd = A.fixed.kd.nodes + A.fixed.kd.meta[A.fc].node_base; sxy = A.fixed.kd.leaf_xy + fbase; sidx = A.fixed.kd.leaf_idx + fbase; }
-  else {
-    g = A.fixed.grid.meta[A.fc]; cst = A.fixed.grid.cell_start + g.cell_base;
-    sidx = A.fixed.grid.sorted_idx + fbase; sxy = A.fixed.grid.sorted_xy + fbase;
-  }
-  const float md2 = A.max_distance * A.max_distance;
-  const int group = (A.use_distmap || A.use_kd) ? 1 : A.nn_group, sub = tid & (group - 1);
-  const int per_step = kFindBlock / group;
-  auto query = [&](float qx, float qy) {
-    if (A.use_kd) return kd_query(knd, sxy, sidx, qx, qy, md2);
-    return group == kNNGroup ? nn_query<kNNGroup>(g, cst, sidx, sxy, qx, qy, A.max_distance, md2, sub)
-                             : nn_query<1>(g, cst, sidx, sxy, qx, qy, A.max_distance, md2, sub);
-  };
-  for (int j0 = 0; j0 < n; j0 += per_step) {
-    const int j = j0 + tid / group;
-    int best = -1; bool ok = false;
-    if (j < n) {
-      const float2 pm = A.moving.xy[mbase + j];
-      float qx, qy; xf_point(A.T, pm.x, pm.y, qx, qy);
-      best = A.use_distmap ? distmap_lookup(dm, A.fixed.dist.parent, qx, qy) : query(qx, qy);
-      if (best >= 0 && sub == 0) {
-        const float2 nm = A.moving.nrm[mbase + j], nf = A.fixed.nrm[fbase + best];
-        float nqx, nqy; xf_normal(A.T, nm.x, nm.y, nqx, nqy);
-        ok = !(__builtin_fmaf(nqx, nf.x, nqy * nf.y) < A.normal_cos);
-        if (ok && A.inl_tau > 0.0f) ok = pair_chi(A.T, A.fixed.xy[fbase + best], nf, pm, nm) < A.inl_tau;
-      }
-    }
-    // lanes are in ascending query order (tid / group), so the ballot compaction keeps ascending moving index
-    const u64 bal = __ballot(ok);
-    const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int before = s_base, total = 0;
-    for (int w = 0; w < kFindBlock / 64; ++w) { const int t = s_wave_tot[w]; if (w < wave) before += t; total += t; }
-    if (ok) { A.out_pairs[2 * (before + prefix)] = best; A.out_pairs[2 * (before + prefix) + 1] = j; }
-    __syncthreads();
-    if (tid == 0) s_base += total;
-    __syncthreads();
-  }
-  if (tid == 0) *A.out_count = s_base;
-}
-
-// The same finder over many workgroups (more queries than one workgroup takes in one trip: a map-sized moving cloud against a scan's
-// structure is 98 trips of one workgroup otherwise).  Workgroup b owns the queries [b * per_step, (b + 1) * per_step), ascending.
-// Phase 0: search, normal gate, match[j] = fixed index or -1, pairs per workgroup.  Phase 1 (a second launch of the same shape): every
-// workgroup adds up the counts in front of it, ranks its own pairs by ballot and writes them -- ascending moving index, as the
-// reference emits them (correspondence_finder_kd_tree_2d.cpp:12-27, correspondence_finder_nn_2d.cpp:63-80).
-template <int kPhase>
-__global__ __launch_bounds__(kFindBlock) void k_find_nn_multi(const FindNNArgs A) {
-  __shared__ int s_wave_tot[kFindBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = A.moving.count[A.mc];
-  const int group = (A.use_distmap || A.use_kd) ? 1 : A.nn_group, sub = tid & (group - 1);
-  const int per_step = kFindBlock / group;
-  const int j = blockIdx.x * per_step + tid / group;
-  if (kPhase == 0) {
-    const int fbase = A.fixed.start[A.fc], mbase = A.moving.start[A.mc];
-    int best = -1; bool ok = false;
-    if (j < n) {
-      const float2 pm = A.moving.xy[mbase + j];
-      float qx, qy; xf_point(A.T, pm.x, pm.y, qx, qy);
-      if (A.use_distmap) best = distmap_lookup(A.fixed.dist.meta[A.fc], A.fixed.dist.parent, qx, qy);
-      else if (A.use_kd) {
-        best = kd_query(A.fixed.kd.nodes + A.fixed.kd.meta[A.fc].node_base, A.fixed.kd.leaf_xy + fbase, A.fixed.kd.leaf_idx + fbase, qx, qy, A.max_distance * A.max_distance);
-      } else {
-        const GridMeta g = A.fixed.grid.meta[A.fc];
-        const int32_t* cst = A.fixed.grid.cell_start + g.cell_base; const int32_t* sidx = A.fixed.grid.sorted_idx + fbase; const float2* sxy = A.fixed.grid.sorted_xy + fbase;
-        const float md2 = A.max_distance * A.max_distance;
-        best = group == kNNGroup ? nn_query<kNNGroup>(g, cst, sidx, sxy, qx, qy, A.max_distance, md2, sub) : nn_query<1>(g, cst, sidx, sxy, qx, qy, A.max_distance, md2, sub);
-      }
-      if (best >= 0 && sub == 0) {
-        const float2 nm = A.moving.nrm[mbase + j], nf = A.fixed.nrm[fbase + best];
-        float nqx, nqy; xf_normal(A.T, nm.x, nm.y, nqx, nqy);
-        ok = !(__builtin_fmaf(nqx, nf.x, nqy * nf.y) < A.normal_cos);
-        if (ok && A.inl_tau > 0.0f) ok = pair_chi(A.T, A.fixed.xy[fbase + best], nf, pm, nm) < A.inl_tau;
-      }
-      if (sub == 0) A.match[j] = ok ? best : -1;
-    }
-    const u64 bal = __ballot(ok);
-    if (lane == 0) s_wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    if (tid == 0) { int t = 0; for (int w = 0; w < kFindBlock / 64; ++w) t += s_wave_tot[w]; A.block_count[blockIdx.x] = t; }
-  } else {
-    __shared__ int s_before;
-    if (tid == 0) s_before = 0;
-    __syncthreads();
-    int mine = 0;
-    for (int b = tid; b < (int) blockIdx.x; b += kFindBlock) mine += A.block_count[b];
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if (lane == 0 && mine) atomicAdd(&s_before, mine);
-    const int best = (j < n && sub == 0) ? A.match[j] : -1;
-    const bool ok = best >= 0;
-    const u64 bal = __ballot(ok);
-    const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int before = s_before, total = 0;
-    for (int w = 0; w < kFindBlock / 64; ++w) { const int t = s_wave_tot[w]; if (w < wave) before += t; total += t; }
-    if (ok) { A.out_pairs[2 * (before + prefix)] = best; A.out_pairs[2 * (before + prefix) + 1] = j; }
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *A.out_count = s_before + total;
   }
 }
 

@@ -7,8 +7,9 @@
 //                      accumulates the plane-to-plane factor (octave/solver/nicp_post.m:4-26,69-90) in
 //                      registers, reduces with wave shuffles + one LDS hop, and lane 0 solves the 3x3
 //                      system and right-updates the pose -- no host round trip, no global atomics.
-//   k_find_projective  CorrespondenceFinderProjective2f::compute for one (fixed, moving, pose): ordered pairs.
-//   k_find_*_batch     the same finders for n_items (fixed, moving, pose) triples in one launch, a workgroup per item (lsm2d_k_find_batch.h).
+//   k_find_projective  CorrespondenceFinderProjective2f::compute for one (fixed, moving, pose): ordered pairs (lsm2d_k_finder.h).
+//   k_find_nn[_multi]  the point-query finders (exact grid NN, KD-tree, distance map) for one (fixed, moving, pose): pairs in ascending moving index.
+//   k_find_*_batch     the same finders for n_items (fixed, moving, pose) triples in one launch, a workgroup per item: the single kernels' bodies.
 //   k_project_canvas   PointNormal2fProjectorPolar::compute: source index / depth / transformed point per column.
 //   k_linearize_*      SE2Plane2PlaneErrorFactor over a correspondence vector (two-stage deterministic reduce).
 //   k_repack_cloud     AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
@@ -61,7 +62,7 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_placement.h"
 #include "lsm2d_k_align_pair.h"
 #include "lsm2d_k_split_finder.h"
-#include "lsm2d_k_find_batch.h"
+#include "lsm2d_k_finder.h"
 #include "lsm2d_k_mapping.h"
 #include "lsm2d_k_layout.h"
 

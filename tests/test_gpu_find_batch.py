@@ -142,8 +142,9 @@ def test_point_query_batch_both_roles(ctx, po, fx, kind):
     # one batch, both search forms: items against m (6000 >= 4 x 1081) search cooperatively, items against small (1000) do not
     two = _multi(ctx, [fx.m, fx.small])
     _run_and_compare(po, osp, f, two, [fx.m, fx.small], np.int32([0, 1, 1, 0, 0, 1]), fx.scan_set, fx.scans, None, fx.inv, tag=(kind, "mixed group widths"))
-    # moving clouds at the trip boundaries of both group widths (1024 and 256 queries per trip)
-    sizes = [0, 1, 255, 256, 257, 1023, 1024, 1025]
+    # moving clouds at the trip boundaries of both group widths (1024 and 256 queries per trip); from three trips on (2049, 3073 with one lane per query) the
+    # single call spreads the queries over many workgroups (k_find_nn_multi): all three kernels that share the match, against each other and the oracle
+    sizes = [0, 1, 255, 256, 257, 1023, 1024, 1025, 2049, 3073]
     prefixes = [np.ascontiguousarray(fx.m[:k]) for k in sizes]
     pset = _multi(ctx, prefixes)
     poses = np.tile(fx.x0[0], (len(sizes), 1))
