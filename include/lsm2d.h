@@ -49,7 +49,9 @@ extern "C" {
                              (0.7.0, number unchanged: additions only) + lsm2d_cloudset_create_reserved_many / lsm2d_cloudset_clear_clouds, lsm2d_clip_scene_batch,
                                     lsm2d_merge_scene_batch (N independent trackers per call: one workgroup per tracker, the single-tracker calls' bits);
                              (0.7.1, number unchanged: an addition only) + lsm2d_find_correspondences_batch (plugin interface #1 for n_items triples in one
-                                    launch, the single call's bits); lsm2d_align_batch_pairs of more than one alignment derives its pairs through it */
+                                    launch, the single call's bits); lsm2d_align_batch_pairs of more than one alignment derives its pairs through it;
+                             (0.7.2, number unchanged: an addition only) + lsm2d_linearize_batch (the factor over n_items correspondence vectors in one
+                                    launch, the single call's bits in both orders of summation) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -414,6 +416,30 @@ int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* slice,
                     const lsm2d_cloudset* moving, int32_t moving_index,
                     const lsm2d_correspondence* pairs, int32_t n_pairs, const float pose[3],
                     float out_H[9], float out_b[3], lsm2d_iteration_stats* out_stats);
+/* The same factor over n_items correspondence vectors in ONE launch (two in the tree order): what a caller with n_items pose hypotheses needs after
+ * lsm2d_find_correspondences_batch -- the candidate loop of MultiLoopDetectorBruteForce2D (MULTI.json:964-986) reads exactly these statistics, and a
+ * host with its own solver gets H AND b at the poses it chooses (registration/aligner_slice_processor_laser_2d.h:4,8; octave/solver/nicp_post.m:4-26,69-90).
+ * Item i linearises pairs[i * pair_capacity .. + n_pairs[i]) between cloud fixed_index[i] of `fixed` and cloud moving_index[i] of `moving` at poses[i];
+ * pairs / pair_capacity / n_pairs are laid out as lsm2d_find_correspondences_batch writes them, so its output feeds this call untouched.  Only the first
+ * n_pairs[i] entries of a row are read or checked: the tails may be uninitialised.
+ * Per item H, b, the counts, the chi^2 sums and the pair digest (slice 0) are those of lsm2d_linearize, bit for bit, in both orders of summation (option
+ * "sum_order"): the single call's kernels and the batch's share their device functions and the item keeps the single call's launch shape.
+ * Indices: the rule of lsm2d_batch (NULL: cloud i, or cloud 0 of a one-cloud set; the set then holds 1 or n_items clouds; indices may repeat).  Sets in any
+ * state are read; counts are resolved and pending work is flushed once for the whole batch (one wait at most: the checks need the sizes).
+ * n_items == 0 is a successful no-op; n_pairs[i] == 0 gives zeros and n_correspondences == 0.
+ * Checked before anything is launched or written: n_pairs[i] outside [0, pair_capacity] and a pair index outside its item's clouds are
+ * LSM2D_BAD_ARGUMENT, and lsm2d_last_error names the item.
+ * The pairs pass through a device buffer of fixed size (2^21 pairs, an item counting with its pair_capacity; at most 65536 items): a batch beyond it runs as
+ * several launches over consecutive items, one wait each -- the items are independent, no bit changes.  With one batch in flight (lsm2d_align_batch_begin) the call works;
+ * with two it is refused (LSM2D_BAD_ARGUMENT).  "kernel_timing" / lsm2d_last_kernel_ms cover the (last) launch as they cover lsm2d_linearize's. */
+int lsm2d_linearize_batch(lsm2d_context* ctx, const lsm2d_slice_params* slice,
+                          const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                          const lsm2d_cloudset* moving, const int32_t* moving_index,
+                          int32_t n_items,
+                          const lsm2d_correspondence* pairs /* [n_items][pair_capacity] */, int32_t pair_capacity,
+                          const int32_t* n_pairs /* [n_items] */, const float* poses /* [n_items][3] */,
+                          float* out_H /* [n_items][9] */, float* out_b /* [n_items][3] */,
+                          lsm2d_iteration_stats* out_stats /* [n_items] or NULL */);
 
 /* ---- plugin interface #2: MultiAligner2D::compute, batched --------------------------------------
  * Replaces aligner->setFixed / setMoving / setMovingInFixed / compute / movingInFixed /

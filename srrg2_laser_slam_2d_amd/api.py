@@ -766,6 +766,42 @@ def linearize(ctx: Context, slice_params: SliceParams, fixed, moving, correspond
     return H.reshape(3, 3), b, st
 
 
+def linearize_batch(ctx: Context, slice_params: SliceParams, fixed, moving, correspondences, poses, fixed_index=None, moving_index=None):
+    """``linearize`` for ``len(poses)`` independent (fixed, moving, correspondence vector, pose) items in one launch (lsm2d_linearize_batch): item ``i`` is
+    between cloud ``fixed_index[i]`` of the set ``fixed`` and cloud ``moving_index[i]`` of the set ``moving`` (None: cloud ``i``, or the only cloud of a
+    one-cloud set) at ``poses[i]``.  ``correspondences``: the list of int32 ``[k, 2]`` arrays ``finder.compute_batch`` returns, or a tuple
+    ``(padded [n, cap, 2], counts [n])`` as lsm2d_find_correspondences_batch writes them (only the first ``counts[i]`` pairs of a row are read).
+    Returns ``(H [n, 3, 3], b [n, 3], stats)``, ``stats`` a list of ``n`` IterationStats; per item the bits of ``linearize``."""
+    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
+    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+    n = len(x)
+    if isinstance(correspondences, tuple):
+        padded, cnt = correspondences
+        padded = np.ascontiguousarray(padded, np.int32)
+        cnt = np.ascontiguousarray(cnt, np.int32).reshape(-1)
+        if padded.ndim != 3 or padded.shape[2] != 2 or len(padded) != n or len(cnt) != n:
+            raise ValueError("linearize_batch: padded correspondences must be [n, cap, 2] with n counts, n = len(poses)")
+        cap = padded.shape[1]
+    else:
+        rows = [np.ascontiguousarray(c, np.int32).reshape(-1, 2) for c in correspondences]
+        if len(rows) != n:
+            raise ValueError("linearize_batch: one correspondence vector per pose")
+        cnt = np.array([len(r) for r in rows], np.int32)
+        cap = max(int(cnt.max()) if n else 0, 1)
+        padded = np.empty((max(n, 1), cap, 2), np.int32)
+        for i, r in enumerate(rows):
+            padded[i, : len(r)] = r
+    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
+    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
+    H = np.empty((max(n, 1), 9), np.float32); b = np.empty((max(n, 1), 3), np.float32); st = (IterationStats * max(n, 1))()
+    check(ctx._lib.lsm2d_linearize_batch(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
+                                         mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, padded.ctypes.data_as(C.c_void_p), cap,
+                                         cnt.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p),
+                                         b.ctypes.data_as(C.c_void_p), st),
+          "lsm2d_linearize_batch", ctx.handle)
+    return H[:n].reshape(n, 3, 3), b[:n], [st[i] for i in range(n)]
+
+
 class SceneClipperProjective2D:
     """mapping/scene_clipper_projective_2d.{h,cpp}: keeps what the sensor sees of the local map, at most one point per projector
     column, in the robot frame; ``voxelize_resolution`` > 0 additionally voxelises the clipped cloud (.cpp:36-48; both shipped configs

@@ -273,3 +273,131 @@ extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp,
   }
   return LSM2D_SUCCESS;
 }
+
+// ---- factor for a whole batch ---------------------------------------------------------------------------------------
+// The device room for the pairs of ONE launch of the batched factor, in pairs: the batch finder's.  As there, every item counts with its pair_capacity
+// slots whatever it holds (the rule depends on the arguments' shape alone), so a launch takes kLinBatchPairBudget / pair_capacity items -- at least one, at
+// most kLinBatchMaxItems, which bounds the item table -- and a batch beyond that runs as several launches over consecutive items, each with its own wait.
+// Only the first n_pairs[i] entries of a row travel: they are packed one vector after the other on their way to the staging buffer.
+static constexpr size_t kLinBatchPairBudget = (size_t) 2 << 20;
+static constexpr size_t kLinBatchMaxItems = (size_t) 1 << 16;
+
+static inline int lin_blocks(int32_t n_pairs) { int b = (n_pairs + 255) / 256; return b < 1 ? 1 : (b > 1024 ? 1024 : b); }      // lsm2d_linearize's launch shape
+static inline size_t up256(size_t v) { return (v + 255) & ~(size_t) 255; }
+
+// where a launch's parts lie in the lane's device scratch and (the first three and the results) in its pinned staging
+struct LinBatchLayout {
+  size_t o_wg, o_pairs, up_bytes, o_part, o_dig, o_out, d_bytes, h_out, h_bytes;
+  LinBatchLayout(size_t cnt, size_t blocks, size_t npairs) {
+    o_wg = up256(sizeof(LinItem) * cnt); o_pairs = up256(o_wg + sizeof(int32_t) * blocks); up_bytes = o_pairs + sizeof(lsm2d_correspondence) * npairs;
+    o_part = up256(up_bytes); o_dig = up256(o_part + sizeof(float) * kAccumWords * blocks); o_out = up256(o_dig + sizeof(unsigned long long) * cnt);
+    d_bytes = o_out + sizeof(float) * kLinOutWords * cnt;
+    h_out = up256(up_bytes); h_bytes = h_out + sizeof(float) * kLinOutWords * cnt;
+  }
+};
+
+extern "C" int lsm2d_linearize_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                     const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const lsm2d_correspondence* pairs,
+                                     int32_t pair_capacity, const int32_t* n_pairs, const float* poses, float* out_H, float* out_b, lsm2d_iteration_stats* st) {
+  if (!ctx || !sp || !fixed || !moving || n_items < 0 || pair_capacity < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: bad argument");
+  if (fixed->ctx != ctx || moving->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: cloud set from another (or a destroyed) context");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  if (n_items == 0) return LSM2D_SUCCESS;
+  if (!n_pairs || !poses || !out_H || !out_b) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: null argument");
+  if (!fixed_index && fixed->n_clouds != 1 && fixed->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: fixed set must hold 1 or n_items clouds");
+  if (!moving_index && moving->n_clouds != 1 && moving->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: moving set must hold 1 or n_items clouds");
+  char msg[160];
+  std::vector<int32_t> fc((size_t) n_items), mc((size_t) n_items);
+  for (int32_t i = 0; i < n_items; ++i) {
+    fc[(size_t) i] = fixed_index ? fixed_index[i] : (fixed->n_clouds == 1 ? 0 : i);
+    mc[(size_t) i] = moving_index ? moving_index[i] : (moving->n_clouds == 1 ? 0 : i);
+    if (!valid_cloud_index(fixed, fc[(size_t) i]) || !valid_cloud_index(moving, mc[(size_t) i])) {
+      snprintf(msg, sizeof msg, "linearize_batch: item %d: cloud index out of range", (int) i);
+      return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
+    }
+  }
+  // sizes only the device knows, pending unpacking / preprocessing: once for the whole batch (the validation below needs the sizes)
+  { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
+  { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
+  // every item is checked before anything is launched or written
+  for (int32_t i = 0; i < n_items; ++i) {
+    const int32_t np = n_pairs[i];
+    if (np > 0 && !pairs) return fail(ctx, LSM2D_BAD_ARGUMENT, "linearize_batch: null argument");
+    if (np < 0 || np > pair_capacity) {
+      snprintf(msg, sizeof msg, "linearize_batch: item %d: n_pairs %d outside [0, pair_capacity %d]", (int) i, (int) np, (int) pair_capacity);
+      return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
+    }
+    const lsm2d_correspondence* row = np ? pairs + (size_t) i * (size_t) pair_capacity : nullptr;
+    const int32_t nf = fixed->h_count[fc[(size_t) i]], nm = moving->h_count[mc[(size_t) i]];
+    for (int32_t k = 0; k < np; ++k)
+      if (row[k].fixed_idx < 0 || row[k].fixed_idx >= nf || row[k].moving_idx < 0 || row[k].moving_idx >= nm) {
+        snprintf(msg, sizeof msg, "linearize_batch: item %d: correspondence %d (%d, %d) out of range", (int) i, (int) k, (int) row[k].fixed_idx, (int) row[k].moving_idx);
+        return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
+      }
+  }
+  size_t per_launch = kLinBatchPairBudget / (size_t) (pair_capacity > 0 ? pair_capacity : 1);
+  if (per_launch > kLinBatchMaxItems) per_launch = kLinBatchMaxItems;
+  if (per_launch < 1) per_launch = 1;
+  if (per_launch > (size_t) n_items) per_launch = (size_t) n_items;
+  // the largest launch decides the buffers' sizes: they are grown (and waited for) once, ahead of the first launch
+  size_t d_need = 0, h_need = 0;
+  for (size_t k0 = 0; k0 < (size_t) n_items; k0 += per_launch) {
+    const size_t cnt = (size_t) n_items - k0 < per_launch ? (size_t) n_items - k0 : per_launch;
+    size_t blocks = 0, np = 0;
+    for (size_t k = 0; k < cnt; ++k) { blocks += (size_t) lin_blocks(n_pairs[k0 + k]); np += (size_t) n_pairs[k0 + k]; }
+    const LinBatchLayout Y(cnt, blocks, np);
+    d_need = std::max(d_need, Y.d_bytes); h_need = std::max(h_need, Y.h_bytes);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  { int rc = ensure_scratch(ctx, d_need); if (rc) return rc; rc = ensure_stage(ctx, h_need); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  LinBatchArgs A;
+  A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr);
+  A.cauchy = sp->robustifier == LSM2D_ROBUST_CAUCHY; A.tau = sp->chi_threshold;
+  for (size_t k0 = 0; k0 < (size_t) n_items; k0 += per_launch) {
+    const size_t cnt = (size_t) n_items - k0 < per_launch ? (size_t) n_items - k0 : per_launch;
+    size_t blocks = 0, np = 0;
+    for (size_t k = 0; k < cnt; ++k) { blocks += (size_t) lin_blocks(n_pairs[k0 + k]); np += (size_t) n_pairs[k0 + k]; }
+    const LinBatchLayout Y(cnt, blocks, np);
+    LinItem* items = (LinItem*) hs; int32_t* wg = (int32_t*) (hs + Y.o_wg); char* hp = hs + Y.o_pairs;
+    size_t b0 = 0, p0 = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+      LinItem& it = items[k];
+      it.fc = fc[k0 + k]; it.mc = mc[k0 + k]; it.n_pairs = n_pairs[k0 + k]; it.blocks = lin_blocks(it.n_pairs); it.T = make_iso(poses + 3 * (k0 + k));
+      it.block_base = (int32_t) b0; it.pair_base = (int32_t) p0; it.pad0 = it.pad1 = 0;
+      for (int b = 0; b < it.blocks; ++b) wg[b0 + (size_t) b] = (int32_t) k;
+      if (it.n_pairs) memcpy(hp + sizeof(lsm2d_correspondence) * p0, pairs + (k0 + k) * (size_t) pair_capacity, sizeof(lsm2d_correspondence) * (size_t) it.n_pairs);
+      b0 += (size_t) it.blocks; p0 += (size_t) it.n_pairs;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    A.items = (const LinItem*) ds; A.wg_item = (const int32_t*) (ds + Y.o_wg); A.pairs = (const int32_t*) (ds + Y.o_pairs); A.n_items = (int32_t) cnt;
+    A.partial = (float*) (ds + Y.o_part); A.dig = (unsigned long long*) (ds + Y.o_dig); A.out = (float*) (ds + Y.o_out);
+    if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(A.dig, 0, sizeof(unsigned long long) * cnt, ctx->stream));
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+    if (ctx->sum_order) hipLaunchKernelGGL(k_linearize_seq_batch, dim3((unsigned) cnt), dim3(kAlignBlock), 0, ctx->stream, A);      // pair after pair, a workgroup per item
+    else {
+      hipLaunchKernelGGL(k_linearize_partial_batch, dim3((unsigned) blocks), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(k_linearize_final_batch, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, ctx->stream, A);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+    note_timed(ctx, ctx->kernel_timing);
+    HIPCHK(ctx, hipMemcpyAsync(hs + Y.h_out, A.out, sizeof(float) * kLinOutWords * cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_sync(ctx));      // the one wait of this launch
+    for (size_t k = 0; k < cnt; ++k) {
+      const float* h = (const float*) (hs + Y.h_out) + kLinOutWords * k;
+      float* H = out_H + 9 * (k0 + k); float* b = out_b + 3 * (k0 + k);
+      H[0] = h[0]; H[1] = h[1]; H[2] = h[2]; H[3] = h[1]; H[4] = h[3]; H[5] = h[4]; H[6] = h[2]; H[7] = h[4]; H[8] = h[5];
+      b[0] = h[6]; b[1] = h[7]; b[2] = h[8];
+      if (st) {
+        lsm2d_iteration_stats& s = st[k0 + k];
+        int32_t iv[3]; memcpy(iv, h + 11, sizeof iv);
+        s.n_inliers = iv[0]; s.n_outliers = iv[1]; s.n_correspondences = iv[2]; s.chi_inliers = h[9]; s.chi_outliers = h[10];
+        unsigned long long dg; memcpy(&dg, h + kAccumWords, sizeof dg);
+        s.pair_digest_lo = (uint32_t) dg; s.pair_digest_hi = (uint32_t) (dg >> 32);
+      }
+    }
+  }
+  return LSM2D_SUCCESS;
+}

@@ -215,56 +215,64 @@ struct LinArgs {
   unsigned long long* dig;      // the pairs' digest (lsm2d_iteration_stats.pair_digest, slice 0), zeroed by the host: every workgroup adds its share
 };
 
-__global__ __launch_bounds__(256) void k_linearize_partial(const LinArgs A) {
-  __shared__ float red[4 * kAccumWords];
-  __shared__ u64 s_dig;
+// The three bodies below ARE the factor's reduction: the single-call kernels (k_linearize_*) and the batch kernels (k_linearize_*_batch) both call them, so an
+// item of a batch gets the single call's bits by construction (tests/test_gpu_linearize_batch.py compares them bit for bit, in both orders of summation).
+// Workgroup `blk` of the `nblk` workgroups of 256 threads that share one correspondence vector: a grid-stride walk over the pairs, the thread's sums through the
+// wave tree and the workgroup's four waves, one row of kAccumWords to `row`; the workgroup's share of the pair digest is added to *dig (zeroed beforehand).
+LSM2D_DEV void linearize_partial_body(const CloudDev& fixed, const CloudDev& moving, int fc, int mc, const int32_t* pairs, int n_pairs, const Iso& T, bool cauchy,
+                                      float tau, int blk, int nblk, float* row, unsigned long long* dig, float* red /* [4 * kAccumWords] */, u64* s_dig) {
   const int tid = threadIdx.x;
-  const int fbase = A.fixed.start[A.fc], mbase = A.moving.start[A.mc];
+  const int fbase = fixed.start[fc], mbase = moving.start[mc];
   Accum acc; accum_zero(acc);
-  if (tid == 0) s_dig = 0ull;
+  if (tid == 0) *s_dig = 0ull;
   __syncthreads();
   u64 dg = 0ull;
-  for (int k = blockIdx.x * 256 + tid; k < A.n_pairs; k += gridDim.x * 256) {
-    const int fi = A.pairs[2 * k], mi = A.pairs[2 * k + 1];
+  for (int k = blk * 256 + tid; k < n_pairs; k += nblk * 256) {
+    const int fi = pairs[2 * k], mi = pairs[2 * k + 1];
     dg += pair_hash_dev(0u, (uint32_t) fi, (uint32_t) mi);
-    accumulate_pair(A.T, A.fixed.xy[fbase + fi], A.fixed.nrm[fbase + fi], A.moving.xy[mbase + mi], A.moving.nrm[mbase + mi],
-                    A.cauchy != 0, A.tau, acc);
+    accumulate_pair(T, fixed.xy[fbase + fi], fixed.nrm[fbase + fi], moving.xy[mbase + mi], moving.nrm[mbase + mi], cauchy, tau, acc);
   }
-  if (dg) atomicAdd(reinterpret_cast<unsigned long long*>(&s_dig), (unsigned long long) dg);
+  if (dg) atomicAdd(reinterpret_cast<unsigned long long*>(s_dig), (unsigned long long) dg);
   block_reduce_store(acc, red, tid);
   __syncthreads();
   if (tid == 0) {
-    if (A.dig && s_dig) atomicAdd(A.dig, (unsigned long long) s_dig);
+    if (dig && *s_dig) atomicAdd(dig, (unsigned long long) *s_dig);
     Accum t; block_reduce_gather(red, 4, t);
-    float* p = A.partial + (size_t) blockIdx.x * kAccumWords;
+    float* p = row;
     p[0] = t.h00; p[1] = t.h01; p[2] = t.h02; p[3] = t.h11; p[4] = t.h12; p[5] = t.h22; p[6] = t.b0; p[7] = t.b1; p[8] = t.b2;
     p[9] = t.chi_in; p[10] = t.chi_out; p[11] = __int_as_float(t.n_in); p[12] = __int_as_float(t.n_out); p[13] = __int_as_float(t.n_corr);
   }
 }
 
-// "sum_order" 1: the same factor with the sums formed pair after pair in the order of the correspondence vector (the reference's loop): ONE workgroup,
-// trips of kAlignBlock consecutive pairs, their terms as records in LDS, eleven lanes of wave 0 adding them in ascending position (lsm2d_device.h)
-__global__ __launch_bounds__(kAlignBlock) void k_linearize_seq(const LinArgs A) {
-  __shared__ __attribute__((aligned(16))) float s_rec[kSeqHalf * kSeqFields];
-  __shared__ float red[(kAlignBlock / 64) * kAccumWords];
-  __shared__ u64 s_dig;
+// ONE thread: the rows of a vector's workgroups added in ascending block order (fixed order => deterministic)
+LSM2D_DEV void linearize_final_body(const float* partial, int n_blocks, float* out) {
+  Accum t; block_reduce_gather(partial, n_blocks, t);
+  out[0] = t.h00; out[1] = t.h01; out[2] = t.h02; out[3] = t.h11; out[4] = t.h12; out[5] = t.h22; out[6] = t.b0; out[7] = t.b1; out[8] = t.b2;
+  out[9] = t.chi_in; out[10] = t.chi_out; out[11] = __int_as_float(t.n_in); out[12] = __int_as_float(t.n_out); out[13] = __int_as_float(t.n_corr);
+}
+
+// "sum_order" 1: ONE workgroup of kAlignBlock threads owns the vector: trips of kAlignBlock consecutive pairs, their terms as records in LDS, eleven lanes of
+// wave 0 adding them in ascending position (lsm2d_device.h).  The totals go to out[kAccumWords], the digest to *dig (written, not added).
+LSM2D_DEV void linearize_seq_body(const CloudDev& fixed, const CloudDev& moving, int fc, int mc, const int32_t* pairs, int n_pairs, const Iso& T, bool cauchy,
+                                  float tau, float* out, unsigned long long* dig, float* s_rec /* [kSeqHalf * kSeqFields], 16-byte aligned */,
+                                  float* red /* [(kAlignBlock / 64) * kAccumWords] */, u64* s_dig) {
   const int tid = threadIdx.x;
-  const int fbase = A.fixed.start[A.fc], mbase = A.moving.start[A.mc];
+  const int fbase = fixed.start[fc], mbase = moving.start[mc];
   Accum acc; accum_zero(acc);
   float seq_acc = 0.0f;
-  if (tid == 0) s_dig = 0ull;
+  if (tid == 0) *s_dig = 0ull;
   __syncthreads();
   u64 dg = 0ull;
-  for (int k0 = 0; k0 < A.n_pairs; k0 += kAlignBlock) {
+  for (int k0 = 0; k0 < n_pairs; k0 += kAlignBlock) {
     const int k = k0 + tid;
     float t[kSeqFields]; seq_zero(t);
-    if (k < A.n_pairs) {
-      const int fi = A.pairs[2 * k], mi = A.pairs[2 * k + 1];
+    if (k < n_pairs) {
+      const int fi = pairs[2 * k], mi = pairs[2 * k + 1];
       dg += pair_hash_dev(0u, (uint32_t) fi, (uint32_t) mi);
-      bool inl; pair_terms(A.T, A.fixed.xy[fbase + fi], A.fixed.nrm[fbase + fi], A.moving.xy[mbase + mi], A.moving.nrm[mbase + mi], A.cauchy != 0, A.tau, false, t, inl);
+      bool inl; pair_terms(T, fixed.xy[fbase + fi], fixed.nrm[fbase + fi], moving.xy[mbase + mi], moving.nrm[mbase + mi], cauchy, tau, false, t, inl);
       ++acc.n_corr; acc.n_in += inl ? 1 : 0; acc.n_out += inl ? 0 : 1;
     }
-    const int n_rec = A.n_pairs - k0 < kAlignBlock ? A.n_pairs - k0 : kAlignBlock;
+    const int n_rec = n_pairs - k0 < kAlignBlock ? n_pairs - k0 : kAlignBlock;
     for (int h0 = 0; h0 < n_rec; h0 += kSeqHalf) {
       if (tid >= h0 && tid < h0 + kSeqHalf) seq_store(s_rec, tid - h0, t);
       __syncthreads();
@@ -273,21 +281,88 @@ __global__ __launch_bounds__(kAlignBlock) void k_linearize_seq(const LinArgs A) 
       __syncthreads();
     }
   }
-  if (dg) atomicAdd(reinterpret_cast<unsigned long long*>(&s_dig), (unsigned long long) dg);
+  if (dg) atomicAdd(reinterpret_cast<unsigned long long*>(s_dig), (unsigned long long) dg);
   block_reduce_store(acc, red, tid);
   __syncthreads();
   if (tid < 64) {
     float v; int vi; block_reduce_gather_lane(red, kAlignBlock / 64, tid, v, vi);
     const float tot = seq_total(seq_acc, tid);
-    if (tid < 11) A.out[tid] = tot;
-    else if (tid < kAccumWords) A.out[tid] = __int_as_float(vi);
-    if (tid == 0 && A.dig) *A.dig = (unsigned long long) s_dig;
+    if (tid < 11) out[tid] = tot;
+    else if (tid < kAccumWords) out[tid] = __int_as_float(vi);
+    if (tid == 0 && dig) *dig = (unsigned long long) *s_dig;
   }
+}
+
+__global__ __launch_bounds__(256) void k_linearize_partial(const LinArgs A) {
+  __shared__ float red[4 * kAccumWords];
+  __shared__ u64 s_dig;
+  linearize_partial_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, (int) blockIdx.x, (int) gridDim.x,
+                         A.partial + (size_t) blockIdx.x * kAccumWords, A.dig, red, &s_dig);
+}
+
+// "sum_order" 1: the same factor with the sums formed pair after pair in the order of the correspondence vector (the reference's loop): ONE workgroup
+__global__ __launch_bounds__(kAlignBlock) void k_linearize_seq(const LinArgs A) {
+  __shared__ __attribute__((aligned(16))) float s_rec[kSeqHalf * kSeqFields];
+  __shared__ float red[(kAlignBlock / 64) * kAccumWords];
+  __shared__ u64 s_dig;
+  linearize_seq_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, A.out, A.dig, s_rec, red, &s_dig);
 }
 
 __global__ void k_linearize_final(const float* partial, int n_blocks, float* out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  Accum t; block_reduce_gather(partial, n_blocks, t);     // fixed block order => deterministic
-  out[0] = t.h00; out[1] = t.h01; out[2] = t.h02; out[3] = t.h11; out[4] = t.h12; out[5] = t.h22; out[6] = t.b0; out[7] = t.b1; out[8] = t.b2;
-  out[9] = t.chi_in; out[10] = t.chi_out; out[11] = __int_as_float(t.n_in); out[12] = __int_as_float(t.n_out); out[13] = __int_as_float(t.n_corr);
+  linearize_final_body(partial, n_blocks, out);
+}
+
+// ---- the factor for a whole batch of correspondence vectors (lsm2d_linearize_batch) -----------------------------------------------------
+// Item i = (cloud fc of the fixed set, cloud mc of the moving set, T, n_pairs pairs from pair_base on in one packed array).  Tree order: the item owns
+// `blocks` = clamp(ceil(n_pairs / 256), 1, 1024) consecutive workgroups of ONE flat launch, from block_base on -- the single call's launch shape, so its
+// workgroups stride over its pairs exactly as the single call's do; wg_item (host-built, one int per workgroup) says whose workgroup this is.  A second
+// launch gathers every item's rows, one thread per item.  Reference order: one workgroup of kAlignBlock threads per item.  Nobody waits for another
+// workgroup; the only atomics are the digest's 64-bit wrapping adds.
+struct LinItem {
+  int32_t fc, mc, n_pairs, blocks;
+  Iso T;
+  int32_t block_base, pair_base, pad0, pad1;
+};
+static_assert(sizeof(LinItem) == 48, "the host fills an array of these");
+static constexpr int kLinOutWords = 16;      // an item's results: the kAccumWords sums and counts, then the 64-bit pair digest
+
+struct LinBatchArgs {
+  CloudDev fixed, moving;
+  const LinItem* items;       // [n_items]
+  const int32_t* wg_item;     // [sum of blocks]: the item a workgroup of k_linearize_partial_batch works for
+  const int32_t* pairs;       // the items' vectors one after the other, [sum of n_pairs][2]
+  int32_t n_items; int32_t cauchy; float tau;
+  float* partial;             // [sum of blocks][kAccumWords]
+  unsigned long long* dig;    // [n_items], zeroed by the host (tree order only)
+  float* out;                 // [n_items][kLinOutWords]
+};
+
+// (the item's values are the same in every lane: fetched through a uniform index they stay in scalar registers, like the single call's kernel arguments)
+__global__ __launch_bounds__(256) void k_linearize_partial_batch(const LinBatchArgs A) {
+  __shared__ float red[4 * kAccumWords];
+  __shared__ u64 s_dig;
+  const int i = __builtin_amdgcn_readfirstlane(A.wg_item[blockIdx.x]);
+  const LinItem it = A.items[i];
+  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau,
+                         (int) blockIdx.x - it.block_base, it.blocks, A.partial + (size_t) blockIdx.x * kAccumWords, A.dig + i, red, &s_dig);
+}
+
+__global__ __launch_bounds__(256) void k_linearize_final_batch(const LinBatchArgs A) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n_items) return;
+  const LinItem it = A.items[i];
+  float* row = A.out + (size_t) i * kLinOutWords;
+  linearize_final_body(A.partial + (size_t) it.block_base * kAccumWords, it.blocks, row);
+  *reinterpret_cast<unsigned long long*>(row + kAccumWords) = A.dig[i];
+}
+
+__global__ __launch_bounds__(kAlignBlock) void k_linearize_seq_batch(const LinBatchArgs A) {
+  __shared__ __attribute__((aligned(16))) float s_rec[kSeqHalf * kSeqFields];
+  __shared__ float red[(kAlignBlock / 64) * kAccumWords];
+  __shared__ u64 s_dig;
+  const LinItem it = A.items[blockIdx.x];
+  float* row = A.out + (size_t) blockIdx.x * kLinOutWords;
+  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau, row,
+                     reinterpret_cast<unsigned long long*>(row + kAccumWords), s_rec, red, &s_dig);
 }

@@ -12,6 +12,7 @@
 //   k_find_*_batch     the same finders for n_items (fixed, moving, pose) triples in one launch, a workgroup per item: the single kernels' bodies.
 //   k_project_canvas   PointNormal2fProjectorPolar::compute: source index / depth / transformed point per column.
 //   k_linearize_*      SE2Plane2PlaneErrorFactor over a correspondence vector (two-stage deterministic reduce).
+//   k_linearize_*_batch  the same factor over a batch of vectors: the same device functions, an item keeps the single call's launch shape.
 //   k_repack_cloud     AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"

@@ -16,6 +16,7 @@
 #pragma once
 #include <lsm2d.h>
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <map>
@@ -104,6 +105,48 @@ inline std::vector<CorrespondenceVector> findCorrespondencesBatch(Context& ctx, 
         "lsm2d_find_correspondences_batch", ctx.get());
   std::vector<CorrespondenceVector> out(n);
   for (size_t i = 0; i < n; ++i) out[i].assign(buf.begin() + (ptrdiff_t) (i * cap), buf.begin() + (ptrdiff_t) (i * cap + (size_t) cnt[i]));
+  return out;
+}
+
+// SE2Plane2PlaneErrorFactor + robustifier over a correspondence vector (lsm2d_linearize; registration/aligner_slice_processor_laser_2d.h:4,8): H (row-major
+// 3x3), b and the statistics of cloud fixed_index of `fixed` against cloud moving_index of `moving` at `pose`.  The slice parameters' robustifier and
+// chi_threshold are the ones that matter here.
+struct Linearization {
+  std::array<float, 9> H{}; std::array<float, 3> b{}; lsm2d_iteration_stats stats{};
+};
+inline Linearization linearize(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving, const CorrespondenceVector& pairs,
+                               const Vector3f& pose, int32_t fixed_index = 0, int32_t moving_index = 0) {
+  Linearization r;
+  check(lsm2d_linearize(ctx.get(), &sp, fixed.get(), fixed_index, moving.get(), moving_index, pairs.empty() ? nullptr : pairs.data(), (int32_t) pairs.size(),
+                        pose.data(), r.H.data(), r.b.data(), &r.stats),
+        "lsm2d_linearize", ctx.get());
+  return r;
+}
+// ... and over poses.size() vectors in one launch (lsm2d_linearize_batch): item i is pairs[i] between cloud fixed_index[i] of `fixed` and cloud
+// moving_index[i] of `moving` (an empty index vector: cloud i, or the only cloud of a one-cloud set) at poses[i]; per item what linearize() returns, bit for
+// bit.  `pairs` is what findCorrespondencesBatch returns.
+inline std::vector<Linearization> linearizeBatch(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving,
+                                                 const std::vector<CorrespondenceVector>& pairs, const std::vector<Vector3f>& poses,
+                                                 const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
+  const size_t n = poses.size();
+  if (pairs.size() != n) throw std::runtime_error("linearizeBatch| one correspondence vector per pose");
+  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
+    throw std::runtime_error("linearizeBatch| an index vector is empty or holds one entry per pose");
+  size_t cap = 1;
+  for (const auto& v : pairs) cap = std::max(cap, v.size());
+  std::vector<Correspondence> buf(std::max<size_t>(cap * n, 1)); std::vector<int32_t> cnt(std::max<size_t>(n, 1), 0);
+  for (size_t i = 0; i < n; ++i) { std::copy(pairs[i].begin(), pairs[i].end(), buf.begin() + (ptrdiff_t) (i * cap)); cnt[i] = (int32_t) pairs[i].size(); }
+  std::vector<float> H(9 * std::max<size_t>(n, 1)), b(3 * std::max<size_t>(n, 1)); std::vector<lsm2d_iteration_stats> st(std::max<size_t>(n, 1));
+  check(lsm2d_linearize_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
+                              moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, buf.data(), (int32_t) cap, cnt.data(),
+                              n ? poses[0].data() : nullptr, H.data(), b.data(), st.data()),
+        "lsm2d_linearize_batch", ctx.get());
+  std::vector<Linearization> out(n);
+  for (size_t i = 0; i < n; ++i) {
+    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].H.begin());
+    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].b.begin());
+    out[i].stats = st[i];
+  }
   return out;
 }
 

@@ -1,0 +1,339 @@
+"""GPU tests of lsm2d_linearize_batch (k_linearize_partial_batch / k_linearize_final_batch / k_linearize_seq_batch).  Per item the batched call must return
+exactly what lsm2d_linearize returns -- H, b, the counts, the chi^2 sums and the pair digest -- in both orders of summation, and that call is held bit for
+bit to the CPU oracle (po.linearize_device_order for "sum_order" 0, the sequential po.linearize for "sum_order" 1), so every batch here is compared with
+single calls AND with the oracle.  No tolerance appears in this file."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from srrg2_laser_slam_2d_amd import api, synth
+from srrg2_laser_slam_2d_amd._capi import BAD_ARGUMENT, IterationStats
+
+pytestmark = pytest.mark.gpu
+
+PAIR_BUDGET = 1 << 21      # pairs per launch (kLinBatchPairBudget, lsm2d_capi_finder.inc)
+TAU = 0.01
+# where blocks_i = clamp(ceil(n / 256), 1, 1024) steps, where a trip of kAlignBlock = 512 and a half-trip of kSeqHalf = 256 end; the large item (past the
+# 1024-workgroup clamp: 1024 x 256 = 262 144, so the grid-stride loop takes a second trip) sits in the middle, ragged block offsets on both sides of it
+EDGE_COUNTS = [0, 1, 255, 256, 257, 262444, 511, 512, 513, 1025]
+
+
+class _Fx:
+    pass
+
+
+@pytest.fixture(scope="module")
+def fx(ctx, po):
+    f = _Fx()
+    wl = synth.make_workload(3, 3000, seed=5, map_noise=0.004, scan_noise=0.004)
+    f.wl = wl
+    f.scans = [wl.scan_points[wl.scan_offsets[i]:wl.scan_offsets[i + 1]] for i in range(3)]
+    f.map = wl.map_points
+    f.x0 = np.ascontiguousarray(wl.x0, np.float32)
+    f.scan_set = api.CloudSet(ctx, wl.scan_points, wl.scan_offsets)
+    f.map_set = api.CloudSet(ctx, f.map)
+    f.real = [po.find(po.slice_params(), f.scans[i], f.map, f.x0[i]) for i in range(3)]
+    assert min(len(r) for r in f.real) > 300
+    # the shape-edge batch: fixed_index cycles 0, 1, 2 with repeats; vectors longer than the real one are drawn from it with repetition
+    rng = np.random.default_rng(11)
+    f.edge_fi = (np.arange(len(EDGE_COUNTS)) % 3).astype(np.int32)
+    f.edge_vec = []
+    for k, c in enumerate(EDGE_COUNTS):
+        real = f.real[f.edge_fi[k]]
+        f.edge_vec.append(np.ascontiguousarray(real[:c] if c <= len(real) else real[rng.integers(0, len(real), c)], np.int32))
+    f.edge_poses = np.ascontiguousarray(f.x0[f.edge_fi])
+    return f
+
+
+@pytest.fixture()
+def order_ctx(ctx, request):
+    ctx.set_option("sum_order", request.param)
+    try:
+        yield ctx
+    finally:
+        ctx.set_option("sum_order", 0)
+
+
+def _sp(robust=api.ROBUST_NONE):
+    return api.make_slice_params(robustifier=robust, chi_threshold=TAU)
+
+
+def _osp(po, robust=api.ROBUST_NONE):
+    return po.slice_params(robustifier=robust, chi_threshold=TAU)
+
+
+def _key(H, b, st):
+    """everything an item returns, as bytes and integers: equality of keys is bitwise equality"""
+    return (np.asarray(H, np.float32).tobytes(), np.asarray(b, np.float32).tobytes(), int(st.n_correspondences), int(st.n_inliers), int(st.n_outliers),
+            np.float32(st.chi_inliers).tobytes(), np.float32(st.chi_outliers).tobytes(), int(st.pair_digest))
+
+
+def _okey(H, b, ost):
+    return (np.asarray(H, np.float32).tobytes(), np.asarray(b, np.float32).tobytes(), int(ost.n_corr), int(ost.n_in), int(ost.n_out),
+            np.float32(ost.chi_in).tobytes(), np.float32(ost.chi_out).tobytes(), int(ost.pair_digest))
+
+
+def _batch_keys(res):
+    H, b, st = res
+    assert H.shape == (len(st), 3, 3) and b.shape == (len(st), 3)
+    return [_key(H[i], b[i], st[i]) for i in range(len(st))]
+
+
+def _single_keys(ctx, sp, fixed, fi, moving, mi, vecs, poses):
+    return [_key(*api.linearize(ctx, sp, fixed, moving, vecs[k], poses[k], fixed_index=int(fi[k]), moving_index=int(mi[k]))) for k in range(len(vecs))]
+
+
+# ---- 1. shape edges, both orders of summation ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("robust", [api.ROBUST_NONE, api.ROBUST_CAUCHY], ids=["plain", "cauchy"])
+@pytest.mark.parametrize("order_ctx", [0, 1], ids=["tree", "reference"], indirect=True)
+def test_shape_edges_equal_single_calls_and_oracle(order_ctx, po, fx, robust):
+    ctx = order_ctx
+    order = ctx.get_option("sum_order")
+    sp, osp = _sp(robust), _osp(po, robust)
+    n = len(EDGE_COUNTS)
+    H, b, st = api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, fx.edge_vec, fx.edge_poses, fixed_index=fx.edge_fi)
+    got = _batch_keys((H, b, st))
+    one = _single_keys(ctx, sp, fx.scan_set, fx.edge_fi, fx.map_set, np.zeros(n, int), fx.edge_vec, fx.edge_poses)
+    oracle = po.linearize if order else po.linearize_device_order
+    for k in range(n):
+        assert got[k] == one[k], ("batch vs single call", order, robust, k, EDGE_COUNTS[k])
+        want = _okey(*oracle(osp, fx.scans[fx.edge_fi[k]], fx.map, fx.edge_vec[k], fx.edge_poses[k]))
+        assert got[k] == want, ("batch vs oracle", order, robust, k, EDGE_COUNTS[k])
+        assert st[k].n_correspondences == EDGE_COUNTS[k] and st[k].pair_digest == po.pair_digest(fx.edge_vec[k])
+    assert np.all(H[0] == 0) and np.all(b[0] == 0) and st[0].n_correspondences == 0
+    if robust == api.ROBUST_CAUCHY:
+        assert any(s.n_inliers > 0 and s.n_outliers > 0 for s in st)
+    # the other order gives other bits for every count >= 255: a kernel summing in the wrong order cannot have passed
+    other = po.linearize_device_order if order else po.linearize
+    for k in range(n):
+        if EDGE_COUNTS[k] >= 255:
+            assert got[k][:2] != _okey(*other(osp, fx.scans[fx.edge_fi[k]], fx.map, fx.edge_vec[k], fx.edge_poses[k]))[:2], (order, robust, k)
+
+
+# ---- raw calls (buffers chosen by the test) ----------------------------------------------------------------------------------------------------------------
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class _Out:
+    def __init__(self, n):
+        self.H = np.full((max(n, 1), 9), -7.0, np.float32); self.b = np.full((max(n, 1), 3), -7.0, np.float32)
+        self.st = (IterationStats * max(n, 1))()
+        C.memset(self.st, 0x5A, C.sizeof(self.st))
+
+    def untouched(self):
+        return bool(np.all(self.H == -7.0) and np.all(self.b == -7.0) and bytes(self.st) == b"\x5a" * C.sizeof(self.st))
+
+    def keys(self, n):
+        return [_key(self.H[i].reshape(3, 3), self.b[i], self.st[i]) for i in range(n)]
+
+
+def _raw(ctx, sp, fixed, fi, moving, mi, pairs, cap, cnt, poses, n=None):
+    poses = None if poses is None else np.ascontiguousarray(poses, np.float32)
+    n = len(poses) if n is None else n
+    out = _Out(n)
+    rc = ctx._lib.lsm2d_linearize_batch(ctx.handle, C.byref(sp), fixed.handle, _ptr(fi), moving.handle, _ptr(mi), n, _ptr(pairs), cap, _ptr(cnt), _ptr(poses),
+                                        _ptr(out.H), _ptr(out.b), out.st)
+    return rc, out
+
+
+def _padded(vecs, cap=None, fill=-7):
+    cap = max(max((len(v) for v in vecs), default=0), 1) if cap is None else cap
+    p = np.full((max(len(vecs), 1), cap, 2), fill, np.int32)
+    for i, v in enumerate(vecs):
+        p[i, : len(v)] = v
+    return p, np.array([len(v) for v in vecs], np.int32)
+
+
+# ---- 2. hand-off: the batch finder's output buffers go to the batch factor unchanged -------------------------------------------------------------------------
+def test_find_batch_output_feeds_linearize_batch_unchanged(ctx, po, fx):
+    cols, n = 721, 6
+    finder = api.CorrespondenceFinderProjective2f(ctx, api.PointNormal2fProjectorPolar(cols, -math.pi, math.pi, 0.3, 30.0))
+    sp = finder.slice_params()
+    fi = np.int32([0, 1, 2, 2, 0, 1])
+    rng = np.random.default_rng(3)
+    poses = (fx.x0[fi] + rng.uniform(-1.0, 1.0, (n, 3)) * np.float32([0.03, 0.03, 0.01])).astype(np.float32)
+    pairs = np.full((n, cols, 2), -7, np.int32); cnt = np.full(n, -7, np.int32)      # the rows' tails keep the -7
+    rc = ctx._lib.lsm2d_find_correspondences_batch(ctx.handle, C.byref(sp), fx.scan_set.handle, _ptr(fi), fx.map_set.handle, None, n, _ptr(poses), _ptr(pairs), cols, _ptr(cnt))
+    assert rc == 0 and cnt.min() > 100 and cnt.max() < cols
+    assert all(np.all(pairs[i, cnt[i]:] == -7) for i in range(n))
+    spl = _sp(api.ROBUST_CAUCHY)
+    rc, out = _raw(ctx, spl, fx.scan_set, fi, fx.map_set, None, pairs, cols, cnt, poses)
+    assert rc == 0
+    vecs = [pairs[i, : cnt[i]].copy() for i in range(n)]
+    assert out.keys(n) == _single_keys(ctx, spl, fx.scan_set, fi, fx.map_set, np.zeros(n, int), vecs, poses)
+    for i in range(n):
+        assert np.array_equal(vecs[i], po.find(po.slice_params(canvas_cols=cols), fx.scans[fi[i]], fx.map, poses[i])), i
+    # ... and the Python form that takes the padded array with its counts
+    assert _batch_keys(api.linearize_batch(ctx, spl, fx.scan_set, fx.map_set, (pairs, cnt), poses, fixed_index=fi)) == out.keys(n)
+
+
+# ---- 3. index rules and set states ---------------------------------------------------------------------------------------------------------------------------
+def test_index_rules_and_set_states(ctx, po, fx):
+    sp, osp = _sp(), _osp(po)
+    # NULL / NULL on sets of n_items clouds
+    maps = [fx.map, np.ascontiguousarray(fx.map[::2]), np.ascontiguousarray(fx.map[1::3])]
+    offs = np.concatenate([[0], np.cumsum([len(m) for m in maps])]).astype(np.int32)
+    three = api.CloudSet(ctx, np.ascontiguousarray(np.concatenate(maps)), offs)
+    vecs = [po.find(po.slice_params(), fx.scans[i], maps[i], fx.x0[i]) for i in range(3)]
+    assert min(len(v) for v in vecs) > 100
+    got = _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, three, vecs, fx.x0))
+    assert got == _single_keys(ctx, sp, fx.scan_set, np.arange(3), three, np.arange(3), vecs, fx.x0)
+    assert got == [_okey(*po.linearize_device_order(osp, fx.scans[i], maps[i], vecs[i], fx.x0[i])) for i in range(3)]
+    # both index arrays, with repeats, over the same sets
+    fi, mi = np.int32([2, 2, 0, 1]), np.int32([2, 0, 0, 1])
+    v4 = [po.find(po.slice_params(), fx.scans[fi[k]], maps[mi[k]], fx.x0[fi[k]]) for k in range(4)]
+    got = _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, three, v4, fx.x0[fi], fixed_index=fi, moving_index=mi))
+    assert got == _single_keys(ctx, sp, fx.scan_set, fi, three, mi, v4, fx.x0[fi])
+    # NULL moving index over a one-cloud set
+    got = _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, fx.real, fx.x0))
+    assert got == [_okey(*po.linearize_device_order(osp, fx.scans[i], fx.map, fx.real[i], fx.x0[i])) for i in range(3)]
+    # a NULL index over a set of neither 1 nor n_items clouds
+    p, c = _padded(fx.real[:2])
+    rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, p, p.shape[1], c, fx.x0[:2])
+    assert rc == BAD_ARGUMENT and out.untouched()
+    # a fixed set whose size only the device knows: a preprocessed scan written into a reserved set and never downloaded
+    sensor = synth.sample_poses(fx.wl.world, 1, seed=21)
+    ranges = synth.make_scan_ranges(fx.wl.world, sensor, n_beams=721, angle_min=-2.0, angle_max=2.0, noise_sigma=0.004, seed=9)[0]
+    cloud = po.preprocess_scan(po.Preprocessor(721, -2.0, 2.0, 0.3, 30.0, 0.3, 5, 0.02), ranges)
+    pose = synth.invert_poses(synth.compose_poses(sensor, np.array([[0.05, -0.04, 0.02]]))).astype(np.float32)
+    vec = po.find(po.slice_params(), cloud, fx.map, pose[0])
+    assert len(vec) > 100
+    pre = api.RawDataPreprocessorProjective2D(ctx, range_min=0.3, range_max=30.0, voxelize_resolution=0.02, normal_point_distance=0.3, normal_min_points=5)
+    pre.setRawData(ranges, -2.0, 2.0, 0.0, 40.0)
+    pending = pre.compute_into(api.CloudSet.reserved(ctx, 1024))
+    poses2 = np.repeat(pose, 2, axis=0)
+    got = _batch_keys(api.linearize_batch(ctx, sp, pending, fx.map_set, [vec, vec[::2]], poses2))
+    uploaded = api.CloudSet(ctx, cloud)
+    assert got == _batch_keys(api.linearize_batch(ctx, sp, uploaded, fx.map_set, [vec, vec[::2]], poses2))
+    assert got == [_okey(*po.linearize_device_order(osp, cloud, fx.map, v, pose[0])) for v in (vec, vec[::2])]
+    assert np.array_equal(pending.download(0), cloud)
+
+
+# ---- 4. refusals ---------------------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_name_the_item_and_write_nothing(ctx, fx):
+    sp = _sp()
+    lib = ctx._lib
+    base, cnt = _padded(fx.real)
+    cap = base.shape[1]
+
+    def refused(pairs, counts, item, capacity=cap):
+        rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, pairs, capacity, counts, fx.x0)
+        text = lib.lsm2d_last_error(ctx.handle).decode()
+        assert rc == BAD_ARGUMENT and out.untouched(), (rc, text)
+        assert "item %d" % item in text, text
+
+    p = base.copy(); p[1, 5, 0] = -1
+    refused(p, cnt, 1)                                            # a negative index
+    p = base.copy(); p[2, cnt[2] - 1, 0] = len(fx.scans[2])
+    refused(p, cnt, 2)                                            # an index equal to the fixed cloud's size
+    p = base.copy(); p[0, 0, 1] = len(fx.map)
+    refused(p, cnt, 0)                                            # ... to the moving cloud's
+    c = cnt.copy(); c[1] = cap + 1
+    refused(base, c, 1)                                           # n_pairs[i] > pair_capacity
+    c = cnt.copy(); c[2] = -1
+    refused(base, c, 2)
+    # what lies behind a row's n_pairs is neither read nor checked: the tails hold -7
+    assert np.all(base[0, cnt[0]:] == -7) or cnt[0] == cap
+    rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, base, cap, cnt, fx.x0)
+    assert rc == 0 and out.keys(3) == _single_keys(ctx, sp, fx.scan_set, np.arange(3), fx.map_set, np.zeros(3, int), fx.real, fx.x0)
+    # cloud indices out of range
+    for fi in (np.int32([0, 1, 3]), np.int32([0, -1, 2])):
+        rc, out = _raw(ctx, sp, fx.scan_set, fi, fx.map_set, None, base, cap, cnt, fx.x0)
+        assert rc == BAD_ARGUMENT and out.untouched() and "item" in lib.lsm2d_last_error(ctx.handle).decode()
+    # n_items 0: a successful no-op, whatever the item arrays are
+    rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, None, cap, None, None, n=0)
+    assert rc == 0 and out.untouched()
+    H, b, st = api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, [], np.zeros((0, 3), np.float32))
+    assert H.shape == (0, 3, 3) and b.shape == (0, 3) and st == []
+
+
+# ---- 5. a batch beyond the device buffer's budget: several launches over consecutive items ---------------------------------------------------------------------
+def test_chunked_batch_equals_small_batches(ctx, po, fx):
+    n, cap = 300, 8192
+    assert n * cap > PAIR_BUDGET and PAIR_BUDGET // cap < n
+    rng = np.random.default_rng(29)
+    fi = (np.arange(n) % 3).astype(np.int32)
+    vecs = [fx.real[fi[k]][: int(rng.integers(0, len(fx.real[fi[k]]) + 1))] for k in range(n)]
+    poses = (fx.x0[fi] + rng.uniform(-1.0, 1.0, (n, 3)) * np.float32([0.02, 0.02, 0.01])).astype(np.float32)
+    sp = _sp(api.ROBUST_CAUCHY)
+    pairs, cnt = _padded(vecs, cap)
+    rc, out = _raw(ctx, sp, fx.scan_set, fi, fx.map_set, None, pairs, cap, cnt, poses)
+    assert rc == 0
+    got = out.keys(n)
+    small = []
+    for k0 in range(0, n, 50):      # 50 x 8192 pairs: one launch each
+        small += _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, vecs[k0:k0 + 50], poses[k0:k0 + 50], fixed_index=fi[k0:k0 + 50]))
+    assert got == small
+    per_launch = PAIR_BUDGET // cap
+    for k in (0, per_launch - 1, per_launch, n - 1):      # items on both sides of a launch boundary, against the oracle
+        assert got[k] == _okey(*po.linearize_device_order(_osp(po, api.ROBUST_CAUCHY), fx.scans[fi[k]], fx.map, vecs[k], poses[k])), k
+    assert len(set(got)) > 250      # the items differ
+
+
+def test_more_items_than_one_launch_takes(ctx, po, fx):
+    """short vectors: the pair budget alone would put all of them into one launch, the bound on the item table (kLinBatchMaxItems) splits it"""
+    max_items, cap = 1 << 16, 2
+    n = max_items + 5
+    rng = np.random.default_rng(31)
+    fi = (np.arange(n) % 3).astype(np.int32)
+    cnt = rng.integers(0, cap + 1, n).astype(np.int32)
+    pairs = np.full((n, cap, 2), -7, np.int32)
+    for s in range(3):
+        rows = np.flatnonzero(fi == s)
+        pairs[rows] = fx.real[s][rng.integers(0, len(fx.real[s]), (len(rows), cap))]
+    pairs[np.arange(cap)[None, :] >= cnt[:, None]] = -7
+    poses = np.ascontiguousarray(fx.x0[fi])
+    sp = _sp(api.ROBUST_CAUCHY)
+    rc, out = _raw(ctx, sp, fx.scan_set, fi, fx.map_set, None, pairs, cap, cnt, poses)
+    assert rc == 0
+    # the same items in two launches cut elsewhere
+    cut = 40000
+    rc, a = _raw(ctx, sp, fx.scan_set, fi[:cut], fx.map_set, None, pairs[:cut], cap, cnt[:cut], poses[:cut])
+    assert rc == 0
+    rc, b = _raw(ctx, sp, fx.scan_set, fi[cut:], fx.map_set, None, pairs[cut:], cap, cnt[cut:], poses[cut:])
+    assert rc == 0
+    assert np.array_equal(out.H.view(np.uint32), np.concatenate([a.H, b.H]).view(np.uint32)) and np.array_equal(out.b.view(np.uint32), np.concatenate([a.b, b.b]).view(np.uint32))
+    assert bytes(out.st) == bytes(a.st) + bytes(b.st)
+    osp = _osp(po, api.ROBUST_CAUCHY)
+    for k in (0, cut - 1, cut, max_items - 1, max_items, n - 1):
+        st = out.st[k]
+        want = _okey(*po.linearize_device_order(osp, fx.scans[fi[k]], fx.map, pairs[k, : cnt[k]], poses[k]))
+        assert _key(out.H[k].reshape(3, 3), out.b[k], st) == want, k
+    assert int(sum(out.st[k].n_correspondences for k in range(max_items, n))) == int(cnt[max_items:].sum())
+
+
+# ---- 6. batches in flight ------------------------------------------------------------------------------------------------------------------------------------------
+def _aligner(ctx):
+    al = api.MultiAligner2D(ctx, max_iterations=8, min_num_inliers=10)
+    finder = api.CorrespondenceFinderProjective2f(ctx, api.PointNormal2fProjectorPolar(1081, -math.pi, math.pi, 0.3, 30.0))
+    al.param_slice_processors.append(api.AlignerSliceProcessorLaser2D(finder, min_num_correspondences=10))
+    return al
+
+
+def test_with_batches_in_flight(ctx, fx):
+    sp = _sp(api.ROBUST_CAUCHY)
+    al = _aligner(ctx)
+    want_al = al.compute_batch([fx.scan_set], [fx.map_set], fx.x0)
+    want = _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, fx.real, fx.x0))
+    # one batch begun: the call works and gives the same bits, and so does the batch
+    prep = al.prepare_batch([fx.scan_set], [fx.map_set], fx.x0)
+    prep.begin()
+    got = _batch_keys(api.linearize_batch(ctx, sp, fx.scan_set, fx.map_set, fx.real, fx.x0))
+    res = prep.wait(copy=True)
+    assert got == want
+    assert np.array_equal(res.pose.view(np.uint32), want_al.pose.view(np.uint32)) and np.array_equal(res.status, want_al.status)
+    # two begun: refused like every call that moves data, nothing written; with both waited for it works again
+    pairs, cnt = _padded(fx.real)
+    a, b = al.prepare_batch([fx.scan_set], [fx.map_set], fx.x0), al.prepare_batch([fx.scan_set], [fx.map_set], fx.x0[::-1].copy(), fixed_index=np.int32([[2, 1, 0]]))
+    a.begin(); b.begin()
+    try:
+        rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, pairs, pairs.shape[1], cnt, fx.x0)
+        assert rc == BAD_ARGUMENT and out.untouched()
+    finally:
+        ra, rb = a.wait(copy=True), b.wait(copy=True)
+    assert np.array_equal(ra.pose.view(np.uint32), rb.pose[::-1].view(np.uint32))
+    rc, out = _raw(ctx, sp, fx.scan_set, None, fx.map_set, None, pairs, pairs.shape[1], cnt, fx.x0)
+    assert rc == 0 and out.keys(3) == want
