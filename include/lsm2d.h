@@ -51,7 +51,9 @@ extern "C" {
                              (0.7.1, number unchanged: an addition only) + lsm2d_find_correspondences_batch (plugin interface #1 for n_items triples in one
                                     launch, the single call's bits); lsm2d_align_batch_pairs of more than one alignment derives its pairs through it;
                              (0.7.2, number unchanged: an addition only) + lsm2d_linearize_batch (the factor over n_items correspondence vectors in one
-                                    launch, the single call's bits in both orders of summation) */
+                                    launch, the single call's bits in both orders of summation);
+                             (0.7.3, number unchanged: an addition only) + lsm2d_score_batch (finder, then factor, for n_items pose hypotheses with the
+                                    pairs kept on the device: one copy down and one wait per call, the bits of the two batch calls in sequence) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -440,6 +442,29 @@ int lsm2d_linearize_batch(lsm2d_context* ctx, const lsm2d_slice_params* slice,
                           const int32_t* n_pairs /* [n_items] */, const float* poses /* [n_items][3] */,
                           float* out_H /* [n_items][9] */, float* out_b /* [n_items][3] */,
                           lsm2d_iteration_stats* out_stats /* [n_items] or NULL */);
+/* Finder, then factor, for n_items pose hypotheses, with the pairs kept on the device: what the candidate loops of the loop detector and the relocaliser
+ * (MULTI.json:964-986, :749-769) read of a candidate -- inlier / outlier counts, chi^2 sums -- and what a particle filter weighs by or a host with its own
+ * solver needs at poses it chooses: H AND b (registration/aligner_slice_processor_laser_2d.h:4,8; octave/solver/nicp_post.m:4-26,69-90).  Item i matches
+ * cloud fixed_index[i] of `fixed` against cloud moving_index[i] of `moving` at poses[i] with the slice's finder and linearises what it found at the same pose.
+ * Per item H, b, the counts, the chi^2 sums and the pair digest (slice 0) are, bit for bit, those of lsm2d_find_correspondences_batch at poses[i] followed
+ * by lsm2d_linearize_batch on what it wrote -- in both orders of summation (option "sum_order"), for all four finder kinds, with and without the Cauchy
+ * robustifier; hence also those of the single calls.  An item that finds no pair returns zeros and n_correspondences == 0.
+ * The pairs never leave the device: the finder's kernels write them into the lane's scratch and the factor's kernels (linearize_*_body, the single call's)
+ * read them there, an item's count included.  There is no pair_capacity argument: every item's slot is the slice's largest possible vector (canvas_cols,
+ * or the largest moving cloud).  There is no host-side check of pair indices (the pairs are the finder's own); the count is clamped to the slot on the device.
+ * Indices: the rule of lsm2d_batch (NULL: cloud i, or cloud 0 of a one-cloud set; the set then holds 1 or n_items clouds; indices may repeat).  Sets in any
+ * state are read; counts are resolved and pending work is flushed once for the whole batch; the fixed set's search structure is built or reused once.
+ * A batch whose n_items x slot exceeds the 2^21-pair buffer runs as several launch groups over consecutive items, queued one behind the other and reusing
+ * the same pair scratch; the items' arguments go up once, the results (16 words per item) come down in one copy, and the call waits ONCE, at its end.
+ * n_items == 0 is a successful no-op.  A cloud index out of range is LSM2D_BAD_ARGUMENT, lsm2d_last_error names the item, nothing is launched or written.
+ * Canvases that do not fit LDS are LSM2D_CAPACITY_EXCEEDED, as in lsm2d_find_correspondences_batch.  With one batch in flight (lsm2d_align_batch_begin) the
+ * call works; with two it is refused (LSM2D_BAD_ARGUMENT).  "kernel_timing" / lsm2d_last_kernel_ms cover the last launch group, finder and factor together. */
+int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* slice,
+                      const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                      const lsm2d_cloudset* moving, const int32_t* moving_index,
+                      int32_t n_items, const float* poses /* [n_items][3] */,
+                      float* out_H /* [n_items][9] */, float* out_b /* [n_items][3] */,
+                      lsm2d_iteration_stats* out_stats /* [n_items] or NULL */);
 
 /* ---- plugin interface #2: MultiAligner2D::compute, batched --------------------------------------
  * Replaces aligner->setFixed / setMoving / setMovingInFixed / compute / movingInFixed /

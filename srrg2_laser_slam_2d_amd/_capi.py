@@ -123,6 +123,7 @@ SYMBOLS = [
     ("lsm2d_merge_scene_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_float, _P, _P]),
     ("lsm2d_find_correspondences_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("lsm2d_linearize_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("lsm2d_score_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 ]
 
 _lib = None

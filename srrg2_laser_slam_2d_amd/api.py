@@ -802,6 +802,34 @@ def linearize_batch(ctx: Context, slice_params: SliceParams, fixed, moving, corr
     return H[:n].reshape(n, 3, 3), b[:n], [st[i] for i in range(n)]
 
 
+def score_batch(ctx: Context, slice_params: SliceParams, fixed, moving, poses, fixed_index=None, moving_index=None):
+    """Finder, then factor, for ``len(poses)`` pose hypotheses in one call with the pairs kept on the device (lsm2d_score_batch): item ``i`` matches cloud
+    ``fixed_index[i]`` of the set ``fixed`` against cloud ``moving_index[i]`` of the set ``moving`` (None: cloud ``i``, or the only cloud of a one-cloud set)
+    at ``poses[i]`` with the slice's finder and linearises what it found there.  Returns ``(H [n, 3, 3], b [n, 3], stats)``, ``stats`` a list of ``n``
+    IterationStats: per item the bits of ``finder.compute_batch`` followed by ``linearize_batch``, one copy down and one wait.  ``score_accept(stats, ...)``
+    applies the loop detector's acceptance test to them."""
+    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
+    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+    n = len(x)
+    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
+    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
+    H = np.empty((max(n, 1), 9), np.float32); b = np.empty((max(n, 1), 3), np.float32); st = (IterationStats * max(n, 1))()
+    check(ctx._lib.lsm2d_score_batch(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
+                                     mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, x.ctypes.data_as(C.c_void_p),
+                                     H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), st),
+          "lsm2d_score_batch", ctx.handle)
+    return H[:n].reshape(n, 3, 3), b[:n], [st[i] for i in range(n)]
+
+
+def score_accept(stats, relocalize_min_inliers: int = 500, relocalize_max_chi_inliers: float = 0.1, relocalize_min_inliers_ratio: float = 0.8) -> np.ndarray:
+    """``BatchResult.loop_closure_accept``'s test (MULTI.json:964-986; the relocaliser's 700 / 0.01 / 0.75: :749-769) on the statistics ``score_batch``
+    returns, minus the aligner's status, which a scored hypothesis does not have: inliers >= min, chi_inliers / inliers <= max,
+    inliers / correspondences >= ratio.  Returns bool [n]."""
+    n_in = np.array([s.n_inliers for s in stats], np.float64); n_c = np.array([max(s.n_correspondences, 1) for s in stats], np.float64)
+    chi = np.array([s.chi_inliers for s in stats], np.float64)
+    return (n_in >= relocalize_min_inliers) & (chi / np.maximum(n_in, 1.0) <= relocalize_max_chi_inliers) & (n_in / n_c >= relocalize_min_inliers_ratio)
+
+
 class SceneClipperProjective2D:
     """mapping/scene_clipper_projective_2d.{h,cpp}: keeps what the sensor sees of the local map, at most one point per projector
     column, in the robot frame; ``voxelize_resolution`` > 0 additionally voxelises the clipped cloud (.cpp:36-48; both shipped configs

@@ -115,32 +115,70 @@ extern "C" int lsm2d_find_correspondences(lsm2d_context* ctx, const lsm2d_slice_
 // a 100 000-point moving cloud go 20 to a launch.
 static constexpr size_t kFindBatchPairBudget = (size_t) 2 << 20;
 
+// The launch part of a batched finder pass, shared by lsm2d_find_correspondences_batch (find_batch_impl) and lsm2d_score_batch: what is the same for every
+// item -- the sets' device views, the fixed set's search structure or the projector, the gates, the slot size -- and which kernel runs.
+struct FindBatchLaunch {
+  bool point_query = false;
+  FindBatchArgs A; FindNNBatchArgs N;
+  size_t lds = 0;
+};
+
+// Sizes only the device knows and pending unpacking / preprocessing are settled once for the whole batch, the fixed set's search structure is built or
+// found, the launch arguments but the three per-launch pointers are filled in.  `who` heads the messages.
+static int find_batch_prepare(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const lsm2d_cloudset* moving, float inl_tau,
+                              int32_t capacity, const char* who, FindBatchLaunch& P) {
+  char msg[160];
+  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
+  { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
+  P.point_query = is_point_query(sp->finder);
+  if (!P.point_query && sp->finder != LSM2D_FINDER_PROJECTIVE) { snprintf(msg, sizeof msg, "%s: finder not supported", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  FindBatchArgs& A = P.A; FindNNBatchArgs& N = P.N;
+  if (P.point_query) {
+    N.fixed = cloud_dev(fixed, nullptr); N.moving = cloud_dev(moving, nullptr);
+    N.use_distmap = sp->finder == LSM2D_FINDER_DISTMAP; N.use_kd = sp->finder == LSM2D_FINDER_KDTREE;
+    snprintf(msg, sizeof msg, "%s: max_distance must be > 0", who);
+    const int rc = prepare_point_query(ctx, sp, fixed, N.fixed, msg); if (rc) return rc;
+    N.max_distance = sp->max_distance; N.normal_cos = sp->normal_cos; N.inl_tau = inl_tau; N.pair_capacity = capacity;
+  } else {
+    if (!make_projk(sp->projector, &A.proj)) { snprintf(msg, sizeof msg, "%s: bad projector", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
+    P.lds = sizeof(u64) * 2 * (size_t) A.proj.cols;
+    if ((int) P.lds > ctx->max_dyn_lds) { snprintf(msg, sizeof msg, "%s: canvases do not fit LDS", who); return fail(ctx, LSM2D_CAPACITY_EXCEEDED, msg); }
+    A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr);
+    A.point_distance = sp->point_distance; A.normal_cos = sp->normal_cos; A.inl_tau = inl_tau; A.pair_capacity = capacity;
+  }
+  return LSM2D_SUCCESS;
+}
+
+// the arguments of cnt items, item k = (cloud fc[k] of `fixed`, cloud mc[k] of `moving`, poses[k]), as the kernels read them
+static void find_batch_fill_items(FindItem* items, const lsm2d_cloudset* fixed, const int32_t* fc, const lsm2d_cloudset* moving, const int32_t* mc,
+                                  const float* poses, size_t cnt) {
+  for (size_t k = 0; k < cnt; ++k) {
+    FindItem& it = items[k];
+    it.fc = fc[k]; it.mc = mc[k]; it.T = make_iso(poses + 3 * k); it.pad = 0;
+    it.nn_group = fixed->h_count[it.fc] >= 4 * (int64_t) moving->h_count[it.mc] ? kNNGroup : 1;      // dense fixed cloud: cooperative search, item by item
+  }
+}
+
+// one launch: a workgroup per item; item k's count goes to d_count[k], its pairs to slot k of d_pairs (all three device addresses)
+static void find_batch_launch(lsm2d_context* ctx, FindBatchLaunch& P, const FindItem* d_items, size_t cnt, int32_t* d_count, int32_t* d_pairs) {
+  if (P.point_query) {
+    P.N.items = d_items; P.N.out_count = d_count; P.N.out_pairs = d_pairs;
+    hipLaunchKernelGGL(k_find_nn_batch, dim3((unsigned) cnt), dim3(kFindBlock), 0, ctx->stream, P.N);
+  } else {
+    P.A.items = d_items; P.A.out_count = d_count; P.A.out_pairs = d_pairs;
+    hipLaunchKernelGGL(k_find_projective_batch, dim3((unsigned) cnt), dim3(kFindBlock), P.lds, ctx->stream, P.A);
+  }
+}
+
 // n items, item k = (cloud fc[k] of `fixed`, cloud mc[k] of `moving`, poses[k]); its pairs go to out_pairs + slot * pair_stride and its count to
 // out_n + slot * count_stride, slot = slots ? slots[k] : k.  The callers have checked the pointers, the indices and the capacity rule.
 static int find_batch_impl(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fc, const lsm2d_cloudset* moving,
                            const int32_t* mc, int32_t n, const float* poses, float inl_tau, lsm2d_correspondence* out_pairs, int32_t capacity,
                            int32_t* out_n, const int32_t* slots, size_t pair_stride, size_t count_stride) {
-  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  // sizes only the device knows, pending unpacking / preprocessing: once for the whole batch
-  { int rc0 = resolve_count(fixed); if (rc0) return rc0; rc0 = resolve_count(moving); if (rc0) return rc0; }
-  { int rc0 = flush_pending(fixed); if (rc0) return rc0; rc0 = flush_pending(moving); if (rc0) return rc0; }
-  const bool point_query = is_point_query(sp->finder);
-  if (!point_query && sp->finder != LSM2D_FINDER_PROJECTIVE) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: finder not supported");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  FindBatchArgs A; FindNNBatchArgs N;
-  size_t lds = 0;
-  if (point_query) {
-    N.fixed = cloud_dev(fixed, nullptr); N.moving = cloud_dev(moving, nullptr);
-    N.use_distmap = sp->finder == LSM2D_FINDER_DISTMAP; N.use_kd = sp->finder == LSM2D_FINDER_KDTREE;
-    const int rc = prepare_point_query(ctx, sp, fixed, N.fixed, "find_correspondences_batch: max_distance must be > 0"); if (rc) return rc;
-    N.max_distance = sp->max_distance; N.normal_cos = sp->normal_cos; N.inl_tau = inl_tau; N.pair_capacity = capacity;
-  } else {
-    if (!make_projk(sp->projector, &A.proj)) return fail(ctx, LSM2D_BAD_ARGUMENT, "find_correspondences_batch: bad projector");
-    lds = sizeof(u64) * 2 * (size_t) A.proj.cols;
-    if ((int) lds > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "find_correspondences_batch: canvases do not fit LDS");
-    A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr);
-    A.point_distance = sp->point_distance; A.normal_cos = sp->normal_cos; A.inl_tau = inl_tau; A.pair_capacity = capacity;
-  }
+  FindBatchLaunch P;
+  { const int rc = find_batch_prepare(ctx, sp, fixed, moving, inl_tau, capacity, "find_correspondences_batch", P); if (rc) return rc; }
   size_t per_launch = kFindBatchPairBudget / (size_t) (capacity > 0 ? capacity : 1);
   if (per_launch < 1) per_launch = 1;
   if (per_launch > (size_t) n) per_launch = (size_t) n;
@@ -152,21 +190,10 @@ static int find_batch_impl(lsm2d_context* ctx, const lsm2d_slice_params* sp, con
   char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
   for (size_t k0 = 0; k0 < (size_t) n; k0 += per_launch) {
     const size_t cnt = (size_t) n - k0 < per_launch ? (size_t) n - k0 : per_launch;
-    FindItem* items = (FindItem*) hs;
-    for (size_t k = 0; k < cnt; ++k) {
-      FindItem& it = items[k];
-      it.fc = fc[k0 + k]; it.mc = mc[k0 + k]; it.T = make_iso(poses + 3 * (k0 + k)); it.pad = 0;
-      it.nn_group = fixed->h_count[it.fc] >= 4 * (int64_t) moving->h_count[it.mc] ? kNNGroup : 1;      // dense fixed cloud: cooperative search, item by item
-    }
+    find_batch_fill_items((FindItem*) hs, fixed, fc + k0, moving, mc + k0, poses + 3 * k0, cnt);
     HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(FindItem) * cnt, hipMemcpyHostToDevice, ctx->stream));
     if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
-    if (point_query) {
-      N.items = (const FindItem*) ds; N.out_count = (int32_t*) (ds + o_cnt); N.out_pairs = (int32_t*) (ds + o_pairs);
-      hipLaunchKernelGGL(k_find_nn_batch, dim3((unsigned) cnt), dim3(kFindBlock), 0, ctx->stream, N);
-    } else {
-      A.items = (const FindItem*) ds; A.out_count = (int32_t*) (ds + o_cnt); A.out_pairs = (int32_t*) (ds + o_pairs);
-      hipLaunchKernelGGL(k_find_projective_batch, dim3((unsigned) cnt), dim3(kFindBlock), lds, ctx->stream, A);
-    }
+    find_batch_launch(ctx, P, (const FindItem*) ds, cnt, (int32_t*) (ds + o_cnt), (int32_t*) (ds + o_pairs));
     HIPCHK(ctx, hipGetLastError());
     if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
     note_timed(ctx, ctx->kernel_timing);
@@ -282,7 +309,6 @@ extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp,
 static constexpr size_t kLinBatchPairBudget = (size_t) 2 << 20;
 static constexpr size_t kLinBatchMaxItems = (size_t) 1 << 16;
 
-static inline int lin_blocks(int32_t n_pairs) { int b = (n_pairs + 255) / 256; return b < 1 ? 1 : (b > 1024 ? 1024 : b); }      // lsm2d_linearize's launch shape
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t) 255; }
 
 // where a launch's parts lie in the lane's device scratch and (the first three and the results) in its pinned staging
@@ -399,5 +425,90 @@ extern "C" int lsm2d_linearize_batch(lsm2d_context* ctx, const lsm2d_slice_param
       }
     }
   }
+  return LSM2D_SUCCESS;
+}
+
+// ---- finder + factor for a whole batch: pose hypotheses scored on the device ------------------------------------------------------------------------
+// One result row of the batched factor (kLinOutWords words) as the ABI's H, b and statistics.
+static void lin_row_out(const float* h, float* H, float* b, lsm2d_iteration_stats* s) {
+  H[0] = h[0]; H[1] = h[1]; H[2] = h[2]; H[3] = h[1]; H[4] = h[3]; H[5] = h[4]; H[6] = h[2]; H[7] = h[4]; H[8] = h[5];
+  b[0] = h[6]; b[1] = h[7]; b[2] = h[8];
+  if (s) {
+    int32_t iv[3]; memcpy(iv, h + 11, sizeof iv);
+    s->n_inliers = iv[0]; s->n_outliers = iv[1]; s->n_correspondences = iv[2]; s->chi_inliers = h[9]; s->chi_outliers = h[10];
+    unsigned long long dg; memcpy(&dg, h + kAccumWords, sizeof dg);
+    s->pair_digest_lo = (uint32_t) dg; s->pair_digest_hi = (uint32_t) (dg >> 32);
+  }
+}
+
+// The batch finder's kernels write every item's pairs into its slot of the lane's device scratch and its count next to them; the k_score_* kernels linearise
+// them there.  A slot is the slice's largest possible vector (find_batch_need), so a launch group takes kFindBatchPairBudget / slot items (at least one, at
+// most kLinBatchMaxItems): the groups are queued one behind the other on the stream and reuse the same pair and partial-row scratch, while the items'
+// arguments (uploaded once), their counts, digests and result rows are arrays over the whole batch.  One copy down and ONE wait, at the end.
+extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                 const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, float* out_H, float* out_b,
+                                 lsm2d_iteration_stats* st) {
+  if (!ctx || !sp || !fixed || !moving || n_items < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: bad argument");
+  if (fixed->ctx != ctx || moving->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: cloud set from another (or a destroyed) context");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  if (n_items == 0) return LSM2D_SUCCESS;
+  if (!poses || !out_H || !out_b) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: null argument");
+  if (!fixed_index && fixed->n_clouds != 1 && fixed->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: fixed set must hold 1 or n_items clouds");
+  if (!moving_index && moving->n_clouds != 1 && moving->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: moving set must hold 1 or n_items clouds");
+  const size_t n = (size_t) n_items;
+  std::vector<int32_t> fc(n), mc(n);
+  for (int32_t i = 0; i < n_items; ++i) {
+    fc[(size_t) i] = fixed_index ? fixed_index[i] : (fixed->n_clouds == 1 ? 0 : i);
+    mc[(size_t) i] = moving_index ? moving_index[i] : (moving->n_clouds == 1 ? 0 : i);
+    if (!valid_cloud_index(fixed, fc[(size_t) i]) || !valid_cloud_index(moving, mc[(size_t) i])) {
+      char msg[160]; snprintf(msg, sizeof msg, "score_batch: item %d: cloud index out of range", (int) i);
+      return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
+    }
+  }
+  long long need = 0;
+  { const int rc0 = find_batch_need(sp, moving, &need); if (rc0) return rc0; }
+  if (need < 0 || need > 0x7fffffffll) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: bad projector");
+  const int32_t slot = (int32_t) need;
+  FindBatchLaunch P;
+  { const int rc = find_batch_prepare(ctx, sp, fixed, moving, 0.0f, slot, "score_batch", P); if (rc) return rc; }
+  size_t per_group = kFindBatchPairBudget / (size_t) (slot > 0 ? slot : 1);
+  if (per_group > kLinBatchMaxItems) per_group = kLinBatchMaxItems;
+  if (per_group < 1) per_group = 1;
+  if (per_group > n) per_group = n;
+  const size_t B = (size_t) lin_blocks(slot);
+  // device: [items | counts | digests | result rows] over the whole batch, then [pairs | partial rows] of one launch group; host: items up, rows down
+  const size_t o_cnt = up256(sizeof(FindItem) * n), o_dig = up256(o_cnt + sizeof(int32_t) * n), o_out = up256(o_dig + sizeof(unsigned long long) * n);
+  const size_t o_pairs = up256(o_out + sizeof(float) * kLinOutWords * n), o_part = up256(o_pairs + sizeof(lsm2d_correspondence) * per_group * (size_t) slot);
+  const size_t d_bytes = o_part + sizeof(float) * kAccumWords * per_group * B;
+  const size_t h_out = up256(sizeof(FindItem) * n), h_bytes = h_out + sizeof(float) * kLinOutWords * n;
+  { int rc = ensure_scratch(ctx, d_bytes); if (rc) return rc; rc = ensure_stage(ctx, h_bytes); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  find_batch_fill_items((FindItem*) hs, fixed, fc.data(), moving, mc.data(), poses, n);
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(FindItem) * n, hipMemcpyHostToDevice, ctx->stream));
+  if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + o_dig, 0, sizeof(unsigned long long) * n, ctx->stream));
+  ScoreBatchArgs S;
+  S.fixed = P.point_query ? P.N.fixed : P.A.fixed; S.moving = P.point_query ? P.N.moving : P.A.moving;
+  S.slot = slot; S.blocks_per_item = (int32_t) B; S.cauchy = sp->robustifier == LSM2D_ROBUST_CAUCHY; S.tau = sp->chi_threshold;
+  S.pairs = (const int32_t*) (ds + o_pairs); S.partial = (float*) (ds + o_part);
+  for (size_t k0 = 0; k0 < n; k0 += per_group) {
+    const size_t cnt = n - k0 < per_group ? n - k0 : per_group;
+    const bool timed = ctx->kernel_timing && k0 + cnt == n;      // the last launch group, finder and factor together
+    S.items = (const FindItem*) ds + k0; S.count = (const int32_t*) (ds + o_cnt) + k0; S.n_items = (int32_t) cnt;
+    S.dig = (unsigned long long*) (ds + o_dig) + k0; S.out = (float*) (ds + o_out) + kLinOutWords * k0;
+    if (timed) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+    find_batch_launch(ctx, P, S.items, cnt, (int32_t*) (ds + o_cnt) + k0, (int32_t*) (ds + o_pairs));
+    if (ctx->sum_order) hipLaunchKernelGGL(k_score_seq_batch, dim3((unsigned) cnt), dim3(kAlignBlock), 0, ctx->stream, S);      // pair after pair, a workgroup per item
+    else {
+      hipLaunchKernelGGL(k_score_partial_batch, dim3((unsigned) (cnt * B)), dim3(256), 0, ctx->stream, S);
+      hipLaunchKernelGGL(k_score_final_batch, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, ctx->stream, S);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (timed) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  }
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(hs + h_out, ds + o_out, sizeof(float) * kLinOutWords * n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  for (size_t k = 0; k < n; ++k) lin_row_out((const float*) (hs + h_out) + kLinOutWords * k, out_H + 9 * k, out_b + 3 * k, st ? st + k : nullptr);
   return LSM2D_SUCCESS;
 }

@@ -3,13 +3,7 @@
 // In a batch launch one workgroup of kFindBlock threads owns one item (blockIdx.x) from its z-buffers / its first query to its last pair: nobody waits for
 // another workgroup, nothing polls.  The single-call and the batch kernels share their bodies (find_projective_body, find_nn_body, nn_match), so an item's pairs
 // and their order are the single call's (tests/test_gpu_find_batch.py compares them bit for bit).
-struct FindItem {
-  int32_t fc, mc;        // the item's clouds in the fixed / moving set
-  Iso T;                 // local_map_in_sensor
-  int32_t nn_group;      // exact NN: lanes per query (kNNGroup when the item's fixed cloud holds >= 4 x its moving cloud's points, else 1)
-  int32_t pad;
-};
-static_assert(sizeof(FindItem) == 32, "the host fills an array of these");
+// (FindItem, the arguments of one item: lsm2d_k_split_finder.h, where the factor over the batch finder's slots reads it too)
 
 // ---- projective: (fixed, moving, pose) -> pairs in ascending column ------------------------------
 struct FindArgs {

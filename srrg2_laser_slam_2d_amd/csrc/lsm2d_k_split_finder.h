@@ -366,3 +366,68 @@ __global__ __launch_bounds__(kAlignBlock) void k_linearize_seq_batch(const LinBa
   linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau, row,
                      reinterpret_cast<unsigned long long*>(row + kAccumWords), s_rec, red, &s_dig);
 }
+
+// ---- the factor over the batch finder's own slots (lsm2d_score_batch) --------------------------------------------------------------------
+// k_find_projective_batch / k_find_nn_batch leave item i's pairs in slot i of `slot` pairs and its count in count[i], both in device memory; the three kernels
+// below linearise them where they lie, so the pairs never travel.  An item's count is read from the device (clamped to [0, slot]: nothing outside the slot is
+// read, whatever the word holds) instead of from a host-built table, and the bodies are linearize_*_body unchanged: item i has the bits of lsm2d_linearize on
+// the pairs lsm2d_find_correspondences_batch returns.  Tree order: ONE flat launch of n_items x B workgroups, B = lin_blocks(slot); workgroup w is virtual
+// block w % B of item w / B, and of an item's B workgroups the first lin_blocks(count) -- the single call's launch shape for that count -- do its work while
+// the others return before their first barrier.  A second launch, a thread per item, gathers those rows in block order and appends the digest.  Reference
+// order: one workgroup of kAlignBlock threads per item.  Nobody waits for another workgroup; the only atomics are the digest's 64-bit wrapping adds.
+struct FindItem {
+  int32_t fc, mc;        // the item's clouds in the fixed / moving set
+  Iso T;                 // local_map_in_sensor
+  int32_t nn_group;      // exact NN: lanes per query (kNNGroup when the item's fixed cloud holds >= 4 x its moving cloud's points, else 1)
+  int32_t pad;
+};
+static_assert(sizeof(FindItem) == 32, "the host fills an array of these");
+
+LSM2D_HD int lin_blocks(int n_pairs) { const int b = (n_pairs + 255) / 256; return b < 1 ? 1 : (b > 1024 ? 1024 : b); }      // lsm2d_linearize's launch shape
+
+struct ScoreBatchArgs {
+  CloudDev fixed, moving;
+  const FindItem* items;      // [n_items]: the finder's own arguments (clouds and T)
+  const int32_t* count;       // [n_items]: what the finder wrote
+  const int32_t* pairs;       // [n_items][slot][2]: what the finder wrote
+  int32_t n_items, slot, blocks_per_item;      // blocks_per_item = lin_blocks(slot)
+  int32_t cauchy; float tau;
+  float* partial;             // [n_items][blocks_per_item][kAccumWords]
+  unsigned long long* dig;    // [n_items], zeroed by the host (tree order only)
+  float* out;                 // [n_items][kLinOutWords]
+};
+
+LSM2D_DEV int score_count(const ScoreBatchArgs& A, int i) { const int n = A.count[i]; return n < 0 ? 0 : (n > A.slot ? A.slot : n); }
+
+// (item and virtual block are the same in every lane: through readfirstlane they and what is fetched by them stay in scalar registers)
+__global__ __launch_bounds__(256) void k_score_partial_batch(const ScoreBatchArgs A) {
+  __shared__ float red[4 * kAccumWords];
+  __shared__ u64 s_dig;
+  const int i = __builtin_amdgcn_readfirstlane((int) (blockIdx.x / (unsigned) A.blocks_per_item));
+  const int blk = __builtin_amdgcn_readfirstlane((int) (blockIdx.x % (unsigned) A.blocks_per_item));
+  const int n = __builtin_amdgcn_readfirstlane(score_count(A, i));
+  const int nblk = lin_blocks(n);
+  if (blk >= nblk) return;      // the whole workgroup, before any barrier
+  const FindItem it = A.items[i];
+  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) i * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, blk, nblk,
+                         A.partial + (size_t) blockIdx.x * kAccumWords, A.dig + i, red, &s_dig);
+}
+
+__global__ __launch_bounds__(256) void k_score_final_batch(const ScoreBatchArgs A) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n_items) return;
+  float* row = A.out + (size_t) i * kLinOutWords;
+  linearize_final_body(A.partial + (size_t) i * (size_t) A.blocks_per_item * kAccumWords, lin_blocks(score_count(A, i)), row);
+  *reinterpret_cast<unsigned long long*>(row + kAccumWords) = A.dig[i];
+}
+
+__global__ __launch_bounds__(kAlignBlock) void k_score_seq_batch(const ScoreBatchArgs A) {
+  __shared__ __attribute__((aligned(16))) float s_rec[kSeqHalf * kSeqFields];
+  __shared__ float red[(kAlignBlock / 64) * kAccumWords];
+  __shared__ u64 s_dig;
+  const FindItem it = A.items[blockIdx.x];
+  const int n = __builtin_amdgcn_readfirstlane(score_count(A, (int) blockIdx.x));
+  float* row = A.out + (size_t) blockIdx.x * kLinOutWords;
+  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) blockIdx.x * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, row,
+                     reinterpret_cast<unsigned long long*>(row + kAccumWords), s_rec, red, &s_dig);
+}

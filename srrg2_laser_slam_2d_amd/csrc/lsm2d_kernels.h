@@ -13,6 +13,7 @@
 //   k_project_canvas   PointNormal2fProjectorPolar::compute: source index / depth / transformed point per column.
 //   k_linearize_*      SE2Plane2PlaneErrorFactor over a correspondence vector (two-stage deterministic reduce).
 //   k_linearize_*_batch  the same factor over a batch of vectors: the same device functions, an item keeps the single call's launch shape.
+//   k_score_*_batch    the same factor over the slots k_find_*_batch has just filled, counts read from the device: the pairs never leave it (lsm2d_score_batch).
 //   k_repack_cloud     AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"

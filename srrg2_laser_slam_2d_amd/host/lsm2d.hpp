@@ -150,6 +150,29 @@ inline std::vector<Linearization> linearizeBatch(Context& ctx, const lsm2d_slice
   return out;
 }
 
+// Finder, then factor, for poses.size() pose hypotheses with the pairs kept on the device (lsm2d_score_batch): item i matches cloud fixed_index[i] of
+// `fixed` against cloud moving_index[i] of `moving` (an empty index vector: cloud i, or the only cloud of a one-cloud set) at poses[i] with the finder `sp`
+// names and linearises what it found there; per item what findCorrespondencesBatch (a finder's computeBatch) followed by linearizeBatch returns, bit for
+// bit, with one copy down and one wait.
+inline std::vector<Linearization> scoreBatch(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving,
+                                             const std::vector<Vector3f>& poses, const std::vector<int32_t>& fixed_index = {},
+                                             const std::vector<int32_t>& moving_index = {}) {
+  const size_t n = poses.size();
+  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
+    throw std::runtime_error("scoreBatch| an index vector is empty or holds one entry per pose");
+  std::vector<float> H(9 * std::max<size_t>(n, 1)), b(3 * std::max<size_t>(n, 1)); std::vector<lsm2d_iteration_stats> st(std::max<size_t>(n, 1));
+  check(lsm2d_score_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
+                          moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, H.data(), b.data(), st.data()),
+        "lsm2d_score_batch", ctx.get());
+  std::vector<Linearization> out(n);
+  for (size_t i = 0; i < n; ++i) {
+    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].H.begin());
+    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].b.begin());
+    out[i].stats = st[i];
+  }
+  return out;
+}
+
 class CorrespondenceFinderProjective2f {
  public:
   explicit CorrespondenceFinderProjective2f(Context& ctx) : _ctx(ctx) {}

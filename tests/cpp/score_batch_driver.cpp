@@ -1,0 +1,83 @@
+// Drives scoreBatch of the C++ host mirror (lsm2d_score_batch):
+//   score_batch_driver scans.bin offsets.bin map.bin poses.bin cols tau sum_order
+// reads n ragged float32 [N,4] scans (int32 offsets [n+1]), one map and n float32 poses, scores the whole batch (scan i fixed, the map moving, the projective
+// finder, a Cauchy robustifier of threshold tau) -- once as it is and once through a reversed index array -- compares every item byte for byte with
+// computeBatch -> linearizeBatch on the same items, and prints the batch's results as JSON (floats as their bit patterns) with the two-call route's pairs.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <lsm2d.hpp>
+
+using namespace lsm2d_host;
+
+template <class T> static std::vector<T> read_all(const char* path) {
+  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
+  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
+  std::vector<T> v((size_t) n);
+  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
+  fclose(f); return v;
+}
+
+static bool same(const Linearization& a, const Linearization& b) {
+  return !memcmp(a.H.data(), b.H.data(), sizeof(float) * 9) && !memcmp(a.b.data(), b.b.data(), sizeof(float) * 3) &&
+         !memcmp(&a.stats, &b.stats, sizeof(lsm2d_iteration_stats));
+}
+
+static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
+
+int main(int argc, char** argv) {
+  if (argc < 8) { fprintf(stderr, "usage: %s scans.bin offsets.bin map.bin poses.bin cols tau sum_order\n", argv[0]); return 2; }
+  try {
+    Context ctx(0);
+    const PointNormal2fVectorCloud all = read_all<PointNormal2f>(argv[1]);
+    const std::vector<int32_t> offs = read_all<int32_t>(argv[2]);
+    PointNormal2fVectorCloud map = read_all<PointNormal2f>(argv[3]);
+    const std::vector<float> pf = read_all<float>(argv[4]);
+    const int cols = atoi(argv[5]); const float tau = (float) atof(argv[6]);
+    ctx.setOption("sum_order", atoi(argv[7]));
+    const size_t n = offs.size() - 1;
+    std::vector<PointNormal2fVectorCloud> scans(n);
+    std::vector<Vector3f> poses(n);
+    for (size_t i = 0; i < n; ++i) {
+      scans[i].assign(all.begin() + offs[i], all.begin() + offs[i + 1]);
+      poses[i] = Vector3f{{pf[3 * i], pf[3 * i + 1], pf[3 * i + 2]}};
+    }
+    CloudSet scan_set(ctx, scans), map_set(ctx, map);
+
+    CorrespondenceFinderProjective2f cf(ctx);
+    cf.param_projector->param_canvas_cols = cols; cf.param_projector->param_range_max = 30.f;
+    cf.param_projector->param_angle_col_min = -(float) M_PI; cf.param_projector->param_angle_col_max = (float) M_PI;
+    lsm2d_slice_params sp = cf.sliceParams();
+    sp.robustifier = LSM2D_ROBUST_CAUCHY; sp.chi_threshold = tau;
+
+    const std::vector<Linearization> batch = scoreBatch(ctx, sp, scan_set, map_set, poses);
+    // ... a reversed index array: item i is scan n-1-i
+    std::vector<int32_t> rev(n); std::vector<Vector3f> rposes(n);
+    for (size_t i = 0; i < n; ++i) { rev[i] = (int32_t) (n - 1 - i); rposes[i] = poses[n - 1 - i]; }
+    const std::vector<Linearization> batch_rev = scoreBatch(ctx, sp, scan_set, map_set, rposes, rev);
+    // the two-call route in the same program
+    const std::vector<CorrespondenceVector> pairs = cf.computeBatch(scan_set, map_set, poses);
+    const std::vector<Linearization> two = linearizeBatch(ctx, sp, scan_set, map_set, pairs, poses);
+
+    int equal_two_calls = two.size() == n && batch.size() == n, equal_reversed = batch_rev.size() == n;
+    for (size_t i = 0; i < n && equal_two_calls && equal_reversed; ++i) {
+      if (!same(two[i], batch[i])) equal_two_calls = 0;
+      if (!same(batch[i], batch_rev[n - 1 - i])) equal_reversed = 0;
+    }
+    const size_t n_empty = scoreBatch(ctx, sp, scan_set, map_set, std::vector<Vector3f>()).size();
+
+    printf("{\"n\": %zu, \"equal_two_calls\": %d, \"equal_reversed\": %d, \"n_empty\": %zu, \"items\": [", n, equal_two_calls, equal_reversed, n_empty);
+    for (size_t i = 0; i < n; ++i) {
+      const Linearization& r = batch[i];
+      printf("%s{\"H\": [", i ? "," : "");
+      for (int k = 0; k < 9; ++k) printf("%s%u", k ? "," : "", bits(r.H[(size_t) k]));
+      printf("], \"b\": [%u,%u,%u], \"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u], \"pairs\": [", bits(r.b[0]), bits(r.b[1]), bits(r.b[2]),
+             r.stats.n_correspondences, r.stats.n_inliers, r.stats.n_outliers, bits(r.stats.chi_inliers), bits(r.stats.chi_outliers),
+             r.stats.pair_digest_lo, r.stats.pair_digest_hi);
+      for (size_t k = 0; k < pairs[i].size(); ++k) printf("%s[%d,%d]", k ? "," : "", pairs[i][k].fixed_idx, pairs[i][k].moving_idx);
+      printf("]}");
+    }
+    printf("]}\n");
+  } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
+  return 0;
+}
