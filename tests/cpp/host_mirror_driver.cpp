@@ -4,6 +4,7 @@
 // reads two float32 [N,4] clouds, runs the finder at the given pose and the aligner from it, prints JSON.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <lsm2d.hpp>
 
 using namespace lsm2d_host;
@@ -68,6 +69,20 @@ int main(int argc, char** argv) {
       n_kept = al2.correspondences(0).size(); its_runs = al2.iterationStats().size(); last_inl = al2.iterationStats().back().n_inliers;
     }
 
+    // a damped Gauss-Newton step and a prior whose information matrix is full and NOT symmetric (taken as given, row-major), its mean away from the
+    // start pose: status, iterations and the bits of the pose and of all nine information entries, for the caller to compare with its own call
+    // (three iterations: short of convergence, where the damping no longer shows in the pose)
+    int d_status = 0; size_t d_its = 0; uint32_t d_bits[12];
+    { MultiAligner2D al3(ctx);
+      al3.param_max_iterations = 3; al3.param_damping = 50.f; al3.param_slice_processors.push_back(slice);
+      al3.setFixed(&fixed_props); al3.setMoving(&moving_props); al3.setMovingInFixed(pose);
+      al3.setPrior(Vector3f{{pose[0] + 0.05f, pose[1] - 0.03f, pose[2] + 0.4f}}, std::array<float, 9>{{36.f, 19.f, -18.f, 15.f, 31.25f, 0.f, -21.f, 0.f, 27.25f}});
+      al3.compute();
+      d_status = al3.status(); d_its = al3.iterationStats().size();
+      for (int k = 0; k < 3; ++k) memcpy(&d_bits[k], &al3.movingInFixed()[(size_t) k], 4);
+      for (int k = 0; k < 9; ++k) memcpy(&d_bits[3 + k], &al3.informationMatrix()[(size_t) k], 4);
+    }
+
     // the other two finders and the mapping steps, through their reference-named classes
     CorrespondenceVector nn_pairs, dm_pairs, kd_pairs;
     { CorrespondenceFinderKDTree2D kd(ctx, "exact"); kd.param_max_distance_m = 0.3f;      // the exact grid search
@@ -97,9 +112,12 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < correspondences.size(); ++i) printf("%s[%d,%d]", i ? "," : "", correspondences[i].fixed_idx, correspondences[i].moving_idx);
     const Vector3f& x = aligner.movingInFixed();
     printf("], \"status\": %d, \"pose\": [%.9g, %.9g, %.9g], \"iterations\": %zu, \"last_n_corr\": %d, \"n_all\": %zu, \"digest_matches\": %d, \"n_kept\": %zu, "
-           "\"iterations_with_inlier_runs\": %zu, \"last_inliers_with_inlier_runs\": %d}\n", aligner.status(), x[0], x[1], x[2],
+           "\"iterations_with_inlier_runs\": %zu, \"last_inliers_with_inlier_runs\": %d, ", aligner.status(), x[0], x[1], x[2],
            aligner.iterationStats().size(), aligner.iterationStats().empty() ? 0 : aligner.iterationStats().back().n_correspondences,
            n_all, (int) (dig_stats == dig_pairs && dig_stats != 0), n_kept, its_runs, last_inl);
+    printf("\"damped\": {\"status\": %d, \"iterations\": %zu, \"bits\": [", d_status, d_its);
+    for (int k = 0; k < 12; ++k) printf("%s%u", k ? "," : "", d_bits[k]);
+    printf("]}}\n");
   } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
   return 0;
 }

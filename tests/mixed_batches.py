@@ -63,11 +63,15 @@ def _slice_clouds(world, robots, S, beams, fov, few, seed):
     return np.ascontiguousarray(np.concatenate(parts, 0), np.float32), offs, first
 
 
-def batch(seed: int, n: int, setting: str):
+def batch(seed: int, n: int, setting: str, damping: float = 0.0, full_omega: bool = False):
     """The first n alignments of a setting's mixed batch.  Returns a dict: kinds [n] (str), x0 float32 [n, 3], priors (list of (z, omega) or None),
     fixed_index int32 [ns, n], map (the one moving cloud, float32 [20000, 4]), slices (per slice: cols, cauchy, tau, S, min_corr, pts, offs), aligner
-    parameters (max_iterations, min_num_inliers, termination_chi_epsilon, inlier_only, keep_only_inlier)."""
+    parameters (max_iterations, min_num_inliers, termination_chi_epsilon, inlier_only, keep_only_inlier, damping).
+    damping: the Gauss-Newton damping aligner() and oracle_align() pass on.  full_omega (settings with priors): every prior's information matrix is a full
+    symmetric positive definite L L^T instead of a diagonal, and its mean is turned by a further rotation, so that the prior's own rotation is not the
+    identity at the start.  Neither touches a draw of the batch itself: what full_omega needs comes from a generator of its own."""
     assert setting in SETTINGS and 0 < n <= NMAX, (setting, n)
+    assert not full_omega or setting in ("S2", "S3"), setting
     rng = np.random.default_rng([seed, SETTINGS.index(setting)])
     world, m, robots = _world()
     kinds = _kinds(rng)
@@ -102,15 +106,24 @@ def batch(seed: int, n: int, setting: str):
         z = synth.invert_poses(synth.compose_poses(robots[robot], rng.uniform(-0.01, 0.01, (NMAX, 3)))).astype(np.float32)
         w = (rng.uniform(5.0, 60.0, (NMAX, 3)) * (rng.random(NMAX) < 0.5)[:, None]).astype(np.float32)
         priors = [(z[i], np.diag(w[i])) for i in range(n)]
+        if full_omega:
+            rng_f = np.random.default_rng([seed, SETTINGS.index(setting), 1])
+            diag = rng_f.uniform(3.0, 8.0, (NMAX, 3)); low = rng_f.uniform(-3.0, 3.0, (NMAX, 3)); turn = rng_f.uniform(-0.4, 0.4, NMAX)
+            z[:, 2] = ((z[:, 2].astype(np.float64) + turn + math.pi) % (2.0 * math.pi) - math.pi).astype(np.float32)
+            priors = []
+            for i in range(n):
+                L = np.array([[diag[i, 0], 0.0, 0.0], [low[i, 0], diag[i, 1], 0.0], [low[i, 1], low[i, 2], diag[i, 2]]])
+                priors.append((z[i], (L @ L.T).astype(np.float32)))
     if setting == "S2":
         params.update(termination_chi_epsilon=1e-3, inlier_only=True, keep_only_inlier=True)
+    params["damping"] = float(damping)
     return dict(setting=setting, seed=seed, n=n, ns=len(slices), kinds=kinds[:n], x0=x0[:n].copy(), priors=priors,
                 fixed_index=np.ascontiguousarray(np.stack(fixed_index)[:, :n]), map=m, slices=slices, **params)
 
 
 def aligner(ctx, spec):
     """the api aligner of a batch (ctx may be None: parameters only)"""
-    al = api.MultiAligner2D(ctx, max_iterations=spec["max_iterations"], min_num_inliers=spec["min_num_inliers"],
+    al = api.MultiAligner2D(ctx, max_iterations=spec["max_iterations"], min_num_inliers=spec["min_num_inliers"], damping=spec["damping"],
                             termination_chi_epsilon=spec["termination_chi_epsilon"])
     al.param_enable_inlier_only_runs = spec["inlier_only"]
     al.param_keep_only_inlier_correspondences = spec["keep_only_inlier"]
@@ -124,10 +137,11 @@ def aligner(ctx, spec):
     return al
 
 
-def oracle_align(po, spec, i, device_order=False, want_pairs=False):
-    """po.align of alignment i: the device-order fp32 oracle (device_order=True, the tree order) or the sequential one (the reference's order)"""
+def oracle_align(po, spec, i, device_order=False, want_pairs=False, double=False):
+    """po.align of alignment i: the device-order fp32 oracle (device_order=True, the tree order) or the sequential one (the reference's order); double: the
+    fp64 oracle"""
     kw = dict(prior_z=spec["priors"][i][0], prior_omega=spec["priors"][i][1]) if spec["priors"] is not None else {}
-    ap = po.aligner_params(spec["max_iterations"], min_num_inliers=spec["min_num_inliers"], device_order=device_order,
+    ap = po.aligner_params(spec["max_iterations"], min_num_inliers=spec["min_num_inliers"], damping=spec["damping"], device_order=device_order,
                            termination_chi_epsilon=spec["termination_chi_epsilon"], enable_inlier_only_runs=spec["inlier_only"],
                            keep_only_inlier_correspondences=spec["keep_only_inlier"], **kw)
     osl = [oracle_slice(po, p.slice_params()) for p in aligner(None, spec).param_slice_processors]      # the values the api hands the library
@@ -135,4 +149,36 @@ def oracle_align(po, spec, i, device_order=False, want_pairs=False):
     for s, sl in enumerate(spec["slices"]):
         c = int(spec["fixed_index"][s, i])
         fixed.append(sl["pts"][sl["offs"][c]:sl["offs"][c + 1]])
-    return po.align(ap, osl, fixed, [spec["map"]] * spec["ns"], spec["x0"][i], want_pairs=want_pairs)
+    return po.align(ap, osl, fixed, [spec["map"]] * spec["ns"], spec["x0"][i], want_pairs=want_pairs, double=double)
+
+
+# ---- what tests/test_damping_and_prior_cpu.py measures on the oracle and tests/test_gpu_damping_and_prior.py asserts on the device -------------------------
+DAMPING_SEED, DAMPING_N, DAMPING = 2024, 120, 50.0
+MIN_DIFFERENT = 95      # of the 114 finite alignments among the first 120 (the device-order oracle with diagonal priors: S1 98, S3 99 differ from damping 0)
+
+
+def wall_cloud():
+    """test_oracle.py::test_aligner_status_logic's wall: 400 points on y = 2, normals (0, -1) -- nothing observes the translation along it"""
+    return np.stack([np.linspace(-3, 3, 400), np.full(400, 2.0), np.zeros(400), -np.ones(400)], 1).astype(np.float32)
+
+
+# (start, damping, status, iterations), 8 iterations, min_num_correspondences 0: identity start -- b is zero, so every successful step is zero and the pose stays exactly zero
+WALL_ROWS = [((0.0, 0.0, 0.0), 0.0, 3, 1)]
+WALL_ROWS += [((0.0, 0.0, 0.0), lam, 0, 8) for lam in (1e-6, 1e-3, 1.0, 100.0)]
+WALL_ROWS += [((0.0, 0.0, 0.0), lam, 3, 1) for lam in (-1.0, float("nan"), float("inf"))]
+WALL_OFFSET_START = (0.01, 0.02, 0.003)      # with damping 1 the direction nothing observes is held, the other two converge: Success after 8 iterations
+WALL_OFFSET_TOL = 1e-6                       # the oracle ends within 3.5e-8 of (0.01, 0, 0) in both orders
+
+
+def prior_variants(spec):
+    """the latency-kernel cases: no prior, the batch's (full) matrices, each made asymmetric ([0,1] += 4, [2,0] -= 3), and those transposed"""
+    asym = []
+    for z, om in spec["priors"]:
+        a = om.copy(); a[0, 1] += 4.0; a[2, 0] -= 3.0
+        asym.append((z, a))
+    return dict(none=None, full=spec["priors"], asymmetric=asym, transposed=[(z, a.T.copy()) for z, a in asym])
+
+
+def with_slices(spec, ns, **changes):
+    """the batch with its first ns slices only (and whatever else is to change)"""
+    return dict(spec, ns=ns, slices=spec["slices"][:ns], fixed_index=np.ascontiguousarray(spec["fixed_index"][:ns]), **changes)

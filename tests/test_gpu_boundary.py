@@ -252,6 +252,22 @@ def test_cpp_host_mirror_driver(ctx, po, small_workload, tmp_path):
     o_run = po.align(po.aligner_params(20, device_order=True, enable_inlier_only_runs=True, keep_only_inlier_correspondences=True), [spc], [f], [wl.map_points], x0, want_pairs=True)
     assert r["digest_matches"] == 1 and r["n_all"] == len(o_all["pairs"][0]) and r["iterations_with_inlier_runs"] == o_run["iterations"] == 40
     assert r["n_kept"] == len(o_run["pairs"][0]) == r["last_inliers_with_inlier_runs"] == o_run["stats"][-1].n_in
+    # a damping of 50 and a full, asymmetric prior matrix with its mean away from the start pose, through the C++ mirror: the bits of the Python call and of
+    # the device-order oracle (pose and all nine information entries), and not those of the undamped or the transposed-matrix call (three iterations: after
+    # twenty the damped and the undamped run have converged to the same bits)
+    z = np.float32([x0[0] + np.float32(0.05), x0[1] - np.float32(0.03), x0[2] + np.float32(0.4)])
+    om = np.float32([[36.0, 19.0, -18.0], [15.0, 31.25, 0.0], [-21.0, 0.0, 27.25]])
+    al = _aligner(ctx, its=3); al.param_damping = 50.0
+    fs, ms = api.CloudSet(ctx, f), api.CloudSet(ctx, wl.map_points)
+    py = al.compute_batch([fs], [ms], x0[None, :], priors=[(z, om)])
+    bits = lambda res: np.concatenate([res.pose[0].view(np.uint32), res.information[0].ravel().view(np.uint32)]).tolist()
+    od = po.align(po.aligner_params(3, damping=50.0, prior_z=z, prior_omega=om, device_order=True), [po.slice_params()], [f], [wl.map_points], x0)
+    assert r["damped"]["status"] == int(py.status[0]) == od["status"] == 0 and r["damped"]["iterations"] == int(py.iterations[0]) == od["iterations"] == 3
+    assert r["damped"]["bits"] == bits(py)
+    assert r["damped"]["bits"] == np.concatenate([od["pose"].view(np.uint32), od["H"].ravel().view(np.uint32)]).tolist()
+    assert r["damped"]["bits"][:3] != bits(al.compute_batch([fs], [ms], x0[None, :], priors=[(z, om.T.copy())]))[:3]
+    al.param_damping = 0.0
+    assert r["damped"]["bits"][:3] != bits(al.compute_batch([fs], [ms], x0[None, :], priors=[(z, om)]))[:3]
     # the other finders and the mapping classes of the C++ mirror give the oracle's counts on the same inputs
     assert r["n_nn"] == len(po.find(po.slice_params(finder=po.FINDER_NN, max_distance=0.3), f, wl.map_points, x0))
     assert r["n_kdtree"] == len(po.find(po.slice_params(finder=po.FINDER_KDTREE_APPROX, max_distance=0.3, kd_max_leaf_range=0.02, kd_min_leaf_points=9), f, wl.map_points, x0))
