@@ -53,7 +53,9 @@ extern "C" {
                              (0.7.2, number unchanged: an addition only) + lsm2d_linearize_batch (the factor over n_items correspondence vectors in one
                                     launch, the single call's bits in both orders of summation);
                              (0.7.3, number unchanged: an addition only) + lsm2d_score_batch (finder, then factor, for n_items pose hypotheses with the
-                                    pairs kept on the device: one copy down and one wait per call, the bits of the two batch calls in sequence) */
+                                    pairs kept on the device: one copy down and one wait per call, the bits of the two batch calls in sequence);
+                             (0.7.4, number unchanged: an addition only) + lsm2d_score_select, lsm2d_select_params, LSM2D_SELECT_MAX_K (lsm2d_score_batch's
+                                    scoring, then the acceptance test and the best k hypotheses ranked on the device: only k rows come down) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -465,6 +467,43 @@ int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* slice,
                       int32_t n_items, const float* poses /* [n_items][3] */,
                       float* out_H /* [n_items][9] */, float* out_b /* [n_items][3] */,
                       lsm2d_iteration_stats* out_stats /* [n_items] or NULL */);
+
+/* lsm2d_score_batch's scoring, then the acceptance test of the candidate loops and the best k of the accepted hypotheses, ranked on the device: what the
+ * loop detector's and the relocaliser's candidate loops (MULTI.json:964-986, :749-769) ask of n_items scored hypotheses -- "which pass, and which of those
+ * are best?" -- without n_items result rows travelling to the host and being scanned there.
+ * Scoring: every item is scored exactly as lsm2d_score_batch scores it -- the same kernels, the same launch groups, the same bits in both values of
+ * "sum_order" -- and its row stays on the device.
+ * Acceptance, in fp32 with IEEE division (LoopClosureSweep::accept of host/lsm2d.hpp without its status term): item i is accepted when
+ *     n_inliers >= min_inliers,   chi_inliers / max((float) n_inliers, 1.f) <= max_chi_per_inlier,
+ *     (float) n_inliers / (float) max(n_correspondences, 1) >= min_inlier_ratio.
+ * A NaN on either side of a comparison rejects the item; {0, +Inf, 0} accepts every item whose chi_inliers is not NaN.
+ * Ranking of the accepted items, a total order (the result is unique): n_inliers descending, then chi_inliers ascending compared on its bit pattern as
+ * uint32 (its order as a value: the sum is non-negative and not NaN), then item index ascending.  What the reference's relocaliser ranks by is not in its
+ * tree: the order is an assumption of this build (PARITY.md section 3).
+ * Outputs: *out_n_accepted the number of accepted items among all n_items; *out_n_selected = min(k, n_accepted); out_index[0 .. n_selected) the item
+ * indices, best first; rows j < n_selected of out_H / out_b / out_stats (each may be NULL) the bits lsm2d_score_batch returns for item out_index[j].
+ * Entries at positions >= n_selected are not written.
+ * 1 <= k <= LSM2D_SELECT_MAX_K: another k, a NULL select, out_index or count pointer is LSM2D_BAD_ARGUMENT, returned before anything is launched or
+ * written.  n_items == 0 succeeds and sets both counts to 0.  Cloud-index and capacity errors and the refusal with two batches in flight are those of
+ * lsm2d_score_batch; nothing is written then, the counts included.
+ * Up: the items' arguments, once.  Down: ONE copy of the two counts, k indices and k rows (16 + 68 k bytes, whatever n_items is).  ONE wait, at the end of
+ * the call, however many launch groups the batch needs.  "kernel_timing" / lsm2d_last_kernel_ms cover the last launch group plus the selection. */
+#define LSM2D_SELECT_MAX_K 1024
+typedef struct {
+  int32_t min_inliers;          /* relocalize_min_inliers        (MULTI.json:982 / :765) */
+  float   max_chi_per_inlier;   /* relocalize_max_chi_inliers    (:979 / :762) */
+  float   min_inlier_ratio;     /* relocalize_min_inliers_ratio  (:985 / :768) */
+} lsm2d_select_params;
+
+int lsm2d_score_select(lsm2d_context* ctx, const lsm2d_slice_params* slice,
+                       const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                       const lsm2d_cloudset* moving, const int32_t* moving_index,
+                       int32_t n_items, const float* poses /* [n_items][3] */,
+                       const lsm2d_select_params* select, int32_t k,
+                       int32_t* out_index /* [k] */,
+                       float* out_H /* [k][9] or NULL */, float* out_b /* [k][3] or NULL */,
+                       lsm2d_iteration_stats* out_stats /* [k] or NULL */,
+                       int32_t* out_n_selected, int32_t* out_n_accepted);
 
 /* ---- plugin interface #2: MultiAligner2D::compute, batched --------------------------------------
  * Replaces aligner->setFixed / setMoving / setMovingInFixed / compute / movingInFixed /

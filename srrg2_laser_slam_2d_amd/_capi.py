@@ -54,6 +54,15 @@ class IterationStats(C.Structure):
         return (int(self.pair_digest_hi) << 32) | int(self.pair_digest_lo)
 
 
+class SelectParamsC(C.Structure):
+    """lsm2d_select_params"""
+    _fields_ = [("min_inliers", C.c_int32), ("max_chi_per_inlier", C.c_float), ("min_inlier_ratio", C.c_float)]
+
+
+SELECT_MAX_K = 1024      # LSM2D_SELECT_MAX_K
+SELECT_TILE = 2048       # entries a workgroup of k_select_tile sorts (kSelectTile, csrc/lsm2d_k_select.h): where the selection takes another pass
+
+
 class Preprocessor(C.Structure):
     _fields_ = [("n_beams", C.c_int32), ("angle_min", C.c_float), ("angle_max", C.c_float), ("range_min", C.c_float),
                 ("range_max", C.c_float), ("normal_point_distance", C.c_float), ("normal_min_points", C.c_int32),
@@ -124,6 +133,8 @@ SYMBOLS = [
     ("lsm2d_find_correspondences_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("lsm2d_linearize_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("lsm2d_score_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("lsm2d_score_select", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, C.POINTER(SelectParamsC), C.c_int32, _P, _P, _P, _P,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

@@ -28,6 +28,7 @@ import numpy as np
 from . import _capi
 from ._capi import (FINDER_NN, FINDER_PROJECTIVE, ROBUST_CAUCHY, ROBUST_NONE, AlignerParams, Batch, Correspondence,
                     IterationStats, Lsm2dError, Prior, Projector, SliceParams, check)
+from ._capi import SELECT_MAX_K, SELECT_TILE      # noqa: F401  (LSM2D_SELECT_MAX_K; the selection's tile: where it takes another pass)
 
 STATUS_NAMES = {0: "Success", 1: "NotEnoughCorrespondences", 2: "NotEnoughInliers", 3: "SingularH"}
 
@@ -828,6 +829,115 @@ def score_accept(stats, relocalize_min_inliers: int = 500, relocalize_max_chi_in
     n_in = np.array([s.n_inliers for s in stats], np.float64); n_c = np.array([max(s.n_correspondences, 1) for s in stats], np.float64)
     chi = np.array([s.chi_inliers for s in stats], np.float64)
     return (n_in >= relocalize_min_inliers) & (chi / np.maximum(n_in, 1.0) <= relocalize_max_chi_inliers) & (n_in / n_c >= relocalize_min_inliers_ratio)
+
+
+@dataclasses.dataclass
+class SelectParams:
+    """lsm2d_select_params: the thresholds of the candidate loops' acceptance test.  The class defaults are the loop detector's (MULTI.json:964-986),
+    ``relocalizer()`` gives the relocaliser's (:749-769)."""
+    min_inliers: int = 500
+    max_chi_per_inlier: float = 0.1
+    min_inlier_ratio: float = 0.8
+
+    @classmethod
+    def relocalizer(cls) -> "SelectParams":
+        return cls(700, 0.01, 0.75)
+
+    def struct(self) -> _capi.SelectParamsC:
+        return _capi.SelectParamsC(int(self.min_inliers), float(self.max_chi_per_inlier), float(self.min_inlier_ratio))
+
+
+def _stats_array(stats) -> np.ndarray:
+    """a list of IterationStats or a structured array as a structured STATS_DTYPE array [n]"""
+    if isinstance(stats, np.ndarray):
+        return stats.reshape(-1)
+    out = np.zeros(len(stats), STATS_DTYPE)
+    for i, s in enumerate(stats):
+        out[i] = (s.n_correspondences, s.n_inliers, s.n_outliers, s.chi_inliers, s.chi_outliers, s.pair_digest_lo, s.pair_digest_hi)
+    return out
+
+
+def _select_accept(st: np.ndarray, select: SelectParams) -> np.ndarray:
+    """lsm2d_score_select's acceptance test in numpy float32 (IEEE division, like the kernel's): bool [n]; a NaN on either side of a comparison rejects"""
+    n_in = st["n_inliers"].astype(np.float32)
+    n_c = np.maximum(st["n_correspondences"], 1).astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        per_inlier = st["chi_inliers"].astype(np.float32) / np.maximum(n_in, np.float32(1.0))
+        ratio = n_in / n_c
+        return (st["n_inliers"] >= np.int32(select.min_inliers)) & (per_inlier <= np.float32(select.max_chi_per_inlier)) & \
+               (ratio >= np.float32(select.min_inlier_ratio))
+
+
+def score_rank(stats, select: SelectParams, k: int):
+    """lsm2d_score_select's acceptance test and ranking on statistics the caller already holds (from ``score_batch``, an aligner or the oracle), in numpy
+    float32 / integer arithmetic: accepted are the items with inliers >= min, chi_inliers / max(inliers, 1) <= max and inliers / max(correspondences, 1) >=
+    ratio; they are ranked by inliers descending, then chi_inliers ascending on its bit pattern as uint32, then index ascending.  ``stats``: a list of
+    IterationStats or a structured STATS_DTYPE array.  Returns ``(index int32 [min(k, n_accepted)], n_accepted)``."""
+    if k < 1:
+        raise ValueError("score_rank: k must be >= 1")
+    st = _stats_array(stats)
+    ok = np.flatnonzero(_select_accept(st, select))
+    key = ((np.uint64(0x7fffffff) - st["n_inliers"][ok].astype(np.uint64)) << np.uint64(32)) | \
+        np.ascontiguousarray(st["chi_inliers"][ok], np.float32).view(np.uint32).astype(np.uint64)
+    order = np.lexsort((ok, key))      # by key, ties by index
+    return ok[order][:k].astype(np.int32), int(len(ok))
+
+
+def score_select(ctx: Context, slice_params: SliceParams, fixed, moving, poses, select: SelectParams, k: int, fixed_index=None, moving_index=None):
+    """``score_batch``'s scoring, then the acceptance test and the best ``k`` accepted hypotheses ranked on the device (lsm2d_score_select): only ``k`` rows
+    come down, with one copy and one wait.  Returns ``(index int32 [m], H [m, 3, 3], b [m, 3], stats structured STATS_DTYPE [m], n_accepted)``,
+    ``m = min(k, n_accepted)``, best first: ``index`` is what ``score_rank`` gives on ``score_batch``'s statistics, the rows are ``score_batch``'s for
+    those items, bit for bit."""
+    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
+    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+    n = len(x)
+    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
+    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
+    kk = max(int(k), 1)
+    index = np.empty(kk, np.int32); H = np.empty((kk, 9), np.float32); b = np.empty((kk, 3), np.float32); st = np.zeros(kk, STATS_DTYPE)
+    n_sel = C.c_int32(0); n_acc = C.c_int32(0)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_score_select(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
+                                      mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, x.ctypes.data_as(C.c_void_p),
+                                      C.byref(sel), int(k), index.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                      st.ctypes.data_as(C.c_void_p), C.byref(n_sel), C.byref(n_acc)),
+          "lsm2d_score_select", ctx.handle)
+    m = n_sel.value
+    return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], n_acc.value
+
+
+@dataclasses.dataclass
+class RelocalizeResult:
+    index: np.ndarray          # int32 [m]: the selected hypotheses, best first
+    score_stats: np.ndarray    # structured [m]: their statistics at their own poses
+    n_accepted: int            # hypotheses that passed the acceptance test, of all
+    result: BatchResult        # the aligner's results for the selected hypotheses, started from their own poses
+    accepted: np.ndarray       # bool [m]: aligner succeeded and the aligned statistics pass the acceptance test
+
+
+def relocalize(aligner: MultiAligner2D, fixed, moving, poses, select: SelectParams, k: int, fixed_index=None, moving_index=None) -> RelocalizeResult:
+    """The candidate loop of the relocaliser / loop detector (MULTI.json:749-769, :964-986) over ``len(poses)`` hypotheses: ``score_select`` with the
+    aligner's (one) slice, then ``aligner.compute_batch`` on the selected hypotheses from their own poses, then the acceptance test on the statistics of
+    the last iteration each started.  Pure composition: the same as calling the two entry points by hand."""
+    if len(aligner.param_slice_processors) != 1:
+        raise ValueError("relocalize: the aligner must have exactly one slice")
+    ctx = aligner._ctx
+    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
+    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+    n = len(x)
+    index, _, _, st, n_acc = score_select(ctx, aligner.param_slice_processors[0].slice_params(), fx, mv, x, select, k, fixed_index, moving_index)
+
+    def chosen(cs, idx):      # the selected items' clouds, spelled out: NULL means "cloud i" only while the batch is the whole set
+        if idx is None and cs.n_clouds == 1:
+            return None
+        full = np.arange(n, dtype=np.int32) if idx is None else np.ascontiguousarray(idx, np.int32).reshape(n)
+        return full[index][None, :]
+
+    if not len(index):      # nothing passed: nothing to align
+        z = np.zeros
+        return RelocalizeResult(index, st, n_acc, BatchResult(z((0, 3), np.float32), z((0, 3, 3), np.float32), z(0, np.int32), z(0, np.int32), None, 0.0), z(0, bool))
+    res = aligner.compute_batch([fx], [mv], x[index], fixed_index=chosen(fx, fixed_index), moving_index=chosen(mv, moving_index), want_stats=True)
+    return RelocalizeResult(index, st, n_acc, res, (res.status == 0) & _select_accept(res.last_stats(), select))
 
 
 class SceneClipperProjective2D:

@@ -445,42 +445,61 @@ static void lin_row_out(const float* h, float* H, float* b, lsm2d_iteration_stat
 // them there.  A slot is the slice's largest possible vector (find_batch_need), so a launch group takes kFindBatchPairBudget / slot items (at least one, at
 // most kLinBatchMaxItems): the groups are queued one behind the other on the stream and reuse the same pair and partial-row scratch, while the items'
 // arguments (uploaded once), their counts, digests and result rows are arrays over the whole batch.  One copy down and ONE wait, at the end.
-extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
-                                 const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, float* out_H, float* out_b,
-                                 lsm2d_iteration_stats* st) {
-  if (!ctx || !sp || !fixed || !moving || n_items < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: bad argument");
-  if (fixed->ctx != ctx || moving->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: cloud set from another (or a destroyed) context");
+// The scoring is shared by lsm2d_score_batch, which copies every row down, and lsm2d_score_select, which ranks the rows where they lie: score_batch_head is
+// what both check before they look at n_items, score_batch_queue everything from the index rules to the last launch group -- it leaves the rows on the device
+// (ds + o_out), waits for nothing and, with "kernel_timing", has recorded the lane's first event in front of the last group; the caller records the second.
+struct ScoreQueued {
+  size_t n = 0;
+  size_t o_out = 0;       // device: the result rows, [n][kLinOutWords]
+  size_t o_extra = 0;     // device: d_extra bytes of the caller's behind everything the scoring uses
+  size_t h_out = 0;       // staging: h_down bytes of the caller's behind the items' arguments
+};
+
+static int score_batch_head(lsm2d_context* ctx, const char* who, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const lsm2d_cloudset* moving,
+                            int32_t n_items) {
+  char msg[160];
+  if (!ctx || !sp || !fixed || !moving || n_items < 0) { snprintf(msg, sizeof msg, "%s: bad argument", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
+  if (fixed->ctx != ctx || moving->ctx != ctx) {
+    snprintf(msg, sizeof msg, "%s: cloud set from another (or a destroyed) context", who);
+    return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
+  }
   if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  if (n_items == 0) return LSM2D_SUCCESS;
-  if (!poses || !out_H || !out_b) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: null argument");
-  if (!fixed_index && fixed->n_clouds != 1 && fixed->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: fixed set must hold 1 or n_items clouds");
-  if (!moving_index && moving->n_clouds != 1 && moving->n_clouds != n_items) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: moving set must hold 1 or n_items clouds");
+  return LSM2D_SUCCESS;
+}
+
+static int score_batch_queue(lsm2d_context* ctx, const char* who, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                             const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, size_t d_extra, size_t h_down,
+                             ScoreQueued& Q) {
+  char msg[160];
+  if (!fixed_index && fixed->n_clouds != 1 && fixed->n_clouds != n_items) { snprintf(msg, sizeof msg, "%s: fixed set must hold 1 or n_items clouds", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
+  if (!moving_index && moving->n_clouds != 1 && moving->n_clouds != n_items) { snprintf(msg, sizeof msg, "%s: moving set must hold 1 or n_items clouds", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
   const size_t n = (size_t) n_items;
   std::vector<int32_t> fc(n), mc(n);
   for (int32_t i = 0; i < n_items; ++i) {
     fc[(size_t) i] = fixed_index ? fixed_index[i] : (fixed->n_clouds == 1 ? 0 : i);
     mc[(size_t) i] = moving_index ? moving_index[i] : (moving->n_clouds == 1 ? 0 : i);
     if (!valid_cloud_index(fixed, fc[(size_t) i]) || !valid_cloud_index(moving, mc[(size_t) i])) {
-      char msg[160]; snprintf(msg, sizeof msg, "score_batch: item %d: cloud index out of range", (int) i);
+      snprintf(msg, sizeof msg, "%s: item %d: cloud index out of range", who, (int) i);
       return fail(ctx, LSM2D_BAD_ARGUMENT, msg);
     }
   }
   long long need = 0;
   { const int rc0 = find_batch_need(sp, moving, &need); if (rc0) return rc0; }
-  if (need < 0 || need > 0x7fffffffll) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: bad projector");
+  if (need < 0 || need > 0x7fffffffll) { snprintf(msg, sizeof msg, "%s: bad projector", who); return fail(ctx, LSM2D_BAD_ARGUMENT, msg); }
   const int32_t slot = (int32_t) need;
   FindBatchLaunch P;
-  { const int rc = find_batch_prepare(ctx, sp, fixed, moving, 0.0f, slot, "score_batch", P); if (rc) return rc; }
+  { const int rc = find_batch_prepare(ctx, sp, fixed, moving, 0.0f, slot, who, P); if (rc) return rc; }
   size_t per_group = kFindBatchPairBudget / (size_t) (slot > 0 ? slot : 1);
   if (per_group > kLinBatchMaxItems) per_group = kLinBatchMaxItems;
   if (per_group < 1) per_group = 1;
   if (per_group > n) per_group = n;
   const size_t B = (size_t) lin_blocks(slot);
-  // device: [items | counts | digests | result rows] over the whole batch, then [pairs | partial rows] of one launch group; host: items up, rows down
+  // device: [items | counts | digests | result rows] over the whole batch, then [pairs | partial rows] of one launch group, then the caller's; host: items
+  // up, the caller's down
   const size_t o_cnt = up256(sizeof(FindItem) * n), o_dig = up256(o_cnt + sizeof(int32_t) * n), o_out = up256(o_dig + sizeof(unsigned long long) * n);
   const size_t o_pairs = up256(o_out + sizeof(float) * kLinOutWords * n), o_part = up256(o_pairs + sizeof(lsm2d_correspondence) * per_group * (size_t) slot);
-  const size_t d_bytes = o_part + sizeof(float) * kAccumWords * per_group * B;
-  const size_t h_out = up256(sizeof(FindItem) * n), h_bytes = h_out + sizeof(float) * kLinOutWords * n;
+  const size_t o_extra = up256(o_part + sizeof(float) * kAccumWords * per_group * B), d_bytes = o_extra + d_extra;
+  const size_t h_out = up256(sizeof(FindItem) * n), h_bytes = h_out + h_down;
   { int rc = ensure_scratch(ctx, d_bytes); if (rc) return rc; rc = ensure_stage(ctx, h_bytes); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
@@ -504,11 +523,91 @@ extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* s
       hipLaunchKernelGGL(k_score_final_batch, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, ctx->stream, S);
     }
     HIPCHK(ctx, hipGetLastError());
-    if (timed) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   }
+  Q.n = n; Q.o_out = o_out; Q.o_extra = o_extra; Q.h_out = h_out;
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                 const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, float* out_H, float* out_b,
+                                 lsm2d_iteration_stats* st) {
+  { const int rc = score_batch_head(ctx, "score_batch", sp, fixed, moving, n_items); if (rc) return rc; }
+  if (n_items == 0) return LSM2D_SUCCESS;
+  if (!poses || !out_H || !out_b) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_batch: null argument");
+  ScoreQueued Q;
+  { const int rc = score_batch_queue(ctx, "score_batch", sp, fixed, fixed_index, moving, moving_index, n_items, poses, 0, sizeof(float) * kLinOutWords * (size_t) n_items, Q); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  const size_t n = Q.n;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
-  HIPCHK(ctx, hipMemcpyAsync(hs + h_out, ds + o_out, sizeof(float) * kLinOutWords * n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(hs + Q.h_out, ds + Q.o_out, sizeof(float) * kLinOutWords * n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
-  for (size_t k = 0; k < n; ++k) lin_row_out((const float*) (hs + h_out) + kLinOutWords * k, out_H + 9 * k, out_b + 3 * k, st ? st + k : nullptr);
+  for (size_t k = 0; k < n; ++k) lin_row_out((const float*) (hs + Q.h_out) + kLinOutWords * k, out_H + 9 * k, out_b + 3 * k, st ? st + k : nullptr);
+  return LSM2D_SUCCESS;
+}
+
+// ---- ... and ranked on the device: the acceptance test and the best k (lsm2d_k_select.h) ------------------------------------------------------------------------
+// Behind the last launch group, on the same stream: keys and the accepted count (k_select_keys), passes of k_select_tile over two ping-pong arrays of (key,
+// index) entries until one tile is left -- a pass turns m entries into ceil(m / tile) x k, less than half of them while m > tile -- and k_select_gather,
+// which fills the one region that comes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]], 16 + 68 k bytes whatever n_items is.  A
+// batch of at most one tile does all three in ONE launch (k_select_tile_one: four launches and a memset less, which is what counts at 1000 items).
+extern "C" int lsm2d_score_select(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
+                                  const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses,
+                                  const lsm2d_select_params* select, int32_t k, int32_t* out_index, float* out_H, float* out_b, lsm2d_iteration_stats* out_stats,
+                                  int32_t* out_n_selected, int32_t* out_n_accepted) {
+  static_assert(LSM2D_SELECT_MAX_K == kSelectMaxK, "the ABI's limit is the kernels'");
+  if (!select || !out_index || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: null argument");
+  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: k outside [1, LSM2D_SELECT_MAX_K]");
+  { const int rc = score_batch_head(ctx, "score_select", sp, fixed, moving, n_items); if (rc) return rc; }
+  if (n_items == 0) { *out_n_selected = 0; *out_n_accepted = 0; return LSM2D_SUCCESS; }
+  if (!poses) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: null argument");
+  const size_t n = (size_t) n_items, K = (size_t) k;
+  const size_t n_first = ((n + kSelectTile - 1) / kSelectTile) * K;      // what the first pass leaves
+  // the caller's part of the scratch: [keys A | index A] of n entries, [keys B | index B] of n_first, the accepted count, the region that goes down
+  const size_t e_idx_a = up256(sizeof(u64) * n), e_key_b = up256(e_idx_a + sizeof(int32_t) * n), e_idx_b = up256(e_key_b + sizeof(u64) * n_first);
+  const size_t e_acc = up256(e_idx_b + sizeof(int32_t) * n_first), e_down = e_acc + 256;
+  const size_t down_bytes = sizeof(int32_t) * (kSelectHeaderWords + K) + sizeof(float) * kLinOutWords * K;
+  ScoreQueued Q;
+  { const int rc = score_batch_queue(ctx, "score_select", sp, fixed, fixed_index, moving, moving_index, n_items, poses, e_down + down_bytes, down_bytes, Q); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch; char* const de = ds + Q.o_extra;
+  u64* key[2] = {(u64*) de, (u64*) (de + e_key_b)}; int32_t* idx[2] = {(int32_t*) (de + e_idx_a), (int32_t*) (de + e_idx_b)};
+  SelectArgs A;
+  A.rows = (const float*) (ds + Q.o_out); A.n_items = n_items; A.k = k;
+  A.min_inliers = select->min_inliers; A.max_chi_per_inlier = select->max_chi_per_inlier; A.min_inlier_ratio = select->min_inlier_ratio;
+  A.keys = key[0]; A.index = idx[0]; A.n_accepted = (int32_t*) (de + e_acc);
+  if (n <= (size_t) kSelectTile) {      // one tile: keys, sort and gather in one launch of one workgroup
+    int32_t sort_size = 2;
+    while ((size_t) sort_size < n) sort_size <<= 1;
+    hipLaunchKernelGGL(k_select_tile_one, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, (int32_t*) (de + e_down));
+  } else {
+    HIPCHK(ctx, hipMemsetAsync(A.n_accepted, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(k_select_keys, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
+    size_t m = n; int src = 0;
+    for (;;) {      // array A has room for n entries, B for n_first: pass p writes fewer than pass p - 2 read
+      const size_t tiles = (m + kSelectTile - 1) / kSelectTile;
+      hipLaunchKernelGGL(k_select_tile, dim3((unsigned) tiles), dim3(kSelectBlock), 0, ctx->stream, (const u64*) key[src], (const int32_t*) idx[src], (int32_t) m,
+                         k, key[src ^ 1], idx[src ^ 1]);
+      src ^= 1; m = tiles * K;
+      if (tiles == 1) break;
+    }
+    hipLaunchKernelGGL(k_select_gather, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], (int32_t*) (de + e_down));
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));      // the last launch group and the selection
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(hs + Q.h_out, de + e_down, down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  const int32_t* h = (const int32_t*) (hs + Q.h_out);
+  const int32_t n_acc = h[0], n_sel = h[1];
+  if (n_acc < 0 || n_acc > n_items || n_sel != (n_acc < k ? n_acc : k)) return fail(ctx, LSM2D_DEVICE_ERROR, "score_select: the selection's counters are inconsistent");
+  const int32_t* h_index = h + kSelectHeaderWords; const float* h_rows = (const float*) (h + kSelectHeaderWords + K);
+  float H[9], b[3];
+  for (int32_t j = 0; j < n_sel; ++j) {
+    out_index[j] = h_index[j];
+    lin_row_out(h_rows + kLinOutWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : H, out_b ? out_b + 3 * (size_t) j : b, out_stats ? out_stats + j : nullptr);
+  }
+  *out_n_selected = n_sel; *out_n_accepted = n_acc;
   return LSM2D_SUCCESS;
 }

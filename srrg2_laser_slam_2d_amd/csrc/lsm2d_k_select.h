@@ -1,0 +1,154 @@
+// lsm2d_k_select.h -- acceptance test and best-k ranking over the result rows lsm2d_score_batch's kernels leave on the device (lsm2d_score_select).
+// Part of lsm2d_kernels.h (included there, inside namespace lsm2d).
+//
+// The candidate loops of the loop detector and the relocaliser (MULTI.json:964-986, :749-769) ask of n scored hypotheses "which pass the acceptance test, and
+// which of those are best?".  Three kernels answer on the device, behind the last launch group of the scoring, so that only k rows travel:
+//   k_select_keys    a thread per item: the acceptance test on its row, a 64-bit sort key, the number of accepted items.
+//   k_select_tile    a workgroup per tile of kSelectTile (key, index) entries: a bitonic sort in LDS by (key, index), the k smallest written out.  Queued
+//                    again and again over the survivors until one tile is left: ceil(n / tile) x k entries per pass, less than half of what came in.
+//   k_select_gather  the selected rows, their indices and the two counters into ONE contiguous region: what the host copies down.
+//   k_select_tile_one  a batch of at most one tile: the three steps above in ONE launch of one workgroup (the same device functions; the count needs no atomic).
+// The order is total -- n_inliers descending, chi_inliers ascending on its bit pattern, item index ascending -- so the selection is unique; every entry's
+// place after a pass is a function of the entries alone, never of the order in which workgroups run.  The only atomic is one integer add per workgroup of
+// k_select_keys.
+#pragma once
+
+static constexpr int kSelectMaxK = 1024;               // LSM2D_SELECT_MAX_K
+static constexpr int kSelectTile = 2 * kSelectMaxK;    // entries a workgroup of k_select_tile sorts: a power of two, 2 x the largest k, 24 KB of LDS
+static constexpr int kSelectBlock = kSelectTile / 2;   // one compare-exchange per thread and step
+static constexpr u64 kSelectRejected = ~(u64) 0;       // the key of a rejected item and of the padding: above every accepted key, never selected
+static constexpr int kSelectHeaderWords = 4;           // the region that goes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]]
+static_assert((kSelectTile & (kSelectTile - 1)) == 0 && kSelectTile >= 2 * kSelectMaxK, "the tile is a power of two holding two selections");
+static_assert(kSelectTile * (sizeof(u64) + sizeof(int32_t)) < 64 * 1024, "static LDS stays below 64 KB");
+static_assert(kSelectBlock <= 1024, "one workgroup");
+
+struct SelectArgs {
+  const float* rows;          // [n_items][kLinOutWords]: where k_score_final_batch / k_score_seq_batch left them
+  int32_t n_items, k;
+  int32_t min_inliers; float max_chi_per_inlier, min_inlier_ratio;
+  u64* keys; int32_t* index;  // [n_items]: k_select_keys writes, the first pass of k_select_tile reads
+  int32_t* n_accepted;        // one word, zeroed by the host
+};
+
+// The acceptance test of LoopClosureSweep::accept (host/lsm2d.hpp) without its status term, in fp32.  The divisions are IEEE: the library is built without
+// any fast-math flag and hipcc's fp32 divide is correctly rounded by default, so numpy's float32 quotients (api.score_rank) are the same bits.  A NaN on
+// either side of a comparison makes it false: the item is rejected.
+LSM2D_DEV bool select_accept(int32_t n_inliers, int32_t n_correspondences, float chi_inliers, int32_t min_inliers, float max_chi_per_inlier,
+                             float min_inlier_ratio) {
+  const float n_in = (float) n_inliers;
+  const float per_inlier = chi_inliers / fmaxf(n_in, 1.0f);
+  const float ratio = n_in / (float) (n_correspondences > 1 ? n_correspondences : 1);
+  return n_inliers >= min_inliers && per_inlier <= max_chi_per_inlier && ratio >= min_inlier_ratio;
+}
+
+// item i's sort key: (0x7fffffff - n_inliers, chi_inliers' bits) when it is accepted, all ones when it is not
+LSM2D_DEV u64 select_key(const SelectArgs& A, int i, bool* ok) {
+  const float* row = A.rows + (size_t) i * kLinOutWords;      // words 9, 11, 13: chi_inliers, n_inliers, n_correspondences (linearize_final_body)
+  const float chi = row[9];
+  const int32_t n_in = __float_as_int(row[11]), n_c = __float_as_int(row[13]);
+  *ok = select_accept(n_in, n_c, chi, A.min_inliers, A.max_chi_per_inlier, A.min_inlier_ratio);
+  return *ok ? ((u64) (uint32_t) (0x7fffffff - n_in) << 32) | (u64) __float_as_uint(chi) : kSelectRejected;
+}
+
+__global__ __launch_bounds__(256) void k_select_keys(const SelectArgs A) {
+  __shared__ int32_t s_cnt[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool ok = false;
+  if (i < A.n_items) {
+    A.keys[i] = select_key(A, i, &ok);
+    A.index[i] = i;
+  }
+  const unsigned long long m = __ballot(ok);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int32_t c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (c) atomicAdd(A.n_accepted, c);
+  }
+}
+
+LSM2D_DEV bool select_before(u64 ka, int32_t ia, u64 kb, int32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// The first `size_all` entries (a power of two, at most the tile) of (s_key, s_idx) in LDS sorted ascending by (key, index): a bitonic network, one
+// compare-exchange per thread and step, a barrier after every step (and in front of the first).  All pairs (key, index) are distinct -- item indices are --
+// but for the padding, which is equal in both words: the network's result does not depend on how it treats equals.
+LSM2D_DEV void select_sort(u64* s_key, int32_t* s_idx, int size_all) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  for (int size = 2; size <= size_all; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;      // the t-th pair of this step
+      if (hi < size_all) {
+        const bool up = (lo & size) == 0;                              // ascending stretch (the last merge: all of it)
+        const u64 ka = s_key[lo], kb = s_key[hi];
+        const int32_t ia = s_idx[lo], ib = s_idx[hi];
+        if (select_before(kb, ib, ka, ia) == up) { s_key[lo] = kb; s_key[hi] = ka; s_idx[lo] = ib; s_idx[hi] = ia; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Workgroup b sorts entries [b * tile, min((b + 1) * tile, n_in)) of (keys_in, index_in), padded with (all ones, INT32_MAX), and writes the first k of them to
+// entries [b * k, (b + 1) * k) of (keys_out, index_out).
+__global__ __launch_bounds__(kSelectBlock) void k_select_tile(const u64* keys_in, const int32_t* index_in, int32_t n_in, int32_t k, u64* keys_out,
+                                                              int32_t* index_out) {
+  __shared__ u64 s_key[kSelectTile];
+  __shared__ int32_t s_idx[kSelectTile];
+  const int t = threadIdx.x;
+  const long long base = (long long) blockIdx.x * kSelectTile;
+  for (int e = t; e < kSelectTile; e += kSelectBlock) {
+    const long long g = base + e;
+    const bool in = g < (long long) n_in;
+    s_key[e] = in ? keys_in[g] : kSelectRejected;
+    s_idx[e] = in ? index_in[g] : 0x7fffffff;
+  }
+  select_sort(s_key, s_idx, kSelectTile);
+  for (int e = t; e < k; e += kSelectBlock) {
+    keys_out[(size_t) blockIdx.x * (size_t) k + (size_t) e] = s_key[e];
+    index_out[(size_t) blockIdx.x * (size_t) k + (size_t) e] = s_idx[e];
+  }
+}
+
+// n_selected = min(k, n_accepted); header, then the indices and the rows of the first n_selected entries of the sorted (keys, index).  Positions >=
+// n_selected are left alone (the host does not read them).
+LSM2D_DEV void select_gather(const SelectArgs& A, int n_acc, const u64* keys, const int32_t* index, int32_t* down) {
+  const int n_sel = n_acc < A.k ? n_acc : A.k;
+  if (threadIdx.x == 0) { down[0] = n_acc; down[1] = n_sel; down[2] = 0; down[3] = 0; }
+  int32_t* d_index = down + kSelectHeaderWords;
+  int32_t* d_rows = down + kSelectHeaderWords + A.k;
+  const int32_t* rows = reinterpret_cast<const int32_t*>(A.rows);      // words are moved as bits: counts and the digest lie among the sums
+  for (int e = threadIdx.x; e < n_sel * kLinOutWords; e += (int) blockDim.x) {
+    const int j = e / kLinOutWords, w = e % kLinOutWords;
+    const int32_t i = index[j];
+    if (keys[j] == kSelectRejected || (uint32_t) i >= (uint32_t) A.n_items) continue;      // (cannot be: the n_accepted smallest entries are accepted items)
+    if (w == 0) d_index[j] = i;
+    d_rows[e] = rows[(size_t) i * kLinOutWords + w];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_select_gather(const SelectArgs A, const u64* keys, const int32_t* index, int32_t* down) {
+  select_gather(A, *A.n_accepted, keys, index, down);
+}
+
+// n_items <= tile: keys, sort and gather by ONE workgroup in one launch.  `sort_size`: the smallest power of two >= max(n_items, 2) -- the network runs over
+// that many entries only.  The accepted items are counted through LDS: A.keys, A.index and A.n_accepted are not used.
+__global__ __launch_bounds__(kSelectBlock) void k_select_tile_one(const SelectArgs A, int32_t sort_size, int32_t* down) {
+  __shared__ u64 s_key[kSelectTile];
+  __shared__ int32_t s_idx[kSelectTile];
+  __shared__ int32_t s_cnt[kSelectBlock / 64];
+  const int t = threadIdx.x;
+  int mine = 0;
+  for (int e = t; e < sort_size; e += kSelectBlock) {
+    bool ok = false;
+    const bool in = e < A.n_items;
+    s_key[e] = in ? select_key(A, e, &ok) : kSelectRejected;
+    s_idx[e] = in ? e : 0x7fffffff;
+    mine += __popcll(__ballot(ok));      // (over the lanes that are in the loop; lane 0 of a wave is whenever one of its lanes is)
+  }
+  if ((t & 63) == 0) s_cnt[t >> 6] = mine;
+  select_sort(s_key, s_idx, sort_size);
+  int n_acc = 0;
+  for (int w = 0; w < kSelectBlock / 64; ++w) n_acc += s_cnt[w];
+  select_gather(A, n_acc, s_key, s_idx, down);
+}

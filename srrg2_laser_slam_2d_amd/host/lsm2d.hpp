@@ -173,6 +173,81 @@ inline std::vector<Linearization> scoreBatch(Context& ctx, const lsm2d_slice_par
   return out;
 }
 
+// scoreBatch's scoring, then the acceptance test and the best k accepted hypotheses ranked on the device (lsm2d_score_select): only k rows come down, with
+// one copy and one wait.  index[j] is the j-th best hypothesis -- inliers descending, chi_inliers ascending, index ascending -- and rows[j] what scoreBatch
+// returns for it, bit for bit; n_accepted counts the hypotheses that pass among all of them.
+struct Selection {
+  std::vector<int32_t> index; std::vector<Linearization> rows; int32_t n_accepted = 0;
+};
+inline Selection scoreSelect(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
+                             const lsm2d_select_params& select, int32_t k, const std::vector<int32_t>& fixed_index = {},
+                             const std::vector<int32_t>& moving_index = {}) {
+  const size_t n = poses.size();
+  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
+    throw std::runtime_error("scoreSelect| an index vector is empty or holds one entry per pose");
+  const size_t cap = (size_t) std::max<int32_t>(k, 1);
+  std::vector<int32_t> idx(cap); std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap);
+  int32_t n_sel = 0; Selection out;
+  check(lsm2d_score_select(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
+                           moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, &select, k, idx.data(), H.data(),
+                           b.data(), st.data(), &n_sel, &out.n_accepted),
+        "lsm2d_score_select", ctx.get());
+  out.index.assign(idx.begin(), idx.begin() + n_sel); out.rows.resize((size_t) n_sel);
+  for (size_t i = 0; i < (size_t) n_sel; ++i) {
+    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out.rows[i].H.begin());
+    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out.rows[i].b.begin());
+    out.rows[i].stats = st[i];
+  }
+  return out;
+}
+
+// lsm2d_score_select's acceptance test on one item's statistics (fp32, IEEE division)
+inline bool selectAccept(const lsm2d_iteration_stats& st, const lsm2d_select_params& p) {
+  const float n_in = (float) st.n_inliers, n_c = (float) (st.n_correspondences > 1 ? st.n_correspondences : 1);
+  return st.n_inliers >= p.min_inliers && st.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= p.max_chi_per_inlier && n_in / n_c >= p.min_inlier_ratio;
+}
+
+// The candidate loop of the relocaliser / loop detector (MULTI.json:749-769, :964-986) over poses.size() hypotheses of one laser slice: scoreSelect, then
+// lsm2d_align_batch on the selected hypotheses from their own poses, then the acceptance test on the statistics of the last iteration each started.  Pure
+// composition: the same as calling the two entry points by hand.
+struct Relocalization {
+  Selection selection;
+  std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> status, iterations;
+  std::vector<lsm2d_iteration_stats> last_stats; std::vector<char> accepted;
+};
+inline Relocalization relocalize(Context& ctx, const lsm2d_aligner_params& aligner, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving,
+                                 const std::vector<Vector3f>& poses, const lsm2d_select_params& select, int32_t k,
+                                 const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
+  Relocalization r;
+  r.selection = scoreSelect(ctx, sp, fixed, moving, poses, select, k, fixed_index, moving_index);
+  const size_t m = r.selection.index.size();
+  if (!m) return r;
+  // the selected items' clouds, spelled out: NULL means "cloud i" only while the batch is the whole set
+  auto chosen = [&](const CloudSet& cs, const std::vector<int32_t>& idx) {
+    std::vector<int32_t> out;
+    if (idx.empty() && cs.numClouds() == 1) return out;
+    for (int32_t i : r.selection.index) out.push_back(idx.empty() ? i : idx[(size_t) i]);
+    return out;
+  };
+  const std::vector<int32_t> fi = chosen(fixed, fixed_index), mi = chosen(moving, moving_index);
+  std::vector<Vector3f> x0(m);
+  for (size_t j = 0; j < m; ++j) x0[j] = poses[(size_t) r.selection.index[j]];
+  const lsm2d_cloudset* fx[1] = {fixed.get()}; const lsm2d_cloudset* mv[1] = {moving.get()};
+  lsm2d_batch b{}; b.n_alignments = (int32_t) m; b.n_slices = 1; b.slices = &sp; b.fixed = fx; b.moving = mv;
+  b.fixed_index = fi.empty() ? nullptr : fi.data(); b.moving_index = mi.empty() ? nullptr : mi.data(); b.init_pose = x0[0].data();
+  const size_t cap = (size_t) lsm2d_stats_capacity(&aligner);
+  std::vector<lsm2d_iteration_stats> st(m * cap);
+  r.pose.resize(m); r.information.resize(m); r.status.resize(m); r.iterations.resize(m); r.last_stats.resize(m); r.accepted.resize(m);
+  check(lsm2d_align_batch(ctx.get(), &aligner, &b, r.pose[0].data(), r.information[0].data(), r.status.data(), r.iterations.data(), st.data()),
+        "lsm2d_align_batch", ctx.get());
+  for (size_t j = 0; j < m; ++j) {
+    const size_t it = (size_t) std::min<long>(std::max<long>((long) r.iterations[j] - 1, 0), (long) cap - 1);
+    r.last_stats[j] = st[j * cap + it];
+    r.accepted[j] = r.status[j] == LSM2D_SUCCESS && selectAccept(r.last_stats[j], select);
+  }
+  return r;
+}
+
 class CorrespondenceFinderProjective2f {
  public:
   explicit CorrespondenceFinderProjective2f(Context& ctx) : _ctx(ctx) {}
