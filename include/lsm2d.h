@@ -183,7 +183,7 @@ int  lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out_ctx);
 void lsm2d_destroy(lsm2d_context* ctx);
 /* blocks until everything queued on the context's stream has finished */
 int  lsm2d_synchronize(lsm2d_context* ctx);
-/* Options: the WHOLE public set (15 keys; anything else is LSM2D_BAD_ARGUMENT "unknown option").  Results never depend on any of them but "sum_order".
+/* Options: the WHOLE public set (16 keys; anything else is LSM2D_BAD_ARGUMENT "unknown option").  Results never depend on any of them but "sum_order".
  * "sum_order": 0 (default) = H, b and the chi^2 statistics of an iteration are added in TREES (a thread's pairs, then the 64 lanes of a wave, then the eight
  *   waves): the fast order.  1 = added PAIR AFTER PAIR in the order of the reference's correspondence vector -- ascending canvas column for the projective
  *   finder (registration/correspondence_finder_projective_2d.cpp:55-74), ascending moving index for the point-query finders
@@ -226,6 +226,12 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   50000): how far a pose may move before the kept survivor lists of the projective culling are rebuilt.
  * "balance" (default 1): batches of 257 .. 4096 culled alignments are placed on the chip by estimated work (one small launch ahead of k_align; a
  *   batch run again with unchanged sets and start poses keeps its placement: get "last_cull_estimate"); 0: workgroup i runs alignment i.
+ * "fast_forward" (default 1): k_align and its packed, narrow and reference-order forms stop iterating once the pose repeats.  One Gauss-Newton iteration is a
+ *   pure function of the pose it starts at, so when the pose after an iteration equals, BIT FOR BIT, the pose one of the last eight iterations started at, the
+ *   remaining iterations only go round that cycle (period 1: a fixed point of the fp32 arithmetic): whole periods are skipped, the remainder runs.  Pose,
+ *   information matrix, status, iteration count (skipped iterations are counted) and every iteration's statistics row are those of the full run; 0 runs every
+ *   iteration (the A/B switch).  Without effect -- every iteration runs -- with termination_chi_epsilon > 0, with enable_inlier_only_runs, in zero-copy batches (at most
+ *   "zero_copy_max" alignments: their results and statistics live in pinned host memory), on the split path and in the latency kernel.
  * "grid_big_threshold" (default 16384): fixed clouds of at least this many points get the NN finder's search grid built by chip-wide kernels
  *   (histogram / scan / scatter over many workgroups) instead of one workgroup per cloud.
  * "distmap_build": 0 = automatic (default: the distance maps of CorrespondenceFinderNN2D are built from the points' side, one disc of atomic minima

@@ -373,7 +373,7 @@ int AlignBatch::lay_out_lds() {
   proj_culled_for_all = proj_only && A.cull == 1 && ctx->proj_modes && ctx->cull_block == 0;
   for (int s = 0; s < ns && proj_culled_for_all; ++s)
     proj_culled_for_all = A.s[s].moving.lane_xy != nullptr && A.s[s].moving.lane_bounds != nullptr && A.s[s].moving.block_bounds != nullptr;
-  A.units_off = 0; A.cull_keep = ctx->cull_keep;
+  A.units_off = 0; A.cull_keep = ctx->cull_keep; A.fast_forward = ctx->fast_forward;
   A.cull_mt = ctx->cull_keep ? 1e-6f * (float) ctx->cull_margin_um : 0.0f; A.cull_mth = ctx->cull_keep ? 1e-6f * (float) ctx->cull_margin_urad : 0.0f; A.cull_mt2 = A.cull_mt * A.cull_mt;      // (lists rebuilt every iteration: no margins)
   if (proj_culled_for_all) {
     int nb_max = kCullBlocks;

@@ -59,6 +59,11 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ Iso s_list_iso[kMaxSlices];                             // ... and the transform it was built at
   uint16_t* l_units = reinterpret_cast<uint16_t*>(smem + A.units_off);      // [n_slices][kCullBlocks * kAlignBlock]
   float* l_rec = reinterpret_cast<float*>(smem + (kSeq ? A.seq_off : 0));   // kSeq: [kSeqHalf][kSeqFields]: half a trip's pair records
+  // "fast_forward" (AlignArgs::fast_forward): the poses the last eight iterations STARTED at, as bit patterns, in a ring (slot = pushes & 7); how many were
+  // pushed; the iterations thread 0 found it may skip behind the current one (0: none), read by everybody after the iteration's closing barrier.  In LDS like
+  // the rest of thread 0's serial state: no register held across the loops
+  __shared__ uint32_t s_ring[3 * kFfRing];
+  __shared__ int s_ring_n, s_skip;
   __shared__ PriorDev s_prior;      // read once: with zero-copy arguments A.prior is host memory, a PCIe round trip per access
 
   // (the alignment's index is wave-uniform: said so, or everything indexed by it would live in vector registers)
@@ -170,6 +175,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       s_phase = 0; s_phase_start = 0; s_phase_end = A.max_it; s_it0 = 0;
       for (int k = 0; k < 9; ++k) s_H[k] = 0.0f;
     }
+    s_ring_n = 0; s_skip = 0;
     for (int s = 0; s < kMaxSlices; ++s) { s_list_iso[s].c = 1.0f; s_list_iso[s].s = 0.0f; s_list_iso[s].tx = 0.0f; s_list_iso[s].ty = 0.0f; }
     if (!s_done) begin_iteration();      // (resumed: the transforms and the zeroed sums the first launch's last begin_iteration() made, made again from the same pose)
     for (int s = 0; s < kMaxSlices; ++s) s_rebuild[s] = 1;      // no list yet
@@ -278,6 +284,16 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   int it = __builtin_amdgcn_readfirstlane(s_it0);
   const int it_cap = __builtin_amdgcn_readfirstlane(A.inlier_runs ? 2 * A.max_it : A.max_it);      // (a scalar: as a select and a shift it lived in a vector register, spilled for the loop's back edge)
   const bool want_dig = A.out_stats != nullptr;      // the digest leaves the kernel through the statistics only
+  // Fast-forward.  One iteration is a pure function of the pose it starts at (begin_iteration makes s_iso from s_pose; the stream, the bin walk and the sums
+  // depend on s_iso alone -- the z-buffer's minimum and the fixed trees are deterministic, a kept or rebuilt unit list changes no bit; the prior, the damping
+  // and the solve depend on the sums and s_pose).  So when the pose AFTER iteration `it` equals, bit for bit, the pose iteration it - p + 1 started at, the
+  // poses repeat with period p from there on, and with R iterations of the phase left, skipping (R / p) * p of them leaves s_pose, s_H, s_last_n_in,
+  // out_last_pose and the status exactly what the full run would have left; the R mod p others run.  Off where an iteration depends on more than the pose:
+  // the chi^2 termination test (s_prev_chi; a fixed point ends itself there one iteration later anyway), the inlier-only runs (s_phase), and where `it`
+  // means more than a count (the first of two launches, a resumed second one, the XCD window's positions); and in a zero-copy launch (host_polls: at most
+  // "zero_copy_max" alignments, results and statistics rows in pinned HOST memory -- a skipped row copied from the row one period back would be a read across
+  // the host link on thread 0's serial path; the small calls, most of which the latency kernel and the split path take anyway, are the follow-up: DESIGN section 9)
+  const bool ff_on = A.fast_forward && !(A.term_eps > 0.0f) && !A.inlier_runs && !A.host_polls && !kFirstStage && !kXcdWindow && !resumed;      // (wave-uniform: kernel arguments)
   for (; it < it_cap; ++it) {
     const bool lists_only = kFirstStage && it == A.stage_split;      // the first of two launches enters this iteration for the LENGTH of its unit lists alone
     const bool inl_only = A.inlier_runs && __builtin_amdgcn_readfirstlane(s_phase) != 0;
@@ -751,6 +767,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       // (thread 0's serial state lives in LDS, not in registers every thread would carry -- and spill -- across the loops)
       StatsDev last; last.n_corr = s_n_corr; last.n_in = __float_as_int(s_sum[11]); last.n_out = __float_as_int(s_sum[12]); last.chi_in = s_sum[9]; last.chi_out = s_sum[10];
       s_last_n_in = last.n_in;
+      int skip = 0;      // fast-forward: iterations to jump over behind this one
 #ifdef LSM2D_DEBUG_UNITS      // diagnostics build: the culled stream's list length and whether it was rebuilt, in place of the outlier statistics
       if (kProjCulled) { last.n_out = s_nunits[0]; last.chi_out = (float) s_rebuild[0]; }
 #endif
@@ -762,11 +779,39 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
         s_H[6] = s_sum[2]; s_H[7] = s_sum[4]; s_H[8] = s_sum[5];
         s_rhs[0] = s_sum[6]; s_rhs[1] = s_sum[7]; s_rhs[2] = s_sum[8];
         if (A.prior) add_prior(s_prior, s_pose, s_H, s_rhs);
+        if (ff_on) {      // the pose this iteration started at: into the ring before the solve overwrites it
+          const int n = s_ring_n;
+          uint32_t* e = s_ring + 3 * (n & (kFfRing - 1));
+          e[0] = __float_as_uint(s_pose[0]); e[1] = __float_as_uint(s_pose[1]); e[2] = __float_as_uint(s_pose[2]);
+          s_ring_n = n + 1;
+        }
         float dmp = A.damping;
         asm volatile("" : "+v"(dmp));      // (not a loop invariant to hoist -- as a double it was kept, and spilled, across the whole kernel)
         if (!solve_update(s_H, s_rhs, dmp, s_pose)) { s_status = LSM2D_SINGULAR_H; s_done = 1; }
         else {
-          bool phase_over = it + 1 >= s_phase_end;
+          if (ff_on) {
+            // the new pose against the ring, newest entry first, as integers (-0 is not +0, a NaN is its pattern): entry k back is the start of iteration it - k
+            const uint32_t p0 = __float_as_uint(s_pose[0]), p1 = __float_as_uint(s_pose[1]), p2 = __float_as_uint(s_pose[2]);
+            const int n = s_ring_n;
+            for (int k = 0; k < kFfRing && k < n; ++k) {
+              const uint32_t* e = s_ring + 3 * ((n - 1 - k) & (kFfRing - 1));
+              if (e[0] != p0 || e[1] != p1 || e[2] != p2) continue;
+              const unsigned p = (unsigned) (k + 1), left = (unsigned) (s_phase_end - (it + 1));
+              skip = (int) ((left / p) * p);
+              if (A.out_stats) {      // the skipped iterations' rows are the cycle's: written by this thread, read back by it in program order
+                StatsDev* row = A.out_stats + (size_t) a * A.stats_stride;
+                for (int j = it + 1; j <= it + skip; ++j) {
+                  StatsDev r = row[j - (int) p];
+#ifdef LSM2D_DEBUG_UNITS      // diagnostics build: a skipped row says so, and with which period (tools/units_probe.py)
+                  r.chi_out = -(float) p;
+#endif
+                  row[j] = r;
+                }
+              }
+              break;
+            }
+          }
+          bool phase_over = it + skip + 1 >= s_phase_end;
           if (A.term_eps > 0.0f) {      // the aligner's termination criterion: relative decay of the total chi^2 (lsm2d.h), afresh in every phase
             const float chi_now = s_sum[9] + s_sum[10];      // (= last.chi_in + last.chi_out, read again: kept in registers across the solve they were spilled)
             if (it > s_phase_start && __builtin_fabsf(s_prev_chi - chi_now) < A.term_eps * chi_now) phase_over = true;      // status stays RUNNING: decided below as after max_iterations
@@ -779,12 +824,14 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
           }
         }
       }
+      if (ff_on) s_skip = skip;              // every iteration, whichever way it went: nobody adds a stale one
       if (!s_done) begin_iteration();        // next iteration's transforms and zeroed sums, under the same barrier
       // the XCD lockstep: nobody starts its next pass before everybody on this XCD has finished the pass xcd_window back (the others stand at the barrier below anyway)
       if (kXcdWindow && xsync && !s_done) xcd_wait(xsync, (it + 1) * A.n_slices - 1 - A.xcd_window * A.n_slices, A.xcd_positions);
     }
     LSM2D_PH(2);
     __syncthreads();
+    if (ff_on) it += __builtin_amdgcn_readfirstlane(s_skip);      // (every thread alike: `it` stays a scalar, and the exit below counts the skipped iterations in)
     if (s_done) { ++it; break; }
   }
   if (kXcdWindow && xsync && tid == 0) __hip_atomic_fetch_add(&xsync[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // gone: nobody waits for this workgroup any more

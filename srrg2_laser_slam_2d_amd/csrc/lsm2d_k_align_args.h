@@ -99,6 +99,10 @@ struct AlignArgs {
   int32_t seq_off;
   const int32_t* order2;                    // (round 6, k_align_two) a SECOND alignment for workgroup b to run after its first (-1: none), or nullptr: a batch of a few alignments more than
                                             // the chip holds packs its lightest ones two to a workgroup instead of starting another dispatch round (balance_order, "packed")
+  // "fast_forward" (align_body): an iteration is a pure function of the pose it starts at, so once the pose after an iteration equals, bit for bit, the
+  // start pose of one of the last eight iterations, the rest of the phase is that cycle again and again -- whole periods of it are skipped, results unchanged
+  // (0: every iteration runs; A/B switch.  Ignored with term_eps > 0, inlier_runs, host_polls, the two-launch form and the XCD window)
+  int32_t fast_forward;
   SliceDev s[kMaxSlices];
 };
 

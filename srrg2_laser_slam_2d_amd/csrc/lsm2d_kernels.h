@@ -24,6 +24,7 @@
 namespace lsm2d {
 
 static constexpr int kMaxSlices = 4;
+static constexpr int kFfRing = 8;      // align_body's fast-forward: iteration-start poses remembered = the longest period it finds (a power of two)
 // Measured-and-rejected experiments (DESIGN App. A) are compiled only into a -DLSM2D_EXPERIMENTS build of the library (round 5): the second launch form of
 // a culled batch (k_first_iteration / k_balance_only), the row-major culled stream ("cull" 2), the round-3 stream's block-length knob ("cull_block") and the
 // A/B option keys of lsm2d_capi.hip.  The shipped library carries none of them; their bit-identity tests run against the experiments build only.
