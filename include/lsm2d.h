@@ -226,11 +226,15 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   50000): how far a pose may move before the kept survivor lists of the projective culling are rebuilt.
  * "balance" (default 1): batches of 257 .. 4096 culled alignments are placed on the chip by estimated work (one small launch ahead of k_align; a
  *   batch run again with unchanged sets and start poses keeps its placement: get "last_cull_estimate"); 0: workgroup i runs alignment i.
- * "fast_forward" (default 1): k_align and its packed, narrow and reference-order forms stop iterating once the pose repeats.  One Gauss-Newton iteration is a
- *   pure function of the pose it starts at, so when the pose after an iteration equals, BIT FOR BIT, the pose one of the last eight iterations started at, the
- *   remaining iterations only go round that cycle (period 1: a fixed point of the fp32 arithmetic): whole periods are skipped, the remainder runs.  Pose,
- *   information matrix, status, iteration count (skipped iterations are counted) and every iteration's statistics row are those of the full run; 0 runs every
- *   iteration (the A/B switch).  Without effect -- every iteration runs -- with termination_chi_epsilon > 0, with enable_inlier_only_runs, in zero-copy batches (at most
+ * "fast_forward" (0, 1 or 2; default 2): k_align and its packed, narrow and reference-order forms stop iterating once the pose repeats.  One Gauss-Newton
+ *   iteration is a pure function of the pose it starts at, so when the pose after an iteration equals, BIT FOR BIT, the pose one of the last sixteen iterations
+ *   started at, the remaining iterations only go round that cycle (period 1: a fixed point of the fp32 arithmetic).
+ *     2: the alignment finishes there.  Its last iteration would repeat one the cycle has already been through: that one's start and end pose, information
+ *        matrix and inlier count were kept, and the results are written from them; no iteration runs behind the match.
+ *     1: whole periods are skipped and the remainder of a period runs again (the rule before 2 existed; kept as the A/B switch inside one library).
+ *     0: every iteration runs.
+ *   Pose, information matrix, status, iteration count (skipped iterations are counted) and every iteration's statistics row are those of the full run whatever
+ *   the value.  Without effect -- every iteration runs -- with termination_chi_epsilon > 0, with enable_inlier_only_runs, in zero-copy batches (at most
  *   "zero_copy_max" alignments: their results and statistics live in pinned host memory), on the split path and in the latency kernel.
  * "grid_big_threshold" (default 16384): fixed clouds of at least this many points get the NN finder's search grid built by chip-wide kernels
  *   (histogram / scan / scatter over many workgroups) instead of one workgroup per cloud.

@@ -96,7 +96,7 @@ struct lsm2d_context {
   int last_align_width = 0;    // what the latest k_align launch used
   int cull = 1;                // k_align, projective slices: exact culling of the moving cloud against the fixed canvas (0: off; results do not depend on it)
   int cull_keep = 1;           // ... the culled stream's unit lists are kept across iterations while the estimate stays within the margins they were built with (0: rebuilt every iteration; A/B knob)
-  int fast_forward = 1;        // k_align and its forms: once an iteration ends on a pose that one of the last eight iterations started at, bit for bit, whole periods of the cycle are skipped (0: every iteration runs; results do not depend on it)
+  int fast_forward = 2;        // k_align and its forms: once an iteration ends on a pose that one of the last sixteen iterations started at, bit for bit, the alignment finishes from what the last iteration's twin left (1: whole periods of the cycle are skipped, the remainder runs; 0: every iteration runs; results do not depend on it)
   int cull_margin_um = 10000; // the translation margin in micrometres (10 mm) and
   int cull_margin_urad = 2000; // the rotation margin in microradians (2 mrad): tuning knobs, results do not depend on them
   int kd_wg_max_points = 16384; // KD-tree build: clouds of at most this many points are built by ONE launch, a workgroup per cloud walking the levels itself (k_kd_build_wg); 0: the level loop for all (A/B knob; same trees)
@@ -499,7 +499,7 @@ const OptionDesc kOptions[] = {
   {"kd_lds_nodes",       &lsm2d_context::kd_lds_nodes,       0, 4096,       0},
   {"sum_order",          &lsm2d_context::sum_order,          0, 1,          0},
   {"align_width",        &lsm2d_context::align_width,        0, 1024,       0},
-  {"fast_forward",       &lsm2d_context::fast_forward,       0, 1,          0},
+  {"fast_forward",       &lsm2d_context::fast_forward,       0, 2,          0},
   // ---- read-only
   {"last_align_path",    &lsm2d_context::last_align_path,    0, 0, kOptReadOnly},
   {"last_align_width",   &lsm2d_context::last_align_width,   0, 0, kOptReadOnly},

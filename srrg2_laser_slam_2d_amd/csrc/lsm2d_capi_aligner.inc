@@ -104,8 +104,8 @@ struct AlignBatch {
   bool async; hipStream_t pre, ks;      // begun asynchronously; the stream of what goes AHEAD of k_align (start poses, estimate); the stream of the batch's own operations
   int n, ns, stats_stride, it_cap;
   AlignArgs A;
-  // ---- scratch / staging layout: [init_pose | prior | indices | out_pose | out_H | status | its | stats | last_pose | clock | work]
-  size_t off, o_pose_in, o_prior, o_fidx[kMaxSlices], o_midx[kMaxSlices], in_bytes, o_pose, o_H, o_status, o_its, o_stats, o_last_pose, o_clock, out_bytes, o_work, total_bytes;
+  // ---- scratch / staging layout: [init_pose | prior | indices | out_pose | out_H | status | its | stats | last_pose | clock | work | ff_rows]
+  size_t off, o_pose_in, o_prior, o_fidx[kMaxSlices], o_midx[kMaxSlices], in_bytes, o_pose, o_H, o_status, o_its, o_stats, o_last_pose, o_clock, out_bytes, o_work, o_ff_rows, total_bytes;
 #ifdef LSM2D_EXPERIMENTS
   size_t o_order, o_resume;
 #endif
@@ -172,6 +172,8 @@ int AlignBatch::validate_and_lay_out_scratch() {
   o_clock = ctx->kernel_timing ? take(sizeof(unsigned long long) * 4 * (size_t) n_clock) : 0;
   out_bytes = off - o_pose;      // what travels back to the host
   o_work = take(sizeof(int32_t) * (size_t) n);                                                     // balanced placement: the estimate's counts (device only)
+  // "fast_forward" 2: H and inlier count of every alignment's last kFfRing iterations (device only; 640 bytes per alignment; needs no clearing: a row is read only after its alignment wrote it)
+  o_ff_rows = (ctx->fast_forward == 2 && !out_work) ? take(sizeof(uint32_t) * kFfRowWords * kFfRing * (size_t) n) : 0;
 #ifdef LSM2D_EXPERIMENTS      // the two-launch form of a batch ("two_stage"): its order and the state between its launches (device only)
   o_order = take(sizeof(int32_t) * (size_t) n), o_resume = take(sizeof(ResumeDev) * (size_t) n);
 #endif
@@ -374,6 +376,7 @@ int AlignBatch::lay_out_lds() {
   for (int s = 0; s < ns && proj_culled_for_all; ++s)
     proj_culled_for_all = A.s[s].moving.lane_xy != nullptr && A.s[s].moving.lane_bounds != nullptr && A.s[s].moving.block_bounds != nullptr;
   A.units_off = 0; A.cull_keep = ctx->cull_keep; A.fast_forward = ctx->fast_forward;
+  A.ff_rows = (ctx->fast_forward == 2 && !out_work) ? (uint32_t*) ((char*) L->d_scratch + o_ff_rows) : nullptr;      // (the lane's DEVICE scratch whatever path the call takes: a zero-copy launch does not fast-forward)
   A.cull_mt = ctx->cull_keep ? 1e-6f * (float) ctx->cull_margin_um : 0.0f; A.cull_mth = ctx->cull_keep ? 1e-6f * (float) ctx->cull_margin_urad : 0.0f; A.cull_mt2 = A.cull_mt * A.cull_mt;      // (lists rebuilt every iteration: no margins)
   if (proj_culled_for_all) {
     int nb_max = kCullBlocks;

@@ -59,11 +59,13 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ Iso s_list_iso[kMaxSlices];                             // ... and the transform it was built at
   uint16_t* l_units = reinterpret_cast<uint16_t*>(smem + A.units_off);      // [n_slices][kCullBlocks * kAlignBlock]
   float* l_rec = reinterpret_cast<float*>(smem + (kSeq ? A.seq_off : 0));   // kSeq: [kSeqHalf][kSeqFields]: half a trip's pair records
-  // "fast_forward" (AlignArgs::fast_forward): the poses the last eight iterations STARTED at, as bit patterns, in a ring (slot = pushes & 7); how many were
-  // pushed; the iterations thread 0 found it may skip behind the current one (0: none), read by everybody after the iteration's closing barrier.  In LDS like
-  // the rest of thread 0's serial state: no register held across the loops
+  // "fast_forward" (AlignArgs::fast_forward): the poses the last kFfRing iterations STARTED at, as bit patterns, in a ring (slot = pushes & (kFfRing - 1)); how
+  // many were pushed; the iterations thread 0 found it may skip behind the current one (0: none), read by everybody after the iteration's closing barrier.  In
+  // LDS like the rest of thread 0's serial state: no register held across the loops.  (What else "fast_forward" 2 keeps of those iterations -- H and the
+  // inlier count -- lies in device memory: AlignArgs::ff_rows)
   __shared__ uint32_t s_ring[3 * kFfRing];
   __shared__ int s_ring_n, s_skip;
+  __shared__ uint32_t* s_ff_rows;      // this alignment's row of A.ff_rows, or nullptr ("fast_forward" 2 only: the host hands the rows over for that value alone).  Thread 0 reads it back where it needs it: as a kernel argument and a product with `a` it was four scalar registers held across the loops -- in the narrow kernel, spills
   __shared__ PriorDev s_prior;      // read once: with zero-copy arguments A.prior is host memory, a PCIe round trip per access
 
   // (the alignment's index is wave-uniform: said so, or everything indexed by it would live in vector registers)
@@ -176,6 +178,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       for (int k = 0; k < 9; ++k) s_H[k] = 0.0f;
     }
     s_ring_n = 0; s_skip = 0;
+    s_ff_rows = A.ff_rows ? A.ff_rows + (size_t) a * (kFfRing * kFfRowWords) : nullptr;
     for (int s = 0; s < kMaxSlices; ++s) { s_list_iso[s].c = 1.0f; s_list_iso[s].s = 0.0f; s_list_iso[s].tx = 0.0f; s_list_iso[s].ty = 0.0f; }
     if (!s_done) begin_iteration();      // (resumed: the transforms and the zeroed sums the first launch's last begin_iteration() made, made again from the same pose)
     for (int s = 0; s < kMaxSlices; ++s) s_rebuild[s] = 1;      // no list yet
@@ -288,7 +291,11 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   // depend on s_iso alone -- the z-buffer's minimum and the fixed trees are deterministic, a kept or rebuilt unit list changes no bit; the prior, the damping
   // and the solve depend on the sums and s_pose).  So when the pose AFTER iteration `it` equals, bit for bit, the pose iteration it - p + 1 started at, the
   // poses repeat with period p from there on, and with R iterations of the phase left, skipping (R / p) * p of them leaves s_pose, s_H, s_last_n_in,
-  // out_last_pose and the status exactly what the full run would have left; the R mod p others run.  Off where an iteration depends on more than the pose:
+  // out_last_pose and the status exactly what the full run would have left; the R mod p others run ("fast_forward" 1).  They need not either ("fast_forward"
+  // 2): the LAST iteration, it + R, is the twin of iteration t = s + ((R - 1) mod p), s = it - p + 1 <= t <= it, which has been executed -- its start pose and
+  // the pose it ended on (the start of t + 1, or the pose just solved if t == it) are in the ring, and its H (as solve_update was given it: prior included,
+  // damping not, which the solve applies to a copy) and inlier count wait in the alignment's row of A.ff_rows, stored by thread 0 iteration by iteration without
+  // waiting and read once here.  The alignment finishes from those, R iterations counted and no iteration run.  Off where an iteration depends on more than the pose:
   // the chi^2 termination test (s_prev_chi; a fixed point ends itself there one iteration later anyway), the inlier-only runs (s_phase), and where `it`
   // means more than a count (the first of two launches, a resumed second one, the XCD window's positions); and in a zero-copy launch (host_polls: at most
   // "zero_copy_max" alignments, results and statistics rows in pinned HOST memory -- a skipped row copied from the row one period back would be a read across
@@ -301,6 +308,8 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     { const int q = (4 * it) / A.max_it; if (q == 0) __builtin_amdgcn_s_setprio(3); else if (q == 1) __builtin_amdgcn_s_setprio(2); else if (q == 2) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #elif LSM2D_PRIO_BY_PROGRESS == 2
     { if (2 * it < A.max_it) __builtin_amdgcn_s_setprio(3); else if (4 * it < 3 * A.max_it) __builtin_amdgcn_s_setprio(2); else if (8 * it < 7 * A.max_it) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+#elif LSM2D_PRIO_BY_PROGRESS == 3      // the other way round, for launches behind the fast-forward: whoever still iterates late is what the launch waits for
+    { if (it < 4) __builtin_amdgcn_s_setprio(0); else if (it < 6) __builtin_amdgcn_s_setprio(1); else if (it < 8) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
 #endif
     for (int s = 0; s < A.n_slices; ++s) {
       const SliceDev& S = A.s[s];
@@ -798,12 +807,26 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
               if (e[0] != p0 || e[1] != p1 || e[2] != p2) continue;
               const unsigned p = (unsigned) (k + 1), left = (unsigned) (s_phase_end - (it + 1));
               skip = (int) ((left / p) * p);
+              const uint32_t* const rows = s_ff_rows;
+              if (rows && left > 0) {      // finish from the ring: the last iteration's twin is `back` entries back (0: this very iteration), 0 <= back <= k
+                const int back = k - (int) ((left - 1) % p);
+                if (back > 0) {      // (back == 0: it is its own twin -- s_H, s_last_n_in, the pose just solved and out_last_pose are what they must be)
+                  const uint32_t* et = s_ring + 3 * ((n - 1 - back) & (kFfRing - 1));      // the pose the twin started at,
+                  const uint32_t* en = s_ring + 3 * ((n - back) & (kFfRing - 1));          // the pose it ended on: the start of the iteration behind it
+                  const uint32_t* w = rows + ((n - 1 - back) & (kFfRing - 1)) * kFfRowWords;
+                  _Pragma("nounroll") for (int j = 0; j < 9; ++j) s_H[j] = __uint_as_float(w[j]);      // (once per alignment: word by word, no registers for a row)
+                  s_last_n_in = (int) w[9];
+                  if (A.out_last_pose) { A.out_last_pose[3 * a + 0] = __uint_as_float(et[0]); A.out_last_pose[3 * a + 1] = __uint_as_float(et[1]); A.out_last_pose[3 * a + 2] = __uint_as_float(et[2]); }
+                  s_pose[0] = __uint_as_float(en[0]); s_pose[1] = __uint_as_float(en[1]); s_pose[2] = __uint_as_float(en[2]);
+                }
+                skip = (int) left;      // all of them: phase_over below, and ff_on excludes a second phase -- s_done, the status decided at the exit
+              }
               if (A.out_stats) {      // the skipped iterations' rows are the cycle's: written by this thread, read back by it in program order
                 StatsDev* row = A.out_stats + (size_t) a * A.stats_stride;
                 for (int j = it + 1; j <= it + skip; ++j) {
                   StatsDev r = row[j - (int) p];
 #ifdef LSM2D_DEBUG_UNITS      // diagnostics build: a skipped row says so, and with which period (tools/units_probe.py)
-                  r.chi_out = -(float) p;
+                  r.chi_out = (rows ? -0.5f : 0.0f) - (float) p;      // (... and a row filled in by "fast_forward" 2 -- nothing runs behind it -- by the half)
 #endif
                   row[j] = r;
                 }
@@ -812,6 +835,12 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             }
           }
           bool phase_over = it + skip + 1 >= s_phase_end;
+          if (ff_on && !phase_over)      // another iteration follows: what a twin of THIS one would leave behind besides its poses -- H as the solve was given it (which it does not change), the inlier count
+            if (uint32_t* w = s_ff_rows) {
+              w += ((s_ring_n - 1) & (kFfRing - 1)) * kFfRowWords;
+              for (int k = 0; k < 9; ++k) w[k] = __float_as_uint(s_H[k]);
+              w[9] = (uint32_t) s_last_n_in;
+            }
           if (A.term_eps > 0.0f) {      // the aligner's termination criterion: relative decay of the total chi^2 (lsm2d.h), afresh in every phase
             const float chi_now = s_sum[9] + s_sum[10];      // (= last.chi_in + last.chi_out, read again: kept in registers across the solve they were spilled)
             if (it > s_phase_start && __builtin_fabsf(s_prev_chi - chi_now) < A.term_eps * chi_now) phase_over = true;      // status stays RUNNING: decided below as after max_iterations

@@ -100,8 +100,10 @@ struct AlignArgs {
   const int32_t* order2;                    // (round 6, k_align_two) a SECOND alignment for workgroup b to run after its first (-1: none), or nullptr: a batch of a few alignments more than
                                             // the chip holds packs its lightest ones two to a workgroup instead of starting another dispatch round (balance_order, "packed")
   // "fast_forward" (align_body): an iteration is a pure function of the pose it starts at, so once the pose after an iteration equals, bit for bit, the
-  // start pose of one of the last eight iterations, the rest of the phase is that cycle again and again -- whole periods of it are skipped, results unchanged
-  // (0: every iteration runs; A/B switch.  Ignored with term_eps > 0, inlier_runs, host_polls, the two-launch form and the XCD window)
+  // start pose of one of the last kFfRing iterations, the rest of the phase is that cycle again and again.  1: whole periods of it are skipped and the
+  // remainder runs; 2: the alignment finishes at once, from what the twin of its last iteration left -- poses in the ring (LDS), H and inlier count in ff_rows;
+  // results unchanged (0: every iteration runs; A/B switch.  Ignored with term_eps > 0, inlier_runs, host_polls, the two-launch form and the XCD window)
+  uint32_t* ff_rows;                        // [n_align][kFfRing][kFfRowWords] device scratch, written and read by the alignment's thread 0 only; nullptr unless fast_forward == 2
   int32_t fast_forward;
   SliceDev s[kMaxSlices];
 };

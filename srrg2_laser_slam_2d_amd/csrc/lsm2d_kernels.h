@@ -24,7 +24,8 @@
 namespace lsm2d {
 
 static constexpr int kMaxSlices = 4;
-static constexpr int kFfRing = 8;      // align_body's fast-forward: iteration-start poses remembered = the longest period it finds (a power of two)
+static constexpr int kFfRing = 16;     // align_body's fast-forward: iteration-start poses remembered = the longest period it finds (a power of two)
+static constexpr int kFfRowWords = 10; // ... and per remembered iteration, for "fast_forward" 2, in device memory (AlignArgs::ff_rows): H's nine words and the inlier count
 // Measured-and-rejected experiments (DESIGN App. A) are compiled only into a -DLSM2D_EXPERIMENTS build of the library (round 5): the second launch form of
 // a culled batch (k_first_iteration / k_balance_only), the row-major culled stream ("cull" 2), the round-3 stream's block-length knob ("cull_block") and the
 // A/B option keys of lsm2d_capi.hip.  The shipped library carries none of them; their bit-identity tests run against the experiments build only.
@@ -46,6 +47,8 @@ LSM2D_HD int cull_block_steps(int T, int nbs = kCullBlocks) { return 2 * ((T + 2
 // launch), so the last workgroup of a CU ends up alone, with nobody to issue under its barriers, bin walks and solves.  A
 // workgroup that lowers its priority as it advances lets the ones behind it catch up: all of a CU's workgroups finish together.
 // 0 off (1.86 ms on configs[1]), 1 quarters of the iterations (1.69), 2 halving intervals -- 1/2, 3/4, 7/8 (1.65).
+// 3 (-DLSM2D_PRIO_BY_PROGRESS=3, an A/B build): RISING with the iteration -- 0 below 4, 1, 2, and 3 from 8 on -- for launches behind the fast-forward, where
+// one alignment in ten reaches iteration 8 and is then what the launch waits for (measured: docs/REJECTED.md).
 #ifndef LSM2D_SEQ_WALK_PRIO
 #define LSM2D_SEQ_WALK_PRIO 1      // k_align_seq: the walking wave at top priority while it walks (configs[1], "sum_order" 1: 0.954 -> 0.937 ms; profiles/r06/sum_order_walker_quads_ab_r06.txt)
 #endif

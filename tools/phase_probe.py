@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Where a k_align workgroup's cycles go (library built with -DLSM2D_PHASE_PROBE): query / projection phase, barrier + reduction, solve + rest.
-usage: LSM2D_EXTRA_HIPCC_FLAGS=-DLSM2D_PHASE_PROBE python -m srrg2_laser_slam_2d_amd.build --force && python tools/phase_probe.py <role> <finder>"""
+usage: LSM2D_EXTRA_HIPCC_FLAGS=-DLSM2D_PHASE_PROBE python -m srrg2_laser_slam_2d_amd.build --force && python tools/phase_probe.py <role> <finder>
+With --full-length (role A, projective; LSM2D_EXTRA_HIPCC_FLAGS="-DLSM2D_PHASE_PROBE=3 -DLSM2D_DEBUG_UNITS": buckets unit lists | stream | everything else, and the
+fast-forward's filled-in statistics rows marked): only the alignments of the headline batch that EXECUTE every iteration -- the ones the launch waits for behind the
+fast-forward -- first inside the whole batch, then by themselves, one workgroup per otherwise empty CU: what one of their iterations costs there, stream and the rest."""
 import math, os, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 dump = tempfile.mktemp(suffix=".stamps"); os.environ["LSM2D_DUMP_STAMPS"] = dump
 from srrg2_laser_slam_2d_amd import api, synth
 
-role, kind = (sys.argv + ["B", "distmap"])[1:3]
+FULL_LENGTH = "--full-length" in sys.argv
+if FULL_LENGTH:
+    sys.argv.remove("--full-length")
+role, kind = (sys.argv + (["A", "projective"] if FULL_LENGTH else ["B", "distmap"]))[1:3]
 ctx = api.Context(0, kernel_timing=True); ctx.set_option("clock_stride", 1)
 for kv in filter(None, os.environ.get("LSM2D_BENCH_OPTIONS", "").split(",")):
     ctx.set_option(kv.partition("=")[0].strip(), int(kv.partition("=")[2]))
@@ -22,6 +28,33 @@ al = api.MultiAligner2D(ctx, max_iterations=20, min_num_inliers=10)
 al.param_slice_processors.append(api.AlignerSliceProcessorLaser2D(f, min_num_correspondences=10))
 scans = api.CloudSet(ctx, wl.scan_points, wl.scan_offsets); mp = api.CloudSet(ctx, wl.map_points)
 x0 = wl.x0 if role == "A" else synth.invert_poses(wl.x0.astype(np.float64)).astype(np.float32)
+def stamped(n):      # the last launch's stamps: [n] x (lifetime, first bucket, third bucket) in cycles -- the dump gives the second relative to its minimum: it is the remainder
+    rows = [l.split() for l in open(dump) if not l.startswith("#")][-n:]
+    a = np.array([[int(v) for v in r[1:3]] + [int(r[4], 16)] for r in rows], dtype=np.float64)
+    return a[:, 0], a[:, 1], a[:, 2]
+if FULL_LENGTH:
+    its = al.param_max_iterations if hasattr(al, "param_max_iterations") else 20
+    ctx.set_option("align_path", 1); ctx.set_option("zero_copy_max", 0)      # k_align, results by copies, whatever the batch size
+    for _ in range(3):
+        r = al.compute_batch([scans], [mp], x0, want_stats=True)
+    executed = ((np.arange(r.stats.shape[1])[None, :] < r.iterations[:, None]) & ~(r.stats["chi_outliers"] < 0)).sum(1)
+    full = np.flatnonzero(executed == its)
+    life, lists, rest = stamped(len(x0))
+    print("fast_forward %d: kernel %.3f ms; iterations executed: mean %.2f; alignments that execute all %d: %s" % (ctx.get_option("fast_forward"), r.kernel_ms, executed.mean(), its, full.tolist()))
+    print("  inside the batch: lifetime of those %s kcyc (median of all %.0f, max of all %.0f)" % (np.round(life[full] / 1e3).astype(int).tolist(), np.median(life) / 1e3, life.max() / 1e3))
+    if len(full):
+        sub = api.CloudSet(ctx, np.concatenate([wl.scan_points[wl.scan_offsets[i]:wl.scan_offsets[i + 1]] for i in full]),
+                           np.concatenate([[0], np.cumsum([wl.scan_offsets[i + 1] - wl.scan_offsets[i] for i in full])]).astype(np.int32))
+        for _ in range(3):
+            r1 = al.compute_batch([sub], [mp], x0[full], want_stats=True)
+        assert np.array_equal(r1.pose.view(np.uint32), r.pose[full].view(np.uint32)) and np.all(r1.iterations == its)
+        life, lists, rest = stamped(len(full))
+        stream = life - lists - rest
+        print("  by themselves (%d workgroups, a CU each): kernel %.3f ms; lifetime %s kcyc; per iteration: %s kcyc = unit lists %s + stream %s + everything else (prologue / %d included) %s"
+              % (len(full), r1.kernel_ms, np.round(life / 1e3).astype(int).tolist(), np.round(life / its / 1e3, 1).tolist(), np.round(lists / its / 1e3, 1).tolist(),
+                 np.round(stream / its / 1e3, 1).tolist(), its, np.round(rest / its / 1e3, 1).tolist()))
+    os.remove(dump)
+    sys.exit(0)
 for _ in range(5):
     r = al.compute_batch([scans], [mp], x0) if role == "A" else al.compute_batch([mp], [scans], x0)
 rows = [l.split() for l in open(dump) if not l.startswith("#")][-1000:]
