@@ -241,6 +241,29 @@ def _as_cloudset(ctx: Context, cloud) -> CloudSet:
     return cloud if isinstance(cloud, CloudSet) else CloudSet(ctx, cloud)
 
 
+def _ptr(a):
+    """a numpy array as a pointer argument; None stays NULL"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class _BatchItems:
+    """The items of a batched finder / factor / score call, marshalled once for every wrapper of the family: the sets as CloudSet, ``poses`` as float32
+    ``[n, 3]``, the optional index arrays as int32 ``[n]`` or NULL.  ``head(slice_params)`` is the argument list all these entry points begin with (context,
+    slice, fixed set and index, moving set and index, n_items); ``rows`` = max(n, 1) sizes the outputs, so that an empty batch still passes real pointers."""
+
+    def __init__(self, ctx: Context, fixed, moving, poses, fixed_index, moving_index):
+        self.ctx = ctx
+        self.fixed, self.moving = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
+        self.poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+        self.n = len(self.poses)
+        self.rows = max(self.n, 1)
+        self.fixed_index = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(self.n)
+        self.moving_index = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(self.n)
+
+    def head(self, slice_params: SliceParams) -> tuple:
+        return (self.ctx.handle, C.byref(slice_params), self.fixed.handle, _ptr(self.fixed_index), self.moving.handle, _ptr(self.moving_index), self.n)
+
+
 @dataclasses.dataclass
 class PointNormal2fProjectorPolar:
     """Parameters of the polar projector (apps/synthetic_scene_generator.cpp:69-75; MULTI.json:71-97)."""
@@ -323,24 +346,17 @@ class _FinderBase:
         matches cloud ``fixed_index[i]`` of the set ``fixed`` against cloud ``moving_index[i]`` of the set ``moving`` under ``poses[i]``
         (None: cloud ``i``, or the only cloud of a one-cloud set).  Returns a list of int32 ``[k, 2]`` arrays (fixed_idx, moving_idx): per
         item what ``compute()`` returns, in the same order."""
-        ctx, lib = self._ctx, self._ctx._lib
-        fixed = _as_cloudset(ctx, fixed); moving = _as_cloudset(ctx, moving)
-        x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
-        n = len(x)
+        ctx = self._ctx
+        it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
         sp = self.slice_params()
-        fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
-        mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
         if sp.finder == FINDER_PROJECTIVE:
             cap = int(sp.projector.canvas_cols)
         else:
-            cap = int(max(moving.counts)) if len(moving.counts) else 0
+            cap = int(max(it.moving.counts)) if len(it.moving.counts) else 0
         cap = max(cap, 1)
-        out = np.empty((max(n, 1), cap, 2), np.int32); cnt = np.zeros(max(n, 1), np.int32)
-        check(lib.lsm2d_find_correspondences_batch(ctx.handle, C.byref(sp), fixed.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
-                                                   moving.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n,
-                                                   x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)),
-              "lsm2d_find_correspondences_batch", ctx.handle)
-        return [out[i, : cnt[i]].copy() for i in range(n)]
+        out = np.empty((it.rows, cap, 2), np.int32); cnt = np.zeros(it.rows, np.int32)
+        check(ctx._lib.lsm2d_find_correspondences_batch(*it.head(sp), _ptr(it.poses), _ptr(out), cap, _ptr(cnt)), "lsm2d_find_correspondences_batch", ctx.handle)
+        return [out[i, : cnt[i]].copy() for i in range(it.n)]
 
 
 class CorrespondenceFinderProjective2f(_FinderBase):
@@ -773,9 +789,8 @@ def linearize_batch(ctx: Context, slice_params: SliceParams, fixed, moving, corr
     one-cloud set) at ``poses[i]``.  ``correspondences``: the list of int32 ``[k, 2]`` arrays ``finder.compute_batch`` returns, or a tuple
     ``(padded [n, cap, 2], counts [n])`` as lsm2d_find_correspondences_batch writes them (only the first ``counts[i]`` pairs of a row are read).
     Returns ``(H [n, 3, 3], b [n, 3], stats)``, ``stats`` a list of ``n`` IterationStats; per item the bits of ``linearize``."""
-    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
-    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
-    n = len(x)
+    it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
+    n = it.n
     if isinstance(correspondences, tuple):
         padded, cnt = correspondences
         padded = np.ascontiguousarray(padded, np.int32)
@@ -789,16 +804,11 @@ def linearize_batch(ctx: Context, slice_params: SliceParams, fixed, moving, corr
             raise ValueError("linearize_batch: one correspondence vector per pose")
         cnt = np.array([len(r) for r in rows], np.int32)
         cap = max(int(cnt.max()) if n else 0, 1)
-        padded = np.empty((max(n, 1), cap, 2), np.int32)
+        padded = np.empty((it.rows, cap, 2), np.int32)
         for i, r in enumerate(rows):
             padded[i, : len(r)] = r
-    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
-    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
-    H = np.empty((max(n, 1), 9), np.float32); b = np.empty((max(n, 1), 3), np.float32); st = (IterationStats * max(n, 1))()
-    check(ctx._lib.lsm2d_linearize_batch(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
-                                         mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, padded.ctypes.data_as(C.c_void_p), cap,
-                                         cnt.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p),
-                                         b.ctypes.data_as(C.c_void_p), st),
+    H = np.empty((it.rows, 9), np.float32); b = np.empty((it.rows, 3), np.float32); st = (IterationStats * it.rows)()
+    check(ctx._lib.lsm2d_linearize_batch(*it.head(slice_params), _ptr(padded), cap, _ptr(cnt), _ptr(it.poses), _ptr(H), _ptr(b), st),
           "lsm2d_linearize_batch", ctx.handle)
     return H[:n].reshape(n, 3, 3), b[:n], [st[i] for i in range(n)]
 
@@ -809,16 +819,10 @@ def score_batch(ctx: Context, slice_params: SliceParams, fixed, moving, poses, f
     at ``poses[i]`` with the slice's finder and linearises what it found there.  Returns ``(H [n, 3, 3], b [n, 3], stats)``, ``stats`` a list of ``n``
     IterationStats: per item the bits of ``finder.compute_batch`` followed by ``linearize_batch``, one copy down and one wait.  ``score_accept(stats, ...)``
     applies the loop detector's acceptance test to them."""
-    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
-    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
-    n = len(x)
-    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
-    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
-    H = np.empty((max(n, 1), 9), np.float32); b = np.empty((max(n, 1), 3), np.float32); st = (IterationStats * max(n, 1))()
-    check(ctx._lib.lsm2d_score_batch(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
-                                     mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, x.ctypes.data_as(C.c_void_p),
-                                     H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), st),
-          "lsm2d_score_batch", ctx.handle)
+    it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
+    n = it.n
+    H = np.empty((it.rows, 9), np.float32); b = np.empty((it.rows, 3), np.float32); st = (IterationStats * it.rows)()
+    check(ctx._lib.lsm2d_score_batch(*it.head(slice_params), _ptr(it.poses), _ptr(H), _ptr(b), st), "lsm2d_score_batch", ctx.handle)
     return H[:n].reshape(n, 3, 3), b[:n], [st[i] for i in range(n)]
 
 
@@ -888,19 +892,13 @@ def score_select(ctx: Context, slice_params: SliceParams, fixed, moving, poses, 
     come down, with one copy and one wait.  Returns ``(index int32 [m], H [m, 3, 3], b [m, 3], stats structured STATS_DTYPE [m], n_accepted)``,
     ``m = min(k, n_accepted)``, best first: ``index`` is what ``score_rank`` gives on ``score_batch``'s statistics, the rows are ``score_batch``'s for
     those items, bit for bit."""
-    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
-    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
-    n = len(x)
-    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(n)
-    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(n)
+    it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
     kk = max(int(k), 1)
     index = np.empty(kk, np.int32); H = np.empty((kk, 9), np.float32); b = np.empty((kk, 3), np.float32); st = np.zeros(kk, STATS_DTYPE)
     n_sel = C.c_int32(0); n_acc = C.c_int32(0)
     sel = select.struct()
-    check(ctx._lib.lsm2d_score_select(ctx.handle, C.byref(slice_params), fx.handle, None if fi is None else fi.ctypes.data_as(C.c_void_p),
-                                      mv.handle, None if mi is None else mi.ctypes.data_as(C.c_void_p), n, x.ctypes.data_as(C.c_void_p),
-                                      C.byref(sel), int(k), index.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
-                                      st.ctypes.data_as(C.c_void_p), C.byref(n_sel), C.byref(n_acc)),
+    check(ctx._lib.lsm2d_score_select(*it.head(slice_params), _ptr(it.poses), C.byref(sel), int(k), _ptr(index), _ptr(H), _ptr(b), _ptr(st), C.byref(n_sel),
+                                      C.byref(n_acc)),
           "lsm2d_score_select", ctx.handle)
     m = n_sel.value
     return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], n_acc.value

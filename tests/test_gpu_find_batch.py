@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 RMAX = 25.0
 MD, RES, NCOS = 0.4, 0.1, 0.7
-PAIR_BUDGET = 1 << 21      # pairs per launch (kFindBatchPairBudget, lsm2d_capi_finder.inc)
+PAIR_BUDGET = 1 << 21      # pairs per launch (kBatchPairBudget, lsm2d_capi_finder.inc)
 
 
 class _Fx:

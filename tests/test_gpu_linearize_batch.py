@@ -13,7 +13,7 @@ from srrg2_laser_slam_2d_amd._capi import BAD_ARGUMENT, IterationStats
 
 pytestmark = pytest.mark.gpu
 
-PAIR_BUDGET = 1 << 21      # pairs per launch (kLinBatchPairBudget, lsm2d_capi_finder.inc)
+PAIR_BUDGET = 1 << 21      # pairs per launch (kBatchPairBudget, lsm2d_capi_finder.inc)
 TAU = 0.01
 # where blocks_i = clamp(ceil(n / 256), 1, 1024) steps, where a trip of kAlignBlock = 512 and a half-trip of kSeqHalf = 256 end; the large item (past the
 # 1024-workgroup clamp: 1024 x 256 = 262 144, so the grid-stride loop takes a second trip) sits in the middle, ragged block offsets on both sides of it

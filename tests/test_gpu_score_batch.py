@@ -13,7 +13,7 @@ from srrg2_laser_slam_2d_amd._capi import BAD_ARGUMENT, IterationStats
 
 pytestmark = pytest.mark.gpu
 
-PAIR_BUDGET = 1 << 21      # pair slots per launch group (kFindBatchPairBudget, lsm2d_capi_finder.inc)
+PAIR_BUDGET = 1 << 21      # pair slots per launch group (kBatchPairBudget, lsm2d_capi_finder.inc)
 TAU = 0.01
 MD = 0.3
 # where an item's lin_blocks(count) = clamp(ceil(count / 256), 1, 1024) steps, where a trip of kAlignBlock = 512 and a half-trip of kSeqHalf = 256 end; the

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 T = api.SELECT_TILE        # entries a workgroup of k_select_tile sorts: where the selection takes another pass
 MAX_K = api.SELECT_MAX_K
-PAIR_BUDGET = 1 << 21      # pair slots per launch group (kFindBatchPairBudget, lsm2d_capi_finder.inc)
+PAIR_BUDGET = 1 << 21      # pair slots per launch group (kBatchPairBudget, lsm2d_capi_finder.inc)
 EVERYTHING = api.SelectParams(0, float("inf"), 0.0)
 NOTHING = api.SelectParams(10 ** 9, 0.0, 2.0)
 
