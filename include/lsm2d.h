@@ -55,7 +55,10 @@ extern "C" {
                              (0.7.3, number unchanged: an addition only) + lsm2d_score_batch (finder, then factor, for n_items pose hypotheses with the
                                     pairs kept on the device: one copy down and one wait per call, the bits of the two batch calls in sequence);
                              (0.7.4, number unchanged: an addition only) + lsm2d_score_select, lsm2d_select_params, LSM2D_SELECT_MAX_K (lsm2d_score_batch's
-                                    scoring, then the acceptance test and the best k hypotheses ranked on the device: only k rows come down) */
+                                    scoring, then the acceptance test and the best k hypotheses ranked on the device: only k rows come down);
+                             (0.7.5, number unchanged: an addition only) + lsm2d_score_aligner_batch, lsm2d_score_aligner_select (hypotheses scored against an
+                                    ALIGNER -- all its slices, sensor offsets, the skip rule and the optional prior -- in one call with one wait, and ranked
+                                    on the device) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -540,6 +543,45 @@ int lsm2d_align_batch(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, c
                       int32_t* out_status,              /* [n]     lsm2d_status >= 0 */
                       int32_t* out_iterations,          /* [n]     iterations started; may be NULL */
                       lsm2d_iteration_stats* out_stats  /* [n][lsm2d_stats_capacity(aligner)]; may be NULL */);
+
+/* ---- pose hypotheses scored against an ALIGNER (the two-laser robot's relocaliser, MULTI.json:700-732 with the slices at :715-721 and the odometry
+ * prior of :402-422; its relocaliser's own aligner is unset, :749-769, so it falls back on this one): lsm2d_score_batch / lsm2d_score_select for a
+ * lsm2d_batch -- up to 4 slices, WithSensor offsets, min_num_correspondences, an optional prior per hypothesis -- in ONE call with ONE wait.
+ * batch: n_alignments = the hypotheses, init_pose = their poses X, prior = [n] or NULL; cloud selection is lsm2d_batch's rule per slice (fixed_index /
+ * moving_index are [n_slices][n] or NULL; indices may repeat; a set without index holds 1 or n clouds).
+ * A scored item is what the first iteration of MultiAligner2D::compute holds just before its solve.  For slices s = 0 .. n_slices - 1, in order:
+ *   1. effective pose: Xe = X bit for bit when sensor_in_robot[s] compares equal to (0, 0, 0) (so (-0, 0, 0) too), else Xe = S^-1 X, in the aligner's
+ *      own fp32 operations;
+ *   2. pairs: the slice's finder at Xe -- lsm2d_find_correspondences_batch's pairs;
+ *   3. the pairs enter n_correspondences and the pair digest WHETHER OR NOT the slice is skipped, and the digest uses lsm2d_pair_hash(s, ...): the
+ *      slice index, as the aligner's digest does (lsm2d_score_batch hashes with slice 0);
+ *   4. a slice with n_pairs <= min_num_correspondences contributes nothing else;
+ *   5. otherwise its H, b, n_inliers, n_outliers and chi^2 sums are the bits lsm2d_score_batch gives for that slice at Xe, in both values of "sum_order";
+ *   6. the slices' values are added in fp32, in slice order, starting from +0 (a -0 therefore becomes +0);
+ *   7. the prior, when one is given AND at least one slice contributed, is added last (the aligner's own device function: omega is taken as given,
+ *      symmetric or not, and all nine entries of H are kept as summed);
+ *   8. out_active[i] is the number of slices that contributed.  0: H and b are zeros, no prior is added, n_correspondences and the digest are still
+ *      reported -- the hypothesis an aligner would end with LSM2D_NOT_ENOUGH_CORRESPONDENCES.
+ * Consequences.  With "sum_order" 1 an item equals the sequential oracle's align(max_iterations = 1) bit for bit -- its H, its first statistics row, its
+ * NOT_ENOUGH_CORRESPONDENCES status -- and the oracle's solve_update(H, b, X, damping) on the item's H and b gives that alignment's pose bit for bit.
+ * In the default order a slice's tree is lsm2d_linearize's (256-thread workgroups), NOT k_align's 512-thread tree: lsm2d_align_batch's first iteration is
+ * not the yardstick there; the combination above over lsm2d_linearize per slice is.
+ * Refused before anything is launched or written: n_slices outside [1, 4] or a NULL the call needs (LSM2D_BAD_ARGUMENT); a cloud index out of range
+ * (LSM2D_BAD_ARGUMENT; lsm2d_last_error names item and slice); canvases that do not fit LDS (LSM2D_CAPACITY_EXCEEDED); two batches in flight (as
+ * lsm2d_score_batch); for the select form k outside [1, LSM2D_SELECT_MAX_K].  n_alignments == 0 succeeds (the select form sets both counts to 0).
+ * Up: poses, priors and index tables, once; the slices' item tables are made on the device.  Down: ONE copy -- n combined rows (80 bytes each), or for the
+ * select form 16 bytes + k indices and rows.  ONE wait, however many slices and launch groups there are; a launch group is sized by the largest slot
+ * among the slices.  "kernel_timing" / lsm2d_last_kernel_ms cover the last launch group of the last slice, the combination and the selection.
+ * lsm2d_score_aligner_select ranks as lsm2d_score_select does (same test, same total order) on the combined statistics; an item with active == 0 is
+ * rejected whatever the thresholds are: it has no aligner status to pass.  Rows j < n_selected of out_H / out_b / out_stats / out_active (each may be
+ * NULL) are lsm2d_score_aligner_batch's for item out_index[j]. */
+int lsm2d_score_aligner_batch(lsm2d_context* ctx, const lsm2d_batch* batch,
+                              float* out_H /* [n][9] */, float* out_b /* [n][3] */,
+                              lsm2d_iteration_stats* out_stats /* [n] or NULL */, int32_t* out_active /* [n] or NULL */);
+int lsm2d_score_aligner_select(lsm2d_context* ctx, const lsm2d_batch* batch, const lsm2d_select_params* select, int32_t k,
+                               int32_t* out_index /* [k] */, float* out_H /* [k][9] or NULL */, float* out_b /* [k][3] or NULL */,
+                               lsm2d_iteration_stats* out_stats /* [k] or NULL */, int32_t* out_active /* [k] or NULL */,
+                               int32_t* out_n_selected, int32_t* out_n_accepted);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -872,15 +872,19 @@ def _select_accept(st: np.ndarray, select: SelectParams) -> np.ndarray:
                (ratio >= np.float32(select.min_inlier_ratio))
 
 
-def score_rank(stats, select: SelectParams, k: int):
+def score_rank(stats, select: SelectParams, k: int, active=None):
     """lsm2d_score_select's acceptance test and ranking on statistics the caller already holds (from ``score_batch``, an aligner or the oracle), in numpy
     float32 / integer arithmetic: accepted are the items with inliers >= min, chi_inliers / max(inliers, 1) <= max and inliers / max(correspondences, 1) >=
     ratio; they are ranked by inliers descending, then chi_inliers ascending on its bit pattern as uint32, then index ascending.  ``stats``: a list of
-    IterationStats or a structured STATS_DTYPE array.  Returns ``(index int32 [min(k, n_accepted)], n_accepted)``."""
+    IterationStats or a structured STATS_DTYPE array.  ``active`` (``score_aligner``'s, optional): an item whose count is 0 is rejected whatever the
+    thresholds are, as lsm2d_score_aligner_select rejects it.  Returns ``(index int32 [min(k, n_accepted)], n_accepted)``."""
     if k < 1:
         raise ValueError("score_rank: k must be >= 1")
     st = _stats_array(stats)
-    ok = np.flatnonzero(_select_accept(st, select))
+    acc = _select_accept(st, select)
+    if active is not None:
+        acc = acc & (np.asarray(active).reshape(-1) > 0)
+    ok = np.flatnonzero(acc)
     key = ((np.uint64(0x7fffffff) - st["n_inliers"][ok].astype(np.uint64)) << np.uint64(32)) | \
         np.ascontiguousarray(st["chi_inliers"][ok], np.float32).view(np.uint32).astype(np.uint64)
     order = np.lexsort((ok, key))      # by key, ties by index
@@ -904,6 +908,39 @@ def score_select(ctx: Context, slice_params: SliceParams, fixed, moving, poses, 
     return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], n_acc.value
 
 
+def score_aligner(aligner: "MultiAligner2D", fixed, moving, poses, priors=None, fixed_index=None, moving_index=None):
+    """``len(poses)`` pose hypotheses scored against the whole aligner -- every slice with its sensor offset and ``min_num_correspondences``, the optional
+    prior per hypothesis -- in one call with one wait (lsm2d_score_aligner_batch): what the first iteration of ``aligner.compute_batch`` holds just before
+    its solve.  ``fixed[s]`` / ``moving[s]``, ``priors``, ``*_index[s][i]``: as ``compute_batch`` takes them.  Returns ``(H [n, 3, 3], b [n, 3], stats
+    structured STATS_DTYPE [n], active int32 [n])``; ``active[i]`` counts the slices that contributed (0: zeros, the hypothesis an aligner would end with
+    NotEnoughCorrespondences).  With ``"sum_order"`` 1 an item is the sequential oracle's ``align(max_iterations=1)`` bit for bit."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)
+    n = bd.n_alignments; rows = max(n, 1)
+    H = np.empty((rows, 9), np.float32); b = np.empty((rows, 3), np.float32); st = np.zeros(rows, STATS_DTYPE); active = np.zeros(rows, np.int32)
+    check(ctx._lib.lsm2d_score_aligner_batch(ctx.handle, C.byref(bd), _ptr(H), _ptr(b), _ptr(st), _ptr(active)), "lsm2d_score_aligner_batch", ctx.handle)
+    del keep
+    return H[:n].reshape(n, 3, 3), b[:n], st[:n], active[:n]
+
+
+def score_aligner_select(aligner: "MultiAligner2D", fixed, moving, poses, select: SelectParams, k: int, priors=None, fixed_index=None, moving_index=None):
+    """``score_aligner``'s scoring, then the acceptance test and the best ``k`` accepted hypotheses ranked on the device (lsm2d_score_aligner_select); a
+    hypothesis no slice contributed to is rejected.  Returns ``(index int32 [m], H [m, 3, 3], b [m, 3], stats [m], active int32 [m], n_accepted)``,
+    ``m = min(k, n_accepted)``, best first: ``index`` is ``score_rank(stats, select, k, active)`` on ``score_aligner``'s results, the rows are its rows."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)
+    kk = max(int(k), 1)
+    index = np.empty(kk, np.int32); H = np.empty((kk, 9), np.float32); b = np.empty((kk, 3), np.float32); st = np.zeros(kk, STATS_DTYPE)
+    active = np.zeros(kk, np.int32)
+    n_sel = C.c_int32(0); n_acc = C.c_int32(0)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_score_aligner_select(ctx.handle, C.byref(bd), C.byref(sel), int(k), _ptr(index), _ptr(H), _ptr(b), _ptr(st), _ptr(active),
+                                              C.byref(n_sel), C.byref(n_acc)), "lsm2d_score_aligner_select", ctx.handle)
+    del keep
+    m = n_sel.value
+    return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], active[:m], n_acc.value
+
+
 @dataclasses.dataclass
 class RelocalizeResult:
     index: np.ndarray          # int32 [m]: the selected hypotheses, best first
@@ -913,12 +950,15 @@ class RelocalizeResult:
     accepted: np.ndarray       # bool [m]: aligner succeeded and the aligned statistics pass the acceptance test
 
 
-def relocalize(aligner: MultiAligner2D, fixed, moving, poses, select: SelectParams, k: int, fixed_index=None, moving_index=None) -> RelocalizeResult:
+def relocalize(aligner: MultiAligner2D, fixed, moving, poses, select: SelectParams, k: int, fixed_index=None, moving_index=None, priors=None) -> RelocalizeResult:
     """The candidate loop of the relocaliser / loop detector (MULTI.json:749-769, :964-986) over ``len(poses)`` hypotheses: ``score_select`` with the
     aligner's (one) slice, then ``aligner.compute_batch`` on the selected hypotheses from their own poses, then the acceptance test on the statistics of
-    the last iteration each started.  Pure composition: the same as calling the two entry points by hand."""
-    if len(aligner.param_slice_processors) != 1:
-        raise ValueError("relocalize: the aligner must have exactly one slice")
+    the last iteration each started.  Pure composition: the same as calling the two entry points by hand.
+    An aligner with several slices and / or ``priors`` (one ``(z, omega)`` per hypothesis) takes ``fixed`` / ``moving`` as lists of sets, one per slice
+    (``*_index``: ``[n_slices][n]``), scores with ``score_aligner_select`` and hands the selected hypotheses' priors on to the aligner."""
+    ns = len(aligner.param_slice_processors)
+    if ns != 1 or priors is not None or isinstance(fixed, (list, tuple)) or isinstance(moving, (list, tuple)):
+        return _relocalize_aligner(aligner, fixed, moving, poses, select, k, fixed_index, moving_index, priors)
     ctx = aligner._ctx
     fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
     x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
@@ -935,6 +975,41 @@ def relocalize(aligner: MultiAligner2D, fixed, moving, poses, select: SelectPara
         z = np.zeros
         return RelocalizeResult(index, st, n_acc, BatchResult(z((0, 3), np.float32), z((0, 3, 3), np.float32), z(0, np.int32), z(0, np.int32), None, 0.0), z(0, bool))
     res = aligner.compute_batch([fx], [mv], x[index], fixed_index=chosen(fx, fixed_index), moving_index=chosen(mv, moving_index), want_stats=True)
+    return RelocalizeResult(index, st, n_acc, res, (res.status == 0) & _select_accept(res.last_stats(), select))
+
+
+def _relocalize_aligner(aligner, fixed, moving, poses, select, k, fixed_index, moving_index, priors) -> RelocalizeResult:
+    """``relocalize`` for an aligner with several slices and / or priors: ``score_aligner_select``, then ``compute_batch`` on the selected hypotheses"""
+    ctx = aligner._ctx
+    ns = len(aligner.param_slice_processors)
+    if ns < 1:
+        raise ValueError("relocalize: the aligner has no slice")
+    as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
+    fx = [_as_cloudset(ctx, f) for f in as_list(fixed)]; mv = [_as_cloudset(ctx, m) for m in as_list(moving)]
+    if len(fx) != ns or len(mv) != ns:
+        raise ValueError("relocalize: one fixed and one moving set per slice of the aligner")
+    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
+    n = len(x)
+    if priors is not None and len(priors) != n:
+        raise ValueError("relocalize: one prior per hypothesis")
+    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(ns, n)
+    mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(ns, n)
+    index, _, _, st, _, n_acc = score_aligner_select(aligner, fx, mv, x, select, k, priors, fi, mi)
+    if not len(index):      # nothing passed: nothing to align
+        z = np.zeros
+        return RelocalizeResult(index, st, n_acc, BatchResult(z((0, 3), np.float32), z((0, 3, 3), np.float32), z(0, np.int32), z(0, np.int32), None, 0.0), z(0, bool))
+
+    def chosen(sets, idx):      # the selected items' clouds, spelled out for every slice: NULL means "cloud i" only while the batch is the whole set
+        if idx is None and all(cs.n_clouds == 1 for cs in sets):
+            return None
+        rows = []
+        for s_, cs in enumerate(sets):
+            full = idx[s_] if idx is not None else (np.zeros(n, np.int32) if cs.n_clouds == 1 else np.arange(n, dtype=np.int32))
+            rows.append(full[index])
+        return np.stack(rows)
+
+    pr = None if priors is None else [priors[int(i)] for i in index]
+    res = aligner.compute_batch(fx, mv, x[index], priors=pr, fixed_index=chosen(fx, fi), moving_index=chosen(mv, mi), want_stats=True)
     return RelocalizeResult(index, st, n_acc, res, (res.status == 0) & _select_accept(res.last_stats(), select))
 
 

@@ -1,6 +1,6 @@
 // lsm2d_capi_finder.inc -- plugin interface #1 (CorrespondenceFinder_::compute for the four finder kinds), the factor over a correspondence vector, and both
 // for a whole batch: apart (lsm2d_find_correspondences_batch, lsm2d_linearize_batch) and with the pairs kept on the device (lsm2d_score_batch,
-// lsm2d_score_select).  The steps these entry points share are stated once, up front: what a refusal says (failf), the cloud sets settled (settle_sets),
+// lsm2d_score_select; for a whole aligner: lsm2d_score_aligner_batch, lsm2d_score_aligner_select).  The steps these entry points share are stated once, up front: what a refusal says (failf), the cloud sets settled (settle_sets),
 // the timing bracket round a call's launches (TimedLaunch), a batch's head checks and index rules (batch_head, resolve_items), how many items a launch
 // takes (items_per_launch) and what a result row of the factor means (lin_row_out).  Where a call's parts lie in the lane's buffers is a *Layout struct.
 // Part of lsm2d_capi.hip (included there); not a translation unit of its own.
@@ -486,6 +486,41 @@ struct ScoreLayout {
   }
 };
 
+// Where one slice's arrays over the whole batch and the launch groups' shared scratch lie (device addresses), and the salt of its pairs' digest: what
+// lsm2d_score_batch's one slice (salt 0) and every slice of lsm2d_score_aligner_batch (slice * 0x632BE5AB, each at its own base in the scratch) hand to
+// the launch groups.
+struct ScoreSliceDev {
+  const FindItem* items; int32_t* cnt; unsigned long long* dig; float* out;      // [n] each, rows of kLinOutWords
+  int32_t* pairs; float* partial;                                                 // of ONE launch group
+  uint32_t salt;
+};
+
+// The launch groups of one slice over n items, per_group items each (every item a slot of `slot` pairs), queued one behind the other: finder, then factor.
+// `timed`: the timing bracket is begun in front of the last group.  Waits for nothing.
+static int score_slice_queue(lsm2d_context* ctx, FindBatchLaunch& P, const lsm2d_slice_params* sp, size_t n, size_t per_group, int32_t slot,
+                             const ScoreSliceDev& D, bool timed) {
+  Lane& L = lane(ctx);
+  const size_t B = (size_t) lin_blocks(slot);
+  ScoreBatchArgs S;
+  S.fixed = P.point_query ? P.N.fixed : P.A.fixed; S.moving = P.point_query ? P.N.moving : P.A.moving;
+  S.slot = slot; S.blocks_per_item = (int32_t) B; S.cauchy = sp->robustifier == LSM2D_ROBUST_CAUCHY; S.tau = sp->chi_threshold; S.slice_salt = D.salt;
+  S.pairs = D.pairs; S.partial = D.partial;
+  for (size_t k0 = 0; k0 < n; k0 += per_group) {
+    const size_t cnt = std::min(per_group, n - k0);
+    S.items = D.items + k0; S.count = D.cnt + k0; S.n_items = (int32_t) cnt;
+    S.dig = D.dig + k0; S.out = D.out + kLinOutWords * k0;
+    if (timed && k0 + cnt == n) HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).begin());      // the last launch group
+    find_batch_launch(ctx, P, S.items, cnt, D.cnt + k0, D.pairs);
+    if (ctx->sum_order) hipLaunchKernelGGL(k_score_seq_batch, dim3((unsigned) cnt), dim3(kAlignBlock), 0, ctx->stream, S);      // pair after pair, a workgroup per item
+    else {
+      hipLaunchKernelGGL(k_score_partial_batch, dim3((unsigned) (cnt * B)), dim3(256), 0, ctx->stream, S);
+      hipLaunchKernelGGL(k_score_final_batch, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, ctx->stream, S);
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return LSM2D_SUCCESS;
+}
+
 static int score_batch_queue(lsm2d_context* ctx, const char* who, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
                              const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, size_t d_extra, size_t h_down,
                              ScoreLayout& Y) {
@@ -505,24 +540,9 @@ static int score_batch_queue(lsm2d_context* ctx, const char* who, const lsm2d_sl
   find_batch_fill_items((FindItem*) hs, fixed, fc.data(), moving, mc.data(), poses, n);
   HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(FindItem) * n, hipMemcpyHostToDevice, ctx->stream));
   if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_dig, 0, sizeof(unsigned long long) * n, ctx->stream));
-  ScoreBatchArgs S;
-  S.fixed = P.point_query ? P.N.fixed : P.A.fixed; S.moving = P.point_query ? P.N.moving : P.A.moving;
-  S.slot = slot; S.blocks_per_item = (int32_t) B; S.cauchy = sp->robustifier == LSM2D_ROBUST_CAUCHY; S.tau = sp->chi_threshold;
-  S.pairs = (const int32_t*) (ds + Y.o_pairs); S.partial = (float*) (ds + Y.o_part);
-  for (size_t k0 = 0; k0 < n; k0 += per_group) {
-    const size_t cnt = std::min(per_group, n - k0);
-    S.items = (const FindItem*) ds + k0; S.count = (const int32_t*) (ds + Y.o_cnt) + k0; S.n_items = (int32_t) cnt;
-    S.dig = (unsigned long long*) (ds + Y.o_dig) + k0; S.out = (float*) (ds + Y.o_out) + kLinOutWords * k0;
-    if (k0 + cnt == n) HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).begin());      // the last launch group
-    find_batch_launch(ctx, P, S.items, cnt, (int32_t*) (ds + Y.o_cnt) + k0, (int32_t*) (ds + Y.o_pairs));
-    if (ctx->sum_order) hipLaunchKernelGGL(k_score_seq_batch, dim3((unsigned) cnt), dim3(kAlignBlock), 0, ctx->stream, S);      // pair after pair, a workgroup per item
-    else {
-      hipLaunchKernelGGL(k_score_partial_batch, dim3((unsigned) (cnt * B)), dim3(256), 0, ctx->stream, S);
-      hipLaunchKernelGGL(k_score_final_batch, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, ctx->stream, S);
-    }
-    HIPCHK(ctx, hipGetLastError());
-  }
-  return LSM2D_SUCCESS;
+  const ScoreSliceDev D = {(const FindItem*) ds, (int32_t*) (ds + Y.o_cnt), (unsigned long long*) (ds + Y.o_dig), (float*) (ds + Y.o_out),
+                           (int32_t*) (ds + Y.o_pairs), (float*) (ds + Y.o_part), 0u};
+  return score_slice_queue(ctx, P, sp, n, per_group, slot, D, true);
 }
 
 extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
@@ -547,6 +567,53 @@ extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* s
 // index) entries until one tile is left -- a pass turns m entries into ceil(m / tile) x k, less than half of them while m > tile -- and k_select_gather,
 // which fills the one region that comes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]], 16 + 68 k bytes whatever n_items is.  A
 // batch of at most one tile does all three in ONE launch (k_select_tile_one: four launches and a memset less, which is what counts at 1000 items).
+// where the selection's own part of the scratch lies: [keys A | index A] of n entries, [keys B | index B] of what the first pass leaves, the accepted count,
+// the region that goes down ([header | index[k] | rows[k][row_words]]: down_bytes)
+struct SelectLayout {
+  size_t n, K, e_idx_a, e_key_b, e_idx_b, e_acc, e_down, down_bytes, d_bytes;
+  SelectLayout(size_t n_, size_t K_, size_t row_words) : n(n_), K(K_) {
+    const size_t n_first = ((n + kSelectTile - 1) / kSelectTile) * K;      // what the first pass leaves
+    e_idx_a = up256(sizeof(u64) * n); e_key_b = up256(e_idx_a + sizeof(int32_t) * n); e_idx_b = up256(e_key_b + sizeof(u64) * n_first);
+    e_acc = up256(e_idx_b + sizeof(int32_t) * n_first); e_down = e_acc + 256;
+    down_bytes = sizeof(int32_t) * (kSelectHeaderWords + K) + sizeof(float) * row_words * K;
+    d_bytes = e_down + down_bytes;
+  }
+};
+
+// The selection's launches over rows of format Row, behind the scoring on the same stream; `de`: the selection's part of the scratch.  Ends the timing
+// bracket, queues the one copy down to `h_down`, waits (the one wait of the call) and checks the counters.  A (rows, n_items, k, thresholds) is the caller's.
+template <class Row>
+static int select_queue(lsm2d_context* ctx, const char* who, SelectArgs A, const SelectLayout& E, char* de, char* h_down) {
+  Lane& L = lane(ctx);
+  const size_t n = E.n, K = E.K;
+  u64* key[2] = {(u64*) de, (u64*) (de + E.e_key_b)}; int32_t* idx[2] = {(int32_t*) (de + E.e_idx_a), (int32_t*) (de + E.e_idx_b)};
+  A.keys = key[0]; A.index = idx[0]; A.n_accepted = (int32_t*) (de + E.e_acc);
+  if (n <= (size_t) kSelectTile) {      // one tile: keys, sort and gather in one launch of one workgroup
+    int32_t sort_size = 2;
+    while ((size_t) sort_size < n) sort_size <<= 1;
+    hipLaunchKernelGGL(k_select_tile_one<Row>, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, (int32_t*) (de + E.e_down));
+  } else {
+    HIPCHK(ctx, hipMemsetAsync(A.n_accepted, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(k_select_keys<Row>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
+    size_t m = n; int src = 0;
+    for (;;) {      // array A has room for n entries, B for n_first: pass p writes fewer than pass p - 2 read
+      const size_t tiles = (m + kSelectTile - 1) / kSelectTile;
+      hipLaunchKernelGGL(k_select_tile, dim3((unsigned) tiles), dim3(kSelectBlock), 0, ctx->stream, (const u64*) key[src], (const int32_t*) idx[src], (int32_t) m,
+                         A.k, key[src ^ 1], idx[src ^ 1]);
+      src ^= 1; m = tiles * K;
+      if (tiles == 1) break;
+    }
+    hipLaunchKernelGGL(k_select_gather<Row>, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], (int32_t*) (de + E.e_down));
+  }
+  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
+  HIPCHK(ctx, hipMemcpyAsync(h_down, de + E.e_down, E.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  const int32_t* h = (const int32_t*) h_down;
+  const int32_t n_acc = h[0], n_sel = h[1];
+  if (n_acc < 0 || n_acc > A.n_items || n_sel != (n_acc < A.k ? n_acc : A.k)) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the selection's counters are inconsistent", who);
+  return LSM2D_SUCCESS;
+}
+
 extern "C" int lsm2d_score_select(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
                                   const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses,
                                   const lsm2d_select_params* select, int32_t k, int32_t* out_index, float* out_H, float* out_b, lsm2d_iteration_stats* out_stats,
@@ -557,49 +624,193 @@ extern "C" int lsm2d_score_select(lsm2d_context* ctx, const lsm2d_slice_params* 
   { const int rc = batch_head(ctx, "score_select", sp, fixed, moving, n_items, 0); if (rc) return rc; }
   if (n_items == 0) { *out_n_selected = 0; *out_n_accepted = 0; return LSM2D_SUCCESS; }
   if (!poses) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: null argument");
-  const size_t n = (size_t) n_items, K = (size_t) k;
-  const size_t n_first = ((n + kSelectTile - 1) / kSelectTile) * K;      // what the first pass leaves
-  // the caller's part of the scratch: [keys A | index A] of n entries, [keys B | index B] of n_first, the accepted count, the region that goes down
-  const size_t e_idx_a = up256(sizeof(u64) * n), e_key_b = up256(e_idx_a + sizeof(int32_t) * n), e_idx_b = up256(e_key_b + sizeof(u64) * n_first);
-  const size_t e_acc = up256(e_idx_b + sizeof(int32_t) * n_first), e_down = e_acc + 256;
-  const size_t down_bytes = sizeof(int32_t) * (kSelectHeaderWords + K) + sizeof(float) * kLinOutWords * K;
+  const size_t K = (size_t) k;
+  const SelectLayout E((size_t) n_items, K, kLinOutWords);
   ScoreLayout Y;
-  { const int rc = score_batch_queue(ctx, "score_select", sp, fixed, fixed_index, moving, moving_index, n_items, poses, e_down + down_bytes, down_bytes, Y); if (rc) return rc; }
+  { const int rc = score_batch_queue(ctx, "score_select", sp, fixed, fixed_index, moving, moving_index, n_items, poses, E.d_bytes, E.down_bytes, Y); if (rc) return rc; }
   Lane& L = lane(ctx);
-  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch; char* const de = ds + Y.o_extra;
-  u64* key[2] = {(u64*) de, (u64*) (de + e_key_b)}; int32_t* idx[2] = {(int32_t*) (de + e_idx_a), (int32_t*) (de + e_idx_b)};
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
   SelectArgs A;
   A.rows = (const float*) (ds + Y.o_out); A.n_items = n_items; A.k = k;
   A.min_inliers = select->min_inliers; A.max_chi_per_inlier = select->max_chi_per_inlier; A.min_inlier_ratio = select->min_inlier_ratio;
-  A.keys = key[0]; A.index = idx[0]; A.n_accepted = (int32_t*) (de + e_acc);
-  if (n <= (size_t) kSelectTile) {      // one tile: keys, sort and gather in one launch of one workgroup
-    int32_t sort_size = 2;
-    while ((size_t) sort_size < n) sort_size <<= 1;
-    hipLaunchKernelGGL(k_select_tile_one, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, (int32_t*) (de + e_down));
-  } else {
-    HIPCHK(ctx, hipMemsetAsync(A.n_accepted, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(k_select_keys, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
-    size_t m = n; int src = 0;
-    for (;;) {      // array A has room for n entries, B for n_first: pass p writes fewer than pass p - 2 read
-      const size_t tiles = (m + kSelectTile - 1) / kSelectTile;
-      hipLaunchKernelGGL(k_select_tile, dim3((unsigned) tiles), dim3(kSelectBlock), 0, ctx->stream, (const u64*) key[src], (const int32_t*) idx[src], (int32_t) m,
-                         k, key[src ^ 1], idx[src ^ 1]);
-      src ^= 1; m = tiles * K;
-      if (tiles == 1) break;
-    }
-    hipLaunchKernelGGL(k_select_gather, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], (int32_t*) (de + e_down));
-  }
-  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
-  HIPCHK(ctx, hipMemcpyAsync(hs + Y.h_out, de + e_down, down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
-  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  { const int rc = select_queue<ScoreRow>(ctx, "score_select", A, E, ds + Y.o_extra, hs + Y.h_out); if (rc) return rc; }
   const int32_t* h = (const int32_t*) (hs + Y.h_out);
   const int32_t n_acc = h[0], n_sel = h[1];
-  if (n_acc < 0 || n_acc > n_items || n_sel != (n_acc < k ? n_acc : k)) return fail(ctx, LSM2D_DEVICE_ERROR, "score_select: the selection's counters are inconsistent");
   const int32_t* h_index = h + kSelectHeaderWords; const float* h_rows = (const float*) (h + kSelectHeaderWords + K);
   float H[9], b[3];
   for (int32_t j = 0; j < n_sel; ++j) {
     out_index[j] = h_index[j];
     lin_row_out(h_rows + kLinOutWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : H, out_b ? out_b + 3 * (size_t) j : b, out_stats ? out_stats + j : nullptr);
+  }
+  *out_n_selected = n_sel; *out_n_accepted = n_acc;
+  return LSM2D_SUCCESS;
+}
+
+// ---- hypotheses scored against an ALIGNER: all its slices, sensor offsets, the skip rule, the prior (lsm2d_k_score_aligner.h) ---------------------------------
+// Up, once: poses, priors (as PriorDev, the aligner's own host-side form) and the per-slice index tables.  k_score_aligner_items turns them into every
+// slice's FindItem table on the device; then slice after slice runs lsm2d_score_batch's launch groups (score_slice_queue) on its OWN items, counts, digests
+// and rows, with its slice's salt, all slices sharing the pair and partial-row scratch of one launch group -- sized by the largest slot among them, which
+// also decides the groups; k_score_combine leaves one combined row per item.  The timing bracket is begun in front of the last group of the last slice.
+
+// device: [poses | priors | fixed index | moving index] (the upload), then per slice [items | counts | digests | rows] over the whole batch, the combined
+// rows, [pairs | partial rows] of one launch group, d_extra bytes of the caller's; staging: the upload, then h_down bytes of the caller's
+struct ScoreAlignerLayout {
+  size_t n = 0, ns = 0, o_prior = 0, o_fidx = 0, o_midx = 0, up_bytes = 0, o_items = 0, o_cnt = 0, o_dig = 0, o_out = 0, o_comb = 0, o_pairs = 0, o_part = 0,
+         o_extra = 0, d_bytes = 0, h_out = 0, h_bytes = 0;
+  ScoreAlignerLayout() = default;
+  ScoreAlignerLayout(size_t n_, size_t ns_, bool prior, bool fidx, bool midx, size_t per_group, size_t slot_max, size_t d_extra, size_t h_down) : n(n_), ns(ns_) {
+    o_prior = up256(sizeof(float) * 3 * n); o_fidx = up256(o_prior + (prior ? sizeof(PriorDev) * n : 0));
+    o_midx = up256(o_fidx + (fidx ? sizeof(int32_t) * ns * n : 0)); up_bytes = o_midx + (midx ? sizeof(int32_t) * ns * n : 0);
+    o_items = up256(up_bytes); o_cnt = up256(o_items + sizeof(FindItem) * ns * n); o_dig = up256(o_cnt + sizeof(int32_t) * ns * n);
+    o_out = up256(o_dig + sizeof(unsigned long long) * ns * n); o_comb = up256(o_out + sizeof(float) * kLinOutWords * ns * n);
+    o_pairs = up256(o_comb + sizeof(float) * kCombWords * n); o_part = up256(o_pairs + sizeof(lsm2d_correspondence) * per_group * slot_max);
+    o_extra = up256(o_part + sizeof(float) * kAccumWords * per_group * (size_t) lin_blocks((int) slot_max)); d_bytes = o_extra + d_extra;
+    h_out = up256(up_bytes); h_bytes = h_out + h_down;
+  }
+};
+
+// one combined row as the ABI's H, b, statistics and active count
+static void comb_row_out(const float* h, float* H, float* b, lsm2d_iteration_stats* s, int32_t* active) {
+  if (H) memcpy(H, h, sizeof(float) * 9);
+  if (b) memcpy(b, h + kCombB, sizeof(float) * 3);
+  int32_t iv[4]; memcpy(iv, h + CombRow::kNin, sizeof iv);      // n_inliers, n_outliers, n_correspondences, active
+  if (s) {
+    s->n_inliers = iv[0]; s->n_outliers = iv[1]; s->n_correspondences = iv[2]; s->chi_inliers = h[CombRow::kChi]; s->chi_outliers = h[kCombChiOut];
+    unsigned long long dg; memcpy(&dg, h + kCombDigest, sizeof dg);
+    s->pair_digest_lo = (uint32_t) dg; s->pair_digest_hi = (uint32_t) (dg >> 32);
+  }
+  if (active) *active = iv[3];
+}
+
+// the descriptor's shape, the sets, a lane to stage through: what is checked before n_alignments is looked at
+static int score_aligner_head(lsm2d_context* ctx, const char* who, const lsm2d_batch* b) {
+  if (!ctx || !b || b->n_alignments < 0 || b->n_slices < 1 || b->n_slices > kMaxSlices || !b->slices || !b->fixed || !b->moving)
+    return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: bad batch descriptor (1 .. %d slices)", who, kMaxSlices);
+  for (int s = 0; s < b->n_slices; ++s) { const int rc = batch_head(ctx, who, b->slices + s, b->fixed[s], b->moving[s], b->n_alignments, 0); if (rc) return rc; }
+  return LSM2D_SUCCESS;
+}
+
+// Everything from the index rules to k_score_combine: leaves the combined rows on the device (ds + Y.o_comb), waits for nothing, has begun the timing
+// bracket; the caller ends it.  n_alignments > 0 and score_aligner_head have been checked.
+static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y) {
+  const int ns = b->n_slices; const int32_t n_items = b->n_alignments; const size_t n = (size_t) n_items;
+  if (!b->init_pose) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
+  // every refusal first: the index rules per slice, then what the slices' finders need
+  for (int s = 0; s < ns; ++s) {
+    const lsm2d_cloudset* f = b->fixed[s]; const lsm2d_cloudset* m = b->moving[s];
+    const int32_t* fi = b->fixed_index ? b->fixed_index + (size_t) s * n : nullptr; const int32_t* mi = b->moving_index ? b->moving_index + (size_t) s * n : nullptr;
+    if (!fi && f->n_clouds != 1 && f->n_clouds != n_items) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: slice %d: fixed set must hold 1 or n_alignments clouds", who, s);
+    if (!mi && m->n_clouds != 1 && m->n_clouds != n_items) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: slice %d: moving set must hold 1 or n_alignments clouds", who, s);
+    for (int32_t i = 0; i < n_items; ++i) {
+      const int32_t fc = fi ? fi[i] : (f->n_clouds == 1 ? 0 : i), mc = mi ? mi[i] : (m->n_clouds == 1 ? 0 : i);
+      if (!valid_cloud_index(f, fc) || !valid_cloud_index(m, mc)) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: item %d, slice %d: cloud index out of range", who, (int) i, s);
+    }
+  }
+  for (int s = 0; s < ns; ++s) {
+    const lsm2d_slice_params& sp = b->slices[s];
+    if (is_point_query(sp.finder)) { if (sp.finder != LSM2D_FINDER_DISTMAP && !(sp.max_distance > 0.0f)) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: max_distance must be > 0", who); continue; }
+    if (sp.finder != LSM2D_FINDER_PROJECTIVE) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: finder not supported", who);
+    ProjK pk;
+    if (!make_projk(sp.projector, &pk)) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: bad projector", who);
+    if ((long long) (sizeof(u64) * 2) * (long long) pk.cols > (long long) ctx->max_dyn_lds) return failf(ctx, LSM2D_CAPACITY_EXCEEDED, "%s: canvases do not fit LDS", who);
+  }
+  FindBatchLaunch P[kMaxSlices]; int32_t slot[kMaxSlices]; int32_t slot_max = 1;
+  for (int s = 0; s < ns; ++s) {
+    long long need = 0;
+    { const int rc0 = find_batch_need(b->slices + s, b->moving[s], &need); if (rc0) return rc0; }
+    if (need < 0 || need > 0x7fffffffll) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: bad projector", who);
+    slot[s] = (int32_t) need; slot_max = std::max(slot_max, slot[s]);
+    { const int rc = find_batch_prepare(ctx, b->slices + s, b->fixed[s], b->moving[s], 0.0f, slot[s], who, P[s]); if (rc) return rc; }
+  }
+  const size_t per_group = items_per_launch((size_t) slot_max, n, kLinBatchMaxItems);
+  Y = ScoreAlignerLayout(n, (size_t) ns, b->prior != nullptr, b->fixed_index != nullptr, b->moving_index != nullptr, per_group, (size_t) slot_max, d_extra, h_down);
+  { int rc = ensure_scratch(ctx, Y.d_bytes); if (rc) return rc; rc = ensure_stage(ctx, Y.h_bytes); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  memcpy(hs, b->init_pose, sizeof(float) * 3 * n);
+  if (b->prior) {
+    PriorDev* p = (PriorDev*) (hs + Y.o_prior);
+    for (size_t i = 0; i < n; ++i) {      // as the aligner stages them (AlignBatch::stage_inputs)
+      inverse_host(b->prior[i].z, p[i].z_inv); sincos_fixed(p[i].z_inv[2], p[i].sz, p[i].cz);
+      memcpy(p[i].omega, b->prior[i].omega, sizeof(float) * 9);
+    }
+  }
+  if (b->fixed_index) memcpy(hs + Y.o_fidx, b->fixed_index, sizeof(int32_t) * (size_t) ns * n);
+  if (b->moving_index) memcpy(hs + Y.o_midx, b->moving_index, sizeof(int32_t) * (size_t) ns * n);
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));      // the one copy up
+  if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_dig, 0, sizeof(unsigned long long) * (size_t) ns * n, ctx->stream));
+  ScoreAlignerArgs A;
+  A.poses = (const float*) ds; A.prior = b->prior ? (const PriorDev*) (ds + Y.o_prior) : nullptr; A.n_items = n_items; A.n_slices = ns;
+  A.out = (float*) (ds + Y.o_comb);
+  ScoreSliceDev D[kMaxSlices];
+  for (int s = 0; s < kMaxSlices; ++s) {
+    ScoreAlignerSlice& S = A.s[s];
+    memset(&S, 0, sizeof S);
+    if (s >= ns) continue;
+    const lsm2d_slice_params& sp = b->slices[s];
+    S.f_count = b->fixed[s]->d_count; S.m_count = b->moving[s]->d_count;
+    S.f_index = b->fixed_index ? (const int32_t*) (ds + Y.o_fidx) + (size_t) s * n : nullptr;
+    S.m_index = b->moving_index ? (const int32_t*) (ds + Y.o_midx) + (size_t) s * n : nullptr;
+    S.f_clouds = b->fixed[s]->n_clouds; S.m_clouds = b->moving[s]->n_clouds;
+    S.has_sensor = !(sp.sensor_in_robot[0] == 0.0f && sp.sensor_in_robot[1] == 0.0f && sp.sensor_in_robot[2] == 0.0f);      // the aligner's test (fill_align_args)
+    inverse_host(sp.sensor_in_robot, S.Sinv); sincos_fixed(S.Sinv[2], S.sSinv, S.cSinv);
+    S.items = (FindItem*) (ds + Y.o_items) + (size_t) s * n;
+    S.count = (const int32_t*) (ds + Y.o_cnt) + (size_t) s * n; S.rows = (const float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n;
+    S.slot = slot[s]; S.min_corr = sp.min_num_correspondences;
+    D[s] = ScoreSliceDev{S.items, (int32_t*) (ds + Y.o_cnt) + (size_t) s * n, (unsigned long long*) (ds + Y.o_dig) + (size_t) s * n,
+                         (float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n, (int32_t*) (ds + Y.o_pairs), (float*) (ds + Y.o_part), (uint32_t) s * 0x632BE5ABu};
+  }
+  hipLaunchKernelGGL(k_score_aligner_items, dim3((unsigned) ((n + 255) / 256), (unsigned) ns), dim3(256), 0, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  for (int s = 0; s < ns; ++s) { const int rc = score_slice_queue(ctx, P[s], b->slices + s, n, per_group, slot[s], D[s], s == ns - 1); if (rc) return rc; }
+  hipLaunchKernelGGL(k_score_combine, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_score_aligner_batch(lsm2d_context* ctx, const lsm2d_batch* batch, float* out_H, float* out_b, lsm2d_iteration_stats* out_stats,
+                                         int32_t* out_active) {
+  static const char who[] = "score_aligner_batch";
+  { const int rc = score_aligner_head(ctx, who, batch); if (rc) return rc; }
+  if (batch->n_alignments == 0) return LSM2D_SUCCESS;
+  if (!out_H || !out_b) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_aligner_batch: null argument");
+  ScoreAlignerLayout Y;
+  { const int rc = score_aligner_queue(ctx, who, batch, 0, sizeof(float) * kCombWords * (size_t) batch->n_alignments, Y); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());
+  HIPCHK(ctx, hipMemcpyAsync(hs + Y.h_out, ds + Y.o_comb, sizeof(float) * kCombWords * Y.n, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  for (size_t k = 0; k < Y.n; ++k)
+    comb_row_out((const float*) (hs + Y.h_out) + kCombWords * k, out_H + 9 * k, out_b + 3 * k, out_stats ? out_stats + k : nullptr, out_active ? out_active + k : nullptr);
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_score_aligner_select(lsm2d_context* ctx, const lsm2d_batch* batch, const lsm2d_select_params* select, int32_t k, int32_t* out_index,
+                                          float* out_H, float* out_b, lsm2d_iteration_stats* out_stats, int32_t* out_active, int32_t* out_n_selected,
+                                          int32_t* out_n_accepted) {
+  static const char who[] = "score_aligner_select";
+  if (!select || !out_index || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_aligner_select: null argument");
+  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_aligner_select: k outside [1, LSM2D_SELECT_MAX_K]");
+  { const int rc = score_aligner_head(ctx, who, batch); if (rc) return rc; }
+  if (batch->n_alignments == 0) { *out_n_selected = 0; *out_n_accepted = 0; return LSM2D_SUCCESS; }
+  const size_t K = (size_t) k;
+  const SelectLayout E((size_t) batch->n_alignments, K, kCombWords);
+  ScoreAlignerLayout Y;
+  { const int rc = score_aligner_queue(ctx, who, batch, E.d_bytes, E.down_bytes, Y); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
+  HIPCHK(ctx, hipGetLastError());
+  SelectArgs A;
+  A.rows = (const float*) (ds + Y.o_comb); A.n_items = batch->n_alignments; A.k = k;
+  A.min_inliers = select->min_inliers; A.max_chi_per_inlier = select->max_chi_per_inlier; A.min_inlier_ratio = select->min_inlier_ratio;
+  { const int rc = select_queue<CombRow>(ctx, who, A, E, ds + Y.o_extra, hs + Y.h_out); if (rc) return rc; }
+  const int32_t* h = (const int32_t*) (hs + Y.h_out);
+  const int32_t n_acc = h[0], n_sel = h[1];
+  const int32_t* h_index = h + kSelectHeaderWords; const float* h_rows = (const float*) (h + kSelectHeaderWords + K);
+  for (int32_t j = 0; j < n_sel; ++j) {
+    out_index[j] = h_index[j];
+    comb_row_out(h_rows + kCombWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : nullptr, out_b ? out_b + 3 * (size_t) j : nullptr, out_stats ? out_stats + j : nullptr,
+                 out_active ? out_active + j : nullptr);
   }
   *out_n_selected = n_sel; *out_n_accepted = n_acc;
   return LSM2D_SUCCESS;

@@ -17,13 +17,19 @@ static constexpr int kSelectMaxK = 1024;               // LSM2D_SELECT_MAX_K
 static constexpr int kSelectTile = 2 * kSelectMaxK;    // entries a workgroup of k_select_tile sorts: a power of two, 2 x the largest k, 24 KB of LDS
 static constexpr int kSelectBlock = kSelectTile / 2;   // one compare-exchange per thread and step
 static constexpr u64 kSelectRejected = ~(u64) 0;       // the key of a rejected item and of the padding: above every accepted key, never selected
-static constexpr int kSelectHeaderWords = 4;           // the region that goes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]]
+static constexpr int kSelectHeaderWords = 4;           // the region that goes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][Row::kWords]]
 static_assert((kSelectTile & (kSelectTile - 1)) == 0 && kSelectTile >= 2 * kSelectMaxK, "the tile is a power of two holding two selections");
 static_assert(kSelectTile * (sizeof(u64) + sizeof(int32_t)) < 64 * 1024, "static LDS stays below 64 KB");
 static_assert(kSelectBlock <= 1024, "one workgroup");
 
+// What a result row looks like to the selection: its length in words and where the three statistics of the acceptance test lie in it.  ScoreRow: the rows
+// k_score_final_batch / k_score_seq_batch leave (linearize_final_body's words).  The kernels that read rows take the format as a template argument; a format
+// with kActive >= 0 names a word that counts the aligner slices that contributed: an item whose count is 0 is rejected whatever the thresholds are
+// (lsm2d_k_score_aligner.h: it has no aligner status to pass).  k_select_tile sees keys and indices only.
+struct ScoreRow { static constexpr int kWords = kLinOutWords, kChi = 9, kNin = 11, kNcorr = 13, kActive = -1; };
+
 struct SelectArgs {
-  const float* rows;          // [n_items][kLinOutWords]: where k_score_final_batch / k_score_seq_batch left them
+  const float* rows;          // [n_items][Row::kWords]: where the scoring's last kernel left them
   int32_t n_items, k;
   int32_t min_inliers; float max_chi_per_inlier, min_inlier_ratio;
   u64* keys; int32_t* index;  // [n_items]: k_select_keys writes, the first pass of k_select_tile reads
@@ -42,20 +48,23 @@ LSM2D_DEV bool select_accept(int32_t n_inliers, int32_t n_correspondences, float
 }
 
 // item i's sort key: (0x7fffffff - n_inliers, chi_inliers' bits) when it is accepted, all ones when it is not
+template <class Row>
 LSM2D_DEV u64 select_key(const SelectArgs& A, int i, bool* ok) {
-  const float* row = A.rows + (size_t) i * kLinOutWords;      // words 9, 11, 13: chi_inliers, n_inliers, n_correspondences (linearize_final_body)
-  const float chi = row[9];
-  const int32_t n_in = __float_as_int(row[11]), n_c = __float_as_int(row[13]);
+  const float* row = A.rows + (size_t) i * Row::kWords;
+  const float chi = row[Row::kChi];
+  const int32_t n_in = __float_as_int(row[Row::kNin]), n_c = __float_as_int(row[Row::kNcorr]);
   *ok = select_accept(n_in, n_c, chi, A.min_inliers, A.max_chi_per_inlier, A.min_inlier_ratio);
+  if constexpr (Row::kActive >= 0) *ok = *ok && __float_as_int(row[Row::kActive]) > 0;
   return *ok ? ((u64) (uint32_t) (0x7fffffff - n_in) << 32) | (u64) __float_as_uint(chi) : kSelectRejected;
 }
 
+template <class Row>
 __global__ __launch_bounds__(256) void k_select_keys(const SelectArgs A) {
   __shared__ int32_t s_cnt[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool ok = false;
   if (i < A.n_items) {
-    A.keys[i] = select_key(A, i, &ok);
+    A.keys[i] = select_key<Row>(A, i, &ok);
     A.index[i] = i;
   }
   const unsigned long long m = __ballot(ok);
@@ -112,27 +121,30 @@ __global__ __launch_bounds__(kSelectBlock) void k_select_tile(const u64* keys_in
 
 // n_selected = min(k, n_accepted); header, then the indices and the rows of the first n_selected entries of the sorted (keys, index).  Positions >=
 // n_selected are left alone (the host does not read them).
+template <class Row>
 LSM2D_DEV void select_gather(const SelectArgs& A, int n_acc, const u64* keys, const int32_t* index, int32_t* down) {
   const int n_sel = n_acc < A.k ? n_acc : A.k;
   if (threadIdx.x == 0) { down[0] = n_acc; down[1] = n_sel; down[2] = 0; down[3] = 0; }
   int32_t* d_index = down + kSelectHeaderWords;
   int32_t* d_rows = down + kSelectHeaderWords + A.k;
   const int32_t* rows = reinterpret_cast<const int32_t*>(A.rows);      // words are moved as bits: counts and the digest lie among the sums
-  for (int e = threadIdx.x; e < n_sel * kLinOutWords; e += (int) blockDim.x) {
-    const int j = e / kLinOutWords, w = e % kLinOutWords;
+  for (int e = threadIdx.x; e < n_sel * Row::kWords; e += (int) blockDim.x) {
+    const int j = e / Row::kWords, w = e % Row::kWords;
     const int32_t i = index[j];
     if (keys[j] == kSelectRejected || (uint32_t) i >= (uint32_t) A.n_items) continue;      // (cannot be: the n_accepted smallest entries are accepted items)
     if (w == 0) d_index[j] = i;
-    d_rows[e] = rows[(size_t) i * kLinOutWords + w];
+    d_rows[e] = rows[(size_t) i * Row::kWords + w];
   }
 }
 
+template <class Row>
 __global__ __launch_bounds__(256) void k_select_gather(const SelectArgs A, const u64* keys, const int32_t* index, int32_t* down) {
-  select_gather(A, *A.n_accepted, keys, index, down);
+  select_gather<Row>(A, *A.n_accepted, keys, index, down);
 }
 
 // n_items <= tile: keys, sort and gather by ONE workgroup in one launch.  `sort_size`: the smallest power of two >= max(n_items, 2) -- the network runs over
 // that many entries only.  The accepted items are counted through LDS: A.keys, A.index and A.n_accepted are not used.
+template <class Row>
 __global__ __launch_bounds__(kSelectBlock) void k_select_tile_one(const SelectArgs A, int32_t sort_size, int32_t* down) {
   __shared__ u64 s_key[kSelectTile];
   __shared__ int32_t s_idx[kSelectTile];
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(kSelectBlock) void k_select_tile_one(const SelectAr
   for (int e = t; e < sort_size; e += kSelectBlock) {
     bool ok = false;
     const bool in = e < A.n_items;
-    s_key[e] = in ? select_key(A, e, &ok) : kSelectRejected;
+    s_key[e] = in ? select_key<Row>(A, e, &ok) : kSelectRejected;
     s_idx[e] = in ? e : 0x7fffffff;
     mine += __popcll(__ballot(ok));      // (over the lanes that are in the loop; lane 0 of a wave is whenever one of its lanes is)
   }
@@ -150,5 +162,5 @@ __global__ __launch_bounds__(kSelectBlock) void k_select_tile_one(const SelectAr
   select_sort(s_key, s_idx, sort_size);
   int n_acc = 0;
   for (int w = 0; w < kSelectBlock / 64; ++w) n_acc += s_cnt[w];
-  select_gather(A, n_acc, s_key, s_idx, down);
+  select_gather<Row>(A, n_acc, s_key, s_idx, down);
 }

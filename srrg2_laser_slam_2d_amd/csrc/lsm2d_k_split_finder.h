@@ -219,8 +219,9 @@ struct LinArgs {
 // item of a batch gets the single call's bits by construction (tests/test_gpu_linearize_batch.py compares them bit for bit, in both orders of summation).
 // Workgroup `blk` of the `nblk` workgroups of 256 threads that share one correspondence vector: a grid-stride walk over the pairs, the thread's sums through the
 // wave tree and the workgroup's four waves, one row of kAccumWords to `row`; the workgroup's share of the pair digest is added to *dig (zeroed beforehand).
+// slice_salt: slice * 0x632BE5AB of the digest's hash (pair_hash_dev) -- 0 from every caller that linearises a lone slice; the aligner scoring passes its slice's.
 LSM2D_DEV void linearize_partial_body(const CloudDev& fixed, const CloudDev& moving, int fc, int mc, const int32_t* pairs, int n_pairs, const Iso& T, bool cauchy,
-                                      float tau, int blk, int nblk, float* row, unsigned long long* dig, float* red /* [4 * kAccumWords] */, u64* s_dig) {
+                                      float tau, uint32_t slice_salt, int blk, int nblk, float* row, unsigned long long* dig, float* red /* [4 * kAccumWords] */, u64* s_dig) {
   const int tid = threadIdx.x;
   const int fbase = fixed.start[fc], mbase = moving.start[mc];
   Accum acc; accum_zero(acc);
@@ -229,7 +230,7 @@ LSM2D_DEV void linearize_partial_body(const CloudDev& fixed, const CloudDev& mov
   u64 dg = 0ull;
   for (int k = blk * 256 + tid; k < n_pairs; k += nblk * 256) {
     const int fi = pairs[2 * k], mi = pairs[2 * k + 1];
-    dg += pair_hash_dev(0u, (uint32_t) fi, (uint32_t) mi);
+    dg += pair_hash_dev(slice_salt, (uint32_t) fi, (uint32_t) mi);
     accumulate_pair(T, fixed.xy[fbase + fi], fixed.nrm[fbase + fi], moving.xy[mbase + mi], moving.nrm[mbase + mi], cauchy, tau, acc);
   }
   if (dg) atomicAdd(reinterpret_cast<unsigned long long*>(s_dig), (unsigned long long) dg);
@@ -254,7 +255,7 @@ LSM2D_DEV void linearize_final_body(const float* partial, int n_blocks, float* o
 // "sum_order" 1: ONE workgroup of kAlignBlock threads owns the vector: trips of kAlignBlock consecutive pairs, their terms as records in LDS, eleven lanes of
 // wave 0 adding them in ascending position (lsm2d_device.h).  The totals go to out[kAccumWords], the digest to *dig (written, not added).
 LSM2D_DEV void linearize_seq_body(const CloudDev& fixed, const CloudDev& moving, int fc, int mc, const int32_t* pairs, int n_pairs, const Iso& T, bool cauchy,
-                                  float tau, float* out, unsigned long long* dig, float* s_rec /* [kSeqHalf * kSeqFields], 16-byte aligned */,
+                                  float tau, uint32_t slice_salt, float* out, unsigned long long* dig, float* s_rec /* [kSeqHalf * kSeqFields], 16-byte aligned */,
                                   float* red /* [(kAlignBlock / 64) * kAccumWords] */, u64* s_dig) {
   const int tid = threadIdx.x;
   const int fbase = fixed.start[fc], mbase = moving.start[mc];
@@ -268,7 +269,7 @@ LSM2D_DEV void linearize_seq_body(const CloudDev& fixed, const CloudDev& moving,
     float t[kSeqFields]; seq_zero(t);
     if (k < n_pairs) {
       const int fi = pairs[2 * k], mi = pairs[2 * k + 1];
-      dg += pair_hash_dev(0u, (uint32_t) fi, (uint32_t) mi);
+      dg += pair_hash_dev(slice_salt, (uint32_t) fi, (uint32_t) mi);
       bool inl; pair_terms(T, fixed.xy[fbase + fi], fixed.nrm[fbase + fi], moving.xy[mbase + mi], moving.nrm[mbase + mi], cauchy, tau, false, t, inl);
       ++acc.n_corr; acc.n_in += inl ? 1 : 0; acc.n_out += inl ? 0 : 1;
     }
@@ -296,7 +297,7 @@ LSM2D_DEV void linearize_seq_body(const CloudDev& fixed, const CloudDev& moving,
 __global__ __launch_bounds__(256) void k_linearize_partial(const LinArgs A) {
   __shared__ float red[4 * kAccumWords];
   __shared__ u64 s_dig;
-  linearize_partial_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, (int) blockIdx.x, (int) gridDim.x,
+  linearize_partial_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, 0u, (int) blockIdx.x, (int) gridDim.x,
                          A.partial + (size_t) blockIdx.x * kAccumWords, A.dig, red, &s_dig);
 }
 
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(kAlignBlock) void k_linearize_seq(const LinArgs A) 
   __shared__ __attribute__((aligned(16))) float s_rec[kSeqHalf * kSeqFields];
   __shared__ float red[(kAlignBlock / 64) * kAccumWords];
   __shared__ u64 s_dig;
-  linearize_seq_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, A.out, A.dig, s_rec, red, &s_dig);
+  linearize_seq_body(A.fixed, A.moving, A.fc, A.mc, A.pairs, A.n_pairs, A.T, A.cauchy != 0, A.tau, 0u, A.out, A.dig, s_rec, red, &s_dig);
 }
 
 __global__ void k_linearize_final(const float* partial, int n_blocks, float* out) {
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void k_linearize_partial_batch(const LinBatchA
   __shared__ u64 s_dig;
   const int i = __builtin_amdgcn_readfirstlane(A.wg_item[blockIdx.x]);
   const LinItem it = A.items[i];
-  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau,
+  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau, 0u,
                          (int) blockIdx.x - it.block_base, it.blocks, A.partial + (size_t) blockIdx.x * kAccumWords, A.dig + i, red, &s_dig);
 }
 
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(kAlignBlock) void k_linearize_seq_batch(const LinBa
   __shared__ u64 s_dig;
   const LinItem it = A.items[blockIdx.x];
   float* row = A.out + (size_t) blockIdx.x * kLinOutWords;
-  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau, row,
+  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) it.pair_base, it.n_pairs, it.T, A.cauchy != 0, A.tau, 0u, row,
                      reinterpret_cast<unsigned long long*>(row + kAccumWords), s_rec, red, &s_dig);
 }
 
@@ -392,6 +393,7 @@ struct ScoreBatchArgs {
   const int32_t* pairs;       // [n_items][slot][2]: what the finder wrote
   int32_t n_items, slot, blocks_per_item;      // blocks_per_item = lin_blocks(slot)
   int32_t cauchy; float tau;
+  uint32_t slice_salt;        // slice * 0x632BE5AB of the pairs' digest (pair_hash_dev): 0 for a lone slice, the aligner's salt when the items are slice `slice` of one (lsm2d_score_aligner_batch)
   float* partial;             // [n_items][blocks_per_item][kAccumWords]
   unsigned long long* dig;    // [n_items], zeroed by the host (tree order only)
   float* out;                 // [n_items][kLinOutWords]
@@ -409,7 +411,7 @@ __global__ __launch_bounds__(256) void k_score_partial_batch(const ScoreBatchArg
   const int nblk = lin_blocks(n);
   if (blk >= nblk) return;      // the whole workgroup, before any barrier
   const FindItem it = A.items[i];
-  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) i * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, blk, nblk,
+  linearize_partial_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) i * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, A.slice_salt, blk, nblk,
                          A.partial + (size_t) blockIdx.x * kAccumWords, A.dig + i, red, &s_dig);
 }
 
@@ -428,6 +430,6 @@ __global__ __launch_bounds__(kAlignBlock) void k_score_seq_batch(const ScoreBatc
   const FindItem it = A.items[blockIdx.x];
   const int n = __builtin_amdgcn_readfirstlane(score_count(A, (int) blockIdx.x));
   float* row = A.out + (size_t) blockIdx.x * kLinOutWords;
-  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) blockIdx.x * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, row,
+  linearize_seq_body(A.fixed, A.moving, it.fc, it.mc, A.pairs + 2 * (size_t) blockIdx.x * (size_t) A.slot, n, it.T, A.cauchy != 0, A.tau, A.slice_salt, row,
                      reinterpret_cast<unsigned long long*>(row + kAccumWords), s_rec, red, &s_dig);
 }

@@ -248,6 +248,110 @@ inline Relocalization relocalize(Context& ctx, const lsm2d_aligner_params& align
   return r;
 }
 
+// ---- pose hypotheses scored against a whole aligner: its slices with their sensor offsets and skip thresholds, an optional prior per hypothesis ----
+// (lsm2d_score_aligner_batch / lsm2d_score_aligner_select).  slices[s] reads fixed[s] / moving[s]; the index vectors are empty or [n_slices][n] flat, as
+// lsm2d_batch takes them; priors is empty or holds one per pose.  A row is what the first iteration of lsm2d_align_batch holds just before its solve;
+// active counts the slices that contributed (0: zeros, the hypothesis the aligner would end with LSM2D_NOT_ENOUGH_CORRESPONDENCES).
+struct AlignerScore { Linearization row; int32_t active = 0; };
+struct AlignerSelection { std::vector<int32_t> index; std::vector<AlignerScore> rows; int32_t n_accepted = 0; };
+namespace detail {
+struct ScoreAlignerBatch {
+  std::vector<const lsm2d_cloudset*> fx, mv; lsm2d_batch b{};
+  ScoreAlignerBatch(const char* who, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
+                    const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses, const std::vector<lsm2d_prior>& priors,
+                    const std::vector<int32_t>& fixed_index, const std::vector<int32_t>& moving_index) {
+    const size_t n = poses.size(), ns = slices.size();
+    if (fixed.size() != ns || moving.size() != ns) throw std::runtime_error(std::string(who) + "| one fixed and one moving set per slice");
+    if ((!fixed_index.empty() && fixed_index.size() != ns * n) || (!moving_index.empty() && moving_index.size() != ns * n))
+      throw std::runtime_error(std::string(who) + "| an index vector is empty or holds n_slices x n entries");
+    if (!priors.empty() && priors.size() != n) throw std::runtime_error(std::string(who) + "| priors is empty or holds one per pose");
+    for (size_t s = 0; s < ns; ++s) { fx.push_back(fixed[s] ? fixed[s]->get() : nullptr); mv.push_back(moving[s] ? moving[s]->get() : nullptr); }
+    b.n_alignments = (int32_t) n; b.n_slices = (int32_t) ns; b.slices = slices.data(); b.fixed = fx.data(); b.moving = mv.data();
+    b.fixed_index = fixed_index.empty() ? nullptr : fixed_index.data(); b.moving_index = moving_index.empty() ? nullptr : moving_index.data();
+    b.init_pose = n ? poses[0].data() : nullptr; b.prior = priors.empty() ? nullptr : priors.data();
+  }
+};
+inline void fillAlignerScores(std::vector<AlignerScore>& out, size_t m, const std::vector<float>& H, const std::vector<float>& b,
+                              const std::vector<lsm2d_iteration_stats>& st, const std::vector<int32_t>& active) {
+  out.resize(m);
+  for (size_t i = 0; i < m; ++i) {
+    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].row.H.begin());
+    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].row.b.begin());
+    out[i].row.stats = st[i]; out[i].active = active[i];
+  }
+}
+}  // namespace detail
+inline std::vector<AlignerScore> scoreAligner(Context& ctx, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
+                                              const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses,
+                                              const std::vector<lsm2d_prior>& priors = {}, const std::vector<int32_t>& fixed_index = {},
+                                              const std::vector<int32_t>& moving_index = {}) {
+  const detail::ScoreAlignerBatch d("scoreAligner", slices, fixed, moving, poses, priors, fixed_index, moving_index);
+  const size_t n = poses.size(), cap = std::max<size_t>(n, 1);
+  std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap); std::vector<int32_t> active(cap, 0);
+  check(lsm2d_score_aligner_batch(ctx.get(), &d.b, H.data(), b.data(), st.data(), active.data()), "lsm2d_score_aligner_batch", ctx.get());
+  std::vector<AlignerScore> out; detail::fillAlignerScores(out, n, H, b, st, active);
+  return out;
+}
+// ... then the acceptance test and the best k accepted hypotheses ranked on the device, as scoreSelect ranks; a hypothesis with active == 0 is rejected
+inline AlignerSelection scoreAlignerSelect(Context& ctx, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
+                                           const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses, const lsm2d_select_params& select,
+                                           int32_t k, const std::vector<lsm2d_prior>& priors = {}, const std::vector<int32_t>& fixed_index = {},
+                                           const std::vector<int32_t>& moving_index = {}) {
+  const detail::ScoreAlignerBatch d("scoreAlignerSelect", slices, fixed, moving, poses, priors, fixed_index, moving_index);
+  const size_t cap = (size_t) std::max<int32_t>(k, 1);
+  std::vector<int32_t> idx(cap), active(cap, 0); std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap);
+  int32_t n_sel = 0; AlignerSelection out;
+  check(lsm2d_score_aligner_select(ctx.get(), &d.b, &select, k, idx.data(), H.data(), b.data(), st.data(), active.data(), &n_sel, &out.n_accepted),
+        "lsm2d_score_aligner_select", ctx.get());
+  out.index.assign(idx.begin(), idx.begin() + n_sel);
+  detail::fillAlignerScores(out.rows, (size_t) n_sel, H, b, st, active);
+  return out;
+}
+
+// relocalize for the two-laser robot (MULTI.json:700-732: two WithSensor slices and the odometry prior; the relocaliser's own aligner is unset, :749-769,
+// and falls back on it): scoreAlignerSelect, then lsm2d_align_batch on the selected hypotheses from their own poses with their own priors, then the
+// acceptance test on the statistics of the last iteration each started.  Pure composition.
+struct AlignerRelocalization {
+  AlignerSelection selection;
+  std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> status, iterations;
+  std::vector<lsm2d_iteration_stats> last_stats; std::vector<char> accepted;
+};
+inline AlignerRelocalization relocalize(Context& ctx, const lsm2d_aligner_params& aligner, const std::vector<lsm2d_slice_params>& slices,
+                                        const std::vector<const CloudSet*>& fixed, const std::vector<const CloudSet*>& moving,
+                                        const std::vector<Vector3f>& poses, const lsm2d_select_params& select, int32_t k,
+                                        const std::vector<lsm2d_prior>& priors = {}, const std::vector<int32_t>& fixed_index = {},
+                                        const std::vector<int32_t>& moving_index = {}) {
+  AlignerRelocalization r;
+  r.selection = scoreAlignerSelect(ctx, slices, fixed, moving, poses, select, k, priors, fixed_index, moving_index);
+  const size_t m = r.selection.index.size(), n = poses.size(), ns = slices.size();
+  if (!m) return r;
+  // the selected items' clouds, spelled out for every slice: NULL means "cloud i" only while the batch is the whole set
+  auto chosen = [&](const std::vector<const CloudSet*>& sets, const std::vector<int32_t>& idx) {
+    std::vector<int32_t> out;
+    bool all_single = idx.empty();
+    for (const CloudSet* cs : sets) all_single = all_single && cs->numClouds() == 1;
+    if (all_single) return out;
+    for (size_t s = 0; s < ns; ++s)
+      for (int32_t i : r.selection.index) out.push_back(!idx.empty() ? idx[s * n + (size_t) i] : (sets[s]->numClouds() == 1 ? 0 : i));
+    return out;
+  };
+  const std::vector<int32_t> fi = chosen(fixed, fixed_index), mi = chosen(moving, moving_index);
+  std::vector<Vector3f> x0(m); std::vector<lsm2d_prior> pr;
+  for (size_t j = 0; j < m; ++j) { x0[j] = poses[(size_t) r.selection.index[j]]; if (!priors.empty()) pr.push_back(priors[(size_t) r.selection.index[j]]); }
+  const detail::ScoreAlignerBatch d("relocalize", slices, fixed, moving, x0, pr, fi, mi);
+  const size_t cap = (size_t) lsm2d_stats_capacity(&aligner);
+  std::vector<lsm2d_iteration_stats> st(m * cap);
+  r.pose.resize(m); r.information.resize(m); r.status.resize(m); r.iterations.resize(m); r.last_stats.resize(m); r.accepted.resize(m);
+  check(lsm2d_align_batch(ctx.get(), &aligner, &d.b, r.pose[0].data(), r.information[0].data(), r.status.data(), r.iterations.data(), st.data()),
+        "lsm2d_align_batch", ctx.get());
+  for (size_t j = 0; j < m; ++j) {
+    const size_t it = (size_t) std::min<long>(std::max<long>((long) r.iterations[j] - 1, 0), (long) cap - 1);
+    r.last_stats[j] = st[j * cap + it];
+    r.accepted[j] = r.status[j] == LSM2D_SUCCESS && selectAccept(r.last_stats[j], select);
+  }
+  return r;
+}
+
 class CorrespondenceFinderProjective2f {
  public:
   explicit CorrespondenceFinderProjective2f(Context& ctx) : _ctx(ctx) {}
