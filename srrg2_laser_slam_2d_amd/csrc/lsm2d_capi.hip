@@ -78,17 +78,12 @@ struct lsm2d_context {
   int n_cu = 0;                // compute units of the device (hipDeviceProp_t.multiProcessorCount)
   int cull_est_um = 0, cull_est_urad = 40000;      // margins of the work estimate's chunk test ("cull_est_um", "cull_est_urad"; placement only)
   int results_to_host = 1;     // batches that travel by copies: poses, information matrices, statuses, iteration counts and clock stamps written straight to pinned host memory (0: to the device and copied; A/B knob)
-  int two_stage = 0;           // 1: ... in TWO launches: iteration 0 first (k_first_iteration), the rest placed by the length of iteration 1's unit lists.  Measured on configs[1]: the second
-                               // launch 0.698 ms with a tail of 7 % instead of 10, but the first costs 95 us (every workgroup in the same phase at the same time: nothing overlaps) and the ordering 16:
-                               // 0.861 vs 0.836 ms per step.  Off; kept as an A/B knob with its bit-identity test
   int balance_notes = 1;       // ... group the workgroup ids by the CU the previous launch of the same shape ran them on (0: assume b, b + n_cu, ...; A/B knob)
   int32_t* d_wg_place = nullptr; unsigned long long wg_place_shape = 0;      // the notes (one int per workgroup) and the launch shape they belong to
-  uint32_t* d_xcd = nullptr; size_t d_xcd_bytes = 0;                         // the XCD window's counters (AlignArgs::xcd_sync), cleared per launch
   int proj_modes = 1;          // projective batches against map-sized clouds: the instantiation with the culled stream only (0: the shared one; A/B knob)
   int kd_modes = 1;            // KD-tree batches: the instantiations with one form of the descent only (0: the shared one; A/B knob)
   int nn_lds_only = 1;         // grid NN with every alignment's tables staged in LDS: the instantiation without the search in global memory (0: the shared one; A/B knob)
   int nn_qcache = 1;           // grid NN over a map-sized fixed cloud: cache every query's cell ranges in LDS between iterations (0: off; A/B knob)
-  int cull_block = 0;          // steps per unit of the culled stream (0: automatic, ~1/25 of a chunk; even; tuning knob)
   int sum_order = 0;           // 0: H, b and the chi^2 sums are formed in trees (a thread's pairs, 64 lanes, 8 waves: the fast order); 1: pair after pair in the reference's order
                                // (nicp_post.m:69-90: ascending column / moving index) -- bitwise the sequential fp32 CPU restatement the tests check against; k_align_seq, k_split_finish<true>, k_linearize_seq
   int pack_extra_max = 32;     // packed batches above 2048 alignments: up to this many more than whole rounds hold (experiments build: tuning knob)
@@ -108,8 +103,6 @@ struct lsm2d_context {
   int clock_stride = 0;               // 0: ~32 stamped workgroups per launch; > 0: every clock_stride-th ("clock_stride" option, diagnostics)
   long long last_clock_khz = 0;       // in-kernel clock of the most recent timed k_align launch (median over the stamped workgroups), 0 = none
   long long last_wg_lifetime_ns = 0;  // median lifetime of its stamped workgroups
-  int xcd_lockstep = 0;        // big-map batches of one dispatch round: the workgroups of an XCD walk the map in step, pass by pass ("xcd_lockstep": 0 free-running, 1 nobody starts
-                               // a pass before everybody on its XCD has finished the previous one, 2 .. : the one before that, ...)
   int uploads = 0;             // host-to-device cloud uploads queued so far ("uploads", read-only: the adapters' upload-once test reads it)
   long long last_h2d_bytes = 0; // bytes the most recent cloud upload moved over the host link
   int experiments =
@@ -119,9 +112,7 @@ struct lsm2d_context {
       0;
 #endif
   int lane_streams = 1;        // asynchronously begun batches launch on their lane's own stream (lane_stream); experiments build: 0 = in order on the context's stream, as first built
-  int order_cluster = 0;       // experiments build: > 0 = big-map batches are dealt to workgroup ids by the sensors' positions and headings (value / 10 = metres per radian of heading): see make_placement
   int estimate_reuse = 1;      // a prepared batch run again with unchanged start poses keeps its placement (no k_cull_estimate launch); experiments build: 0 switches that off
-  int last_xcd_lockstep = 0;   // what the latest aligner call ran with (0: free-running)
   int last_cull_estimate = 0;  // what the latest aligner call did about the placement's estimate ("last_cull_estimate")
   int last_query_cull = 0;     // the latest aligner call ran its point-query finder with the exact culling of the queries (k_align, tiles of 64 moving points)
   long long last_kd_levels = 0, last_kd_nodes = 0;      // shape of the most recently built KD-tree set (levels of the deepest tree, nodes in all of them)
@@ -280,7 +271,7 @@ struct lsm2d_cloudset {
   mutable float4* d_lane_xy = nullptr; mutable long long* d_lane_start = nullptr; mutable int32_t* d_lane_T = nullptr;
   mutable float4* d_lane_bounds = nullptr;      // bounding circle of every thread's chunk of every cloud (k_lane_bounds): what the culling tests
   mutable float4* d_block_bounds = nullptr;     // ... and of every block of every chunk (k_block_bounds): the block-level test of the unit lists
-  mutable int32_t block_stride = kCullBlocks;   // blocks per chunk in d_block_bounds: kCullBlocksMax for a set that holds a map-sized cloud (cull_blocks_for)
+  mutable int32_t block_stride = kCullBlocks;   // blocks per chunk in d_block_bounds
   mutable float4* d_aos = nullptr;              // (x, y, nx, ny) rows of the whole set (k_aos_rows): one gather per z-buffer winner in k_align's bin walk
   hipEvent_t ev_stage = nullptr; bool stage_on_side = false;      // behind the set's latest copy OUT of h_upload queued on a side stream (the refill's pageable path): what acquire_upload_stage waits for
   hipEvent_t ev_prep = nullptr;                 // behind the set's latest preprocessing launch on the refill stream: its NEXT refill's copy (another stream) overwrites what that launch reads
@@ -340,9 +331,6 @@ enum : unsigned { kFProj = 1, kFNN = 2, kFDist = 4, kFKd = 8 };
 struct AlignVariant { unsigned finders; int mode; AlignKernel fn; };
 static const AlignVariant kAlignVariants[] = {
   {kFProj, 5, k_align<true, false, false, false, 5>}, {kFProj, 0, k_align<true, false, false>},
-#ifdef LSM2D_EXPERIMENTS
-  {kFProj, 6, k_align<true, false, false, false, 6>},      // 5 with the XCD lockstep ("xcd_lockstep": measured, 2x slower on configs[4] for 65 % less fabric traffic: DESIGN App. A)
-#endif
   {kFNN, 1, k_align<false, true, false, false, 1>},   {kFNN, 2, k_align<false, true, false, false, 2>}, {kFNN, 0, k_align<false, true, false>},
   {kFDist, 0, k_align<false, false, true>},
   {kFKd, 3, k_align<false, false, false, true, 3>},   {kFKd, 4, k_align<false, false, false, true, 4>}, {kFKd, 0, k_align<false, false, false, true>},
@@ -404,9 +392,6 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   (void) hipFuncSetAttribute((const void*) k_align<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align<true, false, false, false, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-#ifdef LSM2D_EXPERIMENTS
-  (void) hipFuncSetAttribute((const void*) k_align<true, false, false, false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-#endif
   (void) hipFuncSetAttribute((const void*) k_align<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   for (const AlignVariant& v : kAlignVariantsSeq) (void) hipFuncSetAttribute((const void*) v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
@@ -414,10 +399,6 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   (void) hipFuncSetAttribute((const void*) k_align_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_cull_estimate, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-#ifdef LSM2D_EXPERIMENTS
-  (void) hipFuncSetAttribute((const void*) k_first_iteration, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_balance_only, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-#endif
   (void) hipFuncSetAttribute((const void*) k_kd_build_scan<1>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_kd_build_scan<0>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_kd_build_scan_multi<1>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
@@ -457,7 +438,6 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
   if (c->d_wg_place) (void) hipFree(c->d_wg_place);
   for (hipEvent_t e : {c->side_pre.ev, c->side_refill.ev, c->side_copy.ev, c->ev_main, c->ev_a_est}) if (e) (void) hipEventDestroy(e);
   for_each_extra_stream(c, true, [](hipStream_t st) { (void) hipStreamDestroy(st); });
-  if (c->d_xcd) (void) hipFree(c->d_xcd);
   for (auto& bd : c->beam_dirs) if (bd.d_dir) (void) hipFree(bd.d_dir);
   if (c->owns_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
@@ -472,17 +452,12 @@ extern "C" int lsm2d_synchronize(lsm2d_context* ctx) {
 
 // ---- options ---------------------------------------------------------------------------------------------------------------------------
 // ONE table (round 5; 39 strcmp lines before).  Public keys are the ones include/lsm2d.h documents: what a caller may legitimately choose.  The A/B knobs of
-// measured-and-rejected or always-on alternatives (DESIGN App. A) exist only in a -DLSM2D_EXPERIMENTS build of the library: the shipped one answers
+// always-on alternatives (DESIGN App. A) exist only in a -DLSM2D_EXPERIMENTS build of the library: the shipped one answers
 // "unknown option" to them, and "experiments" reads 0 there.
 namespace {
-enum : int { kOptBool = 1, kOptEven = 2, kOptResetsNotes = 4, kOptReadOnly = 8, kOptExperiment = 16 };
+enum : int { kOptBool = 1, kOptResetsNotes = 4, kOptReadOnly = 8, kOptExperiment = 16 };
 struct OptionDesc { const char* key; int lsm2d_context::* field; long long lo, hi; int flags; };
 struct OptionDescLL { const char* key; long long lsm2d_context::* field; };
-#ifdef LSM2D_EXPERIMENTS
-constexpr int kCullMax = 2;
-#else
-constexpr int kCullMax = 1;
-#endif
 const OptionDesc kOptions[] = {
   // ---- public (include/lsm2d.h)
   {"kernel_timing",      &lsm2d_context::kernel_timing,      0, 1,          kOptBool},
@@ -490,7 +465,7 @@ const OptionDesc kOptions[] = {
   {"align_path",         &lsm2d_context::align_path,         0, 3,          0},
   {"find_path",          &lsm2d_context::find_path,          0, 1,          0},
   {"zero_copy_max",      &lsm2d_context::zero_copy_max,      0, 65536,      0},
-  {"cull",               &lsm2d_context::cull,               0, kCullMax,   0},
+  {"cull",               &lsm2d_context::cull,               0, 1,          0},
   {"balance",            &lsm2d_context::balance,            0, 1,          0},
   {"cull_margin_um",     &lsm2d_context::cull_margin_um,     0, 1000000,    0},
   {"cull_margin_urad",   &lsm2d_context::cull_margin_urad,   0, 50000,      0},      // (the kept lists' proof compares |sin dth| with the margin: asin(x) - x stays below the test's 0.05-column slack up to here)
@@ -507,21 +482,18 @@ const OptionDesc kOptions[] = {
   {"max_dyn_lds",        &lsm2d_context::max_dyn_lds,        0, 0, kOptReadOnly},      // bytes of LDS one workgroup may ask for
   {"uploads",            &lsm2d_context::uploads,            0, 0, kOptReadOnly},      // host-to-device cloud uploads this context has queued so far (lsm2d_cloudset_create / _upload)
   {"last_cull_estimate", &lsm2d_context::last_cull_estimate, 0, 0, kOptReadOnly},      // 1: the latest aligner call launched the placement's estimate; 0: it reused the order of an unchanged prepared batch, or needed none
-  {"last_xcd_lockstep",  &lsm2d_context::last_xcd_lockstep,  0, 0, kOptReadOnly},
   {"experiments",        &lsm2d_context::experiments,        0, 0, kOptReadOnly},
 #ifdef LSM2D_EXPERIMENTS
   // ---- A/B knobs of the experiments build (the GPU suite with LSM2D_EXPERIMENTS=1; each one's measurement: DESIGN App. A)
   {"cull_est_um",        &lsm2d_context::cull_est_um,        0, 1000000, kOptExperiment},
   {"cull_est_urad",      &lsm2d_context::cull_est_urad,      0, 1000000, kOptExperiment},
   {"results_to_host",    &lsm2d_context::results_to_host,    0, 1,       kOptExperiment},
-  {"two_stage",          &lsm2d_context::two_stage,          0, 1,       kOptExperiment | kOptResetsNotes},
   {"balance_notes",      &lsm2d_context::balance_notes,      0, 1,       kOptExperiment | kOptResetsNotes},
   {"cull_keep",          &lsm2d_context::cull_keep,          0, 1,       kOptExperiment | kOptBool},
   {"nn_qcache",          &lsm2d_context::nn_qcache,          0, 1,       kOptExperiment | kOptBool},
   {"nn_lds_only",        &lsm2d_context::nn_lds_only,        0, 1,       kOptExperiment | kOptBool},
   {"kd_modes",           &lsm2d_context::kd_modes,           0, 1,       kOptExperiment | kOptBool},
   {"proj_modes",         &lsm2d_context::proj_modes,         0, 1,       kOptExperiment | kOptBool},
-  {"cull_block",         &lsm2d_context::cull_block,         0, 4096,    kOptExperiment | kOptEven},
   {"kd_chain",           &lsm2d_context::kd_chain,           0, 1,       kOptExperiment},
   {"grid_big_cells_x10", &lsm2d_context::grid_big_cells_x10, 5, 400,     kOptExperiment},
   {"kd_scan_max_clouds", &lsm2d_context::kd_scan_max_clouds, 0, 0x7fffffff, kOptExperiment},
@@ -529,8 +501,6 @@ const OptionDesc kOptions[] = {
   {"kd_wg_max_points",   &lsm2d_context::kd_wg_max_points,   0, 1 << 20, kOptExperiment},
   {"estimate_reuse",     &lsm2d_context::estimate_reuse,     0, 1,       kOptExperiment},
   {"lane_streams",       &lsm2d_context::lane_streams,       0, 1,       kOptExperiment},
-  {"xcd_lockstep",       &lsm2d_context::xcd_lockstep,       0, 64,      kOptExperiment},
-  {"order_cluster",      &lsm2d_context::order_cluster,      0, 10000,   kOptExperiment},
   {"pack_extra_max",     &lsm2d_context::pack_extra_max,     0, 1024,    kOptExperiment},
 #endif
 };
@@ -547,8 +517,8 @@ extern "C" int lsm2d_set_option(lsm2d_context* ctx, const char* key, int64_t val
     if (strcmp(key, o.key)) continue;
     if (o.flags & kOptReadOnly) return fail(ctx, LSM2D_BAD_ARGUMENT, "set_option: this key is read-only");
     if (o.flags & kOptBool) value = value != 0;
-    if (value < o.lo || value > o.hi || ((o.flags & kOptEven) && (value & 1))) {
-      char buf[160]; snprintf(buf, sizeof buf, "set_option: %s must be %sin %lld .. %lld", o.key, (o.flags & kOptEven) ? "even and " : "", o.lo, o.hi);
+    if (value < o.lo || value > o.hi) {
+      char buf[160]; snprintf(buf, sizeof buf, "set_option: %s must be in %lld .. %lld", o.key, o.lo, o.hi);
       return fail(ctx, LSM2D_BAD_ARGUMENT, buf);
     }
     if (o.field == &lsm2d_context::align_width && value != 0 && value != 256 && value != 512 && value != 1024)      // (any other value used to act as 0)

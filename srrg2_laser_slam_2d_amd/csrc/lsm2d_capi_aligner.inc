@@ -32,7 +32,6 @@ struct lsm2d_pending {
   size_t o_pose = 0, o_H = 0, o_status = 0, o_its = 0, o_stats = 0, o_last_pose = 0, o_clock = 0;
   int n = 0, stats_stride = 0, n_clock = 0, clock_stride = 0;
   bool zero_copy = false, want_stats = false, want_last_pose = false, stamps = false, timed = false, async = false;
-  uint32_t* xcd_sync = nullptr; int xcd_stride = 0, xcd_window = 0, xcd_positions = 0;
 };
 static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats, float* out_last_pose);
 
@@ -106,9 +105,6 @@ struct AlignBatch {
   AlignArgs A;
   // ---- scratch / staging layout: [init_pose | prior | indices | out_pose | out_H | status | its | stats | last_pose | clock | work | ff_rows]
   size_t off, o_pose_in, o_prior, o_fidx[kMaxSlices], o_midx[kMaxSlices], in_bytes, o_pose, o_H, o_status, o_its, o_stats, o_last_pose, o_clock, out_bytes, o_work, o_ff_rows, total_bytes;
-#ifdef LSM2D_EXPERIMENTS
-  size_t o_order, o_resume;
-#endif
   int clock_stride, n_clock;
   bool had_inputs; char* hs; char* ds;
   // ---- which path
@@ -118,7 +114,7 @@ struct AlignBatch {
   // ---- slices, LDS
   int cols_max, fcan_total, max_fixed_rows; const KdCache* kd_cache0;
   size_t lds, pq_bytes, lds_budget, lds_pair0, lds_mov, lds_fix, lds_pair;
-  bool proj_culled_for_all, xcd_on, nn_lds_for_all;
+  bool proj_culled_for_all, nn_lds_for_all;
   // ---- inputs, results
   bool same_inputs, host_results, stamps;
 
@@ -174,9 +170,6 @@ int AlignBatch::validate_and_lay_out_scratch() {
   o_work = take(sizeof(int32_t) * (size_t) n);                                                     // balanced placement: the estimate's counts (device only)
   // "fast_forward" 2: H and inlier count of every alignment's last kFfRing iterations (device only; 640 bytes per alignment; needs no clearing: a row is read only after its alignment wrote it)
   o_ff_rows = (ctx->fast_forward == 2 && !out_work) ? take(sizeof(uint32_t) * kFfRowWords * kFfRing * (size_t) n) : 0;
-#ifdef LSM2D_EXPERIMENTS      // the two-launch form of a batch ("two_stage"): its order and the state between its launches (device only)
-  o_order = take(sizeof(int32_t) * (size_t) n), o_resume = take(sizeof(ResumeDev) * (size_t) n);
-#endif
   total_bytes = off;
   had_inputs = L->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
   int rc = ensure_scratch(ctx, total_bytes); if (rc) return rc;
@@ -310,7 +303,6 @@ int AlignBatch::prepare_slices() {
     S.fcan_offset = fcan_total; fcan_total += S.proj.cols; if (S.proj.cols > cols_max) cols_max = S.proj.cols;
   }
   A.cols_max = cols_max; A.fcan_total = fcan_total;
-  A.cull_block = ctx->cull_block;
   A.cull = ctx->cull;      // (the test's column loop wraps once: canvases below 64 columns are not worth it and would need a second wrap)
   for (int s = 0; s < ns; ++s) if (b->slices[s].finder == LSM2D_FINDER_PROJECTIVE && A.s[s].proj.cols < 64) A.cull = 0;
   return LSM2D_SUCCESS;
@@ -370,9 +362,8 @@ int AlignBatch::lay_out_lds() {
   if (pq_bytes) { lds = (lds + 15) & ~(size_t) 15; A.pq_cull_off = (int32_t) lds; lds += pq_bytes; }
   ctx->last_query_cull = A.pq_cull_off > 0;
   // the projective instantiation with the culled stream only: every slice's moving set has its lane-chunked copy and chunk circles, and culling is on
-  // (its unit lists -- kCullBlocks x 512 16-bit entries per slice, kept across iterations -- sit behind everything else in dynamic LDS; "cull_block" is the
-  // round-3 stream's tuning knob: a batch that sets it runs the shared instantiation)
-  proj_culled_for_all = proj_only && A.cull == 1 && ctx->proj_modes && ctx->cull_block == 0;
+  // (its unit lists -- kCullBlocks x 512 16-bit entries per slice, kept across iterations -- sit behind everything else in dynamic LDS)
+  proj_culled_for_all = proj_only && A.cull == 1 && ctx->proj_modes;
   for (int s = 0; s < ns && proj_culled_for_all; ++s)
     proj_culled_for_all = A.s[s].moving.lane_xy != nullptr && A.s[s].moving.lane_bounds != nullptr && A.s[s].moving.block_bounds != nullptr;
   A.units_off = 0; A.cull_keep = ctx->cull_keep; A.fast_forward = ctx->fast_forward;
@@ -389,16 +380,6 @@ int AlignBatch::lay_out_lds() {
   // "sum_order" 1: the trip's pair records (lsm2d_device.h), behind everything else -- three workgroups per CU instead of four
   A.seq_off = 0;
   if (ctx->sum_order) { lds = (lds + 15) & ~(size_t) 15; A.seq_off = (int32_t) lds; lds += kSeqLdsBytes; }
-  // the XCD window (AlignArgs::xcd_sync): a big-map batch of ONE dispatch round -- every workgroup resident from the start (64 VGPRs, <= 40 KB of LDS: four per
-  // CU) -- whose position space fits the counters
-  A.xcd_sync = nullptr; A.xcd_window = 0; A.xcd_stride = 0; A.xcd_positions = 0;
-  xcd_on = false;
-  if (kExperiments && proj_culled_for_all && ctx->xcd_lockstep > 0 && n > 1 && n <= 4 * ctx->n_cu && !out_work) {
-    bool big = false;
-    for (int s = 0; s < ns; ++s) big = big || b->moving[s]->block_stride == kCullBlocksMax;
-    const long long positions = (long long) it_cap * ns;      // one per (iteration, slice) pass
-    if (big && positions > 0 && positions <= 65536) { xcd_on = true; A.xcd_positions = (int32_t) positions; A.xcd_stride = (int32_t) ((16 + positions + 63) & ~63ll); A.xcd_window = ctx->xcd_lockstep - 1; }
-  }
   // the NN instantiation without the search in global memory: the staging holds every alignment's tables (sized for the largest fixed cloud above), and no
   // alignment takes the cooperative loop, which searches in global memory (the kernel's rule: fixed cloud >= 4 x moving cloud) -- whatever the pairing
   nn_lds_for_all = false;
@@ -448,10 +429,10 @@ int AlignBatch::stage_inputs() {
   // wait for a read of host memory
   A.inline_n1 = n == 1 && !use_split;
   if (A.inline_n1) { memcpy(A.pose1, b->init_pose, sizeof A.pose1); if (b->prior) memcpy(&A.prior1, hs + o_prior, sizeof A.prior1); }
-  // the stream this batch's own operations go to: its lane's when it was begun asynchronously (lane_stream) -- not for the split path (one workspace per context)
-  // nor the experiments' XCD counters.  Everything queued so far went to the context's stream (set preparation: pending preprocessing, trees, lane copies): an
+  // the stream this batch's own operations go to: its lane's when it was begun asynchronously (lane_stream) -- not for the split path (one workspace per context).
+  // Everything queued so far went to the context's stream (set preparation: pending preprocessing, trees, lane copies): an
   // event behind it orders the lane's stream and the pre-kernels' stream
-  ks = (async && !out_work && !use_split && !xcd_on) ? lane_stream(ctx) : ctx->stream;
+  ks = (async && !out_work && !use_split) ? lane_stream(ctx) : ctx->stream;
   if (ks != ctx->stream && pre != ctx->stream) {
     HIPCHK(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
     HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->ev_main, 0));
@@ -467,16 +448,6 @@ int AlignBatch::stage_inputs() {
   }
   L->inputs_valid = !zero_copy && !L->inputs_shadow.empty();
   A.init_pose = (const float*) (ds + o_pose_in);
-  if (xcd_on && !use_split && !use_pair && !zero_copy) {
-    const size_t xb = sizeof(uint32_t) * 16 * (size_t) A.xcd_stride;
-    if (xb > ctx->d_xcd_bytes) {
-      if (ctx->d_xcd) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(ctx->d_xcd)); ctx->d_xcd = nullptr; ctx->d_xcd_bytes = 0; }
-      HIPCHK(ctx, hipMalloc((void**) &ctx->d_xcd, xb)); ctx->d_xcd_bytes = xb;
-    }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_xcd, 0, xb, ctx->stream));
-    A.xcd_sync = ctx->d_xcd;
-  }
-  ctx->last_xcd_lockstep = A.xcd_sync ? A.xcd_window + 1 : 0;
   // the SMALL results of a batch that travels by copies (56 bytes per alignment + the clock stamps) are written by the kernels straight into the pinned
   // staging buffer: the device-to-host copy behind the launch -- a hand-over to the copy engine, 9 us of gap + 6 us of copy on the timeline of a
   // 1000-alignment step -- is gone, the stream wait ends with the kernel.  The statistics (28 bytes per iteration and alignment) stay on the device and are copied.
@@ -528,68 +499,9 @@ int AlignBatch::make_placement() {
   A.order = nullptr; A.wg_place = nullptr;
   A.cull_est_mt = 1e-6f * (float) ctx->cull_est_um; A.cull_est_mth = 1e-6f * (float) ctx->cull_est_urad;
   if (out_work) return LSM2D_SUCCESS;
-  A.stage = 0; A.stage_split = 0; A.resume = nullptr; A.stage_work = nullptr;
-  // a culled batch of about one dispatch round, two launches: iteration 0 anywhere (k_first_iteration), then the rest placed by what iteration 1's lists hold
-#ifdef LSM2D_EXPERIMENTS
-  const bool two_stage = !use_split && !use_pair && !zero_copy && A.cull && ctx->balance && ctx->two_stage && n > 256 && n <= 1024 && proj_culled_for_all &&
-                         proj_only && ap->max_iterations >= 4;
-  if (two_stage) {
-    int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work); int32_t* d_order = (int32_t*) ((char*) L->d_scratch + o_order);
-    const unsigned long long shape = ((unsigned long long) (unsigned) n << 32) ^ ((unsigned long long) lds << 8) ^ 6ull;
-    if (!ctx->d_wg_place) {
-      HIPCHK(ctx, hipMalloc(&ctx->d_wg_place, sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
-      HIPCHK(ctx, hipMemsetAsync(ctx->d_wg_place, 0, sizeof(int32_t) * 1025, ctx->stream));
-    }
-    const bool notes = ctx->balance_notes && ctx->wg_place_shape == shape;
-    A.stage = 1; A.stage_split = 1; A.resume = (ResumeDev*) ((char*) L->d_scratch + o_resume); A.stage_work = d_work;
-    hipLaunchKernelGGL(k_first_iteration, dim3((unsigned) n), dim3(kAlignBlock), lds, ctx->stream, A);
-    hipLaunchKernelGGL(k_balance_only, dim3(1), dim3(kAlignBlock), sizeof(BalanceLds), ctx->stream, (const int32_t*) d_work, n, ctx->n_cu, d_order,
-                       notes ? (const int32_t*) ctx->d_wg_place : (const int32_t*) nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    A.stage = 2; A.order = d_order;
-    if (ctx->balance_notes) { A.wg_place = ctx->d_wg_place; ctx->wg_place_shape = shape; }
-  }
-  else
-#endif
   // (a batch of many dispatch rounds balances itself, and the estimate of 65 536 alignments costs more than its heaviest-first order saves:
   // configs[3] 47.6 vs 47.2 ms per step -- the placement is for batches of up to four rounds)
   ctx->last_cull_estimate = 0;
-#ifdef LSM2D_EXPERIMENTS
-  // "order_cluster" (round 6, VERDICT r5 item 3a; measured: DESIGN App. A): the alignments of a big-map batch dealt to workgroup ids by WHERE THEY LOOK FROM -- k-means
-  // of the sensors' positions and headings into eight groups, group g on the ids = g mod 8, the ids of one XCD under the dispatcher's round-robin -- so that an XCD's
-  // L2 serves alignments that stream the same parts of the map.  Host-side, one 4 KB upload; replaces the balanced placement for that launch.
-  if (ctx->order_cluster && !use_split && !use_pair && !zero_copy && n > 256 && n <= 4096 && has_proj && proj_culled_for_all) {
-    const int K = 8;
-    std::vector<float> feat((size_t) 4 * n); const float Lh = 0.1f * (float) ctx->order_cluster;      // metres a radian of heading counts for (the option's value / 10)
-    for (int i = 0; i < n; ++i) {
-      const float* x = b->init_pose + 3 * (size_t) i; const float c = cosf(x[2]), s_ = sinf(x[2]);
-      feat[4 * i] = -(c * x[0] + s_ * x[1]); feat[4 * i + 1] = -(-s_ * x[0] + c * x[1]);      // the sensor's position in the map: -R^T t
-      feat[4 * i + 2] = Lh * c; feat[4 * i + 3] = -Lh * s_;                                     // its heading, on a circle of radius Lh
-    }
-    std::vector<float> cen((size_t) 4 * K); std::vector<int> lab((size_t) n, 0);
-    for (int k = 0; k < K; ++k) for (int d = 0; d < 4; ++d) cen[4 * k + d] = feat[4 * (size_t) ((long long) k * n / K) + d];
-    for (int it = 0; it < 12; ++it) {
-      for (int i = 0; i < n; ++i) {
-        float best = 3.4e38f; int bk = 0;
-        for (int k = 0; k < K; ++k) { float d2 = 0.0f; for (int d = 0; d < 4; ++d) { const float e = feat[4 * i + d] - cen[4 * k + d]; d2 += e * e; } if (d2 < best) { best = d2; bk = k; } }
-        lab[i] = bk;
-      }
-      std::vector<float> sum((size_t) 4 * K, 0.0f); std::vector<int> cnt((size_t) K, 0);
-      for (int i = 0; i < n; ++i) { ++cnt[lab[i]]; for (int d = 0; d < 4; ++d) sum[4 * lab[i] + d] += feat[4 * i + d]; }
-      for (int k = 0; k < K; ++k) if (cnt[k]) for (int d = 0; d < 4; ++d) cen[4 * k + d] = sum[4 * k + d] / (float) cnt[k];
-    }
-    std::vector<int32_t> by_cluster((size_t) n); { int p = 0; for (int k = 0; k < K; ++k) for (int i = 0; i < n; ++i) if (lab[i] == k) by_cluster[p++] = i; }
-    // position p of the cluster-sorted list -> group p / ceil(n / 8) -> workgroup id group + 8 * (p mod ceil(n / 8)); ids beyond n - 1 wrap into the gaps
-    std::vector<int32_t> ord((size_t) n, -1); const int per = (n + K - 1) / K; std::vector<int32_t> spill;
-    for (int p = 0; p < n; ++p) { const int id = p / per + K * (p % per); if (id < n) ord[id] = by_cluster[p]; else spill.push_back(by_cluster[p]); }
-    for (int id = 0, q = 0; id < n; ++id) if (ord[id] < 0) ord[id] = spill[q++];
-    if (!L->d_order) { HIPCHK(ctx, hipMalloc(&L->d_order, sizeof(int32_t) * kOrderInts)); }
-    HIPCHK(ctx, hipMemcpy(L->d_order, ord.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));      // (synchronous: an experiment's upload)
-    L->order_valid = false;
-    A.order = L->d_order;
-  }
-  else
-#endif
   if (!use_split && !use_pair && !zero_copy && A.cull && ctx->balance && n > 256 && n <= 4096 && has_proj) {
     int bs = -1;
     for (int s = 0; s < ns && bs < 0; ++s) if (A.s[s].finder == LSM2D_FINDER_PROJECTIVE && A.s[s].moving.lane_xy && A.s[s].moving.lane_bounds) bs = s;
@@ -597,7 +509,7 @@ int AlignBatch::make_placement() {
       int32_t* d_work = (int32_t*) ((char*) L->d_scratch + o_work);
       // the workgroups of the previous launch of the same shape noted the CU they ran on (AlignArgs::wg_place): the placement groups by those notes
       // (round 6) packed: one dispatch round of 4 n_cu workgroups, the lightest alignments two to a workgroup (pack_two_for; the pairs are made by balance_order)
-      const bool packed = proj_culled_for_all && !(kExperiments && ctx->two_stage) && pack_two_for(ctx, n, lds);
+      const bool packed = proj_culled_for_all && pack_two_for(ctx, n, lds);
       const unsigned long long shape = ((unsigned long long) (unsigned) n << 32) ^ ((unsigned long long) lds << 8) ^ (unsigned long long) (proj_culled_for_all ? 5 : 0) ^ (packed ? 0x80ull : 0ull);
       if (!ctx->d_wg_place) {      // 1024 notes + the estimate's ticket counter
         HIPCHK(ctx, hipMalloc(&ctx->d_wg_place, sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
@@ -707,7 +619,7 @@ int AlignBatch::launch() {
       // serves every alignment (kNNMode of align_body).  One table (round 5; a 12-way ladder before); the mixed instantiations take whatever is left.
       const unsigned finders = (has_proj ? kFProj : 0u) | (has_nn ? kFNN : 0u) | (has_dist ? kFDist : 0u) | (has_kd ? kFKd : 0u);
       int mode = 0;
-      if (finders == kFProj) mode = proj_culled_for_all ? (A.xcd_sync ? 6 : 5) : 0;                                                    // every slice: the culled stream over kept unit lists
+      if (finders == kFProj) mode = proj_culled_for_all ? 5 : 0;                                                                       // every slice: the culled stream over kept unit lists
       else if (finders == kFNN) mode = A.nn_lds_points == 0 ? 1 : (nn_lds_for_all ? 2 : 0);                        // tables in global memory / in LDS for every alignment
       else if (finders == kFKd && ns == 1 && ctx->kd_modes) mode = A.kd_lds_points > 0 ? 3 : 4;                    // whole trees in LDS / only their tops
       AlignKernel fn = nullptr;
@@ -746,7 +658,6 @@ int AlignBatch::hand_over() {
   P.o_pose = o_pose; P.o_H = o_H; P.o_status = o_status; P.o_its = o_its; P.o_stats = o_stats; P.o_last_pose = o_last_pose; P.o_clock = o_clock;
   P.n = n; P.stats_stride = stats_stride; P.n_clock = n_clock; P.clock_stride = clock_stride;
   P.zero_copy = zero_copy; P.want_stats = out_stats != nullptr; P.want_last_pose = out_last_pose != nullptr; P.stamps = stamps; P.timed = ctx->kernel_timing != 0; P.async = async;
-  P.xcd_sync = A.xcd_sync; P.xcd_stride = A.xcd_stride; P.xcd_window = A.xcd_window; P.xcd_positions = A.xcd_positions;
   if (async) {
     HIPCHK(ctx, hipEventRecord(L->ev_done, ks));      // (zero-copy batches too: what their wait falls back to when the statuses do not arrive within the spin budget)
     L->busy = true; ++ctx->inflight;
@@ -808,20 +719,6 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
   if (out_its) memcpy(out_its, hs + o_its, sizeof(int32_t) * (size_t) n);
   if (out_stats) memcpy(out_stats, hs + o_stats, sizeof(StatsDev) * (size_t) n * (size_t) stats_stride);
   if (out_last_pose) memcpy(out_last_pose, hs + o_last_pose, sizeof(float) * 3 * (size_t) n);
-  if (P.xcd_sync) if (const char* dump = getenv("LSM2D_DUMP_XCD")) {      // diagnostics: the XCD window's counters after the launch, one line per XCC that took part
-    std::vector<uint32_t> h((size_t) 16 * P.xcd_stride);
-    if (hipMemcpy(h.data(), P.xcd_sync, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) if (FILE* f = fopen(dump, "a")) {
-      fprintf(f, "# launch n=%d lockstep=%d passes=%d\n", n, P.xcd_window + 1, P.xcd_positions);
-      for (int x = 0; x < 16; ++x) {
-        const uint32_t* c = h.data() + (size_t) x * P.xcd_stride;
-        if (!c[0]) continue;
-        fprintf(f, "xcc %2d registered %u gone %u watchdog %u (last: need %u saw %u reg %u gone %u at g %u) done:", x, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
-        for (int q = 0; q < P.xcd_positions && q < 48; ++q) fprintf(f, " %u", c[16 + q]);
-        fprintf(f, " ... %u\n", c[16 + P.xcd_positions - 1]);
-      }
-      fclose(f);
-    }
-  }
   if (stamps) {     // median over the stamped workgroups: shader cycles per 10 ns tick of the constant 100 MHz counter
     const unsigned long long* ck = (const unsigned long long*) (hs + o_clock);
     std::vector<double> khz; std::vector<unsigned long long> life;

@@ -373,7 +373,7 @@ static int ensure_lane_layout(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
   // block circles: 57 KB per cloud.  They are what the kept unit lists are built from -- worth it for a map or a few thousand big clouds, not for tens of
   // thousands of scan-sized moving clouds (round-4 advisor: several GB there): beyond 256 MB the set goes without them and its batches run the chunk-level
   // stream of the shared instantiation (proj_culled_for_all needs block_bounds)
-  const int nbs = cull_blocks_for(maxT);      // 7 blocks per chunk, 14 when the set holds a map-sized cloud (lsm2d_kernels.h)
+  const int nbs = kCullBlocks;      // blocks per chunk (lsm2d_kernels.h)
   const bool want_blocks = sizeof(float4) * (size_t) nc * nbs * kAlignBlock <= ((size_t) 256 << 20);
   DevTmp t_xy, t_bounds, t_blocks, t_start, t_T;
   HIPCHK(ctx, hipMalloc(&t_xy.p, sizeof(float4) * (size_t) slots));

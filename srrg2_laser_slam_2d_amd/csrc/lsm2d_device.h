@@ -376,29 +376,6 @@ LSM2D_DEV void project_cloud_units_t(const float4* __restrict__ lane_xy, int T_s
 // off each other's cells, as above) -- and every entry is a unit that survived the BLOCK-level test (a block = B steps = 2 B consecutive map points,
 // ~6 cm of wall on configs[1] and [4] alike), so a chunk that straddles the edge of what the scan saw is streamed in part only.  Thread u takes the
 // entries u, u + nthreads, ...: whole waves run out of work together.
-// Round 5: the XCD lockstep of k_align<1,0,0,0,6> (AlignArgs::xcd_sync in lsm2d_kernels.h) -- how a workgroup LOOKS at its XCD's counters: a SCALAR load with glc
-// (past the scalar cache, served by the L2, where the other CUs' atomic adds are performed; tools/l2_poll_probe.hip: it sees them within a poll, a plain or
-// sc0 vector load -- which is what the compiler makes of an atomic add of zero -- never does).  One request, no lane, no vector register, and a READ.
-LSM2D_DEV unsigned xcd_look(const uint32_t* p) {
-  unsigned v;
-  asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(p) : "memory");
-  return v;
-}
-// wait until every workgroup registered on this XCD has counted itself into done[need] (or has gone).  Called by ONE thread of a workgroup while the others
-// stand at a barrier.  The counters only grow, and the workgroup that is furthest behind waits for nobody, so every wait ends; should that reasoning ever be
-// wrong, ~100 ms end it too (the lockstep changes no result: giving up on it is always safe) -- counted in word 2 of the XCD's counters (LSM2D_DUMP_XCD).
-LSM2D_DEV void xcd_wait(uint32_t* sync, int need, int limit) {
-  if (need < 0 || need >= limit) return;
-  int polls = 0;
-#pragma nounroll
-  for (;;) {
-    const unsigned d = xcd_look(sync + 16 + need), reg = xcd_look(sync), gone = xcd_look(sync + 1);
-    if ((int) (d + gone - reg) >= 0) return;
-    if (polls < 8) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(48);      // ~0.25 us at first, ~1.3 us later: 125 workgroups per XCD, one looking thread each
-    if (++polls > 60000) { __hip_atomic_fetch_add(&sync[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); sync[3] = (unsigned) need; sync[4] = d; sync[5] = reg; sync[6] = gone; return; }
-  }
-}
-
 // (kStride: the threads that share the list -- the workgroup's width; nthreads: the chunks of a row of the lane-chunked copy, 512 whatever the width.  0: the same)
 template <bool kGuarded, int kStride = 0>
 LSM2D_DEV void project_cloud_list_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, u64* canvas, int tid, int nthreads,
@@ -447,61 +424,6 @@ LSM2D_DEV void project_cloud_list(const float4* __restrict__ lane_xy, int T_step
   if (P.tiny_ok) project_cloud_list_t<false, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B);
   else project_cloud_list_t<true, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B);
 }
-
-#ifdef LSM2D_EXPERIMENTS      // ("cull" 2: measured 3 % slower than the block units, DESIGN App. A; compiled into the experiments build only)
-// The same survivors, balanced to within one step: the s surviving chunks x T steps form a matrix (row = step t, column = survivor i);
-// thread u takes the elements u, u + nthreads, ... of its row-major order.  The lanes of a wave then hold consecutive survivors at the SAME
-// step -- their 16-byte loads fall into one row of the copy, and they stay a chunk apart along the map -- and every thread gets
-// floor or ceil of s T / nthreads steps.  One step (two points) per element: the column is advanced incrementally (no division in the
-// loop), the survivor's chunk comes from the LDS list one element ahead, two loads are in flight.
-template <bool kGuarded>
-LSM2D_DEV void project_cloud_rows_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, u64* canvas, int tid, int nthreads,
-                                    const uint16_t* surv, int s) {
-  const Iso T = Tin; ProjK P = Pin;
-  asm volatile("" : "+v"(P.K01));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const unsigned long long pb = reinterpret_cast<unsigned long long>(lane_xy);
-  const unsigned pb_hi = (unsigned) __builtin_amdgcn_readfirstlane((int) (pb >> 32));
-  const unsigned pb_lo = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) pb);
-  float4* ubase = reinterpret_cast<float4*>(((unsigned long long) pb_hi << 32) | (unsigned long long) pb_lo);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ubase, (short) 0, 0x7fffffff, 0x00020000);
-  const int row_bytes = nthreads * (int) sizeof(float4);
-  const int q0 = nthreads / s, d = nthreads - q0 * s;          // one division per call, wave-uniform: an element's successor is q0 rows and d columns on
-  // (t, i): step and column of the NEXT element to be loaded
-  int t = 0, i = tid;
-  if (i >= s) { const int q = i / s; t = q; i -= q * s; }
-  auto advance = [&]() { t += q0; i += d; if (i >= s) { i -= s; ++t; } };
-  auto issue = [&](int g, int tt, float4& buf, int& idx) {
-    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, g * (int) sizeof(float4) + tt * row_bytes, 0, 0);
-    buf = make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
-    idx = 2 * (g * T_steps + tt);
-  };
-  auto pair = [&](const float4& v, int k) {
-    project_point_stream<kGuarded>(T, P, v.x, v.y, k, canvas);
-    project_point_stream<kGuarded>(T, P, v.z, v.w, k + 1, canvas);
-  };
-  float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va; int ia = 0, ib = 0;
-  bool ha = t < T_steps;
-  if (ha) { issue((int) surv[i], t, va, ia); advance(); }
-  bool hb = ha && t < T_steps;
-  if (hb) { issue((int) surv[i], t, vb, ib); advance(); }
-  int g_next = (hb && t < T_steps) ? (int) surv[i] : 0;        // the survivor of the element after those two, fetched ahead of its use
-  while (ha) {
-    pair(va, ia);
-    ha = hb && t < T_steps;
-    if (ha) { issue(g_next, t, va, ia); advance(); g_next = t < T_steps ? (int) surv[i] : 0; }
-    if (!hb) break;
-    pair(vb, ib);
-    hb = ha && t < T_steps;
-    if (hb) { issue(g_next, t, vb, ib); advance(); g_next = t < T_steps ? (int) surv[i] : 0; }
-  }
-}
-LSM2D_DEV void project_cloud_rows(const float4* __restrict__ lane_xy, int T_steps, const Iso& T, const ProjK& P, u64* canvas, int tid, int nthreads,
-                                  const uint16_t* surv, int s) {
-  if (P.tiny_ok) project_cloud_rows_t<false>(lane_xy, T_steps, T, P, canvas, tid, nthreads, surv, s);
-  else project_cloud_rows_t<true>(lane_xy, T_steps, T, P, canvas, tid, nthreads, surv, s);
-}
-#endif
 
 LSM2D_DEV void project_cloud_units(const float4* __restrict__ lane_xy, int T_steps, const Iso& T, const ProjK& P, u64* canvas, int tid, int nthreads,
                                    const uint16_t* surv, int s, int B, int nb) {

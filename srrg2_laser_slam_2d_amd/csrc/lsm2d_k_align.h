@@ -8,21 +8,19 @@
 // lost 17-25 % per alignment).  The z-buffer does not care who streams which point; the bin walk and the sums keep the 512 VIRTUAL threads of the wide kernel --
 // thread t plays virtual threads t, t + kW, ... one after the other, each with its own partial sums, its waves' trees written to the same eight rows of `red` --
 // so every result keeps its bits (tests: 256 against 512).
-template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0, bool kFirstStage = false, bool kSeq = false, int kW = kAlignBlock>
+template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0, bool kSeq = false, int kW = kAlignBlock>
 LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
-  static_assert(kW == kAlignBlock || (kNNMode == 5 && !kFirstStage && !kSeq && kW % 64 == 0 && kW >= 256 && kW < kAlignBlock), "narrow workgroups: the culled projective stream only");
+  static_assert(kW == kAlignBlock || (kNNMode == 5 && !kSeq && kW % 64 == 0 && kW >= 256 && kW < kAlignBlock), "narrow workgroups: the culled projective stream only");
   __builtin_assume(A.n_slices >= 1 && A.n_slices <= kMaxSlices);      // (the host refuses anything else: the slice loops need no guard -- which, as a flag, was kept in a vector register and spilled)
   constexpr bool kNNGlobal = kNNMode == 1, kNNLds = kNNMode == 2;
   // the same for a pure KD-tree batch: 3 = every alignment's whole tree, leaf arrays included, is in LDS (the tracker's wiring: a tree per scan); 4 = only the
   // top of the tree is (the map is the fixed cloud): the other form of the descent and of the leaf scan is compiled out
   constexpr bool kKdAllLds = kNNMode == 3, kKdTop = kNNMode == 4;
   // ... and for a pure projective batch: 5 = every slice streams a lane-chunked moving cloud through the exact culling in units (what a batch against a map
-  // does): the plain lane stream, the row-major variant and the per-pair stream of small clouds are compiled out
-  // 6 = 5 with the XCD window (AlignArgs::xcd_sync: big maps, one dispatch round): an instantiation of its own, so that the headline's loop does not carry the
-  // window's state (in one body: 16 bytes of scratch in the kernel that had none)
-  constexpr bool kProjCulled = kNNMode == 5 || kNNMode == 6, kXcdWindow = kNNMode == 6;
+  // does): the plain lane stream and the per-pair stream of small clouds are compiled out
+  constexpr bool kProjCulled = kNNMode == 5;
   static_assert(kNNMode == 0 || ((kNNMode <= 2) && kHasNN && !kHasProj && !kHasDist && !kHasKd) || ((kNNMode == 3 || kNNMode == 4) && kHasKd && !kHasProj && !kHasDist && !kHasNN) ||
-                ((kNNMode == 5 || kNNMode == 6) && kHasProj && !kHasNN && !kHasDist && !kHasKd), "kNNMode: one finder only");
+                (kNNMode == 5 && kHasProj && !kHasNN && !kHasDist && !kHasKd), "kNNMode: one finder only");
   extern __shared__ __align__(16) unsigned char smem[];
   // (round 4: the fixed winners' payload no longer sits in LDS -- 16 bytes per column, 17 KB at 1081 -- the bin walk gathers it like the moving winner's,
   // one 16-byte row of the cloud's AoS copy each, both in flight together; the room holds the culled stream's unit lists)
@@ -51,7 +49,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ int   s_n_corr, s_active, s_done, s_status, s_last_n_in;
   __shared__ float s_prev_chi;      // total chi^2 of the previous iteration (termination_chi_epsilon)
   __shared__ u64 s_dig;             // this iteration's pair digest (lsm2d_iteration_stats.pair_digest): every matched pair adds its hash; only when statistics go out
-  __shared__ int s_it0;            // the iteration this launch starts at (0, or where the first of two launches stopped)
+  __shared__ int s_it0;            // the iteration this launch starts at (always 0 now; kept so that the kernels' LDS layout and code stay as they were)
   __shared__ int s_phase, s_phase_start, s_phase_end;      // 0: the regular loop, 1: the inlier-only runs (enable_inlier_only_runs); iterations [start, end) belong to the phase
   __shared__ uint16_t s_surv[kAlignBlock];      // culling: the chunks of the moving cloud that survived this iteration's test, compacted in thread order
   __shared__ int s_wcnt[2 * (kAlignBlock / 64)];
@@ -97,13 +95,6 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #define LSM2D_PH_STREAM() do { } while (0)
 #endif
   if (A.wg_place && tid == 0) A.wg_place[blockIdx.x] = place_key();
-  // the XCD lockstep (AlignArgs::xcd_sync): this workgroup's counters are its XCD's; it counts itself in before anything else
-  uint32_t* xsync = nullptr;      // (wave-uniform: SGPRs)
-  if (kXcdWindow && !kFirstStage && A.xcd_sync) {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20) & 15u;      // HW_REG_XCC_ID
-    xsync = A.xcd_sync + (size_t) xcc * A.xcd_stride;
-    if (tid == 0) __hip_atomic_fetch_add(&xsync[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
   const bool stamp = A.clock_out && tid == 0 && a % A.clock_stride == 0;
   if (stamp) { s_clk[0] = __builtin_amdgcn_s_memtime(); s_clk[1] = __builtin_amdgcn_s_memrealtime(); }
   if (A.prior && tid >= 64 && tid < 64 + kPriorWords)
@@ -162,29 +153,19 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     }
     if (A.out_last_pose) { A.out_last_pose[3 * a + 0] = s_pose[0]; A.out_last_pose[3 * a + 1] = s_pose[1]; A.out_last_pose[3 * a + 2] = s_pose[2]; }
   };
-  const bool resumed = kExperiments && kProjCulled && !kFirstStage && A.stage == 2;      // the second of two launches: the alignment goes on where k_first_iteration left it
   if (tid == 0) {
-    if (resumed) {
-      const ResumeDev R = A.resume[a];
-      s_pose[0] = R.pose[0]; s_pose[1] = R.pose[1]; s_pose[2] = R.pose[2];
-      s_done = R.done; s_status = R.status; s_last_n_in = R.last_n_in; s_prev_chi = R.prev_chi;
-      s_phase = R.phase; s_phase_start = R.phase_start; s_phase_end = R.phase_end; s_it0 = R.it;
-      for (int k = 0; k < 9; ++k) s_H[k] = R.H[k];
-    } else {
-      if (A.inline_n1) { s_pose[0] = A.pose1[0]; s_pose[1] = A.pose1[1]; s_pose[2] = A.pose1[2]; }
-      else { s_pose[0] = A.init_pose[3 * a + 0]; s_pose[1] = A.init_pose[3 * a + 1]; s_pose[2] = A.init_pose[3 * a + 2]; }
-      s_done = 0; s_status = LSM2D_RUNNING; s_last_n_in = 0;
-      s_phase = 0; s_phase_start = 0; s_phase_end = A.max_it; s_it0 = 0;
-      for (int k = 0; k < 9; ++k) s_H[k] = 0.0f;
-    }
+    if (A.inline_n1) { s_pose[0] = A.pose1[0]; s_pose[1] = A.pose1[1]; s_pose[2] = A.pose1[2]; }
+    else { s_pose[0] = A.init_pose[3 * a + 0]; s_pose[1] = A.init_pose[3 * a + 1]; s_pose[2] = A.init_pose[3 * a + 2]; }
+    s_done = 0; s_status = LSM2D_RUNNING; s_last_n_in = 0;
+    s_phase = 0; s_phase_start = 0; s_phase_end = A.max_it; s_it0 = 0;
+    for (int k = 0; k < 9; ++k) s_H[k] = 0.0f;
     s_ring_n = 0; s_skip = 0;
     s_ff_rows = A.ff_rows ? A.ff_rows + (size_t) a * (kFfRing * kFfRowWords) : nullptr;
     for (int s = 0; s < kMaxSlices; ++s) { s_list_iso[s].c = 1.0f; s_list_iso[s].s = 0.0f; s_list_iso[s].tx = 0.0f; s_list_iso[s].ty = 0.0f; }
-    if (!s_done) begin_iteration();      // (resumed: the transforms and the zeroed sums the first launch's last begin_iteration() made, made again from the same pose)
+    if (!s_done) begin_iteration();
     for (int s = 0; s < kMaxSlices; ++s) s_rebuild[s] = 1;      // no list yet
   }
   __syncthreads();
-  if (resumed && s_done) return;         // it finished in the first launch: its results are out
   if (kNNGlobal) for (int i = tid; i < A.nn_qcache; i += kAlignBlock) l_qc[8 * i] = 0x7fffffff;      // no cell cached yet (visible after the barriers below)
   bool nn_lds = false;
   if (kHasNN && !kNNGlobal && A.nn_lds_points > 0) {
@@ -296,13 +277,11 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   // the pose it ended on (the start of t + 1, or the pose just solved if t == it) are in the ring, and its H (as solve_update was given it: prior included,
   // damping not, which the solve applies to a copy) and inlier count wait in the alignment's row of A.ff_rows, stored by thread 0 iteration by iteration without
   // waiting and read once here.  The alignment finishes from those, R iterations counted and no iteration run.  Off where an iteration depends on more than the pose:
-  // the chi^2 termination test (s_prev_chi; a fixed point ends itself there one iteration later anyway), the inlier-only runs (s_phase), and where `it`
-  // means more than a count (the first of two launches, a resumed second one, the XCD window's positions); and in a zero-copy launch (host_polls: at most
+  // the chi^2 termination test (s_prev_chi; a fixed point ends itself there one iteration later anyway), the inlier-only runs (s_phase); and in a zero-copy launch (host_polls: at most
   // "zero_copy_max" alignments, results and statistics rows in pinned HOST memory -- a skipped row copied from the row one period back would be a read across
   // the host link on thread 0's serial path; the small calls, most of which the latency kernel and the split path take anyway, are the follow-up: DESIGN section 9)
-  const bool ff_on = A.fast_forward && !(A.term_eps > 0.0f) && !A.inlier_runs && !A.host_polls && !kFirstStage && !kXcdWindow && !resumed;      // (wave-uniform: kernel arguments)
+  const bool ff_on = A.fast_forward && !(A.term_eps > 0.0f) && !A.inlier_runs && !A.host_polls;      // (wave-uniform: kernel arguments)
   for (; it < it_cap; ++it) {
-    const bool lists_only = kFirstStage && it == A.stage_split;      // the first of two launches enters this iteration for the LENGTH of its unit lists alone
     const bool inl_only = A.inlier_runs && __builtin_amdgcn_readfirstlane(s_phase) != 0;
 #if LSM2D_PRIO_BY_PROGRESS == 1
     { const int q = (4 * it) / A.max_it; if (q == 0) __builtin_amdgcn_s_setprio(3); else if (q == 1) __builtin_amdgcn_s_setprio(2); else if (q == 2) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
@@ -367,7 +346,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             const int Tm = S.moving.lane_T[mc];
             const int nbs = __builtin_amdgcn_readfirstlane(S.moving.block_stride);
             const int B = cull_block_steps(Tm, nbs), nb = (Tm + B - 1) / B;
-            if (__builtin_amdgcn_readfirstlane(s_rebuild[s]) || lists_only) {      // (lists_only: the list the second launch will build first, whatever the kept one covers)
+            if (__builtin_amdgcn_readfirstlane(s_rebuild[s])) {
               typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
               const float m_t = A.cull_mt, m_th = A.cull_mth;      // (0 when the lists are not kept: the host sees to that -- a select made here was a vector register held across the iteration)
               const unsigned long long bb = reinterpret_cast<unsigned long long>(S.moving.lane_bounds + (size_t) mc * kAlignBlock);
@@ -424,7 +403,6 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
               if (tid == 0) { s_nunits[s] = n_units; s_list_iso[s] = T; }
               __syncthreads();
             }
-            if (lists_only) continue;
             LSM2D_PH_LISTS();
             const int n_units = __builtin_amdgcn_readfirstlane(s_nunits[s]);
             if (n_units > 0) project_cloud_list<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B);
@@ -453,23 +431,15 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             const int Tm = S.moving.lane_T[mc];
             // blocks of an even number of steps, 7 per chunk (measured on configs[1], T = 98: blocks of 2 / 4 / 6 / 8 / 14 steps 1.098 / 1.017 /
             // 0.991 / 0.983 / 0.969 ms -- what a unit costs to set up outweighs the better balance of smaller ones; element-wise row-major
-            // order, balanced to one step, 1.066: project_cloud_rows, "cull" 2)
-            const int B = (kExperiments && A.cull_block > 0) ? A.cull_block : cull_block_steps(Tm), nb = (Tm + B - 1) / B;
-            if (n_surv > 0) {
-#ifdef LSM2D_EXPERIMENTS
-              if (!kProjCulled && A.cull == 2) project_cloud_rows(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, s_surv, n_surv);
-              else
-#endif
-              project_cloud_units(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, s_surv, n_surv, B, nb);
-            }
+            // order, balanced to one step, 1.066: docs/REJECTED.md)
+            const int B = cull_block_steps(Tm), nb = (Tm + B - 1) / B;
+            if (n_surv > 0) project_cloud_units(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, s_surv, n_surv, B, nb);
           }
           else if (S.moving.lane_xy) project_cloud_lanes(S.moving.lane_xy + S.moving.lane_start[mc], S.moving.lane_T[mc], T, S.proj, mcan, tid, kAlignBlock);
           else project_cloud(S.moving.xy + S.moving.start[mc], S.moving.count[mc], T, S.proj, mcan, tid, kAlignBlock);
         }
         __syncthreads();
         LSM2D_PH_STREAM();
-        if (kXcdWindow && xsync && tid == 0 && it * A.n_slices + s < A.xcd_positions)      // this workgroup's pass (it, s) over the map is behind all its waves
-          __hip_atomic_fetch_add(&xsync[16 + it * A.n_slices + s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         // bin walk (correspondence_finder_projective_2d.cpp:55-74): the fixed side comes from LDS, the two gathers of the
         // moving winner are issued together, and every cell read is reset for the next projection
         const int mbase = S.moving.start[pick_cloud(S.moving, a)], fbase = S.fixed.start[pick_cloud(S.fixed, a)];
@@ -757,21 +727,6 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       // joins once it is done with the partials.  The point-query branches write `red` without such a barrier in between.
       if (kHasNN || kHasDist || kHasKd) __syncthreads();
     }
-    if (lists_only) {      // what the second launch will stream per iteration -> its placement; the state it goes on from
-      if (tid == 0) {
-        ResumeDev R;
-        R.pose[0] = s_pose[0]; R.pose[1] = s_pose[1]; R.pose[2] = s_pose[2];
-        for (int k = 0; k < 9; ++k) R.H[k] = s_H[k];
-        R.prev_chi = s_prev_chi; R.phase = s_phase; R.phase_start = s_phase_start; R.phase_end = s_phase_end;
-        R.last_n_in = s_last_n_in; R.status = s_status; R.done = 0; R.it = it;
-        A.resume[a] = R;
-        int units = 0;
-        for (int s = 0; s < A.n_slices; ++s) units += s_nunits[s];
-        const int w = (units + 7 * A.n_slices - 1) / (7 * A.n_slices);      // <= 512: a slice's list holds at most kCullBlocks x 512 units
-        A.stage_work[a] = w < 1 ? 1 : (w > kAlignBlock ? kAlignBlock : w);
-      }
-      return;
-    }
     if (tid == 0) {
       // (thread 0's serial state lives in LDS, not in registers every thread would carry -- and spill -- across the loops)
       StatsDev last; last.n_corr = s_n_corr; last.n_in = __float_as_int(s_sum[11]); last.n_out = __float_as_int(s_sum[12]); last.chi_in = s_sum[9]; last.chi_out = s_sum[10];
@@ -855,22 +810,18 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       }
       if (ff_on) s_skip = skip;              // every iteration, whichever way it went: nobody adds a stale one
       if (!s_done) begin_iteration();        // next iteration's transforms and zeroed sums, under the same barrier
-      // the XCD lockstep: nobody starts its next pass before everybody on this XCD has finished the pass xcd_window back (the others stand at the barrier below anyway)
-      if (kXcdWindow && xsync && !s_done) xcd_wait(xsync, (it + 1) * A.n_slices - 1 - A.xcd_window * A.n_slices, A.xcd_positions);
     }
     LSM2D_PH(2);
     __syncthreads();
     if (ff_on) it += __builtin_amdgcn_readfirstlane(s_skip);      // (every thread alike: `it` stays a scalar, and the exit below counts the skipped iterations in)
     if (s_done) { ++it; break; }
   }
-  if (kXcdWindow && xsync && tid == 0) __hip_atomic_fetch_add(&xsync[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // gone: nobody waits for this workgroup any more
   if (tid == 0) {
     int st = s_status;
     if (st == LSM2D_RUNNING) st = (A.max_it > 0 && s_last_n_in < A.min_inliers) ? LSM2D_NOT_ENOUGH_INLIERS : LSM2D_SUCCESS;
     A.out_pose[3 * a + 0] = s_pose[0]; A.out_pose[3 * a + 1] = s_pose[1]; A.out_pose[3 * a + 2] = s_pose[2];
     if (A.out_H) for (int k = 0; k < 9; ++k) A.out_H[9 * a + k] = s_H[k];
     if (A.out_its) A.out_its[a] = it;
-    if (kFirstStage) { A.resume[a].done = 1; A.stage_work[a] = 0; }      // finished before the second launch: its workgroup there leaves at once
     // the status goes last, behind a system-scope release: with results written straight to pinned host memory the host polls
     // this word instead of waiting for the stream (lsm2d_align_batch), and whoever sees it sees everything above
     if (stamp) {
@@ -905,7 +856,7 @@ constexpr int align_min_waves() {
 }
 template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0>
 __global__ __launch_bounds__(kAlignBlock, (align_min_waves<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>())) void k_align(const AlignArgs A) {
-  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode, false>(A);
+  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>(A);
 }
 #ifndef LSM2D_SEQ_MIN_WAVES
 #define LSM2D_SEQ_MIN_WAVES 8
@@ -913,44 +864,29 @@ __global__ __launch_bounds__(kAlignBlock, (align_min_waves<kHasProj, kHasNN, kHa
 // The culled projective stream with up to TWO alignments per workgroup, one after the other (AlignArgs::order2): the whole body again, from its prologue -- an
 // instantiation of its own (two copies of the body), so that the headline's kernel does not carry a loop around it (in one kernel: 80 bytes of scratch).
 __global__ __launch_bounds__(kAlignBlock, LSM2D_ALIGN_MIN_WAVES) void k_align_two(const AlignArgs A) {
-  align_body<true, false, false, false, 5, false>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
+  align_body<true, false, false, false, 5>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
   const int a2 = __builtin_amdgcn_readfirstlane(A.order2[blockIdx.x]);
   if (a2 < 0) return;
   __syncthreads();      // (thread 0 is done with the first one's results before anybody overwrites the state they came from)
-  align_body<true, false, false, false, 5, false>(A, a2);
+  align_body<true, false, false, false, 5>(A, a2);
 }
 // ... and the same with the reference's order of summation ("sum_order" 1: no narrow form exists for it, so every batch between one and two rounds is packed)
 __global__ __launch_bounds__(kAlignBlock, LSM2D_SEQ_MIN_WAVES) void k_align_seq_two(const AlignArgs A) {
-  align_body<true, false, false, false, 5, false, true>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
+  align_body<true, false, false, false, 5, true>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
   const int a2 = __builtin_amdgcn_readfirstlane(A.order2[blockIdx.x]);
   if (a2 < 0) return;
   __syncthreads();
-  align_body<true, false, false, false, 5, false, true>(A, a2);
+  align_body<true, false, false, false, 5, true>(A, a2);
 }
 // The culled projective stream in NARROW workgroups (align_body's kW): 256 threads, six workgroups -- 1536 alignments -- resident per round where the wide kernel
 // holds 1024.  The same results as k_align<1,0,0,0,5>, bit for bit; chosen by the host (align_width_for) for batches just above a multiple of 1024 alignments.
 template <int kW>
 __global__ __launch_bounds__(kW, LSM2D_ALIGN_MIN_WAVES) void k_align_narrow(const AlignArgs A) {
-  align_body<true, false, false, false, 5, false, false, kW>(A);
+  align_body<true, false, false, false, 5, false, kW>(A);
 }
 // "sum_order" 1: the same kernel with the reference's order of summation (align_body<.., kSeq = true>).  14 KB of pair records per workgroup beside the canvases (four workgroups per CU still fit the headline's shape):
 // the register budget stays that of 8 waves per SIMD -- 4 for the mixed instantiations, as above
 template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0>
 __global__ __launch_bounds__(kAlignBlock, ((kHasProj && (kHasNN || kHasDist || kHasKd)) ? LSM2D_MIXED_MIN_WAVES : LSM2D_SEQ_MIN_WAVES)) void k_align_seq(const AlignArgs A) {
-  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode, false, true>(A);
+  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode, true>(A);
 }
-// Round 4 (late): TWO launches for a culled batch of about one dispatch round.  The placement of such a batch decides its tail (the launch lasts as long as
-// the CU with the largest sum of work), and what an alignment will stream is known badly at its START pose -- the estimate of k_cull_estimate left a tail of
-// 10 % -- but well after ONE Gauss-Newton iteration, which takes most of the start error out.  So: this kernel runs iteration 0 of every alignment in any
-// order (a twentieth of the work: its own tail does not matter), builds the unit lists of iteration 1 for their length alone, and leaves pose, phase and
-// statistics state in ResumeDev; k_balance_only deals the alignments out by those lengths; k_align runs the other nineteen iterations from the saved state.
-// The same arithmetic on the same values in the same order: every result keeps its bits (the second launch rebuilds its lists; a list is a superset of
-// what can pair, whatever pose within its margins it was built at).  MEASURED AND NOT SHIPPED ("two_stage" 0 by default): the second launch takes 0.698 ms
-// instead of 0.745 -- but a twentieth of that is the iteration it no longer runs, its tail is still 7 % (the length of a list is not the whole of an
-// alignment's cost), and this kernel takes 95 us for its twentieth of the work: all thousand workgroups are in the same phase at the same time, and the
-// phases that wait (prologue, list building, barriers) have no other workgroup's stream to hide under.  0.861 vs 0.836 ms per step.
-#ifdef LSM2D_EXPERIMENTS
-__global__ __launch_bounds__(kAlignBlock, LSM2D_ALIGN_MIN_WAVES) void k_first_iteration(const AlignArgs A) {
-  align_body<true, false, false, false, 5, true>(A);
-}
-#endif

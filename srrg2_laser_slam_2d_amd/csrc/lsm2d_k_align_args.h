@@ -34,10 +34,6 @@ LSM2D_DEV u64 pair_hash_dev(uint32_t slice_salt, uint32_t f, uint32_t m) {
 // one pair into the iteration's digest: a fire-and-forget 64-bit LDS add (order-independent: the sum wraps mod 2^64), no register held across the loops
 LSM2D_DEV void digest_add(u64* s_dig, uint32_t slice_salt, int f, int m) { atomicAdd(reinterpret_cast<unsigned long long*>(s_dig), (unsigned long long) pair_hash_dev(slice_salt, (uint32_t) f, (uint32_t) m)); }
 
-struct ResumeDev {      // what an alignment carries from one iteration to the next (thread 0's serial state in k_align)
-  float pose[3]; float H[9]; float prev_chi;
-  int32_t phase, phase_start, phase_end, last_n_in, status, done, it;
-};
 struct AlignArgs {
   int32_t n_align, n_slices, max_it, min_inliers;
   float   damping;
@@ -52,14 +48,8 @@ struct AlignArgs {
   int32_t kd_lds_points;                    // > 0: ... and, for scan-sized fixed clouds, for this many leaf points (whole trees on chip)
   const int32_t* order;                     // alignment handled by workgroup b (nullptr: b itself) -- the balanced placement of k_balance_order
   float cull_est_mt, cull_est_mth;          // margins of k_cull_estimate's chunk test (metres, radians)
-  // two launches for one batch (k_first_iteration, then k_align: see k_first_iteration): stage 0 the whole alignment in this launch; 1 the iterations before
-  // stage_split, then the next iteration's unit lists for their LENGTH only, the state to `resume`, the length to `stage_work`; 2 the rest, from `resume`
-  int32_t stage, stage_split;
-  struct ResumeDev* resume;                 // [n]
-  int32_t* stage_work;                      // [n] 0 .. 512: the units the alignment will stream per iteration (0: it finished in the first stage)
   float cull_mt2;                           // cull_mt squared (host)
   int32_t* wg_place;                        // [grid] or nullptr: every workgroup notes the CU it ran on (place_key) for the next call's placement
-  int32_t cull_block;                       // steps per unit of the culled stream (0: automatic; tuning knob)
   int32_t cull;                             // 1: projective slices drop the chunks of the moving cloud that cannot yield a pair (chunk_may_matter), results unchanged
   // kProjCulled (round 4): every slice keeps a LIST of the (block, chunk) units that survive the test at block level, in dynamic LDS at units_off
   // (kCullBlocks * kAlignBlock 16-bit entries per slice), built with margins (cull_mt metres, cull_mth radians) and kept while the slice's transform
@@ -67,18 +57,6 @@ struct AlignArgs {
   int32_t units_off, cull_keep;
   int32_t units_stride;                     // entries per slice of the unit lists: the largest block_stride of the batch's moving sets x kAlignBlock
   float   cull_mt, cull_mth;
-  // Round 5, big maps (k_align<1,0,0,0,6>): the workgroups of one XCD walk the map IN STEP, pass by pass.  A 1M-point map's lane copy (8 MB) does not fit an
-  // XCD's 4 MiB L2, and 125 workgroups streaming different parts of it at the same time missed on 44 % of their requests (41 GB of fabric reads per
-  // 1000-alignment launch for 50 MB of data, the chip at 1.83 GHz under that load: profiles/r05/size_sweep_r05a.txt).  All workgroups of a one-round launch start
-  // together and walk their unit lists in the same block-major order -- what pulls them apart is only that their lists differ in length, a quarter of a pass per
-  // iteration.  So every workgroup counts itself into done[g] when ITS pass g = (iteration, slice) is over, and its thread 0 -- at the end of the serial solve,
-  // while the other threads stand at the iteration's closing barrier anyway -- waits until every workgroup registered on ITS XCD has finished the pass that
-  // lies xcd_window passes back (0: the one just finished) or has gone.  One atomic add and a handful of scalar looks per workgroup and iteration; the counters
-  // of an XCD are touched by that XCD only (plain L2 atomics, no fabric traffic, no fence).  Nothing but the ORDER IN TIME of the z-buffer updates changes:
-  // every result keeps its bits.  xcd_sync == nullptr: free-running (the host offers the lockstep only to launches of one dispatch round, whose workgroups
-  // are all resident from the start).  What was tried before this form -- per wave and per BLOCK of the map -- and what it cost: DESIGN App. A.
-  uint32_t* xcd_sync;                       // [16 XCC ids][xcd_stride]: word 0 workgroups registered, word 1 workgroups gone, words 2..6 the watchdog's notes, word 16 + g: workgroups that have finished pass g
-  int32_t xcd_stride, xcd_window, xcd_positions;
   int32_t pq_cull_off;                      // > 0: byte offset in dynamic LDS of the point-query finders' culling state (occupancy bitmap of the fixed cloud, then
   int32_t pq_keep_words;                    //   pq_keep_words 64-bit words of per-tile keep bits); single-slice NN / KD-tree batches with scan-sized fixed clouds
   int32_t pair_mov_cap;                     // latency kernel: moving points per slice it may keep in LDS (kPairMovCap, or 0: no room)
@@ -102,7 +80,7 @@ struct AlignArgs {
   // "fast_forward" (align_body): an iteration is a pure function of the pose it starts at, so once the pose after an iteration equals, bit for bit, the
   // start pose of one of the last kFfRing iterations, the rest of the phase is that cycle again and again.  1: whole periods of it are skipped and the
   // remainder runs; 2: the alignment finishes at once, from what the twin of its last iteration left -- poses in the ring (LDS), H and inlier count in ff_rows;
-  // results unchanged (0: every iteration runs; A/B switch.  Ignored with term_eps > 0, inlier_runs, host_polls, the two-launch form and the XCD window)
+  // results unchanged (0: every iteration runs; A/B switch.  Ignored with term_eps > 0, inlier_runs and host_polls)
   uint32_t* ff_rows;                        // [n_align][kFfRing][kFfRowWords] device scratch, written and read by the alignment's thread 0 only; nullptr unless fast_forward == 2
   int32_t fast_forward;
   SliceDev s[kMaxSlices];

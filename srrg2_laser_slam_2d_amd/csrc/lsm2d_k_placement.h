@@ -214,10 +214,3 @@ __global__ __launch_bounds__(kAlignBlock) void k_cull_estimate(const AlignArgs A
   balance_order(*reinterpret_cast<BalanceLds*>(smem), work, (int) gridDim.x, n_cu, 4, order, place, tid, kAlignBlock, order2);
   if (tid == 0) __hip_atomic_store(done_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next call
 }
-
-#ifdef LSM2D_EXPERIMENTS
-__global__ __launch_bounds__(kAlignBlock) void k_balance_only(const int32_t* __restrict__ work, int n, int n_cu, int32_t* __restrict__ order, const int32_t* __restrict__ place) {
-  extern __shared__ __align__(16) unsigned char smem[];      // BalanceLds
-  balance_order(*reinterpret_cast<BalanceLds*>(smem), work, n, n_cu, 4, order, place, threadIdx.x, kAlignBlock);
-}
-#endif

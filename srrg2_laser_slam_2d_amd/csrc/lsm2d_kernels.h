@@ -28,21 +28,10 @@ namespace lsm2d {
 static constexpr int kMaxSlices = 4;
 static constexpr int kFfRing = 16;     // align_body's fast-forward: iteration-start poses remembered = the longest period it finds (a power of two)
 static constexpr int kFfRowWords = 10; // ... and per remembered iteration, for "fast_forward" 2, in device memory (AlignArgs::ff_rows): H's nine words and the inlier count
-// Measured-and-rejected experiments (DESIGN App. A) are compiled only into a -DLSM2D_EXPERIMENTS build of the library (round 5): the second launch form of
-// a culled batch (k_first_iteration / k_balance_only), the row-major culled stream ("cull" 2), the round-3 stream's block-length knob ("cull_block") and the
-// A/B option keys of lsm2d_capi.hip.  The shipped library carries none of them; their bit-identity tests run against the experiments build only.
-#ifdef LSM2D_EXPERIMENTS
-static constexpr bool kExperiments = true;
-#else
-static constexpr bool kExperiments = false;
-#endif
+// (A -DLSM2D_EXPERIMENTS build of the library differs on the host side only: lsm2d_capi.hip's A/B option keys, switches for alternatives that are always on in the
+// product.  Its kernels are the shipped ones; the code of the measured-and-rejected launch forms is gone from the tree: docs/REJECTED.md.)
 // exact culling of a projective slice's moving cloud (k_align): a thread's chunk of T steps is cut into at most kCullBlocks blocks of B steps
 static constexpr int kCullBlocks = 7;
-// Round 5 (experiments build only; measured, no gain: DESIGN App. A): a MAP-SIZED chunk (T >= kCullBigT steps: a cloud of half a million points and more) cut
-// into 14 blocks instead of 7 -- the same point visits on configs[4] to four digits, 14 KB more LDS.  Which count a SET uses (CloudDev::block_stride, the
-// stride of its block_bounds) is decided once, by its largest cloud; every cloud of the set is cut into that many.  The shipped library: 7 everywhere.
-static constexpr int kCullBlocksMax = 14, kCullBigT = 512;
-LSM2D_HD int cull_blocks_for(int maxT) { return (kExperiments && maxT >= kCullBigT) ? kCullBlocksMax : kCullBlocks; }
 LSM2D_HD int cull_block_steps(int T, int nbs = kCullBlocks) { return 2 * ((T + 2 * nbs - 1) / (2 * nbs)); }      // even; ceil(T / B) <= nbs for every T >= 1
 // Wave priority by progress.  The SIMD arbitrates by priority, then AGE: with equal priorities the oldest two waves of a SIMD run
 // at full single-wave speed and the younger workgroups of a CU wait (tools/occupancy_probe.py: lifetimes 0.97 .. 2.19 ms in one

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import fuzz_cases
-from conftest import golden_path, has_experiments, need_experiments, xset
+from conftest import golden_path
 from gpu_helpers import (_same_correspondence_sets, _assert_bitwise_equal_to_device_order_oracle, _pose_diff, _Envelope, _projector, _aligner, _nn_aligner, _ranges_in_pose_out_step, _kd_finder, _kd_aligner, _neg_eps, _oracle_slice, POSE_TOL_M, POSE_TOL_RAD)
 from srrg2_laser_slam_2d_amd import api, synth
 
@@ -250,26 +250,6 @@ def test_configs4_full_size_properties_1000_scans_vs_1m_map(ctx, po):
     finally:
         ctx.set_option("cull", 1)
     assert np.array_equal(plain.pose, res.pose) and np.array_equal(plain.information, res.information) and np.array_equal(plain.iterations, res.iterations)
-    # round 5 (experiments build; measured and not shipped, DESIGN App. A): the XCD lockstep -- the workgroups of an XCD walk the map in step, pass by pass
-    # ("xcd_lockstep" k: nobody starts a pass before everybody on its XCD has finished the pass k - 1 back) -- changes WHEN a map point is visited, never a result:
-    # with a termination criterion that ends alignments at different iterations (workgroups that go early) and with start poses that fail at once (workgroups
-    # that are gone before the others have started)
-    if has_experiments(ctx):
-        al_eps = _aligner(ctx); al_eps.param_termination_chi_epsilon = 1e-3
-        x_bad = wl.x0.copy(); x_bad[::9, 0] += 400.0
-        for al_w, x0_w in ((al, wl.x0), (al_eps, wl.x0), (al, x_bad)):
-            got = {}
-            for w in (0, 1, 3):
-                try:
-                    xset(ctx, xcd_lockstep=w)
-                    got[w] = al_w.compute_batch([fixed], [moving], x0_w, want_stats=True)
-                    assert ctx.get_option("last_xcd_lockstep") == w
-                finally:
-                    xset(ctx, xcd_lockstep=0)
-            for w in (1, 3):
-                assert np.array_equal(got[w].pose, got[0].pose) and np.array_equal(got[w].information, got[0].information) and np.array_equal(got[w].status, got[0].status), w
-                assert np.array_equal(got[w].iterations, got[0].iterations) and np.array_equal(got[w].stats, got[0].stats), w
-        assert (got[0].status[::9] != 0).all() and (got[0].status == 0).sum() > 800
     for i in (0, 499, 999):
         sc = wl.scan_points[wl.scan_offsets[i]:wl.scan_offsets[i + 1]]
         rt = po.align(po.aligner_params(20, device_order=True), [po.slice_params()], [sc], [wl.map_points], wl.x0[i])

@@ -18,7 +18,6 @@ import numpy as np
 import pytest
 
 import mixed_batches as mb
-from conftest import need_experiments
 from gpu_helpers import POSE_TOL_M, POSE_TOL_RAD, _Envelope, _assert_bitwise_equal_to_device_order_oracle, _oracle_slice, _pose_diff, _same_correspondence_sets
 from srrg2_laser_slam_2d_amd import _capi, api, synth
 from mixed_batches import MIN_DIFFERENT as MIXED_MIN_DIFFERENT, WALL_OFFSET_START, WALL_OFFSET_TOL, WALL_ROWS, wall_cloud
@@ -351,22 +350,6 @@ def test_forms_that_only_carry_state(ctx, po):
     assert k == 114 and d >= MIXED_MIN_DIFFERENT, (d, k)
     print("damping and prior, state-carrying forms: prepared x 3, begin / wait, pairs (S3, full prior matrices, last_align_path %d), lsm2d_sweep_align (S1, against last_align_path %d) "
           "with damping 50: the automatic call's bits; %d alignments of it equal the oracle bit for bit" % (path, path1, checked))
-
-
-def test_two_launches_for_one_batch(ctx, po):
-    """"two_stage" 1 (the experiments build): k_first_iteration's solve, then the remaining iterations from the state carried in memory -- n = 300, S1, damping 50.
-    The library takes the two launches for a culled, balanced, purely projective batch of 257 .. 1024 alignments with at least four iterations that goes through the
-    ordinary transfers (a batch above 256 with an index array does); no option reports that it did: a kernel trace of this test shows k_first_iteration's dispatches."""
-    need_experiments(ctx)
-    spec = _spec(300, "S1", DAMPING, False)
-    ref, _, _ = _run(ctx, spec)
-    r, path, _ = _run(ctx, spec, two_stage=1)
-    assert path == 1
-    _assert_same_bits(r, ref, spec["kinds"], "two_stage 1")
-    checked = _assert_oracle_bits(po, r, spec, 0, "two_stage 1")
-    d, k = _count_different(r, _run(ctx, _spec(300, "S1", 0.0, False), two_stage=1)[0], spec)
-    assert k == 114 and d >= MIXED_MIN_DIFFERENT, (d, k)
-    print("damping and prior, two_stage 1, n 300: last_align_path 1; %d alignments equal the oracle bit for bit" % checked)
 
 
 def test_against_the_fp64_oracle(ctx, po):

@@ -67,9 +67,9 @@ print("  correlation of a CU's end time with its sum of true units: %.3f; with i
 
 # is what is left a property of the PLACE?  residual of "end = const + slope x units" per XCD and per shader engine
 X = np.stack([S_units, np.ones(len(cus))], 1); coef, *_ = np.linalg.lstsq(X, T, rcond=None); resid = T - X @ coef
-xcd_of = cus >> 16; se_of = (cus >> 8) & 7
+xcc_of = cus >> 16; se_of = (cus >> 8) & 7
 print("  residual of the units model, balanced launch: rms %.2f %%, max %.2f %%" % (100 * resid.std() / T.mean(), 100 * np.abs(resid).max() / T.mean()))
-print("  per XCD  : mean end time " + " ".join("%d:%.0f" % (x, T[xcd_of == x].mean()) for x in np.unique(xcd_of)) + " | mean residual " + " ".join("%+.1f" % resid[xcd_of == x].mean() for x in np.unique(xcd_of)))
+print("  per XCD  : mean end time " + " ".join("%d:%.0f" % (x, T[xcc_of == x].mean()) for x in np.unique(xcc_of)) + " | mean residual " + " ".join("%+.1f" % resid[xcc_of == x].mean() for x in np.unique(xcc_of)))
 print("  per SE   : mean residual " + " ".join("%d:%+.1f" % (x, resid[se_of == x].mean()) for x in np.unique(se_of)))
 worst = np.argsort(-T)[:8]
-print("  the eight CUs that end last: " + ", ".join("xcd %d se %d cu %d: %.0f us, units %+.1f %% of mean, %d wgs" % (xcd_of[i], se_of[i], cus[i] & 255, T[i], 100 * (S_units[i] / S_units[n_on == 4].mean() - 1), n_on[i]) for i in worst))
+print("  the eight CUs that end last: " + ", ".join("xcd %d se %d cu %d: %.0f us, units %+.1f %% of mean, %d wgs" % (xcc_of[i], se_of[i], cus[i] & 255, T[i], 100 * (S_units[i] / S_units[n_on == 4].mean() - 1), n_on[i]) for i in worst))
