@@ -810,6 +810,27 @@ LSM2D_DEV bool solve_update(const float H[9], const float b[3], float damping, f
   return true;
 }
 
+// solve_update's LDL^T without early exits: the same operations on the same values whenever it succeeds; a failed pivot or a
+// non-finite step is reported at the end (what was computed behind it is discarded by the caller, as solve_update's return does)
+LSM2D_DEV bool solve_flat(float h00, float h01, float h02, float h11, float h12, float h22, float b0, float b1, float b2, float damping,
+                          float& dx, float& dy, float& dth) {
+  const double a00 = (double) h00 + (double) damping, a01 = h01, a02 = h02;
+  const double a11 = (double) h11 + (double) damping, a12 = h12, a22 = (double) h22 + (double) damping;
+  const double r0 = -(double) b0, r1 = -(double) b1, r2 = -(double) b2;
+  const double d0 = a00;
+  const double l10 = a01 / d0, l20 = a02 / d0;
+  const double d1 = a11 - l10 * a01;
+  const double l21 = (a12 - l20 * a01) / d1;
+  const double d2 = a22 - l20 * a02 - l21 * l21 * d1;
+  const double y0 = r0, y1 = r1 - l10 * y0, y2 = r2 - l20 * y0 - l21 * y1;
+  const double z2 = y2 / d2;
+  const double z1 = y1 / d1 - l21 * z2;
+  const double z0 = y0 / d0 - l10 * z1 - l20 * z2;
+  dx = (float) z0; dy = (float) z1; dth = (float) z2;
+  return (d0 > 0) & (d1 > 0) & (d2 > 0) & (bool) __builtin_isfinite(d0) & (bool) __builtin_isfinite(d1) & (bool) __builtin_isfinite(d2) &
+         (bool) __builtin_isfinite(z0) & (bool) __builtin_isfinite(z1) & (bool) __builtin_isfinite(z2);
+}
+
 // v2t(a) * v2t(b) -> t2v, with cos/sin of a given (host- or device-computed)
 LSM2D_DEV void compose(float ca, float sa, const float a[3], const float b[3], float out[3]) {
   out[0] = __builtin_fmaf(ca, b[0], __builtin_fmaf(-sa, b[1], a[0]));

@@ -1,4 +1,4 @@
-// lsm2d_k_align.h -- k_align: one workgroup owns one alignment for all its iterations -- the moving cloud streamed through the LDS z-buffer, the bin walk, the point-query passes, the reduction, the 3x3 solve (MultiAligner2D::compute; registration/correspondence_finder_projective_2d.cpp:35-74; octave/solver/nicp_post.m:69-97); k_align_seq: the same with the reference's order of summation.
+// lsm2d_k_align.h -- k_align: one workgroup owns one alignment for all its iterations -- the moving cloud streamed through the LDS z-buffer, the bin walk, the point-query passes, the reduction, the 3x3 solve as a vector over wave 0 (MultiAligner2D::compute; registration/correspondence_finder_projective_2d.cpp:35-74; octave/solver/nicp_post.m:69-97); k_align_seq: the same with the reference's order of summation.
 // Part of lsm2d_kernels.h (included there, inside namespace lsm2d, in this order); not a translation unit of its own.
 // kSeq: "sum_order" 1 -- H, b and the chi^2 statistics are added pair after pair in the reference's order (lsm2d_device.h: pair_terms / seq_walk) instead of
 // in trees; instantiations of their own (k_align_seq), so the default kernels do not carry the records' code
@@ -41,12 +41,13 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   float2* l_knr = l_kxy + A.kd_lds_points + (A.kd_lds_points & 1);
   __shared__ float s_pose[3];
   __shared__ Iso   s_iso[kMaxSlices];
-  // s_H: information matrix (H of the last solved iteration, built and solved IN LDS: thread 0's serial code has 64 registers like
-  // everybody else, and what it kept in private arrays went to scratch -- eleven dependent round trips to memory per iteration);
-  // s_sum: this iteration's sums in the order of Accum (h00 h01 h02 h11 h12 h22 b0 b1 b2 chi_in chi_out | n_in n_out as integers),
-  // each added by the lane of wave 0 that gathered it
-  __shared__ float s_H[9], s_rhs[3], s_sum[kAccumWords + 2];
-  __shared__ int   s_n_corr, s_active, s_done, s_status, s_last_n_in;
+  // s_H: information matrix (H of the last solved iteration, prior included), stored by the nine lanes of wave 0 that hold its entries;
+  // s_sum: this iteration's sums in the order of Accum (h00 h01 h02 h11 h12 h22 b0 b1 b2 chi_in chi_out | n_in n_out as integers), then the pairs of
+  // all slices and the number of active slices (integers: kSumPairs, kSumActive), each added by the lane of wave 0 that gathered it
+  __shared__ float s_H[9], s_sum[kAccumWords + 2];
+  constexpr int kSumPairs = 13, kSumActive = 14, kSumWords = 15;
+  static_assert(kSumWords <= kAccumWords + 2 && kAccumWords + 2 == 16, "s_sum: one word per lane of a row of sixteen");
+  __shared__ int   s_done, s_status, s_last_n_in;
   __shared__ float s_prev_chi;      // total chi^2 of the previous iteration (termination_chi_epsilon)
   __shared__ u64 s_dig;             // this iteration's pair digest (lsm2d_iteration_stats.pair_digest): every matched pair adds its hash; only when statistics go out
   __shared__ int s_it0;            // the iteration this launch starts at (always 0 now; kept so that the kernels' LDS layout and code stay as they were)
@@ -58,12 +59,12 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   uint16_t* l_units = reinterpret_cast<uint16_t*>(smem + A.units_off);      // [n_slices][kCullBlocks * kAlignBlock]
   float* l_rec = reinterpret_cast<float*>(smem + (kSeq ? A.seq_off : 0));   // kSeq: [kSeqHalf][kSeqFields]: half a trip's pair records
   // "fast_forward" (AlignArgs::fast_forward): the poses the last kFfRing iterations STARTED at, as bit patterns, in a ring (slot = pushes & (kFfRing - 1)); how
-  // many were pushed; the iterations thread 0 found it may skip behind the current one (0: none), read by everybody after the iteration's closing barrier.  In
-  // LDS like the rest of thread 0's serial state: no register held across the loops.  (What else "fast_forward" 2 keeps of those iterations -- H and the
+  // many were pushed; the iterations wave 0 found it may skip behind the current one (0: none), read by everybody after the iteration's closing barrier.  In
+  // LDS like the rest of wave 0's serial state: no register held across the loops.  (What else "fast_forward" 2 keeps of those iterations -- H and the
   // inlier count -- lies in device memory: AlignArgs::ff_rows)
   __shared__ uint32_t s_ring[3 * kFfRing];
   __shared__ int s_ring_n, s_skip;
-  __shared__ uint32_t* s_ff_rows;      // this alignment's row of A.ff_rows, or nullptr ("fast_forward" 2 only: the host hands the rows over for that value alone).  Thread 0 reads it back where it needs it: as a kernel argument and a product with `a` it was four scalar registers held across the loops -- in the narrow kernel, spills
+  __shared__ uint32_t* s_ff_rows;      // this alignment's row of A.ff_rows, or nullptr ("fast_forward" 2 only: the host hands the rows over for that value alone).  Wave 0 reads it back with the rest of its state: as a kernel argument and a product with `a` it was four scalar registers held across the loops -- in the narrow kernel, spills
   __shared__ PriorDev s_prior;      // read once: with zero-copy arguments A.prior is host memory, a PCIe round trip per access
 
   // (the alignment's index is wave-uniform: said so, or everything indexed by it would live in vector registers)
@@ -75,7 +76,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ unsigned long long s_ph[4];
   if (tid == 0) { s_ph[0] = s_ph[1] = s_ph[2] = 0; s_ph[3] = __builtin_amdgcn_s_memtime(); }
 #define LSM2D_PH_STAMP(k) do { if (tid == 0) { const unsigned long long now__ = __builtin_amdgcn_s_memtime(); s_ph[k] += now__ - s_ph[3]; s_ph[3] = now__; } } while (0)
-  // -DLSM2D_PHASE_PROBE=1 (or empty): the three buckets above.  =2: unit lists + stream | bin walk + reduction | solve + the rest.  =3: unit lists | stream | everything else.
+  // -DLSM2D_PHASE_PROBE=1 (or empty): the three buckets above.  =2: unit lists + stream | bin walk + reduction | solve + the rest.  =3: unit lists | stream | everything else.  =4: bin walk + wave sums | everything else | wave 0's stretch (a single slice).
 #if LSM2D_PHASE_PROBE + 0 == 2
 #define LSM2D_PH(k) LSM2D_PH_STAMP((k) == 0 ? 1 : (k))
 #define LSM2D_PH_LISTS() do { } while (0)
@@ -84,6 +85,12 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #define LSM2D_PH(k) LSM2D_PH_STAMP(2)
 #define LSM2D_PH_LISTS() LSM2D_PH_STAMP(0)
 #define LSM2D_PH_STREAM() LSM2D_PH_STAMP(1)
+#elif LSM2D_PHASE_PROBE + 0 == 4      // bin walk + wave sums | everything else | wave 0's stretch behind the sums' barrier, up to the iteration's closing barrier
+#define LSM2D_PH(k) do { } while (0)
+#define LSM2D_PH_LISTS() do { } while (0)
+#define LSM2D_PH_STREAM() LSM2D_PH_STAMP(1)
+#define LSM2D_PH_SUMS() LSM2D_PH_STAMP(0)
+#define LSM2D_PH_TAIL() LSM2D_PH_STAMP(2)
 #else
 #define LSM2D_PH(k) LSM2D_PH_STAMP(k)
 #define LSM2D_PH_LISTS() do { } while (0)
@@ -93,6 +100,10 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #define LSM2D_PH(k) do { } while (0)
 #define LSM2D_PH_LISTS() do { } while (0)
 #define LSM2D_PH_STREAM() do { } while (0)
+#endif
+#ifndef LSM2D_PH_SUMS
+#define LSM2D_PH_SUMS() do { } while (0)
+#define LSM2D_PH_TAIL() do { } while (0)
 #endif
   if (A.wg_place && tid == 0) A.wg_place[blockIdx.x] = place_key();
   const bool stamp = A.clock_out && tid == 0 && a % A.clock_stride == 0;
@@ -127,7 +138,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   for (int i = tid; i < A.fcan_total; i += kW) fcan[i] = kEmptyCell;
   for (int i = tid; i < A.cols_max; i += kW) mcan[i] = kEmptyCell;      // afterwards the bin walk resets what it reads
   // per-iteration set-up by lane 0: X_eff = S^-1 X per slice (AlignerSliceProcessorLaser2DWithSensor), cos/sin once per
-  // slice, zeroed sums.  Done here for iteration 0 and at the end of every solve for the next one (no extra barrier).
+  // slice, zeroed sums.  Done here for iteration 0; at the end of every solve wave 0 does the same for the next one, a slice per lane (no extra barrier).
   auto begin_iteration = [&]() {
     for (int s = 0; s < A.n_slices; ++s) {
       float Xe[3] = {s_pose[0], s_pose[1], s_pose[2]};
@@ -139,8 +150,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     float zf = 0.0f; int zi = 0;
     asm volatile("" : "+v"(zf), "+v"(zi));
     for (int k = 0; k < 11; ++k) s_sum[k] = zf;
-    s_sum[11] = s_sum[12] = __int_as_float(zi);
-    s_n_corr = s_active = zi;
+    for (int k = 11; k < kSumWords; ++k) s_sum[k] = __int_as_float(zi);
     s_dig = (u64) (unsigned) zi;
     if (kProjCulled) for (int s = 0; s < A.n_slices; ++s) {
       // has the slice's transform left the neighbourhood its unit list serves?  Seen from the sensor the change is a rotation by dth about the origin
@@ -275,7 +285,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   // out_last_pose and the status exactly what the full run would have left; the R mod p others run ("fast_forward" 1).  They need not either ("fast_forward"
   // 2): the LAST iteration, it + R, is the twin of iteration t = s + ((R - 1) mod p), s = it - p + 1 <= t <= it, which has been executed -- its start pose and
   // the pose it ended on (the start of t + 1, or the pose just solved if t == it) are in the ring, and its H (as solve_update was given it: prior included,
-  // damping not, which the solve applies to a copy) and inlier count wait in the alignment's row of A.ff_rows, stored by thread 0 iteration by iteration without
+  // damping not, which the solve applies to a copy) and inlier count wait in the alignment's row of A.ff_rows, stored by wave 0 iteration by iteration without
   // waiting and read once here.  The alignment finishes from those, R iterations counted and no iteration run.  Off where an iteration depends on more than the pose:
   // the chi^2 termination test (s_prev_chi; a fixed point ends itself there one iteration later anyway), the inlier-only runs (s_phase); and in a zero-copy launch (host_polls: at most
   // "zero_copy_max" alignments, results and statistics rows in pinned HOST memory -- a skipped row copied from the row one period back would be a read across
@@ -314,7 +324,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
         if (tid < ((n + 7) & ~7) - n) { float z[kSeqFields]; seq_zero(z); seq_store(l_rec, n + tid, z); }
         __syncthreads();
         // (LSM2D_SEQ_WALK_PRIO: the walking wave ahead of the other workgroups' streams on its SIMD -- its workgroup's other seven waves wait for it, and for the
-        // solve, which is thread 0's: the wave keeps the priority until the next iteration sets the one its progress earns)
+        // solve, which is wave 0's: the wave keeps the priority until the next iteration sets the one its progress earns)
         if (tid < 64) seq_acc = seq_walk<LSM2D_SEQ_WALK_PRIO != 0>(l_rec, n, tid, seq_acc);
         __syncthreads();
       };
@@ -708,18 +718,27 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       if constexpr (kW == kAlignBlock)      // (the narrow workgroups' virtual waves have written their rows in the walk)
       block_reduce_store(acc, red, tid, (kHasProj && !kHasNN && !kHasDist && !kHasKd) ? 32 - __builtin_clz(((S.proj.cols + kAlignBlock - 1) / kAlignBlock) | 1) : 0);
       __syncthreads();
+      LSM2D_PH_SUMS();
       if (tid < 64) {
-        // lanes 0..13 of wave 0 each add one quantity over the waves (wave order) and then into the iteration's sum themselves
-        float v; int vi; block_reduce_gather_lane(red, kAlignBlock / 64, tid, v, vi);
-        if constexpr (kSeq) v = seq_total(seq_acc, tid);      // (the partial sums' floats were never touched: the eleven quantities are the walker's)
-        const int n_corr = __builtin_amdgcn_readlane(vi, 13);
-        if (tid == 0) s_n_corr += n_corr;
-        if (n_corr > S.min_corr) {     // slices with #pairs <= min_num_correspondences are skipped
-          int ts = tid; asm volatile("" : "+v"(ts));      // (s_sum's address for this lane made here: hoisted, it was spilled across the iteration)
-          if (tid < 11) s_sum[ts] += v;
-          else if (tid < 13) s_sum[ts] = __int_as_float(__float_as_int(s_sum[ts]) + vi);
-          if (tid == 0) ++s_active;
+        // lanes 0..13 of wave 0 each add one quantity over the waves and then into the iteration's sum themselves; lane 13 the pairs, lane 14 counts the active slices
+        int ln = tid; asm volatile("" : "+v"(ln));      // (s_sum's and red's addresses for this lane made here: hoisted, they were spilled across the iteration)
+        const float cur = s_sum[ln & 15];
+        // (wave order, from +0: block_reduce_gather's sums; float and integer sum of the same words, each lane uses its own kind)
+        float v = 0.0f; int vi = 0;
+        {
+          const float* rr = red + (ln < kAccumWords ? ln : 0);
+          float g[kAlignBlock / 64];
+#pragma unroll
+          for (int w = 0; w < kAlignBlock / 64; ++w) g[w] = rr[w * kAccumWords];
+#pragma unroll
+          for (int w = 0; w < kAlignBlock / 64; ++w) { v += g[w]; vi += __float_as_int(g[w]); }
         }
+        if constexpr (kSeq) v = seq_total(seq_acc, tid);      // (the partial sums' floats were never touched: the eleven quantities are the walker's)
+        const int n_corr_s = __builtin_amdgcn_readlane(vi, 13);
+        const bool act = n_corr_s > S.min_corr;     // slices with #pairs <= min_num_correspondences are skipped (their pairs still count)
+        float tot = cur;
+        if (act || ln == kSumPairs) tot = ln < 11 ? cur + v : __int_as_float(__float_as_int(cur) + (ln == kSumPairs ? n_corr_s : (ln == kSumActive ? 1 : vi)));
+        if (ln < kSumWords) s_sum[ln] = tot;
       }
       LSM2D_PH(1);
       // pure projective kernels need no barrier here: the other waves go on to the next slice's projection (the cells it
@@ -727,91 +746,163 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       // joins once it is done with the partials.  The point-query branches write `red` without such a barrier in between.
       if (kHasNN || kHasDist || kHasKd) __syncthreads();
     }
-    if (tid == 0) {
-      // (thread 0's serial state lives in LDS, not in registers every thread would carry -- and spill -- across the loops)
-      StatsDev last; last.n_corr = s_n_corr; last.n_in = __float_as_int(s_sum[11]); last.n_out = __float_as_int(s_sum[12]); last.chi_in = s_sum[9]; last.chi_out = s_sum[10];
-      s_last_n_in = last.n_in;
+    if (tid < 64) {
+      // Wave 0's stretch, as a VECTOR over the wave: behind the fast-forward the launch waits for a few lone workgroups, and nobody issues under this stretch.
+      // The operations on every value and their order are block_reduce_gather's, solve_update's, add_prior's, begin_iteration's and the ring rule's; what
+      // changed is who holds what.  Lane q < 15 owns word q of s_sum; lanes 32..40 the nine entries of the information matrix, lane 41 the inlier count beside
+      // them; decisions are taken by every lane alike from v_readlane broadcasts.  The serial state still lives in LDS from one iteration to the next --
+      // no register is held across the loops for it -- and EVERYTHING the stretch reads there is asked for here, at once: one round trip instead of one per value.
+      // (the lane made HERE: every per-lane address and constant below derives from it -- hoisted in front of the loops they would be registers all threads keep)
+      int ln = tid; asm volatile("" : "+v"(ln));
+      const int l16 = ln & (kFfRing - 1);
+      static_assert(kFfRing == 16 && kMaxSlices == 4, "lane masks below");
+      const float p0 = s_pose[0], p1 = s_pose[1], p2 = s_pose[2];
+      const int n = s_ring_n, phase_end = s_phase_end;
+      uint32_t* const ffw = s_ff_rows;
+      const Iso iso0 = s_iso[0], Ll = s_list_iso[ln & 3];
+      const uint32_t e0 = s_ring[3 * l16], e1 = s_ring[3 * l16 + 1], e2 = s_ring[3 * l16 + 2];      // lane j < 16: slot j of the ring
+      const float tot = s_sum[l16];      // lane q < 15: word q of the sums
+#define LSM2D_RL_F(x, k) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k))
+      const int hk = ln - 32;
+      const bool h_lane = (unsigned) hk < 9u;
+      const int n_corr = __builtin_amdgcn_readlane(__float_as_int(tot), kSumPairs), active = __builtin_amdgcn_readlane(__float_as_int(tot), kSumActive);
+      const int n_in = __builtin_amdgcn_readlane(__float_as_int(tot), 11);
+      const float chi_in = LSM2D_RL_F(tot, 9), chi_out = LSM2D_RL_F(tot, 10);
+      if (ln == 0) s_last_n_in = n_in;
       int skip = 0;      // fast-forward: iterations to jump over behind this one
+      if (A.out_stats) {      // the statistics row: one word per lane
+        static_assert(sizeof(StatsDev) == 28, "seven words: n_corr n_in n_out chi_in chi_out dig_lo dig_hi");
+        int n_out = __builtin_amdgcn_readlane(__float_as_int(tot), 12); float chi_o = chi_out;
 #ifdef LSM2D_DEBUG_UNITS      // diagnostics build: the culled stream's list length and whether it was rebuilt, in place of the outlier statistics
-      if (kProjCulled) { last.n_out = s_nunits[0]; last.chi_out = (float) s_rebuild[0]; }
+        if (kProjCulled) { n_out = s_nunits[0]; chi_o = (float) s_rebuild[0]; }
 #endif
-      if (A.out_stats) { const u64 dg = s_dig; last.dig_lo = (uint32_t) dg; last.dig_hi = (uint32_t) (dg >> 32); A.out_stats[(size_t) a * A.stats_stride + it] = last; }
-      if (!s_active) { s_status = LSM2D_NOT_ENOUGH_CORRESPONDENCES; s_done = 1; }
+        const u64 dg = s_dig;
+        const int w = ln == 0 ? n_corr : ln == 1 ? n_in : ln == 2 ? n_out : ln == 3 ? __float_as_int(chi_in) : ln == 4 ? __float_as_int(chi_o) : ln == 5 ? (int) (uint32_t) dg : (int) (uint32_t) (dg >> 32);
+        if (ln < 7) reinterpret_cast<int32_t*>(A.out_stats + (size_t) a * A.stats_stride + it)[ln] = w;
+      }
+      bool done = false;
+      float np0 = 0.0f, np1 = 0.0f, np2 = 0.0f;      // the pose the next iteration starts at
+      if (!active) { if (ln == 0) { s_status = LSM2D_NOT_ENOUGH_CORRESPONDENCES; s_done = 1; } done = true; }
       else {
-        // information matrix = H of the last iteration: assembled, given its prior and solved where it lies
-        s_H[0] = s_sum[0]; s_H[1] = s_sum[1]; s_H[2] = s_sum[2]; s_H[3] = s_sum[1]; s_H[4] = s_sum[3]; s_H[5] = s_sum[4];
-        s_H[6] = s_sum[2]; s_H[7] = s_sum[4]; s_H[8] = s_sum[5];
-        s_rhs[0] = s_sum[6]; s_rhs[1] = s_sum[7]; s_rhs[2] = s_sum[8];
-        if (A.prior) add_prior(s_prior, s_pose, s_H, s_rhs);
-        if (ff_on) {      // the pose this iteration started at: into the ring before the solve overwrites it
-          const int n = s_ring_n;
-          uint32_t* e = s_ring + 3 * (n & (kFfRing - 1));
-          e[0] = __float_as_uint(s_pose[0]); e[1] = __float_as_uint(s_pose[1]); e[2] = __float_as_uint(s_pose[2]);
-          s_ring_n = n + 1;
+        // the solve's nine inputs as broadcasts; information matrix = H of the last iteration (h00 h01 h02 / h01 h11 h12 / h02 h12 h22), prior included: one store by its nine lanes
+        float x0 = LSM2D_RL_F(tot, 0), x1 = LSM2D_RL_F(tot, 1), x2 = LSM2D_RL_F(tot, 2), x3 = LSM2D_RL_F(tot, 3), x4 = LSM2D_RL_F(tot, 4), x5 = LSM2D_RL_F(tot, 5),
+              x6 = LSM2D_RL_F(tot, 6), x7 = LSM2D_RL_F(tot, 7), x8 = LSM2D_RL_F(tot, 8);
+        float Hq = (hk == 0) ? x0 : (hk == 1 || hk == 3) ? x1 : (hk == 2 || hk == 6) ? x2 : (hk == 4) ? x3 : (hk == 5 || hk == 7) ? x4 : x5;      // (lane 41: the inlier count, below)
+        if (A.prior) {      // add_prior's terms: lane q < 9 that of its solve input (the upper triangle's and b's), lane 32 + k that of H's entry k
+          const int pr = h_lane ? hk / 3 : (int) ((0x210211000ull >> (4 * l16)) & 15), pc = h_lane ? hk - 3 * (hk / 3) : (int) ((0x333221210ull >> (4 * l16)) & 15);
+          float P = 0.0f;
+          if (ln < 9 || h_lane) P = prior_term_lane_call(s_prior, p0, p1, p2, pr, pc);
+          Hq += P;
+          const float tp = tot + P;
+          x0 = LSM2D_RL_F(tp, 0); x1 = LSM2D_RL_F(tp, 1); x2 = LSM2D_RL_F(tp, 2); x3 = LSM2D_RL_F(tp, 3); x4 = LSM2D_RL_F(tp, 4); x5 = LSM2D_RL_F(tp, 5);
+          x6 = LSM2D_RL_F(tp, 6); x7 = LSM2D_RL_F(tp, 7); x8 = LSM2D_RL_F(tp, 8);
+        }
+        if (h_lane) s_H[hk] = Hq;
+        if (ff_on) {      // the pose this iteration started at: into the ring (slot = pushes so far & 15)
+          if (ln < 3) s_ring[3 * (n & (kFfRing - 1)) + ln] = __float_as_uint(ln == 0 ? p0 : (ln == 1 ? p1 : p2));
+          if (ln == 0) s_ring_n = n + 1;
         }
         float dmp = A.damping;
         asm volatile("" : "+v"(dmp));      // (not a loop invariant to hoist -- as a double it was kept, and spilled, across the whole kernel)
-        if (!solve_update(s_H, s_rhs, dmp, s_pose)) { s_status = LSM2D_SINGULAR_H; s_done = 1; }
+        float dx, dy, dth;
+        const bool ok = solve_flat(x0, x1, x2, x3, x4, x5, x6, x7, x8, dmp, dx, dy, dth);
+        if (!ok) { if (ln == 0) { s_status = LSM2D_SINGULAR_H; s_done = 1; } done = true; }      // (nothing of the step has been written: s_pose stays the start pose)
         else {
+          // cos / sin of the heading the iteration started at: slice 0's, the same function of the same float, unless a sensor offset stands between them
+          float sn = iso0.s, cs = iso0.c;
+          if (A.s[0].has_sensor) sincos_fixed(p2, sn, cs);
+          np0 = __builtin_fmaf(cs, dx, __builtin_fmaf(-sn, dy, p0));
+          np1 = __builtin_fmaf(sn, dx, __builtin_fmaf(cs, dy, p1));
+          np2 = wrap_angle(p2 + dth);
+          if (ln < 3) s_pose[ln] = ln == 0 ? np0 : (ln == 1 ? np1 : np2);
           if (ff_on) {
-            // the new pose against the ring, newest entry first, as integers (-0 is not +0, a NaN is its pattern): entry k back is the start of iteration it - k
-            const uint32_t p0 = __float_as_uint(s_pose[0]), p1 = __float_as_uint(s_pose[1]), p2 = __float_as_uint(s_pose[2]);
-            const int n = s_ring_n;
-            for (int k = 0; k < kFfRing && k < n; ++k) {
-              const uint32_t* e = s_ring + 3 * ((n - 1 - k) & (kFfRing - 1));
-              if (e[0] != p0 || e[1] != p1 || e[2] != p2) continue;
-              const unsigned p = (unsigned) (k + 1), left = (unsigned) (s_phase_end - (it + 1));
-              skip = (int) ((left / p) * p);
-              const uint32_t* const rows = s_ff_rows;
-              if (rows && left > 0) {      // finish from the ring: the last iteration's twin is `back` entries back (0: this very iteration), 0 <= back <= k
-                const int back = k - (int) ((left - 1) % p);
-                if (back > 0) {      // (back == 0: it is its own twin -- s_H, s_last_n_in, the pose just solved and out_last_pose are what they must be)
-                  const uint32_t* et = s_ring + 3 * ((n - 1 - back) & (kFfRing - 1));      // the pose the twin started at,
-                  const uint32_t* en = s_ring + 3 * ((n - back) & (kFfRing - 1));          // the pose it ended on: the start of the iteration behind it
-                  const uint32_t* w = rows + ((n - 1 - back) & (kFfRing - 1)) * kFfRowWords;
-                  _Pragma("nounroll") for (int j = 0; j < 9; ++j) s_H[j] = __uint_as_float(w[j]);      // (once per alignment: word by word, no registers for a row)
-                  s_last_n_in = (int) w[9];
-                  if (A.out_last_pose) { A.out_last_pose[3 * a + 0] = __uint_as_float(et[0]); A.out_last_pose[3 * a + 1] = __uint_as_float(et[1]); A.out_last_pose[3 * a + 2] = __uint_as_float(et[2]); }
-                  s_pose[0] = __uint_as_float(en[0]); s_pose[1] = __uint_as_float(en[1]); s_pose[2] = __uint_as_float(en[2]);
+            // the new pose against the ring, as integers (-0 is not +0, a NaN is its pattern).  Slot j holds the start of iteration it - k, k = (n - j) & 15, if
+            // that many were pushed; slot n & 15 is this iteration's own start pose, on its way there.  The hit with the smallest k is the newest entry, the
+            // smallest period: the sixteen hits rotated into the order of k, lowest bit first.
+            const int kb = (n - ln) & (kFfRing - 1);
+            const bool own = kb == 0;
+            const bool hit = ln < kFfRing && kb <= n && (own ? __float_as_uint(p0) : e0) == __float_as_uint(np0) && (own ? __float_as_uint(p1) : e1) == __float_as_uint(np1) &&
+                             (own ? __float_as_uint(p2) : e2) == __float_as_uint(np2);
+            const uint32_t bal = (uint32_t) __ballot(hit) & 0xFFFFu;
+            if (bal) {      // once per alignment: lane 0 alone, as it always was
+              const uint32_t rev = __builtin_bitreverse32(bal) >> 16;      // bit i: slot 15 - i, i.e. k = (i + n + 1) & 15
+              const int rot = (n + 1) & (kFfRing - 1);
+              const uint32_t byk = ((rev << rot) | (rev >> (kFfRing - rot))) & 0xFFFFu;
+              const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(byk)), n1 = n + 1;
+              if (ln == 0) {
+                const unsigned p = (unsigned) (k + 1), left = (unsigned) (phase_end - (it + 1));
+                skip = (int) ((left / p) * p);
+                const uint32_t* const rows = ffw;
+                if (rows && left > 0) {      // finish from the ring: the last iteration's twin is `back` entries back (0: this very iteration), 0 <= back <= k
+                  const int back = k - (int) ((left - 1) % p);
+                  if (back > 0) {      // (back == 0: it is its own twin -- s_H, s_last_n_in, the pose just solved and out_last_pose are what they must be)
+                    const uint32_t* et = s_ring + 3 * ((n1 - 1 - back) & (kFfRing - 1));      // the pose the twin started at,
+                    const uint32_t* en = s_ring + 3 * ((n1 - back) & (kFfRing - 1));          // the pose it ended on: the start of the iteration behind it
+                    const uint32_t* w = rows + ((n1 - 1 - back) & (kFfRing - 1)) * kFfRowWords;
+                    _Pragma("nounroll") for (int j = 0; j < 9; ++j) s_H[j] = __uint_as_float(w[j]);      // (once per alignment: word by word, no registers for a row)
+                    s_last_n_in = (int) w[9];
+                    if (A.out_last_pose) { A.out_last_pose[3 * a + 0] = __uint_as_float(et[0]); A.out_last_pose[3 * a + 1] = __uint_as_float(et[1]); A.out_last_pose[3 * a + 2] = __uint_as_float(et[2]); }
+                    s_pose[0] = __uint_as_float(en[0]); s_pose[1] = __uint_as_float(en[1]); s_pose[2] = __uint_as_float(en[2]);
+                  }
+                  skip = (int) left;      // all of them: phase_over below, and ff_on excludes a second phase -- s_done, the status decided at the exit
                 }
-                skip = (int) left;      // all of them: phase_over below, and ff_on excludes a second phase -- s_done, the status decided at the exit
-              }
-              if (A.out_stats) {      // the skipped iterations' rows are the cycle's: written by this thread, read back by it in program order
-                StatsDev* row = A.out_stats + (size_t) a * A.stats_stride;
-                for (int j = it + 1; j <= it + skip; ++j) {
-                  StatsDev r = row[j - (int) p];
+                if (A.out_stats) {      // the skipped iterations' rows are the cycle's: written by this wave, read back by it in program order
+                  StatsDev* row = A.out_stats + (size_t) a * A.stats_stride;
+                  for (int j = it + 1; j <= it + skip; ++j) {
+                    StatsDev r = row[j - (int) p];
 #ifdef LSM2D_DEBUG_UNITS      // diagnostics build: a skipped row says so, and with which period (tools/units_probe.py)
-                  r.chi_out = (rows ? -0.5f : 0.0f) - (float) p;      // (... and a row filled in by "fast_forward" 2 -- nothing runs behind it -- by the half)
+                    r.chi_out = (rows ? -0.5f : 0.0f) - (float) p;      // (... and a row filled in by "fast_forward" 2 -- nothing runs behind it -- by the half)
 #endif
-                  row[j] = r;
+                    row[j] = r;
+                  }
                 }
               }
-              break;
+              skip = __builtin_amdgcn_readfirstlane(skip);      // lane 0's
             }
           }
-          bool phase_over = it + skip + 1 >= s_phase_end;
-          if (ff_on && !phase_over)      // another iteration follows: what a twin of THIS one would leave behind besides its poses -- H as the solve was given it (which it does not change), the inlier count
-            if (uint32_t* w = s_ff_rows) {
-              w += ((s_ring_n - 1) & (kFfRing - 1)) * kFfRowWords;
-              for (int k = 0; k < 9; ++k) w[k] = __float_as_uint(s_H[k]);
-              w[9] = (uint32_t) s_last_n_in;
-            }
+          bool phase_over = it + skip + 1 >= phase_end;
+          if (ff_on && !phase_over && ffw)      // another iteration follows: what a twin of THIS one would leave behind besides its poses -- H as the solve was given it, the inlier count: one store by ten lanes
+            if ((unsigned) hk < (unsigned) kFfRowWords) ffw[(n & (kFfRing - 1)) * kFfRowWords + hk] = hk == 9 ? (uint32_t) n_in : __float_as_uint(Hq);
           if (A.term_eps > 0.0f) {      // the aligner's termination criterion: relative decay of the total chi^2 (lsm2d.h), afresh in every phase
-            const float chi_now = s_sum[9] + s_sum[10];      // (= last.chi_in + last.chi_out, read again: kept in registers across the solve they were spilled)
+            const float chi_now = chi_in + chi_out;
             if (it > s_phase_start && __builtin_fabsf(s_prev_chi - chi_now) < A.term_eps * chi_now) phase_over = true;      // status stays RUNNING: decided below as after max_iterations
-            s_prev_chi = chi_now;
+            if (ln == 0) s_prev_chi = chi_now;
           }
           if (phase_over) {
             // enable_inlier_only_runs (lsm2d.h): the regular loop ended without a failure and with enough inliers -> up to max_it iterations over inliers only
-            if (A.inlier_runs && s_phase == 0 && last.n_in >= A.min_inliers) { s_phase = 1; s_phase_start = it + 1; s_phase_end = it + 1 + A.max_it; }
-            else s_done = 1;
+            if (A.inlier_runs && s_phase == 0 && n_in >= A.min_inliers) { if (ln == 0) { s_phase = 1; s_phase_start = it + 1; s_phase_end = it + 1 + A.max_it; } }
+            else { if (ln == 0) s_done = 1; done = true; }
           }
         }
       }
-      if (ff_on) s_skip = skip;              // every iteration, whichever way it went: nobody adds a stale one
-      if (!s_done) begin_iteration();        // next iteration's transforms and zeroed sums, under the same barrier
+#undef LSM2D_RL_F
+      if (ff_on && ln == 0) s_skip = skip;      // every iteration, whichever way it went: nobody adds a stale one
+      if (!done) {      // begin_iteration for the next one, under the same barrier: lane j prepares slice j (its constants through the scalar cache, picked by lane)
+        int hs = 0; float cS = 1.0f, sS = 0.0f, S0 = 0.0f, S1 = 0.0f, S2 = 0.0f;
+        for (int j = 0; j < A.n_slices; ++j) {
+          const SliceDev& Sj = A.s[__builtin_amdgcn_readfirstlane(j)];      // (said to be wave-uniform: the loop over lanes is not to become one load with a per-lane address -- a trip to the L2)
+          if (ln == j) { hs = Sj.has_sensor; cS = Sj.cSinv; sS = Sj.sSinv; S0 = Sj.Sinv[0]; S1 = Sj.Sinv[1]; S2 = Sj.Sinv[2]; }
+        }
+        if (ln < A.n_slices) {
+          const float Sv[3] = {S0, S1, S2}, X[3] = {np0, np1, np2};
+          float Xe[3] = {np0, np1, np2};
+          if (hs) compose(cS, sS, Sv, X, Xe);
+          Iso N; sincos_fixed(Xe[2], N.s, N.c); N.tx = Xe[0]; N.ty = Xe[1];
+          s_iso[ln] = N;
+          if (kProjCulled) {      // (see begin_iteration)
+            const float cd = N.c * Ll.c + N.s * Ll.s, sd = N.s * Ll.c - N.c * Ll.s;
+            const float ddx = N.tx - (cd * Ll.tx - sd * Ll.ty), ddy = N.ty - (sd * Ll.tx + cd * Ll.ty);
+            s_rebuild[ln] = (A.cull_keep && cd > 0.5f && __builtin_fabsf(sd) <= A.cull_mth && ddx * ddx + ddy * ddy <= A.cull_mt2) ? 0 : 1;
+          }
+        }
+        int zi = 0; asm volatile("" : "+v"(zi));      // (made here, every time: see begin_iteration)
+        if (ln < kSumWords) s_sum[ln] = __int_as_float(zi);
+        if (ln == 0) s_dig = (u64) (unsigned) zi;
+        if (A.out_last_pose && ln < 3) A.out_last_pose[3 * a + ln] = ln == 0 ? np0 : (ln == 1 ? np1 : np2);
+      }
     }
     LSM2D_PH(2);
+    LSM2D_PH_TAIL();
     __syncthreads();
     if (ff_on) it += __builtin_amdgcn_readfirstlane(s_skip);      // (every thread alike: `it` stays a scalar, and the exit below counts the skipped iterations in)
     if (s_done) { ++it; break; }

@@ -168,6 +168,26 @@ LSM2D_DEV void prior_apply(const PriorDev& Pz, const float pose[3], float Hp[9],
 }
 LSM2D_DEV void prior_terms(const PriorDev& Pz, const float pose[3], float Hp[9], float bp[3]) { prior_apply<false>(Pz, pose, Hp, bp); }
 LSM2D_DEV void add_prior_inline(const PriorDev& Pz, const float pose[3], float H[9], float b[3]) { prior_apply<true>(Pz, pose, H, b); }
+// ONE entry of the odometry prior's J^T Omega [J | e] (prior_apply's operations for that entry, in its order): row r in 0..2, column c in
+// 0..2 of the H term, c == 3 the b term.  J = [[cs, -sn, 0], [sn, cs, 0], [0, 0, 1]].
+LSM2D_DEV float prior_term_lane(const PriorDev& Pz, const float pose[3], int r, int c) {
+  float E[3]; compose(Pz.cz, Pz.sz, Pz.z_inv, pose, E);
+  float cs, sn; sincos_fixed(E[2], sn, cs);
+  const float msn = -sn;
+  const float x0 = c == 0 ? cs : (c == 1 ? msn : (c == 2 ? 0.0f : E[0]));
+  const float x1 = c == 0 ? sn : (c == 1 ? cs : (c == 2 ? 0.0f : E[1]));
+  const float x2 = c == 2 ? 1.0f : (c == 3 ? E[2] : 0.0f);
+  const float j0 = r == 0 ? cs : (r == 1 ? msn : 0.0f);
+  const float j1 = r == 0 ? sn : (r == 1 ? cs : 0.0f);
+  const float j2 = r == 2 ? 1.0f : 0.0f;
+  float oj[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { float v = 0.0f; v += Pz.omega[3 * k + 0] * x0; v += Pz.omega[3 * k + 1] * x1; v += Pz.omega[3 * k + 2] * x2; oj[k] = v; }
+  float v = 0.0f; v += j0 * oj[0]; v += j1 * oj[1]; v += j2 * oj[2];
+  return v;
+}
+// k_align's wave 0 calls it (one entry per lane), out of line like add_prior below: its temporaries stay out of the register allocation of the kernel's loops
+__device__ __noinline__ float prior_term_lane_call(const PriorDev& Pz, float px, float py, float pth, int r, int c) { const float pose[3] = {px, py, pth}; return prior_term_lane(Pz, pose, r, c); }
 // k_align (64 VGPRs) and the split path call it: rarely taken, and out of the register allocation of their loops
 __device__ __noinline__ void add_prior(const PriorDev& Pz, const float pose[3], float H[9], float b[3]) { add_prior_inline(Pz, pose, H, b); }
 

@@ -63,46 +63,6 @@ LSM2D_DEV void pair_wave_sums(const Accum& A, float* red, int tid, bool cauchy, 
   }
 }
 
-// ONE entry of the odometry prior's J^T Omega [J | e] (prior_apply's operations for that entry, in its order): row r in 0..2, column c in
-// 0..2 of the H term, c == 3 the b term.  J = [[cs, -sn, 0], [sn, cs, 0], [0, 0, 1]].
-LSM2D_DEV float prior_term_lane(const PriorDev& Pz, const float pose[3], int r, int c) {
-  float E[3]; compose(Pz.cz, Pz.sz, Pz.z_inv, pose, E);
-  float cs, sn; sincos_fixed(E[2], sn, cs);
-  const float msn = -sn;
-  const float x0 = c == 0 ? cs : (c == 1 ? msn : (c == 2 ? 0.0f : E[0]));
-  const float x1 = c == 0 ? sn : (c == 1 ? cs : (c == 2 ? 0.0f : E[1]));
-  const float x2 = c == 2 ? 1.0f : (c == 3 ? E[2] : 0.0f);
-  const float j0 = r == 0 ? cs : (r == 1 ? msn : 0.0f);
-  const float j1 = r == 0 ? sn : (r == 1 ? cs : 0.0f);
-  const float j2 = r == 2 ? 1.0f : 0.0f;
-  float oj[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { float v = 0.0f; v += Pz.omega[3 * k + 0] * x0; v += Pz.omega[3 * k + 1] * x1; v += Pz.omega[3 * k + 2] * x2; oj[k] = v; }
-  float v = 0.0f; v += j0 * oj[0]; v += j1 * oj[1]; v += j2 * oj[2];
-  return v;
-}
-
-// solve_update's LDL^T without early exits: the same operations on the same values whenever it succeeds; a failed pivot or a
-// non-finite step is reported at the end (what was computed behind it is discarded by the caller, as solve_update's return does)
-LSM2D_DEV bool solve_flat(float h00, float h01, float h02, float h11, float h12, float h22, float b0, float b1, float b2, float damping,
-                          float& dx, float& dy, float& dth) {
-  const double a00 = (double) h00 + (double) damping, a01 = h01, a02 = h02;
-  const double a11 = (double) h11 + (double) damping, a12 = h12, a22 = (double) h22 + (double) damping;
-  const double r0 = -(double) b0, r1 = -(double) b1, r2 = -(double) b2;
-  const double d0 = a00;
-  const double l10 = a01 / d0, l20 = a02 / d0;
-  const double d1 = a11 - l10 * a01;
-  const double l21 = (a12 - l20 * a01) / d1;
-  const double d2 = a22 - l20 * a02 - l21 * l21 * d1;
-  const double y0 = r0, y1 = r1 - l10 * y0, y2 = r2 - l20 * y0 - l21 * y1;
-  const double z2 = y2 / d2;
-  const double z1 = y1 / d1 - l21 * z2;
-  const double z0 = y0 / d0 - l10 * z1 - l20 * z2;
-  dx = (float) z0; dy = (float) z1; dth = (float) z2;
-  return (d0 > 0) & (d1 > 0) & (d2 > 0) & (bool) __builtin_isfinite(d0) & (bool) __builtin_isfinite(d1) & (bool) __builtin_isfinite(d2) &
-         (bool) __builtin_isfinite(z0) & (bool) __builtin_isfinite(z1) & (bool) __builtin_isfinite(z2);
-}
-
 #ifndef LSM2D_PAIR_READ_FIRST
 #define LSM2D_PAIR_READ_FIRST false      // z-buffer updates of the on-chip moving cloud: fire-and-forget (neighbouring lanes hold neighbouring columns' points)
 #endif

@@ -5,7 +5,7 @@
 //                      streams the moving cloud through an LDS polar z-buffer (64-bit ds_min keys),
 //                      walks the two canvases bin by bin (registration/correspondence_finder_projective_2d.cpp:55-74),
 //                      accumulates the plane-to-plane factor (octave/solver/nicp_post.m:4-26,69-90) in
-//                      registers, reduces with wave shuffles + one LDS hop, and lane 0 solves the 3x3
+//                      registers, reduces with wave shuffles + one LDS hop, and wave 0 solves the 3x3
 //                      system and right-updates the pose -- no host round trip, no global atomics.
 //   k_find_projective  CorrespondenceFinderProjective2f::compute for one (fixed, moving, pose): ordered pairs (lsm2d_k_finder.h).
 //   k_find_nn[_multi]  the point-query finders (exact grid NN, KD-tree, distance map) for one (fixed, moving, pose): pairs in ascending moving index.

@@ -3,7 +3,9 @@
 usage: LSM2D_EXTRA_HIPCC_FLAGS=-DLSM2D_PHASE_PROBE python -m srrg2_laser_slam_2d_amd.build --force && python tools/phase_probe.py <role> <finder>
 With --full-length (role A, projective; LSM2D_EXTRA_HIPCC_FLAGS="-DLSM2D_PHASE_PROBE=3 -DLSM2D_DEBUG_UNITS": buckets unit lists | stream | everything else, and the
 fast-forward's filled-in statistics rows marked): only the alignments of the headline batch that EXECUTE every iteration -- the ones the launch waits for behind the
-fast-forward -- first inside the whole batch, then by themselves, one workgroup per otherwise empty CU: what one of their iterations costs there, stream and the rest."""
+fast-forward -- first inside the whole batch, then by themselves, one workgroup per otherwise empty CU: what one of their iterations costs there, stream and the rest.
+Built with -DLSM2D_PHASE_PROBE=4 instead (pass --mode4: the library cannot say how it was built) the buckets are bin walk + wave sums | wave 0's stretch behind the sums'
+barrier | everything else, and the lone workgroups are measured once more with want_stats=False: the launch bench.py times writes no statistics rows and no digest."""
 import math, os, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +15,9 @@ from srrg2_laser_slam_2d_amd import api, synth
 FULL_LENGTH = "--full-length" in sys.argv
 if FULL_LENGTH:
     sys.argv.remove("--full-length")
+MODE4 = "--mode4" in sys.argv
+if MODE4:
+    sys.argv.remove("--mode4")
 role, kind = (sys.argv + (["A", "projective"] if FULL_LENGTH else ["B", "distmap"]))[1:3]
 ctx = api.Context(0, kernel_timing=True); ctx.set_option("clock_stride", 1)
 for kv in filter(None, os.environ.get("LSM2D_BENCH_OPTIONS", "").split(",")):
@@ -49,6 +54,20 @@ if FULL_LENGTH:
             r1 = al.compute_batch([sub], [mp], x0[full], want_stats=True)
         assert np.array_equal(r1.pose.view(np.uint32), r.pose[full].view(np.uint32)) and np.all(r1.iterations == its)
         life, lists, rest = stamped(len(full))
+        def lone_stretch(label, res, n):      # mode 4's buckets of the last launch
+            life, walk, tail = stamped(n)
+            other = life - walk - tail
+            print("  by themselves, %s (%d workgroups, a CU each): kernel %.3f ms; lifetime %s kcyc; per iteration: %s kcyc = bin walk + wave sums %s + wave 0's stretch %s + everything else (prologue / %d included) %s"
+                  % (label, n, res.kernel_ms, np.round(life / 1e3).astype(int).tolist(), np.round(life / its / 1e3, 1).tolist(), np.round(walk / its / 1e3, 2).tolist(),
+                     np.round(tail / its / 1e3, 2).tolist(), its, np.round(other / its / 1e3, 1).tolist()))
+        if MODE4:
+            lone_stretch("statistics rows written", r1, len(full))
+            for _ in range(3):
+                r0 = al.compute_batch([sub], [mp], x0[full], want_stats=False)
+            assert np.array_equal(r0.pose.view(np.uint32), r1.pose.view(np.uint32)) and np.all(r0.iterations == its)
+            lone_stretch("want_stats=False", r0, len(full))
+            os.remove(dump)
+            sys.exit(0)
         stream = life - lists - rest
         print("  by themselves (%d workgroups, a CU each): kernel %.3f ms; lifetime %s kcyc; per iteration: %s kcyc = unit lists %s + stream %s + everything else (prologue / %d included) %s"
               % (len(full), r1.kernel_ms, np.round(life / 1e3).astype(int).tolist(), np.round(life / its / 1e3, 1).tolist(), np.round(lists / its / 1e3, 1).tolist(),
