@@ -227,6 +227,16 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  * "cull" (default 1): the aligner's projective slices drop, exactly, the parts of a map-sized moving cloud that cannot yield a pair (and its
  *   point-query slices the tiles of queries nobody is near); 0 streams everything.  "cull_margin_um" (10000) / "cull_margin_urad" (2000, at most
  *   50000): how far a pose may move before the kept survivor lists of the projective culling are rebuilt.
+ * "cand_lists" (default 1): k_align on a single-slice culled projective batch keeps, once an alignment has run "cand_first_it" (default 3) iterations, a CANDIDATE
+ *   list: the indices of the streamed map points that can still win, or beat the winner of, a z-buffer column under any transform within "cand_margin_um" (default
+ *   30, at most 100000) micrometres / "cand_margin_urad" (default 3, at most 50000) microradians of the one the list was built at.  While the pose stays there an
+ *   iteration gathers those points (a few thousand where it would stream 41 000 on a 100k-point map) instead of streaming the kept survivor list; a pose that leaves
+ *   drops the list, and up to "cand_max_builds" (default 2) lists are built per alignment.  "cand_cap" (default 3328; lowered to the room in LDS): entries a list
+ *   may hold -- a longer one is not used and the alignment goes on streaming.  The moving canvas keeps its bits, hence every result does, whatever the values.  A
+ *   batch gets lists (and the kernel that carries them, k_align_cand) only where they pay and fit: one slice, "sum_order" 0, the wide unpacked launch form, at most one
+ *   dispatch round of alignments (4 x the CUs: what the lists shorten is the tail a few long alignments leave on an emptying chip), a moving cloud of at most 48 points
+ *   per entry of room (a denser map's lists do not fit), no other batch in flight when it is begun, and room in LDS beside four workgroups per CU.  Every other batch
+ *   runs exactly as without the option.  0: no lists.
  * "balance" (default 1): batches of 257 .. 4096 culled alignments are placed on the chip by estimated work (one small launch ahead of k_align; a
  *   batch run again with unchanged sets and start poses keeps its placement: get "last_cull_estimate"); 0: workgroup i runs alignment i.
  * "fast_forward" (0, 1 or 2; default 2): k_align and its packed, narrow and reference-order forms stop iterating once the pose repeats.  One Gauss-Newton
@@ -244,7 +254,9 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  * "distmap_build": 0 = automatic (default: the distance maps of CorrespondenceFinderNN2D are built from the points' side, one disc of atomic minima
  *   per point, whenever squared pixel distance and point index pack into 31 bits), 1 = always the per-pixel gather build; identical maps.
  * "kd_lds_nodes" (default 1536): nodes of the fixed cloud's KD-tree a k_align workgroup keeps in LDS (its top levels).
- * Read-only (lsm2d_get_option): "last_align_path" (1 k_align, 2 split, 3 slice pair), "last_query_cull", "last_cull_estimate", "last_kd_levels",
+ * Read-only (lsm2d_get_option): "last_align_path" (1 k_align, 2 split, 3 slice pair), "last_query_cull", "last_cull_estimate", "last_cand_builds" / "last_cand_iterations" /
+ *   "last_cand_overflows" (the latest aligner call that asked for statistics: candidate lists built, iterations a list served, lists too long
+ *   to be used; a call without statistics hands no counter over and leaves them as they were), "last_kd_levels",
  *   "last_kd_nodes", "last_kernel_clock_khz", "last_workgroup_lifetime_ns", "max_dyn_lds", "uploads" (host-to-device cloud uploads queued so far:
  *   lsm2d_cloudset_create / _upload / lsm2d_preprocess_scans_refill), "last_h2d_bytes", "experiments" (1: this library was built with
  *   -DLSM2D_EXPERIMENTS and also knows the A/B knobs of DESIGN.md App. A; the shipped library: 0). */

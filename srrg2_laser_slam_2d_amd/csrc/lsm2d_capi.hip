@@ -94,6 +94,14 @@ struct lsm2d_context {
   int fast_forward = 2;        // k_align and its forms: once an iteration ends on a pose that one of the last sixteen iterations started at, bit for bit, the alignment finishes from what the last iteration's twin left (1: whole periods of the cycle are skipped, the remainder runs; 0: every iteration runs; results do not depend on it)
   int cull_margin_um = 10000; // the translation margin in micrometres (10 mm) and
   int cull_margin_urad = 2000; // the rotation margin in microradians (2 mrad): tuning knobs, results do not depend on them
+  // k_align, single-slice culled projective batches: CANDIDATE lists (lsm2d_device.h) -- once the pose has settled an iteration gathers the few thousand points that can
+  // still win a column instead of streaming the unit list; results do not depend on any of these
+  int cand_lists = 1;          // 0: no lists
+  int cand_margin_um = 30, cand_margin_urad = 3;      // how far the slice transform may move from the one a list was built at (micrometres, microradians)
+  int cand_cap = 3328;         // entries a list may hold (32-bit point indices in LDS; a longer one is not used); the host lowers it to the room there is
+  int cand_first_it = 3;       // the first iteration (counted from 0) that may build a list
+  int cand_max_builds = 2;     // lists an alignment may build
+  int last_cand_builds = 0, last_cand_iterations = 0, last_cand_overflows = 0;      // the latest batch that asked for statistics: lists built, iterations served by one, lists too long to use
   int kd_wg_max_points = 16384; // KD-tree build: clouds of at most this many points are built by ONE launch, a workgroup per cloud walking the levels itself (k_kd_build_wg); 0: the level loop for all (A/B knob; same trees)
   int kd_wide_min_points = 1024;   // KD-tree build of larger clouds: levels whose evenly split nodes would hold at least this many points run a workgroup per node (0: a wave per node always; A/B knob)
   int grid_big_cells_x10 = 50;     // exact NN grid over a map-sized cloud: cells per side = this / 10 x sqrt(points); role B / NN on configs[1]: 2.0 2.08 ms, 3.0 1.85, 4.0 1.67, 5.0 1.66, 6.0 (rounds 2-3) 1.72, 8.0 1.73 (tuning knob)
@@ -392,6 +400,7 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   (void) hipFuncSetAttribute((const void*) k_align<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align<true, false, false, false, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+  (void) hipFuncSetAttribute((const void*) k_align_cand, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipFuncSetAttribute((const void*) k_align<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   for (const AlignVariant& v : kAlignVariantsSeq) (void) hipFuncSetAttribute((const void*) v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
@@ -475,10 +484,19 @@ const OptionDesc kOptions[] = {
   {"sum_order",          &lsm2d_context::sum_order,          0, 1,          0},
   {"align_width",        &lsm2d_context::align_width,        0, 1024,       0},
   {"fast_forward",       &lsm2d_context::fast_forward,       0, 2,          0},
+  {"cand_lists",         &lsm2d_context::cand_lists,         0, 1,          0},
+  {"cand_margin_um",     &lsm2d_context::cand_margin_um,     1, 100000,     0},
+  {"cand_margin_urad",   &lsm2d_context::cand_margin_urad,   1, 50000,      0},      // (the list's proof bounds the rotation by 1.001 times the margin: asin(x) <= 1.0005 x up to here)
+  {"cand_cap",           &lsm2d_context::cand_cap,           1, 8192,       0},
+  {"cand_first_it",      &lsm2d_context::cand_first_it,      1, 0x3fffffff, 0},
+  {"cand_max_builds",    &lsm2d_context::cand_max_builds,    0, 127,        0},
   // ---- read-only
   {"last_align_path",    &lsm2d_context::last_align_path,    0, 0, kOptReadOnly},
   {"last_align_width",   &lsm2d_context::last_align_width,   0, 0, kOptReadOnly},
   {"last_query_cull",    &lsm2d_context::last_query_cull,    0, 0, kOptReadOnly},
+  {"last_cand_builds",     &lsm2d_context::last_cand_builds,     0, 0, kOptReadOnly},
+  {"last_cand_iterations", &lsm2d_context::last_cand_iterations, 0, 0, kOptReadOnly},
+  {"last_cand_overflows",  &lsm2d_context::last_cand_overflows,  0, 0, kOptReadOnly},
   {"max_dyn_lds",        &lsm2d_context::max_dyn_lds,        0, 0, kOptReadOnly},      // bytes of LDS one workgroup may ask for
   {"uploads",            &lsm2d_context::uploads,            0, 0, kOptReadOnly},      // host-to-device cloud uploads this context has queued so far (lsm2d_cloudset_create / _upload)
   {"last_cull_estimate", &lsm2d_context::last_cull_estimate, 0, 0, kOptReadOnly},      // 1: the latest aligner call launched the placement's estimate; 0: it reused the order of an unchanged prepared batch, or needed none

@@ -29,7 +29,7 @@ extern "C" int32_t lsm2d_stats_capacity(const lsm2d_aligner_params* ap) {
 struct lsm2d_pending {
   lsm2d_context* ctx = nullptr;
   Lane* lane = nullptr;                     // the lane the batch was launched on: its pinned staging buffer is where the results are (or are copied to), its ev_done what a wait waits for
-  size_t o_pose = 0, o_H = 0, o_status = 0, o_its = 0, o_stats = 0, o_last_pose = 0, o_clock = 0;
+  size_t o_pose = 0, o_H = 0, o_status = 0, o_its = 0, o_stats = 0, o_last_pose = 0, o_clock = 0, o_cand = 0;
   int n = 0, stats_stride = 0, n_clock = 0, clock_stride = 0;
   bool zero_copy = false, want_stats = false, want_last_pose = false, stamps = false, timed = false, async = false;
 };
@@ -104,7 +104,7 @@ struct AlignBatch {
   int n, ns, stats_stride, it_cap;
   AlignArgs A;
   // ---- scratch / staging layout: [init_pose | prior | indices | out_pose | out_H | status | its | stats | last_pose | clock | work | ff_rows]
-  size_t off, o_pose_in, o_prior, o_fidx[kMaxSlices], o_midx[kMaxSlices], in_bytes, o_pose, o_H, o_status, o_its, o_stats, o_last_pose, o_clock, out_bytes, o_work, o_ff_rows, total_bytes;
+  size_t off, o_pose_in, o_prior, o_fidx[kMaxSlices], o_midx[kMaxSlices], in_bytes, o_pose, o_H, o_status, o_its, o_stats, o_last_pose, o_clock, o_cand, out_bytes, o_work, o_ff_rows, total_bytes;
   int clock_stride, n_clock;
   bool had_inputs; char* hs; char* ds;
   // ---- which path
@@ -166,6 +166,7 @@ int AlignBatch::validate_and_lay_out_scratch() {
   // in-kernel clock stamps of ~32 workgroups spread over the grid (timed k_align launches only)
   clock_stride = ctx->clock_stride > 0 ? ctx->clock_stride : (n / 32 > 1 ? n / 32 : 1), n_clock = (n + clock_stride - 1) / clock_stride;
   o_clock = ctx->kernel_timing ? take(sizeof(unsigned long long) * 4 * (size_t) n_clock) : 0;
+  o_cand = out_stats ? take(sizeof(int32_t) * (size_t) n) : 0;      // the candidate lists' books, one word per alignment (AlignArgs::cand_out): with the statistics only
   out_bytes = off - o_pose;      // what travels back to the host
   o_work = take(sizeof(int32_t) * (size_t) n);                                                     // balanced placement: the estimate's counts (device only)
   // "fast_forward" 2: H and inlier count of every alignment's last kFfRing iterations (device only; 640 bytes per alignment; needs no clearing: a row is read only after its alignment wrote it)
@@ -377,6 +378,39 @@ int AlignBatch::lay_out_lds() {
     if ((int) (at + need) + 2048 <= ctx->max_dyn_lds && at + need + 2048 <= 40 * 1024) { A.units_off = (int32_t) at; lds = at + need; }      // four workgroups per CU must still fit (160 KB)
     else proj_culled_for_all = false;
   }
+  // Round 20: a single slice's candidate list (lsm2d_device.h) behind the unit lists -- a word per column, then up to "cand_cap" 32-bit entries -- for the batches it pays for
+  // and by room, launched as k_align_cand; every other batch runs the kernel it always ran.  The rules, each from a measurement (DESIGN section 5):
+  //  - room: four workgroups per CU must still fit, and only the wide unpacked form carries the code: not with "sum_order" 1, and not where the batch takes the narrow or
+  //    the packed form with or without the list's bytes (they are chosen by the workgroups a CU holds: align_width_for, pack_two_for);
+  //  - at most ONE dispatch round (4 workgroups x the CUs): what the lists shorten is the tail a few long alignments leave on an emptying chip.  A batch of many rounds
+  //    has no such tail -- the next round fills the slots -- and there the builds of the many alignments that are done after three to five iterations are pure cost
+  //    (65 536 candidates: 15.2 -> 19.6 ms per step with lists);
+  //  - a moving cloud whose lists can fit: the candidates grow with the cloud's density -- about 2 % of a 100k-point map's points -- and a list that outgrows its room is a
+  //    wasted build (1M points: every list overflowed, 3.9 -> 6.6 ms per step).  48 points of cloud per entry of room is the bound; the kernel, for its part, does not
+  //    build a second list for an alignment whose first one was too long;
+  //  - no other batch in flight: a batch begun while another one runs has its tail under that one's launch or the next one's, so there is nothing to shorten, while the
+  //    build's passes and the list's LDS -- room the next batch's pre-kernels would have found free -- are paid (the streamed pipeline: 0.362 - 0.368 -> 0.381 - 0.384 ms per
+  //    step with lists, profiles/r20/stream_ab.txt).  A batch begun alone and waited for gets its lists.
+  A.cand_off = 0;
+  const int one_round = 4 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
+  if (proj_culled_for_all && ns == 1 && ctx->cand_lists && ctx->cull_keep && !ctx->sum_order && cols_max <= 16384 && n <= one_round && !(async && ctx->inflight >= 1)) {
+    const size_t at = (lds + 15) & ~(size_t) 15, bits = sizeof(uint32_t) * (size_t) cand_blocker_words(cols_max);
+    const size_t limit = std::min((size_t) 40 * 1024, (size_t) (ctx->max_dyn_lds > 0 ? ctx->max_dyn_lds : 0));
+    long long cap = at + bits + 2048 < limit ? (long long) ((limit - 2048 - at - bits) / sizeof(uint32_t)) : 0;
+    const bool cloud_fits = (long long) max_moving <= 48ll * cap;      // (against the room, not against a capacity the caller lowered)
+    if (cap > ctx->cand_cap) cap = ctx->cand_cap;
+    if (cap >= 64 && cloud_fits) {
+      const size_t with = at + bits + sizeof(uint32_t) * (size_t) cap;
+      const bool wide = align_width_for(ctx, n, lds) == kAlignBlock && align_width_for(ctx, n, with) == kAlignBlock;
+      const bool balanced = !use_split && !zero_copy && A.cull && ctx->balance && n > 256 && n <= 4096;      // (make_placement's condition for a placement, hence for packing)
+      const bool packed = balanced && (pack_two_for(ctx, n, lds) || pack_two_for(ctx, n, with));
+      if (wide && !packed) {
+        A.cand_off = (int32_t) at; A.cand_cap = (int32_t) cap; lds = with;
+        A.cand_first_it = ctx->cand_first_it; A.cand_max_builds = ctx->cand_max_builds;
+        A.cand_mt = 1e-6f * (float) ctx->cand_margin_um; A.cand_mth = 1e-6f * (float) ctx->cand_margin_urad;
+      }
+    }
+  }
   // "sum_order" 1: the trip's pair records (lsm2d_device.h), behind everything else -- three workgroups per CU instead of four
   A.seq_off = 0;
   if (ctx->sum_order) { lds = (lds + 15) & ~(size_t) 15; A.seq_off = (int32_t) lds; lds += kSeqLdsBytes; }
@@ -456,6 +490,7 @@ int AlignBatch::stage_inputs() {
   A.out_pose = (float*) (ro + o_pose); A.out_H = (float*) (ro + o_H); A.out_status = (int32_t*) (ro + o_status); A.out_its = (int32_t*) (ro + o_its);
   A.out_stats = out_stats ? (StatsDev*) (ds + o_stats) : nullptr;
   A.out_last_pose = out_last_pose ? (float*) (ro + o_last_pose) : nullptr;
+  A.cand_out = out_stats ? (int32_t*) (ro + o_cand) : nullptr;
 
   ctx->last_clock_khz = 0; ctx->last_wg_lifetime_ns = 0;
   stamps = ctx->kernel_timing && !use_split && !use_pair;
@@ -475,6 +510,7 @@ int AlignBatch::stage_inputs() {
     // host memset of 4 n bytes; on the device for the paths that copy -- and one that is still unwritten after the wait turns the call into LSM2D_DEVICE_ERROR
     if (host_results) memset(hs + o_status, 0xFF, sizeof(int32_t) * (size_t) n);
     else HIPCHK(ctx, hipMemsetAsync(ds + o_status, 0xFF, sizeof(int32_t) * (size_t) n, ks));
+    if (out_stats) { if (host_results) memset(hs + o_cand, 0, sizeof(int32_t) * (size_t) n); else HIPCHK(ctx, hipMemsetAsync(ds + o_cand, 0, sizeof(int32_t) * (size_t) n, ks)); }      // (the paths without lists write nothing there)
   }
   ctx->last_align_path = use_split ? 2 : (use_pair ? 3 : 1);
   return LSM2D_SUCCESS;
@@ -638,7 +674,7 @@ int AlignBatch::launch() {
       else
       if (width == 256) hipLaunchKernelGGL(k_align_narrow<256>, grid, dim3(256), lds, ks, A);
       else
-      hipLaunchKernelGGL(fn, grid, block, lds, ks, A);
+      hipLaunchKernelGGL(A.cand_off > 0 && mode == 5 && !ctx->sum_order ? (AlignKernel) k_align_cand : fn, grid, block, lds, ks, A);
     }
   }
   HIPCHK(ctx, hipGetLastError());
@@ -655,7 +691,7 @@ int AlignBatch::hand_over() {
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
   P.ctx = ctx; P.lane = L;
-  P.o_pose = o_pose; P.o_H = o_H; P.o_status = o_status; P.o_its = o_its; P.o_stats = o_stats; P.o_last_pose = o_last_pose; P.o_clock = o_clock;
+  P.o_pose = o_pose; P.o_H = o_H; P.o_status = o_status; P.o_its = o_its; P.o_stats = o_stats; P.o_last_pose = o_last_pose; P.o_clock = o_clock; P.o_cand = o_cand;
   P.n = n; P.stats_stride = stats_stride; P.n_clock = n_clock; P.clock_stride = clock_stride;
   P.zero_copy = zero_copy; P.want_stats = out_stats != nullptr; P.want_last_pose = out_last_pose != nullptr; P.stamps = stamps; P.timed = ctx->kernel_timing != 0; P.async = async;
   if (async) {
@@ -719,6 +755,12 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
   if (out_its) memcpy(out_its, hs + o_its, sizeof(int32_t) * (size_t) n);
   if (out_stats) memcpy(out_stats, hs + o_stats, sizeof(StatsDev) * (size_t) n * (size_t) stats_stride);
   if (out_last_pose) memcpy(out_last_pose, hs + o_last_pose, sizeof(float) * 3 * (size_t) n);
+  if (P.want_stats) {      // the candidate lists' books of this batch (align_body's s_cand_stat: iterations served | lists built << 16 | of which too long << 24)
+    const uint32_t* cw = (const uint32_t*) (hs + P.o_cand);
+    long long its = 0, builds = 0, over = 0;
+    for (int i = 0; i < n; ++i) { its += cw[i] & 0xFFFFu; builds += (cw[i] >> 16) & 0xFFu; over += cw[i] >> 24; }
+    ctx->last_cand_iterations = (int) std::min(its, (long long) 0x7fffffff); ctx->last_cand_builds = (int) std::min(builds, (long long) 0x7fffffff); ctx->last_cand_overflows = (int) std::min(over, (long long) 0x7fffffff);
+  }
   if (stamps) {     // median over the stamped workgroups: shader cycles per 10 ns tick of the constant 100 MHz counter
     const unsigned long long* ck = (const unsigned long long*) (hs + o_clock);
     std::vector<double> khz; std::vector<unsigned long long> life;

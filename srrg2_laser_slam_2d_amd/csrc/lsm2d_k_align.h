@@ -8,7 +8,11 @@
 // lost 17-25 % per alignment).  The z-buffer does not care who streams which point; the bin walk and the sums keep the 512 VIRTUAL threads of the wide kernel --
 // thread t plays virtual threads t, t + kW, ... one after the other, each with its own partial sums, its waves' trees written to the same eight rows of `red` --
 // so every result keeps its bits (tests: 256 against 512).
-template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0, bool kSeq = false, int kW = kAlignBlock>
+// kCandLists: the instantiation carries the candidate lists of round 20 (lsm2d_device.h) -- k_align_cand, the wide culled projective kernel, alone: with their code the
+// narrow, the packed and the reference-order forms, which share this body, needed private memory (16 .. 32 bytes of scratch; the packed ones a copy of the
+// arguments), and in the shapes those forms are chosen for the lists' room in LDS runs out anyway; and inside k_align<1,0,0,0,5> it
+// would change the kernel of every batch that gets no list.  The host gives a list an offset only to a batch it launches as k_align_cand.
+template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0, bool kSeq = false, int kW = kAlignBlock, bool kCandLists = false>
 LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   static_assert(kW == kAlignBlock || (kNNMode == 5 && !kSeq && kW % 64 == 0 && kW >= 256 && kW < kAlignBlock), "narrow workgroups: the culled projective stream only");
   __builtin_assume(A.n_slices >= 1 && A.n_slices <= kMaxSlices);      // (the host refuses anything else: the slice loops need no guard -- which, as a flag, was kept in a vector register and spilled)
@@ -19,6 +23,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   // ... and for a pure projective batch: 5 = every slice streams a lane-chunked moving cloud through the exact culling in units (what a batch against a map
   // does): the plain lane stream and the per-pair stream of small clouds are compiled out
   constexpr bool kProjCulled = kNNMode == 5;
+  constexpr bool kCand = kCandLists && kProjCulled && !kSeq && kW == kAlignBlock;
   static_assert(kNNMode == 0 || ((kNNMode <= 2) && kHasNN && !kHasProj && !kHasDist && !kHasKd) || ((kNNMode == 3 || kNNMode == 4) && kHasKd && !kHasProj && !kHasDist && !kHasNN) ||
                 (kNNMode == 5 && kHasProj && !kHasNN && !kHasDist && !kHasKd), "kNNMode: one finder only");
   extern __shared__ __align__(16) unsigned char smem[];
@@ -56,6 +61,15 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ int s_wcnt[2 * (kAlignBlock / 64)];
   __shared__ int s_nunits[kMaxSlices], s_rebuild[kMaxSlices];      // kProjCulled: entries in a slice's unit list; the list must be rebuilt before it is streamed again
   __shared__ Iso s_list_iso[kMaxSlices];                             // ... and the transform it was built at
+  // kProjCulled, round 20: the slice's CANDIDATE list (lsm2d_device.h, "candidate lists"; AlignArgs::cand_off > 0: a single slice, and room in LDS).  The transform
+  // it was built at; its entries (counted by the build's waves, past the capacity if they must); what the coming iteration does about it -- 0: streams the
+  // unit list, 1: gathers the list's points instead, 2: streams the unit list and builds a list behind it; and what happened so far: iterations served by a
+  // list (bits 0..15, saturating), lists built (16..23), of which too long to be used (24..31).  Wave 0's, like s_rebuild: no register is held across the loops.
+  __shared__ Iso s_cand_iso;
+  __shared__ int s_cand_n, s_cand_state, s_cand_stat;
+  // ... and the launch's arguments for it, read back from here by whoever needs them: as kernel arguments they were loop invariants, scalar registers held -- and
+  // spilled into vector registers -- across the loops.  Words: offset (0: no lists), capacity, first iteration, lists per alignment | margins (floats)
+  __shared__ int s_cand_par[6];
   uint16_t* l_units = reinterpret_cast<uint16_t*>(smem + A.units_off);      // [n_slices][kCullBlocks * kAlignBlock]
   float* l_rec = reinterpret_cast<float*>(smem + (kSeq ? A.seq_off : 0));   // kSeq: [kSeqHalf][kSeqFields]: half a trip's pair records
   // "fast_forward" (AlignArgs::fast_forward): the poses the last kFfRing iterations STARTED at, as bit patterns, in a ring (slot = pushes & (kFfRing - 1)); how
@@ -174,6 +188,11 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     for (int s = 0; s < kMaxSlices; ++s) { s_list_iso[s].c = 1.0f; s_list_iso[s].s = 0.0f; s_list_iso[s].tx = 0.0f; s_list_iso[s].ty = 0.0f; }
     if (!s_done) begin_iteration();
     for (int s = 0; s < kMaxSlices; ++s) s_rebuild[s] = 1;      // no list yet
+    if (kCand) {
+    s_cand_n = 0; s_cand_state = 0; s_cand_stat = 0;
+    s_cand_par[0] = A.cand_off; s_cand_par[1] = A.cand_cap; s_cand_par[2] = A.cand_first_it; s_cand_par[3] = A.cand_max_builds;
+    s_cand_par[4] = __float_as_int(A.cand_mt); s_cand_par[5] = __float_as_int(A.cand_mth);
+    }
   }
   __syncthreads();
   if (kNNGlobal) for (int i = tid; i < A.nn_qcache; i += kAlignBlock) l_qc[8 * i] = 0x7fffffff;      // no cell cached yet (visible after the barriers below)
@@ -356,6 +375,15 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             const int Tm = S.moving.lane_T[mc];
             const int nbs = __builtin_amdgcn_readfirstlane(S.moving.block_stride);
             const int B = cull_block_steps(Tm, nbs), nb = (Tm + B - 1) / B;
+            // Round 20: what wave 0 decided about the slice's candidate list when it prepared this iteration (s_cand_state; a single slice: s == 0)
+            const int cst = kCand ? __builtin_amdgcn_readfirstlane(s_cand_state) : 0;      // (stays 0 where the launch has no room for lists)
+            if (kCand && cst == 1) {      // the list serves this transform: its points alone -- the unit list is neither rebuilt (s_rebuild is 0: wave 0 saw to that) nor read
+              const float2* mxy = S.moving.xy + S.moving.start[mc];
+              const uint32_t* cand = reinterpret_cast<const uint32_t*>(smem + __builtin_amdgcn_readfirstlane(s_cand_par[0])) + cand_blocker_words(S.proj.cols);
+              const int n_cand = __builtin_amdgcn_readfirstlane(s_cand_n);
+              if (S.proj.tiny_ok) project_candidates_t<false, kW>(mxy, T, S.proj, mcan, tid, cand, n_cand);
+              else project_candidates_t<true, kW>(mxy, T, S.proj, mcan, tid, cand, n_cand);
+            } else {
             if (__builtin_amdgcn_readfirstlane(s_rebuild[s])) {
               typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
               const float m_t = A.cull_mt, m_th = A.cull_mth;      // (0 when the lists are not kept: the host sees to that -- a select made here was a vector register held across the iteration)
@@ -416,6 +444,13 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             LSM2D_PH_LISTS();
             const int n_units = __builtin_amdgcn_readfirstlane(s_nunits[s]);
             if (n_units > 0) project_cloud_list<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B);
+            if (kCand && cst == 2) {
+              // Build, behind the stream: (a) every column's blocker, (b) the unit list's points once more, against the rule (lsm2d_device.h); wave 0 looks at the
+              // count behind the sums' barrier (too long: not used, the alignment goes on streaming units)
+              uint32_t* blk = reinterpret_cast<uint32_t*>(smem + __builtin_amdgcn_readfirstlane(s_cand_par[0]));
+              cand_build<kW, kAlignBlock>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, tid, units, n_units, B, blk, s_cand_par, &s_cand_n);
+            }
+            }
           }
           else if (S.moving.lane_xy && S.moving.lane_bounds && A.cull) {
             // exact culling against the fixed canvas (chunk_may_matter): every thread tests the chunk it would stream, the survivors are
@@ -888,11 +923,40 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
           float Xe[3] = {np0, np1, np2};
           if (hs) compose(cS, sS, Sv, X, Xe);
           Iso N; sincos_fixed(Xe[2], N.s, N.c); N.tx = Xe[0]; N.ty = Xe[1];
+          const Iso cur0 = s_iso[0];      // (kProjCulled, the candidate list: the transform the iteration that ends here had)
           s_iso[ln] = N;
           if (kProjCulled) {      // (see begin_iteration)
             const float cd = N.c * Ll.c + N.s * Ll.s, sd = N.s * Ll.c - N.c * Ll.s;
             const float ddx = N.tx - (cd * Ll.tx - sd * Ll.ty), ddy = N.ty - (sd * Ll.tx + cd * Ll.ty);
-            s_rebuild[ln] = (A.cull_keep && cd > 0.5f && __builtin_fabsf(sd) <= A.cull_mth && ddx * ddx + ddy * ddy <= A.cull_mt2) ? 0 : 1;
+            const int rb = (A.cull_keep && cd > 0.5f && __builtin_fabsf(sd) <= A.cull_mth && ddx * ddx + ddy * ddy <= A.cull_mt2) ? 0 : 1;
+            s_rebuild[ln] = rb;
+            if (kCand && s_cand_par[0] > 0 && ln == 0) {
+              // Round 20, the candidate list (a single slice: lane 0's).  First the books of the iteration that has just ended: a list
+              // it built (the sums' barrier stands behind the build's counting) is the list from here on if it fits, built at the transform this iteration had --
+              // asked for in `cur0` before s_iso[0] was overwritten.  Then the policy for the coming iteration.  The list serves N while the unit list it was taken
+              // from does (a list whose pose was left is dropped) and N is within the tight margins of the transform it was built at.  A new one is built from
+              // iteration cand_first_it on, while fewer than cand_max_builds were (a test of the step just taken against a fraction of the margins, so that
+              // only settled poses build, measured slower than building at cand_first_it whatever the step was: docs/REJECTED.md).  Everything is read here and now, from LDS: nothing of it lives in a register anywhere else in the kernel.
+              int st = s_cand_state, stat = s_cand_stat;
+              const int n_built = s_cand_n, cap = s_cand_par[1], first_it = s_cand_par[2], max_builds = s_cand_par[3];
+              const float mt = __int_as_float(s_cand_par[4]), mth = __int_as_float(s_cand_par[5]);
+              Iso Lc = s_cand_iso;
+              if (st == 2) {
+                const bool fits = n_built <= cap;
+                // (as arithmetic, not `fits ? 0x10000 : 0x1010000`: hipcc 6.x turned that select into an s_cselect_b32 on a stale SCC behind a v_cmp that sets VCC --
+                // every list was booked as too long; seen in the assembly, the counters of tests/test_gpu_candidate_lists.py are what guards it)
+                int over = fits ? 0 : 1; asm volatile("" : "+v"(over));
+                stat += 0x10000 + (over << 24);
+                st = fits ? 1 : 0;
+                if (fits) { Lc = cur0; s_cand_iso = cur0; }
+              }
+              const bool serves = st == 1 && !rb && cand_pose_within(N, Lc, mt, mth);
+              const bool build = !serves && it + 1 >= first_it && ((stat >> 16) & 0xFF) < max_builds && (stat >> 24) == 0;      // (a list that was too long once will be again: no second try)
+              if (serves && (stat & 0xFFFF) != 0xFFFF) ++stat;      // counted where it is decided: the alignment's last iteration too
+              s_cand_state = serves ? 1 : (build ? 2 : 0);
+              s_cand_stat = stat;
+              if (build) s_cand_n = 0;
+            }
           }
         }
         int zi = 0; asm volatile("" : "+v"(zi));      // (made here, every time: see begin_iteration)
@@ -913,6 +977,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     A.out_pose[3 * a + 0] = s_pose[0]; A.out_pose[3 * a + 1] = s_pose[1]; A.out_pose[3 * a + 2] = s_pose[2];
     if (A.out_H) for (int k = 0; k < 9; ++k) A.out_H[9 * a + k] = s_H[k];
     if (A.out_its) A.out_its[a] = it;
+    if (kCand && A.cand_out) A.cand_out[a] = s_cand_stat;      // (handed over only when the caller asked for statistics: the timed launch does not pay for it)
     // the status goes last, behind a system-scope release: with results written straight to pinned host memory the host polls
     // this word instead of waiting for the stream (lsm2d_align_batch), and whoever sees it sees everything above
     if (stamp) {
@@ -948,6 +1013,11 @@ constexpr int align_min_waves() {
 template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0>
 __global__ __launch_bounds__(kAlignBlock, (align_min_waves<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>())) void k_align(const AlignArgs A) {
   align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>(A);
+}
+// Round 20: k_align<1,0,0,0,5> WITH the candidate lists (align_body's kCandLists) -- a kernel of its own, launched only for a batch the host has given a list's room
+// (AlignArgs::cand_off > 0); every other batch runs the kernel it always ran, instruction for instruction.
+__global__ __launch_bounds__(kAlignBlock, LSM2D_ALIGN_MIN_WAVES) void k_align_cand(const AlignArgs A) {
+  align_body<true, false, false, false, 5, false, kAlignBlock, true>(A);
 }
 #ifndef LSM2D_SEQ_MIN_WAVES
 #define LSM2D_SEQ_MIN_WAVES 8

@@ -84,6 +84,13 @@ struct AlignArgs {
   uint32_t* ff_rows;                        // [n_align][kFfRing][kFfRowWords] device scratch, written and read by the alignment's thread 0 only; nullptr unless fast_forward == 2
   int32_t fast_forward;
   SliceDev s[kMaxSlices];
+  // kProjCulled, round 20: the candidate list of a single-slice batch (lsm2d_device.h, "candidate lists").  cand_off > 0: byte offset in dynamic LDS of a word per
+  // column (its blocker's depth: cand_blocker_words) and behind them cand_cap 32-bit point indices -- given only where both fit behind the unit
+  // lists without changing the launch form or the workgroups a CU holds; 0: no lists.  cand_mt / cand_mth: the margins a list serves (metres, radians); cand_first_it: the first iteration that may build
+  // one; cand_max_builds: lists per alignment.  cand_out [n_align] or nullptr: every alignment's books (align_body's s_cand_stat), summed by the host
+  int32_t cand_off, cand_cap, cand_first_it, cand_max_builds;
+  float   cand_mt, cand_mth;
+  int32_t* cand_out;                        // (behind everything else: the kernels without lists read every older field at the offset it always had)
 };
 
 LSM2D_DEV int pick_cloud(const CloudDev& c, int a) {
