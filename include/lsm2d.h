@@ -58,7 +58,9 @@ extern "C" {
                                     scoring, then the acceptance test and the best k hypotheses ranked on the device: only k rows come down);
                              (0.7.5, number unchanged: an addition only) + lsm2d_score_aligner_batch, lsm2d_score_aligner_select (hypotheses scored against an
                                     ALIGNER -- all its slices, sensor offsets, the skip rule and the optional prior -- in one call with one wait, and ranked
-                                    on the device) */
+                                    on the device);
+                             (0.7.6, number unchanged: an addition only) + lsm2d_clip_scene_voxelized_batch (lsm2d_clip_scene_batch with the clipper's
+                                    voxelize_resolution > 0 branch inside the same launch, the single voxelised call's bits per tracker) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -396,6 +398,16 @@ int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* projector, lsm
 int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector* projector, const lsm2d_cloudset* scenes, int32_t n_trackers,
                            const int32_t* scene_index, const float* robot_in_local_map /* [n_trackers][3] */, const float sensor_in_robot[3],
                            lsm2d_cloudset* clipped, int32_t* out_n_points);
+/* lsm2d_clip_scene_voxelized for n_trackers at once -- the clipper's voxelize_resolution > 0 branch (mapping/scene_clipper_projective_2d.cpp:36-48;
+ * the class default is 0.1) in the SAME single launch: each tracker's workgroup keeps its clipped points in LDS, in the sensor frame, voxelises
+ * them with coefficients (res, res, 0.1, 0.1) and writes only the voxels, moved to the robot frame, to cloud i of `clipped`.  Each tracker has the
+ * bits and the count of lsm2d_clip_scene_voxelized for the same scene, pose, offset and resolution.  No source indices (a voxel has no source
+ * point).  Arguments, set requirements and the asynchronous form (out_n_points NULL; the host's bound per cloud is canvas_cols: a voxelised cloud
+ * never grows) as lsm2d_clip_scene_batch; canvas_cols <= 2048, more is LSM2D_CAPACITY_EXCEEDED and nothing is launched.
+ * voxelize_resolution <= 0 is lsm2d_clip_scene_batch. */
+int lsm2d_clip_scene_voxelized_batch(lsm2d_context* ctx, const lsm2d_projector* projector, const lsm2d_cloudset* scenes, int32_t n_trackers,
+                                     const int32_t* scene_index, const float* robot_in_local_map /* [n_trackers][3] */, const float sensor_in_robot[3],
+                                     float voxelize_resolution, lsm2d_cloudset* clipped, int32_t* out_n_points);
 /* lsm2d_merge_scenes for n_trackers at once: cloud scene_index[i] (NULL: i) of `scenes` (a set of lsm2d_cloudset_create_reserved_many;
  * no index twice) gets cloud meas_index[k * n_trackers + i] (NULL: i) of measurements[k], k = 0 .. n_measurements - 1 (1 .. 4), merged
  * one after the other at measurement_in_scene[i][k] ([n_trackers][n_measurements][3]).  All or nothing: when a scene may lack room for

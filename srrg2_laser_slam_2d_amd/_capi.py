@@ -129,6 +129,7 @@ SYMBOLS = [
     ("lsm2d_cloudset_create_reserved_many", C.c_int, [_P, C.c_int32, C.c_int64, C.POINTER(_P)]),
     ("lsm2d_cloudset_clear_clouds", C.c_int, [_P, C.c_int32, _P]),
     ("lsm2d_clip_scene_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("lsm2d_clip_scene_voxelized_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, _P, _P, C.c_float, _P, _P]),
     ("lsm2d_merge_scene_batch", C.c_int, [_P, C.POINTER(Projector), _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_float, _P, _P]),
     ("lsm2d_find_correspondences_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("lsm2d_linearize_batch", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),

@@ -1076,21 +1076,26 @@ class SceneClipperProjective2D:
         return self._clipped
 
     def compute_batch(self, scenes: CloudSet, robot_in_local_map, clipped: CloudSet, scene_index=None):
-        """compute() for N trackers at once (lsm2d_clip_scene_batch, voxelize_resolution 0 only): tracker i clips cloud
+        """compute() for N trackers at once, in one launch (lsm2d_clip_scene_batch; ``voxelize_resolution`` > 0:
+        lsm2d_clip_scene_voxelized_batch, the branch of .cpp:36-48 per tracker, canvas_cols <= 2048): tracker i clips cloud
         ``scene_index[i]`` (None: i) of ``scenes`` at ``robot_in_local_map[i]`` * the sensor offset into cloud i of ``clipped`` (a
         ``CloudSet.reserved_many`` of >= N clouds of >= canvas_cols points).  Returns the N sizes, or None when asynchronous."""
         if self.param_projector is None:
             raise RuntimeError("SceneClipperProjective2D::compute| Missing Projector")
-        if float(self.param_voxelize_resolution) > 0:
-            raise ValueError("the batched clipper has no voxelised form (voxelize_resolution must be 0)")
         poses = np.ascontiguousarray(robot_in_local_map, np.float32).reshape(-1, 3)
         n = len(poses)
         idx = None if scene_index is None else np.ascontiguousarray(scene_index, np.int32).ravel()
         pr = self.param_projector.struct()
+        vox = float(self.param_voxelize_resolution)
         out = None if self.asynchronous else np.empty(n, np.int32)
-        check(self._ctx._lib.lsm2d_clip_scene_batch(self._ctx.handle, C.byref(pr), scenes.handle, n, None if idx is None else idx.ctypes.data_as(C.c_void_p),
-                                                    poses.ctypes.data_as(C.c_void_p), self._sensor_in_robot.ctypes.data_as(C.c_void_p), clipped.handle,
-                                                    None if out is None else out.ctypes.data_as(C.c_void_p)), "lsm2d_clip_scene_batch", self._ctx.handle)
+        lib = self._ctx._lib
+        head = (self._ctx.handle, C.byref(pr), scenes.handle, n, None if idx is None else idx.ctypes.data_as(C.c_void_p),
+                poses.ctypes.data_as(C.c_void_p), self._sensor_in_robot.ctypes.data_as(C.c_void_p))
+        tail = (clipped.handle, None if out is None else out.ctypes.data_as(C.c_void_p))
+        if vox > 0:
+            check(lib.lsm2d_clip_scene_voxelized_batch(*head, vox, *tail), "lsm2d_clip_scene_voxelized_batch", self._ctx.handle)
+        else:
+            check(lib.lsm2d_clip_scene_batch(*head, *tail), "lsm2d_clip_scene_batch", self._ctx.handle)
         clipped._set_pending()
         return out
 
@@ -1294,7 +1299,7 @@ class TrackerBatch:
 
     def __init__(self, ctx: Context, n_trackers: int, projector: PointNormal2fProjectorPolar, preprocessor: RawDataPreprocessorProjective2D,
                  aligner: MultiAligner2D, angle_min: float, angle_max: float, range_min: float = 0.0, range_max: float = float("inf"),
-                 merge_threshold: float = 0.2, prior_omega=None, map_capacity: int = 50000):
+                 merge_threshold: float = 0.2, prior_omega=None, map_capacity: int = 50000, clip_voxelize_resolution: float = 0.0):
         from . import synth
         if len(aligner.param_slice_processors) != 2:
             raise ValueError("TrackerBatch: the aligner needs two slices (front and rear scan)")
@@ -1307,7 +1312,8 @@ class TrackerBatch:
         self.maps = CloudSet.reserved_many(ctx, self.n, map_capacity)
         self.clipped = CloudSet.reserved_many(ctx, self.n, projector.param_canvas_cols)
         self.scans = [None, None]            # the two scan sets (lsm2d_preprocess_scans once, refilled every step)
-        self.clipper = SceneClipperProjective2D(ctx, projector, voxelize_resolution=0.0, asynchronous=True)
+        # clip_voxelize_resolution > 0: the clipper voxelises what it clipped (the reference class's default is 0.1; the shipped configurations use 0)
+        self.clipper = SceneClipperProjective2D(ctx, projector, voxelize_resolution=float(clip_voxelize_resolution), asynchronous=True)
         self.clipper.setSensorInRobot(self.sensor_in_robot[0])
         self.merger = MergerProjective2D(ctx, projector, merge_threshold, asynchronous=True)
         om = np.diag([100.0, 100.0, 100.0]) if prior_omega is None else prior_omega

@@ -406,9 +406,11 @@ extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr,
 // The per-tracker arguments go to the OUTPUT set's own pinned buffer (acquire_upload_stage: it waits only when the set's previous batch has not
 // been waited for since -- in a tracker step the aligner's wait comes in between), which the kernel reads directly: nothing else is staged, so
 // an asynchronous call leaves nothing behind in the context's staging buffer that a later call could overwrite under it.
-extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector* pr, const lsm2d_cloudset* scenes, int32_t n,
-                                      const int32_t* scene_index, const float* robot_in_local_map, const float sensor_in_robot[3],
-                                      lsm2d_cloudset* clipped, int32_t* out_n) {
+// vox_res > 0: the voxelize_resolution branch (mapping/scene_clipper_projective_2d.cpp:36-48) inside the same launch -- k_clip_vox_batch keeps the clipped
+// cloud in LDS, voxelises it in the SENSOR frame and writes only the voxels, moved to the robot frame
+static int clip_scene_batch_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const lsm2d_cloudset* scenes, int32_t n,
+                                 const int32_t* scene_index, const float* robot_in_local_map, const float sensor_in_robot[3],
+                                 float vox_res, lsm2d_cloudset* clipped, int32_t* out_n) {
   if (!ctx || !pr || !scenes || !robot_in_local_map || !sensor_in_robot || !clipped || n < 1 || scenes == clipped ||
       scenes->ctx != ctx || clipped->ctx != ctx || !clipped->many || clipped->n_clouds < n)
     return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: bad argument (clipped: a reserved-many set of >= n_trackers clouds, not the scenes' set)");
@@ -416,8 +418,12 @@ extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector*
     if (!valid_cloud_index(scenes, scene_index ? scene_index[i] : i)) return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: scene index out of range");
   ProjK P;
   if (!make_projk(*pr, &P)) return fail(ctx, LSM2D_BAD_ARGUMENT, "clip_scene_batch: bad projector");
+  const bool vox = vox_res > 0.0f;
+  if (vox && P.cols > kVoxMax) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: voxelisation takes at most 2048 columns");
   if (clipped->capacity < P.cols) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: clipped clouds smaller than canvas_cols");
   if ((int) (sizeof(u64) * (size_t) P.cols) + 512 > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: canvas does not fit LDS");
+  // (k_clip_vox_batch's LDS is static: points, normals and keys at kVoxMax entries, the canvas aliased onto the keys)
+  if (vox && (int) (3 * sizeof(u64) * (size_t) kVoxMax) + 512 > ctx->max_dyn_lds) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "clip_scene_batch: the voxelising workgroup does not fit LDS");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   { const int rc0 = flush_pending(scenes); if (rc0) return rc0; }
   HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
@@ -443,11 +449,17 @@ extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector*
     A.out_count = (int32_t*) L.h_stage_dev;
     for (int i = 0; i < n; ++i) h_out[i] = kStatusNotWritten;
   }
-  hipLaunchKernelGGL(k_clip_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * (size_t) P.cols, ctx->stream, A);
+  if (vox) {
+    ClipVoxBatchArgs V; V.c = A;
+    V.inv_rx = 1.0f / vox_res; V.inv_rn = 1.0f / 0.1f;      // coefficients (res, res, 0.1, 0.1): scene_clipper_projective_2d.cpp:46
+    hipLaunchKernelGGL(k_clip_vox_batch, dim3((unsigned) n), dim3(kVoxBlock), 0, ctx->stream, V);
+  } else {
+    hipLaunchKernelGGL(k_clip_batch, dim3((unsigned) n), dim3(kFindBlock), sizeof(u64) * (size_t) P.cols, ctx->stream, A);
+  }
   HIPCHK(ctx, hipGetLastError());
   clipped->staged_epoch = ctx->sync_epoch;
   ctx->have_timing = false;
-  if (!out_n) {                               // at most one point per column
+  if (!out_n) {                               // at most one point per column (a voxelised cloud never grows)
     for (int i = 0; i < n; ++i) { clipped->total += (int64_t) P.cols - clipped->h_count[i]; clipped->h_count[i] = P.cols; }
     clipped->count_pending = true;
     return LSM2D_SUCCESS;
@@ -456,6 +468,18 @@ extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector*
   // (exact sizes now for clouds 0 .. n; a set whose other clouds' sizes were pending stays pending: their numbers are still upper bounds)
   for (int i = 0; i < n; ++i) { clipped->total += (int64_t) h_out[i] - clipped->h_count[i]; clipped->h_count[i] = h_out[i]; out_n[i] = h_out[i]; }
   return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_clip_scene_batch(lsm2d_context* ctx, const lsm2d_projector* pr, const lsm2d_cloudset* scenes, int32_t n,
+                                      const int32_t* scene_index, const float* robot_in_local_map, const float sensor_in_robot[3],
+                                      lsm2d_cloudset* clipped, int32_t* out_n) {
+  return clip_scene_batch_impl(ctx, pr, scenes, n, scene_index, robot_in_local_map, sensor_in_robot, 0.0f, clipped, out_n);
+}
+// voxelize_resolution <= 0: lsm2d_clip_scene_batch itself
+extern "C" int lsm2d_clip_scene_voxelized_batch(lsm2d_context* ctx, const lsm2d_projector* pr, const lsm2d_cloudset* scenes, int32_t n,
+                                                const int32_t* scene_index, const float* robot_in_local_map, const float sensor_in_robot[3],
+                                                float voxelize_resolution, lsm2d_cloudset* clipped, int32_t* out_n) {
+  return clip_scene_batch_impl(ctx, pr, scenes, n, scene_index, robot_in_local_map, sensor_in_robot, voxelize_resolution, clipped, out_n);
 }
 
 extern "C" int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector* pr, lsm2d_cloudset* scenes, int32_t n,

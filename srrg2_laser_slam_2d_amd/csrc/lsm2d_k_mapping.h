@@ -46,7 +46,11 @@ __global__ __launch_bounds__(kFindBlock) void k_clip_emit(const ClipEmitArgs A);
 // n_dev: when non-null the scene's size is only known on the device (its set was last written by an asynchronous clip / merge)
 struct ClipSmallArgs { const float2* xy; const float2* nrm; int32_t n; const int32_t* n_dev; ProjK proj; ClipEmitArgs emit; };
 
-LSM2D_DEV void clip_emit_body(const ClipEmitArgs& A, const u64* canvas, int* s_tot /* [2][kFindBlock / 64] */, int tid) {
+// the compaction of the filled cells, ascending column: put(pos, src, x, y, nx, ny) once per filled cell, the point moved by A.T and, unless
+// A.s_identity, by A.S.  Every thread of the kFindBlock workgroup calls it (one barrier per kFindBlock columns); returns the number of
+// filled cells, the same value in every thread.  The destination is the caller's: global rows (clip_emit_body) or LDS (k_clip_vox_batch).
+template <typename Put>
+LSM2D_DEV int clip_compact_cells(const ClipEmitArgs& A, const u64* canvas, int* s_tot /* [2][kFindBlock / 64] */, int tid, Put put) {
   int base = 0, parity = 0;
   for (int c0 = 0; c0 < A.cols; c0 += kFindBlock, parity ^= 1) {
     const int col = c0 + tid;
@@ -63,10 +67,17 @@ LSM2D_DEV void clip_emit_body(const ClipEmitArgs& A, const u64* canvas, int* s_t
         xf_point(A.S, x, y, tx, ty); xf_normal(A.S, nx, ny, tnx, tny);
         x = tx; y = ty; nx = tnx; ny = tny;
       }
-      A.out_xy[pos] = make_float2(x, y); A.out_nrm[pos] = make_float2(nx, ny);
-      if (A.out_src) A.out_src[pos] = src;
+      put(pos, src, x, y, nx, ny);
     }
   }
+  return base;
+}
+
+LSM2D_DEV void clip_emit_body(const ClipEmitArgs& A, const u64* canvas, int* s_tot /* [2][kFindBlock / 64] */, int tid) {
+  const int base = clip_compact_cells(A, canvas, s_tot, tid, [&](int pos, int src, float x, float y, float nx, float ny) {
+    A.out_xy[pos] = make_float2(x, y); A.out_nrm[pos] = make_float2(nx, ny);
+    if (A.out_src) A.out_src[pos] = src;
+  });
   if (A.host_polls) {      // the count goes last, behind every thread's system-scope release of its rows: the synchronous form's host side polls it
     __threadfence_system();
     __syncthreads();
@@ -512,6 +523,54 @@ __global__ __launch_bounds__(kFindBlock) void k_clip_batch(const ClipBatchArgs A
   E.out_xy = A.out_xy + (size_t) t * A.out_stride; E.out_nrm = A.out_nrm + (size_t) t * A.out_stride; E.out_src = nullptr;
   E.out_count_dev = A.out_count_dev + t; E.out_count = A.host_polls ? A.out_count + t : A.out_count_dev + t; E.host_polls = A.host_polls;
   clip_emit_body(E, can, s_tot, tid);
+}
+
+// the same with the clipper's voxelize_resolution > 0 branch (lsm2d_clip_scene_voxelized_batch; mapping/scene_clipper_projective_2d.cpp:36-48): what the
+// single call does in two launches (k_clip_small, k_voxelize_clipped) with the clipped cloud going through global memory in between happens here in ONE
+// workgroup's LDS -- the filled cells are compacted in the SENSOR frame straight into s_q / s_n (clip_compact_cells with s_identity = 1, the positions
+// k_clip_small writes its rows to), voxelize_lds runs on them with coefficients (res, res, 0.1, 0.1), and only the voxels go out, moved to the robot frame by S.
+// The same device bodies in the same order as the two kernels: the same bits.
+// LDS: s_q, s_n, s_key at kVoxMax entries (48 KB) + s_tot, all static.  The canvas (cols <= kVoxMax cells of 8 B: the host refuses more) is ALIASED onto s_key:
+// it is dead once the compaction has passed the barrier behind it, and voxelize_lds writes its first key only after that barrier.
+// Every thread reaches every barrier and the count store on every path (k = 0 included); no workgroup waits for another.
+struct ClipVoxBatchArgs { ClipBatchArgs c; float inv_rx, inv_rn; };
+__global__ __launch_bounds__(kVoxBlock) void k_clip_vox_batch(const ClipVoxBatchArgs V) {
+  static_assert(kVoxBlock == kFindBlock, "project_cloud / clip_compact_cells and voxelize_lds share one workgroup");
+  __shared__ float2 s_q[kVoxMax];
+  __shared__ float2 s_n[kVoxMax];
+  __shared__ u64 s_key[kVoxMax];
+  __shared__ int s_tot[2 * (kVoxBlock / 64)];
+  const ClipBatchArgs& A = V.c;
+  u64* can = s_key;
+  const int tid = threadIdx.x, t = blockIdx.x;
+  const ClipBatchItem it = A.items[t];
+  for (int i = tid; i < A.proj.cols; i += kFindBlock) can[i] = kEmptyCell;
+  __syncthreads();
+  const int n = it.n >= 0 ? it.n : A.scene_count_dev[it.si];
+  project_cloud(A.xy + it.start, n, it.T, A.proj, can, tid, kFindBlock);
+  __syncthreads();
+  ClipEmitArgs E;
+  E.gcanvas = nullptr; E.cols = A.proj.cols; E.xy = A.xy + it.start; E.nrm = A.nrm + it.start;
+  E.T = it.T; E.S = A.S; E.s_identity = 1;                       // voxelisation happens in the sensor frame
+  E.out_xy = nullptr; E.out_nrm = nullptr; E.out_src = nullptr; E.out_count_dev = nullptr; E.out_count = nullptr; E.host_polls = 0;
+  const int k = clip_compact_cells(E, can, s_tot, tid, [&](int pos, int, float x, float y, float nx, float ny) {
+    s_q[pos] = make_float2(x, y); s_n[pos] = make_float2(nx, ny);
+  });
+  __syncthreads();                                               // the points are staged; the canvas is dead: its cells become the sort's keys
+  float2* oxy = A.out_xy + (size_t) t * A.out_stride; float2* onr = A.out_nrm + (size_t) t * A.out_stride;
+  const int nv = voxelize_lds<kVoxBlock>(s_q, s_n, s_key, k, V.inv_rx, V.inv_rn, s_tot, tid, [&](int pos, float x, float y, float nx, float ny) {
+    if (!A.s_identity) {
+      float tx, ty, tnx, tny;
+      xf_point(A.S, x, y, tx, ty); xf_normal(A.S, nx, ny, tnx, tny);
+      x = tx; y = ty; nx = tnx; ny = tny;
+    }
+    oxy[pos] = make_float2(x, y); onr[pos] = make_float2(nx, ny);
+  });
+  if (A.host_polls) {      // the count goes last, behind every thread's system-scope release of its rows (k_voxelize_clipped's protocol)
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) { A.out_count_dev[t] = nv; __hip_atomic_store(A.out_count + t, nv, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+  } else if (tid == 0) A.out_count_dev[t] = nv;
 }
 
 // per (tracker, measurement): measurement_in_scene^-1 and measurement_in_scene; the measurement cloud's first point and size (-1: its set's d_count[mc])

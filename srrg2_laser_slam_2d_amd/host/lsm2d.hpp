@@ -10,7 +10,7 @@
 //   LaserMessageBatchStream            batches of fresh LaserMessages through preprocessor + aligner, pipelined over three scan sets
 //       (lsm2d_preprocess_scans_refill, lsm2d_align_batch_begin / _wait)
 //   TrackerBatch                       N independent live trackers stepped together: one batched clip, align and merge per step
-//       (lsm2d_clip_scene_batch, lsm2d_align_batch, lsm2d_merge_scene_batch), each tracker's bits those of the single-tracker calls
+//       (lsm2d_clip_scene_batch or, with Params::clip_voxelize_resolution > 0, lsm2d_clip_scene_voxelized_batch; lsm2d_align_batch, lsm2d_merge_scene_batch), each tracker's bits those of the single-tracker calls
 // This header depends on nothing but the C ABI and the standard library, so it compiles with plain g++;
 // the SRRG-side adapter (adapters/srrg/) is the same code expressed with srrg2_core types.
 #pragma once
@@ -764,6 +764,7 @@ class TrackerBatch {
     std::array<float, 9> prior_omega{{100, 0, 0, 0, 100, 0, 0, 0, 100}};
     float merge_threshold = 0.2f;
     int64_t map_capacity = 50000;
+    float clip_voxelize_resolution = 0.0f;               // > 0: the clipper voxelises what it clipped (scene_clipper_projective_2d.cpp:36-48; the class default is 0.1)
   };
   TrackerBatch(Context& ctx, int32_t n_trackers, const Params& p) : _ctx(ctx), _n(n_trackers), _p(p), _est((size_t) n_trackers * 3, 0.0),
                                                                        _prior((size_t) n_trackers), _x((size_t) n_trackers * 3), _H((size_t) n_trackers * 9),
@@ -798,7 +799,11 @@ class TrackerBatch {
     }
     std::vector<float> guess((size_t) _n * 3), x0((size_t) _n * 3, 0.0f), mis((size_t) _n * 6);
     for (int32_t i = 0; i < _n; ++i) { double g[3]; compose(&_est[(size_t) i * 3], odometry + 3 * i, g); for (int c = 0; c < 3; ++c) guess[(size_t) i * 3 + c] = (float) g[c]; }
-    check(lsm2d_clip_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, guess.data(), _p.slices[0].sensor_in_robot, _clipped, nullptr), "lsm2d_clip_scene_batch", _ctx.get());
+    if (_p.clip_voxelize_resolution > 0.0f)
+      check(lsm2d_clip_scene_voxelized_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, guess.data(), _p.slices[0].sensor_in_robot, _p.clip_voxelize_resolution, _clipped, nullptr),
+            "lsm2d_clip_scene_voxelized_batch", _ctx.get());
+    else
+      check(lsm2d_clip_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, guess.data(), _p.slices[0].sensor_in_robot, _clipped, nullptr), "lsm2d_clip_scene_batch", _ctx.get());
     const lsm2d_cloudset* fixed[2] = {_scans[0], _scans[1]}; const lsm2d_cloudset* moving[2] = {_clipped, _clipped};
     lsm2d_batch b{};
     b.n_alignments = _n; b.n_slices = 2; b.slices = _p.slices.data(); b.fixed = fixed; b.moving = moving; b.init_pose = x0.data(); b.prior = _prior.data();
@@ -819,7 +824,10 @@ class TrackerBatch {
  private:
   static void compose(const double a[3], const double b[3], double o[3]) {
     const double c = std::cos(a[2]), s = std::sin(a[2]);
-    o[0] = a[0] + c * b[0] - s * b[1]; o[1] = a[1] + s * b[0] + c * b[1]; o[2] = a[2] + b[2];
+    // the angle is brought back into [-pi, pi) with the operations of api.TrackerBatch's composition (synth.compose_poses: a floored modulo), so that
+    // both classes hand the same float32 guesses and sensor poses to the library
+    double th = std::fmod(a[2] + b[2] + M_PI, 2.0 * M_PI); if (th < 0.0) th += 2.0 * M_PI;
+    o[0] = a[0] + c * b[0] - s * b[1]; o[1] = a[1] + s * b[0] + c * b[1]; o[2] = th - M_PI;
   }
   static void inverse(const double a[3], double o[3]) {
     const double c = std::cos(a[2]), s = std::sin(a[2]);
