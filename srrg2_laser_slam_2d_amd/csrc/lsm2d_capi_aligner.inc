@@ -768,7 +768,7 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
     if (const char* dump = getenv("LSM2D_DUMP_STAMPS")) {      // diagnostics: one line per stamped workgroup (tools/occupancy_probe.py reads them)
       if (FILE* f = fopen(dump, "a")) {
         unsigned long long t0 = ~0ull; for (int i = 0; i < n_clock; ++i) if (ck[4 * i + 1] > 0 && ck[4 * i + 2] < t0) t0 = ck[4 * i + 2];
-        fprintf(f, "# launch n=%d stride=%d\n", n, clock_stride);
+        fprintf(f, "# launch n=%d stride=%d t0=%llu\n", n, clock_stride, t0);      // (t0: what the third column is relative to)
         for (int i = 0; i < n_clock; ++i)
           fprintf(f, "%d %llu %llu %llu 0x%llx\n", i * clock_stride, ck[4 * i], ck[4 * i + 1], ck[4 * i + 2] - t0, ck[4 * i + 3]);
         fclose(f);

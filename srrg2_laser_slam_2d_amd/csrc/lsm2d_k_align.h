@@ -90,6 +90,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ unsigned long long s_ph[4];
   if (tid == 0) { s_ph[0] = s_ph[1] = s_ph[2] = 0; s_ph[3] = __builtin_amdgcn_s_memtime(); }
 #define LSM2D_PH_STAMP(k) do { if (tid == 0) { const unsigned long long now__ = __builtin_amdgcn_s_memtime(); s_ph[k] += now__ - s_ph[3]; s_ph[3] = now__; } } while (0)
+#define LSM2D_PH_SKIP() do { if (tid == 0) s_ph[3] = __builtin_amdgcn_s_memtime(); } while (0)      // what went before belongs to no bucket
   // -DLSM2D_PHASE_PROBE=1 (or empty): the three buckets above.  =2: unit lists + stream | bin walk + reduction | solve + the rest.  =3: unit lists | stream | everything else.  =4: bin walk + wave sums | everything else | wave 0's stretch (a single slice).
 #if LSM2D_PHASE_PROBE + 0 == 2
 #define LSM2D_PH(k) LSM2D_PH_STAMP((k) == 0 ? 1 : (k))
@@ -105,6 +106,16 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #define LSM2D_PH_STREAM() LSM2D_PH_STAMP(1)
 #define LSM2D_PH_SUMS() LSM2D_PH_STAMP(0)
 #define LSM2D_PH_TAIL() LSM2D_PH_STAMP(2)
+#elif LSM2D_PHASE_PROBE + 0 == 5      // k_align_cand: the unit list's stream in an iteration that builds no list | the build iteration's stream (blockers included) | a list-served gather; the remainder of the lifetime is everything else
+#define LSM2D_PH(k) do { } while (0)
+#define LSM2D_PH_LISTS() LSM2D_PH_SKIP()
+#define LSM2D_PH_STREAM() do { } while (0)
+#define LSM2D_PH_CAND(k) do { if ((k) >= 0 && (k) <= 2) LSM2D_PH_STAMP((k) & 3); else LSM2D_PH_SKIP(); } while (0)
+#elif LSM2D_PHASE_PROBE + 0 == 6      // k_align_cand: a blockers pass of its own (none since round 22) | the collect pass | unit-list rebuilds
+#define LSM2D_PH(k) do { } while (0)
+#define LSM2D_PH_LISTS() LSM2D_PH_STAMP(2)
+#define LSM2D_PH_STREAM() do { } while (0)
+#define LSM2D_PH_CAND(k) do { if ((k) == 3) LSM2D_PH_STAMP(0); else if ((k) == 4) LSM2D_PH_STAMP(1); else LSM2D_PH_SKIP(); } while (0)
 #else
 #define LSM2D_PH(k) LSM2D_PH_STAMP(k)
 #define LSM2D_PH_LISTS() do { } while (0)
@@ -118,6 +129,9 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #ifndef LSM2D_PH_SUMS
 #define LSM2D_PH_SUMS() do { } while (0)
 #define LSM2D_PH_TAIL() do { } while (0)
+#endif
+#ifndef LSM2D_PH_CAND      // the candidate lists' sections (modes 5 and 6; tools/phase_probe.py --lists): -1 a section begins, 0 / 1 / 2 a plain stream, a build iteration's stream, a gather ends, 3 / 4 a blockers pass, a collect pass ends
+#define LSM2D_PH_CAND(k) do { } while (0)
 #endif
   if (A.wg_place && tid == 0) A.wg_place[blockIdx.x] = place_key();
   const bool stamp = A.clock_out && tid == 0 && a % A.clock_stride == 0;
@@ -377,12 +391,14 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             const int B = cull_block_steps(Tm, nbs), nb = (Tm + B - 1) / B;
             // Round 20: what wave 0 decided about the slice's candidate list when it prepared this iteration (s_cand_state; a single slice: s == 0)
             const int cst = kCand ? __builtin_amdgcn_readfirstlane(s_cand_state) : 0;      // (stays 0 where the launch has no room for lists)
+            LSM2D_PH_CAND(-1);
             if (kCand && cst == 1) {      // the list serves this transform: its points alone -- the unit list is neither rebuilt (s_rebuild is 0: wave 0 saw to that) nor read
               const float2* mxy = S.moving.xy + S.moving.start[mc];
               const uint32_t* cand = reinterpret_cast<const uint32_t*>(smem + __builtin_amdgcn_readfirstlane(s_cand_par[0])) + cand_blocker_words(S.proj.cols);
               const int n_cand = __builtin_amdgcn_readfirstlane(s_cand_n);
               if (S.proj.tiny_ok) project_candidates_t<false, kW>(mxy, T, S.proj, mcan, tid, cand, n_cand);
               else project_candidates_t<true, kW>(mxy, T, S.proj, mcan, tid, cand, n_cand);
+              LSM2D_PH_CAND(2);
             } else {
             if (__builtin_amdgcn_readfirstlane(s_rebuild[s])) {
               typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -443,12 +459,21 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
             }
             LSM2D_PH_LISTS();
             const int n_units = __builtin_amdgcn_readfirstlane(s_nunits[s]);
-            if (n_units > 0) project_cloud_list<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B);
             if (kCand && cst == 2) {
-              // Build, behind the stream: (a) every column's blocker, (b) the unit list's points once more, against the rule (lsm2d_device.h); wave 0 looks at the
-              // count behind the sums' barrier (too long: not used, the alignment goes on streaming units)
+              // Build: (a) every column's blocker, made by the stream itself from the r, th, u and column it has just computed for the canvas (the blockers
+              // cleared in front of it); (b) behind it, the unit list's points once more, against the rule (lsm2d_device.h); wave 0 looks at the count behind
+              // the sums' barrier (too long: not used, the alignment goes on streaming units)
               uint32_t* blk = reinterpret_cast<uint32_t*>(smem + __builtin_amdgcn_readfirstlane(s_cand_par[0]));
-              cand_build<kW, kAlignBlock>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, tid, units, n_units, B, blk, s_cand_par, &s_cand_n);
+              cand_clear_blockers<kW>(S.proj, tid, blk);
+              __syncthreads();
+              if (n_units > 0) project_cloud_list_blk<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B, blk, s_cand_par);
+              __syncthreads();
+              LSM2D_PH_CAND(1);
+              cand_collect<kW, kAlignBlock>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, tid, units, n_units, B, blk, s_cand_par, &s_cand_n);
+              LSM2D_PH_CAND(4);
+            } else {
+              if (n_units > 0) project_cloud_list<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B);
+              LSM2D_PH_CAND(0);
             }
             }
           }
@@ -811,7 +836,10 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
 #ifdef LSM2D_DEBUG_UNITS      // diagnostics build: the culled stream's list length and whether it was rebuilt, in place of the outlier statistics
         if (kProjCulled) { n_out = s_nunits[0]; chi_o = (float) s_rebuild[0]; }
 #endif
-        const u64 dg = s_dig;
+        u64 dg = s_dig;
+#ifdef LSM2D_DEBUG_CAND      // diagnostics build: what the iteration did about the candidate list (s_cand_state) and the list's entries, in place of the pair digest
+        if (kCand) dg = ((u64) (unsigned) s_cand_n << 32) | (u64) (unsigned) s_cand_state;
+#endif
         const int w = ln == 0 ? n_corr : ln == 1 ? n_in : ln == 2 ? n_out : ln == 3 ? __float_as_int(chi_in) : ln == 4 ? __float_as_int(chi_o) : ln == 5 ? (int) (uint32_t) dg : (int) (uint32_t) (dg >> 32);
         if (ln < 7) reinterpret_cast<int32_t*>(A.out_stats + (size_t) a * A.stats_stride + it)[ln] = w;
       }
@@ -963,6 +991,12 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
         if (ln < kSumWords) s_sum[ln] = __int_as_float(zi);
         if (ln == 0) s_dig = (u64) (unsigned) zi;
         if (A.out_last_pose && ln < 3) A.out_last_pose[3 * a + ln] = ln == 0 ? np0 : (ln == 1 ? np1 : np2);
+      } else if (kCand && ln == 0 && s_cand_par[0] > 0) {
+        // The alignment ends with this iteration.  If it built a list, the build is booked all the same, behind the iteration that made its blockers (as
+        // arithmetic, like the books above: no select on a condition code)
+        int built = s_cand_state == 2 ? 1 : 0, over = s_cand_n > s_cand_par[1] ? 1 : 0;
+        asm volatile("" : "+v"(built), "+v"(over));
+        s_cand_stat += (built << 16) + ((built & over) << 24);
       }
     }
     LSM2D_PH(2);

@@ -5,7 +5,10 @@ With --full-length (role A, projective; LSM2D_EXTRA_HIPCC_FLAGS="-DLSM2D_PHASE_P
 fast-forward's filled-in statistics rows marked): only the alignments of the headline batch that EXECUTE every iteration -- the ones the launch waits for behind the
 fast-forward -- first inside the whole batch, then by themselves, one workgroup per otherwise empty CU: what one of their iterations costs there, stream and the rest.
 Built with -DLSM2D_PHASE_PROBE=4 instead (pass --mode4: the library cannot say how it was built) the buckets are bin walk + wave sums | wave 0's stretch behind the sums'
-barrier | everything else, and the lone workgroups are measured once more with want_stats=False: the launch bench.py times writes no statistics rows and no digest."""
+barrier | everything else, and the lone workgroups are measured once more with want_stats=False: the launch bench.py times writes no statistics rows and no digest.
+With --lists5 / --lists6 (LSM2D_EXTRA_HIPCC_FLAGS="-DLSM2D_PHASE_PROBE=5 -DLSM2D_DEBUG_UNITS -DLSM2D_DEBUG_CAND", or =6) the same alignments get the candidate lists'
+columns: cycles in the unit list's plain stream | the build iteration's stream | a list-served gather (5), in a blockers pass of its own | the collect pass | unit-list
+rebuilds (6), each in all and per iteration of its kind, what is in none of them, and the entries of every list built -- inside the whole batch and alone on a CU."""
 import math, os, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +21,10 @@ if FULL_LENGTH:
 MODE4 = "--mode4" in sys.argv
 if MODE4:
     sys.argv.remove("--mode4")
+LISTS = 0      # --lists5 / --lists6: the candidate lists' columns, library built with -DLSM2D_PHASE_PROBE=5 (or 6) -DLSM2D_DEBUG_UNITS -DLSM2D_DEBUG_CAND
+for m in (5, 6):
+    if "--lists%d" % m in sys.argv:
+        sys.argv.remove("--lists%d" % m); LISTS = m; FULL_LENGTH = True
 role, kind = (sys.argv + (["A", "projective"] if FULL_LENGTH else ["B", "distmap"]))[1:3]
 ctx = api.Context(0, kernel_timing=True); ctx.set_option("clock_stride", 1)
 for kv in filter(None, os.environ.get("LSM2D_BENCH_OPTIONS", "").split(",")):
@@ -37,6 +44,48 @@ def stamped(n):      # the last launch's stamps: [n] x (lifetime, first bucket, 
     rows = [l.split() for l in open(dump) if not l.startswith("#")][-n:]
     a = np.array([[int(v) for v in r[1:3]] + [int(r[4], 16)] for r in rows], dtype=np.float64)
     return a[:, 0], a[:, 1], a[:, 2]
+def stamped_abs(n):      # the same with all three buckets as they were stamped (the dump's header line carries what the third column is relative to)
+    lines = open(dump).read().split("\n")
+    t0 = [int(l.split("t0=")[1]) for l in lines if l.startswith("# launch") and "t0=" in l][-1]
+    rows = [l.split() for l in lines if l and not l.startswith("#")][-n:]
+    a = np.array([[int(r[1]), int(r[2]), (int(r[3]) + t0) % 2 ** 64, int(r[4], 16)] for r in rows], dtype=np.float64)      # (exact integers: the dump's difference may have wrapped)
+    return a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+if LISTS:
+    # The candidate lists' columns: per iteration of bench.py's full-length alignments, cycles of thread 0 in the unit list's stream, in the build iteration's
+    # stream, in a blockers pass of its own, in the collect pass, in a list-served gather, in unit-list rebuilds and in everything else; entries per list.
+    # Mode 5 stamps plain stream | build iteration's stream | gather, mode 6 blockers pass | collect pass | unit-list rebuilds: two builds, two runs.
+    its = 20
+    names = {5: ("plain stream", "build iteration's stream", "gather"), 6: ("blockers pass", "collect pass", "unit-list rebuilds")}[LISTS]
+    ctx.set_option("align_path", 1); ctx.set_option("zero_copy_max", 0)
+    def report(label, res, idx, n):
+        life, b0, b1, b2 = stamped_abs(n)
+        state = res.stats["pair_digest_lo"].astype(np.int64); entries = res.stats["pair_digest_hi"].astype(np.int64)
+        for j, i in enumerate(idx):
+            ran = int(res.iterations[i]) if res.iterations[i] <= its else its
+            st = state[i, :ran]
+            n_plain, n_build, n_served = int((st == 0).sum()), int((st == 2).sum()), int((st == 1).sum())
+            per = {5: (n_plain, n_build, n_served), 6: (n_build, n_build, ran)}[LISTS]
+            cells = ["%s %.0f cyc in all, %d iterations, %.0f each" % (nm, b[i], k, b[i] / max(k, 1)) for nm, b, k in zip(names, (b0, b1, b2), per)]
+            print("  %s: alignment %d: lifetime %.0f cyc over %d iterations (%d plain, %d build, %d served); %s; everything else in this mode %.0f; entries per list %s (state per iteration %s)"
+                  % (label, idx_names[j], life[i], ran, n_plain, n_build, n_served, "; ".join(cells), life[i] - b0[i] - b1[i] - b2[i],
+                     entries[i, :ran][st == 2].tolist(), "".join(str(int(v)) for v in st)))
+    for _ in range(3):
+        r = al.compute_batch([scans], [mp], x0, want_stats=True)
+    executed = ((np.arange(r.stats.shape[1])[None, :] < r.iterations[:, None]) & ~(r.stats["chi_outliers"] < 0)).sum(1)
+    full = np.flatnonzero(executed == its)
+    life = stamped_abs(len(x0))[0]
+    print("mode %d, fast_forward %d, cand_lists %d: kernel %.3f ms; alignments that execute all %d iterations: %s; lifetime of all: median %.0f cyc, max %.0f cyc; lists built %d, iterations served %d"
+          % (LISTS, ctx.get_option("fast_forward"), ctx.get_option("cand_lists"), r.kernel_ms, its, full.tolist(), np.median(life), life.max(), ctx.get_option("last_cand_builds"), ctx.get_option("last_cand_iterations")))
+    idx_names = full.tolist()
+    report("inside the whole batch", r, full.tolist(), len(x0))
+    sub = api.CloudSet(ctx, np.concatenate([wl.scan_points[wl.scan_offsets[i]:wl.scan_offsets[i + 1]] for i in full]),
+                       np.concatenate([[0], np.cumsum([wl.scan_offsets[i + 1] - wl.scan_offsets[i] for i in full])]).astype(np.int32))
+    for _ in range(3):
+        r1 = al.compute_batch([sub], [mp], x0[full], want_stats=True)
+    assert np.array_equal(r1.pose.view(np.uint32), r.pose[full].view(np.uint32)) and np.all(r1.iterations == its)
+    report("alone, a CU each", r1, list(range(len(full))), len(full))
+    os.remove(dump)
+    sys.exit(0)
 if FULL_LENGTH:
     its = al.param_max_iterations if hasattr(al, "param_max_iterations") else 20
     ctx.set_option("align_path", 1); ctx.set_option("zero_copy_max", 0)      # k_align, results by copies, whatever the batch size
