@@ -425,247 +425,7 @@ LSM2D_DEV void project_cloud_list(const float4* __restrict__ lane_xy, int T_step
   else project_cloud_list_t<true, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B);
 }
 
-// ---- Round 20: CANDIDATE lists -- the second, tighter level of the kept lists ----------------------------------------------------------------
-// Once the pose has settled an iteration still streams the whole unit list (some 41 k points on configs[1]) to keep one winner per column.  A candidate list,
-// built in an iteration that has just streamed its unit list at the slice transform T0, holds the INDICES of the streamed points that can still be, or beat, a
-// winner under any transform T near T0; while it is valid the iteration gathers those points alone (project_candidates).  The moving canvas such an iteration
-// makes equals the unit list's canvas at T cell for cell -- the unit list's own proof (chunk_may_matter) carries the rest: every pair, sum and pose keeps its bits.
-//
-// What "near" means.  T applies M = [[c, -s], [s, c]] with the fp32 outputs of sincos_fixed (abs error 9.3e-8 each: M is a rotation scaled by rho, |rho - 1| <=
-// 1.4e-7), so in exact arithmetic q_T = A q_0 + d with A = M_T M_0^-1 a rotation by dth = atan2(sd, cd) scaled by kappa, |kappa - 1| <= 2.8e-7, and d = t_T - A t_0:
-// cd, sd, dx, dy are the quantities begin_iteration forms for s_rebuild.  The list serves every T with |d| <= m_t and |dth| <= 1.001 m_th; k_align's validity
-// test leaves room for what its own fp32 evaluation of cd, sd, d can be off by (cand_pose_within).  Where T and T0 have the SAME rotation bits A is the identity
-// and d = t_T - t_0, one subtraction of two nearby floats: nothing to allow for.  Otherwise: the factor 1 / rho_0^2 the expression leaves out, 2.8e-7 |t_0|; the
-// roundings of cd (two products of at most 3e-8 and a sum of 6e-8) and sd (6e-8), 1.4e-7 |t_0| together; the roundings of the two products and the sum per
-// component, 1.7e-7 |t_0|_1: 4e-7 (|t_0|_1 + |t_T|_1) covers them; 3e-7 on |sd|; asin(x) <= 1.0005 x for x <= 0.05, the largest margin the option table admits.
-//
-// Depth.  The stream computes qx = fl(c px + a), a = fl(-s py + tx) (and qy alike): each rounding is at most 6e-8 of its result, |a| <= |py| + |t| and |q| = r, so
-// the computed q is within eq = 6e-8 (|p| + |t| + 1.42 r) of M p + t; a point at depth r has |p| <= (r + |t|) / rho, hence eq <= eq(r) = 1.5e-7 r + 1.25e-7 |t|_1: a
-// bound from the depth alone, which a column's winner carries in its key.  r2 = fma(qx, qx, qy qy) and r = sqrt_rn(r2) add 1.2e-7 r.  Exactly, | |q_T| - |q_0| | <=
-// |kappa - 1| |q_0| + |d|.  So the depths the stream computes for ONE point under T0 and under any served T differ by at most
-//   md(r) = m_t + 2 eq(r) + (2 x 1.2e-7 + 2.8e-7) r  <=  m_t + 1.0e-6 r + 2.6e-7 (|t|_1 + 2 m_t) + 1e-7      (cand_depth_margin; |t_T|_1 <= |t_0|_1 + 2 m_t)
-// with 1.8e-7 r to spare for the two roundings (6e-8 r each) of the comparison that uses it.
-// Column.  The bearing of A q_0 is that of q_0 plus dth; adding d turns it by at most asin(|d| / (|q_0| - |d|)); the computed q is off by eq on either side, i.e.
-// by eq / r of bearing each; bearing()'s polynomial (5e-8 rad), its octant fix-ups (three roundings of at most 1.2e-7 rad) and the rounding of u = fma(K00, th,
-// K01) (half an ulp of 16 384: 4.9e-4 columns) add at most 1.3e-3 columns per evaluation at up to 16 384 columns (the host offers no list to a wider canvas).
-// With asin(x) <= 1.048 x on [0, 1/2] the computed u of one point under T0 and under a served T differ by at most
-//   cs(r) = K00 (1.001 m_th + 1.06 md / (r - md)) + 4e-3   columns, claimed only where md <= r / 4      (cand_classify; md >= m_t + 2 eq covers the numerator)
-// -- unless the bearing WRAPS between -pi and pi: a point within cs of either end makes no claim.
-// The rule.  Call a streamed point INTERIOR when, at T0, its depth is inside [rmin, rmax] by more than md and its u is farther than cs from both edges of a valid
-// column: under every served T it passes the gates and falls into that same column.  A column's BLOCKER is the nearest of its interior points (project_point_stream_blk:
-// the minimum of r + md(r) per column, an array of its own -- not the canvas's winner: along a wall seen at an angle the nearest point of a column sits at the
-// column's edge, and on configs[1] a quarter of the winners are no interior points).  A streamed point p is DROPPED when it cannot pass the gates under any served
-// T -- coordinates that are not finite (padding slots), a depth beyond a range gate by more than md, a column beyond either end of the canvas by more than cs -- or
-// when it is interior and its column's blocker b has r_b + md(r_b) < r_p - md(r_p): under every served T both are in the column and b is strictly nearer, so p is
-// not the winner; b itself is in the list (the inequality fails for b against itself, and for every interior point at most as deep -- an interior winner among
-// them).  Everything else is kept: points near a column edge or a range gate (from either side), points just outside the field of view, the points of a column
-// without a blocker, every winner.  Keeping a point that could have gone is always harmless.
-LSM2D_DEV float cand_depth_margin(float r, float m_t, float tn2 /* |tx| + |ty| + 2 m_t */) { return m_t + __builtin_fmaf(1.0e-6f, r, __builtin_fmaf(2.6e-7f, tn2, 1e-7f)); }
-// 0: p passes the gates under no served transform; 1: no claim; 2: interior (column `col`, depth r, margin md) under every served transform.  ONE statement of the
-// rule in two steps: from the point to what the stream makes of it (r, th, u, col: project_point_stream's operations, one for one), and from there to the class.
-// The build iteration's stream (project_point_stream_blk) enters at the second step with the r, th, u and col it has just made for the canvas.
-LSM2D_DEV int cand_classify_polar(const ProjK& P, float r, float th, float u, int col /* v_cvt_flr_i32_f32 of u */, float m_t, float m_th, float tn2, float& md) {
-  md = cand_depth_margin(r, m_t, tn2);
-  if (r < P.rmin - md || r > P.rmax + md) return 0;
-  if (!(md <= 0.25f * r)) return 1;
-  const float aK = __builtin_fabsf(P.K00);
-  const float cs = __builtin_fmaf(aK, __builtin_fmaf(1.06f, md / (r - md), 1.001f * m_th), 4e-3f);
-  if ((3.14159274101257324f - __builtin_fabsf(th)) * aK <= cs) return 1;      // the bearing may wrap
-  if (u < -cs || u > P.colsf + cs) return 0;
-  if ((unsigned) col >= (unsigned) P.cols) return 1;
-  if (!(r >= P.rmin + md && r <= P.rmax - md)) return 1;
-  const float f = u - (float) col;      // (exact: u and its floor are within one of each other)
-  return (f > cs && 1.0f - f > cs) ? 2 : 1;
-}
-template <bool kGuarded>
-LSM2D_DEV int cand_classify(const Iso& T, const ProjK& P, float px, float py, float m_t, float m_th, float tn2, float& r, float& md, int& col) {
-  r = 0.0f; md = 0.0f; col = -1;
-  if (!(__builtin_fabsf(px) < __builtin_huge_valf() && __builtin_fabsf(py) < __builtin_huge_valf())) return 0;      // q is infinite or not a number under every T: r2 fails the gate
-  float qx, qy;
-  xf_point(T, px, py, qx, qy);
-  const float r2 = __builtin_fmaf(qx, qx, qy * qy);
-  if (!(r2 >= 1e-30f && r2 <= 1e37f)) return 1;
-  float y0;
-  r = sqrt_rn_seed(r2, y0);
-  const float th = bearing<kGuarded>(qy, qx, r, y0);      // (pure functions of their operands: made in front of the depth tests instead of behind them, the class is the same)
-  const float u = __builtin_fmaf(P.K00, th, P.K01);
-  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(col) : "v"(u));
-  const int cl = cand_classify_polar(P, r, th, u, col, m_t, m_th, tn2, md);
-  if ((unsigned) col >= (unsigned) P.cols) col = -1;
-  return cl;
-}
-// One point of the BUILD iteration's stream: project_point_stream's operation sequence for the canvas -- and, inside the gate's branch, the point's entry in the
-// blockers from the r, th, u and col just made.  blk[] comes out word for word what a pass of its own over the same points with cand_classify made of it:
-//  * an interior point (class 2) has rmin + md <= r <= rmax - md with md > 0 (cand_depth_margin: at least 1e-7), so rmin <= r <= rmax for r = sqrt_rn(r2) --
-//    which IS r2lo <= r2 <= r2hi (make_projk: the smallest / largest float whose correctly rounded root reaches rmin / stays within rmax; sqrt_rn is monotone) --
-//    and a column inside the canvas: every interior point is inside both branches below.  Where rmin + md rounds to rmin (md below half an ulp of it) the point
-//    at r == rmin is interior and r2 >= r2lo holds with equality of the roots; the same at rmax.  [r2lo, r2hi] lies inside cand_classify's own [1e-30, 1e37]
-//    (ranges are clamped to [1e-15, 1e18] m), and a point with a coordinate that is not finite has an r2 that fails the gate here and class 0 there;
-//  * inside the branches r, th, u and col are made by the functions cand_classify calls, on the same operands, with the same kGuarded, and T is the slice's T0;
-//  * a point outside them was never interior, so it never touched blk[].
-template <bool kGuarded>
-LSM2D_DEV void project_point_stream_blk(const Iso& T, const ProjK& P, float px, float py, int idx, u64* canvas, uint32_t* blk, const int* par) {
-  float qx, qy;
-  xf_point(T, px, py, qx, qy);
-  const float r2 = __builtin_fmaf(qx, qx, qy * qy);
-  if (r2 >= P.r2lo && r2 <= P.r2hi) {
-    float y0;
-    const float r  = sqrt_rn_seed(r2, y0);
-    const float th = bearing<kGuarded>(qy, qx, r, y0);
-    const float u  = __builtin_fmaf(P.K00, th, P.K01);
-    int col;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(col) : "v"(u));
-    if ((unsigned) col < (unsigned) P.cols) {
-      atomicMin(&canvas[col], ((u64) __float_as_uint(r) << 32) | (u64) (uint32_t) idx);
-      // (the margins from k_align's s_cand_par, here and now: as arguments they were loop invariants held in registers across the stream)
-      const float m_t = __int_as_float(par[4]), m_th = __int_as_float(par[5]);
-      const float tn2 = __builtin_fabsf(T.tx) + __builtin_fabsf(T.ty) + 2.0f * m_t;
-      float md;
-      if (cand_classify_polar(P, r, th, u, col, m_t, m_th, tn2, md) == 2) atomicMin(&blk[col], __float_as_uint(r + md));
-    }
-  }
-}
-// project_cloud_list_t for the build iteration: the same loads, the same two-buffer look-ahead, project_point_stream_blk for project_point_stream
-template <bool kGuarded, int kStride>
-LSM2D_DEV void project_cloud_list_blk_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, u64* canvas, int tid, int nthreads,
-                                        const uint16_t* units, int n_units, int B, uint32_t* blk, const int* par) {
-  const Iso T = Tin; ProjK P = Pin;
-  asm volatile("" : "+v"(P.K01));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const unsigned long long pb = reinterpret_cast<unsigned long long>(lane_xy);
-  const unsigned pb_hi = (unsigned) __builtin_amdgcn_readfirstlane((int) (pb >> 32));
-  const unsigned pb_lo = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) pb);
-  float4* ubase = reinterpret_cast<float4*>(((unsigned long long) pb_hi << 32) | (unsigned long long) pb_lo);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ubase, (short) 0, 0x7fffffff, 0x00020000);
-  const int row_bytes = nthreads * (int) sizeof(float4);
-  for (int k = tid; k < n_units; k += kStride) {
-    const int code = (int) units[k];
-    const int g = code & 511, t0 = (code >> 9) * B;
-    const int nsteps = T_steps - t0 < B ? T_steps - t0 : B;
-    const int voff = g * (int) sizeof(float4) + t0 * row_bytes;
-    int idx = 2 * (g * T_steps + t0);
-    auto load = [&](int soff) {
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-      return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
-    };
-    auto pair = [&](const float4& v, int i) {
-      project_point_stream_blk<kGuarded>(T, P, v.x, v.y, i, canvas, blk, par);
-      project_point_stream_blk<kGuarded>(T, P, v.z, v.w, i + 1, canvas, blk, par);
-    };
-    int t = 0, soff = 0;
-    float4 va = load(0);
-    for (; t + 2 <= nsteps; t += 2) {
-      const float4 vb = load(soff + row_bytes);
-      pair(va, idx);
-      soff += 2 * row_bytes;
-      va = load(soff);
-      pair(vb, idx + 2);
-      idx += 4;
-    }
-    if (t < nsteps) pair(va, idx);
-  }
-}
-// The build's pass over the unit list's points: project_cloud_list_t's loads and index arithmetic, every point handed to f(px, py, index) pair by pair
-template <int kStride, class F>
-LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_steps, int tid, int nthreads, const uint16_t* units, int n_units, int B, F f) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const unsigned long long pb = reinterpret_cast<unsigned long long>(lane_xy);
-  const unsigned pb_hi = (unsigned) __builtin_amdgcn_readfirstlane((int) (pb >> 32));
-  const unsigned pb_lo = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) pb);
-  float4* ubase = reinterpret_cast<float4*>(((unsigned long long) pb_hi << 32) | (unsigned long long) pb_lo);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ubase, (short) 0, 0x7fffffff, 0x00020000);
-  const int row_bytes = nthreads * (int) sizeof(float4);
-  for (int k = tid; k < n_units; k += kStride) {
-    const int code = (int) units[k];
-    const int g = code & 511, t0 = (code >> 9) * B;
-    const int nsteps = T_steps - t0 < B ? T_steps - t0 : B;
-    const int voff = g * (int) sizeof(float4) + t0 * row_bytes;
-    int idx = 2 * (g * T_steps + t0);
-    for (int t = 0; t < nsteps; ++t, idx += 2) {
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + t * row_bytes, 0, 0);
-      f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), idx);
-    }
-  }
-}
-// Build, the pass behind the stream: every point against the rule; the kept indices are appended to `cand` (any order serves: the z-buffer's minimum does not depend on it) through
-// one LDS counter, a wave's keeps of a step in one add.  The counter goes on counting past `cap`: the caller sees the overflow there and does not use the list.
-template <bool kGuarded, int kStride>
-LSM2D_DEV void cand_collect_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, int tid, int nthreads, const uint16_t* units, int n_units, int B,
-                              const uint32_t* blk, uint32_t* cand, int cap, int* count, float m_t, float m_th) {
-  const Iso T = Tin; const ProjK P = Pin;
-  const float tn2 = __builtin_fabsf(T.tx) + __builtin_fabsf(T.ty) + 2.0f * m_t;
-  auto keeps = [&](float px, float py) -> bool {
-    float r, md; int col;
-    const int cl = cand_classify<kGuarded>(T, P, px, py, m_t, m_th, tn2, r, md, col);
-    if (cl != 2) return cl == 1;
-    return !(__uint_as_float(blk[col]) < r - md);
-  };
-  cand_for_each_pair<kStride>(lane_xy, T_steps, tid, nthreads, units, n_units, B, [&](float ax, float ay, float bx, float by, int idx) {
-    const bool k0 = keeps(ax, ay), k1 = keeps(bx, by);
-    const u64 b0 = __ballot(k0), b1 = __ballot(k1);
-    const u64 act = b0 | b1;
-    if (act) {
-      const int n0 = __popcll(b0);
-      int base = 0;
-      if ((int) __builtin_amdgcn_mbcnt_hi((unsigned) (act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) act, 0u)) == 0 && (k0 || k1)) base = atomicAdd(count, n0 + __popcll(b1));      // the first keeping lane
-      base = __builtin_amdgcn_readlane(base, __builtin_amdgcn_readfirstlane(__builtin_ctzll(act)));
-      const int p0 = base + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (b0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) b0, 0u));
-      const int p1 = base + n0 + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (b1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) b1, 0u));
-      if (k0 && p0 < cap) cand[p0] = (uint32_t) idx;
-      if (k1 && p1 < cap) cand[p1] = (uint32_t) (idx + 1);
-    }
-  });
-}
-// Use: the iteration's stream while the list is valid.  Thread t takes entries t, t + kStride, ...: the 8-byte point gathered from the cloud by its index (the
-// key's index is that index), the next entry's on its way while this one is projected; project_point_stream as ever.
-template <bool kGuarded, int kStride>
-LSM2D_DEV void project_candidates_t(const float2* __restrict__ mxy, const Iso& Tin, const ProjK& Pin, u64* canvas, int tid, const uint32_t* cand, int n) {
-  const Iso T = Tin; ProjK P = Pin;
-  asm volatile("" : "+v"(P.K01));
-  int k = tid;
-  if (k >= n) return;
-  int idx = (int) cand[k];
-  float2 p = mxy[idx];
-  for (; k < n; k += kStride) {
-    const int kn = k + kStride;
-    const int idn = (int) cand[kn < n ? kn : k];
-    const float2 pn = mxy[idn];
-    project_point_stream<kGuarded>(T, P, p.x, p.y, idx, canvas);
-    idx = idn; p = pn;
-  }
-}
-// The build as k_align calls it.  `blk`: a word per column -- all ones (a NaN: no blocker, and no comparison with it holds) before the stream, then the minimum over
-// the column's interior points of r + md(r), as bits (positive floats order like their patterns) -- the list behind them; capacity and margins are read from
-// k_align's s_cand_par (LDS) here and now.  The barriers are everybody's: cand_clear_blockers and one in front of the stream; the stream (made in the same pass
-// as the canvas: project_cloud_list_blk), one more, then cand_collect (it does not look at the canvas, so it may stand in front of the bin walk).
-LSM2D_HD int cand_blocker_words(int cols) { return (cols + 3) & ~3; }
-template <int kStride>
-LSM2D_DEV void cand_clear_blockers(const ProjK& P, int tid, uint32_t* blk) { for (int c = tid; c < P.cols; c += kStride) blk[c] = 0xFFFFFFFFu; }
-template <int kStride>
-LSM2D_DEV void project_cloud_list_blk(const float4* __restrict__ lane_xy, int T_steps, const Iso& T, const ProjK& P, u64* canvas, int tid, int nthreads,
-                                      const uint16_t* units, int n_units, int B, uint32_t* blk, const int* par) {
-  if (P.tiny_ok) project_cloud_list_blk_t<false, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B, blk, par);
-  else project_cloud_list_blk_t<true, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B, blk, par);
-}
-template <int kStride, int kChunks>
-LSM2D_DEV void cand_collect(const float4* lane_xy, int T_steps, const Iso& T, const ProjK& P, int tid, const uint16_t* units, int n_units, int B, uint32_t* blk, const int* par, int* count) {
-  const int cap = __builtin_amdgcn_readfirstlane(par[1]);
-  const float m_t = __int_as_float(__builtin_amdgcn_readfirstlane(par[4])), m_th = __int_as_float(__builtin_amdgcn_readfirstlane(par[5]));
-  uint32_t* cand = blk + cand_blocker_words(P.cols);
-  if (P.tiny_ok) cand_collect_t<false, kStride>(lane_xy, T_steps, T, P, tid, kChunks, units, n_units, B, blk, cand, cap, count, m_t, m_th);
-  else cand_collect_t<true, kStride>(lane_xy, T_steps, T, P, tid, kChunks, units, n_units, B, blk, cand, cap, count, m_t, m_th);
-}
-// has the transform N stayed within (m_t, m_th) of L, with room for what this fp32 evaluation can be off by?  (begin_iteration's expression for s_rebuild; the proof above)
-LSM2D_DEV bool cand_pose_within(const Iso& N, const Iso& L, float m_t, float m_th) {
-  if (__float_as_uint(N.c) == __float_as_uint(L.c) && __float_as_uint(N.s) == __float_as_uint(L.s)) {      // the same rotation, bit for bit: d = t - t0
-    const float ex = N.tx - L.tx, ey = N.ty - L.ty;
-    return ex * ex + ey * ey <= m_t * m_t * 0.999999f;
-  }
-  const float cd = N.c * L.c + N.s * L.s, sd = N.s * L.c - N.c * L.s;
-  const float dx = N.tx - (cd * L.tx - sd * L.ty), dy = N.ty - (sd * L.tx + cd * L.ty);
-  const float lim = m_t - 4e-7f * (__builtin_fabsf(N.tx) + __builtin_fabsf(N.ty) + __builtin_fabsf(L.tx) + __builtin_fabsf(L.ty));
-  return cd > 0.5f && __builtin_fabsf(sd) <= m_th - 3e-7f && lim > 0.0f && dx * dx + dy * dy <= lim * lim * 0.999999f;
-}
+#include "lsm2d_device_cand.h"      // ---- candidate lists (k_align_cand): rule, blockers, collect, gather
 
 LSM2D_DEV void project_cloud_units(const float4* __restrict__ lane_xy, int T_steps, const Iso& T, const ProjK& P, u64* canvas, int tid, int nthreads,
                                    const uint16_t* surv, int s, int B, int nb) {
@@ -744,185 +504,7 @@ LSM2D_DEV float pair_chi(const Iso& T, float2 pf, float2 nf, float2 pm, float2 n
   return __builtin_fmaf(e0, e0, __builtin_fmaf(e1, e1, e2 * e2));
 }
 
-// ---- "sum_order" 1: H, b and the chi^2 statistics added PAIR AFTER PAIR, the reference's order --------------------------------------
-// The reference adds one factor after the other into H and b (octave/solver/nicp_post.m:69-90: H += J'*J; b += J'*e inside the loop over the
-// correspondences; the correspondence vector is in ascending column for the projective finder, correspondence_finder_projective_2d.cpp:55-74, and
-// in ascending moving index for the point-query finders, correspondence_finder_kd_tree_2d.cpp:12-27).  The default kernels add in trees (a thread's
-// pairs, then 64 lanes, then 8 waves): the same terms, another association.  With the option on, every thread that holds a pair writes the pair's
-// TERMS -- accumulate_pair's operations up to the sums, in its order -- as a record of kSeqFields floats into LDS, slot = the pair's position in the
-// reference's order within the current trip of the workgroup (a trip: 512 consecutive columns / moving indices, handed over in two halves); after the barrier
-// eleven lanes of wave 0 walk the records in ascending slot, lane q adding quantity q with exactly the fused operations the sequential CPU restatement of the factor
-// uses (the tests hold the two against each other bit for bit): h = fma(w a_i, a_j, h), two of them chained for h22 and b2, chi sums by plain adds.  A slot without a pair holds zeros:
-// fma(+0, +0, h) == h and h + 0 == h bit for bit (no sum here is ever -0: they start at +0).  The counts are integers and keep their ballots.
-// Record = 14 floats, 56 bytes: a0 a1 a2 e0 | wa0 wa1 wa2 w | dd de chi_in chi_out | 1 0 (wa_i = w * a_i, rounded by the thread that holds the pair: the
-// reference's `wa` temporaries; the two constants travel with every record).  The records of HALF a trip (kSeqHalf = 256) sit in LDS; lane q of the walking wave
-// reads, per record, the four operands of ITS two fused adds straight from LDS -- acc = fma(x1, y1, acc); acc = fma(x2, y2, acc) -- at four per-lane FIELD
-// offsets and one stride for all: an operand that is a constant for this lane (1 for the chi sums' y1; 0, 0 for the second add of the nine quantities that have
-// none) reads the record's constant fields.  So a record costs the walk four LDS reads with immediate offsets (the compiler pairs them: ds_read2_b32) and two
-// dependent FMAs, nothing else.  (Round 6, measured in isolation -- tools/seq_walk_probe.py: a first form that selected and multiplied in the loop and waited for
-// each record's loads 135 cycles per record; per-lane strides for the constants -- sixteen address adds per four records -- 65; this one: see DESIGN section 5.)
-static constexpr int kSeqFields = 14, kSeqHalf = 256;
-static constexpr int kSeqLdsBytes = kSeqHalf * kSeqFields * 4;
-template <bool kInlineLog = false>
-LSM2D_DEV void pair_terms(const Iso& T, float2 pf, float2 nf, float2 pm, float2 nm, bool cauchy, float tau, bool inl_only,
-                          float (&t)[kSeqFields], bool& inlier) {
-  float qx, qy, nqx, nqy;
-  xf_point(T, pm.x, pm.y, qx, qy);
-  xf_normal(T, nm.x, nm.y, nqx, nqy);
-  const float dx = qx - pf.x, dy = qy - pf.y;
-  const float e0 = __builtin_fmaf(nf.x, dx, nf.y * dy);
-  const float e1 = nqx - nf.x, e2 = nqy - nf.y;
-  const float a0 = __builtin_fmaf(T.c, nf.x, T.s * nf.y);
-  const float a1 = __builtin_fmaf(-T.s, nf.x, T.c * nf.y);
-  const float a2 = __builtin_fmaf(a1, pm.x, -(a0 * pm.y));
-  const float d0 = -nqy, d1 = nqx;
-  const float chi = __builtin_fmaf(e0, e0, __builtin_fmaf(e1, e1, e2 * e2));
-  float w = 1.0f, kern = 0.0f;
-  inlier = true;
-  if (cauchy) {
-    const float q = chi / tau;
-    w = 1.0f / (1.0f + q);
-    inlier = chi < tau;
-    if (!inlier) kern = tau * (kInlineLog ? log_fixed_inline(1.0f + q) : log_fixed(1.0f + q));
-    if (inl_only) w = inlier ? 1.0f : 0.0f;
-  }
-  t[0] = a0; t[1] = a1; t[2] = a2; t[3] = e0;
-  t[4] = w * a0; t[5] = w * a1; t[6] = w * a2; t[7] = w;
-  t[8] = __builtin_fmaf(d0, d0, d1 * d1);
-  t[9] = __builtin_fmaf(d0, e1, d1 * e2);
-  t[10] = inlier ? chi : 0.0f;
-  t[11] = inlier ? 0.0f : kern;
-}
-// "no pair in this slot": zeros and the constants
-LSM2D_DEV void seq_zero(float (&t)[kSeqFields]) {
-#pragma unroll
-  for (int f = 0; f < 12; ++f) t[f] = 0.0f;
-  t[12] = 1.0f; t[13] = 0.0f;
-}
-// `rec`: the region's start; record `slot` (0 .. kSeqHalf - 1) as seven 8-byte stores
-LSM2D_DEV void seq_store(float* rec, int slot, const float (&t)[kSeqFields]) {
-  float2* r = reinterpret_cast<float2*>(rec + slot * kSeqFields);
-#pragma unroll
-  for (int f = 0; f < kSeqFields / 2; ++f) r[f] = make_float2(t[2 * f], t[2 * f + 1]);
-}
-// The walk, one wave.  The chain of a quantity is serial -- acc = fma(x1, y1, acc); acc = fma(x2, y2, acc), record after record -- and what a single lane walking
-// it pays per record is the LDS round trip of the record's operands as far as nothing covers it: the first form of this round (lane q < 11 walks quantity q, two
-// groups of two records in flight: all the registers the kernel has for it) took 44 cycles per record.  Now a QUAD of lanes walks a quantity: lane j of quad q
-// (lane 4 q + j) holds the operands of records 8 b + 2 j and 8 b + 2 j + 1 of batch b, so ONE pair of LDS reads per operand brings eight records, and the running
-// sum travels round the quad -- quad_perm:[3,0,1,2], one DPP move -- picking up each lane's two records in ascending record order: lane 0 takes it from lane 3
-// (the previous batch's end), adds records 8 b and 8 b + 1, lane 1 takes it from lane 0, ...  Every lane executes every step; the value that counts is in lane s
-// after step s, what the other lanes compute meanwhile is overwritten before it is ever read on the chain.  Per record: two fused adds + half a move = 2.5
-// vector instructions on the chain and an eighth of the LDS reads, the next batch's loads in flight under this batch's twenty instructions.  The same fused operations on
-// the same values in the same order as before: the same bits (the tests hold the kernel against the sequential CPU restatement bit for bit).
-// `acc`: the caller keeps it per lane between calls (zero at first, in all lanes); the running sum of quantity q is lane 4 q + 3's after every call -- seq_total()
-// brings it to lane q.  Records n .. 8 ceil(n / 8) - 1 of the buffer must hold "no pair" records (k_align_seq, which walks its pairs only, pads them; the split path's kernels write every slot of a half-trip).
-#ifndef LSM2D_SEQ_WALK_QUADS
-#define LSM2D_SEQ_WALK_QUADS 1      // 0: the single-lane walk (A/B: profiles/r06/sum_order_walker_quads_ab_r06.txt)
-#endif
-// Measured (tools/seq_walk_probe.py: cycles per record in isolation; configs[1] with "sum_order" 1: k_align_seq ms; profiles/r06/sum_order_walker_quads_ab_r06.txt):
-//   single lane 44 / 1.123;  quads, R records per lane and batch, B batches in registers: R 1 B 4: 44 / 1.114;  R 2 B 2 (shipped): 30 / 0.955-0.961;  R 2 B 3: 28 / 0.971;
-//   R 4 B 2: 23 / 0.944 with 48 bytes of scratch in the headline instantiation.  The cost is ~14 cycles for a record's two dependent fused adds + ~30 per move of the
-//   sum to the next lane (a DPP result feeding the chain), i.e. per R records.  Bringing the OPERANDS to the sum instead (quad broadcasts, the x operand as
-//   v_fmac_f32_dpp's own): 33-37 / 1.04-1.06 -- four DPP instructions per record cost more than half a move.  Loads pinned ahead of the chain (sched_barrier): slower.
-#ifndef LSM2D_SEQ_QUAD_R
-#define LSM2D_SEQ_QUAD_R 2
-#endif
-#ifndef LSM2D_SEQ_QUAD_BUFS
-#define LSM2D_SEQ_QUAD_BUFS 2
-#endif
-#ifndef LSM2D_SEQ_UNROLL
-#define LSM2D_SEQ_UNROLL 2      // single-lane walk: records per group; two groups in flight (2 / 3 / 4 / 6: 1.119 / 1.143 / 1.115 / 1.199 ms on configs[1]; 4 and up spill at 64 registers)
-#endif
-LSM2D_DEV float seq_quad_prev(float v) {      // lane 4 q + j <- lane 4 q + (j + 3) % 4
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x93 /* quad_perm:[3,0,1,2] */, 0xF, 0xF, true));
-}
-template <bool kTopPriority = false>      // kTopPriority: s_setprio 3 once the walk's addresses are made (k_align_seq: the caller says when it ends)
-LSM2D_DEV float seq_walk(const float* rec, int n, int lane, float acc) {
-  asm volatile("" : "+v"(lane));      // (the lane's field offsets are made HERE, every time: as loop invariants of the iteration loop they are registers held -- and spilled -- across the whole kernel)
-#if LSM2D_SEQ_WALK_QUADS
-  const int q = (lane >> 2) < 11 ? (lane >> 2) : 0, j = lane & 3;      // (quads 11 .. 15 walk along like quad 0 and hold nothing of value)
-#else
-  const int q = lane < 11 ? lane : 0;
-#endif
-  const bool chi = q >= 9, has2 = q == 5 || q == 8;
-  const int fx1 = (int) ((0xBA654655444ull >> (4 * q)) & 15), fy1 = chi ? 12 : (int) ((0x00333221210ull >> (4 * q)) & 15);      // field of x1 (wa_i, or the chi term) and of y1 (a_j, e0, or the constant 1)
-  const int fx2 = has2 ? 7 : 13, fy2 = has2 ? (q == 5 ? 8 : 9) : 13;                                                             // w and dd / de; elsewhere the constant 0 twice
-#if LSM2D_SEQ_WALK_QUADS
-  constexpr int kR = LSM2D_SEQ_QUAD_R, kBufs = LSM2D_SEQ_QUAD_BUFS;      // records per lane and batch; batches in registers
-  const float* r0 = rec + kR * j * kSeqFields;      // this lane's first record of batch 0
-  const float* px1 = r0 + fx1; const float* py1 = r0 + fy1; const float* px2 = r0 + fx2; const float* py2 = r0 + fy2;
-  constexpr int kBatch = 4 * kR * kSeqFields;      // floats from one batch to the next
-  struct Ops { float x1[kR], y1[kR], x2[kR], y2[kR]; };
-  auto load = [&](int b) {
-    Ops o; const int off = b * kBatch;
-#pragma unroll
-    for (int r = 0; r < kR; ++r) { o.x1[r] = px1[off + r * kSeqFields]; o.y1[r] = py1[off + r * kSeqFields]; o.x2[r] = px2[off + r * kSeqFields]; o.y2[r] = py2[off + r * kSeqFields]; }
-    return o;
-  };
-  auto chain = [&](const Ops& o) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float t = seq_quad_prev(acc);
-#pragma unroll
-      for (int r = 0; r < kR; ++r) { t = __builtin_fmaf(o.x1[r], o.y1[r], t); t = __builtin_fmaf(o.x2[r], o.y2[r], t); }
-      acc = t;
-    }
-  };
-  const int nb = (n + 4 * kR - 1) / (4 * kR);
-  if (nb <= 0) return acc;
-  Ops buf[kBufs];
-  if constexpr (kTopPriority) __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-  for (int i = 0; i + 1 < kBufs; ++i) buf[i] = load(i < nb ? i : nb - 1);
-  for (int b = 0; b < nb; b += kBufs) {      // buf[i] holds batch b + i; the free buffer takes batch b + i + kBufs - 1 (past the end: the last batch again, never used)
-#pragma unroll
-    for (int i = 0; i < kBufs; ++i) {
-      if (b + i < nb) {
-        const int nxt = b + i + kBufs - 1;
-        buf[(i + kBufs - 1) % kBufs] = load(nxt < nb ? nxt : nb - 1);
-        chain(buf[i]);
-      }
-    }
-  }
-  return acc;
-#else
-  const float* px1 = rec + fx1; const float* py1 = rec + fy1; const float* px2 = rec + fx2; const float* py2 = rec + fy2;
-  // two groups of kU records in flight: the NEXT group's loads are issued before this group's dependent adds run
-  constexpr int kU = LSM2D_SEQ_UNROLL;
-  float ax1[kU], ay1[kU], ax2[kU], ay2[kU], bx1[kU], by1[kU], bx2[kU], by2[kU];
-  auto load = [&](int k0, float (&x1)[kU], float (&y1)[kU], float (&x2)[kU], float (&y2)[kU]) {
-#pragma unroll
-    for (int j = 0; j < kU; ++j) { x1[j] = px1[(k0 + j) * kSeqFields]; y1[j] = py1[(k0 + j) * kSeqFields]; x2[j] = px2[(k0 + j) * kSeqFields]; y2[j] = py2[(k0 + j) * kSeqFields]; }
-  };
-  auto add = [&](const float (&x1)[kU], const float (&y1)[kU], const float (&x2)[kU], const float (&y2)[kU]) {
-#pragma unroll
-    for (int j = 0; j < kU; ++j) { acc = __builtin_fmaf(x1[j], y1[j], acc); acc = __builtin_fmaf(x2[j], y2[j], acc); }
-  };
-  int k = 0;
-  if (n >= kU) {
-    load(0, ax1, ay1, ax2, ay2);
-    for (; k + 3 * kU <= n; k += 2 * kU) {      // A holds group k; B <- k + kU; add A; A <- k + 2 kU; add B
-      load(k + kU, bx1, by1, bx2, by2);
-      add(ax1, ay1, ax2, ay2);
-      load(k + 2 * kU, ax1, ay1, ax2, ay2);
-      add(bx1, by1, bx2, by2);
-    }
-    if (k + 2 * kU <= n) { load(k + kU, bx1, by1, bx2, by2); add(ax1, ay1, ax2, ay2); add(bx1, by1, bx2, by2); k += 2 * kU; }
-    else { add(ax1, ay1, ax2, ay2); k += kU; }
-  }
-  for (; k < n; ++k) { acc = __builtin_fmaf(px1[k * kSeqFields], py1[k * kSeqFields], acc); acc = __builtin_fmaf(px2[k * kSeqFields], py2[k * kSeqFields], acc); }
-  return acc;
-#endif
-}
-// the walk's result for lane q < 11 of the walking wave: the running sum of quantity q (every lane of the wave calls)
-LSM2D_DEV float seq_total(float acc, int lane) {
-#if LSM2D_SEQ_WALK_QUADS
-  const int src = lane < 11 ? 4 * lane + 3 : lane;
-  return __int_as_float(__builtin_amdgcn_ds_bpermute(4 * src, __float_as_int(acc)));
-#else
-  return acc;
-#endif
-}
+#include "lsm2d_device_seq.h"      // ---- "sum_order" 1: pair records and the walk in the reference's order
 
 // ---- wave64 / workgroup reduction: shuffle butterfly, one LDS hop, fixed order => deterministic ----
 static constexpr int kAccumWords = 14;

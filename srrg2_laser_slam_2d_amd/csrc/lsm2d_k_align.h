@@ -1,5 +1,6 @@
 // lsm2d_k_align.h -- k_align: one workgroup owns one alignment for all its iterations -- the moving cloud streamed through the LDS z-buffer, the bin walk, the point-query passes, the reduction, the 3x3 solve as a vector over wave 0 (MultiAligner2D::compute; registration/correspondence_finder_projective_2d.cpp:35-74; octave/solver/nicp_post.m:69-97); k_align_seq: the same with the reference's order of summation.
-// Part of lsm2d_kernels.h (included there, inside namespace lsm2d, in this order); not a translation unit of its own.
+// Part of lsm2d_kernels.h (included there, inside namespace lsm2d, in this order); not a translation unit of its own.  This file is align_body, the one device function all of them share;
+// the __global__ kernels that instantiate it are in lsm2d_k_align_kernels.h, its phase-probe macros in lsm2d_k_align_probe.h.
 // kSeq: "sum_order" 1 -- H, b and the chi^2 statistics are added pair after pair in the reference's order (lsm2d_device.h: pair_terms / seq_walk) instead of
 // in trees; instantiations of their own (k_align_seq), so the default kernels do not carry the records' code
 // kW: threads of the workgroup (round 6).  512 = kAlignBlock everywhere but in the NARROW instantiation of the culled projective stream (k_align_narrow<256>):
@@ -86,52 +87,9 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   constexpr int nwaves = kW / 64;      // physical waves (the rows of `red` stay kAlignBlock / 64: one per VIRTUAL wave)
   constexpr int kPriorWords = (int) (sizeof(PriorDev) / sizeof(float));
   __shared__ unsigned long long s_clk[2];      // start stamps wait in LDS: no register is held across the kernel for them
-#ifdef LSM2D_PHASE_PROBE      // diagnostics build: thread 0 sums the cycles it spends in the query / projection phase, at the barrier + reduction, and in the solve
+#ifdef LSM2D_PHASE_PROBE      // diagnostics build: thread 0 sums the cycles it spends in the query / projection phase, at the barrier + reduction, and in the solve (the LSM2D_PH* macros: lsm2d_k_align_probe.h)
   __shared__ unsigned long long s_ph[4];
   if (tid == 0) { s_ph[0] = s_ph[1] = s_ph[2] = 0; s_ph[3] = __builtin_amdgcn_s_memtime(); }
-#define LSM2D_PH_STAMP(k) do { if (tid == 0) { const unsigned long long now__ = __builtin_amdgcn_s_memtime(); s_ph[k] += now__ - s_ph[3]; s_ph[3] = now__; } } while (0)
-#define LSM2D_PH_SKIP() do { if (tid == 0) s_ph[3] = __builtin_amdgcn_s_memtime(); } while (0)      // what went before belongs to no bucket
-  // -DLSM2D_PHASE_PROBE=1 (or empty): the three buckets above.  =2: unit lists + stream | bin walk + reduction | solve + the rest.  =3: unit lists | stream | everything else.  =4: bin walk + wave sums | everything else | wave 0's stretch (a single slice).
-#if LSM2D_PHASE_PROBE + 0 == 2
-#define LSM2D_PH(k) LSM2D_PH_STAMP((k) == 0 ? 1 : (k))
-#define LSM2D_PH_LISTS() do { } while (0)
-#define LSM2D_PH_STREAM() LSM2D_PH_STAMP(0)
-#elif LSM2D_PHASE_PROBE + 0 == 3
-#define LSM2D_PH(k) LSM2D_PH_STAMP(2)
-#define LSM2D_PH_LISTS() LSM2D_PH_STAMP(0)
-#define LSM2D_PH_STREAM() LSM2D_PH_STAMP(1)
-#elif LSM2D_PHASE_PROBE + 0 == 4      // bin walk + wave sums | everything else | wave 0's stretch behind the sums' barrier, up to the iteration's closing barrier
-#define LSM2D_PH(k) do { } while (0)
-#define LSM2D_PH_LISTS() do { } while (0)
-#define LSM2D_PH_STREAM() LSM2D_PH_STAMP(1)
-#define LSM2D_PH_SUMS() LSM2D_PH_STAMP(0)
-#define LSM2D_PH_TAIL() LSM2D_PH_STAMP(2)
-#elif LSM2D_PHASE_PROBE + 0 == 5      // k_align_cand: the unit list's stream in an iteration that builds no list | the build iteration's stream (blockers included) | a list-served gather; the remainder of the lifetime is everything else
-#define LSM2D_PH(k) do { } while (0)
-#define LSM2D_PH_LISTS() LSM2D_PH_SKIP()
-#define LSM2D_PH_STREAM() do { } while (0)
-#define LSM2D_PH_CAND(k) do { if ((k) >= 0 && (k) <= 2) LSM2D_PH_STAMP((k) & 3); else LSM2D_PH_SKIP(); } while (0)
-#elif LSM2D_PHASE_PROBE + 0 == 6      // k_align_cand: a blockers pass of its own (none since round 22) | the collect pass | unit-list rebuilds
-#define LSM2D_PH(k) do { } while (0)
-#define LSM2D_PH_LISTS() LSM2D_PH_STAMP(2)
-#define LSM2D_PH_STREAM() do { } while (0)
-#define LSM2D_PH_CAND(k) do { if ((k) == 3) LSM2D_PH_STAMP(0); else if ((k) == 4) LSM2D_PH_STAMP(1); else LSM2D_PH_SKIP(); } while (0)
-#else
-#define LSM2D_PH(k) LSM2D_PH_STAMP(k)
-#define LSM2D_PH_LISTS() do { } while (0)
-#define LSM2D_PH_STREAM() do { } while (0)
-#endif
-#else
-#define LSM2D_PH(k) do { } while (0)
-#define LSM2D_PH_LISTS() do { } while (0)
-#define LSM2D_PH_STREAM() do { } while (0)
-#endif
-#ifndef LSM2D_PH_SUMS
-#define LSM2D_PH_SUMS() do { } while (0)
-#define LSM2D_PH_TAIL() do { } while (0)
-#endif
-#ifndef LSM2D_PH_CAND      // the candidate lists' sections (modes 5 and 6; tools/phase_probe.py --lists): -1 a section begins, 0 / 1 / 2 a plain stream, a build iteration's stream, a gather ends, 3 / 4 a blockers pass, a collect pass ends
-#define LSM2D_PH_CAND(k) do { } while (0)
 #endif
   if (A.wg_place && tid == 0) A.wg_place[blockIdx.x] = place_key();
   const bool stamp = A.clock_out && tid == 0 && a % A.clock_stride == 0;
@@ -326,13 +284,8 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   const bool ff_on = A.fast_forward && !(A.term_eps > 0.0f) && !A.inlier_runs && !A.host_polls;      // (wave-uniform: kernel arguments)
   for (; it < it_cap; ++it) {
     const bool inl_only = A.inlier_runs && __builtin_amdgcn_readfirstlane(s_phase) != 0;
-#if LSM2D_PRIO_BY_PROGRESS == 1
-    { const int q = (4 * it) / A.max_it; if (q == 0) __builtin_amdgcn_s_setprio(3); else if (q == 1) __builtin_amdgcn_s_setprio(2); else if (q == 2) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-#elif LSM2D_PRIO_BY_PROGRESS == 2
+    // wave priority by progress (lsm2d_kernels.h): halving intervals -- 1/2, 3/4, 7/8 of the iterations (configs[1]: 1.65 ms; off 1.86, quarters 1.69)
     { if (2 * it < A.max_it) __builtin_amdgcn_s_setprio(3); else if (4 * it < 3 * A.max_it) __builtin_amdgcn_s_setprio(2); else if (8 * it < 7 * A.max_it) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-#elif LSM2D_PRIO_BY_PROGRESS == 3      // the other way round, for launches behind the fast-forward: whoever still iterates late is what the launch waits for
-    { if (it < 4) __builtin_amdgcn_s_setprio(0); else if (it < 6) __builtin_amdgcn_s_setprio(1); else if (it < 8) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
-#endif
     for (int s = 0; s < A.n_slices; ++s) {
       const SliceDev& S = A.s[s];
       const Iso T = s_iso[s];
@@ -356,9 +309,9 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
       auto seq_walk_buffer = [&](int n) {      // n records in LDS, "no pair" records up to the next multiple of eight (seq_walk takes eight at a time)
         if (tid < ((n + 7) & ~7) - n) { float z[kSeqFields]; seq_zero(z); seq_store(l_rec, n + tid, z); }
         __syncthreads();
-        // (LSM2D_SEQ_WALK_PRIO: the walking wave ahead of the other workgroups' streams on its SIMD -- its workgroup's other seven waves wait for it, and for the
+        // (seq_walk<true>: the walking wave at top priority while it walks, ahead of the other workgroups' streams on its SIMD -- its workgroup's other seven waves wait for it, and for the
         // solve, which is wave 0's: the wave keeps the priority until the next iteration sets the one its progress earns)
-        if (tid < 64) seq_acc = seq_walk<LSM2D_SEQ_WALK_PRIO != 0>(l_rec, n, tid, seq_acc);
+        if (tid < 64) seq_acc = seq_walk<true>(l_rec, n, tid, seq_acc);
         __syncthreads();
       };
       auto seq_trip = [&](const float (&t)[kSeqFields], int parity /* 0, 1, 0, ... from trip to trip: s_wcnt's two buffers */) {
@@ -518,9 +471,6 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
         const float4* maos = S.moving.aos ? S.moving.aos + mbase : nullptr;      // (a set without its AoS copy -- sizes still pending on the device, or
         const float4* faos = S.fixed.aos ? S.fixed.aos + fbase : nullptr;        //  unpacked by this launch -- is gathered from its split arrays)
         const u64* fcs = fcan + S.fcan_offset;
-#ifndef LSM2D_BINWALK_BATCHED
-#define LSM2D_BINWALK_BATCHED 1
-#endif
         if constexpr (kSeq) {
           // "sum_order" 1: trips of kAlignBlock consecutive columns (every thread takes part in every trip: the barriers), slot = column - first column of the trip
           for (int col0 = 0; col0 < S.proj.cols; col0 += kAlignBlock) {
@@ -571,7 +521,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
           }
         }
         else
-        if (LSM2D_BINWALK_BATCHED && kProjCulled && maos && faos) {
+        if (kProjCulled && maos && faos) {
           // Round 5: the walk as a two-deep pipeline -- the NEXT column's cells are read and gated (LDS) and its winners' two 16-byte rows asked for BEFORE this
           // column's factor terms are formed; the terms are added in the same column order as before (the sums keep their bits).  A trip used to end in two
           // dependent gathers from L2 that nothing covered: three exposed round trips per thread, iteration and slice; now the second and third travel under
@@ -1030,58 +980,4 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     if (A.host_polls) { __threadfence_system(); __hip_atomic_store(&A.out_status[a], st, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
     else A.out_status[a] = st;
   }
-}
-// Registers: 8 waves per SIMD (64 VGPRs, four workgroups per CU) for every single-finder instantiation.  The MIXED instantiations (a projective slice next to a
-// point-query slice in one aligner: all forms of all finders in one body) spilled 176 bytes per thread at that budget; they are given 4 waves per SIMD
-// (128 VGPRs, two workgroups per CU) and have no private segment -- a configuration no BASELINE workload uses (round 5; tools/isa_dump.sh prints every kernel's frame).
-#ifndef LSM2D_MIXED_MIN_WAVES
-#define LSM2D_MIXED_MIN_WAVES 4
-#endif
-#ifndef LSM2D_NNGLOBAL_MIN_WAVES
-#define LSM2D_NNGLOBAL_MIN_WAVES LSM2D_QUERY_MIN_WAVES      // k_align<0,1,0,0,1>: A/B knob (6: 80 VGPRs, no frame, three workgroups per CU)
-#endif
-template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd, int kNNMode>
-constexpr int align_min_waves() {
-  return (kHasProj && (kHasNN || kHasDist || kHasKd)) ? LSM2D_MIXED_MIN_WAVES : kHasProj ? LSM2D_ALIGN_MIN_WAVES : kNNMode == 1 ? LSM2D_NNGLOBAL_MIN_WAVES : LSM2D_QUERY_MIN_WAVES;
-}
-template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0>
-__global__ __launch_bounds__(kAlignBlock, (align_min_waves<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>())) void k_align(const AlignArgs A) {
-  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode>(A);
-}
-// Round 20: k_align<1,0,0,0,5> WITH the candidate lists (align_body's kCandLists) -- a kernel of its own, launched only for a batch the host has given a list's room
-// (AlignArgs::cand_off > 0); every other batch runs the kernel it always ran, instruction for instruction.
-__global__ __launch_bounds__(kAlignBlock, LSM2D_ALIGN_MIN_WAVES) void k_align_cand(const AlignArgs A) {
-  align_body<true, false, false, false, 5, false, kAlignBlock, true>(A);
-}
-#ifndef LSM2D_SEQ_MIN_WAVES
-#define LSM2D_SEQ_MIN_WAVES 8
-#endif
-// The culled projective stream with up to TWO alignments per workgroup, one after the other (AlignArgs::order2): the whole body again, from its prologue -- an
-// instantiation of its own (two copies of the body), so that the headline's kernel does not carry a loop around it (in one kernel: 80 bytes of scratch).
-__global__ __launch_bounds__(kAlignBlock, LSM2D_ALIGN_MIN_WAVES) void k_align_two(const AlignArgs A) {
-  align_body<true, false, false, false, 5>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
-  const int a2 = __builtin_amdgcn_readfirstlane(A.order2[blockIdx.x]);
-  if (a2 < 0) return;
-  __syncthreads();      // (thread 0 is done with the first one's results before anybody overwrites the state they came from)
-  align_body<true, false, false, false, 5>(A, a2);
-}
-// ... and the same with the reference's order of summation ("sum_order" 1: no narrow form exists for it, so every batch between one and two rounds is packed)
-__global__ __launch_bounds__(kAlignBlock, LSM2D_SEQ_MIN_WAVES) void k_align_seq_two(const AlignArgs A) {
-  align_body<true, false, false, false, 5, true>(A, __builtin_amdgcn_readfirstlane(A.order[blockIdx.x]));
-  const int a2 = __builtin_amdgcn_readfirstlane(A.order2[blockIdx.x]);
-  if (a2 < 0) return;
-  __syncthreads();
-  align_body<true, false, false, false, 5, true>(A, a2);
-}
-// The culled projective stream in NARROW workgroups (align_body's kW): 256 threads, six workgroups -- 1536 alignments -- resident per round where the wide kernel
-// holds 1024.  The same results as k_align<1,0,0,0,5>, bit for bit; chosen by the host (align_width_for) for batches just above a multiple of 1024 alignments.
-template <int kW>
-__global__ __launch_bounds__(kW, LSM2D_ALIGN_MIN_WAVES) void k_align_narrow(const AlignArgs A) {
-  align_body<true, false, false, false, 5, false, kW>(A);
-}
-// "sum_order" 1: the same kernel with the reference's order of summation (align_body<.., kSeq = true>).  14 KB of pair records per workgroup beside the canvases (four workgroups per CU still fit the headline's shape):
-// the register budget stays that of 8 waves per SIMD -- 4 for the mixed instantiations, as above
-template <bool kHasProj, bool kHasNN, bool kHasDist, bool kHasKd = false, int kNNMode = 0>
-__global__ __launch_bounds__(kAlignBlock, ((kHasProj && (kHasNN || kHasDist || kHasKd)) ? LSM2D_MIXED_MIN_WAVES : LSM2D_SEQ_MIN_WAVES)) void k_align_seq(const AlignArgs A) {
-  align_body<kHasProj, kHasNN, kHasDist, kHasKd, kNNMode, true>(A);
 }

@@ -130,10 +130,7 @@ LSM2D_DEV void unpack_fixed_set(const SliceDev& S, int tid, int nthreads) {
   if (tid == 0) *const_cast<int32_t*>(S.fixed.count) = S.unpack_n;
 }
 #ifndef LSM2D_ALIGN_MIN_WAVES
-#define LSM2D_ALIGN_MIN_WAVES 8      // waves per SIMD the register allocator must leave room for
-#endif
-#ifndef LSM2D_QUERY_MIN_WAVES
-#define LSM2D_QUERY_MIN_WAVES 8      // the same for the instantiations without a projective slice (point-query finders); 6 and 4 measured 15-50 % slower
+#define LSM2D_ALIGN_MIN_WAVES 8      // waves per SIMD the register allocator must leave room for (tools/variant_bench.sh builds with other values; the other kernels' budgets: lsm2d_k_align_kernels.h)
 #endif
 // SE2 odometry prior (AlignerSliceOdom2DPrior, MULTI.json:402-422): e = t2v(Z^-1 X), J = blkdiag(R_e, 1) for the right perturbation;
 // adds J^T Omega J to H and J^T Omega e to b.  One definition for k_align and the split path: the same operation order in both.

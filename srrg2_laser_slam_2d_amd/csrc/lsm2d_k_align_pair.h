@@ -63,9 +63,7 @@ LSM2D_DEV void pair_wave_sums(const Accum& A, float* red, int tid, bool cauchy, 
   }
 }
 
-#ifndef LSM2D_PAIR_READ_FIRST
-#define LSM2D_PAIR_READ_FIRST false      // z-buffer updates of the on-chip moving cloud: fire-and-forget (neighbouring lanes hold neighbouring columns' points)
-#endif
+// project_point<false> below: z-buffer updates of the on-chip moving cloud are fire-and-forget (neighbouring lanes hold neighbouring columns' points, so a read first saves no update)
 
 // kSeq ("sum_order" 1): H, b and the chi^2 sums pair after pair in the reference's order -- k_align_seq's bits (pose, H, status, iterations, statistics,
 // pair digest) for one or two projective slices, both slices' records walked at once (see "the reference's order" below); its LDS is k_align_pair<false>'s
@@ -230,8 +228,8 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
     if (on_chip) {
       // both clouds in LDS (the tracker's case): one point's z-buffer update per thread, then the walk one column at a time -- every gather is
       // an LDS row, so there is no latency worth a second column in flight, and a wave without a second column does not walk through one
-      if (tid < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p0.x, p0.y, tid, mcan);
-      if (j1 < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p1.x, p1.y, j1, mcan);
+      if (tid < m_count) project_point<false>(T, Pk, p0.x, p0.y, tid, mcan);
+      if (j1 < m_count) project_point<false>(T, Pk, p1.x, p1.y, j1, mcan);
       __syncthreads();
       LSM2D_PC(1);
       for (int col = tid; col < Pk.cols; col += kAlignBlock) {
@@ -250,8 +248,8 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
     } else {
     if (S.moving.lane_xy) project_cloud_lanes(S.moving.lane_xy + S.moving.lane_start[mc], S.moving.lane_T[mc], T, S.proj, mcan, tid, kAlignBlock);
     else if (m_on_chip) {         // the same points every iteration: no load, no wait
-      if (tid < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, S.proj, p0.x, p0.y, tid, mcan);
-      if (j1 < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, S.proj, p1.x, p1.y, j1, mcan);
+      if (tid < m_count) project_point<false>(T, S.proj, p0.x, p0.y, tid, mcan);
+      if (j1 < m_count) project_point<false>(T, S.proj, p1.x, p1.y, j1, mcan);
     }
     else project_cloud(mp, m_count, T, S.proj, mcan, tid, kAlignBlock);
     __syncthreads();
@@ -310,8 +308,8 @@ __global__ __launch_bounds__(kPairBlock) void k_align_pair(const AlignArgs A) {
       // waves meet every barrier -- also when the two canvases need different numbers of trips (the narrower slice's extra trips hold no records).
       if (S.moving.lane_xy) project_cloud_lanes(S.moving.lane_xy + S.moving.lane_start[mc], S.moving.lane_T[mc], T, S.proj, mcan, tid, kAlignBlock);
       else if (m_on_chip) {
-        if (tid < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p0.x, p0.y, tid, mcan);
-        if (j1 < m_count) project_point<LSM2D_PAIR_READ_FIRST>(T, Pk, p1.x, p1.y, j1, mcan);
+        if (tid < m_count) project_point<false>(T, Pk, p0.x, p0.y, tid, mcan);
+        if (j1 < m_count) project_point<false>(T, Pk, p1.x, p1.y, j1, mcan);
       }
       else project_cloud(mp, m_count, T, S.proj, mcan, tid, kAlignBlock);
       __syncthreads();

@@ -61,12 +61,8 @@ struct KdDev {
 template <bool kAllLds = false>
 LSM2D_DEV int kd_query_pos(const KdNode* __restrict__ nodes, const float2* __restrict__ lxy, float qx, float qy, float md2, float2& best_xy,
                            const float4* l_plane = nullptr, const int2* l_link = nullptr, int lds_nodes = 0) {
-#ifndef LSM2D_KD_NODE_TOGETHER
-#define LSM2D_KD_NODE_TOGETHER 1
-#endif
   int k = 0;
   int2 L;
-#if LSM2D_KD_NODE_TOGETHER
   // Round 6: a node's two halves -- its plane and its link, one 32-byte record -- are asked for TOGETHER as soon as the node is known.  (Before: the link first,
   // and the plane only inside the loop, behind the test of the link: below the levels staged in LDS every level of the descent cost two dependent trips to L2
   // instead of one.  The leaf's plane is fetched for nothing: the same line.)  The same tests on the same values: the same leaf.
@@ -81,16 +77,6 @@ LSM2D_DEV int kd_query_pos(const KdNode* __restrict__ nodes, const float2* __res
     k = L.x + (t < 0.0f ? 0 : 1);
     node(k);
   }
-#else
-  if (kAllLds || lds_nodes > 0) L = l_link[0]; else { const int4 w = reinterpret_cast<const int4*>(nodes)[1]; L = make_int2(w.x, w.y); }
-  while (L.x >= 0) {
-    float4 P;
-    if (kAllLds || k < lds_nodes) P = l_plane[k]; else P = reinterpret_cast<const float4*>(nodes)[2 * k];
-    const float t = (qx - P.x) * P.z + (qy - P.y) * P.w;
-    k = L.x + (t < 0.0f ? 0 : 1);
-    if (kAllLds || k < lds_nodes) L = l_link[k]; else { const int4 w = reinterpret_cast<const int4*>(nodes)[2 * k + 1]; L = make_int2(w.x, w.y); }
-  }
-#endif
   const int b = -1 - L.x, e = L.y;
   int bestpos = -1; float bd = md2;
   auto consider = [&](int j, float px, float py) {
@@ -141,10 +127,7 @@ struct CloudDev {            // device view of a cloud set
 // (2k+1)^2 block around q for k = 1, 2, 4, ... and stops as soon as the best distance is strictly inside the
 // block (every point outside it is farther than k*h, so it can neither win nor tie) or the block covers
 // max_distance.  Converged ICP queries finish in the first 3x3 block.
-#ifndef LSM2D_NN_GROUP
-#define LSM2D_NN_GROUP 4
-#endif
-static constexpr int kNNGroup = LSM2D_NN_GROUP;      // lanes that cooperate on one query on a dense fixed cloud: they read 4 consecutive candidates (32 bytes);
+static constexpr int kNNGroup = 4;      // lanes that cooperate on one query on a dense fixed cloud: they read 4 consecutive candidates (32 bytes);
                                         // measured on configs[1] role B with ~13 points per cell: 2 lanes 2.81 ms, 4 lanes 2.48, 8 lanes 2.76, 16 lanes 3.92;
                                         // again with two candidates per trip: 2.53 / 2.36 / 2.73 (the oracle's device-order mode encodes 4)
 

@@ -37,26 +37,19 @@ LSM2D_HD int cull_block_steps(int T, int nbs = kCullBlocks) { return 2 * ((T + 2
 // at full single-wave speed and the younger workgroups of a CU wait (tools/occupancy_probe.py: lifetimes 0.97 .. 2.19 ms in one
 // launch), so the last workgroup of a CU ends up alone, with nobody to issue under its barriers, bin walks and solves.  A
 // workgroup that lowers its priority as it advances lets the ones behind it catch up: all of a CU's workgroups finish together.
-// 0 off (1.86 ms on configs[1]), 1 quarters of the iterations (1.69), 2 halving intervals -- 1/2, 3/4, 7/8 (1.65).
-// 3 (-DLSM2D_PRIO_BY_PROGRESS=3, an A/B build): RISING with the iteration -- 0 below 4, 1, 2, and 3 from 8 on -- for launches behind the fast-forward, where
-// one alignment in ten reaches iteration 8 and is then what the launch waits for (measured: docs/REJECTED.md).
-#ifndef LSM2D_SEQ_WALK_PRIO
-#define LSM2D_SEQ_WALK_PRIO 1      // k_align_seq: the walking wave at top priority while it walks (configs[1], "sum_order" 1: 0.954 -> 0.937 ms; profiles/r06/sum_order_walker_quads_ab_r06.txt)
-#endif
-#ifndef LSM2D_PRIO_BY_PROGRESS
-#define LSM2D_PRIO_BY_PROGRESS 2
-#endif
-#ifndef LSM2D_ALIGN_BLOCK
-#define LSM2D_ALIGN_BLOCK 512
-#endif
-static constexpr int kAlignBlock = LSM2D_ALIGN_BLOCK;
+// The schedule is align_body's: halving intervals -- priority 3 for the first 1/2 of the iterations, 2 up to 3/4, 1 up to 7/8, then 0 (1.65 ms on configs[1]; off 1.86,
+// quarters of the iterations 1.69; those two and the schedule rising with the iteration are gone from the tree: docs/REJECTED.md).
+// k_align_seq's walking wave is at top priority while it walks (seq_walk<true>; configs[1], "sum_order" 1: 0.954 -> 0.937 ms; profiles/r06/sum_order_walker_quads_ab_r06.txt).
+static constexpr int kAlignBlock = 512;
 static constexpr int kFindBlock = 1024;
 
 #include "lsm2d_k_search.h"
 #include "lsm2d_k_structures.h"
 #include "lsm2d_k_kdbuild.h"
 #include "lsm2d_k_align_args.h"
+#include "lsm2d_k_align_probe.h"
 #include "lsm2d_k_align.h"
+#include "lsm2d_k_align_kernels.h"
 #include "lsm2d_k_placement.h"
 #include "lsm2d_k_align_pair.h"
 #include "lsm2d_k_split_finder.h"
