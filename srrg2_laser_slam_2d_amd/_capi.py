@@ -195,6 +195,5 @@ class Lsm2dError(RuntimeError):
 
 def check(code: int, where: str, ctx=None):
     if code < 0:
-        detail = load().lsm2d_last_error(ctx).decode() if True else ""
-        raise Lsm2dError(code, where, detail)
+        raise Lsm2dError(code, where, load().lsm2d_last_error(ctx).decode())
     return code

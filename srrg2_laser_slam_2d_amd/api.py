@@ -17,6 +17,7 @@ Errors: the reference throws ``std::runtime_error`` on missing inputs
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import weakref
 import dataclasses
@@ -91,39 +92,55 @@ class Context:
             pass
 
 
+def _ptr(a):
+    """a numpy array or a torch tensor as a pointer argument; None stays NULL"""
+    if a is None:
+        return None
+    return C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a.ctypes.data_as(C.c_void_p)
+
+
+_Made = collections.namedtuple("_Made", "handle n_clouds n_points counts capacity")      # a set the library has made already: CloudSet._adopt's way into __init__
+
+
 class CloudSet:
     """Device-resident ragged set of PointNormal2fVectorCloud (lsm2d_cloudset)."""
 
     def __init__(self, ctx: Context, points, offsets=None):
+        """``points``: float32 [N, 4] (x, y, nx, ny) on the host, or a torch tensor of that shape on ctx's device; ``offsets`` [n_clouds + 1] cuts them into
+        clouds (None: one cloud).  Every field a set has is set here and nowhere else."""
+        made = points if isinstance(points, _Made) else self._create(ctx, points, offsets)
         self._ctx = ctx
         self._lib = ctx._lib
-        h = C.c_void_p()
-        if hasattr(points, "data_ptr"):          # a torch tensor already on ctx's device
+        self._h = made.handle
+        self.n_clouds = made.n_clouds
+        self.capacity = made.capacity      # points a cloud of a reserved set has room for; None for every other set
+        self._n_points, self._counts = made.n_points, made.counts
+        self._pending = False
+        ctx._sets.add(self)
+
+    @classmethod
+    def _adopt(cls, ctx: Context, handle, n_clouds: int, n_points: int, counts: np.ndarray, capacity: Optional[int] = None) -> "CloudSet":
+        """The one way to put a CloudSet around a handle the library returned: every constructor ends here."""
+        return cls(ctx, _Made(handle, int(n_clouds), int(n_points), counts, capacity))
+
+    @staticmethod
+    def _create(ctx: Context, points, offsets) -> _Made:
+        """lsm2d_cloudset_create / _create_from_device: host points [N, 4] or a torch tensor already on ctx's device"""
+        if hasattr(points, "data_ptr"):
             if not points.is_cuda or not points.is_contiguous() or points.dtype.itemsize != 4 or points.shape[-1] != 4:
                 raise ValueError("device points must be a contiguous float32 [N, 4] tensor on the GPU")
-            total = int(points.shape[0])
-            offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
-            n_clouds = 1 if offs is None else len(offs) - 1
+            pts, create = points, ctx._lib.lsm2d_cloudset_create_from_device
             _producer_stream_wait(points)
-            rc = self._lib.lsm2d_cloudset_create_from_device(
-                ctx.handle, C.c_void_p(points.data_ptr()), None if offs is None else offs.ctypes.data_as(C.c_void_p),
-                n_clouds, total, C.byref(h))
         else:
-            pts = np.ascontiguousarray(points, np.float32)
+            pts, create = np.ascontiguousarray(points, np.float32), ctx._lib.lsm2d_cloudset_create
             if pts.ndim != 2 or pts.shape[1] != 4:
                 raise ValueError("points must be [N, 4] (x, y, nx, ny)")
-            total = len(pts)
-            offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
-            n_clouds = 1 if offs is None else len(offs) - 1
-            rc = self._lib.lsm2d_cloudset_create(ctx.handle, pts.ctypes.data_as(C.c_void_p),
-                                                 None if offs is None else offs.ctypes.data_as(C.c_void_p),
-                                                 n_clouds, total, C.byref(h))
-        check(rc, "lsm2d_cloudset_create", ctx.handle)
-        self._h = h
-        ctx._sets.add(self)
-        self.n_clouds = n_clouds
-        self.n_points = total
-        self.counts = np.array([total], np.int64) if offs is None else np.diff(offs.astype(np.int64))
+        total = int(pts.shape[0])
+        offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        n_clouds = 1 if offs is None else len(offs) - 1
+        h = C.c_void_p()
+        check(create(ctx.handle, _ptr(pts), _ptr(offs), n_clouds, total, C.byref(h)), "lsm2d_cloudset_create", ctx.handle)
+        return _Made(h, n_clouds, total, np.array([total], np.int64) if offs is None else np.diff(offs.astype(np.int64)), None)
 
     @property
     def handle(self):
@@ -132,34 +149,24 @@ class CloudSet:
     @classmethod
     def reserved(cls, ctx: Context, capacity: int) -> "CloudSet":
         """One growable device cloud (the local map a tracker keeps merging into / a clipped scene)."""
-        self = cls.__new__(cls)
-        self._ctx, self._lib = ctx, ctx._lib
         h = C.c_void_p()
         check(ctx._lib.lsm2d_cloudset_create_reserved(ctx.handle, int(capacity), C.byref(h)), "lsm2d_cloudset_create_reserved", ctx.handle)
-        self._h, self.n_clouds, self.n_points, self.counts, self.capacity = h, 1, 0, np.zeros(1, np.int64), int(capacity)
-        ctx._sets.add(self)
-        return self
+        return cls._adopt(ctx, h, 1, 0, np.zeros(1, np.int64), int(capacity))
 
     @classmethod
     def reserved_many(cls, ctx: Context, n_clouds: int, capacity: int) -> "CloudSet":
         """``n_clouds`` growable device clouds, each with room for ``capacity`` points (the local maps of N trackers, or their clipped
         scenes: lsm2d_cloudset_create_reserved_many).  The single-cloud calls refuse such a set; the batched clipper / merger fill it."""
-        self = cls.__new__(cls)
-        self._ctx, self._lib = ctx, ctx._lib
         h = C.c_void_p()
         check(ctx._lib.lsm2d_cloudset_create_reserved_many(ctx.handle, int(n_clouds), int(capacity), C.byref(h)),
               "lsm2d_cloudset_create_reserved_many", ctx.handle)
-        self._h, self.n_clouds, self.n_points, self.counts, self.capacity = h, int(n_clouds), 0, np.zeros(int(n_clouds), np.int64), int(capacity)
-        self._many = True
-        ctx._sets.add(self)
-        return self
+        return cls._adopt(ctx, h, n_clouds, 0, np.zeros(int(n_clouds), np.int64), int(capacity))
 
     def clear(self, indices=None):
         """Empties clouds ``indices`` (None: all) of a ``reserved_many`` set, asynchronously (lsm2d_cloudset_clear_clouds)."""
         idx = None if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
-        check(self._lib.lsm2d_cloudset_clear_clouds(self._h, 0 if idx is None else len(idx), None if idx is None else idx.ctypes.data_as(C.c_void_p)),
-              "lsm2d_cloudset_clear_clouds", self._ctx.handle)
-        if not getattr(self, "_pending", False):
+        check(self._lib.lsm2d_cloudset_clear_clouds(self._h, 0 if idx is None else len(idx), _ptr(idx)), "lsm2d_cloudset_clear_clouds", self._ctx.handle)
+        if not self._pending:
             c = self._counts.copy(); c[slice(None) if idx is None else idx] = 0
             self._counts = c; self._n_points = int(c.sum())
 
@@ -171,29 +178,22 @@ class CloudSet:
         self._resolve()
         return self._n_points
 
-    @n_points.setter
-    def n_points(self, v):
-        self._n_points = int(v)
-
     @property
     def counts(self) -> np.ndarray:
         self._resolve()
         return self._counts
 
-    @counts.setter
-    def counts(self, v):
-        self._counts = v
-
     def _resolve(self):
-        if getattr(self, "_pending", False) and self.n_clouds > 1:      # all sizes of a multi-cloud set with one wait
+        if not self._pending:
+            return
+        if self.n_clouds > 1:      # all sizes of a multi-cloud set with one wait
             c = np.empty(self.n_clouds, np.int32)
-            check(min(self._lib.lsm2d_cloudset_cloud_sizes(self._h, c.ctypes.data_as(C.c_void_p), self.n_clouds), 0), "lsm2d_cloudset_cloud_sizes", self._ctx.handle)
-            self._pending = False
-            self._n_points = int(c.sum()); self._counts = c.astype(np.int64)
-        elif getattr(self, "_pending", False):
-            n = int(self._lib.lsm2d_cloudset_cloud_size(self._h, 0))
-            self._pending = False
-            self._n_points = n; self._counts = np.array([n], np.int64)
+            check(min(self._lib.lsm2d_cloudset_cloud_sizes(self._h, _ptr(c), self.n_clouds), 0), "lsm2d_cloudset_cloud_sizes", self._ctx.handle)
+            counts = c.astype(np.int64)
+        else:
+            counts = np.array([int(self._lib.lsm2d_cloudset_cloud_size(self._h, 0))], np.int64)
+        self._pending = False
+        self._n_points, self._counts = int(counts.sum()), counts
 
     def _set_count(self, n: int):
         self._pending = False
@@ -206,14 +206,13 @@ class CloudSet:
         """Refill this single-cloud set in place (no allocation, no wait for the stream: the points are copied into the
         set's pinned staging buffer before the call returns)."""
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-        check(self._lib.lsm2d_cloudset_upload(self._h, pts.ctypes.data_as(C.c_void_p), len(pts)), "lsm2d_cloudset_upload", self._ctx.handle)
+        check(self._lib.lsm2d_cloudset_upload(self._h, _ptr(pts), len(pts)), "lsm2d_cloudset_upload", self._ctx.handle)
         self._set_count(len(pts))
 
     def download(self, cloud_index: int = 0) -> np.ndarray:
         cap = int(self.counts[cloud_index])
         out = np.empty((max(cap, 1), 4), np.float32); n = C.c_int64(0)
-        check(self._lib.lsm2d_cloudset_download(self._h, cloud_index, out.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
-              "lsm2d_cloudset_download", self._ctx.handle)
+        check(self._lib.lsm2d_cloudset_download(self._h, cloud_index, _ptr(out), cap, C.byref(n)), "lsm2d_cloudset_download", self._ctx.handle)
         return out[: n.value].copy()
 
     def close(self):
@@ -241,11 +240,6 @@ def _as_cloudset(ctx: Context, cloud) -> CloudSet:
     return cloud if isinstance(cloud, CloudSet) else CloudSet(ctx, cloud)
 
 
-def _ptr(a):
-    """a numpy array as a pointer argument; None stays NULL"""
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 class _BatchItems:
     """The items of a batched finder / factor / score call, marshalled once for every wrapper of the family: the sets as CloudSet, ``poses`` as float32
     ``[n, 3]``, the optional index arrays as int32 ``[n]`` or NULL.  ``head(slice_params)`` is the argument list all these entry points begin with (context,
@@ -262,6 +256,17 @@ class _BatchItems:
 
     def head(self, slice_params: SliceParams) -> tuple:
         return (self.ctx.handle, C.byref(slice_params), self.fixed.handle, _ptr(self.fixed_index), self.moving.handle, _ptr(self.moving_index), self.n)
+
+
+def _pair_capacity(slice_params: SliceParams, moving: CloudSet, moving_index: Optional[int] = None) -> int:
+    """How many pairs a slice can return, at least 1 (an output buffer is never empty): the projective finder gives at most one per canvas column, the
+    others at most one per moving point -- of cloud ``moving_index``, or of the set's largest cloud when the call spans the set."""
+    if slice_params.finder == FINDER_PROJECTIVE:
+        return max(int(slice_params.projector.canvas_cols), 1)
+    counts = moving.counts
+    if moving_index is not None:
+        return max(int(counts[moving_index]), 1)
+    return max(int(counts.max()) if len(counts) else 0, 1)
 
 
 @dataclasses.dataclass
@@ -286,9 +291,7 @@ class PointNormal2fProjectorPolar:
         src = np.empty(cols, np.int32); depth = np.empty(cols, np.float32); xy = np.empty((cols, 4), np.float32)
         pose = np.ascontiguousarray(pose, np.float32)
         pr = self.struct()
-        check(ctx._lib.lsm2d_project(ctx.handle, C.byref(pr), cs.handle, cloud_index, pose.ctypes.data_as(C.c_void_p),
-                                     src.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p),
-                                     xy.ctypes.data_as(C.c_void_p)), "lsm2d_project", ctx.handle)
+        check(ctx._lib.lsm2d_project(ctx.handle, C.byref(pr), cs.handle, cloud_index, _ptr(pose), _ptr(src), _ptr(depth), _ptr(xy)), "lsm2d_project", ctx.handle)
         return src, depth, xy
 
 
@@ -320,23 +323,18 @@ class _FinderBase:
     def slice_params(self, **kw) -> SliceParams:
         raise NotImplementedError
 
-    def _capacity(self) -> int:
-        raise NotImplementedError
-
     def compute(self) -> np.ndarray:
         if self._fixed is None:
             raise RuntimeError(type(self).__name__ + "::compute| Missing fixed!")
         if self._moving is None:
             raise RuntimeError(type(self).__name__ + "::compute| Missing moving!")
         sp = self.slice_params()
-        cap = max(self._capacity(), 1)
+        cap = _pair_capacity(sp, self._moving, self._moving_index)
         out = np.empty((cap, 2), np.int32)
         n = C.c_int32(0)
         lib = self._ctx._lib
-        check(lib.lsm2d_find_correspondences(self._ctx.handle, C.byref(sp), self._fixed.handle, self._fixed_index,
-                                             self._moving.handle, self._moving_index,
-                                             self._local_map_in_sensor.ctypes.data_as(C.c_void_p),
-                                             out.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
+        check(lib.lsm2d_find_correspondences(self._ctx.handle, C.byref(sp), self._fixed.handle, self._fixed_index, self._moving.handle, self._moving_index,
+                                             _ptr(self._local_map_in_sensor), _ptr(out), cap, C.byref(n)),
               "lsm2d_find_correspondences", self._ctx.handle)
         self._correspondences = out[:n.value].copy()
         return self._correspondences
@@ -349,11 +347,7 @@ class _FinderBase:
         ctx = self._ctx
         it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
         sp = self.slice_params()
-        if sp.finder == FINDER_PROJECTIVE:
-            cap = int(sp.projector.canvas_cols)
-        else:
-            cap = int(max(it.moving.counts)) if len(it.moving.counts) else 0
-        cap = max(cap, 1)
+        cap = _pair_capacity(sp, it.moving)
         out = np.empty((it.rows, cap, 2), np.int32); cnt = np.zeros(it.rows, np.int32)
         check(ctx._lib.lsm2d_find_correspondences_batch(*it.head(sp), _ptr(it.poses), _ptr(out), cap, _ptr(cnt)), "lsm2d_find_correspondences_batch", ctx.handle)
         return [out[i, : cnt[i]].copy() for i in range(it.n)]
@@ -375,9 +369,6 @@ class CorrespondenceFinderProjective2f(_FinderBase):
             raise RuntimeError("CorrespondenceFinderProjective2f::compute| Missing Projector")
         return make_slice_params(finder=FINDER_PROJECTIVE, projector=self.param_projector,
                                  point_distance=self.param_point_distance, normal_cos=self.param_normal_cos, **kw)
-
-    def _capacity(self) -> int:
-        return self.param_projector.param_canvas_cols
 
 
 class CorrespondenceFinderKDTree2D(_FinderBase):
@@ -406,9 +397,6 @@ class CorrespondenceFinderKDTree2D(_FinderBase):
                                  max_distance=self.param_max_distance_m, normal_cos=self.param_normal_cos,
                                  kd_max_leaf_range=self.param_max_leaf_range, kd_min_leaf_points=self.param_min_leaf_points, **kw)
 
-    def _capacity(self) -> int:
-        return int(self._moving.counts[self._moving_index])
-
 
 class CorrespondenceFinderNN2D(_FinderBase):
     """registration/correspondence_finder_nn_2d.{h,cpp}: distance-map finder (one grid lookup per query)."""
@@ -428,9 +416,6 @@ class CorrespondenceFinderNN2D(_FinderBase):
         return make_slice_params(finder=_capi.FINDER_DISTMAP, projector=PointNormal2fProjectorPolar(),
                                  max_distance=self.param_max_distance_m, resolution=self.param_resolution,
                                  normal_cos=self.param_normal_cos, **kw)
-
-    def _capacity(self) -> int:
-        return int(self._moving.counts[self._moving_index])
 
 
 def make_slice_params(finder=FINDER_PROJECTIVE, projector: Optional[PointNormal2fProjectorPolar] = None,
@@ -512,11 +497,27 @@ class BatchResult:
         chi_inliers / inliers <= max, inliers / correspondences >= ratio.  The relocaliser uses the same test with
         700 / 0.01 / 0.75 (MULTI.json:749-769).  Returns bool [n]."""
         st = self.last_stats()
-        n_in = st["n_inliers"].astype(np.float64); n_c = np.maximum(st["n_correspondences"], 1).astype(np.float64)
-        ok = (self.status == 0) & (st["n_inliers"] >= relocalize_min_inliers)
-        ok &= st["chi_inliers"] / np.maximum(n_in, 1.0) <= relocalize_max_chi_inliers
-        ok &= n_in / n_c >= relocalize_min_inliers_ratio
-        return ok
+        return (self.status == 0) & _accept(st["n_inliers"], st["n_correspondences"], st["chi_inliers"], relocalize_min_inliers, relocalize_max_chi_inliers,
+                                            relocalize_min_inliers_ratio)
+
+    @classmethod
+    def _from_arrays(cls, ctx: Context, arrays, timed: bool, copy: bool = False, pairs=None) -> "BatchResult":
+        """The result of an aligner call from the arrays it wrote, ``(pose [n, 3], H [n, 9], status, iterations, stats or None)``: as they are, or copies
+        of them.  timed: the call was a k_align launch with the context's events around it, so the three timing reads are its own."""
+        if copy:
+            arrays = [None if a is None else a.copy() for a in arrays]
+        pose, H, status, iterations, stats = arrays
+        if not timed:
+            return cls(pose, H.reshape(len(pose), 3, 3), status, iterations, stats, 0.0, 0.0, 0.0, pairs)
+        return cls(pose, H.reshape(len(pose), 3, 3), status, iterations, stats, ctx.last_kernel_ms(), ctx.get_option("last_kernel_clock_khz") * 1e-3,
+                   ctx.get_option("last_workgroup_lifetime_ns") * 1e-6, pairs)
+
+
+def _accept(n_inliers, n_correspondences, chi_inliers, min_inliers, max_chi_inliers, min_inliers_ratio) -> np.ndarray:
+    """The loop detector's acceptance test in float64, on statistics: inliers >= min, chi_inliers / inliers <= max, inliers / correspondences >= ratio
+    (``_select_accept`` is the device's float32 form of it).  bool [n]."""
+    n_in = np.asarray(n_inliers, np.float64); n_c = np.maximum(np.asarray(n_correspondences, np.float64), 1.0)
+    return (n_in >= min_inliers) & (np.asarray(chi_inliers, np.float64) / np.maximum(n_in, 1.0) <= max_chi_inliers) & (n_in / n_c >= min_inliers_ratio)
 
 
 STATS_DTYPE = np.dtype([("n_correspondences", np.int32), ("n_inliers", np.int32), ("n_outliers", np.int32),
@@ -524,9 +525,19 @@ STATS_DTYPE = np.dtype([("n_correspondences", np.int32), ("n_inliers", np.int32)
                         ("pair_digest_lo", np.uint32), ("pair_digest_hi", np.uint32)])
 
 
+def _result_arrays(lib, aligner_params: AlignerParams, n: int, want_stats: bool) -> tuple:
+    """the arrays an aligner call of ``n`` alignments writes: (pose, H, status, iterations, stats or None), in the order of the ABI's arguments"""
+    stats = np.zeros((n, int(lib.lsm2d_stats_capacity(C.byref(aligner_params)))), STATS_DTYPE) if want_stats else None
+    return np.empty((n, 3), np.float32), np.empty((n, 9), np.float32), np.empty(n, np.int32), np.empty(n, np.int32), stats
+
+
 def pair_digests(stats: np.ndarray) -> np.ndarray:
     """uint64 digest of every iteration's correspondence set (lsm2d_iteration_stats.pair_digest_lo / _hi)."""
     return (stats["pair_digest_hi"].astype(np.uint64) << np.uint64(32)) | stats["pair_digest_lo"].astype(np.uint64)
+
+
+# what a batch descriptor (MultiAligner2D._batch) points to; the index arrays and the priors are None where the call has none
+_BatchKeep = collections.namedtuple("_BatchKeep", "fixed_sets moving_sets slices fixed_handles moving_handles x0 fixed_index moving_index prior")
 
 
 class MultiAligner2D:
@@ -609,77 +620,67 @@ class MultiAligner2D:
         slices = self.param_slice_processors
         ns = len(slices)
         b, keep = self._batch(fixed, moving, init_poses, priors, fixed_index, moving_index)
-        n = b.n_alignments; moving_sets = keep[1]
-        ap = AlignerParams(self.param_max_iterations, self.param_min_num_inliers, self.param_damping, self.param_termination_chi_epsilon,
-                           1 if self.param_enable_inlier_only_runs else 0, 1 if self.param_keep_only_inlier_correspondences else 0)
-        pose = np.empty((n, 3), np.float32); H = np.empty((n, 9), np.float32)
-        status = np.empty(n, np.int32); its = np.empty(n, np.int32)
-        stats = np.zeros((n, int(lib.lsm2d_stats_capacity(C.byref(ap)))), STATS_DTYPE) if want_stats else None
+        n = b.n_alignments
+        ap = self._aligner_params()
+        arrays = _result_arrays(lib, ap, n, want_stats)
+        out = [_ptr(a) for a in arrays]
         pairs = None
         if want_pairs and n:
-            cap = 1
-            for s_, m_ in zip(slices, moving_sets):
-                sp_ = s_.slice_params()
-                cap = max(cap, sp_.projector.canvas_cols if sp_.finder == FINDER_PROJECTIVE else int(max(m_.counts)) if len(m_.counts) else 1)
+            cap = max([_pair_capacity(s.slice_params(), m) for s, m in zip(slices, keep.moving_sets)], default=1)
             pbuf = np.empty((n, ns, cap, 2), np.int32); pcnt = np.zeros((n, ns), np.int32)
-            check(lib.lsm2d_align_batch_pairs(ctx.handle, C.byref(ap), C.byref(b), pose.ctypes.data_as(C.c_void_p),
-                                              H.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p), its.ctypes.data_as(C.c_void_p),
-                                              stats.ctypes.data_as(C.c_void_p) if want_stats else None,
-                                              pbuf.ctypes.data_as(C.c_void_p), cap, pcnt.ctypes.data_as(C.c_void_p)),
-                  "lsm2d_align_batch_pairs", ctx.handle)
+            check(lib.lsm2d_align_batch_pairs(ctx.handle, C.byref(ap), C.byref(b), *out, _ptr(pbuf), cap, _ptr(pcnt)), "lsm2d_align_batch_pairs", ctx.handle)
             pairs = [[pbuf[i, s_, : pcnt[i, s_]].copy() for s_ in range(ns)] for i in range(n)]
         else:
-            check(lib.lsm2d_align_batch(ctx.handle, C.byref(ap), C.byref(b), pose.ctypes.data_as(C.c_void_p),
-                                        H.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p),
-                                        its.ctypes.data_as(C.c_void_p),
-                                        stats.ctypes.data_as(C.c_void_p) if want_stats else None),
-                  "lsm2d_align_batch", ctx.handle)
+            check(lib.lsm2d_align_batch(ctx.handle, C.byref(ap), C.byref(b), *out), "lsm2d_align_batch", ctx.handle)
         timed = bool(n and ctx.kernel_timing) and not pairs      # (the finder passes behind a pairs call overwrite the timed events)
-        return BatchResult(pose, H.reshape(n, 3, 3), status, its, stats, ctx.last_kernel_ms() if timed else 0.0,
-                           ctx.get_option("last_kernel_clock_khz") * 1e-3 if timed else 0.0,
-                           ctx.get_option("last_workgroup_lifetime_ns") * 1e-6 if timed else 0.0, pairs)
+        return BatchResult._from_arrays(ctx, arrays, timed, pairs=pairs)
 
+    def _aligner_params(self) -> AlignerParams:
+        """lsm2d_aligner_params of this aligner as it is configured now"""
+        return AlignerParams(self.param_max_iterations, self.param_min_num_inliers, self.param_damping, self.param_termination_chi_epsilon,
+                             1 if self.param_enable_inlier_only_runs else 0, 1 if self.param_keep_only_inlier_correspondences else 0)
 
-def _batch_method(self, fixed, moving, init_poses, priors=None, fixed_index=None, moving_index=None):
-    """lsm2d_batch descriptor of a call (and everything it points to, to be kept alive by the caller)"""
-    ctx = self._ctx
-    slices = self.param_slice_processors
-    ns = len(slices)
-    x0 = np.array(init_poses, dtype=np.float32, order="C", copy=True).reshape(-1, 3)      # the descriptor's OWN copy (round-4 advisor: PreparedBatch.set_init_poses wrote into the caller's array)
-    n = len(x0)
-    sp = (SliceParams * ns)(*[s.slice_params() for s in slices])
-    fixed_sets = [_as_cloudset(ctx, f) for f in fixed]          # keep host-array uploads alive for the duration of the call
-    moving_sets = [_as_cloudset(ctx, m) for m in moving]
-    fx = (C.c_void_p * ns)(*[f.handle.value for f in fixed_sets])
-    mv = (C.c_void_p * ns)(*[m.handle.value for m in moving_sets])
-    b = Batch()
-    b.n_alignments, b.n_slices = n, ns
-    b.slices = sp
-    b.fixed = C.cast(fx, C.POINTER(C.c_void_p)); b.moving = C.cast(mv, C.POINTER(C.c_void_p))
-    keep = [fixed_sets, moving_sets, sp, fx, mv, x0]
-    if fixed_index is not None:
-        fi = np.ascontiguousarray(fixed_index, np.int32).reshape(ns, n); keep.append(fi)
-        b.fixed_index = fi.ctypes.data_as(C.POINTER(C.c_int32))
-    if moving_index is not None:
-        mi = np.ascontiguousarray(moving_index, np.int32).reshape(ns, n); keep.append(mi)
-        b.moving_index = mi.ctypes.data_as(C.POINTER(C.c_int32))
-    b.init_pose = x0.ctypes.data_as(C.POINTER(C.c_float))
-    if priors is not None:
-        pr = (Prior * n)()
-        for i, (z, om) in enumerate(priors):
-            pr[i].z = (C.c_float * 3)(*np.asarray(z, np.float32).ravel())
-            pr[i].omega = (C.c_float * 9)(*np.asarray(om, np.float32).ravel())
-        b.prior = pr; keep.append(pr)
-    return b, keep
+    def _batch(self, fixed, moving, init_poses, priors=None, fixed_index=None, moving_index=None):
+        """lsm2d_batch descriptor of a call, and in ``keep`` (a ``_BatchKeep``) everything it points to, to be kept alive by the caller"""
+        ctx = self._ctx
+        slices = self.param_slice_processors
+        ns = len(slices)
+        x0 = np.array(init_poses, dtype=np.float32, order="C", copy=True).reshape(-1, 3)      # the descriptor's OWN copy (round-4 advisor: PreparedBatch.set_init_poses wrote into the caller's array)
+        n = len(x0)
+        sp = (SliceParams * ns)(*[s.slice_params() for s in slices])
+        fixed_sets = [_as_cloudset(ctx, f) for f in fixed]          # keep host-array uploads alive for the duration of the call
+        moving_sets = [_as_cloudset(ctx, m) for m in moving]
+        fx = (C.c_void_p * ns)(*[f.handle.value for f in fixed_sets])
+        mv = (C.c_void_p * ns)(*[m.handle.value for m in moving_sets])
+        fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(ns, n)
+        mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(ns, n)
+        pr = None
+        if priors is not None:
+            pr = (Prior * n)()
+            for i, (z, om) in enumerate(priors):
+                pr[i].z = (C.c_float * 3)(*np.asarray(z, np.float32).ravel())
+                pr[i].omega = (C.c_float * 9)(*np.asarray(om, np.float32).ravel())
+        b = Batch()
+        b.n_alignments, b.n_slices = n, ns
+        b.slices = sp
+        b.fixed = C.cast(fx, C.POINTER(C.c_void_p)); b.moving = C.cast(mv, C.POINTER(C.c_void_p))
+        b.fixed_index = C.cast(_ptr(fi), C.POINTER(C.c_int32)); b.moving_index = C.cast(_ptr(mi), C.POINTER(C.c_int32))
+        b.init_pose = C.cast(_ptr(x0), C.POINTER(C.c_float))
+        if pr is not None:
+            b.prior = pr
+        return b, _BatchKeep(fixed_sets, moving_sets, sp, fx, mv, x0, fi, mi, pr)
 
+    def estimate_work(self, fixed, moving, init_poses, fixed_index=None, moving_index=None) -> np.ndarray:
+        """lsm2d_estimate_work: per alignment, what it will cost relative to the others (chunks of the moving cloud its first iteration streams),
+        without running it -- what a sweep sharded over devices or ranks balances its shards by (distributed.shard_by_work).  int32 [n]."""
+        b, keep = self._batch(fixed, moving, init_poses, None, fixed_index, moving_index)
+        work = np.empty(b.n_alignments, np.int32)
+        check(self._ctx._lib.lsm2d_estimate_work(self._ctx.handle, C.byref(b), _ptr(work)), "lsm2d_estimate_work", self._ctx.handle)
+        return work
 
-def _estimate_work_method(self, fixed, moving, init_poses, fixed_index=None, moving_index=None) -> np.ndarray:
-    """lsm2d_estimate_work: per alignment, what it will cost relative to the others (chunks of the moving cloud its first iteration streams),
-    without running it -- what a sweep sharded over devices or ranks balances its shards by (distributed.shard_by_work).  int32 [n]."""
-    b, keep = self._batch(fixed, moving, init_poses, None, fixed_index, moving_index)
-    work = np.empty(b.n_alignments, np.int32)
-    check(self._ctx._lib.lsm2d_estimate_work(self._ctx.handle, C.byref(b), work.ctypes.data_as(C.c_void_p)), "lsm2d_estimate_work", self._ctx.handle)
-    return work
+    def prepare_batch(self, fixed, moving, init_poses, priors=None, fixed_index=None, moving_index=None, want_stats: bool = False) -> "PreparedBatch":
+        """compute_batch's arguments, marshalled once: ``prepare_batch(...).run()`` == ``compute_batch(...)`` (tests), call after call."""
+        return PreparedBatch(self, fixed, moving, init_poses, priors, fixed_index, moving_index, want_stats)
 
 
 class PreparedBatch:
@@ -694,18 +695,15 @@ class PreparedBatch:
         self._aligner = aligner
         self._ctx = aligner._ctx
         self._b, self._keep = aligner._batch(fixed, moving, init_poses, priors, fixed_index, moving_index)
-        self._x0 = self._keep[5]
-        n = self._b.n_alignments
-        self._ap = AlignerParams(aligner.param_max_iterations, aligner.param_min_num_inliers, aligner.param_damping, aligner.param_termination_chi_epsilon,
-                                 1 if aligner.param_enable_inlier_only_runs else 0, 1 if aligner.param_keep_only_inlier_correspondences else 0)
+        self._x0 = self._keep.x0
+        self._ap = aligner._aligner_params()
         lib = self._ctx._lib
-        self.pose = np.empty((n, 3), np.float32); self._H = np.empty((n, 9), np.float32)
-        self.status = np.empty(n, np.int32); self.iterations = np.empty(n, np.int32)
-        self.stats = np.zeros((n, int(lib.lsm2d_stats_capacity(C.byref(self._ap)))), STATS_DTYPE) if want_stats else None
-        self._args = (self._ctx.handle, C.byref(self._ap), C.byref(self._b), self.pose.ctypes.data_as(C.c_void_p), self._H.ctypes.data_as(C.c_void_p),
-                      self.status.ctypes.data_as(C.c_void_p), self.iterations.ctypes.data_as(C.c_void_p),
-                      self.stats.ctypes.data_as(C.c_void_p) if want_stats else None)
+        self._arrays = _result_arrays(lib, self._ap, self._b.n_alignments, want_stats)
+        self.pose, self._H, self.status, self.iterations, self.stats = self._arrays
+        self._out = tuple(_ptr(a) for a in self._arrays)
+        self._args = (self._ctx.handle, C.byref(self._ap), C.byref(self._b)) + self._out
         self._fn = lib.lsm2d_align_batch
+        self._pending = None      # the handle of lsm2d_align_batch_begin while the batch is in flight
 
     def set_init_poses(self, init_poses) -> None:
         self._x0[...] = np.asarray(init_poses, np.float32).reshape(self._x0.shape)
@@ -713,7 +711,7 @@ class PreparedBatch:
     def begin(self) -> None:
         """lsm2d_align_batch_begin: queue the batch and return; ``wait()`` hands its results over.  At most two batches of a context may be in flight, waited for in
         the order they were begun -- two PreparedBatch objects alternating (each keeps its own result arrays)."""
-        if getattr(self, "_pending", None) is not None:
+        if self._pending is not None:
             raise RuntimeError("PreparedBatch.begin: this batch is in flight already")
         h = C.c_void_p()
         check(self._ctx._lib.lsm2d_align_batch_begin(self._ctx.handle, C.byref(self._ap), C.byref(self._b), 1 if self.stats is not None else 0, C.byref(h)),
@@ -721,27 +719,17 @@ class PreparedBatch:
         self._pending = h
 
     def wait(self, copy: bool = False) -> BatchResult:
-        if getattr(self, "_pending", None) is None:
+        if self._pending is None:
             raise RuntimeError("PreparedBatch.wait: nothing in flight")
         h, self._pending = self._pending, None
         ctx = self._ctx
-        check(ctx._lib.lsm2d_align_batch_wait(h, self._args[3], self._args[4], self._args[5], self._args[6], self._args[7]), "lsm2d_align_batch_wait", ctx.handle)
-        n = self._b.n_alignments
-        timed = bool(n and ctx.kernel_timing)
-        c = (lambda a: None if a is None else a.copy()) if copy else (lambda a: a)
-        return BatchResult(c(self.pose), c(self._H).reshape(n, 3, 3), c(self.status), c(self.iterations), c(self.stats), ctx.last_kernel_ms() if timed else 0.0,
-                           ctx.get_option("last_kernel_clock_khz") * 1e-3 if timed else 0.0,
-                           ctx.get_option("last_workgroup_lifetime_ns") * 1e-6 if timed else 0.0, None)
+        check(ctx._lib.lsm2d_align_batch_wait(h, *self._out), "lsm2d_align_batch_wait", ctx.handle)
+        return BatchResult._from_arrays(ctx, self._arrays, bool(self._b.n_alignments and ctx.kernel_timing), copy)
 
     def run(self, copy: bool = False) -> BatchResult:
         ctx = self._ctx
         check(self._fn(*self._args), "lsm2d_align_batch", ctx.handle)
-        n = self._b.n_alignments
-        timed = bool(n and ctx.kernel_timing)
-        c = (lambda a: None if a is None else a.copy()) if copy else (lambda a: a)
-        return BatchResult(c(self.pose), c(self._H).reshape(n, 3, 3), c(self.status), c(self.iterations), c(self.stats), ctx.last_kernel_ms() if timed else 0.0,
-                           ctx.get_option("last_kernel_clock_khz") * 1e-3 if timed else 0.0,
-                           ctx.get_option("last_workgroup_lifetime_ns") * 1e-6 if timed else 0.0, None)
+        return BatchResult._from_arrays(ctx, self._arrays, bool(self._b.n_alignments and ctx.kernel_timing), copy)
 
 
 def run_pipelined(batches, copy: bool = True):
@@ -759,16 +747,6 @@ def run_pipelined(batches, copy: bool = True):
         yield prev.wait(copy=copy)
 
 
-def _prepare_batch_method(self, fixed, moving, init_poses, priors=None, fixed_index=None, moving_index=None, want_stats: bool = False) -> PreparedBatch:
-    """compute_batch's arguments, marshalled once: ``prepare_batch(...).run()`` == ``compute_batch(...)`` (tests), call after call."""
-    return PreparedBatch(self, fixed, moving, init_poses, priors, fixed_index, moving_index, want_stats)
-
-
-MultiAligner2D._batch = _batch_method
-MultiAligner2D.estimate_work = _estimate_work_method
-MultiAligner2D.prepare_batch = _prepare_batch_method
-
-
 def linearize(ctx: Context, slice_params: SliceParams, fixed, moving, correspondences, pose,
               fixed_index: int = 0, moving_index: int = 0):
     """SE2Plane2PlaneErrorFactor over a correspondence vector: returns (H [3,3], b [3], IterationStats)."""
@@ -777,9 +755,7 @@ def linearize(ctx: Context, slice_params: SliceParams, fixed, moving, correspond
     pose = np.ascontiguousarray(pose, np.float32)
     H = np.empty(9, np.float32); b = np.empty(3, np.float32); st = IterationStats()
     check(ctx._lib.lsm2d_linearize(ctx.handle, C.byref(slice_params), fx.handle, fixed_index, mv.handle, moving_index,
-                                   corr.ctypes.data_as(C.c_void_p), len(corr), pose.ctypes.data_as(C.c_void_p),
-                                   H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(st)),
-          "lsm2d_linearize", ctx.handle)
+                                   _ptr(corr), len(corr), _ptr(pose), _ptr(H), _ptr(b), C.byref(st)), "lsm2d_linearize", ctx.handle)
     return H.reshape(3, 3), b, st
 
 
@@ -830,9 +806,8 @@ def score_accept(stats, relocalize_min_inliers: int = 500, relocalize_max_chi_in
     """``BatchResult.loop_closure_accept``'s test (MULTI.json:964-986; the relocaliser's 700 / 0.01 / 0.75: :749-769) on the statistics ``score_batch``
     returns, minus the aligner's status, which a scored hypothesis does not have: inliers >= min, chi_inliers / inliers <= max,
     inliers / correspondences >= ratio.  Returns bool [n]."""
-    n_in = np.array([s.n_inliers for s in stats], np.float64); n_c = np.array([max(s.n_correspondences, 1) for s in stats], np.float64)
-    chi = np.array([s.chi_inliers for s in stats], np.float64)
-    return (n_in >= relocalize_min_inliers) & (chi / np.maximum(n_in, 1.0) <= relocalize_max_chi_inliers) & (n_in / n_c >= relocalize_min_inliers_ratio)
+    st = _stats_array(stats)
+    return _accept(st["n_inliers"], st["n_correspondences"], st["chi_inliers"], relocalize_min_inliers, relocalize_max_chi_inliers, relocalize_min_inliers_ratio)
 
 
 @dataclasses.dataclass
@@ -915,11 +890,10 @@ def score_aligner(aligner: "MultiAligner2D", fixed, moving, poses, priors=None, 
     structured STATS_DTYPE [n], active int32 [n])``; ``active[i]`` counts the slices that contributed (0: zeros, the hypothesis an aligner would end with
     NotEnoughCorrespondences).  With ``"sum_order"`` 1 an item is the sequential oracle's ``align(max_iterations=1)`` bit for bit."""
     ctx = aligner._ctx
-    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)      # (keep: what bd points to, alive until this function returns)
     n = bd.n_alignments; rows = max(n, 1)
     H = np.empty((rows, 9), np.float32); b = np.empty((rows, 3), np.float32); st = np.zeros(rows, STATS_DTYPE); active = np.zeros(rows, np.int32)
     check(ctx._lib.lsm2d_score_aligner_batch(ctx.handle, C.byref(bd), _ptr(H), _ptr(b), _ptr(st), _ptr(active)), "lsm2d_score_aligner_batch", ctx.handle)
-    del keep
     return H[:n].reshape(n, 3, 3), b[:n], st[:n], active[:n]
 
 
@@ -928,7 +902,7 @@ def score_aligner_select(aligner: "MultiAligner2D", fixed, moving, poses, select
     hypothesis no slice contributed to is rejected.  Returns ``(index int32 [m], H [m, 3, 3], b [m, 3], stats [m], active int32 [m], n_accepted)``,
     ``m = min(k, n_accepted)``, best first: ``index`` is ``score_rank(stats, select, k, active)`` on ``score_aligner``'s results, the rows are its rows."""
     ctx = aligner._ctx
-    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)      # (keep: as in score_aligner)
     kk = max(int(k), 1)
     index = np.empty(kk, np.int32); H = np.empty((kk, 9), np.float32); b = np.empty((kk, 3), np.float32); st = np.zeros(kk, STATS_DTYPE)
     active = np.zeros(kk, np.int32)
@@ -936,7 +910,6 @@ def score_aligner_select(aligner: "MultiAligner2D", fixed, moving, poses, select
     sel = select.struct()
     check(ctx._lib.lsm2d_score_aligner_select(ctx.handle, C.byref(bd), C.byref(sel), int(k), _ptr(index), _ptr(H), _ptr(b), _ptr(st), _ptr(active),
                                               C.byref(n_sel), C.byref(n_acc)), "lsm2d_score_aligner_select", ctx.handle)
-    del keep
     m = n_sel.value
     return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], active[:m], n_acc.value
 
@@ -956,34 +929,11 @@ def relocalize(aligner: MultiAligner2D, fixed, moving, poses, select: SelectPara
     the last iteration each started.  Pure composition: the same as calling the two entry points by hand.
     An aligner with several slices and / or ``priors`` (one ``(z, omega)`` per hypothesis) takes ``fixed`` / ``moving`` as lists of sets, one per slice
     (``*_index``: ``[n_slices][n]``), scores with ``score_aligner_select`` and hands the selected hypotheses' priors on to the aligner."""
-    ns = len(aligner.param_slice_processors)
-    if ns != 1 or priors is not None or isinstance(fixed, (list, tuple)) or isinstance(moving, (list, tuple)):
-        return _relocalize_aligner(aligner, fixed, moving, poses, select, k, fixed_index, moving_index, priors)
-    ctx = aligner._ctx
-    fx, mv = _as_cloudset(ctx, fixed), _as_cloudset(ctx, moving)
-    x = np.ascontiguousarray(poses, np.float32).reshape(-1, 3)
-    n = len(x)
-    index, _, _, st, n_acc = score_select(ctx, aligner.param_slice_processors[0].slice_params(), fx, mv, x, select, k, fixed_index, moving_index)
-
-    def chosen(cs, idx):      # the selected items' clouds, spelled out: NULL means "cloud i" only while the batch is the whole set
-        if idx is None and cs.n_clouds == 1:
-            return None
-        full = np.arange(n, dtype=np.int32) if idx is None else np.ascontiguousarray(idx, np.int32).reshape(n)
-        return full[index][None, :]
-
-    if not len(index):      # nothing passed: nothing to align
-        z = np.zeros
-        return RelocalizeResult(index, st, n_acc, BatchResult(z((0, 3), np.float32), z((0, 3, 3), np.float32), z(0, np.int32), z(0, np.int32), None, 0.0), z(0, bool))
-    res = aligner.compute_batch([fx], [mv], x[index], fixed_index=chosen(fx, fixed_index), moving_index=chosen(mv, moving_index), want_stats=True)
-    return RelocalizeResult(index, st, n_acc, res, (res.status == 0) & _select_accept(res.last_stats(), select))
-
-
-def _relocalize_aligner(aligner, fixed, moving, poses, select, k, fixed_index, moving_index, priors) -> RelocalizeResult:
-    """``relocalize`` for an aligner with several slices and / or priors: ``score_aligner_select``, then ``compute_batch`` on the selected hypotheses"""
     ctx = aligner._ctx
     ns = len(aligner.param_slice_processors)
     if ns < 1:
         raise ValueError("relocalize: the aligner has no slice")
+    whole_aligner = ns != 1 or priors is not None or isinstance(fixed, (list, tuple)) or isinstance(moving, (list, tuple))
     as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
     fx = [_as_cloudset(ctx, f) for f in as_list(fixed)]; mv = [_as_cloudset(ctx, m) for m in as_list(moving)]
     if len(fx) != ns or len(mv) != ns:
@@ -992,9 +942,12 @@ def _relocalize_aligner(aligner, fixed, moving, poses, select, k, fixed_index, m
     n = len(x)
     if priors is not None and len(priors) != n:
         raise ValueError("relocalize: one prior per hypothesis")
-    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(ns, n)
+    fi = None if fixed_index is None else np.ascontiguousarray(fixed_index, np.int32).reshape(ns, n)      # (one slice without priors: the [1, n] case)
     mi = None if moving_index is None else np.ascontiguousarray(moving_index, np.int32).reshape(ns, n)
-    index, _, _, st, _, n_acc = score_aligner_select(aligner, fx, mv, x, select, k, priors, fi, mi)
+    if whole_aligner:
+        index, _, _, st, _, n_acc = score_aligner_select(aligner, fx, mv, x, select, k, priors, fi, mi)
+    else:
+        index, _, _, st, n_acc = score_select(ctx, aligner.param_slice_processors[0].slice_params(), fx[0], mv[0], x, select, k, fi, mi)
     if not len(index):      # nothing passed: nothing to align
         z = np.zeros
         return RelocalizeResult(index, st, n_acc, BatchResult(z((0, 3), np.float32), z((0, 3, 3), np.float32), z(0, np.int32), z(0, np.int32), None, 0.0), z(0, bool))
@@ -1056,8 +1009,7 @@ class SceneClipperProjective2D:
         pr = self.param_projector.struct()
         vox = float(self.param_voxelize_resolution)
         lib = self._ctx._lib
-        args = (self._ctx.handle, C.byref(pr), self._full_scene.handle, 0, self._robot_in_local_map.ctypes.data_as(C.c_void_p),
-                self._sensor_in_robot.ctypes.data_as(C.c_void_p))
+        args = (self._ctx.handle, C.byref(pr), self._full_scene.handle, 0, _ptr(self._robot_in_local_map), _ptr(self._sensor_in_robot))
 
         def call(out_n, out_src):      # voxelize_resolution > 0: the branch of scene_clipper_projective_2d.cpp:36-48 (no source indices)
             if vox > 0:
@@ -1070,7 +1022,7 @@ class SceneClipperProjective2D:
             self.source_indices = np.zeros(0, np.int32)
             return self._clipped
         n = C.c_int32(0); src = np.empty(cols, np.int32)
-        call(C.byref(n), src.ctypes.data_as(C.c_void_p))
+        call(C.byref(n), _ptr(src))
         self._clipped._set_count(n.value)
         self.source_indices = src[: n.value].copy() if not vox > 0 else np.zeros(0, np.int32)
         return self._clipped
@@ -1089,9 +1041,8 @@ class SceneClipperProjective2D:
         vox = float(self.param_voxelize_resolution)
         out = None if self.asynchronous else np.empty(n, np.int32)
         lib = self._ctx._lib
-        head = (self._ctx.handle, C.byref(pr), scenes.handle, n, None if idx is None else idx.ctypes.data_as(C.c_void_p),
-                poses.ctypes.data_as(C.c_void_p), self._sensor_in_robot.ctypes.data_as(C.c_void_p))
-        tail = (clipped.handle, None if out is None else out.ctypes.data_as(C.c_void_p))
+        head = (self._ctx.handle, C.byref(pr), scenes.handle, n, _ptr(idx), _ptr(poses), _ptr(self._sensor_in_robot))
+        tail = (clipped.handle, _ptr(out))
         if vox > 0:
             check(lib.lsm2d_clip_scene_voxelized_batch(*head, vox, *tail), "lsm2d_clip_scene_voxelized_batch", self._ctx.handle)
         else:
@@ -1129,23 +1080,25 @@ class MergerProjective2D:
         if self._scene is None or self._measurement is None:
             raise RuntimeError("MergerProjective2D::compute| missing scene or measurement")
         pr = self.param_projector.struct()
-        if self.asynchronous:
-            check(self._ctx._lib.lsm2d_merge_scene(self._ctx.handle, C.byref(pr), self._scene.handle, self._measurement.handle,
-                                                   self._measurement_index, self._measurement_in_scene.ctypes.data_as(C.c_void_p),
-                                                   float(self.param_merge_threshold), None, None),
-                  "lsm2d_merge_scene", self._ctx.handle)
-            self._scene._set_pending()
-            self.counts = (0, 0, 0)
-            return -1
-        size = C.c_int32(0); counts = (C.c_int32 * 3)()
-        check(self._ctx._lib.lsm2d_merge_scene(self._ctx.handle, C.byref(pr), self._scene.handle, self._measurement.handle,
-                                               self._measurement_index, self._measurement_in_scene.ctypes.data_as(C.c_void_p),
-                                               float(self.param_merge_threshold), C.byref(size), counts),
+        size, counts = self._outputs(1)
+        check(self._ctx._lib.lsm2d_merge_scene(self._ctx.handle, C.byref(pr), self._scene.handle, self._measurement.handle, self._measurement_index,
+                                               _ptr(self._measurement_in_scene), float(self.param_merge_threshold), None if size is None else C.byref(size), counts),
               "lsm2d_merge_scene", self._ctx.handle)
-        self._scene._set_count(size.value)
-        self.counts = tuple(counts)
-        return size.value
+        self.counts = (0, 0, 0) if counts is None else tuple(counts)
+        return self._scene_size(size)
 
+    def _outputs(self, n_measurements: int):
+        """What lsm2d_merge_scene / _scenes write when somebody waits for it: the scene's new size and one (new, merged, replaced) triple per measurement.
+        Asynchronous: nobody waits, None (NULL) both."""
+        return (None, None) if self.asynchronous else (C.c_int32(0), (C.c_int32 * (3 * n_measurements))())
+
+    def _scene_size(self, size) -> int:
+        """tells the scene its new size -- or, asynchronous, that the device alone knows it (-1)"""
+        if size is None:
+            self._scene._set_pending()
+            return -1
+        self._scene._set_count(size.value)
+        return size.value
 
     def compute_all(self, measurements: Sequence, poses, indices: Optional[Sequence[int]] = None) -> int:
         """Merges several measurements, each at its own pose in the scene, in the given order -- what one setMeasurement /
@@ -1161,18 +1114,11 @@ class MergerProjective2D:
         p = np.ascontiguousarray(poses, np.float32).reshape(n, 3)
         idx = None if indices is None else (C.c_int32 * n)(*[int(i) for i in indices])      # which cloud of each (multi-cloud) set
         pr = self.param_projector.struct()
-        if self.asynchronous:
-            check(self._ctx._lib.lsm2d_merge_scenes(self._ctx.handle, C.byref(pr), self._scene.handle, n, handles, idx, p.ctypes.data_as(C.c_void_p),
-                                                    float(self.param_merge_threshold), None, None), "lsm2d_merge_scenes", self._ctx.handle)
-            self._scene._set_pending()
-            self.counts = (0, 0, 0)
-            return -1
-        size = C.c_int32(0); counts = (C.c_int32 * (3 * n))()
-        check(self._ctx._lib.lsm2d_merge_scenes(self._ctx.handle, C.byref(pr), self._scene.handle, n, handles, idx, p.ctypes.data_as(C.c_void_p),
-                                                float(self.param_merge_threshold), C.byref(size), counts), "lsm2d_merge_scenes", self._ctx.handle)
-        self._scene._set_count(size.value)
-        self.counts = [tuple(counts[3 * k:3 * k + 3]) for k in range(n)]
-        return size.value
+        size, counts = self._outputs(n)
+        check(self._ctx._lib.lsm2d_merge_scenes(self._ctx.handle, C.byref(pr), self._scene.handle, n, handles, idx, _ptr(p), float(self.param_merge_threshold),
+                                                None if size is None else C.byref(size), counts), "lsm2d_merge_scenes", self._ctx.handle)
+        self.counts = (0, 0, 0) if counts is None else [tuple(counts[3 * k:3 * k + 3]) for k in range(n)]
+        return self._scene_size(size)
 
     def compute_batch(self, scenes: CloudSet, measurements: Sequence[CloudSet], poses, scene_index=None, meas_index=None):
         """compute_all() for N trackers at once (lsm2d_merge_scene_batch): cloud ``scene_index[i]`` (None: i) of the ``reserved_many``
@@ -1189,17 +1135,11 @@ class MergerProjective2D:
         pr = self.param_projector.struct()
         sizes = None if self.asynchronous else np.empty(n, np.int32)
         counts = None if self.asynchronous else np.empty((n, k, 3), np.int32)
-        check(self._ctx._lib.lsm2d_merge_scene_batch(self._ctx.handle, C.byref(pr), scenes.handle, n, None if sidx is None else sidx.ctypes.data_as(C.c_void_p),
-                                                     k, handles, None if midx is None else midx.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
-                                                     float(self.param_merge_threshold), None if sizes is None else sizes.ctypes.data_as(C.c_void_p),
-                                                     None if counts is None else counts.ctypes.data_as(C.c_void_p)), "lsm2d_merge_scene_batch", self._ctx.handle)
+        check(self._ctx._lib.lsm2d_merge_scene_batch(self._ctx.handle, C.byref(pr), scenes.handle, n, _ptr(sidx), k, handles, _ptr(midx), _ptr(p),
+                                                     float(self.param_merge_threshold), _ptr(sizes), _ptr(counts)), "lsm2d_merge_scene_batch", self._ctx.handle)
         scenes._set_pending()
         self.counts = counts
         return sizes
-
-
-def _data_pointer(a):
-    return C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a.ctypes.data_as(C.c_void_p)
 
 
 class RawDataPreprocessorProjective2D:
@@ -1233,38 +1173,33 @@ class RawDataPreprocessorProjective2D:
         self._msg = (r, float(angle_min), float(angle_max), float(range_min), float(range_max))
         return True
 
-    def compute(self) -> CloudSet:
+    def _message(self):
+        """the ranges set with setRawData and their lsm2d_preprocessor: the message's limits clamped by this preprocessor's"""
         if self._msg is None:
             raise RuntimeError("RawDataPreprocessorProjective2D::compute| no raw data")
         r, a0, a1, m_rmin, m_rmax = self._msg
-        pp = _capi.Preprocessor(r.shape[1], a0, a1, max(m_rmin, self.param_range_min), min(m_rmax, self.param_range_max),   # .cpp:83-84
-                                self.param_normal_point_distance, self.param_normal_min_points, self.param_voxelize_resolution)
+        return r, _capi.Preprocessor(r.shape[1], a0, a1, max(m_rmin, self.param_range_min), min(m_rmax, self.param_range_max),   # .cpp:83-84
+                                     self.param_normal_point_distance, self.param_normal_min_points, self.param_voxelize_resolution)
+
+    def compute(self) -> CloudSet:
+        r, pp = self._message()
+        ctx, lib = self._ctx, self._ctx._lib
         h = C.c_void_p()
         _producer_stream_wait(r)
-        check(self._ctx._lib.lsm2d_preprocess_scans(self._ctx.handle, C.byref(pp), _data_pointer(r), r.shape[0], C.byref(h)),
-              "lsm2d_preprocess_scans", self._ctx.handle)
-        cs = CloudSet.__new__(CloudSet)
-        cs._ctx, cs._lib, cs._h = self._ctx, self._ctx._lib, h
-        self._ctx._sets.add(cs)
-        cs.n_clouds = r.shape[0]
-        cs.n_points = int(self._ctx._lib.lsm2d_cloudset_num_points(h))
+        check(lib.lsm2d_preprocess_scans(ctx.handle, C.byref(pp), _ptr(r), r.shape[0], C.byref(h)), "lsm2d_preprocess_scans", ctx.handle)
+        n_points = lib.lsm2d_cloudset_num_points(h)
         sizes = np.empty(r.shape[0], np.int32)
-        check(min(self._ctx._lib.lsm2d_cloudset_cloud_sizes(h, sizes.ctypes.data_as(C.c_void_p), len(sizes)), 0), "lsm2d_cloudset_cloud_sizes", self._ctx.handle)
-        cs.counts = sizes.astype(np.int64)
-        self._meas = cs
-        return cs
+        check(min(lib.lsm2d_cloudset_cloud_sizes(h, _ptr(sizes), len(sizes)), 0), "lsm2d_cloudset_cloud_sizes", ctx.handle)
+        self._meas = CloudSet._adopt(ctx, h, r.shape[0], n_points, sizes.astype(np.int64))
+        return self._meas
 
     def refill(self, out: CloudSet) -> CloudSet:
         """The streaming form: the batch of messages set with setRawData goes into ``out`` -- a set an earlier ``compute()`` made for the same number of scans
         and beams -- with no allocation and no wait (lsm2d_preprocess_scans_refill): the ranges are fetched by an asynchronous copy (keep them untouched until
         the batch that reads ``out`` has been waited for), the clouds' sizes stay on the device.  Same kernel, same bits as ``compute()``."""
-        if self._msg is None:
-            raise RuntimeError("RawDataPreprocessorProjective2D::compute| no raw data")
-        r, a0, a1, m_rmin, m_rmax = self._msg
-        pp = _capi.Preprocessor(r.shape[1], a0, a1, max(m_rmin, self.param_range_min), min(m_rmax, self.param_range_max),
-                                self.param_normal_point_distance, self.param_normal_min_points, self.param_voxelize_resolution)
+        r, pp = self._message()
         _producer_stream_wait(r)
-        check(self._ctx._lib.lsm2d_preprocess_scans_refill(self._ctx.handle, C.byref(pp), _data_pointer(r), r.shape[0], out.handle),
+        check(self._ctx._lib.lsm2d_preprocess_scans_refill(self._ctx.handle, C.byref(pp), _ptr(r), r.shape[0], out.handle),
               "lsm2d_preprocess_scans_refill", self._ctx.handle)
         self._meas = out
         return out
@@ -1272,17 +1207,12 @@ class RawDataPreprocessorProjective2D:
     def compute_into(self, out: CloudSet) -> CloudSet:
         """The live tracker's form: the ONE scan set with setRawData goes into the reserved set ``out`` -- no allocation,
         nothing waits; the cloud's size stays on the device until it is read (lsm2d_preprocess_scan_into)."""
-        if self._msg is None:
-            raise RuntimeError("RawDataPreprocessorProjective2D::compute| no raw data")
-        r, a0, a1, m_rmin, m_rmax = self._msg
+        r, pp = self._message()
         if r.shape[0] != 1:
             raise ValueError("compute_into takes one scan")
-        pp = _capi.Preprocessor(r.shape[1], a0, a1, max(m_rmin, self.param_range_min), min(m_rmax, self.param_range_max),
-                                self.param_normal_point_distance, self.param_normal_min_points, self.param_voxelize_resolution)
         if hasattr(r, "data_ptr") and r.is_cuda:
             raise ValueError("compute_into stages the scan from host memory")
-        check(self._ctx._lib.lsm2d_preprocess_scan_into(self._ctx.handle, C.byref(pp), _data_pointer(r), out.handle),
-              "lsm2d_preprocess_scan_into", self._ctx.handle)
+        check(self._ctx._lib.lsm2d_preprocess_scan_into(self._ctx.handle, C.byref(pp), _ptr(r), out.handle), "lsm2d_preprocess_scan_into", self._ctx.handle)
         out._set_pending()
         self._meas = out
         return out
