@@ -60,7 +60,10 @@ extern "C" {
                                     ALIGNER -- all its slices, sensor offsets, the skip rule and the optional prior -- in one call with one wait, and ranked
                                     on the device);
                              (0.7.6, number unchanged: an addition only) + lsm2d_clip_scene_voxelized_batch (lsm2d_clip_scene_batch with the clipper's
-                                    voxelize_resolution > 0 branch inside the same launch, the single voxelised call's bits per tracker) */
+                                    voxelize_resolution > 0 branch inside the same launch, the single voxelised call's bits per tracker);
+                             (0.7.7, number unchanged: an addition only) + lsm2d_align_select, lsm2d_sweep_align_select (lsm2d_align_batch's alignment, then
+                                    the candidate loops' acceptance test -- status term included -- and the best k aligned candidates ranked on the device:
+                                    only k rows come down, whatever the iteration count is) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -568,6 +571,35 @@ int lsm2d_align_batch(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, c
                       int32_t* out_iterations,          /* [n]     iterations started; may be NULL */
                       lsm2d_iteration_stats* out_stats  /* [n][lsm2d_stats_capacity(aligner)]; may be NULL */);
 
+/* lsm2d_align_batch's alignment, then the verdict of the candidate loops (MultiLoopDetectorBruteForce2D, MultiRelocalizer2D: MULTI.json:964-986, :749-769)
+ * made on the device: which candidates' aligner succeeded AND whose last iteration passes the thresholds, and which k of those are best.  What a caller
+ * otherwise gets by asking lsm2d_align_batch for every iteration's statistics (lsm2d_stats_capacity x 28 bytes per candidate: 55 MB for 65 536 candidates
+ * of a 30-iteration aligner) and scanning them on the host.
+ * Alignment: candidate i is aligned exactly as lsm2d_align_batch(..., out_stats != NULL) aligns it -- the same path rule, kernels and launch forms, the
+ * same bits in both values of "sum_order" and every value of "fast_forward" -- with ONE exception: the results stay in device memory, so the zero-copy
+ * form (results written to pinned host memory) is not taken, whatever "zero_copy_max" says.
+ * Acceptance (PARITY.md section 3, items 18 and 18c): candidate i is accepted when status[i] == LSM2D_SUCCESS, iterations[i] >= 1 and lsm2d_score_select's
+ * fp32 test passes on row iterations[i] - 1 of its statistics -- the last iteration it started.  A candidate that started no iteration is rejected.
+ * Ranking: lsm2d_score_select's total order on that last row -- n_inliers descending, chi_inliers ascending on its bit pattern, candidate index ascending.
+ * Outputs: *out_n_accepted the accepted candidates among all n_alignments; *out_n_selected = min(k, n_accepted); *out_n_success (may be NULL) the candidates
+ * with status LSM2D_SUCCESS; out_index[0 .. n_selected) the selected candidates, best first; rows j < n_selected of out_pose / out_H / out_iterations
+ * (the last two may be NULL) the bits lsm2d_align_batch returns for candidate out_index[j], out_last_stats[j] (may be NULL) its statistics row
+ * iterations - 1.  Positions >= n_selected are not written.
+ * Refused before anything is launched or written: a NULL the call needs (ctx, aligner, batch, select, out_index, out_pose, the two count pointers) or k
+ * outside [1, LSM2D_SELECT_MAX_K] (LSM2D_BAD_ARGUMENT), and whatever lsm2d_align_batch refuses: a bad descriptor, cloud indices out of range, canvases
+ * that do not fit LDS, two batches in flight.  n_alignments == 0 succeeds with all counts 0.
+ * Up: what lsm2d_align_batch sends up.  Down: ONE copy of [n_accepted, n_selected, n_success, never-reported | k indices | k rows of 96 bytes].  ONE wait.
+ * The check that every alignment's workgroup reported is made on the device (the fourth header word): non-zero is LSM2D_DEVICE_ERROR, as for
+ * lsm2d_align_batch.  The call is synchronous (there is no begin / wait form); with one batch in flight it works on the free lane like every other call.
+ * "kernel_timing" / lsm2d_last_kernel_ms cover the aligner's launch PLUS the packing and the selection behind it.  The read-only options
+ * "last_cand_builds" / "last_cand_iterations" / "last_cand_overflows" are derived from arrays that stay on the device here: after this call they keep
+ * the previous call's values. */
+int lsm2d_align_select(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, const lsm2d_batch* batch,
+                       const lsm2d_select_params* select, int32_t k,
+                       int32_t* out_index /* [k] */, float* out_pose /* [k][3] */, float* out_H /* [k][9] or NULL */,
+                       int32_t* out_iterations /* [k] or NULL */, lsm2d_iteration_stats* out_last_stats /* [k] or NULL */,
+                       int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success /* or NULL */);
+
 /* ---- pose hypotheses scored against an ALIGNER (the two-laser robot's relocaliser, MULTI.json:700-732 with the slices at :715-721 and the odometry
  * prior of :402-422; its relocaliser's own aligner is unset, :749-769, so it falls back on this one): lsm2d_score_batch / lsm2d_score_select for a
  * lsm2d_batch -- up to 4 slices, WithSensor offsets, min_num_correspondences, an optional prior per hypothesis -- in ONE call with ONE wait.
@@ -674,6 +706,13 @@ int     lsm2d_sweep_set_scans(lsm2d_sweep* sweep, const float* scans_xynn, const
 int     lsm2d_sweep_align(lsm2d_sweep* sweep, const lsm2d_aligner_params* aligner, const lsm2d_slice_params* slice, int32_t n_candidates,
                           const int32_t* scan_index, const float* init_pose, float* out_pose, float* out_H, int32_t* out_status,
                           int32_t* out_iterations, lsm2d_iteration_stats* out_last_stats);
+/* ... with the verdict made on the devices: every shard runs lsm2d_align_select with the same k on its block of candidates, the host merges the <= G x k
+ * rows by the same key over GLOBAL candidate indices and sums the counts.  The order is total, so the result does not depend on G: it is
+ * lsm2d_align_select's on one device, bit for bit.  Outputs and refusals as there (out_H / out_iterations / out_last_stats / out_n_success may be NULL). */
+int     lsm2d_sweep_align_select(lsm2d_sweep* sweep, const lsm2d_aligner_params* aligner, const lsm2d_slice_params* slice, int32_t n_candidates,
+                                 const int32_t* scan_index, const float* init_pose, const lsm2d_select_params* select, int32_t k,
+                                 int32_t* out_index, float* out_pose, float* out_H, int32_t* out_iterations, lsm2d_iteration_stats* out_last_stats,
+                                 int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,10 @@ SYMBOLS = [
     ("lsm2d_score_aligner_batch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, _P]),
     ("lsm2d_score_aligner_select", C.c_int, [_P, C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32)]),
+    ("lsm2d_align_select", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, _P, _P, _P, _P, _P,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("lsm2d_sweep_align_select", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(SliceParams), C.c_int32, _P, _P, C.POINTER(SelectParamsC), C.c_int32,
+                                           _P, _P, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

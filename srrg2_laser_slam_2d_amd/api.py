@@ -914,6 +914,63 @@ def score_aligner_select(aligner: "MultiAligner2D", fixed, moving, poses, select
     return index[:m], H[:m].reshape(m, 3, 3), b[:m], st[:m], active[:m], n_acc.value
 
 
+def last_stats_rows(iterations, stats) -> np.ndarray:
+    """Row ``iterations[i] - 1`` of every candidate's statistics ``[n, capacity]`` -- the last iteration it started -- as a structured STATS_DTYPE array
+    ``[n]``; a candidate that started none gets zeros (lsm2d_sweep_align's ``out_last_stats``).  ``stats`` of one dimension is taken as those rows already."""
+    its = np.asarray(iterations, np.int64).reshape(-1)
+    st = np.asarray(stats)
+    if st.ndim == 1:
+        last = st.copy()
+    else:
+        last = st[np.arange(len(its)), np.clip(its - 1, 0, st.shape[1] - 1)] if len(its) else np.zeros(0, STATS_DTYPE)
+    last[its < 1] = np.zeros(1, STATS_DTYPE)[0]
+    return last
+
+
+def align_rank(status, iterations, stats, select: SelectParams, k: int):
+    """lsm2d_align_select's acceptance test and ranking on results the caller already holds (a ``BatchResult``'s or the oracle's), in numpy float32 /
+    integer arithmetic: candidate i is accepted when ``status[i] == 0``, ``iterations[i] >= 1`` and ``_select_accept`` passes on row ``iterations[i] - 1``
+    of its statistics; the accepted are ranked by ``score_rank``'s key on that row -- inliers descending, chi_inliers ascending on its bit pattern, index
+    ascending.  ``stats``: structured ``[n, capacity]`` (every iteration's rows) or ``[n]`` (the last rows).  Returns ``(index int32 [min(k, n_accepted)],
+    n_accepted, n_success)``."""
+    status = np.asarray(status).reshape(-1); its = np.asarray(iterations).reshape(-1)
+    ok = (status == 0) & (its >= 1)
+    index, n_acc = score_rank(last_stats_rows(its, stats), select, k, active=ok.astype(np.int32))
+    return index, n_acc, int(np.count_nonzero(status == 0))
+
+
+@dataclasses.dataclass
+class AlignSelectResult:
+    index: np.ndarray          # int32 [m]: the selected candidates, best first; m = min(k, n_accepted)
+    pose: np.ndarray           # [m, 3]: compute_batch's pose of candidate index[j]
+    information: np.ndarray    # [m, 3, 3]
+    iterations: np.ndarray     # int32 [m]
+    last_stats: np.ndarray     # structured [m]: the statistics of the last iteration each started
+    n_accepted: int            # candidates whose aligner succeeded and whose last iteration passes the thresholds, of all
+    n_success: int             # candidates whose aligner succeeded, of all
+    kernel_ms: float = 0.0     # the aligner's launch plus the selection (0 when the context is not timed)
+
+
+def align_select(aligner: "MultiAligner2D", fixed, moving, init_poses, select: SelectParams, k: int, priors=None, fixed_index=None,
+                 moving_index=None) -> AlignSelectResult:
+    """``aligner.compute_batch(..., want_stats=True)``'s alignment, then the candidate loops' verdict made on the device (lsm2d_align_select): aligner
+    succeeded, the last started iteration passes ``select``, the best ``k`` of those ranked -- ``k`` rows come down with one copy and one wait, not every
+    iteration's statistics of every candidate.  ``index`` is ``align_rank`` on ``compute_batch``'s results, the rows are its rows, bit for bit."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, init_poses, priors, fixed_index, moving_index)      # (keep: what bd points to, alive until this function returns)
+    ap = aligner._aligner_params()
+    kk = max(int(k), 1)
+    index = np.empty(kk, np.int32); pose = np.empty((kk, 3), np.float32); H = np.empty((kk, 9), np.float32); its = np.empty(kk, np.int32)
+    st = np.zeros(kk, STATS_DTYPE)
+    n_sel = C.c_int32(0); n_acc = C.c_int32(0); n_suc = C.c_int32(0)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_align_select(ctx.handle, C.byref(ap), C.byref(bd), C.byref(sel), int(k), _ptr(index), _ptr(pose), _ptr(H), _ptr(its), _ptr(st),
+                                      C.byref(n_sel), C.byref(n_acc), C.byref(n_suc)), "lsm2d_align_select", ctx.handle)
+    m = n_sel.value
+    ms = ctx.last_kernel_ms() if (bd.n_alignments and ctx.kernel_timing) else 0.0
+    return AlignSelectResult(index[:m], pose[:m], H[:m].reshape(m, 3, 3), its[:m], st[:m], n_acc.value, n_suc.value, ms)
+
+
 @dataclasses.dataclass
 class RelocalizeResult:
     index: np.ndarray          # int32 [m]: the selected hypotheses, best first

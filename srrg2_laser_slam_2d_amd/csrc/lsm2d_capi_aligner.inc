@@ -10,6 +10,8 @@
 //   estimate_only | make_placement  lsm2d_estimate_work's answer | the balanced placement of a culled batch (k_cull_estimate), kept for an unchanged batch
 //   launch                        the kernels, the events, the copies of the results
 //   hand_over                     a lsm2d_pending for an asynchronous begin, or the wait and the results (align_batch_finish)
+// SELECT mode (lsm2d_align_select: AlignBatch::select != NULL) runs the same stages with the results kept on the device -- no zero-copy form, no results written
+// to pinned host memory, no copy of them queued -- and hand_over ends in k_align_rows and select_queue<AlignRow>: k rows come down (select_finish).
 // ---- plugin interface #2 ----------------------------------------------------------------------------------------
 extern "C" uint64_t lsm2d_pair_hash(uint32_t slice, uint32_t fixed_idx, uint32_t moving_idx) {      // the kernels' pair_hash_dev, on the host
   const uint32_t a = fixed_idx * 0x9E3779B1u, b = (moving_idx ^ (slice * 0x632BE5ABu)) * 0x85EBCA77u;
@@ -117,6 +119,11 @@ struct AlignBatch {
   bool proj_culled_for_all, nn_lds_for_all;
   // ---- inputs, results
   bool same_inputs, host_results, stamps;
+  // ---- select mode (lsm2d_align_select): the thresholds and k (NULL: every other call), where the rows and the selection's part of the scratch lie, what it hands back
+  const lsm2d_select_params* select = nullptr; int32_t select_k = 0;
+  size_t o_rows = 0, o_sel = 0;
+  lsm2d_iteration_stats* sel_last_stats = nullptr;      // [k] or NULL (out_stats only says that statistics are wanted, as for a begun batch)
+  int32_t* sel_index = nullptr; int32_t* sel_n_selected = nullptr; int32_t* sel_n_accepted = nullptr; int32_t* sel_n_success = nullptr;
 
   size_t take(size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; }
   int validate_and_lay_out_scratch();
@@ -128,6 +135,7 @@ struct AlignBatch {
   int make_placement();
   int launch();
   int hand_over();
+  int select_finish();
 };
 
 int AlignBatch::validate_and_lay_out_scratch() {
@@ -171,6 +179,10 @@ int AlignBatch::validate_and_lay_out_scratch() {
   o_work = take(sizeof(int32_t) * (size_t) n);                                                     // balanced placement: the estimate's counts (device only)
   // "fast_forward" 2: H and inlier count of every alignment's last kFfRing iterations (device only; 640 bytes per alignment; needs no clearing: a row is read only after its alignment wrote it)
   o_ff_rows = (ctx->fast_forward == 2 && !out_work) ? take(sizeof(uint32_t) * kFfRowWords * kFfRing * (size_t) n) : 0;
+  if (select) {      // the candidates' rows and the selection's own arrays, behind everything the aligner uses (the staging buffer takes the region that comes down at the same offset)
+    o_rows = take(sizeof(float) * AlignRow::kWords * (size_t) n);
+    o_sel = take(SelectLayout((size_t) n, (size_t) select_k, AlignRow::kWords).d_bytes);
+  }
   total_bytes = off;
   had_inputs = L->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
   int rc = ensure_scratch(ctx, total_bytes); if (rc) return rc;
@@ -208,7 +220,7 @@ int AlignBatch::choose_path() {
   // (Not for big batches: with 1000 alignments reading their start poses and writing their results over the host link the step takes 1.485 ms
   // against 1.467 with the three small transfers; tools/zero_copy_ab.py.)
   // ("zero_copy_max" bounds every batch, so the A/B knob works below 256 too; batches that carry index arrays stay on the transfers above 256)
-  zero_copy = !out_work && !use_split && n <= ctx->zero_copy_max && (n <= 256 || (!b->fixed_index && !b->moving_index));
+  zero_copy = !select && !out_work && !use_split && n <= ctx->zero_copy_max && (n <= 256 || (!b->fixed_index && !b->moving_index));
   pair_eligible = pair_order_ok(ctx, n) && ctx->align_path != 1 && (ns == 1 || ns == 2) && proj_only && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
   if (zero_copy) ds = (char*) L->h_stage_dev;
   return LSM2D_SUCCESS;
@@ -485,7 +497,7 @@ int AlignBatch::stage_inputs() {
   // the SMALL results of a batch that travels by copies (56 bytes per alignment + the clock stamps) are written by the kernels straight into the pinned
   // staging buffer: the device-to-host copy behind the launch -- a hand-over to the copy engine, 9 us of gap + 6 us of copy on the timeline of a
   // 1000-alignment step -- is gone, the stream wait ends with the kernel.  The statistics (28 bytes per iteration and alignment) stay on the device and are copied.
-  host_results = !zero_copy && !use_split && ctx->results_to_host && n > 0;
+  host_results = !select && !zero_copy && !use_split && ctx->results_to_host && n > 0;      // (select mode: k_align_rows reads them where the kernels leave them, on the device)
   char* const ro = host_results ? (char*) L->h_stage_dev : ds;
   A.out_pose = (float*) (ro + o_pose); A.out_H = (float*) (ro + o_H); A.out_status = (int32_t*) (ro + o_status); A.out_its = (int32_t*) (ro + o_its);
   A.out_stats = out_stats ? (StatsDev*) (ds + o_stats) : nullptr;
@@ -680,6 +692,7 @@ int AlignBatch::launch() {
   HIPCHK(ctx, hipGetLastError());
   for (int s = 0; s < ns; ++s)                  // sets the kernel's prologue unpacks (SliceDev::unpack_src)
     if (A.s[s].unpack_src) { b->fixed[s]->unpack_pending = false; b->fixed[s]->staged_epoch = ctx->sync_epoch; }
+  if (select) return LSM2D_SUCCESS;      // the results stay where they are; the timing bracket ends behind the selection (select_finish)
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L->ev1, ks));
   ctx->have_timing = ctx->kernel_timing;
   if (host_results) { if (out_stats) HIPCHK(ctx, hipMemcpyAsync(hs + o_stats, ds + o_stats, sizeof(StatsDev) * (size_t) n * (size_t) stats_stride, hipMemcpyDeviceToHost, ks)); }
@@ -688,6 +701,7 @@ int AlignBatch::launch() {
 }
 
 int AlignBatch::hand_over() {
+  if (select) return select_finish();
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
   P.ctx = ctx; P.lane = L;
@@ -703,14 +717,44 @@ int AlignBatch::hand_over() {
   return align_batch_finish(P, out_pose, out_H, out_status, out_its, out_stats, out_last_pose);
 }
 
-static int align_batch_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, float* out_pose,
-                            float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats, float* out_last_pose,
-                            int32_t* out_work = nullptr, lsm2d_pending* pend = nullptr) {
-  if (!ctx || !ap || !b || ((!out_pose || !out_status) && !out_work)) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: null argument");
-  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
-  AlignBatch B;
-  B.ctx = ctx; B.L = &lane(ctx); B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = out_status; B.out_its = out_its; B.out_stats = out_stats;
-  B.out_last_pose = out_last_pose; B.out_work = out_work; B.pend = pend;
+// Select mode's second half.  Behind the aligner's launch on the same stream: k_align_rows packs every candidate's results and the LAST statistics row it
+// started into an AlignRow and counts the Success and the never-written statuses into the two words behind the selection's accepted count; select_queue ranks the
+// rows, ends the timing bracket (the aligner's launch PLUS the selection), copies [n_accepted, n_selected, n_success, n_unwritten | index[k] | rows[k]] down
+// and waits -- the one copy and the one wait of the call.  The never-reported check of align_batch_finish is the fourth header word.
+int AlignBatch::select_finish() {
+  const SelectLayout E((size_t) n, (size_t) select_k, AlignRow::kWords);
+  char* const d = (char*) L->d_scratch;      // (== ds: select mode never takes the zero-copy form)
+  char* const de = d + o_sel;
+  HIPCHK(ctx, hipMemsetAsync(de + E.e_acc, 0, sizeof(int32_t) * 3, ks));      // accepted | Success | never written
+  AlignRowsArgs R;
+  R.pose = (const float*) (d + o_pose); R.H = (const float*) (d + o_H); R.status = (const int32_t*) (d + o_status); R.its = (const int32_t*) (d + o_its);
+  R.stats = (const StatsDev*) (d + o_stats); R.n = n; R.stats_stride = stats_stride; R.not_written = kStatusNotWritten;
+  R.rows = (float*) (d + o_rows); R.counts = (int32_t*) (de + E.e_acc) + 1;
+  hipLaunchKernelGGL(k_align_rows<AlignRow>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ks, R);
+  HIPCHK(ctx, hipGetLastError());
+  SelectArgs S;
+  S.rows = R.rows; S.n_items = n; S.k = select_k;
+  S.min_inliers = select->min_inliers; S.max_chi_per_inlier = select->max_chi_per_inlier; S.min_inlier_ratio = select->min_inlier_ratio;
+  { const int rc = select_queue<AlignRow>(ctx, "align_select", S, E, de, hs + o_sel); if (rc) return rc; }
+  const int32_t* h = (const int32_t*) (hs + o_sel);
+  const int32_t n_acc = h[0], n_sel = h[1], n_success = h[2], n_unwritten = h[3];
+  if (n_unwritten != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
+  if (n_success < n_acc || n_success > n) return fail(ctx, LSM2D_DEVICE_ERROR, "align_select: the selection's counters are inconsistent");
+  const int32_t* h_index = h + kSelectHeaderWords; const int32_t* h_rows = h + kSelectHeaderWords + select_k;
+  for (int32_t j = 0; j < n_sel; ++j) {
+    const int32_t* row = h_rows + AlignRow::kWords * (size_t) j;
+    sel_index[j] = h_index[j];
+    memcpy(out_pose + 3 * (size_t) j, row + AlignRow::kPose, sizeof(float) * 3);
+    if (out_H) memcpy(out_H + 9 * (size_t) j, row + AlignRow::kH, sizeof(float) * 9);
+    if (out_its) out_its[j] = row[AlignRow::kIts];
+    if (sel_last_stats) memcpy(sel_last_stats + j, row + AlignRow::kStats, sizeof(lsm2d_iteration_stats));
+  }
+  *sel_n_selected = n_sel; *sel_n_accepted = n_acc;
+  if (sel_n_success) *sel_n_success = n_success;
+  return LSM2D_SUCCESS;
+}
+
+static int align_batch_run(AlignBatch& B) {
   int rc = B.validate_and_lay_out_scratch();
   if (rc == kEmptyBatch) return LSM2D_SUCCESS;
   if (!rc) rc = B.choose_path();
@@ -719,9 +763,20 @@ static int align_batch_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, 
   if (!rc) rc = B.stage_inputs();
   if (!rc) rc = B.make_placement();
   if (rc) return rc;
-  if (out_work) return B.estimate_only();
+  if (B.out_work) return B.estimate_only();
   rc = B.launch();
   return rc ? rc : B.hand_over();
+}
+
+static int align_batch_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, float* out_pose,
+                            float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats, float* out_last_pose,
+                            int32_t* out_work = nullptr, lsm2d_pending* pend = nullptr) {
+  if (!ctx || !ap || !b || ((!out_pose || !out_status) && !out_work)) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: null argument");
+  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
+  AlignBatch B;
+  B.ctx = ctx; B.L = &lane(ctx); B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = out_status; B.out_its = out_its; B.out_stats = out_stats;
+  B.out_last_pose = out_last_pose; B.out_work = out_work; B.pend = pend;
+  return align_batch_run(B);
 }
 
 // the second half: wait for the batch, check that every alignment reported, hand the results over
@@ -785,6 +840,29 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
 extern "C" int lsm2d_align_batch(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, float* out_pose,
                                  float* out_H, int32_t* out_status, int32_t* out_its, lsm2d_iteration_stats* out_stats) {
   return align_batch_impl(ctx, ap, b, out_pose, out_H, out_status, out_its, out_stats, nullptr);
+}
+
+// ---- aligned, accepted and ranked: the candidate loops' verdict with k rows coming down (include/lsm2d.h).  The alignment is lsm2d_align_batch's with statistics
+// (the same stages, path rule, kernels and launch forms); synchronous, on the context's current lane like every other call.
+extern "C" int lsm2d_align_select(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, const lsm2d_select_params* select, int32_t k,
+                                  int32_t* out_index, float* out_pose, float* out_H, int32_t* out_its, lsm2d_iteration_stats* out_last_stats,
+                                  int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  if (!ctx || !ap || !b || !select || !out_index || !out_pose || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_select: null argument");
+  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_select: k outside [1, LSM2D_SELECT_MAX_K]");
+  if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
+  static int32_t wanted_status; static lsm2d_iteration_stats wanted_stats;      // (the stages ask "is this output wanted?" of the pointers: statuses and statistics are, on the device)
+  AlignBatch B;
+  B.ctx = ctx; B.L = &lane(ctx); B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = &wanted_status; B.out_its = out_its;
+  B.out_stats = &wanted_stats; B.out_last_pose = nullptr; B.out_work = nullptr; B.pend = nullptr;
+  B.select = select; B.select_k = k; B.sel_index = out_index; B.sel_last_stats = out_last_stats; B.sel_n_selected = out_n_selected; B.sel_n_accepted = out_n_accepted;
+  B.sel_n_success = out_n_success;
+  if (b->n_alignments == 0) {      // an empty batch: its descriptor is checked as ever, the counts are zeros
+    const int rc = B.validate_and_lay_out_scratch();
+    if (rc != kEmptyBatch) return rc;
+    *out_n_selected = 0; *out_n_accepted = 0; if (out_n_success) *out_n_success = 0;
+    return LSM2D_SUCCESS;
+  }
+  return align_batch_run(B);
 }
 
 // ---- a batch in flight: MultiAligner2D::compute over a batch, split where the host would otherwise sleep.  begin() queues everything -- inputs, placement,

@@ -567,6 +567,7 @@ extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* s
 // index) entries until one tile is left -- a pass turns m entries into ceil(m / tile) x k, less than half of them while m > tile -- and k_select_gather,
 // which fills the one region that comes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]], 16 + 68 k bytes whatever n_items is.  A
 // batch of at most one tile does all three in ONE launch (k_select_tile_one: four launches and a memset less, which is what counts at 1000 items).
+// (SelectLayout and select_queue also serve lsm2d_capi_aligner.inc, which is included behind this file: lsm2d_align_select ranks AlignRow rows with them.)
 // where the selection's own part of the scratch lies: [keys A | index A] of n entries, [keys B | index B] of what the first pass leaves, the accepted count,
 // the region that goes down ([header | index[k] | rows[k][row_words]]: down_bytes)
 struct SelectLayout {

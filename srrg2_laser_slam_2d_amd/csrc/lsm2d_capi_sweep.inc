@@ -156,3 +156,77 @@ extern "C" int lsm2d_sweep_align(lsm2d_sweep* sw, const lsm2d_aligner_params* ap
   for (int r = 0; r < G; ++r) if (rcs[(size_t) r] != LSM2D_SUCCESS) return sweep_fail(sw, rcs[(size_t) r], std::string("sweep_align: device ") + std::to_string(r) + ": " + lsm2d_last_error(sw->ctx[(size_t) r]));
   return LSM2D_SUCCESS;
 }
+
+// ---- ... with the verdict made on the devices: every shard runs lsm2d_align_select with the caller's k on its block of candidates, and the host merges the
+// <= G x k rows by the selection's own key over GLOBAL candidate indices -- n_inliers descending, chi_inliers ascending on its bit pattern, index ascending.
+// A candidate among the best k of all is among the best k of its shard, and the order is total: the result is lsm2d_align_select's on one device, whatever G is.
+extern "C" int lsm2d_sweep_align_select(lsm2d_sweep* sw, const lsm2d_aligner_params* ap, const lsm2d_slice_params* slice, int32_t n_candidates,
+                                        const int32_t* scan_index, const float* init_pose, const lsm2d_select_params* select, int32_t k,
+                                        int32_t* out_index, float* out_pose, float* out_H, int32_t* out_iterations, lsm2d_iteration_stats* out_last_stats,
+                                        int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  if (!sw || !ap || !slice || !select || !out_index || !out_pose || !out_n_selected || !out_n_accepted || n_candidates < 0 || (n_candidates > 0 && !init_pose))
+    return fail(nullptr, LSM2D_BAD_ARGUMENT, "sweep_align_select: bad argument");
+  if (k < 1 || k > LSM2D_SELECT_MAX_K) return sweep_fail(sw, LSM2D_BAD_ARGUMENT, "sweep_align_select: k outside [1, LSM2D_SELECT_MAX_K]");
+  if (sw->map.size() != sw->ctx.size() || sw->scans.size() != sw->ctx.size()) return sweep_fail(sw, LSM2D_BAD_ARGUMENT, "sweep_align_select: set_map / set_scans first");
+  if (n_candidates == 0) { *out_n_selected = 0; *out_n_accepted = 0; if (out_n_success) *out_n_success = 0; return LSM2D_SUCCESS; }
+  const int G = (int) sw->ctx.size();
+  const int n_scans = lsm2d_cloudset_num_clouds(sw->scans[0]);
+  if (!scan_index && n_scans != n_candidates && n_scans != 1) return sweep_fail(sw, LSM2D_BAD_ARGUMENT, "sweep_align_select: scan_index needed unless there is one scan per candidate");
+  struct Shard { std::vector<int32_t> index, its; std::vector<float> pose, H; std::vector<lsm2d_iteration_stats> stats; int32_t n_sel = 0, n_acc = 0, n_success = 0; };
+  std::vector<int> rcs; std::vector<std::thread> workers; std::vector<Shard> shards;
+  try {
+    rcs.assign((size_t) G, LSM2D_SUCCESS); workers.reserve((size_t) G); shards.resize((size_t) G);
+    for (Shard& s : shards) { s.index.resize((size_t) k); s.its.resize((size_t) k); s.pose.resize(3 * (size_t) k); s.H.resize(9 * (size_t) k); s.stats.resize((size_t) k); }
+  } catch (...) { return sweep_fail(sw, LSM2D_OUT_OF_MEMORY, "sweep_align_select: out of memory"); }
+  bool spawn_failed = false;
+  for (int r = 0; r < G && !spawn_failed; ++r) {
+    const long long lo = (long long) n_candidates * r / G, hi = (long long) n_candidates * (r + 1) / G;
+    if (hi <= lo) continue;
+    try {
+    workers.emplace_back([=, &rcs, &shards]() {
+      try {
+      const int n = (int) (hi - lo);
+      Shard& s = shards[(size_t) r];
+      std::vector<int32_t> own_index;      // (without an index array candidate i uses scan i: the shard's scans start at lo)
+      const int32_t* idx = scan_index ? scan_index + lo : nullptr;
+      if (!idx && n_scans != 1) { own_index.resize((size_t) n); for (int i = 0; i < n; ++i) own_index[(size_t) i] = (int32_t) (lo + i); idx = own_index.data(); }
+      const lsm2d_cloudset* fx = sw->scans[(size_t) r]; const lsm2d_cloudset* mv = sw->map[(size_t) r];
+      lsm2d_batch b; memset(&b, 0, sizeof b);
+      b.n_alignments = n; b.n_slices = 1; b.slices = slice; b.fixed = &fx; b.moving = &mv; b.fixed_index = idx; b.init_pose = init_pose + 3 * lo;
+      rcs[(size_t) r] = lsm2d_align_select(sw->ctx[(size_t) r], ap, &b, select, k, s.index.data(), s.pose.data(), s.H.data(), s.its.data(), s.stats.data(),
+                                           &s.n_sel, &s.n_acc, &s.n_success);
+      for (int32_t j = 0; j < s.n_sel; ++j) s.index[(size_t) j] += (int32_t) lo;      // global candidate indices from here on
+      } catch (const std::bad_alloc&) { rcs[(size_t) r] = LSM2D_OUT_OF_MEMORY; } catch (...) { rcs[(size_t) r] = LSM2D_DEVICE_ERROR; }
+    });
+    } catch (...) { spawn_failed = true; }
+  }
+  for (auto& w : workers) w.join();
+  if (spawn_failed) return sweep_fail(sw, LSM2D_OUT_OF_MEMORY, "sweep_align_select: could not start a worker thread");
+  for (int r = 0; r < G; ++r) if (rcs[(size_t) r] != LSM2D_SUCCESS) return sweep_fail(sw, rcs[(size_t) r], std::string("sweep_align_select: device ") + std::to_string(r) + ": " + lsm2d_last_error(sw->ctx[(size_t) r]));
+  struct Entry { uint64_t key; int32_t index; int shard, row; };
+  std::vector<Entry> all;
+  long long n_acc = 0, n_success = 0;
+  try {
+    for (int r = 0; r < G; ++r) {
+      const Shard& s = shards[(size_t) r];
+      n_acc += s.n_acc; n_success += s.n_success;
+      for (int32_t j = 0; j < s.n_sel; ++j) {
+        uint32_t chi_bits; memcpy(&chi_bits, &s.stats[(size_t) j].chi_inliers, sizeof chi_bits);
+        all.push_back({((uint64_t) (uint32_t) (0x7fffffff - s.stats[(size_t) j].n_inliers) << 32) | (uint64_t) chi_bits, s.index[(size_t) j], r, (int) j});
+      }
+    }
+  } catch (...) { return sweep_fail(sw, LSM2D_OUT_OF_MEMORY, "sweep_align_select: out of memory"); }
+  std::sort(all.begin(), all.end(), [](const Entry& a, const Entry& b) { return a.key < b.key || (a.key == b.key && a.index < b.index); });
+  const int32_t n_sel = (int32_t) std::min<long long>((long long) k, n_acc);      // (every shard handed back min(k, its accepted): all.size() >= n_sel)
+  for (int32_t j = 0; j < n_sel && (size_t) j < all.size(); ++j) {
+    const Entry& e = all[(size_t) j]; const Shard& s = shards[(size_t) e.shard];
+    out_index[j] = e.index;
+    memcpy(out_pose + 3 * (size_t) j, s.pose.data() + 3 * (size_t) e.row, sizeof(float) * 3);
+    if (out_H) memcpy(out_H + 9 * (size_t) j, s.H.data() + 9 * (size_t) e.row, sizeof(float) * 9);
+    if (out_iterations) out_iterations[j] = s.its[(size_t) e.row];
+    if (out_last_stats) out_last_stats[j] = s.stats[(size_t) e.row];
+  }
+  *out_n_selected = n_sel; *out_n_accepted = (int32_t) n_acc;
+  if (out_n_success) *out_n_success = (int32_t) n_success;
+  return LSM2D_SUCCESS;
+}

@@ -27,6 +27,9 @@ static_assert(kSelectBlock <= 1024, "one workgroup");
 // with kActive >= 0 names a word that counts the aligner slices that contributed: an item whose count is 0 is rejected whatever the thresholds are
 // (lsm2d_k_score_aligner.h: it has no aligner status to pass).  k_select_tile sees keys and indices only.
 struct ScoreRow { static constexpr int kWords = kLinOutWords, kChi = 9, kNin = 11, kNcorr = 13, kActive = -1; };
+// A format may say that the two spare header words of the region that goes down carry two counts of its own, made by the kernel that wrote its rows into the
+// two words BEHIND SelectArgs::n_accepted (AlignRow, lsm2d_k_align_select.h); for every other format they are zeros.
+template <class Row> struct SelectCarriesCounts { static constexpr bool value = false; };
 
 struct SelectArgs {
   const float* rows;          // [n_items][Row::kWords]: where the scoring's last kernel left them
@@ -124,7 +127,11 @@ __global__ __launch_bounds__(kSelectBlock) void k_select_tile(const u64* keys_in
 template <class Row>
 LSM2D_DEV void select_gather(const SelectArgs& A, int n_acc, const u64* keys, const int32_t* index, int32_t* down) {
   const int n_sel = n_acc < A.k ? n_acc : A.k;
-  if (threadIdx.x == 0) { down[0] = n_acc; down[1] = n_sel; down[2] = 0; down[3] = 0; }
+  if (threadIdx.x == 0) {
+    down[0] = n_acc; down[1] = n_sel;
+    if constexpr (SelectCarriesCounts<Row>::value) { down[2] = A.n_accepted[1]; down[3] = A.n_accepted[2]; }
+    else { down[2] = 0; down[3] = 0; }
+  }
   int32_t* d_index = down + kSelectHeaderWords;
   int32_t* d_rows = down + kSelectHeaderWords + A.k;
   const int32_t* rows = reinterpret_cast<const int32_t*>(A.rows);      // words are moved as bits: counts and the digest lie among the sums

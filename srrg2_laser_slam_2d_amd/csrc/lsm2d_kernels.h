@@ -15,6 +15,8 @@
 //   k_linearize_*_batch  the same factor over a batch of vectors: the same device functions, an item keeps the single call's launch shape.
 //   k_score_*_batch    the same factor over the slots k_find_*_batch has just filled, counts read from the device: the pairs never leave it (lsm2d_score_batch).
 //   k_select_*         the acceptance test and the best k of those rows, ranked on the device: only k rows travel (lsm2d_score_select; lsm2d_k_select.h).
+//   k_align_rows       one row per ALIGNED candidate (pose, H, status, iterations, its last iteration's statistics) for the same selection, and the counts of
+//                      Success and never-written statuses (lsm2d_align_select; lsm2d_k_align_select.h).
 //   k_score_aligner_items / k_score_combine  hypotheses scored against a whole aligner: per-slice item tables from the poses, and the slices' rows combined with
 //                      the skip rule and the prior into one row per item (lsm2d_score_aligner_batch / _select; lsm2d_k_score_aligner.h).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
@@ -54,6 +56,7 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_align_pair.h"
 #include "lsm2d_k_split_finder.h"
 #include "lsm2d_k_select.h"
+#include "lsm2d_k_align_select.h"
 #include "lsm2d_k_score_aligner.h"
 #include "lsm2d_k_finder.h"
 #include "lsm2d_k_mapping.h"

@@ -248,6 +248,39 @@ inline Relocalization relocalize(Context& ctx, const lsm2d_aligner_params& align
   return r;
 }
 
+// lsm2d_align_batch's alignment of init_pose.size() candidates, then the candidate loops' verdict made on the device (lsm2d_align_select): aligner
+// succeeded, the last iteration started passes `select`, the best k of those ranked -- inliers descending, chi_inliers ascending, index ascending.  Only k
+// rows come down: row j is what lsm2d_align_batch returns for candidate index[j], last_stats[j] its statistics row iterations - 1.  slices[s] reads
+// fixed[s] / moving[s]; the index vectors are empty or [n_slices][n] flat and priors is empty or holds one per candidate, as lsm2d_batch takes them.
+struct AlignSelection {
+  std::vector<int32_t> index; std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> iterations;
+  std::vector<lsm2d_iteration_stats> last_stats; int32_t n_accepted = 0, n_success = 0;
+};
+inline AlignSelection alignSelect(Context& ctx, const lsm2d_aligner_params& aligner, const std::vector<lsm2d_slice_params>& slices,
+                                  const std::vector<const CloudSet*>& fixed, const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& init_pose,
+                                  const lsm2d_select_params& select, int32_t k, const std::vector<lsm2d_prior>& priors = {},
+                                  const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
+  const size_t n = init_pose.size(), ns = slices.size();
+  if (fixed.size() != ns || moving.size() != ns) throw std::runtime_error("alignSelect| one fixed and one moving set per slice");
+  if ((!fixed_index.empty() && fixed_index.size() != ns * n) || (!moving_index.empty() && moving_index.size() != ns * n) || (!priors.empty() && priors.size() != n))
+    throw std::runtime_error("alignSelect| an index vector is empty or [n_slices][n]; priors is empty or holds one per candidate");
+  std::vector<const lsm2d_cloudset*> fx, mv;
+  for (size_t s = 0; s < ns; ++s) { fx.push_back(fixed[s] ? fixed[s]->get() : nullptr); mv.push_back(moving[s] ? moving[s]->get() : nullptr); }
+  lsm2d_batch b{}; b.n_alignments = (int32_t) n; b.n_slices = (int32_t) ns; b.slices = slices.data(); b.fixed = fx.data(); b.moving = mv.data();
+  b.fixed_index = fixed_index.empty() ? nullptr : fixed_index.data(); b.moving_index = moving_index.empty() ? nullptr : moving_index.data();
+  b.init_pose = n ? init_pose[0].data() : nullptr; b.prior = priors.empty() ? nullptr : priors.data();
+  const size_t cap = (size_t) std::max<int32_t>(k, 1);
+  AlignSelection out; int32_t n_sel = 0;
+  out.index.resize(cap); out.pose.resize(cap); out.information.resize(cap); out.iterations.resize(cap); out.last_stats.resize(cap);
+  static_assert(sizeof(Vector3f) == 3 * sizeof(float) && sizeof(std::array<float, 9>) == 9 * sizeof(float), "rows are packed");
+  check(lsm2d_align_select(ctx.get(), &aligner, &b, &select, k, out.index.data(), out.pose[0].data(), out.information[0].data(), out.iterations.data(),
+                           out.last_stats.data(), &n_sel, &out.n_accepted, &out.n_success),
+        "lsm2d_align_select", ctx.get());
+  out.index.resize((size_t) n_sel); out.pose.resize((size_t) n_sel); out.information.resize((size_t) n_sel); out.iterations.resize((size_t) n_sel);
+  out.last_stats.resize((size_t) n_sel);
+  return out;
+}
+
 // ---- pose hypotheses scored against a whole aligner: its slices with their sensor offsets and skip thresholds, an optional prior per hypothesis ----
 // (lsm2d_score_aligner_batch / lsm2d_score_aligner_select).  slices[s] reads fixed[s] / moving[s]; the index vectors are empty or [n_slices][n] flat, as
 // lsm2d_batch takes them; priors is empty or holds one per pose.  A row is what the first iteration of lsm2d_align_batch holds just before its solve;
@@ -742,8 +775,28 @@ class LoopClosureSweep {
     return status[i] == LSM2D_SUCCESS && st.n_inliers >= param_relocalize_min_inliers &&
            st.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= param_relocalize_max_chi_inliers && n_in / n_c >= param_relocalize_min_inliers_ratio;
   }
+  // compute + accept + "take the best k" on the devices (lsm2d_sweep_align_select): every shard ranks its candidates where they lie, k rows per shard come
+  // down and are merged by the same key.  selected[j] is the j-th best accepted candidate (param_relocalize_* are the thresholds) and row j of pose /
+  // information / iterations / last_stats its results -- the bits compute() gives for that candidate; status is left empty (every selected candidate
+  // succeeded).  n_accepted / n_success count among all candidates.
+  void computeSelect(const std::vector<int32_t>& scan_index, const std::vector<Vector3f>& init_pose, int32_t k) {
+    const int n = (int) init_pose.size();
+    if ((int) scan_index.size() != n) throw std::runtime_error("LoopClosureSweep::computeSelect| one scan index per candidate");
+    const lsm2d_slice_params sp = param_slice;
+    lsm2d_aligner_params ap{param_max_iterations, param_min_num_inliers, 0.f, 0.f, 0, 0};
+    const lsm2d_select_params sel{param_relocalize_min_inliers, param_relocalize_max_chi_inliers, param_relocalize_min_inliers_ratio};
+    const size_t cap = (size_t) std::max<int32_t>(k, 1);
+    selected.assign(cap, 0); pose.assign(cap, Vector3f{{0.f, 0.f, 0.f}}); information.assign(cap, std::array<float, 9>{});
+    status.clear(); iterations.assign(cap, 0); last_stats.assign(cap, lsm2d_iteration_stats{});
+    int32_t n_sel = 0; n_accepted = 0; n_success = 0;
+    checkSweep(lsm2d_sweep_align_select(_sw, &ap, &sp, n, scan_index.data(), n ? init_pose[0].data() : nullptr, &sel, k, selected.data(), pose[0].data(),
+                                        information[0].data(), iterations.data(), last_stats.data(), &n_sel, &n_accepted, &n_success), "align_select");
+    selected.resize((size_t) n_sel); pose.resize((size_t) n_sel); information.resize((size_t) n_sel); iterations.resize((size_t) n_sel);
+    last_stats.resize((size_t) n_sel);
+  }
   std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information;
   std::vector<int32_t> status, iterations; std::vector<lsm2d_iteration_stats> last_stats;
+  std::vector<int32_t> selected; int32_t n_accepted = 0, n_success = 0;      // computeSelect
  private:
   void checkSweep(int rc, const char* where) const {
     if (rc < 0) throw std::runtime_error(std::string("LoopClosureSweep::") + where + "| " + lsm2d_status_string(rc) + ": " + lsm2d_sweep_last_error(_sw));

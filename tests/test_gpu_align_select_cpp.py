@@ -1,0 +1,73 @@
+"""alignSelect and LoopClosureSweep::computeSelect of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU:
+the selection, the counts and every row equal api.align_select on the same inputs, bit for bit -- alignSelect in both orders of summation, computeSelect (two
+shards on one device, merged on the host) in the default order, the only one a sweep's contexts run in."""
+import json
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import align_select_cases as cases
+from conftest import ROOT
+from srrg2_laser_slam_2d_amd import api
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    d = tmp_path_factory.mktemp("align_select_cpp")
+    exe = str(d / "align_select_driver")
+    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
+                    os.path.join(ROOT, "tests", "cpp", "align_select_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    c = cases.make_cases()
+    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
+    return exe, d, c
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+
+
+def _same(block, got):
+    assert block["n_accepted"] == got.n_accepted and block["n_success"] == got.n_success and block["index"] == got.index.tolist()
+    assert len(block["rows"]) == len(got.index)
+    for j, row in enumerate(block["rows"]):
+        s = got.last_stats[j]
+        assert row["pose"] == _bits(got.pose[j]) and row["H"] == _bits(got.information[j]) and row["iterations"] == int(got.iterations[j]), j
+        assert row["counts"] == [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])], j
+        assert row["chi"] == _bits([s["chi_inliers"], s["chi_outliers"]]) and row["digest"] == [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])], j
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_cpp_align_select(ctx, driver, order):
+    exe, d, c = driver
+    k = 9
+    ctx.set_option("sum_order", order)
+    try:
+        finder = api.CorrespondenceFinderProjective2f(ctx, api.PointNormal2fProjectorPolar(cases.COLS, -math.pi, math.pi, 0.3, 30.0))
+        al = api.MultiAligner2D(ctx, max_iterations=cases.ITERATIONS, min_num_inliers=0)
+        al.param_slice_processors.append(api.AlignerSliceProcessorLaser2D(finder, robustifier=api.RobustifierCauchy(cases.TAU), min_num_correspondences=cases.MIN_CORR))
+        first = al.compute_batch([c.scan], [c.map], c.poses, want_stats=True)
+        n_in = first.last_stats()["n_inliers"][first.status == 0]
+        al.param_min_num_inliers = int(np.sort(n_in)[len(n_in) // 2])      # the middle of the inlier counts: some candidates end NotEnoughInliers
+        res = al.compute_batch([c.scan], [c.map], c.poses, want_stats=True)
+        sel = cases.middle_thresholds(res.last_stats()[res.status == 0])
+        got = api.align_select(al, [c.scan], [c.map], c.poses, sel, k)
+    finally:
+        ctx.set_option("sum_order", 0)
+    assert len(got.index) == k and k < got.n_accepted < got.n_success < len(c.poses)      # a selection that is cut at k; the status term and the thresholds both reject
+    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
+    out = subprocess.run([exe] + [str(d / f) for f in ("scan.bin", "map.bin", "poses.bin")] +
+                         [str(cases.COLS), repr(cases.TAU), str(cases.ITERATIONS), str(al.param_min_num_inliers), str(order), str(sel.min_inliers), str(int(thr[0])),
+                          str(int(thr[1])), str(k)], check=True, capture_output=True, text=True, timeout=120).stdout
+    r = json.loads(out)
+    assert r["n"] == len(c.poses) and r["n_empty"] == 0
+    _same(r["align_select"], got)
+    if order == 0:
+        _same(r["compute_select"], got)
+    else:
+        assert r["compute_select"] is None
