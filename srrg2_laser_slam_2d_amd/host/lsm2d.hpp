@@ -52,24 +52,41 @@ class Context {
   lsm2d_context* _h = nullptr;
 };
 
+namespace detail {
+// what the C ABI takes for a vector: its first element, NULL when there is none (a cloud as its floats x, y, nx, ny; poses as their floats)
+template <class T> const T* ptrOrNull(const std::vector<T>& v) { return v.empty() ? nullptr : v.data(); }
+inline const float* ptrOrNull(const PointNormal2fVectorCloud& c) { return c.empty() ? nullptr : &c[0].x; }
+inline const float* ptrOrNull(const std::vector<Vector3f>& v) { return v.empty() ? nullptr : v[0].data(); }
+
+// the one owner of a lsm2d_cloudset*: every set this header makes lives in one of these, so that a throw anywhere gives it back; reads as the pointer
+class CloudSetHandle {
+ public:
+  CloudSetHandle() = default; ~CloudSetHandle() { lsm2d_cloudset_destroy(_h); }
+  CloudSetHandle(const CloudSetHandle&) = delete; CloudSetHandle& operator=(const CloudSetHandle&) = delete;
+  operator lsm2d_cloudset*() const { return _h; }
+  lsm2d_cloudset** out() { return &_h; }      // where a creating call puts the set: only while this handle is empty
+ private:
+  lsm2d_cloudset* _h = nullptr;
+};
+}  // namespace detail
+using detail::ptrOrNull;
+
 // device-resident copy of one cloud or of a ragged batch of clouds
 class CloudSet {
  public:
-  CloudSet(Context& ctx, const PointNormal2fVectorCloud& cloud) : _ctx(&ctx) {
-    check(lsm2d_cloudset_create(ctx.get(), cloud.empty() ? nullptr : &cloud[0].x, nullptr, 1, (int64_t) cloud.size(), &_h), "lsm2d_cloudset_create", ctx.get());
+  CloudSet(Context& ctx, const PointNormal2fVectorCloud& cloud) {
+    check(lsm2d_cloudset_create(ctx.get(), ptrOrNull(cloud), nullptr, 1, (int64_t) cloud.size(), _h.out()), "lsm2d_cloudset_create", ctx.get());
   }
-  CloudSet(Context& ctx, const std::vector<PointNormal2fVectorCloud>& clouds) : _ctx(&ctx) {
+  CloudSet(Context& ctx, const std::vector<PointNormal2fVectorCloud>& clouds) {
     std::vector<int32_t> offs(1, 0); PointNormal2fVectorCloud packed;
     for (const auto& c : clouds) { packed.insert(packed.end(), c.begin(), c.end()); offs.push_back((int32_t) packed.size()); }
-    check(lsm2d_cloudset_create(ctx.get(), packed.empty() ? nullptr : &packed[0].x, offs.data(), (int32_t) clouds.size(), (int64_t) packed.size(), &_h),
+    check(lsm2d_cloudset_create(ctx.get(), ptrOrNull(packed), offs.data(), (int32_t) clouds.size(), (int64_t) packed.size(), _h.out()),
           "lsm2d_cloudset_create", ctx.get());
   }
-  ~CloudSet() { lsm2d_cloudset_destroy(_h); }
-  CloudSet(const CloudSet&) = delete; CloudSet& operator=(const CloudSet&) = delete;
   lsm2d_cloudset* get() const { return _h; }
   int32_t numClouds() const { return lsm2d_cloudset_num_clouds(_h); }
  private:
-  Context* _ctx; lsm2d_cloudset* _h = nullptr;
+  detail::CloudSetHandle _h;
 };
 
 // PointNormal2fProjectorPolar parameters (apps/synthetic_scene_generator.cpp:69-75, MULTI.json:71-97)
@@ -82,6 +99,64 @@ struct PointNormal2fProjectorPolar {
 };
 using PointNormal2fProjectorPolarPtr = std::shared_ptr<PointNormal2fProjectorPolar>;
 
+// what the factor returns for one item: H (row-major 3x3), b and the statistics; with the slices of a whole aligner, how many of them contributed
+struct Linearization { std::array<float, 9> H{}; std::array<float, 3> b{}; lsm2d_iteration_stats stats{}; };
+struct AlignerScore { Linearization row; int32_t active = 0; };
+
+namespace detail {
+template <class T> bool emptyOrHolds(const std::vector<T>& v, size_t n) { return v.empty() || v.size() == n; }
+// an index vector is left out (empty) or holds `n` entries; `rule` is the caller's wording of that, `others` what its wording covers besides
+inline void checkIndexVectors(const char* who, const char* rule, const std::vector<int32_t>& fixed_index, const std::vector<int32_t>& moving_index, size_t n,
+                              bool others = true) {
+  if (!emptyOrHolds(fixed_index, n) || !emptyOrHolds(moving_index, n) || !others) throw std::runtime_error(std::string(who) + "| " + rule);
+}
+constexpr const char* ONE_PER_POSE = "an index vector is empty or holds one entry per pose";
+
+// the flat rows a scoring call fills -- H[9 m], b[3 m], stats[m] and, for a whole aligner, active[m] -- with room for at least one
+struct RowBuffer {
+  std::vector<float> H, b; std::vector<lsm2d_iteration_stats> stats; std::vector<int32_t> active;
+  explicit RowBuffer(size_t m, bool with_active = false)
+      : H(9 * std::max<size_t>(m, 1)), b(3 * std::max<size_t>(m, 1)), stats(std::max<size_t>(m, 1)), active(with_active ? std::max<size_t>(m, 1) : 0, 0) {}
+  void fill(Linearization& r, size_t i) const {
+    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), r.H.begin());
+    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), r.b.begin());
+    r.stats = stats[i];
+  }
+  void fill(AlignerScore& r, size_t i) const { fill(r.row, i); r.active = active[i]; }
+  template <class Row> std::vector<Row> rows(size_t m) const { std::vector<Row> out(m); for (size_t i = 0; i < m; ++i) fill(out[i], i); return out; }
+};
+
+// a lsm2d_batch and the two handle arrays it points into: slices[s] reads fixed[s] / moving[s]; everything else stays the caller's
+struct BatchDescriptor {
+  std::vector<const lsm2d_cloudset*> fx, mv; lsm2d_batch b{};
+  BatchDescriptor(size_t n, const lsm2d_slice_params* slices, std::vector<const lsm2d_cloudset*> fixed, std::vector<const lsm2d_cloudset*> moving,
+                  const float* init_pose, const lsm2d_prior* prior = nullptr, const int32_t* fixed_index = nullptr, const int32_t* moving_index = nullptr)
+      : fx(std::move(fixed)), mv(std::move(moving)) {
+    b.n_alignments = (int32_t) n; b.n_slices = (int32_t) fx.size(); b.slices = slices; b.fixed = fx.data(); b.moving = mv.data();
+    b.fixed_index = fixed_index; b.moving_index = moving_index; b.init_pose = init_pose; b.prior = prior;
+  }
+  BatchDescriptor(const BatchDescriptor&) = delete; BatchDescriptor& operator=(const BatchDescriptor&) = delete;
+};
+inline std::vector<const lsm2d_cloudset*> handles(const std::vector<const CloudSet*>& sets) {
+  std::vector<const lsm2d_cloudset*> out;
+  for (const CloudSet* cs : sets) out.push_back(cs ? cs->get() : nullptr);
+  return out;
+}
+inline void checkSetsPerSlice(const char* who, size_t n_slices, const std::vector<const CloudSet*>& fixed, const std::vector<const CloudSet*>& moving) {
+  if (fixed.size() != n_slices || moving.size() != n_slices) throw std::runtime_error(std::string(who) + "| one fixed and one moving set per slice");
+}
+// the batch of the aligner-scoring calls, refusing what they refuse
+inline BatchDescriptor alignerBatch(const char* who, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
+                                    const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses, const std::vector<lsm2d_prior>& priors,
+                                    const std::vector<int32_t>& fixed_index, const std::vector<int32_t>& moving_index) {
+  const size_t n = poses.size(), ns = slices.size();
+  checkSetsPerSlice(who, ns, fixed, moving);
+  checkIndexVectors(who, "an index vector is empty or holds n_slices x n entries", fixed_index, moving_index, ns * n);
+  if (!emptyOrHolds(priors, n)) throw std::runtime_error(std::string(who) + "| priors is empty or holds one per pose");
+  return BatchDescriptor(n, slices.data(), handles(fixed), handles(moving), ptrOrNull(poses), ptrOrNull(priors), ptrOrNull(fixed_index), ptrOrNull(moving_index));
+}
+}  // namespace detail
+
 // compute() of a finder for poses.size() independent (fixed, moving, pose) triples in one launch (lsm2d_find_correspondences_batch): item i matches cloud
 // fixed_index[i] of `fixed` against cloud moving_index[i] of `moving` (an empty index vector: cloud i, or the only cloud of a one-cloud set) under poses[i];
 // per item the vector compute() fills, in the same order
@@ -89,8 +164,7 @@ inline std::vector<CorrespondenceVector> findCorrespondencesBatch(Context& ctx, 
                                                                   const std::vector<Vector3f>& poses, const std::vector<int32_t>& fixed_index,
                                                                   const std::vector<int32_t>& moving_index) {
   const size_t n = poses.size();
-  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
-    throw std::runtime_error("findCorrespondencesBatch| an index vector is empty or holds one entry per pose");
+  detail::checkIndexVectors("findCorrespondencesBatch", detail::ONE_PER_POSE, fixed_index, moving_index, n);
   size_t cap = 0;
   if (sp.finder == LSM2D_FINDER_PROJECTIVE) cap = (size_t) (sp.projector.canvas_cols > 0 ? sp.projector.canvas_cols : 0);
   else {      // one pair per point of the largest moving cloud
@@ -99,26 +173,22 @@ inline std::vector<CorrespondenceVector> findCorrespondencesBatch(Context& ctx, 
     for (int32_t v : sizes) cap = std::max(cap, (size_t) v);
   }
   std::vector<Correspondence> buf(std::max<size_t>(cap * n, 1)); std::vector<int32_t> cnt(std::max<size_t>(n, 1), 0);
-  check(lsm2d_find_correspondences_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
-                                         moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, buf.data(),
-                                         (int32_t) cap, cnt.data()),
+  check(lsm2d_find_correspondences_batch(ctx.get(), &sp, fixed.get(), ptrOrNull(fixed_index), moving.get(), ptrOrNull(moving_index), (int32_t) n, ptrOrNull(poses),
+                                         buf.data(), (int32_t) cap, cnt.data()),
         "lsm2d_find_correspondences_batch", ctx.get());
   std::vector<CorrespondenceVector> out(n);
   for (size_t i = 0; i < n; ++i) out[i].assign(buf.begin() + (ptrdiff_t) (i * cap), buf.begin() + (ptrdiff_t) (i * cap + (size_t) cnt[i]));
   return out;
 }
 
-// SE2Plane2PlaneErrorFactor + robustifier over a correspondence vector (lsm2d_linearize; registration/aligner_slice_processor_laser_2d.h:4,8): H (row-major
-// 3x3), b and the statistics of cloud fixed_index of `fixed` against cloud moving_index of `moving` at `pose`.  The slice parameters' robustifier and
-// chi_threshold are the ones that matter here.
-struct Linearization {
-  std::array<float, 9> H{}; std::array<float, 3> b{}; lsm2d_iteration_stats stats{};
-};
+// SE2Plane2PlaneErrorFactor + robustifier over a correspondence vector (lsm2d_linearize; registration/aligner_slice_processor_laser_2d.h:4,8): H, b and the
+// statistics of cloud fixed_index of `fixed` against cloud moving_index of `moving` at `pose`.  The slice parameters' robustifier and chi_threshold are the
+// ones that matter here.
 inline Linearization linearize(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving, const CorrespondenceVector& pairs,
                                const Vector3f& pose, int32_t fixed_index = 0, int32_t moving_index = 0) {
   Linearization r;
-  check(lsm2d_linearize(ctx.get(), &sp, fixed.get(), fixed_index, moving.get(), moving_index, pairs.empty() ? nullptr : pairs.data(), (int32_t) pairs.size(),
-                        pose.data(), r.H.data(), r.b.data(), &r.stats),
+  check(lsm2d_linearize(ctx.get(), &sp, fixed.get(), fixed_index, moving.get(), moving_index, ptrOrNull(pairs), (int32_t) pairs.size(), pose.data(),
+                        r.H.data(), r.b.data(), &r.stats),
         "lsm2d_linearize", ctx.get());
   return r;
 }
@@ -130,24 +200,16 @@ inline std::vector<Linearization> linearizeBatch(Context& ctx, const lsm2d_slice
                                                  const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
   const size_t n = poses.size();
   if (pairs.size() != n) throw std::runtime_error("linearizeBatch| one correspondence vector per pose");
-  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
-    throw std::runtime_error("linearizeBatch| an index vector is empty or holds one entry per pose");
+  detail::checkIndexVectors("linearizeBatch", detail::ONE_PER_POSE, fixed_index, moving_index, n);
   size_t cap = 1;
   for (const auto& v : pairs) cap = std::max(cap, v.size());
   std::vector<Correspondence> buf(std::max<size_t>(cap * n, 1)); std::vector<int32_t> cnt(std::max<size_t>(n, 1), 0);
   for (size_t i = 0; i < n; ++i) { std::copy(pairs[i].begin(), pairs[i].end(), buf.begin() + (ptrdiff_t) (i * cap)); cnt[i] = (int32_t) pairs[i].size(); }
-  std::vector<float> H(9 * std::max<size_t>(n, 1)), b(3 * std::max<size_t>(n, 1)); std::vector<lsm2d_iteration_stats> st(std::max<size_t>(n, 1));
-  check(lsm2d_linearize_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
-                              moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, buf.data(), (int32_t) cap, cnt.data(),
-                              n ? poses[0].data() : nullptr, H.data(), b.data(), st.data()),
+  detail::RowBuffer rows(n);
+  check(lsm2d_linearize_batch(ctx.get(), &sp, fixed.get(), ptrOrNull(fixed_index), moving.get(), ptrOrNull(moving_index), (int32_t) n, buf.data(), (int32_t) cap,
+                              cnt.data(), ptrOrNull(poses), rows.H.data(), rows.b.data(), rows.stats.data()),
         "lsm2d_linearize_batch", ctx.get());
-  std::vector<Linearization> out(n);
-  for (size_t i = 0; i < n; ++i) {
-    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].H.begin());
-    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].b.begin());
-    out[i].stats = st[i];
-  }
-  return out;
+  return rows.rows<Linearization>(n);
 }
 
 // Finder, then factor, for poses.size() pose hypotheses with the pairs kept on the device (lsm2d_score_batch): item i matches cloud fixed_index[i] of
@@ -158,46 +220,31 @@ inline std::vector<Linearization> scoreBatch(Context& ctx, const lsm2d_slice_par
                                              const std::vector<Vector3f>& poses, const std::vector<int32_t>& fixed_index = {},
                                              const std::vector<int32_t>& moving_index = {}) {
   const size_t n = poses.size();
-  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
-    throw std::runtime_error("scoreBatch| an index vector is empty or holds one entry per pose");
-  std::vector<float> H(9 * std::max<size_t>(n, 1)), b(3 * std::max<size_t>(n, 1)); std::vector<lsm2d_iteration_stats> st(std::max<size_t>(n, 1));
-  check(lsm2d_score_batch(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
-                          moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, H.data(), b.data(), st.data()),
+  detail::checkIndexVectors("scoreBatch", detail::ONE_PER_POSE, fixed_index, moving_index, n);
+  detail::RowBuffer rows(n);
+  check(lsm2d_score_batch(ctx.get(), &sp, fixed.get(), ptrOrNull(fixed_index), moving.get(), ptrOrNull(moving_index), (int32_t) n, ptrOrNull(poses), rows.H.data(),
+                          rows.b.data(), rows.stats.data()),
         "lsm2d_score_batch", ctx.get());
-  std::vector<Linearization> out(n);
-  for (size_t i = 0; i < n; ++i) {
-    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].H.begin());
-    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].b.begin());
-    out[i].stats = st[i];
-  }
-  return out;
+  return rows.rows<Linearization>(n);
 }
 
 // scoreBatch's scoring, then the acceptance test and the best k accepted hypotheses ranked on the device (lsm2d_score_select): only k rows come down, with
 // one copy and one wait.  index[j] is the j-th best hypothesis -- inliers descending, chi_inliers ascending, index ascending -- and rows[j] what scoreBatch
 // returns for it, bit for bit; n_accepted counts the hypotheses that pass among all of them.
-struct Selection {
-  std::vector<int32_t> index; std::vector<Linearization> rows; int32_t n_accepted = 0;
-};
+struct Selection { std::vector<int32_t> index; std::vector<Linearization> rows; int32_t n_accepted = 0; };
 inline Selection scoreSelect(Context& ctx, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
                              const lsm2d_select_params& select, int32_t k, const std::vector<int32_t>& fixed_index = {},
                              const std::vector<int32_t>& moving_index = {}) {
   const size_t n = poses.size();
-  if ((!fixed_index.empty() && fixed_index.size() != n) || (!moving_index.empty() && moving_index.size() != n))
-    throw std::runtime_error("scoreSelect| an index vector is empty or holds one entry per pose");
+  detail::checkIndexVectors("scoreSelect", detail::ONE_PER_POSE, fixed_index, moving_index, n);
   const size_t cap = (size_t) std::max<int32_t>(k, 1);
-  std::vector<int32_t> idx(cap); std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap);
+  detail::RowBuffer rows(cap);
   int32_t n_sel = 0; Selection out;
-  check(lsm2d_score_select(ctx.get(), &sp, fixed.get(), fixed_index.empty() ? nullptr : fixed_index.data(), moving.get(),
-                           moving_index.empty() ? nullptr : moving_index.data(), (int32_t) n, n ? poses[0].data() : nullptr, &select, k, idx.data(), H.data(),
-                           b.data(), st.data(), &n_sel, &out.n_accepted),
+  out.index.resize(cap);
+  check(lsm2d_score_select(ctx.get(), &sp, fixed.get(), ptrOrNull(fixed_index), moving.get(), ptrOrNull(moving_index), (int32_t) n, ptrOrNull(poses), &select, k,
+                           out.index.data(), rows.H.data(), rows.b.data(), rows.stats.data(), &n_sel, &out.n_accepted),
         "lsm2d_score_select", ctx.get());
-  out.index.assign(idx.begin(), idx.begin() + n_sel); out.rows.resize((size_t) n_sel);
-  for (size_t i = 0; i < (size_t) n_sel; ++i) {
-    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out.rows[i].H.begin());
-    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out.rows[i].b.begin());
-    out.rows[i].stats = st[i];
-  }
+  out.index.resize((size_t) n_sel); out.rows = rows.rows<Linearization>((size_t) n_sel);
   return out;
 }
 
@@ -207,22 +254,46 @@ inline bool selectAccept(const lsm2d_iteration_stats& st, const lsm2d_select_par
   return st.n_inliers >= p.min_inliers && st.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= p.max_chi_per_inlier && n_in / n_c >= p.min_inlier_ratio;
 }
 
-// The candidate loop of the relocaliser / loop detector (MULTI.json:749-769, :964-986) over poses.size() hypotheses of one laser slice: scoreSelect, then
-// lsm2d_align_batch on the selected hypotheses from their own poses, then the acceptance test on the statistics of the last iteration each started.  Pure
-// composition: the same as calling the two entry points by hand.
-struct Relocalization {
-  Selection selection;
+// What both relocalize() add to their selection: the selected hypotheses aligned from their own poses (lsm2d_align_batch), row j for selection.index[j];
+// last_stats[j] the statistics of the last iteration it started and accepted[j] whether the aligner succeeded and those pass the acceptance test.
+struct AlignedSelection {
   std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> status, iterations;
   std::vector<lsm2d_iteration_stats> last_stats; std::vector<char> accepted;
 };
+namespace detail {
+// the tail of both relocalize(): the selected items' poses and priors (their clouds come spelled out, `fi` / `mi`: NULL means "cloud i" only while the batch
+// is the whole set), the aligner on them, each one's last started iteration, the acceptance test on it
+inline void alignSelected(Context& ctx, const lsm2d_aligner_params& aligner, const lsm2d_slice_params* slices, std::vector<const lsm2d_cloudset*> fixed,
+                          std::vector<const lsm2d_cloudset*> moving, const std::vector<int32_t>& selected, const std::vector<Vector3f>& poses,
+                          const std::vector<lsm2d_prior>& priors, const std::vector<int32_t>& fi, const std::vector<int32_t>& mi,
+                          const lsm2d_select_params& select, AlignedSelection& r) {
+  const size_t m = selected.size();
+  std::vector<Vector3f> x0(m); std::vector<lsm2d_prior> pr;
+  for (size_t j = 0; j < m; ++j) { x0[j] = poses[(size_t) selected[j]]; if (!priors.empty()) pr.push_back(priors[(size_t) selected[j]]); }
+  const BatchDescriptor d(m, slices, std::move(fixed), std::move(moving), ptrOrNull(x0), ptrOrNull(pr), ptrOrNull(fi), ptrOrNull(mi));
+  const size_t cap = (size_t) lsm2d_stats_capacity(&aligner);
+  std::vector<lsm2d_iteration_stats> st(m * cap);
+  r.pose.resize(m); r.information.resize(m); r.status.resize(m); r.iterations.resize(m); r.last_stats.resize(m); r.accepted.resize(m);
+  check(lsm2d_align_batch(ctx.get(), &aligner, &d.b, r.pose[0].data(), r.information[0].data(), r.status.data(), r.iterations.data(), st.data()),
+        "lsm2d_align_batch", ctx.get());
+  for (size_t j = 0; j < m; ++j) {
+    const size_t it = (size_t) std::min<long>(std::max<long>((long) r.iterations[j] - 1, 0), (long) cap - 1);
+    r.last_stats[j] = st[j * cap + it];
+    r.accepted[j] = r.status[j] == LSM2D_SUCCESS && selectAccept(r.last_stats[j], select);
+  }
+}
+}  // namespace detail
+
+// The candidate loop of the relocaliser / loop detector (MULTI.json:749-769, :964-986) over poses.size() hypotheses of one laser slice: scoreSelect, then
+// lsm2d_align_batch on the selected hypotheses from their own poses, then the acceptance test on the statistics of the last iteration each started.  Pure
+// composition: the same as calling the two entry points by hand.
+struct Relocalization : AlignedSelection { Selection selection; };
 inline Relocalization relocalize(Context& ctx, const lsm2d_aligner_params& aligner, const lsm2d_slice_params& sp, const CloudSet& fixed, const CloudSet& moving,
                                  const std::vector<Vector3f>& poses, const lsm2d_select_params& select, int32_t k,
                                  const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
   Relocalization r;
   r.selection = scoreSelect(ctx, sp, fixed, moving, poses, select, k, fixed_index, moving_index);
-  const size_t m = r.selection.index.size();
-  if (!m) return r;
-  // the selected items' clouds, spelled out: NULL means "cloud i" only while the batch is the whole set
+  if (r.selection.index.empty()) return r;
   auto chosen = [&](const CloudSet& cs, const std::vector<int32_t>& idx) {
     std::vector<int32_t> out;
     if (idx.empty() && cs.numClouds() == 1) return out;
@@ -230,21 +301,7 @@ inline Relocalization relocalize(Context& ctx, const lsm2d_aligner_params& align
     return out;
   };
   const std::vector<int32_t> fi = chosen(fixed, fixed_index), mi = chosen(moving, moving_index);
-  std::vector<Vector3f> x0(m);
-  for (size_t j = 0; j < m; ++j) x0[j] = poses[(size_t) r.selection.index[j]];
-  const lsm2d_cloudset* fx[1] = {fixed.get()}; const lsm2d_cloudset* mv[1] = {moving.get()};
-  lsm2d_batch b{}; b.n_alignments = (int32_t) m; b.n_slices = 1; b.slices = &sp; b.fixed = fx; b.moving = mv;
-  b.fixed_index = fi.empty() ? nullptr : fi.data(); b.moving_index = mi.empty() ? nullptr : mi.data(); b.init_pose = x0[0].data();
-  const size_t cap = (size_t) lsm2d_stats_capacity(&aligner);
-  std::vector<lsm2d_iteration_stats> st(m * cap);
-  r.pose.resize(m); r.information.resize(m); r.status.resize(m); r.iterations.resize(m); r.last_stats.resize(m); r.accepted.resize(m);
-  check(lsm2d_align_batch(ctx.get(), &aligner, &b, r.pose[0].data(), r.information[0].data(), r.status.data(), r.iterations.data(), st.data()),
-        "lsm2d_align_batch", ctx.get());
-  for (size_t j = 0; j < m; ++j) {
-    const size_t it = (size_t) std::min<long>(std::max<long>((long) r.iterations[j] - 1, 0), (long) cap - 1);
-    r.last_stats[j] = st[j * cap + it];
-    r.accepted[j] = r.status[j] == LSM2D_SUCCESS && selectAccept(r.last_stats[j], select);
-  }
+  detail::alignSelected(ctx, aligner, &sp, {fixed.get()}, {moving.get()}, r.selection.index, poses, {}, fi, mi, select, r);
   return r;
 }
 
@@ -261,19 +318,16 @@ inline AlignSelection alignSelect(Context& ctx, const lsm2d_aligner_params& alig
                                   const lsm2d_select_params& select, int32_t k, const std::vector<lsm2d_prior>& priors = {},
                                   const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
   const size_t n = init_pose.size(), ns = slices.size();
-  if (fixed.size() != ns || moving.size() != ns) throw std::runtime_error("alignSelect| one fixed and one moving set per slice");
-  if ((!fixed_index.empty() && fixed_index.size() != ns * n) || (!moving_index.empty() && moving_index.size() != ns * n) || (!priors.empty() && priors.size() != n))
-    throw std::runtime_error("alignSelect| an index vector is empty or [n_slices][n]; priors is empty or holds one per candidate");
-  std::vector<const lsm2d_cloudset*> fx, mv;
-  for (size_t s = 0; s < ns; ++s) { fx.push_back(fixed[s] ? fixed[s]->get() : nullptr); mv.push_back(moving[s] ? moving[s]->get() : nullptr); }
-  lsm2d_batch b{}; b.n_alignments = (int32_t) n; b.n_slices = (int32_t) ns; b.slices = slices.data(); b.fixed = fx.data(); b.moving = mv.data();
-  b.fixed_index = fixed_index.empty() ? nullptr : fixed_index.data(); b.moving_index = moving_index.empty() ? nullptr : moving_index.data();
-  b.init_pose = n ? init_pose[0].data() : nullptr; b.prior = priors.empty() ? nullptr : priors.data();
+  detail::checkSetsPerSlice("alignSelect", ns, fixed, moving);
+  detail::checkIndexVectors("alignSelect", "an index vector is empty or [n_slices][n]; priors is empty or holds one per candidate", fixed_index, moving_index, ns * n,
+                            detail::emptyOrHolds(priors, n));
+  const detail::BatchDescriptor d(n, slices.data(), detail::handles(fixed), detail::handles(moving), ptrOrNull(init_pose), ptrOrNull(priors), ptrOrNull(fixed_index),
+                                  ptrOrNull(moving_index));
   const size_t cap = (size_t) std::max<int32_t>(k, 1);
   AlignSelection out; int32_t n_sel = 0;
   out.index.resize(cap); out.pose.resize(cap); out.information.resize(cap); out.iterations.resize(cap); out.last_stats.resize(cap);
   static_assert(sizeof(Vector3f) == 3 * sizeof(float) && sizeof(std::array<float, 9>) == 9 * sizeof(float), "rows are packed");
-  check(lsm2d_align_select(ctx.get(), &aligner, &b, &select, k, out.index.data(), out.pose[0].data(), out.information[0].data(), out.iterations.data(),
+  check(lsm2d_align_select(ctx.get(), &aligner, &d.b, &select, k, out.index.data(), out.pose[0].data(), out.information[0].data(), out.iterations.data(),
                            out.last_stats.data(), &n_sel, &out.n_accepted, &out.n_success),
         "lsm2d_align_select", ctx.get());
   out.index.resize((size_t) n_sel); out.pose.resize((size_t) n_sel); out.information.resize((size_t) n_sel); out.iterations.resize((size_t) n_sel);
@@ -285,70 +339,37 @@ inline AlignSelection alignSelect(Context& ctx, const lsm2d_aligner_params& alig
 // (lsm2d_score_aligner_batch / lsm2d_score_aligner_select).  slices[s] reads fixed[s] / moving[s]; the index vectors are empty or [n_slices][n] flat, as
 // lsm2d_batch takes them; priors is empty or holds one per pose.  A row is what the first iteration of lsm2d_align_batch holds just before its solve;
 // active counts the slices that contributed (0: zeros, the hypothesis the aligner would end with LSM2D_NOT_ENOUGH_CORRESPONDENCES).
-struct AlignerScore { Linearization row; int32_t active = 0; };
 struct AlignerSelection { std::vector<int32_t> index; std::vector<AlignerScore> rows; int32_t n_accepted = 0; };
-namespace detail {
-struct ScoreAlignerBatch {
-  std::vector<const lsm2d_cloudset*> fx, mv; lsm2d_batch b{};
-  ScoreAlignerBatch(const char* who, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
-                    const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses, const std::vector<lsm2d_prior>& priors,
-                    const std::vector<int32_t>& fixed_index, const std::vector<int32_t>& moving_index) {
-    const size_t n = poses.size(), ns = slices.size();
-    if (fixed.size() != ns || moving.size() != ns) throw std::runtime_error(std::string(who) + "| one fixed and one moving set per slice");
-    if ((!fixed_index.empty() && fixed_index.size() != ns * n) || (!moving_index.empty() && moving_index.size() != ns * n))
-      throw std::runtime_error(std::string(who) + "| an index vector is empty or holds n_slices x n entries");
-    if (!priors.empty() && priors.size() != n) throw std::runtime_error(std::string(who) + "| priors is empty or holds one per pose");
-    for (size_t s = 0; s < ns; ++s) { fx.push_back(fixed[s] ? fixed[s]->get() : nullptr); mv.push_back(moving[s] ? moving[s]->get() : nullptr); }
-    b.n_alignments = (int32_t) n; b.n_slices = (int32_t) ns; b.slices = slices.data(); b.fixed = fx.data(); b.moving = mv.data();
-    b.fixed_index = fixed_index.empty() ? nullptr : fixed_index.data(); b.moving_index = moving_index.empty() ? nullptr : moving_index.data();
-    b.init_pose = n ? poses[0].data() : nullptr; b.prior = priors.empty() ? nullptr : priors.data();
-  }
-};
-inline void fillAlignerScores(std::vector<AlignerScore>& out, size_t m, const std::vector<float>& H, const std::vector<float>& b,
-                              const std::vector<lsm2d_iteration_stats>& st, const std::vector<int32_t>& active) {
-  out.resize(m);
-  for (size_t i = 0; i < m; ++i) {
-    std::copy(H.begin() + (ptrdiff_t) (9 * i), H.begin() + (ptrdiff_t) (9 * i + 9), out[i].row.H.begin());
-    std::copy(b.begin() + (ptrdiff_t) (3 * i), b.begin() + (ptrdiff_t) (3 * i + 3), out[i].row.b.begin());
-    out[i].row.stats = st[i]; out[i].active = active[i];
-  }
-}
-}  // namespace detail
 inline std::vector<AlignerScore> scoreAligner(Context& ctx, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
                                               const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses,
                                               const std::vector<lsm2d_prior>& priors = {}, const std::vector<int32_t>& fixed_index = {},
                                               const std::vector<int32_t>& moving_index = {}) {
-  const detail::ScoreAlignerBatch d("scoreAligner", slices, fixed, moving, poses, priors, fixed_index, moving_index);
-  const size_t n = poses.size(), cap = std::max<size_t>(n, 1);
-  std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap); std::vector<int32_t> active(cap, 0);
-  check(lsm2d_score_aligner_batch(ctx.get(), &d.b, H.data(), b.data(), st.data(), active.data()), "lsm2d_score_aligner_batch", ctx.get());
-  std::vector<AlignerScore> out; detail::fillAlignerScores(out, n, H, b, st, active);
-  return out;
+  const detail::BatchDescriptor d = detail::alignerBatch("scoreAligner", slices, fixed, moving, poses, priors, fixed_index, moving_index);
+  detail::RowBuffer rows(poses.size(), true);
+  check(lsm2d_score_aligner_batch(ctx.get(), &d.b, rows.H.data(), rows.b.data(), rows.stats.data(), rows.active.data()), "lsm2d_score_aligner_batch", ctx.get());
+  return rows.rows<AlignerScore>(poses.size());
 }
 // ... then the acceptance test and the best k accepted hypotheses ranked on the device, as scoreSelect ranks; a hypothesis with active == 0 is rejected
 inline AlignerSelection scoreAlignerSelect(Context& ctx, const std::vector<lsm2d_slice_params>& slices, const std::vector<const CloudSet*>& fixed,
                                            const std::vector<const CloudSet*>& moving, const std::vector<Vector3f>& poses, const lsm2d_select_params& select,
                                            int32_t k, const std::vector<lsm2d_prior>& priors = {}, const std::vector<int32_t>& fixed_index = {},
                                            const std::vector<int32_t>& moving_index = {}) {
-  const detail::ScoreAlignerBatch d("scoreAlignerSelect", slices, fixed, moving, poses, priors, fixed_index, moving_index);
+  const detail::BatchDescriptor d = detail::alignerBatch("scoreAlignerSelect", slices, fixed, moving, poses, priors, fixed_index, moving_index);
   const size_t cap = (size_t) std::max<int32_t>(k, 1);
-  std::vector<int32_t> idx(cap), active(cap, 0); std::vector<float> H(9 * cap), b(3 * cap); std::vector<lsm2d_iteration_stats> st(cap);
+  detail::RowBuffer rows(cap, true);
   int32_t n_sel = 0; AlignerSelection out;
-  check(lsm2d_score_aligner_select(ctx.get(), &d.b, &select, k, idx.data(), H.data(), b.data(), st.data(), active.data(), &n_sel, &out.n_accepted),
+  out.index.resize(cap);
+  check(lsm2d_score_aligner_select(ctx.get(), &d.b, &select, k, out.index.data(), rows.H.data(), rows.b.data(), rows.stats.data(), rows.active.data(), &n_sel,
+                                   &out.n_accepted),
         "lsm2d_score_aligner_select", ctx.get());
-  out.index.assign(idx.begin(), idx.begin() + n_sel);
-  detail::fillAlignerScores(out.rows, (size_t) n_sel, H, b, st, active);
+  out.index.resize((size_t) n_sel); out.rows = rows.rows<AlignerScore>((size_t) n_sel);
   return out;
 }
 
 // relocalize for the two-laser robot (MULTI.json:700-732: two WithSensor slices and the odometry prior; the relocaliser's own aligner is unset, :749-769,
 // and falls back on it): scoreAlignerSelect, then lsm2d_align_batch on the selected hypotheses from their own poses with their own priors, then the
 // acceptance test on the statistics of the last iteration each started.  Pure composition.
-struct AlignerRelocalization {
-  AlignerSelection selection;
-  std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> status, iterations;
-  std::vector<lsm2d_iteration_stats> last_stats; std::vector<char> accepted;
-};
+struct AlignerRelocalization : AlignedSelection { AlignerSelection selection; };
 inline AlignerRelocalization relocalize(Context& ctx, const lsm2d_aligner_params& aligner, const std::vector<lsm2d_slice_params>& slices,
                                         const std::vector<const CloudSet*>& fixed, const std::vector<const CloudSet*>& moving,
                                         const std::vector<Vector3f>& poses, const lsm2d_select_params& select, int32_t k,
@@ -356,9 +377,9 @@ inline AlignerRelocalization relocalize(Context& ctx, const lsm2d_aligner_params
                                         const std::vector<int32_t>& moving_index = {}) {
   AlignerRelocalization r;
   r.selection = scoreAlignerSelect(ctx, slices, fixed, moving, poses, select, k, priors, fixed_index, moving_index);
-  const size_t m = r.selection.index.size(), n = poses.size(), ns = slices.size();
-  if (!m) return r;
-  // the selected items' clouds, spelled out for every slice: NULL means "cloud i" only while the batch is the whole set
+  const size_t n = poses.size(), ns = slices.size();
+  if (r.selection.index.empty()) return r;
+  // (for every slice; not the one-slice relocalize's lambda, which asks a set for its number of clouds once: the calls a program makes stay what they were)
   auto chosen = [&](const std::vector<const CloudSet*>& sets, const std::vector<int32_t>& idx) {
     std::vector<int32_t> out;
     bool all_single = idx.empty();
@@ -369,34 +390,41 @@ inline AlignerRelocalization relocalize(Context& ctx, const lsm2d_aligner_params
     return out;
   };
   const std::vector<int32_t> fi = chosen(fixed, fixed_index), mi = chosen(moving, moving_index);
-  std::vector<Vector3f> x0(m); std::vector<lsm2d_prior> pr;
-  for (size_t j = 0; j < m; ++j) { x0[j] = poses[(size_t) r.selection.index[j]]; if (!priors.empty()) pr.push_back(priors[(size_t) r.selection.index[j]]); }
-  const detail::ScoreAlignerBatch d("relocalize", slices, fixed, moving, x0, pr, fi, mi);
-  const size_t cap = (size_t) lsm2d_stats_capacity(&aligner);
-  std::vector<lsm2d_iteration_stats> st(m * cap);
-  r.pose.resize(m); r.information.resize(m); r.status.resize(m); r.iterations.resize(m); r.last_stats.resize(m); r.accepted.resize(m);
-  check(lsm2d_align_batch(ctx.get(), &aligner, &d.b, r.pose[0].data(), r.information[0].data(), r.status.data(), r.iterations.data(), st.data()),
-        "lsm2d_align_batch", ctx.get());
-  for (size_t j = 0; j < m; ++j) {
-    const size_t it = (size_t) std::min<long>(std::max<long>((long) r.iterations[j] - 1, 0), (long) cap - 1);
-    r.last_stats[j] = st[j * cap + it];
-    r.accepted[j] = r.status[j] == LSM2D_SUCCESS && selectAccept(r.last_stats[j], select);
-  }
+  detail::alignSelected(ctx, aligner, slices.data(), detail::handles(fixed), detail::handles(moving), r.selection.index, poses, priors, fi, mi, select, r);
   return r;
 }
 
-class CorrespondenceFinderProjective2f {
+// what every finder class has: the two clouds (uploaded when set; the reference keeps raw pointers and a _fixed_changed_flag), the pose, where the pairs
+// go, and the one lsm2d_find_correspondences call.  A finder kind adds its parameters, how many pairs to make room for and what it refuses.
+class CorrespondenceFinderBase {
  public:
-  explicit CorrespondenceFinderProjective2f(Context& ctx) : _ctx(ctx) {}
+  void setFixed(const PointNormal2fVectorCloud* fixed) { _fixed.reset(fixed ? new CloudSet(_ctx, *fixed) : nullptr); }
+  void setMoving(const PointNormal2fVectorCloud* moving) { _moving.reset(moving ? new CloudSet(_ctx, *moving) : nullptr); _n_moving = moving ? moving->size() : 0; }
+  void setLocalMapInSensor(const Vector3f& pose) { _local_map_in_sensor = pose; }
+  void setCorrespondences(CorrespondenceVector* c) { _correspondences = c; }
+ protected:
+  explicit CorrespondenceFinderBase(Context& ctx) : _ctx(ctx) {}
+  // room for `capacity` pairs, then as many as were found (projective .cpp:49,76; kd .cpp:10; nn .cpp:60)
+  void find(const lsm2d_slice_params& sp, size_t capacity) {
+    _correspondences->resize(capacity);
+    int32_t k = 0;
+    check(lsm2d_find_correspondences(_ctx.get(), &sp, _fixed->get(), 0, _moving->get(), 0, _local_map_in_sensor.data(), _correspondences->data(),
+                                     (int32_t) _correspondences->size(), &k),
+          "lsm2d_find_correspondences", _ctx.get());
+    _correspondences->resize((size_t) k);
+  }
+  Context& _ctx;
+  std::unique_ptr<CloudSet> _fixed, _moving; size_t _n_moving = 0;
+  Vector3f _local_map_in_sensor{{0.f, 0.f, 0.f}};
+  CorrespondenceVector* _correspondences = nullptr;
+};
+
+class CorrespondenceFinderProjective2f : public CorrespondenceFinderBase {
+ public:
+  explicit CorrespondenceFinderProjective2f(Context& ctx) : CorrespondenceFinderBase(ctx) {}
   float param_point_distance = 0.5f;   // .h:16-20
   float param_normal_cos = 0.8f;       // .h:21
   PointNormal2fProjectorPolarPtr param_projector{new PointNormal2fProjectorPolar};
-
-  // the clouds are uploaded when set (the reference keeps raw pointers and a _fixed_changed_flag)
-  void setFixed(const PointNormal2fVectorCloud* fixed) { _fixed.reset(fixed ? new CloudSet(_ctx, *fixed) : nullptr); }
-  void setMoving(const PointNormal2fVectorCloud* moving) { _moving.reset(moving ? new CloudSet(_ctx, *moving) : nullptr); }
-  void setLocalMapInSensor(const Vector3f& pose) { _local_map_in_sensor = pose; }
-  void setCorrespondences(CorrespondenceVector* c) { _correspondences = c; }
 
   lsm2d_slice_params sliceParams() const {
     lsm2d_slice_params sp{};
@@ -411,12 +439,7 @@ class CorrespondenceFinderProjective2f {
     if (!_moving) throw std::runtime_error("CorrespondenceFinderProjective2f::compute| Missing moving!");
     if (!_correspondences) throw std::runtime_error("CorrespondenceFinderProjective2f::compute| Missing correspondences!");
     const lsm2d_slice_params sp = sliceParams();
-    _correspondences->resize((size_t) sp.projector.canvas_cols);        // .cpp:49
-    int32_t k = 0;
-    check(lsm2d_find_correspondences(_ctx.get(), &sp, _fixed->get(), 0, _moving->get(), 0, _local_map_in_sensor.data(),
-                                     _correspondences->data(), (int32_t) _correspondences->size(), &k),
-          "lsm2d_find_correspondences", _ctx.get());
-    _correspondences->resize((size_t) k);                                 // .cpp:76
+    find(sp, (size_t) sp.projector.canvas_cols);
   }
   // compute() for a whole batch of (fixed, moving, pose) triples in one launch: see findCorrespondencesBatch
   std::vector<CorrespondenceVector> computeBatch(const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
@@ -424,27 +447,18 @@ class CorrespondenceFinderProjective2f {
     if (!param_projector) throw std::runtime_error("CorrespondenceFinderProjective2f::computeBatch| Missing Projector");
     return findCorrespondencesBatch(_ctx, sliceParams(), fixed, moving, poses, fixed_index, moving_index);
   }
- private:
-  Context& _ctx;
-  std::unique_ptr<CloudSet> _fixed, _moving;
-  Vector3f _local_map_in_sensor{{0.f, 0.f, 0.f}};
-  CorrespondenceVector* _correspondences = nullptr;
 };
 
 // CorrespondenceFinderKDTree2D (registration/correspondence_finder_kd_tree_2d.{h,cpp}) and CorrespondenceFinderNN2D
 // (registration/correspondence_finder_nn_2d.{h,cpp}): same surface, different lsm2d_finder.
-class CorrespondenceFinderPointQuery {
+class CorrespondenceFinderPointQuery : public CorrespondenceFinderBase {
  public:
-  CorrespondenceFinderPointQuery(Context& ctx, int finder) : _ctx(ctx), _finder(finder) {}
+  CorrespondenceFinderPointQuery(Context& ctx, int finder) : CorrespondenceFinderBase(ctx), _finder(finder) {}
   float param_max_distance_m = 1e-2f;   // kd .h:23 (nn .h:20-24 defaults to 1)
   float param_resolution = 5e-2f;       // nn .h:25-29
   float param_normal_cos = 0.8f;
   float param_max_leaf_range = 1e-2f;   // kd .h:26-28 -- honoured by LSM2D_FINDER_KDTREE (search "kdtree")
   unsigned param_min_leaf_points = 20;  // kd .h:29-33
-  void setFixed(const PointNormal2fVectorCloud* fixed) { _fixed.reset(fixed ? new CloudSet(_ctx, *fixed) : nullptr); }
-  void setMoving(const PointNormal2fVectorCloud* moving) { _moving.reset(moving ? new CloudSet(_ctx, *moving) : nullptr); _n_moving = moving ? moving->size() : 0; }
-  void setLocalMapInSensor(const Vector3f& pose) { _local_map_in_sensor = pose; }
-  void setCorrespondences(CorrespondenceVector* c) { _correspondences = c; }
   lsm2d_slice_params sliceParams() const {
     lsm2d_slice_params sp{};
     sp.finder = _finder; sp.projector = PointNormal2fProjectorPolar().abi();
@@ -453,28 +467,22 @@ class CorrespondenceFinderPointQuery {
     return sp;
   }
   void compute() {
-    if (_finder == LSM2D_FINDER_DISTMAP && !(param_resolution > 0.f)) throw std::runtime_error("resolution must be > 0");      // nn .cpp:11-14
+    refuseBadResolution();
     if (!_fixed || !_moving || !_correspondences) throw std::runtime_error("CorrespondenceFinder::compute| missing fixed, moving or correspondences");
-    const lsm2d_slice_params sp = sliceParams();
-    _correspondences->resize(_n_moving);                                   // kd .cpp:10, nn .cpp:60
-    int32_t k = 0;
-    check(lsm2d_find_correspondences(_ctx.get(), &sp, _fixed->get(), 0, _moving->get(), 0, _local_map_in_sensor.data(),
-                                     _correspondences->data(), (int32_t) _correspondences->size(), &k),
-          "lsm2d_find_correspondences", _ctx.get());
-    _correspondences->resize((size_t) k);
+    find(sliceParams(), _n_moving);
   }
   // compute() for a whole batch of (fixed, moving, pose) triples in one launch: see findCorrespondencesBatch
   std::vector<CorrespondenceVector> computeBatch(const CloudSet& fixed, const CloudSet& moving, const std::vector<Vector3f>& poses,
                                                  const std::vector<int32_t>& fixed_index = {}, const std::vector<int32_t>& moving_index = {}) {
-    if (_finder == LSM2D_FINDER_DISTMAP && !(param_resolution > 0.f)) throw std::runtime_error("resolution must be > 0");
+    refuseBadResolution();
     return findCorrespondencesBatch(_ctx, sliceParams(), fixed, moving, poses, fixed_index, moving_index);
   }
  protected:
-  Context& _ctx; int _finder;
+  int _finder;
  private:
-  std::unique_ptr<CloudSet> _fixed, _moving; size_t _n_moving = 0;
-  Vector3f _local_map_in_sensor{{0.f, 0.f, 0.f}};
-  CorrespondenceVector* _correspondences = nullptr;
+  void refuseBadResolution() const {      // nn .cpp:11-14
+    if (_finder == LSM2D_FINDER_DISTMAP && !(param_resolution > 0.f)) throw std::runtime_error("resolution must be > 0");
+  }
 };
 // search "kdtree" (default): the reference's own tree and single-leaf descent (approximate, honours max_leaf_range / min_leaf_points);
 // "exact": an exact nearest-neighbour search on a uniform grid (LSM2D_FINDER_NN), for which the two leaf parameters have no meaning
@@ -494,19 +502,17 @@ struct CorrespondenceFinderNN2D : CorrespondenceFinderPointQuery {
 // a single growable device cloud: the tracker's local map / the clipped scene
 class ReservedCloud {
  public:
-  ReservedCloud(Context& ctx, int64_t capacity) : _ctx(ctx) { check(lsm2d_cloudset_create_reserved(ctx.get(), capacity, &_h), "lsm2d_cloudset_create_reserved", ctx.get()); }
-  ~ReservedCloud() { lsm2d_cloudset_destroy(_h); }
-  ReservedCloud(const ReservedCloud&) = delete; ReservedCloud& operator=(const ReservedCloud&) = delete;
+  ReservedCloud(Context& ctx, int64_t capacity) : _ctx(ctx) { check(lsm2d_cloudset_create_reserved(ctx.get(), capacity, _h.out()), "lsm2d_cloudset_create_reserved", ctx.get()); }
   lsm2d_cloudset* get() const { return _h; }
-  void upload(const PointNormal2fVectorCloud& c) { check(lsm2d_cloudset_upload(_h, c.empty() ? nullptr : &c[0].x, (int64_t) c.size()), "lsm2d_cloudset_upload", _ctx.get()); }
+  void upload(const PointNormal2fVectorCloud& c) { check(lsm2d_cloudset_upload(get(), ptrOrNull(c), (int64_t) c.size()), "lsm2d_cloudset_upload", _ctx.get()); }
   PointNormal2fVectorCloud download() const {
-    PointNormal2fVectorCloud c((size_t) lsm2d_cloudset_num_points(_h)); int64_t n = 0;
-    check(lsm2d_cloudset_download(_h, 0, c.empty() ? nullptr : &c[0].x, (int64_t) c.size(), &n), "lsm2d_cloudset_download", _ctx.get());
+    PointNormal2fVectorCloud c((size_t) size()); int64_t n = 0;
+    check(lsm2d_cloudset_download(get(), 0, c.empty() ? nullptr : &c[0].x, (int64_t) c.size(), &n), "lsm2d_cloudset_download", _ctx.get());
     c.resize((size_t) n); return c;
   }
-  int64_t size() const { return lsm2d_cloudset_num_points(_h); }
+  int64_t size() const { return lsm2d_cloudset_num_points(get()); }
  private:
-  Context& _ctx; lsm2d_cloudset* _h = nullptr;
+  Context& _ctx; detail::CloudSetHandle _h;
 };
 
 // SceneClipperProjective2D (mapping/scene_clipper_projective_2d.{h,cpp})
@@ -627,8 +633,7 @@ class MultiAligner2D {
       own.emplace_back(new CloudSet(_ctx, *fi->second)); fx.push_back(own.back()->get());
       own.emplace_back(new CloudSet(_ctx, *mi->second)); mv.push_back(own.back()->get());
     }
-    lsm2d_batch b{}; b.n_alignments = 1; b.n_slices = ns; b.slices = sp.data(); b.fixed = fx.data(); b.moving = mv.data();
-    b.init_pose = _moving_in_fixed.data(); b.prior = _has_prior ? &_prior : nullptr;
+    const detail::BatchDescriptor d(1, sp.data(), std::move(fx), std::move(mv), _moving_in_fixed.data(), _has_prior ? &_prior : nullptr);
     lsm2d_aligner_params ap{param_max_iterations, param_min_num_inliers, param_damping, param_termination_chi_epsilon,
                             param_enable_inlier_only_runs ? 1 : 0, param_keep_only_inlier_correspondences ? 1 : 0};
     _stats.assign((size_t) lsm2d_stats_capacity(&ap), lsm2d_iteration_stats{});
@@ -637,15 +642,15 @@ class MultiAligner2D {
     if (store_correspondences) {
       size_t cap = 1;
       for (int s = 0; s < ns; ++s) {
-        const size_t need = sp[(size_t) s].finder == LSM2D_FINDER_PROJECTIVE ? (size_t) sp[(size_t) s].projector.canvas_cols : (size_t) lsm2d_cloudset_num_points(mv[(size_t) s]);
+        const size_t need = sp[(size_t) s].finder == LSM2D_FINDER_PROJECTIVE ? (size_t) sp[(size_t) s].projector.canvas_cols : (size_t) lsm2d_cloudset_num_points(d.mv[(size_t) s]);
         cap = need > cap ? need : cap;
       }
       std::vector<lsm2d_correspondence> buf(cap * (size_t) ns); std::vector<int32_t> cnt((size_t) ns, 0);
-      check(lsm2d_align_batch_pairs(_ctx.get(), &ap, &b, _moving_in_fixed.data(), _information.data(), &st, &its, _stats.data(), buf.data(), (int32_t) cap, cnt.data()),
+      check(lsm2d_align_batch_pairs(_ctx.get(), &ap, &d.b, _moving_in_fixed.data(), _information.data(), &st, &its, _stats.data(), buf.data(), (int32_t) cap, cnt.data()),
             "lsm2d_align_batch_pairs", _ctx.get());
       for (int s = 0; s < ns; ++s) _pairs[(size_t) s].assign(buf.begin() + (long) (cap * (size_t) s), buf.begin() + (long) (cap * (size_t) s) + cnt[(size_t) s]);
     } else {
-      check(lsm2d_align_batch(_ctx.get(), &ap, &b, _moving_in_fixed.data(), _information.data(), &st, &its, _stats.data()), "lsm2d_align_batch", _ctx.get());
+      check(lsm2d_align_batch(_ctx.get(), &ap, &d.b, _moving_in_fixed.data(), _information.data(), &st, &its, _stats.data()), "lsm2d_align_batch", _ctx.get());
     }
     _stats.resize((size_t) its); _status = st;
   }
@@ -681,15 +686,12 @@ class LaserMessageBatchStream {
     pose.resize((size_t) n_scans); information.resize((size_t) n_scans); status.resize((size_t) n_scans); iterations.resize((size_t) n_scans);
     _start.resize((size_t) n_scans);
   }
-  ~LaserMessageBatchStream() {
-    try { while (flush()) {} } catch (...) {}
-    for (auto* s : _sets) if (s) lsm2d_cloudset_destroy(s);
-  }
+  ~LaserMessageBatchStream() { try { while (flush()) {} } catch (...) {} }
   LaserMessageBatchStream(const LaserMessageBatchStream&) = delete; LaserMessageBatchStream& operator=(const LaserMessageBatchStream&) = delete;
   bool push(const float* ranges /* [n_scans][n_beams] */, const Vector3f* init_pose /* [n_scans] */) {
     if (_pushed > _begun) begin_next();                                   // batch k - 1: its scans are on the device (or on their way)
     if (!_sets[0])                                                        // the first push makes the three sets (allocation; nothing is in flight yet), every later one refills
-      for (auto& s : _sets) check(lsm2d_preprocess_scans(_ctx.get(), &_pre, ranges, _n, &s), "lsm2d_preprocess_scans", _ctx.get());
+      for (auto& s : _sets) check(lsm2d_preprocess_scans(_ctx.get(), &_pre, ranges, _n, s.out()), "lsm2d_preprocess_scans", _ctx.get());
     else                                                                  // (the set batch k - 3 read: retired by the previous push)
       check(lsm2d_preprocess_scans_refill(_ctx.get(), &_pre, ranges, _n, _sets[_pushed % 3]), "lsm2d_preprocess_scans_refill", _ctx.get());
     _start.assign(init_pose, init_pose + _n);
@@ -703,7 +705,7 @@ class LaserMessageBatchStream {
   long retired() const { return _retired - 1; }                           // the push (0-based) whose results the members hold; -1: none yet
   std::vector<Vector3f> pose; std::vector<std::array<float, 9>> information; std::vector<int32_t> status, iterations;
  private:
-  void begin_next() {
+  void begin_next() {      // (a plain descriptor on the stack: detail::BatchDescriptor would allocate its two handle arrays on every step)
     const lsm2d_cloudset* fx[1] = {_sets[_begun % 3]}; const lsm2d_cloudset* mv[1] = {_map.get()};
     lsm2d_batch b{}; b.n_alignments = _n; b.n_slices = 1; b.slices = &_slice; b.fixed = fx; b.moving = mv; b.init_pose = _start[0].data();
     check(lsm2d_align_batch_begin(_ctx.get(), &_aligner, &b, 0, &_pending[_begun & 1]), "lsm2d_align_batch_begin", _ctx.get());
@@ -716,7 +718,7 @@ class LaserMessageBatchStream {
     return true;
   }
   Context& _ctx; lsm2d_preprocessor _pre; const CloudSet& _map; lsm2d_slice_params _slice; lsm2d_aligner_params _aligner; int _n;
-  lsm2d_cloudset* _sets[3] = {nullptr, nullptr, nullptr}; lsm2d_pending* _pending[2] = {nullptr, nullptr};
+  detail::CloudSetHandle _sets[3]; lsm2d_pending* _pending[2] = {nullptr, nullptr};
   std::vector<Vector3f> _start;                                             // the start poses of the batch pushed last (begun by the next push)
   long _pushed = 0, _begun = 0, _retired = 0;
 };
@@ -732,8 +734,7 @@ class LoopClosureSweep {
     if (rc < 0) throw std::runtime_error(std::string("LoopClosureSweep| ") + lsm2d_status_string(rc) + ": " + lsm2d_sweep_last_error(nullptr));
   }
   ~LoopClosureSweep() { lsm2d_sweep_destroy(_sw); }
-  LoopClosureSweep(const LoopClosureSweep&) = delete;
-  LoopClosureSweep& operator=(const LoopClosureSweep&) = delete;
+  LoopClosureSweep(const LoopClosureSweep&) = delete; LoopClosureSweep& operator=(const LoopClosureSweep&) = delete;
   int numDevices() const { return lsm2d_sweep_num_devices(_sw); }
   // relocalize_aligner's parameters (MULTI.json:602-630) and its one laser slice (MULTI.json:572-600,771-784: projective finder,
   // point_distance 1.414, normal_cos 0.8, Cauchy 0.05, min_num_correspondences 10)
@@ -750,7 +751,7 @@ class LoopClosureSweep {
   // acceptance thresholds (MULTI.json:964-986)
   int param_relocalize_min_inliers = 500; float param_relocalize_max_chi_inliers = 0.1f, param_relocalize_min_inliers_ratio = 0.8f;
 
-  void setMap(const PointNormal2fVectorCloud& map) { checkSweep(lsm2d_sweep_set_map(_sw, map.empty() ? nullptr : &map[0].x, (int64_t) map.size()), "set_map"); }
+  void setMap(const PointNormal2fVectorCloud& map) { checkSweep(lsm2d_sweep_set_map(_sw, ptrOrNull(map), (int64_t) map.size()), "set_map"); }
   void setScans(const std::vector<PointNormal2fVectorCloud>& scans) {
     std::vector<float> packed; std::vector<int32_t> offs(1, 0);
     for (const auto& c : scans) { for (const auto& p : c) { packed.push_back(p.x); packed.push_back(p.y); packed.push_back(p.nx); packed.push_back(p.ny); } offs.push_back((int32_t) (packed.size() / 4)); }
@@ -759,38 +760,28 @@ class LoopClosureSweep {
   void setScansPacked(const float* xynn, const int32_t* offsets, int n_scans) { checkSweep(lsm2d_sweep_set_scans(_sw, xynn, offsets, n_scans), "set_scans"); }
   // candidates: (scan index, initial guess of moving-in-fixed); results in candidate order
   void compute(const std::vector<int32_t>& scan_index, const std::vector<Vector3f>& init_pose) {
-    const int n = (int) init_pose.size();
-    if ((int) scan_index.size() != n) throw std::runtime_error("LoopClosureSweep::compute| one scan index per candidate");
-    const lsm2d_slice_params sp = param_slice;
-    lsm2d_aligner_params ap{param_max_iterations, param_min_num_inliers, 0.f, 0.f, 0, 0};
-    pose.assign((size_t) n, Vector3f{{0.f, 0.f, 0.f}}); information.assign((size_t) n, std::array<float, 9>{});
-    status.assign((size_t) n, 0); iterations.assign((size_t) n, 0); last_stats.assign((size_t) n, lsm2d_iteration_stats{});
+    const lsm2d_aligner_params ap = alignerParams("LoopClosureSweep::compute| one scan index per candidate", scan_index, init_pose);
+    const size_t n = init_pose.size();
+    pose.assign(n, Vector3f{{0.f, 0.f, 0.f}}); information.assign(n, std::array<float, 9>{});
+    status.assign(n, 0); iterations.assign(n, 0); last_stats.assign(n, lsm2d_iteration_stats{});
     static_assert(sizeof(Vector3f) == 3 * sizeof(float), "poses are packed");
-    checkSweep(lsm2d_sweep_align(_sw, &ap, &sp, n, scan_index.data(), n ? init_pose[0].data() : nullptr, n ? pose[0].data() : nullptr,
+    checkSweep(lsm2d_sweep_align(_sw, &ap, &param_slice, (int) n, scan_index.data(), ptrOrNull(init_pose), n ? pose[0].data() : nullptr,
                                  n ? information[0].data() : nullptr, status.data(), iterations.data(), last_stats.data()), "align");
   }
-  bool accept(size_t i) const {
-    const auto& st = last_stats[i];
-    const float n_in = (float) st.n_inliers, n_c = (float) (st.n_correspondences > 0 ? st.n_correspondences : 1);
-    return status[i] == LSM2D_SUCCESS && st.n_inliers >= param_relocalize_min_inliers &&
-           st.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= param_relocalize_max_chi_inliers && n_in / n_c >= param_relocalize_min_inliers_ratio;
-  }
+  bool accept(size_t i) const { return status[i] == LSM2D_SUCCESS && selectAccept(last_stats[i], selectParams()); }
   // compute + accept + "take the best k" on the devices (lsm2d_sweep_align_select): every shard ranks its candidates where they lie, k rows per shard come
   // down and are merged by the same key.  selected[j] is the j-th best accepted candidate (param_relocalize_* are the thresholds) and row j of pose /
   // information / iterations / last_stats its results -- the bits compute() gives for that candidate; status is left empty (every selected candidate
   // succeeded).  n_accepted / n_success count among all candidates.
   void computeSelect(const std::vector<int32_t>& scan_index, const std::vector<Vector3f>& init_pose, int32_t k) {
-    const int n = (int) init_pose.size();
-    if ((int) scan_index.size() != n) throw std::runtime_error("LoopClosureSweep::computeSelect| one scan index per candidate");
-    const lsm2d_slice_params sp = param_slice;
-    lsm2d_aligner_params ap{param_max_iterations, param_min_num_inliers, 0.f, 0.f, 0, 0};
-    const lsm2d_select_params sel{param_relocalize_min_inliers, param_relocalize_max_chi_inliers, param_relocalize_min_inliers_ratio};
+    const lsm2d_aligner_params ap = alignerParams("LoopClosureSweep::computeSelect| one scan index per candidate", scan_index, init_pose);
+    const lsm2d_select_params sel = selectParams();
     const size_t cap = (size_t) std::max<int32_t>(k, 1);
     selected.assign(cap, 0); pose.assign(cap, Vector3f{{0.f, 0.f, 0.f}}); information.assign(cap, std::array<float, 9>{});
     status.clear(); iterations.assign(cap, 0); last_stats.assign(cap, lsm2d_iteration_stats{});
     int32_t n_sel = 0; n_accepted = 0; n_success = 0;
-    checkSweep(lsm2d_sweep_align_select(_sw, &ap, &sp, n, scan_index.data(), n ? init_pose[0].data() : nullptr, &sel, k, selected.data(), pose[0].data(),
-                                        information[0].data(), iterations.data(), last_stats.data(), &n_sel, &n_accepted, &n_success), "align_select");
+    checkSweep(lsm2d_sweep_align_select(_sw, &ap, &param_slice, (int) init_pose.size(), scan_index.data(), ptrOrNull(init_pose), &sel, k, selected.data(),
+                                        pose[0].data(), information[0].data(), iterations.data(), last_stats.data(), &n_sel, &n_accepted, &n_success), "align_select");
     selected.resize((size_t) n_sel); pose.resize((size_t) n_sel); information.resize((size_t) n_sel); iterations.resize((size_t) n_sel);
     last_stats.resize((size_t) n_sel);
   }
@@ -798,6 +789,12 @@ class LoopClosureSweep {
   std::vector<int32_t> status, iterations; std::vector<lsm2d_iteration_stats> last_stats;
   std::vector<int32_t> selected; int32_t n_accepted = 0, n_success = 0;      // computeSelect
  private:
+  // what both candidate calls start from: one scan index per candidate, and the aligner the parameters describe
+  lsm2d_aligner_params alignerParams(const char* refusal, const std::vector<int32_t>& scan_index, const std::vector<Vector3f>& init_pose) const {
+    if (scan_index.size() != init_pose.size()) throw std::runtime_error(refusal);
+    return {param_max_iterations, param_min_num_inliers, 0.f, 0.f, 0, 0};
+  }
+  lsm2d_select_params selectParams() const { return {param_relocalize_min_inliers, param_relocalize_max_chi_inliers, param_relocalize_min_inliers_ratio}; }
   void checkSweep(int rc, const char* where) const {
     if (rc < 0) throw std::runtime_error(std::string("LoopClosureSweep::") + where + "| " + lsm2d_status_string(rc) + ": " + lsm2d_sweep_last_error(_sw));
   }
@@ -822,32 +819,30 @@ class TrackerBatch {
   TrackerBatch(Context& ctx, int32_t n_trackers, const Params& p) : _ctx(ctx), _n(n_trackers), _p(p), _est((size_t) n_trackers * 3, 0.0),
                                                                        _prior((size_t) n_trackers), _x((size_t) n_trackers * 3), _H((size_t) n_trackers * 9),
                                                                        _status((size_t) n_trackers) {
-    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.map_capacity, &_maps), "lsm2d_cloudset_create_reserved_many", ctx.get());
-    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.projector.canvas_cols, &_clipped), "lsm2d_cloudset_create_reserved_many", ctx.get());
+    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.map_capacity, _maps.out()), "lsm2d_cloudset_create_reserved_many", ctx.get());
+    check(lsm2d_cloudset_create_reserved_many(ctx.get(), _n, p.projector.canvas_cols, _clipped.out()), "lsm2d_cloudset_create_reserved_many", ctx.get());
     for (auto& q : _prior) { for (float& z : q.z) z = 0.0f; for (int k = 0; k < 9; ++k) q.omega[k] = p.prior_omega[(size_t) k]; }
   }
-  ~TrackerBatch() { for (lsm2d_cloudset* s : {_maps, _clipped, _scans[0], _scans[1]}) lsm2d_cloudset_destroy(s); }
   TrackerBatch(const TrackerBatch&) = delete; TrackerBatch& operator=(const TrackerBatch&) = delete;
   int32_t size() const { return _n; }
   // trackers idx[0 .. m) start a new local map at robot pose poses[m][3] from their scans front / rear [m][n_beams]
   void reset(int32_t m, const int32_t* idx, const float* front, const float* rear, const double* poses) {
-    lsm2d_cloudset* meas[2] = {nullptr, nullptr};
+    detail::CloudSetHandle meas[2];       // (they go when reset() returns or throws: by then the merge has read them)
     const float* r[2] = {front, rear};
-    for (int s = 0; s < 2; ++s) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], m, &meas[s]), "lsm2d_preprocess_scans", _ctx.get());
+    for (int s = 0; s < 2; ++s) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], m, meas[s].out()), "lsm2d_preprocess_scans", _ctx.get());
     std::vector<float> mis((size_t) m * 6);
     for (int32_t i = 0; i < m; ++i) { std::copy(poses + 3 * i, poses + 3 * i + 3, &_est[(size_t) idx[i] * 3]); sensorPoses(idx[i], &mis[(size_t) i * 6]); }
     int rc = lsm2d_cloudset_clear_clouds(_maps, m, idx);
     const lsm2d_cloudset* ms[2] = {meas[0], meas[1]};
     if (rc == LSM2D_SUCCESS) rc = lsm2d_merge_scene_batch(_ctx.get(), &_p.projector, _maps, m, idx, 2, ms, nullptr, mis.data(), _p.merge_threshold, nullptr, nullptr);
-    if (rc == LSM2D_SUCCESS) rc = lsm2d_synchronize(_ctx.get());      // (the scan sets go: the merge has read them)
-    lsm2d_cloudset_destroy(meas[0]); lsm2d_cloudset_destroy(meas[1]);
+    if (rc == LSM2D_SUCCESS) rc = lsm2d_synchronize(_ctx.get());
     check(rc, "TrackerBatch::reset", _ctx.get());
   }
   // one step of every tracker: front / rear [N][n_beams] raw ranges (kept untouched until step() returns), odometry [N][3]
   void step(const float* front, const float* rear, const double* odometry) {
     const float* r[2] = {front, rear};
     for (int s = 0; s < 2; ++s) {
-      if (!_scans[s]) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], _n, &_scans[s]), "lsm2d_preprocess_scans", _ctx.get());
+      if (!_scans[s]) check(lsm2d_preprocess_scans(_ctx.get(), &_p.preprocessor, r[s], _n, _scans[s].out()), "lsm2d_preprocess_scans", _ctx.get());
       else check(lsm2d_preprocess_scans_refill(_ctx.get(), &_p.preprocessor, r[s], _n, _scans[s]), "lsm2d_preprocess_scans_refill", _ctx.get());
     }
     std::vector<float> guess((size_t) _n * 3), x0((size_t) _n * 3, 0.0f), mis((size_t) _n * 6);
@@ -857,16 +852,15 @@ class TrackerBatch {
             "lsm2d_clip_scene_voxelized_batch", _ctx.get());
     else
       check(lsm2d_clip_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, guess.data(), _p.slices[0].sensor_in_robot, _clipped, nullptr), "lsm2d_clip_scene_batch", _ctx.get());
-    const lsm2d_cloudset* fixed[2] = {_scans[0], _scans[1]}; const lsm2d_cloudset* moving[2] = {_clipped, _clipped};
-    lsm2d_batch b{};
-    b.n_alignments = _n; b.n_slices = 2; b.slices = _p.slices.data(); b.fixed = fixed; b.moving = moving; b.init_pose = x0.data(); b.prior = _prior.data();
+    const lsm2d_cloudset* fx[2] = {_scans[0], _scans[1]}; const lsm2d_cloudset* mv[2] = {_clipped, _clipped};
+    lsm2d_batch b{};      // (on the stack, as in the stream: detail::BatchDescriptor would add two allocations to the three above)
+    b.n_alignments = _n; b.n_slices = 2; b.slices = _p.slices.data(); b.fixed = fx; b.moving = mv; b.init_pose = x0.data(); b.prior = _prior.data();
     check(lsm2d_align_batch(_ctx.get(), &_p.aligner, &b, _x.data(), _H.data(), _status.data(), nullptr, nullptr), "lsm2d_align_batch", _ctx.get());
     for (int32_t i = 0; i < _n; ++i) {          // estimate = guess * x^-1, then both scans at the corrected pose
       const double xd[3] = {_x[(size_t) i * 3], _x[(size_t) i * 3 + 1], _x[(size_t) i * 3 + 2]}, gd[3] = {guess[(size_t) i * 3], guess[(size_t) i * 3 + 1], guess[(size_t) i * 3 + 2]};
       double xi[3]; inverse(xd, xi); compose(gd, xi, &_est[(size_t) i * 3]); sensorPoses(i, &mis[(size_t) i * 6]);
     }
-    const lsm2d_cloudset* ms[2] = {_scans[0], _scans[1]};
-    check(lsm2d_merge_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, 2, ms, nullptr, mis.data(), _p.merge_threshold, nullptr, nullptr), "lsm2d_merge_scene_batch", _ctx.get());
+    check(lsm2d_merge_scene_batch(_ctx.get(), &_p.projector, _maps, _n, nullptr, 2, fx, nullptr, mis.data(), _p.merge_threshold, nullptr, nullptr), "lsm2d_merge_scene_batch", _ctx.get());
   }
   const std::vector<float>& movingInFixed() const { return _x; }         // [N][3]: the aligner's result of the last step
   const std::vector<float>& informationMatrix() const { return _H; }     // [N][9]
@@ -895,7 +889,7 @@ class TrackerBatch {
   Context& _ctx; int32_t _n; Params _p;
   std::vector<double> _est; std::vector<lsm2d_prior> _prior;
   std::vector<float> _x, _H; std::vector<int32_t> _status;
-  lsm2d_cloudset *_maps = nullptr, *_clipped = nullptr, *_scans[2] = {nullptr, nullptr};
+  detail::CloudSetHandle _maps, _clipped, _scans[2];
 };
 
 }  // namespace lsm2d_host

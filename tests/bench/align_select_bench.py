@@ -34,11 +34,9 @@ ITERATIONS = 30
 
 
 def _build(tmp):
-    exe = os.path.join(tmp, "align_select_bench")
-    lib_dir = os.path.join(HERE_ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(HERE_ROOT, "include"), os.path.join(HERE_ROOT, "tests", "cpp", "align_select_bench.cpp"),
-                    "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
-    return exe
+    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
+    import cpp_build
+    return cpp_build.build("align_select_bench.cpp", tmp)
 
 
 def run_part(api, exe, tmp, part, scans, offs, m, poses, index, sel, args):

@@ -5,7 +5,8 @@ C++ host of the reference's kind pays per batch, beside bench.py's figure for th
     python tests/bench/batch_step_bench.py [--steps 300] [--scans 1000] [--map-points 100000]"""
 import argparse, json, os, subprocess, sys, tempfile
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cpp_build
 from srrg2_laser_slam_2d_amd import synth
 
 
@@ -17,9 +18,7 @@ def main():
     a = ap.parse_args()
     wl = synth.make_workload(a.scans, a.map_points, seed=0, n_beams=a.beams)
     with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "batch_step_bench"); lib = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "batch_step_bench.cpp"),
-                        "-L" + lib, "-llsm2d_hip", "-Wl,-rpath," + lib, "-o", exe], check=True)
+        exe = cpp_build.build("batch_step_bench.cpp", d)
         np.ascontiguousarray(wl.map_points, np.float32).tofile(os.path.join(d, "map.bin"))
         np.ascontiguousarray(wl.scan_points, np.float32).tofile(os.path.join(d, "scans.bin"))
         np.ascontiguousarray(wl.scan_offsets, np.int32).tofile(os.path.join(d, "offs.bin"))

@@ -44,11 +44,9 @@ def _workload(synth, workdir, n, n_map):
 
 
 def _build(tmp):
-    exe = os.path.join(tmp, "score_select_bench")
-    lib_dir = os.path.join(HERE_ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(HERE_ROOT, "include"), os.path.join(HERE_ROOT, "tests", "cpp", "score_select_bench.cpp"),
-                    "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
-    return exe
+    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
+    import cpp_build
+    return cpp_build.build("score_select_bench.cpp", tmp)
 
 
 def run_part(api, ctx, exe, tmp, part, scans, offs, m, poses, order, args):

@@ -6,15 +6,14 @@ bit-identical to the synchronous calls, beside bench.py --stream's figure for th
     python tests/bench/stream_step_bench.py [--steps 300] [--scans 1000] [--map-points 100000]"""
 import argparse, json, os, subprocess, sys, tempfile
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cpp_build
 from srrg2_laser_slam_2d_amd import synth
 
 
-def build(exe):
-    lib = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "stream_step_bench.cpp"), "-L" + lib, "-llsm2d_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-o", exe], check=True)
+def build(out_dir):
+    return cpp_build.build("stream_step_bench.cpp", out_dir, flags=("-O2", "-D__HIP_PLATFORM_AMD__"), include_dirs=("/opt/rocm/include",),
+                           link_flags=("-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"))
 
 
 def run(steps=300, warmup=300, scans=1000, map_points=100000, iterations=20, beams=1081, batches=4, seed=0, ahead=1, workdir=None):
@@ -30,8 +29,7 @@ def run(steps=300, warmup=300, scans=1000, map_points=100000, iterations=20, bea
     if workdir:
         os.makedirs(workdir, exist_ok=True)
     with (contextlib.nullcontext(workdir) if workdir else tempfile.TemporaryDirectory()) as d:
-        exe = os.path.join(d, "stream_step_bench")
-        build(exe)
+        exe = build(d)
         np.ascontiguousarray(m, np.float32).tofile(os.path.join(d, "map.bin"))
         np.ascontiguousarray(np.stack(rg), np.float32).tofile(os.path.join(d, "ranges.bin"))
         np.ascontiguousarray(np.stack(x0), np.float32).tofile(os.path.join(d, "x0.bin"))

@@ -15,6 +15,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cpp_build      # noqa: E402
 
 
 def write_inputs(d, n_scenarios, steps):
@@ -29,10 +30,7 @@ def write_inputs(d, n_scenarios, steps):
 
 
 def build_driver(d):
-    exe = os.path.join(d, "track_batch_driver"); lib = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "track_batch_driver.cpp"),
-                    "-L" + lib, "-llsm2d_hip", "-Wl,-rpath," + lib, "-o", exe], check=True)
-    return exe
+    return cpp_build.build("track_batch_driver.cpp", d)
 
 
 def run(exe, d, tc, n_scenarios, steps, n, episodes, timeout=900):

@@ -5,7 +5,8 @@ asynchronous calls) plus the CPU oracle's time for the same step.
     python tests/bench/track_step_bench.py [--steps 2000]"""
 import argparse, json, math, os, subprocess, sys, tempfile, time
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cpp_build
 from srrg2_laser_slam_2d_amd import synth
 
 
@@ -36,9 +37,7 @@ def main():
     if args.workdir:
         os.makedirs(args.workdir, exist_ok=True)
     with (contextlib.nullcontext(args.workdir) if args.workdir else tempfile.TemporaryDirectory()) as d:
-        exe = os.path.join(d, "track_step_bench"); lib = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "track_step_bench.cpp"),
-                        "-L" + lib, "-llsm2d_hip_experiments" if os.environ.get("LSM2D_EXPERIMENTS", "0") not in ("", "0") else "-llsm2d_hip", "-Wl,-rpath," + lib, "-o", exe], check=True)
+        exe = cpp_build.build("track_step_bench.cpp", d, link="lsm2d_hip_experiments" if os.environ.get("LSM2D_EXPERIMENTS", "0") not in ("", "0") else True)
         host_map.tofile(os.path.join(d, "map.bin")); scans[0].tofile(os.path.join(d, "s0.bin")); scans[1].tofile(os.path.join(d, "s1.bin"))
         out = {"local_map_points": int(len(host_map)), "scan_points": [int(len(s)) for s in scans]}
         ranges[0].tofile(os.path.join(d, "r0.bin")); ranges[1].tofile(os.path.join(d, "r1.bin"))

@@ -105,12 +105,12 @@ def test_srrg_adapter_sources_compile_against_the_stand_in_headers(tmp_path):
     """adapters/srrg/* are written against the srrg2 stack, which is absent from this image.  tests/cpp/adapter_shim holds stand-in
     headers (test infrastructure) declaring exactly the upstream names those sources use, so every adapter translation unit -- and the
     driver the GPU test runs -- is at least COMPILED here (g++, no GPU needed)."""
-    import subprocess
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "adapters", "srrg"), "-I" + os.path.join(ROOT, "tests", "cpp", "adapter_shim")]
+    import cpp_build
+    inc = [os.path.join(ROOT, "adapters", "srrg"), os.path.join(ROOT, "tests", "cpp", "adapter_shim")]
     units = [os.path.join(ROOT, "adapters", "srrg", "correspondence_finder_hip_2d.cpp"), os.path.join(ROOT, "adapters", "srrg", "multi_aligner_hip_2d.cpp"),
              os.path.join(ROOT, "tests", "cpp", "adapter_driver.cpp")]      # the driver includes mapping_hip_2d.h and raw_data_preprocessor_hip_2d.h (header-only)
     for u in units:
-        r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", *inc, u], capture_output=True, text=True)
+        r = cpp_build.syntax_only(u, include_dirs=inc)
         assert r.returncode == 0, r.stderr[-3000:]
     # every entry point the adapters call is declared in include/lsm2d.h and exported by the library
     import re

@@ -10,12 +10,12 @@ every one of them.  The condition is therefore checked (and the GPU tests run) w
 taken from the rows of all candidates: under those the status term alone rejects dozens of candidates."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_select_cases as cases
+import cpp_build
 from conftest import ROOT
 
 NAMES = {"lsm2d_align_select": 13, "lsm2d_sweep_align_select": 16}
@@ -52,9 +52,7 @@ def test_mirrors_have_align_select():
 
 @pytest.mark.parametrize("source", ["align_select_driver.cpp", "align_select_bench.cpp"])
 def test_cpp_sources_compile(source):
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"), os.path.join(ROOT, "tests", "cpp", source)],
-                       capture_output=True, text=True)
+    r = cpp_build.syntax_only(source)
     assert r.returncode == 0, r.stderr[-3000:]
 
 

@@ -3,14 +3,13 @@ the selection, the counts and every row equal api.align_select on the same input
 shards on one device, merged on the host) in the default order, the only one a sweep's contexts run in."""
 import json
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import align_select_cases as cases
-from conftest import ROOT
+import cpp_build
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +18,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("align_select_cpp")
-    exe = str(d / "align_select_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "align_select_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("align_select_driver.cpp", d, flags=("-O2", "-pthread"))
     c = cases.make_cases()
     c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
     return exe, d, c

@@ -8,6 +8,8 @@ import math
 import numpy as np
 import pytest
 
+import cpp_build
+
 import fuzz_cases
 from conftest import golden_path, has_experiments, need_experiments, xset
 from gpu_helpers import (_same_correspondence_sets, _assert_bitwise_equal_to_device_order_oracle, _pose_diff, _Envelope, _projector, _aligner, _nn_aligner, _ranges_in_pose_out_step, _kd_finder, _kd_aligner, _neg_eps, _oracle_slice, POSE_TOL_M, POSE_TOL_RAD)
@@ -24,11 +26,9 @@ def test_srrg_adapters_compile_and_run(ctx, po, small_workload, tmp_path):
     import os
     import subprocess
     from conftest import ROOT
-    exe = str(tmp_path / "adapter_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib"); ad = os.path.join(ROOT, "adapters", "srrg")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"), "-I" + ad, "-I" + os.path.join(ROOT, "tests", "cpp", "adapter_shim"),
-                    os.path.join(ROOT, "tests", "cpp", "adapter_driver.cpp"), os.path.join(ad, "correspondence_finder_hip_2d.cpp"),
-                    os.path.join(ad, "multi_aligner_hip_2d.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    ad = os.path.join(ROOT, "adapters", "srrg")
+    exe = cpp_build.build(["adapter_driver.cpp", os.path.join(ad, "correspondence_finder_hip_2d.cpp"), os.path.join(ad, "multi_aligner_hip_2d.cpp")], tmp_path,
+                          flags=("-O1", "-Wall"), include_dirs=(ad, os.path.join(cpp_build.CPP, "adapter_shim")))
     wl = small_workload
     f = wl.scan_points[wl.scan_offsets[0]:wl.scan_offsets[1]]
     f.tofile(tmp_path / "fixed.bin"); wl.map_points.tofile(tmp_path / "moving.bin")
@@ -116,13 +116,8 @@ def test_cpp_loop_closure_sweep_over_several_contexts(ctx, po, tmp_path):
     one host thread each, the submap replicated device to device, candidates block-sharded -- must give, bit for bit, the poses,
     information matrices, statuses and last-iteration statistics of ONE lsm2d_align_batch over all candidates; acceptance decisions
     as MULTI.json:979-985."""
-    import os
     import subprocess
-    from conftest import ROOT
-    exe = str(tmp_path / "sweep_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "sweep_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-pthread", "-o", exe], check=True)
+    exe = cpp_build.build("sweep_driver.cpp", tmp_path, flags=("-O1", "-Wall"), link_flags=("-pthread",))
     n_cand, n_unique, iters, tau = 1500, 64, 15, 0.05
     wl = synth.make_workload(n_unique, 50000, seed=21)
     scan_index = (np.arange(n_cand) * 7 % n_unique).astype(np.int32)
@@ -225,14 +220,8 @@ def test_cpp_stream_step_through_the_bare_c_abi_and_the_mirror_class(ctx):
 def test_cpp_host_mirror_driver(ctx, po, small_workload, tmp_path):
     """The header-only C++ mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and driven like
     apps/visual_test_correspondence_finder_projective_2d.cpp / apps/visual_test_aligner_2d.cpp."""
-    import os
     import subprocess
-    from conftest import ROOT
-    exe = str(tmp_path / "host_mirror_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "host_mirror_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe],
-                   check=True)
+    exe = cpp_build.build("host_mirror_driver.cpp", tmp_path)
     wl = small_workload
     f = wl.scan_points[wl.scan_offsets[0]:wl.scan_offsets[1]]
     f.tofile(tmp_path / "fixed.bin"); wl.map_points.tofile(tmp_path / "moving.bin")

@@ -11,6 +11,7 @@ import pytest
 
 import tracker_chain as tc
 import tracker_fleet_vox as tfv
+import cpp_build
 from conftest import ROOT
 from srrg2_laser_slam_2d_amd import api
 
@@ -22,10 +23,7 @@ N, STEPS, RES = 3, 4, 0.1
 def test_cpp_tracker_batch_voxelised_clip(ctx, tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tests", "bench"))
     import track_batch_bench as tbb
-    exe = str(tmp_path / "clip_vox_batch_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "clip_vox_batch_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("clip_vox_batch_driver.cpp", tmp_path)
     tbb.write_inputs(str(tmp_path), N, STEPS)
     seeds = tfv.fleet_seeds(N, STEPS)
     out = subprocess.run([exe, str(tmp_path), str(N), str(STEPS), str(tc.N_BEAMS), repr(tc.A0), repr(tc.A1), str(N), repr(RES)],

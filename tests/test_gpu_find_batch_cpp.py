@@ -2,23 +2,19 @@
 mirror's own single compute() calls item by item (checked inside the driver) and the CPU oracle (checked here), bit for bit."""
 import json
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import cpp_build
 from srrg2_laser_slam_2d_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_compute_batch(po, tmp_path):
-    exe = str(tmp_path / "find_batch_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "find_batch_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("find_batch_driver.cpp", tmp_path)
     world = synth.make_world(4)
     m = synth.make_map(world, 6000, seed=2)
     robots = synth.sample_poses(world, 6, seed=8)

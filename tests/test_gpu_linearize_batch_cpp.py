@@ -2,13 +2,12 @@
 mirror's own single linearize() calls item by item, byte for byte (checked inside the driver), and the CPU oracle in the order of summation asked for
 (checked here), bit for bit."""
 import json
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import cpp_build
 from srrg2_laser_slam_2d_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +18,7 @@ TAU = 0.01
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("linearize_batch_cpp")
-    exe = str(d / "linearize_batch_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "linearize_batch_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("linearize_batch_driver.cpp", d)
     wl = synth.make_workload(3, 3000, seed=5, map_noise=0.004, scan_noise=0.004)
     # five items over the three scans: every scan once and two of them again under another pose
     which = [0, 1, 2, 1, 0]

@@ -4,14 +4,13 @@ api.score_aligner / api.score_aligner_select / api.relocalize on the same inputs
 row equals scoreAligner's, and relocalize equals the entry points called by hand."""
 import json
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import score_aligner_cases as cases
-from conftest import ROOT
+import cpp_build
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +19,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("score_aligner_cpp")
-    exe = str(d / "score_aligner_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "score_aligner_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("score_aligner_driver.cpp", d)
     c = cases.make_inputs()
     rng = np.random.default_rng(4)
     c.scan = (np.arange(24) % c.n).astype(np.int32)      # 24 hypotheses over the four scans, some of them far from everything

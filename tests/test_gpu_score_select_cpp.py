@@ -3,14 +3,13 @@ and the relocalisation's results equal api.score_select / api.relocalize on the 
 scoreBatch row (checked inside the driver)."""
 import json
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import score_select_cases as cases
-from conftest import ROOT
+import cpp_build
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +18,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("score_select_cpp")
-    exe = str(d / "score_select_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"),
-                    os.path.join(ROOT, "tests", "cpp", "score_select_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("score_select_driver.cpp", d)
     c = cases.make_cases()
     c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
     return exe, d, c

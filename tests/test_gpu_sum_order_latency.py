@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_build
+
 from srrg2_laser_slam_2d_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -291,10 +293,8 @@ def test_adapter_hip_context_follows_its_sum_order_param(tmp_path):
     """adapters/srrg HipContext: a change of its sum_order PARAM after the first handle() reaches the context (lsm2d_get_option), both ways; a failed
     apply throws and leaves no context behind (tests/cpp/adapter_sum_order_driver.cpp)"""
     from conftest import ROOT
-    exe = str(tmp_path / "adapter_sum_order_driver")
-    lib_dir = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "lib"); ad = os.path.join(ROOT, "adapters", "srrg")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"), "-I" + ad, "-I" + os.path.join(ROOT, "tests", "cpp", "adapter_shim"),
-                    os.path.join(ROOT, "tests", "cpp", "adapter_sum_order_driver.cpp"), "-L" + lib_dir, "-llsm2d_hip", "-ldl", "-Wl,-rpath," + lib_dir, "-o", exe], check=True)
+    exe = cpp_build.build("adapter_sum_order_driver.cpp", tmp_path, flags=("-O1", "-Wall"), link_flags=("-ldl",),
+                          include_dirs=(os.path.join(ROOT, "adapters", "srrg"), os.path.join(cpp_build.CPP, "adapter_shim")))
     out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout
     r = json.loads(out.strip().splitlines()[-1])
     assert r == {"first": 0, "after_on": 1, "after_off": 0, "same_context": 1, "threw": 1, "after_failure": 1}, r

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import score_select_cases as cases
+import cpp_build
 from conftest import ROOT
 
 NAME = "lsm2d_score_select"
@@ -72,9 +73,7 @@ def test_mirrors_have_score_select():
 
 
 def test_cpp_mirror_compiles():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host"), os.path.join(ROOT, "tests", "cpp", "score_select_driver.cpp")],
-                       capture_output=True, text=True)
+    r = cpp_build.syntax_only("score_select_driver.cpp")
     assert r.returncode == 0, r.stderr[-3000:]
 
 
