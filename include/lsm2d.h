@@ -63,7 +63,10 @@ extern "C" {
                                     voxelize_resolution > 0 branch inside the same launch, the single voxelised call's bits per tracker);
                              (0.7.7, number unchanged: an addition only) + lsm2d_align_select, lsm2d_sweep_align_select (lsm2d_align_batch's alignment, then
                                     the candidate loops' acceptance test -- status term included -- and the best k aligned candidates ranked on the device:
-                                    only k rows come down, whatever the iteration count is) */
+                                    only k rows come down, whatever the iteration count is);
+                             (0.7.8, number unchanged: an addition only) + lsm2d_score_select_grouped, lsm2d_score_aligner_select_grouped,
+                                    lsm2d_align_select_grouped, LSM2D_SELECT_MAX_GROUP_ROWS (the three select calls per GROUP of the batch -- a fleet's
+                                    candidates, the best k per robot: one call, one wait, n_groups x k rows come down) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -638,6 +641,47 @@ int lsm2d_score_aligner_select(lsm2d_context* ctx, const lsm2d_batch* batch, con
                                int32_t* out_index /* [k] */, float* out_H /* [k][9] or NULL */, float* out_b /* [k][3] or NULL */,
                                lsm2d_iteration_stats* out_stats /* [k] or NULL */, int32_t* out_active /* [k] or NULL */,
                                int32_t* out_n_selected, int32_t* out_n_accepted);
+
+/* ---- the three select calls PER GROUP of the batch (0.7.8): a fleet server's N robots each have their own loop-closure candidates or relocalisation
+ * hypotheses, laid one robot behind the other in ONE batch, and each robot wants ITS best k -- not the best k of the pool, which a robot with many good
+ * candidates would fill.  Each call is its ungrouped sibling plus groups: the same arguments, scoring / alignment, thresholds and k (shared by all groups).
+ * Groups: group_offsets is a host array of n_groups + 1 int32 values, non-decreasing, group_offsets[0] == 0, group_offsets[n_groups] == n_items
+ * (n_alignments for the batch forms); group g is items [group_offsets[g], group_offsets[g + 1]).  Empty groups are legal: 0 accepted, 0 selected.
+ * Outputs: every per-row output has n_groups x k rows; group g's j-th best lands in slot g * k + j, j < out_n_selected[g]; other slots are not written.
+ * out_index holds BATCH item indices, not positions within the group.  out_n_selected, out_n_accepted (and lsm2d_align_select_grouped's out_n_success, which
+ * may be NULL) are [n_groups].
+ * Meaning: group g's block is bit for bit what the ungrouped call returns for the sub-batch of g's items, with the indices shifted by group_offsets[g]: the
+ * same fp32 acceptance test, the same total order (n_inliers descending, chi_inliers ascending on its bits, index ascending; PARITY.md section 3, 18d).  The
+ * result is unique and does not depend on the order in which workgroups run.
+ * Refused before anything is launched or written: everything the ungrouped sibling refuses; a NULL group_offsets, n_groups < 1, offsets that decrease, do
+ * not start at 0 or do not end at the batch's size; n_groups x k above LSM2D_SELECT_MAX_GROUP_ROWS (all LSM2D_BAD_ARGUMENT).
+ * LSM2D_SELECT_MAX_GROUP_ROWS = 2^18 rows: what comes down is n_groups x (16 + 4 k + 4 k row_words) bytes -- row_words 17 (score), 20 (score_aligner), 24
+ * (align) -- so the cap bounds the one copy, and the pinned staging behind it, at about 25 MB of 96-byte aligned-candidate rows.
+ * Cost: ONE upload of the sibling's arguments with the group table behind them in the same copy, ONE copy down, ONE wait, whatever n_groups and the groups'
+ * sizes are.  While every group holds at most 2048 items the selection is ONE launch of a workgroup per group; a larger group takes segmented passes (a keys
+ * launch, a tile pass per halving, a gather), small groups of the same call riding along.  "kernel_timing" / lsm2d_last_kernel_ms cover what they cover for
+ * the sibling.  The never-reported check of lsm2d_align_select stays one global count and one LSM2D_DEVICE_ERROR.  The calls are synchronous. */
+#define LSM2D_SELECT_MAX_GROUP_ROWS (1 << 18)
+int lsm2d_score_select_grouped(lsm2d_context* ctx, const lsm2d_slice_params* slice,
+                               const lsm2d_cloudset* fixed, const int32_t* fixed_index /* [n_items] or NULL */,
+                               const lsm2d_cloudset* moving, const int32_t* moving_index /* [n_items] or NULL */,
+                               int32_t n_items, const float* poses /* [n_items][3] */,
+                               const lsm2d_select_params* select, int32_t k,
+                               int32_t n_groups, const int32_t* group_offsets /* [n_groups + 1] */,
+                               int32_t* out_index /* [n_groups * k] */, float* out_H /* [n_groups * k][9] or NULL */, float* out_b /* [n_groups * k][3] or NULL */,
+                               lsm2d_iteration_stats* out_stats /* [n_groups * k] or NULL */,
+                               int32_t* out_n_selected /* [n_groups] */, int32_t* out_n_accepted /* [n_groups] */);
+int lsm2d_score_aligner_select_grouped(lsm2d_context* ctx, const lsm2d_batch* batch, const lsm2d_select_params* select, int32_t k,
+                                       int32_t n_groups, const int32_t* group_offsets /* [n_groups + 1] */,
+                                       int32_t* out_index /* [n_groups * k] */, float* out_H /* [n_groups * k][9] or NULL */, float* out_b /* [n_groups * k][3] or NULL */,
+                                       lsm2d_iteration_stats* out_stats /* [n_groups * k] or NULL */, int32_t* out_active /* [n_groups * k] or NULL */,
+                                       int32_t* out_n_selected /* [n_groups] */, int32_t* out_n_accepted /* [n_groups] */);
+int lsm2d_align_select_grouped(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, const lsm2d_batch* batch,
+                               const lsm2d_select_params* select, int32_t k,
+                               int32_t n_groups, const int32_t* group_offsets /* [n_groups + 1] */,
+                               int32_t* out_index /* [n_groups * k] */, float* out_pose /* [n_groups * k][3] */, float* out_H /* [n_groups * k][9] or NULL */,
+                               int32_t* out_iterations /* [n_groups * k] or NULL */, lsm2d_iteration_stats* out_last_stats /* [n_groups * k] or NULL */,
+                               int32_t* out_n_selected /* [n_groups] */, int32_t* out_n_accepted /* [n_groups] */, int32_t* out_n_success /* [n_groups] or NULL */);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -60,6 +60,7 @@ class SelectParamsC(C.Structure):
 
 
 SELECT_MAX_K = 1024      # LSM2D_SELECT_MAX_K
+SELECT_MAX_GROUP_ROWS = 1 << 18      # LSM2D_SELECT_MAX_GROUP_ROWS: n_groups x k of the grouped select calls
 SELECT_TILE = 2048       # entries a workgroup of k_select_tile sorts (kSelectTile, csrc/lsm2d_k_select.h): where the selection takes another pass
 
 
@@ -143,6 +144,12 @@ SYMBOLS = [
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("lsm2d_sweep_align_select", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(SliceParams), C.c_int32, _P, _P, C.POINTER(SelectParamsC), C.c_int32,
                                            _P, _P, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # the select calls per group of the batch: the sibling's arguments with (n_groups, group_offsets) behind k; the counts are arrays [n_groups]
+    ("lsm2d_score_select_grouped", C.c_int, [_P, C.POINTER(SliceParams), _P, _P, _P, _P, C.c_int32, _P, C.POINTER(SelectParamsC), C.c_int32, C.c_int32, _P,
+                                             _P, _P, _P, _P, _P, _P]),
+    ("lsm2d_score_aligner_select_grouped", C.c_int, [_P, C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("lsm2d_align_select_grouped", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -971,6 +971,111 @@ def align_select(aligner: "MultiAligner2D", fixed, moving, init_poses, select: S
     return AlignSelectResult(index[:m], pose[:m], H[:m].reshape(m, 3, 3), its[:m], st[:m], n_acc.value, n_suc.value, ms)
 
 
+# ---- the select calls per GROUP of the batch: a fleet's candidates, the best k per robot (lsm2d_*_select_grouped) ----
+
+def _group_offsets(offsets) -> np.ndarray:
+    """``offsets`` as the contiguous int32 array the C calls take (n_groups + 1 values; the calls check the rest)"""
+    return np.ascontiguousarray(offsets, np.int32).reshape(-1)
+
+
+def _ragged(a: np.ndarray, n_sel: np.ndarray, k: int) -> list:
+    """views ``a[g * k : g * k + n_sel[g]]`` of an array of n_groups x k rows, one per group"""
+    return [a[g * k: g * k + int(m)] for g, m in enumerate(n_sel)]
+
+
+def score_rank_grouped(stats, offsets, select: SelectParams, k: int, active=None):
+    """``score_rank`` per group: group ``g`` is items ``offsets[g] .. offsets[g + 1]`` and is ranked on its own, its indices shifted by ``offsets[g]`` so
+    that they are batch item indices.  The restatement the grouped select calls are held to.  Returns ``(index: list of int32 arrays, one per group,
+    n_accepted int32 [n_groups])``."""
+    st = _stats_array(stats); off = _group_offsets(offsets)
+    act = None if active is None else np.asarray(active).reshape(-1)
+    index, n_acc = [], np.zeros(len(off) - 1, np.int32)
+    for g in range(len(off) - 1):
+        lo, hi = int(off[g]), int(off[g + 1])
+        idx, n_acc[g] = score_rank(st[lo:hi], select, k, None if act is None else act[lo:hi])
+        index.append((idx + np.int32(lo)).astype(np.int32))
+    return index, n_acc
+
+
+def align_rank_grouped(status, iterations, stats, offsets, select: SelectParams, k: int):
+    """``align_rank`` per group, indices shifted by the group's offset.  Returns ``(index: list of int32 arrays, one per group, n_accepted int32
+    [n_groups], n_success int32 [n_groups])``."""
+    status = np.asarray(status).reshape(-1); its = np.asarray(iterations).reshape(-1); st = np.asarray(stats); off = _group_offsets(offsets)
+    index, n_acc, n_suc = [], np.zeros(len(off) - 1, np.int32), np.zeros(len(off) - 1, np.int32)
+    for g in range(len(off) - 1):
+        lo, hi = int(off[g]), int(off[g + 1])
+        idx, n_acc[g], n_suc[g] = align_rank(status[lo:hi], its[lo:hi], st[lo:hi], select, k)
+        index.append((idx + np.int32(lo)).astype(np.int32))
+    return index, n_acc, n_suc
+
+
+def score_select_grouped(ctx: Context, slice_params: SliceParams, fixed, moving, poses, offsets, select: SelectParams, k: int, fixed_index=None,
+                         moving_index=None):
+    """``score_select`` per group of the batch in ONE call with one copy down and one wait (lsm2d_score_select_grouped): group ``g`` is hypotheses
+    ``offsets[g] .. offsets[g + 1]``, and its block is what ``score_select`` returns for that sub-batch, with batch item indices.  Returns ``(index, H, b,
+    stats, n_accepted)``: the first four are lists with one entry per group (views of ``m_g = min(k, n_accepted[g])`` rows, best first), ``n_accepted``
+    int32 ``[n_groups]``."""
+    it = _BatchItems(ctx, fixed, moving, poses, fixed_index, moving_index)
+    off = _group_offsets(offsets); G = max(len(off) - 1, 0); kk = max(int(k), 1); rows = max(G, 1) * kk
+    index = np.empty(rows, np.int32); H = np.empty((rows, 3, 3), np.float32); b = np.empty((rows, 3), np.float32); st = np.zeros(rows, STATS_DTYPE)
+    n_sel = np.zeros(max(G, 1), np.int32); n_acc = np.zeros(max(G, 1), np.int32)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_score_select_grouped(*it.head(slice_params), _ptr(it.poses), C.byref(sel), int(k), G, _ptr(off), _ptr(index), _ptr(H), _ptr(b),
+                                              _ptr(st), _ptr(n_sel), _ptr(n_acc)), "lsm2d_score_select_grouped", ctx.handle)
+    n_sel = n_sel[:G]
+    return _ragged(index, n_sel, kk), _ragged(H, n_sel, kk), _ragged(b, n_sel, kk), _ragged(st, n_sel, kk), n_acc[:G]
+
+
+def score_aligner_select_grouped(aligner: "MultiAligner2D", fixed, moving, poses, offsets, select: SelectParams, k: int, priors=None, fixed_index=None,
+                                 moving_index=None):
+    """``score_aligner_select`` per group of the batch in one call (lsm2d_score_aligner_select_grouped).  Returns ``(index, H, b, stats, active,
+    n_accepted)``: lists with one entry per group, and ``n_accepted`` int32 ``[n_groups]``."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)      # (keep: what bd points to, alive until this function returns)
+    off = _group_offsets(offsets); G = max(len(off) - 1, 0); kk = max(int(k), 1); rows = max(G, 1) * kk
+    index = np.empty(rows, np.int32); H = np.empty((rows, 3, 3), np.float32); b = np.empty((rows, 3), np.float32); st = np.zeros(rows, STATS_DTYPE)
+    active = np.zeros(rows, np.int32)
+    n_sel = np.zeros(max(G, 1), np.int32); n_acc = np.zeros(max(G, 1), np.int32)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_score_aligner_select_grouped(ctx.handle, C.byref(bd), C.byref(sel), int(k), G, _ptr(off), _ptr(index), _ptr(H), _ptr(b), _ptr(st),
+                                                      _ptr(active), _ptr(n_sel), _ptr(n_acc)), "lsm2d_score_aligner_select_grouped", ctx.handle)
+    n_sel = n_sel[:G]
+    return _ragged(index, n_sel, kk), _ragged(H, n_sel, kk), _ragged(b, n_sel, kk), _ragged(st, n_sel, kk), _ragged(active, n_sel, kk), n_acc[:G]
+
+
+@dataclasses.dataclass
+class AlignSelectGroupedResult:
+    index: list                # per group: int32 [m_g], the group's selected candidates as BATCH indices, best first; m_g = min(k, n_accepted[g])
+    pose: list                 # per group: [m_g, 3]
+    information: list          # per group: [m_g, 3, 3]
+    iterations: list           # per group: int32 [m_g]
+    last_stats: list           # per group: structured [m_g]
+    n_accepted: np.ndarray     # int32 [n_groups]
+    n_success: np.ndarray      # int32 [n_groups]
+    kernel_ms: float = 0.0     # the aligner's launch plus the selection (0 when the context is not timed)
+
+
+def align_select_grouped(aligner: "MultiAligner2D", fixed, moving, init_poses, offsets, select: SelectParams, k: int, priors=None, fixed_index=None,
+                         moving_index=None) -> AlignSelectGroupedResult:
+    """``align_select`` per group of the batch -- every robot's own candidates, its own verdict -- in ONE call with one copy down and one wait
+    (lsm2d_align_select_grouped): group ``g``'s entries are what ``align_select`` returns for candidates ``offsets[g] .. offsets[g + 1]`` alone, with batch
+    indices; ``align_rank_grouped`` on ``compute_batch``'s results restates it."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, init_poses, priors, fixed_index, moving_index)      # (keep: what bd points to, alive until this function returns)
+    ap = aligner._aligner_params()
+    off = _group_offsets(offsets); G = max(len(off) - 1, 0); kk = max(int(k), 1); rows = max(G, 1) * kk
+    index = np.empty(rows, np.int32); pose = np.empty((rows, 3), np.float32); H = np.empty((rows, 3, 3), np.float32); its = np.empty(rows, np.int32)
+    st = np.zeros(rows, STATS_DTYPE)
+    n_sel = np.zeros(max(G, 1), np.int32); n_acc = np.zeros(max(G, 1), np.int32); n_suc = np.zeros(max(G, 1), np.int32)
+    sel = select.struct()
+    check(ctx._lib.lsm2d_align_select_grouped(ctx.handle, C.byref(ap), C.byref(bd), C.byref(sel), int(k), G, _ptr(off), _ptr(index), _ptr(pose), _ptr(H),
+                                              _ptr(its), _ptr(st), _ptr(n_sel), _ptr(n_acc), _ptr(n_suc)), "lsm2d_align_select_grouped", ctx.handle)
+    n_sel = n_sel[:G]
+    ms = ctx.last_kernel_ms() if (bd.n_alignments and ctx.kernel_timing) else 0.0
+    return AlignSelectGroupedResult(_ragged(index, n_sel, kk), _ragged(pose, n_sel, kk), _ragged(H, n_sel, kk), _ragged(its, n_sel, kk),
+                                    _ragged(st, n_sel, kk), n_acc[:G], n_suc[:G], ms)
+
+
 @dataclasses.dataclass
 class RelocalizeResult:
     index: np.ndarray          # int32 [m]: the selected hypotheses, best first

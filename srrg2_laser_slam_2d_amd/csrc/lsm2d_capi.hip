@@ -620,3 +620,4 @@ static int ensure_scratch(lsm2d_context* ctx, size_t bytes) {
 #include "lsm2d_capi_finder.inc"
 #include "lsm2d_capi_aligner.inc"
 #include "lsm2d_capi_sweep.inc"
+#include "lsm2d_capi_select_grouped.inc"

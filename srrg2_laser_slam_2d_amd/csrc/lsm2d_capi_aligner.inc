@@ -124,6 +124,8 @@ struct AlignBatch {
   size_t o_rows = 0, o_sel = 0;
   lsm2d_iteration_stats* sel_last_stats = nullptr;      // [k] or NULL (out_stats only says that statistics are wanted, as for a begun batch)
   int32_t* sel_index = nullptr; int32_t* sel_n_selected = nullptr; int32_t* sel_n_accepted = nullptr; int32_t* sel_n_success = nullptr;
+  // ---- ... per group (lsm2d_align_select_grouped): the groups' layout (NULL: one pool), whose table rides up at the end of the input block; the counts above are [n_groups] then
+  const SelectGroupedLayout* groups = nullptr; size_t o_gtab = 0;
 
   size_t take(size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; }
   int validate_and_lay_out_scratch();
@@ -136,6 +138,7 @@ struct AlignBatch {
   int launch();
   int hand_over();
   int select_finish();
+  int select_finish_grouped();
 };
 
 int AlignBatch::validate_and_lay_out_scratch() {
@@ -166,6 +169,7 @@ int AlignBatch::validate_and_lay_out_scratch() {
     if (b->fixed_index) o_fidx[s] = take(sizeof(int32_t) * (size_t) n);
     if (b->moving_index) o_midx[s] = take(sizeof(int32_t) * (size_t) n);
   }
+  if (groups) o_gtab = take(groups->table_bytes());
   in_bytes = off;
   o_pose = take(sizeof(float) * 3 * (size_t) n), o_H = take(sizeof(float) * 9 * (size_t) n);
   o_status = take(sizeof(int32_t) * (size_t) n), o_its = take(sizeof(int32_t) * (size_t) n);
@@ -181,7 +185,7 @@ int AlignBatch::validate_and_lay_out_scratch() {
   o_ff_rows = (ctx->fast_forward == 2 && !out_work) ? take(sizeof(uint32_t) * kFfRowWords * kFfRing * (size_t) n) : 0;
   if (select) {      // the candidates' rows and the selection's own arrays, behind everything the aligner uses (the staging buffer takes the region that comes down at the same offset)
     o_rows = take(sizeof(float) * AlignRow::kWords * (size_t) n);
-    o_sel = take(SelectLayout((size_t) n, (size_t) select_k, AlignRow::kWords).d_bytes);
+    o_sel = take(groups ? groups->d_bytes : SelectLayout((size_t) n, (size_t) select_k, AlignRow::kWords).d_bytes);
   }
   total_bytes = off;
   had_inputs = L->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
@@ -471,6 +475,7 @@ int AlignBatch::stage_inputs() {
     }
     A.prior = (const PriorDev*) (ds + o_prior);
   }
+  if (groups) memcpy(hs + o_gtab, groups->table.data(), groups->table_bytes());
   // one alignment (the live tracker's call): start pose and prior ride in the kernel arguments, so the kernel's prologue does not
   // wait for a read of host memory
   A.inline_n1 = n == 1 && !use_split;
@@ -701,7 +706,7 @@ int AlignBatch::launch() {
 }
 
 int AlignBatch::hand_over() {
-  if (select) return select_finish();
+  if (select) return groups ? select_finish_grouped() : select_finish();
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
   P.ctx = ctx; P.lane = L;
@@ -751,6 +756,44 @@ int AlignBatch::select_finish() {
   }
   *sel_n_selected = n_sel; *sel_n_accepted = n_acc;
   if (sel_n_success) *sel_n_success = n_success;
+  return LSM2D_SUCCESS;
+}
+
+// ... per group: the same packing (k_align_rows still makes the rows and the ONE global never-written count), then select_queue_grouped.  Group g's block
+// comes down as [n_accepted, n_selected, n_success of the group, never-reported of the batch | index[k] | rows[k]] and lands in slots g * k + j.
+int AlignBatch::select_finish_grouped() {
+  const SelectGroupedLayout& E = *groups;
+  char* const d = (char*) L->d_scratch;
+  char* const de = d + o_sel;
+  HIPCHK(ctx, hipMemsetAsync(de + E.e_acc, 0, sizeof(int32_t) * 2, ks));      // Success | never written (the groups' accepted words lie behind them)
+  AlignRowsArgs R;
+  R.pose = (const float*) (d + o_pose); R.H = (const float*) (d + o_H); R.status = (const int32_t*) (d + o_status); R.its = (const int32_t*) (d + o_its);
+  R.stats = (const StatsDev*) (d + o_stats); R.n = n; R.stats_stride = stats_stride; R.not_written = kStatusNotWritten;
+  R.rows = (float*) (d + o_rows); R.counts = (int32_t*) (de + E.e_acc);
+  hipLaunchKernelGGL(k_align_rows<AlignRow>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ks, R);
+  HIPCHK(ctx, hipGetLastError());
+  SelectArgs S;
+  S.rows = R.rows; S.n_items = n; S.k = select_k;
+  S.min_inliers = select->min_inliers; S.max_chi_per_inlier = select->max_chi_per_inlier; S.min_inlier_ratio = select->min_inlier_ratio;
+  { const int rc = select_queue_grouped<AlignRow>(ctx, "align_select_grouped", S, E, de, (const int32_t*) (d + o_gtab), hs + o_sel); if (rc) return rc; }
+  const int32_t* h0 = (const int32_t*) (hs + o_sel);
+  if (h0[3] != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
+  const size_t K = (size_t) select_k;
+  for (size_t g = 0; g < E.G; ++g) {
+    const int32_t* h = h0 + E.group_words * g;
+    const int32_t* h_index = h + kSelectHeaderWords; const int32_t* h_rows = h + kSelectHeaderWords + K;
+    for (int32_t j = 0; j < h[1]; ++j) {
+      const int32_t* row = h_rows + AlignRow::kWords * (size_t) j;
+      const size_t slot = g * K + (size_t) j;
+      sel_index[slot] = h_index[j];
+      memcpy(out_pose + 3 * slot, row + AlignRow::kPose, sizeof(float) * 3);
+      if (out_H) memcpy(out_H + 9 * slot, row + AlignRow::kH, sizeof(float) * 9);
+      if (out_its) out_its[slot] = row[AlignRow::kIts];
+      if (sel_last_stats) memcpy(sel_last_stats + slot, row + AlignRow::kStats, sizeof(lsm2d_iteration_stats));
+    }
+    sel_n_selected[g] = h[1]; sel_n_accepted[g] = h[0];
+    if (sel_n_success) sel_n_success[g] = h[2];
+  }
   return LSM2D_SUCCESS;
 }
 

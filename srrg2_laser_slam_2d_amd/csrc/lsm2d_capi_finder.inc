@@ -475,14 +475,16 @@ extern "C" int lsm2d_linearize_batch(lsm2d_context* ctx, const lsm2d_slice_param
 
 // device: [items | counts | digests | result rows] over the whole batch, then [pairs | partial rows] of one launch group, then d_extra bytes of the caller's;
 // staging: the items' arguments (up), then h_down bytes of the caller's
+// (up_extra: bytes of the caller's that ride up behind the items in the same copy -- the grouped selection's table; 0 for every other call)
 struct ScoreLayout {
-  size_t n = 0, o_cnt = 0, o_dig = 0, o_out = 0, o_pairs = 0, o_part = 0, o_extra = 0, d_bytes = 0, h_out = 0, h_bytes = 0;
+  size_t n = 0, o_up = 0, up_bytes = 0, o_cnt = 0, o_dig = 0, o_out = 0, o_pairs = 0, o_part = 0, o_extra = 0, d_bytes = 0, h_out = 0, h_bytes = 0;
   ScoreLayout() = default;
-  ScoreLayout(size_t n_, size_t per_group, size_t slot, size_t blocks_per_item, size_t d_extra, size_t h_down) : n(n_) {
-    o_cnt = up256(sizeof(FindItem) * n); o_dig = up256(o_cnt + sizeof(int32_t) * n); o_out = up256(o_dig + sizeof(unsigned long long) * n);
+  ScoreLayout(size_t n_, size_t per_group, size_t slot, size_t blocks_per_item, size_t d_extra, size_t h_down, size_t up_extra = 0) : n(n_) {
+    o_up = up256(sizeof(FindItem) * n); up_bytes = up_extra ? o_up + up_extra : sizeof(FindItem) * n;
+    o_cnt = up256(o_up + up_extra); o_dig = up256(o_cnt + sizeof(int32_t) * n); o_out = up256(o_dig + sizeof(unsigned long long) * n);
     o_pairs = up256(o_out + sizeof(float) * kLinOutWords * n); o_part = up256(o_pairs + sizeof(lsm2d_correspondence) * per_group * slot);
     o_extra = up256(o_part + sizeof(float) * kAccumWords * per_group * blocks_per_item); d_bytes = o_extra + d_extra;
-    h_out = up256(sizeof(FindItem) * n); h_bytes = h_out + h_down;
+    h_out = up256(o_up + up_extra); h_bytes = h_out + h_down;
   }
 };
 
@@ -523,7 +525,7 @@ static int score_slice_queue(lsm2d_context* ctx, FindBatchLaunch& P, const lsm2d
 
 static int score_batch_queue(lsm2d_context* ctx, const char* who, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
                              const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses, size_t d_extra, size_t h_down,
-                             ScoreLayout& Y) {
+                             ScoreLayout& Y, const void* up_extra = nullptr, size_t up_extra_bytes = 0) {
   std::vector<int32_t> fc, mc;
   { const int rc = resolve_items(ctx, who, true, fixed, fixed_index, moving, moving_index, n_items, fc, mc); if (rc) return rc; }
   long long need = 0;
@@ -533,12 +535,13 @@ static int score_batch_queue(lsm2d_context* ctx, const char* who, const lsm2d_sl
   FindBatchLaunch P;
   { const int rc = find_batch_prepare(ctx, sp, fixed, moving, 0.0f, slot, who, P); if (rc) return rc; }
   const size_t n = (size_t) n_items, per_group = items_per_launch((size_t) slot, n, kLinBatchMaxItems), B = (size_t) lin_blocks(slot);
-  Y = ScoreLayout(n, per_group, (size_t) slot, B, d_extra, h_down);
+  Y = ScoreLayout(n, per_group, (size_t) slot, B, d_extra, h_down, up_extra_bytes);
   { int rc = ensure_scratch(ctx, Y.d_bytes); if (rc) return rc; rc = ensure_stage(ctx, Y.h_bytes); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
   find_batch_fill_items((FindItem*) hs, fixed, fc.data(), moving, mc.data(), poses, n);
-  HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(FindItem) * n, hipMemcpyHostToDevice, ctx->stream));
+  if (up_extra_bytes) memcpy(hs + Y.o_up, up_extra, up_extra_bytes);
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_dig, 0, sizeof(unsigned long long) * n, ctx->stream));
   const ScoreSliceDev D = {(const FindItem*) ds, (int32_t*) (ds + Y.o_cnt), (unsigned long long*) (ds + Y.o_dig), (float*) (ds + Y.o_out),
                            (int32_t*) (ds + Y.o_pairs), (float*) (ds + Y.o_part), 0u};
@@ -659,9 +662,12 @@ struct ScoreAlignerLayout {
   size_t n = 0, ns = 0, o_prior = 0, o_fidx = 0, o_midx = 0, up_bytes = 0, o_items = 0, o_cnt = 0, o_dig = 0, o_out = 0, o_comb = 0, o_pairs = 0, o_part = 0,
          o_extra = 0, d_bytes = 0, h_out = 0, h_bytes = 0;
   ScoreAlignerLayout() = default;
-  ScoreAlignerLayout(size_t n_, size_t ns_, bool prior, bool fidx, bool midx, size_t per_group, size_t slot_max, size_t d_extra, size_t h_down) : n(n_), ns(ns_) {
+  size_t o_up_extra = 0;      // (up_extra bytes of the caller's behind the upload, in the same copy: the grouped selection's table; 0 for every other call)
+  ScoreAlignerLayout(size_t n_, size_t ns_, bool prior, bool fidx, bool midx, size_t per_group, size_t slot_max, size_t d_extra, size_t h_down,
+                     size_t up_extra = 0) : n(n_), ns(ns_) {
     o_prior = up256(sizeof(float) * 3 * n); o_fidx = up256(o_prior + (prior ? sizeof(PriorDev) * n : 0));
     o_midx = up256(o_fidx + (fidx ? sizeof(int32_t) * ns * n : 0)); up_bytes = o_midx + (midx ? sizeof(int32_t) * ns * n : 0);
+    if (up_extra) { o_up_extra = up256(up_bytes); up_bytes = o_up_extra + up_extra; }
     o_items = up256(up_bytes); o_cnt = up256(o_items + sizeof(FindItem) * ns * n); o_dig = up256(o_cnt + sizeof(int32_t) * ns * n);
     o_out = up256(o_dig + sizeof(unsigned long long) * ns * n); o_comb = up256(o_out + sizeof(float) * kLinOutWords * ns * n);
     o_pairs = up256(o_comb + sizeof(float) * kCombWords * n); o_part = up256(o_pairs + sizeof(lsm2d_correspondence) * per_group * slot_max);
@@ -693,7 +699,8 @@ static int score_aligner_head(lsm2d_context* ctx, const char* who, const lsm2d_b
 
 // Everything from the index rules to k_score_combine: leaves the combined rows on the device (ds + Y.o_comb), waits for nothing, has begun the timing
 // bracket; the caller ends it.  n_alignments > 0 and score_aligner_head have been checked.
-static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y) {
+static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y,
+                               const void* up_extra = nullptr, size_t up_extra_bytes = 0) {
   const int ns = b->n_slices; const int32_t n_items = b->n_alignments; const size_t n = (size_t) n_items;
   if (!b->init_pose) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
   // every refusal first: the index rules per slice, then what the slices' finders need
@@ -724,11 +731,13 @@ static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_
     { const int rc = find_batch_prepare(ctx, b->slices + s, b->fixed[s], b->moving[s], 0.0f, slot[s], who, P[s]); if (rc) return rc; }
   }
   const size_t per_group = items_per_launch((size_t) slot_max, n, kLinBatchMaxItems);
-  Y = ScoreAlignerLayout(n, (size_t) ns, b->prior != nullptr, b->fixed_index != nullptr, b->moving_index != nullptr, per_group, (size_t) slot_max, d_extra, h_down);
+  Y = ScoreAlignerLayout(n, (size_t) ns, b->prior != nullptr, b->fixed_index != nullptr, b->moving_index != nullptr, per_group, (size_t) slot_max, d_extra, h_down,
+                         up_extra_bytes);
   { int rc = ensure_scratch(ctx, Y.d_bytes); if (rc) return rc; rc = ensure_stage(ctx, Y.h_bytes); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
   memcpy(hs, b->init_pose, sizeof(float) * 3 * n);
+  if (up_extra_bytes) memcpy(hs + Y.o_up_extra, up_extra, up_extra_bytes);
   if (b->prior) {
     PriorDev* p = (PriorDev*) (hs + Y.o_prior);
     for (size_t i = 0; i < n; ++i) {      // as the aligner stages them (AlignBatch::stage_inputs)
@@ -815,4 +824,116 @@ extern "C" int lsm2d_score_aligner_select(lsm2d_context* ctx, const lsm2d_batch*
   }
   *out_n_selected = n_sel; *out_n_accepted = n_acc;
   return LSM2D_SUCCESS;
+}
+
+// ---- ... ranked PER GROUP of the batch: the fleet's form of the three select calls (lsm2d_k_select_grouped.h) --------------------------------------------------
+// Group g is items [off[g], off[g + 1]); every group gets the block the ungrouped call returns for its sub-batch, indices shifted by off[g].  The host knows
+// every group's size, so it lays out every launch: a table [offsets | one closing descriptor per group | keys descriptors | the passes' descriptors] rides up
+// with the call's arguments, in the same copy.  Every group at most one tile: ONE launch, a workgroup per group, and the table is the offsets alone.
+// Otherwise: keys over (group, chunk) descriptors, passes of k_select_tile_seg over the groups that are still larger than a tile -- group g's m entries
+// become ceil(m / tile) x k, in its own stretch of the other array -- and k_select_gather_group, which sorts what is left of every group and gathers.
+// (Here: the checks, the layout and select_queue_grouped, beside select_queue.  The three entry points are in lsm2d_capi_select_grouped.inc, the last include
+// part: what instantiates the grouped kernels comes behind every older kernel's first use, so those keep their places in the code object.)
+
+// offsets: n_groups + 1 values, non-decreasing, from 0 to n; n_groups x k within LSM2D_SELECT_MAX_GROUP_ROWS
+static int check_groups(lsm2d_context* ctx, const char* who, int32_t n_groups, const int32_t* off, int32_t n, int32_t k) {
+  static_assert(LSM2D_SELECT_MAX_GROUP_ROWS == (1 << 18), "the ABI's cap");
+  if (!off) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
+  if (n_groups < 1) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: n_groups must be >= 1", who);
+  if ((long long) n_groups * (long long) k > (long long) LSM2D_SELECT_MAX_GROUP_ROWS)
+    return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: n_groups x k above LSM2D_SELECT_MAX_GROUP_ROWS", who);
+  if (off[0] != 0 || off[n_groups] != n) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: group_offsets must start at 0 and end at the batch's size", who);
+  for (int32_t g = 0; g < n_groups; ++g)
+    if (off[g + 1] < off[g]) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: group_offsets decrease at group %d", who, (int) g);
+  return LSM2D_SUCCESS;
+}
+
+// The table that rides up (words), where the selection's own part of the scratch lies -- [keys A | index A] of n entries, [keys B | index B] of what the first
+// pass leaves, [Success, never written | accepted[G]], the region that goes down -- and every launch of the segmented form.
+struct SelectGroupedLayout {
+  struct Pass { size_t t_off, count; };
+  size_t n, G, K, group_words, n_b = 0;
+  bool one_tile = true;
+  std::vector<int32_t> table; size_t t_fin = 0, t_keys = 0, n_keys = 0; std::vector<Pass> passes;      // (t_*: word offsets of SelectSeg arrays in the table)
+  size_t e_idx_a = 0, e_key_b = 0, e_idx_b = 0, e_acc = 0, e_down = 0, down_bytes = 0, d_bytes = 0;
+  size_t table_bytes() const { return sizeof(int32_t) * table.size(); }
+  SelectGroupedLayout(const int32_t* off, size_t G_, size_t K_, size_t row_words) : n((size_t) off[G_]), G(G_), K(K_), group_words(kSelectHeaderWords + K_ + K_ * row_words) {
+    static_assert(sizeof(SelectSeg) == 4 * sizeof(int32_t), "a descriptor is four words of the table");
+    for (size_t g = 0; g < G; ++g) if (off[g + 1] - off[g] > kSelectTile) one_tile = false;
+    table.assign(off, off + G + 1);
+    if (!one_tile) {
+      const auto push = [this](int32_t a, int32_t b, int32_t c, int32_t d) { table.push_back(a); table.push_back(b); table.push_back(c); table.push_back(d); };
+      while (table.size() % 4) table.push_back(0);
+      t_fin = table.size(); table.resize(t_fin + 4 * G, 0);      // filled once the passes are known
+      t_keys = table.size();
+      for (size_t g = 0; g < G; ++g)
+        for (int32_t c = off[g]; c < off[g + 1]; c += 256) { push(c, std::min<int32_t>(256, off[g + 1] - c), 0, (int32_t) g); ++n_keys; }
+      std::vector<int32_t> base(off, off + G), cnt(G), b_base(G, 0);
+      for (size_t g = 0; g < G; ++g) {
+        cnt[g] = off[g + 1] - off[g];
+        if (cnt[g] > kSelectTile) { b_base[g] = (int32_t) n_b; n_b += (size_t) ((cnt[g] + kSelectTile - 1) / kSelectTile) * K; }      // (< cnt[g]: n_b < n)
+      }
+      for (int src = 0;; src ^= 1) {      // a pass reads array `src` and writes the other: a group's stretch of A is its items', of B what its first pass left
+        Pass P = {table.size(), 0};
+        for (size_t g = 0; g < G; ++g) {
+          if (cnt[g] <= kSelectTile) continue;
+          const int32_t tiles = (cnt[g] + kSelectTile - 1) / kSelectTile, out = src ? off[g] : b_base[g];
+          for (int32_t j = 0; j < tiles; ++j) push(base[g] + j * kSelectTile, std::min<int32_t>(kSelectTile, cnt[g] - j * kSelectTile), out + j * (int32_t) K, 0);
+          P.count += (size_t) tiles; base[g] = out; cnt[g] = tiles * (int32_t) K;      // (tiles >= 2: tiles x k <= tiles x tile / 2 < the entries that came in)
+          table[t_fin + 4 * g + 3] = src ^ 1;
+        }
+        if (!P.count) break;
+        passes.push_back(P);
+      }
+      for (size_t g = 0; g < G; ++g) { table[t_fin + 4 * g] = base[g]; table[t_fin + 4 * g + 1] = cnt[g]; }
+      e_idx_a = up256(sizeof(u64) * n); e_key_b = up256(e_idx_a + sizeof(int32_t) * n); e_idx_b = up256(e_key_b + sizeof(u64) * n_b);
+      e_acc = up256(e_idx_b + sizeof(int32_t) * n_b);
+    }
+    e_down = up256(e_acc + sizeof(int32_t) * (2 + G));
+    down_bytes = sizeof(int32_t) * group_words * G;
+    d_bytes = e_down + down_bytes;
+  }
+};
+
+// select_queue for groups: the launches behind the scoring on the same stream, the end of the timing bracket, the one copy down to `h_down`, the one wait,
+// every group's counters checked.  `d_table`: where the layout's table lies on the device.  (A format that carries counts: the caller has zeroed the two
+// words at de + e_acc and queued the kernel that counts into them.)
+template <class Row>
+static int select_queue_grouped(lsm2d_context* ctx, const char* who, SelectArgs S, const SelectGroupedLayout& E, char* de, const int32_t* d_table, char* h_down) {
+  Lane& L = lane(ctx);
+  int32_t* const acc = (int32_t*) (de + E.e_acc);
+  u64* const key_b = (u64*) (de + E.e_key_b); int32_t* const idx_b = (int32_t*) (de + E.e_idx_b);
+  S.keys = (u64*) de; S.index = (int32_t*) (de + E.e_idx_a); S.n_accepted = acc + 2;
+  SelectGroupedArgs A;
+  A.S = S; A.offsets = d_table; A.unwritten = SelectCarriesCounts<Row>::value ? acc + 1 : nullptr; A.down = (int32_t*) (de + E.e_down);
+  if (E.one_tile) hipLaunchKernelGGL(k_select_group_one<Row>, dim3((unsigned) E.G), dim3(kSelectBlock), 0, ctx->stream, A);
+  else {
+    HIPCHK(ctx, hipMemsetAsync(S.n_accepted, 0, sizeof(int32_t) * E.G, ctx->stream));
+    hipLaunchKernelGGL(k_select_keys_seg<Row>, dim3((unsigned) E.n_keys), dim3(256), 0, ctx->stream, A, (const SelectSeg*) (d_table + E.t_keys));
+    int src = 0;
+    for (const SelectGroupedLayout::Pass& P : E.passes) {
+      hipLaunchKernelGGL(k_select_tile_seg<kSelectTile>, dim3((unsigned) P.count), dim3(kSelectBlock), 0, ctx->stream, (const u64*) (src ? key_b : S.keys),
+                         (const int32_t*) (src ? idx_b : S.index), src ? S.keys : key_b, src ? S.index : idx_b, (const SelectSeg*) (d_table + P.t_off), S.k);
+      src ^= 1;
+    }
+    hipLaunchKernelGGL(k_select_gather_group<Row>, dim3((unsigned) E.G), dim3(kSelectBlock), 0, ctx->stream, A, (const SelectSeg*) (d_table + E.t_fin),
+                       (const u64*) key_b, (const int32_t*) idx_b);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
+  HIPCHK(ctx, hipMemcpyAsync(h_down, de + E.e_down, E.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  for (size_t g = 0; g < E.G; ++g) {
+    const int32_t* h = (const int32_t*) h_down + E.group_words * g;
+    const int32_t size = E.table[g + 1] - E.table[g], n_acc = h[0], n_sel = h[1];
+    bool ok = n_acc >= 0 && n_acc <= size && n_sel == (n_acc < S.k ? n_acc : S.k);
+    if (SelectCarriesCounts<Row>::value) ok = ok && h[2] >= n_acc && h[2] <= size;
+    if (!ok) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the selection's counters are inconsistent (group %d)", who, (int) g);
+  }
+  return LSM2D_SUCCESS;
+}
+
+// an empty batch with groups: every group reports 0 accepted and 0 selected
+static void groups_report_empty(int32_t n_groups, int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  for (int32_t g = 0; g < n_groups; ++g) { out_n_selected[g] = 0; out_n_accepted[g] = 0; if (out_n_success) out_n_success[g] = 0; }
 }

@@ -17,6 +17,8 @@
 //   k_select_*         the acceptance test and the best k of those rows, ranked on the device: only k rows travel (lsm2d_score_select; lsm2d_k_select.h).
 //   k_align_rows       one row per ALIGNED candidate (pose, H, status, iterations, its last iteration's statistics) for the same selection, and the counts of
 //                      Success and never-written statuses (lsm2d_align_select; lsm2d_k_align_select.h).
+//   k_select_group_one / k_select_*_seg / k_select_gather_group  the same selection per GROUP of the batch: a fleet's candidates, the best k per robot
+//                      (lsm2d_*_select_grouped; lsm2d_k_select_grouped.h).
 //   k_score_aligner_items / k_score_combine  hypotheses scored against a whole aligner: per-slice item tables from the poses, and the slices' rows combined with
 //                      the skip rule and the prior into one row per item (lsm2d_score_aligner_batch / _select; lsm2d_k_score_aligner.h).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
@@ -57,6 +59,7 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_split_finder.h"
 #include "lsm2d_k_select.h"
 #include "lsm2d_k_align_select.h"
+#include "lsm2d_k_select_grouped.h"
 #include "lsm2d_k_score_aligner.h"
 #include "lsm2d_k_finder.h"
 #include "lsm2d_k_mapping.h"
