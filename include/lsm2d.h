@@ -66,7 +66,9 @@ extern "C" {
                                     only k rows come down, whatever the iteration count is);
                              (0.7.8, number unchanged: an addition only) + lsm2d_score_select_grouped, lsm2d_score_aligner_select_grouped,
                                     lsm2d_align_select_grouped, LSM2D_SELECT_MAX_GROUP_ROWS (the three select calls per GROUP of the batch -- a fleet's
-                                    candidates, the best k per robot: one call, one wait, n_groups x k rows come down) */
+                                    candidates, the best k per robot: one call, one wait, n_groups x k rows come down);
+                             (0.7.9, number unchanged: an addition only) + lsm2d_relocalize_select (lsm2d_score_aligner_select, then lsm2d_align_select
+                                    over the selected hypotheses, chained on the device: one upload, one copy down, one wait) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -682,6 +684,41 @@ int lsm2d_align_select_grouped(lsm2d_context* ctx, const lsm2d_aligner_params* a
                                int32_t* out_index /* [n_groups * k] */, float* out_pose /* [n_groups * k][3] */, float* out_H /* [n_groups * k][9] or NULL */,
                                int32_t* out_iterations /* [n_groups * k] or NULL */, lsm2d_iteration_stats* out_last_stats /* [n_groups * k] or NULL */,
                                int32_t* out_n_selected /* [n_groups] */, int32_t* out_n_accepted /* [n_groups] */, int32_t* out_n_success /* [n_groups] or NULL */);
+
+/* ---- relocalise in ONE call (0.7.9): the candidate loop of the relocaliser / loop detector (MultiRelocalizer2D, MultiLoopDetectorBruteForce2D:
+ * MULTI.json:749-769, :964-986) scores its hypotheses, keeps the best that pass the acceptance test, aligns those and judges the aligned ones.  That is
+ * lsm2d_score_aligner_select followed by lsm2d_align_select, with the host in the middle only to gather the selected hypotheses' poses, priors and cloud
+ * indices and send them up again.  Here the selection's answer stays on the device, a kernel writes the aligner's input block from it, and both answers come
+ * down together.
+ * batch: the descriptor lsm2d_score_aligner_select takes -- 1 .. 4 slices, optional per-hypothesis priors, optional [n_slices][n] index arrays, init_pose
+ * holding the hypotheses.
+ * Meaning (PARITY.md section 3, item 18e).  Every output is bit for bit what the two existing calls give, made in this order:
+ *   1. lsm2d_score_aligner_select(batch, score_select, k_score) returns m = n_scored_selected indices idx[0 .. m), best first;
+ *   2. lsm2d_align_select(aligner, batch', align_select, k), where batch' has m candidates and candidate j is hypothesis idx[j]: its pose, its prior, its
+ *      cloud in every slice (where batch has no index array, lsm2d_batch's rule spelled out: cloud idx[j], or cloud 0 of a one-cloud set);
+ *   3. out_index[r] = idx[the second call's index]: out_index holds BATCH indices;
+ *   4. the counts are the second call's; n_success counts the m real candidates only;
+ *   5. ties in the second ranking break by slot j, i.e. by stage-1 rank;
+ *   6. m == 0: the second stage's counts are zeros and the call succeeds.
+ * in both values of "sum_order", every "fast_forward" and every "align_path".  align_select == NULL: score_select's thresholds judge the aligned candidates too.
+ * Outputs: out_scored_index / out_scored_stats (may be NULL) / the two scored counts as lsm2d_score_aligner_select gives index, statistics and counts;
+ * out_index .. out_n_success as lsm2d_align_select gives them.  Positions beyond the counts are not written.
+ * Refused before anything is launched or written: everything either sibling refuses; k_score or k outside [1, LSM2D_SELECT_MAX_K]; a batch in flight on
+ * the context (the call uses both lanes).  n_alignments == 0 succeeds with all counts 0.
+ * Cost: ONE upload (stage 1's), ONE copy down -- [16 bytes | k_score indices | k_score rows of 80 bytes] and [16 bytes | k indices | k rows of 96 bytes],
+ * adjacent -- and ONE wait.  The aligner always runs k_score alignments: slots beyond m are PADS that repeat idx[0] (hypothesis 0 when m == 0); their rows
+ * are never ranked, counted or returned.  So a call in which nothing passes stage 1 still pays k_score alignments: a caller who expects mostly empty
+ * selections is better served by the two calls.  The path rule ("align_path" 0) decides for k_score candidates, not for m: the launch form may differ from
+ * the two-call route's, the bits do not.  "kernel_timing" / lsm2d_last_kernel_ms cover the whole chain, from in front of stage 1's first launch (its upload
+ * included -- more than lsm2d_score_aligner_select's own bracket, which begins at the last launch group) to the final selection.  The call is synchronous. */
+int lsm2d_relocalize_select(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, const lsm2d_batch* batch,
+                            const lsm2d_select_params* score_select, int32_t k_score,     /* stage 1: lsm2d_score_aligner_select's test and k */
+                            const lsm2d_select_params* align_select, int32_t k,           /* stage 2: lsm2d_align_select's; NULL = score_select */
+                            int32_t* out_scored_index /* [k_score] */, lsm2d_iteration_stats* out_scored_stats /* [k_score] or NULL */,
+                            int32_t* out_n_scored_selected, int32_t* out_n_scored_accepted,
+                            int32_t* out_index /* [k] */, float* out_pose /* [k][3] */, float* out_H /* [k][9] or NULL */,
+                            int32_t* out_iterations /* [k] or NULL */, lsm2d_iteration_stats* out_last_stats /* [k] or NULL */,
+                            int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success /* or NULL */);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -150,6 +150,10 @@ SYMBOLS = [
     ("lsm2d_score_aligner_select_grouped", C.c_int, [_P, C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lsm2d_align_select_grouped", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                              _P, _P, _P, _P]),
+    # score_aligner_select, then align_select over the selected hypotheses, chained on the device (align_select may be NULL: score_select's thresholds)
+    ("lsm2d_relocalize_select", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.POINTER(SelectParamsC),
+                                          C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

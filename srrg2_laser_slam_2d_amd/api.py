@@ -1454,3 +1454,44 @@ class TrackerBatch:
         self.estimate = np.array([c(self.guess[i][None, :].astype(np.float64), inv(x[i][None, :].astype(np.float64)))[0] for i in range(self.n)], np.float64)
         self.merger.compute_batch(self.maps, self.scans, self._sensor_poses(self.estimate))
         return x, r.status, r.information
+
+
+@dataclasses.dataclass
+class RelocalizeSelectResult:
+    scored_index: np.ndarray   # int32 [m]: stage 1's selection, best first (``score_aligner_select``'s index); m = min(k_score, n_scored_accepted)
+    scored_stats: np.ndarray   # structured [m]: their statistics at their own poses
+    n_scored_accepted: int     # hypotheses that passed stage 1's acceptance test, of all
+    index: np.ndarray          # int32 [r]: the aligned and accepted hypotheses as BATCH indices, best first; r = min(k, n_accepted)
+    pose: np.ndarray           # [r, 3]
+    information: np.ndarray    # [r, 3, 3]
+    iterations: np.ndarray     # int32 [r]
+    last_stats: np.ndarray     # structured [r]: the statistics of the last iteration each started
+    n_accepted: int            # of the m aligned hypotheses: aligner succeeded and the last iteration passes stage 2's thresholds
+    n_success: int             # of the m aligned hypotheses: aligner succeeded
+    kernel_ms: float = 0.0     # from stage 1's first launch to the final selection (0 when the context is not timed)
+
+
+def relocalize_select(aligner: "MultiAligner2D", fixed, moving, poses, score_select: SelectParams, k_score: int, align_select: SelectParams = None,
+                      k: int = None, priors=None, fixed_index=None, moving_index=None) -> RelocalizeSelectResult:
+    """The relocaliser / loop detector's candidate loop (MULTI.json:749-769, :964-986) in ONE call with one upload, one copy down and one wait
+    (lsm2d_relocalize_select): ``score_aligner_select(..., score_select, k_score)``, then ``align_select(..., align_select, k)`` over the selected
+    hypotheses -- their poses, priors and clouds gathered on the device -- with ``index`` mapped back to batch indices.  Every output is the two calls'
+    bit for bit.  ``align_select`` None: ``score_select``; ``k`` None: ``k_score``.  The aligner always runs ``k_score`` alignments (slots nothing was
+    selected for repeat a selected hypothesis and are never returned), so where mostly nothing passes stage 1 the two calls are cheaper."""
+    ctx = aligner._ctx
+    bd, keep = aligner._batch(fixed, moving, poses, priors, fixed_index, moving_index)      # (keep: what bd points to, alive until this function returns)
+    ap = aligner._aligner_params()
+    k2 = int(k_score if k is None else k)
+    ks, kk = max(int(k_score), 1), max(k2, 1)
+    s_index = np.empty(ks, np.int32); s_st = np.zeros(ks, STATS_DTYPE)
+    index = np.empty(kk, np.int32); pose = np.empty((kk, 3), np.float32); H = np.empty((kk, 9), np.float32); its = np.empty(kk, np.int32)
+    st = np.zeros(kk, STATS_DTYPE)
+    n_ssel = C.c_int32(0); n_sacc = C.c_int32(0); n_sel = C.c_int32(0); n_acc = C.c_int32(0); n_suc = C.c_int32(0)
+    sel1 = score_select.struct(); sel2 = None if align_select is None else align_select.struct()
+    check(ctx._lib.lsm2d_relocalize_select(ctx.handle, C.byref(ap), C.byref(bd), C.byref(sel1), int(k_score), None if sel2 is None else C.byref(sel2), k2,
+                                           _ptr(s_index), _ptr(s_st), C.byref(n_ssel), C.byref(n_sacc), _ptr(index), _ptr(pose), _ptr(H), _ptr(its), _ptr(st),
+                                           C.byref(n_sel), C.byref(n_acc), C.byref(n_suc)), "lsm2d_relocalize_select", ctx.handle)
+    m, r = n_ssel.value, n_sel.value
+    ms = ctx.last_kernel_ms() if (bd.n_alignments and ctx.kernel_timing) else 0.0
+    return RelocalizeSelectResult(s_index[:m], s_st[:m], n_sacc.value, index[:r], pose[:r], H[:r].reshape(r, 3, 3), its[:r], st[:r], n_acc.value,
+                                  n_suc.value, ms)

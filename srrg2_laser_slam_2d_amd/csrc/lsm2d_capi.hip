@@ -585,8 +585,8 @@ static PtrKind pointer_kind(const void* p, int* device = nullptr) {
 // (both lanes taken by batches in flight: the "current" staging buffers are the older batch's -- its arguments, its results.  Every entry point that stages
 // anything comes through here and fails loudly instead of writing over them; lsm2d_align_batch_begin says the same before it gets here)
 static const char* const kBothLanesBusy = "two batches are in flight on this context and its staging buffers are theirs: wait for the older one first (lsm2d_align_batch_wait)";
-static int ensure_stage(lsm2d_context* ctx, size_t bytes) {
-  Lane& L = lane(ctx);
+// (the forms that name the lane: an AlignBatch asks for ITS lane's buffers, which lsm2d_relocalize_select makes the other one than the current)
+static int ensure_stage(lsm2d_context* ctx, Lane& L, size_t bytes) {
   if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
   if (bytes <= L.h_stage_bytes) return LSM2D_SUCCESS;
   if (L.h_stage) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipHostFree(L.h_stage)); L.h_stage = nullptr; L.h_stage_bytes = 0; }
@@ -598,8 +598,9 @@ static int ensure_stage(lsm2d_context* ctx, size_t bytes) {
   return LSM2D_SUCCESS;
 }
 
-static int ensure_scratch(lsm2d_context* ctx, size_t bytes) {
-  Lane& L = lane(ctx);
+static int ensure_stage(lsm2d_context* ctx, size_t bytes) { return ensure_stage(ctx, lane(ctx), bytes); }
+
+static int ensure_scratch(lsm2d_context* ctx, Lane& L, size_t bytes) {
   if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
   L.inputs_valid = false;      // (whoever asks is about to write the scratch; lsm2d_align_batch looks at the flag before it asks)
   if (bytes <= L.d_scratch_bytes) return LSM2D_SUCCESS;
@@ -612,6 +613,7 @@ static int ensure_scratch(lsm2d_context* ctx, size_t bytes) {
   L.d_scratch_bytes = cap;
   return LSM2D_SUCCESS;
 }
+static int ensure_scratch(lsm2d_context* ctx, size_t bytes) { return ensure_scratch(ctx, lane(ctx), bytes); }
 
 // ---- the rest of the host side, by subject (one translation unit: they share the context, the cloud sets and the helpers above) ----
 #include "lsm2d_capi_cloudsets.inc"
@@ -621,3 +623,4 @@ static int ensure_scratch(lsm2d_context* ctx, size_t bytes) {
 #include "lsm2d_capi_aligner.inc"
 #include "lsm2d_capi_sweep.inc"
 #include "lsm2d_capi_select_grouped.inc"
+#include "lsm2d_capi_relocalize.inc"

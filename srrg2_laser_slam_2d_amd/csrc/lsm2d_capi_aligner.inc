@@ -12,6 +12,9 @@
 //   hand_over                     a lsm2d_pending for an asynchronous begin, or the wait and the results (align_batch_finish)
 // SELECT mode (lsm2d_align_select: AlignBatch::select != NULL) runs the same stages with the results kept on the device -- no zero-copy form, no results written
 // to pinned host memory, no copy of them queued -- and hand_over ends in k_align_rows and select_queue<AlignRow>: k rows come down (select_finish).
+// ... and with its INPUTS ON THE DEVICE (lsm2d_relocalize_select: AlignBatch::reloc != NULL, lsm2d_capi_relocalize.inc) select mode takes a batch whose start
+// poses, priors and index arrays a kernel writes from an earlier stage's selection: stage_inputs copies nothing and queues no upload (reloc_stage_inputs),
+// every shortcut that assumes the host knows the inputs is off, the timing bracket is the earlier stage's, and hand_over ends in reloc_finish.
 // ---- plugin interface #2 ----------------------------------------------------------------------------------------
 extern "C" uint64_t lsm2d_pair_hash(uint32_t slice, uint32_t fixed_idx, uint32_t moving_idx) {      // the kernels' pair_hash_dev, on the host
   const uint32_t a = fixed_idx * 0x9E3779B1u, b = (moving_idx ^ (slice * 0x632BE5ABu)) * 0x85EBCA77u;
@@ -96,6 +99,7 @@ static bool pack_two_for(const lsm2d_context* ctx, int n, size_t lds) {
   return n <= slots + 24 || n > narrow_per_cu * n_cu;      // (against the narrow kernel, whole step, us per alignment: 1041 0.876 vs 0.895, 1050 0.892 vs 0.888, 1060 0.905 vs 0.882: profiles/r06/packed_ab_r06S.txt)
 }
 
+struct RelocStage;      // what the first stage of lsm2d_relocalize_select left on the device (lsm2d_capi_relocalize.inc)
 // Everything the stages of one lsm2d_align_batch call share.  The members carry the names the statements below always used.
 struct AlignBatch {
   // ---- the call
@@ -126,8 +130,15 @@ struct AlignBatch {
   int32_t* sel_index = nullptr; int32_t* sel_n_selected = nullptr; int32_t* sel_n_accepted = nullptr; int32_t* sel_n_success = nullptr;
   // ---- ... per group (lsm2d_align_select_grouped): the groups' layout (NULL: one pool), whose table rides up at the end of the input block; the counts above are [n_groups] then
   const SelectGroupedLayout* groups = nullptr; size_t o_gtab = 0;
+  // ---- ... with the inputs ON THE DEVICE (lsm2d_relocalize_select, lsm2d_capi_relocalize.inc): the batch's n slots are filled by a kernel from an earlier
+  // stage's selection (reloc_stage_inputs), not from the host.  The descriptor's init_pose / prior / index pointers then only say "there is one" and are never
+  // read, every shortcut that assumes the host knows the inputs is off (inline_n1, defer_unpack, the inputs' shadow, the kept placement), the timing bracket is
+  // the earlier stage's, and reloc_down_bytes of the scratch and the staging at o_reloc_down hold what the call copies down (reloc_finish)
+  RelocStage* reloc = nullptr; size_t reloc_down_bytes = 0, o_reloc_down = 0;
 
   size_t take(size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; }
+  int reloc_stage_inputs();
+  int reloc_finish();
   int validate_and_lay_out_scratch();
   int choose_path();
   int prepare_slices();
@@ -187,10 +198,11 @@ int AlignBatch::validate_and_lay_out_scratch() {
     o_rows = take(sizeof(float) * AlignRow::kWords * (size_t) n);
     o_sel = take(groups ? groups->d_bytes : SelectLayout((size_t) n, (size_t) select_k, AlignRow::kWords).d_bytes);
   }
+  if (reloc) o_reloc_down = take(reloc_down_bytes);
   total_bytes = off;
   had_inputs = L->inputs_valid;      // (the lane's scratch still holds the previous batch's input block: ensure_scratch below clears the flag)
-  int rc = ensure_scratch(ctx, total_bytes); if (rc) return rc;
-  rc = ensure_stage(ctx, total_bytes); if (rc) return rc;
+  int rc = ensure_scratch(ctx, *L, total_bytes); if (rc) return rc;
+  rc = ensure_stage(ctx, *L, total_bytes); if (rc) return rc;
   hs = (char*) L->h_stage; ds = (char*) L->d_scratch;
   return LSM2D_SUCCESS;
 }
@@ -281,19 +293,25 @@ int AlignBatch::prepare_slices() {
     if (!b->fixed_index && f->n_clouds != 1 && f->n_clouds != n) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: fixed set must hold 1 or n_alignments clouds");
     if (!b->moving_index && m->n_clouds != 1 && m->n_clouds != n) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: moving set must hold 1 or n_alignments clouds");
     const int32_t* d_fi = nullptr; const int32_t* d_mi = nullptr;
-    if (b->fixed_index) {
-      const int32_t* src = b->fixed_index + (size_t) s * n;
-      for (int i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= f->n_clouds) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: fixed_index out of range");
-      memcpy(hs + o_fidx[s], src, sizeof(int32_t) * (size_t) n); d_fi = (const int32_t*) (ds + o_fidx[s]);
-    }
-    if (b->moving_index) {
-      const int32_t* src = b->moving_index + (size_t) s * n;
-      for (int i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= m->n_clouds) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: moving_index out of range");
-      memcpy(hs + o_midx[s], src, sizeof(int32_t) * (size_t) n); d_mi = (const int32_t*) (ds + o_midx[s]);
+    if (reloc) {
+      // inputs on the device: both index arrays are written there (reloc_stage_inputs) from tables the earlier stage checked against the sets; the
+      // descriptor's pointers are not read
+      d_fi = (const int32_t*) (ds + o_fidx[s]); d_mi = (const int32_t*) (ds + o_midx[s]);
+    } else {
+      if (b->fixed_index) {
+        const int32_t* src = b->fixed_index + (size_t) s * n;
+        for (int i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= f->n_clouds) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: fixed_index out of range");
+        memcpy(hs + o_fidx[s], src, sizeof(int32_t) * (size_t) n); d_fi = (const int32_t*) (ds + o_fidx[s]);
+      }
+      if (b->moving_index) {
+        const int32_t* src = b->moving_index + (size_t) s * n;
+        for (int i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= m->n_clouds) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: moving_index out of range");
+        memcpy(hs + o_midx[s], src, sizeof(int32_t) * (size_t) n); d_mi = (const int32_t*) (ds + o_midx[s]);
+      }
     }
     // a fixed set whose upload still sits in its pinned buffer: single-alignment projective calls unpack it in the kernel's prologue
-    // (decided once the kernel is known, below); every other reader gets it unpacked by a launch of its own, here
-    const bool defer_unpack = f->unpack_pending && n == 1 && !use_split && proj_only && f != m;
+    // (decided once the kernel is known, below); every other reader gets it unpacked by a launch of its own, here (inputs on the device: always here)
+    const bool defer_unpack = !reloc && f->unpack_pending && n == 1 && !use_split && proj_only && f != m;
     if (!defer_unpack) { const int urc = flush_pending(f); if (urc) return urc; }
     { const int urc = flush_pending(m); if (urc) return urc; }
     if (sp.finder == LSM2D_FINDER_PROJECTIVE) { const int lrc = ensure_lane_layout(ctx, m); if (lrc) return lrc; }
@@ -466,20 +484,27 @@ int AlignBatch::lay_out_lds() {
 
 int AlignBatch::stage_inputs() {
   // ---- inputs
-  memcpy(hs + o_pose_in, b->init_pose, sizeof(float) * 3 * (size_t) n);
-  if (b->prior) {
-    PriorDev* p = (PriorDev*) (hs + o_prior);
-    for (int i = 0; i < n; ++i) {
-      inverse_host(b->prior[i].z, p[i].z_inv); sincos_fixed(p[i].z_inv[2], p[i].sz, p[i].cz);
-      memcpy(p[i].omega, b->prior[i].omega, sizeof(float) * 9);
+  if (reloc) {
+    // inputs on the device: the host stages nothing -- b->init_pose / b->prior only say "there is one" -- and a single slot's start pose and prior cannot ride
+    // in the kernel arguments, which the host would have to know
+    if (b->prior) A.prior = (const PriorDev*) (ds + o_prior);
+    A.inline_n1 = 0;
+  } else {
+    memcpy(hs + o_pose_in, b->init_pose, sizeof(float) * 3 * (size_t) n);
+    if (b->prior) {
+      PriorDev* p = (PriorDev*) (hs + o_prior);
+      for (int i = 0; i < n; ++i) {
+        inverse_host(b->prior[i].z, p[i].z_inv); sincos_fixed(p[i].z_inv[2], p[i].sz, p[i].cz);
+        memcpy(p[i].omega, b->prior[i].omega, sizeof(float) * 9);
+      }
+      A.prior = (const PriorDev*) (ds + o_prior);
     }
-    A.prior = (const PriorDev*) (ds + o_prior);
+    // one alignment (the live tracker's call): start pose and prior ride in the kernel arguments, so the kernel's prologue does not
+    // wait for a read of host memory
+    A.inline_n1 = n == 1 && !use_split;
+    if (A.inline_n1) { memcpy(A.pose1, b->init_pose, sizeof A.pose1); if (b->prior) memcpy(&A.prior1, hs + o_prior, sizeof A.prior1); }
   }
   if (groups) memcpy(hs + o_gtab, groups->table.data(), groups->table_bytes());
-  // one alignment (the live tracker's call): start pose and prior ride in the kernel arguments, so the kernel's prologue does not
-  // wait for a read of host memory
-  A.inline_n1 = n == 1 && !use_split;
-  if (A.inline_n1) { memcpy(A.pose1, b->init_pose, sizeof A.pose1); if (b->prior) memcpy(&A.prior1, hs + o_prior, sizeof A.prior1); }
   // the stream this batch's own operations go to: its lane's when it was begun asynchronously (lane_stream) -- not for the split path (one workspace per context).
   // Everything queued so far went to the context's stream (set preparation: pending preprocessing, trees, lane copies): an
   // event behind it orders the lane's stream and the pre-kernels' stream
@@ -491,11 +516,19 @@ int AlignBatch::stage_inputs() {
   // Round 5: a batch that comes again with the SAME input block (start poses, index arrays; no priors) while nothing else has touched the lane's scratch needs no
   // upload: the blit and the wait behind it are 8 us of a 0.77 ms step (kernel trace: copy 2.4 us + 5.6 us until k_align starts).  Compared byte for byte against a
   // host-side shadow of what was uploaded last -- up to 64 KB; a sweep's index arrays beyond that are uploaded as before.
-  same_inputs = !zero_copy && !out_work && !b->prior && had_inputs && in_bytes <= (64u << 10) && L->inputs_shadow.size() == in_bytes &&
-                           !memcmp(L->inputs_shadow.data(), hs, in_bytes);
-  if (!zero_copy && !same_inputs) {
-    HIPCHK(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, pre));
-    if (!out_work && !b->prior && in_bytes <= (64u << 10)) L->inputs_shadow.assign((const unsigned char*) hs, (const unsigned char*) hs + in_bytes); else L->inputs_shadow.clear();
+  if (reloc) {
+    // inputs on the device: the block is written where it lies, on the stream of what goes ahead of the estimate and the aligner.  The host holds no copy of it:
+    // nothing to compare, nothing to upload, and no shadow for a later batch to compare against
+    same_inputs = false;
+    L->inputs_shadow.clear();
+    const int rrc = reloc_stage_inputs(); if (rrc) return rrc;
+  } else {
+    same_inputs = !zero_copy && !out_work && !b->prior && had_inputs && in_bytes <= (64u << 10) && L->inputs_shadow.size() == in_bytes &&
+                             !memcmp(L->inputs_shadow.data(), hs, in_bytes);
+    if (!zero_copy && !same_inputs) {
+      HIPCHK(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, pre));
+      if (!out_work && !b->prior && in_bytes <= (64u << 10)) L->inputs_shadow.assign((const unsigned char*) hs, (const unsigned char*) hs + in_bytes); else L->inputs_shadow.clear();
+    }
   }
   L->inputs_valid = !zero_copy && !L->inputs_shadow.empty();
   A.init_pose = (const float*) (ds + o_pose_in);
@@ -579,10 +612,12 @@ int AlignBatch::make_placement() {
       for (int s = 0; s < ns; ++s) {
         const unsigned long long id[4] = {b->fixed[s]->uid, b->fixed[s]->version, b->moving[s]->uid, b->moving[s]->version};
         mix(id, sizeof id); mix(&b->slices[s], sizeof(lsm2d_slice_params));
-        if (b->fixed_index) mix(b->fixed_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
-        if (b->moving_index) mix(b->moving_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
+        if (b->fixed_index && !reloc) mix(b->fixed_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
+        if (b->moving_index && !reloc) mix(b->moving_index + (size_t) s * n, sizeof(int32_t) * (size_t) n);
       }
-      const bool reuse = ctx->estimate_reuse && notes && L->order_valid && L->order_key == key && L->order_poses.size() == 3 * (size_t) n &&
+      // (inputs made on the device: the host cannot tell whether they are a batch it has placed before -- the estimate runs, behind the kernel that writes the
+      // poses on the same stream, and what it leaves in d_order is nobody's to keep)
+      const bool reuse = !reloc && ctx->estimate_reuse && notes && L->order_valid && L->order_key == key && L->order_poses.size() == 3 * (size_t) n &&
                          !memcmp(L->order_poses.data(), b->init_pose, sizeof(float) * 3 * (size_t) n);
       // A batch begun while another one is in flight starts on the slots that one's tail leaves free -- wherever they are: the launch balances itself as a batch
       // of many dispatch rounds does, and what is left of the placement's gain (2 % with a kept order) is less than the estimate's own chip time when it has to be made
@@ -607,8 +642,8 @@ int AlignBatch::make_placement() {
         }
         ctx->last_cull_estimate = 1;
         // (kept only once it was made WITH notes: the first call of a shape orders by the round-3 assumption, the second by what the first really did)
-        L->order_valid = notes; L->order_key = key;
-        if (notes) L->order_poses.assign(b->init_pose, b->init_pose + 3 * (size_t) n);
+        L->order_valid = notes && !reloc; L->order_key = key;
+        if (notes && !reloc) L->order_poses.assign(b->init_pose, b->init_pose + 3 * (size_t) n);
       }
       A.order = L->d_order;
       if (packed) A.order2 = L->d_order + kPackOrder2At;      // (kept with the order: a batch that comes again with the same start poses finds both)
@@ -625,7 +660,7 @@ int AlignBatch::launch() {
     HIPCHK(ctx, hipStreamWaitEvent(ks, ctx->ev_main, 0));
   }
   HIPCHK(ctx, join_pre_stream(ctx, ks));      // whatever the second stream holds for this batch (its start poses, its estimate) comes first
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L->ev0, ks));
+  if (ctx->kernel_timing && !reloc) HIPCHK(ctx, hipEventRecord(L->ev0, ks));      // (lsm2d_relocalize_select: the bracket was begun by the stage in front, on its lane)
   if (use_split) {
     // workspace: global canvases + running pose / flags, grown on demand and kept by the context
     const size_t can_bytes = sizeof(u64) * 2 * (size_t) fcan_total * (size_t) n;
@@ -706,7 +741,7 @@ int AlignBatch::launch() {
 }
 
 int AlignBatch::hand_over() {
-  if (select) return groups ? select_finish_grouped() : select_finish();
+  if (select) return reloc ? reloc_finish() : (groups ? select_finish_grouped() : select_finish());
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
   P.ctx = ctx; P.lane = L;

@@ -584,18 +584,18 @@ struct SelectLayout {
   }
 };
 
-// The selection's launches over rows of format Row, behind the scoring on the same stream; `de`: the selection's part of the scratch.  Ends the timing
-// bracket, queues the one copy down to `h_down`, waits (the one wait of the call) and checks the counters.  A (rows, n_items, k, thresholds) is the caller's.
+// The selection's launches over rows of format Row, behind the scoring on the same stream; `de`: the selection's part of the scratch; `down`: where the
+// region that goes down is written (select_queue: de + E.e_down; lsm2d_relocalize_select: next to the second stage's, so that one copy takes both).  Waits
+// for nothing, copies nothing.  A (rows, n_items, k, thresholds) is the caller's.
 template <class Row>
-static int select_queue(lsm2d_context* ctx, const char* who, SelectArgs A, const SelectLayout& E, char* de, char* h_down) {
-  Lane& L = lane(ctx);
+static int select_launches(lsm2d_context* ctx, SelectArgs A, const SelectLayout& E, char* de, int32_t* down) {
   const size_t n = E.n, K = E.K;
   u64* key[2] = {(u64*) de, (u64*) (de + E.e_key_b)}; int32_t* idx[2] = {(int32_t*) (de + E.e_idx_a), (int32_t*) (de + E.e_idx_b)};
   A.keys = key[0]; A.index = idx[0]; A.n_accepted = (int32_t*) (de + E.e_acc);
   if (n <= (size_t) kSelectTile) {      // one tile: keys, sort and gather in one launch of one workgroup
     int32_t sort_size = 2;
     while ((size_t) sort_size < n) sort_size <<= 1;
-    hipLaunchKernelGGL(k_select_tile_one<Row>, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, (int32_t*) (de + E.e_down));
+    hipLaunchKernelGGL(k_select_tile_one<Row>, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, down);
   } else {
     HIPCHK(ctx, hipMemsetAsync(A.n_accepted, 0, sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(k_select_keys<Row>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
@@ -607,8 +607,17 @@ static int select_queue(lsm2d_context* ctx, const char* who, SelectArgs A, const
       src ^= 1; m = tiles * K;
       if (tiles == 1) break;
     }
-    hipLaunchKernelGGL(k_select_gather<Row>, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], (int32_t*) (de + E.e_down));
+    hipLaunchKernelGGL(k_select_gather<Row>, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], down);
   }
+  return LSM2D_SUCCESS;
+}
+
+// ... and the rest of a select call: the launches above, the end of the timing bracket, the one copy down to `h_down`, the wait (the one wait of the call) and
+// the check of the counters.
+template <class Row>
+static int select_queue(lsm2d_context* ctx, const char* who, SelectArgs A, const SelectLayout& E, char* de, char* h_down) {
+  Lane& L = lane(ctx);
+  { const int rc = select_launches<Row>(ctx, A, E, de, (int32_t*) (de + E.e_down)); if (rc) return rc; }
   HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
   HIPCHK(ctx, hipMemcpyAsync(h_down, de + E.e_down, E.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
   HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
@@ -697,13 +706,11 @@ static int score_aligner_head(lsm2d_context* ctx, const char* who, const lsm2d_b
   return LSM2D_SUCCESS;
 }
 
-// Everything from the index rules to k_score_combine: leaves the combined rows on the device (ds + Y.o_comb), waits for nothing, has begun the timing
-// bracket; the caller ends it.  n_alignments > 0 and score_aligner_head have been checked.
-static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y,
-                               const void* up_extra = nullptr, size_t up_extra_bytes = 0) {
+// every refusal of score_aligner_queue, which makes them first: the index rules per slice, then what the slices' finders need (lsm2d_relocalize_select makes
+// them ahead of its second stage's preparation as well)
+static int score_aligner_refusals(lsm2d_context* ctx, const char* who, const lsm2d_batch* b) {
   const int ns = b->n_slices; const int32_t n_items = b->n_alignments; const size_t n = (size_t) n_items;
   if (!b->init_pose) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
-  // every refusal first: the index rules per slice, then what the slices' finders need
   for (int s = 0; s < ns; ++s) {
     const lsm2d_cloudset* f = b->fixed[s]; const lsm2d_cloudset* m = b->moving[s];
     const int32_t* fi = b->fixed_index ? b->fixed_index + (size_t) s * n : nullptr; const int32_t* mi = b->moving_index ? b->moving_index + (size_t) s * n : nullptr;
@@ -722,6 +729,17 @@ static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_
     if (!make_projk(sp.projector, &pk)) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: bad projector", who);
     if ((long long) (sizeof(u64) * 2) * (long long) pk.cols > (long long) ctx->max_dyn_lds) return failf(ctx, LSM2D_CAPACITY_EXCEEDED, "%s: canvases do not fit LDS", who);
   }
+  return LSM2D_SUCCESS;
+}
+
+// Everything from the index rules to k_score_combine: leaves the combined rows on the device (ds + Y.o_comb), waits for nothing, has begun the timing
+// bracket; the caller ends it.  n_alignments > 0 and score_aligner_head have been checked.
+// (chained: lsm2d_relocalize_select's stage 1 -- the caller has made the refusals already, an O(n_slices x n) pass over the index tables that is not made
+// twice, and has begun a timing bracket of its own in front of the call, which runs to its final selection)
+static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y,
+                               const void* up_extra = nullptr, size_t up_extra_bytes = 0, bool chained = false) {
+  const int ns = b->n_slices; const int32_t n_items = b->n_alignments; const size_t n = (size_t) n_items;
+  if (!chained) { const int rc = score_aligner_refusals(ctx, who, b); if (rc) return rc; }
   FindBatchLaunch P[kMaxSlices]; int32_t slot[kMaxSlices]; int32_t slot_max = 1;
   for (int s = 0; s < ns; ++s) {
     long long need = 0;
@@ -772,7 +790,7 @@ static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_
   }
   hipLaunchKernelGGL(k_score_aligner_items, dim3((unsigned) ((n + 255) / 256), (unsigned) ns), dim3(256), 0, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());
-  for (int s = 0; s < ns; ++s) { const int rc = score_slice_queue(ctx, P[s], b->slices + s, n, per_group, slot[s], D[s], s == ns - 1); if (rc) return rc; }
+  for (int s = 0; s < ns; ++s) { const int rc = score_slice_queue(ctx, P[s], b->slices + s, n, per_group, slot[s], D[s], !chained && s == ns - 1); if (rc) return rc; }
   hipLaunchKernelGGL(k_score_combine, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
   return LSM2D_SUCCESS;
 }

@@ -21,6 +21,8 @@
 //                      (lsm2d_*_select_grouped; lsm2d_k_select_grouped.h).
 //   k_score_aligner_items / k_score_combine  hypotheses scored against a whole aligner: per-slice item tables from the poses, and the slices' rows combined with
 //                      the skip rule and the prior into one row per item (lsm2d_score_aligner_batch / _select; lsm2d_k_score_aligner.h).
+//   k_reloc_items / k_align_rows_live  the scoring's selection turned into the aligner's input block on the device, and k_align_rows for a batch whose tail
+//                      is padding (lsm2d_relocalize_select; lsm2d_k_relocalize.h).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"
@@ -64,5 +66,6 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_finder.h"
 #include "lsm2d_k_mapping.h"
 #include "lsm2d_k_layout.h"
+#include "lsm2d_k_relocalize.h"
 
 }  // namespace lsm2d
