@@ -140,9 +140,18 @@ LSM2D_DEV void project_cloud_list_blk_t(const float4* __restrict__ lane_xy, int 
     if (t < nsteps) pair(va, idx);
   }
 }
-// The build's pass over the unit list's points: project_cloud_list_t's loads and index arithmetic, every point handed to f(px, py, index) pair by pair
-template <int kStride, class F>
-LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_steps, int tid, int nthreads, const uint16_t* units, int n_units, int B, F f) {
+// The build's pass over the unit list's points: project_cloud_list_t's loads, index arithmetic and two-buffer look-ahead (two steps per trip, the buffers swapping
+// roles, the scalar offset advancing unconditionally); every step's pair of points is handed to f(ax, ay, bx, by, t), t the step inside the unit (points 2 t and
+// 2 t + 1 of it), and behind a unit's last step end(index of the unit's first point) is called.  The last trip's look-ahead reads one row past the block -- the next
+// block's, the next cloud's, or one of the two spare rows ensure_lane_layout() keeps behind the last cloud: the addresses the stream of the same unit has just read,
+// and nothing past them -- and is never used.
+// The loop over units is the WAVE's, not the lane's: the lanes of a wave hold consecutive entries, so the wave runs trips while its first lane has one, and a lane
+// without an entry takes an empty unit (no step, so f is never called for it; its first load reads the cloud's first row, which exists: the list is not empty) and
+// arrives at end() with the others.  end() is therefore reached by all 64 lanes of a wave together, once per trip, behind the reconvergence of the step loop: it may
+// use cross-lane operations over the full wave.  No barrier stands inside, so waves with different trip counts cannot wait for each other.
+static constexpr int kCandSegSteps = 16;      // steps between two end()s: two bits per step fill the 32-bit mask cand_collect_t keeps per lane (B is 14 at 100k points)
+template <int kStride, class F, class E>
+LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_steps, int tid, int nthreads, const uint16_t* units, int n_units, int B, F f, E end) {
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   const unsigned long long pb = reinterpret_cast<unsigned long long>(lane_xy);
   const unsigned pb_hi = (unsigned) __builtin_amdgcn_readfirstlane((int) (pb >> 32));
@@ -150,45 +159,67 @@ LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_step
   float4* ubase = reinterpret_cast<float4*>(((unsigned long long) pb_hi << 32) | (unsigned long long) pb_lo);
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ubase, (short) 0, 0x7fffffff, 0x00020000);
   const int row_bytes = nthreads * (int) sizeof(float4);
-  for (int k = tid; k < n_units; k += kStride) {
-    const int code = (int) units[k];
+  const int lane = tid & 63;
+  for (int kw = __builtin_amdgcn_readfirstlane(tid - lane); kw < n_units; kw += kStride) {
+    const bool have = kw + lane < n_units;
+    const int code = have ? (int) units[kw + lane] : 0;
     const int g = code & 511, t0 = (code >> 9) * B;
-    const int nsteps = T_steps - t0 < B ? T_steps - t0 : B;
-    const int voff = g * (int) sizeof(float4) + t0 * row_bytes;
-    int idx = 2 * (g * T_steps + t0);
-    for (int t = 0; t < nsteps; ++t, idx += 2) {
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + t * row_bytes, 0, 0);
-      f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), idx);
+    const int usteps = !have ? 0 : T_steps - t0 < B ? T_steps - t0 : B;
+    // (a unit of more than kCandSegSteps steps -- a cloud of more than 7 x 16 x 1024 points -- is taken in segments, each with its own end(): B is the wave's, so is the trip count)
+    for (int s0 = 0; s0 < B; s0 += kCandSegSteps) {
+      const int nsteps = usteps - s0 < kCandSegSteps ? usteps - s0 : kCandSegSteps;      // <= 0: nothing of this lane's, the first row again
+      const int voff = nsteps > 0 ? g * (int) sizeof(float4) + (t0 + s0) * row_bytes : 0;
+      auto load = [&](int soff) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0); };
+      auto pair = [&](const u32x4& w, int t) { f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), t); };
+      int t = 0, soff = 0;
+      u32x4 va = load(0);
+      for (; t + 2 <= nsteps; t += 2) {
+        const u32x4 vb = load(soff + row_bytes);
+        pair(va, t);
+        soff += 2 * row_bytes;
+        va = load(soff);
+        pair(vb, t + 1);
+      }
+      if (t < nsteps) pair(va, t);
+      end(2 * (g * T_steps + t0 + s0));
     }
   }
 }
 // Build, the pass behind the stream: every point against the rule; the kept indices are appended to `cand` (any order serves: the z-buffer's minimum does not depend on it) through
-// one LDS counter, a wave's keeps of a step in one add.  The counter goes on counting past `cap`: the caller sees the overflow there and does not use the list.
+// one LDS counter, a wave's keeps of a unit in one add.  The counter goes on counting past `cap`: the caller sees the overflow there and does not use the list.
+// Inside a unit a lane only notes what it keeps -- bit 2 t + j of its mask for point j of step t, no cross-lane operation in the step (a lane keeps about 3 of its
+// 80 points) -- and behind the unit's last step the wave appends once: cand_for_each_pair brings all 64 lanes to end() together (a lane without a unit with an empty
+// mask), so the inclusive scan of the lanes' popcounts (wave_sum63_i's DPP tree: every lane is its source's equal in EXEC) has the wave's total in lane 63, lane 0
+// adds it to the counter when it is not zero -- a wave-uniform branch -- and every lane writes the indices of its set bits from base + (its scan - its popcount) on,
+// while the position is inside the capacity.  Every kept point is counted exactly once, in the total of its own wave and unit.
+LSM2D_DEV int wave_sum63_i(int v);      // (with the wave reductions, further down lsm2d_device.h)
 template <bool kGuarded, int kStride>
 LSM2D_DEV void cand_collect_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, int tid, int nthreads, const uint16_t* units, int n_units, int B,
                               const uint32_t* blk, uint32_t* cand, int cap, int* count, float m_t, float m_th) {
   const Iso T = Tin; const ProjK P = Pin;
   const float tn2 = __builtin_fabsf(T.tx) + __builtin_fabsf(T.ty) + 2.0f * m_t;
-  auto keeps = [&](float px, float py) -> bool {
-    float r, md; int col;
-    const int cl = cand_classify<kGuarded>(T, P, px, py, m_t, m_th, tn2, r, md, col);
-    if (cl != 2) return cl == 1;
-    return !(__uint_as_float(blk[col]) < r - md);
-  };
-  cand_for_each_pair<kStride>(lane_xy, T_steps, tid, nthreads, units, n_units, B, [&](float ax, float ay, float bx, float by, int idx) {
-    const bool k0 = keeps(ax, ay), k1 = keeps(bx, by);
-    const u64 b0 = __ballot(k0), b1 = __ballot(k1);
-    const u64 act = b0 | b1;
-    if (act) {
-      const int n0 = __popcll(b0);
+  // (a step's two points are classified first and their columns' blockers read side by side, one LDS round trip for the pair instead of one inside each point's
+  // branch; a point that is not interior reads word 0 -- blk[] has a word per column -- and does not look at it: the rule's comparison as before)
+  unsigned mask = 0;
+  cand_for_each_pair<kStride>(lane_xy, T_steps, tid, nthreads, units, n_units, B, [&](float ax, float ay, float bx, float by, int t) {
+    float r0, md0, r1, md1; int col0, col1;
+    const int cl0 = cand_classify<kGuarded>(T, P, ax, ay, m_t, m_th, tn2, r0, md0, col0);
+    const int cl1 = cand_classify<kGuarded>(T, P, bx, by, m_t, m_th, tn2, r1, md1, col1);
+    const float b0 = __uint_as_float(blk[cl0 == 2 ? col0 : 0]), b1 = __uint_as_float(blk[cl1 == 2 ? col1 : 0]);
+    const bool k0 = cl0 == 2 ? !(b0 < r0 - md0) : cl0 == 1, k1 = cl1 == 2 ? !(b1 < r1 - md1) : cl1 == 1;
+    mask |= ((k0 ? 1u : 0u) | (k1 ? 2u : 0u)) << (2 * t);
+  }, [&](int idx0) {
+    const int n = __popc(mask);
+    const int incl = wave_sum63_i(n);
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    if (total) {
       int base = 0;
-      if ((int) __builtin_amdgcn_mbcnt_hi((unsigned) (act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) act, 0u)) == 0 && (k0 || k1)) base = atomicAdd(count, n0 + __popcll(b1));      // the first keeping lane
-      base = __builtin_amdgcn_readlane(base, __builtin_amdgcn_readfirstlane(__builtin_ctzll(act)));
-      const int p0 = base + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (b0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) b0, 0u));
-      const int p1 = base + n0 + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (b1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) b1, 0u));
-      if (k0 && p0 < cap) cand[p0] = (uint32_t) idx;
-      if (k1 && p1 < cap) cand[p1] = (uint32_t) (idx + 1);
+      if ((tid & 63) == 0) base = atomicAdd(count, total);
+      int pos = __builtin_amdgcn_readfirstlane(base) + incl - n;
+      for (unsigned m = mask; m; m &= m - 1, ++pos)
+        if (pos < cap) cand[pos] = (uint32_t) (idx0 + __builtin_ctz(m));
     }
+    mask = 0;
   });
 }
 // Use: the iteration's stream while the list is valid.  Thread t takes entries t, t + kStride, ...: the 8-byte point gathered from the cloud by its index (the
