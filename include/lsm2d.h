@@ -247,6 +247,10 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   dispatch round of alignments (4 x the CUs: what the lists shorten is the tail a few long alignments leave on an emptying chip), a moving cloud of at most 48 points
  *   per entry of room (a denser map's lists do not fit), no other batch in flight when it is begun, and room in LDS beside four workgroups per CU.  Every other batch
  *   runs exactly as without the option.  0: no lists.
+ * "cand_queue" (default 1): how a list is built.  1: the iteration that builds it tests every point it streams against the blocker its column has at that moment and
+ *   notes the points that test cannot drop yet -- about a quarter of them on a 100k-point map -- in a queue in device memory; the list is then collected from the
+ *   queue.  0: from the streamed points once more.  The list is the same set, and every result keeps its bits.  "cand_queue_cap" (default and largest value 16384;
+ *   0 .. 16384): the queue's entries per alignment (4 bytes each, allocated for batches that get lists only); a build that notes more falls back to 0's pass.
  * "balance" (default 1): batches of 257 .. 4096 culled alignments are placed on the chip by estimated work (one small launch ahead of k_align; a
  *   batch run again with unchanged sets and start poses keeps its placement: get "last_cull_estimate"); 0: workgroup i runs alignment i.
  * "fast_forward" (0, 1 or 2; default 2): k_align and its packed, narrow and reference-order forms stop iterating once the pose repeats.  One Gauss-Newton
@@ -265,8 +269,8 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   per point, whenever squared pixel distance and point index pack into 31 bits), 1 = always the per-pixel gather build; identical maps.
  * "kd_lds_nodes" (default 1536): nodes of the fixed cloud's KD-tree a k_align workgroup keeps in LDS (its top levels).
  * Read-only (lsm2d_get_option): "last_align_path" (1 k_align, 2 split, 3 slice pair), "last_query_cull", "last_cull_estimate", "last_cand_builds" / "last_cand_iterations" /
- *   "last_cand_overflows" (the latest aligner call that asked for statistics: candidate lists built, iterations a list served, lists too long
- *   to be used; a call without statistics hands no counter over and leaves them as they were), "last_kd_levels",
+ *   "last_cand_overflows" / "last_cand_fallbacks" (the latest aligner call that asked for statistics: candidate lists built, iterations a list served, lists too long
+ *   to be used, builds whose queue was too short; a call without statistics hands no counter over and leaves them as they were), "last_kd_levels",
  *   "last_kd_nodes", "last_kernel_clock_khz", "last_workgroup_lifetime_ns", "max_dyn_lds", "uploads" (host-to-device cloud uploads queued so far:
  *   lsm2d_cloudset_create / _upload / lsm2d_preprocess_scans_refill), "last_h2d_bytes", "experiments" (1: this library was built with
  *   -DLSM2D_EXPERIMENTS and also knows the A/B knobs of DESIGN.md App. A; the shipped library: 0). */
@@ -597,7 +601,7 @@ int lsm2d_align_batch(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, c
  * The check that every alignment's workgroup reported is made on the device (the fourth header word): non-zero is LSM2D_DEVICE_ERROR, as for
  * lsm2d_align_batch.  The call is synchronous (there is no begin / wait form); with one batch in flight it works on the free lane like every other call.
  * "kernel_timing" / lsm2d_last_kernel_ms cover the aligner's launch PLUS the packing and the selection behind it.  The read-only options
- * "last_cand_builds" / "last_cand_iterations" / "last_cand_overflows" are derived from arrays that stay on the device here: after this call they keep
+ * "last_cand_builds" / "last_cand_iterations" / "last_cand_overflows" / "last_cand_fallbacks" are derived from arrays that stay on the device here: after this call they keep
  * the previous call's values. */
 int lsm2d_align_select(lsm2d_context* ctx, const lsm2d_aligner_params* aligner, const lsm2d_batch* batch,
                        const lsm2d_select_params* select, int32_t k,

@@ -33,6 +33,7 @@ struct Lane {
   // pinned host staging + device scratch, grown on demand (ensure_stage / ensure_scratch)
   void* h_stage = nullptr; size_t h_stage_bytes = 0; void* h_stage_dev = nullptr;
   void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
+  void* d_cand_queue = nullptr; size_t d_cand_queue_bytes = 0;                // k_align_cand's queue of maybes (AlignArgs::cand_queue): device scratch of its own, so that only a batch with candidate lists allocates it
   int32_t* d_order = nullptr;                                                // [4096] the placement the latest estimate made: kept for the next run of the SAME batch (order_valid / order_key / order_poses)
   bool order_valid = false; unsigned long long order_key = 0; std::vector<float> order_poses;      // the placement d_order holds: which batch it was made for
   // what the lane's device scratch holds as a batch's INPUT block (start poses, index arrays), byte for byte, while nothing else has used the scratch since: a batch
@@ -101,6 +102,9 @@ struct lsm2d_context {
   int cand_cap = 3328;         // entries a list may hold (32-bit point indices in LDS; a longer one is not used); the host lowers it to the room there is
   int cand_first_it = 3;       // the first iteration (counted from 0) that may build a list
   int cand_max_builds = 2;     // lists an alignment may build
+  int cand_queue = 1;          // 1: a build collects from the queue of the points its stream could not drop; 0: from the unit list once more (A/B switch)
+  int cand_queue_cap = 16384;  // the queue's room per alignment (32-bit point indices in device memory); a build with more maybes collects from the unit list.  0: every build does
+  int last_cand_fallbacks = 0; // ... and the builds that outgrew the queue
   int last_cand_builds = 0, last_cand_iterations = 0, last_cand_overflows = 0;      // the latest batch that asked for statistics: lists built, iterations served by one, lists too long to use
   int kd_wg_max_points = 16384; // KD-tree build: clouds of at most this many points are built by ONE launch, a workgroup per cloud walking the levels itself (k_kd_build_wg); 0: the level loop for all (A/B knob; same trees)
   int kd_wide_min_points = 1024;   // KD-tree build of larger clouds: levels whose evenly split nodes would hold at least this many points run a workgroup per node (0: a wave per node always; A/B knob)
@@ -438,6 +442,7 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
   for (Lane& L : c->lanes) {
     if (L.h_stage) (void) hipHostFree(L.h_stage);
     if (L.d_scratch) (void) hipFree(L.d_scratch);
+    if (L.d_cand_queue) (void) hipFree(L.d_cand_queue);
     if (L.d_order) (void) hipFree(L.d_order);
     for (hipEvent_t e : {L.ev0, L.ev1, L.ev_done}) if (e) (void) hipEventDestroy(e);
   }
@@ -490,6 +495,8 @@ const OptionDesc kOptions[] = {
   {"cand_cap",           &lsm2d_context::cand_cap,           1, 8192,       0},
   {"cand_first_it",      &lsm2d_context::cand_first_it,      1, 0x3fffffff, 0},
   {"cand_max_builds",    &lsm2d_context::cand_max_builds,    0, 127,        0},
+  {"cand_queue",         &lsm2d_context::cand_queue,         0, 1,          0},
+  {"cand_queue_cap",     &lsm2d_context::cand_queue_cap,     0, 16384,      0},      // (32 trips of the 512 threads: what one keep mask per lane covers in cand_collect_queue_t)
   // ---- read-only
   {"last_align_path",    &lsm2d_context::last_align_path,    0, 0, kOptReadOnly},
   {"last_align_width",   &lsm2d_context::last_align_width,   0, 0, kOptReadOnly},
@@ -497,6 +504,7 @@ const OptionDesc kOptions[] = {
   {"last_cand_builds",     &lsm2d_context::last_cand_builds,     0, 0, kOptReadOnly},
   {"last_cand_iterations", &lsm2d_context::last_cand_iterations, 0, 0, kOptReadOnly},
   {"last_cand_overflows",  &lsm2d_context::last_cand_overflows,  0, 0, kOptReadOnly},
+  {"last_cand_fallbacks",  &lsm2d_context::last_cand_fallbacks,  0, 0, kOptReadOnly},
   {"max_dyn_lds",        &lsm2d_context::max_dyn_lds,        0, 0, kOptReadOnly},      // bytes of LDS one workgroup may ask for
   {"uploads",            &lsm2d_context::uploads,            0, 0, kOptReadOnly},      // host-to-device cloud uploads this context has queued so far (lsm2d_cloudset_create / _upload)
   {"last_cull_estimate", &lsm2d_context::last_cull_estimate, 0, 0, kOptReadOnly},      // 1: the latest aligner call launched the placement's estimate; 0: it reused the order of an unchanged prepared batch, or needed none
@@ -614,6 +622,14 @@ static int ensure_scratch(lsm2d_context* ctx, Lane& L, size_t bytes) {
   return LSM2D_SUCCESS;
 }
 static int ensure_scratch(lsm2d_context* ctx, size_t bytes) { return ensure_scratch(ctx, lane(ctx), bytes); }
+// the lane's queue of maybes (k_align_cand): grown on demand like the scratch, never cleared -- a region is read only up to what its alignment has just written
+static int ensure_cand_queue(lsm2d_context* ctx, Lane& L, size_t bytes) {
+  if (bytes <= L.d_cand_queue_bytes) return LSM2D_SUCCESS;
+  if (L.d_cand_queue) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(L.d_cand_queue)); L.d_cand_queue = nullptr; L.d_cand_queue_bytes = 0; }
+  HIPCHK(ctx, hipMalloc(&L.d_cand_queue, bytes));
+  L.d_cand_queue_bytes = bytes;
+  return LSM2D_SUCCESS;
+}
 
 // ---- the rest of the host side, by subject (one translation unit: they share the context, the cloud sets and the helpers above) ----
 #include "lsm2d_capi_cloudsets.inc"

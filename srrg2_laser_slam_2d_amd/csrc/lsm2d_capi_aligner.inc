@@ -189,7 +189,7 @@ int AlignBatch::validate_and_lay_out_scratch() {
   // in-kernel clock stamps of ~32 workgroups spread over the grid (timed k_align launches only)
   clock_stride = ctx->clock_stride > 0 ? ctx->clock_stride : (n / 32 > 1 ? n / 32 : 1), n_clock = (n + clock_stride - 1) / clock_stride;
   o_clock = ctx->kernel_timing ? take(sizeof(unsigned long long) * 4 * (size_t) n_clock) : 0;
-  o_cand = out_stats ? take(sizeof(int32_t) * (size_t) n) : 0;      // the candidate lists' books, one word per alignment (AlignArgs::cand_out): with the statistics only
+  o_cand = out_stats ? take(sizeof(int32_t) * 2 * (size_t) n) : 0;      // the candidate lists' books, [2][n] words (AlignArgs::cand_out: every alignment's books, then its builds that fell back from the queue): with the statistics only
   out_bytes = off - o_pose;      // what travels back to the host
   o_work = take(sizeof(int32_t) * (size_t) n);                                                     // balanced placement: the estimate's counts (device only)
   // "fast_forward" 2: H and inlier count of every alignment's last kFfRing iterations (device only; 640 bytes per alignment; needs no clearing: a row is read only after its alignment wrote it)
@@ -442,6 +442,12 @@ int AlignBatch::lay_out_lds() {
         A.cand_off = (int32_t) at; A.cand_cap = (int32_t) cap; lds = with;
         A.cand_first_it = ctx->cand_first_it; A.cand_max_builds = ctx->cand_max_builds;
         A.cand_mt = 1e-6f * (float) ctx->cand_margin_um; A.cand_mth = 1e-6f * (float) ctx->cand_margin_urad;
+        // Round 30: the queue of maybes, "cand_queue_cap" entries per alignment in device memory of the lane's (at most one dispatch round of 16 384: 64 MB); "cand_queue" 0: none
+        A.cand_qcap = ctx->cand_queue ? ctx->cand_queue_cap : -1;
+        if (A.cand_qcap > 0) {
+          const int qrc = ensure_cand_queue(ctx, *L, sizeof(uint32_t) * (size_t) n * (size_t) A.cand_qcap); if (qrc) return qrc;
+          A.cand_queue = (uint32_t*) L->d_cand_queue;
+        }
       }
     }
   }
@@ -560,7 +566,7 @@ int AlignBatch::stage_inputs() {
     // host memset of 4 n bytes; on the device for the paths that copy -- and one that is still unwritten after the wait turns the call into LSM2D_DEVICE_ERROR
     if (host_results) memset(hs + o_status, 0xFF, sizeof(int32_t) * (size_t) n);
     else HIPCHK(ctx, hipMemsetAsync(ds + o_status, 0xFF, sizeof(int32_t) * (size_t) n, ks));
-    if (out_stats) { if (host_results) memset(hs + o_cand, 0, sizeof(int32_t) * (size_t) n); else HIPCHK(ctx, hipMemsetAsync(ds + o_cand, 0, sizeof(int32_t) * (size_t) n, ks)); }      // (the paths without lists write nothing there)
+    if (out_stats) { if (host_results) memset(hs + o_cand, 0, sizeof(int32_t) * 2 * (size_t) n); else HIPCHK(ctx, hipMemsetAsync(ds + o_cand, 0, sizeof(int32_t) * 2 * (size_t) n, ks)); }      // (the paths without lists write nothing there)
   }
   ctx->last_align_path = use_split ? 2 : (use_pair ? 3 : 1);
   return LSM2D_SUCCESS;
@@ -890,8 +896,9 @@ static int align_batch_finish(lsm2d_pending& P, float* out_pose, float* out_H, i
   if (out_last_pose) memcpy(out_last_pose, hs + o_last_pose, sizeof(float) * 3 * (size_t) n);
   if (P.want_stats) {      // the candidate lists' books of this batch (align_body's s_cand_stat: iterations served | lists built << 16 | of which too long << 24)
     const uint32_t* cw = (const uint32_t*) (hs + P.o_cand);
-    long long its = 0, builds = 0, over = 0;
-    for (int i = 0; i < n; ++i) { its += cw[i] & 0xFFFFu; builds += (cw[i] >> 16) & 0xFFu; over += cw[i] >> 24; }
+    long long its = 0, builds = 0, over = 0, fell = 0;
+    for (int i = 0; i < n; ++i) { its += cw[i] & 0xFFFFu; builds += (cw[i] >> 16) & 0xFFu; over += cw[i] >> 24; fell += cw[n + i]; }
+    ctx->last_cand_fallbacks = (int) std::min(fell, (long long) 0x7fffffff);
     ctx->last_cand_iterations = (int) std::min(its, (long long) 0x7fffffff); ctx->last_cand_builds = (int) std::min(builds, (long long) 0x7fffffff); ctx->last_cand_overflows = (int) std::min(over, (long long) 0x7fffffff);
   }
   if (stamps) {     // median over the stamped workgroups: shader cycles per 10 ns tick of the constant 100 MHz counter

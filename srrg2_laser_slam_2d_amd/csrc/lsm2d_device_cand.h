@@ -1,4 +1,4 @@
-// lsm2d_device_cand.h -- the candidate lists of the culled projective stream (k_align_cand): the rule and its proof, the build iteration's stream with its blockers, the collect pass, the gather that serves a list, and the test that a list still holds.
+// lsm2d_device_cand.h -- the candidate lists of the culled projective stream (k_align_cand): the rule and its proof, the build iteration's stream with its blockers, the collect pass over the unit list and the one over the queue of maybes, the gather that serves a list, and the test that a list still holds.
 // Part of lsm2d_device.h (included there, inside namespace lsm2d, at the place this text was cut from); not a header of its own.
 // ---- Round 20: CANDIDATE lists -- the second, tighter level of the kept lists ----------------------------------------------------------------
 // Once the pose has settled an iteration still streams the whole unit list (some 41 k points on configs[1]) to keep one winner per column.  A candidate list,
@@ -78,8 +78,19 @@ LSM2D_DEV int cand_classify(const Iso& T, const ProjK& P, float px, float py, fl
 //    (ranges are clamped to [1e-15, 1e18] m), and a point with a coordinate that is not finite has an r2 that fails the gate here and class 0 there;
 //  * inside the branches r, th, u and col are made by the functions cand_classify calls, on the same operands, with the same kGuarded, and T is the slice's T0;
 //  * a point outside them was never interior, so it never touched blk[].
-template <bool kGuarded>
-LSM2D_DEV void project_point_stream_blk(const Iso& T, const ProjK& P, float px, float py, int idx, u64* canvas, uint32_t* blk, const int* par) {
+// kQueue (the build with "cand_queue" 1): the PROVISIONAL test.  The function says whether the point is a MAYBE -- whether the collect still has to look at it --
+// and everything it does not call a maybe is SETTLED: dropped by the rule (above) whatever the rest of the stream brings.
+//  * a class-2 point whose column held, before this point's own entry, a blocker `old` with old < r - md (`old` is what the atomic minimum returns; the all-ones
+//    start word is a NaN, the comparison fails, the point stays a maybe).  Blockers only fall: the word the collect reads behind the barrier is the minimum over
+//    every entry, `old` among them, and positive floats order like their patterns, so final <= old < r - md in float order -- the very comparison cand_collect_t
+//    makes, on the same r and md (made by the same functions on the same operands: the list above), with a smaller left side: the point is dropped there too;
+//  * a point with a coordinate that is not finite: class 0 by cand_classify's first line.  (It also keeps the padding slots' indices, which lie behind the
+//    cloud's last point, out of the queue: the collect over the queue gathers its points from the cloud itself.)
+// Every other streamed point is a maybe: class 2 against a blocker that does not beat it yet, class 1 inside the gates, and every point outside the stream's own
+// gates, whose class the stream does not know.  A maybe gets the full rule from cand_collect_queue_t -- cand_classify and the final blocker, as cand_collect_t
+// applies them -- so kept = (maybes the rule keeps) = (streamed points the rule keeps): the list is the same SET as the pass over the unit list makes.
+template <bool kGuarded, bool kQueue>
+LSM2D_DEV bool project_point_stream_blk(const Iso& T, const ProjK& P, float px, float py, int idx, u64* canvas, uint32_t* blk, const int* par) {
   float qx, qy;
   xf_point(T, px, py, qx, qy);
   const float r2 = __builtin_fmaf(qx, qx, qy * qy);
@@ -96,9 +107,14 @@ LSM2D_DEV void project_point_stream_blk(const Iso& T, const ProjK& P, float px, 
       const float m_t = __int_as_float(par[4]), m_th = __int_as_float(par[5]);
       const float tn2 = __builtin_fabsf(T.tx) + __builtin_fabsf(T.ty) + 2.0f * m_t;
       float md;
-      if (cand_classify_polar(P, r, th, u, col, m_t, m_th, tn2, md) == 2) atomicMin(&blk[col], __float_as_uint(r + md));
+      if (cand_classify_polar(P, r, th, u, col, m_t, m_th, tn2, md) == 2) {
+        const uint32_t old = atomicMin(&blk[col], __float_as_uint(r + md));
+        if (kQueue) return !(__uint_as_float(old) < r - md);
+      }
     }
+    return kQueue;
   }
+  return kQueue && __builtin_fabsf(px) < __builtin_huge_valf() && __builtin_fabsf(py) < __builtin_huge_valf();
 }
 // project_cloud_list_t for the build iteration: the same loads, the same two-buffer look-ahead, project_point_stream_blk for project_point_stream
 template <bool kGuarded, int kStride>
@@ -124,8 +140,8 @@ LSM2D_DEV void project_cloud_list_blk_t(const float4* __restrict__ lane_xy, int 
       return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
     };
     auto pair = [&](const float4& v, int i) {
-      project_point_stream_blk<kGuarded>(T, P, v.x, v.y, i, canvas, blk, par);
-      project_point_stream_blk<kGuarded>(T, P, v.z, v.w, i + 1, canvas, blk, par);
+      project_point_stream_blk<kGuarded, false>(T, P, v.x, v.y, i, canvas, blk, par);
+      project_point_stream_blk<kGuarded, false>(T, P, v.z, v.w, i + 1, canvas, blk, par);
     };
     int t = 0, soff = 0;
     float4 va = load(0);
@@ -150,7 +166,7 @@ LSM2D_DEV void project_cloud_list_blk_t(const float4* __restrict__ lane_xy, int 
 // arrives at end() with the others.  end() is therefore reached by all 64 lanes of a wave together, once per trip, behind the reconvergence of the step loop: it may
 // use cross-lane operations over the full wave.  No barrier stands inside, so waves with different trip counts cannot wait for each other.
 static constexpr int kCandSegSteps = 16;      // steps between two end()s: two bits per step fill the 32-bit mask cand_collect_t keeps per lane (B is 14 at 100k points)
-template <int kStride, class F, class E>
+template <int kStride, bool kIdx = false, class F, class E>
 LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_steps, int tid, int nthreads, const uint16_t* units, int n_units, int B, F f, E end) {
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   const unsigned long long pb = reinterpret_cast<unsigned long long>(lane_xy);
@@ -170,7 +186,10 @@ LSM2D_DEV void cand_for_each_pair(const float4* __restrict__ lane_xy, int T_step
       const int nsteps = usteps - s0 < kCandSegSteps ? usteps - s0 : kCandSegSteps;      // <= 0: nothing of this lane's, the first row again
       const int voff = nsteps > 0 ? g * (int) sizeof(float4) + (t0 + s0) * row_bytes : 0;
       auto load = [&](int soff) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0); };
-      auto pair = [&](const u32x4& w, int t) { f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), t); };
+      auto pair = [&](const u32x4& w, int t) {
+        if constexpr (kIdx) f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), t, 2 * (g * T_steps + t0 + s0));      // (kIdx: and the index end() will get)
+        else f(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w), t);
+      };
       int t = 0, soff = 0;
       u32x4 va = load(0);
       for (; t + 2 <= nsteps; t += 2) {
@@ -244,6 +263,7 @@ LSM2D_DEV void project_candidates_t(const float2* __restrict__ mxy, const Iso& T
 // the column's interior points of r + md(r), as bits (positive floats order like their patterns) -- the list behind them; capacity and margins are read from
 // k_align's s_cand_par (LDS) here and now.  The barriers are everybody's: cand_clear_blockers and one in front of the stream; the stream (made in the same pass
 // as the canvas: project_cloud_list_blk), one more, then cand_collect (it does not look at the canvas, so it may stand in front of the bin walk).
+// With "cand_queue" 1 the stream is project_cloud_list_blkq and the pass behind the barrier cand_collect_queue (round 30, further down); cand_collect is then the fallback.
 LSM2D_HD int cand_blocker_words(int cols) { return (cols + 3) & ~3; }
 template <int kStride>
 LSM2D_DEV void cand_clear_blockers(const ProjK& P, int tid, uint32_t* blk) { for (int c = tid; c < P.cols; c += kStride) blk[c] = 0xFFFFFFFFu; }
@@ -260,6 +280,95 @@ LSM2D_DEV void cand_collect(const float4* lane_xy, int T_steps, const Iso& T, co
   uint32_t* cand = blk + cand_blocker_words(P.cols);
   if (P.tiny_ok) cand_collect_t<false, kStride>(lane_xy, T_steps, T, P, tid, kChunks, units, n_units, B, blk, cand, cap, count, m_t, m_th);
   else cand_collect_t<true, kStride>(lane_xy, T_steps, T, P, tid, kChunks, units, n_units, B, blk, cand, cap, count, m_t, m_th);
+}
+// ---- Round 30: the QUEUE of maybes ("cand_queue" 1) -- the collect looks at the points the build's stream could not settle, not at the unit list again ----
+// The build iteration's stream on cand_for_each_pair's wave-owned unit loop (the units a lane takes are the ones project_cloud_list_blk_t gives it: entry tid, tid +
+// kStride, ...; the canvas and the blockers are minima, no order matters).  A lane notes its maybes (project_point_stream_blk<., true>) in its mask, bit 2 t + j as
+// cand_collect_t notes its keeps, and behind the unit the wave appends their indices to the alignment's region of the queue in device memory with cand_collect_t's
+// end(): one scan, one add to the LDS counter `qcount`, stores while the position is below `qcap`.  The counter runs on past qcap: the caller sees it there and lets
+// cand_collect make the list from the unit list (what the queue holds then is never read).  `queue` and `qcap` are read from LDS here and now, once per unit.
+template <bool kGuarded, int kStride>
+LSM2D_DEV void project_cloud_list_blkq_t(const float4* __restrict__ lane_xy, int T_steps, const Iso& Tin, const ProjK& Pin, u64* canvas, int tid, int nthreads,
+                                         const uint16_t* units, int n_units, int B, uint32_t* blk, const int* par, int* qcount, uint32_t* const* qptr) {
+  const Iso T = Tin; ProjK P = Pin;
+  asm volatile("" : "+v"(P.K01));
+  unsigned mask = 0;
+  cand_for_each_pair<kStride, true>(lane_xy, T_steps, tid, nthreads, units, n_units, B, [&](float ax, float ay, float bx, float by, int t, int idx0) {
+    const bool m0 = project_point_stream_blk<kGuarded, true>(T, P, ax, ay, idx0 + 2 * t, canvas, blk, par);
+    const bool m1 = project_point_stream_blk<kGuarded, true>(T, P, bx, by, idx0 + 2 * t + 1, canvas, blk, par);
+    mask |= ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << (2 * t);
+  }, [&](int idx0) {
+    const int n = __popc(mask);
+    const int incl = wave_sum63_i(n);
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    if (total) {
+      int base = 0;
+      if ((tid & 63) == 0) base = atomicAdd(qcount, total);
+      const int qcap = __builtin_amdgcn_readfirstlane(par[6]);
+      const unsigned long long qb = reinterpret_cast<unsigned long long>(*qptr);
+      uint32_t* queue = reinterpret_cast<uint32_t*>(((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (qb >> 32)) << 32) |
+                                                    (unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) qb));
+      // (through a buffer resource over the region's qcap words: the pointer read back from LDS has no address space the compiler knows, a plain store through
+      // it is a FLAT one -- and with a flat access pending the stream's loads lose their look-ahead, every wait for one becomes a wait for all)
+      const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(queue, (short) 0, qcap > 0 ? qcap * (int) sizeof(uint32_t) : 0, 0x00020000);
+      int pos = __builtin_amdgcn_readfirstlane(base) + incl - n;
+      for (unsigned m = mask; m; m &= m - 1, ++pos)
+        if (pos < qcap) __builtin_amdgcn_raw_buffer_store_b32((unsigned) (idx0 + __builtin_ctz(m)), qrs, pos * (int) sizeof(uint32_t), 0, 0);
+    }
+    mask = 0;
+  });
+}
+template <int kStride>
+LSM2D_DEV void project_cloud_list_blkq(const float4* __restrict__ lane_xy, int T_steps, const Iso& T, const ProjK& P, u64* canvas, int tid, int nthreads,
+                                       const uint16_t* units, int n_units, int B, uint32_t* blk, const int* par, int* qcount, uint32_t* const* qptr) {
+  if (P.tiny_ok) project_cloud_list_blkq_t<false, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B, blk, par, qcount, qptr);
+  else project_cloud_list_blkq_t<true, kStride>(lane_xy, T_steps, T, P, canvas, tid, nthreads, units, n_units, B, blk, par, qcount, qptr);
+}
+// The collect over the queue's nq <= qcap <= 32 kStride entries (behind the barrier that ends the stream: the blockers are final, the queue is written).  Thread t
+// takes entries t, t + kStride, ... -- project_candidates_t's shape: the 8-byte point gathered from the cloud by its index, the next entry's on its way -- and applies
+// cand_collect_t's rule word for word: cand_classify, the column's blocker for a class-2 point, the same comparison.  The keep of trip i is bit i of ONE mask (at
+// most 32 trips: the host bounds qcap), and behind the loop the wave appends once, as cand_collect_t's end() does: scan, one add to the counter, which goes on
+// counting past `cap`, guarded stores -- of the entries themselves, read back from the queue (a lane keeps about three).  Every lane of the wave reaches the scan.
+template <bool kGuarded, int kStride>
+LSM2D_DEV void cand_collect_queue_t(const float2* __restrict__ mxy, const Iso& Tin, const ProjK& Pin, int tid, const uint32_t* queue, int nq,
+                                    const uint32_t* blk, uint32_t* cand, int cap, int* count, float m_t, float m_th) {
+  const Iso T = Tin; const ProjK P = Pin;
+  const float tn2 = __builtin_fabsf(T.tx) + __builtin_fabsf(T.ty) + 2.0f * m_t;
+  // (the queue through a buffer resource over its nq entries, as the stream wrote it: no flat access)
+  const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(queue), (short) 0, nq * (int) sizeof(uint32_t), 0x00020000);
+  auto entry = [&](int k) { return (int) __builtin_amdgcn_raw_buffer_load_b32(qrs, k * (int) sizeof(uint32_t), 0, 0); };
+  unsigned mask = 0;
+  if (tid < nq) {
+    int k = tid;
+    float2 p = mxy[entry(k)];
+    for (unsigned bit = 1u; k < nq; k += kStride, bit <<= 1) {
+      const int kn = k + kStride;
+      const float2 pn = mxy[entry(kn < nq ? kn : k)];
+      float r, md; int col;
+      const int cl = cand_classify<kGuarded>(T, P, p.x, p.y, m_t, m_th, tn2, r, md, col);
+      const float b = __uint_as_float(blk[cl == 2 ? col : 0]);
+      if (cl == 2 ? !(b < r - md) : cl == 1) mask |= bit;
+      p = pn;
+    }
+  }
+  const int n = __popc(mask);
+  const int incl = wave_sum63_i(n);
+  const int total = __builtin_amdgcn_readlane(incl, 63);
+  if (total) {
+    int base = 0;
+    if ((tid & 63) == 0) base = atomicAdd(count, total);
+    int pos = __builtin_amdgcn_readfirstlane(base) + incl - n;
+    for (unsigned m = mask; m; m &= m - 1, ++pos)
+      if (pos < cap) cand[pos] = (uint32_t) entry(tid + kStride * __builtin_ctz(m));
+  }
+}
+template <int kStride>
+LSM2D_DEV void cand_collect_queue(const float2* mxy, const Iso& T, const ProjK& P, int tid, const uint32_t* queue, int nq, uint32_t* blk, const int* par, int* count) {
+  const int cap = __builtin_amdgcn_readfirstlane(par[1]);
+  const float m_t = __int_as_float(__builtin_amdgcn_readfirstlane(par[4])), m_th = __int_as_float(__builtin_amdgcn_readfirstlane(par[5]));
+  uint32_t* cand = blk + cand_blocker_words(P.cols);
+  if (P.tiny_ok) cand_collect_queue_t<false, kStride>(mxy, T, P, tid, queue, nq, blk, cand, cap, count, m_t, m_th);
+  else cand_collect_queue_t<true, kStride>(mxy, T, P, tid, queue, nq, blk, cand, cap, count, m_t, m_th);
 }
 // has the transform N stayed within (m_t, m_th) of L, with room for what this fp32 evaluation can be off by?  (begin_iteration's expression for s_rebuild; the proof above)
 LSM2D_DEV bool cand_pose_within(const Iso& N, const Iso& L, float m_t, float m_th) {

@@ -69,8 +69,13 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
   __shared__ Iso s_cand_iso;
   __shared__ int s_cand_n, s_cand_state, s_cand_stat;
   // ... and the launch's arguments for it, read back from here by whoever needs them: as kernel arguments they were loop invariants, scalar registers held -- and
-  // spilled into vector registers -- across the loops.  Words: offset (0: no lists), capacity, first iteration, lists per alignment | margins (floats)
-  __shared__ int s_cand_par[6];
+  // spilled into vector registers -- across the loops.  Words: offset (0: no lists), capacity, first iteration, lists per alignment | margins (floats) | the room
+  // of the queue of maybes in entries (-1: "cand_queue" 0, the collect pass over the unit list)
+  __shared__ int s_cand_par[7];
+  // Round 30, the queue of maybes (lsm2d_device_cand.h): this alignment's region of AlignArgs::cand_queue, the maybes the build's stream counted (past the room if
+  // it must: the build then falls back to the pass over the unit list), and the builds that fell back -- thread 0's, handed over with the books
+  __shared__ uint32_t* s_cand_q;
+  __shared__ int s_cand_qn, s_cand_fb;
   uint16_t* l_units = reinterpret_cast<uint16_t*>(smem + A.units_off);      // [n_slices][kCullBlocks * kAlignBlock]
   float* l_rec = reinterpret_cast<float*>(smem + (kSeq ? A.seq_off : 0));   // kSeq: [kSeqHalf][kSeqFields]: half a trip's pair records
   // "fast_forward" (AlignArgs::fast_forward): the poses the last kFfRing iterations STARTED at, as bit patterns, in a ring (slot = pushes & (kFfRing - 1)); how
@@ -162,6 +167,8 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     for (int s = 0; s < kMaxSlices; ++s) s_rebuild[s] = 1;      // no list yet
     if (kCand) {
     s_cand_n = 0; s_cand_state = 0; s_cand_stat = 0;
+    s_cand_qn = 0; s_cand_fb = 0; s_cand_par[6] = A.cand_qcap;
+    s_cand_q = A.cand_queue ? A.cand_queue + (size_t) a * (size_t) (A.cand_qcap > 0 ? A.cand_qcap : 0) : nullptr;
     s_cand_par[0] = A.cand_off; s_cand_par[1] = A.cand_cap; s_cand_par[2] = A.cand_first_it; s_cand_par[3] = A.cand_max_builds;
     s_cand_par[4] = __float_as_int(A.cand_mt); s_cand_par[5] = __float_as_int(A.cand_mth);
     }
@@ -419,10 +426,23 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
               uint32_t* blk = reinterpret_cast<uint32_t*>(smem + __builtin_amdgcn_readfirstlane(s_cand_par[0]));
               cand_clear_blockers<kW>(S.proj, tid, blk);
               __syncthreads();
-              if (n_units > 0) project_cloud_list_blk<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B, blk, s_cand_par);
+              // Round 30 ("cand_queue" 1: qcap >= 0): the stream also queues the points its provisional blockers could not settle, and (b) looks at those
+              // alone -- unless they outgrew the queue's room (a wave-uniform read behind the barrier): then (b) is the pass over the unit list, as with "cand_queue" 0
+              const int qcap = __builtin_amdgcn_readfirstlane(s_cand_par[6]);
+              if (qcap < 0) { if (n_units > 0) project_cloud_list_blk<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B, blk, s_cand_par); }
+              else if (n_units > 0) project_cloud_list_blkq<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B, blk, s_cand_par, &s_cand_qn, &s_cand_q);
               __syncthreads();
               LSM2D_PH_CAND(1);
-              cand_collect<kW, kAlignBlock>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, tid, units, n_units, B, blk, s_cand_par, &s_cand_n);
+              const int nq = __builtin_amdgcn_readfirstlane(s_cand_qn);
+              if (qcap > 0 && nq <= qcap) {
+                const unsigned long long qb = reinterpret_cast<unsigned long long>(s_cand_q);
+                const uint32_t* queue = reinterpret_cast<const uint32_t*>(((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (qb >> 32)) << 32) |
+                                                                          (unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) qb));
+                cand_collect_queue<kW>(S.moving.xy + S.moving.start[mc], T, S.proj, tid, queue, nq, blk, s_cand_par, &s_cand_n);
+              } else {
+                if (qcap >= 0 && tid == 0) ++s_cand_fb;
+                cand_collect<kW, kAlignBlock>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, tid, units, n_units, B, blk, s_cand_par, &s_cand_n);
+              }
               LSM2D_PH_CAND(4);
             } else {
               if (n_units > 0) project_cloud_list<kW>(S.moving.lane_xy + S.moving.lane_start[mc], Tm, T, S.proj, mcan, tid, kAlignBlock, units, n_units, B);
@@ -789,6 +809,8 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
         u64 dg = s_dig;
 #ifdef LSM2D_DEBUG_CAND      // diagnostics build: what the iteration did about the candidate list (s_cand_state) and the list's entries, in place of the pair digest
         if (kCand) dg = ((u64) (unsigned) s_cand_n << 32) | (u64) (unsigned) s_cand_state;
+        // ... and, of a build iteration, the maybes its stream queued (bits 2.. of the low word; none with "cand_queue" 0)
+        if (kCand && s_cand_state == 2) dg |= (u64) (unsigned) s_cand_qn << 2;
 #endif
         const int w = ln == 0 ? n_corr : ln == 1 ? n_in : ln == 2 ? n_out : ln == 3 ? __float_as_int(chi_in) : ln == 4 ? __float_as_int(chi_o) : ln == 5 ? (int) (uint32_t) dg : (int) (uint32_t) (dg >> 32);
         if (ln < 7) reinterpret_cast<int32_t*>(A.out_stats + (size_t) a * A.stats_stride + it)[ln] = w;
@@ -933,7 +955,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
               if (serves && (stat & 0xFFFF) != 0xFFFF) ++stat;      // counted where it is decided: the alignment's last iteration too
               s_cand_state = serves ? 1 : (build ? 2 : 0);
               s_cand_stat = stat;
-              if (build) s_cand_n = 0;
+              if (build) { s_cand_n = 0; s_cand_qn = 0; }
             }
           }
         }
@@ -961,7 +983,7 @@ LSM2D_DEV void align_body(const AlignArgs& A, int a_given = -1) {
     A.out_pose[3 * a + 0] = s_pose[0]; A.out_pose[3 * a + 1] = s_pose[1]; A.out_pose[3 * a + 2] = s_pose[2];
     if (A.out_H) for (int k = 0; k < 9; ++k) A.out_H[9 * a + k] = s_H[k];
     if (A.out_its) A.out_its[a] = it;
-    if (kCand && A.cand_out) A.cand_out[a] = s_cand_stat;      // (handed over only when the caller asked for statistics: the timed launch does not pay for it)
+    if (kCand && A.cand_out) { A.cand_out[a] = s_cand_stat; A.cand_out[A.n_align + a] = s_cand_fb; }      // (handed over only when the caller asked for statistics: the timed launch does not pay for it.  The second word per alignment: its builds that fell back from the queue)
     // the status goes last, behind a system-scope release: with results written straight to pinned host memory the host polls
     // this word instead of waiting for the stream (lsm2d_align_batch), and whoever sees it sees everything above
     if (stamp) {

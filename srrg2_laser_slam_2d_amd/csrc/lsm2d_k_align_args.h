@@ -91,6 +91,10 @@ struct AlignArgs {
   int32_t cand_off, cand_cap, cand_first_it, cand_max_builds;
   float   cand_mt, cand_mth;
   int32_t* cand_out;                        // (behind everything else: the kernels without lists read every older field at the offset it always had)
+  // Round 30, the queue of maybes (lsm2d_device_cand.h): cand_qcap entries of room per alignment, region a at cand_queue + a * cand_qcap (32-bit point indices, device
+  // memory the host keeps per lane, for batches with lists only); cand_qcap < 0: "cand_queue" 0.  With the queue, cand_out has a second word per alignment, at
+  // [n_align + a]: the builds that outgrew the room and made their list from the unit list.  Behind cand_out, for the reason given there
+  uint32_t* cand_queue; int32_t cand_qcap;
 };
 
 LSM2D_DEV int pick_cloud(const CloudDev& c, int a) {

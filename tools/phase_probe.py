@@ -8,7 +8,8 @@ Built with -DLSM2D_PHASE_PROBE=4 instead (pass --mode4: the library cannot say h
 barrier | everything else, and the lone workgroups are measured once more with want_stats=False: the launch bench.py times writes no statistics rows and no digest.
 With --lists5 / --lists6 (LSM2D_EXTRA_HIPCC_FLAGS="-DLSM2D_PHASE_PROBE=5 -DLSM2D_DEBUG_UNITS -DLSM2D_DEBUG_CAND", or =6) the same alignments get the candidate lists'
 columns: cycles in the unit list's plain stream | the build iteration's stream | a list-served gather (5), in a blockers pass of its own | the collect pass | unit-list
-rebuilds (6), each in all and per iteration of its kind, what is in none of them, and the entries of every list built -- inside the whole batch and alone on a CU."""
+rebuilds (6), each in all and per iteration of its kind, what is in none of them, the entries of every list built and the maybes its build queued ("cand_queue" 1; the
+streamed points beside them are units x block steps x 2, an upper bound) -- inside the whole batch and alone on a CU -- and the maybes per build over the whole batch."""
 import math, os, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -55,20 +56,22 @@ if LISTS:
     # stream, in a blockers pass of its own, in the collect pass, in a list-served gather, in unit-list rebuilds and in everything else; entries per list.
     # Mode 5 stamps plain stream | build iteration's stream | gather, mode 6 blockers pass | collect pass | unit-list rebuilds: two builds, two runs.
     its = 20
+    BLOCK_STEPS = 2 * ((((len(wl.map_points) + 1) // 2 + 511) // 512 + 13) // 14)      # cull_block_steps: steps of two points in a unit
     names = {5: ("plain stream", "build iteration's stream", "gather"), 6: ("blockers pass", "collect pass", "unit-list rebuilds")}[LISTS]
     ctx.set_option("align_path", 1); ctx.set_option("zero_copy_max", 0)
     def report(label, res, idx, n):
         life, b0, b1, b2 = stamped_abs(n)
-        state = res.stats["pair_digest_lo"].astype(np.int64); entries = res.stats["pair_digest_hi"].astype(np.int64)
+        lo = res.stats["pair_digest_lo"].astype(np.int64); entries = res.stats["pair_digest_hi"].astype(np.int64)
+        state = lo & 3; maybes = lo >> 2; streamed = 2 * BLOCK_STEPS * res.stats["n_outliers"].astype(np.int64)      # (of a build iteration: LSM2D_DEBUG_CAND; LSM2D_DEBUG_UNITS puts the unit list's length in place of the outliers)
         for j, i in enumerate(idx):
             ran = int(res.iterations[i]) if res.iterations[i] <= its else its
             st = state[i, :ran]
             n_plain, n_build, n_served = int((st == 0).sum()), int((st == 2).sum()), int((st == 1).sum())
             per = {5: (n_plain, n_build, n_served), 6: (n_build, n_build, ran)}[LISTS]
             cells = ["%s %.0f cyc in all, %d iterations, %.0f each" % (nm, b[i], k, b[i] / max(k, 1)) for nm, b, k in zip(names, (b0, b1, b2), per)]
-            print("  %s: alignment %d: lifetime %.0f cyc over %d iterations (%d plain, %d build, %d served); %s; everything else in this mode %.0f; entries per list %s (state per iteration %s)"
+            print("  %s: alignment %d: lifetime %.0f cyc over %d iterations (%d plain, %d build, %d served); %s; everything else in this mode %.0f; entries per list %s, maybes queued of at most so many streamed points per build %s (state per iteration %s)"
                   % (label, idx_names[j], life[i], ran, n_plain, n_build, n_served, "; ".join(cells), life[i] - b0[i] - b1[i] - b2[i],
-                     entries[i, :ran][st == 2].tolist(), "".join(str(int(v)) for v in st)))
+                     entries[i, :ran][st == 2].tolist(), ["%d of %d" % mv for mv in zip(maybes[i, :ran][st == 2].tolist(), streamed[i, :ran][st == 2].tolist())], "".join(str(int(v)) for v in st)))
     for _ in range(3):
         r = al.compute_batch([scans], [mp], x0, want_stats=True)
     executed = ((np.arange(r.stats.shape[1])[None, :] < r.iterations[:, None]) & ~(r.stats["chi_outliers"] < 0)).sum(1)
@@ -76,6 +79,14 @@ if LISTS:
     life = stamped_abs(len(x0))[0]
     print("mode %d, fast_forward %d, cand_lists %d: kernel %.3f ms; alignments that execute all %d iterations: %s; lifetime of all: median %.0f cyc, max %.0f cyc; lists built %d, iterations served %d"
           % (LISTS, ctx.get_option("fast_forward"), ctx.get_option("cand_lists"), r.kernel_ms, its, full.tolist(), np.median(life), life.max(), ctx.get_option("last_cand_builds"), ctx.get_option("last_cand_iterations")))
+    # the provisional test's yield over every build of the batch: maybes / streamed points per build (rows the fast-forward filled in were not executed)
+    lo_all = r.stats["pair_digest_lo"].astype(np.int64)
+    ran_all = (np.arange(r.stats.shape[1])[None, :] < r.iterations[:, None]) & ~(r.stats["chi_outliers"] < 0) & ((lo_all & 3) == 2)
+    mb = (lo_all >> 2)[ran_all]; sm = 2 * BLOCK_STEPS * r.stats["n_outliers"].astype(np.int64)[ran_all]; en = r.stats["pair_digest_hi"].astype(np.int64)[ran_all]
+    if len(mb):
+        sh = mb / np.maximum(sm, 1)
+        print("  builds with statistics rows: %d; maybes per build: min %d, median %d, p90 %d, max %d, sum %d; streamed points per build (units x block: an upper bound): median %d, sum %d; share: median %.3f, p90 %.3f, max %.3f, overall %.3f; builds with more than 16384 maybes: %d; entries per list: median %d, max %d"
+              % (len(mb), mb.min(), np.median(mb), np.percentile(mb, 90), mb.max(), mb.sum(), np.median(sm), sm.sum(), np.median(sh), np.percentile(sh, 90), sh.max(), mb.sum() / max(sm.sum(), 1), int((mb > 16384).sum()), np.median(en), en.max()))
     idx_names = full.tolist()
     report("inside the whole batch", r, full.tolist(), len(x0))
     sub = api.CloudSet(ctx, np.concatenate([wl.scan_points[wl.scan_offsets[i]:wl.scan_offsets[i + 1]] for i in full]),
