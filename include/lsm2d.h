@@ -68,7 +68,10 @@ extern "C" {
                                     lsm2d_align_select_grouped, LSM2D_SELECT_MAX_GROUP_ROWS (the three select calls per GROUP of the batch -- a fleet's
                                     candidates, the best k per robot: one call, one wait, n_groups x k rows come down);
                              (0.7.9, number unchanged: an addition only) + lsm2d_relocalize_select (lsm2d_score_aligner_select, then lsm2d_align_select
-                                    over the selected hypotheses, chained on the device: one upload, one copy down, one wait) */
+                                    over the selected hypotheses, chained on the device: one upload, one copy down, one wait);
+                             (0.7.10, number unchanged: an addition only) + lsm2d_score_grid_select, lsm2d_pose_grid, LSM2D_GRID_MAX_LEVELS,
+                                    LSM2D_GRID_MAX_ITEMS (a grid of pose hypotheses made on the device from a descriptor and scored coarse to fine:
+                                    a level's selection becomes the next level's hypotheses there; no upload of items, one copy down, one wait) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -723,6 +726,63 @@ int lsm2d_relocalize_select(lsm2d_context* ctx, const lsm2d_aligner_params* alig
                             int32_t* out_index /* [k] */, float* out_pose /* [k][3] */, float* out_H /* [k][9] or NULL */,
                             int32_t* out_iterations /* [k] or NULL */, lsm2d_iteration_stats* out_last_stats /* [k] or NULL */,
                             int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success /* or NULL */);
+
+/* ---- a pose grid scored coarse to fine in ONE call (0.7.10).  The hypotheses of ONE scan against one map are not sent up: they are made on the device
+ * from a grid descriptor -- six floats and a few integers in the kernel arguments -- scored and ranked as lsm2d_score_aligner_select scores and ranks; the
+ * k_parents best cells of a level are refined into refine[0] x refine[1] x refine[2] children each, which are the next level's hypotheses, without leaving
+ * the device; the best k of the LAST level come down.  16 x 16 x 16 cells, 64 parents and 4 x 4 x 1 children reach the resolution of a 64 x 64 x 16 grid
+ * with 5 120 scored hypotheses instead of 65 536.
+ * NOT upstream: nothing in the reference says how its relocaliser chooses hypotheses (MultiRelocalizer2D, MULTI.json:749-769).  A coarse-to-fine search is
+ * NOT the exhaustive grid: it finds the fine grid's winner only if that winner's coarse cell is among the parents kept, and can miss it.
+ * Meaning (PARITY.md section 3, item 18f), fixed by the existing calls:
+ *   spacings   s_0 = step; s_l[a] = s_(l-1)[a] / (float) refine[a]: fp32 IEEE division, made on the host once per level.
+ *   offsets    o(i, n) = (float) i - 0.5f * (float) (n - 1), exact in fp32.
+ *   coordinate base[a] + (o * s_l[a]): the product rounded to fp32, then the sum rounded to fp32 -- never fused into an fma.  theta is not wrapped.
+ *   level 0    item i = (it * ny + iy) * nx + ix, base = center, n = count; its origin is i.
+ *   level l>0  with R = rx * ry * rt, item j * R + c is child c = (ct * ry + cy) * rx + cx of parent j; parents are the previous level's selection, best
+ *              first; base = the parent's pose bit for bit as it was scored, n = refine; its origin is the parent's (the level-0 cell it descends from).
+ *   scoring    level l is, bit for bit, lsm2d_score_aligner_select over a batch of the level's REAL items (n0 at level 0, m_(l-1) * R below it), with the
+ *              generated poses as init_pose, no prior and the same cloud in every slice for every item; coarse_select and k_parents below the last level,
+ *              select and k at the last; m_l is that call's n_selected and out_level_counts[l] its {n_accepted, n_selected} -- in both values of
+ *              "sum_order", for every finder kind, for 1 .. 4 slices with sensor offsets.  n_levels == 1 is lsm2d_score_aligner_select on the level-0 grid.
+ *   pads       the device runs k_parents * R slots at every level l >= 1; the slots of parents j >= m_(l-1) are PADS that repeat parent 0's children (the
+ *              grid's centre when nothing was selected).  They are scored and paid for, as lsm2d_relocalize_select pays for its pads, and are never
+ *              accepted, counted, ranked or returned.  When m_l == 0 every deeper level still runs its slots, reports {0, 0}, the final counts are 0 and
+ *              the call succeeds: a caller who expects mostly empty selections is better served by a loop over lsm2d_score_aligner_select.
+ * fixed_cloud / moving_cloud: the ONE cloud of every slice's set that all hypotheses use (the sets may hold more: a fleet's scans and the index of the
+ * robot being relocalised); NULL: cloud 0.
+ * Outputs: row j < *out_n_selected is the j-th best hypothesis of the last level: out_pose the pose it was scored at, out_origin its level-0 cell, out_H /
+ * out_b / out_stats / out_active what lsm2d_score_aligner_select returns for it.  Positions beyond the count are not written.
+ * Refused with LSM2D_BAD_ARGUMENT before anything is launched or written: a NULL the call needs; n_slices outside [1, 4]; a cloud index out of range (the
+ * message names the slice); a count or refine below 1; k_parents outside [1, LSM2D_SELECT_MAX_K] or coarse_select NULL when n_levels > 1; n_levels outside
+ * [1, LSM2D_GRID_MAX_LEVELS]; k outside [1, LSM2D_SELECT_MAX_K]; a step that is negative, NaN or Inf; a centre that is not finite; nx * ny * nt or
+ * k_parents * R above LSM2D_GRID_MAX_ITEMS; whatever lsm2d_score_aligner_select refuses for the slices (canvases that do not fit LDS:
+ * LSM2D_CAPACITY_EXCEEDED); a batch in flight on both lanes.
+ * Cost: NO upload of items; ONE copy down -- the per-level headers, then the last level's header, k indices, k rows of 80 bytes, k poses and k origins --
+ * and ONE wait, however many levels and launch groups there are.  "kernel_timing" / lsm2d_last_kernel_ms cover everything from the first launch to the
+ * last selection.  The call is synchronous and runs on the context's stream in order. */
+#define LSM2D_GRID_MAX_LEVELS 4
+#define LSM2D_GRID_MAX_ITEMS  (1 << 18)      /* hypotheses of one level, pads included */
+typedef struct {
+  float   center[3];    /* x, y, theta of the grid's centre */
+  float   step[3];      /* level 0's spacing per axis; finite, >= 0 (0 with count > 1 is legal: duplicates) */
+  int32_t count[3];     /* level 0: nx, ny, nt, each >= 1 */
+  int32_t n_levels;     /* 1 .. LSM2D_GRID_MAX_LEVELS; level 0 is the grid, each further level refines the parents kept */
+  int32_t refine[3];    /* children per parent and axis at every further level, each >= 1; child spacing = parent spacing / refine */
+  int32_t k_parents;    /* parents kept per level below the last, 1 .. LSM2D_SELECT_MAX_K (ignored when n_levels == 1) */
+} lsm2d_pose_grid;
+
+int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, const lsm2d_slice_params* slices,
+                            const lsm2d_cloudset* const* fixed,  const int32_t* fixed_cloud  /* [n_slices] or NULL: cloud 0 */,
+                            const lsm2d_cloudset* const* moving, const int32_t* moving_cloud /* [n_slices] or NULL: cloud 0 */,
+                            const lsm2d_pose_grid* grid,
+                            const lsm2d_select_params* coarse_select /* levels below the last; may be NULL when n_levels == 1 */,
+                            const lsm2d_select_params* select, int32_t k /* the last level's test and k */,
+                            float* out_pose /* [k][3] */, int32_t* out_origin /* [k] or NULL */,
+                            float* out_H /* [k][9] or NULL */, float* out_b /* [k][3] or NULL */,
+                            lsm2d_iteration_stats* out_stats /* [k] or NULL */, int32_t* out_active /* [k] or NULL */,
+                            int32_t* out_n_selected, int32_t* out_n_accepted,
+                            int32_t* out_level_counts /* [n_levels][2] = {accepted, selected} per level, or NULL */);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

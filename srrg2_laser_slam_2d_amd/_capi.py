@@ -61,7 +61,15 @@ class SelectParamsC(C.Structure):
 
 SELECT_MAX_K = 1024      # LSM2D_SELECT_MAX_K
 SELECT_MAX_GROUP_ROWS = 1 << 18      # LSM2D_SELECT_MAX_GROUP_ROWS: n_groups x k of the grouped select calls
+GRID_MAX_LEVELS = 4      # LSM2D_GRID_MAX_LEVELS
+GRID_MAX_ITEMS = 1 << 18      # LSM2D_GRID_MAX_ITEMS: hypotheses of one level of lsm2d_score_grid_select, pads included
 SELECT_TILE = 2048       # entries a workgroup of k_select_tile sorts (kSelectTile, csrc/lsm2d_k_select.h): where the selection takes another pass
+
+
+class PoseGridC(C.Structure):
+    """lsm2d_pose_grid"""
+    _fields_ = [("center", C.c_float * 3), ("step", C.c_float * 3), ("count", C.c_int32 * 3), ("n_levels", C.c_int32), ("refine", C.c_int32 * 3),
+                ("k_parents", C.c_int32)]
 
 
 class Preprocessor(C.Structure):
@@ -154,6 +162,11 @@ SYMBOLS = [
     ("lsm2d_relocalize_select", C.c_int, [_P, C.POINTER(AlignerParams), C.POINTER(Batch), C.POINTER(SelectParamsC), C.c_int32, C.POINTER(SelectParamsC),
                                           C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # a pose grid made on the device and scored coarse to fine: (ctx, n_slices, slices, fixed, fixed_cloud, moving, moving_cloud, grid, coarse_select, select,
+    # k, out_pose, out_origin, out_H, out_b, out_stats, out_active, out_n_selected, out_n_accepted, out_level_counts)
+    ("lsm2d_score_grid_select", C.c_int, [_P, C.c_int32, C.POINTER(SliceParams), C.POINTER(C.c_void_p), _P, C.POINTER(C.c_void_p), _P, C.POINTER(PoseGridC),
+                                          C.POINTER(SelectParamsC), C.POINTER(SelectParamsC), C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), _P]),
 ]
 
 _lib = None

@@ -640,3 +640,4 @@ static int ensure_cand_queue(lsm2d_context* ctx, Lane& L, size_t bytes) {
 #include "lsm2d_capi_sweep.inc"
 #include "lsm2d_capi_select_grouped.inc"
 #include "lsm2d_capi_relocalize.inc"
+#include "lsm2d_capi_score_grid.inc"

@@ -736,9 +736,15 @@ static int score_aligner_refusals(lsm2d_context* ctx, const char* who, const lsm
 // bracket; the caller ends it.  n_alignments > 0 and score_aligner_head have been checked.
 // (chained: lsm2d_relocalize_select's stage 1 -- the caller has made the refusals already, an O(n_slices x n) pass over the index tables that is not made
 // twice, and has begun a timing bracket of its own in front of the call, which runs to its final selection)
+// (dev: lsm2d_score_grid_select's levels -- the poses were made ON THE DEVICE, at dev->o_poses inside the caller's d_extra region, and so were the constant
+// index tables where the descriptor says there are any: nothing is staged or copied up, no pass is made over the items, b->init_pose is not read.  The
+// layout is the one of dev->n_cap items whatever this level's n is, so every level of the call asks for the same scratch and finds every array in the same
+// place; always chained)
+struct ScoreDevicePoses { size_t n_cap, o_poses; };
 static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_batch* b, size_t d_extra, size_t h_down, ScoreAlignerLayout& Y,
-                               const void* up_extra = nullptr, size_t up_extra_bytes = 0, bool chained = false) {
+                               const void* up_extra = nullptr, size_t up_extra_bytes = 0, bool chained = false, const ScoreDevicePoses* dev = nullptr) {
   const int ns = b->n_slices; const int32_t n_items = b->n_alignments; const size_t n = (size_t) n_items;
+  const size_t n_lay = dev ? dev->n_cap : n;      // the arrays' stride per slice
   if (!chained) { const int rc = score_aligner_refusals(ctx, who, b); if (rc) return rc; }
   FindBatchLaunch P[kMaxSlices]; int32_t slot[kMaxSlices]; int32_t slot_max = 1;
   for (int s = 0; s < ns; ++s) {
@@ -749,26 +755,28 @@ static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_
     { const int rc = find_batch_prepare(ctx, b->slices + s, b->fixed[s], b->moving[s], 0.0f, slot[s], who, P[s]); if (rc) return rc; }
   }
   const size_t per_group = items_per_launch((size_t) slot_max, n, kLinBatchMaxItems);
-  Y = ScoreAlignerLayout(n, (size_t) ns, b->prior != nullptr, b->fixed_index != nullptr, b->moving_index != nullptr, per_group, (size_t) slot_max, d_extra, h_down,
-                         up_extra_bytes);
+  Y = ScoreAlignerLayout(n_lay, (size_t) ns, b->prior != nullptr, b->fixed_index != nullptr, b->moving_index != nullptr,
+                         dev ? items_per_launch((size_t) slot_max, n_lay, kLinBatchMaxItems) : per_group, (size_t) slot_max, d_extra, h_down, up_extra_bytes);
   { int rc = ensure_scratch(ctx, Y.d_bytes); if (rc) return rc; rc = ensure_stage(ctx, Y.h_bytes); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
-  memcpy(hs, b->init_pose, sizeof(float) * 3 * n);
-  if (up_extra_bytes) memcpy(hs + Y.o_up_extra, up_extra, up_extra_bytes);
-  if (b->prior) {
-    PriorDev* p = (PriorDev*) (hs + Y.o_prior);
-    for (size_t i = 0; i < n; ++i) {      // as the aligner stages them (AlignBatch::stage_inputs)
-      inverse_host(b->prior[i].z, p[i].z_inv); sincos_fixed(p[i].z_inv[2], p[i].sz, p[i].cz);
-      memcpy(p[i].omega, b->prior[i].omega, sizeof(float) * 9);
+  if (!dev) {
+    memcpy(hs, b->init_pose, sizeof(float) * 3 * n);
+    if (up_extra_bytes) memcpy(hs + Y.o_up_extra, up_extra, up_extra_bytes);
+    if (b->prior) {
+      PriorDev* p = (PriorDev*) (hs + Y.o_prior);
+      for (size_t i = 0; i < n; ++i) {      // as the aligner stages them (AlignBatch::stage_inputs)
+        inverse_host(b->prior[i].z, p[i].z_inv); sincos_fixed(p[i].z_inv[2], p[i].sz, p[i].cz);
+        memcpy(p[i].omega, b->prior[i].omega, sizeof(float) * 9);
+      }
     }
+    if (b->fixed_index) memcpy(hs + Y.o_fidx, b->fixed_index, sizeof(int32_t) * (size_t) ns * n);
+    if (b->moving_index) memcpy(hs + Y.o_midx, b->moving_index, sizeof(int32_t) * (size_t) ns * n);
+    HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));      // the one copy up
   }
-  if (b->fixed_index) memcpy(hs + Y.o_fidx, b->fixed_index, sizeof(int32_t) * (size_t) ns * n);
-  if (b->moving_index) memcpy(hs + Y.o_midx, b->moving_index, sizeof(int32_t) * (size_t) ns * n);
-  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));      // the one copy up
-  if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_dig, 0, sizeof(unsigned long long) * (size_t) ns * n, ctx->stream));
+  if (!ctx->sum_order) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_dig, 0, sizeof(unsigned long long) * (size_t) ns * n_lay, ctx->stream));
   ScoreAlignerArgs A;
-  A.poses = (const float*) ds; A.prior = b->prior ? (const PriorDev*) (ds + Y.o_prior) : nullptr; A.n_items = n_items; A.n_slices = ns;
+  A.poses = dev ? (const float*) (ds + Y.o_extra + dev->o_poses) : (const float*) ds; A.prior = b->prior ? (const PriorDev*) (ds + Y.o_prior) : nullptr; A.n_items = n_items; A.n_slices = ns;
   A.out = (float*) (ds + Y.o_comb);
   ScoreSliceDev D[kMaxSlices];
   for (int s = 0; s < kMaxSlices; ++s) {
@@ -777,16 +785,16 @@ static int score_aligner_queue(lsm2d_context* ctx, const char* who, const lsm2d_
     if (s >= ns) continue;
     const lsm2d_slice_params& sp = b->slices[s];
     S.f_count = b->fixed[s]->d_count; S.m_count = b->moving[s]->d_count;
-    S.f_index = b->fixed_index ? (const int32_t*) (ds + Y.o_fidx) + (size_t) s * n : nullptr;
-    S.m_index = b->moving_index ? (const int32_t*) (ds + Y.o_midx) + (size_t) s * n : nullptr;
+    S.f_index = b->fixed_index ? (const int32_t*) (ds + Y.o_fidx) + (size_t) s * n_lay : nullptr;
+    S.m_index = b->moving_index ? (const int32_t*) (ds + Y.o_midx) + (size_t) s * n_lay : nullptr;
     S.f_clouds = b->fixed[s]->n_clouds; S.m_clouds = b->moving[s]->n_clouds;
     S.has_sensor = !(sp.sensor_in_robot[0] == 0.0f && sp.sensor_in_robot[1] == 0.0f && sp.sensor_in_robot[2] == 0.0f);      // the aligner's test (fill_align_args)
     inverse_host(sp.sensor_in_robot, S.Sinv); sincos_fixed(S.Sinv[2], S.sSinv, S.cSinv);
-    S.items = (FindItem*) (ds + Y.o_items) + (size_t) s * n;
-    S.count = (const int32_t*) (ds + Y.o_cnt) + (size_t) s * n; S.rows = (const float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n;
+    S.items = (FindItem*) (ds + Y.o_items) + (size_t) s * n_lay;
+    S.count = (const int32_t*) (ds + Y.o_cnt) + (size_t) s * n_lay; S.rows = (const float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n_lay;
     S.slot = slot[s]; S.min_corr = sp.min_num_correspondences;
-    D[s] = ScoreSliceDev{S.items, (int32_t*) (ds + Y.o_cnt) + (size_t) s * n, (unsigned long long*) (ds + Y.o_dig) + (size_t) s * n,
-                         (float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n, (int32_t*) (ds + Y.o_pairs), (float*) (ds + Y.o_part), (uint32_t) s * 0x632BE5ABu};
+    D[s] = ScoreSliceDev{S.items, (int32_t*) (ds + Y.o_cnt) + (size_t) s * n_lay, (unsigned long long*) (ds + Y.o_dig) + (size_t) s * n_lay,
+                         (float*) (ds + Y.o_out) + kLinOutWords * (size_t) s * n_lay, (int32_t*) (ds + Y.o_pairs), (float*) (ds + Y.o_part), (uint32_t) s * 0x632BE5ABu};
   }
   hipLaunchKernelGGL(k_score_aligner_items, dim3((unsigned) ((n + 255) / 256), (unsigned) ns), dim3(256), 0, ctx->stream, A);
   HIPCHK(ctx, hipGetLastError());

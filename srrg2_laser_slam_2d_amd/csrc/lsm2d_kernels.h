@@ -23,6 +23,8 @@
 //                      the skip rule and the prior into one row per item (lsm2d_score_aligner_batch / _select; lsm2d_k_score_aligner.h).
 //   k_reloc_items / k_align_rows_live  the scoring's selection turned into the aligner's input block on the device, and k_align_rows for a batch whose tail
 //                      is padding (lsm2d_relocalize_select; lsm2d_k_relocalize.h).
+//   k_grid_level0 / k_grid_children / k_grid_mask_pads / k_grid_finish  a grid of pose hypotheses made on the device, a level's selection turned into the next
+//                      level's hypotheses, pads kept out of the ranking (lsm2d_score_grid_select; lsm2d_k_score_grid.h).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"
@@ -67,5 +69,6 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_mapping.h"
 #include "lsm2d_k_layout.h"
 #include "lsm2d_k_relocalize.h"
+#include "lsm2d_k_score_grid.h"
 
 }  // namespace lsm2d
