@@ -71,7 +71,11 @@ extern "C" {
                                     over the selected hypotheses, chained on the device: one upload, one copy down, one wait);
                              (0.7.10, number unchanged: an addition only) + lsm2d_score_grid_select, lsm2d_pose_grid, LSM2D_GRID_MAX_LEVELS,
                                     LSM2D_GRID_MAX_ITEMS (a grid of pose hypotheses made on the device from a descriptor and scored coarse to fine:
-                                    a level's selection becomes the next level's hypotheses there; no upload of items, one copy down, one wait) */
+                                    a level's selection becomes the next level's hypotheses there; no upload of items, one copy down, one wait);
+                             (0.7.11, number unchanged: an addition only) + lsm2d_voxelize, lsm2d_voxelize_params, LSM2D_VOXELIZE_MAX_POINTS,
+                                    LSM2D_VOXELIZE_MAX_GROUPS (PointCloud::voxelize over device-resident clouds of any size: several inputs, each moved
+                                    by a pose, voxelised per group into the clouds of a reserved set; one copy down, one wait); read-only option keys
+                                    "voxelize_tile", "voxelize_scan_tiles" */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -783,6 +787,56 @@ int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, const lsm2d_sl
                             lsm2d_iteration_stats* out_stats /* [k] or NULL */, int32_t* out_active /* [k] or NULL */,
                             int32_t* out_n_selected, int32_t* out_n_accepted,
                             int32_t* out_level_counts /* [n_levels][2] = {accepted, selected} per level, or NULL */);
+
+/* ---- voxelise and assemble device-resident clouds of any size in ONE call (0.7.11).  PointCloud::voxelize as the reference uses it --
+ * sensor_processing/raw_data_preprocessor_projective_2d.cpp:38-41 with coefficients (res, res, 1, 1), mapping/scene_clipper_projective_2d.cpp:44-48 with
+ * (res, res, 0.1, 0.1) -- which the older entry points reach only for the at most 2048 points of one scan or one clipped canvas.  Here the inputs are any
+ * clouds of a set, as large as they are: output cloud g of `dst` becomes the voxelisation of the CONCATENATION of every input k with group[k] == g, taken
+ * in the order of the call's list, each first moved by its pose.  Three uses:
+ *   a map assembled       every input in group 0, poses = the local maps' optimised poses: K local maps as one decimated cloud, no download
+ *   a fleet's maps bounded group[k] = k, dst == src, no poses: every cloud of a reserved-many set decimated in place (what keeps lsm2d_merge_scene* away
+ *                         from LSM2D_CAPACITY_EXCEEDED without a round trip through the host)
+ *   a smaller map         one input, one group: a 1M-point map made a 100k-point map -- every aligner and scoring call is linear in the map's points
+ * Meaning (PARITY.md section 3, item 17b; nothing here is new arithmetic):
+ *   transform  input k's point i becomes what lsm2d_merge_scene appends for it at measurement_in_scene = pose[k]: the point and the normal under the
+ *              isometry made from the pose, cosine and sine the deterministic ones of item 11b, no renormalisation.  pose == NULL copies the bits.
+ *   key        the four floors of x * inv_res, y * inv_res, nx * inv_rn, ny * inv_rn on the transformed values, inv = 1.0f / coefficient divided once on
+ *              the host.  The x and y floors must lie in [-32768, 32768) and the normal floors in [-16, 15]; a point that fails (NaN and Inf fail) has no
+ *              key, is dropped and is counted in out_dropped per group.
+ *   order      ascending key, then ascending concatenation index (list position, then point index).
+ *   voxel      four fp32 sums from +0 in that order, times 1.0f / (float) count; nn = sqrtf(fmaf(anx, anx, any * any)), both normal components divided
+ *              by nn when nn > 0.  Voxels come out in ascending key order.
+ *   groups     equal keys in different groups are never merged; an empty group, or one whose points were all dropped, writes a count of 0.
+ * All or nothing: if any group's voxel count exceeds its destination cloud's capacity NO destination cloud is changed, the call returns
+ * LSM2D_CAPACITY_EXCEEDED and out_counts holds the counts that would have been needed (the device decides ahead of its first write to dst).
+ * Aliasing: dst may be src and a destination cloud may be one of the inputs; the result is as if every input were read before anything is written.
+ * Refused with LSM2D_BAD_ARGUMENT before anything is launched or written: a NULL the call needs (ctx, params, src, dst, out_counts); a resolution that is
+ * not > 0 or not finite; n_inputs < 1; n_groups < 1 or above LSM2D_VOXELIZE_MAX_GROUPS; an index outside its set (with dst_index == NULL: n_groups above
+ * dst's clouds); a group value outside [0, n_groups); a destination index given twice; dst not a reserved set; more input points in all than
+ * LSM2D_VOXELIZE_MAX_POINTS; a batch in flight on the lane.
+ * Cost: the call is synchronous; the call's small tables go up, ONE copy comes down (the counts) and there is ONE wait -- plus the one fetch of sizes
+ * when a set's sizes are known to the device only (after an asynchronous clip / merge).  "kernel_timing" / lsm2d_last_kernel_ms cover the whole chain.  A
+ * voxel's sum is one thread's walk: a million points in ONE voxel is legal and slow.  Whatever dst carries derived from its points (row copies, search
+ * grids, KD-trees, distance maps, tile bounds) is invalidated as lsm2d_merge_scene invalidates it.  Read-only options "voxelize_tile" (keys per sort
+ * tile, 1024) and "voxelize_scan_tiles" (16: the tiles whose digit counters one pass of the scan's single workgroup takes; beyond 16 tiles -- 16 384 points -- the
+ * scan carries its running sum from pass to pass) describe the device side's tiling. */
+#define LSM2D_VOXELIZE_MAX_POINTS (1 << 24)      /* input points of one call, all inputs together */
+#define LSM2D_VOXELIZE_MAX_GROUPS (1 << 16)
+typedef struct lsm2d_voxelize_params {
+  float resolution;          /* x and y coefficient, > 0 (the preprocessor's / clipper's `res`) */
+  float normal_resolution;   /* nx and ny coefficient, > 0: 1 = the preprocessor's (res,res,1,1), 0.1 = the clipper's (res,res,0.1,0.1) */
+} lsm2d_voxelize_params;
+
+int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* params,
+                   const lsm2d_cloudset* src, int32_t n_inputs,
+                   const int32_t* src_index,   /* [n_inputs] or NULL: cloud k */
+                   const float* pose,          /* [n_inputs][3] (x, y, theta) or NULL: no transform at all */
+                   const int32_t* group,       /* [n_inputs], values in [0, n_groups), or NULL: all 0 */
+                   int32_t n_groups,
+                   lsm2d_cloudset* dst,
+                   const int32_t* dst_index,   /* [n_groups] or NULL: cloud g; no index twice */
+                   int32_t* out_counts,        /* [n_groups] voxels written */
+                   int32_t* out_dropped);      /* [n_groups] points that had no key, or NULL */
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -72,6 +72,17 @@ class PoseGridC(C.Structure):
                 ("k_parents", C.c_int32)]
 
 
+class VoxelizeParamsC(C.Structure):
+    """lsm2d_voxelize_params"""
+    _fields_ = [("resolution", C.c_float), ("normal_resolution", C.c_float)]
+
+
+VOXELIZE_MAX_POINTS = 1 << 24      # LSM2D_VOXELIZE_MAX_POINTS: input points of one lsm2d_voxelize call
+VOXELIZE_MAX_GROUPS = 1 << 16      # LSM2D_VOXELIZE_MAX_GROUPS
+VOXELIZE_SCAN_TILES = 16           # tiles whose counters one pass of the one-workgroup scan takes (kVoxScanTiles; read-only option "voxelize_scan_tiles")
+VOXELIZE_TILE = 1024               # keys a wave sorts as one tile (kVoxTile, csrc/lsm2d_k_voxelize.h; read-only option "voxelize_tile"): where the sort takes another tile
+
+
 class Preprocessor(C.Structure):
     _fields_ = [("n_beams", C.c_int32), ("angle_min", C.c_float), ("angle_max", C.c_float), ("range_min", C.c_float),
                 ("range_max", C.c_float), ("normal_point_distance", C.c_float), ("normal_min_points", C.c_int32),
@@ -167,6 +178,9 @@ SYMBOLS = [
     ("lsm2d_score_grid_select", C.c_int, [_P, C.c_int32, C.POINTER(SliceParams), C.POINTER(C.c_void_p), _P, C.POINTER(C.c_void_p), _P, C.POINTER(PoseGridC),
                                           C.POINTER(SelectParamsC), C.POINTER(SelectParamsC), C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), _P]),
+    # device-resident clouds voxelised per group into a reserved set: (ctx, params, src, n_inputs, src_index, pose, group, n_groups, dst, dst_index,
+    # out_counts, out_dropped)
+    ("lsm2d_voxelize", C.c_int, [_P, C.POINTER(VoxelizeParamsC), _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -31,6 +31,8 @@ from ._capi import (FINDER_NN, FINDER_PROJECTIVE, ROBUST_CAUCHY, ROBUST_NONE, Al
                     IterationStats, Lsm2dError, Prior, Projector, SliceParams, check)
 from ._capi import SELECT_MAX_K, SELECT_TILE      # noqa: F401  (LSM2D_SELECT_MAX_K; the selection's tile: where it takes another pass)
 
+from ._capi import VOXELIZE_MAX_GROUPS, VOXELIZE_MAX_POINTS      # noqa: F401  (LSM2D_VOXELIZE_MAX_POINTS / _MAX_GROUPS)
+
 STATUS_NAMES = {0: "Success", 1: "NotEnoughCorrespondences", 2: "NotEnoughInliers", 3: "SingularH"}
 
 
@@ -1627,3 +1629,57 @@ def relocalize_grid(aligner: "MultiAligner2D", fixed, moving, grid: PoseGrid, co
         return np.repeat(c[:, None], m, axis=1)
 
     return RelocalizeGridResult(scored, align_select(aligner, fixed, moving, scored.pose, sel2, kk, None, spelled(fixed_cloud), spelled(moving_cloud)))
+
+
+# ---- device-resident clouds voxelised and assembled in one call (lsm2d_voxelize) ----
+
+@dataclasses.dataclass
+class VoxelizeParams:
+    """lsm2d_voxelize_params: PointCloud::voxelize's coefficients (resolution, resolution, normal_resolution, normal_resolution).  ``normal_resolution``
+    1 is the raw-scan preprocessor's (res, res, 1, 1), 0.1 the scene clipper's (res, res, 0.1, 0.1)."""
+    resolution: float = 0.05
+    normal_resolution: float = 1.0
+
+    @classmethod
+    def preprocessor(cls, resolution: float) -> "VoxelizeParams":
+        return cls(resolution, 1.0)
+
+    @classmethod
+    def clipper(cls, resolution: float) -> "VoxelizeParams":
+        return cls(resolution, 0.1)
+
+    def struct(self) -> _capi.VoxelizeParamsC:
+        return _capi.VoxelizeParamsC(float(self.resolution), float(self.normal_resolution))
+
+
+def voxelize(ctx: Context, params: VoxelizeParams, src: CloudSet, src_index=None, poses=None, groups=None, n_groups: int = 1, dst: Optional[CloudSet] = None,
+             dst_index=None):
+    """Clouds of ``src`` voxelised on the device into the clouds of the reserved set ``dst`` in ONE call (lsm2d_voxelize): output cloud g is the voxelisation
+    of the concatenation of every input k with ``groups[k] == g`` in list order, each first moved by ``poses[k]`` (None: no transform at all).
+    ``src_index`` None: every cloud of ``src`` in order; ``groups`` None: all inputs in group 0; ``dst_index`` None: group g to cloud g.  ``dst`` None
+    reserves a set sized by the inputs (``n_groups`` clouds, each with room for every input point); ``dst`` may be ``src`` (a fleet's maps decimated in
+    place: ``groups=range(n)``, ``n_groups=n``).  Returns ``(dst, counts, dropped)``: int32 ``[n_groups]`` voxels written and points that had no key.
+    All or nothing: when a group does not fit its destination cloud nothing is written and ``Lsm2dError`` (CAPACITY_EXCEEDED) carries the needed counts
+    as ``.counts``."""
+    idx = None if src_index is None else np.ascontiguousarray(src_index, np.int32).ravel()
+    n_inputs = src.n_clouds if idx is None else len(idx)
+    ps = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(n_inputs, 3)
+    gr = None if groups is None else np.ascontiguousarray(groups, np.int32).reshape(n_inputs)
+    n_groups = int(n_groups)
+    di = None if dst_index is None else np.ascontiguousarray(dst_index, np.int32).reshape(n_groups)
+    if dst is None:
+        c = src.counts
+        room = max(int(c.sum() if idx is None else c[idx].sum()), 1)
+        dst = CloudSet.reserved(ctx, room) if n_groups == 1 else CloudSet.reserved_many(ctx, n_groups, room)
+    p = params.struct()
+    counts = np.zeros(max(n_groups, 1), np.int32); dropped = np.zeros(max(n_groups, 1), np.int32)
+    try:
+        check(ctx._lib.lsm2d_voxelize(ctx.handle, C.byref(p), src.handle, n_inputs, _ptr(idx), _ptr(ps), _ptr(gr), n_groups, dst.handle, _ptr(di), _ptr(counts),
+                                      _ptr(dropped)), "lsm2d_voxelize", ctx.handle)
+    except Lsm2dError as e:
+        e.counts, e.dropped = counts[:n_groups].copy(), dropped[:n_groups].copy()
+        raise
+    if not dst._pending:
+        c = dst._counts.copy(); c[np.arange(n_groups) if di is None else di] = counts[:n_groups]
+        dst._counts = c; dst._n_points = int(c.sum())
+    return dst, counts[:n_groups], dropped[:n_groups]

@@ -127,6 +127,7 @@ struct lsm2d_context {
   int estimate_reuse = 1;      // a prepared batch run again with unchanged start poses keeps its placement (no k_cull_estimate launch); experiments build: 0 switches that off
   int last_cull_estimate = 0;  // what the latest aligner call did about the placement's estimate ("last_cull_estimate")
   int last_query_cull = 0;     // the latest aligner call ran its point-query finder with the exact culling of the queries (k_align, tiles of 64 moving points)
+  int voxelize_tile = kVoxTile, voxelize_scan_tiles = kVoxScanTiles;      // lsm2d_voxelize's tiling, for callers and tests to read ("voxelize_tile": keys per sort tile; "voxelize_scan_tiles": the tiles one pass of the scan's workgroup takes, 16)
   long long last_kd_levels = 0, last_kd_nodes = 0;      // shape of the most recently built KD-tree set (levels of the deepest tree, nodes in all of them)
   std::vector<lsm2d_cloudset*> live_sets;      // lsm2d_destroy orphans what is left (a set destroyed after its context must not touch it)
   Lane lanes[2]; int cur = 0;            // the two lanes and which one is current (lane()): see struct Lane
@@ -509,6 +510,8 @@ const OptionDesc kOptions[] = {
   {"uploads",            &lsm2d_context::uploads,            0, 0, kOptReadOnly},      // host-to-device cloud uploads this context has queued so far (lsm2d_cloudset_create / _upload)
   {"last_cull_estimate", &lsm2d_context::last_cull_estimate, 0, 0, kOptReadOnly},      // 1: the latest aligner call launched the placement's estimate; 0: it reused the order of an unchanged prepared batch, or needed none
   {"experiments",        &lsm2d_context::experiments,        0, 0, kOptReadOnly},
+  {"voxelize_tile",       &lsm2d_context::voxelize_tile,       0, 0, kOptReadOnly},
+  {"voxelize_scan_tiles", &lsm2d_context::voxelize_scan_tiles, 0, 0, kOptReadOnly},
 #ifdef LSM2D_EXPERIMENTS
   // ---- A/B knobs of the experiments build (the GPU suite with LSM2D_EXPERIMENTS=1; each one's measurement: DESIGN App. A)
   {"cull_est_um",        &lsm2d_context::cull_est_um,        0, 1000000, kOptExperiment},
@@ -641,3 +644,4 @@ static int ensure_cand_queue(lsm2d_context* ctx, Lane& L, size_t bytes) {
 #include "lsm2d_capi_select_grouped.inc"
 #include "lsm2d_capi_relocalize.inc"
 #include "lsm2d_capi_score_grid.inc"
+#include "lsm2d_capi_voxelize.inc"

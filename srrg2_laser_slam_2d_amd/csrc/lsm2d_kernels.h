@@ -25,6 +25,9 @@
 //                      is padding (lsm2d_relocalize_select; lsm2d_k_relocalize.h).
 //   k_grid_level0 / k_grid_children / k_grid_mask_pads / k_grid_finish  a grid of pose hypotheses made on the device, a level's selection turned into the next
 //                      level's hypotheses, pads kept out of the ranking (lsm2d_score_grid_select; lsm2d_k_score_grid.h).
+//   k_vox_keys / k_vox_hist / k_vox_scan / k_vox_scatter / k_vox_head_count / k_vox_head_write / k_vox_sum / k_vox_verdict / k_vox_write / k_vox_finish
+//                      PointCloud::voxelize over device-resident clouds of any size: keys, a stable radix sort, the runs' sums in the reference's order, the
+//                      voxels to the clouds of a reserved set behind a capacity verdict made on the device (lsm2d_voxelize; lsm2d_k_voxelize.h).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"
@@ -70,5 +73,6 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_layout.h"
 #include "lsm2d_k_relocalize.h"
 #include "lsm2d_k_score_grid.h"
+#include "lsm2d_k_voxelize.h"
 
 }  // namespace lsm2d
