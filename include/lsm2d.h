@@ -75,7 +75,12 @@ extern "C" {
                              (0.7.11, number unchanged: an addition only) + lsm2d_voxelize, lsm2d_voxelize_params, LSM2D_VOXELIZE_MAX_POINTS,
                                     LSM2D_VOXELIZE_MAX_GROUPS (PointCloud::voxelize over device-resident clouds of any size: several inputs, each moved
                                     by a pose, voxelised per group into the clouds of a reserved set; one copy down, one wait); read-only option keys
-                                    "voxelize_tile", "voxelize_scan_tiles" */
+                                    "voxelize_tile", "voxelize_scan_tiles";
+                             (0.7.12, number unchanged: an addition only) + lsm2d_gridset (create / clear / upload / download / destroy),
+                                    lsm2d_grid_geometry, lsm2d_occupancy_update, lsm2d_occupancy_render, lsm2d_occupancy_render_params,
+                                    LSM2D_OCCUPANCY_MAX_SIDE / _MAX_CELLS / _MAX_RAYS / _MAX_RAY_CELLS (occupancy grids on the device: clouds ray-traced
+                                    from their sensor poses into hit / miss counts, rendered to 0 .. 100 / -1; not in the reference); read-only option
+                                    keys "occupancy_tile", "last_occupancy_wg_median_ns", "last_occupancy_wg_max_ns" */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -837,6 +842,67 @@ int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* params,
                    const int32_t* dst_index,   /* [n_groups] or NULL: cloud g; no index twice */
                    int32_t* out_counts,        /* [n_groups] voxels written */
                    int32_t* out_dropped);      /* [n_groups] points that had no key, or NULL */
+
+/* ---- occupancy grids on the device (0.7.12): scans ray-traced into hit / miss counts, and the counts rendered.  A capability of THIS build: the reference
+ * tree has no grid mapper (like the ranking order of PARITY.md section 3, item 18a and the pose pyramid of item 18f); what a planner, a fleet UI or a map
+ * server reads of a 2D laser SLAM is which cells the beams passed through and which they ended in, and the clouds and the poses are already on the device.
+ * A grid set is n_grids grids of ONE geometry; cell (cx, cy) covers [origin + c * resolution, origin + (c + 1) * resolution) on each axis and carries two
+ * uint32 counters, hits and misses, stored side by side (a cell is one 8-byte access).  Host arrays are row-major: row = cy, column = cx.
+ * lsm2d_occupancy_update mirrors lsm2d_voxelize's argument list.  Meaning (PARITY.md section 3, item 17c); everything after the transform is integers:
+ *   transform  input k's point i becomes what lsm2d_merge_scene appends for it at measurement_in_scene = pose[k]: xf_point (csrc/lsm2d_device.h) under the
+ *              isometry the host makes from the pose, cosine and sine the deterministic ones of item 11b.  pose == NULL copies the bits.  The ray starts
+ *              at the pose's translation (pose[k][0], pose[k][1]) -- (0, 0) when pose == NULL.  Normals are not read.              [item 17c.1; 17b.1; 11b]
+ *   cells      inv = 1.0f / resolution, divided once on the host; a coordinate v on an axis with origin o has the cell floorf((v - o) * inv), the
+ *              difference and the product rounded separately (never an fma).  All four cell coordinates of a ray must lie in [-2^20, 2^20) (NaN and Inf
+ *              fail) and L = max(|x1 - x0|, |y1 - y0|) must be <= LSM2D_OCCUPANCY_MAX_RAY_CELLS; a point that fails either test gives no ray and is counted
+ *              in out_dropped of its grid.                                                                                        [item 17c.2]
+ *   walk       with ax = |x1 - x0|, ay = |y1 - y0| and the signs s, s': x-major iff ax >= ay (a tie is x-major); step i = 0 .. L is the cell with the major
+ *              coordinate m0 + s i and the minor coordinate n0 + s' ((2 i a + L) / (2 L)), a the minor extent, the division integer and non-negative
+ *              (2 * 32767^2 + 32767 < 2^31); L = 0 is the single cell (x0, y0).  Steps 0 .. L - 1 add 1 to `misses` of their cell, step L adds 1 to
+ *              `hits`.  A step whose cell lies outside the grid adds nothing and the ray goes on: there is no clipping rule.  This is the incremental
+ *              error-term (Bresenham) walk: L + 1 cells, 8-connected, never more than half a cell from the ideal line on the minor axis
+ *              (tests/test_occupancy_abi.py checks all three in exact rationals).                                                [item 17c.3]
+ *   sums       counters accumulate over calls, and within a call over every input sent to the grid; they saturate at 2^32 - 1.  Integer sums have no
+ *              order: the result is unique.                                                                                       [item 17c.4]
+ * Refused with LSM2D_BAD_ARGUMENT before anything is launched or written: a NULL the call needs; a resolution that is not > 0 or not finite; a non-finite
+ * origin; a side < 1 or above LSM2D_OCCUPANCY_MAX_SIDE; n_grids < 1, or the cells of the set above LSM2D_OCCUPANCY_MAX_CELLS; n_inputs < 1; an index
+ * outside its set; a grid value outside [0, n_grids); more input points than LSM2D_OCCUPANCY_MAX_RAYS; a set of another context; a batch in flight on
+ * the lane.
+ * Cost: the call is synchronous; the small tables go up, ONE copy comes down (rays, dropped, fault word) and there is ONE wait -- plus the one fetch of
+ * sizes when the source set's sizes are known to the device only (as in lsm2d_voxelize).  "kernel_timing" / lsm2d_last_kernel_ms cover the chain; with it
+ * on, the tile workgroups' clock stamps come down in a second copy and "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns" read them
+ * (diagnostics).  Two launches: k_occ_rays (a thread per point) and k_occ_tiles (a workgroup per grid and tile of "occupancy_tile" = 64 x 64 cells,
+ * read-only, summing in LDS; no global atomics on the grid).  Tiles overlapped by many scans work longest (measured: DESIGN.md section 8).
+ * lsm2d_occupancy_render: v = hits + misses in 64 bits; v < max(min_visits, 1) gives -1 (unknown); else p = (float) hits / (float) v (IEEE division, both
+ * conversions round to nearest) and the value is (int8) rintf(100.0f * p), the product rounded once, ties to even: 0 .. 100.  One byte per cell comes down
+ * instead of eight.                                                                                                               [item 17c.6]
+ * NOT BUILT (item 17c.5): an asynchronous form; per-grid geometry; maximum-range truncation and clearing along beams without a return
+ * (a cloud holds returns only: a beam without a return clears nothing); a once-per-scan rule per cell (every ray counts); splitting a tile's work over
+ * several workgroups; log-odds with decay. */
+#define LSM2D_OCCUPANCY_MAX_SIDE      16384
+#define LSM2D_OCCUPANCY_MAX_CELLS     (1 << 28)   /* all grids of a set together: 2 GB of counters */
+#define LSM2D_OCCUPANCY_MAX_RAYS      (1 << 24)   /* input points of one update, all inputs together */
+#define LSM2D_OCCUPANCY_MAX_RAY_CELLS 32767       /* longest ray, in cells along its major axis */
+typedef struct lsm2d_grid_geometry { float origin_x, origin_y, resolution; int32_t width, height; } lsm2d_grid_geometry;
+typedef struct lsm2d_gridset lsm2d_gridset;
+
+int  lsm2d_gridset_create(lsm2d_context* ctx, const lsm2d_grid_geometry* geometry, int32_t n_grids, lsm2d_gridset** out);   /* counters zero */
+int  lsm2d_gridset_clear(lsm2d_gridset* grids, int32_t n, const int32_t* grid_index /* [n] or NULL: every grid */);           /* queued, no wait */
+int  lsm2d_gridset_upload(lsm2d_gridset* grids, int32_t grid_index, const uint32_t* hits, const uint32_t* misses);   /* host [height][width]; a NULL array leaves that counter */
+int  lsm2d_gridset_download(const lsm2d_gridset* grids, int32_t grid_index, uint32_t* out_hits, uint32_t* out_misses); /* either may be NULL */
+void lsm2d_gridset_destroy(lsm2d_gridset* grids);
+
+int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids,
+                           const lsm2d_cloudset* src, int32_t n_inputs,
+                           const int32_t* src_index,  /* [n_inputs] or NULL: cloud k */
+                           const float* pose,         /* [n_inputs][3] sensor in the grid's frame, or NULL: no transform, origin (0, 0) */
+                           const int32_t* grid,       /* [n_inputs] in [0, n_grids), or NULL: all 0 */
+                           int32_t* out_rays,         /* [n_grids] rays walked, or NULL */
+                           int32_t* out_dropped);     /* [n_grids] points that gave no ray, or NULL */
+
+typedef struct lsm2d_occupancy_render_params { int32_t min_visits; } lsm2d_occupancy_render_params;
+int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* grids, int32_t grid_index,
+                           const lsm2d_occupancy_render_params* params, int8_t* out /* host [height][width] */);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -83,6 +83,24 @@ VOXELIZE_SCAN_TILES = 16           # tiles whose counters one pass of the one-wo
 VOXELIZE_TILE = 1024               # keys a wave sorts as one tile (kVoxTile, csrc/lsm2d_k_voxelize.h; read-only option "voxelize_tile"): where the sort takes another tile
 
 
+class GridGeometryC(C.Structure):
+    """lsm2d_grid_geometry"""
+    _fields_ = [("origin_x", C.c_float), ("origin_y", C.c_float), ("resolution", C.c_float), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class OccupancyRenderParamsC(C.Structure):
+    """lsm2d_occupancy_render_params"""
+    _fields_ = [("min_visits", C.c_int32)]
+
+
+OCCUPANCY_MAX_SIDE = 16384           # LSM2D_OCCUPANCY_MAX_SIDE
+OCCUPANCY_MAX_CELLS = 1 << 28        # LSM2D_OCCUPANCY_MAX_CELLS: all grids of a set together
+OCCUPANCY_MAX_RAYS = 1 << 24         # LSM2D_OCCUPANCY_MAX_RAYS: input points of one lsm2d_occupancy_update call
+OCCUPANCY_MAX_RAY_CELLS = 32767      # LSM2D_OCCUPANCY_MAX_RAY_CELLS: longest ray, in cells along its major axis
+OCCUPANCY_TILE = 64                  # cells per side of the tile one workgroup owns (kOccTile, csrc/lsm2d_k_occupancy.h; read-only option "occupancy_tile")
+OCCUPANCY_BLOCK = 256                # input boxes a tile's workgroup tests per round (kOccBlock)
+
+
 class Preprocessor(C.Structure):
     _fields_ = [("n_beams", C.c_int32), ("angle_min", C.c_float), ("angle_max", C.c_float), ("range_min", C.c_float),
                 ("range_max", C.c_float), ("normal_point_distance", C.c_float), ("normal_min_points", C.c_int32),
@@ -181,6 +199,15 @@ SYMBOLS = [
     # device-resident clouds voxelised per group into a reserved set: (ctx, params, src, n_inputs, src_index, pose, group, n_groups, dst, dst_index,
     # out_counts, out_dropped)
     ("lsm2d_voxelize", C.c_int, [_P, C.POINTER(VoxelizeParamsC), _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    # occupancy grids: a set of hit / miss counter grids of one geometry, and clouds ray-traced into it: (ctx, grids, src, n_inputs, src_index, pose, grid,
+    # out_rays, out_dropped); the render: (ctx, grids, grid_index, params, out)
+    ("lsm2d_gridset_create", C.c_int, [_P, C.POINTER(GridGeometryC), C.c_int32, C.POINTER(_P)]),
+    ("lsm2d_gridset_clear", C.c_int, [_P, C.c_int32, _P]),
+    ("lsm2d_gridset_upload", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("lsm2d_gridset_download", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("lsm2d_gridset_destroy", None, [_P]),
+    ("lsm2d_occupancy_update", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("lsm2d_occupancy_render", C.c_int, [_P, _P, C.c_int32, C.POINTER(OccupancyRenderParamsC), _P]),
 ]
 
 _lib = None

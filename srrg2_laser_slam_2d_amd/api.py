@@ -32,6 +32,7 @@ from ._capi import (FINDER_NN, FINDER_PROJECTIVE, ROBUST_CAUCHY, ROBUST_NONE, Al
 from ._capi import SELECT_MAX_K, SELECT_TILE      # noqa: F401  (LSM2D_SELECT_MAX_K; the selection's tile: where it takes another pass)
 
 from ._capi import VOXELIZE_MAX_GROUPS, VOXELIZE_MAX_POINTS      # noqa: F401  (LSM2D_VOXELIZE_MAX_POINTS / _MAX_GROUPS)
+from ._capi import OCCUPANCY_MAX_CELLS, OCCUPANCY_MAX_RAY_CELLS, OCCUPANCY_MAX_RAYS, OCCUPANCY_MAX_SIDE      # noqa: F401  (LSM2D_OCCUPANCY_MAX_*)
 
 STATUS_NAMES = {0: "Success", 1: "NotEnoughCorrespondences", 2: "NotEnoughInliers", 3: "SingularH"}
 
@@ -1683,3 +1684,101 @@ def voxelize(ctx: Context, params: VoxelizeParams, src: CloudSet, src_index=None
         c = dst._counts.copy(); c[np.arange(n_groups) if di is None else di] = counts[:n_groups]
         dst._counts = c; dst._n_points = int(c.sum())
     return dst, counts[:n_groups], dropped[:n_groups]
+
+
+# ---- occupancy grids on the device (lsm2d_gridset, lsm2d_occupancy_update, lsm2d_occupancy_render; not in the reference, which has no grid mapper) ----
+
+@dataclasses.dataclass
+class GridGeometry:
+    """lsm2d_grid_geometry: cell (cx, cy) covers [origin + c * resolution, origin + (c + 1) * resolution) on each axis; arrays are [height][width]."""
+    origin_x: float = 0.0
+    origin_y: float = 0.0
+    resolution: float = 0.05
+    width: int = 1
+    height: int = 1
+
+    def struct(self) -> _capi.GridGeometryC:
+        return _capi.GridGeometryC(float(self.origin_x), float(self.origin_y), float(self.resolution), int(self.width), int(self.height))
+
+
+class GridSet:
+    """``n_grids`` device-resident occupancy grids of one geometry (lsm2d_gridset): two uint32 counters per cell, hits and misses, zero at creation."""
+
+    def __init__(self, ctx: Context, geometry: GridGeometry, n_grids: int = 1):
+        self._ctx, self._lib = ctx, ctx._lib
+        self.geometry, self.n_grids = geometry, int(n_grids)
+        g = geometry.struct(); h = C.c_void_p()
+        check(self._lib.lsm2d_gridset_create(ctx.handle, C.byref(g), int(n_grids), C.byref(h)), "lsm2d_gridset_create", ctx.handle)
+        self._h = h
+        ctx._sets.add(self)      # closed with its context, like a cloud set
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def shape(self) -> tuple:
+        return (int(self.geometry.height), int(self.geometry.width))
+
+    def clear(self, indices=None):
+        """Zeroes grids ``indices`` (None: every grid); queued, no wait (lsm2d_gridset_clear)."""
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
+        check(self._lib.lsm2d_gridset_clear(self._h, 0 if idx is None else len(idx), _ptr(idx)), "lsm2d_gridset_clear", self._ctx.handle)
+
+    def upload(self, grid_index: int = 0, hits=None, misses=None):
+        """Sets the counters of one grid from uint32 ``[height][width]`` arrays; None leaves that counter as it is (lsm2d_gridset_upload)."""
+        h = None if hits is None else np.ascontiguousarray(hits, np.uint32).reshape(self.shape)
+        m = None if misses is None else np.ascontiguousarray(misses, np.uint32).reshape(self.shape)
+        check(self._lib.lsm2d_gridset_upload(self._h, int(grid_index), _ptr(h), _ptr(m)), "lsm2d_gridset_upload", self._ctx.handle)
+
+    def download(self, grid_index: int = 0) -> tuple:
+        """-> (hits, misses), uint32 ``[height][width]`` (lsm2d_gridset_download)."""
+        h = np.empty(self.shape, np.uint32); m = np.empty(self.shape, np.uint32)
+        check(self._lib.lsm2d_gridset_download(self._h, int(grid_index), _ptr(h), _ptr(m)), "lsm2d_gridset_download", self._ctx.handle)
+        return h, m
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.lsm2d_gridset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def occupancy_update(ctx: Context, grids: GridSet, src: CloudSet, src_index=None, poses=None, grid=None):
+    """The points of clouds of ``src`` ray-traced into the counters of ``grids`` in ONE call (lsm2d_occupancy_update): input k's points are moved by
+    ``poses[k]`` (the sensor in the grid's frame; None: no transform, rays start at (0, 0)); each ray from the sensor's cell to the point's cell adds 1 to
+    ``misses`` of every cell before its last and 1 to ``hits`` of its last, in grid ``grid[k]`` (None: grid 0).  ``src_index`` None: every cloud of ``src``
+    in order.  Returns ``(rays, dropped)``: int32 ``[n_grids]`` rays walked and points that gave no ray."""
+    idx = None if src_index is None else np.ascontiguousarray(src_index, np.int32).ravel()
+    n_inputs = src.n_clouds if idx is None else len(idx)
+    ps = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(n_inputs, 3)
+    gr = None if grid is None else np.ascontiguousarray(grid, np.int32).reshape(n_inputs)
+    rays = np.zeros(grids.n_grids, np.int32); dropped = np.zeros(grids.n_grids, np.int32)
+    check(ctx._lib.lsm2d_occupancy_update(ctx.handle, grids.handle, src.handle, n_inputs, _ptr(idx), _ptr(ps), _ptr(gr), _ptr(rays), _ptr(dropped)),
+          "lsm2d_occupancy_update", ctx.handle)
+    return rays, dropped
+
+
+def occupancy_render(ctx: Context, grids: GridSet, grid_index: int = 0, min_visits: int = 1) -> np.ndarray:
+    """One grid as a consumer reads it (lsm2d_occupancy_render): int8 ``[height][width]``, -1 where hits + misses < max(min_visits, 1), else the share of
+    hits in percent, 0 .. 100.  Bit for bit ``occupancy_values`` of the downloaded counters."""
+    p = _capi.OccupancyRenderParamsC(int(min_visits))
+    out = np.empty(grids.shape, np.int8)
+    check(ctx._lib.lsm2d_occupancy_render(ctx.handle, grids.handle, int(grid_index), C.byref(p), _ptr(out)), "lsm2d_occupancy_render", ctx.handle)
+    return out
+
+
+def occupancy_values(hits, misses, min_visits: int = 1) -> np.ndarray:
+    """lsm2d_occupancy_render's rule in numpy float32: v = hits + misses in 64 bits; v < max(min_visits, 1) gives -1; else rint(100 * (float32(hits) /
+    float32(v))), each operation rounded once to float32, ties to even."""
+    h = np.asarray(hits, np.uint32).astype(np.uint64); v = h + np.asarray(misses, np.uint32).astype(np.uint64)
+    known = v >= np.uint64(max(int(min_visits), 1))
+    den = np.where(known, v, np.uint64(1)).astype(np.float32)
+    p = h.astype(np.float32) / den
+    val = np.rint(np.float32(100.0) * p).astype(np.int8)
+    return np.where(known, val, np.int8(-1)).astype(np.int8)

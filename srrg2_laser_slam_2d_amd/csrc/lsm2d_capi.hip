@@ -128,6 +128,9 @@ struct lsm2d_context {
   int last_cull_estimate = 0;  // what the latest aligner call did about the placement's estimate ("last_cull_estimate")
   int last_query_cull = 0;     // the latest aligner call ran its point-query finder with the exact culling of the queries (k_align, tiles of 64 moving points)
   int voxelize_tile = kVoxTile, voxelize_scan_tiles = kVoxScanTiles;      // lsm2d_voxelize's tiling, for callers and tests to read ("voxelize_tile": keys per sort tile; "voxelize_scan_tiles": the tiles one pass of the scan's workgroup takes, 16)
+  int occupancy_tile = kOccTile;      // lsm2d_occupancy_update's tiling ("occupancy_tile": cells per side of the tile one workgroup owns)
+  long long last_occ_wg_median_ns = 0, last_occ_wg_max_ns = 0;      // kernel timing on: the median and the longest lifetime of the latest update's tile workgroups that had work
+  std::vector<struct lsm2d_gridset*> live_gridsets;      // lsm2d_destroy orphans what is left, as it does live_sets
   long long last_kd_levels = 0, last_kd_nodes = 0;      // shape of the most recently built KD-tree set (levels of the deepest tree, nodes in all of them)
   std::vector<lsm2d_cloudset*> live_sets;      // lsm2d_destroy orphans what is left (a set destroyed after its context must not touch it)
   Lane lanes[2]; int cur = 0;            // the two lanes and which one is current (lane()): see struct Lane
@@ -142,6 +145,7 @@ struct lsm2d_context {
   hipEvent_t ev_main = nullptr;      // orders the lanes' streams (and the pre-kernels' stream) behind what the context's own stream holds (lane_stream)
 };
 static inline Lane& lane(lsm2d_context* ctx) { return ctx->lanes[ctx->cur]; }
+static void orphan_gridsets(lsm2d_context* ctx);      // (lsm2d_capi_occupancy.inc)
 // Side streams, created on first use with the highest priority the device has: what they carry is short, and the launch in flight holds every wave slot of the
 // chip -- the slots that come free at its end should go to the next batches' pre-kernels first, not to the 1000 long-lived workgroups of the launch queued behind it.
 static bool make_side_stream(SideStream& s) {
@@ -440,6 +444,7 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
   // that has not been waited for is the caller's to delete -- include/lsm2d.h: wait for every begun batch before lsm2d_destroy)
   (void) sync_streams(c, true);
   for (lsm2d_cloudset* cs : c->live_sets) cs->ctx = nullptr;        // still owned by the caller: destroy them any time, use them no more
+  orphan_gridsets(c);
   for (Lane& L : c->lanes) {
     if (L.h_stage) (void) hipHostFree(L.h_stage);
     if (L.d_scratch) (void) hipFree(L.d_scratch);
@@ -512,6 +517,7 @@ const OptionDesc kOptions[] = {
   {"experiments",        &lsm2d_context::experiments,        0, 0, kOptReadOnly},
   {"voxelize_tile",       &lsm2d_context::voxelize_tile,       0, 0, kOptReadOnly},
   {"voxelize_scan_tiles", &lsm2d_context::voxelize_scan_tiles, 0, 0, kOptReadOnly},
+  {"occupancy_tile",      &lsm2d_context::occupancy_tile,      0, 0, kOptReadOnly},
 #ifdef LSM2D_EXPERIMENTS
   // ---- A/B knobs of the experiments build (the GPU suite with LSM2D_EXPERIMENTS=1; each one's measurement: DESIGN App. A)
   {"cull_est_um",        &lsm2d_context::cull_est_um,        0, 1000000, kOptExperiment},
@@ -537,6 +543,7 @@ const OptionDescLL kOptionsLL[] = {      // read-only, 64-bit
   {"last_kd_levels", &lsm2d_context::last_kd_levels}, {"last_kd_nodes", &lsm2d_context::last_kd_nodes},
   {"last_kernel_clock_khz", &lsm2d_context::last_clock_khz}, {"last_workgroup_lifetime_ns", &lsm2d_context::last_wg_lifetime_ns},
   {"last_h2d_bytes", &lsm2d_context::last_h2d_bytes},
+  {"last_occupancy_wg_median_ns", &lsm2d_context::last_occ_wg_median_ns}, {"last_occupancy_wg_max_ns", &lsm2d_context::last_occ_wg_max_ns},
 };
 }  // namespace
 
@@ -645,3 +652,4 @@ static int ensure_cand_queue(lsm2d_context* ctx, Lane& L, size_t bytes) {
 #include "lsm2d_capi_relocalize.inc"
 #include "lsm2d_capi_score_grid.inc"
 #include "lsm2d_capi_voxelize.inc"
+#include "lsm2d_capi_occupancy.inc"

@@ -1,0 +1,245 @@
+// lsm2d_capi_occupancy.inc -- occupancy grids on the device: grid sets (create, clear, upload, download, destroy), lsm2d_occupancy_update (the points of
+// device-resident clouds ray-traced from their sensor poses into hit / miss counters) and lsm2d_occupancy_render (include/lsm2d.h; PARITY.md section 3,
+// item 17c; not in the reference, which has no grid mapper).  Part of lsm2d_capi.hip, included LAST: what launches the kernels of lsm2d_k_occupancy.h comes
+// behind every older kernel's first use.
+//
+// lsm2d_occupancy_update:
+//   up          the call's tables -- per input (transform, ray start, where its points begin, its grid), the concatenation offsets, the inputs' boxes as
+//               {max, max, min, min}, per grid the range of its inputs -- through the lane's pinned staging buffer into its scratch: one copy.  The inputs are
+//               listed grid by grid (a stable counting sort on the host): a tile's workgroup loops over its own grid's inputs only.
+//   the chain   k_occ_rays, k_occ_tiles -- on the context's stream in order
+//   down        [rays | dropped | fault]: ONE copy, ONE wait.  With kernel timing on the tile workgroups' clock stamps follow in a copy of their own
+//               (diagnostics: "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns").
+
+struct lsm2d_gridset {
+  lsm2d_context* ctx = nullptr;
+  lsm2d_grid_geometry geo = {};
+  int32_t n_grids = 0;
+  size_t cells_per_grid = 0;
+  uint2* d_cells = nullptr;      // [n_grids][height][width] = {hits, misses}: a cell is one 8-byte access
+};
+
+static void orphan_gridsets(lsm2d_context* ctx) { for (lsm2d_gridset* gs : ctx->live_gridsets) gs->ctx = nullptr; }
+
+extern "C" int lsm2d_gridset_create(lsm2d_context* ctx, const lsm2d_grid_geometry* geo, int32_t n_grids, lsm2d_gridset** out) {
+  static_assert(LSM2D_OCCUPANCY_MAX_SIDE == kOccMaxSide && LSM2D_OCCUPANCY_MAX_CELLS == kOccMaxCells && LSM2D_OCCUPANCY_MAX_RAYS == kOccMaxRays &&
+                LSM2D_OCCUPANCY_MAX_RAY_CELLS == kOccMaxRayCells, "the ABI's limits are the kernels'");
+  if (out) *out = nullptr;
+  if (!ctx || !geo || !out) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: null argument");
+  if (!(geo->resolution > 0.0f) || !std::isfinite(geo->resolution)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: resolution must be finite and > 0");
+  if (!std::isfinite(geo->origin_x) || !std::isfinite(geo->origin_y)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: the origin must be finite");
+  if (geo->width < 1 || geo->height < 1 || geo->width > kOccMaxSide || geo->height > kOccMaxSide)
+    return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: a side must lie in 1 .. LSM2D_OCCUPANCY_MAX_SIDE");
+  if (n_grids < 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: n_grids must be >= 1");
+  const long long per = (long long) geo->width * geo->height;
+  if (per * n_grids > (long long) kOccMaxCells) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: more cells than LSM2D_OCCUPANCY_MAX_CELLS");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  lsm2d_gridset* gs = new (std::nothrow) lsm2d_gridset;
+  if (!gs) return LSM2D_OUT_OF_MEMORY;
+  gs->geo = *geo; gs->n_grids = n_grids; gs->cells_per_grid = (size_t) per;
+  DevTmp cells;
+  { const hipError_t e = hipMalloc(&cells.p, sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids); if (e != hipSuccess) { delete gs; HIPCHK(ctx, e); } }
+  { const hipError_t e = hipMemsetAsync(cells.p, 0, sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids, ctx->stream); if (e != hipSuccess) { delete gs; HIPCHK(ctx, e); } }
+  gs->d_cells = (uint2*) cells.release();
+  gs->ctx = ctx; ctx->live_gridsets.push_back(gs);
+  *out = gs;
+  return LSM2D_SUCCESS;
+}
+
+extern "C" void lsm2d_gridset_destroy(lsm2d_gridset* gs) {
+  if (!gs) return;
+  if (gs->ctx) {
+    (void) hipSetDevice(gs->ctx->device);
+    (void) stream_sync(gs->ctx);      // a queued clear or update may still write the cells
+    auto& v = gs->ctx->live_gridsets;
+    for (size_t i = 0; i < v.size(); ++i) if (v[i] == gs) { v[i] = v.back(); v.pop_back(); break; }
+  }
+  if (gs->d_cells) (void) hipFree(gs->d_cells);
+  delete gs;
+}
+
+static bool valid_grid_index(const lsm2d_gridset* gs, int32_t i) { return gs && i >= 0 && i < gs->n_grids; }
+
+extern "C" int lsm2d_gridset_clear(lsm2d_gridset* gs, int32_t n, const int32_t* grid_index) {
+  if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_clear: null argument (or the set's context is gone)");
+  lsm2d_context* ctx = gs->ctx;
+  if (grid_index && n < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_clear: n must be >= 0");
+  if (grid_index) for (int32_t j = 0; j < n; ++j) if (!valid_grid_index(gs, grid_index[j])) return failf(ctx, LSM2D_BAD_ARGUMENT, "gridset_clear: entry %d: grid index outside the set", (int) j);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(uint2) * gs->cells_per_grid;
+  if (!grid_index) { HIPCHK(ctx, hipMemsetAsync(gs->d_cells, 0, bytes * (size_t) gs->n_grids, ctx->stream)); return LSM2D_SUCCESS; }
+  for (int32_t j = 0; j < n; ++j) HIPCHK(ctx, hipMemsetAsync(gs->d_cells + gs->cells_per_grid * (size_t) grid_index[j], 0, bytes, ctx->stream));
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_gridset_upload(lsm2d_gridset* gs, int32_t grid_index, const uint32_t* hits, const uint32_t* misses) {
+  if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_upload: null argument (or the set's context is gone)");
+  lsm2d_context* ctx = gs->ctx;
+  if (!valid_grid_index(gs, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_upload: grid index outside the set");
+  if (!hits && !misses) return LSM2D_SUCCESS;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t n = gs->cells_per_grid;
+  DevTmp planar;      // the host arrays as they are; k_occ_put interleaves them (a NULL array leaves its counter)
+  HIPCHK(ctx, hipMalloc(&planar.p, sizeof(uint32_t) * n * 2));
+  uint32_t* const dh = (uint32_t*) planar.p; uint32_t* const dm = dh + n;
+  if (hits) HIPCHK(ctx, hipMemcpyAsync(dh, hits, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+  if (misses) HIPCHK(ctx, hipMemcpyAsync(dm, misses, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+  OccPutArgs P; P.cells = gs->d_cells + n * (size_t) grid_index; P.hits = hits ? dh : nullptr; P.misses = misses ? dm : nullptr; P.n = (long long) n;
+  hipLaunchKernelGGL(k_occ_put<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, stream_sync(ctx));
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_gridset_download(const lsm2d_gridset* gs, int32_t grid_index, uint32_t* out_hits, uint32_t* out_misses) {
+  if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_download: null argument (or the set's context is gone)");
+  lsm2d_context* ctx = gs->ctx;
+  if (!valid_grid_index(gs, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_download: grid index outside the set");
+  if (!out_hits && !out_misses) return LSM2D_SUCCESS;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t n = gs->cells_per_grid;
+  std::vector<uint2> cells(n);
+  HIPCHK(ctx, hipMemcpyAsync(cells.data(), gs->d_cells + n * (size_t) grid_index, sizeof(uint2) * n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, stream_sync(ctx));
+  for (size_t c = 0; c < n; ++c) { if (out_hits) out_hits[c] = cells[c].x; if (out_misses) out_misses[c] = cells[c].y; }
+  return LSM2D_SUCCESS;
+}
+
+struct OccupancyLayout {
+  size_t u_inputs = 0, u_offset = 0, u_box = 0, u_first = 0, up_bytes = 0;      // the block that travels up (the same offsets in the staging buffer and in the scratch)
+  size_t o_down = 0, d_rays = 0, d_dropped = 0, d_fault = 0, down_bytes = 0;    // the block that travels down, cleared before the chain
+  size_t o_rays = 0, o_stamps = 0, bytes = 0;
+  OccupancyLayout(size_t n, size_t n_inputs, size_t n_grids, size_t n_workgroups) {
+    u_inputs = 0; u_offset = up256(sizeof(OccInput) * n_inputs); u_box = up256(u_offset + sizeof(int32_t) * (n_inputs + 1));
+    u_first = up256(u_box + sizeof(int32_t) * 4 * n_inputs); up_bytes = up256(u_first + sizeof(int32_t) * (n_grids + 1));
+    o_down = up_bytes;
+    d_rays = 0; d_dropped = sizeof(int32_t) * n_grids; d_fault = 2 * sizeof(int32_t) * n_grids; down_bytes = d_fault + 4 * sizeof(int32_t);
+    o_rays = up256(o_down + down_bytes);
+    o_stamps = up256(o_rays + sizeof(int4) * (n ? n : 1));
+    bytes = up256(o_stamps + sizeof(unsigned long long) * n_workgroups);
+  }
+};
+
+extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, const lsm2d_cloudset* src, int32_t n_inputs, const int32_t* src_index,
+                                      const float* pose, const int32_t* grid, int32_t* out_rays, int32_t* out_dropped) {
+  // ---- refusals: nothing is launched or written before the last of them
+  if (!ctx || !grids || !src) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: null argument");
+  if (src->ctx != ctx || grids->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: a set from another (or a destroyed) context");
+  if (n_inputs < 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: n_inputs must be >= 1");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  const int32_t n_grids = grids->n_grids;
+  for (int32_t k = 0; k < n_inputs; ++k) {
+    if (!valid_cloud_index(src, src_index ? src_index[k] : k)) return failf(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: input %d: cloud index outside the source set", (int) k);
+    if (grid && (grid[k] < 0 || grid[k] >= n_grids)) return failf(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: input %d: grid outside [0, n_grids)", (int) k);
+  }
+  // sizes the device alone knows are upper bounds on the host: a sum of bounds within the limit settles it, else the real sizes are fetched -- and they are
+  // fetched anyway before the tables are made, which hold exact offsets (as in lsm2d_voxelize)
+  long long total = 0;
+  for (int32_t k = 0; k < n_inputs; ++k) total += src->h_count[(size_t) (src_index ? src_index[k] : k)];
+  if (total > kOccMaxRays && !src->count_pending) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: more input points than LSM2D_OCCUPANCY_MAX_RAYS");
+  { const int rc0 = resolve_count(src); if (rc0) return rc0; }
+  total = 0;
+  for (int32_t k = 0; k < n_inputs; ++k) total += src->h_count[(size_t) (src_index ? src_index[k] : k)];
+  if (total > kOccMaxRays) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update: more input points than LSM2D_OCCUPANCY_MAX_RAYS");
+  // ---- from here on the call launches
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  { const int rc0 = flush_pending(src); if (rc0) return rc0; }
+  HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
+  OccGeo G;
+  G.ox = grids->geo.origin_x; G.oy = grids->geo.origin_y; G.inv = 1.0f / grids->geo.resolution; G.w = grids->geo.width; G.h = grids->geo.height; G.n_grids = n_grids;
+  G.tiles_x = (G.w + kOccTile - 1) / kOccTile; G.tiles_y = (G.h + kOccTile - 1) / kOccTile;
+  const size_t n_wg = (size_t) G.tiles_x * (size_t) G.tiles_y * (size_t) n_grids;      // (<= LSM2D_OCCUPANCY_MAX_CELLS: a tile holds a cell at least)
+  const bool stamps = ctx->kernel_timing != 0;
+  const OccupancyLayout Y((size_t) total, (size_t) n_inputs, (size_t) n_grids, stamps ? n_wg : 0);
+  { int rc = ensure_scratch(ctx, Y.bytes); if (rc) return rc; rc = ensure_stage(ctx, std::max(Y.up_bytes, Y.down_bytes)); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const ds = (char*) L.d_scratch; char* const hs = (char*) L.h_stage;
+  {
+    OccInput* hin = (OccInput*) (hs + Y.u_inputs); int32_t* hoff = (int32_t*) (hs + Y.u_offset); int32_t* hbox = (int32_t*) (hs + Y.u_box);
+    int32_t* hfirst = (int32_t*) (hs + Y.u_first);
+    // the inputs grid by grid, list order kept inside a grid: a counting sort
+    for (int32_t g = 0; g <= n_grids; ++g) hfirst[g] = 0;
+    for (int32_t k = 0; k < n_inputs; ++k) ++hfirst[(grid ? grid[k] : 0) + 1];
+    for (int32_t g = 0; g < n_grids; ++g) hfirst[g + 1] += hfirst[g];
+    std::vector<int32_t> cursor(hfirst, hfirst + n_grids), order((size_t) n_inputs);
+    for (int32_t k = 0; k < n_inputs; ++k) order[(size_t) cursor[(size_t) (grid ? grid[k] : 0)]++] = k;
+    int32_t o = 0;
+    for (int32_t j = 0; j < n_inputs; ++j) {
+      const int32_t k = order[(size_t) j], ci = src_index ? src_index[k] : k;
+      OccInput& in = hin[j];
+      if (pose) { in.T = make_iso(pose + 3 * (size_t) k); in.sx = pose[3 * (size_t) k]; in.sy = pose[3 * (size_t) k + 1]; }
+      else { in.T.c = 1.0f; in.T.s = 0.0f; in.T.tx = 0.0f; in.T.ty = 0.0f; in.sx = 0.0f; in.sy = 0.0f; }
+      in.start = src->h_start[(size_t) ci]; in.grid = grid ? grid[k] : 0; in.has_pose = pose != nullptr; in.pad = 0;
+      hoff[j] = o; o += src->h_count[(size_t) ci];
+      hbox[4 * j] = hbox[4 * j + 1] = 0x7fffffff; hbox[4 * j + 2] = hbox[4 * j + 3] = kOccDropped;
+    }
+    hoff[n_inputs] = o;
+  }
+  const int n = (int) total;
+  int32_t* const d_fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
+  // ---- the timing bracket of the whole call
+  ctx->have_timing = false;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ds + Y.o_down, 0, Y.down_bytes, ctx->stream));
+  if (n > 0) {
+    OccRaysArgs R;
+    R.xy = src->d_xy; R.inputs = (const OccInput*) (ds + Y.u_inputs); R.offset = (const int32_t*) (ds + Y.u_offset); R.n_inputs = n_inputs; R.n = n; R.G = G;
+    R.rays = (int4*) (ds + Y.o_rays); R.box = (int32_t*) (ds + Y.u_box);
+    R.n_rays = (int32_t*) (ds + Y.o_down + Y.d_rays); R.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped); R.fault = d_fault;
+    hipLaunchKernelGGL(k_occ_rays<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
+    HIPCHK(ctx, hipGetLastError());
+    OccTilesArgs T;
+    T.rays = R.rays; T.offset = R.offset; T.box = R.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_inputs; T.n = n; T.G = G;
+    T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
+    if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
+    hipLaunchKernelGGL(k_occ_tiles<kOccTile>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(hs, ds + Y.o_down, Y.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  const int32_t* const h_rays = (const int32_t*) (hs + Y.d_rays); const int32_t* const h_dropped = (const int32_t*) (hs + Y.d_dropped);
+  if (*(const int32_t*) (hs + Y.d_fault)) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: an index left its array on the device (the counters may be partly updated)");
+  long long sum = 0;
+  for (int32_t g = 0; g < n_grids; ++g) {
+    if (h_rays[g] < 0 || h_dropped[g] < 0) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: the counters are inconsistent");
+    sum += (long long) h_rays[g] + h_dropped[g];
+  }
+  if (sum != total) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: the counters are inconsistent");
+  for (int32_t g = 0; g < n_grids; ++g) { if (out_rays) out_rays[g] = h_rays[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
+  ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
+  if (stamps && n > 0) {      // diagnostics: how unevenly the tiles' work is spread (a copy and a wait of its own, with kernel timing on only)
+    std::vector<unsigned long long> t(n_wg);
+    HIPCHK(ctx, hipMemcpy(t.data(), ds + Y.o_stamps, sizeof(unsigned long long) * n_wg, hipMemcpyDeviceToHost));
+    t.erase(std::remove(t.begin(), t.end(), 0ull), t.end());
+    if (!t.empty()) {
+      std::sort(t.begin(), t.end());
+      ctx->last_occ_wg_median_ns = (long long) t[t.size() / 2] * 10; ctx->last_occ_wg_max_ns = (long long) t.back() * 10;      // (s_memrealtime: 100 MHz)
+    }
+  }
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* grids, int32_t grid_index, const lsm2d_occupancy_render_params* params,
+                                      int8_t* out) {
+  if (!ctx || !grids || !params || !out) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: null argument");
+  if (grids->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: a grid set from another (or a destroyed) context");
+  if (!valid_grid_index(grids, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: grid index outside the set");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t n = grids->cells_per_grid;
+  { const int rc = ensure_scratch(ctx, up256(n)); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  OccRenderArgs R; R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.min_visits = params->min_visits; R.out = (int8_t*) L.d_scratch;
+  ctx->have_timing = false;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  hipLaunchKernelGGL(k_occ_render<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));      // one byte per cell comes down instead of eight
+  HIPCHK(ctx, stream_sync(ctx));
+  return LSM2D_SUCCESS;
+}

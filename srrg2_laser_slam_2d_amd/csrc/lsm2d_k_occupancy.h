@@ -1,0 +1,228 @@
+// lsm2d_k_occupancy.h -- occupancy grids on the device: the points of device-resident clouds ray-traced from their sensor poses into per-cell hit / miss
+// counters (lsm2d_occupancy_update), and the counters rendered to what a map consumer reads (lsm2d_occupancy_render).
+// Part of lsm2d_kernels.h (included there LAST, inside namespace lsm2d: every older kernel keeps its place in the code object).
+//
+// A capability of this build, not of the reference: the reference tree has no grid mapper.  Meaning: PARITY.md section 3, item 17c; everything behind the
+// transform is integer arithmetic, so the result is unique whatever the order of the sums.  The chain, every step a launch of its own on the lane's stream:
+//   k_occ_rays    a thread per concatenated point: its input by binary search in the call's offset table (as k_vox_keys), the point moved by the input's pose
+//                 (xf_point: lsm2d_merge_scene's transform; no pose: the bits copied), the four cell coordinates floorf((v - o) * inv) with the difference and
+//                 the product rounded separately, and a 16-byte ray record {x0, y0, x1, y1} to scratch -- or a marker for a point that gives no ray (a
+//                 coordinate outside [-2^20, 2^20), NaN and Inf among them, or a ray longer than kOccMaxRayCells).  Per (wave, input) the bounding box of the
+//                 live rays and the live / dropped counts are reduced over the wave and added with ONE integer atomic each to the input's box and the
+//                 grid's counts.
+//   k_occ_tiles   a workgroup of 256 threads per (grid, tile of kOccTile x kOccTile cells).  The host lists a grid's inputs contiguously; the workgroup tests
+//                 256 input boxes a round against its tile and keeps the inputs that can touch it.  A workgroup no box touches leaves before it zeroes
+//                 anything.  For a kept input the threads stride over its ray records: reject by the ray's own box, the step interval [i_lo, i_hi] whose major
+//                 coordinate lies in the tile in O(1), the minor coordinate started from the closed form (ONE 32-bit division per (ray, tile)) and carried by
+//                 its remainder, at most kOccTile steps, each a no-return LDS atomic into one of two kOccTile x kOccTile uint32 arrays (32 KB).  After one
+//                 barrier a thread per cell adds the non-zero LDS counts into the grid: a plain 8-byte load, a saturating add in 64 bits, a plain store -- a
+//                 tile has exactly ONE owner per launch.
+//   k_occ_render  a thread per cell: -1 below min_visits, else rintf(100 * hits / (hits + misses)).
+//   k_occ_put     a thread per cell: host counters (planar) into the interleaved cells, a NULL array leaving its counter (lsm2d_gridset_upload).
+// The walk (item 17c.3): with L the major extent and a the minor extent, step i = 0 .. L is the cell (m0 + s i, n0 + s' ((2 i a + L) / (2 L))), the division
+// integer; 2 * 32767^2 + 32767 < 2^31.  Steps 0 .. L - 1 are misses, step L is the hit; a cell outside the grid adds nothing and the ray goes on.
+// Every index is checked against its array; a failed check sets the fault word and the host answers LSM2D_DEVICE_ERROR.  No global atomics on the grid, no
+// workgroup waits for another, no float atomics, no scratch memory.  Tiles overlapped by many scans work longest: the known imbalance, measured in DESIGN.md
+// section 8, not engineered around.  The kernels are templates on the tile size for their place in the code object (an instantiation is emitted where it is
+// first used: the last include part of the host side).
+#pragma once
+
+static constexpr int kOccTile = 64;                    // cells per side of a tile: what ONE workgroup owns ("occupancy_tile")
+static constexpr int kOccBlock = 256;                  // threads of a tile's workgroup = input boxes tested per round
+static constexpr int kOccMaxSide = 16384;              // LSM2D_OCCUPANCY_MAX_SIDE
+static constexpr int kOccMaxCells = 1 << 28;           // LSM2D_OCCUPANCY_MAX_CELLS
+static constexpr int kOccMaxRays = 1 << 24;            // LSM2D_OCCUPANCY_MAX_RAYS
+static constexpr int kOccMaxRayCells = 32767;          // LSM2D_OCCUPANCY_MAX_RAY_CELLS
+static constexpr int kOccDropped = -0x7fffffff - 1;    // x0 of a record whose point gave no ray (no cell coordinate reaches it)
+
+struct OccInput { Iso T; float sx, sy; int32_t start, grid, has_pose, pad; };      // per input, in the host's order (grid by grid): transform, ray start, where its points begin
+struct OccGeo { float ox, oy, inv; int32_t w, h, n_grids, tiles_x, tiles_y; };
+
+struct OccRaysArgs {
+  const float2* xy;                                 // the source set
+  const OccInput* inputs; const int32_t* offset;    // [n_inputs], [n_inputs + 1] concatenation offsets
+  int32_t n_inputs, n;                              // n: concatenated points
+  OccGeo G;
+  int4* rays;                                       // [n]
+  int32_t* box;                                     // [n_inputs][4] = {xmin, ymin, xmax, ymax} of the input's live rays, uploaded as {max, max, min, min}
+  int32_t* n_rays; int32_t* n_dropped;              // [n_grids]
+  int32_t* fault;
+};
+
+LSM2D_DEV float occ_cell(float v, float o, float inv) { return __builtin_floorf(__fmul_rn(__fsub_rn(v, o), inv)); }
+LSM2D_DEV bool occ_in_range(float c) { return c >= -1048576.0f && c < 1048576.0f; }      // (NaN fails)
+
+template <int kTile>
+__global__ __launch_bounds__(256) void k_occ_rays(const OccRaysArgs A) {
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const bool in_range = i < A.n;
+  int k = -1, grid = -1, x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  bool live = false;
+  if (in_range) {
+    int lo = 0, hi = A.n_inputs;      // the last input k with offset[k] <= i (empty inputs share their successor's offset and lose)
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.offset[mid] <= i) lo = mid; else hi = mid; }
+    const OccInput in = A.inputs[lo];
+    k = lo; grid = in.grid;
+    const float2 p = A.xy[(size_t) in.start + (size_t) (i - A.offset[lo])];
+    float x = p.x, y = p.y;
+    if (in.has_pose) xf_point(in.T, p.x, p.y, x, y);
+    const float fx0 = occ_cell(in.sx, A.G.ox, A.G.inv), fy0 = occ_cell(in.sy, A.G.oy, A.G.inv);
+    const float fx1 = occ_cell(x, A.G.ox, A.G.inv), fy1 = occ_cell(y, A.G.oy, A.G.inv);
+    if (occ_in_range(fx0) && occ_in_range(fy0) && occ_in_range(fx1) && occ_in_range(fy1)) {
+      x0 = (int) fx0; y0 = (int) fy0; x1 = (int) fx1; y1 = (int) fy1;
+      const int ax = x1 > x0 ? x1 - x0 : x0 - x1, ay = y1 > y0 ? y1 - y0 : y0 - y1;
+      live = (ax > ay ? ax : ay) <= kOccMaxRayCells;
+    }
+    A.rays[i] = live ? make_int4(x0, y0, x1, y1) : make_int4(kOccDropped, 0, 0, 0);
+  }
+  // per (wave, input): the box of the live rays and the two counts, reduced over the wave; one lane adds them
+  u64 todo = __ballot(in_range);
+  while (todo) {
+    const int leader = __ffsll((long long) todo) - 1;
+    const int kk = __shfl(k, leader);
+    const bool mine = in_range && k == kk, lv = mine && live;
+    int bx0 = lv ? (x0 < x1 ? x0 : x1) : 0x7fffffff, by0 = lv ? (y0 < y1 ? y0 : y1) : 0x7fffffff;
+    int bx1 = lv ? (x0 > x1 ? x0 : x1) : kOccDropped, by1 = lv ? (y0 > y1 ? y0 : y1) : kOccDropped;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int a = __shfl_xor(bx0, o), b = __shfl_xor(by0, o), c = __shfl_xor(bx1, o), d = __shfl_xor(by1, o);
+      bx0 = a < bx0 ? a : bx0; by0 = b < by0 ? b : by0; bx1 = c > bx1 ? c : bx1; by1 = d > by1 ? d : by1;
+    }
+    const u64 m_mine = __ballot(mine);
+    const int nl = __popcll(__ballot(lv)), nd = __popcll(m_mine) - nl;
+    if (lane == leader) {
+      if (kk < 0 || kk >= A.n_inputs || grid < 0 || grid >= A.G.n_grids) *A.fault = 1;
+      else {
+        if (nl) {
+          atomicMin(A.box + 4 * (size_t) kk, bx0); atomicMin(A.box + 4 * (size_t) kk + 1, by0);
+          atomicMax(A.box + 4 * (size_t) kk + 2, bx1); atomicMax(A.box + 4 * (size_t) kk + 3, by1);
+          atomicAdd(A.n_rays + grid, nl);
+        }
+        if (nd) atomicAdd(A.n_dropped + grid, nd);
+      }
+    }
+    todo &= ~m_mine;
+  }
+}
+
+struct OccTilesArgs {
+  const int4* rays; const int32_t* offset; const int32_t* box;      // [n], [n_inputs + 1], [n_inputs][4]
+  const int32_t* grid_first;                                        // [n_grids + 1]: grid g's inputs are grid_first[g] .. grid_first[g + 1]
+  int32_t n_inputs, n;
+  OccGeo G;
+  uint2* cells;                                                     // [n_grids][h][w] = {hits, misses}
+  int32_t* fault;
+  unsigned long long* stamps;                                       // [workgroups] or NULL: 10 ns ticks a workgroup that had work lived (kernel timing on: diagnostics)
+};
+
+template <int kTile>
+__global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
+  __shared__ uint32_t s_hits[kTile * kTile];
+  __shared__ uint32_t s_miss[kTile * kTile];
+  __shared__ int32_t s_list[kOccBlock];
+  __shared__ int32_t s_n;
+  const int tid = threadIdx.x;
+  const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const int tpg = A.G.tiles_x * A.G.tiles_y;
+  const int g = (int) (blockIdx.x / (unsigned) tpg), t = (int) (blockIdx.x - (unsigned) g * (unsigned) tpg);
+  if (g >= A.G.n_grids) { if (tid == 0) *A.fault = 1; return; }
+  const int ty = t / A.G.tiles_x, tx = t - ty * A.G.tiles_x;
+  const int cx0 = tx * kTile, cy0 = ty * kTile;      // the tile's cells, both ends inclusive, cut to the grid
+  const int cx1 = (cx0 + kTile < A.G.w ? cx0 + kTile : A.G.w) - 1, cy1 = (cy0 + kTile < A.G.h ? cy0 + kTile : A.G.h) - 1;
+  const int first = A.grid_first[g], last = A.grid_first[g + 1];
+  if (first < 0 || last > A.n_inputs || first > last) { if (tid == 0) *A.fault = 1; return; }
+  bool zeroed = false;
+  for (int base = first; base < last; base += kOccBlock) {
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const int k = base + tid;
+    if (k < last) {
+      const int4 B = *(const int4*) (A.box + 4 * (size_t) k);
+      if (B.x <= cx1 && B.z >= cx0 && B.y <= cy1 && B.w >= cy0) s_list[atomicAdd(&s_n, 1)] = k;      // (an input without a live ray keeps {max, max, min, min})
+    }
+    __syncthreads();
+    const int m = s_n;
+    if (m > 0 && !zeroed) {
+      for (int c = tid; c < kTile * kTile; c += kOccBlock) { s_hits[c] = 0u; s_miss[c] = 0u; }
+      __syncthreads();
+      zeroed = true;
+    }
+    for (int j = 0; j < m; ++j) {
+      const int kk = s_list[j];
+      const int b = A.offset[kk], e = A.offset[kk + 1];
+      if (b < 0 || e > A.n || b > e) { *A.fault = 1; continue; }
+      for (int r = b + tid; r < e; r += kOccBlock) {
+        const int4 R = A.rays[r];
+        if (R.x == kOccDropped) continue;
+        if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) continue;
+        const int dx = R.z - R.x, dy = R.w - R.y;
+        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+        const bool xm = ax >= ay;      // a tie is x-major
+        const int L = xm ? ax : ay, a = xm ? ay : ax;
+        const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
+        const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
+        const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
+        int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
+        ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
+        if (ilo > ihi) continue;
+        const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
+        const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
+        uint32_t q = num / den, rem = num - q * den;
+        for (int i = ilo; i <= ihi; ++i) {      // at most kTile steps
+          const int nn = n0 + sn * (int) q;
+          if (nn >= nlo && nn <= nhi) {
+            const int mm = m0 + sm * i;
+            const int c = ((xm ? nn : mm) - cy0) * kTile + ((xm ? mm : nn) - cx0);
+            if (c < 0 || c >= kTile * kTile) *A.fault = 1;
+            else if (i == L) atomicAdd(&s_hits[c], 1u);
+            else atomicAdd(&s_miss[c], 1u);
+          }
+          rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
+          if (rem >= den) { rem -= den; ++q; }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (!zeroed) return;
+  for (int c = tid; c < kTile * kTile; c += kOccBlock) {
+    const uint32_t hh = s_hits[c], mm = s_miss[c];
+    if (!(hh | mm)) continue;
+    const int cx = cx0 + (c % kTile), cy = cy0 + (c / kTile);
+    if (cx > cx1 || cy > cy1) { *A.fault = 1; continue; }      // (the walk adds inside the cut tile only)
+    uint2* const cell = A.cells + (((size_t) g * (size_t) A.G.h + (size_t) cy) * (size_t) A.G.w + (size_t) cx);
+    const uint2 v = *cell;
+    const u64 nh = (u64) v.x + hh, nm = (u64) v.y + mm;
+    *cell = make_uint2(nh > 0xffffffffull ? 0xffffffffu : (uint32_t) nh, nm > 0xffffffffull ? 0xffffffffu : (uint32_t) nm);
+  }
+  if (A.stamps && tid == 0) A.stamps[blockIdx.x] = __builtin_amdgcn_s_memrealtime() - t_start;
+}
+
+struct OccRenderArgs { const uint2* cells; long long n; int32_t min_visits; int8_t* out; };
+
+template <int kTile>
+__global__ __launch_bounds__(256) void k_occ_render(const OccRenderArgs A) {
+  const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
+  if (c >= A.n) return;
+  const uint2 v = A.cells[c];
+  const u64 visits = (u64) v.x + (u64) v.y;
+  const u64 need = A.min_visits > 1 ? (u64) A.min_visits : 1ull;
+  int8_t o = -1;
+  if (visits >= need) {
+    const float p = (float) v.x / (float) visits;
+    o = (int8_t) __builtin_rintf(__fmul_rn(100.0f, p));
+  }
+  A.out[c] = o;
+}
+
+struct OccPutArgs { uint2* cells; const uint32_t* hits; const uint32_t* misses; long long n; };
+
+template <int kTile>
+__global__ __launch_bounds__(256) void k_occ_put(const OccPutArgs A) {
+  const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
+  if (c >= A.n) return;
+  uint2 v = A.cells[c];
+  if (A.hits) v.x = A.hits[c];
+  if (A.misses) v.y = A.misses[c];
+  A.cells[c] = v;
+}

@@ -28,6 +28,9 @@
 //   k_vox_keys / k_vox_hist / k_vox_scan / k_vox_scatter / k_vox_head_count / k_vox_head_write / k_vox_sum / k_vox_verdict / k_vox_write / k_vox_finish
 //                      PointCloud::voxelize over device-resident clouds of any size: keys, a stable radix sort, the runs' sums in the reference's order, the
 //                      voxels to the clouds of a reserved set behind a capacity verdict made on the device (lsm2d_voxelize; lsm2d_k_voxelize.h).
+//   k_occ_rays / k_occ_tiles / k_occ_render / k_occ_put
+//                      occupancy grids: device-resident clouds ray-traced from their sensor poses into per-cell hit / miss counters, a workgroup per tile
+//                      summing in LDS, and the counters rendered to 0 .. 100 / -1 (lsm2d_occupancy_update / _render; lsm2d_k_occupancy.h; not in the reference).
 //   k_repack_cloud    AoS float4 (x,y,nx,ny) -> split xy / normal arrays with even-aligned cloud starts.
 #pragma once
 #include "lsm2d_device.h"
@@ -74,5 +77,6 @@ static constexpr int kFindBlock = 1024;
 #include "lsm2d_k_relocalize.h"
 #include "lsm2d_k_score_grid.h"
 #include "lsm2d_k_voxelize.h"
+#include "lsm2d_k_occupancy.h"
 
 }  // namespace lsm2d

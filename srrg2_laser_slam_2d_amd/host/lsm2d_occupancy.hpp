@@ -1,0 +1,69 @@
+// lsm2d_occupancy.hpp -- occupancy grids on the device over the C ABI (include/lsm2d.h, 0.7.12): GridSet, the owner of a lsm2d_gridset, occupancyUpdate
+// (the points of device-resident clouds ray-traced from their sensor poses into hit / miss counters) and occupancyRender (the counters as a map consumer
+// reads them).  An extension of lsm2d.hpp (which it includes and whose types it uses; lsm2d.hpp itself keeps its set of C calls).  A capability of this
+// build: the reference tree has no grid mapper (PARITY.md section 3, item 17c).
+#pragma once
+
+#include "lsm2d.hpp"
+
+namespace lsm2d_host {
+
+// n_grids device-resident grids of one geometry, two uint32 counters per cell (hits, misses), zero at creation; host arrays are [height][width]
+class GridSet {
+ public:
+  struct Counters { std::vector<uint32_t> hits, misses; };
+  GridSet(Context& ctx, const lsm2d_grid_geometry& geometry, int32_t n_grids = 1) : _ctx(ctx), _geometry(geometry), _n_grids(n_grids) {
+    check(lsm2d_gridset_create(ctx.get(), &geometry, n_grids, &_h), "lsm2d_gridset_create", ctx.get());
+  }
+  ~GridSet() { lsm2d_gridset_destroy(_h); }
+  GridSet(const GridSet&) = delete; GridSet& operator=(const GridSet&) = delete;
+  lsm2d_gridset* get() const { return _h; }
+  int32_t numGrids() const { return _n_grids; }
+  const lsm2d_grid_geometry& geometry() const { return _geometry; }
+  size_t cells() const { return (size_t) _geometry.width * (size_t) _geometry.height; }
+  // indices empty: every grid
+  void clear(const std::vector<int32_t>& indices = {}) {
+    check(lsm2d_gridset_clear(_h, (int32_t) indices.size(), detail::ptrOrNull(indices)), "lsm2d_gridset_clear", _ctx.get());
+  }
+  // an empty vector leaves that counter as it is
+  void upload(int32_t grid_index, const std::vector<uint32_t>& hits, const std::vector<uint32_t>& misses) {
+    if ((!hits.empty() && hits.size() != cells()) || (!misses.empty() && misses.size() != cells()))
+      throw std::runtime_error("GridSet::upload| hits and misses are empty or hold height x width counters");
+    check(lsm2d_gridset_upload(_h, grid_index, detail::ptrOrNull(hits), detail::ptrOrNull(misses)), "lsm2d_gridset_upload", _ctx.get());
+  }
+  Counters download(int32_t grid_index) const {
+    Counters c; c.hits.resize(cells()); c.misses.resize(cells());
+    check(lsm2d_gridset_download(_h, grid_index, c.hits.data(), c.misses.data()), "lsm2d_gridset_download", _ctx.get());
+    return c;
+  }
+ private:
+  Context& _ctx; lsm2d_grid_geometry _geometry; int32_t _n_grids; lsm2d_gridset* _h = nullptr;
+};
+
+// rays[g]: rays walked into grid g; dropped[g]: its points that gave no ray
+struct OccupancyUpdate { std::vector<int32_t> rays, dropped; };
+
+// src_index empty: input k is cloud k of src (n_inputs = its clouds); poses empty: no transform at all, every ray starts at (0, 0); grid empty: every
+// input into grid 0.  Throws on every refusal of the call.
+inline OccupancyUpdate occupancyUpdate(Context& ctx, GridSet& grids, const lsm2d_cloudset* src, const std::vector<int32_t>& src_index = {},
+                                       const std::vector<Vector3f>& poses = {}, const std::vector<int32_t>& grid = {}) {
+  const int32_t n_inputs = src_index.empty() ? lsm2d_cloudset_num_clouds(src) : (int32_t) src_index.size();
+  const size_t n = (size_t) (n_inputs > 0 ? n_inputs : 0);
+  if ((!poses.empty() && poses.size() != n) || (!grid.empty() && grid.size() != n))
+    throw std::runtime_error("occupancyUpdate| poses and grid are empty or hold one entry per input");
+  OccupancyUpdate out;
+  out.rays.assign((size_t) grids.numGrids(), 0); out.dropped.assign((size_t) grids.numGrids(), 0);
+  check(lsm2d_occupancy_update(ctx.get(), grids.get(), src, n_inputs, ptrOrNull(src_index), ptrOrNull(poses), ptrOrNull(grid), out.rays.data(), out.dropped.data()),
+        "lsm2d_occupancy_update", ctx.get());
+  return out;
+}
+
+// [height][width]: -1 where hits + misses < max(min_visits, 1), else the share of hits in percent, 0 .. 100
+inline std::vector<int8_t> occupancyRender(Context& ctx, const GridSet& grids, int32_t grid_index = 0, int32_t min_visits = 1) {
+  const lsm2d_occupancy_render_params p{min_visits};
+  std::vector<int8_t> out(grids.cells());
+  check(lsm2d_occupancy_render(ctx.get(), grids.get(), grid_index, &p, out.data()), "lsm2d_occupancy_render", ctx.get());
+  return out;
+}
+
+}  // namespace lsm2d_host
