@@ -80,7 +80,8 @@ extern "C" {
                                     lsm2d_grid_geometry, lsm2d_occupancy_update, lsm2d_occupancy_render, lsm2d_occupancy_render_params,
                                     LSM2D_OCCUPANCY_MAX_SIDE / _MAX_CELLS / _MAX_RAYS / _MAX_RAY_CELLS (occupancy grids on the device: clouds ray-traced
                                     from their sensor poses into hit / miss counts, rendered to 0 .. 100 / -1; not in the reference); read-only option
-                                    keys "occupancy_tile", "last_occupancy_wg_median_ns", "last_occupancy_wg_max_ns" */
+                                    keys "occupancy_tile", "last_occupancy_wg_median_ns", "last_occupancy_wg_max_ns";
+                             (0.7.13, number unchanged: an addition only, no new symbol) + read-only option key "live_handles" */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -285,7 +286,9 @@ int  lsm2d_synchronize(lsm2d_context* ctx);
  *   to be used, builds whose queue was too short; a call without statistics hands no counter over and leaves them as they were), "last_kd_levels",
  *   "last_kd_nodes", "last_kernel_clock_khz", "last_workgroup_lifetime_ns", "max_dyn_lds", "uploads" (host-to-device cloud uploads queued so far:
  *   lsm2d_cloudset_create / _upload / lsm2d_preprocess_scans_refill), "last_h2d_bytes", "experiments" (1: this library was built with
- *   -DLSM2D_EXPERIMENTS and also knows the A/B knobs of DESIGN.md App. A; the shipped library: 0). */
+ *   -DLSM2D_EXPERIMENTS and also knows the A/B knobs of DESIGN.md App. A; the shipped library: 0), "live_handles" (device buffers, pinned host
+ *   buffers, events and streams the library holds at this moment, over ALL contexts and sets of the process -- a set may outlive its context; whatever
+ *   a context and its sets acquired is gone from the count once both are destroyed, in either order: what a leak test on a shared GPU can assert). */
 int  lsm2d_set_option(lsm2d_context* ctx, const char* key, int64_t value);
 /* reads a knob back; also "last_align_path": what the most recent lsm2d_align_batch ran (1 k_align, 2 split, 3 slice pair) */
 int  lsm2d_get_option(lsm2d_context* ctx, const char* key, int64_t* out_value);

@@ -6,6 +6,7 @@
 namespace lsm2d { static constexpr int LSM2D_RUNNING = -99; }
 using lsm2d::LSM2D_RUNNING;
 #include "lsm2d_kernels.h"
+#include "lsm2d_capi_own.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -19,6 +20,7 @@ using lsm2d::LSM2D_RUNNING;
 #include <algorithm>
 #include <thread>
 #include <atomic>
+#include <memory>
 
 using namespace lsm2d;
 
@@ -31,39 +33,38 @@ static thread_local std::string g_last_error;
 // was begun on (lsm2d_pending::lane).  At most two batches are in flight.
 struct Lane {
   // pinned host staging + device scratch, grown on demand (ensure_stage / ensure_scratch)
-  void* h_stage = nullptr; size_t h_stage_bytes = 0; void* h_stage_dev = nullptr;
-  void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
-  void* d_cand_queue = nullptr; size_t d_cand_queue_bytes = 0;                // k_align_cand's queue of maybes (AlignArgs::cand_queue): device scratch of its own, so that only a batch with candidate lists allocates it
-  int32_t* d_order = nullptr;                                                // [4096] the placement the latest estimate made: kept for the next run of the SAME batch (order_valid / order_key / order_poses)
+  Grown<PinnedBuf> h_stage;      // (h_stage.dev(): its device-side address)
+  Grown<DevBuf<>> d_scratch;
+  Grown<DevBuf<>> d_cand_queue;              // k_align_cand's queue of maybes (AlignArgs::cand_queue): device scratch of its own, so that only a batch with candidate lists allocates it
+  DevBuf<int32_t> d_order;                                                   // [4096] the placement the latest estimate made: kept for the next run of the SAME batch (order_valid / order_key / order_poses)
   bool order_valid = false; unsigned long long order_key = 0; std::vector<float> order_poses;      // the placement d_order holds: which batch it was made for
   // what the lane's device scratch holds as a batch's INPUT block (start poses, index arrays), byte for byte, while nothing else has used the scratch since: a batch
   // that comes again with the same inputs needs no upload either (ensure_scratch invalidates it: every other user of the scratch comes through there)
   std::vector<unsigned char> inputs_shadow; bool inputs_valid = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around the lane's latest timed launch (lsm2d_last_kernel_ms)
-  hipEvent_t ev_done = nullptr;                 // "this lane's batch's last operation has run"
+  Event ev0, ev1;      // around the lane's latest timed launch (lsm2d_last_kernel_ms)
+  Event ev_done;                                // "this lane's batch's last operation has run"
   bool busy = false;                            // a batch begun on this lane has not been waited for
   // a batch begun asynchronously launches on ITS LANE's stream: two batches in flight are two streams, and the second one's workgroups fill the slots the first
   // one's tail leaves free instead of waiting for its last workgroup (lane_stream; created on first use)
-  hipStream_t k_stream = nullptr;
+  Stream k_stream;
 };
 // A side stream of the streamed pipeline with the event that orders other streams behind it, created on first use (make_side_stream)
 struct SideStream {
-  hipStream_t st = nullptr; hipEvent_t ev = nullptr;
+  Stream st; Event ev;
   bool dirty = false;         // something was queued here that the next aligner call has to wait for (join_pre_stream / join_refill_stream)
   bool recorded = false;      // ev has been recorded at least once
 };
 
 struct lsm2d_context {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool owns_stream = false;
+  Stream stream;               // its own, or the caller's (borrowed: lsm2d_create)
   bool have_timing = false;
   int timed_lane = -1;         // the lane whose ev0 / ev1 lsm2d_last_kernel_ms reads: the one that recorded the latest timed launch (note_timed), or whose batch was most recently waited for; -1: the current one
   std::string last_error;
-  void* d_split = nullptr; size_t d_split_bytes = 0;      // workspace of the split aligner path
-  void* d_kd_work = nullptr; size_t d_kd_work_bytes = 0;  // working set of the KD-tree build (ping-pong copies, queues, counters): kept, grown on demand
-  void* h_flag = nullptr;                                 // 256 pinned bytes of its own for small read-backs inside a call (the KD-tree build's level counts)
-  struct BeamDirs { int n_beams; float angle_min, angle_max; float2* d_dir; };
+  Grown<DevBuf<>> d_split;                                // workspace of the split aligner path
+  Grown<DevBuf<>> d_kd_work;                              // working set of the KD-tree build (ping-pong copies, queues, counters): kept, grown on demand
+  PinnedBuf h_flag;                                       // 256 pinned bytes of its own for small read-backs inside a call (the KD-tree build's level counts)
+  struct BeamDirs { int n_beams; float angle_min, angle_max; DevBuf<float2> d_dir; };
   std::vector<BeamDirs> beam_dirs;                        // (cos, sin) per beam of the sensors seen so far (lsm2d_preprocess_scan_into)
   int max_dyn_lds = 0;
   unsigned long long sync_epoch = 1;   // bumped by every stream_sync()
@@ -80,7 +81,7 @@ struct lsm2d_context {
   int cull_est_um = 0, cull_est_urad = 40000;      // margins of the work estimate's chunk test ("cull_est_um", "cull_est_urad"; placement only)
   int results_to_host = 1;     // batches that travel by copies: poses, information matrices, statuses, iteration counts and clock stamps written straight to pinned host memory (0: to the device and copied; A/B knob)
   int balance_notes = 1;       // ... group the workgroup ids by the CU the previous launch of the same shape ran them on (0: assume b, b + n_cu, ...; A/B knob)
-  int32_t* d_wg_place = nullptr; unsigned long long wg_place_shape = 0;      // the notes (one int per workgroup) and the launch shape they belong to
+  DevBuf<int32_t> d_wg_place; unsigned long long wg_place_shape = 0;      // the notes (one int per workgroup) and the launch shape they belong to
   int proj_modes = 1;          // projective batches against map-sized clouds: the instantiation with the culled stream only (0: the shared one; A/B knob)
   int kd_modes = 1;            // KD-tree batches: the instantiations with one form of the descent only (0: the shared one; A/B knob)
   int nn_lds_only = 1;         // grid NN with every alignment's tables staged in LDS: the instantiation without the search in global memory (0: the shared one; A/B knob)
@@ -139,10 +140,10 @@ struct lsm2d_context {
   // start poses' upload, its placement's estimate -- is queued here, so the chip runs it in the slots the launch in flight leaves free (its tail), and k_align
   // on the first stream waits for an event behind it
   SideStream side_pre;         // (pre_stream; `recorded`: an estimate queued there may still be running)
-  hipEvent_t ev_a_est = nullptr; bool a_est_recorded = false;      // ... and behind the latest estimate queued on the context's own stream: the two share ONE ticket counter (make_placement)
+  Event ev_a_est; bool a_est_recorded = false;      // ... and behind the latest estimate queued on the context's own stream: the two share ONE ticket counter (make_placement)
   SideStream side_refill;      // lsm2d_preprocess_scans_refill while a batch is in flight: a stream of its own (refill_stream)
   SideStream side_copy;        // ... and one for its host-to-device copy (the copy engine's; nothing it waits for)
-  hipEvent_t ev_main = nullptr;      // orders the lanes' streams (and the pre-kernels' stream) behind what the context's own stream holds (lane_stream)
+  Event ev_main;      // orders the lanes' streams (and the pre-kernels' stream) behind what the context's own stream holds (lane_stream)
 };
 static inline Lane& lane(lsm2d_context* ctx) { return ctx->lanes[ctx->cur]; }
 static void orphan_gridsets(lsm2d_context* ctx);      // (lsm2d_capi_occupancy.inc)
@@ -152,8 +153,7 @@ static bool make_side_stream(SideStream& s) {
   if (s.st) return true;
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void) hipGetLastError(); prio_greatest = 0; }
-  if (hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, prio_greatest) != hipSuccess) { (void) hipGetLastError(); s.st = nullptr; return false; }
-  if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); (void) hipStreamDestroy(s.st); s.st = nullptr; s.ev = nullptr; return false; }
+  if (s.st.create(hipStreamNonBlocking, prio_greatest) != hipSuccess || s.ev.create(hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); s.st.reset(); return false; }
   return true;
 }
 // the stream a batch's PRE-kernels go to (its start poses, its estimate): the second one while another batch is in flight, else the context's own
@@ -189,9 +189,9 @@ static hipStream_t refill_copy_stream(lsm2d_context* ctx, hipStream_t refill) {
 // everything that prepares sets; an event recorded on it at begin() orders the lane's stream (and the pre-kernels' stream) behind what it holds.
 static hipStream_t lane_stream(lsm2d_context* ctx) {
   if (!ctx->lane_streams) return ctx->stream;
-  hipStream_t& st = lane(ctx).k_stream;
-  if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void) hipGetLastError(); st = nullptr; return ctx->stream; }
-  if (!ctx->ev_main && hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); ctx->ev_main = nullptr; return ctx->stream; }
+  Stream& st = lane(ctx).k_stream;
+  if (!st && st.create(hipStreamNonBlocking) != hipSuccess) { (void) hipGetLastError(); return ctx->stream; }
+  if (!ctx->ev_main && ctx->ev_main.create(hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); return ctx->stream; }
   return st;
 }
 // what was queued on the refill stream comes before whatever `st` (and the context's own stream) is given next
@@ -254,21 +254,22 @@ static hipError_t wait_for_statuses(lsm2d_context* ctx, const int32_t* st, int n
   return hipSuccess;
 }
 
+// (the three caches own their blocks and are move-only; the typed pointers beside a block are views into it)
 struct GridCache {     // one search grid per (cloud set, max_distance), built on first use
   float max_distance = 0.0f;
-  void* d_block = nullptr;      // ONE allocation (hipMalloc costs ~0.1 ms a call); the pointers below are views into it
+  DevBuf<> d_block;             // ONE allocation (hipMalloc costs ~0.1 ms a call); the pointers below are views into it
   GridMeta* d_meta = nullptr; int32_t* d_cell_start = nullptr; int32_t* d_cursor = nullptr;
   int32_t* d_sorted_idx = nullptr; float2* d_sorted_xy = nullptr; float2* d_sorted_nrm = nullptr;
 };
 
 struct DistCache {     // one distance map per (cloud set, max_distance, resolution)
   float max_distance = 0.0f, resolution = 0.0f;
-  DistMeta* d_meta = nullptr; int32_t* d_parent = nullptr;
+  DevBuf<DistMeta> d_meta; DevBuf<int32_t> d_parent;
 };
 
 struct KdCache {       // one KD-tree per cloud of the set, per (max_leaf_range, min_leaf_points)
   float max_leaf_range = 0.0f; int min_leaf_points = 0;
-  void* d_block = nullptr;      // one allocation; the pointers below are views into it
+  DevBuf<> d_block;             // one allocation; the pointers below are views into it
   KdMeta* d_meta = nullptr; KdNode* d_nodes = nullptr; float2* d_leaf_xy = nullptr; int32_t* d_leaf_idx = nullptr; float2* d_leaf_nrm = nullptr;
   int levels = 0; long long total_nodes = 0; int max_nodes_per_cloud = 0;
   // a reserved single-cloud set (the live tracker's scan, refilled every step) keeps the allocation when its contents change: the next reset() rebuilds
@@ -281,32 +282,36 @@ struct lsm2d_cloudset {
   lsm2d_context* ctx = nullptr;
   const unsigned long long uid = next_cloudset_uid();      // never reused: what a context remembers about a batch (the kept placement) names its sets by uid + version
   mutable unsigned long long version = 0;                   // bumped whenever the contents change (cloudset_drop_grids)
-  mutable std::vector<GridCache> grids;
-  mutable std::vector<DistCache> dists;
-  mutable std::vector<KdCache> kds;
-  // lane-chunked copy of xy for k_align's streaming pass (built on first use, dropped when the contents change)
-  mutable float4* d_lane_xy = nullptr; mutable long long* d_lane_start = nullptr; mutable int32_t* d_lane_T = nullptr;
-  mutable float4* d_lane_bounds = nullptr;      // bounding circle of every thread's chunk of every cloud (k_lane_bounds): what the culling tests
-  mutable float4* d_block_bounds = nullptr;     // ... and of every block of every chunk (k_block_bounds): the block-level test of the unit lists
-  mutable int32_t block_stride = kCullBlocks;   // blocks per chunk in d_block_bounds
-  mutable float4* d_aos = nullptr;              // (x, y, nx, ny) rows of the whole set (k_aos_rows): one gather per z-buffer winner in k_align's bin walk
-  hipEvent_t ev_stage = nullptr; bool stage_on_side = false;      // behind the set's latest copy OUT of h_upload queued on a side stream (the refill's pageable path): what acquire_upload_stage waits for
-  hipEvent_t ev_prep = nullptr;                 // behind the set's latest preprocessing launch on the refill stream: its NEXT refill's copy (another stream) overwrites what that launch reads
-  mutable float4* d_tile_bounds = nullptr; mutable int32_t* d_tile_start = nullptr;      // bounding circles of the tiles of 64 points (k_tile_bounds): the point-query finders' culling
+  // Everything DERIVED from the contents, built on first use and dropped when they change (cloudset_drop_grids): a new derived buffer is a field here and nothing more
+  struct Derived {
+    std::vector<GridCache> grids;
+    std::vector<DistCache> dists;
+    std::vector<KdCache> kds;
+    // lane-chunked copy of xy for k_align's streaming pass
+    DevBuf<float4> d_lane_xy; DevBuf<long long> d_lane_start; DevBuf<int32_t> d_lane_T;
+    DevBuf<float4> d_lane_bounds;      // bounding circle of every thread's chunk of every cloud (k_lane_bounds): what the culling tests
+    DevBuf<float4> d_block_bounds;     // ... and of every block of every chunk (k_block_bounds): the block-level test of the unit lists
+    DevBuf<float4> d_aos;              // (x, y, nx, ny) rows of the whole set (k_aos_rows): one gather per z-buffer winner in k_align's bin walk
+    DevBuf<float4> d_tile_bounds; DevBuf<int32_t> d_tile_start;      // bounding circles of the tiles of 64 points (k_tile_bounds): the point-query finders' culling
+  };
+  mutable Derived derived;
+  mutable int32_t block_stride = kCullBlocks;   // blocks per chunk in derived.d_block_bounds
+  Event ev_stage; bool stage_on_side = false;   // behind the set's latest copy OUT of h_upload queued on a side stream (the refill's pageable path): what acquire_upload_stage waits for
+  Event ev_prep;                                // behind the set's latest preprocessing launch on the refill stream: its NEXT refill's copy (another stream) overwrites what that launch reads
   int32_t n_clouds = 0;
   mutable int64_t total = 0;  // logical points
   int64_t padded_total = 0;   // device points incl. even-alignment padding
   int64_t capacity = 0;       // > 0: a reserved single growable cloud (lsm2d_cloudset_create_reserved) -- or, with `many`, the room of every cloud
   bool many = false;          // lsm2d_cloudset_create_reserved_many: n_clouds growable clouds in fixed slots; never taken for a single reserved cloud
-  float2* d_xy = nullptr; float2* d_nrm = nullptr;
-  int32_t* d_start = nullptr; int32_t* d_count = nullptr;
-  float* d_ranges = nullptr;      // lsm2d_preprocess_scans_refill: the device copy of the ranges the set was last refilled from
+  DevBuf<float2> d_xy, d_nrm;
+  DevBuf<int32_t> d_start, d_count;
+  DevBuf<float> d_ranges;         // lsm2d_preprocess_scans_refill: the device copy of the ranges the set was last refilled from
   std::vector<int32_t> h_start; mutable std::vector<int32_t> h_count;
   // Asynchronous clip / merge leave the size of a reserved set known to the device only: h_count[0] is then an UPPER BOUND
   // and count_pending is set; kernels read d_count, and whatever needs the exact number calls resolve_count() (one sync).
   mutable bool count_pending = false;
   // per-set pinned staging for lsm2d_cloudset_upload, so an upload does not have to wait for the stream
-  void* h_upload = nullptr; size_t h_upload_bytes = 0; void* h_upload_dev = nullptr;
+  Grown<PinnedBuf> h_upload;      // (h_upload.dev(): its device-side address)
   mutable unsigned long long staged_epoch = 0;       // ctx->sync_epoch when the last transfer out of h_upload was queued (0: none pending)
   // lsm2d_cloudset_upload of a scan-sized set only fills h_upload: the unpacking into d_xy / d_nrm / d_count is queued by the first
   // consumer (flush_pending) -- or done by the aligner kernel itself in its prologue (single-alignment calls: one launch less per scan)
@@ -328,13 +333,6 @@ struct lsm2d_cloudset {
       return e__ == hipErrorOutOfMemory ? LSM2D_OUT_OF_MEMORY : LSM2D_DEVICE_ERROR;                 \
     }                                                                                               \
   } while (0)
-
-// scope guard for device temporaries: every early return (HIPCHK) releases them
-struct DevTmp {
-  void* p = nullptr;
-  ~DevTmp() { if (p) (void) hipFree(p); }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
 
 static int fail(lsm2d_context* ctx, int code, const char* msg) {
   g_last_error = msg;
@@ -387,53 +385,39 @@ extern "C" int lsm2d_create(int device_id, void* hip_stream, lsm2d_context** out
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(nullptr, LSM2D_NO_DEVICE, "no HIP device visible");
   if (device_id < 0 || device_id >= n) return fail(nullptr, LSM2D_BAD_ARGUMENT, "device_id out of range");
-  lsm2d_context* c = new (std::nothrow) lsm2d_context;
+  std::unique_ptr<lsm2d_context> c(new (std::nothrow) lsm2d_context);      // (whatever it has acquired by a failure below goes with it)
   if (!c) return LSM2D_OUT_OF_MEMORY;
   c->device = device_id;
-  lsm2d_context* ctx = c;
+  lsm2d_context* ctx = c.get();
   hipError_t e = hipSetDevice(device_id);
-  if (e == hipSuccess && hip_stream) { c->stream = (hipStream_t) hip_stream; c->owns_stream = false; }
-  else if (e == hipSuccess) { e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking); c->owns_stream = true; }
+  if (e == hipSuccess && hip_stream) c->stream.borrow((hipStream_t) hip_stream);
+  else if (e == hipSuccess) e = c->stream.create(hipStreamNonBlocking);
   for (Lane& L : c->lanes) {
-    if (e == hipSuccess) e = hipEventCreate(&L.ev0);
-    if (e == hipSuccess) e = hipEventCreate(&L.ev1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming);
+    if (e == hipSuccess) e = L.ev0.create();
+    if (e == hipSuccess) e = L.ev1.create();
+    if (e == hipSuccess) e = L.ev_done.create(hipEventDisableTiming);
   }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_a_est, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_flag, 256, hipHostMallocDefault);
-  if (e != hipSuccess) { g_last_error = hipGetErrorString(e); delete c; return LSM2D_DEVICE_ERROR; }
+  if (e == hipSuccess) e = c->ev_a_est.create(hipEventDisableTiming);
+  if (e == hipSuccess) e = c->h_flag.alloc(256, hipHostMallocDefault);
+  if (e != hipSuccess) { g_last_error = hipGetErrorString(e); return LSM2D_DEVICE_ERROR; }
   // allow the big-canvas configurations to use the whole 160 KiB LDS of a CDNA4 CU
   hipDeviceProp_t prop;
   HIPCHK(ctx, hipGetDeviceProperties(&prop, device_id));
   c->max_dyn_lds = (int) prop.sharedMemPerBlock;
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  (void) hipFuncSetAttribute((const void*) k_align<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align<true, false, false, false, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align_cand, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+  const void* const big_lds[] = {
+    (const void*) k_align<true, false, false>, (const void*) k_align<true, false, false, false, 5>, (const void*) k_align_cand,
+    (const void*) k_align<true, true, true>, (const void*) k_align<true, true, true, true>,
+    (const void*) k_align_narrow<256>, (const void*) k_align_pair<false>, (const void*) k_align_pair<true>, (const void*) k_cull_estimate,
+    (const void*) k_kd_build_scan<1>, (const void*) k_kd_build_scan<0>, (const void*) k_kd_build_scan_multi<1>, (const void*) k_kd_build_scan_multi<0>,
+    (const void*) k_find_projective, (const void*) k_find_projective_batch, (const void*) k_project_canvas, (const void*) k_project_split,
+    (const void*) k_clip_small, (const void*) k_merge_small, (const void*) k_merge_multi, (const void*) k_clip_batch, (const void*) k_merge_batch,
+    (const void*) k_split_project<true>, (const void*) k_split_project<false>,
+  };
+  for (const void* k : big_lds) (void) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   for (const AlignVariant& v : kAlignVariantsSeq) (void) hipFuncSetAttribute((const void*) v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align_narrow<256>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_align_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_cull_estimate, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_kd_build_scan<1>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_kd_build_scan<0>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_kd_build_scan_multi<1>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_kd_build_scan_multi<0>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_find_projective, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_find_projective_batch, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_project_canvas, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_project_split, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_clip_small, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_merge_small, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_merge_multi, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_clip_batch, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_merge_batch, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_split_project<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
-  (void) hipFuncSetAttribute((const void*) k_split_project<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
   (void) hipGetLastError();
-  *out = c;
+  *out = c.release();
   return LSM2D_SUCCESS;
 }
 
@@ -445,21 +429,10 @@ extern "C" void lsm2d_destroy(lsm2d_context* c) {
   (void) sync_streams(c, true);
   for (lsm2d_cloudset* cs : c->live_sets) cs->ctx = nullptr;        // still owned by the caller: destroy them any time, use them no more
   orphan_gridsets(c);
-  for (Lane& L : c->lanes) {
-    if (L.h_stage) (void) hipHostFree(L.h_stage);
-    if (L.d_scratch) (void) hipFree(L.d_scratch);
-    if (L.d_cand_queue) (void) hipFree(L.d_cand_queue);
-    if (L.d_order) (void) hipFree(L.d_order);
-    for (hipEvent_t e : {L.ev0, L.ev1, L.ev_done}) if (e) (void) hipEventDestroy(e);
-  }
-  if (c->h_flag) (void) hipHostFree(c->h_flag);
-  if (c->d_split) (void) hipFree(c->d_split);
-  if (c->d_kd_work) (void) hipFree(c->d_kd_work);
-  if (c->d_wg_place) (void) hipFree(c->d_wg_place);
-  for (hipEvent_t e : {c->side_pre.ev, c->side_refill.ev, c->side_copy.ev, c->ev_main, c->ev_a_est}) if (e) (void) hipEventDestroy(e);
-  for_each_extra_stream(c, true, [](hipStream_t st) { (void) hipStreamDestroy(st); });
-  for (auto& bd : c->beam_dirs) if (bd.d_dir) (void) hipFree(bd.d_dir);
-  if (c->owns_stream && c->stream) (void) hipStreamDestroy(c->stream);
+  // Every buffer and event goes with the context; the streams are taken out first and go after them, the context's own last (locals leave in reverse order)
+  Stream own = std::move(c->stream);
+  std::vector<Stream> extra;
+  for_each_extra_stream(c, true, [&extra](Stream& s) { extra.push_back(std::move(s)); });
   delete c;
 }
 
@@ -572,6 +545,7 @@ extern "C" int lsm2d_get_option(lsm2d_context* ctx, const char* key, int64_t* ou
   if (!ctx || !key || !out_value) return LSM2D_BAD_ARGUMENT;
   for (const OptionDesc& o : kOptions) if (!strcmp(key, o.key)) { *out_value = ctx->*(o.field); return LSM2D_SUCCESS; }
   for (const OptionDescLL& o : kOptionsLL) if (!strcmp(key, o.key)) { *out_value = ctx->*(o.field); return LSM2D_SUCCESS; }
+  if (!strcmp(key, "live_handles")) { *out_value = live_handles(); return LSM2D_SUCCESS; }      // (the process's, not a member: a set may outlive its context)
   return fail(ctx, LSM2D_BAD_ARGUMENT, "unknown option");
 }
 
@@ -604,15 +578,12 @@ static PtrKind pointer_kind(const void* p, int* device = nullptr) {
 // anything comes through here and fails loudly instead of writing over them; lsm2d_align_batch_begin says the same before it gets here)
 static const char* const kBothLanesBusy = "two batches are in flight on this context and its staging buffers are theirs: wait for the older one first (lsm2d_align_batch_wait)";
 // (the forms that name the lane: an AlignBatch asks for ITS lane's buffers, which lsm2d_relocalize_select makes the other one than the current)
+// (what every grow-on-demand buffer of the context does before its old block goes: whatever the context's stream still holds may be using it)
+static auto wait_for_stream(lsm2d_context* ctx) { return [ctx] { return stream_sync(ctx); }; }
 static int ensure_stage(lsm2d_context* ctx, Lane& L, size_t bytes) {
   if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  if (bytes <= L.h_stage_bytes) return LSM2D_SUCCESS;
-  if (L.h_stage) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipHostFree(L.h_stage)); L.h_stage = nullptr; L.h_stage_bytes = 0; }
-  size_t cap = bytes + bytes / 2 + 4096;
-  HIPCHK(ctx, hipHostMalloc(&L.h_stage, cap, hipHostMallocCoherent | hipHostMallocMapped));
-  // the buffer's device-side address, looked up once: kernels with small outputs write them there directly (no device-to-host copy)
-  HIPCHK(ctx, hipHostGetDevicePointer(&L.h_stage_dev, L.h_stage, 0));
-  L.h_stage_bytes = cap;
+  // (mapped: the buffer's device-side address is looked up once -- kernels with small outputs write them there directly, no device-to-host copy)
+  HIPCHK(ctx, L.h_stage.ensure(bytes, bytes + bytes / 2 + 4096, wait_for_stream(ctx), hipHostMallocCoherent | hipHostMallocMapped));
   return LSM2D_SUCCESS;
 }
 
@@ -621,25 +592,13 @@ static int ensure_stage(lsm2d_context* ctx, size_t bytes) { return ensure_stage(
 static int ensure_scratch(lsm2d_context* ctx, Lane& L, size_t bytes) {
   if (L.busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
   L.inputs_valid = false;      // (whoever asks is about to write the scratch; lsm2d_align_batch looks at the flag before it asks)
-  if (bytes <= L.d_scratch_bytes) return LSM2D_SUCCESS;
   // (a NEW allocation holds nobody's input block: the shadow goes with the old one -- round-5 advisor: a batch run again with more outputs, e.g. statistics,
   // grew the scratch, compared equal against the shadow and skipped the upload into memory that had never seen it)
-  L.inputs_shadow.clear();
-  if (L.d_scratch) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(L.d_scratch)); L.d_scratch = nullptr; L.d_scratch_bytes = 0; }
-  size_t cap = bytes + bytes / 2 + 4096;
-  HIPCHK(ctx, hipMalloc(&L.d_scratch, cap));
-  L.d_scratch_bytes = cap;
+  if (bytes > L.d_scratch.bytes) L.inputs_shadow.clear();
+  HIPCHK(ctx, L.d_scratch.ensure(bytes, bytes + bytes / 2 + 4096, wait_for_stream(ctx)));
   return LSM2D_SUCCESS;
 }
 static int ensure_scratch(lsm2d_context* ctx, size_t bytes) { return ensure_scratch(ctx, lane(ctx), bytes); }
-// the lane's queue of maybes (k_align_cand): grown on demand like the scratch, never cleared -- a region is read only up to what its alignment has just written
-static int ensure_cand_queue(lsm2d_context* ctx, Lane& L, size_t bytes) {
-  if (bytes <= L.d_cand_queue_bytes) return LSM2D_SUCCESS;
-  if (L.d_cand_queue) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(L.d_cand_queue)); L.d_cand_queue = nullptr; L.d_cand_queue_bytes = 0; }
-  HIPCHK(ctx, hipMalloc(&L.d_cand_queue, bytes));
-  L.d_cand_queue_bytes = bytes;
-  return LSM2D_SUCCESS;
-}
 
 // ---- the rest of the host side, by subject (one translation unit: they share the context, the cloud sets and the helpers above) ----
 #include "lsm2d_capi_cloudsets.inc"

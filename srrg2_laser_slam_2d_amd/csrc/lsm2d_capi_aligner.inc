@@ -238,7 +238,7 @@ int AlignBatch::choose_path() {
   // ("zero_copy_max" bounds every batch, so the A/B knob works below 256 too; batches that carry index arrays stay on the transfers above 256)
   zero_copy = !select && !out_work && !use_split && n <= ctx->zero_copy_max && (n <= 256 || (!b->fixed_index && !b->moving_index));
   pair_eligible = pair_order_ok(ctx, n) && ctx->align_path != 1 && (ns == 1 || ns == 2) && proj_only && (n <= 256 || ctx->align_path == 3) && ap->max_iterations > 0;
-  if (zero_copy) ds = (char*) L->h_stage_dev;
+  if (zero_copy) ds = (char*) L->h_stage.dev();
   return LSM2D_SUCCESS;
 }
 
@@ -322,7 +322,7 @@ int AlignBatch::prepare_slices() {
       arc = ensure_aos(ctx, m); if (arc) return arc;
     }
     S.fixed = cloud_dev(f, d_fi); S.moving = cloud_dev(m, d_mi);
-    S.unpack_src = defer_unpack ? (const float4*) f->h_upload_dev : nullptr; S.unpack_n = defer_unpack ? f->h_count[0] : 0;
+    S.unpack_src = defer_unpack ? (const float4*) f->h_upload.dev() : nullptr; S.unpack_n = defer_unpack ? f->h_count[0] : 0;
     if (sp.finder == LSM2D_FINDER_NN) { const int grc = ensure_grid(ctx, f, sp.max_distance, &S.fixed.grid); if (grc) return grc; }
     if (sp.finder == LSM2D_FINDER_DISTMAP) { const int grc = ensure_distmap(ctx, f, sp.max_distance, sp.resolution, &S.fixed.dist); if (grc) return grc; }
     if (sp.finder == LSM2D_FINDER_KDTREE) { const int grc = ensure_kdtree(ctx, f, sp.kd_max_leaf_range, sp.kd_min_leaf_points, &S.fixed.kd, &kd_cache0); if (grc) return grc; }
@@ -360,7 +360,7 @@ int AlignBatch::lay_out_lds() {
     const int keep_words = (((mm + 63) / 64 + kAlignBlock - 1) / kAlignBlock) * (kAlignBlock / 64);
     if (mf <= 16384 && mm >= 4096 && mm > 2 * mf && keep_words <= 512) {
       const int trc = ensure_tile_bounds(ctx, m); if (trc) return trc;
-      if (m->d_tile_bounds) { A.pq_keep_words = keep_words; pq_bytes = 128 * 5 * 4 + sizeof(u64) * (size_t) keep_words + 16; A.s[0].moving = cloud_dev_with_tiles(A.s[0].moving, m); }
+      if (m->derived.d_tile_bounds) { A.pq_keep_words = keep_words; pq_bytes = 128 * 5 * 4 + sizeof(u64) * (size_t) keep_words + 16; A.s[0].moving = cloud_dev_with_tiles(A.s[0].moving, m); }
     }
   }
   lds_budget = 38 * 1024 - pq_bytes;
@@ -445,7 +445,8 @@ int AlignBatch::lay_out_lds() {
         // Round 30: the queue of maybes, "cand_queue_cap" entries per alignment in device memory of the lane's (at most one dispatch round of 16 384: 64 MB); "cand_queue" 0: none
         A.cand_qcap = ctx->cand_queue ? ctx->cand_queue_cap : -1;
         if (A.cand_qcap > 0) {
-          const int qrc = ensure_cand_queue(ctx, *L, sizeof(uint32_t) * (size_t) n * (size_t) A.cand_qcap); if (qrc) return qrc;
+          const size_t qbytes = sizeof(uint32_t) * (size_t) n * (size_t) A.cand_qcap;      // (grown on demand like the scratch, to the byte; never cleared: a region is read only up to what its alignment has just written)
+          HIPCHK(ctx, L->d_cand_queue.ensure(qbytes, qbytes, wait_for_stream(ctx)));
           A.cand_queue = (uint32_t*) L->d_cand_queue;
         }
       }
@@ -542,7 +543,7 @@ int AlignBatch::stage_inputs() {
   // staging buffer: the device-to-host copy behind the launch -- a hand-over to the copy engine, 9 us of gap + 6 us of copy on the timeline of a
   // 1000-alignment step -- is gone, the stream wait ends with the kernel.  The statistics (28 bytes per iteration and alignment) stay on the device and are copied.
   host_results = !select && !zero_copy && !use_split && ctx->results_to_host && n > 0;      // (select mode: k_align_rows reads them where the kernels leave them, on the device)
-  char* const ro = host_results ? (char*) L->h_stage_dev : ds;
+  char* const ro = host_results ? (char*) L->h_stage.dev() : ds;
   A.out_pose = (float*) (ro + o_pose); A.out_H = (float*) (ro + o_H); A.out_status = (int32_t*) (ro + o_status); A.out_its = (int32_t*) (ro + o_its);
   A.out_stats = out_stats ? (StatsDev*) (ds + o_stats) : nullptr;
   A.out_last_pose = out_last_pose ? (float*) (ro + o_last_pose) : nullptr;
@@ -550,7 +551,7 @@ int AlignBatch::stage_inputs() {
 
   ctx->last_clock_khz = 0; ctx->last_wg_lifetime_ns = 0;
   stamps = ctx->kernel_timing && !use_split && !use_pair;
-  if (stamps) { A.clock_out = (unsigned long long*) ((host_results ? (char*) L->h_stage_dev : ds) + o_clock); A.clock_stride = clock_stride; }
+  if (stamps) { A.clock_out = (unsigned long long*) ((host_results ? (char*) L->h_stage.dev() : ds) + o_clock); A.clock_stride = clock_stride; }
   A.host_polls = zero_copy;
   if (zero_copy) {
     memset(hs + o_pose, 0, out_bytes);
@@ -604,10 +605,10 @@ int AlignBatch::make_placement() {
       const bool packed = proj_culled_for_all && pack_two_for(ctx, n, lds);
       const unsigned long long shape = ((unsigned long long) (unsigned) n << 32) ^ ((unsigned long long) lds << 8) ^ (unsigned long long) (proj_culled_for_all ? 5 : 0) ^ (packed ? 0x80ull : 0ull);
       if (!ctx->d_wg_place) {      // 1024 notes + the estimate's ticket counter
-        HIPCHK(ctx, hipMalloc(&ctx->d_wg_place, sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
+        HIPCHK(ctx, ctx->d_wg_place.alloc(sizeof(int32_t) * 1025)); ctx->wg_place_shape = 0;
         HIPCHK(ctx, hipMemsetAsync(ctx->d_wg_place, 0, sizeof(int32_t) * 1025, pre));      // (on the stream the estimate that reads the ticket is queued on)
       }
-      if (!L->d_order) { HIPCHK(ctx, hipMalloc(&L->d_order, sizeof(int32_t) * kOrderInts)); L->order_valid = false; }
+      if (!L->d_order) { HIPCHK(ctx, L->d_order.alloc(sizeof(int32_t) * kOrderInts)); L->order_valid = false; }
       const bool notes = ctx->balance_notes && ctx->wg_place_shape == shape;
       // Round 5: the order lives in a buffer of its own and is KEPT.  A caller that runs the same batch again -- the same sets (uid and version), index arrays,
       // slice parameters, launch shape and START POSES: a candidate sweep re-scored, bench.py's resident step -- gets the placement made for it the first time
@@ -674,11 +675,7 @@ int AlignBatch::launch() {
     const size_t w_H = w_done + (((sizeof(int32_t) * (size_t) n) + 255) & ~(size_t) 255), w_last = w_H + (((sizeof(float) * 9 * (size_t) n) + 255) & ~(size_t) 255);
     const size_t w_phase = w_last + ((sizeof(StatsDev) * (size_t) n + 255) & ~(size_t) 255);
     const size_t w_total = w_phase + sizeof(int32_t) * 3 * (size_t) n;
-    if (w_total > ctx->d_split_bytes) {
-      if (ctx->d_split) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(ctx->d_split)); ctx->d_split = nullptr; ctx->d_split_bytes = 0; }
-      HIPCHK(ctx, hipMalloc(&ctx->d_split, w_total + w_total / 2));
-      ctx->d_split_bytes = w_total + w_total / 2;
-    }
+    HIPCHK(ctx, ctx->d_split.ensure(w_total, w_total + w_total / 2, wait_for_stream(ctx)));
     char* w = (char*) ctx->d_split;
     SplitArgs SA; SA.A = A;
     SA.gcan = (u64*) w; SA.pose = (float*) (w + w_pose); SA.done = (int32_t*) (w + w_done); SA.H_last = (float*) (w + w_H); SA.last = (StatsDev*) (w + w_last);

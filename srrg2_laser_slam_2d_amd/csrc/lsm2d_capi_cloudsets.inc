@@ -18,15 +18,33 @@ static int cloudset_layout(lsm2d_cloudset* cs, const int32_t* offsets, int32_t n
 }
 
 static int cloudset_alloc(lsm2d_context* ctx, lsm2d_cloudset* cs) {
-  HIPCHK(ctx, hipMalloc((void**) &cs->d_xy, sizeof(float2) * (size_t) cs->padded_total));
-  HIPCHK(ctx, hipMalloc((void**) &cs->d_nrm, sizeof(float2) * (size_t) cs->padded_total));
-  HIPCHK(ctx, hipMalloc((void**) &cs->d_start, sizeof(int32_t) * (size_t) cs->n_clouds));
-  HIPCHK(ctx, hipMalloc((void**) &cs->d_count, sizeof(int32_t) * (size_t) cs->n_clouds));
+  HIPCHK(ctx, cs->d_xy.alloc(sizeof(float2) * (size_t) cs->padded_total));
+  HIPCHK(ctx, cs->d_nrm.alloc(sizeof(float2) * (size_t) cs->padded_total));
+  HIPCHK(ctx, cs->d_start.alloc(sizeof(int32_t) * (size_t) cs->n_clouds));
+  HIPCHK(ctx, cs->d_count.alloc(sizeof(int32_t) * (size_t) cs->n_clouds));
   HIPCHK(ctx, hipMemsetAsync(cs->d_xy, 0, sizeof(float2) * (size_t) cs->padded_total, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(cs->d_nrm, 0, sizeof(float2) * (size_t) cs->padded_total, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(cs->d_start, cs->h_start.data(), sizeof(int32_t) * (size_t) cs->n_clouds, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(cs->d_count, cs->h_count.data(), sizeof(int32_t) * (size_t) cs->n_clouds, hipMemcpyHostToDevice, ctx->stream));
   return LSM2D_SUCCESS;
+}
+
+// A set under construction: destroyed by whatever return comes before it is released into the caller's `*out`
+struct CloudsetDestroy { void operator()(lsm2d_cloudset* cs) const { lsm2d_cloudset_destroy(cs); } };
+typedef std::unique_ptr<lsm2d_cloudset, CloudsetDestroy> CloudsetGuard;
+// THE way a set comes to be: new, registered with its context (live_sets), laid out by `layout(set)` -- clouds, starts, sizes, padded_total --, allocated
+template <class Layout> static int cloudset_new(lsm2d_context* ctx, CloudsetGuard& cs, Layout layout) {
+  cs.reset(new (std::nothrow) lsm2d_cloudset);
+  if (!cs) return LSM2D_OUT_OF_MEMORY;
+  cs->ctx = ctx; ctx->live_sets.push_back(cs.get());
+  const int rc = layout(cs.get());
+  return rc != LSM2D_SUCCESS ? rc : cloudset_alloc(ctx, cs.get());
+}
+// ... in fixed slots of `stride` points: n_clouds empty clouds (the reserved forms, a set of scans)
+static void cloudset_slots(lsm2d_cloudset* cs, int32_t n_clouds, int64_t stride) {
+  cs->n_clouds = n_clouds; cs->total = 0; cs->padded_total = stride * n_clouds + 2;
+  cs->h_start.resize(n_clouds); cs->h_count.assign(n_clouds, 0);
+  for (int32_t c = 0; c < n_clouds; ++c) cs->h_start[c] = (int32_t) (stride * c);
 }
 
 static int cloudset_create_impl(lsm2d_context* ctx, const void* points, bool on_device, const int32_t* offsets,
@@ -35,41 +53,30 @@ static int cloudset_create_impl(lsm2d_context* ctx, const void* points, bool on_
     return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_create: bad argument");
   *out = nullptr;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  lsm2d_cloudset* cs = new (std::nothrow) lsm2d_cloudset;
-  if (!cs) return LSM2D_OUT_OF_MEMORY;
-  cs->ctx = ctx; ctx->live_sets.push_back(cs);
-  int rc = cloudset_layout(cs, offsets, n_clouds, total);
-  if (rc == LSM2D_SUCCESS) rc = cloudset_alloc(ctx, cs);
-  if (rc != LSM2D_SUCCESS) { lsm2d_cloudset_destroy(cs); return rc; }
+  CloudsetGuard cs;
+  { const int rc = cloudset_new(ctx, cs, [&](lsm2d_cloudset* s) { return cloudset_layout(s, offsets, n_clouds, total); }); if (rc != LSM2D_SUCCESS) return rc; }
+  // (the staging buffers and the one-cloud offsets live until the function returns: behind the wait below, which their copies and the kernel need)
+  DevBuf<> d_src; DevBuf<int32_t> d_off;
+  const std::vector<int32_t> one = {0, (int32_t) total};
   if (total > 0) {
     // stage the AoS points (and the logical offsets) on the device, then split / pad with one kernel
     const size_t pts_bytes = sizeof(float4) * (size_t) total, off_bytes = sizeof(int32_t) * (size_t) (n_clouds + 1);
-    void* d_src = nullptr; int32_t* d_off = nullptr;
-    std::vector<int32_t> one = {0, (int32_t) total};
     const int32_t* h_off = offsets ? offsets : one.data();
-    hipError_t e = hipSuccess;
     if (!on_device) {
       ++ctx->uploads; ctx->last_h2d_bytes = (long long) pts_bytes;
-      e = hipMalloc(&d_src, pts_bytes);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_src, points, pts_bytes, hipMemcpyHostToDevice, ctx->stream);
+      HIPCHK(ctx, d_src.alloc(pts_bytes));
+      HIPCHK(ctx, hipMemcpyAsync(d_src, points, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (e == hipSuccess) e = hipMalloc((void**) &d_off, off_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, h_off, off_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      const int block = 256;
-      long long blocks = (total + block - 1) / block; if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(k_repack_cloud, dim3((unsigned) blocks), dim3(block), 0, ctx->stream,
-                         (const float4*) (on_device ? points : d_src), d_off, cs->d_start, n_clouds, (long long) total, cs->d_xy, cs->d_nrm);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = stream_sync(ctx);
-    if (d_src) (void) hipFree(d_src);
-    if (d_off) (void) hipFree(d_off);
-    if (e != hipSuccess) { lsm2d_cloudset_destroy(cs); HIPCHK(ctx, e); }
-  } else {
-    HIPCHK(ctx, stream_sync(ctx));
+    HIPCHK(ctx, d_off.alloc(off_bytes));
+    HIPCHK(ctx, hipMemcpyAsync(d_off, h_off, off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int block = 256;
+    long long blocks = (total + block - 1) / block; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_repack_cloud, dim3((unsigned) blocks), dim3(block), 0, ctx->stream,
+                       (const float4*) (on_device ? points : d_src), d_off, cs->d_start, n_clouds, (long long) total, cs->d_xy, cs->d_nrm);
+    HIPCHK(ctx, hipGetLastError());
   }
-  *out = cs;
+  HIPCHK(ctx, stream_sync(ctx));      // (the temporaries above and the caller's points back the copies: they go after this wait)
+  *out = cs.release();
   return LSM2D_SUCCESS;
 }
 
@@ -84,28 +91,9 @@ extern "C" int lsm2d_cloudset_create_from_device(lsm2d_context* ctx, const void*
 extern "C" void lsm2d_cloudset_destroy(lsm2d_cloudset* cs) {
   if (!cs) return;
   if (cs->ctx) (void) hipSetDevice(cs->ctx->device);
-  if (cs->d_xy) (void) hipFree(cs->d_xy);
-  if (cs->d_nrm) (void) hipFree(cs->d_nrm);
-  if (cs->d_start) (void) hipFree(cs->d_start);
-  if (cs->d_count) (void) hipFree(cs->d_count);
-  if (cs->d_ranges) (void) hipFree(cs->d_ranges);
-  if (cs->ev_prep) (void) hipEventDestroy(cs->ev_prep);
-  if (cs->ev_stage) (void) hipEventDestroy(cs->ev_stage);
-  for (auto& g : cs->grids) if (g.d_block) (void) hipFree(g.d_block);
-  for (auto& d : cs->dists) { if (d.d_meta) (void) hipFree(d.d_meta); if (d.d_parent) (void) hipFree(d.d_parent); }
-  for (auto& k : cs->kds) if (k.d_block) (void) hipFree(k.d_block);
-  if (cs->d_lane_xy) (void) hipFree(cs->d_lane_xy);
-  if (cs->d_lane_start) (void) hipFree(cs->d_lane_start);
-  if (cs->d_lane_T) (void) hipFree(cs->d_lane_T);
-  if (cs->d_lane_bounds) (void) hipFree(cs->d_lane_bounds);
-  if (cs->d_block_bounds) (void) hipFree(cs->d_block_bounds);
-  if (cs->d_aos) (void) hipFree(cs->d_aos);
-  if (cs->d_tile_bounds) (void) hipFree(cs->d_tile_bounds);
-  if (cs->d_tile_start) (void) hipFree(cs->d_tile_start);
   if (cs->ctx && cs->staged_epoch == cs->ctx->sync_epoch) (void) stream_sync(cs->ctx);      // a staged transfer may still be reading h_upload
-  if (cs->h_upload) (void) hipHostFree(cs->h_upload);
   if (cs->ctx) { auto& v = cs->ctx->live_sets; for (size_t i = 0; i < v.size(); ++i) if (v[i] == cs) { v[i] = v.back(); v.pop_back(); break; } }
-  delete cs;
+  delete cs;      // (its arrays, events, caches and pinned buffer go with it)
 }
 static int flush_pending(const lsm2d_cloudset* cs);
 static int resolve_count(const lsm2d_cloudset* cs) {
@@ -142,7 +130,7 @@ static int flush_pending(const lsm2d_cloudset* cs) {
   const int n = cs->h_count[0];
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_upload_unpack, dim3((unsigned) (n > 4096 ? 16 : (n + 255) / 256 > 0 ? (n + 255) / 256 : 1)), dim3(256), 0, ctx->stream,
-                     (const float4*) cs->h_upload_dev, n, cs->d_xy, cs->d_nrm, cs->d_count);
+                     (const float4*) cs->h_upload.dev(), n, cs->d_xy, cs->d_nrm, cs->d_count);
   HIPCHK(ctx, hipGetLastError());
   cs->unpack_pending = false; cs->staged_epoch = ctx->sync_epoch;
   return LSM2D_SUCCESS;
@@ -184,56 +172,36 @@ extern "C" int32_t lsm2d_cloudset_cloud_sizes(const lsm2d_cloudset* cs, int32_t*
   return n;
 }
 
-static void cloudset_drop_grids(const lsm2d_cloudset* cs) {     // the contents changed: cached NN grids are stale
+// the contents changed: everything derived from them is stale and goes.  Two things stay: a reserved single-cloud set with one KD-tree keeps that tree's
+// allocation for the next build (KdCache::valid), and a refill keeps the AoS rows, which its launch rewrites in place (keep_aos)
+static void cloudset_drop_grids(const lsm2d_cloudset* cs, bool keep_aos = false) {
   ++cs->version;
-  for (auto& g : cs->grids) if (g.d_block) (void) hipFree(g.d_block);
-  cs->grids.clear();
-  if (cs->d_lane_xy) { (void) hipFree(cs->d_lane_xy); cs->d_lane_xy = nullptr; }
-  if (cs->d_lane_start) { (void) hipFree(cs->d_lane_start); cs->d_lane_start = nullptr; }
-  if (cs->d_lane_T) { (void) hipFree(cs->d_lane_T); cs->d_lane_T = nullptr; }
-  if (cs->d_lane_bounds) { (void) hipFree(cs->d_lane_bounds); cs->d_lane_bounds = nullptr; }
-  if (cs->d_block_bounds) { (void) hipFree(cs->d_block_bounds); cs->d_block_bounds = nullptr; }
-  if (cs->d_aos) { (void) hipFree(cs->d_aos); cs->d_aos = nullptr; }
-  if (cs->d_tile_bounds) { (void) hipFree(cs->d_tile_bounds); cs->d_tile_bounds = nullptr; }
-  if (cs->d_tile_start) { (void) hipFree(cs->d_tile_start); cs->d_tile_start = nullptr; }
-  for (auto& d : cs->dists) { if (d.d_meta) (void) hipFree(d.d_meta); if (d.d_parent) (void) hipFree(d.d_parent); }
-  cs->dists.clear();
-  if (cs->capacity > 0 && cs->n_clouds == 1 && cs->kds.size() == 1) cs->kds[0].valid = false;      // a reserved set: the allocation is recycled by the next build (KdCache::valid)
-  else { for (auto& k : cs->kds) if (k.d_block) (void) hipFree(k.d_block); cs->kds.clear(); }
+  lsm2d_cloudset::Derived fresh;
+  if (keep_aos) fresh.d_aos = std::move(cs->derived.d_aos);
+  if (cs->capacity > 0 && cs->n_clouds == 1 && cs->derived.kds.size() == 1) { cs->derived.kds[0].valid = false; fresh.kds = std::move(cs->derived.kds); }
+  cs->derived = std::move(fresh);
 }
 
+// the reserved forms: n_clouds empty clouds with room for `capacity` points each, every slot starting on an even point (16-byte aligned xy), as cloudset_layout lays them out
+static int cloudset_create_slots(lsm2d_context* ctx, int32_t n_clouds, int64_t capacity, bool many, lsm2d_cloudset** out) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  CloudsetGuard cs;
+  const int rc = cloudset_new(ctx, cs, [&](lsm2d_cloudset* s) { cloudset_slots(s, n_clouds, capacity + (capacity & 1)); s->capacity = capacity; s->many = many; return LSM2D_SUCCESS; });
+  if (rc != LSM2D_SUCCESS) return rc;
+  if (stream_sync(ctx) != hipSuccess) return LSM2D_DEVICE_ERROR;
+  *out = cs.release();
+  return LSM2D_SUCCESS;
+}
 extern "C" int lsm2d_cloudset_create_reserved(lsm2d_context* ctx, int64_t capacity, lsm2d_cloudset** out) {
   if (!ctx || !out || capacity < 1 || capacity > 0x7ffffff0) return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_create_reserved: bad argument");
   *out = nullptr;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  lsm2d_cloudset* cs = new (std::nothrow) lsm2d_cloudset;
-  if (!cs) return LSM2D_OUT_OF_MEMORY;
-  cs->ctx = ctx; ctx->live_sets.push_back(cs); cs->n_clouds = 1; cs->total = 0; cs->capacity = capacity; cs->padded_total = capacity + (capacity & 1) + 2;
-  cs->h_start.assign(1, 0); cs->h_count.assign(1, 0);
-  int rc = cloudset_alloc(ctx, cs);
-  if (rc == LSM2D_SUCCESS) { hipError_t e = stream_sync(ctx); if (e != hipSuccess) rc = LSM2D_DEVICE_ERROR; }
-  if (rc != LSM2D_SUCCESS) { lsm2d_cloudset_destroy(cs); return rc; }
-  *out = cs;
-  return LSM2D_SUCCESS;
+  return cloudset_create_slots(ctx, 1, capacity, false, out);
 }
-
 extern "C" int lsm2d_cloudset_create_reserved_many(lsm2d_context* ctx, int32_t n_clouds, int64_t capacity, lsm2d_cloudset** out) {
   if (!ctx || !out || n_clouds < 1 || capacity < 1 || capacity > 0x7ffffff0) return fail(ctx, LSM2D_BAD_ARGUMENT, "cloudset_create_reserved_many: bad argument");
   *out = nullptr;
-  const int64_t stride = capacity + (capacity & 1);      // every slot starts on an even point (16-byte aligned xy), as cloudset_layout lays them out
-  if (stride * n_clouds > 0x7ffffff0) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "cloudset_create_reserved_many: too many points");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  lsm2d_cloudset* cs = new (std::nothrow) lsm2d_cloudset;
-  if (!cs) return LSM2D_OUT_OF_MEMORY;
-  cs->ctx = ctx; ctx->live_sets.push_back(cs); cs->n_clouds = n_clouds; cs->total = 0; cs->capacity = capacity; cs->many = true;
-  cs->padded_total = stride * n_clouds + 2;
-  cs->h_start.resize(n_clouds); cs->h_count.assign(n_clouds, 0);
-  for (int32_t c = 0; c < n_clouds; ++c) cs->h_start[c] = (int32_t) (stride * c);
-  int rc = cloudset_alloc(ctx, cs);
-  if (rc == LSM2D_SUCCESS) { hipError_t e = stream_sync(ctx); if (e != hipSuccess) rc = LSM2D_DEVICE_ERROR; }
-  if (rc != LSM2D_SUCCESS) { lsm2d_cloudset_destroy(cs); return rc; }
-  *out = cs;
-  return LSM2D_SUCCESS;
+  if ((capacity + (capacity & 1)) * n_clouds > 0x7ffffff0) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "cloudset_create_reserved_many: too many points");
+  return cloudset_create_slots(ctx, n_clouds, capacity, true, out);
 }
 
 // asynchronous: the device-side sizes of the named clouds are zeroed on the context's stream (contiguous runs of indices: one memset each)
@@ -271,13 +239,9 @@ static int acquire_upload_stage(lsm2d_cloudset* cs, size_t need) {
   if (cs->staged_epoch == ctx->sync_epoch) HIPCHK(ctx, stream_sync(ctx));
   // ... and a copy queued on a side stream (the refill while a batch is in flight) is not covered by the context stream's epoch: its own event
   if (cs->stage_on_side) { HIPCHK(ctx, hipEventSynchronize(cs->ev_stage)); cs->stage_on_side = false; }
-  if (need > cs->h_upload_bytes) {
-    if (cs->h_upload) { HIPCHK(ctx, hipHostFree(cs->h_upload)); cs->h_upload = nullptr; cs->h_upload_bytes = 0; }
-    const size_t want = cs->capacity > 0 && !cs->many ? sizeof(float) * 4 * (size_t) cs->capacity + 16 : need;      // (a set of many clouds stages the batched calls' per-tracker arguments only)
-    HIPCHK(ctx, hipHostMalloc(&cs->h_upload, want > need ? want : need, hipHostMallocCoherent | hipHostMallocMapped));
-    HIPCHK(ctx, hipHostGetDevicePointer(&cs->h_upload_dev, cs->h_upload, 0));
-    cs->h_upload_bytes = want > need ? want : need;
-  }
+  // (a set of many clouds stages the batched calls' per-tracker arguments only; nothing to wait for here: the waits above cover the old buffer)
+  const size_t want = cs->capacity > 0 && !cs->many ? sizeof(float) * 4 * (size_t) cs->capacity + 16 : need;
+  HIPCHK(ctx, cs->h_upload.ensure(need, want > need ? want : need, [] { return hipSuccess; }, hipHostMallocCoherent | hipHostMallocMapped));
   return LSM2D_SUCCESS;
 }
 
@@ -311,7 +275,7 @@ extern "C" int lsm2d_cloudset_upload(lsm2d_cloudset* cs, const float* pts, int64
       HIPCHK(ctx, hipMemcpyAsync(cs->d_nrm, hn, sizeof(float2) * (size_t) n, hipMemcpyHostToDevice, ctx->stream));
     }
     // the count travels in the same staging buffer (h_count may be rewritten by the host before the copy runs)
-    int32_t* hcnt = (int32_t*) ((char*) cs->h_upload + cs->h_upload_bytes - sizeof(int32_t));
+    int32_t* hcnt = (int32_t*) ((char*) cs->h_upload + cs->h_upload.bytes - sizeof(int32_t));
     *hcnt = (int32_t) n;
     HIPCHK(ctx, hipMemcpyAsync(cs->d_count, hcnt, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   }

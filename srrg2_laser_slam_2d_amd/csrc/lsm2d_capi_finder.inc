@@ -140,7 +140,7 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
     rc = ensure_stage(ctx, bytes); if (rc) return rc;
     Lane& L = lane(ctx);
     const bool direct = bytes <= (1u << 16);             // up to 8k pairs: written straight to pinned host memory
-    char* dv = (char*) (direct ? L.h_stage_dev : L.d_scratch);
+    char* dv = (char*) (direct ? L.h_stage.dev() : L.d_scratch);
     N.out_count = (int32_t*) dv; N.out_pairs = (int32_t*) (dv + 16);
     N.match = (int32_t*) ((char*) L.d_scratch + o_match); N.block_count = (int32_t*) ((char*) L.d_scratch + o_cnt);
     const TimedLaunch timing(ctx, L, ctx->stream);
@@ -170,7 +170,7 @@ static int find_correspondences_impl(lsm2d_context* ctx, const lsm2d_slice_param
   Lane& L = lane(ctx);
   A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr); A.fc = fi; A.mc = mi;
   A.point_distance = sp->point_distance; A.normal_cos = sp->normal_cos; A.T = make_iso(pose); A.inl_tau = inl_tau;
-  char* dv = (char*) L.h_stage_dev;       // <= one pair per column: written straight to pinned host memory
+  char* dv = (char*) L.h_stage.dev();       // <= one pair per column: written straight to pinned host memory
   A.out_count = (int32_t*) dv; A.out_pairs = (int32_t*) (dv + 16);
   A.fcan_global = nullptr; A.mcan_global = nullptr;
   const TimedLaunch timing(ctx, L, ctx->stream);
@@ -352,7 +352,7 @@ extern "C" int lsm2d_linearize(lsm2d_context* ctx, const lsm2d_slice_params* sp,
   if (n_pairs) memcpy(L.h_stage, pairs, Y.pair_bytes);
   // up to 8k pairs (a canvas worth): the kernels read the pairs from, and write the sums to, the pinned staging buffer directly
   const bool direct = n_pairs <= 8192;
-  char* dv = (char*) (direct ? L.h_stage_dev : L.d_scratch);
+  char* dv = (char*) (direct ? L.h_stage.dev() : L.d_scratch);
   if (!direct && n_pairs) HIPCHK(ctx, hipMemcpyAsync(L.d_scratch, L.h_stage, Y.pair_bytes, hipMemcpyHostToDevice, ctx->stream));
   LinArgs A;
   A.fixed = cloud_dev(fixed, nullptr); A.moving = cloud_dev(moving, nullptr); A.fc = fi; A.mc = mi;

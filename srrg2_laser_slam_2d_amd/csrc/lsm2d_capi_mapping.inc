@@ -23,11 +23,11 @@ static int beam_dirs_device(lsm2d_context* ctx, const lsm2d_preprocessor* pp, co
   for (const auto& bd : ctx->beam_dirs) if (bd.n_beams == nb && bd.angle_min == pp->angle_min && bd.angle_max == pp->angle_max) { *out = bd.d_dir; return LSM2D_SUCCESS; }
   std::vector<float2> hd((size_t) nb);
   beam_dirs_host(pp, hd.data());
-  float2* d = nullptr;
-  HIPCHK(ctx, hipMalloc((void**) &d, sizeof(float2) * (size_t) nb));
-  hipError_t e = hipMemcpy(d, hd.data(), sizeof(float2) * (size_t) nb, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void) hipFree(d); HIPCHK(ctx, e); }
-  ctx->beam_dirs.push_back({nb, pp->angle_min, pp->angle_max, d}); *out = d;
+  DevBuf<float2> d;
+  HIPCHK(ctx, d.alloc(sizeof(float2) * (size_t) nb));
+  HIPCHK(ctx, hipMemcpy(d, hd.data(), sizeof(float2) * (size_t) nb, hipMemcpyHostToDevice));
+  *out = d;
+  ctx->beam_dirs.push_back({nb, pp->angle_min, pp->angle_max, std::move(d)});
   return LSM2D_SUCCESS;
 }
 // the preprocessing kernels' arguments: the scans' ranges and beam directions in, the clouds of `out` out (a stride of n_beams, made even, per cloud)
@@ -50,38 +50,34 @@ extern "C" int lsm2d_preprocess_scans(lsm2d_context* ctx, const lsm2d_preprocess
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int stride = nb + (nb & 1);
   if ((int64_t) stride * n_scans > 0x7ffffff0) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "preprocess_scans: too many points");
-  lsm2d_cloudset* cs = new (std::nothrow) lsm2d_cloudset;
-  if (!cs) return LSM2D_OUT_OF_MEMORY;
-  cs->ctx = ctx; ctx->live_sets.push_back(cs); cs->n_clouds = n_scans; cs->padded_total = (int64_t) stride * n_scans + 2;
-  cs->h_start.resize(n_scans); cs->h_count.assign(n_scans, 0);
-  for (int c = 0; c < n_scans; ++c) cs->h_start[c] = c * stride;
-  int rc = cloudset_alloc(ctx, cs);
-  if (rc != LSM2D_SUCCESS) { lsm2d_cloudset_destroy(cs); return rc; }
+  CloudsetGuard cs;
+  int rc = cloudset_new(ctx, cs, [&](lsm2d_cloudset* s) { cloudset_slots(s, n_scans, stride); return LSM2D_SUCCESS; });
+  if (rc != LSM2D_SUCCESS) return rc;
   // where the ranges live: device memory is read in place, pinned (or registered) host memory is copied from directly, pageable
   // host memory goes through the context's pinned staging buffer (one more pass over it on the host)
   int rdev = -1;
   const PtrKind kind = pointer_kind(ranges, &rdev);
-  if (kind == PtrKind::device && rdev != ctx->device) { lsm2d_cloudset_destroy(cs); return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans: device-resident ranges must live on the context's device"); }
+  if (kind == PtrKind::device && rdev != ctx->device) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans: device-resident ranges must live on the context's device");
   // (the beam directions travel in the staging buffer on every call here)
   const size_t rbytes = sizeof(float) * (size_t) nb * (size_t) n_scans, dbytes = sizeof(float2) * (size_t) nb;
   const size_t o_rng = (dbytes + 255) & ~(size_t) 255;
-  rc = ensure_scratch(ctx, o_rng + (kind == PtrKind::device ? 0 : rbytes)); if (rc) { lsm2d_cloudset_destroy(cs); return rc; }
-  rc = ensure_stage(ctx, o_rng + (kind == PtrKind::pageable ? rbytes : 0)); if (rc) { lsm2d_cloudset_destroy(cs); return rc; }
+  rc = ensure_scratch(ctx, o_rng + (kind == PtrKind::device ? 0 : rbytes)); if (rc) return rc;
+  rc = ensure_stage(ctx, o_rng + (kind == PtrKind::pageable ? rbytes : 0)); if (rc) return rc;
   Lane& L = lane(ctx);
   if (kind == PtrKind::pageable) memcpy((char*) L.h_stage + o_rng, ranges, rbytes);
   beam_dirs_host(pp, (float2*) L.h_stage);
-  const PrepArgs A = make_prep_args(pp, kind == PtrKind::device ? ranges : (const float*) ((char*) L.d_scratch + o_rng), (const float2*) L.d_scratch, cs);
-  hipError_t e = hipMemcpyAsync(L.d_scratch, L.h_stage, kind == PtrKind::pageable ? o_rng + rbytes : dbytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && kind == PtrKind::pinned) e = hipMemcpyAsync((char*) L.d_scratch + o_rng, ranges, rbytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(L.ev0, ctx->stream);
-  if (e == hipSuccess) { launch_preprocess_scans(A, n_scans, ctx->stream); e = hipGetLastError(); }
-  if (e == hipSuccess && ctx->kernel_timing) e = hipEventRecord(L.ev1, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(cs->h_count.data(), cs->d_count, sizeof(int32_t) * (size_t) n_scans, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = stream_sync(ctx);
-  if (e != hipSuccess) { lsm2d_cloudset_destroy(cs); HIPCHK(ctx, e); }
+  const PrepArgs A = make_prep_args(pp, kind == PtrKind::device ? ranges : (const float*) ((char*) L.d_scratch + o_rng), (const float2*) L.d_scratch, cs.get());
+  HIPCHK(ctx, hipMemcpyAsync(L.d_scratch, L.h_stage, kind == PtrKind::pageable ? o_rng + rbytes : dbytes, hipMemcpyHostToDevice, ctx->stream));
+  if (kind == PtrKind::pinned) HIPCHK(ctx, hipMemcpyAsync((char*) L.d_scratch + o_rng, ranges, rbytes, hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  launch_preprocess_scans(A, n_scans, ctx->stream);
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cs->h_count.data(), cs->d_count, sizeof(int32_t) * (size_t) n_scans, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, stream_sync(ctx));
   note_timed(ctx, ctx->kernel_timing);
   cs->total = 0; for (int c = 0; c < n_scans; ++c) cs->total += cs->h_count[c];
-  *out = cs;
+  *out = cs.release();
   return LSM2D_SUCCESS;
 }
 
@@ -102,11 +98,9 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
   const PtrKind kind = pointer_kind(ranges, &rdev);
   if (kind == PtrKind::device && rdev != ctx->device) return fail(ctx, LSM2D_BAD_ARGUMENT, "preprocess_scans_refill: device-resident ranges must live on the context's device");
   const size_t rbytes = sizeof(float) * (size_t) nb * (size_t) n_scans;
-  // everything derived from the old contents goes -- except the AoS rows, which this launch rewrites in place (hipFree is a device-wide wait)
-  float4* keep_aos = set->d_aos; set->d_aos = nullptr;
-  cloudset_drop_grids(set);
-  set->d_aos = keep_aos;
-  if (kind != PtrKind::device && !set->d_ranges) HIPCHK(ctx, hipMalloc((void**) &set->d_ranges, rbytes));
+  // everything derived from the old contents goes -- except the AoS rows, which this launch rewrites in place (releasing a device buffer is a device-wide wait)
+  cloudset_drop_grids(set, /* keep_aos */ true);
+  if (kind != PtrKind::device && !set->d_ranges) HIPCHK(ctx, set->d_ranges.alloc(rbytes));
   const float2* d_dir = nullptr;
   { const int rc0 = beam_dirs_device(ctx, pp, &d_dir); if (rc0) return rc0; }
   const hipStream_t pre = refill_stream(ctx), cpy = refill_copy_stream(ctx, pre);
@@ -117,7 +111,7 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
     HIPCHK(ctx, hipMemcpyAsync(set->d_ranges, set->h_upload, rbytes, hipMemcpyHostToDevice, cpy));
     set->staged_epoch = ctx->sync_epoch;
     if (cpy != ctx->stream) {      // (round-5 advisor: the epoch above speaks for the context's stream only)
-      if (!set->ev_stage && hipEventCreateWithFlags(&set->ev_stage, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); set->ev_stage = nullptr; }
+      if (!set->ev_stage && set->ev_stage.create(hipEventDisableTiming) != hipSuccess) (void) hipGetLastError();
       if (set->ev_stage) { HIPCHK(ctx, hipEventRecord(set->ev_stage, cpy)); set->stage_on_side = true; }
       else HIPCHK(ctx, hipStreamSynchronize(cpy));
     }
@@ -126,12 +120,12 @@ extern "C" int lsm2d_preprocess_scans_refill(lsm2d_context* ctx, const lsm2d_pre
   if (cpy != pre && kind != PtrKind::device) { HIPCHK(ctx, hipEventRecord(ctx->side_copy.ev, cpy)); HIPCHK(ctx, hipStreamWaitEvent(pre, ctx->side_copy.ev, 0)); }
   ++ctx->uploads; ctx->last_h2d_bytes = kind == PtrKind::device ? 0 : (long long) rbytes;
   PrepArgs A = make_prep_args(pp, kind == PtrKind::device ? ranges : (const float*) set->d_ranges, d_dir, set);
-  A.out_aos = set->d_aos;
+  A.out_aos = set->derived.d_aos;
   launch_preprocess_scans(A, n_scans, pre);
   HIPCHK(ctx, hipGetLastError());
   if (pre != ctx->stream) {
     HIPCHK(ctx, hipEventRecord(ctx->side_refill.ev, pre)); ctx->side_refill.dirty = true;      // the next aligner call waits for it (join_refill_stream)
-    if (!set->ev_prep && hipEventCreateWithFlags(&set->ev_prep, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); set->ev_prep = nullptr; }
+    if (!set->ev_prep && set->ev_prep.create(hipEventDisableTiming) != hipSuccess) (void) hipGetLastError();
     if (set->ev_prep) HIPCHK(ctx, hipEventRecord(set->ev_prep, pre));
     else HIPCHK(ctx, hipStreamSynchronize(pre));      // (no event to be had: the only safe order left)
   }
@@ -155,7 +149,7 @@ extern "C" int lsm2d_preprocess_scan_into(lsm2d_context* ctx, const lsm2d_prepro
   out->unpack_pending = false;                  // an upload nobody read is simply replaced
   int rc = acquire_upload_stage(out, rbytes + 16); if (rc) return rc;
   memcpy(out->h_upload, ranges, rbytes);
-  const PrepArgs A = make_prep_args(pp, (const float*) out->h_upload_dev, d_dir, out);      // the kernel reads the ranges straight from the pinned buffer: no copy, no extra launch
+  const PrepArgs A = make_prep_args(pp, (const float*) out->h_upload.dev(), d_dir, out);      // the kernel reads the ranges straight from the pinned buffer: no copy, no extra launch
   out->h_count[0] = nb; out->total = nb; out->count_pending = true;          // at most one point per beam
   if (!ctx->kernel_timing) {                    // the launch is queued by the set's first reader (flush_pending / flush_preprocessing_together)
     out->prep_pending = true; out->prep_args = A;
@@ -212,7 +206,7 @@ static int clip_scene_impl(lsm2d_context* ctx, const lsm2d_projector* pr, const 
   const bool s_ident = sensor_in_robot[0] == 0.0f && sensor_in_robot[1] == 0.0f && sensor_in_robot[2] == 0.0f;
   A.s_identity = s_ident || vox;                  // voxelisation happens in the sensor frame
   // synchronous form: source indices and the count go straight to the pinned staging buffer (no device-to-host copy)
-  char* dvo = (char*) (out_n ? L.h_stage_dev : L.d_scratch);
+  char* dvo = (char*) (out_n ? L.h_stage.dev() : L.d_scratch);
   if (out_n) *(int32_t*) ((char*) L.h_stage + o_cnt) = kStatusNotWritten;
   A.out_xy = clipped->d_xy; A.out_nrm = clipped->d_nrm; A.out_src = (int32_t*) (dvo + o_src);
   A.out_count = vox ? (int32_t*) ((char*) L.d_scratch + o_cnt) : (int32_t*) (dvo + o_cnt);      // with voxelisation the final count is k_voxelize_clipped's
@@ -292,7 +286,7 @@ extern "C" int lsm2d_merge_scene(lsm2d_context* ctx, const lsm2d_projector* pr, 
   float cam_inv[3]; inverse_host(measurement_in_scene, cam_inv);
   const Iso Tinv = make_iso(cam_inv), M = make_iso(measurement_in_scene);
   char* ds = (char*) L.d_scratch;
-  char* dvo = out_size ? (char*) L.h_stage_dev : ds;      // synchronous form: the four counters go straight to the pinned staging buffer
+  char* dvo = out_size ? (char*) L.h_stage.dev() : ds;      // synchronous form: the four counters go straight to the pinned staging buffer
   if (out_size) *(int32_t*) ((char*) L.h_stage + o_out) = kStatusNotWritten;
   u64* d_scan = (u64*) ds; u64* d_mcan = (u64*) (ds + o_mcan);
   float2* d_txy = (float2*) (ds + o_txy); float2* d_tn = (float2*) (ds + o_tn);
@@ -372,7 +366,7 @@ extern "C" int lsm2d_merge_scenes(lsm2d_context* ctx, const lsm2d_projector* pr,
   int rc = ensure_scratch(ctx, bytes); if (rc) return rc;
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
   Lane& L = lane(ctx);
-  char* dvo = (char*) (out_size ? L.h_stage_dev : L.d_scratch);         // synchronous form: the counters go straight to the pinned staging buffer, the last size last
+  char* dvo = (char*) (out_size ? L.h_stage.dev() : L.d_scratch);         // synchronous form: the counters go straight to the pinned staging buffer, the last size last
   if (out_size) { *(int32_t*) ((char*) L.h_stage + o_out + 16 * (size_t) (n - 1)) = kStatusNotWritten; }
   MergeMultiArgs MM; MM.n = n;
   for (int k = 0; k < n; ++k) {
@@ -438,7 +432,7 @@ static int clip_scene_batch_impl(lsm2d_context* ctx, const lsm2d_projector* pr, 
     items[i].T = make_iso(cam_inv); items[i].start = scenes->h_start[si]; items[i].n = scenes->count_pending ? -1 : scenes->h_count[si]; items[i].si = si; items[i].pad = 0;
   }
   ClipBatchArgs A;
-  A.xy = scenes->d_xy; A.nrm = scenes->d_nrm; A.scene_count_dev = scenes->d_count; A.items = (const ClipBatchItem*) clipped->h_upload_dev;
+  A.xy = scenes->d_xy; A.nrm = scenes->d_nrm; A.scene_count_dev = scenes->d_count; A.items = (const ClipBatchItem*) clipped->h_upload.dev();
   A.proj = P; A.S = make_iso(sensor_in_robot);
   A.s_identity = sensor_in_robot[0] == 0.0f && sensor_in_robot[1] == 0.0f && sensor_in_robot[2] == 0.0f;
   A.out_xy = clipped->d_xy; A.out_nrm = clipped->d_nrm; A.out_stride = clipped->n_clouds > 1 ? clipped->h_start[1] : 0; A.out_count_dev = clipped->d_count;
@@ -446,7 +440,7 @@ static int clip_scene_batch_impl(lsm2d_context* ctx, const lsm2d_projector* pr, 
   Lane& L = lane(ctx);
   int32_t* h_out = (int32_t*) L.h_stage;
   if (out_n) {
-    A.out_count = (int32_t*) L.h_stage_dev;
+    A.out_count = (int32_t*) L.h_stage.dev();
     for (int i = 0; i < n; ++i) h_out[i] = kStatusNotWritten;
   }
   if (vox) {
@@ -543,7 +537,7 @@ extern "C" int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector
   }
   MergeBatchArgs A;
   A.sxy = scenes->d_xy; A.snrm = scenes->d_nrm; A.scene_count_dev = scenes->d_count;
-  A.scenes = (const int4*) scenes->h_upload_dev; A.items = (const MergeBatchItem*) ((char*) scenes->h_upload_dev + o_items);
+  A.scenes = (const int4*) scenes->h_upload.dev(); A.items = (const MergeBatchItem*) ((char*) scenes->h_upload.dev() + o_items);
   for (int k = 0; k < kMergeMulti; ++k) {
     const lsm2d_cloudset* ms = meas[k < nm ? k : 0];
     A.mxy[k] = ms->d_xy; A.mnrm[k] = ms->d_nrm; A.mcount_dev[k] = ms->d_count;
@@ -553,7 +547,7 @@ extern "C" int lsm2d_merge_scene_batch(lsm2d_context* ctx, const lsm2d_projector
   Lane& L = lane(ctx);
   const int32_t* h_out = (const int32_t*) L.h_stage;
   if (out_sizes) {
-    A.out = (int32_t*) L.h_stage_dev;
+    A.out = (int32_t*) L.h_stage.dev();
     for (int i = 0; i < n; ++i) ((int32_t*) L.h_stage)[4 * ((size_t) i * nm + nm - 1)] = kStatusNotWritten;
   } else {
     A.out = (int32_t*) L.d_scratch;
@@ -594,7 +588,7 @@ extern "C" int lsm2d_project(lsm2d_context* ctx, const lsm2d_projector* pr, cons
   rc = ensure_stage(ctx, bytes); if (rc) return rc;
   Lane& L = lane(ctx);
   A.cloud = cloud_dev(cloud, nullptr); A.ci = ci; A.T = make_iso(pose);
-  char* dv = (char*) L.h_stage_dev;       // the canvas rows go straight to pinned host memory
+  char* dv = (char*) L.h_stage.dev();       // the canvas rows go straight to pinned host memory
   A.out_xynn = (float4*) dv;
   A.out_src = (int32_t*) (dv + cols * 16);
   A.out_depth = (float*) (dv + cols * 20);

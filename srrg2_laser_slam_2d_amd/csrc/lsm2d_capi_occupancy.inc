@@ -16,7 +16,7 @@ struct lsm2d_gridset {
   lsm2d_grid_geometry geo = {};
   int32_t n_grids = 0;
   size_t cells_per_grid = 0;
-  uint2* d_cells = nullptr;      // [n_grids][height][width] = {hits, misses}: a cell is one 8-byte access
+  DevBuf<uint2> d_cells;         // [n_grids][height][width] = {hits, misses}: a cell is one 8-byte access
 };
 
 static void orphan_gridsets(lsm2d_context* ctx) { for (lsm2d_gridset* gs : ctx->live_gridsets) gs->ctx = nullptr; }
@@ -34,15 +34,14 @@ extern "C" int lsm2d_gridset_create(lsm2d_context* ctx, const lsm2d_grid_geometr
   const long long per = (long long) geo->width * geo->height;
   if (per * n_grids > (long long) kOccMaxCells) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create: more cells than LSM2D_OCCUPANCY_MAX_CELLS");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  lsm2d_gridset* gs = new (std::nothrow) lsm2d_gridset;
+  struct Destroy { void operator()(lsm2d_gridset* g) const { lsm2d_gridset_destroy(g); } };
+  std::unique_ptr<lsm2d_gridset, Destroy> gs(new (std::nothrow) lsm2d_gridset);      // (as a cloud set: registered at once, destroyed by any return before it is released into *out)
   if (!gs) return LSM2D_OUT_OF_MEMORY;
+  gs->ctx = ctx; ctx->live_gridsets.push_back(gs.get());
   gs->geo = *geo; gs->n_grids = n_grids; gs->cells_per_grid = (size_t) per;
-  DevTmp cells;
-  { const hipError_t e = hipMalloc(&cells.p, sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids); if (e != hipSuccess) { delete gs; HIPCHK(ctx, e); } }
-  { const hipError_t e = hipMemsetAsync(cells.p, 0, sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids, ctx->stream); if (e != hipSuccess) { delete gs; HIPCHK(ctx, e); } }
-  gs->d_cells = (uint2*) cells.release();
-  gs->ctx = ctx; ctx->live_gridsets.push_back(gs);
-  *out = gs;
+  HIPCHK(ctx, gs->d_cells.alloc(sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids));
+  HIPCHK(ctx, hipMemsetAsync(gs->d_cells, 0, sizeof(uint2) * gs->cells_per_grid * (size_t) n_grids, ctx->stream));
+  *out = gs.release();
   return LSM2D_SUCCESS;
 }
 
@@ -54,8 +53,7 @@ extern "C" void lsm2d_gridset_destroy(lsm2d_gridset* gs) {
     auto& v = gs->ctx->live_gridsets;
     for (size_t i = 0; i < v.size(); ++i) if (v[i] == gs) { v[i] = v.back(); v.pop_back(); break; }
   }
-  if (gs->d_cells) (void) hipFree(gs->d_cells);
-  delete gs;
+  delete gs;      // (its cells go with it)
 }
 
 static bool valid_grid_index(const lsm2d_gridset* gs, int32_t i) { return gs && i >= 0 && i < gs->n_grids; }
@@ -79,9 +77,9 @@ extern "C" int lsm2d_gridset_upload(lsm2d_gridset* gs, int32_t grid_index, const
   if (!hits && !misses) return LSM2D_SUCCESS;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = gs->cells_per_grid;
-  DevTmp planar;      // the host arrays as they are; k_occ_put interleaves them (a NULL array leaves its counter)
-  HIPCHK(ctx, hipMalloc(&planar.p, sizeof(uint32_t) * n * 2));
-  uint32_t* const dh = (uint32_t*) planar.p; uint32_t* const dm = dh + n;
+  DevBuf<uint32_t> planar;      // the host arrays as they are; k_occ_put interleaves them (a NULL array leaves its counter)
+  HIPCHK(ctx, planar.alloc(sizeof(uint32_t) * n * 2));
+  uint32_t* const dh = planar; uint32_t* const dm = dh + n;
   if (hits) HIPCHK(ctx, hipMemcpyAsync(dh, hits, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
   if (misses) HIPCHK(ctx, hipMemcpyAsync(dm, misses, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
   OccPutArgs P; P.cells = gs->d_cells + n * (size_t) grid_index; P.hits = hits ? dh : nullptr; P.misses = misses ? dm : nullptr; P.n = (long long) n;

@@ -42,9 +42,9 @@ static bool make_projk(const lsm2d_projector& p, ProjK* k) {
 }
 static CloudDev cloud_dev(const lsm2d_cloudset* cs, const int32_t* d_index) {
   CloudDev c; c.xy = cs->d_xy; c.nrm = cs->d_nrm; c.start = cs->d_start; c.count = cs->d_count; c.index = d_index; c.n_clouds = cs->n_clouds;
-  c.lane_xy = cs->d_lane_xy; c.lane_start = cs->d_lane_start; c.lane_T = cs->d_lane_T; c.lane_bounds = cs->d_lane_bounds;
-  c.block_bounds = cs->d_block_bounds; c.block_stride = cs->block_stride; c.aos = cs->d_aos;
-  c.tile_bounds = cs->d_tile_bounds; c.tile_start = cs->d_tile_start;
+  c.lane_xy = cs->derived.d_lane_xy; c.lane_start = cs->derived.d_lane_start; c.lane_T = cs->derived.d_lane_T; c.lane_bounds = cs->derived.d_lane_bounds;
+  c.block_bounds = cs->derived.d_block_bounds; c.block_stride = cs->block_stride; c.aos = cs->derived.d_aos;
+  c.tile_bounds = cs->derived.d_tile_bounds; c.tile_start = cs->derived.d_tile_start;
   c.grid = GridDev{nullptr, nullptr, nullptr, nullptr, nullptr};
   c.dist = DistDev{nullptr, nullptr};
   c.kd = KdDev{nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -53,7 +53,7 @@ static CloudDev cloud_dev(const lsm2d_cloudset* cs, const int32_t* d_index) {
 // NN finder: uniform grid over every cloud of the (fixed) set, cached per max_distance.  Replaces
 // CorrespondenceFinderKDTree2D::reset() (registration/correspondence_finder_kd_tree_2d.cpp:31-38).
 static int ensure_grid(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_distance, GridDev* out) {
-  for (const auto& g : cs->grids)
+  for (const auto& g : cs->derived.grids)
     if (g.max_distance == max_distance) { *out = GridDev{g.d_meta, g.d_cell_start, g.d_sorted_idx, g.d_sorted_xy, g.d_sorted_nrm}; return LSM2D_SUCCESS; }
   const int nc = cs->n_clouds;
   std::vector<int32_t> cell_base(nc), gcap(nc);
@@ -67,15 +67,14 @@ static int ensure_grid(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_d
     gcap[c] = cap; cell_base[c] = (int32_t) cells; cells += (int64_t) cap * cap + 1;
     if (cells > 0x7fffffff) return fail(ctx, LSM2D_CAPACITY_EXCEEDED, "grid: too many cells");
   }
-  GridCache g; g.max_distance = max_distance;
-  DevTmp t_block;
+  GridCache g; g.max_distance = max_distance;      // (published to the set only once built: an early return takes the block with it)
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; };
   const size_t o_meta = take(sizeof(GridMeta) * (size_t) nc), o_start = take(sizeof(int32_t) * (size_t) cells), o_cursor = take(sizeof(int32_t) * (size_t) cells);
   const size_t o_sidx = take(sizeof(int32_t) * (size_t) cs->padded_total), o_sxy = take(sizeof(float2) * (size_t) cs->padded_total), o_snr = take(sizeof(float2) * (size_t) cs->padded_total);
   const size_t o_base = take(sizeof(int32_t) * (size_t) nc), o_gcap = take(sizeof(int32_t) * (size_t) nc), o_tiles = take(sizeof(int32_t) * 2048);
-  HIPCHK(ctx, hipMalloc(&t_block.p, off));
-  char* blk = (char*) t_block.p;
+  HIPCHK(ctx, g.d_block.alloc(off));
+  char* blk = (char*) g.d_block;
   g.d_meta = (GridMeta*) (blk + o_meta); g.d_cell_start = (int32_t*) (blk + o_start); g.d_cursor = (int32_t*) (blk + o_cursor);
   g.d_sorted_idx = (int32_t*) (blk + o_sidx); g.d_sorted_xy = (float2*) (blk + o_sxy); g.d_sorted_nrm = (float2*) (blk + o_snr);
   int32_t* d_base = (int32_t*) (blk + o_base); int32_t* d_gcap = (int32_t*) (blk + o_gcap); int32_t* d_tiles = (int32_t*) (blk + o_tiles);
@@ -106,9 +105,8 @@ static int ensure_grid(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_d
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, stream_sync(ctx));      // host vectors above must outlive the copies
-  g.d_block = t_block.release();      // owned by the cache from here on
-  cs->grids.push_back(g);
   *out = GridDev{g.d_meta, g.d_cell_start, g.d_sorted_idx, g.d_sorted_xy, g.d_sorted_nrm};
+  cs->derived.grids.push_back(std::move(g));
   return LSM2D_SUCCESS;
 }
 
@@ -120,14 +118,15 @@ static int ensure_grid(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_d
 // side by side by ONE launch with ONE wait for the trees' sizes (kd_scan_launch).
 static constexpr int kKdScanCap = 1280;      // points per cloud the LDS layout is sized for (58 KB)
 struct KdScanPrep {
-  const lsm2d_cloudset* cs = nullptr; KdCache kc; DevTmp block; KdBuildScanArgs W; std::vector<KdMeta> h_meta;
+  const lsm2d_cloudset* cs = nullptr; KdCache kc; KdBuildScanArgs W;      // (kc owns the block until kd_scan_launch publishes it)
+  std::vector<KdMeta> h_meta;
 };
 static void kd_defaults(float& max_leaf_range, int& min_leaf_points) {      // the class defaults (correspondence_finder_kd_tree_2d.h:26-33), as the oracle applies them
   if (!(max_leaf_range > 0.0f)) max_leaf_range = 1e-2f;
   if (min_leaf_points <= 0) min_leaf_points = 20;
 }
 static const KdCache* kd_cached(const lsm2d_cloudset* cs, float max_leaf_range, int min_leaf_points) {
-  for (const auto& k : cs->kds) if (k.valid && k.max_leaf_range == max_leaf_range && k.min_leaf_points == min_leaf_points) return &k;
+  for (const auto& k : cs->derived.kds) if (k.valid && k.max_leaf_range == max_leaf_range && k.min_leaf_points == min_leaf_points) return &k;
   return nullptr;
 }
 static bool kd_scan_eligible(const lsm2d_context* ctx, const lsm2d_cloudset* cs) {
@@ -135,6 +134,27 @@ static bool kd_scan_eligible(const lsm2d_context* ctx, const lsm2d_cloudset* cs)
   if (nc < 1 || nc > ctx->kd_scan_max_clouds || nc > 8 || cs->count_pending || (int) kd_scan_lds_bytes(kKdScanCap) > ctx->max_dyn_lds) return false;
   for (int c = 0; c < nc; ++c) if (cs->h_count[c] > kKdScanCap || cs->h_count[c] > ctx->kd_wg_max_points) return false;
   return true;
+}
+// The block the trees of a set are built into (meta, `nodes` nodes, the leaf-order arrays), owned by `kc` until the build has succeeded, and kc's views into it:
+// the block a reserved single-cloud set kept across a change of its contents (cloudset_drop_grids) moves out of the set when it is large enough, else it goes
+// and a new one is allocated
+static int kd_take_block(lsm2d_context* ctx, const lsm2d_cloudset* cs, long long nodes, KdCache& kc) {
+  const size_t np = (size_t) cs->padded_total;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; };
+  const size_t o_meta = take(sizeof(KdMeta) * (size_t) cs->n_clouds), o_nodes = take(sizeof(KdNode) * (size_t) nodes);
+  const size_t o_lxy = take(sizeof(float2) * np), o_lidx = take(sizeof(int32_t) * np), o_lnr = take(sizeof(float2) * np);
+  std::vector<KdCache>& kds = cs->derived.kds;
+  kc.block_bytes = off;
+  if (kds.size() == 1 && !kds[0].valid) {
+    if (kds[0].d_block && kds[0].block_bytes >= off) { kc.d_block = std::move(kds[0].d_block); kc.block_bytes = kds[0].block_bytes; }
+    kds.clear();
+  }
+  if (!kc.d_block) HIPCHK(ctx, kc.d_block.alloc(off));
+  char* blk = (char*) kc.d_block;
+  kc.d_meta = (KdMeta*) (blk + o_meta); kc.d_nodes = (KdNode*) (blk + o_nodes);
+  kc.d_leaf_xy = (float2*) (blk + o_lxy); kc.d_leaf_idx = (int32_t*) (blk + o_lidx); kc.d_leaf_nrm = (float2*) (blk + o_lnr);
+  return LSM2D_SUCCESS;
 }
 // the set's block (recycled for a reserved single-cloud set) and the kernel's arguments; no GPU work
 static int kd_scan_prepare(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_leaf_range, int min_leaf_points, KdScanPrep& P) {
@@ -146,22 +166,8 @@ static int kd_scan_prepare(lsm2d_context* ctx, const lsm2d_cloudset* cs, float m
     const long long room = cs->capacity > 0 ? cs->capacity : cs->h_count[c];      // (a reserved set: for whatever it may hold later -- its allocation is recycled)
     nodes += 2ll * room > 2 ? 2ll * room : 2;
   }
-  const size_t np = (size_t) cs->padded_total;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; };
-  const size_t o_meta = take(sizeof(KdMeta) * (size_t) nc), o_nodes = take(sizeof(KdNode) * (size_t) nodes);
-  const size_t o_lxy = take(sizeof(float2) * np), o_lidx = take(sizeof(int32_t) * np), o_lnr = take(sizeof(float2) * np);
-  const bool recycle = cs->kds.size() == 1 && !cs->kds[0].valid && cs->kds[0].d_block && cs->kds[0].block_bytes >= off;
-  P.kc.block_bytes = off;
-  if (recycle) { P.block.p = cs->kds[0].d_block; P.kc.block_bytes = cs->kds[0].block_bytes; cs->kds.clear(); }      // (owned by the guard again until the build has succeeded)
-  else {
-    if (cs->kds.size() == 1 && !cs->kds[0].valid) { if (cs->kds[0].d_block) (void) hipFree(cs->kds[0].d_block); cs->kds.clear(); }
-    HIPCHK(ctx, hipMalloc(&P.block.p, off));
-  }
-  char* blk = (char*) P.block.p;
   KdCache& kc = P.kc;
-  kc.d_meta = (KdMeta*) (blk + o_meta); kc.d_nodes = (KdNode*) (blk + o_nodes);
-  kc.d_leaf_xy = (float2*) (blk + o_lxy); kc.d_leaf_idx = (int32_t*) (blk + o_lidx); kc.d_leaf_nrm = (float2*) (blk + o_lnr);
+  { const int rc = kd_take_block(ctx, cs, nodes, kc); if (rc) return rc; }
   KdBuildArgs B;
   B.start = cs->d_start; B.meta = kc.d_meta; B.nodes = kc.d_nodes; B.n_nodes = nullptr;
   B.leaf_xy = kc.d_leaf_xy; B.leaf_idx = kc.d_leaf_idx; B.max_leaf_range = max_leaf_range; B.min_leaf_points = min_leaf_points;
@@ -193,8 +199,7 @@ static int kd_scan_launch(lsm2d_context* ctx, KdScanPrep* P, int count) {
     kc.levels = 0; kc.total_nodes = 0; kc.max_nodes_per_cloud = 0;
     for (const KdMeta& m : P[i].h_meta) { kc.total_nodes += m.n_nodes; if (m.n_nodes > kc.max_nodes_per_cloud) kc.max_nodes_per_cloud = m.n_nodes; if (m.pad0 > kc.levels) kc.levels = m.pad0; }
     ctx->last_kd_levels = kc.levels; ctx->last_kd_nodes = kc.total_nodes;
-    kc.d_block = P[i].block.release();      // owned by the cache from here on
-    P[i].cs->kds.push_back(kc);
+    P[i].cs->derived.kds.push_back(std::move(kc));
   }
   return LSM2D_SUCCESS;
 }
@@ -208,7 +213,7 @@ static int ensure_kdtree(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max
     KdScanPrep P;
     int rc = kd_scan_prepare(ctx, cs, max_leaf_range, min_leaf_points, P); if (rc) return rc;
     rc = kd_scan_launch(ctx, &P, 1); if (rc) return rc;
-    const KdCache& k = cs->kds.back();
+    const KdCache& k = cs->derived.kds.back();
     *out = KdDev{k.d_meta, k.d_nodes, k.d_leaf_xy, k.d_leaf_idx, k.d_leaf_nrm}; if (out_cache) *out_cache = &k;
     return LSM2D_SUCCESS;
   }
@@ -225,30 +230,13 @@ static int ensure_kdtree(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max
   const size_t np = (size_t) cs->padded_total, nq = np / 2 + (size_t) nc + 2;
   constexpr int kMaxLevels = 8192;
   KdCache kc; kc.max_leaf_range = max_leaf_range; kc.min_leaf_points = min_leaf_points;
-  DevTmp t_block;
+  { const int rc = kd_take_block(ctx, cs, nodes, kc); if (rc) return rc; }
+  // working set of the build: two ping-pong copies of (xy, idx), two queues, per-cloud node counters, one queue counter per level
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; };
-  const size_t o_meta = take(sizeof(KdMeta) * (size_t) nc), o_nodes = take(sizeof(KdNode) * (size_t) nodes);
-  const size_t o_lxy = take(sizeof(float2) * np), o_lidx = take(sizeof(int32_t) * np), o_lnr = take(sizeof(float2) * np);
-  const bool recycle = cs->kds.size() == 1 && !cs->kds[0].valid && cs->kds[0].d_block && cs->kds[0].block_bytes >= off;
-  kc.block_bytes = off;
-  if (recycle) { t_block.p = cs->kds[0].d_block; kc.block_bytes = cs->kds[0].block_bytes; cs->kds.clear(); }      // (owned by the guard again until the build has succeeded)
-  else {
-    if (cs->kds.size() == 1 && !cs->kds[0].valid) { if (cs->kds[0].d_block) (void) hipFree(cs->kds[0].d_block); cs->kds.clear(); }
-    HIPCHK(ctx, hipMalloc(&t_block.p, off));
-  }
-  char* blk = (char*) t_block.p;
-  kc.d_meta = (KdMeta*) (blk + o_meta); kc.d_nodes = (KdNode*) (blk + o_nodes);
-  kc.d_leaf_xy = (float2*) (blk + o_lxy); kc.d_leaf_idx = (int32_t*) (blk + o_lidx); kc.d_leaf_nrm = (float2*) (blk + o_lnr);
-  // working set of the build: two ping-pong copies of (xy, idx), two queues, per-cloud node counters, one queue counter per level
-  off = 0;
   const size_t w_xy0 = take(sizeof(float2) * np), w_xy1 = take(sizeof(float2) * np), w_ix0 = take(sizeof(int32_t) * np), w_ix1 = take(sizeof(int32_t) * np);
   const size_t w_q0 = take(sizeof(int4) * nq), w_q1 = take(sizeof(int4) * nq), w_nn = take(sizeof(int32_t) * (size_t) nc), w_cnt = take(sizeof(int32_t) * (size_t) (kMaxLevels + 1));
-  if (off > ctx->d_kd_work_bytes) {
-    if (ctx->d_kd_work) { HIPCHK(ctx, stream_sync(ctx)); HIPCHK(ctx, hipFree(ctx->d_kd_work)); ctx->d_kd_work = nullptr; ctx->d_kd_work_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&ctx->d_kd_work, off + off / 2));
-    ctx->d_kd_work_bytes = off + off / 2;
-  }
+  HIPCHK(ctx, ctx->d_kd_work.ensure(off, off + off / 2, wait_for_stream(ctx)));
   char* wk = (char*) ctx->d_kd_work;
   float2* xyb[2] = {(float2*) (wk + w_xy0), (float2*) (wk + w_xy1)}; int32_t* ixb[2] = {(int32_t*) (wk + w_ix0), (int32_t*) (wk + w_ix1)};
   int4* qb[2] = {(int4*) (wk + w_q0), (int4*) (wk + w_q1)};
@@ -339,21 +327,20 @@ static int ensure_kdtree(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max
     if (cs->h_count[c] <= wg_max && h_meta[(size_t) c].pad0 > kc.levels) kc.levels = h_meta[(size_t) c].pad0;
   }
   ctx->last_kd_levels = kc.levels; ctx->last_kd_nodes = kc.total_nodes;
-  kc.d_block = t_block.release();      // owned by the cache from here on (the working set goes with its guard)
-  cs->kds.push_back(kc);
   *out = KdDev{kc.d_meta, kc.d_nodes, kc.d_leaf_xy, kc.d_leaf_idx, kc.d_leaf_nrm};
-  if (out_cache) *out_cache = &cs->kds.back();
+  cs->derived.kds.push_back(std::move(kc));
+  if (out_cache) *out_cache = &cs->derived.kds.back();
   return LSM2D_SUCCESS;
 }
 
-static CloudDev cloud_dev_with_tiles(CloudDev c, const lsm2d_cloudset* cs) { c.tile_bounds = cs->d_tile_bounds; c.tile_start = cs->d_tile_start; return c; }
+static CloudDev cloud_dev_with_tiles(CloudDev c, const lsm2d_cloudset* cs) { c.tile_bounds = cs->derived.d_tile_bounds; c.tile_start = cs->derived.d_tile_start; return c; }
 
 // lane-chunked copy of every cloud for k_align's projective streaming pass (project_cloud_lanes in lsm2d_device.h), with the bounding circles of
 // every thread's chunk and of every block of it (the exact culling).  Everything is built into guarded temporaries and PUBLISHED to the set only
 // after the last launch has finished (round-3 advisor: a failure half-way used to leave d_lane_xy set and never filled -- the next call streamed
 // uninitialised memory).
 static int ensure_lane_layout(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
-  if (cs->d_lane_xy || cs->count_pending) return LSM2D_SUCCESS;     // a size-pending set is a clipped scene: small, and building needs a sync
+  if (cs->derived.d_lane_xy || cs->count_pending) return LSM2D_SUCCESS;     // a size-pending set is a clipped scene: small, and building needs a sync
   const int nc = cs->n_clouds;
   bool any_big = false;                       // every cloud <= one pair per thread: the plain layout already is lane-chunked
   for (int c = 0; c < nc; ++c) if (((long long) cs->h_count[c] + 1) / 2 > kAlignBlock) { any_big = true; break; }
@@ -375,14 +362,12 @@ static int ensure_lane_layout(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
   // stream of the shared instantiation (proj_culled_for_all needs block_bounds)
   const int nbs = kCullBlocks;      // blocks per chunk (lsm2d_kernels.h)
   const bool want_blocks = sizeof(float4) * (size_t) nc * nbs * kAlignBlock <= ((size_t) 256 << 20);
-  DevTmp t_xy, t_bounds, t_blocks, t_start, t_T;
-  HIPCHK(ctx, hipMalloc(&t_xy.p, sizeof(float4) * (size_t) slots));
-  HIPCHK(ctx, hipMalloc(&t_bounds.p, sizeof(float4) * (size_t) nc * kAlignBlock));
-  if (want_blocks) HIPCHK(ctx, hipMalloc(&t_blocks.p, sizeof(float4) * (size_t) nc * nbs * kAlignBlock));
-  HIPCHK(ctx, hipMalloc(&t_start.p, sizeof(long long) * (size_t) nc));
-  HIPCHK(ctx, hipMalloc(&t_T.p, sizeof(int32_t) * (size_t) nc));
-  float4* d_xy = (float4*) t_xy.p; float4* d_bounds = (float4*) t_bounds.p; float4* d_blocks = (float4*) t_blocks.p;
-  long long* d_start = (long long*) t_start.p; int32_t* d_T = (int32_t*) t_T.p;
+  DevBuf<float4> d_xy, d_bounds, d_blocks; DevBuf<long long> d_start; DevBuf<int32_t> d_T;
+  HIPCHK(ctx, d_xy.alloc(sizeof(float4) * (size_t) slots));
+  HIPCHK(ctx, d_bounds.alloc(sizeof(float4) * (size_t) nc * kAlignBlock));
+  if (want_blocks) HIPCHK(ctx, d_blocks.alloc(sizeof(float4) * (size_t) nc * nbs * kAlignBlock));
+  HIPCHK(ctx, d_start.alloc(sizeof(long long) * (size_t) nc));
+  HIPCHK(ctx, d_T.alloc(sizeof(int32_t) * (size_t) nc));
   HIPCHK(ctx, hipMemsetAsync(d_xy + (slots - 2 * kAlignBlock), 0x7f, sizeof(float4) * 2 * kAlignBlock, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_start, lstart.data(), sizeof(long long) * (size_t) nc, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_T, lT.data(), sizeof(int32_t) * (size_t) nc, hipMemcpyHostToDevice, ctx->stream));
@@ -400,28 +385,28 @@ static int ensure_lane_layout(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
   }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));        // the host vectors above back the async copies; and only a finished build is published
-  cs->d_lane_xy = (float4*) t_xy.release(); cs->d_lane_bounds = (float4*) t_bounds.release(); cs->d_block_bounds = (float4*) t_blocks.release();
-  cs->d_lane_start = (long long*) t_start.release(); cs->d_lane_T = (int32_t*) t_T.release();
+  cs->derived.d_lane_xy = std::move(d_xy); cs->derived.d_lane_bounds = std::move(d_bounds); cs->derived.d_block_bounds = std::move(d_blocks);
+  cs->derived.d_lane_start = std::move(d_start); cs->derived.d_lane_T = std::move(d_T);
   cs->block_stride = nbs;
   return LSM2D_SUCCESS;
 }
 
 // (x, y, nx, ny) rows of the whole set: k_align's bin walk gathers a z-buffer winner's point and normal as one 16-byte row
 static int ensure_aos(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
-  if (cs->d_aos || cs->count_pending || cs->unpack_pending || cs->prep_pending) return LSM2D_SUCCESS;      // (a set still changing on the device is gathered from its split arrays)
-  DevTmp t;
-  HIPCHK(ctx, hipMalloc(&t.p, sizeof(float4) * (size_t) cs->padded_total));
+  if (cs->derived.d_aos || cs->count_pending || cs->unpack_pending || cs->prep_pending) return LSM2D_SUCCESS;      // (a set still changing on the device is gathered from its split arrays)
+  DevBuf<float4> t;
+  HIPCHK(ctx, t.alloc(sizeof(float4) * (size_t) cs->padded_total));
   long long blocks = (cs->padded_total + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_aos_rows, dim3((unsigned) blocks), dim3(256), 0, ctx->stream, (const float2*) cs->d_xy, (const float2*) cs->d_nrm, (long long) cs->padded_total, (float4*) t.p);
+  hipLaunchKernelGGL(k_aos_rows, dim3((unsigned) blocks), dim3(256), 0, ctx->stream, (const float2*) cs->d_xy, (const float2*) cs->d_nrm, (long long) cs->padded_total, t);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));
-  cs->d_aos = (float4*) t.release();
+  cs->derived.d_aos = std::move(t);
   return LSM2D_SUCCESS;
 }
 
 // bounding circles of every cloud's tiles of 64 consecutive points: what k_align's point-query branch tests before it runs a tile's queries
 static int ensure_tile_bounds(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
-  if (cs->d_tile_bounds || cs->count_pending) return LSM2D_SUCCESS;
+  if (cs->derived.d_tile_bounds || cs->count_pending) return LSM2D_SUCCESS;
   const int nc = cs->n_clouds;
   std::vector<int32_t> tstart((size_t) nc);
   long long tiles = 0; int max_tiles = 1;
@@ -430,32 +415,31 @@ static int ensure_tile_bounds(lsm2d_context* ctx, const lsm2d_cloudset* cs) {
     tstart[c] = (int32_t) tiles; tiles += t; if (t > max_tiles) max_tiles = t;
     if (tiles > 0x7fffffff) return LSM2D_SUCCESS;          // (no culling for such a set)
   }
-  DevTmp t_bounds, t_start;      // published only when complete (see ensure_lane_layout)
-  HIPCHK(ctx, hipMalloc(&t_bounds.p, sizeof(float4) * (size_t) (tiles > 0 ? tiles : 1)));
-  HIPCHK(ctx, hipMalloc(&t_start.p, sizeof(int32_t) * (size_t) nc));
-  HIPCHK(ctx, hipMemcpyAsync(t_start.p, tstart.data(), sizeof(int32_t) * (size_t) nc, hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<float4> t_bounds; DevBuf<int32_t> t_start;      // published only when complete (see ensure_lane_layout)
+  HIPCHK(ctx, t_bounds.alloc(sizeof(float4) * (size_t) (tiles > 0 ? tiles : 1)));
+  HIPCHK(ctx, t_start.alloc(sizeof(int32_t) * (size_t) nc));
+  HIPCHK(ctx, hipMemcpyAsync(t_start, tstart.data(), sizeof(int32_t) * (size_t) nc, hipMemcpyHostToDevice, ctx->stream));
   int gx = (max_tiles + 3) / 4; if (gx > 4096) gx = 4096; if (gx < 1) gx = 1;
   for (int c0 = 0; c0 < nc; c0 += 32768) {
     const int ny = nc - c0 < 32768 ? nc - c0 : 32768;
     hipLaunchKernelGGL(k_tile_bounds, dim3((unsigned) gx, (unsigned) ny), dim3(256), 0, ctx->stream, (const float2*) cs->d_xy, (const int32_t*) cs->d_start,
-                       (const int32_t*) cs->d_count, (const int32_t*) t_start.p, (float4*) t_bounds.p, c0);
+                       (const int32_t*) cs->d_count, (const int32_t*) t_start, t_bounds, c0);
   }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));        // the host vector above backs the async copy
-  cs->d_tile_bounds = (float4*) t_bounds.release(); cs->d_tile_start = (int32_t*) t_start.release();
+  cs->derived.d_tile_bounds = std::move(t_bounds); cs->derived.d_tile_start = std::move(t_start);
   return LSM2D_SUCCESS;
 }
 
 // Distance-map finder: CorrespondenceFinderNN2D::reset() (registration/correspondence_finder_nn_2d.cpp:10-52,84-97) for every
 // cloud of the (fixed) set, cached per (max_distance, resolution).
 static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float max_distance, float resolution, DistDev* out) {
-  for (const auto& d : cs->dists)
+  for (const auto& d : cs->derived.dists)
     if (d.max_distance == max_distance && d.resolution == resolution) { *out = DistDev{d.d_meta, d.d_parent}; return LSM2D_SUCCESS; }
   if (!(resolution > 0.0f) || max_distance < 0.0f) return fail(ctx, LSM2D_BAD_ARGUMENT, "distmap: resolution must be > 0 and max_distance >= 0");
   const int nc = cs->n_clouds;
-  DevTmp t_bbox;
-  HIPCHK(ctx, hipMalloc(&t_bbox.p, sizeof(float4) * (size_t) nc));
-  float4* d_bbox = (float4*) t_bbox.p;
+  DevBuf<float4> d_bbox;
+  HIPCHK(ctx, d_bbox.alloc(sizeof(float4) * (size_t) nc));
   hipLaunchKernelGGL(k_cloud_bbox, dim3((unsigned) nc), dim3(256), 0, ctx->stream, (const float2*) cs->d_xy, (const int32_t*) cs->d_start,
                      (const int32_t*) cs->d_count, d_bbox);
   HIPCHK(ctx, hipGetLastError());
@@ -484,10 +468,9 @@ static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float ma
   const bool scatter = ctx->distmap_build != 1 && R <= 511 && (((long long) R * R + 1) << gbits) <= (1ll << 31);
   for (auto& m : meta) { m.gbits = scatter ? gbits : 31; m.gmask = scatter ? (int32_t) ((1u << gbits) - 1u) : 0x7fffffff; }
   DistCache d; d.max_distance = max_distance; d.resolution = resolution;
-  DevTmp t_dmeta, t_parent, t_goal;
-  HIPCHK(ctx, hipMalloc(&t_dmeta.p, sizeof(DistMeta) * (size_t) nc));
-  HIPCHK(ctx, hipMalloc(&t_parent.p, sizeof(int32_t) * (size_t) total));
-  d.d_meta = (DistMeta*) t_dmeta.p; d.d_parent = (int32_t*) t_parent.p;
+  DevBuf<int32_t> d_cellgoal;      // (the gather build's working set: goes with this call)
+  HIPCHK(ctx, d.d_meta.alloc(sizeof(DistMeta) * (size_t) nc));
+  HIPCHK(ctx, d.d_parent.alloc(sizeof(int32_t) * (size_t) total));
   HIPCHK(ctx, hipMemcpyAsync(d.d_meta, meta.data(), sizeof(DistMeta) * (size_t) nc, hipMemcpyHostToDevice, ctx->stream));
   if (scatter) {
     HIPCHK(ctx, hipMemsetAsync(d.d_parent, 0xff, sizeof(int32_t) * (size_t) total, ctx->stream));
@@ -495,11 +478,10 @@ static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float ma
     for (int c0 = 0; c0 < nc; c0 += 32768) {         // gridDim.y is limited to 65535
       const int ny = nc - c0 < 32768 ? nc - c0 : 32768;
       hipLaunchKernelGGL(k_distmap_stamp, dim3((unsigned) sb, (unsigned) ny), dim3(256), 0, ctx->stream, (const float2*) cs->d_xy,
-                         (const int32_t*) cs->d_start, (const int32_t*) cs->d_count, (const DistMeta*) d.d_meta, (uint32_t*) d.d_parent, mds_px, R, c0);
+                         (const int32_t*) cs->d_start, (const int32_t*) cs->d_count, (const DistMeta*) d.d_meta, (uint32_t*) d.d_parent.get(), mds_px, R, c0);      // (the stamps are unsigned minima over the map's int32 cells)
     }
   } else {
-    HIPCHK(ctx, hipMalloc(&t_goal.p, sizeof(int32_t) * (size_t) total));
-    int32_t* d_cellgoal = (int32_t*) t_goal.p;
+    HIPCHK(ctx, d_cellgoal.alloc(sizeof(int32_t) * (size_t) total));
     HIPCHK(ctx, hipMemsetAsync(d_cellgoal, 0x7f, sizeof(int32_t) * (size_t) total, ctx->stream));
     int gb = (max_pts + 255) / 256; if (gb > 1024) gb = 1024;
     int fb = (max_rows_cols + 255) / 256; if (fb > 4096) fb = 4096; if (fb < 1) fb = 1;
@@ -516,9 +498,8 @@ static int ensure_distmap(lsm2d_context* ctx, const lsm2d_cloudset* cs, float ma
   }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));
-  t_dmeta.release(); t_parent.release();          // owned by the cache from here on (t_goal is freed by its guard)
-  cs->dists.push_back(d);
   *out = DistDev{d.d_meta, d.d_parent};
+  cs->derived.dists.push_back(std::move(d));
   return LSM2D_SUCCESS;
 }
 
