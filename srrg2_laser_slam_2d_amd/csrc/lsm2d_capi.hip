@@ -21,6 +21,7 @@ using lsm2d::LSM2D_RUNNING;
 #include <thread>
 #include <atomic>
 #include <memory>
+#include <optional>
 
 using namespace lsm2d;
 
@@ -605,9 +606,9 @@ static int ensure_scratch(lsm2d_context* ctx, size_t bytes) { return ensure_scra
 #include "lsm2d_capi_structures.inc"
 #include "lsm2d_capi_mapping.inc"
 #include "lsm2d_capi_finder.inc"
+#include "lsm2d_capi_select.inc"
 #include "lsm2d_capi_aligner.inc"
 #include "lsm2d_capi_sweep.inc"
-#include "lsm2d_capi_select_grouped.inc"
 #include "lsm2d_capi_relocalize.inc"
 #include "lsm2d_capi_score_grid.inc"
 #include "lsm2d_capi_voxelize.inc"

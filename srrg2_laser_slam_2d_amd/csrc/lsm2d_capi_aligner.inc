@@ -149,7 +149,6 @@ struct AlignBatch {
   int launch();
   int hand_over();
   int select_finish();
-  int select_finish_grouped();
 };
 
 int AlignBatch::validate_and_lay_out_scratch() {
@@ -744,7 +743,7 @@ int AlignBatch::launch() {
 }
 
 int AlignBatch::hand_over() {
-  if (select) return reloc ? reloc_finish() : (groups ? select_finish_grouped() : select_finish());
+  if (select) return reloc ? reloc_finish() : select_finish();
   // ---- the batch is queued.  What its results need: kept in a lsm2d_pending (the caller's for an asynchronous begin, a local one otherwise)
   lsm2d_pending local; lsm2d_pending& P = pend ? *pend : local;
   P.ctx = ctx; P.lane = L;
@@ -761,77 +760,37 @@ int AlignBatch::hand_over() {
 }
 
 // Select mode's second half.  Behind the aligner's launch on the same stream: k_align_rows packs every candidate's results and the LAST statistics row it
-// started into an AlignRow and counts the Success and the never-written statuses into the two words behind the selection's accepted count; select_queue ranks the
-// rows, ends the timing bracket (the aligner's launch PLUS the selection), copies [n_accepted, n_selected, n_success, n_unwritten | index[k] | rows[k]] down
-// and waits -- the one copy and the one wait of the call.  The never-reported check of align_batch_finish is the fourth header word.
+// started into an AlignRow and counts the Success and the never-written statuses of the whole batch; select_queue / select_queue_grouped (lsm2d_capi_select.inc)
+// rank the rows, end the timing bracket (the aligner's launch PLUS the selection), copy the blocks [n_accepted, n_selected, n_success, n_unwritten | index[k] |
+// rows[k]] down -- one, or one per group with the group's n_success and the batch's n_unwritten -- and wait: the one copy and the one wait of the call.  Group
+// g's rows land in slots g * k + j.  The never-reported check of align_batch_finish is the first block's fourth header word.
 int AlignBatch::select_finish() {
-  const SelectLayout E((size_t) n, (size_t) select_k, AlignRow::kWords);
+  const SelectLayout E1((size_t) n, (size_t) select_k, AlignRow::kWords);      // (the ungrouped call's; `groups` is the grouped one's)
   char* const d = (char*) L->d_scratch;      // (== ds: select mode never takes the zero-copy form)
   char* const de = d + o_sel;
-  HIPCHK(ctx, hipMemsetAsync(de + E.e_acc, 0, sizeof(int32_t) * 3, ks));      // accepted | Success | never written
+  // the counters: ungrouped [accepted | Success | never written], three words; grouped [Success | never written | accepted[G]], of which select_queue_grouped
+  // zeroes the accepted words where its launches add to them.  k_align_rows counts into the two words [Success | never written] either way.
+  int32_t* const counts = (int32_t*) (de + (groups ? groups->e_acc : E1.e_acc + sizeof(int32_t)));
+  if (groups) HIPCHK(ctx, hipMemsetAsync(counts, 0, sizeof(int32_t) * 2, ks));
+  else HIPCHK(ctx, hipMemsetAsync(counts - 1, 0, sizeof(int32_t) * 3, ks));
   AlignRowsArgs R;
   R.pose = (const float*) (d + o_pose); R.H = (const float*) (d + o_H); R.status = (const int32_t*) (d + o_status); R.its = (const int32_t*) (d + o_its);
   R.stats = (const StatsDev*) (d + o_stats); R.n = n; R.stats_stride = stats_stride; R.not_written = kStatusNotWritten;
-  R.rows = (float*) (d + o_rows); R.counts = (int32_t*) (de + E.e_acc) + 1;
+  R.rows = (float*) (d + o_rows); R.counts = counts;
   hipLaunchKernelGGL(k_align_rows<AlignRow>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ks, R);
   HIPCHK(ctx, hipGetLastError());
-  SelectArgs S;
-  S.rows = R.rows; S.n_items = n; S.k = select_k;
-  S.min_inliers = select->min_inliers; S.max_chi_per_inlier = select->max_chi_per_inlier; S.min_inlier_ratio = select->min_inlier_ratio;
-  { const int rc = select_queue<AlignRow>(ctx, "align_select", S, E, de, hs + o_sel); if (rc) return rc; }
-  const int32_t* h = (const int32_t*) (hs + o_sel);
-  const int32_t n_acc = h[0], n_sel = h[1], n_success = h[2], n_unwritten = h[3];
-  if (n_unwritten != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
-  if (n_success < n_acc || n_success > n) return fail(ctx, LSM2D_DEVICE_ERROR, "align_select: the selection's counters are inconsistent");
-  const int32_t* h_index = h + kSelectHeaderWords; const int32_t* h_rows = h + kSelectHeaderWords + select_k;
-  for (int32_t j = 0; j < n_sel; ++j) {
-    const int32_t* row = h_rows + AlignRow::kWords * (size_t) j;
-    sel_index[j] = h_index[j];
-    memcpy(out_pose + 3 * (size_t) j, row + AlignRow::kPose, sizeof(float) * 3);
-    if (out_H) memcpy(out_H + 9 * (size_t) j, row + AlignRow::kH, sizeof(float) * 9);
-    if (out_its) out_its[j] = row[AlignRow::kIts];
-    if (sel_last_stats) memcpy(sel_last_stats + j, row + AlignRow::kStats, sizeof(lsm2d_iteration_stats));
+  const SelectArgs S = select_args(R.rows, n, select_k, select);
+  const int32_t* const h = (const int32_t*) (hs + o_sel);
+  {
+    const int rc = groups ? select_queue_grouped<AlignRow>(ctx, "align_select_grouped", S, *groups, de, (const int32_t*) (d + o_gtab), hs + o_sel)
+                          : select_queue<AlignRow>(ctx, "align_select", S, E1, de, hs + o_sel);
+    if (rc) return rc;
   }
-  *sel_n_selected = n_sel; *sel_n_accepted = n_acc;
-  if (sel_n_success) *sel_n_success = n_success;
-  return LSM2D_SUCCESS;
-}
-
-// ... per group: the same packing (k_align_rows still makes the rows and the ONE global never-written count), then select_queue_grouped.  Group g's block
-// comes down as [n_accepted, n_selected, n_success of the group, never-reported of the batch | index[k] | rows[k]] and lands in slots g * k + j.
-int AlignBatch::select_finish_grouped() {
-  const SelectGroupedLayout& E = *groups;
-  char* const d = (char*) L->d_scratch;
-  char* const de = d + o_sel;
-  HIPCHK(ctx, hipMemsetAsync(de + E.e_acc, 0, sizeof(int32_t) * 2, ks));      // Success | never written (the groups' accepted words lie behind them)
-  AlignRowsArgs R;
-  R.pose = (const float*) (d + o_pose); R.H = (const float*) (d + o_H); R.status = (const int32_t*) (d + o_status); R.its = (const int32_t*) (d + o_its);
-  R.stats = (const StatsDev*) (d + o_stats); R.n = n; R.stats_stride = stats_stride; R.not_written = kStatusNotWritten;
-  R.rows = (float*) (d + o_rows); R.counts = (int32_t*) (de + E.e_acc);
-  hipLaunchKernelGGL(k_align_rows<AlignRow>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ks, R);
-  HIPCHK(ctx, hipGetLastError());
-  SelectArgs S;
-  S.rows = R.rows; S.n_items = n; S.k = select_k;
-  S.min_inliers = select->min_inliers; S.max_chi_per_inlier = select->max_chi_per_inlier; S.min_inlier_ratio = select->min_inlier_ratio;
-  { const int rc = select_queue_grouped<AlignRow>(ctx, "align_select_grouped", S, E, de, (const int32_t*) (d + o_gtab), hs + o_sel); if (rc) return rc; }
-  const int32_t* h0 = (const int32_t*) (hs + o_sel);
-  if (h0[3] != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
-  const size_t K = (size_t) select_k;
-  for (size_t g = 0; g < E.G; ++g) {
-    const int32_t* h = h0 + E.group_words * g;
-    const int32_t* h_index = h + kSelectHeaderWords; const int32_t* h_rows = h + kSelectHeaderWords + K;
-    for (int32_t j = 0; j < h[1]; ++j) {
-      const int32_t* row = h_rows + AlignRow::kWords * (size_t) j;
-      const size_t slot = g * K + (size_t) j;
-      sel_index[slot] = h_index[j];
-      memcpy(out_pose + 3 * slot, row + AlignRow::kPose, sizeof(float) * 3);
-      if (out_H) memcpy(out_H + 9 * slot, row + AlignRow::kH, sizeof(float) * 9);
-      if (out_its) out_its[slot] = row[AlignRow::kIts];
-      if (sel_last_stats) memcpy(sel_last_stats + slot, row + AlignRow::kStats, sizeof(lsm2d_iteration_stats));
-    }
-    sel_n_selected[g] = h[1]; sel_n_accepted[g] = h[0];
-    if (sel_n_success) sel_n_success[g] = h[2];
-  }
+  if (h[3] != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
+  if (!groups && !select_header_ok(h, n, select_k, true)) return fail(ctx, LSM2D_DEVICE_ERROR, "align_select: the selection's counters are inconsistent");
+  const size_t G = groups ? groups->G : 1, K = (size_t) select_k, words = select_block_words(K, AlignRow::kWords);
+  for (size_t g = 0; g < G; ++g) align_block_out(h + words * g, K, g * K, nullptr, sel_index, out_pose, out_H, out_its, sel_last_stats);
+  groups_report(h, words, G, sel_n_selected, sel_n_accepted, sel_n_success);
   return LSM2D_SUCCESS;
 }
 
@@ -926,25 +885,45 @@ extern "C" int lsm2d_align_batch(lsm2d_context* ctx, const lsm2d_aligner_params*
 
 // ---- aligned, accepted and ranked: the candidate loops' verdict with k rows coming down (include/lsm2d.h).  The alignment is lsm2d_align_batch's with statistics
 // (the same stages, path rule, kernels and launch forms); synchronous, on the context's current lane like every other call.
-extern "C" int lsm2d_align_select(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, const lsm2d_select_params* select, int32_t k,
-                                  int32_t* out_index, float* out_pose, float* out_H, int32_t* out_its, lsm2d_iteration_stats* out_last_stats,
-                                  int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
-  if (!ctx || !ap || !b || !select || !out_index || !out_pose || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_select: null argument");
-  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_select: k outside [1, LSM2D_SELECT_MAX_K]");
+// (grouped: the fleet's candidate loop, ranked per group of the batch -- the groups' table rides up in the input block; lsm2d_capi_select.inc)
+static int align_select_impl(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, const lsm2d_select_params* select, int32_t k, bool grouped,
+                             int32_t n_groups, const int32_t* group_offsets, int32_t* out_index, float* out_pose, float* out_H, int32_t* out_its,
+                             lsm2d_iteration_stats* out_last_stats, int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  const char* const who = grouped ? "align_select_grouped" : "align_select";
+  if (!ctx || !ap || !b || !select || !out_index || !out_pose || !out_n_selected || !out_n_accepted) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
+  if (k < 1 || k > kSelectMaxK) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: k outside [1, LSM2D_SELECT_MAX_K]", who);
   if (lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, "align_batch: two batches are in flight on this context: wait for the older one first (lsm2d_align_batch_wait)");
+  std::optional<SelectGroupedLayout> E;
+  if (grouped) {
+    const int rc = check_groups(ctx, who, n_groups, group_offsets, b->n_alignments, k); if (rc) return rc;
+    E.emplace(group_offsets, (size_t) n_groups, (size_t) k, (size_t) AlignRow::kWords);
+  }
   static int32_t wanted_status; static lsm2d_iteration_stats wanted_stats;      // (the stages ask "is this output wanted?" of the pointers: statuses and statistics are, on the device)
   AlignBatch B;
   B.ctx = ctx; B.L = &lane(ctx); B.ap = ap; B.b = b; B.out_pose = out_pose; B.out_H = out_H; B.out_status = &wanted_status; B.out_its = out_its;
   B.out_stats = &wanted_stats; B.out_last_pose = nullptr; B.out_work = nullptr; B.pend = nullptr;
   B.select = select; B.select_k = k; B.sel_index = out_index; B.sel_last_stats = out_last_stats; B.sel_n_selected = out_n_selected; B.sel_n_accepted = out_n_accepted;
-  B.sel_n_success = out_n_success;
-  if (b->n_alignments == 0) {      // an empty batch: its descriptor is checked as ever, the counts are zeros
+  B.sel_n_success = out_n_success; B.groups = E ? &*E : nullptr;
+  if (b->n_alignments == 0) {      // an empty batch: its descriptor is checked as ever, the counts (every group's) are zeros
     const int rc = B.validate_and_lay_out_scratch();
     if (rc != kEmptyBatch) return rc;
-    *out_n_selected = 0; *out_n_accepted = 0; if (out_n_success) *out_n_success = 0;
+    groups_report(nullptr, 0, E ? E->G : 1, out_n_selected, out_n_accepted, out_n_success);
     return LSM2D_SUCCESS;
   }
   return align_batch_run(B);
+}
+
+extern "C" int lsm2d_align_select(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, const lsm2d_select_params* select, int32_t k,
+                                  int32_t* out_index, float* out_pose, float* out_H, int32_t* out_its, lsm2d_iteration_stats* out_last_stats,
+                                  int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  return align_select_impl(ctx, ap, b, select, k, false, 1, nullptr, out_index, out_pose, out_H, out_its, out_last_stats, out_n_selected, out_n_accepted, out_n_success);
+}
+
+extern "C" int lsm2d_align_select_grouped(lsm2d_context* ctx, const lsm2d_aligner_params* ap, const lsm2d_batch* b, const lsm2d_select_params* select, int32_t k,
+                                          int32_t n_groups, const int32_t* group_offsets, int32_t* out_index, float* out_pose, float* out_H, int32_t* out_its,
+                                          lsm2d_iteration_stats* out_last_stats, int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
+  return align_select_impl(ctx, ap, b, select, k, true, n_groups, group_offsets, out_index, out_pose, out_H, out_its, out_last_stats, out_n_selected, out_n_accepted,
+                           out_n_success);
 }
 
 // ---- a batch in flight: MultiAligner2D::compute over a batch, split where the host would otherwise sleep.  begin() queues everything -- inputs, placement,

@@ -1,6 +1,6 @@
 // lsm2d_capi_finder.inc -- plugin interface #1 (CorrespondenceFinder_::compute for the four finder kinds), the factor over a correspondence vector, and both
-// for a whole batch: apart (lsm2d_find_correspondences_batch, lsm2d_linearize_batch) and with the pairs kept on the device (lsm2d_score_batch,
-// lsm2d_score_select; for a whole aligner: lsm2d_score_aligner_batch, lsm2d_score_aligner_select).  The steps these entry points share are stated once, up front: what a refusal says (failf), the cloud sets settled (settle_sets),
+// for a whole batch: apart (lsm2d_find_correspondences_batch, lsm2d_linearize_batch) and with the pairs kept on the device (lsm2d_score_batch; for a whole
+// aligner: lsm2d_score_aligner_batch; the select calls that rank those rows on the device are in lsm2d_capi_select.inc, behind this part).  The steps these entry points share are stated once, up front: what a refusal says (failf), the cloud sets settled (settle_sets),
 // the timing bracket round a call's launches (TimedLaunch), a batch's head checks and index rules (batch_head, resolve_items), how many items a launch
 // takes (items_per_launch) and what a result row of the factor means (lin_row_out).  Where a call's parts lie in the lane's buffers is a *Layout struct.
 // Part of lsm2d_capi.hip (included there); not a translation unit of its own.
@@ -565,100 +565,6 @@ extern "C" int lsm2d_score_batch(lsm2d_context* ctx, const lsm2d_slice_params* s
   return LSM2D_SUCCESS;
 }
 
-// ---- ... and ranked on the device: the acceptance test and the best k (lsm2d_k_select.h) ------------------------------------------------------------------------
-// Behind the last launch group, on the same stream: keys and the accepted count (k_select_keys), passes of k_select_tile over two ping-pong arrays of (key,
-// index) entries until one tile is left -- a pass turns m entries into ceil(m / tile) x k, less than half of them while m > tile -- and k_select_gather,
-// which fills the one region that comes down: [n_accepted, n_selected, 0, 0 | index[k] | rows[k][kLinOutWords]], 16 + 68 k bytes whatever n_items is.  A
-// batch of at most one tile does all three in ONE launch (k_select_tile_one: four launches and a memset less, which is what counts at 1000 items).
-// (SelectLayout and select_queue also serve lsm2d_capi_aligner.inc, which is included behind this file: lsm2d_align_select ranks AlignRow rows with them.)
-// where the selection's own part of the scratch lies: [keys A | index A] of n entries, [keys B | index B] of what the first pass leaves, the accepted count,
-// the region that goes down ([header | index[k] | rows[k][row_words]]: down_bytes)
-struct SelectLayout {
-  size_t n, K, e_idx_a, e_key_b, e_idx_b, e_acc, e_down, down_bytes, d_bytes;
-  SelectLayout(size_t n_, size_t K_, size_t row_words) : n(n_), K(K_) {
-    const size_t n_first = ((n + kSelectTile - 1) / kSelectTile) * K;      // what the first pass leaves
-    e_idx_a = up256(sizeof(u64) * n); e_key_b = up256(e_idx_a + sizeof(int32_t) * n); e_idx_b = up256(e_key_b + sizeof(u64) * n_first);
-    e_acc = up256(e_idx_b + sizeof(int32_t) * n_first); e_down = e_acc + 256;
-    down_bytes = sizeof(int32_t) * (kSelectHeaderWords + K) + sizeof(float) * row_words * K;
-    d_bytes = e_down + down_bytes;
-  }
-};
-
-// The selection's launches over rows of format Row, behind the scoring on the same stream; `de`: the selection's part of the scratch; `down`: where the
-// region that goes down is written (select_queue: de + E.e_down; lsm2d_relocalize_select: next to the second stage's, so that one copy takes both).  Waits
-// for nothing, copies nothing.  A (rows, n_items, k, thresholds) is the caller's.
-template <class Row>
-static int select_launches(lsm2d_context* ctx, SelectArgs A, const SelectLayout& E, char* de, int32_t* down) {
-  const size_t n = E.n, K = E.K;
-  u64* key[2] = {(u64*) de, (u64*) (de + E.e_key_b)}; int32_t* idx[2] = {(int32_t*) (de + E.e_idx_a), (int32_t*) (de + E.e_idx_b)};
-  A.keys = key[0]; A.index = idx[0]; A.n_accepted = (int32_t*) (de + E.e_acc);
-  if (n <= (size_t) kSelectTile) {      // one tile: keys, sort and gather in one launch of one workgroup
-    int32_t sort_size = 2;
-    while ((size_t) sort_size < n) sort_size <<= 1;
-    hipLaunchKernelGGL(k_select_tile_one<Row>, dim3(1), dim3(kSelectBlock), 0, ctx->stream, A, sort_size, down);
-  } else {
-    HIPCHK(ctx, hipMemsetAsync(A.n_accepted, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(k_select_keys<Row>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
-    size_t m = n; int src = 0;
-    for (;;) {      // array A has room for n entries, B for n_first: pass p writes fewer than pass p - 2 read
-      const size_t tiles = (m + kSelectTile - 1) / kSelectTile;
-      hipLaunchKernelGGL(k_select_tile, dim3((unsigned) tiles), dim3(kSelectBlock), 0, ctx->stream, (const u64*) key[src], (const int32_t*) idx[src], (int32_t) m,
-                         A.k, key[src ^ 1], idx[src ^ 1]);
-      src ^= 1; m = tiles * K;
-      if (tiles == 1) break;
-    }
-    hipLaunchKernelGGL(k_select_gather<Row>, dim3(1), dim3(256), 0, ctx->stream, A, (const u64*) key[src], (const int32_t*) idx[src], down);
-  }
-  return LSM2D_SUCCESS;
-}
-
-// ... and the rest of a select call: the launches above, the end of the timing bracket, the one copy down to `h_down`, the wait (the one wait of the call) and
-// the check of the counters.
-template <class Row>
-static int select_queue(lsm2d_context* ctx, const char* who, SelectArgs A, const SelectLayout& E, char* de, char* h_down) {
-  Lane& L = lane(ctx);
-  { const int rc = select_launches<Row>(ctx, A, E, de, (int32_t*) (de + E.e_down)); if (rc) return rc; }
-  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
-  HIPCHK(ctx, hipMemcpyAsync(h_down, de + E.e_down, E.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
-  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
-  const int32_t* h = (const int32_t*) h_down;
-  const int32_t n_acc = h[0], n_sel = h[1];
-  if (n_acc < 0 || n_acc > A.n_items || n_sel != (n_acc < A.k ? n_acc : A.k)) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the selection's counters are inconsistent", who);
-  return LSM2D_SUCCESS;
-}
-
-extern "C" int lsm2d_score_select(lsm2d_context* ctx, const lsm2d_slice_params* sp, const lsm2d_cloudset* fixed, const int32_t* fixed_index,
-                                  const lsm2d_cloudset* moving, const int32_t* moving_index, int32_t n_items, const float* poses,
-                                  const lsm2d_select_params* select, int32_t k, int32_t* out_index, float* out_H, float* out_b, lsm2d_iteration_stats* out_stats,
-                                  int32_t* out_n_selected, int32_t* out_n_accepted) {
-  static_assert(LSM2D_SELECT_MAX_K == kSelectMaxK, "the ABI's limit is the kernels'");
-  if (!select || !out_index || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: null argument");
-  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: k outside [1, LSM2D_SELECT_MAX_K]");
-  { const int rc = batch_head(ctx, "score_select", sp, fixed, moving, n_items, 0); if (rc) return rc; }
-  if (n_items == 0) { *out_n_selected = 0; *out_n_accepted = 0; return LSM2D_SUCCESS; }
-  if (!poses) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_select: null argument");
-  const size_t K = (size_t) k;
-  const SelectLayout E((size_t) n_items, K, kLinOutWords);
-  ScoreLayout Y;
-  { const int rc = score_batch_queue(ctx, "score_select", sp, fixed, fixed_index, moving, moving_index, n_items, poses, E.d_bytes, E.down_bytes, Y); if (rc) return rc; }
-  Lane& L = lane(ctx);
-  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
-  SelectArgs A;
-  A.rows = (const float*) (ds + Y.o_out); A.n_items = n_items; A.k = k;
-  A.min_inliers = select->min_inliers; A.max_chi_per_inlier = select->max_chi_per_inlier; A.min_inlier_ratio = select->min_inlier_ratio;
-  { const int rc = select_queue<ScoreRow>(ctx, "score_select", A, E, ds + Y.o_extra, hs + Y.h_out); if (rc) return rc; }
-  const int32_t* h = (const int32_t*) (hs + Y.h_out);
-  const int32_t n_acc = h[0], n_sel = h[1];
-  const int32_t* h_index = h + kSelectHeaderWords; const float* h_rows = (const float*) (h + kSelectHeaderWords + K);
-  float H[9], b[3];
-  for (int32_t j = 0; j < n_sel; ++j) {
-    out_index[j] = h_index[j];
-    lin_row_out(h_rows + kLinOutWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : H, out_b ? out_b + 3 * (size_t) j : b, out_stats ? out_stats + j : nullptr);
-  }
-  *out_n_selected = n_sel; *out_n_accepted = n_acc;
-  return LSM2D_SUCCESS;
-}
-
 // ---- hypotheses scored against an ALIGNER: all its slices, sensor offsets, the skip rule, the prior (lsm2d_k_score_aligner.h) ---------------------------------
 // Up, once: poses, priors (as PriorDev, the aligner's own host-side form) and the per-slice index tables.  k_score_aligner_items turns them into every
 // slice's FindItem table on the device; then slice after slice runs lsm2d_score_batch's launch groups (score_slice_queue) on its OWN items, counts, digests
@@ -819,147 +725,4 @@ extern "C" int lsm2d_score_aligner_batch(lsm2d_context* ctx, const lsm2d_batch* 
   for (size_t k = 0; k < Y.n; ++k)
     comb_row_out((const float*) (hs + Y.h_out) + kCombWords * k, out_H + 9 * k, out_b + 3 * k, out_stats ? out_stats + k : nullptr, out_active ? out_active + k : nullptr);
   return LSM2D_SUCCESS;
-}
-
-extern "C" int lsm2d_score_aligner_select(lsm2d_context* ctx, const lsm2d_batch* batch, const lsm2d_select_params* select, int32_t k, int32_t* out_index,
-                                          float* out_H, float* out_b, lsm2d_iteration_stats* out_stats, int32_t* out_active, int32_t* out_n_selected,
-                                          int32_t* out_n_accepted) {
-  static const char who[] = "score_aligner_select";
-  if (!select || !out_index || !out_n_selected || !out_n_accepted) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_aligner_select: null argument");
-  if (k < 1 || k > kSelectMaxK) return fail(ctx, LSM2D_BAD_ARGUMENT, "score_aligner_select: k outside [1, LSM2D_SELECT_MAX_K]");
-  { const int rc = score_aligner_head(ctx, who, batch); if (rc) return rc; }
-  if (batch->n_alignments == 0) { *out_n_selected = 0; *out_n_accepted = 0; return LSM2D_SUCCESS; }
-  const size_t K = (size_t) k;
-  const SelectLayout E((size_t) batch->n_alignments, K, kCombWords);
-  ScoreAlignerLayout Y;
-  { const int rc = score_aligner_queue(ctx, who, batch, E.d_bytes, E.down_bytes, Y); if (rc) return rc; }
-  Lane& L = lane(ctx);
-  char* const hs = (char*) L.h_stage; char* const ds = (char*) L.d_scratch;
-  HIPCHK(ctx, hipGetLastError());
-  SelectArgs A;
-  A.rows = (const float*) (ds + Y.o_comb); A.n_items = batch->n_alignments; A.k = k;
-  A.min_inliers = select->min_inliers; A.max_chi_per_inlier = select->max_chi_per_inlier; A.min_inlier_ratio = select->min_inlier_ratio;
-  { const int rc = select_queue<CombRow>(ctx, who, A, E, ds + Y.o_extra, hs + Y.h_out); if (rc) return rc; }
-  const int32_t* h = (const int32_t*) (hs + Y.h_out);
-  const int32_t n_acc = h[0], n_sel = h[1];
-  const int32_t* h_index = h + kSelectHeaderWords; const float* h_rows = (const float*) (h + kSelectHeaderWords + K);
-  for (int32_t j = 0; j < n_sel; ++j) {
-    out_index[j] = h_index[j];
-    comb_row_out(h_rows + kCombWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : nullptr, out_b ? out_b + 3 * (size_t) j : nullptr, out_stats ? out_stats + j : nullptr,
-                 out_active ? out_active + j : nullptr);
-  }
-  *out_n_selected = n_sel; *out_n_accepted = n_acc;
-  return LSM2D_SUCCESS;
-}
-
-// ---- ... ranked PER GROUP of the batch: the fleet's form of the three select calls (lsm2d_k_select_grouped.h) --------------------------------------------------
-// Group g is items [off[g], off[g + 1]); every group gets the block the ungrouped call returns for its sub-batch, indices shifted by off[g].  The host knows
-// every group's size, so it lays out every launch: a table [offsets | one closing descriptor per group | keys descriptors | the passes' descriptors] rides up
-// with the call's arguments, in the same copy.  Every group at most one tile: ONE launch, a workgroup per group, and the table is the offsets alone.
-// Otherwise: keys over (group, chunk) descriptors, passes of k_select_tile_seg over the groups that are still larger than a tile -- group g's m entries
-// become ceil(m / tile) x k, in its own stretch of the other array -- and k_select_gather_group, which sorts what is left of every group and gathers.
-// (Here: the checks, the layout and select_queue_grouped, beside select_queue.  The three entry points are in lsm2d_capi_select_grouped.inc, the last include
-// part: what instantiates the grouped kernels comes behind every older kernel's first use, so those keep their places in the code object.)
-
-// offsets: n_groups + 1 values, non-decreasing, from 0 to n; n_groups x k within LSM2D_SELECT_MAX_GROUP_ROWS
-static int check_groups(lsm2d_context* ctx, const char* who, int32_t n_groups, const int32_t* off, int32_t n, int32_t k) {
-  static_assert(LSM2D_SELECT_MAX_GROUP_ROWS == (1 << 18), "the ABI's cap");
-  if (!off) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: null argument", who);
-  if (n_groups < 1) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: n_groups must be >= 1", who);
-  if ((long long) n_groups * (long long) k > (long long) LSM2D_SELECT_MAX_GROUP_ROWS)
-    return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: n_groups x k above LSM2D_SELECT_MAX_GROUP_ROWS", who);
-  if (off[0] != 0 || off[n_groups] != n) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: group_offsets must start at 0 and end at the batch's size", who);
-  for (int32_t g = 0; g < n_groups; ++g)
-    if (off[g + 1] < off[g]) return failf(ctx, LSM2D_BAD_ARGUMENT, "%s: group_offsets decrease at group %d", who, (int) g);
-  return LSM2D_SUCCESS;
-}
-
-// The table that rides up (words), where the selection's own part of the scratch lies -- [keys A | index A] of n entries, [keys B | index B] of what the first
-// pass leaves, [Success, never written | accepted[G]], the region that goes down -- and every launch of the segmented form.
-struct SelectGroupedLayout {
-  struct Pass { size_t t_off, count; };
-  size_t n, G, K, group_words, n_b = 0;
-  bool one_tile = true;
-  std::vector<int32_t> table; size_t t_fin = 0, t_keys = 0, n_keys = 0; std::vector<Pass> passes;      // (t_*: word offsets of SelectSeg arrays in the table)
-  size_t e_idx_a = 0, e_key_b = 0, e_idx_b = 0, e_acc = 0, e_down = 0, down_bytes = 0, d_bytes = 0;
-  size_t table_bytes() const { return sizeof(int32_t) * table.size(); }
-  SelectGroupedLayout(const int32_t* off, size_t G_, size_t K_, size_t row_words) : n((size_t) off[G_]), G(G_), K(K_), group_words(kSelectHeaderWords + K_ + K_ * row_words) {
-    static_assert(sizeof(SelectSeg) == 4 * sizeof(int32_t), "a descriptor is four words of the table");
-    for (size_t g = 0; g < G; ++g) if (off[g + 1] - off[g] > kSelectTile) one_tile = false;
-    table.assign(off, off + G + 1);
-    if (!one_tile) {
-      const auto push = [this](int32_t a, int32_t b, int32_t c, int32_t d) { table.push_back(a); table.push_back(b); table.push_back(c); table.push_back(d); };
-      while (table.size() % 4) table.push_back(0);
-      t_fin = table.size(); table.resize(t_fin + 4 * G, 0);      // filled once the passes are known
-      t_keys = table.size();
-      for (size_t g = 0; g < G; ++g)
-        for (int32_t c = off[g]; c < off[g + 1]; c += 256) { push(c, std::min<int32_t>(256, off[g + 1] - c), 0, (int32_t) g); ++n_keys; }
-      std::vector<int32_t> base(off, off + G), cnt(G), b_base(G, 0);
-      for (size_t g = 0; g < G; ++g) {
-        cnt[g] = off[g + 1] - off[g];
-        if (cnt[g] > kSelectTile) { b_base[g] = (int32_t) n_b; n_b += (size_t) ((cnt[g] + kSelectTile - 1) / kSelectTile) * K; }      // (< cnt[g]: n_b < n)
-      }
-      for (int src = 0;; src ^= 1) {      // a pass reads array `src` and writes the other: a group's stretch of A is its items', of B what its first pass left
-        Pass P = {table.size(), 0};
-        for (size_t g = 0; g < G; ++g) {
-          if (cnt[g] <= kSelectTile) continue;
-          const int32_t tiles = (cnt[g] + kSelectTile - 1) / kSelectTile, out = src ? off[g] : b_base[g];
-          for (int32_t j = 0; j < tiles; ++j) push(base[g] + j * kSelectTile, std::min<int32_t>(kSelectTile, cnt[g] - j * kSelectTile), out + j * (int32_t) K, 0);
-          P.count += (size_t) tiles; base[g] = out; cnt[g] = tiles * (int32_t) K;      // (tiles >= 2: tiles x k <= tiles x tile / 2 < the entries that came in)
-          table[t_fin + 4 * g + 3] = src ^ 1;
-        }
-        if (!P.count) break;
-        passes.push_back(P);
-      }
-      for (size_t g = 0; g < G; ++g) { table[t_fin + 4 * g] = base[g]; table[t_fin + 4 * g + 1] = cnt[g]; }
-      e_idx_a = up256(sizeof(u64) * n); e_key_b = up256(e_idx_a + sizeof(int32_t) * n); e_idx_b = up256(e_key_b + sizeof(u64) * n_b);
-      e_acc = up256(e_idx_b + sizeof(int32_t) * n_b);
-    }
-    e_down = up256(e_acc + sizeof(int32_t) * (2 + G));
-    down_bytes = sizeof(int32_t) * group_words * G;
-    d_bytes = e_down + down_bytes;
-  }
-};
-
-// select_queue for groups: the launches behind the scoring on the same stream, the end of the timing bracket, the one copy down to `h_down`, the one wait,
-// every group's counters checked.  `d_table`: where the layout's table lies on the device.  (A format that carries counts: the caller has zeroed the two
-// words at de + e_acc and queued the kernel that counts into them.)
-template <class Row>
-static int select_queue_grouped(lsm2d_context* ctx, const char* who, SelectArgs S, const SelectGroupedLayout& E, char* de, const int32_t* d_table, char* h_down) {
-  Lane& L = lane(ctx);
-  int32_t* const acc = (int32_t*) (de + E.e_acc);
-  u64* const key_b = (u64*) (de + E.e_key_b); int32_t* const idx_b = (int32_t*) (de + E.e_idx_b);
-  S.keys = (u64*) de; S.index = (int32_t*) (de + E.e_idx_a); S.n_accepted = acc + 2;
-  SelectGroupedArgs A;
-  A.S = S; A.offsets = d_table; A.unwritten = SelectCarriesCounts<Row>::value ? acc + 1 : nullptr; A.down = (int32_t*) (de + E.e_down);
-  if (E.one_tile) hipLaunchKernelGGL(k_select_group_one<Row>, dim3((unsigned) E.G), dim3(kSelectBlock), 0, ctx->stream, A);
-  else {
-    HIPCHK(ctx, hipMemsetAsync(S.n_accepted, 0, sizeof(int32_t) * E.G, ctx->stream));
-    hipLaunchKernelGGL(k_select_keys_seg<Row>, dim3((unsigned) E.n_keys), dim3(256), 0, ctx->stream, A, (const SelectSeg*) (d_table + E.t_keys));
-    int src = 0;
-    for (const SelectGroupedLayout::Pass& P : E.passes) {
-      hipLaunchKernelGGL(k_select_tile_seg<kSelectTile>, dim3((unsigned) P.count), dim3(kSelectBlock), 0, ctx->stream, (const u64*) (src ? key_b : S.keys),
-                         (const int32_t*) (src ? idx_b : S.index), src ? S.keys : key_b, src ? S.index : idx_b, (const SelectSeg*) (d_table + P.t_off), S.k);
-      src ^= 1;
-    }
-    hipLaunchKernelGGL(k_select_gather_group<Row>, dim3((unsigned) E.G), dim3(kSelectBlock), 0, ctx->stream, A, (const SelectSeg*) (d_table + E.t_fin),
-                       (const u64*) key_b, (const int32_t*) idx_b);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, TimedLaunch(ctx, L, ctx->stream).end());      // the last launch group and the selection
-  HIPCHK(ctx, hipMemcpyAsync(h_down, de + E.e_down, E.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
-  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
-  for (size_t g = 0; g < E.G; ++g) {
-    const int32_t* h = (const int32_t*) h_down + E.group_words * g;
-    const int32_t size = E.table[g + 1] - E.table[g], n_acc = h[0], n_sel = h[1];
-    bool ok = n_acc >= 0 && n_acc <= size && n_sel == (n_acc < S.k ? n_acc : S.k);
-    if (SelectCarriesCounts<Row>::value) ok = ok && h[2] >= n_acc && h[2] <= size;
-    if (!ok) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the selection's counters are inconsistent (group %d)", who, (int) g);
-  }
-  return LSM2D_SUCCESS;
-}
-
-// an empty batch with groups: every group reports 0 accepted and 0 selected
-static void groups_report_empty(int32_t n_groups, int32_t* out_n_selected, int32_t* out_n_accepted, int32_t* out_n_success) {
-  for (int32_t g = 0; g < n_groups; ++g) { out_n_selected[g] = 0; out_n_accepted[g] = 0; if (out_n_success) out_n_success[g] = 0; }
 }

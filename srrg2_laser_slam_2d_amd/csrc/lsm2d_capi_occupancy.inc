@@ -1,7 +1,6 @@
 // lsm2d_capi_occupancy.inc -- occupancy grids on the device: grid sets (create, clear, upload, download, destroy), lsm2d_occupancy_update (the points of
 // device-resident clouds ray-traced from their sensor poses into hit / miss counters) and lsm2d_occupancy_render (include/lsm2d.h; PARITY.md section 3,
-// item 17c; not in the reference, which has no grid mapper).  Part of lsm2d_capi.hip, included LAST: what launches the kernels of lsm2d_k_occupancy.h comes
-// behind every older kernel's first use.
+// item 17c; not in the reference, which has no grid mapper).  Part of lsm2d_capi.hip.
 //
 // lsm2d_occupancy_update:
 //   up          the call's tables -- per input (transform, ray start, where its points begin, its grid), the concatenation offsets, the inputs' boxes as
@@ -83,7 +82,7 @@ extern "C" int lsm2d_gridset_upload(lsm2d_gridset* gs, int32_t grid_index, const
   if (hits) HIPCHK(ctx, hipMemcpyAsync(dh, hits, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
   if (misses) HIPCHK(ctx, hipMemcpyAsync(dm, misses, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
   OccPutArgs P; P.cells = gs->d_cells + n * (size_t) grid_index; P.hits = hits ? dh : nullptr; P.misses = misses ? dm : nullptr; P.n = (long long) n;
-  hipLaunchKernelGGL(k_occ_put<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
+  hipLaunchKernelGGL(k_occ_put, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, stream_sync(ctx));
   return LSM2D_SUCCESS;
@@ -185,13 +184,13 @@ extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, 
     R.xy = src->d_xy; R.inputs = (const OccInput*) (ds + Y.u_inputs); R.offset = (const int32_t*) (ds + Y.u_offset); R.n_inputs = n_inputs; R.n = n; R.G = G;
     R.rays = (int4*) (ds + Y.o_rays); R.box = (int32_t*) (ds + Y.u_box);
     R.n_rays = (int32_t*) (ds + Y.o_down + Y.d_rays); R.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped); R.fault = d_fault;
-    hipLaunchKernelGGL(k_occ_rays<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
+    hipLaunchKernelGGL(k_occ_rays, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
     HIPCHK(ctx, hipGetLastError());
     OccTilesArgs T;
     T.rays = R.rays; T.offset = R.offset; T.box = R.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_inputs; T.n = n; T.G = G;
     T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
     if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
-    hipLaunchKernelGGL(k_occ_tiles<kOccTile>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
+    hipLaunchKernelGGL(k_occ_tiles, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
     HIPCHK(ctx, hipGetLastError());
   }
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
@@ -233,7 +232,7 @@ extern "C" int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* g
   OccRenderArgs R; R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.min_visits = params->min_visits; R.out = (int8_t*) L.d_scratch;
   ctx->have_timing = false;
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
-  hipLaunchKernelGGL(k_occ_render<kOccTile>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
+  hipLaunchKernelGGL(k_occ_render, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
   HIPCHK(ctx, hipGetLastError());
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);

@@ -1,6 +1,6 @@
 // lsm2d_capi_relocalize.inc -- the relocaliser / loop detector's candidate loop in ONE call (lsm2d_relocalize_select, include/lsm2d.h; MULTI.json:749-769,
 // :964-986): lsm2d_score_aligner_select's scoring and selection, then lsm2d_align_select over the selected hypotheses, with nothing coming down in between.
-// Part of lsm2d_capi.hip, included LAST: what launches the kernels of lsm2d_k_relocalize.h comes behind every older kernel's first use.
+// Part of lsm2d_capi.hip, included behind the aligner's and the selection's parts, whose stages it chains.
 //
 //   stage 1   score_aligner_queue and the selection's launches (select_launches<CombRow>) on the context's CURRENT lane, exactly as lsm2d_score_aligner_select
 //             queues them -- but the region that goes down is written into the OTHER lane's scratch, and nothing is copied or waited for.
@@ -25,12 +25,6 @@ struct RelocStage {
   int32_t* out_scored_index = nullptr; lsm2d_iteration_stats* out_scored_stats = nullptr; int32_t* out_n_scored_selected = nullptr; int32_t* out_n_scored_accepted = nullptr;
 };
 
-// select_launches, named through a template of this part's own: the compiler instantiates a function template where it is FIRST named, and the selection's
-// kernels with it.  Named directly down here, select_launches<CombRow> and <AlignRow> would be instantiated here, behind the grouped kernels, instead of
-// inside select_queue where they always were -- and every kernel behind them would be renumbered in the code object.
-template <class Row>
-static int reloc_select_launches(lsm2d_context* ctx, const SelectArgs& A, const SelectLayout& E, char* de, int32_t* down) { return select_launches<Row>(ctx, A, E, de, down); }
-
 int AlignBatch::reloc_stage_inputs() {
   const RelocStage& R = *reloc;
   const lsm2d_batch* hb = R.batch;
@@ -49,7 +43,7 @@ int AlignBatch::reloc_stage_inputs() {
     S.f_clouds = hb->fixed[s]->n_clouds; S.m_clouds = hb->moving[s]->n_clouds;
     S.f_out = (int32_t*) (ds + o_fidx[s]); S.m_out = (int32_t*) (ds + o_midx[s]);
   }
-  hipLaunchKernelGGL(k_reloc_items<kSelectHeaderWords>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, pre, I);
+  hipLaunchKernelGGL(k_reloc_items, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, pre, I);
   HIPCHK(ctx, hipGetLastError());
   return LSM2D_SUCCESS;
 }
@@ -72,10 +66,7 @@ int AlignBatch::reloc_finish() {
   RL.n_live = d_down1 + 1;      // stage 1's n_selected
   hipLaunchKernelGGL(k_align_rows_live<AlignRow>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ks, RL);
   HIPCHK(ctx, hipGetLastError());
-  SelectArgs S;
-  S.rows = RA.rows; S.n_items = n; S.k = select_k;
-  S.min_inliers = select->min_inliers; S.max_chi_per_inlier = select->max_chi_per_inlier; S.min_inlier_ratio = select->min_inlier_ratio;
-  { const int rc = reloc_select_launches<AlignRow>(ctx, S, E, de, d_down2); if (rc) return rc; }
+  { const int rc = select_launches<AlignRow>(ctx, select_args(RA.rows, n, select_k, select), E, de, d_down2); if (rc) return rc; }
   // the bracket: from in front of stage 1's first launch (its lane's ev0, recorded by the entry point) to here
   HIPCHK(ctx, hipGetLastError());
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(R.L1->ev1, ks));
@@ -85,33 +76,20 @@ int AlignBatch::reloc_finish() {
   HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
   // ---- stage 1's answer, as lsm2d_score_aligner_select hands it over
   const int32_t* h1 = (const int32_t*) h_down;
-  const int32_t n_acc1 = h1[0], n_sel1 = h1[1];
-  const int32_t n_items = R.batch->n_alignments, K1 = R.k_score;
-  if (n_acc1 < 0 || n_acc1 > n_items || n_sel1 != (n_acc1 < K1 ? n_acc1 : K1)) return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: the selection's counters are inconsistent");
-  const int32_t* h1_index = h1 + kSelectHeaderWords; const float* h1_rows = (const float*) (h1 + kSelectHeaderWords + K1);
+  const int32_t n_sel1 = h1[1];
+  if (!select_header_ok(h1, R.batch->n_alignments, R.k_score, false)) return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: the selection's counters are inconsistent");
+  const int32_t* h1_index = h1 + kSelectHeaderWords;
   // ---- stage 2's, as lsm2d_align_select hands it over, with the indices taken through stage 1's
   const int32_t* h2 = (const int32_t*) (h_down + R.o_down2);
-  const int32_t n_acc = h2[0], n_sel = h2[1], n_success = h2[2], n_unwritten = h2[3];
-  if (n_unwritten != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
-  if (n_acc < 0 || n_acc > n_sel1 || n_sel != (n_acc < select_k ? n_acc : select_k) || n_success < n_acc || n_success > n_sel1)
-    return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: the selection's counters are inconsistent");
-  const int32_t* h2_index = h2 + kSelectHeaderWords; const int32_t* h2_rows = h2 + kSelectHeaderWords + select_k;
-  for (int32_t j = 0; j < n_sel; ++j) if (h2_index[j] < 0 || h2_index[j] >= n_sel1) return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: a pad was selected");
-  for (int32_t j = 0; j < n_sel1; ++j) {
-    R.out_scored_index[j] = h1_index[j];
-    if (R.out_scored_stats) comb_row_out(h1_rows + kCombWords * (size_t) j, nullptr, nullptr, R.out_scored_stats + j, nullptr);
-  }
-  *R.out_n_scored_selected = n_sel1; *R.out_n_scored_accepted = n_acc1;
-  for (int32_t j = 0; j < n_sel; ++j) {
-    const int32_t* row = h2_rows + AlignRow::kWords * (size_t) j;
-    sel_index[j] = h1_index[h2_index[j]];
-    memcpy(out_pose + 3 * (size_t) j, row + AlignRow::kPose, sizeof(float) * 3);
-    if (out_H) memcpy(out_H + 9 * (size_t) j, row + AlignRow::kH, sizeof(float) * 9);
-    if (out_its) out_its[j] = row[AlignRow::kIts];
-    if (sel_last_stats) memcpy(sel_last_stats + j, row + AlignRow::kStats, sizeof(lsm2d_iteration_stats));
-  }
-  *sel_n_selected = n_sel; *sel_n_accepted = n_acc;
-  if (sel_n_success) *sel_n_success = n_success;
+  if (h2[3] != 0) { for (Lane& any : ctx->lanes) any.order_valid = false; return fail(ctx, LSM2D_DEVICE_ERROR, "align_batch: an alignment's workgroup never reported (placement or launch fault)"); }
+  if (!select_header_ok(h2, n_sel1, select_k, true)) return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: the selection's counters are inconsistent");
+  const int32_t* h2_index = h2 + kSelectHeaderWords;
+  for (int32_t j = 0; j < h2[1]; ++j) if (h2_index[j] < 0 || h2_index[j] >= n_sel1) return fail(ctx, LSM2D_DEVICE_ERROR, "relocalize_select: a pad was selected");
+  if (R.out_scored_stats) comb_block_out(h1, (size_t) R.k_score, 0, nullptr, nullptr, nullptr, R.out_scored_stats, nullptr);
+  memcpy(R.out_scored_index, h1_index, sizeof(int32_t) * (size_t) n_sel1);
+  groups_report(h1, 0, 1, R.out_n_scored_selected, R.out_n_scored_accepted, nullptr);
+  align_block_out(h2, (size_t) select_k, 0, h1_index, sel_index, out_pose, out_H, out_its, sel_last_stats);
+  groups_report(h2, 0, 1, sel_n_selected, sel_n_accepted, sel_n_success);
   return LSM2D_SUCCESS;
 }
 
@@ -173,10 +151,7 @@ extern "C" int lsm2d_relocalize_select(lsm2d_context* ctx, const lsm2d_aligner_p
   {
     char* const d1 = (char*) R.L1->d_scratch;
     HIPCHK(ctx, hipGetLastError());      // (k_score_combine's launch, as lsm2d_score_aligner_select checks it)
-    SelectArgs S1;
-    S1.rows = (const float*) (d1 + R.Y.o_comb); S1.n_items = batch->n_alignments; S1.k = k_score;
-    S1.min_inliers = score_select->min_inliers; S1.max_chi_per_inlier = score_select->max_chi_per_inlier; S1.min_inlier_ratio = score_select->min_inlier_ratio;
-    const int rc = reloc_select_launches<CombRow>(ctx, S1, E1, d1 + R.Y.o_extra, (int32_t*) ((char*) B.L->d_scratch + B.o_reloc_down)); if (rc) return rc;
+    const int rc = select_launches<CombRow>(ctx, select_args(d1 + R.Y.o_comb, batch->n_alignments, k_score, score_select), E1, d1 + R.Y.o_extra, (int32_t*) ((char*) B.L->d_scratch + B.o_reloc_down)); if (rc) return rc;
     HIPCHK(ctx, hipGetLastError());
   }
   // ---- stage 2: inputs made on the device, placement, launch, rows, selection, the copy and the wait

@@ -1,7 +1,6 @@
 // lsm2d_capi_score_grid.inc -- a grid of pose hypotheses scored coarse to fine in ONE call (lsm2d_score_grid_select, include/lsm2d.h): the hypotheses are
 // made on the device from the grid descriptor, every level is lsm2d_score_aligner_select's scoring and selection, and a level's selection becomes the next
-// level's hypotheses without leaving the device.  Part of lsm2d_capi.hip, included LAST: what launches the kernels of lsm2d_k_score_grid.h comes behind
-// every older kernel's first use.
+// level's hypotheses without leaving the device.  Part of lsm2d_capi.hip, included behind the scoring's and the selection's parts.
 //
 //   per level   k_grid_level0 (level 0) or k_grid_children (below it) writes the level's pose block and origins; score_aligner_queue in its device-poses
 //               mode runs the scoring over them -- no staging, no copy up, no pass over the items; k_grid_mask_pads (below level 0) takes the pads out of
@@ -13,10 +12,6 @@
 // n_cap items, and the sets' search structures are found or built before that as well.  What must outlive a level -- its poses, its origins and its
 // selection, which the next level's generation reads -- lies in the caller's region behind the scoring's layout (d_extra); poses and origins are
 // double-buffered, so k_grid_children never writes what it reads.
-
-// select_launches through a template of this part's own (lsm2d_capi_relocalize.inc explains: a function template is instantiated where it is first named)
-template <class Row>
-static int grid_select_launches(lsm2d_context* ctx, const SelectArgs& A, const SelectLayout& E, char* de, int32_t* down) { return select_launches<Row>(ctx, A, E, de, down); }
 
 // the caller's region behind the scoring's layout, relative to ScoreAlignerLayout::o_extra, and the region that goes down (x_final, final_bytes):
 // [headers[n_levels][4] | the last level's header, index[k], rows[k][kCombWords] | pose[k][3] | origin[k]]
@@ -124,7 +119,7 @@ extern "C" int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, con
         A.f_table[s] = f_tab ? (int32_t*) (ds + Y0.o_fidx) + (size_t) s * n_cap : nullptr; A.m_table[s] = m_tab ? (int32_t*) (ds + Y0.o_midx) + (size_t) s * n_cap : nullptr;
         A.f_cloud[s] = fixed_cloud ? fixed_cloud[s] : 0; A.m_cloud[s] = moving_cloud ? moving_cloud[s] : 0;
       }
-      hipLaunchKernelGGL(k_grid_level0<kSelectHeaderWords>, dim3((unsigned) ((n_cap + 255) / 256)), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(k_grid_level0, dim3((unsigned) ((n_cap + 255) / 256)), dim3(256), 0, ctx->stream, A);
     } else {
       GridChildrenArgs A;
       memset(&A, 0, sizeof A);
@@ -133,7 +128,7 @@ extern "C" int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, con
       A.n_in = (int32_t) G.n[l - 1]; A.k_parents = g.k_parents; A.rx = g.refine[0]; A.ry = g.refine[1]; A.rt = g.refine[2]; A.R = (int32_t) R;
       for (int a = 0; a < 3; ++a) { A.spacing[a] = spacing[l][a]; A.center[a] = g.center[a]; }
       A.pose = d_pose; A.origin = d_origin;
-      hipLaunchKernelGGL(k_grid_children<kSelectHeaderWords>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(k_grid_children, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
     }
     HIPCHK(ctx, hipGetLastError());
     b.n_alignments = (int32_t) n;
@@ -151,10 +146,7 @@ extern "C" int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, con
     }
     const lsm2d_select_params* const sp = l == L - 1 ? select : coarse_select;
     const SelectLayout E(n, G.K[l], kCombWords);
-    SelectArgs S;
-    S.rows = (const float*) (ds + Y.o_comb); S.n_items = (int32_t) n; S.k = (int32_t) G.K[l];
-    S.min_inliers = sp->min_inliers; S.max_chi_per_inlier = sp->max_chi_per_inlier; S.min_inlier_ratio = sp->min_inlier_ratio;
-    { const int rc = grid_select_launches<CombRow>(ctx, S, E, dx, (int32_t*) (dx + G.x_down[l])); if (rc) return rc; }
+    { const int rc = select_launches<CombRow>(ctx, select_args(ds + Y.o_comb, (int32_t) n, (int32_t) G.K[l], sp), E, dx, (int32_t*) (dx + G.x_down[l])); if (rc) return rc; }
     HIPCHK(ctx, hipGetLastError());
   }
   {
@@ -165,7 +157,7 @@ extern "C" int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, con
     F.pose_in = (const float*) (dx + G.x_pose[(L - 1) & 1]); F.origin_in = (const int32_t*) (dx + G.x_origin[(L - 1) & 1]);
     F.headers = (int32_t*) (dx + G.x_final); F.pose = (float*) (dx + G.x_final + G.f_pose); F.origin = (int32_t*) (dx + G.x_final + G.f_origin);
     const size_t threads = std::max((size_t) k, (size_t) (L * kSelectHeaderWords));
-    hipLaunchKernelGGL(k_grid_finish<kSelectHeaderWords>, dim3((unsigned) ((threads + 255) / 256)), dim3(256), 0, ctx->stream, F);
+    hipLaunchKernelGGL(k_grid_finish, dim3((unsigned) ((threads + 255) / 256)), dim3(256), 0, ctx->stream, F);
     HIPCHK(ctx, hipGetLastError());
   }
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(Ln.ev1, ctx->stream));
@@ -174,23 +166,16 @@ extern "C" int lsm2d_score_grid_select(lsm2d_context* ctx, int32_t n_slices, con
   HIPCHK(ctx, hipMemcpyAsync(h_down, dx + G.x_final, G.final_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
   HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
   const int32_t* const hh = (const int32_t*) h_down;
-  for (int l = 0; l < L; ++l) {
-    const int32_t n_acc = hh[kSelectHeaderWords * l], n_sel = hh[kSelectHeaderWords * l + 1];
-    if (n_acc < 0 || n_acc > (int32_t) G.n[l] || n_sel != (n_acc < (int32_t) G.K[l] ? n_acc : (int32_t) G.K[l]))
+  for (int l = 0; l < L; ++l)
+    if (!select_header_ok(hh + kSelectHeaderWords * l, (int32_t) G.n[l], (int32_t) G.K[l], false))
       return fail(ctx, LSM2D_DEVICE_ERROR, "score_grid_select: the selection's counters are inconsistent");
-  }
   const int32_t* const h_last = (const int32_t*) (h_down + G.f_last);
   const int32_t n_acc = h_last[0], n_sel = h_last[1];
   if (n_acc != hh[kSelectHeaderWords * (L - 1)] || n_sel != hh[kSelectHeaderWords * (L - 1) + 1])
     return fail(ctx, LSM2D_DEVICE_ERROR, "score_grid_select: the selection's counters are inconsistent");
-  const float* const h_rows = (const float*) (h_last + kSelectHeaderWords + k);
-  const float* const h_pose = (const float*) (h_down + G.f_pose); const int32_t* const h_origin = (const int32_t*) (h_down + G.f_origin);
-  for (int32_t j = 0; j < n_sel; ++j) {
-    memcpy(out_pose + 3 * (size_t) j, h_pose + 3 * (size_t) j, sizeof(float) * 3);
-    if (out_origin) out_origin[j] = h_origin[j];
-    comb_row_out(h_rows + kCombWords * (size_t) j, out_H ? out_H + 9 * (size_t) j : nullptr, out_b ? out_b + 3 * (size_t) j : nullptr, out_stats ? out_stats + j : nullptr,
-                 out_active ? out_active + j : nullptr);
-  }
+  memcpy(out_pose, h_down + G.f_pose, sizeof(float) * 3 * (size_t) n_sel);
+  if (out_origin) memcpy(out_origin, h_down + G.f_origin, sizeof(int32_t) * (size_t) n_sel);
+  comb_block_out(h_last, (size_t) k, 0, nullptr, out_H, out_b, out_stats, out_active);
   if (out_level_counts) for (int l = 0; l < L; ++l) { out_level_counts[2 * l] = hh[kSelectHeaderWords * l]; out_level_counts[2 * l + 1] = hh[kSelectHeaderWords * l + 1]; }
   *out_n_selected = n_sel; *out_n_accepted = n_acc;
   return LSM2D_SUCCESS;

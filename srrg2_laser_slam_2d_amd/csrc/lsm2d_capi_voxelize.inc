@@ -1,6 +1,5 @@
 // lsm2d_capi_voxelize.inc -- PointCloud::voxelize over device-resident clouds of any size: several inputs, each moved by a pose, voxelised per group into
-// the clouds of a reserved set in ONE call (lsm2d_voxelize, include/lsm2d.h; PARITY.md section 3, item 17b).  Part of lsm2d_capi.hip, included LAST: what
-// launches the kernels of lsm2d_k_voxelize.h comes behind every older kernel's first use.
+// the clouds of a reserved set in ONE call (lsm2d_voxelize, include/lsm2d.h; PARITY.md section 3, item 17b).  Part of lsm2d_capi.hip.
 //
 //   up          the call's tables -- per input (transform, start, group), the concatenation offsets, per group (destination start, room, cloud) -- through the
 //               lane's pinned staging buffer into its scratch: one copy
@@ -122,33 +121,33 @@ extern "C" int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* p
     K.n_inputs = n_inputs; K.n = n; K.inv_res = 1.0f / params->resolution; K.inv_rn = 1.0f / params->normal_resolution;
     K.txy = (float2*) (ds + Y.o_txy); K.tn = (float2*) (ds + Y.o_tn); K.key = (u64*) (ds + Y.o_key[0]); K.idx = (uint32_t*) (ds + Y.o_idx[0]);
     K.dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped);
-    hipLaunchKernelGGL(k_vox_keys<kVoxTile>, dim3(pt_blocks), dim3(256), 0, ctx->stream, K);
+    hipLaunchKernelGGL(k_vox_keys, dim3(pt_blocks), dim3(256), 0, ctx->stream, K);
     HIPCHK(ctx, hipGetLastError());
     for (int d = 0; d < n_digits; ++d) {
       VoxSortArgs S;
       S.key_in = (const u64*) (ds + Y.o_key[final_buf]); S.idx_in = (const uint32_t*) (ds + Y.o_idx[final_buf]);
       S.key_out = (u64*) (ds + Y.o_key[final_buf ^ 1]); S.idx_out = (uint32_t*) (ds + Y.o_idx[final_buf ^ 1]);
       S.hist = (uint32_t*) (ds + Y.o_hist); S.n = n; S.n_tiles = n_tiles; S.shift = 8 * d; S.fault = d_misc + 2;
-      hipLaunchKernelGGL(k_vox_hist<kVoxTile>, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, S);
+      hipLaunchKernelGGL(k_vox_hist, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, S);
       VoxScanArgs C; C.data = S.hist; C.n = 256 * n_tiles; C.total = nullptr;
-      hipLaunchKernelGGL(k_vox_scan<kVoxTile>, dim3(1), dim3(kVoxScanBlock), 0, ctx->stream, C);
-      hipLaunchKernelGGL(k_vox_scatter<kVoxTile>, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, S);
+      hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(kVoxScanBlock), 0, ctx->stream, C);
+      hipLaunchKernelGGL(k_vox_scatter, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, S);
       HIPCHK(ctx, hipGetLastError());
       final_buf ^= 1;
     }
     VoxHeadArgs H;
     H.key = (const u64*) (ds + Y.o_key[final_buf]); H.tile_heads = (uint32_t*) (ds + Y.o_tile_heads); H.n = n; H.n_tiles = n_tiles;
     H.head_pos = (uint32_t*) (ds + Y.o_head_pos); H.group_first = (int32_t*) (ds + Y.o_first); H.fault = d_misc + 2;
-    hipLaunchKernelGGL(k_vox_head_count<kVoxTile>, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, H);
+    hipLaunchKernelGGL(k_vox_head_count, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, H);
     VoxScanArgs C; C.data = H.tile_heads; C.n = n_tiles; C.total = d_misc + 1;
-    hipLaunchKernelGGL(k_vox_scan<kVoxTile>, dim3(1), dim3(kVoxScanBlock), 0, ctx->stream, C);
-    hipLaunchKernelGGL(k_vox_head_write<kVoxTile>, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, H);
+    hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(kVoxScanBlock), 0, ctx->stream, C);
+    hipLaunchKernelGGL(k_vox_head_write, dim3(tile_blocks), dim3(kVoxSortBlock), 0, ctx->stream, H);
     HIPCHK(ctx, hipGetLastError());
     VoxSumArgs U;
     U.key = H.key; U.idx = (const uint32_t*) (ds + Y.o_idx[final_buf]); U.txy = (const float2*) (ds + Y.o_txy); U.tn = (const float2*) (ds + Y.o_tn);
     U.head_pos = H.head_pos; U.n_heads = d_misc + 1; U.n = n; U.n_groups = n_groups;
     U.vxy = (float2*) (ds + Y.o_vxy); U.vn = (float2*) (ds + Y.o_vn); U.group_last = (int32_t*) (ds + Y.o_last); U.fault = d_misc + 2;
-    hipLaunchKernelGGL(k_vox_sum<kVoxTile>, dim3(pt_blocks), dim3(256), 0, ctx->stream, U);
+    hipLaunchKernelGGL(k_vox_sum, dim3(pt_blocks), dim3(256), 0, ctx->stream, U);
     HIPCHK(ctx, hipGetLastError());
   }
   VoxOutArgs O;
@@ -158,9 +157,9 @@ extern "C" int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* p
   O.key = (const u64*) (ds + Y.o_key[final_buf]); O.head_pos = (const uint32_t*) (ds + Y.o_head_pos); O.n_heads = d_misc + 1;
   O.vxy = (const float2*) (ds + Y.o_vxy); O.vn = (const float2*) (ds + Y.o_vn);
   O.dst_xy = dst->d_xy; O.dst_nrm = dst->d_nrm; O.dst_count = dst->d_count; O.fault = d_misc + 2;
-  hipLaunchKernelGGL(k_vox_verdict<kVoxTile>, dim3(group_blocks), dim3(256), 0, ctx->stream, O);
-  if (n > 0) hipLaunchKernelGGL(k_vox_write<kVoxTile>, dim3(pt_blocks), dim3(256), 0, ctx->stream, O);
-  hipLaunchKernelGGL(k_vox_finish<kVoxTile>, dim3(group_blocks), dim3(256), 0, ctx->stream, O);
+  hipLaunchKernelGGL(k_vox_verdict, dim3(group_blocks), dim3(256), 0, ctx->stream, O);
+  if (n > 0) hipLaunchKernelGGL(k_vox_write, dim3(pt_blocks), dim3(256), 0, ctx->stream, O);
+  hipLaunchKernelGGL(k_vox_finish, dim3(group_blocks), dim3(256), 0, ctx->stream, O);
   HIPCHK(ctx, hipGetLastError());
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);

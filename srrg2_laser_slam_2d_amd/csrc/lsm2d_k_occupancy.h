@@ -1,6 +1,6 @@
 // lsm2d_k_occupancy.h -- occupancy grids on the device: the points of device-resident clouds ray-traced from their sensor poses into per-cell hit / miss
 // counters (lsm2d_occupancy_update), and the counters rendered to what a map consumer reads (lsm2d_occupancy_render).
-// Part of lsm2d_kernels.h (included there LAST, inside namespace lsm2d: every older kernel keeps its place in the code object).
+// Part of lsm2d_kernels.h (included there inside namespace lsm2d).
 //
 // A capability of this build, not of the reference: the reference tree has no grid mapper.  Meaning: PARITY.md section 3, item 17c; everything behind the
 // transform is integer arithmetic, so the result is unique whatever the order of the sums.  The chain, every step a launch of its own on the lane's stream:
@@ -23,8 +23,7 @@
 // integer; 2 * 32767^2 + 32767 < 2^31.  Steps 0 .. L - 1 are misses, step L is the hit; a cell outside the grid adds nothing and the ray goes on.
 // Every index is checked against its array; a failed check sets the fault word and the host answers LSM2D_DEVICE_ERROR.  No global atomics on the grid, no
 // workgroup waits for another, no float atomics, no scratch memory.  Tiles overlapped by many scans work longest: the known imbalance, measured in DESIGN.md
-// section 8, not engineered around.  The kernels are templates on the tile size for their place in the code object (an instantiation is emitted where it is
-// first used: the last include part of the host side).
+// section 8, not engineered around.
 #pragma once
 
 static constexpr int kOccTile = 64;                    // cells per side of a tile: what ONE workgroup owns ("occupancy_tile")
@@ -52,7 +51,6 @@ struct OccRaysArgs {
 LSM2D_DEV float occ_cell(float v, float o, float inv) { return __builtin_floorf(__fmul_rn(__fsub_rn(v, o), inv)); }
 LSM2D_DEV bool occ_in_range(float c) { return c >= -1048576.0f && c < 1048576.0f; }      // (NaN fails)
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_occ_rays(const OccRaysArgs A) {
   const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
   const bool in_range = i < A.n;
@@ -115,10 +113,9 @@ struct OccTilesArgs {
   unsigned long long* stamps;                                       // [workgroups] or NULL: 10 ns ticks a workgroup that had work lived (kernel timing on: diagnostics)
 };
 
-template <int kTile>
 __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
-  __shared__ uint32_t s_hits[kTile * kTile];
-  __shared__ uint32_t s_miss[kTile * kTile];
+  __shared__ uint32_t s_hits[kOccTile * kOccTile];
+  __shared__ uint32_t s_miss[kOccTile * kOccTile];
   __shared__ int32_t s_list[kOccBlock];
   __shared__ int32_t s_n;
   const int tid = threadIdx.x;
@@ -127,8 +124,8 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
   const int g = (int) (blockIdx.x / (unsigned) tpg), t = (int) (blockIdx.x - (unsigned) g * (unsigned) tpg);
   if (g >= A.G.n_grids) { if (tid == 0) *A.fault = 1; return; }
   const int ty = t / A.G.tiles_x, tx = t - ty * A.G.tiles_x;
-  const int cx0 = tx * kTile, cy0 = ty * kTile;      // the tile's cells, both ends inclusive, cut to the grid
-  const int cx1 = (cx0 + kTile < A.G.w ? cx0 + kTile : A.G.w) - 1, cy1 = (cy0 + kTile < A.G.h ? cy0 + kTile : A.G.h) - 1;
+  const int cx0 = tx * kOccTile, cy0 = ty * kOccTile;      // the tile's cells, both ends inclusive, cut to the grid
+  const int cx1 = (cx0 + kOccTile < A.G.w ? cx0 + kOccTile : A.G.w) - 1, cy1 = (cy0 + kOccTile < A.G.h ? cy0 + kOccTile : A.G.h) - 1;
   const int first = A.grid_first[g], last = A.grid_first[g + 1];
   if (first < 0 || last > A.n_inputs || first > last) { if (tid == 0) *A.fault = 1; return; }
   bool zeroed = false;
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
     __syncthreads();
     const int m = s_n;
     if (m > 0 && !zeroed) {
-      for (int c = tid; c < kTile * kTile; c += kOccBlock) { s_hits[c] = 0u; s_miss[c] = 0u; }
+      for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) { s_hits[c] = 0u; s_miss[c] = 0u; }
       __syncthreads();
       zeroed = true;
     }
@@ -168,12 +165,12 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
         const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
         const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
         uint32_t q = num / den, rem = num - q * den;
-        for (int i = ilo; i <= ihi; ++i) {      // at most kTile steps
+        for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
           const int nn = n0 + sn * (int) q;
           if (nn >= nlo && nn <= nhi) {
             const int mm = m0 + sm * i;
-            const int c = ((xm ? nn : mm) - cy0) * kTile + ((xm ? mm : nn) - cx0);
-            if (c < 0 || c >= kTile * kTile) *A.fault = 1;
+            const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
+            if (c < 0 || c >= kOccTile * kOccTile) *A.fault = 1;
             else if (i == L) atomicAdd(&s_hits[c], 1u);
             else atomicAdd(&s_miss[c], 1u);
           }
@@ -185,10 +182,10 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
     __syncthreads();
   }
   if (!zeroed) return;
-  for (int c = tid; c < kTile * kTile; c += kOccBlock) {
+  for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) {
     const uint32_t hh = s_hits[c], mm = s_miss[c];
     if (!(hh | mm)) continue;
-    const int cx = cx0 + (c % kTile), cy = cy0 + (c / kTile);
+    const int cx = cx0 + (c % kOccTile), cy = cy0 + (c / kOccTile);
     if (cx > cx1 || cy > cy1) { *A.fault = 1; continue; }      // (the walk adds inside the cut tile only)
     uint2* const cell = A.cells + (((size_t) g * (size_t) A.G.h + (size_t) cy) * (size_t) A.G.w + (size_t) cx);
     const uint2 v = *cell;
@@ -200,7 +197,6 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
 
 struct OccRenderArgs { const uint2* cells; long long n; int32_t min_visits; int8_t* out; };
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_occ_render(const OccRenderArgs A) {
   const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
   if (c >= A.n) return;
@@ -217,7 +213,6 @@ __global__ __launch_bounds__(256) void k_occ_render(const OccRenderArgs A) {
 
 struct OccPutArgs { uint2* cells; const uint32_t* hits; const uint32_t* misses; long long n; };
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_occ_put(const OccPutArgs A) {
   const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
   if (c >= A.n) return;

@@ -1,5 +1,5 @@
 // lsm2d_k_relocalize.h -- the glue that chains the hypothesis scoring to the aligner without the host (lsm2d_relocalize_select).
-// Part of lsm2d_kernels.h (included there LAST, inside namespace lsm2d: every older kernel keeps its place in the code object).
+// Part of lsm2d_kernels.h (included there inside namespace lsm2d, behind the selection and k_align_rows).
 //
 // The relocaliser / loop detector (MULTI.json:749-769, :964-986) scores n hypotheses, keeps the best k_score that pass the acceptance test, aligns those and
 // judges the aligned ones.  The scoring's selection leaves [n_accepted, n_selected, 0, 0 | index[k_score] | rows] in device memory; the hypotheses' poses,
@@ -31,16 +31,12 @@ struct RelocItemsArgs {
 
 static_assert(sizeof(PriorDev) % sizeof(int32_t) == 0, "a prior is moved word by word");
 
-// (a template, like the row packer below, for its place in the code object: an instantiation is emitted where it is first used -- the last include part of
-// the host side -- while a plain kernel would be emitted in front of every instantiation of the older kernels and renumber their labels.  kHeader: where the
-// selection's indices begin.)
-template <int kHeader>
 __global__ __launch_bounds__(256) void k_reloc_items(const RelocItemsArgs A) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= A.k_score) return;
   int n_sel = A.sel[1];
   n_sel = n_sel < 0 ? 0 : (n_sel > A.k_score ? A.k_score : n_sel);
-  int h = n_sel > 0 ? A.sel[kHeader + (j < n_sel ? j : 0)] : 0;
+  int h = n_sel > 0 ? A.sel[kSelectHeaderWords + (j < n_sel ? j : 0)] : 0;
   if ((uint32_t) h >= (uint32_t) A.n_items) h = 0;      // (cannot be: the selection's indices are item indices)
   const int32_t* p = reinterpret_cast<const int32_t*>(A.poses) + 3 * (size_t) h;
   int32_t* po = reinterpret_cast<int32_t*>(A.pose_out) + 3 * (size_t) j;

@@ -1,5 +1,5 @@
 // lsm2d_k_score_grid.h -- a grid of pose hypotheses made, refined and ranked level by level without the host (lsm2d_score_grid_select).
-// Part of lsm2d_kernels.h (included there LAST, inside namespace lsm2d: every older kernel keeps its place in the code object).
+// Part of lsm2d_kernels.h (included there inside namespace lsm2d, behind the selection).
 //
 // The hypotheses of a level lie in device memory as a pose block [n][3] and an origin array [n] (the level-0 cell every descendant came from); the scoring
 // (k_score_aligner_items ... k_score_combine) and the selection (k_select_*) run over them as they are.  Four small kernels stand round those:
@@ -31,9 +31,6 @@ struct GridLevel0Args {
   int32_t f_cloud[kMaxSlices], m_cloud[kMaxSlices];
 };
 
-// (templates, like k_reloc_items, for their place in the code object: an instantiation is emitted where it is first used -- the last include part of the host
-// side.  kHeader: where a selection's indices begin in the region it leaves.)
-template <int kHeader>
 __global__ __launch_bounds__(256) void k_grid_level0(const GridLevel0Args A) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n_cap) return;
@@ -60,7 +57,6 @@ struct GridChildrenArgs {
   float* pose; int32_t* origin;  // [k_parents R][3], [k_parents R]
 };
 
-template <int kHeader>
 __global__ __launch_bounds__(256) void k_grid_children(const GridChildrenArgs A) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= A.k_parents * A.R) return;
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(256) void k_grid_children(const GridChildrenArgs A)
     A.origin[t] = 0;
     return;
   }
-  int h = A.sel[kHeader + (j < m ? j : 0)];
+  int h = A.sel[kSelectHeaderWords + (j < m ? j : 0)];
   if ((uint32_t) h >= (uint32_t) A.n_in) h = 0;      // (cannot be: the selection's indices are slot indices of the previous level)
   const float* base = A.pose_in + 3 * (size_t) h;
   const int cx = c % A.rx, cy = (c / A.rx) % A.ry, ct = c / (A.rx * A.ry);
@@ -102,20 +98,19 @@ struct GridFinishArgs {
   const int32_t* sel[kGridMaxLevels];      // every level's selection; the last one's lies in the region that goes down already
   int32_t n_levels, k, n_last;             // n_last: slots of the last level
   const float* pose_in; const int32_t* origin_in;      // the last level's hypotheses
-  int32_t* headers;              // [n_levels][kHeader]
+  int32_t* headers;              // [n_levels][kSelectHeaderWords]
   float* pose; int32_t* origin;  // [k][3], [k]
 };
 
-template <int kHeader>
 __global__ __launch_bounds__(256) void k_grid_finish(const GridFinishArgs A) {
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < A.n_levels * kHeader) A.headers[j] = A.sel[j / kHeader][j % kHeader];
+  if (j < A.n_levels * kSelectHeaderWords) A.headers[j] = A.sel[j / kSelectHeaderWords][j % kSelectHeaderWords];
   if (j >= A.k) return;
   const int32_t* last = A.sel[A.n_levels - 1];
   int m = last[1];
   m = m < 0 ? 0 : (m > A.k ? A.k : m);
   if (j >= m) return;      // positions beyond the count are not written
-  const int32_t h = last[kHeader + j];
+  const int32_t h = last[kSelectHeaderWords + j];
   if ((uint32_t) h >= (uint32_t) A.n_last) return;      // (cannot be)
   const int32_t* p = reinterpret_cast<const int32_t*>(A.pose_in) + 3 * (size_t) h;
   int32_t* po = reinterpret_cast<int32_t*>(A.pose) + 3 * (size_t) j;

@@ -1,5 +1,5 @@
 // lsm2d_k_voxelize.h -- PointCloud::voxelize over device-resident clouds of any size, several inputs and several outputs per call (lsm2d_voxelize).
-// Part of lsm2d_kernels.h (included there LAST, inside namespace lsm2d: every older kernel keeps its place in the code object).
+// Part of lsm2d_kernels.h (included there inside namespace lsm2d).
 //
 // What voxelize_lds (lsm2d_k_mapping.h) does for at most kVoxMax points of one workgroup in LDS, for a batch of any size: the same key, the same order, the
 // same sums (PARITY.md section 3, item 17b).  The chain, every step a launch of its own on the lane's stream:
@@ -25,8 +25,7 @@
 // Every index is checked against its array before it is used; a check that fails -- it cannot, while the chain is right -- sets a fault word, nothing more is
 // written to the destination set's counts, and the host answers LSM2D_DEVICE_ERROR: a fault is never a wrong answer.
 // No workgroup waits for another: every dependency is a launch boundary.  No float atomics; integer atomics count (the tiles' digits in LDS, the dropped
-// points per group).  The kernels are templates on the tile size for their place in the code object (an instantiation is emitted where it is first used:
-// the last include part of the host side).
+// points per group).
 #pragma once
 
 static constexpr int kVoxTile = 1024;              // keys per sort tile: what ONE wave ranks ("voxelize_tile")
@@ -51,7 +50,6 @@ struct VoxKeysArgs {
   int32_t* dropped;                               // [n_groups]
 };
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_vox_keys(const VoxKeysArgs A) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n) return;
@@ -85,7 +83,6 @@ struct VoxSortArgs {
   int32_t* fault;                 // set when an index leaves its array (cannot be; the host turns it into LSM2D_DEVICE_ERROR)
 };
 
-template <int kTile>
 __global__ __launch_bounds__(kVoxSortBlock) void k_vox_hist(const VoxSortArgs A) {
   __shared__ uint32_t s_cnt[kVoxSortBlock / 64][256];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(kVoxSortBlock) void k_vox_hist(const VoxSortArgs A)
   for (int d = lane; d < 256; d += 64) cnt[d] = 0;
   vox_wave_sync();
   if (tile >= A.n_tiles) return;
-  const int b = tile * kTile, e = b + kTile < A.n ? b + kTile : A.n;
+  const int b = tile * kVoxTile, e = b + kVoxTile < A.n ? b + kVoxTile : A.n;
   for (int i = b + lane; i < e; i += 64) atomicAdd(&cnt[(uint32_t) (A.key_in[i] >> A.shift) & 255u], 1u);
   vox_wave_sync();
   for (int d = lane; d < 256; d += 64) A.hist[(size_t) d * A.n_tiles + tile] = cnt[d];
@@ -103,7 +100,6 @@ __global__ __launch_bounds__(kVoxSortBlock) void k_vox_hist(const VoxSortArgs A)
 // exclusive prefix sum of data[0 .. n) in place, ONE workgroup; the sum of all goes to *total when that is given
 struct VoxScanArgs { uint32_t* data; int32_t n; int32_t* total; };
 
-template <int kTile>
 __global__ __launch_bounds__(kVoxScanBlock) void k_vox_scan(const VoxScanArgs A) {
   __shared__ uint32_t s_wave[kVoxScanBlock / 64];
   __shared__ uint32_t s_carry;
@@ -132,7 +128,6 @@ __global__ __launch_bounds__(kVoxScanBlock) void k_vox_scan(const VoxScanArgs A)
   if (tid == 0 && A.total) *A.total = (int32_t) s_carry;
 }
 
-template <int kTile>
 __global__ __launch_bounds__(kVoxSortBlock) void k_vox_scatter(const VoxSortArgs A) {
   __shared__ uint32_t s_run[kVoxSortBlock / 64][256];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -141,7 +136,7 @@ __global__ __launch_bounds__(kVoxSortBlock) void k_vox_scatter(const VoxSortArgs
   uint32_t* run = s_run[wave];
   for (int d = lane; d < 256; d += 64) run[d] = A.hist[(size_t) d * A.n_tiles + tile];
   vox_wave_sync();
-  const int b = tile * kTile, e = b + kTile < A.n ? b + kTile : A.n;
+  const int b = tile * kVoxTile, e = b + kVoxTile < A.n ? b + kVoxTile : A.n;
   const u64 below = (1ull << lane) - 1ull;
   for (int i0 = b; i0 < e; i0 += 64) {
     const int i = i0 + lane;
@@ -178,23 +173,21 @@ LSM2D_DEV bool vox_is_head(const u64* key, int p) {
   return k != kVoxDropped && (p == 0 || key[p - 1] != k);
 }
 
-template <int kTile>
 __global__ __launch_bounds__(kVoxSortBlock) void k_vox_head_count(const VoxHeadArgs A) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tile = blockIdx.x * (kVoxSortBlock / 64) + wave;
   if (tile >= A.n_tiles) return;
-  const int b = tile * kTile, e = b + kTile < A.n ? b + kTile : A.n;
+  const int b = tile * kVoxTile, e = b + kVoxTile < A.n ? b + kVoxTile : A.n;
   uint32_t c = 0;
   for (int i0 = b; i0 < e; i0 += 64) { const int i = i0 + lane; c += (uint32_t) __popcll(__ballot(i < e && vox_is_head(A.key, i))); }
   if (lane == 0) A.tile_heads[tile] = c;
 }
 
-template <int kTile>
 __global__ __launch_bounds__(kVoxSortBlock) void k_vox_head_write(const VoxHeadArgs A) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tile = blockIdx.x * (kVoxSortBlock / 64) + wave;
   if (tile >= A.n_tiles) return;
-  const int b = tile * kTile, e = b + kTile < A.n ? b + kTile : A.n;
+  const int b = tile * kVoxTile, e = b + kVoxTile < A.n ? b + kVoxTile : A.n;
   const u64 below = (1ull << lane) - 1ull;
   uint32_t h0 = A.tile_heads[tile];
   for (int i0 = b; i0 < e; i0 += 64) {
@@ -221,7 +214,6 @@ struct VoxSumArgs {
   int32_t* fault;
 };
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_vox_sum(const VoxSumArgs A) {
   const int h = blockIdx.x * 256 + threadIdx.x;
   int nh = *A.n_heads; if (nh > A.n) nh = A.n;
@@ -258,7 +250,6 @@ struct VoxOutArgs {
   int32_t* fault;
 };
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_vox_verdict(const VoxOutArgs A) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= A.n_groups) return;
@@ -267,7 +258,6 @@ __global__ __launch_bounds__(256) void k_vox_verdict(const VoxOutArgs A) {
   if (c > A.groups[g].cap) *A.verdict = 1;      // (every writer writes the same word)
 }
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_vox_write(const VoxOutArgs A) {
   const int h = blockIdx.x * 256 + threadIdx.x;
   if (*A.verdict || *A.fault) return;
@@ -283,7 +273,6 @@ __global__ __launch_bounds__(256) void k_vox_write(const VoxOutArgs A) {
   A.dst_xy[(size_t) G.start + j] = A.vxy[h]; A.dst_nrm[(size_t) G.start + j] = A.vn[h];
 }
 
-template <int kTile>
 __global__ __launch_bounds__(256) void k_vox_finish(const VoxOutArgs A) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= A.n_groups || *A.verdict || *A.fault) return;

@@ -96,6 +96,96 @@ def test_a_function_on_one_side_only_fails(isa_diff, tmp_path, capsys):
     assert "only right: k2" in capsys.readouterr().out
 
 
+def at_ordinal(text, f):
+    """`text` (a function at ordinal 0) as the compiler writes it for the f-th function of a code object"""
+    return text.replace(".LBB0_", ".LBB%d_" % f).replace(".Lfunc_end0", ".Lfunc_end%d" % f)
+
+
+def named(name):
+    """BASE's instructions and budget as function `name`, with the lines that carry a function's own name"""
+    return (BASE.replace(".amdhsa_kernel k\n", ".amdhsa_kernel %s\n" % name)
+            + ".Lfunc_end0:\n\t.size\t%s, .Lfunc_end0-%s\n" % (name, name))
+
+
+# two blocks, so that a branch has two labels to choose from
+TWO_BLOCKS = BASE.replace("; %bb.2: ; %._crit_edge\n", ".LBB0_2:\n\tv_mov_b32_e32 v6, 0\n\ts_cbranch_vccnz .LBB0_2\n") + ".Lfunc_end0:\n"
+CALLER = BASE.replace("\ts_endpgm\n", "\ts_getpc_b64 s[2:3]\n\ts_add_u32 s2, s2, _ZN1a6calleeEv@rel32@lo+4\n\ts_swappc_b64 s[30:31], s[2:3]\n\ts_endpgm\n")
+
+
+def test_a_functions_place_in_the_code_object_does_not_count(isa_diff):
+    assert ".LBB7_1" in at_ordinal(TWO_BLOCKS, 7) and ".Lfunc_end7" in at_ordinal(TWO_BLOCKS, 7) and ".LBB0_" not in at_ordinal(TWO_BLOCKS, 7)
+    assert isa_diff.classify(TWO_BLOCKS, at_ordinal(TWO_BLOCKS, 7)) == "identical"
+    assert isa_diff.instructions(TWO_BLOCKS) == isa_diff.instructions(at_ordinal(TWO_BLOCKS, 7))
+    assert "\ts_cbranch_scc1 .LBB_1" in isa_diff.instructions(TWO_BLOCKS) and ".Lfunc_end:" in isa_diff.instructions(TWO_BLOCKS)      # the _<n> part stays
+
+
+def test_a_retargeted_branch_is_a_difference(isa_diff):
+    retargeted = TWO_BLOCKS.replace("s_cbranch_scc1 .LBB0_1", "s_cbranch_scc1 .LBB0_2")
+    assert retargeted != TWO_BLOCKS and ".LBB0_1:" in retargeted and ".LBB0_2:" in retargeted
+    assert isa_diff.classify(TWO_BLOCKS, retargeted) == "different"
+    assert isa_diff.classify(at_ordinal(TWO_BLOCKS, 7), retargeted) == "different"
+
+
+def test_two_ordinals_in_one_function_are_left_alone(isa_diff):
+    mixed = TWO_BLOCKS.replace("s_cbranch_vccnz .LBB0_2", "s_cbranch_vccnz .LBB3_2")
+    lines = isa_diff.instructions(mixed)
+    assert "\ts_cbranch_scc1 .LBB0_1" in lines and "\ts_cbranch_vccnz .LBB3_2" in lines and ".Lfunc_end0:" in lines      # nothing of it rewritten
+    assert isa_diff.classify(TWO_BLOCKS, mixed) == "different"
+    assert isa_diff.classify(mixed, mixed) == "identical"
+    assert isa_diff.classify(mixed, at_ordinal(mixed, 7).replace(".LBB3_", ".LBB9_")) == "different"      # it fails honestly against itself elsewhere
+
+
+def test_linkage_does_not_count(isa_diff):
+    comdat = BASE + "\t.section\t.text.k0,\"axG\",@progbits,k0,comdat\n.Lfunc_end0:\n"
+    plain = BASE + "\t.text\n.Lfunc_end0:\n"
+    assert isa_diff.classify(comdat, plain) == "identical"
+    assert isa_diff.classify(comdat, plain.replace("\t.text\n", "\t.p2align\t8\n")) == "different"      # only section switches are dropped
+
+
+def test_own_name_is_a_placeholder_and_a_callee_is_not(isa_diff):
+    assert named("k_old") != named("k_new") and "\t.size\tk_old, .Lfunc_end0-k_old\n" in named("k_old")
+    assert isa_diff.classify(named("k_old"), named("k_new")) == "different"      # unpaired texts differ by the name
+    assert isa_diff.classify(named("k_old"), named("k_new"), "k_old", "k_new") == "identical"
+    assert isa_diff.classify(named("k_old"), named("k_new").replace("v2, v2, v3", "v2, v2, v4"), "k_old", "k_new") == "different"
+    other_callee = CALLER.replace("_ZN1a6calleeEv", "_ZN1a7callee2Ev")
+    assert other_callee != CALLER
+    assert isa_diff.classify(CALLER, other_callee, "k", "k") == "different"
+    assert isa_diff.classify(CALLER, other_callee, "k_old", "k_new") == "different"
+
+
+def run_renamed(isa_diff, tmp_path, left, right, *renames):
+    a, b = tmp_path / "a.s", tmp_path / "b.s"
+    a.write_text(left)
+    b.write_text(right)
+    return isa_diff.main(["isa_diff.py"] + [x for r in renames for x in ("--rename", r)] + [str(a), str(b)])
+
+
+def test_rename_pairs_a_function_whose_name_changed(isa_diff, tmp_path, capsys):
+    left = listing(("k0", BASE), ("k_old", named("k_old")), ("j_old", at_ordinal(named("j_old"), 2)))
+    right = listing(("k_new", named("k_new")), ("k0", at_ordinal(BASE, 1)), ("j_new", at_ordinal(named("j_new"), 2)))
+    assert run_renamed(isa_diff, tmp_path, left, right) == 1      # unpaired: two functions on each side without a partner
+    assert "1 identical, 0 reordered, 0 different, 4 on one side only" in capsys.readouterr().out
+
+    assert run_renamed(isa_diff, tmp_path, left, right, "k_old=k_new", "j_old=j_new") == 0
+    out = capsys.readouterr().out
+    assert "3 functions on the left, 3 on the right; 3 identical, 0 reordered, 0 different, 0 on one side only" in out
+    assert "identical : k_new" in out and "identical : j_new" in out and "identical : k_old" not in out and "only left" not in out and "only right" not in out
+
+    changed = right.replace("v_mul_f32_e32 v4, v2, v5", "v_mul_f32_e32 v4, v2, v6", 1)      # the first function on the right is k_new
+    assert run_renamed(isa_diff, tmp_path, left, changed, "k_old=k_new", "j_old=j_new") == 1
+    out = capsys.readouterr().out
+    assert "2 identical, 0 reordered, 1 different, 0 on one side only" in out and "different : k_new" in out
+
+
+def test_rename_of_a_missing_function_is_an_error(isa_diff, tmp_path, capsys):
+    left, right = listing(("k_old", named("k_old"))), listing(("k_new", named("k_new")))
+    assert run_renamed(isa_diff, tmp_path, left, right, "k_gone=k_new") == 2
+    assert "k_gone" in capsys.readouterr().err
+    assert run_renamed(isa_diff, tmp_path, left, right, "k_old=k_nowhere") == 2
+    assert "k_nowhere" in capsys.readouterr().err
+    assert run_renamed(isa_diff, tmp_path, left, right, "k_old=k_new") == 0
+
+
 def test_compare_takes_dictionaries(isa_diff):
     buf = io.StringIO()
     assert isa_diff.compare({"k": BASE}, {"k": RENUMBERED}, out=buf) == 0
