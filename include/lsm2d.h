@@ -81,7 +81,9 @@ extern "C" {
                                     LSM2D_OCCUPANCY_MAX_SIDE / _MAX_CELLS / _MAX_RAYS / _MAX_RAY_CELLS (occupancy grids on the device: clouds ray-traced
                                     from their sensor poses into hit / miss counts, rendered to 0 .. 100 / -1; not in the reference); read-only option
                                     keys "occupancy_tile", "last_occupancy_wg_median_ns", "last_occupancy_wg_max_ns";
-                             (0.7.13, number unchanged: an addition only, no new symbol) + read-only option key "live_handles" */
+                             (0.7.13, number unchanged: an addition only) + read-only option key "live_handles"; lsm2d_occupancy_update_scans,
+                                    lsm2d_occupancy_scan_params (occupancy grids from raw range scans: maximum-range truncation and clearing along
+                                    beams without a return) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -881,7 +883,7 @@ int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* params,
  * instead of eight.                                                                                                               [item 17c.6]
  * NOT BUILT (item 17c.5): an asynchronous form; per-grid geometry; maximum-range truncation and clearing along beams without a return
  * (a cloud holds returns only: a beam without a return clears nothing); a once-per-scan rule per cell (every ray counts); splitting a tile's work over
- * several workgroups; log-odds with decay. */
+ * several workgroups; log-odds with decay.  (0.7.13 builds the truncation and the clearing from raw ranges: lsm2d_occupancy_update_scans, below.) */
 #define LSM2D_OCCUPANCY_MAX_SIDE      16384
 #define LSM2D_OCCUPANCY_MAX_CELLS     (1 << 28)   /* all grids of a set together: 2 GB of counters */
 #define LSM2D_OCCUPANCY_MAX_RAYS      (1 << 24)   /* input points of one update, all inputs together */
@@ -906,6 +908,49 @@ int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids,
 typedef struct lsm2d_occupancy_render_params { int32_t min_visits; } lsm2d_occupancy_render_params;
 int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* grids, int32_t grid_index,
                            const lsm2d_occupancy_render_params* params, int8_t* out /* host [height][width] */);
+
+/* ---- occupancy grids from raw scans (0.7.13): the beams of range scans ray-traced into the counters of a grid set -- the returns as lsm2d_occupancy_update
+ * traces a cloud's points, and the beams WITHOUT a return, which no cloud holds, cleared out to a cut.  A door that opens onto a corridor, a person who
+ * walked away: the beams that now pass through return nothing, and only the scan knows of them.  Like 0.7.12 a capability of this build (the reference tree
+ * has no grid mapper); the definition is the contract (PARITY.md section 3, item 17d), everything behind the transform is integer arithmetic.
+ *   classes    beam c of scan k, r = ranges[k][c], by these tests in this order:
+ *                1. !(r >= range_min)   NaN, -Inf, too close: no ray, counted in out_dropped;
+ *                2. r <= trace_range    a HIT ray of length l = r;
+ *                3. r <= range_max      a return beyond the cut: a CLEAR ray of length l = trace_range;
+ *                4. otherwise           no return (+Inf included): a CLEAR ray of length trace_range when clear_no_return, else dropped.        [item 17d.1]
+ *   end point  in the sensor frame (l * dir[c].x, l * dir[c].y), each ONE fp32 product (lsm2d_preprocess_scans' product, oracle F2.1); dir[c] is the cosine
+ *              and sine of the bearing (c - n_beams / 2) * (angle_max - angle_min) / n_beams from the host's libm, made once per sensor geometry (the
+ *              preprocessor's table and cache).  With a pose the end point is moved by xf_point under the isometry of pose[k] (item 17c.1 / 11b) and the
+ *              ray starts at the pose's translation; pose == NULL copies the bits and the ray starts at (0, 0).                                [item 17d.2]
+ *   cells      item 17c.2 unchanged: floorf((v - o) * inv), all four cells in [-2^20, 2^20), L <= LSM2D_OCCUPANCY_MAX_RAY_CELLS; a ray that fails is
+ *              dropped and counted.                                                                                                            [item 17d.3]
+ *   walk       item 17c.3 unchanged.  A HIT ray adds misses on steps 0 .. L - 1 and a hit on step L; a CLEAR ray adds a miss on EVERY step 0 .. L and no hit
+ *              (its end cell is known free: trace_range <= range_max is required, the beam had no return before l).  Cells outside the grid add nothing
+ *              and the ray goes on; counters saturate at 2^32 - 1.  Per grid out_hit_rays + out_clear_rays + out_dropped = the beams sent to it. [item 17d.4]
+ * Refused before anything is launched or written, with LSM2D_CAPACITY_EXCEEDED for n_beams outside 1 .. 2048 (as the preprocessor) and LSM2D_BAD_ARGUMENT
+ * for: a NULL the call needs; a set of another or a destroyed context; n_scans < 1; n_scans * n_beams > LSM2D_OCCUPANCY_MAX_RAYS; !(angle_max > angle_min);
+ * a non-finite range_min, range_max or trace_range; range_min < 0; range_min > range_max; !(trace_range > 0); trace_range < range_min; trace_range >
+ * range_max; clear_no_return outside {0, 1}; a grid value outside [0, n_grids); device-resident ranges on another device; both lanes busy.
+ * Cost: synchronous.  ONE upload of the call's tables (with pageable ranges in the same copy; pinned ranges are copied from directly; device-resident
+ * ranges are read in place), TWO launches -- k_occ_beams (a thread per beam) and k_occ_tiles_scans (k_occ_tiles' body over records that carry the ray's
+ * kind) --, ONE copy down (hit rays, clear rays, dropped, fault word) and ONE wait.  No size fetch: nothing has a size the host does not know.
+ * "kernel_timing" / lsm2d_last_kernel_ms bracket the chain and "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns" work as in 0.7.12.
+ * NOT BUILT (item 17d.5): an asynchronous form; per-grid geometry or per-scan sensor parameters; a once-per-scan rule per cell; splitting a tile's work over
+ * several workgroups; log-odds with decay; intensity or multi-echo. */
+typedef struct lsm2d_occupancy_scan_params {
+  int32_t n_beams;               /* 1 .. 2048, as lsm2d_preprocessor */
+  float   angle_min, angle_max;  /* as lsm2d_preprocessor: bearing of beam c = (c - n/2) * (angle_max - angle_min) / n */
+  float   range_min, range_max;  /* a return: range_min <= r <= range_max (F2.1's gate) */
+  float   trace_range;           /* no ray is traced farther than this [m] */
+  int32_t clear_no_return;       /* 1: a beam with r > range_max (+Inf included) clears out to trace_range; 0: it is dropped */
+} lsm2d_occupancy_scan_params;
+
+int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* grids, const lsm2d_occupancy_scan_params* params,
+                                 const float* ranges,     /* [n_scans][n_beams]: pageable, pinned or device memory of the context's device */
+                                 int32_t n_scans,
+                                 const float* pose,       /* [n_scans][3] sensor in the grid's frame, or NULL */
+                                 const int32_t* grid,     /* [n_scans] or NULL: all 0 */
+                                 int32_t* out_hit_rays, int32_t* out_clear_rays, int32_t* out_dropped /* each [n_grids] or NULL */);
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

@@ -93,6 +93,12 @@ class OccupancyRenderParamsC(C.Structure):
     _fields_ = [("min_visits", C.c_int32)]
 
 
+class OccupancyScanParamsC(C.Structure):
+    """lsm2d_occupancy_scan_params"""
+    _fields_ = [("n_beams", C.c_int32), ("angle_min", C.c_float), ("angle_max", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float),
+                ("trace_range", C.c_float), ("clear_no_return", C.c_int32)]
+
+
 OCCUPANCY_MAX_SIDE = 16384           # LSM2D_OCCUPANCY_MAX_SIDE
 OCCUPANCY_MAX_CELLS = 1 << 28        # LSM2D_OCCUPANCY_MAX_CELLS: all grids of a set together
 OCCUPANCY_MAX_RAYS = 1 << 24         # LSM2D_OCCUPANCY_MAX_RAYS: input points of one lsm2d_occupancy_update call
@@ -208,6 +214,9 @@ SYMBOLS = [
     ("lsm2d_gridset_destroy", None, [_P]),
     ("lsm2d_occupancy_update", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("lsm2d_occupancy_render", C.c_int, [_P, _P, C.c_int32, C.POINTER(OccupancyRenderParamsC), _P]),
+    # ... and raw range scans ray-traced into it, the beams without a return cleared: (ctx, grids, params, ranges, n_scans, pose, grid, out_hit_rays,
+    # out_clear_rays, out_dropped)
+    ("lsm2d_occupancy_update_scans", C.c_int, [_P, _P, C.POINTER(OccupancyScanParamsC), _P, C.c_int32, _P, _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -1764,6 +1764,51 @@ def occupancy_update(ctx: Context, grids: GridSet, src: CloudSet, src_index=None
     return rays, dropped
 
 
+@dataclasses.dataclass
+class OccupancyScanParams:
+    """lsm2d_occupancy_scan_params: the sensor geometry as the preprocessor takes it, the gate of a return (range_min <= r <= range_max), the cut no ray
+    is traced beyond (trace_range <= range_max) and whether a beam without a return (r > range_max, +Inf included) clears out to the cut."""
+    n_beams: int
+    angle_min: float
+    angle_max: float
+    range_min: float = 0.0
+    range_max: float = 30.0
+    trace_range: float = 30.0
+    clear_no_return: bool = True
+
+    def struct(self) -> _capi.OccupancyScanParamsC:
+        return _capi.OccupancyScanParamsC(int(self.n_beams), float(self.angle_min), float(self.angle_max), float(self.range_min), float(self.range_max),
+                                          float(self.trace_range), int(self.clear_no_return))
+
+
+def occupancy_update_scans(ctx: Context, grids: GridSet, params: OccupancyScanParams, ranges, poses=None, grid=None):
+    """Raw range scans ray-traced into the counters of ``grids`` in ONE call (lsm2d_occupancy_update_scans): ``ranges`` is ``[n_scans, n_beams]`` (or one
+    scan ``[n_beams]``), a numpy array or a torch tensor taken as it is (on the context's GPU it is read in place, in pinned host memory it is copied from
+    directly).  A return up to ``trace_range`` is a HIT ray (misses along it, a hit at its end); a return beyond it, and with ``clear_no_return`` a beam
+    without a return, is a CLEAR ray of length ``trace_range`` (misses on every cell, no hit); NaN, -Inf and ranges below ``range_min`` are dropped.
+    ``poses[k]``: the sensor of scan k in the grid's frame (None: no transform, rays start at (0, 0)); ``grid[k]``: its grid (None: grid 0).
+    Returns ``(hit_rays, clear_rays, dropped)``: int32 ``[n_grids]`` each; per grid they sum to the beams sent to it."""
+    if hasattr(ranges, "data_ptr"):
+        r = ranges if ranges.dim() == 2 else ranges[None, :]
+        if r.dtype.itemsize != 4 or not r.dtype.is_floating_point or not r.is_contiguous():
+            raise ValueError("tensor ranges must be contiguous float32")
+        _producer_stream_wait(r)
+    else:
+        r = np.ascontiguousarray(ranges, np.float32)
+        if r.ndim == 1:
+            r = r[None, :]
+    if len(r.shape) != 2 or r.shape[1] != int(params.n_beams):
+        raise ValueError("ranges must be [n_scans, n_beams]")
+    n_scans = int(r.shape[0])
+    ps = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(n_scans, 3)
+    gr = None if grid is None else np.ascontiguousarray(grid, np.int32).reshape(n_scans)
+    p = params.struct()
+    hit = np.zeros(grids.n_grids, np.int32); clear = np.zeros(grids.n_grids, np.int32); dropped = np.zeros(grids.n_grids, np.int32)
+    check(ctx._lib.lsm2d_occupancy_update_scans(ctx.handle, grids.handle, C.byref(p), _ptr(r), n_scans, _ptr(ps), _ptr(gr), _ptr(hit), _ptr(clear), _ptr(dropped)),
+          "lsm2d_occupancy_update_scans", ctx.handle)
+    return hit, clear, dropped
+
+
 def occupancy_render(ctx: Context, grids: GridSet, grid_index: int = 0, min_visits: int = 1) -> np.ndarray:
     """One grid as a consumer reads it (lsm2d_occupancy_render): int8 ``[height][width]``, -1 where hits + misses < max(min_visits, 1), else the share of
     hits in percent, 0 .. 100.  Bit for bit ``occupancy_values`` of the downloaded counters."""

@@ -9,6 +9,11 @@
 //   the chain   k_occ_rays, k_occ_tiles -- on the context's stream in order
 //   down        [rays | dropped | fault]: ONE copy, ONE wait.  With kernel timing on the tile workgroups' clock stamps follow in a copy of their own
 //               (diagnostics: "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns").
+// lsm2d_occupancy_update_scans (0.7.13; item 17d): the same shape from raw range scans, no cloud set and no size fetch:
+//   up          the tables as above -- a row per scan, the regular offsets j * n_beams, boxes, per grid its scans -- and, behind them in the same staging
+//               block, pageable ranges: one copy.  Pinned ranges are copied from directly; device-resident ranges are read in place.
+//   the chain   k_occ_beams, k_occ_tiles_scans
+//   down        [hit | clear | dropped | fault]: ONE copy, ONE wait; the stamps as above.
 
 struct lsm2d_gridset {
   lsm2d_context* ctx = nullptr;
@@ -117,6 +122,18 @@ struct OccupancyLayout {
   }
 };
 
+// diagnostics: how unevenly the tiles' work is spread (a copy and a wait of its own, with kernel timing on only)
+static int occupancy_read_stamps(lsm2d_context* ctx, const char* d_stamps, size_t n_wg) {
+  std::vector<unsigned long long> t(n_wg);
+  HIPCHK(ctx, hipMemcpy(t.data(), d_stamps, sizeof(unsigned long long) * n_wg, hipMemcpyDeviceToHost));
+  t.erase(std::remove(t.begin(), t.end(), 0ull), t.end());
+  if (!t.empty()) {
+    std::sort(t.begin(), t.end());
+    ctx->last_occ_wg_median_ns = (long long) t[t.size() / 2] * 10; ctx->last_occ_wg_max_ns = (long long) t.back() * 10;      // (s_memrealtime: 100 MHz)
+  }
+  return LSM2D_SUCCESS;
+}
+
 extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, const lsm2d_cloudset* src, int32_t n_inputs, const int32_t* src_index,
                                       const float* pose, const int32_t* grid, int32_t* out_rays, int32_t* out_dropped) {
   // ---- refusals: nothing is launched or written before the last of them
@@ -207,15 +224,7 @@ extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, 
   if (sum != total) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: the counters are inconsistent");
   for (int32_t g = 0; g < n_grids; ++g) { if (out_rays) out_rays[g] = h_rays[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
   ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
-  if (stamps && n > 0) {      // diagnostics: how unevenly the tiles' work is spread (a copy and a wait of its own, with kernel timing on only)
-    std::vector<unsigned long long> t(n_wg);
-    HIPCHK(ctx, hipMemcpy(t.data(), ds + Y.o_stamps, sizeof(unsigned long long) * n_wg, hipMemcpyDeviceToHost));
-    t.erase(std::remove(t.begin(), t.end(), 0ull), t.end());
-    if (!t.empty()) {
-      std::sort(t.begin(), t.end());
-      ctx->last_occ_wg_median_ns = (long long) t[t.size() / 2] * 10; ctx->last_occ_wg_max_ns = (long long) t.back() * 10;      // (s_memrealtime: 100 MHz)
-    }
-  }
+  if (stamps && n > 0) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg);
   return LSM2D_SUCCESS;
 }
 
@@ -238,5 +247,124 @@ extern "C" int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* g
   note_timed(ctx, ctx->kernel_timing);
   HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));      // one byte per cell comes down instead of eight
   HIPCHK(ctx, stream_sync(ctx));
+  return LSM2D_SUCCESS;
+}
+
+// ---- from raw scans (0.7.13) ------------------------------------------------------------------------------------------------------------------------------
+struct OccupancyScansLayout {
+  size_t u_inputs = 0, u_offset = 0, u_box = 0, u_first = 0, up_bytes = 0;      // the tables that travel up ...
+  size_t u_ranges = 0, ranges_bytes = 0;                                        // ... and, right behind them, the ranges unless they are device-resident
+  size_t o_down = 0, d_hit = 0, d_clear = 0, d_dropped = 0, d_fault = 0, down_bytes = 0;      // the block that travels down, cleared before the chain
+  size_t o_rays = 0, o_stamps = 0, bytes = 0;
+  OccupancyScansLayout(size_t n, size_t n_scans, size_t n_grids, size_t n_workgroups, bool ranges_travel) {
+    u_inputs = 0; u_offset = up256(sizeof(OccInput) * n_scans); u_box = up256(u_offset + sizeof(int32_t) * (n_scans + 1));
+    u_first = up256(u_box + sizeof(int32_t) * 4 * n_scans); up_bytes = up256(u_first + sizeof(int32_t) * (n_grids + 1));
+    u_ranges = up_bytes; ranges_bytes = ranges_travel ? sizeof(float) * n : 0;
+    o_down = up256(u_ranges + ranges_bytes);
+    d_hit = 0; d_clear = sizeof(int32_t) * n_grids; d_dropped = 2 * sizeof(int32_t) * n_grids; d_fault = 3 * sizeof(int32_t) * n_grids; down_bytes = d_fault + 4 * sizeof(int32_t);
+    o_rays = up256(o_down + down_bytes);
+    o_stamps = up256(o_rays + sizeof(int4) * n);
+    bytes = up256(o_stamps + sizeof(unsigned long long) * n_workgroups);
+  }
+};
+
+extern "C" int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* grids, const lsm2d_occupancy_scan_params* params, const float* ranges,
+                                            int32_t n_scans, const float* pose, const int32_t* grid, int32_t* out_hit_rays, int32_t* out_clear_rays,
+                                            int32_t* out_dropped) {
+  // ---- refusals: nothing is launched or written before the last of them
+  if (!ctx || !grids || !params || !ranges) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: null argument");
+  if (grids->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: a grid set from another (or a destroyed) context");
+  if (n_scans < 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: n_scans must be >= 1");
+  lsm2d_preprocessor geometry = {};      // the sensor geometry as the preprocessor states it: the same check, the same direction table, the same cache
+  geometry.n_beams = params->n_beams; geometry.angle_min = params->angle_min; geometry.angle_max = params->angle_max;
+  geometry.range_min = params->range_min; geometry.range_max = params->range_max; geometry.normal_min_points = 1;
+  { const int rc0 = check_preprocessor(ctx, &geometry, "occupancy_update_scans"); if (rc0) return rc0; }
+  const int nb = params->n_beams;
+  const long long total = (long long) nb * n_scans;
+  if (total > kOccMaxRays) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: more beams than LSM2D_OCCUPANCY_MAX_RAYS");
+  const float rmin = params->range_min, rmax = params->range_max, trace = params->trace_range;
+  if (!std::isfinite(rmin) || !std::isfinite(rmax) || !std::isfinite(trace)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: range_min, range_max and trace_range must be finite");
+  if (rmin < 0.0f || rmin > rmax || !(trace > 0.0f) || trace < rmin || trace > rmax)
+    return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: need 0 <= range_min <= trace_range <= range_max and trace_range > 0");
+  if (params->clear_no_return != 0 && params->clear_no_return != 1) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: clear_no_return must be 0 or 1");
+  const int32_t n_grids = grids->n_grids;
+  if (grid) for (int32_t k = 0; k < n_scans; ++k) if (grid[k] < 0 || grid[k] >= n_grids) return failf(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: scan %d: grid outside [0, n_grids)", (int) k);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rdev = -1;
+  const PtrKind kind = pointer_kind(ranges, &rdev);
+  if (kind == PtrKind::device && rdev != ctx->device) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_update_scans: device-resident ranges must live on the context's device");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  // ---- from here on the call launches
+  const float2* d_dir = nullptr;
+  { const int rc0 = beam_dirs_device(ctx, &geometry, &d_dir); if (rc0) return rc0; }      // (made and uploaded once per sensor geometry)
+  HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
+  OccGeo G;
+  G.ox = grids->geo.origin_x; G.oy = grids->geo.origin_y; G.inv = 1.0f / grids->geo.resolution; G.w = grids->geo.width; G.h = grids->geo.height; G.n_grids = n_grids;
+  G.tiles_x = (G.w + kOccTile - 1) / kOccTile; G.tiles_y = (G.h + kOccTile - 1) / kOccTile;
+  const size_t n_wg = (size_t) G.tiles_x * (size_t) G.tiles_y * (size_t) n_grids;
+  const bool stamps = ctx->kernel_timing != 0;
+  const OccupancyScansLayout Y((size_t) total, (size_t) n_scans, (size_t) n_grids, stamps ? n_wg : 0, kind != PtrKind::device);
+  { int rc = ensure_scratch(ctx, Y.bytes); if (rc) return rc; rc = ensure_stage(ctx, std::max(Y.up_bytes + (kind == PtrKind::pageable ? Y.ranges_bytes : 0), Y.down_bytes)); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  char* const ds = (char*) L.d_scratch; char* const hs = (char*) L.h_stage;
+  {
+    OccInput* hin = (OccInput*) (hs + Y.u_inputs); int32_t* hoff = (int32_t*) (hs + Y.u_offset); int32_t* hbox = (int32_t*) (hs + Y.u_box);
+    int32_t* hfirst = (int32_t*) (hs + Y.u_first);
+    // the scans grid by grid, list order kept inside a grid: a counting sort
+    for (int32_t g = 0; g <= n_grids; ++g) hfirst[g] = 0;
+    for (int32_t k = 0; k < n_scans; ++k) ++hfirst[(grid ? grid[k] : 0) + 1];
+    for (int32_t g = 0; g < n_grids; ++g) hfirst[g + 1] += hfirst[g];
+    std::vector<int32_t> cursor(hfirst, hfirst + n_grids), order((size_t) n_scans);
+    for (int32_t k = 0; k < n_scans; ++k) order[(size_t) cursor[(size_t) (grid ? grid[k] : 0)]++] = k;
+    for (int32_t j = 0; j < n_scans; ++j) {
+      const int32_t k = order[(size_t) j];
+      OccInput& in = hin[j];
+      if (pose) { in.T = make_iso(pose + 3 * (size_t) k); in.sx = pose[3 * (size_t) k]; in.sy = pose[3 * (size_t) k + 1]; }
+      else { in.T.c = 1.0f; in.T.s = 0.0f; in.T.tx = 0.0f; in.T.ty = 0.0f; in.sx = 0.0f; in.sy = 0.0f; }
+      in.start = k * nb; in.grid = grid ? grid[k] : 0; in.has_pose = pose != nullptr; in.pad = 0;      // (the ranges stay in the caller's order)
+      hoff[j] = j * nb;
+      hbox[4 * j] = hbox[4 * j + 1] = 0x7fffffff; hbox[4 * j + 2] = hbox[4 * j + 3] = kOccDropped;
+    }
+    hoff[n_scans] = n_scans * nb;
+    if (kind == PtrKind::pageable) memcpy(hs + Y.u_ranges, ranges, Y.ranges_bytes);
+  }
+  const int n = (int) total;
+  int32_t* const d_fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
+  ++ctx->uploads; ctx->last_h2d_bytes = kind == PtrKind::device ? 0 : (long long) Y.ranges_bytes;
+  // ---- the timing bracket of the whole call
+  ctx->have_timing = false;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes + (kind == PtrKind::pageable ? Y.ranges_bytes : 0), hipMemcpyHostToDevice, ctx->stream));
+  if (kind == PtrKind::pinned) HIPCHK(ctx, hipMemcpyAsync(ds + Y.u_ranges, ranges, Y.ranges_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ds + Y.o_down, 0, Y.down_bytes, ctx->stream));
+  OccBeamsArgs B;
+  B.ranges = kind == PtrKind::device ? ranges : (const float*) (ds + Y.u_ranges); B.beam_dir = d_dir; B.inputs = (const OccInput*) (ds + Y.u_inputs);
+  B.n_inputs = n_scans; B.n_beams = nb; B.n = n; B.n_ranges = n; B.rmin = rmin; B.rmax = rmax; B.trace = trace; B.clear_no_return = params->clear_no_return; B.G = G;
+  B.rays = (int4*) (ds + Y.o_rays); B.box = (int32_t*) (ds + Y.u_box);
+  B.n_hit = (int32_t*) (ds + Y.o_down + Y.d_hit); B.n_clear = (int32_t*) (ds + Y.o_down + Y.d_clear); B.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped); B.fault = d_fault;
+  hipLaunchKernelGGL(k_occ_beams, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, B);
+  HIPCHK(ctx, hipGetLastError());
+  OccTilesArgs T;
+  T.rays = B.rays; T.offset = (const int32_t*) (ds + Y.u_offset); T.box = B.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_scans; T.n = n; T.G = G;
+  T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
+  if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
+  hipLaunchKernelGGL(k_occ_tiles_scans, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(hs, ds + Y.o_down, Y.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  const int32_t* const h_hit = (const int32_t*) (hs + Y.d_hit); const int32_t* const h_clear = (const int32_t*) (hs + Y.d_clear);
+  const int32_t* const h_dropped = (const int32_t*) (hs + Y.d_dropped);
+  if (*(const int32_t*) (hs + Y.d_fault)) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: an index left its array on the device (the counters may be partly updated)");
+  long long sum = 0;
+  for (int32_t g = 0; g < n_grids; ++g) {
+    if (h_hit[g] < 0 || h_clear[g] < 0 || h_dropped[g] < 0) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: the counters are inconsistent");
+    sum += (long long) h_hit[g] + h_clear[g] + h_dropped[g];
+  }
+  if (sum != total) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: the counters are inconsistent");
+  for (int32_t g = 0; g < n_grids; ++g) { if (out_hit_rays) out_hit_rays[g] = h_hit[g]; if (out_clear_rays) out_clear_rays[g] = h_clear[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
+  ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
+  if (stamps) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg);
   return LSM2D_SUCCESS;
 }

@@ -1,6 +1,6 @@
 // lsm2d_occupancy.hpp -- occupancy grids on the device over the C ABI (include/lsm2d.h, 0.7.12): GridSet, the owner of a lsm2d_gridset, occupancyUpdate
 // (the points of device-resident clouds ray-traced from their sensor poses into hit / miss counters) and occupancyRender (the counters as a map consumer
-// reads them).  An extension of lsm2d.hpp (which it includes and whose types it uses; lsm2d.hpp itself keeps its set of C calls).  A capability of this
+// reads them); from 0.7.13 occupancyUpdateScans (raw range scans, the beams without a return cleared).  An extension of lsm2d.hpp (which it includes and whose types it uses; lsm2d.hpp itself keeps its set of C calls).  A capability of this
 // build: the reference tree has no grid mapper (PARITY.md section 3, item 17c).
 #pragma once
 
@@ -55,6 +55,31 @@ inline OccupancyUpdate occupancyUpdate(Context& ctx, GridSet& grids, const lsm2d
   out.rays.assign((size_t) grids.numGrids(), 0); out.dropped.assign((size_t) grids.numGrids(), 0);
   check(lsm2d_occupancy_update(ctx.get(), grids.get(), src, n_inputs, ptrOrNull(src_index), ptrOrNull(poses), ptrOrNull(grid), out.rays.data(), out.dropped.data()),
         "lsm2d_occupancy_update", ctx.get());
+  return out;
+}
+
+// lsm2d_occupancy_update_scans' parameters, with the defaults a caller most often keeps
+struct OccupancyScanParams : lsm2d_occupancy_scan_params {
+  OccupancyScanParams(int32_t n_beams_, float angle_min_, float angle_max_, float range_min_ = 0.0f, float range_max_ = 30.0f, float trace_range_ = 30.0f,
+                      bool clear_no_return_ = true)
+      : lsm2d_occupancy_scan_params{n_beams_, angle_min_, angle_max_, range_min_, range_max_, trace_range_, clear_no_return_ ? 1 : 0} {}
+};
+
+// hit_rays[g] / clear_rays[g]: rays walked into grid g that end in a hit / that only clear; dropped[g]: its beams that gave no ray
+struct OccupancyScanUpdate { std::vector<int32_t> hit_rays, clear_rays, dropped; };
+
+// ranges: [n_scans][n_beams] in pageable, pinned or device memory of the context's device; poses empty: no transform, every ray starts at (0, 0); grid
+// empty: every scan into grid 0.  Throws on every refusal of the call.
+inline OccupancyScanUpdate occupancyUpdateScans(Context& ctx, GridSet& grids, const lsm2d_occupancy_scan_params& params, const float* ranges, int32_t n_scans,
+                                                const std::vector<Vector3f>& poses = {}, const std::vector<int32_t>& grid = {}) {
+  const size_t n = (size_t) (n_scans > 0 ? n_scans : 0);
+  if ((!poses.empty() && poses.size() != n) || (!grid.empty() && grid.size() != n))
+    throw std::runtime_error("occupancyUpdateScans| poses and grid are empty or hold one entry per scan");
+  OccupancyScanUpdate out;
+  out.hit_rays.assign((size_t) grids.numGrids(), 0); out.clear_rays.assign((size_t) grids.numGrids(), 0); out.dropped.assign((size_t) grids.numGrids(), 0);
+  check(lsm2d_occupancy_update_scans(ctx.get(), grids.get(), &params, ranges, n_scans, ptrOrNull(poses), ptrOrNull(grid), out.hit_rays.data(),
+                                     out.clear_rays.data(), out.dropped.data()),
+        "lsm2d_occupancy_update_scans", ctx.get());
   return out;
 }
 
