@@ -83,7 +83,11 @@ extern "C" {
                                     keys "occupancy_tile", "last_occupancy_wg_median_ns", "last_occupancy_wg_max_ns";
                              (0.7.13, number unchanged: an addition only) + read-only option key "live_handles"; lsm2d_occupancy_update_scans,
                                     lsm2d_occupancy_scan_params (occupancy grids from raw range scans: maximum-range truncation and clearing along
-                                    beams without a return) */
+                                    beams without a return);
+                             (0.7.14, number unchanged: an addition only) + log-odds grid sets: lsm2d_logodds_params, lsm2d_logodds_render_params,
+                                    lsm2d_gridset_create_logodds / _set_logodds / _upload_logodds / _download_logodds, lsm2d_occupancy_decay,
+                                    lsm2d_logodds_render_table, lsm2d_occupancy_render_logodds (occupancy as clamped log-odds, one vote per scan and
+                                    cell, the hit winning; both update calls accept either kind of set) */
 
 /* ---- status codes -------------------------------------------------------------------------
  * Replace: std::runtime_error throws of the finders (registration/correspondence_finder_projective_2d.cpp:21-31,
@@ -882,8 +886,9 @@ int lsm2d_voxelize(lsm2d_context* ctx, const lsm2d_voxelize_params* params,
  * conversions round to nearest) and the value is (int8) rintf(100.0f * p), the product rounded once, ties to even: 0 .. 100.  One byte per cell comes down
  * instead of eight.                                                                                                               [item 17c.6]
  * NOT BUILT (item 17c.5): an asynchronous form; per-grid geometry; maximum-range truncation and clearing along beams without a return
- * (a cloud holds returns only: a beam without a return clears nothing); a once-per-scan rule per cell (every ray counts); splitting a tile's work over
- * several workgroups; log-odds with decay.  (0.7.13 builds the truncation and the clearing from raw ranges: lsm2d_occupancy_update_scans, below.) */
+ * (a cloud holds returns only: a beam without a return clears nothing); a once-per-scan rule for counts sets (every ray counts); splitting a tile's work
+ * over several workgroups.  (0.7.13 builds the truncation and the clearing from raw ranges: lsm2d_occupancy_update_scans, below.  0.7.14 builds the
+ * once-per-scan rule and log-odds with decay as a second kind of set, which this call accepts as it accepts a counts set: log-odds grid sets, below.) */
 #define LSM2D_OCCUPANCY_MAX_SIDE      16384
 #define LSM2D_OCCUPANCY_MAX_CELLS     (1 << 28)   /* all grids of a set together: 2 GB of counters */
 #define LSM2D_OCCUPANCY_MAX_RAYS      (1 << 24)   /* input points of one update, all inputs together */
@@ -935,8 +940,8 @@ int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* grids, int32
  * ranges are read in place), TWO launches -- k_occ_beams (a thread per beam) and k_occ_tiles_scans (k_occ_tiles' body over records that carry the ray's
  * kind) --, ONE copy down (hit rays, clear rays, dropped, fault word) and ONE wait.  No size fetch: nothing has a size the host does not know.
  * "kernel_timing" / lsm2d_last_kernel_ms bracket the chain and "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns" work as in 0.7.12.
- * NOT BUILT (item 17d.5): an asynchronous form; per-grid geometry or per-scan sensor parameters; a once-per-scan rule per cell; splitting a tile's work over
- * several workgroups; log-odds with decay; intensity or multi-echo. */
+ * NOT BUILT (item 17d.5): an asynchronous form; per-grid geometry or per-scan sensor parameters; a once-per-scan rule for counts sets; splitting a tile's
+ * work over several workgroups; intensity or multi-echo.  (0.7.14: into a log-odds set -- below -- this call gives every cell one clamped vote per scan.) */
 typedef struct lsm2d_occupancy_scan_params {
   int32_t n_beams;               /* 1 .. 2048, as lsm2d_preprocessor */
   float   angle_min, angle_max;  /* as lsm2d_preprocessor: bearing of beam c = (c - n/2) * (angle_max - angle_min) / n */
@@ -951,6 +956,9 @@ int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* grids, const
                                  const float* pose,       /* [n_scans][3] sensor in the grid's frame, or NULL */
                                  const int32_t* grid,     /* [n_scans] or NULL: all 0 */
                                  int32_t* out_hit_rays, int32_t* out_clear_rays, int32_t* out_dropped /* each [n_grids] or NULL */);
+
+/* Log-odds grid sets (0.7.14) -- a second kind of lsm2d_gridset that both update calls above accept, with its own entry points -- are declared in
+ * lsm2d_logodds.h, an extension of this header (as host/lsm2d_occupancy.hpp extends host/lsm2d.hpp); this header keeps its set of symbols. */
 
 /* What an alignment of `batch` will cost relative to the others, WITHOUT running it: for projective slices against a map-sized moving cloud the
  * number of chunks of that cloud (of 512) that survive the exact culling against the alignment's fixed canvas at its start pose -- what its first

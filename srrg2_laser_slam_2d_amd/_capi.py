@@ -99,6 +99,16 @@ class OccupancyScanParamsC(C.Structure):
                 ("trace_range", C.c_float), ("clear_no_return", C.c_int32)]
 
 
+class LogOddsParamsC(C.Structure):
+    """lsm2d_logodds_params"""
+    _fields_ = [("l_hit", C.c_int32), ("l_miss", C.c_int32), ("l_min", C.c_int32), ("l_max", C.c_int32)]
+
+
+class LogOddsRenderParamsC(C.Structure):
+    """lsm2d_logodds_render_params"""
+    _fields_ = [("min_scans", C.c_int32), ("unit", C.c_float)]
+
+
 OCCUPANCY_MAX_SIDE = 16384           # LSM2D_OCCUPANCY_MAX_SIDE
 OCCUPANCY_MAX_CELLS = 1 << 28        # LSM2D_OCCUPANCY_MAX_CELLS: all grids of a set together
 OCCUPANCY_MAX_RAYS = 1 << 24         # LSM2D_OCCUPANCY_MAX_RAYS: input points of one lsm2d_occupancy_update call
@@ -219,6 +229,19 @@ SYMBOLS = [
     ("lsm2d_occupancy_update_scans", C.c_int, [_P, _P, C.POINTER(OccupancyScanParamsC), _P, C.c_int32, _P, _P, _P, _P, _P]),
 ]
 
+# every symbol the extension header include/lsm2d_logodds.h declares (SYMBOLS stays the list of include/lsm2d.h)
+LOGODDS_SYMBOLS = [
+    # log-odds grid sets (0.7.14): a set of the second kind -- (ctx, geometry, n_grids, params, out) --, its parameters, its typed upload / download
+    # (grids, grid_index, value, observed), the decay (ctx, grids, n, grid_index, amount), the host-only table (unit, out_threshold[100]) and the render
+    ("lsm2d_gridset_create_logodds", C.c_int, [_P, C.POINTER(GridGeometryC), C.c_int32, C.POINTER(LogOddsParamsC), C.POINTER(_P)]),
+    ("lsm2d_gridset_set_logodds", C.c_int, [_P, C.POINTER(LogOddsParamsC)]),
+    ("lsm2d_gridset_upload_logodds", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("lsm2d_gridset_download_logodds", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("lsm2d_occupancy_decay", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("lsm2d_logodds_render_table", C.c_int, [C.c_float, _P]),
+    ("lsm2d_occupancy_render_logodds", C.c_int, [_P, _P, C.c_int32, C.POINTER(LogOddsRenderParamsC), _P]),
+]
+
 _lib = None
 
 
@@ -256,7 +279,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + LOGODDS_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

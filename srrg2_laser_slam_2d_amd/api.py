@@ -1701,14 +1701,33 @@ class GridGeometry:
         return _capi.GridGeometryC(float(self.origin_x), float(self.origin_y), float(self.resolution), int(self.width), int(self.height))
 
 
-class GridSet:
-    """``n_grids`` device-resident occupancy grids of one geometry (lsm2d_gridset): two uint32 counters per cell, hits and misses, zero at creation."""
+@dataclasses.dataclass
+class LogOddsParams:
+    """lsm2d_logodds_params, in integer units of the caller's choice: the vote of a hit (1 .. 2^20) and of a miss (-2^20 .. -1) and the clamps
+    (-2^30 <= l_min <= 0 <= l_max <= 2^30).  With ``unit`` log-odds per integer unit, l_hit = round(log(p_hit / (1 - p_hit)) / unit)."""
+    l_hit: int
+    l_miss: int
+    l_min: int
+    l_max: int
 
-    def __init__(self, ctx: Context, geometry: GridGeometry, n_grids: int = 1):
+    def struct(self) -> _capi.LogOddsParamsC:
+        return _capi.LogOddsParamsC(int(self.l_hit), int(self.l_miss), int(self.l_min), int(self.l_max))
+
+
+class GridSet:
+    """``n_grids`` device-resident occupancy grids of one geometry (lsm2d_gridset), zero at creation.  A counts set (``logodds`` None) holds two uint32
+    counters per cell, hits and misses; a log-odds set (``logodds`` a LogOddsParams; 0.7.14) holds {int32 value, uint32 observed}: every scan of an update
+    gives a cell ONE clamped vote, the scans in list order, and ``observed`` counts the scans that voted (0: unknown)."""
+
+    def __init__(self, ctx: Context, geometry: GridGeometry, n_grids: int = 1, logodds: Optional[LogOddsParams] = None):
         self._ctx, self._lib = ctx, ctx._lib
-        self.geometry, self.n_grids = geometry, int(n_grids)
+        self.geometry, self.n_grids, self.logodds = geometry, int(n_grids), logodds
         g = geometry.struct(); h = C.c_void_p()
-        check(self._lib.lsm2d_gridset_create(ctx.handle, C.byref(g), int(n_grids), C.byref(h)), "lsm2d_gridset_create", ctx.handle)
+        if logodds is None:
+            check(self._lib.lsm2d_gridset_create(ctx.handle, C.byref(g), int(n_grids), C.byref(h)), "lsm2d_gridset_create", ctx.handle)
+        else:
+            p = logodds.struct()
+            check(self._lib.lsm2d_gridset_create_logodds(ctx.handle, C.byref(g), int(n_grids), C.byref(p), C.byref(h)), "lsm2d_gridset_create_logodds", ctx.handle)
         self._h = h
         ctx._sets.add(self)      # closed with its context, like a cloud set
 
@@ -1736,6 +1755,32 @@ class GridSet:
         h = np.empty(self.shape, np.uint32); m = np.empty(self.shape, np.uint32)
         check(self._lib.lsm2d_gridset_download(self._h, int(grid_index), _ptr(h), _ptr(m)), "lsm2d_gridset_download", self._ctx.handle)
         return h, m
+
+    def set_logodds(self, params: LogOddsParams):
+        """The votes and clamps of LATER updates of a log-odds set; host-side only (lsm2d_gridset_set_logodds)."""
+        p = params.struct()
+        check(self._lib.lsm2d_gridset_set_logodds(self._h, C.byref(p)), "lsm2d_gridset_set_logodds", self._ctx.handle)
+        self.logodds = params
+
+    def upload_logodds(self, grid_index: int = 0, value=None, observed=None):
+        """Sets one grid of a log-odds set from an int32 and a uint32 ``[height][width]`` array; None leaves that word as it is.  Values outside the clamps
+        are legal: the next vote pulls them in (lsm2d_gridset_upload_logodds)."""
+        v = None if value is None else np.ascontiguousarray(value, np.int32).reshape(self.shape)
+        o = None if observed is None else np.ascontiguousarray(observed, np.uint32).reshape(self.shape)
+        check(self._lib.lsm2d_gridset_upload_logodds(self._h, int(grid_index), _ptr(v), _ptr(o)), "lsm2d_gridset_upload_logodds", self._ctx.handle)
+
+    def download_logodds(self, grid_index: int = 0) -> tuple:
+        """-> (value int32, observed uint32), ``[height][width]`` (lsm2d_gridset_download_logodds)."""
+        v = np.empty(self.shape, np.int32); o = np.empty(self.shape, np.uint32)
+        check(self._lib.lsm2d_gridset_download_logodds(self._h, int(grid_index), _ptr(v), _ptr(o)), "lsm2d_gridset_download_logodds", self._ctx.handle)
+        return v, o
+
+    def decay(self, amount: int, indices=None):
+        """Every observed cell of grids ``indices`` (None: every grid) moves toward 0 by ``amount`` >= 0, never past it; queued, no wait
+        (lsm2d_occupancy_decay)."""
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
+        check(self._lib.lsm2d_occupancy_decay(self._ctx.handle, self._h, 0 if idx is None else len(idx), _ptr(idx), int(amount)), "lsm2d_occupancy_decay",
+              self._ctx.handle)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1827,3 +1872,33 @@ def occupancy_values(hits, misses, min_visits: int = 1) -> np.ndarray:
     p = h.astype(np.float32) / den
     val = np.rint(np.float32(100.0) * p).astype(np.int8)
     return np.where(known, val, np.int8(-1)).astype(np.int8)
+
+
+# ---- log-odds grid sets (0.7.14; PARITY.md section 3, item 17e) ----
+
+def logodds_render_table(unit: float) -> np.ndarray:
+    """lsm2d_logodds_render_table: int32 ``[100]``, entry j - 1 = ceil(log((j - 0.5) / (100.5 - j)) / unit) -- the smallest value that renders as j percent
+    or more.  Host only; launches nothing."""
+    t = np.empty(100, np.int32)
+    code = _capi.load().lsm2d_logodds_render_table(C.c_float(unit), _ptr(t))
+    if code < 0:
+        raise Lsm2dError(code, "lsm2d_logodds_render_table", "unit must be finite and > 0")
+    return t
+
+
+def occupancy_render_logodds(ctx: Context, grids: GridSet, grid_index: int = 0, unit: float = 0.01, min_scans: int = 1) -> np.ndarray:
+    """One grid of a log-odds set as a consumer reads it (lsm2d_occupancy_render_logodds): int8 ``[height][width]``, -1 where observed < max(min_scans, 1),
+    else the probability in percent, 0 .. 100, by the table of ``unit``.  Bit for bit ``logodds_values`` of the downloaded cells."""
+    p = _capi.LogOddsRenderParamsC(int(min_scans), float(unit))
+    out = np.empty(grids.shape, np.int8)
+    check(ctx._lib.lsm2d_occupancy_render_logodds(ctx.handle, grids.handle, int(grid_index), C.byref(p), _ptr(out)), "lsm2d_occupancy_render_logodds", ctx.handle)
+    return out
+
+
+def logodds_values(value, observed, unit: float, min_scans: int = 1) -> np.ndarray:
+    """lsm2d_occupancy_render_logodds' rule in numpy: -1 where observed < max(min_scans, 1), else the number of entries of ``logodds_render_table(unit)``
+    that are <= value."""
+    t = logodds_render_table(unit)
+    n = np.searchsorted(t, np.asarray(value, np.int32), side="right").astype(np.int8)
+    known = np.asarray(observed, np.uint32) >= np.uint32(max(int(min_scans), 1))
+    return np.where(known, n, np.int8(-1)).astype(np.int8)

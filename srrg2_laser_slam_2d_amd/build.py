@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(LIB_DIR, "liblsm2d_hip.so")
 LIB_PATH_EXPERIMENTS = os.path.join(LIB_DIR, "liblsm2d_hip_experiments.so")
 SOURCES = [os.path.join(CSRC, "lsm2d_capi.hip")]
 # every header and include part under csrc/ (the device arithmetic: lsm2d_device*.h; the kernels by family: lsm2d_k_*.h; the host side's parts: lsm2d_capi_*.inc) + the ABI header
-HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(ROOT, "include", "lsm2d.h")]
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(ROOT, "include", "lsm2d.h"), os.path.join(ROOT, "include", "lsm2d_logodds.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is explicit, so column indices and
 # z-buffer winners are reproducible bit-for-bit by an IEEE CPU (see csrc/lsm2d_device.h).

@@ -2,6 +2,7 @@
 // Owns the device buffers, packs kernel arguments, launches the gfx950 kernels of lsm2d_kernels.h on
 // the context's HIP stream.  No CPU fallback: without a usable HIP device every entry point fails.
 #include "lsm2d.h"
+#include "lsm2d_logodds.h"
 
 namespace lsm2d { static constexpr int LSM2D_RUNNING = -99; }
 using lsm2d::LSM2D_RUNNING;

@@ -21,6 +21,8 @@ struct lsm2d_gridset {
   int32_t n_grids = 0;
   size_t cells_per_grid = 0;
   DevBuf<uint2> d_cells;         // [n_grids][height][width] = {hits, misses}: a cell is one 8-byte access
+  bool logodds = false;          // 0.7.14: a set of the second kind, a cell is {int32 value, uint32 observed} (item 17e)
+  lsm2d_logodds_params lp = {};  // ... and the votes and clamps of its updates
 };
 
 static void orphan_gridsets(lsm2d_context* ctx) { for (lsm2d_gridset* gs : ctx->live_gridsets) gs->ctx = nullptr; }
@@ -74,10 +76,18 @@ extern "C" int lsm2d_gridset_clear(lsm2d_gridset* gs, int32_t n, const int32_t* 
   return LSM2D_SUCCESS;
 }
 
+// the two words of a cell from planar host arrays, whatever they mean: the counts upload and the log-odds upload behind their own checks
+static int gridset_put(lsm2d_gridset* gs, int32_t grid_index, const uint32_t* hits, const uint32_t* misses);
+
 extern "C" int lsm2d_gridset_upload(lsm2d_gridset* gs, int32_t grid_index, const uint32_t* hits, const uint32_t* misses) {
   if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_upload: null argument (or the set's context is gone)");
+  if (gs->logodds) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_upload: a log-odds set (lsm2d_gridset_upload_logodds)");
+  if (!valid_grid_index(gs, grid_index)) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_upload: grid index outside the set");
+  return gridset_put(gs, grid_index, hits, misses);
+}
+
+static int gridset_put(lsm2d_gridset* gs, int32_t grid_index, const uint32_t* hits, const uint32_t* misses) {
   lsm2d_context* ctx = gs->ctx;
-  if (!valid_grid_index(gs, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_upload: grid index outside the set");
   if (!hits && !misses) return LSM2D_SUCCESS;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = gs->cells_per_grid;
@@ -93,10 +103,17 @@ extern "C" int lsm2d_gridset_upload(lsm2d_gridset* gs, int32_t grid_index, const
   return LSM2D_SUCCESS;
 }
 
+static int gridset_get(const lsm2d_gridset* gs, int32_t grid_index, uint32_t* out_hits, uint32_t* out_misses);
+
 extern "C" int lsm2d_gridset_download(const lsm2d_gridset* gs, int32_t grid_index, uint32_t* out_hits, uint32_t* out_misses) {
   if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_download: null argument (or the set's context is gone)");
+  if (gs->logodds) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_download: a log-odds set (lsm2d_gridset_download_logodds)");
+  if (!valid_grid_index(gs, grid_index)) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_download: grid index outside the set");
+  return gridset_get(gs, grid_index, out_hits, out_misses);
+}
+
+static int gridset_get(const lsm2d_gridset* gs, int32_t grid_index, uint32_t* out_hits, uint32_t* out_misses) {
   lsm2d_context* ctx = gs->ctx;
-  if (!valid_grid_index(gs, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_download: grid index outside the set");
   if (!out_hits && !out_misses) return LSM2D_SUCCESS;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = gs->cells_per_grid;
@@ -207,7 +224,11 @@ extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, 
     T.rays = R.rays; T.offset = R.offset; T.box = R.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_inputs; T.n = n; T.G = G;
     T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
     if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
-    hipLaunchKernelGGL(k_occ_tiles, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
+    if (grids->logodds) {      // the set's kind picks the tile kernel: everything around it is the one host path
+      const OccLogoddsArgs P = {T, grids->lp.l_hit, grids->lp.l_miss, grids->lp.l_min, grids->lp.l_max};
+      hipLaunchKernelGGL(k_occ_tiles_logodds<false>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, P);
+    } else
+      hipLaunchKernelGGL(k_occ_tiles, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
     HIPCHK(ctx, hipGetLastError());
   }
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
@@ -232,6 +253,7 @@ extern "C" int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* g
                                       int8_t* out) {
   if (!ctx || !grids || !params || !out) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: null argument");
   if (grids->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: a grid set from another (or a destroyed) context");
+  if (grids->logodds) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: a log-odds set (lsm2d_occupancy_render_logodds)");
   if (!valid_grid_index(grids, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: grid index outside the set");
   if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -348,7 +370,11 @@ extern "C" int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* g
   T.rays = B.rays; T.offset = (const int32_t*) (ds + Y.u_offset); T.box = B.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_scans; T.n = n; T.G = G;
   T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
   if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
-  hipLaunchKernelGGL(k_occ_tiles_scans, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
+  if (grids->logodds) {      // the set's kind picks the tile kernel
+    const OccLogoddsArgs P = {T, grids->lp.l_hit, grids->lp.l_miss, grids->lp.l_min, grids->lp.l_max};
+    hipLaunchKernelGGL(k_occ_tiles_logodds<true>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, P);
+  } else
+    hipLaunchKernelGGL(k_occ_tiles_scans, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
   HIPCHK(ctx, hipGetLastError());
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
@@ -366,5 +392,100 @@ extern "C" int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* g
   for (int32_t g = 0; g < n_grids; ++g) { if (out_hit_rays) out_hit_rays[g] = h_hit[g]; if (out_clear_rays) out_clear_rays[g] = h_clear[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
   ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
   if (stamps) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg);
+  return LSM2D_SUCCESS;
+}
+
+// ---- log-odds grid sets (0.7.14; PARITY.md section 3, item 17e) -------------------------------------------------------------------------------------------
+static const char* logodds_params_fault(const lsm2d_logodds_params* p) {
+  if (p->l_hit < 1 || p->l_hit > (1 << 20)) return "l_hit must lie in 1 .. 2^20";
+  if (p->l_miss > -1 || p->l_miss < -(1 << 20)) return "l_miss must lie in -2^20 .. -1";
+  if (p->l_min > 0 || p->l_min < -(1 << 30)) return "l_min must lie in -2^30 .. 0";
+  if (p->l_max < 0 || p->l_max > (1 << 30)) return "l_max must lie in 0 .. 2^30";
+  return nullptr;
+}
+
+extern "C" int lsm2d_gridset_create_logodds(lsm2d_context* ctx, const lsm2d_grid_geometry* geo, int32_t n_grids, const lsm2d_logodds_params* params,
+                                            lsm2d_gridset** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !geo || !params || !out) return fail(ctx, LSM2D_BAD_ARGUMENT, "gridset_create_logodds: null argument");
+  if (const char* why = logodds_params_fault(params)) return failf(ctx, LSM2D_BAD_ARGUMENT, "gridset_create_logodds: %s", why);
+  const int rc = lsm2d_gridset_create(ctx, geo, n_grids, out);      // (all cells zero: value 0, observed 0 = unknown)
+  if (rc) return rc;
+  (*out)->logodds = true; (*out)->lp = *params;
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_gridset_set_logodds(lsm2d_gridset* gs, const lsm2d_logodds_params* params) {
+  if (!gs || !gs->ctx || !params) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_set_logodds: null argument (or the set's context is gone)");
+  if (!gs->logodds) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_set_logodds: a counts set");
+  if (const char* why = logodds_params_fault(params)) return failf(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_set_logodds: %s", why);
+  gs->lp = *params;      // host-side only: an update queued earlier took its copy at its launch
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_gridset_upload_logodds(lsm2d_gridset* gs, int32_t grid_index, const int32_t* value, const uint32_t* observed) {
+  if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_upload_logodds: null argument (or the set's context is gone)");
+  if (!gs->logodds) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_upload_logodds: a counts set (lsm2d_gridset_upload)");
+  if (!valid_grid_index(gs, grid_index)) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_upload_logodds: grid index outside the set");
+  return gridset_put(gs, grid_index, (const uint32_t*) value, observed);      // (k_occ_put moves words: a value outside the clamps is legal, item 17e)
+}
+
+extern "C" int lsm2d_gridset_download_logodds(const lsm2d_gridset* gs, int32_t grid_index, int32_t* out_value, uint32_t* out_observed) {
+  if (!gs || !gs->ctx) return fail(gs ? gs->ctx : nullptr, LSM2D_BAD_ARGUMENT, "gridset_download_logodds: null argument (or the set's context is gone)");
+  if (!gs->logodds) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_download_logodds: a counts set (lsm2d_gridset_download)");
+  if (!valid_grid_index(gs, grid_index)) return fail(gs->ctx, LSM2D_BAD_ARGUMENT, "gridset_download_logodds: grid index outside the set");
+  return gridset_get(gs, grid_index, (uint32_t*) out_value, out_observed);
+}
+
+extern "C" int lsm2d_occupancy_decay(lsm2d_context* ctx, lsm2d_gridset* gs, int32_t n, const int32_t* grid_index, int32_t amount) {
+  if (!ctx || !gs) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: null argument");
+  if (gs->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: a grid set from another (or a destroyed) context");
+  if (!gs->logodds) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: a counts set");
+  if (amount < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: amount must be >= 0");
+  if (grid_index && n < 0) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: n must be >= 0");
+  if (grid_index) for (int32_t j = 0; j < n; ++j) if (!valid_grid_index(gs, grid_index[j])) return failf(ctx, LSM2D_BAD_ARGUMENT, "occupancy_decay: entry %d: grid index outside the set", (int) j);
+  if (amount == 0) return LSM2D_SUCCESS;      // (nothing moves)
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t per = gs->cells_per_grid;
+  const int32_t launches = grid_index ? n : 1;      // queued, no wait: every grid in one launch, or a launch per listed grid (a grid listed twice decays twice)
+  for (int32_t j = 0; j < launches; ++j) {
+    OccDecayArgs D; D.cells = gs->d_cells + (grid_index ? per * (size_t) grid_index[j] : 0); D.n = (long long) (grid_index ? per : per * (size_t) gs->n_grids); D.amount = amount;
+    hipLaunchKernelGGL(k_occ_decay, dim3((unsigned) ((D.n + 255) / 256)), dim3(256), 0, ctx->stream, D);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_logodds_render_table(float unit, int32_t* out_threshold) {
+  if (!out_threshold || !(unit > 0.0f) || !std::isfinite(unit)) return LSM2D_BAD_ARGUMENT;
+  for (int j = 1; j <= 100; ++j) {      // the smallest integer value whose probability rounds to j percent or more: p >= (j - 0.5) / 100
+    const double t = std::ceil(std::log(((double) j - 0.5) / (100.5 - (double) j)) / (double) unit);
+    out_threshold[j - 1] = t < -2147483648.0 ? INT32_MIN : t > 2147483647.0 ? INT32_MAX : (int32_t) t;
+  }
+  return LSM2D_SUCCESS;
+}
+
+extern "C" int lsm2d_occupancy_render_logodds(lsm2d_context* ctx, const lsm2d_gridset* grids, int32_t grid_index, const lsm2d_logodds_render_params* params,
+                                              int8_t* out) {
+  if (!ctx || !grids || !params || !out) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: null argument");
+  if (grids->ctx != ctx) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: a grid set from another (or a destroyed) context");
+  if (!grids->logodds) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: a counts set (lsm2d_occupancy_render)");
+  if (!valid_grid_index(grids, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: grid index outside the set");
+  OccRenderLogoddsArgs R;
+  if (lsm2d_logodds_render_table(params->unit, R.threshold)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: unit must be finite and > 0");
+  if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t n = grids->cells_per_grid;
+  { const int rc = ensure_scratch(ctx, up256(n)); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.min_scans = params->min_scans; R.out = (int8_t*) L.d_scratch;
+  ctx->have_timing = false;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  hipLaunchKernelGGL(k_occ_render_logodds, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);      // (the 100 thresholds ride in the arguments)
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, stream_sync(ctx));
   return LSM2D_SUCCESS;
 }

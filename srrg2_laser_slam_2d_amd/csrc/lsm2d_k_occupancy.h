@@ -30,6 +30,16 @@
 //                      BOTH kinds and the three counts are reduced over the wave and added by the leader lane, as in k_occ_rays.
 //   k_occ_tiles_scans  k_occ_tiles over records that carry a kind: a step is a hit iff i == L and the ray is a HIT ray; a CLEAR ray adds a miss on every step
 //                      0 .. L.  A sibling kernel beside k_occ_tiles, not a shared body: sharing moved an instruction of k_occ_tiles (see at the kernel).
+// Into a log-odds grid set (0.7.14, PARITY.md section 3, item 17e: a cell is {int32 value, uint32 observed}) the second kernel of either chain is
+//   k_occ_tiles_logodds<kKinds>  the same workgroup per (grid, tile), the same box rounds and the same walk, but the scans are applied ONE AFTER THE OTHER in
+//                      ascending input order and every cell gets ONE vote per scan.  The kept list is compacted in order (a ballot per wave, the four waves'
+//                      counts through LDS).  On the first kept input the tile's value / observed words come from the grid into LDS (the 2 x 16 KB of the
+//                      two count arrays).  Per kept scan the walk sets the cell's bit in a hit mask or a miss mask (4096 bits each, no-return LDS OR); after a
+//                      barrier each thread takes 16 bits of both masks, applies the clamped vote to the set bits (a hit bit wins) and clears its bits; a
+//                      second barrier ends the scan.  At the end a cell of the cut tile whose bits differ from the grid's is stored, 8 bytes, plain.
+//   k_occ_decay        a thread per cell: an observed cell's value moves toward 0 by `amount`, never past it (lsm2d_occupancy_decay).
+//   k_occ_render_logodds  a thread per cell: -1 below min_scans, else how many of the 100 thresholds in the kernel's arguments are <= value (branch-free).
+// The typed upload goes through k_occ_put with the words reinterpreted: the kernel is untouched.
 // Every index is checked against its array; a failed check sets the fault word and the host answers LSM2D_DEVICE_ERROR.  No global atomics on the grid, no
 // workgroup waits for another, no float atomics, no scratch memory.  Tiles overlapped by many scans work longest: the known imbalance, measured in DESIGN.md
 // section 8, not engineered around.
@@ -399,4 +409,158 @@ __global__ __launch_bounds__(256) void k_occ_put(const OccPutArgs A) {
   if (A.hits) v.x = A.hits[c];
   if (A.misses) v.y = A.misses[c];
   A.cells[c] = v;
+}
+
+// ---- log-odds grid sets (0.7.14; PARITY.md section 3, item 17e) -----------------------------------------------------------------------------------------
+struct OccLogoddsArgs { OccTilesArgs T; int32_t l_hit, l_miss, l_min, l_max; };      // T.cells: {value (int32 bits), observed}
+
+static constexpr int kOccMaskWords = kOccTile * kOccTile / 32;      // a tile's cells as bits
+
+// The walk is k_occ_tiles' (kKinds: k_occ_tiles_scans'), restated here and not shared for the reason given at k_occ_tiles_scans.  What differs is the
+// accumulation: a step sets a bit, and the bits of ONE scan become one clamped vote per cell before the next scan's walk begins.
+template <bool kKinds>
+__global__ __launch_bounds__(kOccBlock) void k_occ_tiles_logodds(const OccLogoddsArgs P) {
+  __shared__ int32_t s_val[kOccTile * kOccTile];
+  __shared__ uint32_t s_obs[kOccTile * kOccTile];
+  __shared__ uint32_t s_hitm[kOccMaskWords];
+  __shared__ uint32_t s_missm[kOccMaskWords];
+  __shared__ int32_t s_list[kOccBlock];
+  __shared__ int32_t s_wcnt[kOccBlock / 64];
+  const OccTilesArgs& A = P.T;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const int tpg = A.G.tiles_x * A.G.tiles_y;
+  const int g = (int) (blockIdx.x / (unsigned) tpg), t = (int) (blockIdx.x - (unsigned) g * (unsigned) tpg);
+  if (g >= A.G.n_grids) { if (tid == 0) *A.fault = 1; return; }
+  const int ty = t / A.G.tiles_x, tx = t - ty * A.G.tiles_x;
+  const int cx0 = tx * kOccTile, cy0 = ty * kOccTile;      // the tile's cells, both ends inclusive, cut to the grid
+  const int cx1 = (cx0 + kOccTile < A.G.w ? cx0 + kOccTile : A.G.w) - 1, cy1 = (cy0 + kOccTile < A.G.h ? cy0 + kOccTile : A.G.h) - 1;
+  const int first = A.grid_first[g], last = A.grid_first[g + 1];
+  if (first < 0 || last > A.n_inputs || first > last) { if (tid == 0) *A.fault = 1; return; }
+  uint2* const grid_cells = A.cells + (size_t) g * (size_t) A.G.h * (size_t) A.G.w;
+  bool loaded = false;
+  for (int base = first; base < last; base += kOccBlock) {
+    // the kept inputs of this round in ASCENDING order: a ballot per wave, the waves' counts through LDS (rounds ascend by themselves)
+    const int k = base + tid;
+    bool keep = false;
+    if (k < last) {
+      const int4 B = *(const int4*) (A.box + 4 * (size_t) k);
+      keep = B.x <= cx1 && B.z >= cx0 && B.y <= cy1 && B.w >= cy0;      // (an input without a live ray keeps {max, max, min, min})
+    }
+    const u64 bal = __ballot(keep);
+    if ((tid & 63) == 0) s_wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, m = 0;
+#pragma unroll
+    for (int w = 0; w < kOccBlock / 64; ++w) { const int c = s_wcnt[w]; before += w < wave ? c : 0; m += c; }
+    if (keep) s_list[before + __popcll(bal & ((1ull << (tid & 63)) - 1ull))] = k;      // (before + rank < m <= kOccBlock)
+    if (m > 0 && !loaded) {
+      for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) {
+        const int cx = cx0 + (c % kOccTile), cy = cy0 + (c / kOccTile);
+        uint2 v = make_uint2(0u, 0u);      // (outside the cut tile: never voted on, never stored)
+        if (cx <= cx1 && cy <= cy1) v = grid_cells[(size_t) cy * (size_t) A.G.w + (size_t) cx];
+        s_val[c] = (int32_t) v.x; s_obs[c] = v.y;
+      }
+      if (tid < kOccMaskWords) { s_hitm[tid] = 0u; s_missm[tid] = 0u; }
+      loaded = true;
+    }
+    __syncthreads();
+    for (int j = 0; j < m; ++j) {
+      const int kk = s_list[j];
+      const int b = A.offset[kk], e = A.offset[kk + 1];
+      if (b < 0 || e > A.n || b > e) { *A.fault = 1; continue; }      // (the same for every thread: no barrier is left out by some)
+      for (int r = b + tid; r < e; r += kOccBlock) {
+        int4 R = A.rays[r];
+        if (R.x == kOccDropped) continue;
+        bool hit_ray = true;
+        if (kKinds) {
+          hit_ray = ((uint32_t) R.w >> kOccKindShift) == (uint32_t) kOccHit;
+          R.w = (int) ((uint32_t) R.w << (32 - kOccKindShift)) >> (32 - kOccKindShift);      // y1, sign-extended from 22 bits
+        }
+        if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) continue;
+        const int dx = R.z - R.x, dy = R.w - R.y;
+        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+        const bool xm = ax >= ay;      // a tie is x-major
+        const int L = xm ? ax : ay, a = xm ? ay : ax;
+        const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
+        const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
+        const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
+        int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
+        ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
+        if (ilo > ihi) continue;
+        const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
+        const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
+        uint32_t q = num / den, rem = num - q * den;
+        for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
+          const int nn = n0 + sn * (int) q;
+          if (nn >= nlo && nn <= nhi) {
+            const int mm = m0 + sm * i;
+            const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
+            if (c < 0 || c >= kOccTile * kOccTile) *A.fault = 1;
+            else if (i == L && hit_ray) atomicOr(&s_hitm[c >> 5], 1u << (c & 31));      // (a CLEAR ray: a miss on every step)
+            else atomicOr(&s_missm[c >> 5], 1u << (c & 31));
+          }
+          rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
+          if (rem >= den) { rem -= den; ++q; }
+        }
+      }
+      __syncthreads();
+      // one vote per cell: thread tid owns cells 16 tid .. 16 tid + 15, half a word of each mask, reads it, votes and clears it -- nobody else touches them
+      {
+        const uint32_t sh = (uint32_t) (tid & 1) * 16u;
+        const uint32_t hw = s_hitm[tid >> 1], mw = s_missm[tid >> 1];
+        const uint32_t hb = (hw >> sh) & 0xffffu;
+        uint32_t any = hb | ((mw >> sh) & 0xffffu);
+        if (any) {
+          atomicAnd(&s_hitm[tid >> 1], ~(0xffffu << sh)); atomicAnd(&s_missm[tid >> 1], ~(0xffffu << sh));      // (the word's other half is its neighbour's)
+          while (any) {
+            const int bit = __ffs((int) any) - 1;
+            any &= any - 1u;
+            const int c = tid * 16 + bit;
+            long long v = (long long) s_val[c] + (long long) (((hb >> bit) & 1u) ? P.l_hit : P.l_miss);      // the hit wins
+            v = v < (long long) P.l_min ? (long long) P.l_min : v; v = v > (long long) P.l_max ? (long long) P.l_max : v;
+            s_val[c] = (int32_t) v;
+            const uint32_t o = s_obs[c];
+            s_obs[c] = o == 0xffffffffu ? o : o + 1u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!loaded) return;
+  for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) {
+    const int cx = cx0 + (c % kOccTile), cy = cy0 + (c / kOccTile);
+    if (cx > cx1 || cy > cy1) continue;
+    uint2* const cell = grid_cells + ((size_t) cy * (size_t) A.G.w + (size_t) cx);
+    const uint2 was = *cell, now = make_uint2((uint32_t) s_val[c], s_obs[c]);
+    if (was.x != now.x || was.y != now.y) *cell = now;      // (a voted cell whose bits did not move -- clamped and saturated -- needs no store)
+  }
+  if (A.stamps && tid == 0) A.stamps[blockIdx.x] = __builtin_amdgcn_s_memrealtime() - t_start;
+}
+
+struct OccDecayArgs { uint2* cells; long long n; int32_t amount; };
+
+__global__ __launch_bounds__(256) void k_occ_decay(const OccDecayArgs A) {
+  const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
+  if (c >= A.n) return;
+  const uint2 cell = A.cells[c];
+  if (cell.y == 0u) return;      // unknown: keeps its bits
+  const long long v = (long long) (int32_t) cell.x;
+  const long long w = v > 0 ? (v - A.amount > 0 ? v - A.amount : 0) : (v < 0 ? (v + A.amount < 0 ? v + A.amount : 0) : 0);
+  if (w != v) A.cells[c] = make_uint2((uint32_t) (int32_t) w, cell.y);
+}
+
+struct OccRenderLogoddsArgs { const uint2* cells; long long n; int32_t min_scans; int8_t* out; int32_t threshold[100]; };
+
+__global__ __launch_bounds__(256) void k_occ_render_logodds(const OccRenderLogoddsArgs A) {
+  const long long c = (long long) blockIdx.x * 256 + threadIdx.x;
+  if (c >= A.n) return;
+  const uint2 cell = A.cells[c];
+  const int32_t v = (int32_t) cell.x;
+  const uint32_t need = A.min_scans > 1 ? (uint32_t) A.min_scans : 1u;
+  int count = 0;
+#pragma unroll
+  for (int j = 0; j < 100; ++j) count += A.threshold[j] <= v ? 1 : 0;      // the table IS the rendering: no exponential here
+  A.out[c] = cell.y >= need ? (int8_t) count : (int8_t) -1;
 }

@@ -5,15 +5,41 @@
 #pragma once
 
 #include "lsm2d.hpp"
+#include <lsm2d_logodds.h>      // log-odds grid sets (0.7.14): the extension header of the C ABI
 
 namespace lsm2d_host {
+
+// lsm2d_logodds_params in integer units of the caller's choice: the votes of a hit and of a miss, and the clamps
+struct LogOddsParams : lsm2d_logodds_params {
+  LogOddsParams(int32_t l_hit_, int32_t l_miss_, int32_t l_min_, int32_t l_max_) : lsm2d_logodds_params{l_hit_, l_miss_, l_min_, l_max_} {}
+};
 
 // n_grids device-resident grids of one geometry, two uint32 counters per cell (hits, misses), zero at creation; host arrays are [height][width]
 class GridSet {
  public:
   struct Counters { std::vector<uint32_t> hits, misses; };
+  struct LogOdds { std::vector<int32_t> value; std::vector<uint32_t> observed; };
   GridSet(Context& ctx, const lsm2d_grid_geometry& geometry, int32_t n_grids = 1) : _ctx(ctx), _geometry(geometry), _n_grids(n_grids) {
     check(lsm2d_gridset_create(ctx.get(), &geometry, n_grids, &_h), "lsm2d_gridset_create", ctx.get());
+  }
+  // a log-odds set (0.7.14): a cell is {int32 value, uint32 observed}; every scan of an update gives a cell ONE clamped vote, the scans in list order
+  GridSet(Context& ctx, const lsm2d_grid_geometry& geometry, int32_t n_grids, const lsm2d_logodds_params& logodds)
+      : _ctx(ctx), _geometry(geometry), _n_grids(n_grids), _logodds(true) {
+    check(lsm2d_gridset_create_logodds(ctx.get(), &geometry, n_grids, &logodds, &_h), "lsm2d_gridset_create_logodds", ctx.get());
+  }
+  bool isLogOdds() const { return _logodds; }
+  // the votes and clamps of LATER updates; host-side only
+  void setLogOdds(const lsm2d_logodds_params& p) { check(lsm2d_gridset_set_logodds(_h, &p), "lsm2d_gridset_set_logodds", _ctx.get()); }
+  // an empty vector leaves that word as it is; values outside the clamps are legal
+  void uploadLogOdds(int32_t grid_index, const std::vector<int32_t>& value, const std::vector<uint32_t>& observed) {
+    if ((!value.empty() && value.size() != cells()) || (!observed.empty() && observed.size() != cells()))
+      throw std::runtime_error("GridSet::uploadLogOdds| value and observed are empty or hold height x width cells");
+    check(lsm2d_gridset_upload_logodds(_h, grid_index, detail::ptrOrNull(value), detail::ptrOrNull(observed)), "lsm2d_gridset_upload_logodds", _ctx.get());
+  }
+  LogOdds downloadLogOdds(int32_t grid_index) const {
+    LogOdds c; c.value.resize(cells()); c.observed.resize(cells());
+    check(lsm2d_gridset_download_logodds(_h, grid_index, c.value.data(), c.observed.data()), "lsm2d_gridset_download_logodds", _ctx.get());
+    return c;
   }
   ~GridSet() { lsm2d_gridset_destroy(_h); }
   GridSet(const GridSet&) = delete; GridSet& operator=(const GridSet&) = delete;
@@ -37,7 +63,7 @@ class GridSet {
     return c;
   }
  private:
-  Context& _ctx; lsm2d_grid_geometry _geometry; int32_t _n_grids; lsm2d_gridset* _h = nullptr;
+  Context& _ctx; lsm2d_grid_geometry _geometry; int32_t _n_grids; bool _logodds = false; lsm2d_gridset* _h = nullptr;
 };
 
 // rays[g]: rays walked into grid g; dropped[g]: its points that gave no ray
@@ -88,6 +114,26 @@ inline std::vector<int8_t> occupancyRender(Context& ctx, const GridSet& grids, i
   const lsm2d_occupancy_render_params p{min_visits};
   std::vector<int8_t> out(grids.cells());
   check(lsm2d_occupancy_render(ctx.get(), grids.get(), grid_index, &p, out.data()), "lsm2d_occupancy_render", ctx.get());
+  return out;
+}
+
+// every observed cell of grids `indices` (empty: every grid) of a log-odds set moves toward 0 by amount >= 0, never past it; queued, no wait
+inline void occupancyDecay(Context& ctx, GridSet& grids, int32_t amount, const std::vector<int32_t>& indices = {}) {
+  check(lsm2d_occupancy_decay(ctx.get(), grids.get(), (int32_t) indices.size(), detail::ptrOrNull(indices), amount), "lsm2d_occupancy_decay", ctx.get());
+}
+
+// the 100 thresholds of `unit` (log-odds per integer unit): entry j - 1 is the smallest value that renders as j percent or more.  Host only.
+inline std::vector<int32_t> logOddsRenderTable(float unit) {
+  std::vector<int32_t> t(100);
+  if (lsm2d_logodds_render_table(unit, t.data()) != LSM2D_SUCCESS) throw std::runtime_error("logOddsRenderTable| unit must be finite and > 0");
+  return t;
+}
+
+// [height][width] of a log-odds set: -1 where observed < max(min_scans, 1), else the probability in percent, 0 .. 100, by the table of `unit`
+inline std::vector<int8_t> occupancyRenderLogOdds(Context& ctx, const GridSet& grids, int32_t grid_index, float unit, int32_t min_scans = 1) {
+  const lsm2d_logodds_render_params p{min_scans, unit};
+  std::vector<int8_t> out(grids.cells());
+  check(lsm2d_occupancy_render_logodds(ctx.get(), grids.get(), grid_index, &p, out.data()), "lsm2d_occupancy_render_logodds", ctx.get());
   return out;
 }
 
