@@ -937,7 +937,7 @@ int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* grids, int32
  * a non-finite range_min, range_max or trace_range; range_min < 0; range_min > range_max; !(trace_range > 0); trace_range < range_min; trace_range >
  * range_max; clear_no_return outside {0, 1}; a grid value outside [0, n_grids); device-resident ranges on another device; both lanes busy.
  * Cost: synchronous.  ONE upload of the call's tables (with pageable ranges in the same copy; pinned ranges are copied from directly; device-resident
- * ranges are read in place), TWO launches -- k_occ_beams (a thread per beam) and k_occ_tiles_scans (k_occ_tiles' body over records that carry the ray's
+ * ranges are read in place), TWO launches -- k_occ_beams (a thread per beam) and k_occ_tiles<true> (k_occ_tiles over records that carry the ray's
  * kind) --, ONE copy down (hit rays, clear rays, dropped, fault word) and ONE wait.  No size fetch: nothing has a size the host does not know.
  * "kernel_timing" / lsm2d_last_kernel_ms bracket the chain and "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns" work as in 0.7.12.
  * NOT BUILT (item 17d.5): an asynchronous form; per-grid geometry or per-scan sensor parameters; a once-per-scan rule for counts sets; splitting a tile's

@@ -35,8 +35,8 @@ extern "C" {
  * log-odds set; the _logodds calls and lsm2d_occupancy_decay refuse a counts set.  Refused with LSM2D_BAD_ARGUMENT before anything is launched or written:
  * a parameter outside the constraints; a NULL the call needs; the wrong kind of set; amount < 0; a unit that is not > 0 or not finite; an index outside
  * the set.
- * Kernels: k_occ_tiles_logodds (the launch shape of k_occ_tiles: a workgroup per grid and 64 x 64 tile, one owner per tile, no global atomics on the
- * grid; the kept inputs in ascending order, the tile's words in LDS, two 4096-bit masks per scan, two barriers per kept scan), k_occ_decay and
+ * Kernels: k_occ_tiles_logodds (the launch shape and the tile walk of k_occ_tiles: a workgroup per grid and 64 x 64 tile, one owner per tile, no global
+ * atomics on the grid; the kept inputs in ascending order, the tile's words in LDS, two 4096-bit masks per scan, two barriers per kept scan), k_occ_decay and
  * k_occ_render_logodds (a thread per cell).  No older kernel changed.
  * NOT BUILT (item 17e.6): an asynchronous form; per-grid geometry; per-scan sensor parameters; splitting a tile's work over several workgroups; intensity
  * or multi-echo; a once-per-scan rule for counts sets. */

@@ -6,14 +6,16 @@
 //   up          the call's tables -- per input (transform, ray start, where its points begin, its grid), the concatenation offsets, the inputs' boxes as
 //               {max, max, min, min}, per grid the range of its inputs -- through the lane's pinned staging buffer into its scratch: one copy.  The inputs are
 //               listed grid by grid (a stable counting sort on the host): a tile's workgroup loops over its own grid's inputs only.
-//   the chain   k_occ_rays, k_occ_tiles -- on the context's stream in order
+//   the chain   k_occ_rays, k_occ_tiles<false> -- on the context's stream in order
 //   down        [rays | dropped | fault]: ONE copy, ONE wait.  With kernel timing on the tile workgroups' clock stamps follow in a copy of their own
 //               (diagnostics: "last_occupancy_wg_median_ns" / "last_occupancy_wg_max_ns").
 // lsm2d_occupancy_update_scans (0.7.13; item 17d): the same shape from raw range scans, no cloud set and no size fetch:
 //   up          the tables as above -- a row per scan, the regular offsets j * n_beams, boxes, per grid its scans -- and, behind them in the same staging
 //               block, pageable ranges: one copy.  Pinned ranges are copied from directly; device-resident ranges are read in place.
-//   the chain   k_occ_beams, k_occ_tiles_scans
+//   the chain   k_occ_beams, k_occ_tiles<true>
 //   down        [hit | clear | dropped | fault]: ONE copy, ONE wait; the stamps as above.
+// Into a log-odds set the second kernel of either chain is k_occ_tiles_logodds<kKinds>.  The two calls differ in their refusals, in the first kernel and in
+// what travels up; the layout, the geometry, the tables, the tile launch and the finish are one function each, and the two render calls share their tail.
 
 struct lsm2d_gridset {
   lsm2d_context* ctx = nullptr;
@@ -124,20 +126,76 @@ static int gridset_get(const lsm2d_gridset* gs, int32_t grid_index, uint32_t* ou
   return LSM2D_SUCCESS;
 }
 
+// ---- what both update calls share: the layout, the geometry, the tables, the tile launch and the finish -----------------------------------------------------
+// count_rows: the per-grid count rows that come down, [rays | dropped] or [hit | clear | dropped]; ranges_bytes: the ranges that travel up (0: the cloud
+// call, and device-resident ranges)
 struct OccupancyLayout {
-  size_t u_inputs = 0, u_offset = 0, u_box = 0, u_first = 0, up_bytes = 0;      // the block that travels up (the same offsets in the staging buffer and in the scratch)
-  size_t o_down = 0, d_rays = 0, d_dropped = 0, d_fault = 0, down_bytes = 0;    // the block that travels down, cleared before the chain
+  size_t u_inputs = 0, u_offset = 0, u_box = 0, u_first = 0, up_bytes = 0;      // the tables that travel up (the same offsets in the staging buffer and in the scratch) ...
+  size_t u_ranges = 0, ranges_bytes = 0;                                        // ... and, right behind them, the ranges
+  size_t o_down = 0, count_rows = 0, d_row = 0, d_fault = 0, down_bytes = 0;    // the block that travels down, cleared before the chain: count row r at r * d_row, then the fault word
   size_t o_rays = 0, o_stamps = 0, bytes = 0;
-  OccupancyLayout(size_t n, size_t n_inputs, size_t n_grids, size_t n_workgroups) {
+  OccupancyLayout(size_t n, size_t n_inputs, size_t n_grids, size_t n_workgroups, size_t count_rows_, size_t ranges_bytes_) {
     u_inputs = 0; u_offset = up256(sizeof(OccInput) * n_inputs); u_box = up256(u_offset + sizeof(int32_t) * (n_inputs + 1));
     u_first = up256(u_box + sizeof(int32_t) * 4 * n_inputs); up_bytes = up256(u_first + sizeof(int32_t) * (n_grids + 1));
-    o_down = up_bytes;
-    d_rays = 0; d_dropped = sizeof(int32_t) * n_grids; d_fault = 2 * sizeof(int32_t) * n_grids; down_bytes = d_fault + 4 * sizeof(int32_t);
+    u_ranges = up_bytes; ranges_bytes = ranges_bytes_;
+    o_down = up256(u_ranges + ranges_bytes);
+    count_rows = count_rows_; d_row = sizeof(int32_t) * n_grids; d_fault = count_rows * d_row; down_bytes = d_fault + 4 * sizeof(int32_t);
     o_rays = up256(o_down + down_bytes);
     o_stamps = up256(o_rays + sizeof(int4) * (n ? n : 1));
     bytes = up256(o_stamps + sizeof(unsigned long long) * n_workgroups);
   }
 };
+
+static OccGeo occupancy_geo(const lsm2d_gridset* grids) {
+  OccGeo G;
+  G.ox = grids->geo.origin_x; G.oy = grids->geo.origin_y; G.inv = 1.0f / grids->geo.resolution; G.w = grids->geo.width; G.h = grids->geo.height; G.n_grids = grids->n_grids;
+  G.tiles_x = (G.w + kOccTile - 1) / kOccTile; G.tiles_y = (G.h + kOccTile - 1) / kOccTile;
+  return G;
+}
+static size_t occupancy_workgroups(const OccGeo& G) { return (size_t) G.tiles_x * (size_t) G.tiles_y * (size_t) G.n_grids; }      // (<= LSM2D_OCCUPANCY_MAX_CELLS: a tile holds a cell at least)
+
+// the call's tables into the staging buffer: the inputs grid by grid, list order kept inside a grid (a counting sort); per input its row, its offset in the
+// records and an empty box; per grid the range of its inputs.  start(k), count(k): where the caller's input k begins in what the first kernel reads and how
+// many records it gives
+template <class Start, class Count>
+static void occupancy_tables(char* hs, const OccupancyLayout& Y, int32_t n_inputs, int32_t n_grids, const float* pose, const int32_t* grid, Start start, Count count) {
+  OccInput* hin = (OccInput*) (hs + Y.u_inputs); int32_t* hoff = (int32_t*) (hs + Y.u_offset); int32_t* hbox = (int32_t*) (hs + Y.u_box);
+  int32_t* hfirst = (int32_t*) (hs + Y.u_first);
+  for (int32_t g = 0; g <= n_grids; ++g) hfirst[g] = 0;
+  for (int32_t k = 0; k < n_inputs; ++k) ++hfirst[(grid ? grid[k] : 0) + 1];
+  for (int32_t g = 0; g < n_grids; ++g) hfirst[g + 1] += hfirst[g];
+  std::vector<int32_t> cursor(hfirst, hfirst + n_grids), order((size_t) n_inputs);
+  for (int32_t k = 0; k < n_inputs; ++k) order[(size_t) cursor[(size_t) (grid ? grid[k] : 0)]++] = k;
+  int32_t o = 0;
+  for (int32_t j = 0; j < n_inputs; ++j) {
+    const int32_t k = order[(size_t) j];
+    OccInput& in = hin[j];
+    if (pose) { in.T = make_iso(pose + 3 * (size_t) k); in.sx = pose[3 * (size_t) k]; in.sy = pose[3 * (size_t) k + 1]; }
+    else { in.T.c = 1.0f; in.T.s = 0.0f; in.T.tx = 0.0f; in.T.ty = 0.0f; in.sx = 0.0f; in.sy = 0.0f; }
+    in.start = start(k); in.grid = grid ? grid[k] : 0; in.has_pose = pose != nullptr; in.pad = 0;
+    hoff[j] = o; o += count(k);
+    hbox[4 * j] = hbox[4 * j + 1] = 0x7fffffff; hbox[4 * j + 2] = hbox[4 * j + 3] = kOccDropped;
+  }
+  hoff[n_inputs] = o;
+}
+
+// the second kernel of either chain over the first one's records: the set's kind and the records' (kinds: k_occ_beams') pick it
+static int occupancy_launch_tiles(lsm2d_context* ctx, const lsm2d_gridset* grids, char* ds, const OccupancyLayout& Y, int32_t n_inputs, int n, const OccGeo& G, bool stamps, bool kinds) {
+  const size_t n_wg = occupancy_workgroups(G);
+  OccTilesArgs T;
+  T.rays = (const int4*) (ds + Y.o_rays); T.offset = (const int32_t*) (ds + Y.u_offset); T.box = (const int32_t*) (ds + Y.u_box);
+  T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_inputs; T.n = n; T.G = G;
+  T.cells = grids->d_cells; T.fault = (int32_t*) (ds + Y.o_down + Y.d_fault); T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
+  if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
+  const OccLogoddsArgs P = {T, grids->lp.l_hit, grids->lp.l_miss, grids->lp.l_min, grids->lp.l_max};
+  const dim3 wgs((unsigned) n_wg), block(kOccBlock);
+  if (grids->logodds && kinds) hipLaunchKernelGGL(k_occ_tiles_logodds<true>, wgs, block, 0, ctx->stream, P);
+  else if (grids->logodds) hipLaunchKernelGGL(k_occ_tiles_logodds<false>, wgs, block, 0, ctx->stream, P);
+  else if (kinds) hipLaunchKernelGGL(k_occ_tiles<true>, wgs, block, 0, ctx->stream, T);
+  else hipLaunchKernelGGL(k_occ_tiles<false>, wgs, block, 0, ctx->stream, T);
+  HIPCHK(ctx, hipGetLastError());
+  return LSM2D_SUCCESS;
+}
 
 // diagnostics: how unevenly the tiles' work is spread (a copy and a wait of its own, with kernel timing on only)
 static int occupancy_read_stamps(lsm2d_context* ctx, const char* d_stamps, size_t n_wg) {
@@ -148,6 +206,28 @@ static int occupancy_read_stamps(lsm2d_context* ctx, const char* d_stamps, size_
     std::sort(t.begin(), t.end());
     ctx->last_occ_wg_median_ns = (long long) t[t.size() / 2] * 10; ctx->last_occ_wg_max_ns = (long long) t.back() * 10;      // (s_memrealtime: 100 MHz)
   }
+  return LSM2D_SUCCESS;
+}
+
+// the end of both update calls, `who` for the messages: the one copy down and the one wait; the fault word, the counts' signs and their sum against
+// `total`; out[r] (or NULL), one per count row; the stamps of the n_wg_stamped workgroups (0: none were written)
+static int occupancy_finish(lsm2d_context* ctx, const char* who, const OccupancyLayout& Y, int32_t n_grids, long long total, int32_t* const* out, size_t n_wg_stamped) {
+  Lane& L = lane(ctx);
+  char* const ds = (char*) L.d_scratch; char* const hs = (char*) L.h_stage;
+  HIPCHK(ctx, hipMemcpyAsync(hs, ds + Y.o_down, Y.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
+  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
+  if (*(const int32_t*) (hs + Y.d_fault)) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: an index left its array on the device (the counters may be partly updated)", who);
+  long long sum = 0;
+  for (int32_t g = 0; g < n_grids; ++g)
+    for (size_t r = 0; r < Y.count_rows; ++r) {
+      const int32_t c = ((const int32_t*) (hs + r * Y.d_row))[g];
+      if (c < 0) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the counters are inconsistent", who);
+      sum += c;
+    }
+  if (sum != total) return failf(ctx, LSM2D_DEVICE_ERROR, "%s: the counters are inconsistent", who);
+  for (size_t r = 0; r < Y.count_rows; ++r) if (out[r]) memcpy(out[r], hs + r * Y.d_row, Y.d_row);
+  ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
+  if (n_wg_stamped) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg_stamped);
   return LSM2D_SUCCESS;
 }
 
@@ -176,38 +256,15 @@ extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   { const int rc0 = flush_pending(src); if (rc0) return rc0; }
   HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
-  OccGeo G;
-  G.ox = grids->geo.origin_x; G.oy = grids->geo.origin_y; G.inv = 1.0f / grids->geo.resolution; G.w = grids->geo.width; G.h = grids->geo.height; G.n_grids = n_grids;
-  G.tiles_x = (G.w + kOccTile - 1) / kOccTile; G.tiles_y = (G.h + kOccTile - 1) / kOccTile;
-  const size_t n_wg = (size_t) G.tiles_x * (size_t) G.tiles_y * (size_t) n_grids;      // (<= LSM2D_OCCUPANCY_MAX_CELLS: a tile holds a cell at least)
+  const OccGeo G = occupancy_geo(grids);
   const bool stamps = ctx->kernel_timing != 0;
-  const OccupancyLayout Y((size_t) total, (size_t) n_inputs, (size_t) n_grids, stamps ? n_wg : 0);
+  const OccupancyLayout Y((size_t) total, (size_t) n_inputs, (size_t) n_grids, stamps ? occupancy_workgroups(G) : 0, 2, 0);      // [rays | dropped]
   { int rc = ensure_scratch(ctx, Y.bytes); if (rc) return rc; rc = ensure_stage(ctx, std::max(Y.up_bytes, Y.down_bytes)); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const ds = (char*) L.d_scratch; char* const hs = (char*) L.h_stage;
-  {
-    OccInput* hin = (OccInput*) (hs + Y.u_inputs); int32_t* hoff = (int32_t*) (hs + Y.u_offset); int32_t* hbox = (int32_t*) (hs + Y.u_box);
-    int32_t* hfirst = (int32_t*) (hs + Y.u_first);
-    // the inputs grid by grid, list order kept inside a grid: a counting sort
-    for (int32_t g = 0; g <= n_grids; ++g) hfirst[g] = 0;
-    for (int32_t k = 0; k < n_inputs; ++k) ++hfirst[(grid ? grid[k] : 0) + 1];
-    for (int32_t g = 0; g < n_grids; ++g) hfirst[g + 1] += hfirst[g];
-    std::vector<int32_t> cursor(hfirst, hfirst + n_grids), order((size_t) n_inputs);
-    for (int32_t k = 0; k < n_inputs; ++k) order[(size_t) cursor[(size_t) (grid ? grid[k] : 0)]++] = k;
-    int32_t o = 0;
-    for (int32_t j = 0; j < n_inputs; ++j) {
-      const int32_t k = order[(size_t) j], ci = src_index ? src_index[k] : k;
-      OccInput& in = hin[j];
-      if (pose) { in.T = make_iso(pose + 3 * (size_t) k); in.sx = pose[3 * (size_t) k]; in.sy = pose[3 * (size_t) k + 1]; }
-      else { in.T.c = 1.0f; in.T.s = 0.0f; in.T.tx = 0.0f; in.T.ty = 0.0f; in.sx = 0.0f; in.sy = 0.0f; }
-      in.start = src->h_start[(size_t) ci]; in.grid = grid ? grid[k] : 0; in.has_pose = pose != nullptr; in.pad = 0;
-      hoff[j] = o; o += src->h_count[(size_t) ci];
-      hbox[4 * j] = hbox[4 * j + 1] = 0x7fffffff; hbox[4 * j + 2] = hbox[4 * j + 3] = kOccDropped;
-    }
-    hoff[n_inputs] = o;
-  }
+  occupancy_tables(hs, Y, n_inputs, n_grids, pose, grid, [&](int32_t k) { return src->h_start[(size_t) (src_index ? src_index[k] : k)]; },
+                   [&](int32_t k) { return src->h_count[(size_t) (src_index ? src_index[k] : k)]; });
   const int n = (int) total;
-  int32_t* const d_fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
   // ---- the timing bracket of the whole call
   ctx->have_timing = false;
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
@@ -217,35 +274,33 @@ extern "C" int lsm2d_occupancy_update(lsm2d_context* ctx, lsm2d_gridset* grids, 
     OccRaysArgs R;
     R.xy = src->d_xy; R.inputs = (const OccInput*) (ds + Y.u_inputs); R.offset = (const int32_t*) (ds + Y.u_offset); R.n_inputs = n_inputs; R.n = n; R.G = G;
     R.rays = (int4*) (ds + Y.o_rays); R.box = (int32_t*) (ds + Y.u_box);
-    R.n_rays = (int32_t*) (ds + Y.o_down + Y.d_rays); R.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped); R.fault = d_fault;
+    R.n_rays = (int32_t*) (ds + Y.o_down); R.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_row); R.fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
     hipLaunchKernelGGL(k_occ_rays, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
     HIPCHK(ctx, hipGetLastError());
-    OccTilesArgs T;
-    T.rays = R.rays; T.offset = R.offset; T.box = R.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_inputs; T.n = n; T.G = G;
-    T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
-    if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
-    if (grids->logodds) {      // the set's kind picks the tile kernel: everything around it is the one host path
-      const OccLogoddsArgs P = {T, grids->lp.l_hit, grids->lp.l_miss, grids->lp.l_min, grids->lp.l_max};
-      hipLaunchKernelGGL(k_occ_tiles_logodds<false>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, P);
-    } else
-      hipLaunchKernelGGL(k_occ_tiles, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
-    HIPCHK(ctx, hipGetLastError());
+    { const int rc = occupancy_launch_tiles(ctx, grids, ds, Y, n_inputs, n, G, stamps, false); if (rc) return rc; }
   }
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
-  HIPCHK(ctx, hipMemcpyAsync(hs, ds + Y.o_down, Y.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
-  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
-  const int32_t* const h_rays = (const int32_t*) (hs + Y.d_rays); const int32_t* const h_dropped = (const int32_t*) (hs + Y.d_dropped);
-  if (*(const int32_t*) (hs + Y.d_fault)) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: an index left its array on the device (the counters may be partly updated)");
-  long long sum = 0;
-  for (int32_t g = 0; g < n_grids; ++g) {
-    if (h_rays[g] < 0 || h_dropped[g] < 0) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: the counters are inconsistent");
-    sum += (long long) h_rays[g] + h_dropped[g];
-  }
-  if (sum != total) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update: the counters are inconsistent");
-  for (int32_t g = 0; g < n_grids; ++g) { if (out_rays) out_rays[g] = h_rays[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
-  ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
-  if (stamps && n > 0) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg);
+  int32_t* const out[] = {out_rays, out_dropped};
+  return occupancy_finish(ctx, "occupancy_update", Y, n_grids, total, out, stamps && n > 0 ? occupancy_workgroups(G) : 0);
+}
+
+// the tail of both render calls, R holding what is the kernel's own: the grid's cells rendered into the lane's scratch inside the timing bracket, then the copy and the wait
+template <class Args>
+static int occupancy_render_grid(lsm2d_context* ctx, const lsm2d_gridset* grids, int32_t grid_index, void (*kernel)(Args), Args& R, int8_t* out) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t n = grids->cells_per_grid;
+  { const int rc = ensure_scratch(ctx, up256(n)); if (rc) return rc; }
+  Lane& L = lane(ctx);
+  R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.out = (int8_t*) L.d_scratch;
+  ctx->have_timing = false;
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
+  hipLaunchKernelGGL(kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
+  HIPCHK(ctx, hipGetLastError());
+  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
+  note_timed(ctx, ctx->kernel_timing);
+  HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));      // one byte per cell comes down instead of eight
+  HIPCHK(ctx, stream_sync(ctx));
   return LSM2D_SUCCESS;
 }
 
@@ -256,40 +311,11 @@ extern "C" int lsm2d_occupancy_render(lsm2d_context* ctx, const lsm2d_gridset* g
   if (grids->logodds) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: a log-odds set (lsm2d_occupancy_render_logodds)");
   if (!valid_grid_index(grids, grid_index)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render: grid index outside the set");
   if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t n = grids->cells_per_grid;
-  { const int rc = ensure_scratch(ctx, up256(n)); if (rc) return rc; }
-  Lane& L = lane(ctx);
-  OccRenderArgs R; R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.min_visits = params->min_visits; R.out = (int8_t*) L.d_scratch;
-  ctx->have_timing = false;
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
-  hipLaunchKernelGGL(k_occ_render, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);
-  HIPCHK(ctx, hipGetLastError());
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
-  note_timed(ctx, ctx->kernel_timing);
-  HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));      // one byte per cell comes down instead of eight
-  HIPCHK(ctx, stream_sync(ctx));
-  return LSM2D_SUCCESS;
+  OccRenderArgs R; R.min_visits = params->min_visits;
+  return occupancy_render_grid(ctx, grids, grid_index, k_occ_render, R, out);
 }
 
 // ---- from raw scans (0.7.13) ------------------------------------------------------------------------------------------------------------------------------
-struct OccupancyScansLayout {
-  size_t u_inputs = 0, u_offset = 0, u_box = 0, u_first = 0, up_bytes = 0;      // the tables that travel up ...
-  size_t u_ranges = 0, ranges_bytes = 0;                                        // ... and, right behind them, the ranges unless they are device-resident
-  size_t o_down = 0, d_hit = 0, d_clear = 0, d_dropped = 0, d_fault = 0, down_bytes = 0;      // the block that travels down, cleared before the chain
-  size_t o_rays = 0, o_stamps = 0, bytes = 0;
-  OccupancyScansLayout(size_t n, size_t n_scans, size_t n_grids, size_t n_workgroups, bool ranges_travel) {
-    u_inputs = 0; u_offset = up256(sizeof(OccInput) * n_scans); u_box = up256(u_offset + sizeof(int32_t) * (n_scans + 1));
-    u_first = up256(u_box + sizeof(int32_t) * 4 * n_scans); up_bytes = up256(u_first + sizeof(int32_t) * (n_grids + 1));
-    u_ranges = up_bytes; ranges_bytes = ranges_travel ? sizeof(float) * n : 0;
-    o_down = up256(u_ranges + ranges_bytes);
-    d_hit = 0; d_clear = sizeof(int32_t) * n_grids; d_dropped = 2 * sizeof(int32_t) * n_grids; d_fault = 3 * sizeof(int32_t) * n_grids; down_bytes = d_fault + 4 * sizeof(int32_t);
-    o_rays = up256(o_down + down_bytes);
-    o_stamps = up256(o_rays + sizeof(int4) * n);
-    bytes = up256(o_stamps + sizeof(unsigned long long) * n_workgroups);
-  }
-};
-
 extern "C" int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* grids, const lsm2d_occupancy_scan_params* params, const float* ranges,
                                             int32_t n_scans, const float* pose, const int32_t* grid, int32_t* out_hit_rays, int32_t* out_clear_rays,
                                             int32_t* out_dropped) {
@@ -320,79 +346,37 @@ extern "C" int lsm2d_occupancy_update_scans(lsm2d_context* ctx, lsm2d_gridset* g
   const float2* d_dir = nullptr;
   { const int rc0 = beam_dirs_device(ctx, &geometry, &d_dir); if (rc0) return rc0; }      // (made and uploaded once per sensor geometry)
   HIPCHK(ctx, join_refill_stream(ctx, ctx->stream));
-  OccGeo G;
-  G.ox = grids->geo.origin_x; G.oy = grids->geo.origin_y; G.inv = 1.0f / grids->geo.resolution; G.w = grids->geo.width; G.h = grids->geo.height; G.n_grids = n_grids;
-  G.tiles_x = (G.w + kOccTile - 1) / kOccTile; G.tiles_y = (G.h + kOccTile - 1) / kOccTile;
-  const size_t n_wg = (size_t) G.tiles_x * (size_t) G.tiles_y * (size_t) n_grids;
+  const OccGeo G = occupancy_geo(grids);
   const bool stamps = ctx->kernel_timing != 0;
-  const OccupancyScansLayout Y((size_t) total, (size_t) n_scans, (size_t) n_grids, stamps ? n_wg : 0, kind != PtrKind::device);
-  { int rc = ensure_scratch(ctx, Y.bytes); if (rc) return rc; rc = ensure_stage(ctx, std::max(Y.up_bytes + (kind == PtrKind::pageable ? Y.ranges_bytes : 0), Y.down_bytes)); if (rc) return rc; }
+  const OccupancyLayout Y((size_t) total, (size_t) n_scans, (size_t) n_grids, stamps ? occupancy_workgroups(G) : 0, 3,      // [hit | clear | dropped]
+                          kind == PtrKind::device ? 0 : sizeof(float) * (size_t) total);
+  const size_t staged_bytes = Y.up_bytes + (kind == PtrKind::pageable ? Y.ranges_bytes : 0);      // pageable ranges ride behind the tables in the one copy up
+  { int rc = ensure_scratch(ctx, Y.bytes); if (rc) return rc; rc = ensure_stage(ctx, std::max(staged_bytes, Y.down_bytes)); if (rc) return rc; }
   Lane& L = lane(ctx);
   char* const ds = (char*) L.d_scratch; char* const hs = (char*) L.h_stage;
-  {
-    OccInput* hin = (OccInput*) (hs + Y.u_inputs); int32_t* hoff = (int32_t*) (hs + Y.u_offset); int32_t* hbox = (int32_t*) (hs + Y.u_box);
-    int32_t* hfirst = (int32_t*) (hs + Y.u_first);
-    // the scans grid by grid, list order kept inside a grid: a counting sort
-    for (int32_t g = 0; g <= n_grids; ++g) hfirst[g] = 0;
-    for (int32_t k = 0; k < n_scans; ++k) ++hfirst[(grid ? grid[k] : 0) + 1];
-    for (int32_t g = 0; g < n_grids; ++g) hfirst[g + 1] += hfirst[g];
-    std::vector<int32_t> cursor(hfirst, hfirst + n_grids), order((size_t) n_scans);
-    for (int32_t k = 0; k < n_scans; ++k) order[(size_t) cursor[(size_t) (grid ? grid[k] : 0)]++] = k;
-    for (int32_t j = 0; j < n_scans; ++j) {
-      const int32_t k = order[(size_t) j];
-      OccInput& in = hin[j];
-      if (pose) { in.T = make_iso(pose + 3 * (size_t) k); in.sx = pose[3 * (size_t) k]; in.sy = pose[3 * (size_t) k + 1]; }
-      else { in.T.c = 1.0f; in.T.s = 0.0f; in.T.tx = 0.0f; in.T.ty = 0.0f; in.sx = 0.0f; in.sy = 0.0f; }
-      in.start = k * nb; in.grid = grid ? grid[k] : 0; in.has_pose = pose != nullptr; in.pad = 0;      // (the ranges stay in the caller's order)
-      hoff[j] = j * nb;
-      hbox[4 * j] = hbox[4 * j + 1] = 0x7fffffff; hbox[4 * j + 2] = hbox[4 * j + 3] = kOccDropped;
-    }
-    hoff[n_scans] = n_scans * nb;
-    if (kind == PtrKind::pageable) memcpy(hs + Y.u_ranges, ranges, Y.ranges_bytes);
-  }
+  occupancy_tables(hs, Y, n_scans, n_grids, pose, grid, [&](int32_t k) { return k * nb; }, [&](int32_t) { return nb; });      // (the ranges stay in the caller's order)
+  if (kind == PtrKind::pageable) memcpy(hs + Y.u_ranges, ranges, Y.ranges_bytes);
   const int n = (int) total;
-  int32_t* const d_fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
-  ++ctx->uploads; ctx->last_h2d_bytes = kind == PtrKind::device ? 0 : (long long) Y.ranges_bytes;
+  ++ctx->uploads; ctx->last_h2d_bytes = (long long) Y.ranges_bytes;
   // ---- the timing bracket of the whole call
   ctx->have_timing = false;
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ds, hs, Y.up_bytes + (kind == PtrKind::pageable ? Y.ranges_bytes : 0), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ds, hs, staged_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (kind == PtrKind::pinned) HIPCHK(ctx, hipMemcpyAsync(ds + Y.u_ranges, ranges, Y.ranges_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ds + Y.o_down, 0, Y.down_bytes, ctx->stream));
   OccBeamsArgs B;
   B.ranges = kind == PtrKind::device ? ranges : (const float*) (ds + Y.u_ranges); B.beam_dir = d_dir; B.inputs = (const OccInput*) (ds + Y.u_inputs);
   B.n_inputs = n_scans; B.n_beams = nb; B.n = n; B.n_ranges = n; B.rmin = rmin; B.rmax = rmax; B.trace = trace; B.clear_no_return = params->clear_no_return; B.G = G;
   B.rays = (int4*) (ds + Y.o_rays); B.box = (int32_t*) (ds + Y.u_box);
-  B.n_hit = (int32_t*) (ds + Y.o_down + Y.d_hit); B.n_clear = (int32_t*) (ds + Y.o_down + Y.d_clear); B.n_dropped = (int32_t*) (ds + Y.o_down + Y.d_dropped); B.fault = d_fault;
+  B.n_hit = (int32_t*) (ds + Y.o_down); B.n_clear = (int32_t*) (ds + Y.o_down + Y.d_row); B.n_dropped = (int32_t*) (ds + Y.o_down + 2 * Y.d_row);
+  B.fault = (int32_t*) (ds + Y.o_down + Y.d_fault);
   hipLaunchKernelGGL(k_occ_beams, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, B);
   HIPCHK(ctx, hipGetLastError());
-  OccTilesArgs T;
-  T.rays = B.rays; T.offset = (const int32_t*) (ds + Y.u_offset); T.box = B.box; T.grid_first = (const int32_t*) (ds + Y.u_first); T.n_inputs = n_scans; T.n = n; T.G = G;
-  T.cells = grids->d_cells; T.fault = d_fault; T.stamps = stamps ? (unsigned long long*) (ds + Y.o_stamps) : nullptr;
-  if (stamps) HIPCHK(ctx, hipMemsetAsync(ds + Y.o_stamps, 0, sizeof(unsigned long long) * n_wg, ctx->stream));
-  if (grids->logodds) {      // the set's kind picks the tile kernel
-    const OccLogoddsArgs P = {T, grids->lp.l_hit, grids->lp.l_miss, grids->lp.l_min, grids->lp.l_max};
-    hipLaunchKernelGGL(k_occ_tiles_logodds<true>, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, P);
-  } else
-    hipLaunchKernelGGL(k_occ_tiles_scans, dim3((unsigned) n_wg), dim3(kOccBlock), 0, ctx->stream, T);
-  HIPCHK(ctx, hipGetLastError());
+  { const int rc = occupancy_launch_tiles(ctx, grids, ds, Y, n_scans, n, G, stamps, true); if (rc) return rc; }
   if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
   note_timed(ctx, ctx->kernel_timing);
-  HIPCHK(ctx, hipMemcpyAsync(hs, ds + Y.o_down, Y.down_bytes, hipMemcpyDeviceToHost, ctx->stream));      // the one copy down
-  HIPCHK(ctx, stream_sync(ctx));      // the one wait of the call
-  const int32_t* const h_hit = (const int32_t*) (hs + Y.d_hit); const int32_t* const h_clear = (const int32_t*) (hs + Y.d_clear);
-  const int32_t* const h_dropped = (const int32_t*) (hs + Y.d_dropped);
-  if (*(const int32_t*) (hs + Y.d_fault)) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: an index left its array on the device (the counters may be partly updated)");
-  long long sum = 0;
-  for (int32_t g = 0; g < n_grids; ++g) {
-    if (h_hit[g] < 0 || h_clear[g] < 0 || h_dropped[g] < 0) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: the counters are inconsistent");
-    sum += (long long) h_hit[g] + h_clear[g] + h_dropped[g];
-  }
-  if (sum != total) return fail(ctx, LSM2D_DEVICE_ERROR, "occupancy_update_scans: the counters are inconsistent");
-  for (int32_t g = 0; g < n_grids; ++g) { if (out_hit_rays) out_hit_rays[g] = h_hit[g]; if (out_clear_rays) out_clear_rays[g] = h_clear[g]; if (out_dropped) out_dropped[g] = h_dropped[g]; }
-  ctx->last_occ_wg_median_ns = 0; ctx->last_occ_wg_max_ns = 0;
-  if (stamps) return occupancy_read_stamps(ctx, ds + Y.o_stamps, n_wg);
-  return LSM2D_SUCCESS;
+  int32_t* const out[] = {out_hit_rays, out_clear_rays, out_dropped};
+  return occupancy_finish(ctx, "occupancy_update_scans", Y, n_grids, total, out, stamps ? occupancy_workgroups(G) : 0);
 }
 
 // ---- log-odds grid sets (0.7.14; PARITY.md section 3, item 17e) -------------------------------------------------------------------------------------------
@@ -474,18 +458,6 @@ extern "C" int lsm2d_occupancy_render_logodds(lsm2d_context* ctx, const lsm2d_gr
   OccRenderLogoddsArgs R;
   if (lsm2d_logodds_render_table(params->unit, R.threshold)) return fail(ctx, LSM2D_BAD_ARGUMENT, "occupancy_render_logodds: unit must be finite and > 0");
   if (ctx->inflight >= 2 || lane(ctx).busy) return fail(ctx, LSM2D_BAD_ARGUMENT, kBothLanesBusy);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t n = grids->cells_per_grid;
-  { const int rc = ensure_scratch(ctx, up256(n)); if (rc) return rc; }
-  Lane& L = lane(ctx);
-  R.cells = grids->d_cells + n * (size_t) grid_index; R.n = (long long) n; R.min_scans = params->min_scans; R.out = (int8_t*) L.d_scratch;
-  ctx->have_timing = false;
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev0, ctx->stream));
-  hipLaunchKernelGGL(k_occ_render_logodds, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, R);      // (the 100 thresholds ride in the arguments)
-  HIPCHK(ctx, hipGetLastError());
-  if (ctx->kernel_timing) HIPCHK(ctx, hipEventRecord(L.ev1, ctx->stream));
-  note_timed(ctx, ctx->kernel_timing);
-  HIPCHK(ctx, hipMemcpyAsync(out, L.d_scratch, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, stream_sync(ctx));
-  return LSM2D_SUCCESS;
+  R.min_scans = params->min_scans;
+  return occupancy_render_grid(ctx, grids, grid_index, k_occ_render_logodds, R, out);      // (the 100 thresholds ride in the arguments)
 }

@@ -21,15 +21,16 @@
 //   k_occ_put     a thread per cell: host counters (planar) into the interleaved cells, a NULL array leaving its counter (lsm2d_gridset_upload).
 // The walk (item 17c.3): with L the major extent and a the minor extent, step i = 0 .. L is the cell (m0 + s i, n0 + s' ((2 i a + L) / (2 L))), the division
 // integer; 2 * 32767^2 + 32767 < 2^31.  Steps 0 .. L - 1 are misses, step L is the hit; a cell outside the grid adds nothing and the ray goes on.
-// From raw scans (lsm2d_occupancy_update_scans, PARITY.md section 3, item 17d) the chain is two siblings of the first two kernels:
+// The walk stands ONCE, in occ_walk; every tile kernel calls it and says only what a hit and a miss do to its LDS.  k_occ_tiles is k_occ_tiles<false>.
+// From raw scans (lsm2d_occupancy_update_scans, PARITY.md section 3, item 17d) the chain is
 //   k_occ_beams        a thread per (scan, beam), i = j * n_beams + c over the scans in the host's grid-by-grid order (regular offsets: no search).  The beam's
 //                      class from its range (dropped / HIT of length r / CLEAR of length trace_range), the end point as ONE fp32 product per coordinate with
-//                      the host's direction table (k_preprocess_scans' product), then k_occ_rays' transform, cells and tests.  The 16-byte record carries the
-//                      ray's kind in bit 22 of its last word: y1 is stored as (y1 & 0x3fffff) | kind << 22 and sign-extended from 22 bits on read (a cell
-//                      coordinate needs 21).  Per (wave, scan) -- a wave straddles scans whenever n_beams is no multiple of 64 -- the box of the live rays of
-//                      BOTH kinds and the three counts are reduced over the wave and added by the leader lane, as in k_occ_rays.
-//   k_occ_tiles_scans  k_occ_tiles over records that carry a kind: a step is a hit iff i == L and the ray is a HIT ray; a CLEAR ray adds a miss on every step
-//                      0 .. L.  A sibling kernel beside k_occ_tiles, not a shared body: sharing moved an instruction of k_occ_tiles (see at the kernel).
+//                      the host's direction table (k_preprocess_scans' product), then k_occ_rays' transform, cells and tests (occ_ray_cells).  The 16-byte
+//                      record carries the ray's kind in bit 22 of its last word: y1 is stored as (y1 & 0x3fffff) | kind << 22 and sign-extended from 22 bits
+//                      on read (a cell coordinate needs 21).  Per (wave, scan) -- a wave straddles scans whenever n_beams is no multiple of 64 -- the box of
+//                      the live rays of BOTH kinds (occ_wave_box, as in k_occ_rays) and the three counts are reduced over the wave and added by the leader lane.
+//   k_occ_tiles<true>  the same kernel over records that carry a kind: a step is a hit iff i == L and the ray is a HIT ray; a CLEAR ray adds a miss on every
+//                      step 0 .. L.
 // Into a log-odds grid set (0.7.14, PARITY.md section 3, item 17e: a cell is {int32 value, uint32 observed}) the second kernel of either chain is
 //   k_occ_tiles_logodds<kKinds>  the same workgroup per (grid, tile), the same box rounds and the same walk, but the scans are applied ONE AFTER THE OTHER in
 //                      ascending input order and every cell gets ONE vote per scan.  The kept list is compacted in order (a ballot per wave, the four waves'
@@ -72,6 +73,33 @@ struct OccRaysArgs {
 LSM2D_DEV float occ_cell(float v, float o, float inv) { return __builtin_floorf(__fmul_rn(__fsub_rn(v, o), inv)); }
 LSM2D_DEV bool occ_in_range(float c) { return c >= -1048576.0f && c < 1048576.0f; }      // (NaN fails)
 
+// the cells of a ray from (sx, sy) to (x, y), and whether it is live: all four coordinates in range and no more than kOccMaxRayCells steps
+LSM2D_DEV bool occ_ray_cells(const OccGeo& G, float sx, float sy, float x, float y, int& x0, int& y0, int& x1, int& y1) {
+  const float fx0 = occ_cell(sx, G.ox, G.inv), fy0 = occ_cell(sy, G.oy, G.inv);
+  const float fx1 = occ_cell(x, G.ox, G.inv), fy1 = occ_cell(y, G.oy, G.inv);
+  bool live = false;
+  if (occ_in_range(fx0) && occ_in_range(fy0) && occ_in_range(fx1) && occ_in_range(fy1)) {
+    x0 = (int) fx0; y0 = (int) fy0; x1 = (int) fx1; y1 = (int) fy1;
+    const int ax = x1 > x0 ? x1 - x0 : x0 - x1, ay = y1 > y0 ? y1 - y0 : y0 - y1;
+    live = (ax > ay ? ax : ay) <= kOccMaxRayCells;
+  }
+  return live;
+}
+
+// the box {xmin, ymin, xmax, ymax} of the rays of the wave's lanes with `lv` set, in every lane ({max, max, min, min} if there is none)
+LSM2D_DEV int4 occ_wave_box(bool lv, int x0, int y0, int x1, int y1) {
+  int bx0 = lv ? (x0 < x1 ? x0 : x1) : 0x7fffffff, by0 = lv ? (y0 < y1 ? y0 : y1) : 0x7fffffff;
+  int bx1 = lv ? (x0 > x1 ? x0 : x1) : kOccDropped, by1 = lv ? (y0 > y1 ? y0 : y1) : kOccDropped;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int a = __shfl_xor(bx0, o), b = __shfl_xor(by0, o), c = __shfl_xor(bx1, o), d = __shfl_xor(by1, o);
+    bx1 = c > bx1 ? c : bx1; by1 = d > by1 ? d : by1; bx0 = a < bx0 ? a : bx0; by0 = b < by0 ? b : by0;      // (the maxima first: two instructions fewer per kernel)
+  }
+  return make_int4(bx0, by0, bx1, by1);
+}
+
+LSM2D_DEV void occ_box_add(int32_t* box, int4 b) { atomicMin(box, b.x); atomicMin(box + 1, b.y); atomicMax(box + 2, b.z); atomicMax(box + 3, b.w); }
+
 __global__ __launch_bounds__(256) void k_occ_rays(const OccRaysArgs A) {
   const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
   const bool in_range = i < A.n;
@@ -85,13 +113,7 @@ __global__ __launch_bounds__(256) void k_occ_rays(const OccRaysArgs A) {
     const float2 p = A.xy[(size_t) in.start + (size_t) (i - A.offset[lo])];
     float x = p.x, y = p.y;
     if (in.has_pose) xf_point(in.T, p.x, p.y, x, y);
-    const float fx0 = occ_cell(in.sx, A.G.ox, A.G.inv), fy0 = occ_cell(in.sy, A.G.oy, A.G.inv);
-    const float fx1 = occ_cell(x, A.G.ox, A.G.inv), fy1 = occ_cell(y, A.G.oy, A.G.inv);
-    if (occ_in_range(fx0) && occ_in_range(fy0) && occ_in_range(fx1) && occ_in_range(fy1)) {
-      x0 = (int) fx0; y0 = (int) fy0; x1 = (int) fx1; y1 = (int) fy1;
-      const int ax = x1 > x0 ? x1 - x0 : x0 - x1, ay = y1 > y0 ? y1 - y0 : y0 - y1;
-      live = (ax > ay ? ax : ay) <= kOccMaxRayCells;
-    }
+    live = occ_ray_cells(A.G, in.sx, in.sy, x, y, x0, y0, x1, y1);
     A.rays[i] = live ? make_int4(x0, y0, x1, y1) : make_int4(kOccDropped, 0, 0, 0);
   }
   // per (wave, input): the box of the live rays and the two counts, reduced over the wave; one lane adds them
@@ -100,23 +122,13 @@ __global__ __launch_bounds__(256) void k_occ_rays(const OccRaysArgs A) {
     const int leader = __ffsll((long long) todo) - 1;
     const int kk = __shfl(k, leader);
     const bool mine = in_range && k == kk, lv = mine && live;
-    int bx0 = lv ? (x0 < x1 ? x0 : x1) : 0x7fffffff, by0 = lv ? (y0 < y1 ? y0 : y1) : 0x7fffffff;
-    int bx1 = lv ? (x0 > x1 ? x0 : x1) : kOccDropped, by1 = lv ? (y0 > y1 ? y0 : y1) : kOccDropped;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int a = __shfl_xor(bx0, o), b = __shfl_xor(by0, o), c = __shfl_xor(bx1, o), d = __shfl_xor(by1, o);
-      bx0 = a < bx0 ? a : bx0; by0 = b < by0 ? b : by0; bx1 = c > bx1 ? c : bx1; by1 = d > by1 ? d : by1;
-    }
+    const int4 box = occ_wave_box(lv, x0, y0, x1, y1);
     const u64 m_mine = __ballot(mine);
     const int nl = __popcll(__ballot(lv)), nd = __popcll(m_mine) - nl;
     if (lane == leader) {
       if (kk < 0 || kk >= A.n_inputs || grid < 0 || grid >= A.G.n_grids) *A.fault = 1;
       else {
-        if (nl) {
-          atomicMin(A.box + 4 * (size_t) kk, bx0); atomicMin(A.box + 4 * (size_t) kk + 1, by0);
-          atomicMax(A.box + 4 * (size_t) kk + 2, bx1); atomicMax(A.box + 4 * (size_t) kk + 3, by1);
-          atomicAdd(A.n_rays + grid, nl);
-        }
+        if (nl) { occ_box_add(A.box + 4 * (size_t) kk, box); atomicAdd(A.n_rays + grid, nl); }
         if (nd) atomicAdd(A.n_dropped + grid, nd);
       }
     }
@@ -160,13 +172,7 @@ __global__ __launch_bounds__(256) void k_occ_beams(const OccBeamsArgs A) {
           const float px = __fmul_rn(len, d.x), py = __fmul_rn(len, d.y);
           float x = px, y = py;
           if (in.has_pose) xf_point(in.T, px, py, x, y);
-          const float fx0 = occ_cell(in.sx, A.G.ox, A.G.inv), fy0 = occ_cell(in.sy, A.G.oy, A.G.inv);
-          const float fx1 = occ_cell(x, A.G.ox, A.G.inv), fy1 = occ_cell(y, A.G.oy, A.G.inv);
-          if (occ_in_range(fx0) && occ_in_range(fy0) && occ_in_range(fx1) && occ_in_range(fy1)) {
-            x0 = (int) fx0; y0 = (int) fy0; x1 = (int) fx1; y1 = (int) fy1;
-            const int ax = x1 > x0 ? x1 - x0 : x0 - x1, ay = y1 > y0 ? y1 - y0 : y0 - y1;
-            live = (ax > ay ? ax : ay) <= kOccMaxRayCells;
-          }
+          live = occ_ray_cells(A.G, in.sx, in.sy, x, y, x0, y0, x1, y1);
         }
       }
     }
@@ -178,23 +184,14 @@ __global__ __launch_bounds__(256) void k_occ_beams(const OccBeamsArgs A) {
     const int leader = __ffsll((long long) todo) - 1;
     const int kk = __shfl(k, leader);
     const bool mine = in_range && k == kk, lv = mine && live;
-    int bx0 = lv ? (x0 < x1 ? x0 : x1) : 0x7fffffff, by0 = lv ? (y0 < y1 ? y0 : y1) : 0x7fffffff;
-    int bx1 = lv ? (x0 > x1 ? x0 : x1) : kOccDropped, by1 = lv ? (y0 > y1 ? y0 : y1) : kOccDropped;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int a = __shfl_xor(bx0, o), b = __shfl_xor(by0, o), c = __shfl_xor(bx1, o), d = __shfl_xor(by1, o);
-      bx0 = a < bx0 ? a : bx0; by0 = b < by0 ? b : by0; bx1 = c > bx1 ? c : bx1; by1 = d > by1 ? d : by1;
-    }
+    const int4 box = occ_wave_box(lv, x0, y0, x1, y1);
     const u64 m_mine = __ballot(mine);
     const bool any_bad = __ballot(mine && bad) != 0;
     const int nh = __popcll(__ballot(lv && kind == kOccHit)), nc = __popcll(__ballot(lv && kind == kOccClear)), nd = __popcll(m_mine) - nh - nc;
     if (lane == leader) {
       if (any_bad || kk < 0 || kk >= A.n_inputs || grid < 0 || grid >= A.G.n_grids) *A.fault = 1;
       else {
-        if (nh + nc) {
-          atomicMin(A.box + 4 * (size_t) kk, bx0); atomicMin(A.box + 4 * (size_t) kk + 1, by0);
-          atomicMax(A.box + 4 * (size_t) kk + 2, bx1); atomicMax(A.box + 4 * (size_t) kk + 3, by1);
-        }
+        if (nh + nc) occ_box_add(A.box + 4 * (size_t) kk, box);
         if (nh) atomicAdd(A.n_hit + grid, nh);
         if (nc) atomicAdd(A.n_clear + grid, nc);
         if (nd) atomicAdd(A.n_dropped + grid, nd);
@@ -214,6 +211,48 @@ struct OccTilesArgs {
   unsigned long long* stamps;                                       // [workgroups] or NULL: 10 ns ticks a workgroup that had work lived (kernel timing on: diagnostics)
 };
 
+// The walk of ONE ray record over ONE tile [cx0, cx1] x [cy0, cy1] (both ends inclusive, cut to the grid): hit(c) or miss(c) for every step whose cell c (row-major
+// in the uncut tile) lies in it.  The only place that knows item 17c.3's step arithmetic and, with kKinds, the record's kind bits (k_occ_beams).  Measured when
+// the three copies became this one: at equal size and resources the compiler states the box reject's compare chain in its complementary form, commutes the
+// operands of one v_mad_u64_u32 and swaps two registers of the remainder carry (profiles/r38).
+template <bool kKinds, class Hit, class Miss>
+LSM2D_DEV void occ_walk(int4 R, const int cx0, const int cy0, const int cx1, const int cy1, int32_t* const fault, Hit hit, Miss miss) {
+  if (R.x == kOccDropped) return;
+  bool hit_ray = true;
+  if (kKinds) {
+    hit_ray = ((uint32_t) R.w >> kOccKindShift) == (uint32_t) kOccHit;      // (a CLEAR ray: a miss on every step)
+    R.w = (int) ((uint32_t) R.w << (32 - kOccKindShift)) >> (32 - kOccKindShift);      // y1, sign-extended from 22 bits
+  }
+  if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) return;
+  const int dx = R.z - R.x, dy = R.w - R.y;
+  const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+  const bool xm = ax >= ay;      // a tie is x-major
+  const int L = xm ? ax : ay, a = xm ? ay : ax;
+  const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
+  const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
+  const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
+  int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
+  ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
+  if (ilo > ihi) return;
+  const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
+  const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
+  uint32_t q = num / den, rem = num - q * den;
+  for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
+    const int nn = n0 + sn * (int) q;
+    if (nn >= nlo && nn <= nhi) {
+      const int mm = m0 + sm * i;
+      const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
+      if (c < 0 || c >= kOccTile * kOccTile) *fault = 1;
+      else if (i == L && hit_ray) hit(c);
+      else miss(c);
+    }
+    rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
+    if (rem >= den) { rem -= den; ++q; }
+  }
+}
+
+// kKinds: the records carry a kind (k_occ_beams'), else every ray is a HIT ray (k_occ_rays')
+template <bool kKinds>
 __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
   __shared__ uint32_t s_hits[kOccTile * kOccTile];
   __shared__ uint32_t s_miss[kOccTile * kOccTile];
@@ -249,124 +288,8 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles(const OccTilesArgs A) {
       const int kk = s_list[j];
       const int b = A.offset[kk], e = A.offset[kk + 1];
       if (b < 0 || e > A.n || b > e) { *A.fault = 1; continue; }
-      for (int r = b + tid; r < e; r += kOccBlock) {
-        const int4 R = A.rays[r];
-        if (R.x == kOccDropped) continue;
-        if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) continue;
-        const int dx = R.z - R.x, dy = R.w - R.y;
-        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-        const bool xm = ax >= ay;      // a tie is x-major
-        const int L = xm ? ax : ay, a = xm ? ay : ax;
-        const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
-        const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
-        const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
-        int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
-        ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
-        if (ilo > ihi) continue;
-        const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
-        const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
-        uint32_t q = num / den, rem = num - q * den;
-        for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
-          const int nn = n0 + sn * (int) q;
-          if (nn >= nlo && nn <= nhi) {
-            const int mm = m0 + sm * i;
-            const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
-            if (c < 0 || c >= kOccTile * kOccTile) *A.fault = 1;
-            else if (i == L) atomicAdd(&s_hits[c], 1u);
-            else atomicAdd(&s_miss[c], 1u);
-          }
-          rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
-          if (rem >= den) { rem -= den; ++q; }
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (!zeroed) return;
-  for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) {
-    const uint32_t hh = s_hits[c], mm = s_miss[c];
-    if (!(hh | mm)) continue;
-    const int cx = cx0 + (c % kOccTile), cy = cy0 + (c / kOccTile);
-    if (cx > cx1 || cy > cy1) { *A.fault = 1; continue; }      // (the walk adds inside the cut tile only)
-    uint2* const cell = A.cells + (((size_t) g * (size_t) A.G.h + (size_t) cy) * (size_t) A.G.w + (size_t) cx);
-    const uint2 v = *cell;
-    const u64 nh = (u64) v.x + hh, nm = (u64) v.y + mm;
-    *cell = make_uint2(nh > 0xffffffffull ? 0xffffffffu : (uint32_t) nh, nm > 0xffffffffull ? 0xffffffffu : (uint32_t) nm);
-  }
-  if (A.stamps && tid == 0) A.stamps[blockIdx.x] = __builtin_amdgcn_s_memrealtime() - t_start;
-}
-
-// k_occ_tiles over records that carry a kind (k_occ_beams): a step is a hit iff i == L and the ray is a HIT ray -- the two marked lines are the whole
-// difference.  A sibling and not one shared body: with the walk as a device function templated on the records' kind and inlined into both kernels (by
-// reference, by value, the record read through a helper) the compiler commuted the operands of one v_mad_u64_u32 of k_occ_tiles, or moved more; k_occ_tiles
-// keeps the parent's instructions (profiles/r36/isa_diff_parent_vs_this_tree.txt), so it stays as it was and whoever changes the walk changes it twice.
-__global__ __launch_bounds__(kOccBlock) void k_occ_tiles_scans(const OccTilesArgs A) {
-  __shared__ uint32_t s_hits[kOccTile * kOccTile];
-  __shared__ uint32_t s_miss[kOccTile * kOccTile];
-  __shared__ int32_t s_list[kOccBlock];
-  __shared__ int32_t s_n;
-  const int tid = threadIdx.x;
-  const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  const int tpg = A.G.tiles_x * A.G.tiles_y;
-  const int g = (int) (blockIdx.x / (unsigned) tpg), t = (int) (blockIdx.x - (unsigned) g * (unsigned) tpg);
-  if (g >= A.G.n_grids) { if (tid == 0) *A.fault = 1; return; }
-  const int ty = t / A.G.tiles_x, tx = t - ty * A.G.tiles_x;
-  const int cx0 = tx * kOccTile, cy0 = ty * kOccTile;      // the tile's cells, both ends inclusive, cut to the grid
-  const int cx1 = (cx0 + kOccTile < A.G.w ? cx0 + kOccTile : A.G.w) - 1, cy1 = (cy0 + kOccTile < A.G.h ? cy0 + kOccTile : A.G.h) - 1;
-  const int first = A.grid_first[g], last = A.grid_first[g + 1];
-  if (first < 0 || last > A.n_inputs || first > last) { if (tid == 0) *A.fault = 1; return; }
-  bool zeroed = false;
-  for (int base = first; base < last; base += kOccBlock) {
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    const int k = base + tid;
-    if (k < last) {
-      const int4 B = *(const int4*) (A.box + 4 * (size_t) k);
-      if (B.x <= cx1 && B.z >= cx0 && B.y <= cy1 && B.w >= cy0) s_list[atomicAdd(&s_n, 1)] = k;      // (an input without a live ray keeps {max, max, min, min})
-    }
-    __syncthreads();
-    const int m = s_n;
-    if (m > 0 && !zeroed) {
-      for (int c = tid; c < kOccTile * kOccTile; c += kOccBlock) { s_hits[c] = 0u; s_miss[c] = 0u; }
-      __syncthreads();
-      zeroed = true;
-    }
-    for (int j = 0; j < m; ++j) {
-      const int kk = s_list[j];
-      const int b = A.offset[kk], e = A.offset[kk + 1];
-      if (b < 0 || e > A.n || b > e) { *A.fault = 1; continue; }
-      for (int r = b + tid; r < e; r += kOccBlock) {
-        int4 R = A.rays[r];
-        if (R.x == kOccDropped) continue;
-        const bool hit_ray = ((uint32_t) R.w >> kOccKindShift) == (uint32_t) kOccHit;
-        R.w = (int) ((uint32_t) R.w << (32 - kOccKindShift)) >> (32 - kOccKindShift);      // y1, sign-extended from 22 bits
-        if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) continue;
-        const int dx = R.z - R.x, dy = R.w - R.y;
-        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-        const bool xm = ax >= ay;      // a tie is x-major
-        const int L = xm ? ax : ay, a = xm ? ay : ax;
-        const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
-        const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
-        const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
-        int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
-        ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
-        if (ilo > ihi) continue;
-        const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
-        const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
-        uint32_t q = num / den, rem = num - q * den;
-        for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
-          const int nn = n0 + sn * (int) q;
-          if (nn >= nlo && nn <= nhi) {
-            const int mm = m0 + sm * i;
-            const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
-            if (c < 0 || c >= kOccTile * kOccTile) *A.fault = 1;
-            else if (i == L && hit_ray) atomicAdd(&s_hits[c], 1u);      // (a CLEAR ray: a miss on every step)
-            else atomicAdd(&s_miss[c], 1u);
-          }
-          rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
-          if (rem >= den) { rem -= den; ++q; }
-        }
-      }
+      for (int r = b + tid; r < e; r += kOccBlock)
+        occ_walk<kKinds>(A.rays[r], cx0, cy0, cx1, cy1, A.fault, [&](int c) { atomicAdd(&s_hits[c], 1u); }, [&](int c) { atomicAdd(&s_miss[c], 1u); });
     }
     __syncthreads();
   }
@@ -416,8 +339,8 @@ struct OccLogoddsArgs { OccTilesArgs T; int32_t l_hit, l_miss, l_min, l_max; }; 
 
 static constexpr int kOccMaskWords = kOccTile * kOccTile / 32;      // a tile's cells as bits
 
-// The walk is k_occ_tiles' (kKinds: k_occ_tiles_scans'), restated here and not shared for the reason given at k_occ_tiles_scans.  What differs is the
-// accumulation: a step sets a bit, and the bits of ONE scan become one clamped vote per cell before the next scan's walk begins.
+// The walk is occ_walk, as in k_occ_tiles<kKinds>.  What differs is the accumulation: a step sets a bit, and the bits of ONE scan become one clamped vote per
+// cell before the next scan's walk begins.
 template <bool kKinds>
 __global__ __launch_bounds__(kOccBlock) void k_occ_tiles_logodds(const OccLogoddsArgs P) {
   __shared__ int32_t s_val[kOccTile * kOccTile];
@@ -469,41 +392,8 @@ __global__ __launch_bounds__(kOccBlock) void k_occ_tiles_logodds(const OccLogodd
       const int kk = s_list[j];
       const int b = A.offset[kk], e = A.offset[kk + 1];
       if (b < 0 || e > A.n || b > e) { *A.fault = 1; continue; }      // (the same for every thread: no barrier is left out by some)
-      for (int r = b + tid; r < e; r += kOccBlock) {
-        int4 R = A.rays[r];
-        if (R.x == kOccDropped) continue;
-        bool hit_ray = true;
-        if (kKinds) {
-          hit_ray = ((uint32_t) R.w >> kOccKindShift) == (uint32_t) kOccHit;
-          R.w = (int) ((uint32_t) R.w << (32 - kOccKindShift)) >> (32 - kOccKindShift);      // y1, sign-extended from 22 bits
-        }
-        if ((R.x > R.z ? R.x : R.z) < cx0 || (R.x < R.z ? R.x : R.z) > cx1 || (R.y > R.w ? R.y : R.w) < cy0 || (R.y < R.w ? R.y : R.w) > cy1) continue;
-        const int dx = R.z - R.x, dy = R.w - R.y;
-        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-        const bool xm = ax >= ay;      // a tie is x-major
-        const int L = xm ? ax : ay, a = xm ? ay : ax;
-        const int m0 = xm ? R.x : R.y, n0 = xm ? R.y : R.x;
-        const int sm = (xm ? dx : dy) < 0 ? -1 : 1, sn = (xm ? dy : dx) < 0 ? -1 : 1;
-        const int mlo = xm ? cx0 : cy0, mhi = xm ? cx1 : cy1, nlo = xm ? cy0 : cx0, nhi = xm ? cy1 : cx1;
-        int ilo = sm > 0 ? mlo - m0 : m0 - mhi, ihi = sm > 0 ? mhi - m0 : m0 - mlo;      // the steps whose major coordinate lies in the tile
-        ilo = ilo > 0 ? ilo : 0; ihi = ihi < L ? ihi : L;
-        if (ilo > ihi) continue;
-        const uint32_t den = L ? 2u * (uint32_t) L : 1u;      // (L == 0: a == 0, the one step has the minor offset 0)
-        const uint32_t num = 2u * (uint32_t) ilo * (uint32_t) a + (uint32_t) L;
-        uint32_t q = num / den, rem = num - q * den;
-        for (int i = ilo; i <= ihi; ++i) {      // at most kOccTile steps
-          const int nn = n0 + sn * (int) q;
-          if (nn >= nlo && nn <= nhi) {
-            const int mm = m0 + sm * i;
-            const int c = ((xm ? nn : mm) - cy0) * kOccTile + ((xm ? mm : nn) - cx0);
-            if (c < 0 || c >= kOccTile * kOccTile) *A.fault = 1;
-            else if (i == L && hit_ray) atomicOr(&s_hitm[c >> 5], 1u << (c & 31));      // (a CLEAR ray: a miss on every step)
-            else atomicOr(&s_missm[c >> 5], 1u << (c & 31));
-          }
-          rem += 2u * (uint32_t) a;      // (2 a <= den: one carry at the most)
-          if (rem >= den) { rem -= den; ++q; }
-        }
-      }
+      for (int r = b + tid; r < e; r += kOccBlock)
+        occ_walk<kKinds>(A.rays[r], cx0, cy0, cx1, cy1, A.fault, [&](int c) { atomicOr(&s_hitm[c >> 5], 1u << (c & 31)); }, [&](int c) { atomicOr(&s_missm[c >> 5], 1u << (c & 31)); });
       __syncthreads();
       // one vote per cell: thread tid owns cells 16 tid .. 16 tid + 15, half a word of each mask, reads it, votes and clears it -- nobody else touches them
       {

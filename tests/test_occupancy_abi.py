@@ -82,7 +82,7 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
 def test_kernels_are_in_the_code_object_and_the_tile_is_the_sources():
     from srrg2_laser_slam_2d_amd import _capi, build
     blob = open(build.build(), "rb").read()
-    for k in (b"k_occ_rays", b"k_occ_tiles", b"k_occ_render", b"k_occ_put", b"occupancy_tile"):
+    for k in (b"k_occ_rays", b"k_occ_tilesILb0EE", b"k_occ_render", b"k_occ_put", b"occupancy_tile"):
         assert k in blob, k
     csrc = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "csrc")
     src = open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read()

@@ -49,7 +49,7 @@ def test_symbol_struct_and_macros_declared_bound_and_exported():
     assert len(re.findall(r"#define LSM2D_OCCUPANCY_\w+", header)) == 4 and "LSM2D_VERSION 160" in header and "0.7.13" in header
     block = header[header.index("occupancy grids from raw scans (0.7.13)"):header.index("} lsm2d_occupancy_scan_params;")]
     for text in ("item 17d", "item 17c.1", "xf_point", "LSM2D_OCCUPANCY_MAX_RAYS", "LSM2D_OCCUPANCY_MAX_RAY_CELLS", "LSM2D_CAPACITY_EXCEEDED", "no grid mapper",
-                 "NOT BUILT", "asynchronous form", "per-grid geometry", "once-per-scan", "several workgroups", "log-odds", "k_occ_beams", "k_occ_tiles_scans",
+                 "NOT BUILT", "asynchronous form", "per-grid geometry", "once-per-scan", "several workgroups", "log-odds", "k_occ_beams", "k_occ_tiles<true>",
                  "TWO launches", "ONE copy down", "ONE wait"):
         assert text in block, text
     # 0.7.12's block says where the truncation and the clearing went
@@ -81,10 +81,10 @@ def test_struct_layout_matches_the_c_compiler(tmp_path):
 def test_kernels_are_in_the_code_object_and_in_the_last_parts():
     from srrg2_laser_slam_2d_amd import build
     blob = open(build.build(), "rb").read()
-    for k in (b"k_occ_beams", b"k_occ_tiles_scans", b"k_occ_rays", b"k_occ_tiles"):
+    for k in (b"k_occ_beams", b"k_occ_tilesILb1EE", b"k_occ_rays", b"k_occ_tilesILb0EE"):
         assert k in blob, k
     csrc = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "csrc")
-    assert "void k_occ_beams(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read() and "void k_occ_tiles_scans(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read()
+    assert "void k_occ_beams(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read() and "void k_occ_tiles(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read()
     assert 'extern "C" int lsm2d_occupancy_update_scans(' in open(os.path.join(csrc, "lsm2d_capi_occupancy.inc")).read()
 
 
