@@ -27,16 +27,12 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 TAU = 0.05
 COLS = 1081
 ITERATIONS = 30
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("align_select_bench.cpp", tmp)
 
 
 def run_part(api, exe, tmp, part, scans, offs, m, poses, index, sel, args):
@@ -45,9 +41,8 @@ def run_part(api, exe, tmp, part, scans, offs, m, poses, index, sel, args):
     np.ascontiguousarray(scans, np.float32).tofile(files["scans"]); np.ascontiguousarray(offs, np.int32).tofile(files["offsets"])
     np.ascontiguousarray(m, np.float32).tofile(files["map"]); np.ascontiguousarray(poses, np.float32).tofile(files["poses"])
     (np.zeros(0, np.int32) if index is None else np.ascontiguousarray(index, np.int32)).tofile(files["index"])
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
     out = subprocess.run([exe, files["scans"], files["offsets"], files["map"], files["poses"], files["index"], str(COLS), repr(TAU), str(ITERATIONS),
-                          str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), str(args.k), str(args.steps), str(args.warmup), files["out"]],
+                          str(sel.min_inliers), bits_arg(sel.max_chi_per_inlier), bits_arg(sel.min_inlier_ratio), str(args.k), str(args.steps), str(args.warmup), files["out"]],
                          check=True, capture_output=True, text=True).stdout
     r = json.loads(out)
     # ---- parity gate: both verdicts are align_rank's on what that run's lsm2d_align_batch returned
@@ -83,7 +78,7 @@ def main():
     sel = api.SelectParams()      # the loop detector's thresholds
     parts = args.parts.split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("align_select_bench.cpp", tmp)
         lines = []
         if "a" in parts:
             wl = synth.make_workload(args.n, args.map, seed=1)
@@ -98,9 +93,7 @@ def main():
             x0 = synth.invert_poses(synth.compose_poses(synth.invert_poses(wl.x_true)[idx], delta)).astype(np.float32)
             lines.append(run_part(api, exe, tmp, "b", wl.scan_points, wl.scan_offsets, m, x0, idx, sel, args))
         for ln in lines:
-            if args.label:
-                ln["label"] = args.label
-            print(json.dumps(ln), flush=True)
+            bench_common.emit(ln, args.label)
 
 
 if __name__ == "__main__":

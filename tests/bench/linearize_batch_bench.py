@@ -18,29 +18,17 @@ The batch call is host-bound: the device works for 0.03 of its 0.5 ms; the rest 
 the 5 MB copy to the device and the wait.  The loop pays a staging copy, one or two launches and a wait per item (23 us each)."""
 import argparse
 import ctypes as C
-import json
 import math
-import os
 import statistics
 import sys
 import time
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT
+
 TAU = 0.05
-
-
-def _workload(synth, workdir, n, n_map):
-    path = os.path.join(workdir, "pairs_bench_%d_%d.npz" % (n, n_map)) if workdir else None
-    if path and os.path.exists(path):
-        z = np.load(path)
-        return z["scan_points"], z["scan_offsets"], z["map_points"], z["x0"]
-    wl = synth.make_workload(n, n_map, seed=1)
-    if path:
-        os.makedirs(workdir, exist_ok=True)
-        np.savez(path, scan_points=wl.scan_points, scan_offsets=wl.scan_offsets, map_points=wl.map_points, x0=wl.x0)
-    return wl.scan_points, wl.scan_offsets, wl.map_points, wl.x0
 
 
 def _median_ms(fn, steps, warmup):
@@ -135,12 +123,9 @@ def main():
     from srrg2_laser_slam_2d_amd import _capi as capi, api, synth
     po.lib()
     ctx = api.Context(0)
-    wl = _workload(synth, args.workdir, args.n, args.map)
+    wl = bench_common.workload(synth, args.workdir, args.n, args.map)
     for order in [int(v) for v in args.orders.split(",")]:
-        ln = run_order(api, capi, po, ctx, wl, order, args)
-        if args.label:
-            ln["label"] = args.label
-        print(json.dumps(ln), flush=True)
+        bench_common.emit(run_order(api, capi, po, ctx, wl, order, args), args.label)
     ctx.close()
 
 

@@ -27,18 +27,10 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 SEED = 1
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build(["occupancy_bench.cpp", "occupancy_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
-
-
-def _bits(v):
-    return str(int(np.float32(v).view(np.uint32)))
 
 
 def _inputs(synth, part):
@@ -71,7 +63,7 @@ def main():
     sys.path.insert(0, HERE_ROOT)
     from srrg2_laser_slam_2d_amd import synth
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build(["occupancy_bench.cpp", "occupancy_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
         for part in args.parts.split(","):
             pts, offs, poses, grid, n_grids, geo = _inputs(synth, part)
             fp, fo, fq, fg = (os.path.join(tmp, n) for n in ("points.bin", "offsets.bin", "poses.bin", "grid.bin"))
@@ -80,7 +72,7 @@ def main():
                 grid.tofile(fg)
             runs = []
             for _ in range(args.runs):
-                p = subprocess.run([exe, fp, fo, fq, fg if grid is not None else "-", str(n_grids), _bits(geo[0]), _bits(geo[1]), _bits(geo[2]), str(geo[3]), str(geo[4]),
+                p = subprocess.run([exe, fp, fo, fq, fg if grid is not None else "-", str(n_grids), bits_arg(geo[0]), bits_arg(geo[1]), bits_arg(geo[2]), str(geo[3]), str(geo[4]),
                                     str(args.steps), str(args.warmup)], capture_output=True, text=True)
                 assert p.returncode in (0, 3), p.stderr[-2000:]
                 r = json.loads(p.stdout)
@@ -97,9 +89,7 @@ def main():
                         render_ms=ren, render_download_route_ms=ren_host, render_movement_ms=round(max(ren) - min(ren), 4),
                         render_download_route_movement_ms=round(max(ren_host) - min(ren_host), 4),
                         host_route_wins=bool(min(host) < max(dev)), render_download_route_wins=bool(min(ren_host) < max(ren)), parity="ok")
-            if args.label:
-                line["label"] = args.label
-            print(json.dumps(line), flush=True)
+            bench_common.emit(line, args.label)
 
 
 if __name__ == "__main__":

@@ -27,17 +27,11 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import occupancy_scan_bench as scan_bench      # noqa: E402  (the parts, the sensor and the variants are that bench's)
+import bench_common
+import occupancy_scan_bench as scan_bench      # (the parts, the sensor and the variants are that bench's)
+from bench_common import HERE_ROOT, bits_arg as bits
 
 LOGODDS = (85, -40, -200, 350)      # l_hit, l_miss, l_min, l_max at 0.01 log-odds per unit: p_hit 0.7, p_miss 0.4, clamps at 0.12 and 0.97
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build(["occupancy_logodds_bench.cpp", "occupancy_scan_ref.cpp", "occupancy_logodds_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
 
 
 def main():
@@ -52,9 +46,8 @@ def main():
     assert args.steps >= 20, "medians of at least 20 timed steps"
     sys.path.insert(0, HERE_ROOT)
     from srrg2_laser_slam_2d_amd import synth
-    bits = scan_bench._bits
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build(["occupancy_logodds_bench.cpp", "occupancy_scan_ref.cpp", "occupancy_logodds_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
         for part in args.parts.split(","):
             ranges, poses, grid, n_grids, geo = scan_bench._inputs(synth, part)
             fr, fq, fg = (os.path.join(tmp, n) for n in ("ranges.bin", "poses.bin", "grid.bin"))
@@ -90,9 +83,7 @@ def main():
                             host_route_wins=bool(min(host) < max(lo)),
                             logodds_above_counts=bool(float(np.median(lo)) - float(np.median(cnt)) > max(cnt) - min(cnt)),
                             logodds_over_counts=round(float(np.median(lo)) / float(np.median(cnt)), 3), parity="ok")
-                if args.label:
-                    line["label"] = args.label
-                print(json.dumps(line), flush=True)
+                bench_common.emit(line, args.label)
 
 
 if __name__ == "__main__":

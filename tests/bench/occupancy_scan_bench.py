@@ -32,20 +32,12 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 SEED = 1
 N_BEAMS, ANGLE_MIN, ANGLE_MAX, RANGE_MIN = 1081, -0.75 * np.pi, 0.75 * np.pi, 0.1
 VARIANTS = {"none": (60.0, 60.0), "no_return": (12.0, 10.0)}      # (range_max, trace_range)
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build(["occupancy_scan_bench.cpp", "occupancy_scan_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
-
-
-def _bits(v):
-    return str(int(np.float32(v).view(np.uint32)))
 
 
 def _inputs(synth, part):
@@ -72,7 +64,7 @@ def main():
     sys.path.insert(0, HERE_ROOT)
     from srrg2_laser_slam_2d_amd import synth
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build(["occupancy_scan_bench.cpp", "occupancy_scan_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
         for part in args.parts.split(","):
             ranges, poses, grid, n_grids, geo = _inputs(synth, part)
             fr, fq, fg = (os.path.join(tmp, n) for n in ("ranges.bin", "poses.bin", "grid.bin"))
@@ -86,8 +78,8 @@ def main():
                 assert not two_call or share == 0.0, "the two-call route cannot clear: it is timed where no beam is without a return"
                 runs = []
                 for _ in range(args.runs):
-                    p = subprocess.run([exe, fr, fq, fg if grid is not None else "-", str(n_grids), str(N_BEAMS), _bits(ANGLE_MIN), _bits(ANGLE_MAX), _bits(RANGE_MIN),
-                                        _bits(range_max), _bits(trace), "1", _bits(geo[0]), _bits(geo[1]), _bits(geo[2]), str(geo[3]), str(geo[4]), str(args.steps),
+                    p = subprocess.run([exe, fr, fq, fg if grid is not None else "-", str(n_grids), str(N_BEAMS), bits_arg(ANGLE_MIN), bits_arg(ANGLE_MAX), bits_arg(RANGE_MIN),
+                                        bits_arg(range_max), bits_arg(trace), "1", bits_arg(geo[0]), bits_arg(geo[1]), bits_arg(geo[2]), str(geo[3]), str(geo[4]), str(args.steps),
                                         str(args.warmup), "1" if two_call else "0"], capture_output=True, text=True)
                     assert p.returncode in (0, 3), p.stderr[-2000:]
                     r = json.loads(p.stdout)
@@ -109,9 +101,7 @@ def main():
                                 two_call_tile_workgroup_median_us=[r["two_call_tile_workgroup_median_us"] for r in runs],
                                 two_call_tile_workgroup_longest_us=[r["two_call_tile_workgroup_longest_us"] for r in runs],
                                 new_call_above_two_call=bool(float(np.median(new)) - float(np.median(two)) > max(two) - min(two)))
-                if args.label:
-                    line["label"] = args.label
-                print(json.dumps(line), flush=True)
+                bench_common.emit(line, args.label)
 
 
 if __name__ == "__main__":

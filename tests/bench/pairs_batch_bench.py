@@ -14,7 +14,6 @@ run (the batch's pairs against single calls):
 same script times the parent commit next to this one (alternate the two in one job).  --workdir keeps the synthetic workload between invocations."""
 import argparse
 import ctypes as C
-import json
 import math
 import os
 import statistics
@@ -23,19 +22,8 @@ import time
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def _workload(synth, workdir, n, n_map):
-    path = os.path.join(workdir, "pairs_bench_%d_%d.npz" % (n, n_map)) if workdir else None
-    if path and os.path.exists(path):
-        z = np.load(path)
-        return z["scan_points"], z["scan_offsets"], z["map_points"], z["x0"]
-    wl = synth.make_workload(n, n_map, seed=1)
-    if path:
-        os.makedirs(workdir, exist_ok=True)
-        np.savez(path, scan_points=wl.scan_points, scan_offsets=wl.scan_offsets, map_points=wl.map_points, x0=wl.x0)
-    return wl.scan_points, wl.scan_offsets, wl.map_points, wl.x0
+import bench_common
+from bench_common import HERE_ROOT
 
 
 def _median_ms(fn, steps, warmup):
@@ -182,7 +170,7 @@ def main():
     from srrg2_laser_slam_2d_amd import api, synth
     parts = args.parts.split(",")
     ctx = api.Context(0)
-    wl = _workload(synth, args.workdir, args.n, args.map) if ("a" in parts or "b" in parts) else None
+    wl = bench_common.workload(synth, args.workdir, args.n, args.map) if ("a" in parts or "b" in parts) else None
     lines = []
     if "a" in parts:
         lines.append(part_a(api, ctx, wl, args))
@@ -191,9 +179,7 @@ def main():
     if "c" in parts:
         lines.append(part_c(api, ctx, args))
     for ln in lines:
-        if args.label:
-            ln["label"] = args.label
-        print(json.dumps(ln), flush=True)
+        bench_common.emit(ln, args.label)
     ctx.close()
 
 

@@ -25,25 +25,20 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 TAU = 0.05
 COLS = 1081
 ITERATIONS = 30
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("relocalize_bench.cpp", tmp)
 
 
 def run_part(exe, tmp, part, scans, offs, m, poses, sel, args):
     files = {k: os.path.join(tmp, "%s_%s.bin" % (part, k)) for k in ("scans", "offsets", "map", "poses")}
     np.ascontiguousarray(scans, np.float32).tofile(files["scans"]); np.ascontiguousarray(offs, np.int32).tofile(files["offsets"])
     np.ascontiguousarray(m, np.float32).tofile(files["map"]); np.ascontiguousarray(poses, np.float32).tofile(files["poses"])
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
     out = subprocess.run([exe, files["scans"], files["offsets"], files["map"], files["poses"], str(COLS), repr(TAU), str(ITERATIONS), str(sel.min_inliers),
-                          str(int(thr[0])), str(int(thr[1])), str(args.k_score), str(args.k), str(args.steps), str(args.warmup)],
+                          bits_arg(sel.max_chi_per_inlier), bits_arg(sel.min_inlier_ratio), str(args.k_score), str(args.k), str(args.steps), str(args.warmup)],
                          check=True, capture_output=True, text=True).stdout
     r = json.loads(out)
     assert r["outputs_equal"] == 1, "parity: the fused call's outputs against the two calls'"
@@ -77,7 +72,7 @@ def main():
     nobody = api.SelectParams(10 ** 9, 0.0, 2.0)
     parts = args.parts.split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("relocalize_bench.cpp", tmp)
         wl = synth.make_workload(args.n, args.map, seed=1)
         x0 = np.ascontiguousarray(wl.x0, np.float32)
         lines = []
@@ -93,9 +88,7 @@ def main():
         if "c" in parts:
             lines.append(run_part(exe, tmp, "c", wl.scan_points, wl.scan_offsets, wl.map_points, x0, nobody, args))
         for ln in lines:
-            if args.label:
-                ln["label"] = args.label
-            print(json.dumps(ln), flush=True)
+            bench_common.emit(ln, args.label)
 
 
 if __name__ == "__main__":

@@ -28,29 +28,13 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 TAU = 0.05
 COLS = 1081
 MIN_CORR = 10
 SENSORS = [(0.2, 0.1, 0.1), (-0.3, 0.0, math.pi)]
-
-
-def _workload(synth, workdir, n, n_map):
-    path = os.path.join(workdir, "pairs_bench_%d_%d.npz" % (n, n_map)) if workdir else None
-    if path and os.path.exists(path):
-        z = np.load(path)
-        return z["scan_points"], z["scan_offsets"], z["map_points"], z["x0"]
-    wl = synth.make_workload(n, n_map, seed=1)
-    if path:
-        os.makedirs(workdir, exist_ok=True)
-        np.savez(path, scan_points=wl.scan_points, scan_offsets=wl.scan_offsets, map_points=wl.map_points, x0=wl.x0)
-    return wl.scan_points, wl.scan_offsets, wl.map_points, wl.x0
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("score_aligner_bench.cpp", tmp)
 
 
 def run_part(api, po, cases, synth, exe, tmp, part, scans, offs, m, poses, order, args):
@@ -81,10 +65,9 @@ def run_part(api, po, cases, synth, exe, tmp, part, scans, offs, m, poses, order
     n_in = st["n_inliers"].astype(np.float32)
     per_inlier = st["chi_inliers"] / np.maximum(n_in, np.float32(1.0)); ratio = n_in / np.maximum(st["n_correspondences"], 1).astype(np.float32)
     sel = api.SelectParams(int(np.median(st["n_inliers"][ok])), float(np.quantile(per_inlier[ok], 0.9).astype(np.float32)), float(np.quantile(ratio[ok], 0.1).astype(np.float32)))
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
     out = subprocess.run([exe] + [files[k] for k in ("fixed0", "off0", "fixed1", "off1", "map", "poses", "sinv")] +
-                         [str(COLS), repr(TAU), str(order), str(MIN_CORR), str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), str(args.k), str(args.steps),
-                          str(args.warmup)], check=True, capture_output=True, text=True).stdout
+                         [str(COLS), repr(TAU), str(order), str(MIN_CORR), str(sel.min_inliers), bits_arg(sel.max_chi_per_inlier), bits_arg(sel.min_inlier_ratio), str(args.k),
+                          str(args.steps), str(args.warmup)], check=True, capture_output=True, text=True).stdout
     r = json.loads(out)
     # ---- parity gate
     assert r["rows_equal"] == 1, "parity: the new call's rows against the per-slice route combined on the host"
@@ -119,10 +102,10 @@ def main():
     from oracle import pyoracle as po
     from srrg2_laser_slam_2d_amd import api, synth
     po.lib()
-    pts, offs, m, x0 = _workload(synth, args.workdir, args.n, args.map)
+    pts, offs, m, x0 = bench_common.workload(synth, args.workdir, args.n, args.map)
     parts = args.parts.split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("score_aligner_bench.cpp", tmp)
         for order in [int(v) for v in args.orders.split(",")]:
             lines = []
             if "a" in parts:
@@ -137,9 +120,7 @@ def main():
                 scan = np.ascontiguousarray(pts[offs[0]:offs[1]])
                 lines.append(run_part(api, po, cases, synth, exe, tmp, "b", scan, np.int32([0, len(scan)]), m, poses, order, args))
             for ln in lines:
-                if args.label:
-                    ln["label"] = args.label
-                print(json.dumps(ln), flush=True)
+                bench_common.emit(ln, args.label)
 
 
 if __name__ == "__main__":

@@ -31,31 +31,19 @@ Measured on an MI355X (gfx950), medians of 20, every item byte-equal to the two-
       The two-call route at this size: not measured."""
 import argparse
 import ctypes as C
-import json
 import math
-import os
 import statistics
 import sys
 import time
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT
+
 TAU = 0.05
 COLS = 1081
 BUDGET = 1 << 21      # pair slots per launch group
-
-
-def _workload(synth, workdir, n, n_map):
-    path = os.path.join(workdir, "pairs_bench_%d_%d.npz" % (n, n_map)) if workdir else None
-    if path and os.path.exists(path):
-        z = np.load(path)
-        return z["scan_points"], z["scan_offsets"], z["map_points"], z["x0"]
-    wl = synth.make_workload(n, n_map, seed=1)
-    if path:
-        os.makedirs(workdir, exist_ok=True)
-        np.savez(path, scan_points=wl.scan_points, scan_offsets=wl.scan_offsets, map_points=wl.map_points, x0=wl.x0)
-    return wl.scan_points, wl.scan_offsets, wl.map_points, wl.x0
 
 
 def _stats(t):
@@ -215,12 +203,11 @@ def main():
     from srrg2_laser_slam_2d_amd import _capi as capi, api, synth
     po.lib()
     ctx = api.Context(0)
-    wl = _workload(synth, args.workdir, args.n, args.map)
+    wl = bench_common.workload(synth, args.workdir, args.n, args.map)
     parts = args.parts.split(",")
+
     def emit(ln):
-        if args.label:
-            ln["label"] = args.label
-        print(json.dumps(ln), flush=True)
+        bench_common.emit(ln, args.label)
 
     for order in [int(v) for v in args.orders.split(",")]:
         if "a" in parts:

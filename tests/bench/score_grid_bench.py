@@ -26,21 +26,13 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 TAU = 0.05
 COLS = 1081
 CENTER_OFF = (0.013, -0.021, 0.004)
 STEP = (1.0 / 16, 1.0 / 16, 0.01)
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("score_grid_bench.cpp", tmp)
-
-
-def _bits(v):
-    return [str(int(b)) for b in np.float32(v).view(np.uint32).ravel()]
 
 
 def main():
@@ -60,18 +52,17 @@ def main():
     if args.min_inliers is not None:
         sel.min_inliers = args.min_inliers
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("score_grid_bench.cpp", tmp)
         wl = synth.make_workload(4, args.map, seed=1)
         lo, hi = int(wl.scan_offsets[0]), int(wl.scan_offsets[1])
         scan, m = os.path.join(tmp, "scan.bin"), os.path.join(tmp, "map.bin")
         np.ascontiguousarray(wl.scan_points[lo:hi], np.float32).tofile(scan); np.ascontiguousarray(wl.map_points, np.float32).tofile(m)
         center = np.float32(wl.x0[0]) + np.float32(CENTER_OFF)
-        thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
         for part in args.parts.split(","):
             runs = []
             for _ in range(args.runs):
-                out = subprocess.run([exe, scan, m, str(COLS), repr(TAU)] + _bits(center) + _bits(STEP) +
-                                     [str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), "1" if part == "nobody" else "0", str(args.steps), str(args.warmup)],
+                out = subprocess.run([exe, scan, m, str(COLS), repr(TAU)] + [bits_arg(v) for v in center] + [bits_arg(v) for v in STEP] +
+                                     [str(sel.min_inliers), bits_arg(sel.max_chi_per_inlier), bits_arg(sel.min_inlier_ratio), "1" if part == "nobody" else "0", str(args.steps), str(args.warmup)],
                                      check=True, capture_output=True, text=True).stdout
                 r = json.loads(out)
                 assert all(p["outputs_equal"] == 1 for p in r["pyramids"]), "parity: the new call's outputs against the per-level route's"
@@ -87,9 +78,7 @@ def main():
                             level_counts=p0["level_counts"], exhaustive_accepted=runs[0]["exhaustive_accepted"],
                             best_to_exhaustive_best_m=p0["best_to_exhaustive_best_m"], best_to_exhaustive_best_rad=p0["best_to_exhaustive_best_rad"],
                             same_level0_cell=p0["same_level0_cell"], thresholds=[sel.min_inliers, sel.max_chi_per_inlier, sel.min_inlier_ratio], parity="ok")
-                if args.label:
-                    line["label"] = args.label
-                print(json.dumps(line), flush=True)
+                bench_common.emit(line, args.label)
 
 
 if __name__ == "__main__":

@@ -26,27 +26,11 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT
+
 TAU = 0.05
 COLS = 1081
-
-
-def _workload(synth, workdir, n, n_map):
-    path = os.path.join(workdir, "pairs_bench_%d_%d.npz" % (n, n_map)) if workdir else None
-    if path and os.path.exists(path):
-        z = np.load(path)
-        return z["scan_points"], z["scan_offsets"], z["map_points"], z["x0"]
-    wl = synth.make_workload(n, n_map, seed=1)
-    if path:
-        os.makedirs(workdir, exist_ok=True)
-        np.savez(path, scan_points=wl.scan_points, scan_offsets=wl.scan_offsets, map_points=wl.map_points, x0=wl.x0)
-    return wl.scan_points, wl.scan_offsets, wl.map_points, wl.x0
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("score_select_bench.cpp", tmp)
 
 
 def run_part(api, ctx, exe, tmp, part, scans, offs, m, poses, order, args):
@@ -64,9 +48,9 @@ def run_part(api, ctx, exe, tmp, part, scans, offs, m, poses, order, args):
     files = {k: os.path.join(tmp, "%s_%s.bin" % (part, k)) for k in ("scans", "offsets", "map", "poses", "stats")}
     np.ascontiguousarray(scans, np.float32).tofile(files["scans"]); np.ascontiguousarray(offs, np.int32).tofile(files["offsets"])
     np.ascontiguousarray(m, np.float32).tofile(files["map"]); np.ascontiguousarray(poses, np.float32).tofile(files["poses"])
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
     out = subprocess.run([exe, files["scans"], files["offsets"], files["map"], files["poses"], str(COLS), repr(TAU), str(order), str(sel.min_inliers),
-                          str(int(thr[0])), str(int(thr[1])), str(args.k), str(args.steps), str(args.warmup), files["stats"]],
+                          bench_common.bits_arg(sel.max_chi_per_inlier), bench_common.bits_arg(sel.min_inlier_ratio), str(args.k), str(args.steps), str(args.warmup),
+                          files["stats"]],
                          check=True, capture_output=True, text=True).stdout
     r = json.loads(out)
     # ---- parity gate: both selections are score_rank's on the statistics that run returned; they are also the ones this process scored
@@ -99,10 +83,10 @@ def main():
     sys.path.insert(0, HERE_ROOT)
     from srrg2_laser_slam_2d_amd import api, synth
     ctx = api.Context(0)
-    pts, offs, m, x0 = _workload(synth, args.workdir, args.n, args.map)
+    pts, offs, m, x0 = bench_common.workload(synth, args.workdir, args.n, args.map)
     parts = args.parts.split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("score_select_bench.cpp", tmp)
         for order in [int(v) for v in args.orders.split(",")]:
             lines = []
             if "a" in parts:
@@ -117,9 +101,7 @@ def main():
                 scan = np.ascontiguousarray(pts[offs[0]:offs[1]])
                 lines.append(run_part(api, ctx, exe, tmp, "b", scan, np.int32([0, len(scan)]), m, poses, order, args))
             for ln in lines:
-                if args.label:
-                    ln["label"] = args.label
-                print(json.dumps(ln), flush=True)
+                bench_common.emit(ln, args.label)
     ctx.close()
 
 

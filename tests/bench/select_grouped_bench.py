@@ -29,18 +29,14 @@ import tempfile
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 TAU = 0.05
 COLS = 721
 MAP_POINTS = 800
 DISTINCT = 16
 ITERATIONS = 30
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build("select_grouped_bench.cpp", tmp)
 
 
 def run_part(api, exe, tmp, mode, wl, x0, idx, groups, sel, args):
@@ -50,9 +46,9 @@ def run_part(api, exe, tmp, mode, wl, x0, idx, groups, sel, args):
     np.ascontiguousarray(wl.scan_points, np.float32).tofile(files["scans"]); np.ascontiguousarray(wl.scan_offsets, np.int32).tofile(files["offsets"])
     np.ascontiguousarray(wl.map_points, np.float32).tofile(files["map"]); np.ascontiguousarray(x0, np.float32).tofile(files["poses"])
     np.ascontiguousarray(idx, np.int32).tofile(files["index"]); np.ascontiguousarray(groups, np.int32).tofile(files["groups"])
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
     out = subprocess.run([exe, mode, files["scans"], files["offsets"], files["map"], files["poses"], files["index"], files["groups"], str(COLS), repr(TAU),
-                          str(ITERATIONS), str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), str(args.k), str(args.steps), str(args.warmup), files["out"]],
+                          str(ITERATIONS), str(sel.min_inliers), bits_arg(sel.max_chi_per_inlier), bits_arg(sel.min_inlier_ratio), str(args.k), str(args.steps),
+                          str(args.warmup), files["out"]],
                          check=True, capture_output=True, text=True).stdout
     r = json.loads(out)
     # ---- parity gate
@@ -109,7 +105,7 @@ def main():
         return x0, idx, (np.arange(G + 1) * per_robot).astype(np.int32)
 
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build("select_grouped_bench.cpp", tmp)
         lines = []
         for sel in sels:
             if "align" in parts:
@@ -118,9 +114,7 @@ def main():
             if "score" in parts:      # a relocalisation grid per robot: hypotheses within +-0.25 of the truth
                 lines.append(run_part(api, exe, tmp, "score", wl, *candidates(args.grid_robots, args.grid, 0.25, 10), sel, args))
         for ln in lines:
-            if args.label:
-                ln["label"] = args.label
-            print(json.dumps(ln), flush=True)
+            bench_common.emit(ln, args.label)
 
 
 if __name__ == "__main__":

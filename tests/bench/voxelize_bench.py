@@ -29,18 +29,10 @@ import time
 
 import numpy as np
 
-HERE_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_common
+from bench_common import HERE_ROOT, bits_arg
+
 SEED = 1
-
-
-def _build(tmp):
-    sys.path.insert(0, os.path.join(HERE_ROOT, "tests"))
-    import cpp_build
-    return cpp_build.build(["voxelize_bench.cpp", "voxelize_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
-
-
-def _bits(v):
-    return str(int(np.float32(v).view(np.uint32)))
 
 
 def _tenth_resolution(synth, world, n):
@@ -112,7 +104,7 @@ def main():
     from srrg2_laser_slam_2d_amd import synth
     failed = False
     with tempfile.TemporaryDirectory() as tmp:
-        exe = _build(tmp)
+        exe = bench_common.build(["voxelize_bench.cpp", "voxelize_ref.cpp"], tmp, flags=("-O2", "-ffp-contract=off"))
         for part in args.parts.split(","):
             if part == "aligner":
                 line = _aligner_report(args)
@@ -125,7 +117,7 @@ def main():
                     np.ascontiguousarray(poses, np.float32).tofile(fq)
                 runs = []
                 for _ in range(args.runs):
-                    p = subprocess.run([exe, fp, fo, fq if poses is not None else "-", mode, _bits(res), _bits(1.0), str(args.steps), str(args.warmup)],
+                    p = subprocess.run([exe, fp, fo, fq if poses is not None else "-", mode, bits_arg(res), bits_arg(1.0), str(args.steps), str(args.warmup)],
                                        capture_output=True, text=True)
                     assert p.returncode in (0, 3), p.stderr[-2000:]
                     r = json.loads(p.stdout)
@@ -140,9 +132,7 @@ def main():
                 if part in ("map100k", "map1m"):
                     line["gate_device_faster_by_more_than_the_movement"] = bool(min(host) - max(dev) > moved)
                     failed = failed or not line["gate_device_faster_by_more_than_the_movement"]
-            if args.label:
-                line["label"] = args.label
-            print(json.dumps(line), flush=True)
+            bench_common.emit(line, args.label)
     sys.exit(1 if failed else 0)
 
 

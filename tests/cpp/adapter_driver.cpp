@@ -8,19 +8,16 @@
 #include <multi_aligner_hip_2d.h>
 #include <raw_data_preprocessor_hip_2d.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
 #include <sstream>
+
+#include "driver_common.h"
 
 using namespace srrg2_core;
 using namespace srrg2_laser_slam_2d;
 using namespace srrg2_slam_interfaces;
 
 static PointNormal2fVectorCloud readCloud(const char* path) {
-  std::ifstream f(path, std::ios::binary);
-  f.seekg(0, std::ios::end); const size_t bytes = (size_t) f.tellg(); f.seekg(0);
-  std::vector<float> raw(bytes / 4); f.read((char*) raw.data(), (std::streamsize) bytes);
+  const std::vector<float> raw = read_all<float>(path);
   PointNormal2fVectorCloud c(raw.size() / 4);
   for (size_t i = 0; i < c.size(); ++i) {
     c[i].coordinates() = Vector2f(raw[4 * i], raw[4 * i + 1]); c[i].normal() = Vector2f(raw[4 * i + 2], raw[4 * i + 3]);
@@ -250,10 +247,8 @@ int main(int argc, char** argv) {
 
   // ---- raw-data preprocessor sibling (row f2), driven as the pipeline drives the reference module: setRawData(message), compute()
   if (argc >= 12) {
-    std::ifstream rf(argv[8], std::ios::binary);
-    rf.seekg(0, std::ios::end); const size_t bytes = (size_t) rf.tellg(); rf.seekg(0);
     auto msg = std::make_shared<LaserMessage>();
-    msg->ranges.value().resize(bytes / 4); rf.read((char*) msg->ranges.value().data(), (std::streamsize) bytes);
+    msg->ranges.value() = read_all<float>(argv[8]);
     msg->angle_min.setValue((float) atof(argv[9])); msg->angle_max.setValue((float) atof(argv[10]));
     msg->range_min.setValue(0.0f); msg->range_max.setValue(30.0f); msg->topic.setValue("/scan_front");
     RawDataPreprocessorHIP2D pre;
@@ -268,8 +263,9 @@ int main(int argc, char** argv) {
     try { pre.setRawData(nullptr); } catch (const std::runtime_error&) { threw_null = 1; }
     const bool took = pre.setRawData(msg);
     pre.compute();
-    std::ofstream of(argv[11], std::ios::binary);
-    for (const auto& p : meas) { const float v[4] = {p.coordinates().x(), p.coordinates().y(), p.normal().x(), p.normal().y()}; of.write((const char*) v, sizeof v); }
+    std::vector<float> flat;
+    for (const auto& p : meas) flat.insert(flat.end(), {p.coordinates().x(), p.coordinates().y(), p.normal().x(), p.normal().y()});
+    write_all(argv[11], flat.data(), flat.size());
     out << ",\"prep_status_unset\":" << status_unset << ",\"prep_took_other_topic\":" << (int) took_other << ",\"prep_threw_on_null\":" << threw_null
         << ",\"prep_took\":" << (int) took << ",\"prep_status\":" << (int) pre.status() << ",\"prep_points\":" << meas.size()
         << ",\"unprojector_range_max\":" << pre.param_unprojector->param_range_max.value() << ",\"unprojector_range_min\":" << pre.param_unprojector->param_range_min.value();

@@ -4,34 +4,23 @@
 // tau), has the device accept and rank them, and prints both results as JSON (floats as their bit patterns; the two float thresholds come as their bit
 // patterns).  The sweep names device 0 twice: two shards whose rows the host merges; it runs in the default order of summation only (a sweep's contexts
 // take no option).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d.hpp>
+
+#include "driver_common.h"
 
 using namespace lsm2d_host;
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-
 static void print_rows(const std::vector<int32_t>& index, const std::vector<Vector3f>& pose, const std::vector<std::array<float, 9>>& H,
                        const std::vector<int32_t>& its, const std::vector<lsm2d_iteration_stats>& st, int32_t n_accepted, int32_t n_success) {
-  printf("{\"n_accepted\": %d, \"n_success\": %d, \"index\": [", n_accepted, n_success);
-  for (size_t j = 0; j < index.size(); ++j) printf("%s%d", j ? "," : "", index[j]);
-  printf("], \"rows\": [");
+  printf("{\"n_accepted\": %d, \"n_success\": %d, ", n_accepted, n_success);
+  print_int_list("index", index, ", ");
+  printf("\"rows\": [");
   for (size_t j = 0; j < index.size(); ++j) {
-    printf("%s{\"pose\": [%u,%u,%u], \"H\": [", j ? "," : "", bits(pose[j][0]), bits(pose[j][1]), bits(pose[j][2]));
-    for (size_t c = 0; c < 9; ++c) printf("%s%u", c ? "," : "", bits(H[j][c]));
-    const lsm2d_iteration_stats& s = st[j];
-    printf("], \"iterations\": %d, \"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u]}", its[j], s.n_correspondences, s.n_inliers, s.n_outliers,
-           bits(s.chi_inliers), bits(s.chi_outliers), s.pair_digest_lo, s.pair_digest_hi);
+    printf("%s{", j ? "," : "");
+    print_bits_list("pose", pose[j].data(), 3, ", "); print_bits_list("H", H[j].data(), 9, ", ");
+    printf("\"iterations\": %d, ", its[j]);
+    print_stats(st[j]);
+    printf("}");
   }
   printf("]}");
 }
@@ -44,7 +33,7 @@ int main(int argc, char** argv) {
     const std::vector<float> pf = read_all<float>(argv[3]);
     const int cols = atoi(argv[4]); const float tau = (float) atof(argv[5]);
     const int iterations = atoi(argv[6]), min_num_inliers = atoi(argv[7]), order = atoi(argv[8]);
-    const lsm2d_select_params select{atoi(argv[9]), from_bits((uint32_t) strtoul(argv[10], nullptr, 10)), from_bits((uint32_t) strtoul(argv[11], nullptr, 10))};
+    const lsm2d_select_params select{atoi(argv[9]), from_bits_arg(argv[10]), from_bits_arg(argv[11])};
     const int32_t k = atoi(argv[12]);
     const size_t n = pf.size() / 3;
     std::vector<Vector3f> poses(n);

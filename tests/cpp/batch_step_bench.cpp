@@ -3,27 +3,16 @@
 // (configurations/stage_segway_double_config_MULTI.json:964-986).
 //   batch_step_bench map.bin scans.bin offsets.bin x0.bin steps warmup iterations beams
 // map / scans: float32 [N,4]; offsets: int32 [n+1]; x0: float32 [n,3] (map in scan: role A, fixed = scan, moving = map).  Prints one JSON line.
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "lsm2d.h"
 
-template <typename T> static std::vector<T> read_bin(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+#include "driver_common.h"
+
 #define CK(x) do { int rc_ = (x); if (rc_ < 0) { fprintf(stderr, "%s -> %d (%s)\n", #x, rc_, lsm2d_last_error(ctx)); return 1; } } while (0)
 
 int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s map.bin scans.bin offsets.bin x0.bin steps warmup iterations beams\n", argv[0]); return 2; }
-  const std::vector<float> map = read_bin<float>(argv[1]), scans = read_bin<float>(argv[2]), x0 = read_bin<float>(argv[4]);
-  const std::vector<int32_t> offs = read_bin<int32_t>(argv[3]);
+  const std::vector<float> map = read_all<float>(argv[1]), scans = read_all<float>(argv[2]), x0 = read_all<float>(argv[4]);
+  const std::vector<int32_t> offs = read_all<int32_t>(argv[3]);
   const int steps = atoi(argv[5]), warmup = atoi(argv[6]), its = atoi(argv[7]), beams = atoi(argv[8]);
   const int n = (int) offs.size() - 1;
   if (n < 1 || (int) x0.size() != 3 * n) { fprintf(stderr, "inconsistent inputs\n"); return 2; }

@@ -5,27 +5,16 @@
 // (tests/bench/track_batch_bench.py write_inputs); tracker j runs scenario j % n_scenarios.  Prints one JSON object: per step and tracker the pose's
 // three words, the status, the clipped cloud's size and the local map's size, all as hex strings.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 #include <lsm2d.hpp>
 
-template <typename T> static std::vector<T> read_bin(const std::string& path) {
-  FILE* f = fopen(path.c_str(), "rb"); if (!f) { perror(path.c_str()); exit(2); }
-  fseek(f, 0, SEEK_END); const long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+#include "driver_common.h"
 
 int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s dir n_scenarios steps n_beams angle_min angle_max n_trackers resolution\n", argv[0]); return 2; }
   const std::string dir = argv[1];
   const int M = atoi(argv[2]), S = atoi(argv[3]), nb = atoi(argv[4]), N = atoi(argv[7]);
-  const std::vector<float> ranges = read_bin<float>(dir + "/ranges.bin");
-  const std::vector<double> odo = read_bin<double>(dir + "/odo.bin"), start = read_bin<double>(dir + "/start.bin");
+  const std::vector<float> ranges = read_all<float>(dir + "/ranges.bin");
+  const std::vector<double> odo = read_all<double>(dir + "/odo.bin"), start = read_all<double>(dir + "/start.bin");
   if ((long) ranges.size() != (long) M * (S + 1) * 2 * nb || (long) odo.size() != (long) M * S * 3 || (long) start.size() != (long) M * 3) { fprintf(stderr, "bad inputs\n"); return 2; }
   auto rng = [&](int scen, int k, int sensor) { return ranges.data() + (((size_t) scen * (S + 1) + k) * 2 + sensor) * nb; };
   try {

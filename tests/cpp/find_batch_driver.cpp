@@ -3,26 +3,18 @@
 // reads n ragged float32 [N,4] scans (int32 offsets [n+1]), one map and n float32 poses, runs the projective finder (scan i fixed, the map moving) and the
 // exact point-query finder (the map fixed, scan i moving under the inverse pose) over the whole batch, compares every item with the same finder's compute()
 // on that item alone, and prints the batches' pairs as JSON.
-#include <cstdio>
-#include <cstdlib>
 #include <lsm2d.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+using namespace lsm2d_host;
 
 static Vector3f x_inv(const Vector3f& a) {
   const float c = cosf(a[2]), s = sinf(a[2]);
   return Vector3f{{-(c * a[0] + s * a[1]), -(-s * a[0] + c * a[1]), -a[2]}};
 }
 
-static bool same(const CorrespondenceVector& a, const CorrespondenceVector& b) {
+static bool same_pairs(const CorrespondenceVector& a, const CorrespondenceVector& b) {
   if (a.size() != b.size()) return false;
   for (size_t i = 0; i < a.size(); ++i) if (a[i].fixed_idx != b[i].fixed_idx || a[i].moving_idx != b[i].moving_idx) return false;
   return true;
@@ -72,11 +64,11 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < n; ++i) {
       CorrespondenceVector one;
       cf.setFixed(&scans[i]); cf.setMoving(&map); cf.setLocalMapInSensor(poses[i]); cf.setCorrespondences(&one); cf.compute();
-      if (!same(one, proj[i])) equal_single = 0;
-      if (!same(proj[i], proj_rev[n - 1 - i])) equal_reversed = 0;
+      if (!same_pairs(one, proj[i])) equal_single = 0;
+      if (!same_pairs(proj[i], proj_rev[n - 1 - i])) equal_reversed = 0;
       CorrespondenceVector one_nn;
       kd.setFixed(&map); kd.setMoving(&scans[i]); kd.setLocalMapInSensor(inv[i]); kd.setCorrespondences(&one_nn); kd.compute();
-      if (!same(one_nn, nn[i])) equal_single = 0;
+      if (!same_pairs(one_nn, nn[i])) equal_single = 0;
     }
     const size_t n_empty = cf.computeBatch(scan_set, map_set, std::vector<Vector3f>()).size();
 

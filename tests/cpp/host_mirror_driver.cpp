@@ -2,10 +2,9 @@
 // (apps/visual_test_correspondence_finder_projective_2d.cpp:71-97, apps/visual_test_aligner_2d.cpp:102-156):
 //   host_mirror_driver fixed.bin moving.bin x y theta cols iterations
 // reads two float32 [N,4] clouds, runs the finder at the given pose and the aligner from it, prints JSON.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d.hpp>
+
+#include "driver_common.h"
 
 using namespace lsm2d_host;
 
@@ -14,19 +13,11 @@ static Vector3f x_inv(const Vector3f& a) {     // (R,t)^-1 in (x, y, theta) form
   return Vector3f{{-(c * a[0] + s * a[1]), -(-s * a[0] + c * a[1]), -a[2]}};
 }
 
-static PointNormal2fVectorCloud read_cloud(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(PointNormal2f); fseek(f, 0, SEEK_SET);
-  PointNormal2fVectorCloud c((size_t) n);
-  if (n && fread(c.data(), sizeof(PointNormal2f), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return c;
-}
-
 int main(int argc, char** argv) {
   if (argc < 8) { fprintf(stderr, "usage: %s fixed.bin moving.bin x y theta cols iterations\n", argv[0]); return 2; }
   try {
     Context ctx(0);
-    PointNormal2fVectorCloud fixed = read_cloud(argv[1]), moving = read_cloud(argv[2]);
+    PointNormal2fVectorCloud fixed = read_all<PointNormal2f>(argv[1]), moving = read_all<PointNormal2f>(argv[2]);
     Vector3f pose{{(float) atof(argv[3]), (float) atof(argv[4]), (float) atof(argv[5])}};
     const int cols = atoi(argv[6]), its = atoi(argv[7]);
 

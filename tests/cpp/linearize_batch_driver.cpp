@@ -3,27 +3,11 @@
 // reads n ragged float32 [N,4] scans (int32 offsets [n+1]), one map and n float32 poses, finds every item's pairs with the projective finder's batch form
 // (scan i fixed, the map moving), linearises the whole batch under a Cauchy robustifier of threshold tau -- once as it is and once through a reversed index
 // array -- compares every item byte for byte with linearize() on that item alone, and prints the batch's results as JSON (floats as their bit patterns).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d.hpp>
 
+#include "driver_common.h"
+
 using namespace lsm2d_host;
-
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-
-static bool same(const Linearization& a, const Linearization& b) {
-  return !memcmp(a.H.data(), b.H.data(), sizeof(float) * 9) && !memcmp(a.b.data(), b.b.data(), sizeof(float) * 3) &&
-         !memcmp(&a.stats, &b.stats, sizeof(lsm2d_iteration_stats));
-}
-
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
 
 int main(int argc, char** argv) {
   if (argc < 8) { fprintf(stderr, "usage: %s scans.bin offsets.bin map.bin poses.bin cols tau sum_order\n", argv[0]); return 2; }
@@ -61,19 +45,18 @@ int main(int argc, char** argv) {
     int equal_single = 1, equal_reversed = 1;
     for (size_t i = 0; i < n; ++i) {
       const Linearization one = linearize(ctx, sp, scan_set, map_set, pairs[i], poses[i], (int32_t) i, 0);
-      if (!same(one, batch[i])) equal_single = 0;
-      if (!same(batch[i], batch_rev[n - 1 - i])) equal_reversed = 0;
+      if (!same_bytes(one, batch[i])) equal_single = 0;
+      if (!same_bytes(batch[i], batch_rev[n - 1 - i])) equal_reversed = 0;
     }
     const size_t n_empty = linearizeBatch(ctx, sp, scan_set, map_set, std::vector<CorrespondenceVector>(), std::vector<Vector3f>()).size();
 
     printf("{\"n\": %zu, \"equal_single\": %d, \"equal_reversed\": %d, \"n_empty\": %zu, \"items\": [", n, equal_single, equal_reversed, n_empty);
     for (size_t i = 0; i < n; ++i) {
       const Linearization& r = batch[i];
-      printf("%s{\"H\": [", i ? "," : "");
-      for (int k = 0; k < 9; ++k) printf("%s%u", k ? "," : "", bits(r.H[(size_t) k]));
-      printf("], \"b\": [%u,%u,%u], \"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u], \"pairs\": [", bits(r.b[0]), bits(r.b[1]), bits(r.b[2]),
-             r.stats.n_correspondences, r.stats.n_inliers, r.stats.n_outliers, bits(r.stats.chi_inliers), bits(r.stats.chi_outliers),
-             r.stats.pair_digest_lo, r.stats.pair_digest_hi);
+      printf("%s{", i ? "," : "");
+      print_bits_list("H", r.H.data(), 9, ", "); print_bits_list("b", r.b.data(), 3, ", ");
+      print_stats(r.stats);
+      printf(", \"pairs\": [");
       for (size_t k = 0; k < pairs[i].size(); ++k) printf("%s[%d,%d]", k ? "," : "", pairs[i][k].fixed_idx, pairs[i][k].moving_idx);
       printf("]}");
     }

@@ -7,39 +7,21 @@
 // Wall clock round calls that end in their wait, kernel timing off; medians over `steps` after `warmup`.  The two routes' outputs are compared byte for byte
 // after the first call of each AND after the last.  One more update with kernel timing on gives lsm2d_last_kernel_ms and the tile workgroups' median and
 // longest lifetime.  Prints one JSON line.
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+
+#include "driver_common.h"
 
 extern "C" void occref_update(const float* points, const int32_t* offsets, int n_inputs, const float* pose, const int32_t* grid, int n_grids, float ox, float oy,
                               float resolution, int width, int height, uint32_t* hits, uint32_t* misses, int32_t* rays, int32_t* dropped);
-
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void must(int rc, const char* what, lsm2d_context* ctx) { if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); } }
-static void stats(std::vector<double> v, double out[3]) { std::sort(v.begin(), v.end()); out[0] = v[v.size() / 2]; out[1] = v.front(); out[2] = v.back(); }
 
 int main(int argc, char** argv) {
   if (argc < 13) { fprintf(stderr, "usage: %s points.bin offsets.bin poses.bin grid.bin|- n_grids ox_bits oy_bits res_bits width height steps warmup\n", argv[0]); return 2; }
   const std::vector<float> pts = read_all<float>(argv[1]);
   const std::vector<int32_t> offs = read_all<int32_t>(argv[2]);
   const std::vector<float> poses = read_all<float>(argv[3]);
-  const std::vector<int32_t> grid = strcmp(argv[4], "-") ? read_all<int32_t>(argv[4]) : std::vector<int32_t>();
+  const std::vector<int32_t> grid = read_all_or_empty<int32_t>(argv[4]);
   const int32_t G = atoi(argv[5]);
-  const lsm2d_grid_geometry geo{from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]), atoi(argv[9]), atoi(argv[10])};
+  const lsm2d_grid_geometry geo{from_bits_arg(argv[6]), from_bits_arg(argv[7]), from_bits_arg(argv[8]), atoi(argv[9]), atoi(argv[10])};
   const int steps = atoi(argv[11]), warmup = atoi(argv[12]);
   const int32_t K = (int32_t) offs.size() - 1; const int64_t N = offs[(size_t) K];
   const size_t cells = (size_t) geo.width * (size_t) geo.height;
@@ -98,7 +80,7 @@ int main(int argc, char** argv) {
     if (i >= warmup) { rd.push_back(t1 - t0); rh.push_back(t3 - t2); }
   }
   const int render_equal = r_dev == r_host;
-  double d[3], h[3], r1[3], r2[3]; stats(td, d); stats(th, h); stats(rd, r1); stats(rh, r2);
+  double d[3], h[3], r1[3], r2[3]; summary(td, d, true); summary(th, h, true); summary(rd, r1, true); summary(rh, r2, true);      // the upper middle element, as ever
   float kernel_ms = 0.0f; int64_t wg_median = 0, wg_max = 0;
   must(lsm2d_set_option(ctx, "kernel_timing", 1), "lsm2d_set_option", ctx);
   device_route();

@@ -3,21 +3,11 @@
 // The inputs (float [n][4], int32 offsets [n_inputs + 1], float poses [n_inputs][3], int32 grid [n_inputs]) are ray-traced TWICE into a set of n_grids grids
 // (the counters accumulate); out.bin receives, per grid, hits [h][w] uint32, misses [h][w] uint32 and the render [h][w] int8; rays and dropped counts of
 // the second call are printed as JSON.  The Python test compares the bytes with api.occupancy_update / occupancy_render on the same inputs.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_occupancy.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
+using namespace lsm2d_host;
 
 int main(int argc, char** argv) {
   if (argc < 13) { fprintf(stderr, "usage: %s points.bin offsets.bin poses.bin|- grid.bin|- n_grids ox_bits oy_bits res_bits width height min_visits out.bin\n", argv[0]); return 2; }
@@ -27,10 +17,10 @@ int main(int argc, char** argv) {
     const std::vector<int32_t> offs = read_all<int32_t>(argv[2]);
     std::vector<PointNormal2fVectorCloud> clouds;
     for (size_t k = 0; k + 1 < offs.size(); ++k) clouds.emplace_back(pts.begin() + offs[k], pts.begin() + offs[k + 1]);
-    const std::vector<Vector3f> poses = strcmp(argv[3], "-") ? read_all<Vector3f>(argv[3]) : std::vector<Vector3f>();
-    const std::vector<int32_t> grid = strcmp(argv[4], "-") ? read_all<int32_t>(argv[4]) : std::vector<int32_t>();
+    const std::vector<Vector3f> poses = read_all_or_empty<Vector3f>(argv[3]);
+    const std::vector<int32_t> grid = read_all_or_empty<int32_t>(argv[4]);
     const int32_t n_grids = atoi(argv[5]);
-    const lsm2d_grid_geometry geo{from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]), atoi(argv[9]), atoi(argv[10])};
+    const lsm2d_grid_geometry geo{from_bits_arg(argv[6]), from_bits_arg(argv[7]), from_bits_arg(argv[8]), atoi(argv[9]), atoi(argv[10])};
     CloudSet src(ctx, clouds);
     GridSet grids(ctx, geo, n_grids);
     occupancyUpdate(ctx, grids, src.get(), {}, poses, grid);
@@ -42,11 +32,8 @@ int main(int argc, char** argv) {
       fwrite(c.hits.data(), sizeof(uint32_t), c.hits.size(), out); fwrite(c.misses.data(), sizeof(uint32_t), c.misses.size(), out); fwrite(r.data(), 1, r.size(), out);
     }
     fclose(out);
-    printf("{\"rays\": [");
-    for (size_t g = 0; g < u.rays.size(); ++g) printf("%s%d", g ? "," : "", u.rays[g]);
-    printf("], \"dropped\": [");
-    for (size_t g = 0; g < u.dropped.size(); ++g) printf("%s%d", g ? "," : "", u.dropped[g]);
-    printf("]}\n");
+    printf("{");
+    print_int_list("rays", u.rays, ", "); print_int_list("dropped", u.dropped, "}\n");
   } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
   return 0;
 }

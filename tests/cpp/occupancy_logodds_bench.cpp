@@ -11,38 +11,22 @@
 // with kernel timing on gives lsm2d_last_kernel_ms and the tile workgroups' median and longest lifetime under both kinds of set.  Prints one JSON line.
 #include <lsm2d_logodds.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "driver_common.h"
 
 extern "C" void occsref_rays(const lsm2d_occupancy_scan_params* P, const float* ranges, const float* pose, float ox, float oy, float resolution, int32_t* rays, int32_t* kind);
 extern "C" void occlref_update(const lsm2d_logodds_params* P, const int32_t* rays, const int32_t* kind, const int32_t* first, int n_scans, const int32_t* grid, int n_grids,
                                int width, int height, int32_t* value, uint32_t* observed);
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void must(int rc, const char* what, lsm2d_context* ctx) { if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); } }
-static void stats(std::vector<double> v, double out[3]) { if (v.empty()) { out[0] = out[1] = out[2] = 0.0; return; } std::sort(v.begin(), v.end()); out[0] = v[v.size() / 2]; out[1] = v.front(); out[2] = v.back(); }
 static long long total(const std::vector<int32_t>& v) { long long s = 0; for (int32_t x : v) s += x; return s; }
 
 int main(int argc, char** argv) {
   if (argc < 23) { fprintf(stderr, "usage: %s ranges.bin poses.bin grid.bin|- n_grids n_beams amin amax rmin rmax trace (bits) clear ox oy res (bits) width height steps warmup l_hit l_miss l_min l_max\n", argv[0]); return 2; }
   const std::vector<float> ranges = read_all<float>(argv[1]);
   const std::vector<float> poses = read_all<float>(argv[2]);
-  const std::vector<int32_t> grid = strcmp(argv[3], "-") ? read_all<int32_t>(argv[3]) : std::vector<int32_t>();
+  const std::vector<int32_t> grid = read_all_or_empty<int32_t>(argv[3]);
   const int32_t G = atoi(argv[4]);
-  const lsm2d_occupancy_scan_params prm{atoi(argv[5]), from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]), from_bits(argv[9]), from_bits(argv[10]), atoi(argv[11])};
-  const lsm2d_grid_geometry geo{from_bits(argv[12]), from_bits(argv[13]), from_bits(argv[14]), atoi(argv[15]), atoi(argv[16])};
+  const lsm2d_occupancy_scan_params prm{atoi(argv[5]), from_bits_arg(argv[6]), from_bits_arg(argv[7]), from_bits_arg(argv[8]), from_bits_arg(argv[9]), from_bits_arg(argv[10]), atoi(argv[11])};
+  const lsm2d_grid_geometry geo{from_bits_arg(argv[12]), from_bits_arg(argv[13]), from_bits_arg(argv[14]), atoi(argv[15]), atoi(argv[16])};
   const int steps = atoi(argv[17]), warmup = atoi(argv[18]);
   const lsm2d_logodds_params lp{atoi(argv[19]), atoi(argv[20]), atoi(argv[21]), atoi(argv[22])};
   const int32_t K = (int32_t) (ranges.size() / (size_t) prm.n_beams), nb = prm.n_beams;
@@ -87,7 +71,7 @@ int main(int argc, char** argv) {
     if (i >= warmup) { tl.push_back(a1 - a0); tc.push_back(b1 - b0); th.push_back(c1 - c0); }
   }
   equal = equal && grids_equal();
-  double l[3], c[3], h[3]; stats(tl, l); stats(tc, c); stats(th, h);
+  double l[3], c[3], h[3]; summary(tl, l, true); summary(tc, c, true); summary(th, h, true);      // the upper middle element, as ever
   float k_ms[2] = {0.0f, 0.0f}; int64_t wg_median[2] = {0, 0}, wg_max[2] = {0, 0};
   must(lsm2d_set_option(ctx, "kernel_timing", 1), "lsm2d_set_option", ctx);
   for (int which = 0; which < 2; ++which) {

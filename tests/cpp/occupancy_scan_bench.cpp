@@ -9,41 +9,24 @@
 // All accumulate from zero, call after call.  Wall clock round calls that end in their wait, kernel timing off; medians over `steps` after `warmup`.  The
 // new call's counters and counts are compared with the host route's byte for byte after the first call of each AND after the last.  One more new call with
 // kernel timing on gives lsm2d_last_kernel_ms and the tile workgroups' median and longest lifetime.  Prints one JSON line.
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+
+#include "driver_common.h"
 
 extern "C" void occsref_update(const lsm2d_occupancy_scan_params* P, const float* ranges, int n_scans, const float* pose, const int32_t* grid, int n_grids, float ox,
                                float oy, float resolution, int width, int height, uint32_t* hits, uint32_t* misses, int32_t* hit_rays, int32_t* clear_rays,
                                int32_t* dropped);
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void must(int rc, const char* what, lsm2d_context* ctx) { if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); } }
-static void stats(std::vector<double> v, double out[3]) { if (v.empty()) { out[0] = out[1] = out[2] = 0.0; return; } std::sort(v.begin(), v.end()); out[0] = v[v.size() / 2]; out[1] = v.front(); out[2] = v.back(); }
 static long long total(const std::vector<int32_t>& v) { long long s = 0; for (int32_t x : v) s += x; return s; }
 
 int main(int argc, char** argv) {
   if (argc < 20) { fprintf(stderr, "usage: %s ranges.bin poses.bin grid.bin|- n_grids n_beams amin amax rmin rmax trace (bits) clear ox oy res (bits) width height steps warmup two_call\n", argv[0]); return 2; }
   const std::vector<float> ranges = read_all<float>(argv[1]);
   const std::vector<float> poses = read_all<float>(argv[2]);
-  const std::vector<int32_t> grid = strcmp(argv[3], "-") ? read_all<int32_t>(argv[3]) : std::vector<int32_t>();
+  const std::vector<int32_t> grid = read_all_or_empty<int32_t>(argv[3]);
   const int32_t G = atoi(argv[4]);
-  const lsm2d_occupancy_scan_params prm{atoi(argv[5]), from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]), from_bits(argv[9]), from_bits(argv[10]), atoi(argv[11])};
-  const lsm2d_grid_geometry geo{from_bits(argv[12]), from_bits(argv[13]), from_bits(argv[14]), atoi(argv[15]), atoi(argv[16])};
+  const lsm2d_occupancy_scan_params prm{atoi(argv[5]), from_bits_arg(argv[6]), from_bits_arg(argv[7]), from_bits_arg(argv[8]), from_bits_arg(argv[9]), from_bits_arg(argv[10]), atoi(argv[11])};
+  const lsm2d_grid_geometry geo{from_bits_arg(argv[12]), from_bits_arg(argv[13]), from_bits_arg(argv[14]), atoi(argv[15]), atoi(argv[16])};
   const int steps = atoi(argv[17]), warmup = atoi(argv[18]), two_call = atoi(argv[19]);
   const int32_t K = (int32_t) (ranges.size() / (size_t) prm.n_beams);
   const size_t cells = (size_t) geo.width * (size_t) geo.height;
@@ -91,7 +74,7 @@ int main(int argc, char** argv) {
     if (i >= warmup) { tn.push_back(a1 - a0); th.push_back(b1 - b0); if (two_call) t2.push_back(c1 - c0); }
   }
   equal = equal && grids_equal();
-  double n[3], h[3], w[3]; stats(tn, n); stats(th, h); stats(t2, w);
+  double n[3], h[3], w[3]; summary(tn, n, true); summary(th, h, true); summary(t2, w, true);      // the upper middle element, as ever
   float kernel_ms = 0.0f; int64_t wg_median = 0, wg_max = 0;
   must(lsm2d_set_option(ctx, "kernel_timing", 1), "lsm2d_set_option", ctx);
   new_call();

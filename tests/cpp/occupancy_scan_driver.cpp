@@ -4,37 +4,22 @@
 // The scans (float ranges [n_scans][n_beams], float poses [n_scans][3], int32 grid [n_scans]) are ray-traced TWICE into a set of n_grids grids (the counters
 // accumulate); out.bin receives, per grid, hits [h][w] uint32, misses [h][w] uint32 and the render [h][w] int8; the three counts of the second call are
 // printed as JSON.  The Python test compares the bytes with api.occupancy_update_scans / occupancy_render on the same inputs.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_occupancy.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static void print_list(const char* name, const std::vector<int32_t>& v, const char* tail) {
-  printf("\"%s\": [", name);
-  for (size_t g = 0; g < v.size(); ++g) printf("%s%d", g ? "," : "", v[g]);
-  printf("]%s", tail);
-}
+using namespace lsm2d_host;
 
 int main(int argc, char** argv) {
   if (argc < 19) { fprintf(stderr, "usage: %s ranges.bin poses.bin|- grid.bin|- n_grids n_beams amin amax rmin rmax trace (bits) clear ox oy res (bits) width height min_visits out.bin\n", argv[0]); return 2; }
   try {
     Context ctx(0);
     const std::vector<float> ranges = read_all<float>(argv[1]);
-    const std::vector<Vector3f> poses = strcmp(argv[2], "-") ? read_all<Vector3f>(argv[2]) : std::vector<Vector3f>();
-    const std::vector<int32_t> grid = strcmp(argv[3], "-") ? read_all<int32_t>(argv[3]) : std::vector<int32_t>();
+    const std::vector<Vector3f> poses = read_all_or_empty<Vector3f>(argv[2]);
+    const std::vector<int32_t> grid = read_all_or_empty<int32_t>(argv[3]);
     const int32_t n_grids = atoi(argv[4]), n_beams = atoi(argv[5]);
-    const OccupancyScanParams params(n_beams, from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]), from_bits(argv[9]), from_bits(argv[10]), atoi(argv[11]) != 0);
-    const lsm2d_grid_geometry geo{from_bits(argv[12]), from_bits(argv[13]), from_bits(argv[14]), atoi(argv[15]), atoi(argv[16])};
+    const OccupancyScanParams params(n_beams, from_bits_arg(argv[6]), from_bits_arg(argv[7]), from_bits_arg(argv[8]), from_bits_arg(argv[9]), from_bits_arg(argv[10]), atoi(argv[11]) != 0);
+    const lsm2d_grid_geometry geo{from_bits_arg(argv[12]), from_bits_arg(argv[13]), from_bits_arg(argv[14]), atoi(argv[15]), atoi(argv[16])};
     const int32_t n_scans = (int32_t) (ranges.size() / (size_t) n_beams);
     GridSet grids(ctx, geo, n_grids);
     occupancyUpdateScans(ctx, grids, params, ranges.data(), n_scans, poses, grid);
@@ -47,7 +32,7 @@ int main(int argc, char** argv) {
     }
     fclose(out);
     printf("{");
-    print_list("hit_rays", u.hit_rays, ", "); print_list("clear_rays", u.clear_rays, ", "); print_list("dropped", u.dropped, "}\n");
+    print_int_list("hit_rays", u.hit_rays, ", "); print_int_list("clear_rays", u.clear_rays, ", "); print_int_list("dropped", u.dropped, "}\n");
   } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
   return 0;
 }

@@ -6,31 +6,9 @@
 // the same thresholds judge both stages; the two float thresholds come as their bit patterns.  Prints one JSON line: medians, minima and maxima of the wall
 // clock around each route in ms, lsm2d_last_kernel_ms of one more call of each (the two-call route: the sum of its two calls'), the counts, and whether every
 // output of the two routes is equal byte for byte (the caller's parity gate: tests/bench/relocalize_bench.py).
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-static void must(int rc, const char* what, lsm2d_context* ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); }
-}
-static void summary(std::vector<double> t, double out[3]) {
-  std::sort(t.begin(), t.end());
-  out[0] = t.size() % 2 ? t[t.size() / 2] : 0.5 * (t[t.size() / 2 - 1] + t[t.size() / 2]); out[1] = t.front(); out[2] = t.back();
-}
+#include "driver_common.h"
 
 // everything the call returns
 struct Answer {
@@ -53,7 +31,7 @@ int main(int argc, char** argv) {
   const std::vector<float> map = read_all<float>(argv[3]);
   const std::vector<float> poses = read_all<float>(argv[4]);
   const int cols = atoi(argv[5]); const float tau = (float) atof(argv[6]); const int iterations = atoi(argv[7]);
-  const lsm2d_select_params select{atoi(argv[8]), from_bits((uint32_t) strtoul(argv[9], nullptr, 10)), from_bits((uint32_t) strtoul(argv[10], nullptr, 10))};
+  const lsm2d_select_params select{atoi(argv[8]), from_bits_arg(argv[9]), from_bits_arg(argv[10])};
   const int32_t k_score = atoi(argv[11]), k = atoi(argv[12]); const int steps = atoi(argv[13]), warmup = atoi(argv[14]);
   const int32_t n = (int32_t) (poses.size() / 3), n_scans = (int32_t) offs.size() - 1;
   if (n_scans != 1 && n_scans != n) { fprintf(stderr, "offsets.bin: one scan, or one per hypothesis\n"); return 2; }

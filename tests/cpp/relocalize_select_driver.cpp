@@ -4,22 +4,11 @@
 // and aligns every selected hypothesis (lsm2d_align_batch); its verdict is restated here -- accepted rows ranked by inliers descending, chi_inliers ascending
 // on its bits, position in the selection ascending, cut at k -- and compared with relocalizeSelect's answer byte for byte.  Prints JSON (floats as bits).
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_relocalize.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
+using namespace lsm2d_host;
 
 int main(int argc, char** argv) {
   if (argc < 14) { fprintf(stderr, "usage: %s scan.bin map.bin poses.bin cols tau iterations min_num_inliers sum_order min_inliers max_chi_bits min_ratio_bits k_score k\n", argv[0]); return 2; }
@@ -39,7 +28,7 @@ int main(int argc, char** argv) {
     const std::vector<lsm2d_slice_params> slices = {sp};
     const std::vector<const CloudSet*> fixed = {&scan}, moving = {&map};
     const lsm2d_aligner_params ap{atoi(argv[6]), atoi(argv[7]), 0.f, 0.f, 0, 0};
-    const lsm2d_select_params select{atoi(argv[9]), from_bits((uint32_t) strtoul(argv[10], nullptr, 10)), from_bits((uint32_t) strtoul(argv[11], nullptr, 10))};
+    const lsm2d_select_params select{atoi(argv[9]), from_bits_arg(argv[10]), from_bits_arg(argv[11])};
     const int32_t k_score = atoi(argv[12]), k = atoi(argv[13]);
 
     const AlignerRelocalization rel = relocalize(ctx, ap, slices, fixed, moving, poses, select, k_score);
@@ -54,7 +43,7 @@ int main(int argc, char** argv) {
     for (size_t j = 0; j < rel.pose.size(); ++j) {
       n_success += rel.status[j] == LSM2D_SUCCESS;
       if (!rel.accepted[j] || rel.iterations[j] < 1) continue;
-      keyed.emplace_back(((uint64_t) (uint32_t) (0x7fffffff - rel.last_stats[j].n_inliers) << 32) | bits(rel.last_stats[j].chi_inliers), j);
+      keyed.emplace_back(key_of(rel.last_stats[j]), j);
     }
     std::sort(keyed.begin(), keyed.end());
     const size_t r = std::min(keyed.size(), (size_t) k);
@@ -68,19 +57,17 @@ int main(int argc, char** argv) {
     }
     const RelocalizeSelection none = relocalizeSelect(ctx, ap, slices, fixed, moving, std::vector<Vector3f>(), select, k_score, nullptr, k);
 
-    printf("{\"n\": %zu, \"scored_equal\": %d, \"aligned_equal\": %d, \"n_empty\": %zu, \"n_scored_accepted\": %d, \"n_accepted\": %d, \"n_success\": %d, \"scored_index\": [",
+    printf("{\"n\": %zu, \"scored_equal\": %d, \"aligned_equal\": %d, \"n_empty\": %zu, \"n_scored_accepted\": %d, \"n_accepted\": %d, \"n_success\": %d, ",
            n, scored_equal, aligned_equal, none.scored.index.size() + none.aligned.index.size() + (size_t) none.scored.n_accepted + (size_t) none.aligned.n_accepted,
            rs.scored.n_accepted, a.n_accepted, a.n_success);
-    for (size_t j = 0; j < rs.scored.index.size(); ++j) printf("%s%d", j ? "," : "", rs.scored.index[j]);
-    printf("], \"index\": [");
-    for (size_t q = 0; q < a.index.size(); ++q) printf("%s%d", q ? "," : "", a.index[q]);
-    printf("], \"rows\": [");
+    print_int_list("scored_index", rs.scored.index, ", "); print_int_list("index", a.index, ", ");
+    printf("\"rows\": [");
     for (size_t q = 0; q < a.index.size(); ++q) {
-      const lsm2d_iteration_stats& s = a.last_stats[q];
-      printf("%s{\"pose\": [%u,%u,%u], \"H\": [", q ? "," : "", bits(a.pose[q][0]), bits(a.pose[q][1]), bits(a.pose[q][2]));
-      for (int c = 0; c < 9; ++c) printf("%s%u", c ? "," : "", bits(a.information[q][(size_t) c]));
-      printf("], \"iterations\": %d, \"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u]}", a.iterations[q], s.n_correspondences, s.n_inliers, s.n_outliers,
-             bits(s.chi_inliers), bits(s.chi_outliers), s.pair_digest_lo, s.pair_digest_hi);
+      printf("%s{", q ? "," : "");
+      print_bits_list("pose", a.pose[q].data(), 3, ", "); print_bits_list("H", a.information[q].data(), 9, ", ");
+      printf("\"iterations\": %d, ", a.iterations[q]);
+      print_stats(a.last_stats[q]);
+      printf("}");
     }
     printf("]}\n");
   } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }

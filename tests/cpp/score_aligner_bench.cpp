@@ -8,30 +8,11 @@
 // lsm2d_last_kernel_ms of one more call of each, whether the routes agree (rows byte for byte but for the digest, which the old route cannot salt; selections).
 #include <lsm2d.h>
 
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-static void must(int rc, const char* what, lsm2d_context* ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); }
-}
-static void summary(std::vector<double> t, double out[3]) {
-  std::sort(t.begin(), t.end());
-  out[0] = t.size() % 2 ? t[t.size() / 2] : 0.5 * (t[t.size() / 2 - 1] + t[t.size() / 2]); out[1] = t.front(); out[2] = t.back();
-}
+#include "driver_common.h"
+
 static float wrap(float a) {
   while (a > 3.14159274101257324f) a -= 6.28318548202514648f;
   while (a <= -3.14159274101257324f) a += 6.28318548202514648f;
@@ -44,7 +25,7 @@ int main(int argc, char** argv) {
   const std::vector<int32_t> off0 = read_all<int32_t>(argv[2]), off1 = read_all<int32_t>(argv[4]);
   const std::vector<float> sinv = read_all<float>(argv[7]);      // [2][8]
   const int cols = atoi(argv[8]); const float tau = (float) atof(argv[9]); const int order = atoi(argv[10]); const int min_corr = atoi(argv[11]);
-  const lsm2d_select_params select{atoi(argv[12]), from_bits((uint32_t) strtoul(argv[13], nullptr, 10)), from_bits((uint32_t) strtoul(argv[14], nullptr, 10))};
+  const lsm2d_select_params select{atoi(argv[12]), from_bits_arg(argv[13]), from_bits_arg(argv[14])};
   const int32_t k = atoi(argv[15]); const int steps = atoi(argv[16]), warmup = atoi(argv[17]);
   const int32_t n = (int32_t) (poses.size() / 3);
 
@@ -108,12 +89,7 @@ int main(int argc, char** argv) {
     keyed.clear();
     for (int32_t i = 0; i < n; ++i) {
       const lsm2d_iteration_stats& s = st_old[(size_t) i];
-      const float n_in = (float) s.n_inliers, n_c = (float) (s.n_correspondences > 1 ? s.n_correspondences : 1);
-      if (act_old[(size_t) i] > 0 && s.n_inliers >= select.min_inliers && s.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= select.max_chi_per_inlier &&
-          n_in / n_c >= select.min_inlier_ratio) {
-        uint32_t chi; memcpy(&chi, &s.chi_inliers, sizeof chi);
-        keyed.emplace_back(((uint64_t) (uint32_t) (0x7fffffff - s.n_inliers) << 32) | chi, i);
-      }
+      if (act_old[(size_t) i] > 0 && accept(s, select)) keyed.emplace_back(key_of(s), i);
     }
     n_acc_old = (int32_t) keyed.size();
     const size_t m = std::min(K, keyed.size());

@@ -5,38 +5,16 @@
 // projective 721 columns, Cauchy 0.01, sensor (-0.2, 0, 3.0); min_num_correspondences 10.  Scores every hypothesis through the ABI and through scoreAligner
 // (checked equal byte for byte here), selects the best k (scoreAlignerSelect; rows checked against scoreAligner's), runs the two-slice relocalize with an
 // aligner of 8 iterations and checks it against the entry points called by hand; prints everything as JSON (floats as their bit patterns).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d.hpp>
+
+#include "driver_common.h"
 
 using namespace lsm2d_host;
 
-template <class T> static std::vector<T> read_all(const std::string& path) {
-  FILE* f = fopen(path.c_str(), "rb"); if (!f) { perror(path.c_str()); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-
-static bool same(const AlignerScore& a, const AlignerScore& b) {
-  return !memcmp(a.row.H.data(), b.row.H.data(), sizeof(float) * 9) && !memcmp(a.row.b.data(), b.row.b.data(), sizeof(float) * 3) &&
-         !memcmp(&a.row.stats, &b.row.stats, sizeof(lsm2d_iteration_stats)) && a.active == b.active;
-}
-
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-
-static void print_stats(const lsm2d_iteration_stats& s) {
-  printf("\"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u]", s.n_correspondences, s.n_inliers, s.n_outliers, bits(s.chi_inliers),
-         bits(s.chi_outliers), s.pair_digest_lo, s.pair_digest_hi);
-}
-
 static void print_score(const AlignerScore& r) {
-  printf("{\"H\": [");
-  for (int c = 0; c < 9; ++c) printf("%s%u", c ? "," : "", bits(r.row.H[(size_t) c]));
-  printf("], \"b\": [%u,%u,%u], \"active\": %d, ", bits(r.row.b[0]), bits(r.row.b[1]), bits(r.row.b[2]), r.active);
+  printf("{");
+  print_bits_list("H", r.row.H.data(), 9, ", "); print_bits_list("b", r.row.b.data(), 3, ", ");
+  printf("\"active\": %d, ", r.active);
   print_stats(r.row.stats);
   printf("}");
 }
@@ -53,7 +31,7 @@ int main(int argc, char** argv) {
     const std::string dir = std::string(argv[1]) + "/";
     Context ctx(0);
     ctx.setOption("sum_order", atoi(argv[2]));
-    const lsm2d_select_params select{atoi(argv[3]), from_bits((uint32_t) strtoul(argv[4], nullptr, 10)), from_bits((uint32_t) strtoul(argv[5], nullptr, 10))};
+    const lsm2d_select_params select{atoi(argv[3]), from_bits_arg(argv[4]), from_bits_arg(argv[5])};
     const int32_t k = atoi(argv[6]); const bool with_prior = atoi(argv[7]) != 0;
     const std::vector<float> pf = read_all<float>(dir + "poses.bin"), prf = read_all<float>(dir + "priors.bin");
     const size_t n = pf.size() / 3;
@@ -91,7 +69,8 @@ int main(int argc, char** argv) {
     const AlignerSelection sel = scoreAlignerSelect(ctx, slices, fixed, moving, poses, select, k, priors);
     int rows_equal_score_aligner = sel.index.size() == sel.rows.size();
     for (size_t j = 0; j < sel.index.size() && rows_equal_score_aligner; ++j)
-      if (sel.index[j] < 0 || (size_t) sel.index[j] >= n || !same(sel.rows[j], all[(size_t) sel.index[j]])) rows_equal_score_aligner = 0;
+      if (sel.index[j] < 0 || (size_t) sel.index[j] >= n || !same_bytes(sel.rows[j].row, all[(size_t) sel.index[j]].row) ||
+          sel.rows[j].active != all[(size_t) sel.index[j]].active) rows_equal_score_aligner = 0;
     const AlignerSelection none = scoreAlignerSelect(ctx, slices, fixed, moving, std::vector<Vector3f>(), select, k);
 
     // relocalize, and the entry points called by hand
@@ -110,17 +89,18 @@ int main(int argc, char** argv) {
                                   status == rel.status && its == rel.iterations;
     }
 
-    printf("{\"n\": %zu, \"mirror_equals_abi\": %d, \"rows_equal_score_aligner\": %d, \"relocalize_equals_by_hand\": %d, \"n_empty\": %zu, \"n_accepted\": %d, \"index\": [",
+    printf("{\"n\": %zu, \"mirror_equals_abi\": %d, \"rows_equal_score_aligner\": %d, \"relocalize_equals_by_hand\": %d, \"n_empty\": %zu, \"n_accepted\": %d, ",
            n, mirror_equals_abi, rows_equal_score_aligner, relocalize_equals_by_hand, none.index.size() + (size_t) none.n_accepted, sel.n_accepted);
-    for (size_t j = 0; j < sel.index.size(); ++j) printf("%s%d", j ? "," : "", sel.index[j]);
-    printf("], \"all\": [");
+    print_int_list("index", sel.index, ", ");
+    printf("\"all\": [");
     for (size_t i = 0; i < n; ++i) { if (i) printf(","); print_score(all[i]); }
     printf("], \"rows\": [");
     for (size_t j = 0; j < sel.rows.size(); ++j) { if (j) printf(","); print_score(sel.rows[j]); }
     printf("], \"relocalize\": {\"n_accepted\": %d, \"items\": [", rel.selection.n_accepted);
     for (size_t j = 0; j < rel.pose.size(); ++j) {
-      printf("%s{\"pose\": [%u,%u,%u], \"status\": %d, \"iterations\": %d, \"accepted\": %d, ", j ? "," : "", bits(rel.pose[j][0]), bits(rel.pose[j][1]),
-             bits(rel.pose[j][2]), rel.status[j], rel.iterations[j], (int) rel.accepted[j]);
+      printf("%s{", j ? "," : "");
+      print_bits_list("pose", rel.pose[j].data(), 3, ", ");
+      printf("\"status\": %d, \"iterations\": %d, \"accepted\": %d, ", rel.status[j], rel.iterations[j], (int) rel.accepted[j]);
       print_stats(rel.last_stats[j]);
       printf("}");
     }

@@ -8,32 +8,11 @@
 //   route c  the exhaustive 64 x 64 x 16 grid through lsm2d_score_aligner_select, its poses made once outside the timing (for context)
 // nobody = 1: the coarse thresholds pass nobody -- what the pads cost when route b stops after level 0.  Prints one JSON line: medians, minima and maxima of
 // the wall clock in ms, lsm2d_last_kernel_ms of one more call of route a, whether routes a and b agree byte for byte, and how far a's best pose lies from c's.
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static void must(int rc, const char* what, lsm2d_context* ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); }
-}
-static void summary(std::vector<double> t, double out[3]) {
-  std::sort(t.begin(), t.end());
-  out[0] = t.size() % 2 ? t[t.size() / 2] : 0.5 * (t[t.size() / 2 - 1] + t[t.size() / 2]); out[1] = t.front(); out[2] = t.back();
-}
+#include "driver_common.h"
+
 // base + (o * s): two roundings (volatile keeps the compiler from contracting them)
 static float coord(float base, int i, int n, float s) { volatile float o = (float) i - 0.5f * (float) (n - 1); volatile float p = o * s; volatile float r = base + p; return r; }
 
@@ -54,8 +33,8 @@ int main(int argc, char** argv) {
   const std::vector<float> scan = read_all<float>(argv[1]), map = read_all<float>(argv[2]);
   const int cols = atoi(argv[3]); const float tau = (float) atof(argv[4]);
   float center[3], step[3];
-  for (int a = 0; a < 3; ++a) { center[a] = from_bits(argv[5 + a]); step[a] = from_bits(argv[8 + a]); }
-  const lsm2d_select_params select{atoi(argv[11]), from_bits(argv[12]), from_bits(argv[13])};
+  for (int a = 0; a < 3; ++a) { center[a] = from_bits_arg(argv[5 + a]); step[a] = from_bits_arg(argv[8 + a]); }
+  const lsm2d_select_params select{atoi(argv[11]), from_bits_arg(argv[12]), from_bits_arg(argv[13])};
   const bool nobody = atoi(argv[14]) != 0; const int steps = atoi(argv[15]), warmup = atoi(argv[16]);
   const lsm2d_select_params none{1000000000, 0.0f, 2.0f};
   const lsm2d_select_params coarse = nobody ? none : select;

@@ -3,22 +3,11 @@
 //                     coarse: min_inliers max_chi_bits min_ratio_bits  last: min_inliers max_chi_bits min_ratio_bits  k  iterations k_align
 // One projective slice with a Cauchy robustifier, min_num_correspondences 10.  Prints what the two calls return as JSON (floats as bits): the Python test
 // compares it with api.score_grid_select / api.relocalize_grid on the same inputs.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_score_grid.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
+using namespace lsm2d_host;
 
 int main(int argc, char** argv) {
   if (argc < 29) { fprintf(stderr, "usage: %s scan.bin map.bin cols tau sum_order <6 float bits> <8 grid integers> <3 coarse> <3 last> k iterations k_align\n", argv[0]); return 2; }
@@ -34,9 +23,9 @@ int main(int argc, char** argv) {
     const std::vector<lsm2d_slice_params> slices = {sp};
     const std::vector<const CloudSet*> fixed = {&scan}, moving = {&map};
     lsm2d_pose_grid g;
-    for (int a = 0; a < 3; ++a) { g.center[a] = from_bits(argv[6 + a]); g.step[a] = from_bits(argv[9 + a]); g.count[a] = atoi(argv[12 + a]); g.refine[a] = atoi(argv[16 + a]); }
+    for (int a = 0; a < 3; ++a) { g.center[a] = from_bits_arg(argv[6 + a]); g.step[a] = from_bits_arg(argv[9 + a]); g.count[a] = atoi(argv[12 + a]); g.refine[a] = atoi(argv[16 + a]); }
     g.n_levels = atoi(argv[15]); g.k_parents = atoi(argv[19]);
-    const lsm2d_select_params coarse{atoi(argv[20]), from_bits(argv[21]), from_bits(argv[22])}, last{atoi(argv[23]), from_bits(argv[24]), from_bits(argv[25])};
+    const lsm2d_select_params coarse{atoi(argv[20]), from_bits_arg(argv[21]), from_bits_arg(argv[22])}, last{atoi(argv[23]), from_bits_arg(argv[24]), from_bits_arg(argv[25])};
     const int32_t k = atoi(argv[26]), k_align = atoi(argv[28]);
     const lsm2d_aligner_params ap{atoi(argv[27]), 0, 0.f, 0.f, 0, 0};
 
@@ -48,20 +37,21 @@ int main(int argc, char** argv) {
       again = !memcmp(r.scored.pose[j].data(), s.pose[j].data(), 12) && !memcmp(&r.scored.rows[j].row.stats, &s.rows[j].row.stats, sizeof(lsm2d_iteration_stats));
     printf("{\"n_accepted\": %d, \"scored_again_equal\": %d, \"level_counts\": [", s.n_accepted, again);
     for (size_t l = 0; l < s.level_counts.size(); ++l) printf("%s[%d,%d]", l ? "," : "", s.level_counts[l][0], s.level_counts[l][1]);
-    printf("], \"origin\": [");
-    for (size_t j = 0; j < s.origin.size(); ++j) printf("%s%d", j ? "," : "", s.origin[j]);
-    printf("], \"rows\": [");
+    printf("], ");
+    print_int_list("origin", s.origin, ", ");
+    printf("\"rows\": [");
     for (size_t j = 0; j < s.pose.size(); ++j) {
-      const AlignerScore& w = s.rows[j]; const lsm2d_iteration_stats& t = w.row.stats;
-      printf("%s{\"pose\": [%u,%u,%u], \"H\": [", j ? "," : "", bits(s.pose[j][0]), bits(s.pose[j][1]), bits(s.pose[j][2]));
-      for (int c = 0; c < 9; ++c) printf("%s%u", c ? "," : "", bits(w.row.H[(size_t) c]));
-      printf("], \"b\": [%u,%u,%u], \"active\": %d, \"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u]}", bits(w.row.b[0]), bits(w.row.b[1]), bits(w.row.b[2]),
-             w.active, t.n_correspondences, t.n_inliers, t.n_outliers, bits(t.chi_inliers), bits(t.chi_outliers), t.pair_digest_lo, t.pair_digest_hi);
+      const AlignerScore& w = s.rows[j];
+      printf("%s{", j ? "," : "");
+      print_bits_list("pose", s.pose[j].data(), 3, ", "); print_bits_list("H", w.row.H.data(), 9, ", "); print_bits_list("b", w.row.b.data(), 3, ", ");
+      printf("\"active\": %d, ", w.active);
+      print_stats(w.row.stats);
+      printf("}");
     }
     const AlignSelection& a = r.aligned;
-    printf("], \"aligned\": {\"n_accepted\": %d, \"n_success\": %d, \"index\": [", a.n_accepted, a.n_success);
-    for (size_t q = 0; q < a.index.size(); ++q) printf("%s%d", q ? "," : "", a.index[q]);
-    printf("], \"pose\": [");
+    printf("], \"aligned\": {\"n_accepted\": %d, \"n_success\": %d, ", a.n_accepted, a.n_success);
+    print_int_list("index", a.index, ", ");
+    printf("\"pose\": [");
     for (size_t q = 0; q < a.pose.size(); ++q) printf("%s[%u,%u,%u]", q ? "," : "", bits(a.pose[q][0]), bits(a.pose[q][1]), bits(a.pose[q][2]));
     printf("]}}\n");
   } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }

@@ -5,31 +5,9 @@
 // robustifier of threshold tau; the two float thresholds come as their bit patterns.  Prints one JSON line -- medians, minima and maxima of the wall clock
 // around each route in ms, lsm2d_last_kernel_ms of one more call of each, both routes' selections -- and writes the baseline's statistics of all n items to
 // stats_out.bin for the caller's parity gate (tests/bench/score_select_bench.py).
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-static void must(int rc, const char* what, lsm2d_context* ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); }
-}
-static void summary(std::vector<double> t, double out[3]) {
-  std::sort(t.begin(), t.end());
-  out[0] = t.size() % 2 ? t[t.size() / 2] : 0.5 * (t[t.size() / 2 - 1] + t[t.size() / 2]); out[1] = t.front(); out[2] = t.back();
-}
+#include "driver_common.h"
 
 int main(int argc, char** argv) {
   if (argc < 15) { fprintf(stderr, "usage: %s scans.bin offsets.bin map.bin poses.bin cols tau sum_order min_inliers max_chi_bits min_ratio_bits k steps warmup stats_out.bin\n", argv[0]); return 2; }
@@ -38,7 +16,7 @@ int main(int argc, char** argv) {
   const std::vector<float> map = read_all<float>(argv[3]);
   const std::vector<float> poses = read_all<float>(argv[4]);
   const int cols = atoi(argv[5]); const float tau = (float) atof(argv[6]); const int order = atoi(argv[7]);
-  const lsm2d_select_params select{atoi(argv[8]), from_bits((uint32_t) strtoul(argv[9], nullptr, 10)), from_bits((uint32_t) strtoul(argv[10], nullptr, 10))};
+  const lsm2d_select_params select{atoi(argv[8]), from_bits_arg(argv[9]), from_bits_arg(argv[10])};
   const int32_t k = atoi(argv[11]); const int steps = atoi(argv[12]), warmup = atoi(argv[13]);
   const int32_t n = (int32_t) (poses.size() / 3), n_scans = (int32_t) offs.size() - 1;
 
@@ -68,11 +46,7 @@ int main(int argc, char** argv) {
     keyed.clear();
     for (int32_t i = 0; i < n; ++i) {
       const lsm2d_iteration_stats& s = st[(size_t) i];
-      const float n_in = (float) s.n_inliers, n_c = (float) (s.n_correspondences > 1 ? s.n_correspondences : 1);
-      if (s.n_inliers >= select.min_inliers && s.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= select.max_chi_per_inlier && n_in / n_c >= select.min_inlier_ratio) {
-        uint32_t chi; memcpy(&chi, &s.chi_inliers, sizeof chi);
-        keyed.emplace_back(((uint64_t) (uint32_t) (0x7fffffff - s.n_inliers) << 32) | chi, i);
-      }
+      if (accept(s, select)) keyed.emplace_back(key_of(s), i);
     }
     n_acc_base = (int32_t) keyed.size();
     const size_t m = std::min((size_t) k, keyed.size());
@@ -102,17 +76,13 @@ int main(int argc, char** argv) {
         memcmp(&st_new[(size_t) j], &st[i], sizeof(lsm2d_iteration_stats)))
       rows_equal = 0;
   }
-  FILE* f = fopen(argv[14], "wb");
-  if (!f || fwrite(st.data(), sizeof(lsm2d_iteration_stats), (size_t) n, f) != (size_t) n) { perror(argv[14]); return 2; }
-  fclose(f);
+  write_all(argv[14], st.data(), (size_t) n);
   double sn[3], sb[3]; summary(t_new, sn); summary(t_base, sb);
   printf("{\"n_items\": %d, \"k\": %d, \"steps\": %d, \"select_ms\": [%.4f, %.4f, %.4f], \"baseline_ms\": [%.4f, %.4f, %.4f], \"select_kernel_ms\": %.4f, "
-         "\"baseline_kernel_ms\": %.4f, \"rows_equal\": %d, \"n_accepted\": [%d, %d], \"index_select\": [", n, k, steps, sn[0], sn[1], sn[2], sb[0], sb[1], sb[2],
+         "\"baseline_kernel_ms\": %.4f, \"rows_equal\": %d, \"n_accepted\": [%d, %d], ", n, k, steps, sn[0], sn[1], sn[2], sb[0], sb[1], sb[2],
          k_new, k_base, rows_equal, n_acc_new, n_acc_base);
-  for (int32_t j = 0; j < n_sel_new; ++j) printf("%s%d", j ? "," : "", idx_new[(size_t) j]);
-  printf("], \"index_baseline\": [");
-  for (size_t j = 0; j < idx_base.size(); ++j) printf("%s%d", j ? "," : "", idx_base[j]);
-  printf("]}\n");
+  idx_new.resize((size_t) n_sel_new);
+  print_int_list("index_select", idx_new, ", "); print_int_list("index_baseline", idx_base, "}\n");
   lsm2d_cloudset_destroy(fixed); lsm2d_cloudset_destroy(moving); lsm2d_destroy(ctx);
   return 0;
 }

@@ -3,33 +3,11 @@
 // reads one float32 [N,4] scan (fixed), one map (moving) and n float32 poses, selects the best k hypotheses that pass the acceptance test (projective finder,
 // a Cauchy robustifier of threshold tau; the two float thresholds come as their bit patterns), checks every selected row byte for byte against scoreBatch
 // on the same poses, runs relocalize with an aligner of 8 iterations and prints everything as JSON (floats as their bit patterns).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d.hpp>
 
+#include "driver_common.h"
+
 using namespace lsm2d_host;
-
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-
-static bool same(const Linearization& a, const Linearization& b) {
-  return !memcmp(a.H.data(), b.H.data(), sizeof(float) * 9) && !memcmp(a.b.data(), b.b.data(), sizeof(float) * 3) &&
-         !memcmp(&a.stats, &b.stats, sizeof(lsm2d_iteration_stats));
-}
-
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-
-static void print_stats(const lsm2d_iteration_stats& s) {
-  printf("\"counts\": [%d,%d,%d], \"chi\": [%u,%u], \"digest\": [%u,%u]", s.n_correspondences, s.n_inliers, s.n_outliers, bits(s.chi_inliers),
-         bits(s.chi_outliers), s.pair_digest_lo, s.pair_digest_hi);
-}
 
 int main(int argc, char** argv) {
   if (argc < 11) { fprintf(stderr, "usage: %s scan.bin map.bin poses.bin cols tau sum_order min_inliers max_chi_bits min_ratio_bits k\n", argv[0]); return 2; }
@@ -40,7 +18,7 @@ int main(int argc, char** argv) {
     const std::vector<float> pf = read_all<float>(argv[3]);
     const int cols = atoi(argv[4]); const float tau = (float) atof(argv[5]);
     ctx.setOption("sum_order", atoi(argv[6]));
-    const lsm2d_select_params select{atoi(argv[7]), from_bits((uint32_t) strtoul(argv[8], nullptr, 10)), from_bits((uint32_t) strtoul(argv[9], nullptr, 10))};
+    const lsm2d_select_params select{atoi(argv[7]), from_bits_arg(argv[8]), from_bits_arg(argv[9])};
     const int32_t k = atoi(argv[10]);
     const size_t n = pf.size() / 3;
     std::vector<Vector3f> poses(n);
@@ -57,30 +35,30 @@ int main(int argc, char** argv) {
     const std::vector<Linearization> all = scoreBatch(ctx, sp, scan_set, map_set, poses);
     int rows_equal_score_batch = sel.index.size() == sel.rows.size();
     for (size_t j = 0; j < sel.index.size() && rows_equal_score_batch; ++j)
-      if (sel.index[j] < 0 || (size_t) sel.index[j] >= n || !same(sel.rows[j], all[(size_t) sel.index[j]])) rows_equal_score_batch = 0;
+      if (sel.index[j] < 0 || (size_t) sel.index[j] >= n || !same_bytes(sel.rows[j], all[(size_t) sel.index[j]])) rows_equal_score_batch = 0;
     const Selection none = scoreSelect(ctx, sp, scan_set, map_set, std::vector<Vector3f>(), select, k);
 
     const lsm2d_aligner_params ap{8, 10, 0.f, 0.f, 0, 0};
     const Relocalization rel = relocalize(ctx, ap, sp, scan_set, map_set, poses, select, k);
 
-    printf("{\"n\": %zu, \"n_accepted\": %d, \"rows_equal_score_batch\": %d, \"n_empty\": %zu, \"index\": [", n, sel.n_accepted, rows_equal_score_batch,
+    printf("{\"n\": %zu, \"n_accepted\": %d, \"rows_equal_score_batch\": %d, \"n_empty\": %zu, ", n, sel.n_accepted, rows_equal_score_batch,
            none.index.size() + (size_t) none.n_accepted);
-    for (size_t j = 0; j < sel.index.size(); ++j) printf("%s%d", j ? "," : "", sel.index[j]);
-    printf("], \"rows\": [");
+    print_int_list("index", sel.index, ", ");
+    printf("\"rows\": [");
     for (size_t j = 0; j < sel.rows.size(); ++j) {
       const Linearization& r = sel.rows[j];
-      printf("%s{\"H\": [", j ? "," : "");
-      for (int c = 0; c < 9; ++c) printf("%s%u", c ? "," : "", bits(r.H[(size_t) c]));
-      printf("], \"b\": [%u,%u,%u], ", bits(r.b[0]), bits(r.b[1]), bits(r.b[2]));
+      printf("%s{", j ? "," : "");
+      print_bits_list("H", r.H.data(), 9, ", "); print_bits_list("b", r.b.data(), 3, ", ");
       print_stats(r.stats);
       printf("}");
     }
-    printf("], \"relocalize\": {\"n_accepted\": %d, \"index\": [", rel.selection.n_accepted);
-    for (size_t j = 0; j < rel.selection.index.size(); ++j) printf("%s%d", j ? "," : "", rel.selection.index[j]);
-    printf("], \"items\": [");
+    printf("], \"relocalize\": {\"n_accepted\": %d, ", rel.selection.n_accepted);
+    print_int_list("index", rel.selection.index, ", ");
+    printf("\"items\": [");
     for (size_t j = 0; j < rel.pose.size(); ++j) {
-      printf("%s{\"pose\": [%u,%u,%u], \"status\": %d, \"iterations\": %d, \"accepted\": %d, ", j ? "," : "", bits(rel.pose[j][0]), bits(rel.pose[j][1]),
-             bits(rel.pose[j][2]), rel.status[j], rel.iterations[j], (int) rel.accepted[j]);
+      printf("%s{", j ? "," : "");
+      print_bits_list("pose", rel.pose[j].data(), 3, ", ");
+      printf("\"status\": %d, \"iterations\": %d, \"accepted\": %d, ", rel.status[j], rel.iterations[j], (int) rel.accepted[j]);
       print_stats(rel.last_stats[j]);
       printf("}");
     }

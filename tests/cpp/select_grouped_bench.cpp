@@ -10,46 +10,15 @@
 // rows of those items, byte for byte.  Prints one JSON line -- median, minimum and maximum of the wall clock around each route in ms, lsm2d_last_kernel_ms of
 // one more grouped call -- and writes route (c)'s verdict inputs of all n items to out.bin (align: status [n], iterations [n], last rows [n]; score: rows
 // [n]) followed by route (a)'s counts and indices ([G] accepted, [G] selected, [G x k] index) for the caller's own gate (tests/bench/select_grouped_bench.py).
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
-static void must(int rc, const char* what, lsm2d_context* ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); }
-}
-static void summary(std::vector<double> t, double out[3]) {
-  std::sort(t.begin(), t.end());
-  out[0] = t.size() % 2 ? t[t.size() / 2] : 0.5 * (t[t.size() / 2 - 1] + t[t.size() / 2]); out[1] = t.front(); out[2] = t.back();
-}
-static bool accept(const lsm2d_iteration_stats& s, const lsm2d_select_params& p) {
-  const float n_in = (float) s.n_inliers, n_c = (float) (s.n_correspondences > 1 ? s.n_correspondences : 1);
-  return s.n_inliers >= p.min_inliers && s.chi_inliers / (n_in > 1.f ? n_in : 1.f) <= p.max_chi_per_inlier && n_in / n_c >= p.min_inlier_ratio;
-}
-static uint64_t key_of(const lsm2d_iteration_stats& s) {
-  uint32_t chi; memcpy(&chi, &s.chi_inliers, sizeof chi);
-  return ((uint64_t) (uint32_t) (0x7fffffff - s.n_inliers) << 32) | chi;
-}
+#include "driver_common.h"
 
 // one route's verdict: per group the accepted and selected counts, the selected items in slots g * k + j
 struct Verdict {
   std::vector<int32_t> n_acc, n_sel, index;
   Verdict(size_t G, size_t k) : n_acc(G, 0), n_sel(G, 0), index(G * k, -1) {}
-  bool same(const Verdict& o, size_t k) const {
+  bool agrees(const Verdict& o, size_t k) const {
     if (n_acc != o.n_acc || n_sel != o.n_sel) return false;
     for (size_t g = 0; g < n_sel.size(); ++g)
       for (int32_t j = 0; j < n_sel[g]; ++j) if (index[g * k + (size_t) j] != o.index[g * k + (size_t) j]) return false;
@@ -67,7 +36,7 @@ int main(int argc, char** argv) {
   const std::vector<int32_t> index = read_all<int32_t>(argv[6]);
   const std::vector<int32_t> groups = read_all<int32_t>(argv[7]);
   const int cols = atoi(argv[8]); const float tau = (float) atof(argv[9]); const int iterations = atoi(argv[10]);
-  const lsm2d_select_params select{atoi(argv[11]), from_bits((uint32_t) strtoul(argv[12], nullptr, 10)), from_bits((uint32_t) strtoul(argv[13], nullptr, 10))};
+  const lsm2d_select_params select{atoi(argv[11]), from_bits_arg(argv[12]), from_bits_arg(argv[13])};
   const int32_t k = atoi(argv[14]); const int steps = atoi(argv[15]), warmup = atoi(argv[16]);
   const int32_t n = (int32_t) (poses.size() / 3), n_scans = (int32_t) offs.size() - 1, G = (int32_t) groups.size() - 1;
   if ((int32_t) index.size() != n || G < 1 || groups[(size_t) G] != n || k < 1) { fprintf(stderr, "index.bin: one entry per item; groups.bin: offsets from 0 to n\n"); return 2; }
@@ -147,7 +116,7 @@ int main(int argc, char** argv) {
   route_c(); route_b(); route_a(); must(lsm2d_last_kernel_ms(ctx, &k_a), "lsm2d_last_kernel_ms", ctx);
 
   // parity: the three verdicts agree, and the grouped call's rows are the batch call's rows of the selected items
-  const int a_is_c = va.same(vc, K), b_is_c = vb.same(vc, K);
+  const int a_is_c = va.agrees(vc, K), b_is_c = vb.agrees(vc, K);
   int rows_equal = 1; long long n_acc_all = 0, n_sel_all = 0;
   for (int32_t g = 0; g < G && rows_equal; ++g) {
     n_acc_all += va.n_acc[(size_t) g]; n_sel_all += va.n_sel[(size_t) g];

@@ -7,21 +7,11 @@
 // entry per group -- n_accepted, n_success (-1 where the call has none), the selected batch indices, and the selected rows' words as unsigned integers
 // (score: H 9, b 3, statistics 7; score_aligner: the same and active; align: pose 3, H 9, iterations, statistics 7).  The two float thresholds come as
 // their bit patterns; the first triple is the align form's, the second the two score forms' (unaligned hypotheses pass other thresholds than aligned ones).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_grouped.hpp>
 
-using namespace lsm2d_host;
+#include "driver_common.h"
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
+using namespace lsm2d_host;
 
 // one group's block as words
 struct Block { int32_t n_accepted = 0, n_success = -1; std::vector<int32_t> index; std::vector<uint32_t> words; };
@@ -30,16 +20,13 @@ static void print_blocks(const char* name, const std::vector<Block>& blocks) {
   printf("\"%s\": [", name);
   for (size_t g = 0; g < blocks.size(); ++g) {
     const Block& b = blocks[g];
-    printf("%s{\"n_accepted\": %d, \"n_success\": %d, \"index\": [", g ? "," : "", b.n_accepted, b.n_success);
-    for (size_t j = 0; j < b.index.size(); ++j) printf("%s%d", j ? "," : "", b.index[j]);
-    printf("], \"words\": [");
+    printf("%s{\"n_accepted\": %d, \"n_success\": %d, ", g ? "," : "", b.n_accepted, b.n_success);
+    print_int_list("index", b.index, ", ");
+    printf("\"words\": [");
     for (size_t j = 0; j < b.words.size(); ++j) printf("%s%u", j ? "," : "", b.words[j]);
     printf("]}");
   }
   printf("]");
-}
-static void must(int rc, const char* what, Context& ctx) {
-  if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx.get())); exit(1); }
 }
 
 int main(int argc, char** argv) {
@@ -51,9 +38,9 @@ int main(int argc, char** argv) {
     const std::vector<int32_t> groups = read_all<int32_t>(argv[4]);
     const int cols = atoi(argv[5]); const float tau = (float) atof(argv[6]);
     const int iterations = atoi(argv[7]), min_num_inliers = atoi(argv[8]);
-    const lsm2d_select_params select{atoi(argv[9]), from_bits((uint32_t) strtoul(argv[10], nullptr, 10)), from_bits((uint32_t) strtoul(argv[11], nullptr, 10))};
+    const lsm2d_select_params select{atoi(argv[9]), from_bits_arg(argv[10]), from_bits_arg(argv[11])};
     const int32_t k = atoi(argv[12]);
-    const lsm2d_select_params select_score{atoi(argv[13]), from_bits((uint32_t) strtoul(argv[14], nullptr, 10)), from_bits((uint32_t) strtoul(argv[15], nullptr, 10))};
+    const lsm2d_select_params select_score{atoi(argv[13]), from_bits_arg(argv[14]), from_bits_arg(argv[15])};
     const size_t n = pf.size() / 3, G = groups.size() - 1, K = (size_t) k, rows = G * K;
     std::vector<Vector3f> poses(n);
     for (size_t i = 0; i < n; ++i) poses[i] = Vector3f{{pf[3 * i], pf[3 * i + 1], pf[3 * i + 2]}};
@@ -74,7 +61,7 @@ int main(int argc, char** argv) {
 
     // ---- the score form
     must(lsm2d_score_select_grouped(ctx.get(), &sp, scan_set.get(), nullptr, map_set.get(), nullptr, (int32_t) n, pf.data(), &select_score, k, (int32_t) G, groups.data(),
-                                    index.data(), H.data(), bb.data(), st.data(), n_sel.data(), n_acc.data()), "lsm2d_score_select_grouped", ctx);
+                                    index.data(), H.data(), bb.data(), st.data(), n_sel.data(), n_acc.data()), "lsm2d_score_select_grouped", ctx.get());
     blocks.assign(G, Block());
     for (size_t g = 0; g < G; ++g) {
       blocks[g].n_accepted = n_acc[g];
@@ -91,7 +78,7 @@ int main(int argc, char** argv) {
 
     // ---- the score-aligner form
     must(lsm2d_score_aligner_select_grouped(ctx.get(), &b, &select_score, k, (int32_t) G, groups.data(), index.data(), H.data(), bb.data(), st.data(), active.data(),
-                                            n_sel.data(), n_acc.data()), "lsm2d_score_aligner_select_grouped", ctx);
+                                            n_sel.data(), n_acc.data()), "lsm2d_score_aligner_select_grouped", ctx.get());
     blocks.assign(G, Block());
     for (size_t g = 0; g < G; ++g) {
       blocks[g].n_accepted = n_acc[g];
@@ -110,7 +97,7 @@ int main(int argc, char** argv) {
 
     // ---- the align form
     must(lsm2d_align_select_grouped(ctx.get(), &ap, &b, &select, k, (int32_t) G, groups.data(), index.data(), pose.data(), H.data(), its.data(), st.data(), n_sel.data(),
-                                    n_acc.data(), n_suc.data()), "lsm2d_align_select_grouped", ctx);
+                                    n_acc.data(), n_suc.data()), "lsm2d_align_select_grouped", ctx.get());
     blocks.assign(G, Block());
     for (size_t g = 0; g < G; ++g) {
       blocks[g].n_accepted = n_acc[g]; blocks[g].n_success = n_suc[g];

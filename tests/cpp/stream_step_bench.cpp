@@ -4,29 +4,17 @@
 // step i, lsm2d_align_batch_wait for step i - 1.  Every distinct batch's streamed result is compared BIT FOR BIT with the synchronous calls on the same ranges.
 //   stream_step_bench map.bin ranges.bin x0.bin n_scans n_beams n_batches steps warmup iterations angle_min angle_max [refill_ahead = 1]
 // map: float32 [N,4]; ranges: float32 [n_batches][n_scans][n_beams]; x0: float32 [n_batches][n_scans][3].  Prints one JSON line.
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 #include <hip/hip_runtime_api.h>
-#include "lsm2d.h"
 #include "lsm2d.hpp"      // the C++ mirror's LaserMessageBatchStream: the same pipeline as a class, checked below against the same bits
 
-template <typename T> static std::vector<T> read_bin(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+#include "driver_common.h"
+
 #define CK(x) do { int rc_ = (x); if (rc_ < 0) { fprintf(stderr, "%s -> %d (%s)\n", #x, rc_, lsm2d_last_error(ctx)); return 1; } } while (0)
 
 int main(int argc, char** argv) {
   if (argc < 12) { fprintf(stderr, "usage: %s map.bin ranges.bin x0.bin n_scans n_beams n_batches steps warmup iterations angle_min angle_max\n", argv[0]); return 2; }
-  const std::vector<float> map = read_bin<float>(argv[1]), ranges = read_bin<float>(argv[2]), x0 = read_bin<float>(argv[3]);
+  const std::vector<float> map = read_all<float>(argv[1]), ranges = read_all<float>(argv[2]), x0 = read_all<float>(argv[3]);
   const int n = atoi(argv[4]), nb = atoi(argv[5]), nbatch = atoi(argv[6]), steps = atoi(argv[7]), warmup = atoi(argv[8]), its = atoi(argv[9]);
   const float a0 = (float) atof(argv[10]), a1 = (float) atof(argv[11]);
   if (n < 1 || nbatch < 2 || ranges.size() != (size_t) nbatch * n * nb || x0.size() != (size_t) nbatch * n * 3) { fprintf(stderr, "inconsistent inputs\n"); return 2; }

@@ -4,31 +4,19 @@
 //   sweep_driver dir n_devices dev0 [dev1 ...]      files in dir: scans.bin offsets.bin map.bin index.bin x0.bin params.txt
 #include <lsm2d.hpp>
 
-#include <cstdio>
-#include <cstdlib>
 #include <fstream>
-#include <string>
+
+#include "driver_common.h"
 
 using namespace lsm2d_host;
-
-template <typename T>
-static std::vector<T> readAll(const std::string& path) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) { fprintf(stderr, "cannot read %s\n", path.c_str()); exit(2); }
-  f.seekg(0, std::ios::end); const size_t bytes = (size_t) f.tellg(); f.seekg(0);
-  std::vector<T> v(bytes / sizeof(T)); f.read((char*) v.data(), (std::streamsize) bytes);
-  return v;
-}
-template <typename T>
-static void writeAll(const std::string& path, const T* p, size_t n) { std::ofstream f(path, std::ios::binary); f.write((const char*) p, (std::streamsize) (n * sizeof(T))); }
 
 int main(int argc, char** argv) {
   if (argc < 4) { fprintf(stderr, "usage: sweep_driver dir n_devices dev0 [dev1 ...]\n"); return 2; }
   const std::string dir = argv[1];
   const int nd = atoi(argv[2]);
   std::vector<int> devs; for (int i = 0; i < nd; ++i) devs.push_back(atoi(argv[3 + i]));
-  const auto scans = readAll<float>(dir + "/scans.bin"); const auto offs = readAll<int32_t>(dir + "/offsets.bin");
-  const auto map = readAll<float>(dir + "/map.bin"); const auto index = readAll<int32_t>(dir + "/index.bin"); const auto x0 = readAll<float>(dir + "/x0.bin");
+  const auto scans = read_all<float>(dir + "/scans.bin"); const auto offs = read_all<int32_t>(dir + "/offsets.bin");
+  const auto map = read_all<float>(dir + "/map.bin"); const auto index = read_all<int32_t>(dir + "/index.bin"); const auto x0 = read_all<float>(dir + "/x0.bin");
   int cols = 1081, iters = 20; float tau = 0.05f, range_max = 30.f;
   { std::ifstream p(dir + "/params.txt"); p >> cols >> iters >> tau >> range_max; }
   try {
@@ -47,9 +35,9 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < n; ++i) init[i] = Vector3f{{x0[3 * i], x0[3 * i + 1], x0[3 * i + 2]}};
     sweep.compute(index, init);
     std::vector<uint8_t> acc(n); for (size_t i = 0; i < n; ++i) acc[i] = sweep.accept(i) ? 1 : 0;
-    writeAll(dir + "/out_pose.bin", sweep.pose[0].data(), 3 * n); writeAll(dir + "/out_H.bin", sweep.information[0].data(), 9 * n);
-    writeAll(dir + "/out_status.bin", sweep.status.data(), n); writeAll(dir + "/out_stats.bin", sweep.last_stats.data(), n);
-    writeAll(dir + "/out_accept.bin", acc.data(), n);
+    write_all(dir + "/out_pose.bin", sweep.pose[0].data(), 3 * n); write_all(dir + "/out_H.bin", sweep.information[0].data(), 9 * n);
+    write_all(dir + "/out_status.bin", sweep.status.data(), n); write_all(dir + "/out_stats.bin", sweep.last_stats.data(), n);
+    write_all(dir + "/out_accept.bin", acc.data(), n);
     printf("{\"devices\": %d, \"candidates\": %zu}\n", sweep.numDevices(), n);
   } catch (const std::exception& e) { fprintf(stderr, "sweep_driver: %s\n", e.what()); return 1; }
   return 0;

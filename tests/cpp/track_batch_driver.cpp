@@ -6,22 +6,10 @@
 // dir holds ranges.bin (float32 [n_scenarios][steps + 1][2][n_beams]), odo.bin (float64 [n_scenarios][steps][3]), start.bin (float64 [n_scenarios][3]);
 // tracker j runs scenario j % n_scenarios.  An episode starts every tracker's local map from step 0's scans and runs steps 1 .. steps; episodes
 // alternate between the two sides, the first of each side is a warm-up.  Prints one JSON line.
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "lsm2d.h"
 
-template <typename T> static std::vector<T> read_bin(const std::string& path) {
-  FILE* f = fopen(path.c_str(), "rb"); if (!f) { perror(path.c_str()); exit(2); }
-  fseek(f, 0, SEEK_END); const long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+#include "driver_common.h"
+
 static void compose(const double a[3], const double b[3], double o[3]) {
   const double c = cos(a[2]), s = sin(a[2]);
   o[0] = a[0] + c * b[0] - s * b[1]; o[1] = a[1] + s * b[0] + c * b[1]; o[2] = a[2] + b[2];
@@ -36,8 +24,8 @@ int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s dir n_scenarios steps n_beams angle_min angle_max n_trackers episodes\n", argv[0]); return 2; }
   const std::string dir = argv[1];
   const int M = atoi(argv[2]), S = atoi(argv[3]), nb = atoi(argv[4]), N = atoi(argv[7]), episodes = atoi(argv[8]);
-  const std::vector<float> ranges = read_bin<float>(dir + "/ranges.bin");
-  const std::vector<double> odo = read_bin<double>(dir + "/odo.bin"), start = read_bin<double>(dir + "/start.bin");
+  const std::vector<float> ranges = read_all<float>(dir + "/ranges.bin");
+  const std::vector<double> odo = read_all<double>(dir + "/odo.bin"), start = read_all<double>(dir + "/start.bin");
   if ((long) ranges.size() != (long) M * (S + 1) * 2 * nb || (long) odo.size() != (long) M * S * 3 || (long) start.size() != (long) M * 3) { fprintf(stderr, "bad inputs\n"); return 2; }
   auto rng = [&](int scen, int k, int sensor) { return ranges.data() + (((size_t) scen * (S + 1) + k) * 2 + sensor) * nb; };
   lsm2d_preprocessor pp; memset(&pp, 0, sizeof pp);

@@ -4,22 +4,10 @@
 // Every step: clip the device-resident local map around the guess, upload the two scans, align (2 laser slices with their
 // extrinsics + odometry prior, 10 iterations, 721 columns: the MULTI.json parameters), compose the corrected pose on the host,
 // merge both scans.  The map is re-uploaded every `reset` steps so it stays the size a local map between key frames has.
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "lsm2d.h"
 
-static std::vector<float> read_bin(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / 4; fseek(f, 0, SEEK_SET);
-  std::vector<float> v((size_t) n);
-  if (n && fread(v.data(), 4, (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
+#include "driver_common.h"
+
 static void compose(const double a[3], const double b[3], double o[3]) {
   const double c = cos(a[2]), s = sin(a[2]);
   o[0] = a[0] + c * b[0] - s * b[1]; o[1] = a[1] + s * b[0] + c * b[1]; o[2] = a[2] + b[2];
@@ -32,13 +20,13 @@ static void inverse(const double a[3], double o[3]) {
 
 int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s map.bin scan0.bin scan1.bin gx gy gth steps async\n", argv[0]); return 2; }
-  const std::vector<float> map = read_bin(argv[1]), s0 = read_bin(argv[2]), s1 = read_bin(argv[3]);
+  const std::vector<float> map = read_all<float>(argv[1]), s0 = read_all<float>(argv[2]), s1 = read_all<float>(argv[3]);
   const double guess[3] = {atof(argv[4]), atof(argv[5]), atof(argv[6])};
   const int steps = atoi(argv[7]), mode = atoi(argv[8]); const bool async = mode != 0;
   std::vector<float> r0, r1; lsm2d_preprocessor pp; memset(&pp, 0, sizeof pp);
   if (mode == 2) {
     if (argc < 13) { fprintf(stderr, "mode 2 needs ranges0.bin ranges1.bin amin amax\n"); return 2; }
-    r0 = read_bin(argv[9]); r1 = read_bin(argv[10]);
+    r0 = read_all<float>(argv[9]); r1 = read_all<float>(argv[10]);
     pp.n_beams = (int32_t) r0.size(); pp.angle_min = (float) atof(argv[11]); pp.angle_max = (float) atof(argv[12]);
     pp.range_min = 0.3f; pp.range_max = 20.0f; pp.normal_point_distance = 0.3f; pp.normal_min_points = 5; pp.voxelize_resolution = 0.02f;
   }

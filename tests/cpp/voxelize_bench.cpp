@@ -8,37 +8,18 @@
 //                  refuses a set of many clouds: lsm2d_cloudset_create is what a caller has).
 // Wall clock round calls that end in their wait, kernel timing off; medians over `steps` after `warmup`.  Before any time is reported the two routes' outputs
 // are compared byte for byte.  Prints one JSON line.
-#include <lsm2d.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "driver_common.h"
 
 extern "C" int voxref_voxelize(const float* points, const int32_t* offsets, int n_inputs, const float* pose, const int32_t* group, int n_groups, float resolution,
                                float normal_resolution, float* out, int32_t* counts, int32_t* dropped);
-
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void must(int rc, const char* what, lsm2d_context* ctx) { if (rc < 0) { fprintf(stderr, "%s: %s %s\n", what, lsm2d_status_string(rc), lsm2d_last_error(ctx)); exit(1); } }
-static void stats(std::vector<double> v, double out[3]) { std::sort(v.begin(), v.end()); out[0] = v[v.size() / 2]; out[1] = v.front(); out[2] = v.back(); }
 
 int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s points.bin offsets.bin poses.bin|- into_one|fleet res_bits nres_bits steps warmup\n", argv[0]); return 2; }
   const std::vector<float> pts = read_all<float>(argv[1]);
   const std::vector<int32_t> offs = read_all<int32_t>(argv[2]);
-  const std::vector<float> poses = strcmp(argv[3], "-") ? read_all<float>(argv[3]) : std::vector<float>();
+  const std::vector<float> poses = read_all_or_empty<float>(argv[3]);
   const bool fleet = !strcmp(argv[4], "fleet");
-  const lsm2d_voxelize_params P{from_bits(argv[5]), from_bits(argv[6])};
+  const lsm2d_voxelize_params P{from_bits_arg(argv[5]), from_bits_arg(argv[6])};
   const int steps = atoi(argv[7]), warmup = atoi(argv[8]);
   const int32_t K = (int32_t) offs.size() - 1; const int64_t N = offs[(size_t) K];
   int64_t largest = 1; for (int32_t k = 0; k < K; ++k) largest = std::max<int64_t>(largest, offs[(size_t) k + 1] - offs[(size_t) k]);
@@ -96,7 +77,7 @@ int main(int argc, char** argv) {
     double t2 = now_ms(); host_route(); double t3 = now_ms();
     if (i >= warmup) { td.push_back(t1 - t0); th.push_back(t3 - t2); }
   }
-  double d[3], h[3]; stats(td, d); stats(th, h);
+  double d[3], h[3]; summary(td, d, true); summary(th, h, true);      // the upper middle element, as ever
   float kernel_ms = 0.0f;
   must(lsm2d_set_option(ctx, "kernel_timing", 1), "lsm2d_set_option", ctx);
   refill(); device_route();

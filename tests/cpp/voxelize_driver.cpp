@@ -3,29 +3,16 @@
 // The inputs (float [n][4], int32 offsets [n_inputs + 1], float poses [n_inputs][3], int32 groups [n_inputs]) are voxelised into a reserved set of n_groups
 // clouds; with res2_bits != 0 that set is then voxelised IN PLACE (cloud g to cloud g, no poses) at the second resolution.  Prints counts, dropped counts and
 // the clouds of each pass as JSON (floats as bits): the Python test compares it with api.voxelize on the same inputs.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <lsm2d_voxelize.hpp>
+
+#include "driver_common.h"
 
 using namespace lsm2d_host;
 
-template <class T> static std::vector<T> read_all(const char* path) {
-  FILE* f = fopen(path, "rb"); if (!f) { perror(path); exit(2); }
-  fseek(f, 0, SEEK_END); long n = ftell(f) / (long) sizeof(T); fseek(f, 0, SEEK_SET);
-  std::vector<T> v((size_t) n);
-  if (n && fread(v.data(), sizeof(T), (size_t) n, f) != (size_t) n) exit(2);
-  fclose(f); return v;
-}
-static uint32_t bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
-static float from_bits(const char* s) { const uint32_t u = (uint32_t) strtoul(s, nullptr, 10); float v; memcpy(&v, &u, sizeof v); return v; }
-
 static void print_pass(const char* name, const Voxelization& v, const ReservedClouds& dst) {
-  printf("\"%s\": {\"fits\": %d, \"counts\": [", name, v.fits ? 1 : 0);
-  for (size_t g = 0; g < v.counts.size(); ++g) printf("%s%d", g ? "," : "", v.counts[g]);
-  printf("], \"dropped\": [");
-  for (size_t g = 0; g < v.dropped.size(); ++g) printf("%s%d", g ? "," : "", v.dropped[g]);
-  printf("], \"clouds\": [");
+  printf("\"%s\": {\"fits\": %d, ", name, v.fits ? 1 : 0);
+  print_int_list("counts", v.counts, ", "); print_int_list("dropped", v.dropped, ", ");
+  printf("\"clouds\": [");
   for (int32_t g = 0; g < dst.numClouds(); ++g) {
     const PointNormal2fVectorCloud c = dst.download(g);
     printf("%s[", g ? "," : "");
@@ -43,17 +30,17 @@ int main(int argc, char** argv) {
     const std::vector<int32_t> offs = read_all<int32_t>(argv[2]);
     std::vector<PointNormal2fVectorCloud> clouds;
     for (size_t k = 0; k + 1 < offs.size(); ++k) clouds.emplace_back(pts.begin() + offs[k], pts.begin() + offs[k + 1]);
-    const std::vector<Vector3f> poses = strcmp(argv[3], "-") ? read_all<Vector3f>(argv[3]) : std::vector<Vector3f>();
-    const std::vector<int32_t> groups = strcmp(argv[4], "-") ? read_all<int32_t>(argv[4]) : std::vector<int32_t>();
+    const std::vector<Vector3f> poses = read_all_or_empty<Vector3f>(argv[3]);
+    const std::vector<int32_t> groups = read_all_or_empty<int32_t>(argv[4]);
     const int32_t n_groups = atoi(argv[5]);
     CloudSet src(ctx, clouds);
     ReservedClouds dst(ctx, n_groups, atoll(argv[6]));
-    const lsm2d_voxelize_params p1{from_bits(argv[7]), from_bits(argv[8])};
+    const lsm2d_voxelize_params p1{from_bits_arg(argv[7]), from_bits_arg(argv[8])};
     const Voxelization a = voxelize(ctx, p1, src.get(), dst.get(), n_groups, {}, poses, groups);
     printf("{");
     print_pass("first", a, dst);
     if (strtoul(argv[9], nullptr, 10) != 0) {
-      const lsm2d_voxelize_params p2{from_bits(argv[9]), from_bits(argv[8])};
+      const lsm2d_voxelize_params p2{from_bits_arg(argv[9]), from_bits_arg(argv[8])};
       std::vector<int32_t> each((size_t) n_groups);
       for (int32_t g = 0; g < n_groups; ++g) each[(size_t) g] = g;
       const Voxelization b = voxelize(ctx, p2, dst.get(), dst.get(), n_groups, {}, {}, each);

@@ -16,7 +16,7 @@ def _sources(source):
 
 
 def _command(sources, flags, include_dirs):
-    return ["g++", "-std=c++17", *flags, "-I" + INCLUDE, "-I" + HOST, *("-I" + str(d) for d in include_dirs), *sources]
+    return ["g++", "-std=c++17", *flags, "-I" + INCLUDE, "-I" + HOST, "-I" + CPP, *("-I" + str(d) for d in include_dirs), *sources]
 
 
 def build(source, out_dir, flags=("-O2",), include_dirs=(), link=True, link_flags=()):

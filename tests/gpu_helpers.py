@@ -45,6 +45,28 @@ def _assert_bitwise_equal_to_device_order_oracle(res, i, rt, tag):
             assert (int(g["pair_digest_hi"]) << 32 | int(g["pair_digest_lo"])) == o.pair_digest, (tag, "pair digest", k)      # the same correspondence SET, exactly
 
 
+def result_bits(r, rows=None, stats=True):
+    """A batch result (anything with pose, information, status, iterations and, if asked for, stats) as one array of raw words per field, a row per alignment;
+    rows: only those alignments, in that order."""
+    n = len(r.status)
+    d = dict(pose=r.pose.view(np.uint32), information=r.information.reshape(n, 9).view(np.uint32), status=r.status, iterations=r.iterations)
+    if stats:
+        d["stats"] = np.ascontiguousarray(r.stats).view(np.uint8).reshape(n, -1)
+    return d if rows is None else {k: v[rows] for k, v in d.items()}
+
+
+def assert_same_bits(a, b, tag, labels=None, rows=None):
+    """Every field of `a` (result_bits, or arrays under the same names) equals the same field of `b` -- of b's rows `rows` if given -- bit for bit.  A failure
+    names the field, the first alignments that differ and, with `labels` (one per alignment of a), what those are."""
+    for k in a:
+        x, y = a[k].reshape(len(a[k]), -1), b[k].reshape(len(b[k]), -1)
+        if rows is not None:
+            y = y[rows]
+        assert x.shape == y.shape, (tag, k, x.shape, y.shape)
+        d = np.flatnonzero(np.any(x != y, axis=1))
+        assert len(d) == 0, (tag, k, "alignments", d[:8].tolist()) + (() if labels is None else ("labels", np.asarray(labels)[d[:8]].tolist()))
+
+
 def _pose_diff(p, q):
     d = np.abs(np.asarray(p, np.float64) - np.asarray(q, np.float64)); d[2] = abs((d[2] + math.pi) % (2 * math.pi) - math.pi)
     return float(d[:2].max()), float(d[2])

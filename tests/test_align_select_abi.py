@@ -8,46 +8,31 @@ candidate passes the thresholds alone": a candidate ends NotEnoughInliers exactl
 candidate has at least that many, and a NotEnoughCorrespondences candidate has none -- a min_inliers threshold that is a Success candidate's own count rejects
 every one of them.  The condition is therefore checked (and the GPU tests run) with a SECOND set of thresholds as well, align_select_cases.status_thresholds,
 taken from the rows of all candidates: under those the status term alone rejects dozens of candidates."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
+import abi_checks
 import align_select_cases as cases
 import cpp_build
-from conftest import ROOT
 
 NAMES = {"lsm2d_align_select": 13, "lsm2d_sweep_align_select": 16}
 
 
 def test_align_select_symbols_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
     for name, n_args in NAMES.items():
-        assert name + "(" in header, name
-        assert name in bound and len(bound[name][2]) == n_args, name
-        assert hasattr(lib, name), name
-    assert "LSM2D_VERSION 160" in header and "0.7.7" in header      # an addition only: the number stays
+        abi_checks.assert_declared_bound_exported(name, n_args)
+    assert "0.7.7" in abi_checks.header()
 
 
 def test_align_select_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_align_rows", b"k_select_keysINS_8AlignRow", b"k_select_gatherINS_8AlignRow", b"k_select_tile_oneINS_8AlignRow"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_align_rows", b"k_select_keysINS_8AlignRow", b"k_select_gatherINS_8AlignRow", b"k_select_tile_oneINS_8AlignRow"))
 
 
 def test_mirrors_have_align_select():
     from srrg2_laser_slam_2d_amd import api
-    assert callable(api.align_select) and callable(api.align_rank) and callable(api.last_stats_rows)
+    abi_checks.assert_mirrors_have(("align_select", "align_rank", "last_stats_rows"), ("alignSelect(", "computeSelect(", "lsm2d_align_select(", "lsm2d_sweep_align_select("))
     fields = [f.name for f in __import__("dataclasses").fields(api.AlignSelectResult)]
     assert fields[:7] == ["index", "pose", "information", "iterations", "last_stats", "n_accepted", "n_success"]
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d.hpp")).read()
-    for text in ("alignSelect(", "computeSelect(", "lsm2d_align_select(", "lsm2d_sweep_align_select("):
-        assert text in hpp, text
 
 
 @pytest.mark.parametrize("source", ["align_select_driver.cpp", "align_select_bench.cpp"])

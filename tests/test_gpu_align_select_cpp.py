@@ -1,15 +1,14 @@
 """alignSelect and LoopClosureSweep::computeSelect of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU:
 the selection, the counts and every row equal api.align_select on the same inputs, bit for bit -- alignSelect in both orders of summation, computeSelect (two
 shards on one device, merged on the host) in the default order, the only one a sweep's contexts run in."""
-import json
 import math
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_select_cases as cases
 import cpp_build
+from cpp_driver import f32_bits, f32_bits_arg, run_json, stats_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -18,29 +17,21 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("align_select_cpp")
-    exe = cpp_build.build("align_select_driver.cpp", d, flags=("-O2", "-pthread"))
     c = cases.make_cases()
-    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
-    return exe, d, c
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+    return cpp_build.build("align_select_driver.cpp", d, flags=("-O2", "-pthread")), write_bins(d, scan=c.scan, map=c.map, poses=c.poses), c
 
 
 def _same(block, got):
     assert block["n_accepted"] == got.n_accepted and block["n_success"] == got.n_success and block["index"] == got.index.tolist()
     assert len(block["rows"]) == len(got.index)
     for j, row in enumerate(block["rows"]):
-        s = got.last_stats[j]
-        assert row["pose"] == _bits(got.pose[j]) and row["H"] == _bits(got.information[j]) and row["iterations"] == int(got.iterations[j]), j
-        assert row["counts"] == [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])], j
-        assert row["chi"] == _bits([s["chi_inliers"], s["chi_outliers"]]) and row["digest"] == [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])], j
+        assert row["pose"] == f32_bits(got.pose[j]) and row["H"] == f32_bits(got.information[j]) and row["iterations"] == int(got.iterations[j]), j
+        assert {key: row[key] for key in ("counts", "chi", "digest")} == stats_json(got.last_stats[j]), j
 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_cpp_align_select(ctx, driver, order):
-    exe, d, c = driver
+    exe, f, c = driver
     k = 9
     ctx.set_option("sum_order", order)
     try:
@@ -56,11 +47,8 @@ def test_cpp_align_select(ctx, driver, order):
     finally:
         ctx.set_option("sum_order", 0)
     assert len(got.index) == k and k < got.n_accepted < got.n_success < len(c.poses)      # a selection that is cut at k; the status term and the thresholds both reject
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
-    out = subprocess.run([exe] + [str(d / f) for f in ("scan.bin", "map.bin", "poses.bin")] +
-                         [str(cases.COLS), repr(cases.TAU), str(cases.ITERATIONS), str(al.param_min_num_inliers), str(order), str(sel.min_inliers), str(int(thr[0])),
-                          str(int(thr[1])), str(k)], check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [f["scan"], f["map"], f["poses"], cases.COLS, repr(cases.TAU), cases.ITERATIONS, al.param_min_num_inliers, order, sel.min_inliers,
+                       f32_bits_arg(sel.max_chi_per_inlier), f32_bits_arg(sel.min_inlier_ratio), k])
     assert r["n"] == len(c.poses) and r["n_empty"] == 0
     _same(r["align_select"], got)
     if order == 0:

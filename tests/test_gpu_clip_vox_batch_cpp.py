@@ -1,9 +1,7 @@
 """lsm2d_host::TrackerBatch of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp) with Params::clip_voxelize_resolution = 0.1, built with plain
 g++ and run on the GPU (tests/cpp/clip_vox_batch_driver.cpp): 3 trackers, 4 steps, fed from files written here.  Every pose, status, clipped
 size and local-map size must be api.TrackerBatch's for the same input, bit for bit."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +11,7 @@ import tracker_chain as tc
 import tracker_fleet_vox as tfv
 import cpp_build
 from conftest import ROOT
+from cpp_driver import run_json
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -26,9 +25,7 @@ def test_cpp_tracker_batch_voxelised_clip(ctx, tmp_path):
     exe = cpp_build.build("clip_vox_batch_driver.cpp", tmp_path)
     tbb.write_inputs(str(tmp_path), N, STEPS)
     seeds = tfv.fleet_seeds(N, STEPS)
-    out = subprocess.run([exe, str(tmp_path), str(N), str(STEPS), str(tc.N_BEAMS), repr(tc.A0), repr(tc.A1), str(N), repr(RES)],
-                         check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [tmp_path, N, STEPS, tc.N_BEAMS, repr(tc.A0), repr(tc.A1), N, repr(RES)])
     assert r["n_trackers"] == N and len(r["steps"]) == STEPS
     want = tfv.run_fleet(api, ctx, seeds, STEPS, RES)
     plain = tfv.run_fleet(api, ctx, seeds, 1, 0.0)

@@ -11,14 +11,13 @@ import collections
 import ctypes as C
 import math
 import time
-import types
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import mixed_batches as mb
-from gpu_helpers import POSE_TOL_M, POSE_TOL_RAD, _Envelope, _assert_bitwise_equal_to_device_order_oracle, _oracle_slice, _pose_diff, _same_correspondence_sets
+from gpu_helpers import POSE_TOL_M, POSE_TOL_RAD, _Envelope, _assert_bitwise_equal_to_device_order_oracle, _oracle_slice, _pose_diff, _same_correspondence_sets, assert_same_bits, result_bits
 from srrg2_laser_slam_2d_amd import _capi, api, synth
 from mixed_batches import MIN_DIFFERENT as MIXED_MIN_DIFFERENT, WALL_OFFSET_START, WALL_OFFSET_TOL, WALL_ROWS, wall_cloud
 
@@ -69,17 +68,6 @@ def _run(ctx, spec, want_pairs=False, **opts):
     finally:
         for k in opts:
             ctx.set_option(k, 1 if k in ("cull", "balance") else 0)
-
-
-def _bits(r):
-    return dict(pose=r.pose.view(np.uint32), H=r.information.view(np.uint32), status=r.status, iterations=r.iterations, stats=np.ascontiguousarray(r.stats).view(np.uint8))
-
-
-def _assert_same_bits(r, ref, kinds, tag):
-    a, b = _bits(r), _bits(ref)
-    for k in ("pose", "H", "status", "iterations", "stats"):
-        d = np.flatnonzero(np.any((a[k] != b[k]).reshape(len(kinds), -1), axis=1))
-        assert len(d) == 0, (tag, k, "alignments", d[:8].tolist(), "kinds", kinds[d[:8]].tolist())
 
 
 def _finite(spec):
@@ -140,11 +128,11 @@ def test_k_align_wide_narrow_and_seq(order_ctx, po, setting, full):
     for w in (512, 256):
         r, path, width = _run(ctx, spec, align_path=1, align_width=w)
         assert path == 1 and width == (512 if (so and w == 256) else w), (setting, so, w, path, width)      # (no narrow reference-order kernel: 256 launches 512)
-        _assert_same_bits(r, ref, spec["kinds"], ("align_width", w))
+        assert_same_bits(result_bits(r), result_bits(ref), labels=spec["kinds"], tag=("align_width", w))
         forms.append(("align_path 1, align_width %d" % w, path, width))
     r, path, width = _run(ctx, spec, align_path=1, cull=0, balance=0)      # (the stream without culling has no narrow form)
     assert path == 1 and width == 512, (setting, so, path, width)
-    _assert_same_bits(r, ref, spec["kinds"], "cull 0, balance 0")
+    assert_same_bits(result_bits(r), result_bits(ref), labels=spec["kinds"], tag="cull 0, balance 0")
     forms.append(("align_path 1, cull 0, balance 0", path, width))
     checked = _assert_oracle_bits(po, ref, spec, so, "n 120")
     d_lambda, d_omega = _assert_contrasts(ctx, ref, spec, (setting, so), align_path=1)
@@ -164,7 +152,7 @@ def test_packed_workgroups(ctx, po, sum_order, setting, full):
         assert path == 1 and width == 1024, (setting, sum_order, path, width)
         r, path_w, width_w = _run(ctx, spec, align_width=512)
         assert path_w == 1 and width_w == 512, (path_w, width_w)
-        _assert_same_bits(r, ref, spec["kinds"], "align_width 512")
+        assert_same_bits(result_bits(r), result_bits(ref), labels=spec["kinds"], tag="align_width 512")
         checked = _assert_oracle_bits(po, ref, spec, sum_order, "n 1040")
         d_lambda, d_omega = _assert_contrasts(ctx, ref, spec, (setting, sum_order))
     finally:
@@ -216,7 +204,7 @@ def test_split_path(order_ctx, po):
     assert path == 2
     r1, path, _ = _run(ctx, spec, align_path=1)
     assert path == 1
-    _assert_same_bits(r2, r1, spec["kinds"], "split path against k_align")
+    assert_same_bits(result_bits(r2), result_bits(r1), "split path against k_align", spec["kinds"])
     checked = _assert_oracle_bits(po, r2, spec, so, "split")
     diag = _run(ctx, _spec(8, "S3", DAMPING, False), align_path=2)[0]; plain = _run(ctx, _spec(8, "S3", 0.0, True), align_path=2)[0]
     ok = np.flatnonzero(r2.status == 0)
@@ -250,8 +238,7 @@ def test_latency_kernel(order_ctx, po):
                            priors=None if priors is None else priors[i0:i0 + 1])
                 r1, path, _ = _run(ctx, one)
                 assert path == 3 and r1.status[0] == 0, (ns, name, lam, path, r1.status)      # automatic: a single alignment takes the latency kernel in both orders
-                _assert_same_bits(r1, types.SimpleNamespace(pose=r.pose[i0:i0 + 1], information=r.information[i0:i0 + 1], status=r.status[i0:i0 + 1],
-                                                            iterations=r.iterations[i0:i0 + 1], stats=r.stats[i0:i0 + 1]), one["kinds"], ("single alignment against the batch's", ns, name, lam))
+                assert_same_bits(result_bits(r1), result_bits(r), ("single alignment against the batch's", ns, name, lam), one["kinds"], rows=[i0])
                 poses[(name, lam)] = r1.pose[0].tobytes() + r1.information[0].tobytes()
                 runs += 2
         # every input is seen: no two of the eight (prior, damping) combinations give the same pose and information matrix -- the asymmetric Omega and its transpose
@@ -315,10 +302,10 @@ def test_forms_that_only_carry_state(ctx, po):
     al = mb.aligner(ctx, spec)
     prep = al.prepare_batch(fixed, [moving] * 2, spec["x0"], priors=spec["priors"], fixed_index=spec["fixed_index"], want_stats=True)
     for k in range(3):
-        _assert_same_bits(prep.run(copy=True), ref, spec["kinds"], ("prepared", k))
-    prep.begin(); _assert_same_bits(prep.wait(copy=True), ref, spec["kinds"], "begin / wait")
+        assert_same_bits(result_bits(prep.run(copy=True)), result_bits(ref), labels=spec["kinds"], tag=("prepared", k))
+    prep.begin(); assert_same_bits(result_bits(prep.wait(copy=True)), result_bits(ref), labels=spec["kinds"], tag="begin / wait")
     pairs, _, _ = _run(ctx, spec, want_pairs=True)
-    _assert_same_bits(pairs, ref, spec["kinds"], "want_pairs")
+    assert_same_bits(result_bits(pairs), result_bits(ref), labels=spec["kinds"], tag="want_pairs")
     for i in _finite(spec)[:16]:
         w = mb.oracle_align(po, spec, int(i), device_order=True, want_pairs=True)
         assert all(np.array_equal(pairs.pairs[i][s], w["pairs"][s]) for s in range(2)), ("pairs", int(i), spec["kinds"][i])

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import fast_forward_cases as ffc
-from gpu_helpers import _assert_bitwise_equal_to_device_order_oracle, _oracle_slice
+from gpu_helpers import _assert_bitwise_equal_to_device_order_oracle, _oracle_slice, assert_same_bits, result_bits
 from srrg2_laser_slam_2d_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -55,19 +55,10 @@ def _run(ctx, al, n, fast_forward, sum_order=0, priors=None, **opts):
             ctx.set_option(k, 1 if k == "fast_forward" else 0)
 
 
-def _bits(r):
-    return dict(pose=r.pose.view(np.uint32), information=r.information.view(np.uint32), status=r.status, iterations=r.iterations, stats=np.ascontiguousarray(r.stats).view(np.uint8))
-
-
 def _assert_option_changes_nothing_and_tiles_agree(on, off, tag):
-    a, b = _bits(on), _bits(off)
-    n = len(on.status)
-    for k in a:
-        d = np.flatnonzero(np.any((a[k] != b[k]).reshape(n, -1), axis=1))
-        assert len(d) == 0, (tag, k, "fast_forward 1 against 0: alignments", d[:8].tolist())
-        v = a[k].reshape(n, -1)
-        d = np.flatnonzero(np.any(v != v[np.arange(n) % ffc.N], axis=1))
-        assert len(d) == 0, (tag, k, "tiles differ: alignments", d[:8].tolist())
+    a = result_bits(on)
+    assert_same_bits(a, result_bits(off), (tag, "fast_forward 1 against 0"))
+    assert_same_bits(a, a, (tag, "tiles differ"), rows=np.arange(len(on.status)) % ffc.N)
 
 
 def _assert_oracle(res, want, tag):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import ff_finish_cases as fc
-from gpu_helpers import _oracle_slice
+from gpu_helpers import _oracle_slice, assert_same_bits, result_bits
 from srrg2_laser_slam_2d_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -54,33 +54,17 @@ def _run(ctx, al, n, fast_forward, sum_order=0, priors=None, **opts):
             ctx.set_option(k, 2 if k == "fast_forward" else 0)      # (the library's defaults)
 
 
-def _bits(r):
-    n = len(r.status)
-    return dict(pose=r.pose.view(np.uint32), information=r.information.reshape(n, 9).view(np.uint32), status=r.status, iterations=r.iterations,
-                stats=np.ascontiguousarray(r.stats).view(np.uint8).reshape(n, -1))
-
-
-def _assert_same(got, want, tag, what, rows=None):
-    for k in got:
-        a, b = got[k].reshape(len(got[k]), -1), want[k].reshape(len(want[k]), -1)
-        if rows is not None:
-            b = b[rows]
-        assert a.shape == b.shape, (tag, k, what, a.shape, b.shape)
-        d = np.flatnonzero(np.any(a != b, axis=1))
-        assert len(d) == 0, (tag, k, what, "alignments", d[:8].tolist())
-
-
 def _three_ways(ctx, al, n, tag, want, sum_order=0, width=512, priors=None, **opts):
     """"fast_forward" 2, 1 and 0 on the same batch: equal to each other, every tile equal to the first, the first 512 equal to the oracle's arrays `want`"""
     res = {}
     for ff in (2, 1, 0):
         r, path, w = _run(ctx, al, n, ff, sum_order, priors=priors, **opts)
         assert path == 1 and w == width, (tag, ff, path, w)
-        res[ff] = _bits(r)
-    _assert_same(res[2], res[0], tag, "fast_forward 2 against 0")
-    _assert_same(res[1], res[0], tag, "fast_forward 1 against 0")
-    _assert_same(res[2], res[2], tag, "tiles differ", rows=np.arange(n) % fc.N)
-    _assert_same({k: v[:fc.N] for k, v in res[2].items()}, want, tag, "fast_forward 2 against the oracle")
+        res[ff] = result_bits(r)
+    assert_same_bits(res[2], res[0], (tag, "fast_forward 2 against 0"))
+    assert_same_bits(res[1], res[0], (tag, "fast_forward 1 against 0"))
+    assert_same_bits(res[2], res[2], (tag, "tiles differ"), rows=np.arange(n) % fc.N)
+    assert_same_bits({k: v[:fc.N] for k, v in res[2].items()}, want, (tag, "fast_forward 2 against the oracle"))
     return res[2]
 
 

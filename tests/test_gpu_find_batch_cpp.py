@@ -1,13 +1,10 @@
 """computeBatch of the C++ host mirror's finders (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU: the batches equal the
 mirror's own single compute() calls item by item (checked inside the driver) and the CPU oracle (checked here), bit for bit."""
-import json
-import math
-import subprocess
-
 import numpy as np
 import pytest
 
 import cpp_build
+from cpp_driver import run_json, write_bins
 from srrg2_laser_slam_2d_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +18,8 @@ def test_cpp_compute_batch(po, tmp_path):
     pts, offs = synth.make_scans(world, robots, n_beams=1081, noise_sigma=0.01, seed=5)
     x0 = synth.invert_poses(synth.compose_poses(robots, np.array([[0.12, -0.08, 0.04]] * 6))).astype(np.float32)
     x0[5] = np.float32([500.0, 500.0, 1.0])
-    pts.tofile(tmp_path / "scans.bin"); offs.astype(np.int32).tofile(tmp_path / "offsets.bin"); m.tofile(tmp_path / "map.bin"); x0.tofile(tmp_path / "poses.bin")
-    out = subprocess.run([exe] + [str(tmp_path / f) for f in ("scans.bin", "offsets.bin", "map.bin", "poses.bin")] + ["1081", "0.4"],
-                         check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    f = write_bins(tmp_path, scans=pts, offsets=offs.astype(np.int32), map=m, poses=x0)
+    r = run_json(exe, [f["scans"], f["offsets"], f["map"], f["poses"], 1081, "0.4"])
     assert r["n"] == 6 and r["equal_single"] == 1 and r["equal_reversed"] == 1 and r["n_empty"] == 0
     osp = po.slice_params(canvas_cols=1081, range_max=25.0)
     onn = po.slice_params(finder=po.FINDER_NN, max_distance=0.4, normal_cos=0.7)

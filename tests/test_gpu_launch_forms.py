@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import mixed_batches as mb
-from gpu_helpers import _assert_bitwise_equal_to_device_order_oracle
+from gpu_helpers import _assert_bitwise_equal_to_device_order_oracle, assert_same_bits, result_bits
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -24,18 +24,6 @@ CASES = [(0, n, s, w) for n, w in ((300, 512), (1025, 1024), (1040, 1024), (1100
 CASES += [(0, 1040, "S3", 1024), (0, 1537, "S3", 1024)]      # (two slices: the canvases' LDS leaves room for five narrow workgroups per CU -- 1280 -- so 1537 packs)
 CASES += [(1, n, s, 1024) for n in (1040, 1537, 2049) for s in ("S1", "S3")]      # (no narrow form in the reference's order: packed up to 1600, and 2049)
 _ORACLE = {}      # (sum_order, setting, i) -> result: alignment i is the same in every batch size of a setting (mixed_batches: a batch is a prefix of a larger one)
-
-
-def _bits(r, rows=None):
-    rows = np.arange(len(r.status)) if rows is None else rows
-    return dict(pose=r.pose[rows].view(np.uint32), H=r.information[rows].view(np.uint32), status=r.status[rows], iterations=r.iterations[rows],
-                stats=np.ascontiguousarray(r.stats[rows]).view(np.uint8))
-
-
-def _assert_same_bits(a, b, kinds, tag):
-    for k in ("pose", "H", "status", "iterations", "stats"):
-        d = np.flatnonzero(np.any((a[k] != b[k]).reshape(len(kinds), -1), axis=1))
-        assert len(d) == 0, (tag, k, "alignments", d[:8].tolist(), "kinds", kinds[d[:8]].tolist())
 
 
 def _run(ctx, al, spec, x0=None, want_pairs=False, **opts):
@@ -64,43 +52,43 @@ def test_launch_forms_on_mixed_batches(ctx, po, sum_order, n, setting, form):
         ref, path, width = _run(ctx, al, spec)
         assert path == 1, (n, setting, path)      # (first: last_align_width is not updated by split or latency-kernel launches)
         assert width == form, (n, setting, sum_order, width, form)
-        want = _bits(ref)
+        want = result_bits(ref)
         # ---- the variants: every one must give the automatic call's bits, every alignment
         widths = [512, 256] + ([1024] if n > 1024 and n % 1024 else [])
         for w in widths:
             r, path, got_w = _run(ctx, al, spec, align_width=w)
             assert path == 1 and got_w == (512 if (sum_order and w == 256) else w), (n, setting, sum_order, w, got_w)      # (no narrow reference-order kernel: 256 launches 512)
-            _assert_same_bits(_bits(r), want, kinds, ("align_width", w))
+            assert_same_bits(result_bits(r), want, labels=kinds, tag=("align_width", w))
         r, _, _ = _run(ctx, al, spec, cull=0, balance=0)
-        _assert_same_bits(_bits(r), want, kinds, "cull 0, balance 0")
+        assert_same_bits(result_bits(r), want, labels=kinds, tag="cull 0, balance 0")
         perm = np.random.default_rng(n).permutation(n)
         sp = dict(spec, x0=spec["x0"][perm], fixed_index=np.ascontiguousarray(spec["fixed_index"][:, perm]),
                   priors=None if spec["priors"] is None else [spec["priors"][j] for j in perm])
         r, _, _ = _run(ctx, al, sp)
-        _assert_same_bits(_bits(r, np.argsort(perm)), want, kinds, "permuted")
+        assert_same_bits(result_bits(r, np.argsort(perm)), want, labels=kinds, tag="permuted")
         args = (spec["_fixed"], [spec["_moving"]] * spec["ns"], spec["x0"])
         kw = dict(priors=spec["priors"], fixed_index=spec["fixed_index"], want_stats=True)
         prep = al.prepare_batch(*args, **kw)
         for k in range(3):      # the third run: the kept placement (no estimate) where the library keeps one
-            _assert_same_bits(_bits(prep.run(copy=True)), want, kinds, ("prepared", k))
+            assert_same_bits(result_bits(prep.run(copy=True)), want, labels=kinds, tag=("prepared", k))
         if n <= 1024 or (form == 1024 and n < 2048):
             assert ctx.get_option("last_cull_estimate") == 0, (n, setting)
-        prep.begin(); _assert_same_bits(_bits(prep.wait(copy=True)), want, kinds, "begin / wait")
+        prep.begin(); assert_same_bits(result_bits(prep.wait(copy=True)), want, labels=kinds, tag="begin / wait")
         prep2 = al.prepare_batch(spec["_fixed"], [spec["_moving"]] * spec["ns"], sp["x0"], priors=sp["priors"], fixed_index=sp["fixed_index"], want_stats=True)
         prep.begin(); prep2.begin()
         a, b = prep.wait(copy=True), prep2.wait(copy=True)
-        _assert_same_bits(_bits(a), want, kinds, "begin / wait beside a second batch")
-        _assert_same_bits(_bits(b, np.argsort(perm)), want, kinds, "the second batch in flight (permuted)")
+        assert_same_bits(result_bits(a), want, labels=kinds, tag="begin / wait beside a second batch")
+        assert_same_bits(result_bits(b, np.argsort(perm)), want, labels=kinds, tag="the second batch in flight (permuted)")
         # ---- not-a-number starts: a failure status, and the alignments beside them as in the same batch with finite starts there instead
         bad = np.isin(kinds, mb.NON_FINITE)
         assert bad.any() and np.all(ref.status[bad] != 0), ref.status[bad]
         x_fin = spec["x0"].copy(); x_fin[bad] = spec["x0"][np.flatnonzero(kinds == "far")[0]]
         r, _, _ = _run(ctx, al, spec, x0=x_fin)
-        _assert_same_bits(_bits(r, np.flatnonzero(~bad)), _bits(ref, np.flatnonzero(~bad)), kinds[~bad], "finite starts in place of the non-finite ones")
+        assert_same_bits(result_bits(r, np.flatnonzero(~bad)), result_bits(ref, np.flatnonzero(~bad)), labels=kinds[~bad], tag="finite starts in place of the non-finite ones")
         pairs = None
         if setting == "S1" and n == 1040 and not sum_order:
             pairs, _, _ = _run(ctx, al, spec, want_pairs=True)
-            _assert_same_bits(_bits(pairs), want, kinds, "want_pairs")
+            assert_same_bits(result_bits(pairs), want, labels=kinds, tag="want_pairs")
     finally:
         ctx.set_option("sum_order", 0)
     # ---- against the oracle: every alignment up to 1100; above, every light or failing one (those are paired) and a stride sample of the others

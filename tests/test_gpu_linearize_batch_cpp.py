@@ -1,13 +1,11 @@
 """linearize / linearizeBatch of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU: the batch equals the
 mirror's own single linearize() calls item by item, byte for byte (checked inside the driver), and the CPU oracle in the order of summation asked for
 (checked here), bit for bit."""
-import json
-import subprocess
-
 import numpy as np
 import pytest
 
 import cpp_build
+from cpp_driver import f32_bits, run_json, write_bins
 from srrg2_laser_slam_2d_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -26,16 +24,13 @@ def driver(tmp_path_factory):
     offs = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int32)
     x0 = np.ascontiguousarray(wl.x0[which], np.float32)
     x0[3] += np.float32([0.02, -0.01, 0.005]); x0[4] += np.float32([-0.01, 0.02, -0.004])
-    np.concatenate(scans).tofile(d / "scans.bin"); offs.tofile(d / "offsets.bin"); wl.map_points.tofile(d / "map.bin"); x0.tofile(d / "poses.bin")
-    return exe, d, scans, wl.map_points, x0
+    return exe, write_bins(d, scans=np.concatenate(scans), offsets=offs, map=wl.map_points, poses=x0), scans, wl.map_points, x0
 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_cpp_linearize_batch(po, driver, order):
-    exe, d, scans, m, x0 = driver
-    out = subprocess.run([exe] + [str(d / f) for f in ("scans.bin", "offsets.bin", "map.bin", "poses.bin")] + ["1081", repr(TAU), str(order)],
-                         check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    exe, f, scans, m, x0 = driver
+    r = run_json(exe, [f["scans"], f["offsets"], f["map"], f["poses"], 1081, repr(TAU), order])
     assert r["n"] == 5 and r["equal_single"] == 1 and r["equal_reversed"] == 1 and r["n_empty"] == 0
     osp = po.slice_params(robustifier=po.ROBUST_CAUCHY, chi_threshold=TAU)
     oracle = po.linearize if order else po.linearize_device_order
@@ -50,7 +45,7 @@ def test_cpp_linearize_batch(po, driver, order):
         assert np.array_equal(np.array(it["H"], np.uint32), H.ravel().view(np.uint32)), i
         assert np.array_equal(np.array(it["b"], np.uint32), b.view(np.uint32)), i
         assert it["counts"] == [st.n_corr, st.n_in, st.n_out], i
-        assert it["chi"] == [int(np.float32(st.chi_in).view(np.uint32)), int(np.float32(st.chi_out).view(np.uint32))], i
+        assert it["chi"] == f32_bits([st.chi_in, st.chi_out]), i
         assert it["digest"] == [st.pair_digest_lo, st.pair_digest_hi], i
         split = split or (st.n_in > 0 and st.n_out > 0)
     assert split

@@ -1,23 +1,17 @@
 """The log-odds grid set of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d_occupancy.hpp), built with plain g++ and run on the GPU: the cells and the
 render the driver writes are the Python mirror's bytes on the same inputs -- five posed scans with beams of every class into two grids, updated with one set
 of parameters, then with another, decayed, and one grid sent through a download and an upload."""
-import json
-import subprocess
-
 import numpy as np
 import pytest
 
 import cpp_build
 import occupancy_logodds_cases as lc
 import occupancy_scan_cases as sc
+from cpp_driver import f32_bits_arg as bits_arg, run_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-def _bits(v):
-    return str(int(F32(v).view(np.uint32)))
 
 
 def test_cpp_occupancy_logodds(ctx, tmp_path):
@@ -26,8 +20,7 @@ def test_cpp_occupancy_logodds(ctx, tmp_path):
     prm = case["params"]
     first, second = lc.PARAMS, api.LogOddsParams(60, -90, -150, 120)
     w, h, decay, unit, min_scans = sc.W, sc.H, 25, lc.UNIT, 2
-    case["ranges"].tofile(tmp_path / "ranges.bin")
-    np.ascontiguousarray(case["poses"], F32).tofile(tmp_path / "poses.bin"); np.ascontiguousarray(case["grids"], np.int32).tofile(tmp_path / "grid.bin")
+    f = write_bins(tmp_path, ranges=case["ranges"], poses=np.asarray(case["poses"], F32), grid=np.asarray(case["grids"], np.int32))
     # the Python mirror, the same steps
     gs = api.GridSet(ctx, api.GridGeometry(case["origin"][0], case["origin"][1], case["resolution"], w, h), case["n_grids"], first)
     api.occupancy_update_scans(ctx, gs, prm, case["ranges"], case["poses"], case["grids"])
@@ -45,10 +38,10 @@ def test_cpp_occupancy_logodds(ctx, tmp_path):
     ref = b"".join(v[g].tobytes() + o[g].tobytes() + api.logodds_values(v[g], o[g], unit, min_scans).tobytes() for g in range(case["n_grids"]))
     assert want == ref and hit.sum() > 500 and clear.sum() > 200 and np.abs(v).max() > 0
     gs.close()
-    args = [str(tmp_path / n) for n in ("ranges.bin", "poses.bin", "grid.bin")] + [
-        str(case["n_grids"]), str(prm.n_beams), _bits(prm.angle_min), _bits(prm.angle_max), _bits(prm.range_min), _bits(prm.range_max), _bits(prm.trace_range),
-        str(int(prm.clear_no_return)), _bits(case["origin"][0]), _bits(case["origin"][1]), _bits(case["resolution"]), str(w), str(h)]
-    args += [str(x) for p in (first, second) for x in (p.l_hit, p.l_miss, p.l_min, p.l_max)] + [str(decay), _bits(unit), str(min_scans), str(tmp_path / "out.bin")]
-    r = json.loads(subprocess.run([exe] + args, check=True, capture_output=True, text=True, timeout=120).stdout)
+    args = [f["ranges"], f["poses"], f["grid"], case["n_grids"], prm.n_beams, bits_arg(prm.angle_min), bits_arg(prm.angle_max), bits_arg(prm.range_min),
+            bits_arg(prm.range_max), bits_arg(prm.trace_range), int(prm.clear_no_return), bits_arg(case["origin"][0]), bits_arg(case["origin"][1]),
+            bits_arg(case["resolution"]), w, h]
+    args += [x for p in (first, second) for x in (p.l_hit, p.l_miss, p.l_min, p.l_max)] + [decay, bits_arg(unit), min_scans, tmp_path / "out.bin"]
+    r = run_json(exe, args)
     assert r == dict(hit_rays=hit.tolist(), clear_rays=clear.tolist(), dropped=dropped.tolist())
     assert (tmp_path / "out.bin").read_bytes() == want

@@ -1,15 +1,14 @@
 """relocalizeSelect of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d_relocalize.hpp), built with plain g++ and run on the GPU against the existing
 relocalize() of lsm2d.hpp on the same inputs: the driver restates relocalize()'s verdict and compares every output byte for byte; what it prints is also
 api.relocalize_select's answer on the same inputs, bit for bit -- in both orders of summation."""
-import json
 import math
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_select_cases as cases
 import cpp_build
+from cpp_driver import f32_bits, f32_bits_arg, run_json, stats_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -18,19 +17,13 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("relocalize_select_cpp")
-    exe = cpp_build.build("relocalize_select_driver.cpp", d, flags=("-O2", "-pthread"))
     c = cases.make_cases()
-    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
-    return exe, d, c
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+    return cpp_build.build("relocalize_select_driver.cpp", d, flags=("-O2", "-pthread")), write_bins(d, scan=c.scan, map=c.map, poses=c.poses), c
 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_cpp_relocalize_select(ctx, driver, order):
-    exe, d, c = driver
+    exe, f, c = driver
     k_score, k = 64, 5
     ctx.set_option("sum_order", order)
     try:
@@ -49,17 +42,12 @@ def test_cpp_relocalize_select(ctx, driver, order):
         ctx.set_option("sum_order", 0)
     print("scored", got.n_scored_accepted, len(got.scored_index), "aligned", got.n_success, got.n_accepted, len(got.index))
     assert 0 < len(got.scored_index) and len(got.index) == min(k, got.n_accepted) and 0 < got.n_accepted
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
-    out = subprocess.run([exe] + [str(d / f) for f in ("scan.bin", "map.bin", "poses.bin")] +
-                         [str(cases.COLS), repr(cases.TAU), str(cases.ITERATIONS), str(al.param_min_num_inliers), str(order), str(sel.min_inliers), str(int(thr[0])),
-                          str(int(thr[1])), str(k_score), str(k)], check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [f["scan"], f["map"], f["poses"], cases.COLS, repr(cases.TAU), cases.ITERATIONS, al.param_min_num_inliers, order, sel.min_inliers,
+                       f32_bits_arg(sel.max_chi_per_inlier), f32_bits_arg(sel.min_inlier_ratio), k_score, k])
     assert r["n"] == len(c.poses) and r["n_empty"] == 0
     assert r["scored_equal"] == 1 and r["aligned_equal"] == 1      # relocalizeSelect against relocalize(), inside the driver
     assert r["scored_index"] == got.scored_index.tolist() and r["n_scored_accepted"] == got.n_scored_accepted
     assert r["index"] == got.index.tolist() and (r["n_accepted"], r["n_success"]) == (got.n_accepted, got.n_success)
     for j, row in enumerate(r["rows"]):
-        s = got.last_stats[j]
-        assert row["pose"] == _bits(got.pose[j]) and row["H"] == _bits(got.information[j]) and row["iterations"] == int(got.iterations[j]), j
-        assert row["counts"] == [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])], j
-        assert row["chi"] == _bits([s["chi_inliers"], s["chi_outliers"]]) and row["digest"] == [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])], j
+        assert row["pose"] == f32_bits(got.pose[j]) and row["H"] == f32_bits(got.information[j]) and row["iterations"] == int(got.iterations[j]), j
+        assert {key: row[key] for key in ("counts", "chi", "digest")} == stats_json(got.last_stats[j]), j

@@ -2,15 +2,14 @@
 (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU: every row, the selection and the relocalisation's results equal
 api.score_aligner / api.score_aligner_select / api.relocalize on the same inputs, bit for bit; inside the driver the mirror equals the ABI, every selected
 row equals scoreAligner's, and relocalize equals the entry points called by hand."""
-import json
 import math
-import subprocess
 
 import numpy as np
 import pytest
 
 import score_aligner_cases as cases
 import cpp_build
+from cpp_driver import f32_bits, f32_bits_arg, run_json, stats_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -30,26 +29,15 @@ def driver(tmp_path_factory):
     c.fixed_h = [[c.fixed[0][i] for i in c.scan], [c.fixed[1][i] for i in c.scan]]      # one cloud per hypothesis, moved by the slice's S^-1
     for s in range(2):
         off = np.zeros(25, np.int32); off[1:] = np.cumsum([len(a) for a in c.fixed_h[s]])
-        np.concatenate(c.fixed_h[s]).tofile(d / ("fixed%d.bin" % s)); off.tofile(d / ("off%d.bin" % s))
-        c.moving[c.which[s]].tofile(d / ("moving%d.bin" % s))
+        write_bins(d, **{"fixed%d" % s: np.concatenate(c.fixed_h[s]), "off%d" % s: off, "moving%d" % s: c.moving[c.which[s]]})
     c.priors = [cases.asym_prior(X, seed=2) for X in c.hyp]
-    np.concatenate([np.concatenate([z, om.ravel()]) for z, om in c.priors]).astype(np.float32).tofile(d / "priors.bin")
-    c.hyp.tofile(d / "poses.bin")
+    write_bins(d, priors=np.concatenate([np.concatenate([z, om.ravel()]) for z, om in c.priors]).astype(np.float32), poses=c.hyp)
     return exe, d, c
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
-
-
-def _stats_json(s):
-    return {"counts": [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])],
-            "chi": _bits([s["chi_inliers"], s["chi_outliers"]]), "digest": [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])]}
-
-
 def _same_row(row, H, b, st, active, tag):
-    assert row["H"] == _bits(H) and row["b"] == _bits(b) and row["active"] == int(active), tag
-    assert {key: row[key] for key in ("counts", "chi", "digest")} == _stats_json(st), tag
+    assert row["H"] == f32_bits(H) and row["b"] == f32_bits(b) and row["active"] == int(active), tag
+    assert {key: row[key] for key in ("counts", "chi", "digest")} == stats_json(st), tag
 
 
 @pytest.mark.parametrize("with_prior", [0, 1], ids=["plain", "prior"])
@@ -76,10 +64,7 @@ def test_cpp_score_aligner(ctx, driver, order, with_prior):
                                    fixed_index=np.stack([index, index]), want_stats=True)
     finally:
         ctx.set_option("sum_order", 0)
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
-    out = subprocess.run([exe, str(d), str(order), str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), str(k), str(with_prior)],
-                         check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [d, order, sel.min_inliers, f32_bits_arg(sel.max_chi_per_inlier), f32_bits_arg(sel.min_inlier_ratio), k, with_prior])
     assert r["n"] == len(c.hyp) and r["mirror_equals_abi"] == 1 and r["rows_equal_score_aligner"] == 1 and r["relocalize_equals_by_hand"] == 1 and r["n_empty"] == 0
     assert np.any(active == 0) and np.any(active == 2)
     for i, row in enumerate(r["all"]):
@@ -95,9 +80,9 @@ def test_cpp_score_aligner(ctx, driver, order, with_prior):
     assert rr["n_accepted"] == rel.n_accepted and len(rr["items"]) == len(rel.index)
     last = rel.result.last_stats()
     for j, it in enumerate(rr["items"]):
-        assert it["pose"] == _bits(rel.result.pose[j]) and it["status"] == int(rel.result.status[j]) and it["iterations"] == int(rel.result.iterations[j]), j
+        assert it["pose"] == f32_bits(rel.result.pose[j]) and it["status"] == int(rel.result.status[j]) and it["iterations"] == int(rel.result.iterations[j]), j
         assert it["accepted"] == int(rel.accepted[j]), j
-        assert {key: it[key] for key in ("counts", "chi", "digest")} == _stats_json(last[j]), j
+        assert {key: it[key] for key in ("counts", "chi", "digest")} == stats_json(last[j]), j
     assert any(it["status"] == 0 for it in rr["items"])
 
 

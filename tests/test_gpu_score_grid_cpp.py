@@ -1,15 +1,13 @@
 """scoreGridSelect and relocalizeGrid of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d_score_grid.hpp), built with plain g++ and run on the GPU:
 what the driver prints is api.score_grid_select's and api.relocalize_grid's answer on the same inputs, bit for bit -- in both orders of summation."""
-import json
 import math
-import subprocess
 
-import numpy as np
 import pytest
 
 import align_select_cases as ac
 import cpp_build
 import score_grid_cases as gc
+from cpp_driver import f32_bits, f32_bits_arg, run_json, stats_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -18,24 +16,17 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("score_grid_cpp")
-    exe = cpp_build.build("score_grid_driver.cpp", d, flags=("-O2", "-pthread"))
     c = gc.make_cases()
-    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin")
-    return exe, d, c
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+    return cpp_build.build("score_grid_driver.cpp", d, flags=("-O2", "-pthread")), write_bins(d, scan=c.scan, map=c.map), c
 
 
 def _sel_args(sel):
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
-    return [str(int(sel.min_inliers)), str(int(thr[0])), str(int(thr[1]))]
+    return [int(sel.min_inliers), f32_bits_arg(sel.max_chi_per_inlier), f32_bits_arg(sel.min_inlier_ratio)]
 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_cpp_score_grid(ctx, driver, order):
-    exe, d, c = driver
+    exe, f, c = driver
     g, _, _, _ = gc.cases(c)["some"]      # three levels, 0 < m < k_parents at level 0: pads
     k, k_align = 32, 5
     ctx.set_option("sum_order", order)
@@ -51,20 +42,15 @@ def test_cpp_score_grid(ctx, driver, order):
         ctx.set_option("sum_order", 0)
     print("counts", got.level_counts.tolist(), "aligned", rel.aligned.n_success, rel.aligned.n_accepted, len(rel.aligned.index))
     assert 0 < got.level_counts[0, 1] < g.k_parents and len(got.pose) > 0 and len(rel.aligned.index) > 0
-    args = [str(d / "scan.bin"), str(d / "map.bin"), str(ac.COLS), repr(ac.TAU), str(order)]
-    args += [str(v) for v in _bits(g.center)] + [str(v) for v in _bits(g.step)]
-    args += [str(v) for v in g.count] + [str(g.n_levels)] + [str(v) for v in g.refine] + [str(g.k_parents)]
-    args += _sel_args(mid) + _sel_args(mid) + [str(k), str(ac.ITERATIONS), str(k_align)]
-    out = subprocess.run([exe] + args, check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    args = [f["scan"], f["map"], ac.COLS, repr(ac.TAU), order] + f32_bits(g.center) + f32_bits(g.step)
+    args += list(g.count) + [g.n_levels] + list(g.refine) + [g.k_parents] + _sel_args(mid) + _sel_args(mid) + [k, ac.ITERATIONS, k_align]
+    r = run_json(exe, args)
     assert r["scored_again_equal"] == 1
     assert r["level_counts"] == got.level_counts.tolist() and r["n_accepted"] == got.n_accepted and r["origin"] == got.origin.tolist()
     assert len(r["rows"]) == len(got.pose)
     for j, row in enumerate(r["rows"]):
-        s = got.stats[j]
-        assert row["pose"] == _bits(got.pose[j]) and row["H"] == _bits(got.H[j]) and row["b"] == _bits(got.b[j]) and row["active"] == int(got.active[j]), j
-        assert row["counts"] == [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])], j
-        assert row["chi"] == _bits([s["chi_inliers"], s["chi_outliers"]]) and row["digest"] == [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])], j
+        assert row["pose"] == f32_bits(got.pose[j]) and row["H"] == f32_bits(got.H[j]) and row["b"] == f32_bits(got.b[j]) and row["active"] == int(got.active[j]), j
+        assert {key: row[key] for key in ("counts", "chi", "digest")} == stats_json(got.stats[j]), j
     a = r["aligned"]
     assert (a["n_accepted"], a["n_success"]) == (rel.aligned.n_accepted, rel.aligned.n_success) and a["index"] == rel.aligned.index.tolist()
-    assert a["pose"] == [_bits(p) for p in rel.aligned.pose]
+    assert a["pose"] == [f32_bits(p) for p in rel.aligned.pose]

@@ -1,15 +1,13 @@
 """scoreSelect and relocalize of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d.hpp), built with plain g++ and run on the GPU: the selection, its rows
 and the relocalisation's results equal api.score_select / api.relocalize on the same inputs, bit for bit, and every selected row equals the mirror's own
 scoreBatch row (checked inside the driver)."""
-import json
 import math
-import subprocess
 
-import numpy as np
 import pytest
 
 import score_select_cases as cases
 import cpp_build
+from cpp_driver import f32_bits, f32_bits_arg, run_json, stats_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -18,24 +16,13 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("score_select_cpp")
-    exe = cpp_build.build("score_select_driver.cpp", d)
     c = cases.make_cases()
-    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin")
-    return exe, d, c
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
-
-
-def _stats_json(s):
-    return {"counts": [int(s["n_correspondences"]), int(s["n_inliers"]), int(s["n_outliers"])],
-            "chi": _bits([s["chi_inliers"], s["chi_outliers"]]), "digest": [int(s["pair_digest_lo"]), int(s["pair_digest_hi"])]}
+    return cpp_build.build("score_select_driver.cpp", d), write_bins(d, scan=c.scan, map=c.map, poses=c.poses), c
 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_cpp_score_select(ctx, driver, order):
-    exe, d, c = driver
+    exe, f, c = driver
     k = 9
     ctx.set_option("sum_order", order)
     try:
@@ -49,22 +36,19 @@ def test_cpp_score_select(ctx, driver, order):
         rel = api.relocalize(al, c.scan, c.map, c.poses, sel, k)
     finally:
         ctx.set_option("sum_order", 0)
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio]).view(np.uint32)
-    out = subprocess.run([exe] + [str(d / f) for f in ("scan.bin", "map.bin", "poses.bin")] +
-                         [str(cases.COLS), repr(cases.TAU), str(order), str(sel.min_inliers), str(int(thr[0])), str(int(thr[1])), str(k)],
-                         check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [f["scan"], f["map"], f["poses"], cases.COLS, repr(cases.TAU), order, sel.min_inliers, f32_bits_arg(sel.max_chi_per_inlier),
+                       f32_bits_arg(sel.min_inlier_ratio), k])
     assert r["n"] == len(c.poses) and r["rows_equal_score_batch"] == 1 and r["n_empty"] == 0
     assert len(index) == k and n_acc > k      # a selection that is cut at k
     assert r["n_accepted"] == n_acc and r["index"] == index.tolist()
     for j, row in enumerate(r["rows"]):
-        assert row["H"] == _bits(H[j]) and row["b"] == _bits(b[j]), j
-        assert {key: row[key] for key in ("counts", "chi", "digest")} == _stats_json(sst[j]), j
+        assert row["H"] == f32_bits(H[j]) and row["b"] == f32_bits(b[j]), j
+        assert {key: row[key] for key in ("counts", "chi", "digest")} == stats_json(sst[j]), j
     rr = r["relocalize"]
     assert rr["n_accepted"] == rel.n_accepted and rr["index"] == rel.index.tolist() and len(rr["items"]) == len(rel.index)
     last = rel.result.last_stats()
     for j, it in enumerate(rr["items"]):
-        assert it["pose"] == _bits(rel.result.pose[j]) and it["status"] == int(rel.result.status[j]) and it["iterations"] == int(rel.result.iterations[j]), j
+        assert it["pose"] == f32_bits(rel.result.pose[j]) and it["status"] == int(rel.result.status[j]) and it["iterations"] == int(rel.result.iterations[j]), j
         assert it["accepted"] == int(rel.accepted[j]), j
-        assert {key: it[key] for key in ("counts", "chi", "digest")} == _stats_json(last[j]), j
+        assert {key: it[key] for key in ("counts", "chi", "digest")} == stats_json(last[j]), j
     assert any(it["status"] == 0 for it in rr["items"])

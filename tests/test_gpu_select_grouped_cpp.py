@@ -1,9 +1,7 @@
 """The three grouped select calls from C++, built with plain g++ and run on the GPU (tests/cpp/select_grouped_driver.cpp): through the bare C ABI and through
 the host mirror's extension header (srrg2_laser_slam_2d_amd/host/lsm2d_grouped.hpp).  Per group, both routes' counts, indices and every row word equal what
 the Python calls return on the same inputs, bit for bit."""
-import json
 import math
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +9,7 @@ import pytest
 import align_select_cases as cases
 import cpp_build
 import select_grouped_cases as gc
+from cpp_driver import f32_bits_arg, run_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +20,9 @@ K = gc.K_MIXED
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("select_grouped_cpp")
-    exe = cpp_build.build("select_grouped_driver.cpp", d, flags=("-O2", "-pthread"))
     c = cases.make_cases()
-    c.scan.tofile(d / "scan.bin"); c.map.tofile(d / "map.bin"); c.poses.tofile(d / "poses.bin"); gc.offsets(gc.SIZES_MIXED).tofile(d / "groups.bin")
-    return exe, d, c
+    files = write_bins(d, scan=c.scan, map=c.map, poses=c.poses, groups=gc.offsets(gc.SIZES_MIXED))
+    return cpp_build.build("select_grouped_driver.cpp", d, flags=("-O2", "-pthread")), files, c
 
 
 def _words(*parts):
@@ -44,7 +42,7 @@ def _same(blocks, index, n_acc, n_suc, words, tag):
 
 
 def test_cpp_grouped_calls(ctx, driver):
-    exe, d, c = driver
+    exe, f, c = driver
     off = gc.offsets(gc.SIZES_MIXED)
     finder = api.CorrespondenceFinderProjective2f(ctx, api.PointNormal2fProjectorPolar(cases.COLS, -math.pi, math.pi, 0.3, 30.0))
     al = api.MultiAligner2D(ctx, max_iterations=cases.ITERATIONS, min_num_inliers=0)
@@ -63,11 +61,9 @@ def test_cpp_grouped_calls(ctx, driver):
     got = api.align_select_grouped(al, [scan_set], [map_set], c.poses, off, sel, K)
     assert any(len(i) == K for i in got.index) and any(0 < len(i) < K for i in got.index) and np.any(got.n_accepted < got.n_success)
     assert int(s_acc.sum()) > 0 and int(a_acc.sum()) > 0
-    thr = np.float32([sel.max_chi_per_inlier, sel.min_inlier_ratio, sel_score.max_chi_per_inlier, sel_score.min_inlier_ratio]).view(np.uint32)
-    out = subprocess.run([exe] + [str(d / f) for f in ("scan.bin", "map.bin", "poses.bin", "groups.bin")] +
-                         [str(cases.COLS), repr(cases.TAU), str(cases.ITERATIONS), str(al.param_min_num_inliers), str(sel.min_inliers), str(int(thr[0])),
-                          str(int(thr[1])), str(K), str(sel_score.min_inliers), str(int(thr[2])), str(int(thr[3]))], check=True, capture_output=True, text=True, timeout=120).stdout
-    r = json.loads(out)
+    r = run_json(exe, [f["scan"], f["map"], f["poses"], f["groups"], cases.COLS, repr(cases.TAU), cases.ITERATIONS, al.param_min_num_inliers, sel.min_inliers,
+                       f32_bits_arg(sel.max_chi_per_inlier), f32_bits_arg(sel.min_inlier_ratio), K, sel_score.min_inliers, f32_bits_arg(sel_score.max_chi_per_inlier),
+                       f32_bits_arg(sel_score.min_inlier_ratio)])
     G = len(off) - 1
     assert r["n"] == len(c.poses) and r["n_groups"] == G
     s_words = [_words(s_H[g], s_b[g], s_st[g]) for g in range(G)]

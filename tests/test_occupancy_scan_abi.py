@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import cpp_build
 import occupancy_cases as oc
 import occupancy_scan_cases as sc
@@ -33,17 +34,11 @@ def _rays(name):
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------------------------------------
 def test_symbol_struct_and_macros_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    name, n_args = "lsm2d_occupancy_update_scans", 10
-    assert plain.count(name + "(") == 1      # ONE new symbol
-    decl = plain[plain.index(name + "("):]
-    assert decl[:decl.index(");")].count(",") + 1 == n_args
-    assert name in bound and len(bound[name][2]) == n_args and hasattr(lib, name)
-    assert len([s for s in bound if "occupancy" in s or "gridset" in s]) == 8      # 0.7.12's seven and this one
+    name = "lsm2d_occupancy_update_scans"
+    abi_checks.assert_declared_bound_exported(name, 10)
+    header = abi_checks.header()
+    assert re.sub(r"/\*.*?\*/", "", header, flags=re.S).count(name + "(") == 1      # ONE new symbol
+    assert len([s for s in abi_checks.bound_symbols() if "occupancy" in s or "gridset" in s]) == 8      # 0.7.12's seven and this one
     assert "} lsm2d_occupancy_scan_params;" in header and header.index("lsm2d_occupancy_update_scans(") > header.index("int lsm2d_occupancy_render(")
     # the limits are 0.7.12's: no new macro, the number stays
     assert len(re.findall(r"#define LSM2D_OCCUPANCY_\w+", header)) == 4 and "LSM2D_VERSION 160" in header and "0.7.13" in header
@@ -79,23 +74,16 @@ def test_struct_layout_matches_the_c_compiler(tmp_path):
 
 
 def test_kernels_are_in_the_code_object_and_in_the_last_parts():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_occ_beams", b"k_occ_tilesILb1EE", b"k_occ_rays", b"k_occ_tilesILb0EE"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_occ_beams", b"k_occ_tilesILb1EE", b"k_occ_rays", b"k_occ_tilesILb0EE"))
     csrc = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "csrc")
     assert "void k_occ_beams(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read() and "void k_occ_tiles(" in open(os.path.join(csrc, "lsm2d_k_occupancy.h")).read()
     assert 'extern "C" int lsm2d_occupancy_update_scans(' in open(os.path.join(csrc, "lsm2d_capi_occupancy.inc")).read()
 
 
 def test_mirrors_exist():
-    assert callable(api.occupancy_update_scans)
+    abi_checks.assert_mirrors_have("occupancy_update_scans", ("struct OccupancyScanParams", "occupancyUpdateScans(", "lsm2d_occupancy_update_scans("), "lsm2d_occupancy.hpp")
     assert [f.name for f in dataclasses.fields(api.OccupancyScanParams)] == ["n_beams", "angle_min", "angle_max", "range_min", "range_max", "trace_range", "clear_no_return"]
-    host = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host")
-    hpp = open(os.path.join(host, "lsm2d_occupancy.hpp")).read()
-    for text in ("struct OccupancyScanParams", "occupancyUpdateScans(", "lsm2d_occupancy_update_scans("):
-        assert text in hpp, text
-    assert "lsm2d_occupancy" not in open(os.path.join(host, "lsm2d.hpp")).read()
+    assert "lsm2d_occupancy" not in abi_checks.assert_mirrors_have((), ())
 
 
 @pytest.mark.parametrize("source", ["occupancy_scan_ref.cpp", "occupancy_scan_driver.cpp", "occupancy_scan_bench.cpp"])

@@ -1,46 +1,32 @@
 """CPU checks of lsm2d_relocalize_select (ABI 0.7.9): the symbol is declared by include/lsm2d.h, bound by the Python mirror with the right argument count and
 exported by the gfx950 build; the two new kernels are in the library's code object; the Python and C++ mirrors exist and the C++ sources compile; and -- on
 the CPU oracle, no GPU -- the workload and the thresholds the GPU tests use are such that those tests cannot pass vacuously (relocalize_cases)."""
-import ctypes as C
 import dataclasses
-import os
 
 import numpy as np
 import pytest
 
+import abi_checks
 import align_select_cases as ac
 import cpp_build
 import relocalize_cases as rc
-from conftest import ROOT
 
 
 def test_symbol_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    name = "lsm2d_relocalize_select"
-    assert name + "(" in header and "MULTI.json:749-769, :964-986" in header
-    assert name in bound and len(bound[name][2]) == 19
-    assert hasattr(lib, name)
-    assert "LSM2D_VERSION 160" in header and "0.7.9" in header      # an addition only: the number stays
+    abi_checks.assert_declared_bound_exported("lsm2d_relocalize_select", 19)
+    header = abi_checks.header()
+    assert "MULTI.json:749-769, :964-986" in header and "0.7.9" in header
 
 
 def test_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_reloc_items", b"k_align_rows_liveINS_8AlignRow"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_reloc_items", b"k_align_rows_liveINS_8AlignRow"))
 
 
 def test_mirrors_exist():
     from srrg2_laser_slam_2d_amd import api
-    assert callable(api.relocalize_select) and callable(api.relocalize)
+    abi_checks.assert_mirrors_have(("relocalize_select", "relocalize"), ("relocalizeSelect(", "lsm2d_relocalize_select(", '#include "lsm2d.hpp"'), "lsm2d_relocalize.hpp")
     fields = [f.name for f in dataclasses.fields(api.RelocalizeSelectResult)]
     assert fields[:10] == ["scored_index", "scored_stats", "n_scored_accepted", "index", "pose", "information", "iterations", "last_stats", "n_accepted", "n_success"]
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d_relocalize.hpp")).read()
-    for text in ("relocalizeSelect(", "lsm2d_relocalize_select(", '#include "lsm2d.hpp"'):
-        assert text in hpp, text
 
 
 @pytest.mark.parametrize("source", ["relocalize_select_driver.cpp", "relocalize_bench.cpp"])

@@ -4,30 +4,22 @@ score_aligner_cases.combine, a scored item restated in numpy float32 from per-sl
 bit on the inputs the GPU tests use: H, the first statistics row, the digest, the NotEnoughCorrespondences status, and through po.solve_update the pose.
 No tolerance appears in this file."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 import score_aligner_cases as cases
-from conftest import ROOT
 
 NAMES = {"lsm2d_score_aligner_batch": 6, "lsm2d_score_aligner_select": 11}
 
 
 def test_symbols_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    for name, n_args in NAMES.items():
-        assert name + "(" in header
-        assert name in bound and len(bound[name][2]) == n_args and bound[name][1] is C.c_int
-        assert hasattr(lib, name)
+    from srrg2_laser_slam_2d_amd import _capi
+    bound = {name: abi_checks.assert_declared_bound_exported(name, n_args) for name, n_args in NAMES.items()}
+    assert all(b[1] is C.c_int for b in bound.values())
     assert bound["lsm2d_score_aligner_batch"][2][1] == C.POINTER(_capi.Batch)
     assert bound["lsm2d_score_aligner_select"][2][1] == C.POINTER(_capi.Batch) and bound["lsm2d_score_aligner_select"][2][2] == C.POINTER(_capi.SelectParamsC)
-    assert "LSM2D_VERSION 160" in header      # an addition only: the number stays
 
 
 def test_struct_layout():
@@ -40,21 +32,11 @@ def test_struct_layout():
 
 
 def test_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_score_aligner_items", b"k_score_combine", b"k_select_tile_one", b"k_select_keys", b"k_select_gather", b"k_score_partial_batch"):
-        assert k in blob, k
-    out = subprocess.run(["/opt/rocm/llvm/bin/llvm-objdump" if os.path.exists("/opt/rocm/llvm/bin/llvm-objdump") else "objdump", "-h", build.build()],
-                         capture_output=True, text=True).stdout
-    assert ".hip_fatbin" in out
+    abi_checks.assert_kernels_in_code_object((b"k_score_aligner_items", b"k_score_combine", b"k_select_tile_one", b"k_select_keys", b"k_select_gather", b"k_score_partial_batch"))
 
 
 def test_mirrors_have_the_entries():
-    from srrg2_laser_slam_2d_amd import api
-    assert callable(api.score_aligner) and callable(api.score_aligner_select)
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d.hpp")).read()
-    for word in ("scoreAligner(", "scoreAlignerSelect(", "lsm2d_score_aligner_batch(", "lsm2d_score_aligner_select("):
-        assert word in hpp, word
+    abi_checks.assert_mirrors_have(("score_aligner", "score_aligner_select"), ("scoreAligner(", "scoreAlignerSelect(", "lsm2d_score_aligner_batch(", "lsm2d_score_aligner_select("))
 
 
 def test_score_rank_active_rejects_items_without_a_contributing_slice():

@@ -5,12 +5,12 @@ the GPU tests run are such that those tests cannot pass vacuously (score_grid_ca
 import ctypes as C
 import dataclasses
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 import cpp_build
 import score_grid_cases as gc
 from conftest import ROOT
@@ -20,18 +20,11 @@ F32 = np.float32
 
 
 def test_symbol_struct_and_macros_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    name = "lsm2d_score_grid_select"
-    assert name + "(" in header and "} lsm2d_pose_grid;" in header
+    from srrg2_laser_slam_2d_amd import _capi
+    abi_checks.assert_declared_bound_exported("lsm2d_score_grid_select", 20)      # the declaration's parameters, counted: ctx .. out_level_counts
+    header = abi_checks.header()
+    assert "int lsm2d_score_grid_select(" in header and "} lsm2d_pose_grid;" in header and "0.7.10" in header
     assert "#define LSM2D_GRID_MAX_LEVELS 4" in header and "#define LSM2D_GRID_MAX_ITEMS  (1 << 18)" in header
-    assert name in bound and len(bound[name][2]) == 20      # the declaration's parameters, counted: ctx .. out_level_counts
-    decl = header[header.index("int lsm2d_score_grid_select("):]
-    assert re.sub(r"/\*.*?\*/", "", decl[:decl.index(");")], flags=re.S).count(",") + 1 == 20
-    assert hasattr(lib, name)
-    assert "LSM2D_VERSION 160" in header and "0.7.10" in header      # an addition only: the number stays
     assert (_capi.GRID_MAX_LEVELS, _capi.GRID_MAX_ITEMS) == (4, 1 << 18)
 
 
@@ -55,21 +48,16 @@ def test_pose_grid_layout_matches_the_c_compiler(tmp_path):
 
 
 def test_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_grid_level0", b"k_grid_children", b"k_grid_mask_padsINS_7CombRow", b"k_grid_finish"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_grid_level0", b"k_grid_children", b"k_grid_mask_padsINS_7CombRow", b"k_grid_finish"))
 
 
 def test_mirrors_exist():
-    assert callable(api.score_grid_select) and callable(api.relocalize_grid) and callable(api.grid_level_poses)
+    abi_checks.assert_mirrors_have(("score_grid_select", "relocalize_grid", "grid_level_poses"),
+                                   ("scoreGridSelect(", "relocalizeGrid(", "lsm2d_score_grid_select(", '#include "lsm2d.hpp"'), "lsm2d_score_grid.hpp")
     fields = [f.name for f in dataclasses.fields(api.ScoreGridResult)]
     assert fields == ["pose", "origin", "H", "b", "stats", "active", "n_accepted", "level_counts", "kernel_ms"]
     assert [f.name for f in dataclasses.fields(api.PoseGrid)] == ["center", "step", "count", "n_levels", "refine", "k_parents"]
     assert "two" in api.relocalize_grid.__doc__.lower() and "0.4 %" in api.relocalize_grid.__doc__
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d_score_grid.hpp")).read()
-    for text in ("scoreGridSelect(", "relocalizeGrid(", "lsm2d_score_grid_select(", '#include "lsm2d.hpp"'):
-        assert text in hpp, text
 
 
 @pytest.mark.parametrize("source", ["score_grid_driver.cpp", "score_grid_bench.cpp"])

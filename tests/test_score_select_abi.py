@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import score_select_cases as cases
 import cpp_build
 from conftest import ROOT
@@ -18,15 +19,9 @@ NAME = "lsm2d_score_select"
 
 
 def test_score_select_symbol_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, api, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    assert NAME + "(" in header
-    assert NAME in bound
-    assert len(bound[NAME][2]) == 16
-    assert hasattr(lib, NAME)
-    assert "LSM2D_VERSION 160" in header      # an addition only: the number stays
+    from srrg2_laser_slam_2d_amd import _capi, api
+    abi_checks.assert_declared_bound_exported(NAME, 16)
+    header = abi_checks.header()
     m = re.search(r"#define\s+LSM2D_SELECT_MAX_K\s+(\d+)", header)
     assert m and int(m.group(1)) == _capi.SELECT_MAX_K == api.SELECT_MAX_K
     # the tile the tests read: a power of two, at least two selections
@@ -37,10 +32,7 @@ def test_score_select_symbol_declared_bound_and_exported():
 
 
 def test_score_select_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_select_keys", b"k_select_tile", b"k_select_gather"):
-        assert k in blob, k
+    abi_checks.assert_kernels_in_code_object((b"k_select_keys", b"k_select_tile", b"k_select_gather"))
 
 
 def test_select_params_layout_matches_the_c_compiler(tmp_path):
@@ -62,14 +54,10 @@ def test_select_params_layout_matches_the_c_compiler(tmp_path):
 
 def test_mirrors_have_score_select():
     from srrg2_laser_slam_2d_amd import api
-    assert callable(api.score_select) and callable(api.score_rank) and callable(api.relocalize)
+    abi_checks.assert_mirrors_have(("score_select", "score_rank", "relocalize"), ("scoreSelect(", "lsm2d_score_select(", "relocalize("))
     d, r = api.SelectParams(), api.SelectParams.relocalizer()
     assert (d.min_inliers, d.max_chi_per_inlier, d.min_inlier_ratio) == (500, 0.1, 0.8)
     assert (r.min_inliers, r.max_chi_per_inlier, r.min_inlier_ratio) == (700, 0.01, 0.75)
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d.hpp")).read()
-    assert "scoreSelect(" in hpp
-    assert "lsm2d_score_select(" in hpp
-    assert "relocalize(" in hpp
 
 
 def test_cpp_mirror_compiles():

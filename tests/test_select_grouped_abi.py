@@ -3,54 +3,40 @@ declared by include/lsm2d.h, bound by the Python mirror and exported by the gfx9
 code object; the Python and C++ mirrors have their entries and the C++ sources compile; the restatements api.score_rank_grouped / api.align_rank_grouped
 equal a hand loop on hand-made rows; and the group tables the GPU tests use contain every kind of group on the oracle's rows (no GPU), so that the GPU tests
 cannot pass vacuously.  Every comparison is on integers."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
+import abi_checks
 import align_select_cases as acases
 import cpp_build
 import score_select_cases as scases
 import select_grouped_cases as gc
-from conftest import ROOT
 
 NAMES = {"lsm2d_score_select_grouped": 18, "lsm2d_score_aligner_select_grouped": 13, "lsm2d_align_select_grouped": 15}
 
 
 def test_grouped_symbols_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
+    from srrg2_laser_slam_2d_amd import _capi
     for name, n_args in NAMES.items():
-        assert name + "(" in header, name
-        assert name in bound and len(bound[name][2]) == n_args, name
-        assert hasattr(lib, name), name
-    assert "LSM2D_VERSION 160" in header and "0.7.7" in header and "0.7.8" in header      # an addition only: the number stays
+        abi_checks.assert_declared_bound_exported(name, n_args)
+    header = abi_checks.header()
+    assert "0.7.7" in header and "0.7.8" in header
     assert "#define LSM2D_SELECT_MAX_GROUP_ROWS (1 << 18)" in header and _capi.SELECT_MAX_GROUP_ROWS == 1 << 18
 
 
 def test_grouped_kernels_are_in_the_code_object():
-    from srrg2_laser_slam_2d_amd import build
-    blob = open(build.build(), "rb").read()
-    for row in (b"INS_8ScoreRow", b"INS_7CombRow", b"INS_8AlignRow"):
-        for k in (b"k_select_group_one", b"k_select_keys_seg", b"k_select_gather_group"):
-            assert k + row in blob, (k, row)
-    assert b"k_select_tile_seg" in blob
+    abi_checks.assert_kernels_in_code_object([k + row for row in (b"INS_8ScoreRow", b"INS_7CombRow", b"INS_8AlignRow")
+                                              for k in (b"k_select_group_one", b"k_select_keys_seg", b"k_select_gather_group")] + [b"k_select_tile_seg"])
 
 
 def test_mirrors_have_the_grouped_calls():
     from srrg2_laser_slam_2d_amd import api
-    for f in (api.score_select_grouped, api.score_aligner_select_grouped, api.align_select_grouped, api.score_rank_grouped, api.align_rank_grouped):
-        assert callable(f)
+    abi_checks.assert_mirrors_have(("score_select_grouped", "score_aligner_select_grouped", "align_select_grouped", "score_rank_grouped", "align_rank_grouped"),
+                                   ('#include "lsm2d.hpp"', "scoreSelectGrouped(", "scoreAlignerSelectGrouped(", "alignSelectGrouped(") + tuple(n + "(" for n in NAMES),
+                                   "lsm2d_grouped.hpp")
     fields = [f.name for f in __import__("dataclasses").fields(api.AlignSelectGroupedResult)]
     assert fields[:7] == ["index", "pose", "information", "iterations", "last_stats", "n_accepted", "n_success"]
-    host = os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host")
-    grouped = open(os.path.join(host, "lsm2d_grouped.hpp")).read()
-    for text in ('#include "lsm2d.hpp"', "scoreSelectGrouped(", "scoreAlignerSelectGrouped(", "alignSelectGrouped(") + tuple(n + "(" for n in NAMES):
-        assert text in grouped, text
-    assert "_select_grouped" not in open(os.path.join(host, "lsm2d.hpp")).read()      # the first header's set of C calls stays what its stand-in defines
+    assert "_select_grouped" not in abi_checks.assert_mirrors_have((), ())      # the first header's set of C calls stays what its stand-in defines
 
 
 @pytest.mark.parametrize("source", ["select_grouped_driver.cpp", "select_grouped_bench.cpp"])

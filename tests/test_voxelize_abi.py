@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import cpp_build
 import voxelize_cases as vc
 from conftest import ROOT
@@ -22,18 +23,11 @@ T = vc.TILE
 
 
 def test_symbol_struct_and_macros_declared_bound_and_exported():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    header = open(os.path.join(ROOT, "include", "lsm2d.h")).read()
-    bound = {s[0]: s for s in _capi.SYMBOLS}
-    lib = C.CDLL(build.build())
-    name = "lsm2d_voxelize"
-    assert "int " + name + "(" in header and "} lsm2d_voxelize_params;" in header
+    from srrg2_laser_slam_2d_amd import _capi
+    abi_checks.assert_declared_bound_exported("lsm2d_voxelize", 12)
+    header = abi_checks.header()
+    assert "int lsm2d_voxelize(" in header and "} lsm2d_voxelize_params;" in header and "0.7.11" in header
     assert "#define LSM2D_VOXELIZE_MAX_POINTS (1 << 24)" in header and "#define LSM2D_VOXELIZE_MAX_GROUPS (1 << 16)" in header
-    decl = header[header.index("int lsm2d_voxelize("):]
-    assert re.sub(r"/\*.*?\*/", "", decl[:decl.index(");")], flags=re.S).count(",") + 1 == 12
-    assert name in bound and len(bound[name][2]) == 12
-    assert hasattr(lib, name)
-    assert "LSM2D_VERSION 160" in header and "0.7.11" in header      # an addition only: the number stays
     assert (_capi.VOXELIZE_MAX_POINTS, _capi.VOXELIZE_MAX_GROUPS) == (1 << 24, 1 << 16)
     assert _capi.VOXELIZE_MAX_POINTS >= 1 << 24 and _capi.VOXELIZE_MAX_GROUPS >= 1 << 16
     # the reference lines the call restates are cited where it is declared
@@ -59,25 +53,19 @@ def test_params_layout_matches_the_c_compiler(tmp_path):
 
 
 def test_kernels_are_in_the_code_object_and_the_tile_is_the_sources():
-    from srrg2_laser_slam_2d_amd import _capi, build
-    blob = open(build.build(), "rb").read()
-    for k in (b"k_vox_keys", b"k_vox_hist", b"k_vox_scan", b"k_vox_scatter", b"k_vox_head_count", b"k_vox_head_write", b"k_vox_sum", b"k_vox_verdict",
-              b"k_vox_write", b"k_vox_finish"):
-        assert k in blob, k
+    from srrg2_laser_slam_2d_amd import _capi
+    abi_checks.assert_kernels_in_code_object((b"k_vox_keys", b"k_vox_hist", b"k_vox_scan", b"k_vox_scatter", b"k_vox_head_count", b"k_vox_head_write", b"k_vox_sum",
+                                              b"k_vox_verdict", b"k_vox_write", b"k_vox_finish", b"voxelize_tile", b"voxelize_scan_tiles"))
     src = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "csrc", "lsm2d_k_voxelize.h")).read()
     assert int(re.search(r"kVoxTile = (\d+);", src).group(1)) == _capi.VOXELIZE_TILE == T
-    assert b"voxelize_tile" in blob and b"voxelize_scan_tiles" in blob
     block = int(re.search(r"kVoxScanBlock = (\d+);", src).group(1))
     assert "kVoxScanTiles = 4 * kVoxScanBlock / 256;" in src and 4 * block // 256 == _capi.VOXELIZE_SCAN_TILES == vc.SCAN_TILES
 
 
 def test_mirrors_exist():
-    assert callable(api.voxelize)
+    abi_checks.assert_mirrors_have("voxelize", ("voxelize(", "lsm2d_voxelize(", '#include "lsm2d.hpp"'), "lsm2d_voxelize.hpp")
     assert [f.name for f in dataclasses.fields(api.VoxelizeParams)] == ["resolution", "normal_resolution"]
     assert api.VoxelizeParams.clipper(0.05).normal_resolution == 0.1 and api.VoxelizeParams.preprocessor(0.05).normal_resolution == 1.0
-    hpp = open(os.path.join(ROOT, "srrg2_laser_slam_2d_amd", "host", "lsm2d_voxelize.hpp")).read()
-    for text in ("voxelize(", "lsm2d_voxelize(", '#include "lsm2d.hpp"'):
-        assert text in hpp, text
 
 
 @pytest.mark.parametrize("source", ["voxelize_driver.cpp", "voxelize_bench.cpp", "voxelize_ref.cpp"])
